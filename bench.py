@@ -32,11 +32,9 @@ import time
 
 import numpy as np
 
-# Six renders in flight want six hardware queues for their streams, and the runtime makes GPU_MAX_HW_QUEUES per stream priority level
-# -- four unless told otherwise at the process's FIRST HIP call, which in this program is torch's.  So the variable is set here, before
-# torch is imported (never over a value the caller exported); the library measures whether it took and falls back to four renders in
-# flight if not (the line reports both under "config").
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "6")
+# The number of hardware queues per stream priority level (GPU_MAX_HW_QUEUES, read at the process's first HIP call) is the
+# caller's to export and is not set here: the library measures whether six of its streams run side by side and keeps four renders
+# in flight if not (the line reports both under "config").
 # dmabuf IPC: RCCL between processes (and CUDA-tensor sharing) needs it on this pool's driver -- `hipIpcGetMemHandle: invalid argument`
 # without it.  Set here, at the top of the file, so that the ranks the DRIVER starts with `python -m torch.distributed.run ... bench.py`
 # get it too, not only the ones self_launch() starts (never over a value the caller exported).
@@ -63,6 +61,34 @@ def rel_l2(a, b):
     a = a[..., :3].astype(np.float64)
     b = b[..., :3].astype(np.float64)
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+DUMP_BUDGET_BYTES = 64_000_000   # --dump-outputs: all files together
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, images):
+    """--dump-outputs DIR: the images the timed path's last step left for its caller, {name: (H, W, ...) array}, written as
+    DIR/<name>.npy in float32 (float64 arrays stay float64).  When they do not fit in DUMP_BUDGET_BYTES together, every image is
+    cut to the same fixed, seeded sample of pixels -- (n, channels) arrays in increasing pixel order -- and the flat pixel indices
+    (y * W + x) are written as DIR/pixel_index.npy (float64, exact).  Returns what the result line reports about it."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {k: np.asarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in images.items()}
+    h, w = next(iter(arrs.values())).shape[:2]
+    n_pixels = h * w
+    full = sum(a.nbytes for a in arrs.values())
+    sampled = None
+    if full > DUMP_BUDGET_BYTES:
+        per_pixel = full // n_pixels + 8   # (+ its index)
+        k = min(n_pixels, (DUMP_BUDGET_BYTES - 4096) // per_pixel)   # (room for the .npy headers)
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, size=k, replace=False))
+        arrs = {name: a.reshape(n_pixels, -1)[idx] for name, a in arrs.items()}
+        arrs["pixel_index"] = idx.astype(np.float64)
+        sampled = int(k)
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrs), "bytes": int(sum(a.nbytes for a in arrs.values())),
+            "image": [h, w], "sampled_pixels": sampled, "sample_seed": DUMP_SEED if sampled is not None else None}
 
 
 def self_launch(n):
@@ -123,7 +149,7 @@ def main_multi(args):
         for d in sorted(set(devices)):
             torch.cuda.synchronize(d)
 
-    def leg(w, h, spp, bounces, steps, warmup):
+    def leg(w, h, spp, bounces, steps, warmup, dump=None):
         cam = scenes.camera_block(sc.camera, w, h)
         m.set_params(w, h, bounces, accum_mode)
         m.set_camera(cam)
@@ -150,6 +176,7 @@ def main_multi(args):
         elapsed = time.perf_counter() - t0
         plan = m.gather_plan()
         got = m.read_ldr() if args.gather == "ldr" else m.read_accum()
+        dumped = dump_outputs(dump, {"accum": m.read_accum(), "ldr": m.read_ldr()}) if dump else None   # (the assembled images)
         solo = host.Context(devices[0])
         solo.build_scene(sc, builder)
         solo.set_params(w, h, bounces, accum_mode)
@@ -158,10 +185,12 @@ def main_multi(args):
         same = bool(np.array_equal(got, solo.read_ldr() if args.gather == "ldr" else solo.read_accum()))
         solo.close()
         return dict(rays_per_step=rays, steps=steps, ms_per_step=round(elapsed / steps * 1e3, 4), value=round(rays * steps / elapsed / 1e6, 3),
-                    verified_bit_identical_to_one_context=same, gather_plan=plan)
+                    verified_bit_identical_to_one_context=same, gather_plan=plan, dump_outputs=dumped)
 
-    c3 = leg(args.width, args.height, args.spp, args.bounces, args.steps, args.warmup)
+    c3 = leg(args.width, args.height, args.spp, args.bounces, args.steps, args.warmup, dump=args.dump_outputs)
+    dumped = c3.pop("dump_outputs")
     c5 = leg(3840, 2160, 16, 6, max(5, args.steps // 5), 2)
+    c5.pop("dump_outputs")
     c5["workload"] = "C5: the same scene at 3840x2160, 16 spp, 6 bounces"
     out = {
         "metric": "Mrays/sec at 1920x1080, 8 spp, 4 bounces", "value": c3["value"], "unit": "Mrays/s", "n_gpus": n, "steps": args.steps,
@@ -180,6 +209,8 @@ def main_multi(args):
                       "note": "ranks share a device when the box has fewer GPUs than ranks: a rehearsal of the protocol, not a link rate"
                               if len(set(devices)) < n else "one device per rank"},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     print(json.dumps(out))
     m.close()
     ok = c3["verified_bit_identical_to_one_context"] and c5["verified_bit_identical_to_one_context"]
@@ -239,7 +270,13 @@ def main():
                     help="per-launch HBM bytes of each kernel from the committed rocprofv3 --pmc passes (tools/pmc.sh)")
     ap.add_argument("--sq-json", default=os.path.join(ROOT, "profiles", "current_sq.json"),
                     help="per-launch SQ counters of each kernel from the committed rocprofv3 --pmc passes (tools/diag.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed -- the images a caller of the timed path reads back -- as "
+                         "DIR/<name>.npy (float32; a fixed, seeded pixel sample when larger than 64 MB in all), for output-by-output "
+                         "comparison of two builds: the inputs depend on the arguments alone")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` on its own (no torch.distributed.run around it, WORLD_SIZE unset): start the per-GPU
     # processes ourselves.  A CHILD process (never exec: nothing in this process may have touched the GPU, and nothing has --
@@ -489,6 +526,18 @@ def main():
     elapsed = timed(args.steps)
     renders_in_flight = ctx.renders_in_flight()   # 6 where six of the library's streams run side by side, else 4
     gpu_image = ctx.read_accum() if (world == 1 and rank == 0) else None   # the image the timed region left behind (parity)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's images as a caller reads them back; under torch.distributed the assembled one (the gathered kind)
+        if not use_dist:
+            images = {"accum": gpu_image, "ldr": ctx.read_ldr()}
+            if args.depth:
+                images["depth"] = ctx.read_depth()
+        elif args.gather == "ldr":
+            images = {"ldr": ctx.read_ldr()}
+        else:
+            images = {"accum": ctx.read_accum()}
+        dumped = dump_outputs(args.dump_outputs, images)
     verified = None
     if (args.verify or use_dist) and rank == 0:   # N > 1: always -- the assembled image of the last timed step against one context's
         got = ctx.read_ldr() if (use_dist and args.gather == "ldr") else ctx.read_accum()
@@ -932,6 +981,8 @@ def main():
                                         "the timed regions queue steps back to back, so ms_per_step is below their sum")
         if verified is not None:
             out["verified_bit_identical_to_one_context"] = verified
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             from oracle import binding as ob
             t0 = time.perf_counter()

@@ -10,9 +10,7 @@ import os
 import subprocess
 
 # the library keeps six renders in flight where six of its streams get a hardware queue each: GPU_MAX_HW_QUEUES (per stream priority
-# level, four by default) is read by the HIP runtime at the process's first HIP call -- set here, before this module's users can have
-# made one through the library, never over a value the caller exported (jpt.h, jpt_create)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "6")
+# level) is read by the HIP runtime at the process's first HIP call and is the host's to export; it is not set here (jpt.h, jpt_create)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("JPT_LIB", os.path.join(_HERE, "libjpt_hip.so"))  # JPT_LIB: A/B builds (tools/ab.sh)

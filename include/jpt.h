@@ -173,9 +173,9 @@ int jpt_get_stream(jpt_ctx *ctx, void **hip_stream);
  * Six renders in flight are worth 4 % on a 1920x1080x8-spp render and 15 % on small ones when the slots' six streams get a queue
  * each, and cost as much when they have to share four.  PROCESS ENVIRONMENT: the library never writes it (a setenv from a
  * shared library races with every getenv of a multi-threaded host and changes the queue count for all other HIP users of the
- * process).  A host that wants six renders in flight exports GPU_MAX_HW_QUEUES=6 itself, before its first HIP call and before it
- * starts threads (bench.py and the Python binding do, with os.environ.setdefault at import; six, not more: with eight a SECOND
- * context's streams pair up on some queues and it renders a third slower).  Every context MEASURES, before its first queued
+ * process).  A host that wants six renders in flight exports a pool of six queues per level (GPU_MAX_HW_QUEUES) itself, before its
+ * first HIP call and before it starts threads (bench.py and the Python binding leave it to their caller; six, not more: with eight
+ * a SECOND context's streams pair up on some queues and it renders a third slower).  Every context MEASURES, before its first queued
  * render, whether six of its streams run side by side (~1 ms) -- six slots if they do, four if not: a host that exports nothing
  * gets four, which is also all that one blocking render per displayed frame (the addon's use) can ever use.
  * jpt_renders_in_flight: the slots the last queued render was dealt among (0 before the first).
@@ -513,7 +513,7 @@ const char *jpt_debug_last_error(void);
  *   JPT_LIB                   --        (Python binding only) path of the library to load instead of gdpathtracing_amd/libjpt_hip.so
  *
  * The HOST may want to export, before its first HIP call (see jpt_set_stream_priority above):
- *   GPU_MAX_HW_QUEUES=6             six renders in flight instead of four for queued renders (the HIP runtime's variable)
+ *   GPU_MAX_HW_QUEUES               a pool of six per level: six renders in flight instead of four for queued renders (the HIP runtime's variable)
  *   HSA_ENABLE_IPC_MODE_LEGACY=0    multi-process runs (RCCL between ranks) on drivers that only support dmabuf IPC
  */
 

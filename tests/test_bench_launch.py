@@ -21,3 +21,40 @@ def test_gpus_n_without_world_size_starts_torchrun_as_a_child():
     assert "needs torch.distributed.run" not in p.stderr            # round 3's refusal is gone
     assert p.stderr.count("bench.py needs a GPU") >= 2, p.stderr[-2000:]   # both ranks ran bench.py's main
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: images that fit are written whole in float32; larger ones are cut to one seeded pixel sample, the same
+    for every image and from run to run, with its flat indices, and everything written stays within 64 MB."""
+    code = r'''
+import sys, json, numpy as np
+sys.path.insert(0, %r)
+import bench
+d = sys.argv[1]
+rng = np.random.default_rng(5)
+small = {"accum": rng.random((9, 16, 4), dtype=np.float32), "ldr": rng.integers(0, 256, (9, 16, 4)).astype(np.uint8)}
+print(json.dumps(bench.dump_outputs(d + "/small", small)))
+big = {"accum": rng.random((1080, 1920, 4), dtype=np.float32), "ldr": rng.integers(0, 256, (1080, 1920, 4)).astype(np.uint8)}
+np.save(d + "/big_accum_src.npy", big["accum"]); np.save(d + "/big_ldr_src.npy", big["ldr"])
+print(json.dumps(bench.dump_outputs(d + "/big", big)))
+print(json.dumps(bench.dump_outputs(d + "/big2", big)))
+''' % ROOT
+    p = subprocess.run([sys.executable, "-c", code, str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    import json
+    import numpy as np
+    small, big, big2 = (json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{"))
+    assert small["sampled_pixels"] is None and small["files"] == ["accum.npy", "ldr.npy"]
+    a = np.load(tmp_path / "small" / "accum.npy")
+    ldr = np.load(tmp_path / "small" / "ldr.npy")
+    assert a.dtype == np.float32 and a.shape == (9, 16, 4) and ldr.dtype == np.float32 and ldr.shape == (9, 16, 4)
+    assert big["sampled_pixels"] and big["files"] == ["accum.npy", "ldr.npy", "pixel_index.npy"]
+    total = sum(os.path.getsize(tmp_path / "big" / f) for f in big["files"])
+    assert big["bytes"] <= 64_000_000 and total <= 64_000_000
+    idx = np.load(tmp_path / "big" / "pixel_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and idx[-1] < 1080 * 1920
+    k = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "big" / "accum.npy"), np.load(tmp_path / "big_accum_src.npy").reshape(-1, 4)[k])
+    assert np.array_equal(np.load(tmp_path / "big" / "ldr.npy"), np.load(tmp_path / "big_ldr_src.npy").reshape(-1, 4)[k].astype(np.float32))
+    for f in big["files"]:
+        assert np.array_equal(np.load(tmp_path / "big" / f), np.load(tmp_path / "big2" / f))

@@ -1,6 +1,5 @@
 # where the first queued renders of a context spend their time: each render is queued and then waited for
 import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from gdpathtracing_amd import capi, host, scenes
 sc = scenes.demo_scene(51200)

@@ -4,4 +4,4 @@ cd "$GRAFT_REPO_ROOT"
 export FUZZ_FROM=${1:-6372} FUZZ_TO=${2:-6872}
 echo -n "default (six renders in flight where the queues allow): "; python tests/tools/fuzz_more.py 2>&1 | grep "MISMATCH\|extended fuzz done"
 echo -n "JPT_SIX_SLOTS=0: "; JPT_SIX_SLOTS=0 python tests/tools/fuzz_more.py 2>&1 | grep "MISMATCH\|extended fuzz done"
-echo -n "JPT_PIPE_SLOTS=8 GPU_MAX_HW_QUEUES=8: "; JPT_PIPE_SLOTS=8 GPU_MAX_HW_QUEUES=8 python tests/tools/fuzz_more.py 2>&1 | grep "MISMATCH\|extended fuzz done"
+echo -n "JPT_PIPE_SLOTS=8: "; JPT_PIPE_SLOTS=8 python tests/tools/fuzz_more.py 2>&1 | grep "MISMATCH\|extended fuzz done"

@@ -1,6 +1,5 @@
 # Is one of the hardware queues slower on its own?  Activates eight streams in order and times a blocking render on each.
 import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 os.environ["JPT_PIPELINE"] = "0"; os.environ["JPT_GROUPS"] = "1"
 import ctypes as C
 from gdpathtracing_amd import capi, host, scenes

@@ -1,7 +1,6 @@
 # An animation loop on the instanced scene (1 026 instances): every step moves all instances and renders once.
 # Host route (jpt_scene_set_instance_transform x n + jpt_scene_update_tlas) against the device refit (jpt_scene_refit_tlas).
 import os, sys, time; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np
 from gdpathtracing_amd import capi, host, scenes
 sc = scenes.instanced_scene()
