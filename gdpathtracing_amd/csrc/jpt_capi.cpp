@@ -50,13 +50,23 @@ struct DevBuf {
     }
 };
 
+// One render in flight (jpt_render_async): its stream, its workspace and the events that order it.  Slot 0's workspace is
+// also the one renders on the context's own stream use.
+struct PipeSlot {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_paths_done = nullptr, ev_acc_done = nullptr;
+    bool acc_done_valid = false;   // ev_acc_done follows the last accumulation that read `workspace`
+    uint64_t refit_seen = 0;       // the refit (jpt_ctx::refit_wait_seq) the slot's stream has last waited for
+    DevBuf<char> workspace;
+};
+
 }  // namespace
 
 struct jpt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Wf2Async async;  // helper streams / events of the frame groups (launch_wf2_render)
+    Wf2Streams group_streams;  // helper streams / events of the frame groups (launch_wf2_render)
     std::string error;
 
     // host scene
@@ -112,19 +122,15 @@ struct jpt_ctx {
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
     bool depth_valid = false;              // d_depth holds the last render's depth image
-    DevBuf<char> d_workspace;
-    // render pipelining (jpt_render_async): consecutive asynchronous renders run their path kernels on two helper
-    // streams with two workspaces, so one render's launch tails overlap the next render's kernels; the accumulation
-    // kernels stay on the context's stream, in order
+    // render pipelining (jpt_render_async): consecutive asynchronous renders run their path kernels on the slots' streams
+    // with their own workspaces, so one render's launch tails overlap the next render's kernels; the accumulation
+    // kernels are ordered on the context's stream
     static constexpr int kPipeSlots = 8;   // the most; the rule is 4, or 6 where six of the slots' streams run side by side (six_queues_probe)
+    PipeSlot slot[kPipeSlots];
     int six_queues = -1;                   // -1: not probed yet; 0 / 1
     int last_pipe_slots = 0;               // jpt_renders_in_flight
-    bool aux_borrowed[3] = {};             // async.aux_stream[k] is pipe_stream[k] (ensure_group_streams): not destroyed on its own
-    DevBuf<char> d_workspace_more[kPipeSlots - 1];  // slot 0 is d_workspace
-    hipStream_t pipe_stream[kPipeSlots] = {};
+    bool aux_borrowed[kMaxGroups - 1] = {};   // group_streams.aux_stream[k] is slot[k].stream (ensure_group_streams): not destroyed on its own
     uint64_t async_seq = 0;
-    hipEvent_t ev_paths_done[kPipeSlots] = {}, ev_acc_done[kPipeSlots] = {};
-    bool acc_done_valid[kPipeSlots] = {};
     std::vector<uint32_t> h_qcount;  // per-bounce queue sizes of the last wavefront render
     std::vector<hipEvent_t> trace_events;  // pairs around each wf_trace launch of the last render
     int32_t trace_events_used = 0;
@@ -173,8 +179,8 @@ struct jpt_ctx {
     hipStream_t refit_stream = nullptr;
     hipEvent_t ev_set_retired[kInstanceSets] = {}, ev_refit_done = nullptr;
     bool set_retired_valid[kInstanceSets] = {};
-    uint64_t refit_wait_seq = 0, slot_refit_seen[kPipeSlots] = {};
-    int idle_streak = 0;   // queued renders in a row that found nothing in flight (do_render_batch)
+    uint64_t refit_wait_seq = 0;
+    int idle_streak = 0;   // queued renders in a row that found nothing in flight (plan_launch)
     DevBuf<uint32_t> d_tlas4_order, d_tlas4_levels;
     uint32_t n_tlas4_levels = 0;
     bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
@@ -608,6 +614,22 @@ int32_t frames_per_batch(const jpt_ctx* c, int32_t n_frames)
     return (int32_t)std::min<size_t>((size_t)n_frames, fit);
 }
 
+// the statistics a blocking render in batches sums over its batches, f(a's field, b's field); the others are its last batch's
+template <typename F>
+void summed_stats(jpt_stats& a, const jpt_stats& b, F f)
+{
+    f(a.rays, b.rays);
+    f(a.blas_expand, b.blas_expand);
+    f(a.tri_tests, b.tri_tests);
+    f(a.tlas_expand, b.tlas_expand);
+    f(a.inst_visits, b.inst_visits);
+    f(a.shaded_hits, b.shaded_hits);
+    f(a.last_render_ms, b.last_render_ms);
+    f(a.last_trace_ms, b.last_trace_ms);
+    f(a.set_aside, b.set_aside);
+    f(a.set_aside_dropped, b.set_aside_dropped);
+}
+
 int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
 {
     if (!c) return JPT_E_INVALID;
@@ -639,27 +661,9 @@ int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool cou
         const int32_t nb = std::min(per, n_frames - done);
         const int rc = do_render_batch(c, nb, first_frame_index + (uint32_t)done, counted, true);
         if (rc != JPT_OK) return rc;
-        sum.rays += c->stats.rays;
-        sum.blas_expand += c->stats.blas_expand;
-        sum.tri_tests += c->stats.tri_tests;
-        sum.tlas_expand += c->stats.tlas_expand;
-        sum.inst_visits += c->stats.inst_visits;
-        sum.shaded_hits += c->stats.shaded_hits;
-        sum.last_render_ms += c->stats.last_render_ms;
-        sum.last_trace_ms += c->stats.last_trace_ms;
-        sum.set_aside += c->stats.set_aside;
-        sum.set_aside_dropped += c->stats.set_aside_dropped;
+        summed_stats(sum, c->stats, [](auto& a, auto b) { a += b; });
     }
-    c->stats.rays = sum.rays;
-    c->stats.blas_expand = sum.blas_expand;
-    c->stats.tri_tests = sum.tri_tests;
-    c->stats.tlas_expand = sum.tlas_expand;
-    c->stats.inst_visits = sum.inst_visits;
-    c->stats.shaded_hits = sum.shaded_hits;
-    c->stats.last_render_ms = sum.last_render_ms;
-    c->stats.last_trace_ms = sum.last_trace_ms;
-    c->stats.set_aside = sum.set_aside;
-    c->stats.set_aside_dropped = sum.set_aside_dropped;
+    summed_stats(c->stats, sum, [](auto& a, auto b) { a = b; });
     return JPT_OK;
 }
 
@@ -670,17 +674,19 @@ int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool cou
 // rate of queued renders depended on which streams happened to share a queue (round 1, C3: 1.32 ms per render with the
 // most fortunate order, 1.60 and 2.39 with others); the pipeline slots now take their queues from the highest priority
 // level's pool (ensure_pipe_slot below), and so do the helper streams of frame groups (round 5: below).
-bool ensure_pipe_slot(jpt_ctx* c, int slot);
-// frame groups: `groups - 1` helper streams (launch_wf2_render); false = not available, renders run serially
-bool ensure_group_streams(jpt_ctx* c, int groups)
+bool ensure_pipe_slot(jpt_ctx* c, int k);
+// frame groups: up to `groups - 1` helper streams (launch_wf2_render); returns how many there are, in order (0: one group)
+int ensure_group_streams(jpt_ctx* c, int groups)
 {
-    if (!c->async.fork && hipEventCreateWithFlags(&c->async.fork, hipEventDisableTiming) != hipSuccess) {
-        c->async.fork = nullptr;
+    Wf2Streams& gs = c->group_streams;
+    if (!gs.fork && hipEventCreateWithFlags(&gs.fork, hipEventDisableTiming) != hipSuccess) {
+        gs.fork = nullptr;
         (void)hipGetLastError();
-        return false;
+        return 0;
     }
-    for (int k = 0; k + 1 < groups && k < 3; k++) {
-        if (!c->async.aux_stream[k]) {
+    int k = 0;
+    for (; k + 1 < groups && k < kMaxGroups - 1; k++) {
+        if (!gs.aux_stream[k]) {
             // The helper stream of group k + 1 IS pipeline slot k's stream (highest priority level by default, ensure_pipe_slot), not a
             // stream of its own at the context stream's level: the normal level's queues are dealt in the order of first use among ALL
             // the process's streams, and a helper that lands on the context stream's queue runs its group AFTER group 0 instead of
@@ -691,29 +697,30 @@ bool ensure_group_streams(jpt_ctx* c, int groups)
             // slot still holds.  (Normal / low slot priority chosen by the host: a stream of its own, as before.)
             const bool borrow = c->slot_priority != JPT_STREAM_PRIORITY_NORMAL && c->slot_priority != JPT_STREAM_PRIORITY_LOW;
             if (borrow) {
-                if (!ensure_pipe_slot(c, k)) return false;
-                c->async.aux_stream[k] = c->pipe_stream[k];
+                if (!ensure_pipe_slot(c, k)) break;
+                gs.aux_stream[k] = c->slot[k].stream;
                 c->aux_borrowed[k] = true;
-            } else if (hipStreamCreateWithFlags(&c->async.aux_stream[k], hipStreamNonBlocking) != hipSuccess) {
-                c->async.aux_stream[k] = nullptr;
+            } else if (hipStreamCreateWithFlags(&gs.aux_stream[k], hipStreamNonBlocking) != hipSuccess) {
+                gs.aux_stream[k] = nullptr;
                 (void)hipGetLastError();
-                return false;
+                break;
             }
         }
-        if (!c->async.join[k] && hipEventCreateWithFlags(&c->async.join[k], hipEventDisableTiming) != hipSuccess) {
-            c->async.join[k] = nullptr;
+        if (!gs.join[k] && hipEventCreateWithFlags(&gs.join[k], hipEventDisableTiming) != hipSuccess) {
+            gs.join[k] = nullptr;
             (void)hipGetLastError();
-            return false;
+            break;
         }
     }
-    return true;
+    return k;
 }
-// render pipelining: stream + two events of slot `slot`
-bool ensure_pipe_slot(jpt_ctx* c, int slot)
+// render pipelining: stream + two events of slot k
+bool ensure_pipe_slot(jpt_ctx* c, int k)
 {
-    if (c->pipe_stream[slot] && c->ev_paths_done[slot] && c->ev_acc_done[slot]) return true;
+    PipeSlot& ps = c->slot[k];
+    if (ps.stream && ps.ev_paths_done && ps.ev_acc_done) return true;
     bool ok = true;
-    if (!c->pipe_stream[slot]) {
+    if (!ps.stream) {
         // Streams of different PRIORITY levels take their hardware queues from different pools (three levels on this
         // device, GPU_MAX_HW_QUEUES queues each).  The slots' four streams are created at the HIGHEST level: they have that
         // level's pool to themselves -- the host's streams, torch's, RCCL's and this library's own helper streams are all
@@ -726,12 +733,12 @@ bool ensure_pipe_slot(jpt_ctx* c, int slot)
         // (the embedding application decides per context with jpt_set_stream_priority; the default is the highest level)
         const bool normal = c->slot_priority == JPT_STREAM_PRIORITY_NORMAL, low = c->slot_priority == JPT_STREAM_PRIORITY_LOW;
         if (!normal && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least > greatest)
-            ok = hipStreamCreateWithPriority(&c->pipe_stream[slot], hipStreamNonBlocking, low ? least : greatest) == hipSuccess;
+            ok = hipStreamCreateWithPriority(&ps.stream, hipStreamNonBlocking, low ? least : greatest) == hipSuccess;
         else
-            ok = hipStreamCreateWithFlags(&c->pipe_stream[slot], hipStreamNonBlocking) == hipSuccess;
+            ok = hipStreamCreateWithFlags(&ps.stream, hipStreamNonBlocking) == hipSuccess;
     }
-    if (ok && !c->ev_paths_done[slot]) ok = hipEventCreateWithFlags(&c->ev_paths_done[slot], hipEventDisableTiming) == hipSuccess;
-    if (ok && !c->ev_acc_done[slot]) ok = hipEventCreateWithFlags(&c->ev_acc_done[slot], hipEventDisableTiming) == hipSuccess;
+    if (ok && !ps.ev_paths_done) ok = hipEventCreateWithFlags(&ps.ev_paths_done, hipEventDisableTiming) == hipSuccess;
+    if (ok && !ps.ev_acc_done) ok = hipEventCreateWithFlags(&ps.ev_acc_done, hipEventDisableTiming) == hipSuccess;
     if (!ok) (void)hipGetLastError();
     return ok;
 }
@@ -756,15 +763,15 @@ bool six_queues_probe(jpt_ctx* c)
         return false;
     }
     const long long ticks = (long long)khz * 400 / 1000;   // 0.4 ms
-    for (int k = 0; k < kProbe; k++) launch_queue_spin(c->pipe_stream[k], 1);   // (the module is loaded, the queues exist)
+    for (int k = 0; k < kProbe; k++) launch_queue_spin(c->slot[k].stream, 1);   // (the module is loaded, the queues exist)
     for (int k = 0; k < kProbe; k++)
-        if (hipStreamSynchronize(c->pipe_stream[k]) != hipSuccess) return false;
+        if (hipStreamSynchronize(c->slot[k].stream) != hipSuccess) return false;
     double best = 1e9;
     for (int rep = 0; rep < 2; rep++) {   // the better of two: a host hiccup can only make it look serial
         const auto t0 = std::chrono::steady_clock::now();
-        for (int k = 0; k < kProbe; k++) launch_queue_spin(c->pipe_stream[k], ticks);
+        for (int k = 0; k < kProbe; k++) launch_queue_spin(c->slot[k].stream, ticks);
         for (int k = 0; k < kProbe; k++)
-            if (hipStreamSynchronize(c->pipe_stream[k]) != hipSuccess) return false;
+            if (hipStreamSynchronize(c->slot[k].stream) != hipSuccess) return false;
         best = std::min(best, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     }
     if (hipGetLastError() != hipSuccess) return false;
@@ -772,7 +779,130 @@ bool six_queues_probe(jpt_ctx* c)
     return c->six_queues != 0;
 }
 
-int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
+// the event the last render left on the context's stream has completed: nothing of this context is in flight
+bool pipeline_idle(jpt_ctx* c)
+{
+    const bool idle = hipEventQuery(c->ev1) == hipSuccess;
+    (void)hipGetLastError();   // (hipErrorNotReady is an answer, not an error)
+    return idle;
+}
+
+// The launch shape of one render: where it runs, in how many frame groups, with how many segments per tracing block.
+struct LaunchPlan {
+    enum Route { kReference, kStream, kSlot } route = kReference;   // the reference-layout kernel / the context's stream / a pipeline slot
+    int slot = 0, slots = 0;    // kSlot: the slot, and how many there are
+    int groups = 1;             // frame groups (launch_wf2_render)
+    int chain = 1;              // wf2_trace: consecutive segments per block
+};
+// What plan_launch asks of the device, each only where a rule reaches it (their side effects are part of the rules).
+struct PlanDevice {
+    bool (*six_queues)(jpt_ctx*);                // six of the slots' streams run side by side (six_queues_probe)
+    bool (*idle)(jpt_ctx*);                      // nothing of this context is in flight (pipeline_idle)
+    bool (*slot_stream)(jpt_ctx*, int slot);     // the slot's stream and events exist, made if need be (ensure_pipe_slot)
+    int (*group_streams)(jpt_ctx*, int groups);  // helper streams there are for `groups` frame groups (ensure_group_streams)
+};
+const PlanDevice kPlanDevice{six_queues_probe, pipeline_idle, ensure_pipe_slot, ensure_group_streams};
+
+// Every rule of a render's launch shape, in one place.  Makes no HIP call of its own; keeps c->last_pipe_slots and
+// c->idle_streak.  fp: the render's frame_params; cull: its sky cull.
+LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, bool counted, bool blocking, const PlanDevice& dev)
+{
+    LaunchPlan p;
+    if (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps) return p;   // (DEBUG_STEPS exists in the audit kernel only)
+    const bool timed = c->kernel_timing;   // per-launch events want the launches of a render one after another
+    // renders in flight (JPT_PIPE_SLOTS overrides): a render is eleven dependent launches of >= 25-30 us each
+    // however little work it holds, so several of them are needed to fill the chip
+    const int env_slots = tuning().pipe_slots;   // (after the embedding application's cap, jpt_set_memory_policy)
+    const int forced_slots = c->max_slots > 0 ? c->max_slots : (env_slots <= 0 ? 0 : std::min(std::max(env_slots, 2), (int)jpt_ctx::kPipeSlots));
+    // Four renders in flight, each tracing with a quarter of the blocks (four consecutive segments per block: a
+    // deeper queue keeps a block's lanes refilled for a larger share of its launch) beat two renders of full-width
+    // launches on every size tried: C3 1.32 vs 1.45 ms, C2 0.36 vs 0.46, 1 frame 0.30 vs 0.37, 1920x136 0.185 vs
+    // 0.193, 4K x 16 spp 11.1 vs 11.1.  Renders whose workspace exceeds 24 GiB keep two slots and full-width launches
+    // (4 x 24 GiB of workspaces is where this stops).
+    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces) > ((size_t)24 << 30);
+    // ... six where the slots' streams have six hardware queues to themselves (six_queues_probe), four otherwise
+    const bool may_queue = tuning().pipelining && !blocking && !counted;
+    const int slots = forced_slots ? forced_slots : (huge ? 2 : ((may_queue && dev.six_queues(c)) ? 6 : 4));
+    if (may_queue) c->last_pipe_slots = slots;
+    // A host that queues ONE render at a time (jpt_render_async, its own work, jpt_sync or the split read-back, again)
+    // never has a second render in flight: the pipelined form's quarter-width launches then run alone, and a render takes
+    // half as long again as a blocking one (C3 1.93 against 1.26 ms, 3840 x 2160 x 4 spp 3.33 against 2.11:
+    // tools/lone_async_probe.py).  The third queued render in a row that finds nothing in flight -- the event every render
+    // leaves on the context's stream has completed -- is launched like a blocking one instead (frame groups, full-width
+    // launches; nobody waits for it here), and so on until a render finds work in flight.  A queue of renders is not
+    // affected: only its first render finds the pipeline empty.
+    bool lone = false;
+    if (may_queue && !timed) {
+        c->idle_streak = dev.idle(c) ? c->idle_streak + 1 : 0;
+        lone = c->idle_streak >= 3;
+    }
+    const int slot = (int)(c->async_seq % (uint64_t)slots);
+    if (may_queue && !timed && !lone && dev.slot_stream(c, slot)) {
+        // (one frame group: overlapping with the neighbouring render does what groups do, without extra launches:
+        // 3840x2160x16 spp 11.56 ms against 11.96 with two groups, instanced scene 3.80 against 4.05)
+        p.route = LaunchPlan::kSlot;
+        p.slot = slot;
+        p.slots = slots;
+        p.chain = (huge || slots == 1) ? 1 : 4;   // (a single render in flight: full-width launches)
+        return p;
+    }
+    p.route = LaunchPlan::kStream;
+    // Frame groups.  Every launch of the pipeline ends with a tail: a few long rays in a few waves while the rest of the
+    // chip has nothing left to do (a ray's latency under full load is ~20 us on average, ~100 us for the longest; C3's ten
+    // launch boundaries cost 0.5 ms of 1.85 -- render time is 0.48 + 0.17 * spp ms).  Balancing the queues does not
+    // help (tried: equal ray counts per block, same time) and neither does fusing the bounce loop into one persistent
+    // kernel (the barriers move into the blocks).  What helps is having other work ready when a launch drains: the
+    // frames of a render are split into groups, each group runs the pipeline on its own stream with its own queues,
+    // and the hardware fills the slots one group's kernel frees with the blocks of the other group's next kernel.
+    // Measured on one MI355X (ms per blocking render, 1 / 2 / 3 / 4 groups of full-width launches): 3840x2160x16 spp 13.2 /
+    // 11.9 / 12.2 / 13.1; 1920x1080x32 spp 5.92 / 5.38 / 5.75 / 6.18; x8 spp (C3) 1.81 / 1.80 / 2.09 / 2.54; x4 spp 1.17 /
+    // 1.31: every extra launch costs ~25 us.  Two groups whose tracing launches are HALF as wide (two chained segments per
+    // block, wf2_trace) do better, because the two groups' launches then really run side by side: C3 1.76 -> 1.61,
+    // close-up 6.89 -> 6.22, 16 spp 3.11 -> 2.82, instanced scene 4.56 -> 4.03; 1280x720x4 spp 0.69 -> 0.71 (not used
+    // below 12 M paths).  Counted and timed renders run in one group; so does one whose helper streams cannot be made.
+    if (fp.n_frames >= 2 && !counted && !timed) {
+        const int forced = std::min(std::max(tuning().groups, 0), kMaxGroups);   // JPT_GROUPS=n overrides the rule (tuning runs, tests)
+        const size_t paths = (size_t)c->width * (size_t)c->local_rows * (size_t)fp.n_frames;
+        const int wanted = std::min(fp.n_frames, forced ? forced : (paths >= ((size_t)12 << 20) ? 2 : 1));
+        if (wanted > 1) p.groups = 1 + std::min(dev.group_streams(c, wanted), wanted - 1);
+    }
+    // Two frame groups share the chip: half-width launches.  A SMALL render that runs alone (the addon's use: one blocking
+    // 1-spp frame per Godot frame): two chained segments per tracing block.  With a few rays per lane a segment's queue runs dry almost at once; half as
+    // many waves with queues twice as deep keep their lanes fuller (C2 0.779 -> 0.738 ms, a 1-spp 1080p frame
+    // 0.673 -> 0.648).  Not for windows of millions of paths (C3 in one group: 1.39 -> 1.51 ms) nor for scenes
+    // past the caches, which are bound by the latency of their fetches and want every wave they can get (1 M
+    // triangles, 2 spp: 9.49 -> 9.93 ms): one segment per block (profiles/r03/r03ao_lone_chain.txt).
+    const uint64_t window_paths = ((uint64_t)c->width * (uint64_t)c->local_rows - wf2_pixels_outside_window(cull, fp)) * (uint64_t)fp.n_frames;
+    const size_t walked_bytes = c->wide.blas_nodes4.size() * sizeof(WideNodeQ) + c->wide.tris.size() * sizeof(WideTri);
+    const bool small = window_paths <= 1500000u && walked_bytes <= ((size_t)32 << 20);
+    p.chain = (p.groups == 2 || (c->native_tree && !c->ref_is_exact && small)) ? 2 : 1;
+    return p;
+}
+
+// the frame parameters of a render of n_frames frames from first_frame_index
+FrameParams frame_params(const jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool want_depth)
+{
+    // (in the order of the fields: image, partition, bounces, accumulation, first frame, frames, depth frame, display, DEBUG_STEPS)
+    return FrameParams{c->width, c->height, c->local_rows, c->rank, c->world, c->max_bounces, c->accum_mode, first_frame_index,
+                       c->frame_count + 1, n_frames, want_depth ? n_frames - 1 : -1, c->denoise == JPT_DENOISE_PROGRESSIVE ? 0 : 1,
+                       c->debug_steps ? 1 : 0};
+}
+
+// the sum of the kernel-timing event pairs of the last render; *primary_ms (unless null) gets the first pair's, wf2_primary's
+double traced_ms(const jpt_ctx* c, double* primary_ms)
+{
+    double tms = 0.0;
+    for (int32_t k = 0; k + 1 < c->trace_events_used; k += 2) {
+        float t = 0.0f;
+        if (hipEventElapsedTime(&t, c->trace_events[(size_t)k], c->trace_events[(size_t)k + 1]) == hipSuccess) {
+            tms += t;
+            if (k == 0 && primary_ms) *primary_ms = t;
+        }
+    }
+    return tms;
+}
+
+int validate_render(jpt_ctx* c, int32_t n_frames)
 {
     if (!c) return JPT_E_INVALID;
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context (JPT_DEVICE_HOST_ONLY) cannot render: there is no CPU fallback");
@@ -782,9 +912,15 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     if (n_frames < 0) return fail(c, JPT_E_INVALID, "n_frames < 0");
     if (c->refit_active && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
         return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas refits the default kernel's records only: call jpt_scene_update_tlas before rendering with another kernel");
-    HIP_TRY(c, hipSetDevice(c->device));
+    return JPT_OK;
+}
+
+// What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
+// stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.
+int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefront, Wf2Render& r)
+{
     hipStream_t s = c->stream;
-    c->assembled = c->assembled_ldr = false;
+    const int32_t n_frames = fp.n_frames;
     if (c->denoise == JPT_DENOISE_TEMPORAL) {
         // the pass runs once per displayed frame and reads other pixels' depth and history (temporal_reprojection.glsl:57-61)
         if (n_frames > 1) return fail(c, JPT_E_INVALID, "temporal reprojection renders one frame per call");
@@ -806,264 +942,190 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
             c->hist_written = nullptr;
         }
     }
-    DevCounters* cnt = nullptr;
-    if (counted) {
-        cnt = c->d_counters.p;
-        HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(DevCounters), s));
-    }
-    const bool wavefront = c->kernel_variant == JPT_KERNEL_WAVEFRONT && !c->debug_steps;   // (DEBUG_STEPS exists in the audit kernel only)
-    const bool wf2 = wavefront;
-    const int nq = c->max_bounces + 2;
-    if (wavefront && c->local_rows > 0 && c->width > 0 && n_frames > 0) {
+    if (counted) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(DevCounters), s));
+    const bool wf2 = wavefront && c->local_rows > 0 && c->width > 0 && n_frames > 0;
+    if (wf2) {
         const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces);
-        if (c->d_workspace.n < need) {
+        if (c->slot[0].workspace.n < need) {
             HIP_TRY(c, hipStreamSynchronize(s));
-            HIP_TRY(c, c->d_workspace.resize(need));
+            HIP_TRY(c, c->slot[0].workspace.resize(need));
         }
     }
     HIP_TRY(c, hipEventRecord(c->ev0, s));
+    if (!wf2) return JPT_OK;
+    const size_t need_ev = c->kernel_timing ? 2 * (size_t)(c->max_bounces + 1) : 0;
+    while (c->trace_events.size() < need_ev) {
+        hipEvent_t e;
+        HIP_TRY(c, hipEventCreate(&e));
+        c->trace_events.push_back(e);
+    }
+    c->trace_events_used = (int32_t)need_ev;
+    compute_sky_cull(c, r.cull);
+    // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
+    // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed
+    if (c->accum_mode == JPT_ACCUM_REF_LDR8 && n_frames > 1) {
+        const int32_t key[5] = {c->width, c->height, c->local_rows, c->rank, c->world};
+        RefCamera cam_key = c->camera;
+        cam_key.frame_index = 0;
+        const size_t n_tiles = wf2_sky_tile_count(c->width, c->local_rows);
+        if (!c->sky_tiles_valid || c->d_sky_tiles.n < n_tiles || std::memcmp(key, c->sky_tiles_key, sizeof key) != 0 ||
+            std::memcmp(&cam_key, &c->sky_tiles_camera, sizeof cam_key) != 0) {
+            if (c->d_sky_tiles.n < n_tiles) {
+                HIP_TRY(c, hipStreamSynchronize(s));   // (renders in flight may read the old buffer)
+                for (const PipeSlot& ps : c->slot)
+                    if (ps.stream) HIP_TRY(c, hipStreamSynchronize(ps.stream));
+                HIP_TRY(c, c->d_sky_tiles.resize(n_tiles));
+            }
+            launch_sky_tiles(s, fp, c->camera, c->d_sky_tiles.p);
+            std::memcpy(c->sky_tiles_key, key, sizeof key);
+            c->sky_tiles_camera = cam_key;
+            c->sky_tiles_valid = true;
+        }
+        r.sky_tiles = c->d_sky_tiles.p;
+    }
+    return JPT_OK;
+}
+
+// the render's launches on the route of its plan
+int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Render& r, DevCounters* cnt, float* depth_img)
+{
+    hipStream_t s = c->stream;
+    if (p.route == LaunchPlan::kReference) {
+        FrameParams one = fp;
+        for (int32_t f = 0; f < fp.n_frames; f++) {
+            one.frame_index = fp.frame_index + (uint32_t)f;
+            one.frame_count = c->frame_count + (uint32_t)f + 1;
+            one.n_frames = 1;
+            one.depth_frame = 0;
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt);
+        }
+        return JPT_OK;
+    }
+    if (p.route == LaunchPlan::kStream) {
+        launch_wf2_render(s, c->ds, fp, c->camera, c->slot[0].workspace.p, c->d_accum.p, c->d_ldr.p, depth_img, cnt,
+                          c->kernel_timing ? c->trace_events.data() : nullptr, r, p.groups, p.chain, c->group_streams);
+        return JPT_OK;
+    }
+    // a queued render: path kernels and accumulation on the slot's stream with the slot's workspace
+    PipeSlot& ps = c->slot[p.slot];
+    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces);
+    bool slots_ready = true;
+    for (int k = 0; k < p.slots; k++) slots_ready = slots_ready && c->slot[k].stream && c->slot[k].workspace.n >= need;
+    if (!slots_ready) {
+        // The first queued render of this size prepares ALL the slots, so that none of it lands in the middle
+        // of a queue of renders: a stream that gets its own hardware queue costs ~6 ms to create, a device
+        // allocation waits for the device, and a fresh 2 GB allocation costs its first user ~10 ms.
+        HIP_TRY(c, hipStreamSynchronize(s));  // every earlier render ends with a kernel on `s`
+        for (int k = 0; k < p.slots; k++) {
+            PipeSlot& sk = c->slot[k];
+            if (sk.workspace.n < need) {
+                HIP_TRY(c, sk.workspace.resize(need));
+                HIP_TRY(c, hipMemsetAsync(sk.workspace.p, 0, need, s));  // first touch
+                sk.acc_done_valid = false;
+            }
+            if (!ensure_pipe_slot(c, k)) return fail(c, JPT_E_DEVICE, "cannot create the stream of a pipeline slot");
+        }
+    }
+    // this workspace was last read by the accumulation of the render `slots` renders ago; when that is not on record
+    // (first use of the slot, or renders that went through `s` itself since), wait for whatever `s` holds now
+    if (!ps.acc_done_valid) HIP_TRY(c, hipEventRecord(ps.ev_acc_done, s));
+    HIP_TRY(c, hipStreamWaitEvent(ps.stream, ps.ev_acc_done, 0));
+    if (ps.refit_seen != c->refit_wait_seq) {
+        // the instance level this render reads was refitted on the refit stream (jpt_scene_refit_tlas)
+        HIP_TRY(c, hipStreamWaitEvent(ps.stream, c->ev_refit_done, 0));
+        ps.refit_seen = c->refit_wait_seq;
+    }
+    // The accumulation runs on the slot's stream too, after whatever `s` holds now (the previous render's accumulation, an
+    // upload, a read-back), and `s` then waits for it: the results are those of serial execution, and `s` itself carries no
+    // kernels of a render (the hardware runs a handful of queues side by side; a busy `s` would be one more)
+    HIP_TRY(c, hipEventRecord(ps.ev_paths_done, s));
+    r.before_acc = ps.ev_paths_done;
+    launch_wf2_render(ps.stream, c->ds, fp, c->camera, ps.workspace.p, c->d_accum.p, c->d_ldr.p, depth_img, nullptr, nullptr, r,
+                      p.groups, p.chain, c->group_streams);
+    HIP_TRY(c, hipEventRecord(ps.ev_acc_done, ps.stream));
+    HIP_TRY(c, hipStreamWaitEvent(s, ps.ev_acc_done, 0));
+    ps.acc_done_valid = true;
+    c->async_seq++;
+    return JPT_OK;
+}
+
+// a blocking or counted render: its time, ray count and event counters
+int read_back_stats(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefront, const SkyCull& cull)
+{
+    HIP_TRY(c, hipEventSynchronize(c->ev1));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->stats.last_render_ms = ms;
+    c->stats.last_trace_ms = ms;
+    if (wavefront && c->trace_events_used > 0 && fp.n_frames > 0 && c->local_rows > 0) c->stats.last_trace_ms = traced_ms(c, &c->stats.last_primary_ms);
+    if (wavefront && c->slot[0].workspace.p && fp.n_frames > 0 && c->local_rows > 0) {
+        // ray segments traced = sum of the per-bounce queue sizes (always available on this route)
+        const size_t nq = (size_t)c->max_bounces + 2, per_row = wf2_segments();
+        c->h_qcount.assign(nq * per_row + 2u, 0u);   // queue sizes, then the set-aside counts
+        HIP_TRY(c, hipMemcpy(c->h_qcount.data(), c->slot[0].workspace.p, c->h_qcount.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        c->stats.set_aside = c->h_qcount[nq * per_row];
+        c->stats.set_aside_dropped = c->h_qcount[nq * per_row + 1u];
+        // every in-image (pixel, frame) has one primary segment; rows 1.. hold the later bounces' queue sizes
+        uint64_t rays = (uint64_t)c->width * (uint64_t)c->local_rows * (uint64_t)fp.n_frames;
+        for (int b = 1; b <= c->max_bounces; b++)
+            for (size_t k = 0; k < per_row; k++) rays += c->h_qcount[(size_t)b * per_row + k];
+        c->stats.rays = rays;
+    }
+    if (counted) {
+        DevCounters h;
+        HIP_TRY(c, hipMemcpy(&h, c->d_counters.p, sizeof h, hipMemcpyDeviceToHost));
+        // (pixel, frame) pairs outside the render's window were never enumerated on the device: each is one primary
+        // segment that ends at the TLAS root, like the culled ones inside the window
+        const uint64_t outside = wavefront ? wf2_pixels_outside_window(cull, fp) * (uint64_t)fp.n_frames : 0;
+        h.phase[7] += outside;
+        c->stats.rays = h.rays + outside;
+        c->stats.blas_expand = h.blas_expand;
+        c->stats.tri_tests = h.tri_tests;
+        c->stats.tlas_expand = h.tlas_expand + outside;
+        c->stats.inst_visits = h.inst_visits;
+        c->stats.shaded_hits = h.shaded_hits;
+        for (int k = 0; k < 8; k++) c->stats.phase[k] = h.phase[k];
+        c->stats.sky_culled = h.phase[7];
+        c->stats.walk_steps_max = h.walk_max;
+        for (int k = 0; k < 8; k++) c->stats.walk_steps_hist[k] = h.walk_hist[k];
+        c->stats.zero_throughput = h.zero_thr;
+    }
+    return JPT_OK;
+}
+
+// validate -> prepare -> plan -> launch -> read back
+int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
+{
+    int rc = validate_render(c, n_frames);
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->assembled = c->assembled_ldr = false;
+    const bool wavefront = c->kernel_variant == JPT_KERNEL_WAVEFRONT && !c->debug_steps;   // (DEBUG_STEPS exists in the audit kernel only)
+    // the depth image (main.glsl:432,435) has one reader, the temporal pass: off when the host said so (jpt_set_outputs)
+    const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
+    const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
+    Wf2Render r;
+    if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
     if (c->local_rows > 0 && c->width > 0 && n_frames > 0) {
-        FrameParams fp;
-        fp.width = c->width;
-        fp.height = c->height;
-        fp.local_rows = c->local_rows;
-        fp.rank = c->rank;
-        fp.world = c->world;
-        fp.max_bounces = c->max_bounces;
-        fp.accum_mode = c->accum_mode;
-        fp.display_mode = c->denoise == JPT_DENOISE_PROGRESSIVE ? 0 : 1;
-        fp.debug_steps = c->debug_steps ? 1 : 0;
-        // the depth image (main.glsl:432,435) has one reader, the temporal pass: off when the host said so (jpt_set_outputs)
-        const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
-        float* const depth_img = want_depth ? c->d_depth.p : nullptr;
         c->depth_valid = want_depth;
-        if (wavefront) {
-            fp.frame_index = first_frame_index;
-            fp.frame_count = c->frame_count + 1;
-            fp.n_frames = n_frames;
-            fp.depth_frame = want_depth ? n_frames - 1 : -1;
-            const size_t need_ev = c->kernel_timing ? 2 * (size_t)(c->max_bounces + 1) : 0;
-            while (c->trace_events.size() < need_ev) {
-                hipEvent_t e;
-                HIP_TRY(c, hipEventCreate(&e));
-                c->trace_events.push_back(e);
-            }
-            c->trace_events_used = (int32_t)need_ev;
-            if (wf2) compute_sky_cull(c, c->async.cull);
-            // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
-            // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed
-            c->async.sky_tiles = nullptr;
-            if (wf2 && c->accum_mode == JPT_ACCUM_REF_LDR8 && n_frames > 1) {
-                const int32_t key[5] = {c->width, c->height, c->local_rows, c->rank, c->world};
-                RefCamera cam_key = c->camera;
-                cam_key.frame_index = 0;
-                const size_t n_tiles = wf2_sky_tile_count(c->width, c->local_rows);
-                if (!c->sky_tiles_valid || c->d_sky_tiles.n < n_tiles || std::memcmp(key, c->sky_tiles_key, sizeof key) != 0 ||
-                    std::memcmp(&cam_key, &c->sky_tiles_camera, sizeof cam_key) != 0) {
-                    if (c->d_sky_tiles.n < n_tiles) {
-                        HIP_TRY(c, hipStreamSynchronize(s));   // (renders in flight may read the old buffer)
-                        for (int k = 0; k < jpt_ctx::kPipeSlots; k++)
-                            if (c->pipe_stream[k]) HIP_TRY(c, hipStreamSynchronize(c->pipe_stream[k]));
-                        HIP_TRY(c, c->d_sky_tiles.resize(n_tiles));
-                    }
-                    launch_sky_tiles(s, fp, c->camera, c->d_sky_tiles.p);
-                    std::memcpy(c->sky_tiles_key, key, sizeof key);
-                    c->sky_tiles_camera = cam_key;
-                    c->sky_tiles_valid = true;
-                }
-                c->async.sky_tiles = c->d_sky_tiles.p;
-            }
-            const bool pipelining = tuning().pipelining;
-            // renders in flight (JPT_PIPE_SLOTS overrides): a render is eleven dependent launches of >= 25-30 us each
-            // however little work it holds, so several of them are needed to fill the chip
-            const int forced_slots = [c] {
-                if (c->max_slots > 0) return c->max_slots;   // the embedding application's cap (jpt_set_memory_policy)
-                const int k = tuning().pipe_slots;
-                return k <= 0 ? 0 : (k < 2 ? 2 : (k > jpt_ctx::kPipeSlots ? jpt_ctx::kPipeSlots : k));
-            }();
-            // Four renders in flight, each tracing with a quarter of the blocks (four consecutive segments per block: a
-            // deeper queue keeps a block's lanes refilled for a larger share of its launch) beat two renders of full-width
-            // launches on every size tried: C3 1.32 vs 1.45 ms, C2 0.36 vs 0.46, 1 frame 0.30 vs 0.37, 1920x136 0.185 vs
-            // 0.193, 4K x 16 spp 11.1 vs 11.1.  Renders whose workspace exceeds 24 GiB keep two slots and full-width launches.
-            const size_t one_workspace = wf2 ? wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces) : 0;
-            const bool huge = one_workspace > ((size_t)24 << 30);  // 4 x 24 GiB of workspaces is where this stops
-            // ... six where the slots' streams have six hardware queues to themselves (six_queues_probe), four otherwise
-            const bool may_queue = wf2 && pipelining && !blocking && !counted;
-            const int pipe_slots = forced_slots ? forced_slots : (huge ? 2 : ((may_queue && six_queues_probe(c)) ? 6 : 4));
-            const int slot = (int)(c->async_seq % (uint64_t)pipe_slots);
-            if (may_queue) c->last_pipe_slots = pipe_slots;
-            // A host that queues ONE render at a time (jpt_render_async, its own work, jpt_sync or the split read-back, again)
-            // never has a second render in flight: the pipelined form's quarter-width launches then run alone, and a render takes
-            // half as long again as a blocking one (C3 1.93 against 1.26 ms, 3840 x 2160 x 4 spp 3.33 against 2.11:
-            // tools/lone_async_probe.py).  The third queued render in a row that finds nothing in flight -- the event every render
-            // leaves on the context's stream has completed -- is launched like a blocking one instead (frame groups, full-width
-            // launches; nobody waits for it here), and so on until a render finds work in flight.  A queue of renders is not
-            // affected: only its first render finds the pipeline empty.
-            bool lone_async = false;
-            if (wf2 && pipelining && !blocking && !counted && !need_ev) {
-                const bool idle = hipEventQuery(c->ev1) == hipSuccess;
-                (void)hipGetLastError();   // (hipErrorNotReady is an answer, not an error)
-                c->idle_streak = idle ? c->idle_streak + 1 : 0;
-                lone_async = c->idle_streak >= 3;
-            }
-            if (wf2 && pipelining && !blocking && !counted && !need_ev && !lone_async && ensure_pipe_slot(c, slot)) {
-                // asynchronous render: path kernels on a helper stream + the other workspace; the accumulation on `s`
-                hipStream_t ps = c->pipe_stream[slot];
-                DevBuf<char>& ws = slot ? c->d_workspace_more[slot - 1] : c->d_workspace;
-                const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces);
-                bool slots_ready = true;
-                for (int k = 0; k < pipe_slots; k++)
-                    slots_ready = slots_ready && c->pipe_stream[k] && (k ? c->d_workspace_more[k - 1] : c->d_workspace).n >= need;
-                if (!slots_ready) {
-                    // The first queued render of this size prepares ALL the slots, so that none of it lands in the middle
-                    // of a queue of renders: a stream that gets its own hardware queue costs ~6 ms to create, a device
-                    // allocation waits for the device, and a fresh 2 GB allocation costs its first user ~10 ms.
-                    HIP_TRY(c, hipStreamSynchronize(s));  // every earlier render ends with a kernel on `s`
-                    for (int k = 0; k < pipe_slots; k++) {
-                        DevBuf<char>& wk = k ? c->d_workspace_more[k - 1] : c->d_workspace;
-                        if (wk.n < need) {
-                            HIP_TRY(c, wk.resize(need));
-                            HIP_TRY(c, hipMemsetAsync(wk.p, 0, need, s));  // first touch
-                            c->acc_done_valid[k] = false;
-                        }
-                        if (!ensure_pipe_slot(c, k)) return fail(c, JPT_E_DEVICE, "cannot create the stream of a pipeline slot");
-                    }
-                }
-                // this workspace was last read by the accumulation of the render `pipe_slots` renders ago; when that is
-                // not on record (first use of the slot, or renders that went through `s` itself since), wait for
-                // whatever `s` holds now
-                if (!c->acc_done_valid[slot]) HIP_TRY(c, hipEventRecord(c->ev_acc_done[slot], s));
-                HIP_TRY(c, hipStreamWaitEvent(ps, c->ev_acc_done[slot], 0));
-                if (c->slot_refit_seen[slot] != c->refit_wait_seq) {
-                    // the instance level this render reads was refitted on the refit stream (jpt_scene_refit_tlas)
-                    HIP_TRY(c, hipStreamWaitEvent(ps, c->ev_refit_done, 0));
-                    c->slot_refit_seen[slot] = c->refit_wait_seq;
-                }
-                // (one frame group: overlapping with the neighbouring render does what groups do, without extra launches:
-                // 3840x2160x16 spp 11.56 ms against 11.96 with two groups, instanced scene 3.80 against 4.05)
-                Wf2Async one_group = c->async;
-                one_group.aux_stream[0] = nullptr;
-                one_group.trace_chain = (huge || pipe_slots == 1) ? 1 : 4;   // (a single render in flight: full-width launches)
-                // The accumulation runs on the slot's stream too, after whatever `s` holds now (the previous render's accumulation, an
-                // upload, a read-back), and `s` then waits for it: the results are those of serial execution, and `s` itself carries no
-                // kernels of a render (the hardware runs a handful of queues side by side; a busy `s` would be one more)
-                HIP_TRY(c, hipEventRecord(c->ev_paths_done[slot], s));
-                one_group.before_acc = c->ev_paths_done[slot];
-                launch_wf2_render(ps, c->ds, fp, c->camera, ws.p, c->d_accum.p, c->d_ldr.p, depth_img, nullptr, nullptr, one_group);
-                HIP_TRY(c, hipEventRecord(c->ev_acc_done[slot], ps));
-                HIP_TRY(c, hipStreamWaitEvent(s, c->ev_acc_done[slot], 0));
-                c->acc_done_valid[slot] = true;
-                c->async_seq++;
-                pipelined = true;
-            } else if (wf2) {
-                // (launch_wf2_render splits the frames into groups only if the helper streams exist)
-                const int want_groups = wf2_wanted_groups(n_frames, (size_t)c->width * (size_t)c->local_rows * (size_t)n_frames);
-                if (want_groups > 1 && !need_ev && !counted) (void)ensure_group_streams(c, want_groups);
-                // A SMALL render that runs alone (the addon's use: one blocking 1-spp frame per Godot frame): two chained
-                // segments per tracing block.  With a few rays per lane a segment's queue runs dry almost at once; half as
-                // many waves with queues twice as deep keep their lanes fuller (C2 0.779 -> 0.738 ms, a 1-spp 1080p frame
-                // 0.673 -> 0.648).  Not for windows of millions of paths (C3 in one group: 1.39 -> 1.51 ms) nor for scenes
-                // past the caches, which are bound by the latency of their fetches and want every wave they can get (1 M
-                // triangles, 2 spp: 9.49 -> 9.93 ms): one segment per block (profiles/r03/r03ao_lone_chain.txt).
-                Wf2Async lone = c->async;
-                {
-                    FrameParams wfp;
-                    wfp.width = c->width;
-                    wfp.height = c->height;
-                    wfp.local_rows = c->local_rows;
-                    wfp.rank = c->rank;
-                    wfp.world = c->world;
-                    const uint64_t window_paths =
-                        ((uint64_t)c->width * (uint64_t)c->local_rows - wf2_pixels_outside_window(c->async.cull, wfp)) * (uint64_t)n_frames;
-                    const size_t walked_bytes = c->wide.blas_nodes4.size() * sizeof(WideNodeQ) + c->wide.tris.size() * sizeof(WideTri);
-                    const bool small = window_paths <= 1500000u && walked_bytes <= ((size_t)32 << 20);
-                    lone.trace_chain = (c->native_tree && !c->ref_is_exact && small) ? 2 : 1;
-                }
-                launch_wf2_render(s, c->ds, fp, c->camera, c->d_workspace.p, c->d_accum.p, c->d_ldr.p, depth_img, cnt,
-                                  need_ev ? c->trace_events.data() : nullptr, lone);
-            }
-        } else {
-            for (int32_t f = 0; f < n_frames; f++) {
-                fp.frame_index = first_frame_index + (uint32_t)f;
-                fp.frame_count = c->frame_count + (uint32_t)f + 1;
-                fp.n_frames = 1;
-                fp.depth_frame = 0;
-                launch_ref_frame(s, c->ds, fp, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt);
-            }
-        }
+        const LaunchPlan p = plan_launch(c, fp, r.cull, counted, blocking, kPlanDevice);
+        rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->d_depth.p : nullptr);
+        if (rc != JPT_OK) return rc;
+        pipelined = p.route == LaunchPlan::kSlot;
         if (c->denoise == JPT_DENOISE_TEMPORAL) {
             // TemporalReprojection::render's dispatch (temporal_reprojection.cpp:71): screen + depth of this frame in,
             // blended history and the displayed screen out
-            launch_temporal(s, c->temporal, c->d_ldr.p, c->d_depth.p, c->d_hist1.p, c->d_hist2.p);
+            launch_temporal(c->stream, c->temporal, c->d_ldr.p, c->d_depth.p, c->d_hist1.p, c->d_hist2.p);
             c->hist_written = (c->temporal.frame_count % 2u) == 0u ? c->d_hist2.p : c->d_hist1.p;
         }
         HIP_TRY(c, hipGetLastError());
     }
-    HIP_TRY(c, hipEventRecord(c->ev1, s));
-    if (wavefront && !pipelined) c->acc_done_valid[0] = false;  // d_workspace was used on `s` itself: see the pipelined branch
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (wavefront && !pipelined) c->slot[0].acc_done_valid = false;  // slot 0's workspace was used on the context's stream itself
     c->frame_count += (uint32_t)n_frames;
     c->stats.frames = c->frame_count;
-    if (blocking || counted) {
-        HIP_TRY(c, hipEventSynchronize(c->ev1));
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        c->stats.last_render_ms = ms;
-        c->stats.last_trace_ms = ms;
-        if (wavefront && c->trace_events_used > 0 && n_frames > 0 && c->local_rows > 0) {
-            double tms = 0.0;
-            for (int32_t k = 0; k + 1 < c->trace_events_used; k += 2) {
-                float t = 0.0f;
-                if (hipEventElapsedTime(&t, c->trace_events[(size_t)k], c->trace_events[(size_t)k + 1]) == hipSuccess) {
-                    tms += t;
-                    if (k == 0) c->stats.last_primary_ms = t;
-                }
-            }
-            c->stats.last_trace_ms = tms;
-        }
-        if (wavefront && c->d_workspace.p && n_frames > 0 && c->local_rows > 0) {
-            // ray segments traced = sum of the per-bounce queue sizes (always available on this route)
-            const size_t per_row = wf2 ? (size_t)wf2_segments() : 1u;
-            c->h_qcount.assign((size_t)nq * per_row + 2u, 0u);   // queue sizes, then the set-aside counts
-            HIP_TRY(c, hipMemcpy(c->h_qcount.data(), c->d_workspace.p, c->h_qcount.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            c->stats.set_aside = c->h_qcount[(size_t)nq * per_row];
-            c->stats.set_aside_dropped = c->h_qcount[(size_t)nq * per_row + 1u];
-            // every in-image (pixel, frame) has one primary segment; rows 1.. hold the later bounces' queue sizes
-            uint64_t rays = (uint64_t)c->width * (uint64_t)c->local_rows * (uint64_t)n_frames;
-            for (int b = 1; b <= c->max_bounces; b++)
-                for (size_t k = 0; k < per_row; k++) rays += c->h_qcount[(size_t)b * per_row + k];
-            c->stats.rays = rays;
-        }
-        if (counted) {
-            DevCounters h;
-            HIP_TRY(c, hipMemcpy(&h, cnt, sizeof h, hipMemcpyDeviceToHost));
-            // (pixel, frame) pairs outside the render's window were never enumerated on the device: each is one primary
-            // segment that ends at the TLAS root, like the culled ones inside the window
-            uint64_t outside = 0;
-            if (wf2) {
-                FrameParams wfp;
-                wfp.width = c->width;
-                wfp.height = c->height;
-                wfp.local_rows = c->local_rows;
-                wfp.rank = c->rank;
-                wfp.world = c->world;
-                outside = wf2_pixels_outside_window(c->async.cull, wfp) * (uint64_t)n_frames;
-            }
-            h.phase[7] += outside;
-            c->stats.rays = h.rays + outside;
-            c->stats.blas_expand = h.blas_expand;
-            c->stats.tri_tests = h.tri_tests;
-            c->stats.tlas_expand = h.tlas_expand + outside;
-            c->stats.inst_visits = h.inst_visits;
-            c->stats.shaded_hits = h.shaded_hits;
-            for (int k = 0; k < 8; k++) c->stats.phase[k] = h.phase[k];
-            c->stats.sky_culled = h.phase[7];
-            c->stats.walk_steps_max = h.walk_max;
-            for (int k = 0; k < 8; k++) c->stats.walk_steps_hist[k] = h.walk_hist[k];
-            c->stats.zero_throughput = h.zero_thr;
-        }
-    }
-    return JPT_OK;
+    return (blocking || counted) ? read_back_stats(c, fp, counted, wavefront, r.cull) : JPT_OK;
 }
 
 // local strip-major rows -> full image rows, on the host
@@ -1118,6 +1180,29 @@ int ensure_ldr_pinned(jpt_ctx* c)
         c->h_ldr_pinned_px = (size_t)c->width * c->height;
     }
     return JPT_OK;
+}
+
+// drain and destroy the pipeline slots' streams and the frame groups' helper streams (a borrowed helper is a slot's stream: it
+// goes with the slot); the next render that needs them makes new ones
+void release_streams(jpt_ctx* c)
+{
+    for (int k = 0; k < kMaxGroups - 1; k++) {
+        hipStream_t& st = c->group_streams.aux_stream[k];
+        if (st) {
+            (void)hipStreamSynchronize(st);
+            if (!c->aux_borrowed[k]) (void)hipStreamDestroy(st);
+        }
+        st = nullptr;
+        c->aux_borrowed[k] = false;
+    }
+    for (PipeSlot& ps : c->slot) {
+        if (ps.stream) {
+            (void)hipStreamSynchronize(ps.stream);
+            (void)hipStreamDestroy(ps.stream);
+        }
+        ps.stream = nullptr;
+        ps.acc_done_valid = false;
+    }
 }
 
 }  // namespace
@@ -1191,21 +1276,12 @@ void jpt_destroy(jpt_ctx* c)
         if (c->h_refit_t12[k]) (void)hipHostFree(c->h_refit_t12[k]);
         if (c->ev_refit_copied[k]) (void)hipEventDestroy(c->ev_refit_copied[k]);
     }
-    for (int k = 0; k < 3; k++) {
-        if (c->async.aux_stream[k]) {
-            (void)hipStreamSynchronize(c->async.aux_stream[k]);
-            if (!c->aux_borrowed[k]) (void)hipStreamDestroy(c->async.aux_stream[k]);   // (a borrowed one goes with the pipeline slots below)
-        }
-        if (c->async.join[k]) (void)hipEventDestroy(c->async.join[k]);
-    }
-    if (c->async.fork) (void)hipEventDestroy(c->async.fork);
-    for (int k = 0; k < jpt_ctx::kPipeSlots; k++) {
-        if (c->pipe_stream[k]) {
-            (void)hipStreamSynchronize(c->pipe_stream[k]);
-            (void)hipStreamDestroy(c->pipe_stream[k]);
-        }
-        if (c->ev_paths_done[k]) (void)hipEventDestroy(c->ev_paths_done[k]);
-        if (c->ev_acc_done[k]) (void)hipEventDestroy(c->ev_acc_done[k]);
+    release_streams(c);
+    for (hipEvent_t e : c->group_streams.join) if (e) (void)hipEventDestroy(e);
+    if (c->group_streams.fork) (void)hipEventDestroy(c->group_streams.fork);
+    for (PipeSlot& ps : c->slot) {
+        if (ps.ev_paths_done) (void)hipEventDestroy(ps.ev_paths_done);
+        if (ps.ev_acc_done) (void)hipEventDestroy(ps.ev_acc_done);
     }
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
@@ -1222,7 +1298,7 @@ int jpt_set_stream(jpt_ctx* c, void* hip_stream)
         // events its helper streams wait on): drain it before work starts appearing on another one
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        for (int k = 0; k < jpt_ctx::kPipeSlots; k++) c->acc_done_valid[k] = false;
+        for (PipeSlot& ps : c->slot) ps.acc_done_valid = false;
         c->stream = next;
     }
     return JPT_OK;
@@ -1240,23 +1316,8 @@ int jpt_set_stream_priority(jpt_ctx* c, int32_t priority)
     // the pipeline slots' streams are made on first use: drop the ones that exist, the next queued render makes new ones
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 3; k++) {   // the frame groups' helper streams follow: borrowed slot streams go with the slots, own ones are re-made
-        if (c->async.aux_stream[k]) {
-            (void)hipStreamSynchronize(c->async.aux_stream[k]);
-            if (!c->aux_borrowed[k]) (void)hipStreamDestroy(c->async.aux_stream[k]);
-            c->async.aux_stream[k] = nullptr;
-            c->aux_borrowed[k] = false;
-        }
-    }
+    release_streams(c);   // (the frame groups' helper streams follow them)
     c->six_queues = -1;   // (measured again for the new streams)
-    for (int k = 0; k < jpt_ctx::kPipeSlots; k++) {
-        if (c->pipe_stream[k]) {
-            (void)hipStreamSynchronize(c->pipe_stream[k]);
-            (void)hipStreamDestroy(c->pipe_stream[k]);
-            c->pipe_stream[k] = nullptr;
-        }
-        c->acc_done_valid[k] = false;
-    }
     return JPT_OK;
 }
 
@@ -1270,15 +1331,15 @@ int jpt_set_memory_policy(jpt_ctx* c, int32_t renders_in_flight, uint64_t worksp
     HIP_TRY(c, hipSetDevice(c->device));
     // drain, then give back what the new policy no longer allows: the workspaces of slots past the cap, and any workspace
     // larger than the new budget (the next render allocates what it needs)
-    for (int k = 0; k < jpt_ctx::kPipeSlots; k++)
-        if (c->pipe_stream[k]) HIP_TRY(c, hipStreamSynchronize(c->pipe_stream[k]));
+    for (const PipeSlot& ps : c->slot)
+        if (ps.stream) HIP_TRY(c, hipStreamSynchronize(ps.stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const int keep = renders_in_flight > 0 ? renders_in_flight : jpt_ctx::kPipeSlots;
     for (int k = 0; k < jpt_ctx::kPipeSlots; k++) {
-        DevBuf<char>& w = k ? c->d_workspace_more[k - 1] : c->d_workspace;
-        if (k >= keep || (workspace_budget_bytes && w.n > workspace_budget_bytes)) {
-            w.release();
-            c->acc_done_valid[k] = false;
+        PipeSlot& ps = c->slot[k];
+        if (k >= keep || (workspace_budget_bytes && ps.workspace.n > workspace_budget_bytes)) {
+            ps.workspace.release();
+            ps.acc_done_valid = false;
         }
     }
     c->async_seq = 0;   // the next queued render starts at slot 0 again
@@ -1289,8 +1350,8 @@ int jpt_set_memory_policy(jpt_ctx* c, int32_t renders_in_flight, uint64_t worksp
 int jpt_get_workspace_bytes(jpt_ctx* c, uint64_t* bytes_out)
 {
     if (!c || !bytes_out) return JPT_E_INVALID;
-    uint64_t n = c->d_workspace.n;
-    for (int k = 0; k + 1 < jpt_ctx::kPipeSlots; k++) n += c->d_workspace_more[k].n;
+    uint64_t n = 0;
+    for (const PipeSlot& ps : c->slot) n += ps.workspace.n;
     *bytes_out = n;
     return JPT_OK;
 }
@@ -1821,7 +1882,7 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
 {
     if (!c) return JPT_E_INVALID;
     if (width < 0 || height < 0 || width > 65536 || height > 65536) return fail(c, JPT_E_INVALID, "bad resolution");
-    if (max_bounces < 0 || max_bounces > 64) return fail(c, JPT_E_INVALID, "max_bounces must be in [0,64]");
+    if (max_bounces < 0 || max_bounces > kMaxBounces) return fail(c, JPT_E_INVALID, "max_bounces must be in [0,64]");
     if (accum_mode != JPT_ACCUM_REF_LDR8 && accum_mode != JPT_ACCUM_HDR_F32) return fail(c, JPT_E_INVALID, "unknown accum_mode");
     if (sampler_mode < JPT_SAMPLER_NEAREST_CLAMP || sampler_mode > JPT_SAMPLER_LINEAR_REPEAT) return fail(c, JPT_E_INVALID, "unknown sampler_mode");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no framebuffers");
@@ -1869,14 +1930,7 @@ int jpt_sync(jpt_ctx* c)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, c->ev0, c->ev1) == hipSuccess) c->stats.last_render_ms = c->stats.last_trace_ms = ms;
-    if (c->kernel_variant != JPT_KERNEL_REFERENCE_LAYOUT && c->trace_events_used > 0) {
-        double tms = 0.0;
-        for (int32_t k = 0; k + 1 < c->trace_events_used; k += 2) {
-            float t = 0.0f;
-            if (hipEventElapsedTime(&t, c->trace_events[(size_t)k], c->trace_events[(size_t)k + 1]) == hipSuccess) tms += t;
-        }
-        c->stats.last_trace_ms = tms;
-    }
+    if (c->kernel_variant != JPT_KERNEL_REFERENCE_LAYOUT && c->trace_events_used > 0) c->stats.last_trace_ms = traced_ms(c, nullptr);
     return JPT_OK;
 }
 

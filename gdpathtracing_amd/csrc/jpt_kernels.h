@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "jpt_nodeq.h"
 #include "jpt_shade.h"
 #include "jpt_types.h"
@@ -11,6 +13,29 @@
 namespace jpt {
 
 constexpr int kStripRows = 8;  // screen partition granule (jpt_set_partition)
+constexpr int kMaxBounces = 64;  // the largest max_bounces (jpt_set_params)
+constexpr int kMaxGroups = 4;    // the most frame groups a render is split into (launch_wf2_render)
+
+// Runtime flags as template arguments: with_consts<N0, N1, ...>(f, v0, v1, ...) calls f with one constant per flag,
+// std::bool_constant<v != 0> for N == 2 and std::integral_constant<int, v> otherwise.  Every v must lie in [0, N); only the
+// values a launcher passes are instantiated.
+template <int N, int V = 0, typename F>
+inline void with_const(int v, F&& f)
+{
+    if constexpr (V + 1 < N) {
+        if (v != V) return with_const<N, V + 1>(v, f);
+    }
+    if constexpr (N == 2) f(std::bool_constant<V != 0>{});
+    else f(std::integral_constant<int, V>{});
+}
+template <int N, int... Ns, typename F, typename... Vs>
+inline void with_consts(F&& f, int v, Vs... rest)
+{
+    with_const<N>(v, [&](auto k) {
+        if constexpr (sizeof...(Ns) == 0) f(k);
+        else with_consts<Ns...>([&](auto... ks) { f(k, ks...); }, rest...);
+    });
+}
 
 struct DevCounters {  // SURVEY.md 8(d) event counters
     unsigned long long rays, blas_expand, tri_tests, tlas_expand, inst_visits, shaded_hits;
@@ -183,6 +208,7 @@ size_t wf2_sky_tile_count(int width, int local_rows);
 void launch_sky_tiles(hipStream_t stream, const FrameParams& fp, const RefCamera& cam, uint32_t* tile_cell);
 uint32_t wf2_segments();
 uint32_t trace_stack_capacity();  // entries a lane's traversal stack can hold (LDS + scratch)
+// bytes of the workspace a render of this size carves (wf2_layout), for any frame-group count and window
 size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces);
 // Screen rectangles (pixels, inclusive) of the boxes the TLAS root offers a ray; a primary ray through a pixel
 // outside all of them is known to fail all of the root's box tests, i.e. to reach the sky after exactly one TLAS
@@ -192,19 +218,24 @@ struct SkyCull {
     int32_t x0[4], y0[4], x1[4], y1[4];
 };
 
-// helper streams / events for running frame groups concurrently (all null: serial); owned by the context
-struct Wf2Async {
-    hipStream_t aux_stream[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t fork = nullptr, join[3] = {nullptr, nullptr, nullptr};
-    SkyCull cull;          // for the primary launch of this render
-    int trace_chain = 1;   // wf2_trace: consecutive segments per block (1: lowest latency; 4 when renders are queued)
-    hipEvent_t before_acc = nullptr;  // the accumulation kernel waits for this event (whatever its stream)
+// what the context owns for running frame groups side by side: the helper stream of group k + 1 and the event group 0's stream
+// waits on for it (launch_wf2_render uses the first groups - 1 of them)
+struct Wf2Streams {
+    hipStream_t aux_stream[kMaxGroups - 1] = {};
+    hipEvent_t fork = nullptr, join[kMaxGroups - 1] = {};
+};
+// what one render passes to its launches
+struct Wf2Render {
+    SkyCull cull;                          // for the primary launch of this render
+    hipEvent_t before_acc = nullptr;       // the accumulation kernel waits for this event (whatever its stream)
     const uint32_t* sky_tiles = nullptr;   // per 8 x 8 tile of the context's share of the image: its one rgba8 sky cell, if it has one
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
 };
+// `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
+// segments per tracing block
 void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, void* workspace,
                        float4* accum, uint32_t* ldr, float* depth, DevCounters* counters, hipEvent_t* trace_events,
-                       const Wf2Async& async);
+                       const Wf2Render& r, int groups, int chain, const Wf2Streams& streams);
 
 // one wave busy for `ticks` of the device's wall clock (hipDeviceAttributeWallClockRate), to see which streams run side by side
 void launch_queue_spin(hipStream_t stream, long long ticks);
@@ -223,7 +254,6 @@ void launch_tlas4_refit(hipStream_t stream, const float* transforms12, uint32_t 
 void launch_temporal(hipStream_t stream, const RefTemporalParams& tp, uint32_t* screen, const float* depth, float4* hist1,
                      float4* hist2);
 
-int wf2_wanted_groups(int n_frames, size_t paths);
 // pixels of this context's share of the image that lie outside the render's window (the tile-aligned bounding rectangle
 // of the sky cull's screen rectangles): the primary launch does not even enumerate them (their rays are sky by the
 // cull's argument; the event counters are completed with their number on the host)

@@ -21,8 +21,8 @@
 // segment (cursor in LDS) while its neighbours keep walking -- the wave never waits for its slowest ray.
 // Per-lane traversal stacks live in LDS (20 entries x 256 lanes, deeper levels spill to scratch).
 //
-// launch_wf2_render runs one render: a blocking render of many paths splits its frames into two groups that run
-// this pipeline concurrently on two streams; asynchronous renders are pipelined one level up (jpt_capi.cpp).
+// launch_wf2_render runs one render in the frame groups (this pipeline on several streams at once) and with the tracing
+// chain the host chose; the host decides those, and pipelines asynchronous renders one level up (plan_launch, jpt_capi.cpp).
 #include <algorithm>
 #include <cstdlib>
 
@@ -1291,31 +1291,9 @@ void launch_sky_tiles(hipStream_t stream, const FrameParams& fp, const RefCamera
 uint32_t wf2_segments() { return kSegments; }
 uint32_t trace_stack_capacity() { return (uint32_t)(kStackLds + kStackSpill); }
 
-// Frame groups.  Every launch of the pipeline ends with a tail: a few long rays in a few waves while the rest of the
-// chip has nothing left to do (a ray's latency under full load is ~20 us on average, ~100 us for the longest; C3's ten
-// launch boundaries cost 0.5 ms of 1.85 -- render time is 0.48 + 0.17 * spp ms).  Balancing the queues does not
-// help (tried: equal ray counts per block, same time) and neither does fusing the bounce loop into one persistent
-// kernel (the barriers move into the blocks).  What helps is having other work ready when a launch drains: the
-// frames of a render are split into groups, each group runs the pipeline on its own stream with its own queues,
-// and the hardware fills the slots one group's kernel frees with the blocks of the other group's next kernel.
-// Paths never cross groups and the per-pixel accumulation still reads the frames in order: results are unchanged.
-// Measured on one MI355X (ms per blocking render, 1 / 2 / 3 / 4 groups of full-width launches): 3840x2160x16 spp 13.2 /
-// 11.9 / 12.2 / 13.1; 1920x1080x32 spp 5.92 / 5.38 / 5.75 / 6.18; x8 spp (C3) 1.81 / 1.80 / 2.09 / 2.54; x4 spp 1.17 /
-// 1.31: every extra launch costs ~25 us.  Two groups whose tracing launches are HALF as wide (two chained segments per
-// block, wf2_trace) do better, because the two groups' launches then really run side by side: C3 1.76 -> 1.61,
-// close-up 6.89 -> 6.22, 16 spp 3.11 -> 2.82, instanced scene 4.56 -> 4.03; 1280x720x4 spp 0.69 -> 0.71 (not used
-// below 12 M paths).
-constexpr int kMaxGroups = 4;
-static int frame_groups(int n_frames, bool serial, size_t paths)
-{
-    const int forced = [] {  // JPT_GROUPS=n overrides the rule (tuning runs, tests)
-        const int g = tuning().groups;
-        return g < 0 ? 0 : (g > kMaxGroups ? kMaxGroups : g);
-    }();
-    if (serial || n_frames < 2) return 1;
-    const int wanted = forced ? forced : (paths >= ((size_t)12 << 20) ? 2 : 1);
-    return n_frames < wanted ? n_frames : wanted;
-}
+// Frame groups: the frames of a render split into groups, each running the pipeline on its own stream with its own queues
+// (the rule and its measurements: plan_launch, jpt_capi.cpp).  Paths never cross groups and the per-pixel accumulation still
+// reads the frames in order: results are unchanged.
 static void group_frames(int n_frames, int groups, int g, int& first, int& count)
 {
     const int base = n_frames / groups, extra = n_frames % groups;
@@ -1334,33 +1312,80 @@ static uint32_t redo_capacity(size_t paths)
     return (uint32_t)(c > 0x7fffffffu ? 0x7fffffffu : c);
 }
 
+// The workspace of one render, carved from `base` in this order (group 0's queue sizes first: the host reads them).  The one
+// layout there is: launch_wf2_render carves it from the real base, wf2_workspace_bytes from a null one for its size (the
+// pointers are then offsets, never dereferenced).  wf2_primary owns the zeroing of the queue sizes of bounces >= 1 and of
+// the set-aside counts: thread t of block s clears segment s's word of row t (1 <= t <= max_bounces + 1), and threads 192..
+// of block 0 the 64 words behind the rows.
+static_assert(kBlock >= 192 + 64, "wf2_primary clears the 64 set-aside words with threads 192.. of block 0");
+static_assert(kMaxBounces + 1 < 192, "wf2_primary clears the queue-size rows with threads below 192");
+struct Wf2Layout {
+    Wf2Buffers gb[kMaxGroups];
+    Wf2Dims gdm[kMaxGroups];
+    FrameParams gfp[kMaxGroups];
+    float4* rad;          // all groups' blocks, [slot][frame of the group] each
+    uint32_t* fin8;
+    float* first_depth;
+    size_t bytes = 0;     // the end of the last buffer
+};
+static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window)
+{
+    Wf2Layout L;
+    auto carve = [&](size_t bytes) {
+        void* p = reinterpret_cast<void*>(reinterpret_cast<uintptr_t>(base) + L.bytes);
+        L.bytes += (bytes + 255) & ~(size_t)255;
+        return p;
+    };
+    const int nq = fp.max_bounces + 2;
+    const Wf2Dims dm_all = make_dims(fp.width, fp.local_rows, fp.n_frames, window);
+    for (int g = 0; g < groups; g++) {
+        L.gb[g].qcount = (uint32_t*)carve(((size_t)nq * kSegments + 64) * sizeof(uint32_t));   // queue sizes + the set-aside counts
+        L.gb[g].redo_count = L.gb[g].qcount + (size_t)nq * kSegments;
+    }
+    L.rad = (float4*)carve((size_t)dm_all.slots_per_frame * (size_t)fp.n_frames * sizeof(float4));
+    L.fin8 = (uint32_t*)carve((size_t)dm_all.slots_per_frame * (size_t)fp.n_frames * sizeof(uint32_t));
+    L.first_depth = (float*)carve((size_t)dm_all.slots_per_frame * sizeof(float));
+    for (int g = 0; g < groups; g++) {
+        int f0, nf;
+        group_frames(fp.n_frames, groups, g, f0, nf);
+        L.gdm[g] = make_dims(fp.width, fp.local_rows, nf, window);
+        const size_t q = (size_t)L.gdm[g].seg_cap * kSegments;
+        const size_t paths = (size_t)L.gdm[g].slots_per_frame * (size_t)nf;
+        Wf2Buffers& wb = L.gb[g];
+        wb.ray_o[0] = (float4*)carve(q * sizeof(float4));
+        wb.ray_o[1] = (float4*)carve(q * sizeof(float4));
+        wb.ray_d[0] = (float4*)carve(q * sizeof(float4));
+        wb.ray_d[1] = (float4*)carve(q * sizeof(float4));
+        wb.thr_q[0] = (float4*)carve(q * sizeof(float4));
+        wb.thr_q[1] = (float4*)carve(q * sizeof(float4));
+        wb.hit_a = (float4*)carve(q * sizeof(float4));
+        wb.hit_b = (uint32_t*)carve(q * sizeof(uint32_t));
+        wb.redo_cap = redo_capacity(paths);
+        wb.redo_rec = (float4*)carve((size_t)wb.redo_cap * 2 * sizeof(float4));
+        wb.thr = (float4*)carve(paths * sizeof(float4));
+        wb.rad = L.rad + (size_t)f0 * dm_all.slots_per_frame;  // this group's block behind the earlier groups'
+        wb.fin8 = L.fin8 + (size_t)f0 * dm_all.slots_per_frame;
+        wb.first_depth = L.first_depth;
+        L.gfp[g] = fp;
+        L.gfp[g].frame_index = fp.frame_index + (uint32_t)f0;
+        L.gfp[g].n_frames = nf;
+        L.gfp[g].depth_frame = (fp.depth_frame >= 0 && f0 + nf == fp.n_frames) ? nf - 1 : -1;  // the render's last frame writes the depth image (when there is one: jpt_set_outputs)
+    }
+    return L;
+}
+
 size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces)
 {
-    // sized for every layout a render of this size may use (the group count depends on kernel timing, on the
-    // previous render's ray count and on JPT_GROUPS): the largest of 1..kMaxGroups groups
+    // every layout a render of this size may use: the largest of 1..kMaxGroups groups over the whole image
+    FrameParams fp{};
+    fp.width = width;
+    fp.local_rows = local_rows;
+    fp.n_frames = n_frames;
+    fp.max_bounces = max_bounces;
     size_t worst = 0;
-    for (int groups = 1; groups <= kMaxGroups && groups <= (n_frames < 1 ? 1 : n_frames); groups++) {
-        size_t b = 0;
-        for (int g = 0; g < groups; g++) {
-            int f0, nf;
-            group_frames(n_frames, groups, g, f0, nf);
-            const Wf2Dims dm = make_dims(width, local_rows, nf, full_window(width, local_rows));
-            const size_t q = (size_t)dm.seg_cap * kSegments;                  // queue entries
-            const size_t paths = (size_t)dm.slots_per_frame * (size_t)nf;
-            b += q * sizeof(float4) * 6 + 6 * 256;    // two ray queues (o, d, throughput)
-            b += q * sizeof(float4) + 256;            // hit_a
-            b += q * sizeof(uint32_t) + 256;          // hit_b
-            b += paths * sizeof(float4) + 256;        // thr
-            b += ((size_t)(max_bounces + 2) * kSegments + 64) * sizeof(uint32_t) + 256;   // queue sizes + the set-aside counts
-            b += (size_t)redo_capacity(paths) * 2 * sizeof(float4) + 256;    // set-aside records
-        }
-        const Wf2Dims all = make_dims(width, local_rows, n_frames, full_window(width, local_rows));
-        b += (size_t)all.slots_per_frame * (size_t)n_frames * sizeof(float4) + 256;  // rad: a block per group, each [slot][frame of the group]
-        b += (size_t)all.slots_per_frame * (size_t)n_frames * sizeof(uint32_t) + 256;  // fin8
-        b += (size_t)all.slots_per_frame * sizeof(float) + 256;
-        worst = b > worst ? b : worst;
-    }
-    return worst + 17 * 256;
+    for (int groups = 1; groups <= kMaxGroups && groups <= (n_frames < 1 ? 1 : n_frames); groups++)
+        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows)).bytes);
+    return worst;
 }
 
 namespace {
@@ -1373,57 +1398,13 @@ __global__ void add_queue_counts(uint32_t* __restrict__ dst, const uint32_t* __r
 
 void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, void* workspace,
                        float4* accum, uint32_t* ldr, float* depth, DevCounters* counters, hipEvent_t* trace_events,
-                       const Wf2Async& async)
+                       const Wf2Render& r, int groups, int chain, const Wf2Streams& streams)
 {
-    const TileWindow window = cull_window(async.cull, fp);
+    const TileWindow window = cull_window(r.cull, fp);
     const Wf2Dims dm_all = make_dims(fp.width, fp.local_rows, fp.n_frames, window);
     if (dm_all.n_chunks == 0) return;
-    char* w = reinterpret_cast<char*>(workspace);
-    auto carve = [&](size_t bytes) {
-        void* p = w;
-        w += (bytes + 255) & ~(size_t)255;
-        return p;
-    };
+    const Wf2Layout L = wf2_layout(workspace, fp, groups, window);
     const int nq = fp.max_bounces + 2;
-    // per-launch events and event counters want the launches one after another
-    const int groups = frame_groups(fp.n_frames, trace_events != nullptr || counters != nullptr || !async.aux_stream[0],
-                                    (size_t)fp.width * (size_t)fp.local_rows * (size_t)fp.n_frames);
-    Wf2Buffers gb[kMaxGroups];
-    Wf2Dims gdm[kMaxGroups];
-    FrameParams gfp[kMaxGroups];
-    for (int g = 0; g < groups; g++) {  // group 0 first: the host reads it
-        gb[g].qcount = (uint32_t*)carve(((size_t)nq * kSegments + 64) * sizeof(uint32_t));
-        gb[g].redo_count = gb[g].qcount + (size_t)nq * kSegments;
-    }
-    float4* rad_all = (float4*)carve((size_t)dm_all.slots_per_frame * (size_t)fp.n_frames * sizeof(float4));
-    uint32_t* fin8_all = (uint32_t*)carve((size_t)dm_all.slots_per_frame * (size_t)fp.n_frames * sizeof(uint32_t));
-    float* first_depth = (float*)carve((size_t)dm_all.slots_per_frame * sizeof(float));
-    for (int g = 0; g < groups; g++) {
-        int f0, nf;
-        group_frames(fp.n_frames, groups, g, f0, nf);
-        gdm[g] = make_dims(fp.width, fp.local_rows, nf, window);
-        const size_t q = (size_t)gdm[g].seg_cap * kSegments;
-        const size_t paths = (size_t)gdm[g].slots_per_frame * (size_t)nf;
-        Wf2Buffers& wb = gb[g];
-        wb.ray_o[0] = (float4*)carve(q * sizeof(float4));
-        wb.ray_o[1] = (float4*)carve(q * sizeof(float4));
-        wb.ray_d[0] = (float4*)carve(q * sizeof(float4));
-        wb.ray_d[1] = (float4*)carve(q * sizeof(float4));
-        wb.thr_q[0] = (float4*)carve(q * sizeof(float4));
-        wb.thr_q[1] = (float4*)carve(q * sizeof(float4));
-        wb.hit_a = (float4*)carve(q * sizeof(float4));
-        wb.hit_b = (uint32_t*)carve(q * sizeof(uint32_t));
-        wb.redo_cap = redo_capacity(paths);
-        wb.redo_rec = (float4*)carve((size_t)wb.redo_cap * 2 * sizeof(float4));
-        wb.thr = (float4*)carve(paths * sizeof(float4));
-        wb.rad = rad_all + (size_t)f0 * dm_all.slots_per_frame;  // this group's block ([slot][frame of the group]: path ids) behind the earlier groups'
-        wb.fin8 = fin8_all + (size_t)f0 * dm_all.slots_per_frame;
-        wb.first_depth = first_depth;
-        gfp[g] = fp;
-        gfp[g].frame_index = fp.frame_index + (uint32_t)f0;
-        gfp[g].n_frames = nf;
-        gfp[g].depth_frame = (fp.depth_frame >= 0 && f0 + nf == fp.n_frames) ? nf - 1 : -1;  // the render's last frame writes the depth image (when there is one: jpt_set_outputs)
-    }
 
     const bool w4 = ds.use4;
     WideSceneDev sc;
@@ -1440,15 +1421,21 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     const dim3 block(kBlock);
     const WfTune tune{Tuning::refill_idle, Tuning::refill_idle, Tuning::node_min_lanes, Tuning::leaf_min_lanes, Tuning::inst_min_lanes, Tuning::phase_frac16, tuning().tail_rounds, tuning().tail_lanes};
 
-    const int chain = [&] {  // two frame groups share the chip: half-width launches
-        const int c = groups == 2 ? 2 : async.trace_chain;
-        return c < 1 ? 1 : (c > kMaxChain ? kMaxChain : c);
-    }();
+    chain = chain < 1 ? 1 : (chain > kMaxChain ? kMaxChain : chain);
     const dim3 tgrid((kSegments + (uint32_t)chain - 1u) / (uint32_t)chain);
     const dim3 pgrid(kSegments);
+    const int count = counters != nullptr;
     // The waves of a tracing launch finish their last, very long walks themselves, all lanes on one ray (the TAIL instantiations,
     // coop_walk_call): scenes large enough to have such walks (>= 200 000 triangles); JPT_TAIL=0 never, 1 on every scene.
-    const bool tail = w4 && (tuning().tail < 0 ? ds.n_tris >= 200000u : tuning().tail != 0);
+    // walk: 0 two-child records, 1 four-child records, 2 four-child records with TAIL
+    const int walk = !w4 ? 0 : ((tuning().tail < 0 ? ds.n_tris >= 200000u : tuning().tail != 0) ? 2 : 1);
+    // the shading instantiations: the paths' last vertices without the BRDF code, scenes without a texture array without the
+    // sampler code -- texmode 0 no texture array, 1 nearest filter, 2 linear filter (jpt.h: bit 1 of the sampler mode)
+    const bool tex = sh.tex != nullptr && sh.n_layers > 0 && sh.tex_res > 0;
+    const int texmode = !tex ? 0 : ((sh.sampler_mode & 2) ? 2 : 1);
+    // wf2_finish decides exact distance ties on the reference's own trees (EXACT) where the scene keeps them, four-child walks only
+    const TieShadowDev& sx = ds.x;
+    const int finish_walk = !w4 ? 0 : (sx.ok ? 2 : 1);
     // the pipeline of one group on one stream
     auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, hipEvent_t* ev) {
         // (the queue sizes of bounces >= 1 and the set-aside counts start from zero: wf2_primary clears them)
@@ -1458,94 +1445,57 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         // cost 9 %).
         const dim3 sgrid(((dm.seg_cap + kBlock - 1) / kBlock) | 1u, kSegments);
         if (ev) (void)hipEventRecord(ev[0], st);
-        if (tail) {
-            if (counters) hipLaunchKernelGGL((wf2_primary<true, true, true>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, async.cull, counters);
-            else hipLaunchKernelGGL((wf2_primary<false, true, true>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, async.cull, counters);
-        } else if (counters) {
-            if (w4) hipLaunchKernelGGL((wf2_primary<true, true>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, async.cull, counters);
-            else hipLaunchKernelGGL((wf2_primary<true, false>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, async.cull, counters);
-        } else {
-            if (w4) hipLaunchKernelGGL((wf2_primary<false, true>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, async.cull, counters);
-            else hipLaunchKernelGGL((wf2_primary<false, false>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, async.cull, counters);
-        }
+        with_consts<2, 3>([&](auto C, auto W) {
+            hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
+        }, count, walk);
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {
-            {
-                // instantiations: the paths' last vertices without the BRDF code, scenes without a texture array without
-                // the sampler code
-                const bool last = b == gp.max_bounces;
-                const bool tex = sh.tex != nullptr && sh.n_layers > 0 && sh.tex_res > 0;
-                // 0 no texture array, 1 nearest filter, 2 linear filter (jpt.h: bit 1 of the sampler mode)
-                const int texmode = !tex ? 0 : ((sh.sampler_mode & 2) ? 2 : 1);
-#define JPT_LAUNCH_SHADE(C, L, T) hipLaunchKernelGGL((wf2_shade<C, L, T>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters)
-                if (counters) {
-                    if (last) { if (texmode == 0) JPT_LAUNCH_SHADE(true, true, 0); else if (texmode == 1) JPT_LAUNCH_SHADE(true, true, 1); else JPT_LAUNCH_SHADE(true, true, 2); }
-                    else      { if (texmode == 0) JPT_LAUNCH_SHADE(true, false, 0); else if (texmode == 1) JPT_LAUNCH_SHADE(true, false, 1); else JPT_LAUNCH_SHADE(true, false, 2); }
-                } else {
-                    if (last) { if (texmode == 0) JPT_LAUNCH_SHADE(false, true, 0); else if (texmode == 1) JPT_LAUNCH_SHADE(false, true, 1); else JPT_LAUNCH_SHADE(false, true, 2); }
-                    else      { if (texmode == 0) JPT_LAUNCH_SHADE(false, false, 0); else if (texmode == 1) JPT_LAUNCH_SHADE(false, false, 1); else JPT_LAUNCH_SHADE(false, false, 2); }
-                }
-#undef JPT_LAUNCH_SHADE
-            }
+            with_consts<2, 2, 3>([&](auto C, auto LAST, auto TEX) {
+                hipLaunchKernelGGL((wf2_shade<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters);
+            }, count, b == gp.max_bounces, texmode);
             if (b == gp.max_bounces) break;
             if (ev) (void)hipEventRecord(ev[2 * (b + 1)], st);
-            if (tail) {
-                if (counters) hipLaunchKernelGGL((wf2_trace<true, true, true>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
-                else hipLaunchKernelGGL((wf2_trace<false, true, true>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
-            } else if (counters) {
-                if (w4) hipLaunchKernelGGL((wf2_trace<true, true>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
-                else hipLaunchKernelGGL((wf2_trace<true, false>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
-            } else {
-                if (w4) hipLaunchKernelGGL((wf2_trace<false, true>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
-                else hipLaunchKernelGGL((wf2_trace<false, false>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
-            }
+            with_consts<2, 3>([&](auto C, auto W) {
+                hipLaunchKernelGGL((wf2_trace<C, W != 0, W == 2>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
+            }, count, walk);
             if (ev) (void)hipEventRecord(ev[2 * (b + 1) + 1], st);
         }
         if (sh.reach_tri) {  // the paths set aside because their hit is undecidable on the native tree: finished exactly
             const dim3 rgrid(256), rblock(64);   // (blocks past the set-aside count exit at once; more records than threads: grid-stride)
-            const TieShadowDev& sx = ds.x;
-            if (sx.ok && w4) {
-                if (counters) hipLaunchKernelGGL((wf2_finish<true, true, true>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
-                else hipLaunchKernelGGL((wf2_finish<false, true, true>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
-            } else if (counters) {
-                if (w4) hipLaunchKernelGGL((wf2_finish<true, true, false>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
-                else hipLaunchKernelGGL((wf2_finish<true, false, false>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
-            } else {
-                if (w4) hipLaunchKernelGGL((wf2_finish<false, true, false>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
-                else hipLaunchKernelGGL((wf2_finish<false, false, false>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
-            }
+            with_consts<2, 3>([&](auto C, auto W) {
+                hipLaunchKernelGGL((wf2_finish<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
+            }, count, finish_walk);
         }
     };
 
     if (groups == 1) {
-        run_group(stream, gb[0], gdm[0], gfp[0], trace_events);
+        run_group(stream, L.gb[0], L.gdm[0], L.gfp[0], trace_events);
     } else {
         // fork: the helper streams start after everything already queued on the context's stream
-        (void)hipEventRecord(async.fork, stream);
-        for (int g = 1; g < groups; g++) (void)hipStreamWaitEvent(async.aux_stream[g - 1], async.fork, 0);
+        (void)hipEventRecord(streams.fork, stream);
+        for (int g = 1; g < groups; g++) (void)hipStreamWaitEvent(streams.aux_stream[g - 1], streams.fork, 0);
         // issue the groups' launches interleaved, so none of the streams runs ahead of the others on the host side
         // (run_group enqueues a whole pipeline; the hardware queues of the streams drain concurrently)
-        for (int g = 0; g < groups; g++) run_group(g == 0 ? stream : async.aux_stream[g - 1], gb[g], gdm[g], gfp[g], nullptr);
+        for (int g = 0; g < groups; g++) run_group(g == 0 ? stream : streams.aux_stream[g - 1], L.gb[g], L.gdm[g], L.gfp[g], nullptr);
         // join, then fold the other groups' queue sizes into group 0's (the host reads those for the ray count)
         for (int g = 1; g < groups; g++) {
-            (void)hipEventRecord(async.join[g - 1], async.aux_stream[g - 1]);
-            (void)hipStreamWaitEvent(stream, async.join[g - 1], 0);
+            (void)hipEventRecord(streams.join[g - 1], streams.aux_stream[g - 1]);
+            (void)hipStreamWaitEvent(stream, streams.join[g - 1], 0);
         }
         const uint32_t nqc = (uint32_t)nq * kSegments + 2u;   // (and the two set-aside counts behind the queue sizes)
         for (int g = 1; g < groups; g++)
-            hipLaunchKernelGGL(add_queue_counts, dim3((nqc + 255) / 256), dim3(256), 0, stream, gb[0].qcount, gb[g].qcount, nqc);
+            hipLaunchKernelGGL(add_queue_counts, dim3((nqc + 255) / 256), dim3(256), 0, stream, L.gb[0].qcount, L.gb[g].qcount, nqc);
     }
-    Wf2Buffers wb_all = gb[0];
+    Wf2Buffers wb_all = L.gb[0];
     Wf2Dims dm_acc = dm_all;
     dm_acc.acc_groups = groups;
-    wb_all.rad = rad_all;
-    wb_all.fin8 = fin8_all;
-    wb_all.first_depth = first_depth;
+    wb_all.rad = L.rad;
+    wb_all.fin8 = L.fin8;
+    wb_all.first_depth = L.first_depth;
     // the accumulation touches the framebuffers: it waits for whatever ordered the context's renders before this one (before_acc)
-    hipStream_t acc_stream = stream;
-    if (async.before_acc) (void)hipStreamWaitEvent(acc_stream, async.before_acc, 0);
+    if (r.before_acc) (void)hipStreamWaitEvent(stream, r.before_acc, 0);
     const uint32_t ablocks = ((uint32_t)dm_all.full_tiles_x * (uint32_t)dm_all.full_tiles_y * 64u + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(wf2_accumulate, dim3(ablocks), block, 0, acc_stream, wb_all, dm_acc, fp, cam, async.cull, accum, ldr, depth, async.sky_tiles);
+    hipLaunchKernelGGL(wf2_accumulate, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, r.sky_tiles);
 }
 
 uint64_t wf2_pixels_outside_window(const SkyCull& cull, const FrameParams& fp)
@@ -1556,8 +1506,5 @@ uint64_t wf2_pixels_outside_window(const SkyCull& cull, const FrameParams& fp)
     const int64_t inside = std::max<int64_t>(x1 - x0, 0) * std::max<int64_t>(y1 - y0, 0);
     return (uint64_t)((int64_t)fp.width * (int64_t)fp.local_rows - inside);
 }
-
-// the number of frame groups a blocking render of this size wants (helper streams permitting)
-int wf2_wanted_groups(int n_frames, size_t paths) { return frame_groups(n_frames, false, paths); }
 
 }  // namespace jpt
