@@ -1,6 +1,7 @@
 // jpt_builder.cpp -- see jpt_builder.h.  Host C++ only (no device code).
 #include "jpt_builder.h"
 #include "jpt_instance_math.h"
+#include "jpt_mesh_math.h"
 #include "jpt_tuning.h"
 
 #include <algorithm>
@@ -29,6 +30,8 @@ void RefScene::clear()
     inst_cut_range.clear();
     up_mesh_root.clear();
     up_blas_index.clear();
+    tri_vidx.clear();
+    mesh_tri_range.clear();
     exact.clear();
 }
 
@@ -270,9 +273,7 @@ struct SahBlasBuilder {
             order[i] = (uint32_t)i;
         }
         // boxes are padded so every Moller-Trumbore-accepted hit also passes the slab test in float
-        float m = 0.0f;
-        for (int k = 0; k < 3; k++) m = std::max(m, std::max(std::fabs(all.lo[k]), std::fabs(all.hi[k])));
-        pad = m * 2e-6f + 1e-30f;
+        pad = mesh_box_pad(all.lo, all.hi);   // (jpt_mesh_math.h: the device refit's code too)
     }
 
     // Builds the subtree over order[lo, hi) into `out` (pre-order: left child = parent + 1); child indices are
@@ -702,9 +703,13 @@ uint32_t SceneBuilder::add_mesh(const SurfaceView* surfaces, int32_t n_surfaces)
 {
     // the de-indexing half of BuildBVH (bvh.cpp:192-213)
     PendingMesh pm;
+    uint32_t vbase = 0;   // the surfaces' vertices laid end to end (what jpt_scene_update_mesh stages)
     for (int32_t l = 0; l < n_surfaces; l++) {
         const SurfaceView& s = surfaces[l];
+        pm.n_vertices.push_back(s.n_vertices);
+        pm.indices.emplace_back(s.indices, s.indices + s.n_indices);
         for (int32_t i = 0; i + 2 < s.n_indices; i += 3) {
+            for (int j = 0; j < 3; j++) pm.vidx.push_back(vbase + (uint32_t)s.indices[i + j]);
             RefTriangle t;
             std::memset(&t, 0, sizeof t);
             for (int j = 0; j < 3; j++) {
@@ -721,9 +726,37 @@ uint32_t SceneBuilder::add_mesh(const SurfaceView* surfaces, int32_t n_surfaces)
                               ((a.z + b.z) + c.z) * 0.33333333f, ((a.w + b.w) + c.w) * 0.33333333f};
             pm.tris.push_back(t);
         }
+        vbase += (uint32_t)s.n_vertices;
     }
     meshes_.push_back(std::move(pm));
     return (uint32_t)meshes_.size() - 1;
+}
+
+bool SceneBuilder::same_topology(uint32_t mesh_id, const SurfaceView* surfaces, int32_t n_surfaces) const
+{
+    if (mesh_id >= meshes_.size()) return false;
+    const PendingMesh& pm = meshes_[mesh_id];
+    if ((size_t)n_surfaces != pm.n_vertices.size()) return false;
+    for (int32_t l = 0; l < n_surfaces; l++) {
+        const SurfaceView& s = surfaces[l];
+        const std::vector<int32_t>& idx = pm.indices[(size_t)l];
+        if (s.n_vertices != pm.n_vertices[(size_t)l] || (size_t)s.n_indices != idx.size()) return false;
+        if (s.n_indices && (!s.indices || std::memcmp(s.indices, idx.data(), idx.size() * sizeof(int32_t)) != 0)) return false;
+    }
+    return true;
+}
+
+size_t SceneBuilder::mesh_vertex_count(uint32_t mesh_id) const
+{
+    size_t n = 0;
+    if (mesh_id < meshes_.size())
+        for (int32_t v : meshes_[mesh_id].n_vertices) n += (size_t)v;
+    return n;
+}
+
+const float* SceneBuilder::instance_transform(uint32_t instance) const
+{
+    return instance < instances_.size() ? instances_[instance].t12 : nullptr;
 }
 
 bool SceneBuilder::add_instance(uint32_t mesh_id, const float* t12, const int32_t* material_ids, int32_t n_ids)
@@ -981,6 +1014,12 @@ bool SceneBuilder::commit(BuildMode mode, RefScene& out, std::string& err)
                 b.prepare(start, end);
                 root = b.build(0, end - start);
                 b.apply_order(start, end);
+                if (mode == BuildMode::SahWatertight) {
+                    // which vertices each triangle came from, in the order the builder left the triangles (jpt_scene_update_mesh)
+                    out.tri_vidx.resize((size_t)end * 3);
+                    for (int i = 0; i < end - start; i++)
+                        for (int j = 0; j < 3; j++) out.tri_vidx[(size_t)(start + i) * 3 + j] = pm.vidx[(size_t)b.order[(size_t)i] * 3 + j];
+                }
                 if (mode == BuildMode::Sah) {
                     reach.get();
                     out.reach_tri.resize((size_t)end);
@@ -1021,7 +1060,10 @@ bool SceneBuilder::commit(BuildMode mode, RefScene& out, std::string& err)
             }
         }
         out.mesh_roots.push_back(root);
+        out.mesh_tri_range.push_back((uint32_t)start);
+        out.mesh_tri_range.push_back((uint32_t)(end - start));
     }
+    if (mode == BuildMode::SahWatertight) out.tri_vidx.resize(out.triangles.size() * 3, 0u);   // (a scene whose last meshes are empty)
     // BuildBVH on a mesh without triangles pushes no node and returns 0 (bvh.cpp:111-112), so in the reference an instance of
     // such a mesh gets blas_index 0 (geometry_group3d.cpp:311,325) and SHOWS WHATEVER TREE STARTS AT NODE 0 -- the first mesh
     // that has triangles -- under its own transform and materials.  Reproduced: an empty mesh stands for that mesh in every
@@ -1564,13 +1606,7 @@ bool flatten(const RefScene& ref, WideScene& out, std::string& err)
         const RefTriGeometry& g = ref.tri_geom[i];
         WideTri& t = out.tris[i];
         std::memset(&t, 0, sizeof t);
-        t.v0[0] = g.vertices[0].x; t.v0[1] = g.vertices[0].y; t.v0[2] = g.vertices[0].z;
-        t.e1[0] = g.vertices[1].x - g.vertices[0].x; t.e1[1] = g.vertices[1].y - g.vertices[0].y; t.e1[2] = g.vertices[1].z - g.vertices[0].z;
-        t.e2[0] = g.vertices[2].x - g.vertices[0].x; t.e2[1] = g.vertices[2].y - g.vertices[0].y; t.e2[2] = g.vertices[2].z - g.vertices[0].z;
-        // cross(e1, e2), each product and difference rounded on its own like the shader's (no contraction: Makefile)
-        t.nx = t.e1[1] * t.e2[2] - t.e1[2] * t.e2[1];
-        t.ny = t.e1[2] * t.e2[0] - t.e1[0] * t.e2[2];
-        t.nz = t.e1[0] * t.e2[1] - t.e1[1] * t.e2[0];
+        make_wide_tri(&g.vertices[0].x, &g.vertices[1].x, &g.vertices[2].x, t);   // (jpt_mesh_math.h: the device refit's code too)
     }
     // one BLAS tree per distinct root referenced by an instance
     std::vector<std::pair<uint32_t, int32_t>> root_refs;
@@ -1903,16 +1939,21 @@ void tlas4_refit_schedule(const WideScene& w, std::vector<uint32_t>& order, std:
     order.clear();
     level_start.clear();
     level_start.push_back(0);
-    const size_t n = w.tlas_nodes4.size();
-    if (w.tlas_root4 < 0 || (size_t)w.tlas_root4 >= n) return;  // no record: the root is an instance (or nothing)
+    refit4_schedule(w.tlas_nodes4, w.tlas_root4, order, level_start);
+}
+
+void refit4_schedule(const std::vector<WideNode4>& nodes, int32_t root, std::vector<uint32_t>& order, std::vector<uint32_t>& level_start)
+{
+    const size_t n = nodes.size();
+    if (root < 0 || (size_t)root >= n) return;  // no record: the root is an instance or a leaf (or nothing)
     // breadth first from the root: the levels, shallowest first; a record has one parent, so each appears once
     std::vector<std::vector<uint32_t>> levels;
-    levels.push_back({(uint32_t)w.tlas_root4});
+    levels.push_back({(uint32_t)root});
     for (size_t l = 0; l < levels.size() && l <= n; l++) {
         std::vector<uint32_t> next;
         for (uint32_t ni : levels[l])
             for (int k = 0; k < 4; k++) {
-                const int32_t c = w.tlas_nodes4[ni].child[k];
+                const int32_t c = nodes[ni].child[k];
                 if (c >= 0 && (size_t)c < n) next.push_back((uint32_t)c);
             }
         if (!next.empty()) levels.push_back(std::move(next));

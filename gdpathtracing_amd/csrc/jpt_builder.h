@@ -85,6 +85,10 @@ struct RefScene {
     // BLASInstance records against
     std::vector<uint32_t> up_mesh_root;
     std::vector<uint32_t> up_blas_index;
+    // BuildMode::SahWatertight commits (jpt_scene_update_mesh): per triangle, in the order of the triangle arrays, the indices of
+    // its three vertices in its mesh's surfaces' vertices laid end to end; per mesh its first triangle and triangle count
+    std::vector<uint32_t> tri_vidx;
+    std::vector<uint32_t> mesh_tri_range;
     ExactShadow exact;                        // BuildMode::Sah and native uploads
     void clear();
 };
@@ -128,9 +132,19 @@ class SceneBuilder {
     bool set_instance_transform(uint32_t instance, const float* transform12);
     bool rebuild_instances(BuildMode mode, RefScene& out, std::string& err);
     size_t instance_count() const { return instances_.size(); }
+    // deforming a committed mesh (jpt_scene_update_mesh): the surfaces have the vertex counts and index arrays add_mesh saw
+    size_t mesh_count() const { return meshes_.size(); }
+    bool same_topology(uint32_t mesh_id, const SurfaceView* surfaces, int32_t n_surfaces) const;
+    size_t mesh_vertex_count(uint32_t mesh_id) const;
+    const float* instance_transform(uint32_t instance) const;   // the last transform12 of an instance (null: no such instance)
 
   private:
-    struct PendingMesh { std::vector<RefTriangle> tris; };
+    struct PendingMesh {
+        std::vector<RefTriangle> tris;
+        std::vector<int32_t> n_vertices;               // per surface
+        std::vector<std::vector<int32_t>> indices;     // per surface: the index array
+        std::vector<uint32_t> vidx;                    // per triangle: its three vertices, surfaces' vertices laid end to end
+    };
     struct PendingInstance { uint32_t mesh; float t12[12]; uint32_t mats[3]; };
     std::vector<PendingMesh> meshes_;
     std::vector<PendingInstance> instances_;
@@ -160,6 +174,9 @@ bool native_instances_from_uploaded(const std::vector<RefInstance>& up_instances
 // Bottom-up schedule of the four-child TLAS records for a refit on the device (jpt_kernels_post.hip): `order` lists the
 // records of w.tlas_nodes4 deepest level first, level l is order[level_start[l] .. level_start[l + 1]).
 void tlas4_refit_schedule(const WideScene& w, std::vector<uint32_t>& order, std::vector<uint32_t>& level_start);
+// The same for the records under `root` of any four-child array (a mesh's BLAS for jpt_scene_update_mesh): APPENDS the levels to
+// `order` and their ends to `level_start` (whose last entry is where they start)
+void refit4_schedule(const std::vector<WideNode4>& nodes, int32_t root, std::vector<uint32_t>& order, std::vector<uint32_t>& level_start);
 
 // Reference layout -> flattened layout.  Keeps topology, boxes and child order, so traversal visits the
 // same nodes in the same order as main.glsl:270-350 does on the reference arrays.

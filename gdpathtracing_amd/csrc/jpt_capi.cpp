@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include "jpt_builder.h"
 #include "jpt_kernels.h"
 #include "jpt_instance_math.h"
+#include "jpt_mesh_math.h"
 #include "jpt_tuning.h"
 
 using namespace jpt;
@@ -186,6 +188,26 @@ struct jpt_ctx {
     bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
     bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
     std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
+    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in d_nodes4 and its schedule
+    // (refit4_schedule), made at the first update after an upload
+    struct MeshRefit {
+        bool has_tree = false;              // an instance names the mesh and it has triangles: the device holds its tree
+        int32_t root4 = 0;                  // its root reference in d_nodes4
+        uint32_t bvh_root = 0;              // its root in d_bvh (RefScene::mesh_roots)
+        uint32_t tri_first = 0, n_tris = 0;
+        uint32_t rec_first = 0, n_recs = 0;  // the span of d_nodes4 its records occupy
+        uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
+    };
+    std::vector<MeshRefit> mesh_refit;
+    bool mesh_refit_ready = false;
+    std::vector<uint32_t> mesh_order_h, mesh_levels_h;
+    DevBuf<uint32_t> d_mesh_order, d_mesh_levels, d_tri_vidx;
+    DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
+    char* h_mesh_stage[kRefitStages] = {};   // pinned staging ring for the updates (header, vertices, normals, transforms)
+    size_t h_mesh_bytes[kRefitStages] = {};
+    hipEvent_t ev_mesh_copied[kRefitStages] = {}, ev_mesh_drain = nullptr;
+    uint64_t mesh_seq = 0;
+    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
     uint32_t* h_ldr_pinned = nullptr;
     size_t h_ldr_pinned_px = 0;
     void* h_read_pinned = nullptr;   // blocking read-backs (staged_read)
@@ -410,6 +432,8 @@ int upload_scene(jpt_ctx* c)
     c->host_scene_ready = true;
     c->tlas_dirty = false;
     c->refit_active = false;
+    c->mesh_deformed = false;
+    c->mesh_refit_ready = false;
     note_ties(c);
     if (c->device < 0) return JPT_OK;  // host-only context: arrays stay on the host, nothing can be rendered
     HIP_TRY(c, hipSetDevice(c->device));
@@ -910,6 +934,8 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
     if (!c->camera_set) return fail(c, JPT_E_STATE, "jpt_set_camera not called");
     if (n_frames < 0) return fail(c, JPT_E_INVALID, "n_frames < 0");
+    if (c->mesh_deformed && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
+        return fail(c, JPT_E_STATE, "jpt_scene_update_mesh refits the default kernel's records only: call jpt_scene_commit before rendering with another kernel");
     if (c->refit_active && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
         return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas refits the default kernel's records only: call jpt_scene_update_tlas before rendering with another kernel");
     return JPT_OK;
@@ -1275,7 +1301,10 @@ void jpt_destroy(jpt_ctx* c)
     for (int k = 0; k < jpt_ctx::kRefitStages; k++) {
         if (c->h_refit_t12[k]) (void)hipHostFree(c->h_refit_t12[k]);
         if (c->ev_refit_copied[k]) (void)hipEventDestroy(c->ev_refit_copied[k]);
+        if (c->h_mesh_stage[k]) (void)hipHostFree(c->h_mesh_stage[k]);
+        if (c->ev_mesh_copied[k]) (void)hipEventDestroy(c->ev_mesh_copied[k]);
     }
+    if (c->ev_mesh_drain) (void)hipEventDestroy(c->ev_mesh_drain);
     release_streams(c);
     for (hipEvent_t e : c->group_streams.join) if (e) (void)hipEventDestroy(e);
     if (c->group_streams.fork) (void)hipEventDestroy(c->group_streams.fork);
@@ -1550,6 +1579,8 @@ int jpt_scene_share(jpt_ctx* dst, jpt_ctx* src)
     if (!dst || !src) return JPT_E_INVALID;
     if (dst == src) return JPT_OK;
     if (!src->host_scene_ready || src->building) return fail(dst, JPT_E_STATE, "the source context holds no committed scene");
+    if (src->mesh_deformed)
+        return fail(dst, JPT_E_STATE, "the source context's meshes were deformed on the device (jpt_scene_update_mesh): its host copy of the scene is stale until the next jpt_scene_commit");
     if (src->from_commit && (src->tlas_dirty || src->refit_active)) {  // bring the source's host arrays up to date with its last transforms
         const int rc = jpt_scene_update_tlas(src);
         if (rc != JPT_OK) return fail(dst, rc, std::string("source context: ") + src->error);
@@ -1617,73 +1648,22 @@ int upload_tlas_update(jpt_ctx* c)
     return upload_shadow(c, true);
 }
 
-}  // namespace
-
-int jpt_scene_set_instance_transform(jpt_ctx* c, uint32_t instance, const float* transform12)
+// The refit stream and the events that order device refits against renders (jpt_scene_refit_tlas, jpt_scene_update_mesh)
+int ensure_refit_stream(jpt_ctx* c)
 {
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_set_instance_transform needs a scene made by jpt_scene_commit");
-    if (!transform12) return fail(c, JPT_E_INVALID, "null transform");
-    if (!c->builder.set_instance_transform(instance, transform12)) return fail(c, JPT_E_INVALID, "no such instance");
-    c->tlas_dirty = true;
-    return JPT_OK;
-}
-
-int jpt_scene_update_tlas(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_update_tlas needs a scene made by jpt_scene_commit");
-    if (!c->tlas_dirty) return JPT_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::string err;
-    if (!c->builder.rebuild_instances(c->build_mode, c->ref, err)) {
-        c->scene_ready = c->host_scene_ready = false;
-        return fail(c, JPT_E_LIMIT, err);
-    }
-    const int rc = upload_tlas_update(c);
-    if (rc == JPT_OK) c->tlas_dirty = false;
-    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return rc;
-}
-
-int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->native_tree || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas needs a scene made by jpt_scene_commit with the native builder");
-    if (!transforms12 && n_instances) return fail(c, JPT_E_INVALID, "null transforms");
-    if (n_instances != c->ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the refit runs on the device (jpt_scene_update_tlas is the host route)");
-    // the host keeps the transforms (a later jpt_scene_update_tlas rebuilds from them); its arrays are stale from here on
-    for (uint32_t i = 0; i < n_instances; i++) (void)c->builder.set_instance_transform(i, transforms12 + (size_t)i * 12);
-    c->tlas_dirty = true;
-    if (!c->ds.use4 || !c->scene_ready) return jpt_scene_update_tlas(c);  // no four-child records to refit
-    if (n_instances == 0) return JPT_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    const size_t floats = (size_t)n_instances * 12;
-    // a ring of pinned staging buffers, so that the host can queue refits ahead of the device
-    const int st = (int)(c->refit_seq++ % (uint64_t)jpt_ctx::kRefitStages);
-    if (!c->ev_refit_copied[st]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_refit_copied[st], hipEventDisableTiming));
-    else HIP_TRY(c, hipEventSynchronize(c->ev_refit_copied[st]));  // the refit that used this stage last has run
-    if (c->h_refit_floats[st] < floats) {
-        if (c->h_refit_t12[st]) (void)hipHostFree(c->h_refit_t12[st]);
-        c->h_refit_t12[st] = nullptr;
-        c->h_refit_floats[st] = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_refit_t12[st], floats * sizeof(float), hipHostMallocDefault));
-        c->h_refit_floats[st] = floats;
-    }
-    std::memcpy(c->h_refit_t12[st], transforms12, floats * sizeof(float));
-    // the kernel reads the transforms straight from the pinned buffer (48 B per instance over the host link)
-    float* dev_view = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&dev_view, c->h_refit_t12[st], 0));
     if (!c->refit_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->refit_stream, hipStreamNonBlocking));
     for (int k = 0; k < jpt_ctx::kInstanceSets; k++)
         if (!c->ev_set_retired[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_set_retired[k], hipEventDisableTiming));
     if (!c->ev_refit_done) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_refit_done, hipEventDisableTiming));
+    return JPT_OK;
+}
+
+// Instance records and TLAS boxes from the transforms at `dev_view` (n_instances x 12 floats the device can read), written into the
+// copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
+// from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from d_bvh.
+int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances)
+{
+    hipStream_t s = c->stream;
     if (!c->set_b_ready) {
         // first refit since the last host upload: the other copies of the instance arrays start as copies of copy 0
         // (the TLAS tails were all uploaded).  Once per upload, so the drain does not matter.
@@ -1718,7 +1698,6 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
                        c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty() ? c->d_cut_boxes.p : nullptr,
                        c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty() ? c->d_cut_range.p : nullptr);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_refit_copied[st], rs));
     HIP_TRY(c, hipEventRecord(c->ev_refit_done, rs));
     // the context's stream (blocking renders, read-backs, uploads, foreign work) is ordered after the refit; queued
     // renders wait for it on their own streams (do_render_batch), not through the context's stream
@@ -1729,10 +1708,82 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     c->ds.wide_instances4 = winst4_next;
     if (reach_next) c->ds.reach_inst = reach_next;
     if (c->wide.tlas_root4 >= 0) c->ds.tlas_root4 = c->wide.tlas_root4 + (int32_t)tail_base;
+    return JPT_OK;
+}
+
+}  // namespace
+
+int jpt_scene_set_instance_transform(jpt_ctx* c, uint32_t instance, const float* transform12)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!c->host_scene_ready || c->building || !c->from_commit)
+        return fail(c, JPT_E_STATE, "jpt_scene_set_instance_transform needs a scene made by jpt_scene_commit");
+    if (!transform12) return fail(c, JPT_E_INVALID, "null transform");
+    if (!c->builder.set_instance_transform(instance, transform12)) return fail(c, JPT_E_INVALID, "no such instance");
+    c->tlas_dirty = true;
+    return JPT_OK;
+}
+
+int jpt_scene_update_tlas(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!c->host_scene_ready || c->building || !c->from_commit)
+        return fail(c, JPT_E_STATE, "jpt_scene_update_tlas needs a scene made by jpt_scene_commit");
+    if (c->mesh_deformed)
+        return fail(c, JPT_E_STATE, "a mesh was deformed on the device (jpt_scene_update_mesh): the host's copy of the scene is stale until the next jpt_scene_commit");
+    if (!c->tlas_dirty) return JPT_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::string err;
+    if (!c->builder.rebuild_instances(c->build_mode, c->ref, err)) {
+        c->scene_ready = c->host_scene_ready = false;
+        return fail(c, JPT_E_LIMIT, err);
+    }
+    const int rc = upload_tlas_update(c);
+    if (rc == JPT_OK) c->tlas_dirty = false;
+    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return rc;
+}
+
+int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!c->host_scene_ready || c->building || !c->native_tree || !c->from_commit)
+        return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas needs a scene made by jpt_scene_commit with the native builder");
+    if (!transforms12 && n_instances) return fail(c, JPT_E_INVALID, "null transforms");
+    if (n_instances != c->ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the refit runs on the device (jpt_scene_update_tlas is the host route)");
+    // the host keeps the transforms (a later jpt_scene_update_tlas rebuilds from them); its arrays are stale from here on
+    for (uint32_t i = 0; i < n_instances; i++) (void)c->builder.set_instance_transform(i, transforms12 + (size_t)i * 12);
+    c->tlas_dirty = true;
+    if (!c->ds.use4 || !c->scene_ready) return jpt_scene_update_tlas(c);  // no four-child records to refit
+    if (n_instances == 0) return JPT_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t floats = (size_t)n_instances * 12;
+    // a ring of pinned staging buffers, so that the host can queue refits ahead of the device
+    const int st = (int)(c->refit_seq++ % (uint64_t)jpt_ctx::kRefitStages);
+    if (!c->ev_refit_copied[st]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_refit_copied[st], hipEventDisableTiming));
+    else HIP_TRY(c, hipEventSynchronize(c->ev_refit_copied[st]));  // the refit that used this stage last has run
+    if (c->h_refit_floats[st] < floats) {
+        if (c->h_refit_t12[st]) (void)hipHostFree(c->h_refit_t12[st]);
+        c->h_refit_t12[st] = nullptr;
+        c->h_refit_floats[st] = 0;
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_refit_t12[st], floats * sizeof(float), hipHostMallocDefault));
+        c->h_refit_floats[st] = floats;
+    }
+    std::memcpy(c->h_refit_t12[st], transforms12, floats * sizeof(float));
+    // the kernel reads the transforms straight from the pinned buffer (48 B per instance over the host link)
+    float* dev_view = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&dev_view, c->h_refit_t12[st], 0));
+    int rc = ensure_refit_stream(c);
+    if (rc == JPT_OK) rc = queue_instance_refit(c, dev_view, n_instances);
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_refit_copied[st], c->refit_stream));
     // The sky cull (compute_sky_cull) projects the boxes the TLAS root offers, on the host.  For a modest number of
     // instances the host repeats the refit on its own copy of the four-child TLAS records (same arithmetic, same
-    // schedule: ~0.1 us per instance); beyond that the cull is off until the next jpt_scene_update_tlas.
-    if (n_instances <= 4096u && !c->tlas4_levels_h.empty()) {
+    // schedule: ~0.1 us per instance); beyond that the cull is off until the next jpt_scene_update_tlas.  After
+    // jpt_scene_update_mesh the host's root boxes are the committed vertices': off until the next jpt_scene_commit.
+    if (n_instances <= 4096u && !c->tlas4_levels_h.empty() && !c->mesh_deformed) {
         WideScene& w = c->wide;
         std::vector<RefInstance> boxes(n_instances);
         for (uint32_t i = 0; i < n_instances; i++) {
@@ -1776,6 +1827,209 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     c->refit_active = true;
     c->ds.x.tlas_current = false;   // the copy of the reference's instance level is the last HOST update's: until the next one exact ties are decided inside one instance only (jpt_tie_walk.h)
     c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return JPT_OK;
+}
+
+namespace {
+
+// Per mesh: where its records and triangles are on the device and the bottom-up schedule of its records (refit4_schedule), with
+// the triangles' vertex indices; made and uploaded at the first jpt_scene_update_mesh after an upload (once per upload: the
+// host waits for the copies).
+int ensure_mesh_refit(jpt_ctx* c)
+{
+    if (c->mesh_refit_ready) return JPT_OK;
+    const RefScene& r = c->ref;
+    const WideScene& w = c->wide;
+    const size_t n_meshes = r.mesh_roots.size();
+    if (r.mesh_tri_range.size() != 2 * n_meshes || r.tri_vidx.size() != 3 * r.tri_geom.size() || w.instances4.size() != r.instances.size())
+        return fail(c, JPT_E_STATE, "the scene holds no vertex map for device updates: commit it again with JPT_BUILD_SAH_WATERTIGHT");
+    c->mesh_refit.assign(n_meshes, jpt_ctx::MeshRefit{});
+    c->mesh_order_h.clear();
+    c->mesh_levels_h.clear();
+    for (size_t m = 0; m < n_meshes; m++) {
+        jpt_ctx::MeshRefit& mr = c->mesh_refit[m];
+        mr.bvh_root = r.mesh_roots[m];
+        mr.tri_first = r.mesh_tri_range[2 * m];
+        mr.n_tris = r.mesh_tri_range[2 * m + 1];
+        if (mr.n_tris == 0) continue;   // (an empty mesh stands for another mesh's tree: nothing of its own on the device)
+        size_t inst = r.instances.size();
+        for (size_t i = 0; i < r.instances.size(); i++)
+            if (r.instances[i].blas_index == mr.bvh_root) {
+                inst = i;
+                break;
+            }
+        if (inst == r.instances.size()) continue;   // no instance names it: flatten made no tree for it
+        mr.has_tree = true;
+        mr.root4 = w.instances4[inst].root;
+        mr.level_first = (uint32_t)c->mesh_levels_h.size();
+        const size_t order_first = c->mesh_order_h.size();
+        c->mesh_levels_h.push_back((uint32_t)order_first);
+        refit4_schedule(w.blas_nodes4, mr.root4, c->mesh_order_h, c->mesh_levels_h);
+        mr.n_levels = (uint32_t)(c->mesh_levels_h.size() - mr.level_first - 1);
+        if (mr.root4 >= 0) {
+            uint32_t lo = (uint32_t)mr.root4, hi = (uint32_t)mr.root4;
+            for (size_t k = order_first; k < c->mesh_order_h.size(); k++) {
+                lo = std::min(lo, c->mesh_order_h[k]);
+                hi = std::max(hi, c->mesh_order_h[k]);
+            }
+            mr.rec_first = lo;
+            mr.n_recs = hi - lo + 1;
+        }
+    }
+    {
+        const int rc = ensure_refit_stream(c);
+        if (rc != JPT_OK) return rc;
+    }
+    hipStream_t rs = c->refit_stream;
+    HIP_TRY(c, c->d_tri_vidx.upload(r.tri_vidx, rs));
+    HIP_TRY(c, c->d_mesh_order.upload(c->mesh_order_h, rs));
+    HIP_TRY(c, c->d_mesh_levels.upload(c->mesh_levels_h, rs));
+    HIP_TRY(c, hipStreamSynchronize(rs));   // pageable host vectors
+    c->mesh_refit_ready = true;
+    return JPT_OK;
+}
+
+}  // namespace
+
+int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!c->host_scene_ready || c->building || !c->from_commit)
+        return fail(c, JPT_E_STATE, "jpt_scene_update_mesh needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
+    if (c->ref_is_exact || !c->native_tree)
+        return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_REFERENCE_EXACT: its trees are the reference's own, which a refit "
+                                    "would not keep (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
+    if (c->build_mode != BuildMode::SahWatertight)
+        return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_SAH: its reach records and tie shadow are the reference builder's "
+                                    "tree of the committed vertices (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
+    if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
+    if (n_surfaces < 0 || (n_surfaces && !surfaces)) return fail(c, JPT_E_INVALID, "bad surface array");
+    std::vector<SurfaceView> sv((size_t)n_surfaces);
+    int with_normals = 0, with_vertices = 0;
+    for (int32_t i = 0; i < n_surfaces; i++) {
+        const jpt_surface& x = surfaces[i];
+        if (x.n_vertices > 0) {
+            if (!x.vertices) return fail(c, JPT_E_INVALID, "surface needs a vertex array");
+            with_vertices++;
+            with_normals += x.normals ? 1 : 0;
+        }
+        sv[(size_t)i] = SurfaceView{x.vertices, x.normals, nullptr, x.indices, x.n_vertices, x.n_indices};
+    }
+    if (!c->builder.same_topology(mesh_id, sv.data(), n_surfaces)) return fail(c, JPT_E_INVALID, "topology changed: commit the scene again");
+    if (with_normals != 0 && with_normals != with_vertices) return fail(c, JPT_E_INVALID, "give normals for every surface of the mesh or for none");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the update runs on the device");
+    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_mesh_refit(c);
+    if (rc != JPT_OK) return rc;
+    c->mesh_deformed = true;   // (the host's arrays describe the committed vertices from here on)
+    const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
+    if (!mr.has_tree) return JPT_OK;   // no instance names the mesh: the device holds nothing of it
+    hipStream_t s = c->stream, rs = c->refit_stream;
+    // staging: [6 ordered keys + pad: 32 B][vertices][normals][transforms]; the first three parts are copied to the device, the
+    // instance refit reads the transforms from the pinned buffer
+    const size_t nv = c->builder.mesh_vertex_count(mesh_id);
+    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    const size_t head = 32, vbytes = nv * 3 * sizeof(float), nbytes = with_normals ? vbytes : 0, tbytes = (size_t)n_inst * 12 * sizeof(float);
+    const size_t dev_bytes = head + vbytes + nbytes, bytes = dev_bytes + tbytes;
+    const int st = (int)(c->mesh_seq++ % (uint64_t)jpt_ctx::kRefitStages);
+    if (!c->ev_mesh_copied[st]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_copied[st], hipEventDisableTiming));
+    else HIP_TRY(c, hipEventSynchronize(c->ev_mesh_copied[st]));   // the update that used this stage last has run
+    if (!c->ev_mesh_drain) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_drain, hipEventDisableTiming));
+    if (c->h_mesh_bytes[st] < bytes) {
+        if (c->h_mesh_stage[st]) (void)hipHostFree(c->h_mesh_stage[st]);
+        c->h_mesh_stage[st] = nullptr;
+        c->h_mesh_bytes[st] = 0;
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_mesh_stage[st], bytes, hipHostMallocDefault));
+        c->h_mesh_bytes[st] = bytes;
+    }
+    char* h = c->h_mesh_stage[st];
+    {
+        int32_t keys[8] = {ordered_key(FLT_MAX), ordered_key(FLT_MAX), ordered_key(FLT_MAX),
+                           ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), 0, 0};
+        std::memcpy(h, keys, sizeof keys);
+        size_t off = head;
+        for (const SurfaceView& x : sv) {
+            const size_t b = (size_t)x.n_vertices * 3 * sizeof(float);
+            if (b) std::memcpy(h + off, x.vertices, b);
+            if (b && with_normals) std::memcpy(h + off + vbytes, x.normals, b);
+            off += b;
+        }
+        for (uint32_t i = 0; i < n_inst; i++) std::memcpy(h + dev_bytes + (size_t)i * 48, c->builder.instance_transform(i), 48);
+    }
+    if (c->d_mesh_in.n < dev_bytes) {
+        HIP_TRY(c, hipStreamSynchronize(rs));   // (an earlier update may still read the old buffer)
+        HIP_TRY(c, c->d_mesh_in.resize(dev_bytes));
+    }
+    char* hdev = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&hdev, h, 0));
+    // The BLAS records, triangle records and root boxes are shared by every copy of the instance level: the update waits on the
+    // device for every render queued before it (the context's stream follows them all) -- one pipeline drain.
+    HIP_TRY(c, hipEventRecord(c->ev_mesh_drain, s));
+    HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_mesh_drain, 0));
+    HIP_TRY(c, hipMemcpyAsync(c->d_mesh_in.p, h, dev_bytes, hipMemcpyHostToDevice, rs));
+    MeshRefitArgs a;
+    a.bounds = reinterpret_cast<int32_t*>(c->d_mesh_in.p);
+    a.verts = reinterpret_cast<const float*>(c->d_mesh_in.p + head);
+    a.normals = with_normals ? reinterpret_cast<const float*>(c->d_mesh_in.p + head + vbytes) : nullptr;
+    a.vidx = c->d_tri_vidx.p;
+    a.tri_first = mr.tri_first;
+    a.n_tris = mr.n_tris;
+    a.wtris = c->d_wtris.p;
+    a.shade = c->d_shade_tris.p;
+    a.nodes4 = c->d_nodes4.p;
+    a.nodesq = c->d_nodesq.p;
+    a.order = c->d_mesh_order.p;
+    a.level_start = c->d_mesh_levels.p + mr.level_first;
+    a.root4 = mr.root4;
+    a.bvh = c->d_bvh.p;
+    a.bvh_root = mr.bvh_root;
+    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->ref.inst_cut_boxes.empty();
+    a.cut_range = cuts ? c->d_cut_range.p : nullptr;
+    a.instances = c->d_instances.p;   // (blas_index is the same in every copy of the instance level)
+    a.n_instances = n_inst;
+    launch_mesh_refit(rs, a, c->mesh_levels_h.data() + mr.level_first, mr.n_levels);
+    HIP_TRY(c, hipGetLastError());
+    // the instance level over the new root boxes, with the current transforms, as jpt_scene_refit_tlas does
+    rc = queue_instance_refit(c, reinterpret_cast<const float*>(hdev + dev_bytes), n_inst);
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->ev_mesh_copied[st], rs));
+    c->cull_boxes_current = false;   // the host's TLAS boxes are stale: no sky cull until the next upload
+    c->refit_active = true;
+    c->ds.x.tlas_current = false;
+    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return JPT_OK;
+}
+
+int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void* nodesq_out, uint32_t node_capacity, void* tris_out,
+                           void* shade_out, uint32_t tri_capacity, int32_t* info_out)
+{
+    if (!c || !info_out) return JPT_E_INVALID;
+    if (!c->host_scene_ready || c->building || !c->from_commit || c->build_mode != BuildMode::SahWatertight || !c->native_tree)
+        return fail(c, JPT_E_STATE, "jpt_debug_mesh_records needs a scene committed with JPT_BUILD_SAH_WATERTIGHT");
+    if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the records are on the device");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = ensure_mesh_refit(c);
+    if (rc != JPT_OK) return rc;
+    const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
+    info_out[0] = mr.has_tree ? 1 : 0;
+    info_out[1] = mr.root4;
+    info_out[2] = (int32_t)mr.rec_first;
+    info_out[3] = (int32_t)mr.n_recs;
+    info_out[4] = (int32_t)mr.tri_first;
+    info_out[5] = (int32_t)mr.n_tris;
+    if (!mr.has_tree) return JPT_OK;
+    if ((nodes4_out || nodesq_out) && node_capacity < mr.n_recs) return fail(c, JPT_E_INVALID, "record buffers too small");
+    if ((tris_out || shade_out) && tri_capacity < mr.n_tris) return fail(c, JPT_E_INVALID, "triangle buffers too small");
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the context's stream follows every update)
+    if (nodes4_out && mr.n_recs)
+        HIP_TRY(c, hipMemcpy(nodes4_out, c->d_nodes4.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNode4), hipMemcpyDeviceToHost));
+    if (nodesq_out && mr.n_recs)
+        HIP_TRY(c, hipMemcpy(nodesq_out, c->d_nodesq.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
+    if (tris_out) HIP_TRY(c, hipMemcpy(tris_out, c->d_wtris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(WideTri), hipMemcpyDeviceToHost));
+    if (shade_out) HIP_TRY(c, hipMemcpy(shade_out, c->d_shade_tris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(ShadeTri), hipMemcpyDeviceToHost));
     return JPT_OK;
 }
 
@@ -1850,6 +2104,8 @@ int jpt_scene_update_reference_tlas(jpt_ctx* c, const void* blas_instances, uint
 int jpt_scene_get_reference_buffer(jpt_ctx* c, int32_t which, void* out, size_t capacity, size_t* size_out)
 {
     if (!c) return JPT_E_INVALID;
+    if (c->mesh_deformed)
+        return fail(c, JPT_E_STATE, "a mesh was deformed on the device (jpt_scene_update_mesh): the host's copy of the scene is stale until the next jpt_scene_commit");
     if (c->refit_active && (which == JPT_BUF_INSTANCES || which == JPT_BUF_TLAS_NODES || which == JPT_BUF_REACH_INSTANCES)) {
         // the instance level was last refitted on the device: bring the host mirrors (and the device) to a fresh build
         const int rc = jpt_scene_update_tlas(c);

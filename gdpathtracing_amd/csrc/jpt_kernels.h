@@ -249,6 +249,31 @@ void launch_tlas4_refit(hipStream_t stream, const float* transforms12, uint32_t 
                         ReachInst* reach_instances /* may be null */, WideNodeQ* nodesq, uint32_t n_tlas_records,
                         const float* cut_boxes = nullptr, const uint32_t* cut_range = nullptr /* RefScene::inst_cut_*: may be null */);
 
+// Deforming a committed mesh without the host (jpt_scene_update_mesh, jpt_kernels_mesh.hip): the mesh's triangle records from new
+// vertices, its four-child BLAS records refitted bottom-up (order / level_start: refit4_schedule of the mesh, on the device;
+// h_level_start: the same on the host, absolute indices into `order`), its root box in `bvh`, and the cut boxes of its instances
+// dropped.  Every pointer is a device pointer.
+struct MeshRefitArgs {
+    const float* verts = nullptr;        // the mesh's vertices, surfaces end to end (3 floats each)
+    const float* normals = nullptr;      // the same layout, or null: the vertex normals stay
+    const uint32_t* vidx = nullptr;      // per triangle of the scene (device order): its three indices into verts
+    uint32_t tri_first = 0, n_tris = 0;  // the mesh's triangles
+    WideTri* wtris = nullptr;
+    ShadeTri* shade = nullptr;
+    int32_t* bounds = nullptr;           // 6 ordered keys (jpt_mesh_math.h): min xyz preset to +FLT_MAX, max xyz to -FLT_MAX
+    WideNode4* nodes4 = nullptr;
+    WideNodeQ* nodesq = nullptr;
+    const uint32_t* order = nullptr;
+    const uint32_t* level_start = nullptr;
+    int32_t root4 = 0;                   // the mesh's root reference in nodes4 (a leaf reference when the mesh is one leaf)
+    RefBvhNode* bvh = nullptr;
+    uint32_t bvh_root = 0;               // the mesh's root in bvh (RefScene::mesh_roots)
+    uint32_t* cut_range = nullptr;       // RefScene::inst_cut_range (may be null)
+    const RefInstance* instances = nullptr;
+    uint32_t n_instances = 0;
+};
+void launch_mesh_refit(hipStream_t stream, const MeshRefitArgs& args, const uint32_t* h_level_start, uint32_t n_levels);
+
 // one dispatch of temporal_reprojection.glsl over a whole image (jpt_kernels_post.hip): screen rgba8 in/out, depth
 // read-only, hist1 / hist2 the two rgba32f history images
 void launch_temporal(hipStream_t stream, const RefTemporalParams& tp, uint32_t* screen, const float* depth, float4* hist1,

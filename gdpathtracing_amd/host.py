@@ -28,6 +28,16 @@ def _ptr(a):
 _live_contexts = weakref.WeakSet()
 
 
+def _update_surfaces(mesh: scenes.Mesh, with_normals: bool = True):
+    """jpt_surface array of a deformed mesh for jpt_scene_update_mesh (uvs are not read); the caller keeps `mesh` alive"""
+    arr = (capi.Surface * len(mesh.surfaces))()
+    for i, s in enumerate(mesh.surfaces):
+        arr[i].vertices, arr[i].indices = _ptr(s.vertices), _ptr(s.indices)
+        arr[i].normals = _ptr(s.normals) if with_normals else None
+        arr[i].n_vertices, arr[i].n_indices = len(s.vertices), len(s.indices)
+    return arr
+
+
 @atexit.register
 def _close_live_contexts():
     # contexts the caller forgot to close are destroyed while the HIP runtime is still up (this handler is registered
@@ -178,6 +188,31 @@ class Context:
         a, b = np.ascontiguousarray(instances), np.ascontiguousarray(tlas_nodes)
         self._ck(self._lib.jpt_scene_update_reference_tlas(self.h, _ptr(a), len(a), _ptr(b), len(b)), "jpt_scene_update_reference_tlas")
 
+    def update_mesh(self, mesh_id: int, mesh: scenes.Mesh, with_normals: bool = True):
+        """New vertex positions (and normals, unless with_normals=False) for mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT
+        commit: same surfaces, vertex counts and index arrays as at commit.  Triangle records and BLAS boxes are refitted on
+        the device (jpt_scene_update_mesh); no host rebuild, no synchronisation."""
+        arr = _update_surfaces(mesh, with_normals)
+        self._ck(self._lib.jpt_scene_update_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_scene_update_mesh")
+
+    def debug_mesh_records(self, mesh_id: int):
+        """The device's records of one mesh (jpt_debug_mesh_records): dict with the info words and, when the device holds a
+        tree for the mesh, `nodes4` (uint8 [n, 128]), `nodesq` (uint8 [n, 64]), `tris` (uint8 [t, 48]), `shade` (uint8 [t, 64])."""
+        info = (C.c_int32 * 6)()
+        L = self._lib
+        self._ck(L.jpt_debug_mesh_records(self.h, mesh_id, None, None, 0, None, None, 0, info), "jpt_debug_mesh_records")
+        out = dict(has_tree=bool(info[0]), root=int(info[1]), first_record=int(info[2]), n_records=int(info[3]),
+                   first_tri=int(info[4]), n_tris=int(info[5]))
+        if not out["has_tree"]:
+            return out
+        n, t = out["n_records"], out["n_tris"]
+        nodes4, nodesq = np.zeros((n, 128), np.uint8), np.zeros((n, 64), np.uint8)
+        tris, shade = np.zeros((t, 48), np.uint8), np.zeros((t, 64), np.uint8)
+        self._ck(L.jpt_debug_mesh_records(self.h, mesh_id, _ptr(nodes4), _ptr(nodesq), n, _ptr(tris), _ptr(shade), t, info),
+                 "jpt_debug_mesh_records")
+        out.update(nodes4=nodes4, nodesq=nodesq, tris=tris, shade=shade)
+        return out
+
     def reference_buffer(self, which: int, dtype) -> np.ndarray:
         n = C.c_size_t()
         self._ck(self._lib.jpt_scene_get_reference_buffer(self.h, which, None, 0, C.byref(n)), "jpt_scene_get_reference_buffer")
@@ -313,6 +348,16 @@ class GeometryGroup3D:
             else:
                 self.ctx.update_tlas()
         return moved
+
+    def update_mesh(self, mesh_index: int, mesh: Optional[scenes.Mesh] = None):
+        """A deformed mesh without build() again (the reference rebuilds the whole group): `mesh` (default: the scene's own
+        mesh object, changed in place) has the vertex counts and index arrays it had at build(); the library refits that mesh's
+        triangle records and BLAS boxes on the device (the group must be built with capi.BUILD_SAH_WATERTIGHT)."""
+        if mesh is None:
+            mesh = self.scene.meshes[mesh_index]
+        else:
+            self.scene.meshes[mesh_index] = mesh
+        self.ctx.update_mesh(mesh_index, mesh)
 
     def get_triangles_geometry_buffer(self):            # geometry_group3d.cpp:40
         return self.ctx.reference_buffer(capi.BUF_TRI_GEOMETRY, wire.TRI_GEOMETRY)
@@ -470,6 +515,10 @@ class MultiContext:
     def update_reference_tlas(self, instances, tlas_nodes):
         a, b = np.ascontiguousarray(instances), np.ascontiguousarray(tlas_nodes)
         self._ck(self._lib.jpt_multi_update_reference_tlas(self.h, _ptr(a), len(a), _ptr(b), len(b)), "jpt_multi_update_reference_tlas")
+
+    def update_mesh(self, mesh_id: int, mesh: scenes.Mesh, with_normals: bool = True):
+        arr = _update_surfaces(mesh, with_normals)
+        self._ck(self._lib.jpt_multi_update_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_multi_update_mesh")
 
     def set_params(self, width, height, max_bounces=4, accum_mode=capi.ACCUM_REF_LDR8, sampler_mode=0):
         self._ck(self._lib.jpt_multi_set_params(self.h, width, height, max_bounces, accum_mode, sampler_mode), "jpt_multi_set_params")

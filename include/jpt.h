@@ -300,6 +300,26 @@ int jpt_scene_update_tlas(jpt_ctx *ctx);
  *   re-optimises the topology: call it now and then when instances travel far).  The closest hit does not depend on
  *   the topology, so the image equals a fresh commit of the moved scene except at exact distance ties. */
 int jpt_scene_refit_tlas(jpt_ctx *ctx, const float *transforms12, uint32_t n_instances);
+/*   route (ii), on the device: new vertex positions (and normals) for mesh `mesh_id` (jpt_scene_add_mesh's id) of the
+ *   committed scene; same surfaces, vertex counts and index arrays as at jpt_scene_add_mesh (otherwise: JPT_E_INVALID,
+ *   "topology changed: commit the scene again").  Replaces GeometryGroup3D::build() of the whole scene, which is what a
+ *   changed mesh costs in the reference (a skinned MeshInstance3D's surface arrays each frame).  Read: `vertices`, and
+ *   `normals` when non-NULL (for every surface of the mesh or for none; NULL keeps the committed normals); `uvs` is not read,
+ *   the committed uvs and material slots stay.  Kernels on the refit stream make the mesh's triangle records from the new
+ *   vertices, refit the boxes of its BLAS records bottom-up over the topology of the last commit, and refit the instance level
+ *   as jpt_scene_refit_tlas does with the current transforms; the vertices go through a pinned staging ring, so the host does
+ *   not wait (except when a staging slot is reused).  The BLAS records are shared by every render, so the update waits on the
+ *   device for every render queued before it: ONE PIPELINE DRAIN on the device per update; the renders queued after it wait
+ *   for it.  The image of every later render equals a fresh JPT_BUILD_SAH_WATERTIGHT commit of the deformed scene except at
+ *   exact distance ties; the topology stays the last commit's, so the boxes grow with the deformation -- a new commit
+ *   re-optimises the tree: call it now and then when a mesh deforms far.  JPT_BUILD_SAH_WATERTIGHT scenes only (JPT_E_STATE
+ *   otherwise: JPT_BUILD_SAH's reach records and tie shadow are the reference builder's tree of the old vertices, and
+ *   reference-exact trees are the reference's own).  Until the next jpt_scene_commit the host's copy of the scene is stale:
+ *   jpt_scene_update_tlas, jpt_scene_share, jpt_scene_get_reference_buffer and renders with JPT_KERNEL_REFERENCE_LAYOUT or
+ *   debug steps return JPT_E_STATE, and the sky cull is off; jpt_scene_refit_tlas keeps working.  A mesh that no instance
+ *   names has nothing on the device: its update succeeds and changes nothing there.  Host-only contexts: JPT_E_DEVICE after
+ *   the argument checks. */
+int jpt_scene_update_mesh(jpt_ctx *ctx, uint32_t mesh_id, const jpt_surface *surfaces, int32_t n_surfaces);
 /*   route (i): the caller re-ran BLASInstance::set_transform / TLAS::build itself; same instance count and
  *   the same blas_index per instance as the uploaded scene (otherwise: JPT_E_INVALID, upload the whole scene) */
 int jpt_scene_update_reference_tlas(jpt_ctx *ctx, const void *blas_instances, uint32_t n_instances,
@@ -460,6 +480,8 @@ int jpt_multi_update_tlas(jpt_multi *m);
 int jpt_multi_refit_tlas(jpt_multi *m, const float *transforms12, uint32_t n_instances);
 int jpt_multi_update_reference_tlas(jpt_multi *m, const void *blas_instances, uint32_t n_instances,
                                     const void *tlas_nodes, uint32_t n_tlas_nodes);
+/* jpt_scene_update_mesh on every rank's replica */
+int jpt_multi_update_mesh(jpt_multi *m, uint32_t mesh_id, const jpt_surface *surfaces, int32_t n_surfaces);
 int jpt_multi_set_params(jpt_multi *m, int32_t width, int32_t height, int32_t max_bounces, int32_t accum_mode, int32_t sampler_mode);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
@@ -492,6 +514,15 @@ int jpt_debug_quantize_nodes4(const void *nodes4, uint32_t n_nodes, void *nodesq
 int jpt_debug_node_step4(int device_id, const void *nodes4, uint32_t n_nodes, const void *cases32, uint32_t n_cases,
                          int32_t host_rcp_ulps, uint8_t *taken_out);
 const char *jpt_debug_last_error(void);
+/* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
+ * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
+ * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form
+ * (64 B) of indices first .. first + count - 1 of the one index space (child references count from its start; a leaf
+ * reference names triangles of the scene); triangles: WideTri (48 B: v0, nx, e1, ny, e2, nz) and ShadeTri (64 B: n0 n1 n2,
+ * uvs, material slot) of the mesh's triangles in device order.  Any output may be NULL; capacities in records / triangles.
+ * Waits for the context's stream. */
+int jpt_debug_mesh_records(jpt_ctx *ctx, uint32_t mesh_id, void *nodes4_out, void *nodesq_out, uint32_t node_capacity,
+                           void *tris_out, void *shade_out, uint32_t tri_capacity, int32_t *info_out);
 
 /* ---- environment ------------------------------------------------------------------------------------------------------
  * The library READS these once per process (at the first jpt_create; gdpathtracing_amd/csrc/jpt_tuning.h) and never writes the

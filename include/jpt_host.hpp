@@ -486,6 +486,7 @@ class GeometryGroup3D {
             check(ctx, jpt_scene_add_mesh(ctx, sv.data(), (int32_t)sv.size(), &id), "jpt_scene_add_mesh");
             ids.push_back(id);
         }
+        built_meshes_ = meshes;
         built_transforms_.clear();
         for (const NodeRef& r : nodes) {  // :322-341
             float t12[12];
@@ -545,6 +546,23 @@ class GeometryGroup3D {
         return moved;
     }
 
+    // A deformed mesh (a skinned MeshInstance3D's surface arrays this frame).  The reference has no such call -- a changed mesh
+    // needs build() again.  `mesh` is one of the ArrayMesh objects the last build() collected, with the vertex counts and index
+    // arrays it had then and new vertices / normals; the library refits its triangle records and BLAS boxes on the device
+    // (jpt_scene_update_mesh; every rank's replica under attach_multi).  Needs builder == JPT_BUILD_SAH_WATERTIGHT.
+    void update_mesh(const ArrayMesh* mesh)
+    {
+        if (!ctx_) throw std::runtime_error("GeometryGroup3D::update_mesh before build");
+        const size_t id = std::find(built_meshes_.begin(), built_meshes_.end(), mesh) - built_meshes_.begin();
+        if (id == built_meshes_.size()) throw std::runtime_error("GeometryGroup3D::update_mesh: the mesh is not part of the last build()");
+        std::vector<jpt_surface> sv;
+        for (const Surface& x : mesh->surfaces)
+            sv.push_back(jpt_surface{x.vertices.data(), x.normals.empty() ? nullptr : x.normals.data(), nullptr, x.indices.data(),
+                                     (int32_t)(x.vertices.size() / 3), (int32_t)x.indices.size()});
+        if (multi_) mcheck(jpt_multi_update_mesh(multi_, (uint32_t)id, sv.data(), (int32_t)sv.size()), "jpt_multi_update_mesh");
+        else check(ctx_, jpt_scene_update_mesh(ctx_, (uint32_t)id, sv.data(), (int32_t)sv.size()), "jpt_scene_update_mesh");
+    }
+
     // geometry_group3d.cpp:40-68 (bytes as the reference emits them after a REFERENCE_EXACT build)
     PackedByteArray get_triangles_geometry_buffer() const { return get_buffer(JPT_BUF_TRI_GEOMETRY); }
     PackedByteArray get_triangles_data_buffer() const { return get_buffer(JPT_BUF_TRI_DATA); }
@@ -575,6 +593,7 @@ class GeometryGroup3D {
     std::vector<MeshInstance3D> children;
     std::vector<GpuMaterial> materials_;
     std::vector<std::array<float, 12>> built_transforms_;  // per instance, as handed to the library
+    std::vector<const ArrayMesh*> built_meshes_;           // per mesh id of the last build() (update_mesh)
     jpt_ctx* ctx_ = nullptr;
 };
 
