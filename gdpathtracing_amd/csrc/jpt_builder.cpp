@@ -799,13 +799,14 @@ ReachInst reach_instance(const float* t12, const ReachInst& mesh_root)
 // with the root's (InstanceCuts: the cut depends on the mesh alone, so it is made once per mesh).  What the reference's own box
 // decides stays with the reach records (reach_instance).
 struct InstanceCuts {
-    struct Box {
-        float c[3], e[3];   // centre, half extent
-        float lo[3], hi[3];
+    struct Cut {
+        std::vector<float> ce;     // per box: centre.xyz, half extent.xyz (the device's layout: export_to, affine_cut_box)
+        std::vector<float> lohi;   // per box: lo.xyz, hi.xyz
+        size_t size() const { return ce.size() / 6; }
     };
     const std::vector<RefBvhNode>& nodes;
     int n_boxes;
-    std::vector<std::pair<uint32_t, std::vector<Box>>> per_root;   // (a scene has few meshes; the boxes side by side, not scattered over the node array)
+    std::vector<std::pair<uint32_t, Cut>> per_root;   // (a scene has few meshes; the boxes side by side, not scattered over the node array)
 
     // 1 024 boxes per instance while the scene's instances x boxes stay below 2^18 box transforms (a TLAS
     // update is meant to take milliseconds); never fewer than 16
@@ -817,7 +818,7 @@ struct InstanceCuts {
         return (int)std::max<size_t>(std::min<size_t>((size_t)want, share), std::min<size_t>((size_t)want, 16));
     }
 
-    const std::vector<Box>& cut_of(uint32_t root)
+    const Cut& cut_of(uint32_t root)
     {
         for (const auto& e : per_root)
             if (e.first == root) return e.second;
@@ -850,19 +851,15 @@ struct InstanceCuts {
             file(nodes[n].right_child);
         }
         for (const auto& o : open) cut.push_back(o.second);
-        std::vector<Box> boxes;
+        Cut boxes;
         for (uint32_t n : cut) {
             const RefBvhNode& b = nodes[n];
             if (!(b.aabbMin.x <= b.aabbMax.x && b.aabbMin.y <= b.aabbMax.y && b.aabbMin.z <= b.aabbMax.z)) continue;   // an empty leaf's box
-            Box x;
             const float lo[3] = {b.aabbMin.x, b.aabbMin.y, b.aabbMin.z}, hi[3] = {b.aabbMax.x, b.aabbMax.y, b.aabbMax.z};
-            for (int k = 0; k < 3; k++) {
-                x.lo[k] = lo[k];
-                x.hi[k] = hi[k];
-                x.c[k] = 0.5f * (lo[k] + hi[k]);
-                x.e[k] = 0.5f * (hi[k] - lo[k]);
-            }
-            boxes.push_back(x);
+            for (int k = 0; k < 3; k++) boxes.ce.push_back(0.5f * (lo[k] + hi[k]));
+            for (int k = 0; k < 3; k++) boxes.ce.push_back(0.5f * (hi[k] - lo[k]));
+            boxes.lohi.insert(boxes.lohi.end(), lo, lo + 3);
+            boxes.lohi.insert(boxes.lohi.end(), hi, hi + 3);
         }
         per_root.emplace_back(root, std::move(boxes));
         return per_root.back().second;
@@ -877,13 +874,9 @@ struct InstanceCuts {
         if (n_boxes <= 1) return;
         std::vector<std::pair<uint32_t, uint32_t>> placed(per_root.size(), {0u, 0u});
         for (size_t r = 0; r < per_root.size(); r++) {
-            const std::vector<Box>& cut = per_root[r].second;
+            const Cut& cut = per_root[r].second;
             placed[r] = {(uint32_t)(boxes.size() / 6), cut.size() < 2 ? 0u : (uint32_t)cut.size()};
-            if (cut.size() < 2) continue;
-            for (const Box& x : cut) {
-                boxes.insert(boxes.end(), x.c, x.c + 3);
-                boxes.insert(boxes.end(), x.e, x.e + 3);
-            }
+            if (cut.size() >= 2) boxes.insert(boxes.end(), cut.ce.begin(), cut.ce.end());
         }
         for (size_t i = 0; i < instances.size(); i++)
             for (size_t r = 0; r < per_root.size(); r++)
@@ -897,41 +890,22 @@ struct InstanceCuts {
     void tighten(RefInstance& inst)
     {
         if (n_boxes <= 1 || inst.blas_index >= nodes.size()) return;
-        const std::vector<Box>& cut = cut_of(inst.blas_index);
+        const Cut& cut = cut_of(inst.blas_index);
         if (cut.size() < 2) return;
         float lo[3] = {1e34f, 1e34f, 1e34f}, hi[3] = {-1e34f, -1e34f, -1e34f};
         const float* m = inst.transform;   // column-major 4 x 4
         if (m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f) {
-            // the image of a box under an affine map: centre' -+ |M| half-extent (9 + 9 products instead of eight corners x 16); a
-            // few ulp of the coordinates away from the corner rule's box: twice its padding, on the union
-            float am[9];
-            for (int r = 0; r < 3; r++)
-                for (int k = 0; k < 3; k++) am[k * 3 + r] = std::fabs(m[k * 4 + r]);
-            for (const Box& x : cut)
-                for (int r = 0; r < 3; r++) {
-                    const float wc = m[r] * x.c[0] + m[4 + r] * x.c[1] + m[8 + r] * x.c[2] + m[12 + r];
-                    const float we = am[r] * x.e[0] + am[3 + r] * x.e[1] + am[6 + r] * x.e[2];
-                    lo[r] = std::min(lo[r], wc - we);
-                    hi[r] = std::max(hi[r], wc + we);
-                }
-            float big = 0.0f;
-            for (int r = 0; r < 3; r++) big = std::max(big, std::max(std::fabs(lo[r]), std::fabs(hi[r])));
-            const float pad = big * 4e-6f;
-            for (int r = 0; r < 3; r++) {
-                lo[r] -= pad;
-                hi[r] += pad;
-            }
+            affine_cut_box(m, cut.ce.data(), (uint32_t)cut.size(), lo, hi);   // (jpt_mesh_math.h: the device refit's code too)
         } else {
-            for (const Box& x : cut) {
+            for (size_t k = 0; k < cut.size(); k++) {
+                const float* b = &cut.lohi[6 * k];
                 Vec4 l, h;
-                instance_world_box(inst.transform, Vec4{x.lo[0], x.lo[1], x.lo[2], 1.0f}, Vec4{x.hi[0], x.hi[1], x.hi[2], 1.0f}, /*pad_box*/ true, l, h);
+                instance_world_box(inst.transform, Vec4{b[0], b[1], b[2], 1.0f}, Vec4{b[3], b[4], b[5], 1.0f}, /*pad_box*/ true, l, h);
                 lo[0] = std::min(lo[0], l.x); lo[1] = std::min(lo[1], l.y); lo[2] = std::min(lo[2], l.z);
                 hi[0] = std::max(hi[0], h.x); hi[1] = std::max(hi[1], h.y); hi[2] = std::max(hi[2], h.z);
             }
         }
-        if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) return;
-        inst.aabbMin = Vec4{std::max(inst.aabbMin.x, lo[0]), std::max(inst.aabbMin.y, lo[1]), std::max(inst.aabbMin.z, lo[2]), inst.aabbMin.w};
-        inst.aabbMax = Vec4{std::min(inst.aabbMax.x, hi[0]), std::min(inst.aabbMax.y, hi[1]), std::min(inst.aabbMax.z, hi[2]), inst.aabbMax.w};
+        clip_world_box(inst, lo, hi);
     }
 };
 

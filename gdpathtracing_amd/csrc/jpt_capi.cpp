@@ -52,6 +52,86 @@ struct DevBuf {
     }
 };
 
+// A grow-only pinned host buffer (hipHostMalloc), given back by its destructor or release()
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~PinnedBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    hipError_t reserve(size_t want)
+    {
+        if (bytes >= want) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) bytes = want;
+        return e;
+    }
+    template <typename T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// A ring of pinned staging buffers, so that the host can queue device refits ahead of the device: a stage is written again once
+// the work that last read it has run (its `copied` event)
+constexpr int kRefitStages = 4;   // refits the host may queue before it has to wait for a copy to leave its buffer
+struct StagingRing {
+    PinnedBuf buf[kRefitStages];
+    hipEvent_t copied[kRefitStages] = {};
+    uint64_t seq = 0;
+    ~StagingRing()
+    {
+        for (hipEvent_t e : copied)
+            if (e) (void)hipEventDestroy(e);
+    }
+    // the next stage, of at least `bytes`, once the work that used it last has run
+    hipError_t next(size_t bytes, int& st)
+    {
+        st = (int)(seq++ % (uint64_t)kRefitStages);
+        hipError_t e = copied[st] ? hipEventSynchronize(copied[st]) : hipEventCreateWithFlags(&copied[st], hipEventDisableTiming);
+        return e == hipSuccess ? buf[st].reserve(bytes) : e;
+    }
+};
+
+// Several copies of the instance level (RefInstance + WideInstance arrays, TLAS tail of the four-child records): a refit writes a
+// copy the renders in flight do NOT read, so the renders after a refit overlap with the renders before it.
+constexpr int kInstanceSets = 8;   // as many as renders in flight can be: a queue of animation steps stays pipelined
+
+// Every scene array on the device; the view the kernels take (jpt_ctx::ds) points into these (set_scene_view)
+struct SceneBufs {
+    // reference layout
+    DevBuf<RefTriGeometry> tri_geom;
+    DevBuf<ShadeTri> shade_tris;
+    DevBuf<RefMaterial> materials;
+    DevBuf<RefBvhNode> bvh;
+    DevBuf<RefTlasNode> tlas;
+    DevBuf<uint8_t> tex;
+    // flattened layout
+    DevBuf<WideNode> wblas, wtlas;
+    DevBuf<WideTri> wtris;
+    DevBuf<WideInstance> winst;
+    DevBuf<WideNode4> nodes4;   // four-child records: BLAS part, then one TLAS tail per copy of the instance level (one index space)
+    DevBuf<WideNodeQ> nodesq;   // their quantised form (jpt_nodeq.h), same indices: what the kernels walk
+    // the instance level, one copy per kInstanceSets; copy 0 is the one uploads write (the reach records: JPT_BUILD_SAH)
+    struct InstanceSet {
+        DevBuf<RefInstance> inst;
+        DevBuf<WideInstance> winst4;
+        DevBuf<ReachInst> reach;
+    } set[kInstanceSets];
+    DevBuf<ReachTri> reach_tri;   // reach records per triangle
+    DevBuf<float> cut_boxes;      // RefScene::inst_cut_boxes / inst_cut_range (device refits)
+    DevBuf<uint32_t> cut_range;
+    // the reference's own trees beside a native scene (ExactShadow): two-child records + the triangle map
+    DevBuf<RefBvhNode> x_bvh;
+    DevBuf<RefTriGeometry> x_tri_geom;
+    DevBuf<RefInstance> x_inst;
+    DevBuf<RefTlasNode> x_tlas;
+    DevBuf<uint32_t> x_tri_native, x_native_ref, x_tri_leaf, x_subtree_end, x_tlas_parent, x_inst_leaf;
+};
+
 // One render in flight (jpt_render_async): its stream, its workspace and the events that order it.  Slot 0's workspace is
 // also the one renders on the context's own stream use.
 struct PipeSlot {
@@ -75,7 +155,8 @@ struct jpt_ctx {
     SceneBuilder builder;
     RefScene ref;
     WideScene wide;
-    bool building = false, scene_ready = false, ref_is_exact = false, native_tree = false, tlas_dirty = false;
+    bool building = false, scene_ready = false, tlas_dirty = false;
+    int32_t tree = JPT_TREE_NONE;   // the JPT_TREE_* of the scene in c->ref (jpt_scene_tree_kind answers it once host_scene_ready)
     bool host_scene_ready = false;  // c->ref / c->wide hold a complete scene (also true on host-only contexts)
     bool from_commit = false;       // the scene came from jpt_scene_commit: c->builder holds its meshes and transforms
     int32_t upload_mode = JPT_UPLOAD_NATIVE_TREE;  // jpt_set_upload_mode
@@ -89,29 +170,7 @@ struct jpt_ctx {
     int32_t pending_tex_res = 0, pending_layers = 0;
 
     // device scene
-    DevBuf<RefTriGeometry> d_tri_geom;
-    DevBuf<ShadeTri> d_shade_tris;
-    DevBuf<RefMaterial> d_materials;
-    DevBuf<RefBvhNode> d_bvh;
-    DevBuf<RefInstance> d_instances;
-    DevBuf<RefTlasNode> d_tlas;
-    DevBuf<uint8_t> d_tex;
-    DevBuf<WideNode> d_wblas, d_wtlas;
-    DevBuf<WideTri> d_wtris;
-    DevBuf<WideInstance> d_winst, d_winst4;
-    DevBuf<WideNode4> d_nodes4;   // four-child records: BLAS part, then room for the TLAS part (one index space)
-    DevBuf<WideNodeQ> d_nodesq;   // their quantised form (jpt_nodeq.h), same indices: what the kernels walk
-    // the reference's own trees beside a native scene (ExactShadow): two-child records + the triangle map
-    DevBuf<RefBvhNode> d_x_bvh;
-    DevBuf<RefTriGeometry> d_x_tri_geom;
-    DevBuf<RefInstance> d_x_inst;
-    DevBuf<RefTlasNode> d_x_tlas;
-    DevBuf<uint32_t> d_x_tri_native, d_x_native_ref, d_x_tri_leaf, d_x_subtree_end, d_x_tlas_parent, d_x_inst_leaf;
-    DevBuf<ReachTri> d_reach_tri;   // reach records (JPT_BUILD_SAH): per triangle / per instance (one per copy of the instance level)
-    DevBuf<ReachInst> d_reach_inst;
-    DevBuf<float> d_cut_boxes;         // RefScene::inst_cut_boxes / inst_cut_range (device refits)
-    DevBuf<uint32_t> d_cut_range;
-    BuildMode build_mode = BuildMode::ReferenceExact;
+    SceneBufs dev;
     DeviceScene ds;
 
     // per-render state
@@ -162,19 +221,8 @@ struct jpt_ctx {
     DevBuf<float4> d_hist1, d_hist2;   // frameBuffer1 / frameBuffer2 of temporal_reprojection.glsl:16-17
     float4* hist_written = nullptr;    // the one the last temporal pass wrote
 
-    // pinned staging for the split read-back
     // device refit of the instance level (jpt_scene_refit_tlas)
-    static constexpr int kRefitStages = 4;   // refits the host may queue before it has to wait for a copy to leave its buffer
-    float* h_refit_t12[kRefitStages] = {};   // pinned staging for the transforms
-    size_t h_refit_floats[kRefitStages] = {};
-    hipEvent_t ev_refit_copied[kRefitStages] = {};
-    uint64_t refit_seq = 0;
-    // Several copies of the instance level (RefInstance + WideInstance arrays, TLAS tail of d_nodes4): a refit writes
-    // a copy the renders in flight do NOT read, so the renders after a refit overlap with the renders before it.
-    static constexpr int kInstanceSets = 8;   // as many as renders in flight can be: a queue of animation steps stays pipelined
-    DevBuf<RefInstance> d_instances_more[kInstanceSets - 1];
-    DevBuf<WideInstance> d_winst4_more[kInstanceSets - 1];
-    DevBuf<ReachInst> d_reach_inst_more[kInstanceSets - 1];
+    StagingRing refit_stage;           // pinned staging for the transforms
     size_t tlas4_cap = 0;              // records reserved per TLAS tail
     int cur_set = 0;                   // which copy new renders read
     bool set_b_ready = false;          // copies 1.. exist and mirror the last host upload
@@ -188,14 +236,14 @@ struct jpt_ctx {
     bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
     bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
     std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
-    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in d_nodes4 and its schedule
+    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in dev.nodes4 and its schedule
     // (refit4_schedule), made at the first update after an upload
     struct MeshRefit {
         bool has_tree = false;              // an instance names the mesh and it has triangles: the device holds its tree
-        int32_t root4 = 0;                  // its root reference in d_nodes4
-        uint32_t bvh_root = 0;              // its root in d_bvh (RefScene::mesh_roots)
+        int32_t root4 = 0;                  // its root reference in dev.nodes4
+        uint32_t bvh_root = 0;              // its root in dev.bvh (RefScene::mesh_roots)
         uint32_t tri_first = 0, n_tris = 0;
-        uint32_t rec_first = 0, n_recs = 0;  // the span of d_nodes4 its records occupy
+        uint32_t rec_first = 0, n_recs = 0;  // the span of dev.nodes4 its records occupy
         uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
     };
     std::vector<MeshRefit> mesh_refit;
@@ -203,15 +251,11 @@ struct jpt_ctx {
     std::vector<uint32_t> mesh_order_h, mesh_levels_h;
     DevBuf<uint32_t> d_mesh_order, d_mesh_levels, d_tri_vidx;
     DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
-    char* h_mesh_stage[kRefitStages] = {};   // pinned staging ring for the updates (header, vertices, normals, transforms)
-    size_t h_mesh_bytes[kRefitStages] = {};
-    hipEvent_t ev_mesh_copied[kRefitStages] = {}, ev_mesh_drain = nullptr;
-    uint64_t mesh_seq = 0;
+    StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
+    hipEvent_t ev_mesh_drain = nullptr;
     bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
-    uint32_t* h_ldr_pinned = nullptr;
-    size_t h_ldr_pinned_px = 0;
-    void* h_read_pinned = nullptr;   // blocking read-backs (staged_read)
-    size_t h_read_bytes = 0;
+    PinnedBuf h_ldr_pinned;    // the split read-back of the display image
+    PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
     hipEvent_t ev_readback = nullptr;
     bool readback_pending = false;
     bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
@@ -259,12 +303,7 @@ int32_t max_rows_of_any_rank(int32_t height, int32_t world)
 // The blocking read-backs' pinned staging buffer grows to the largest read-back ever made (133 MB after one jpt_read_accum_f32 of a
 // 3840 x 2160 image) and would otherwise be held until jpt_destroy: given back whenever the framebuffers are re-made (another
 // resolution or partition) and by jpt_set_memory_policy; the next read-back allocates what it needs.
-void release_read_staging(jpt_ctx* c)
-{
-    if (c->h_read_pinned) (void)hipHostFree(c->h_read_pinned);
-    c->h_read_pinned = nullptr;
-    c->h_read_bytes = 0;
-}
+void release_read_staging(jpt_ctx* c) { c->h_read_pinned.release(); }
 
 int alloc_framebuffers(jpt_ctx* c)
 {
@@ -286,6 +325,74 @@ int alloc_framebuffers(jpt_ctx* c)
     return JPT_OK;
 }
 
+// the kernels walk the four-child records of the native tree (the native builder's trees and native uploads); reference-exact and
+// as-given trees keep the two-child records so the kernels visit them node for node like main.glsl (event counters equal the
+// oracle's)
+bool walks_nodes4(const jpt_ctx* c) { return c->tree == JPT_TREE_NATIVE_REACH || c->tree == JPT_TREE_NATIVE_WATERTIGHT; }
+
+// the builder's mode for the scene's tree (an as-given upload: ReferenceExact; rebuild_instances only sees committed scenes)
+BuildMode build_mode(const jpt_ctx* c)
+{
+    if (c->tree == JPT_TREE_NATIVE_REACH) return BuildMode::Sah;
+    if (c->tree == JPT_TREE_NATIVE_WATERTIGHT) return BuildMode::SahWatertight;
+    return BuildMode::ReferenceExact;
+}
+
+// The view the kernels take (c->ds) of the scene's device arrays (c->dev): the counts from c->ref / c->wide, the instance level the
+// copy new renders read (cur_set).  Whether the tie shadow is usable and current (ds.x.ok, ds.x.tlas_current) is upload_shadow's.
+void set_scene_view(jpt_ctx* c)
+{
+    const SceneBufs& b = c->dev;
+    const SceneBufs::InstanceSet& is = b.set[c->cur_set];
+    const RefScene& r = c->ref;
+    const WideScene& w = c->wide;
+    DeviceScene& d = c->ds;
+    const bool reach = !r.reach_tri.empty() && r.reach_tri.size() == r.tri_geom.size() && r.reach_inst.size() == r.instances.size();
+    d.reach_tri = reach ? b.reach_tri.p : nullptr;
+    d.reach_inst = reach ? is.reach.p : nullptr;
+    d.ref_tri_geom = b.tri_geom.p;
+    d.shade_tris = b.shade_tris.p;
+    d.ref_materials = b.materials.p;
+    d.ref_bvh = b.bvh.p;
+    d.ref_instances = is.inst.p;
+    d.ref_tlas = b.tlas.p;
+    d.tex = b.tex.p;
+    d.n_tris = (uint32_t)r.tri_geom.size();
+    d.n_materials = (uint32_t)r.materials.size();
+    d.n_ref_bvh = (uint32_t)r.bvh_nodes.size();
+    d.n_instances = (uint32_t)r.instances.size();
+    d.n_ref_tlas = (uint32_t)r.tlas_nodes.size();
+    d.tex_res = r.tex_res;
+    d.n_layers = r.n_layers;
+    d.blas_nodes = b.wblas.p;
+    d.wide_tris = b.wtris.p;
+    d.tlas_nodes = b.wtlas.p;
+    d.wide_instances = b.winst.p;
+    d.tlas_root = w.tlas_root;
+    d.n_blas_nodes = (uint32_t)w.blas_nodes.size();
+    d.n_tlas_nodes = (uint32_t)w.tlas_nodes.size();
+    d.use4 = walks_nodes4(c);
+    d.stack_need4 = w.stack_need4;
+    d.wide_instances4 = is.winst4.p;
+    // upload_nodes4: the BLAS records, then the TLAS tail of each copy
+    const bool any4 = !w.instances4.empty() || !w.blas_nodes4.empty();
+    const size_t tail_base = w.blas_nodes4.size() + (size_t)c->cur_set * c->tlas4_cap;
+    d.nodes4 = any4 ? b.nodes4.p : nullptr;
+    d.nodesq = any4 ? b.nodesq.p : nullptr;
+    d.tlas_root4 = !any4 ? 0 : w.tlas_root4 >= 0 ? w.tlas_root4 + (int32_t)tail_base : w.tlas_root4;
+    TieShadowDev& x = d.x;
+    x.bvh = b.x_bvh.p;
+    x.tri_geom = b.x_tri_geom.p;
+    x.instances = b.x_inst.p;
+    x.tlas = b.x_tlas.p;
+    x.tri_native = b.x_tri_native.p;
+    x.native_ref = b.x_native_ref.p;
+    x.tri_leaf = b.x_tri_leaf.p;
+    x.subtree_end = b.x_subtree_end.p;
+    x.tlas_parent = b.x_tlas_parent.p;
+    x.inst_tlas_leaf = b.x_inst_leaf.p;
+}
+
 // Four-child records on the device: [ BLAS records | TLAS records ], internal child references of the TLAS part and
 // the TLAS root shifted by the BLAS count.  The TLAS part has room for the largest TLAS of this instance count
 // (<= one record per instance), so a TLAS update rewrites the tail only.
@@ -294,47 +401,40 @@ int upload_nodes4(jpt_ctx* c, bool tlas_only)
     const WideScene& w = c->wide;
     const size_t nb = w.blas_nodes4.size(), nt = w.tlas_nodes4.size();
     const size_t cap_t = std::max<size_t>(w.instances4.size(), std::max<size_t>(nt, 1));
-    const size_t cap = nb + (size_t)jpt_ctx::kInstanceSets * cap_t;  // one TLAS tail per copy of the instance level (jpt_scene_refit_tlas)
+    const size_t cap = nb + (size_t)kInstanceSets * cap_t;  // one TLAS tail per copy of the instance level (jpt_scene_refit_tlas)
     hipStream_t s = c->stream;
-    if (w.instances4.empty() && nb == 0) {
-        c->ds.nodes4 = nullptr;
-        c->ds.nodesq = nullptr;
-        c->ds.tlas_root4 = 0;
-        return JPT_OK;
-    }
+    c->cur_set = 0;
+    c->set_b_ready = false;  // the instance arrays of the other copies are made (again) by the next refit
+    for (bool& v : c->set_retired_valid) v = false;
+    if (w.instances4.empty() && nb == 0) return JPT_OK;
     auto quantised = [](const std::vector<WideNode4>& in) {
         std::vector<WideNodeQ> out(in.size());
         for (size_t i = 0; i < in.size(); i++) quantize_node4(in[i], out[i]);
         return out;
     };
-    if (!tlas_only || c->d_nodes4.n < cap) {
-        HIP_TRY(c, c->d_nodes4.resize(cap));
-        HIP_TRY(c, c->d_nodesq.resize(cap));
+    SceneBufs& b = c->dev;
+    if (!tlas_only || b.nodes4.n < cap) {
+        HIP_TRY(c, b.nodes4.resize(cap));
+        HIP_TRY(c, b.nodesq.resize(cap));
         if (nb) {
             const std::vector<WideNodeQ> q = quantised(w.blas_nodes4);
-            HIP_TRY(c, hipMemcpyAsync(c->d_nodes4.p, w.blas_nodes4.data(), nb * sizeof(WideNode4), hipMemcpyHostToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(c->d_nodesq.p, q.data(), nb * sizeof(WideNodeQ), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(b.nodes4.p, w.blas_nodes4.data(), nb * sizeof(WideNode4), hipMemcpyHostToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(b.nodesq.p, q.data(), nb * sizeof(WideNodeQ), hipMemcpyHostToDevice, s));
             HIP_TRY(c, hipStreamSynchronize(s));  // `q` is pageable host memory
         }
     }
-    for (int copy = 0; copy < jpt_ctx::kInstanceSets; copy++) {
+    for (int copy = 0; copy < kInstanceSets; copy++) {
         const size_t base = nb + (size_t)copy * cap_t;
         std::vector<WideNode4> tail(w.tlas_nodes4);
         for (WideNode4& n : tail)
             for (int k = 0; k < 4; k++)
                 if (n.child[k] >= 0) n.child[k] += (int32_t)base;
         const std::vector<WideNodeQ> qtail = quantised(tail);
-        if (nt) HIP_TRY(c, hipMemcpyAsync(c->d_nodes4.p + base, tail.data(), nt * sizeof(WideNode4), hipMemcpyHostToDevice, s));
-        if (nt) HIP_TRY(c, hipMemcpyAsync(c->d_nodesq.p + base, qtail.data(), nt * sizeof(WideNodeQ), hipMemcpyHostToDevice, s));
+        if (nt) HIP_TRY(c, hipMemcpyAsync(b.nodes4.p + base, tail.data(), nt * sizeof(WideNode4), hipMemcpyHostToDevice, s));
+        if (nt) HIP_TRY(c, hipMemcpyAsync(b.nodesq.p + base, qtail.data(), nt * sizeof(WideNodeQ), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));  // `tail`, `qtail` are pageable host memory
     }
     c->tlas4_cap = cap_t;
-    c->cur_set = 0;
-    c->set_b_ready = false;  // the instance arrays of the other copies are made (again) by the next refit
-    for (int k = 0; k < jpt_ctx::kInstanceSets; k++) c->set_retired_valid[k] = false;
-    c->ds.nodes4 = c->d_nodes4.p;
-    c->ds.nodesq = c->d_nodesq.p;
-    c->ds.tlas_root4 = w.tlas_root4 >= 0 ? w.tlas_root4 + (int32_t)nb : w.tlas_root4;
     {
         // bottom-up schedule of the TLAS records, for refits on the device
         std::vector<uint32_t>&order = c->tlas4_order_h, &levels = c->tlas4_levels_h;
@@ -355,7 +455,7 @@ void note_ties(jpt_ctx* c)
 {
     const ExactShadow& x = c->ref.exact;
     c->ties_note.clear();
-    if (c->native_tree) {
+    if (walks_nodes4(c)) {
         if (c->ref.reach_tri.empty()) c->ties_note = "the scene has no reach records (JPT_BUILD_SAH_WATERTIGHT): the native tree's order decides";
         else if (x.instances.empty()) c->ties_note.clear();   // nothing to hit
         else if (!x.valid) c->ties_note = "the reference's TLAS of this scene could not be built (TLAS::build, bvh.cpp:264-317)";
@@ -371,38 +471,28 @@ void note_ties(jpt_ctx* c)
 // ties are then decided by the order of the native walk.
 int upload_shadow(jpt_ctx* c, bool instances_only)
 {
-    TieShadowDev& d = c->ds.x;
-    d.ok = false;
+    c->ds.x.ok = false;
     const ExactShadow& x = c->ref.exact;
     note_ties(c);
-    if (!x.valid || !x.resolvable || !c->native_tree || c->ref.reach_tri.empty() || c->device < 0 || x.instances.empty())
+    if (!x.valid || !x.resolvable || !walks_nodes4(c) || c->ref.reach_tri.empty() || c->device < 0 || x.instances.empty())
         return JPT_OK;
     hipStream_t s = c->stream;
+    SceneBufs& b = c->dev;
     if (!instances_only) {
-        HIP_TRY(c, c->d_x_bvh.upload(x.bvh_nodes, s));
-        HIP_TRY(c, c->d_x_tri_geom.upload(x.tri_geom, s));
-        HIP_TRY(c, c->d_x_tri_native.upload(x.tri_native, s));
-        HIP_TRY(c, c->d_x_native_ref.upload(x.native_ref, s));
-        HIP_TRY(c, c->d_x_tri_leaf.upload(x.tri_leaf, s));
-        HIP_TRY(c, c->d_x_subtree_end.upload(x.subtree_end, s));
+        HIP_TRY(c, b.x_bvh.upload(x.bvh_nodes, s));
+        HIP_TRY(c, b.x_tri_geom.upload(x.tri_geom, s));
+        HIP_TRY(c, b.x_tri_native.upload(x.tri_native, s));
+        HIP_TRY(c, b.x_native_ref.upload(x.native_ref, s));
+        HIP_TRY(c, b.x_tri_leaf.upload(x.tri_leaf, s));
+        HIP_TRY(c, b.x_subtree_end.upload(x.subtree_end, s));
     }
-    HIP_TRY(c, c->d_x_inst.upload(x.instances, s));
-    HIP_TRY(c, c->d_x_tlas.upload(x.tlas_nodes, s));
-    HIP_TRY(c, c->d_x_tlas_parent.upload(x.tlas_parent, s));
-    HIP_TRY(c, c->d_x_inst_leaf.upload(x.inst_tlas_leaf, s));
+    HIP_TRY(c, b.x_inst.upload(x.instances, s));
+    HIP_TRY(c, b.x_tlas.upload(x.tlas_nodes, s));
+    HIP_TRY(c, b.x_tlas_parent.upload(x.tlas_parent, s));
+    HIP_TRY(c, b.x_inst_leaf.upload(x.inst_tlas_leaf, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    d.bvh = c->d_x_bvh.p;
-    d.tri_geom = c->d_x_tri_geom.p;
-    d.instances = c->d_x_inst.p;
-    d.tlas = c->d_x_tlas.p;
-    d.tri_native = c->d_x_tri_native.p;
-    d.native_ref = c->d_x_native_ref.p;
-    d.tri_leaf = c->d_x_tri_leaf.p;
-    d.subtree_end = c->d_x_subtree_end.p;
-    d.tlas_parent = c->d_x_tlas_parent.p;
-    d.inst_tlas_leaf = c->d_x_inst_leaf.p;
-    d.ok = true;
-    d.tlas_current = true;
+    c->ds.x.ok = true;
+    c->ds.x.tlas_current = true;
     return JPT_OK;
 }
 
@@ -411,9 +501,7 @@ int upload_scene(jpt_ctx* c)
 {
     std::string err;
     if (!flatten(c->ref, c->wide, err)) return fail(c, JPT_E_INVALID, "flatten: " + err);
-    // the four-child collapse is for the native builder's trees; reference-exact trees keep the two-child
-    // records so the kernels visit them node for node like main.glsl (event counters equal the oracle's)
-    const bool use4 = !c->ref_is_exact && c->native_tree;
+    const bool use4 = walks_nodes4(c);
     if (use4) flatten4(c->wide);
     else {
         c->wide.blas_nodes4.clear();
@@ -438,7 +526,8 @@ int upload_scene(jpt_ctx* c)
     if (c->device < 0) return JPT_OK;  // host-only context: arrays stay on the host, nothing can be rendered
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    HIP_TRY(c, c->d_tri_geom.upload(c->ref.tri_geom, s));
+    SceneBufs& b = c->dev;
+    HIP_TRY(c, b.tri_geom.upload(c->ref.tri_geom, s));
     {
         std::vector<ShadeTri> st(c->ref.tri_data.size());
         for (size_t i = 0; i < st.size(); i++) {
@@ -450,59 +539,31 @@ int upload_scene(jpt_ctx* c)
             for (int k = 0; k < 3; k++) o.uvs[k][0] = t.uvs[k][0], o.uvs[k][1] = t.uvs[k][1];
             o.material_index = t.material_index;
         }
-        HIP_TRY(c, c->d_shade_tris.upload(st, s));
+        HIP_TRY(c, b.shade_tris.upload(st, s));
         HIP_TRY(c, hipStreamSynchronize(s));   // (the staging vector goes out of scope)
     }
-    HIP_TRY(c, c->d_materials.upload(c->ref.materials, s));
-    HIP_TRY(c, c->d_bvh.upload(c->ref.bvh_nodes, s));
-    HIP_TRY(c, c->d_instances.upload(c->ref.instances, s));
-    HIP_TRY(c, c->d_tlas.upload(c->ref.tlas_nodes, s));
-    HIP_TRY(c, c->d_tex.upload(c->ref.textures, s));
-    HIP_TRY(c, c->d_wblas.upload(c->wide.blas_nodes, s));
-    HIP_TRY(c, c->d_wtlas.upload(c->wide.tlas_nodes, s));
-    HIP_TRY(c, c->d_wtris.upload(c->wide.tris, s));
-    HIP_TRY(c, c->d_winst.upload(c->wide.instances, s));
-    HIP_TRY(c, c->d_winst4.upload(c->wide.instances4, s));
-    HIP_TRY(c, c->d_reach_tri.upload(c->ref.reach_tri, s));
-    HIP_TRY(c, c->d_reach_inst.upload(c->ref.reach_inst, s));
-    HIP_TRY(c, c->d_cut_boxes.upload(c->ref.inst_cut_boxes, s));
-    HIP_TRY(c, c->d_cut_range.upload(c->ref.inst_cut_range, s));
+    HIP_TRY(c, b.materials.upload(c->ref.materials, s));
+    HIP_TRY(c, b.bvh.upload(c->ref.bvh_nodes, s));
+    HIP_TRY(c, b.set[0].inst.upload(c->ref.instances, s));
+    HIP_TRY(c, b.tlas.upload(c->ref.tlas_nodes, s));
+    HIP_TRY(c, b.tex.upload(c->ref.textures, s));
+    HIP_TRY(c, b.wblas.upload(c->wide.blas_nodes, s));
+    HIP_TRY(c, b.wtlas.upload(c->wide.tlas_nodes, s));
+    HIP_TRY(c, b.wtris.upload(c->wide.tris, s));
+    HIP_TRY(c, b.winst.upload(c->wide.instances, s));
+    HIP_TRY(c, b.set[0].winst4.upload(c->wide.instances4, s));
+    HIP_TRY(c, b.reach_tri.upload(c->ref.reach_tri, s));
+    HIP_TRY(c, b.set[0].reach.upload(c->ref.reach_inst, s));
+    HIP_TRY(c, b.cut_boxes.upload(c->ref.inst_cut_boxes, s));
+    HIP_TRY(c, b.cut_range.upload(c->ref.inst_cut_range, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     {
         const int rc4 = upload_nodes4(c, false);
         if (rc4 != JPT_OK) return rc4;
     }
-    DeviceScene& d = c->ds;
-    const bool reach = !c->ref.reach_tri.empty() && c->ref.reach_tri.size() == c->ref.tri_geom.size() &&
-                       c->ref.reach_inst.size() == c->ref.instances.size();
-    d.reach_tri = reach ? c->d_reach_tri.p : nullptr;
-    d.reach_inst = reach ? c->d_reach_inst.p : nullptr;
-    d.ref_tri_geom = c->d_tri_geom.p;
-    d.shade_tris = c->d_shade_tris.p;
-    d.ref_materials = c->d_materials.p;
-    d.ref_bvh = c->d_bvh.p;
-    d.ref_instances = c->d_instances.p;
-    d.ref_tlas = c->d_tlas.p;
-    d.tex = c->d_tex.p;
-    d.n_tris = (uint32_t)c->ref.tri_geom.size();
-    d.n_materials = (uint32_t)c->ref.materials.size();
-    d.n_ref_bvh = (uint32_t)c->ref.bvh_nodes.size();
-    d.n_instances = (uint32_t)c->ref.instances.size();
-    d.n_ref_tlas = (uint32_t)c->ref.tlas_nodes.size();
-    d.tex_res = c->ref.tex_res;
-    d.n_layers = c->ref.n_layers;
-    d.blas_nodes = c->d_wblas.p;
-    d.wide_tris = c->d_wtris.p;
-    d.tlas_nodes = c->d_wtlas.p;
-    d.wide_instances = c->d_winst.p;
-    d.tlas_root = c->wide.tlas_root;
-    d.n_blas_nodes = (uint32_t)c->wide.blas_nodes.size();
-    d.n_tlas_nodes = (uint32_t)c->wide.tlas_nodes.size();
-    d.use4 = use4;
-    d.stack_need4 = c->wide.stack_need4;
-    d.wide_instances4 = c->d_winst4.p;
     {
         const int rcx = upload_shadow(c, false);
+        set_scene_view(c);
         if (rcx != JPT_OK) return rcx;
     }
     c->scene_ready = true;
@@ -541,7 +602,7 @@ void compute_sky_cull(const jpt_ctx* c, SkyCull& out)
     double lo[4][3], hi[4][3];
     int n = 0;
     const WideScene& w = c->wide;
-    const bool use4 = !c->ref_is_exact && c->native_tree;
+    const bool use4 = walks_nodes4(c);
     if (w.instances.empty()) return;
     if (use4) {
         if (w.tlas_root4 < 0 || (size_t)w.tlas_root4 >= w.tlas_nodes4.size()) return;  // the root is a single instance
@@ -899,7 +960,7 @@ LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, b
     const uint64_t window_paths = ((uint64_t)c->width * (uint64_t)c->local_rows - wf2_pixels_outside_window(cull, fp)) * (uint64_t)fp.n_frames;
     const size_t walked_bytes = c->wide.blas_nodes4.size() * sizeof(WideNodeQ) + c->wide.tris.size() * sizeof(WideTri);
     const bool small = window_paths <= 1500000u && walked_bytes <= ((size_t)32 << 20);
-    p.chain = (p.groups == 2 || (c->native_tree && !c->ref_is_exact && small)) ? 2 : 1;
+    p.chain = (p.groups == 2 || (walks_nodes4(c) && small)) ? 2 : 1;
     return p;
 }
 
@@ -1181,15 +1242,9 @@ void scatter_rows(const std::vector<T>& local, T* out, int32_t width, int32_t he
 // own: the split read-back's staging buffer may hold an image in flight.)
 int staged_read(jpt_ctx* c, const void* src, size_t bytes)
 {
-    if (c->h_read_bytes < bytes) {
-        if (c->h_read_pinned) (void)hipHostFree(c->h_read_pinned);
-        c->h_read_pinned = nullptr;
-        c->h_read_bytes = 0;
-        HIP_TRY(c, hipHostMalloc(&c->h_read_pinned, bytes, hipHostMallocDefault));
-        c->h_read_bytes = bytes;
-    }
+    HIP_TRY(c, c->h_read_pinned.reserve(bytes));
     if (bytes) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_read_pinned, src, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->h_read_pinned.p, src, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     return JPT_OK;
@@ -1198,13 +1253,7 @@ int staged_read(jpt_ctx* c, const void* src, size_t bytes)
 // the pinned staging buffer of the display image's split read-backs (one full image)
 int ensure_ldr_pinned(jpt_ctx* c)
 {
-    if (c->h_ldr_pinned_px < (size_t)c->width * c->height) {
-        if (c->h_ldr_pinned) (void)hipHostFree(c->h_ldr_pinned);
-        c->h_ldr_pinned = nullptr;
-        c->h_ldr_pinned_px = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_ldr_pinned, (size_t)c->width * c->height * sizeof(uint32_t), hipHostMallocDefault));
-        c->h_ldr_pinned_px = (size_t)c->width * c->height;
-    }
+    HIP_TRY(c, c->h_ldr_pinned.reserve((size_t)c->width * c->height * sizeof(uint32_t)));
     return JPT_OK;
 }
 
@@ -1293,17 +1342,9 @@ void jpt_destroy(jpt_ctx* c)
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->trace_events) (void)hipEventDestroy(e);
     if (c->ev_readback) (void)hipEventDestroy(c->ev_readback);
-    if (c->h_ldr_pinned) (void)hipHostFree(c->h_ldr_pinned);
-    if (c->h_read_pinned) (void)hipHostFree(c->h_read_pinned);
     if (c->refit_stream) { (void)hipStreamSynchronize(c->refit_stream); (void)hipStreamDestroy(c->refit_stream); }
-    for (int k = 0; k < jpt_ctx::kInstanceSets; k++) if (c->ev_set_retired[k]) (void)hipEventDestroy(c->ev_set_retired[k]);
+    for (hipEvent_t e : c->ev_set_retired) if (e) (void)hipEventDestroy(e);
     if (c->ev_refit_done) (void)hipEventDestroy(c->ev_refit_done);
-    for (int k = 0; k < jpt_ctx::kRefitStages; k++) {
-        if (c->h_refit_t12[k]) (void)hipHostFree(c->h_refit_t12[k]);
-        if (c->ev_refit_copied[k]) (void)hipEventDestroy(c->ev_refit_copied[k]);
-        if (c->h_mesh_stage[k]) (void)hipHostFree(c->h_mesh_stage[k]);
-        if (c->ev_mesh_copied[k]) (void)hipEventDestroy(c->ev_mesh_copied[k]);
-    }
     if (c->ev_mesh_drain) (void)hipEventDestroy(c->ev_mesh_drain);
     release_streams(c);
     for (hipEvent_t e : c->group_streams.join) if (e) (void)hipEventDestroy(e);
@@ -1451,9 +1492,7 @@ int jpt_scene_upload_reference_layout(jpt_ctx* c, const void* tri_geometry, uint
         c->ref.tex_res = up.tex_res;
         c->ref.n_layers = up.n_layers;
     }
-    c->ref_is_exact = false;
-    c->native_tree = native;
-    c->build_mode = native ? BuildMode::Sah : BuildMode::ReferenceExact;
+    c->tree = native ? JPT_TREE_NATIVE_REACH : JPT_TREE_AS_GIVEN;
     rc = upload_scene(c);
     c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
@@ -1471,9 +1510,7 @@ int jpt_scene_tree_kind(jpt_ctx* c)
 {
     if (!c) return JPT_E_INVALID;
     if (!c->host_scene_ready) return JPT_TREE_NONE;
-    if (c->ref_is_exact) return JPT_TREE_REFERENCE_EXACT;
-    if (!c->native_tree) return JPT_TREE_AS_GIVEN;
-    return c->build_mode == BuildMode::Sah ? JPT_TREE_NATIVE_REACH : JPT_TREE_NATIVE_WATERTIGHT;
+    return c->tree;
 }
 
 const char* jpt_scene_upload_note(const jpt_ctx* c) { return c ? c->upload_note.c_str() : ""; }
@@ -1552,18 +1589,17 @@ int jpt_scene_commit(jpt_ctx* c, int32_t builder)
     if (!c || !c->building) return fail(c, JPT_E_STATE, "jpt_scene_begin not called");
     if (builder != JPT_BUILD_REFERENCE_EXACT && builder != JPT_BUILD_SAH && builder != JPT_BUILD_SAH_WATERTIGHT)
         return fail(c, JPT_E_INVALID, "unknown builder");
-    c->build_mode = builder == JPT_BUILD_SAH ? BuildMode::Sah : (builder == JPT_BUILD_SAH_WATERTIGHT ? BuildMode::SahWatertight : BuildMode::ReferenceExact);
+    const BuildMode mode = builder == JPT_BUILD_SAH ? BuildMode::Sah : (builder == JPT_BUILD_SAH_WATERTIGHT ? BuildMode::SahWatertight : BuildMode::ReferenceExact);
     const auto t0 = std::chrono::steady_clock::now();
     c->scene_ready = c->host_scene_ready = false;
     std::string err;
-    if (!c->builder.commit(c->build_mode, c->ref, err))
+    if (!c->builder.commit(mode, c->ref, err))
         return fail(c, JPT_E_LIMIT, err);
     c->ref.materials = c->pending_materials;
     c->ref.textures = c->pending_tex;
     c->ref.tex_res = c->pending_tex_res;
     c->ref.n_layers = c->pending_layers;
-    c->ref_is_exact = (builder == JPT_BUILD_REFERENCE_EXACT);
-    c->native_tree = is_native(c->build_mode);
+    c->tree = builder == JPT_BUILD_SAH ? JPT_TREE_NATIVE_REACH : (builder == JPT_BUILD_SAH_WATERTIGHT ? JPT_TREE_NATIVE_WATERTIGHT : JPT_TREE_REFERENCE_EXACT);
     int rc = validate_ref_scene(c, c->ref);
     if (rc != JPT_OK) return rc;
     c->from_commit = true;
@@ -1589,9 +1625,7 @@ int jpt_scene_share(jpt_ctx* dst, jpt_ctx* src)
     dst->scene_ready = dst->host_scene_ready = false;
     dst->builder = src->builder;   // so that jpt_scene_set_instance_transform / update_tlas keep working on the copy
     dst->ref = src->ref;
-    dst->ref_is_exact = src->ref_is_exact;
-    dst->native_tree = src->native_tree;
-    dst->build_mode = src->build_mode;
+    dst->tree = src->tree;
     dst->from_commit = src->from_commit;
     dst->upload_note = src->upload_note;
     dst->ties_note = src->ties_note;
@@ -1607,7 +1641,7 @@ namespace {
 int upload_tlas_update(jpt_ctx* c)
 {
     std::string err;
-    const bool use4 = !c->ref_is_exact && c->native_tree;
+    const bool use4 = walks_nodes4(c);
     if (!reflatten_tlas(c->ref, c->wide, use4, err)) return fail(c, JPT_E_INVALID, "tlas update: " + err);
     const uint32_t need = use4 ? c->wide.stack_need4 : c->wide.stack_need2;
     if (need > trace_stack_capacity()) {
@@ -1615,44 +1649,36 @@ int upload_tlas_update(jpt_ctx* c)
         return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the TLAS update: a traversal could need " +
                                         std::to_string(need) + " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
     }
-    c->ds.stack_need4 = c->wide.stack_need4;
     if (c->device < 0) return JPT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    SceneBufs& b = c->dev;
     // renders already queued on the stream still read the old records: let them finish before the buffers move
     HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, c->d_instances.upload(c->ref.instances, s));
-    HIP_TRY(c, c->d_tlas.upload(c->ref.tlas_nodes, s));
-    HIP_TRY(c, c->d_wtlas.upload(c->wide.tlas_nodes, s));
-    HIP_TRY(c, c->d_winst.upload(c->wide.instances, s));
-    HIP_TRY(c, c->d_winst4.upload(c->wide.instances4, s));
-    HIP_TRY(c, c->d_reach_inst.upload(c->ref.reach_inst, s));
-    HIP_TRY(c, c->d_cut_boxes.upload(c->ref.inst_cut_boxes, s));
-    HIP_TRY(c, c->d_cut_range.upload(c->ref.inst_cut_range, s));
+    HIP_TRY(c, b.set[0].inst.upload(c->ref.instances, s));
+    HIP_TRY(c, b.tlas.upload(c->ref.tlas_nodes, s));
+    HIP_TRY(c, b.wtlas.upload(c->wide.tlas_nodes, s));
+    HIP_TRY(c, b.winst.upload(c->wide.instances, s));
+    HIP_TRY(c, b.set[0].winst4.upload(c->wide.instances4, s));
+    HIP_TRY(c, b.set[0].reach.upload(c->ref.reach_inst, s));
+    HIP_TRY(c, b.cut_boxes.upload(c->ref.inst_cut_boxes, s));
+    HIP_TRY(c, b.cut_range.upload(c->ref.inst_cut_range, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     {
         const int rc4 = upload_nodes4(c, true);
         if (rc4 != JPT_OK) return rc4;
     }
-    if (c->ds.reach_tri) c->ds.reach_inst = c->d_reach_inst.p;
     c->refit_active = false;
-    DeviceScene& d = c->ds;
-    d.ref_instances = c->d_instances.p;
-    d.ref_tlas = c->d_tlas.p;
-    d.n_ref_tlas = (uint32_t)c->ref.tlas_nodes.size();
-    d.tlas_nodes = c->d_wtlas.p;
-    d.wide_instances = c->d_winst.p;
-    d.tlas_root = c->wide.tlas_root;
-    d.n_tlas_nodes = (uint32_t)c->wide.tlas_nodes.size();
-    d.wide_instances4 = c->d_winst4.p;
-    return upload_shadow(c, true);
+    const int rc = upload_shadow(c, true);
+    set_scene_view(c);
+    return rc;
 }
 
 // The refit stream and the events that order device refits against renders (jpt_scene_refit_tlas, jpt_scene_update_mesh)
 int ensure_refit_stream(jpt_ctx* c)
 {
     if (!c->refit_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->refit_stream, hipStreamNonBlocking));
-    for (int k = 0; k < jpt_ctx::kInstanceSets; k++)
+    for (int k = 0; k < kInstanceSets; k++)
         if (!c->ev_set_retired[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_set_retired[k], hipEventDisableTiming));
     if (!c->ev_refit_done) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_refit_done, hipEventDisableTiming));
     return JPT_OK;
@@ -1660,43 +1686,56 @@ int ensure_refit_stream(jpt_ctx* c)
 
 // Instance records and TLAS boxes from the transforms at `dev_view` (n_instances x 12 floats the device can read), written into the
 // copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
-// from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from d_bvh.
+// from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
 int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances)
 {
     hipStream_t s = c->stream;
+    SceneBufs& b = c->dev;
     if (!c->set_b_ready) {
         // first refit since the last host upload: the other copies of the instance arrays start as copies of copy 0
         // (the TLAS tails were all uploaded).  Once per upload, so the drain does not matter.
         HIP_TRY(c, hipStreamSynchronize(s));
-        for (int k = 0; k + 1 < jpt_ctx::kInstanceSets; k++) {
-            HIP_TRY(c, c->d_instances_more[k].resize(c->d_instances.n));
-            HIP_TRY(c, c->d_winst4_more[k].resize(c->d_winst4.n));
-            HIP_TRY(c, hipMemcpyAsync(c->d_instances_more[k].p, c->d_instances.p, c->d_instances.n * sizeof(RefInstance), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(c->d_winst4_more[k].p, c->d_winst4.p, c->d_winst4.n * sizeof(WideInstance), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(c, c->d_reach_inst_more[k].resize(c->d_reach_inst.n));
-            if (c->d_reach_inst.n)
-                HIP_TRY(c, hipMemcpyAsync(c->d_reach_inst_more[k].p, c->d_reach_inst.p, c->d_reach_inst.n * sizeof(ReachInst), hipMemcpyDeviceToDevice, s));
+        const SceneBufs::InstanceSet& first = b.set[0];
+        for (int k = 1; k < kInstanceSets; k++) {
+            SceneBufs::InstanceSet& to = b.set[k];
+            HIP_TRY(c, to.inst.resize(first.inst.n));
+            HIP_TRY(c, to.winst4.resize(first.winst4.n));
+            HIP_TRY(c, hipMemcpyAsync(to.inst.p, first.inst.p, first.inst.n * sizeof(RefInstance), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, hipMemcpyAsync(to.winst4.p, first.winst4.p, first.winst4.n * sizeof(WideInstance), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(c, to.reach.resize(first.reach.n));
+            if (first.reach.n)
+                HIP_TRY(c, hipMemcpyAsync(to.reach.p, first.reach.p, first.reach.n * sizeof(ReachInst), hipMemcpyDeviceToDevice, s));
         }
         HIP_TRY(c, hipStreamSynchronize(s));
         c->set_b_ready = true;
-        for (int k = 0; k < jpt_ctx::kInstanceSets; k++) c->set_retired_valid[k] = false;
+        for (bool& v : c->set_retired_valid) v = false;
     }
     // The refit writes the copy that new renders do not read yet (`next`); its last readers are the renders queued
     // before the refit that retired it, i.e. before ev_set_retired[next] was recorded on the context's stream (which
     // waits for every render).  The renders queued since read the current copy and keep running meanwhile.
-    const int next = (c->cur_set + 1) % jpt_ctx::kInstanceSets;
+    const int next = (c->cur_set + 1) % kInstanceSets;
     HIP_TRY(c, hipEventRecord(c->ev_set_retired[c->cur_set], s));
     c->set_retired_valid[c->cur_set] = true;
     hipStream_t rs = c->refit_stream;
     if (c->set_retired_valid[next]) HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_set_retired[next], 0));
-    RefInstance* inst_next = next ? c->d_instances_more[next - 1].p : c->d_instances.p;
-    WideInstance* winst4_next = next ? c->d_winst4_more[next - 1].p : c->d_winst4.p;
-    const uint32_t tail_base = (uint32_t)(c->wide.blas_nodes4.size() + (size_t)next * c->tlas4_cap);
-    ReachInst* reach_next = c->ds.reach_tri ? (next ? c->d_reach_inst_more[next - 1].p : c->d_reach_inst.p) : nullptr;
-    launch_tlas4_refit(rs, dev_view, n_instances, c->d_bvh.p, inst_next, nullptr, winst4_next, c->d_nodes4.p, tail_base,
-                       c->d_tlas4_order.p, c->d_tlas4_levels.p, c->n_tlas4_levels, reach_next, c->d_nodesq.p, (uint32_t)c->wide.tlas_nodes4.size(),
-                       c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty() ? c->d_cut_boxes.p : nullptr,
-                       c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty() ? c->d_cut_range.p : nullptr);
+    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty();
+    Tlas4RefitArgs a;
+    a.transforms12 = dev_view;
+    a.n_instances = n_instances;
+    a.bvh = b.bvh.p;
+    a.instances = b.set[next].inst.p;
+    a.wide_instances4 = b.set[next].winst4.p;
+    a.reach = c->ds.reach_tri ? b.set[next].reach.p : nullptr;
+    a.cut_boxes = cuts ? b.cut_boxes.p : nullptr;
+    a.cut_range = cuts ? b.cut_range.p : nullptr;
+    a.nodes4 = b.nodes4.p;
+    a.nodesq = b.nodesq.p;
+    a.n_blas_records = (uint32_t)(c->wide.blas_nodes4.size() + (size_t)next * c->tlas4_cap);
+    a.n_tlas_records = (uint32_t)c->wide.tlas_nodes4.size();
+    a.order = c->d_tlas4_order.p;
+    a.level_start = c->d_tlas4_levels.p;
+    a.n_levels = c->n_tlas4_levels;
+    launch_tlas4_refit(rs, a);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_refit_done, rs));
     // the context's stream (blocking renders, read-backs, uploads, foreign work) is ordered after the refit; queued
@@ -1704,10 +1743,7 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
     HIP_TRY(c, hipStreamWaitEvent(s, c->ev_refit_done, 0));
     c->refit_wait_seq++;
     c->cur_set = next;
-    c->ds.ref_instances = inst_next;
-    c->ds.wide_instances4 = winst4_next;
-    if (reach_next) c->ds.reach_inst = reach_next;
-    if (c->wide.tlas_root4 >= 0) c->ds.tlas_root4 = c->wide.tlas_root4 + (int32_t)tail_base;
+    set_scene_view(c);
     return JPT_OK;
 }
 
@@ -1734,7 +1770,7 @@ int jpt_scene_update_tlas(jpt_ctx* c)
     if (!c->tlas_dirty) return JPT_OK;
     const auto t0 = std::chrono::steady_clock::now();
     std::string err;
-    if (!c->builder.rebuild_instances(c->build_mode, c->ref, err)) {
+    if (!c->builder.rebuild_instances(build_mode(c), c->ref, err)) {
         c->scene_ready = c->host_scene_ready = false;
         return fail(c, JPT_E_LIMIT, err);
     }
@@ -1747,7 +1783,7 @@ int jpt_scene_update_tlas(jpt_ctx* c)
 int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
 {
     if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->native_tree || !c->from_commit)
+    if (!c->host_scene_ready || c->building || !walks_nodes4(c) || !c->from_commit)
         return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas needs a scene made by jpt_scene_commit with the native builder");
     if (!transforms12 && n_instances) return fail(c, JPT_E_INVALID, "null transforms");
     if (n_instances != c->ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
@@ -1759,30 +1795,23 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     if (n_instances == 0) return JPT_OK;
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t floats = (size_t)n_instances * 12;
-    // a ring of pinned staging buffers, so that the host can queue refits ahead of the device
-    const int st = (int)(c->refit_seq++ % (uint64_t)jpt_ctx::kRefitStages);
-    if (!c->ev_refit_copied[st]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_refit_copied[st], hipEventDisableTiming));
-    else HIP_TRY(c, hipEventSynchronize(c->ev_refit_copied[st]));  // the refit that used this stage last has run
-    if (c->h_refit_floats[st] < floats) {
-        if (c->h_refit_t12[st]) (void)hipHostFree(c->h_refit_t12[st]);
-        c->h_refit_t12[st] = nullptr;
-        c->h_refit_floats[st] = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_refit_t12[st], floats * sizeof(float), hipHostMallocDefault));
-        c->h_refit_floats[st] = floats;
-    }
-    std::memcpy(c->h_refit_t12[st], transforms12, floats * sizeof(float));
+    const size_t bytes = (size_t)n_instances * 12 * sizeof(float);
+    int st = 0;
+    HIP_TRY(c, c->refit_stage.next(bytes, st));
+    std::memcpy(c->refit_stage.buf[st].p, transforms12, bytes);
     // the kernel reads the transforms straight from the pinned buffer (48 B per instance over the host link)
     float* dev_view = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&dev_view, c->h_refit_t12[st], 0));
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&dev_view, c->refit_stage.buf[st].p, 0));
     int rc = ensure_refit_stream(c);
     if (rc == JPT_OK) rc = queue_instance_refit(c, dev_view, n_instances);
     if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_refit_copied[st], c->refit_stream));
+    HIP_TRY(c, hipEventRecord(c->refit_stage.copied[st], c->refit_stream));
     // The sky cull (compute_sky_cull) projects the boxes the TLAS root offers, on the host.  For a modest number of
-    // instances the host repeats the refit on its own copy of the four-child TLAS records (same arithmetic, same
-    // schedule: ~0.1 us per instance); beyond that the cull is off until the next jpt_scene_update_tlas.  After
-    // jpt_scene_update_mesh the host's root boxes are the committed vertices': off until the next jpt_scene_commit.
+    // instances the host repeats the TLAS refit on its own copy of the four-child TLAS records (refit_slots, same schedule:
+    // ~0.1 us per instance), over instance boxes by the root rule alone: without the cut tightening the device applies, so its
+    // boxes contain the device's (safe for the cull) but are looser.  Beyond that the cull is off until the next
+    // jpt_scene_update_tlas.  After jpt_scene_update_mesh the host's root boxes are the committed vertices': off until the next
+    // jpt_scene_commit.
     if (n_instances <= 4096u && !c->tlas4_levels_h.empty() && !c->mesh_deformed) {
         WideScene& w = c->wide;
         std::vector<RefInstance> boxes(n_instances);
@@ -1791,35 +1820,12 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
             instance_record(transforms12 + (size_t)i * 12, root.aabbMin, root.aabbMax, true, boxes[i]);
         }
         for (size_t l = 0; l + 1 < c->tlas4_levels_h.size(); l++)
-            for (uint32_t k = c->tlas4_levels_h[l]; k < c->tlas4_levels_h[l + 1]; k++) {
-                WideNode4& node = w.tlas_nodes4[c->tlas4_order_h[k]];
-                for (int slot = 0; slot < 4; slot++) {
-                    const int32_t ch = node.child[slot];
-                    if (ch == kEmptyChild) continue;
-                    float lo[3], hi[3];
-                    if (ch < 0) {
-                        const RefInstance& in = boxes[(uint32_t)~ch];
-                        lo[0] = in.aabbMin.x; lo[1] = in.aabbMin.y; lo[2] = in.aabbMin.z;
-                        hi[0] = in.aabbMax.x; hi[1] = in.aabbMax.y; hi[2] = in.aabbMax.z;
-                    } else {
-                        const WideNode4& below = w.tlas_nodes4[(size_t)ch];
-                        bool any = false;
-                        for (int j = 0; j < 4; j++) {
-                            if (below.child[j] == kEmptyChild) continue;
-                            const float bl[3] = {below.lo_x[j], below.lo_y[j], below.lo_z[j]};
-                            const float bh[3] = {below.hi_x[j], below.hi_y[j], below.hi_z[j]};
-                            for (int a = 0; a < 3; a++) {
-                                lo[a] = any ? imin_(lo[a], bl[a]) : bl[a];
-                                hi[a] = any ? imax_(hi[a], bh[a]) : bh[a];
-                            }
-                            any = true;
-                        }
-                        if (!any) continue;
-                    }
-                    node.lo_x[slot] = lo[0]; node.lo_y[slot] = lo[1]; node.lo_z[slot] = lo[2];
-                    node.hi_x[slot] = hi[0]; node.hi_y[slot] = hi[1]; node.hi_z[slot] = hi[2];
-                }
-            }
+            for (uint32_t k = c->tlas4_levels_h[l]; k < c->tlas4_levels_h[l + 1]; k++)
+                refit_slots(w.tlas_nodes4[c->tlas4_order_h[k]], w.tlas_nodes4.data(), [&](int32_t ref, float* lo, float* hi) {
+                    const RefInstance& in = boxes[(uint32_t)~ref];
+                    lo[0] = in.aabbMin.x; lo[1] = in.aabbMin.y; lo[2] = in.aabbMin.z;
+                    hi[0] = in.aabbMax.x; hi[1] = in.aabbMax.y; hi[2] = in.aabbMax.z;
+                });
         c->cull_boxes_current = true;
     } else {
         c->cull_boxes_current = false;
@@ -1896,10 +1902,10 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     if (!c) return JPT_E_INVALID;
     if (!c->host_scene_ready || c->building || !c->from_commit)
         return fail(c, JPT_E_STATE, "jpt_scene_update_mesh needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
-    if (c->ref_is_exact || !c->native_tree)
+    if (!walks_nodes4(c))
         return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_REFERENCE_EXACT: its trees are the reference's own, which a refit "
                                     "would not keep (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
-    if (c->build_mode != BuildMode::SahWatertight)
+    if (c->tree != JPT_TREE_NATIVE_WATERTIGHT)
         return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_SAH: its reach records and tie shadow are the reference builder's "
                                     "tree of the committed vertices (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
     if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
@@ -1933,18 +1939,10 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     const uint32_t n_inst = (uint32_t)c->ref.instances.size();
     const size_t head = 32, vbytes = nv * 3 * sizeof(float), nbytes = with_normals ? vbytes : 0, tbytes = (size_t)n_inst * 12 * sizeof(float);
     const size_t dev_bytes = head + vbytes + nbytes, bytes = dev_bytes + tbytes;
-    const int st = (int)(c->mesh_seq++ % (uint64_t)jpt_ctx::kRefitStages);
-    if (!c->ev_mesh_copied[st]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_copied[st], hipEventDisableTiming));
-    else HIP_TRY(c, hipEventSynchronize(c->ev_mesh_copied[st]));   // the update that used this stage last has run
+    int st = 0;
+    HIP_TRY(c, c->mesh_stage.next(bytes, st));
     if (!c->ev_mesh_drain) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_drain, hipEventDisableTiming));
-    if (c->h_mesh_bytes[st] < bytes) {
-        if (c->h_mesh_stage[st]) (void)hipHostFree(c->h_mesh_stage[st]);
-        c->h_mesh_stage[st] = nullptr;
-        c->h_mesh_bytes[st] = 0;
-        HIP_TRY(c, hipHostMalloc((void**)&c->h_mesh_stage[st], bytes, hipHostMallocDefault));
-        c->h_mesh_bytes[st] = bytes;
-    }
-    char* h = c->h_mesh_stage[st];
+    char* h = c->mesh_stage.buf[st].as<char>();
     {
         int32_t keys[8] = {ordered_key(FLT_MAX), ordered_key(FLT_MAX), ordered_key(FLT_MAX),
                            ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), 0, 0};
@@ -1976,25 +1974,26 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     a.vidx = c->d_tri_vidx.p;
     a.tri_first = mr.tri_first;
     a.n_tris = mr.n_tris;
-    a.wtris = c->d_wtris.p;
-    a.shade = c->d_shade_tris.p;
-    a.nodes4 = c->d_nodes4.p;
-    a.nodesq = c->d_nodesq.p;
+    const SceneBufs& b = c->dev;
+    a.wtris = b.wtris.p;
+    a.shade = b.shade_tris.p;
+    a.nodes4 = b.nodes4.p;
+    a.nodesq = b.nodesq.p;
     a.order = c->d_mesh_order.p;
     a.level_start = c->d_mesh_levels.p + mr.level_first;
     a.root4 = mr.root4;
-    a.bvh = c->d_bvh.p;
+    a.bvh = b.bvh.p;
     a.bvh_root = mr.bvh_root;
     const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->ref.inst_cut_boxes.empty();
-    a.cut_range = cuts ? c->d_cut_range.p : nullptr;
-    a.instances = c->d_instances.p;   // (blas_index is the same in every copy of the instance level)
+    a.cut_range = cuts ? b.cut_range.p : nullptr;
+    a.instances = b.set[0].inst.p;   // (blas_index is the same in every copy of the instance level)
     a.n_instances = n_inst;
     launch_mesh_refit(rs, a, c->mesh_levels_h.data() + mr.level_first, mr.n_levels);
     HIP_TRY(c, hipGetLastError());
     // the instance level over the new root boxes, with the current transforms, as jpt_scene_refit_tlas does
     rc = queue_instance_refit(c, reinterpret_cast<const float*>(hdev + dev_bytes), n_inst);
     if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->ev_mesh_copied[st], rs));
+    HIP_TRY(c, hipEventRecord(c->mesh_stage.copied[st], rs));
     c->cull_boxes_current = false;   // the host's TLAS boxes are stale: no sky cull until the next upload
     c->refit_active = true;
     c->ds.x.tlas_current = false;
@@ -2006,7 +2005,7 @@ int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void*
                            void* shade_out, uint32_t tri_capacity, int32_t* info_out)
 {
     if (!c || !info_out) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->from_commit || c->build_mode != BuildMode::SahWatertight || !c->native_tree)
+    if (!c->host_scene_ready || c->building || !c->from_commit || c->tree != JPT_TREE_NATIVE_WATERTIGHT)
         return fail(c, JPT_E_STATE, "jpt_debug_mesh_records needs a scene committed with JPT_BUILD_SAH_WATERTIGHT");
     if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the records are on the device");
@@ -2025,11 +2024,11 @@ int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void*
     if ((tris_out || shade_out) && tri_capacity < mr.n_tris) return fail(c, JPT_E_INVALID, "triangle buffers too small");
     HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the context's stream follows every update)
     if (nodes4_out && mr.n_recs)
-        HIP_TRY(c, hipMemcpy(nodes4_out, c->d_nodes4.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNode4), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(nodes4_out, c->dev.nodes4.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNode4), hipMemcpyDeviceToHost));
     if (nodesq_out && mr.n_recs)
-        HIP_TRY(c, hipMemcpy(nodesq_out, c->d_nodesq.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
-    if (tris_out) HIP_TRY(c, hipMemcpy(tris_out, c->d_wtris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(WideTri), hipMemcpyDeviceToHost));
-    if (shade_out) HIP_TRY(c, hipMemcpy(shade_out, c->d_shade_tris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(ShadeTri), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(nodesq_out, c->dev.nodesq.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
+    if (tris_out) HIP_TRY(c, hipMemcpy(tris_out, c->dev.wtris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(WideTri), hipMemcpyDeviceToHost));
+    if (shade_out) HIP_TRY(c, hipMemcpy(shade_out, c->dev.shade_tris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(ShadeTri), hipMemcpyDeviceToHost));
     return JPT_OK;
 }
 
@@ -2043,7 +2042,7 @@ int jpt_scene_update_reference_tlas(jpt_ctx* c, const void* blas_instances, uint
     if (c->from_commit) return fail(c, JPT_E_STATE, "the scene was made by jpt_scene_commit: use jpt_scene_set_instance_transform / jpt_scene_update_tlas");
     if (n_instances != c->ref.instances.size())
         return fail(c, JPT_E_INVALID, "instance count changed: upload the whole scene again");
-    const bool native = c->native_tree;  // the upload built the native tree: instances are matched by the roots the caller named then
+    const bool native = walks_nodes4(c);  // the upload built the native tree: instances are matched by the roots the caller named then
     const RefInstance* in = static_cast<const RefInstance*>(blas_instances);
     for (uint32_t i = 0; i < n_instances; i++) {
         RefInstance one;
@@ -2285,10 +2284,10 @@ int jpt_read_ldr_rgba8(jpt_ctx* c, uint8_t* out)
     const size_t px = whole ? full : (size_t)c->local_rows * c->width;
     rc = staged_read(c, whole ? c->d_full_ldr.p : c->d_ldr.p, px * 4);
     if (rc) return rc;
-    if (whole || c->world == 1) std::memcpy(out, c->h_read_pinned, px * 4);
+    if (whole || c->world == 1) std::memcpy(out, c->h_read_pinned.p, px * 4);
     else {
         std::memset(out, 0, full * 4);
-        scatter_rows(static_cast<const uint32_t*>(c->h_read_pinned), reinterpret_cast<uint32_t*>(out), c->width, c->height, c->rank, c->world, 1);
+        scatter_rows(c->h_read_pinned.as<const uint32_t>(), reinterpret_cast<uint32_t*>(out), c->width, c->height, c->rank, c->world, 1);
     }
     return JPT_OK;
 }
@@ -2308,7 +2307,7 @@ int jpt_readback_ldr_begin(jpt_ctx* c)
     }
     if (!c->ev_readback) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_readback, hipEventDisableTiming));
     if (px)
-        HIP_TRY(c, hipMemcpyAsync(c->h_ldr_pinned, c->readback_full ? c->d_full_ldr.p : c->d_ldr.p, px * sizeof(uint32_t),
+        HIP_TRY(c, hipMemcpyAsync(c->h_ldr_pinned.p, c->readback_full ? c->d_full_ldr.p : c->d_ldr.p, px * sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_readback, c->stream));
     c->readback_pending = true;
@@ -2324,10 +2323,10 @@ int jpt_readback_ldr_end(jpt_ctx* c, uint8_t* out)
     c->readback_pending = false;
     const size_t full = (size_t)c->width * c->height;
     if (c->readback_full || c->world == 1) {
-        std::memcpy(out, c->h_ldr_pinned, full * 4);
+        std::memcpy(out, c->h_ldr_pinned.p, full * 4);
     } else {
         std::memset(out, 0, full * 4);
-        scatter_rows(c->h_ldr_pinned, reinterpret_cast<uint32_t*>(out), c->width, c->height, c->rank, c->world, 1);
+        scatter_rows(c->h_ldr_pinned.as<const uint32_t>(), reinterpret_cast<uint32_t*>(out), c->width, c->height, c->rank, c->world, 1);
     }
     return JPT_OK;
 }
@@ -2342,16 +2341,16 @@ int jpt_read_accum_f32(jpt_ctx* c, float* out)
         if (!c->hist_written) return fail(c, JPT_E_STATE, "no temporal pass has run since the last reset");
         rc = staged_read(c, c->hist_written, full * sizeof(float4));
         if (rc) return rc;
-        std::memcpy(out, c->h_read_pinned, full * sizeof(float4));
+        std::memcpy(out, c->h_read_pinned.p, full * sizeof(float4));
         return JPT_OK;
     }
     const size_t n = c->assembled ? full * 4 : (size_t)c->local_rows * c->width * 4;   // floats
     rc = staged_read(c, c->assembled ? (const void*)c->d_full_accum.p : (const void*)c->d_accum.p, n * sizeof(float));
     if (rc) return rc;
-    if (c->assembled || c->world == 1) std::memcpy(out, c->h_read_pinned, n * sizeof(float));
+    if (c->assembled || c->world == 1) std::memcpy(out, c->h_read_pinned.p, n * sizeof(float));
     else {
         std::memset(out, 0, full * 16);
-        scatter_rows(static_cast<const float*>(c->h_read_pinned), out, c->width, c->height, c->rank, c->world, 4);
+        scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 4);
     }
     return JPT_OK;
 }
@@ -2367,10 +2366,10 @@ int jpt_read_depth_f32(jpt_ctx* c, float* out)
     const size_t n = (size_t)c->local_rows * c->width;
     rc = staged_read(c, c->d_depth.p, n * sizeof(float));
     if (rc) return rc;
-    if (c->world == 1) std::memcpy(out, c->h_read_pinned, n * sizeof(float));
+    if (c->world == 1) std::memcpy(out, c->h_read_pinned.p, n * sizeof(float));
     else {
         std::memset(out, 0, full * 4);
-        scatter_rows(static_cast<const float*>(c->h_read_pinned), out, c->width, c->height, c->rank, c->world, 1);
+        scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 1);
     }
     return JPT_OK;
 }

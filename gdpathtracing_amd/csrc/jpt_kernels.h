@@ -240,14 +240,27 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
 // one wave busy for `ticks` of the device's wall clock (hipDeviceAttributeWallClockRate), to see which streams run side by side
 void launch_queue_spin(hipStream_t stream, long long ticks);
 
-// Moving instances without the host (jpt_scene_refit_tlas): instance records from new transforms, then the boxes of the
-// four-child TLAS records bottom-up over the unchanged topology.  transforms12: n x 12 floats on the device; bvh: the
-// reference-layout BLAS nodes (root boxes); order / level_start: tlas4_refit_schedule, on the device.
-void launch_tlas4_refit(hipStream_t stream, const float* transforms12, uint32_t n_instances, const RefBvhNode* bvh,
-                        RefInstance* ref_instances, WideInstance* wide_instances, WideInstance* wide_instances4, WideNode4* nodes4,
-                        uint32_t n_blas_records, const uint32_t* order, const uint32_t* level_start, uint32_t n_levels,
-                        ReachInst* reach_instances /* may be null */, WideNodeQ* nodesq, uint32_t n_tlas_records,
-                        const float* cut_boxes = nullptr, const uint32_t* cut_range = nullptr /* RefScene::inst_cut_*: may be null */);
+// Moving instances without the host (jpt_scene_refit_tlas, jpt_kernels_post.hip): instance records from new transforms, then the
+// boxes of the four-child TLAS records bottom-up over the unchanged topology, then their quantised form.  Every pointer is a device
+// pointer.
+struct Tlas4RefitArgs {
+    const float* transforms12 = nullptr;     // n_instances x 12 floats
+    uint32_t n_instances = 0;
+    const RefBvhNode* bvh = nullptr;         // the reference-layout BLAS nodes (root boxes)
+    RefInstance* instances = nullptr;        // the copy of the instance level written
+    WideInstance* wide_instances4 = nullptr;
+    ReachInst* reach = nullptr;              // (may be null)
+    const float* cut_boxes = nullptr;        // RefScene::inst_cut_boxes / inst_cut_range (may be null)
+    const uint32_t* cut_range = nullptr;
+    WideNode4* nodes4 = nullptr;
+    WideNodeQ* nodesq = nullptr;
+    uint32_t n_blas_records = 0;             // where the TLAS tail written starts in nodes4 / nodesq
+    uint32_t n_tlas_records = 0;
+    const uint32_t* order = nullptr;         // tlas4_refit_schedule
+    const uint32_t* level_start = nullptr;
+    uint32_t n_levels = 0;
+};
+void launch_tlas4_refit(hipStream_t stream, const Tlas4RefitArgs& args);
 
 // Deforming a committed mesh without the host (jpt_scene_update_mesh, jpt_kernels_mesh.hip): the mesh's triangle records from new
 // vertices, its four-child BLAS records refitted bottom-up (order / level_start: refit4_schedule of the mesh, on the device;

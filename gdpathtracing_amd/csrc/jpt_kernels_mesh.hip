@@ -38,23 +38,6 @@ __device__ __forceinline__ void leaf_box(const MeshRefitArgs& a, uint32_t first,
         }
 }
 
-// the union of the non-empty slots of record `r`; false: it has none
-__device__ __forceinline__ bool record_box(const WideNode4* __restrict__ r, float* lo, float* hi)
-{
-    bool any = false;
-    for (int j = 0; j < 4; j++) {
-        if (r->child[j] == kEmptyChild) continue;
-        const float bl[3] = {r->lo_x[j], r->lo_y[j], r->lo_z[j]};
-        const float bh[3] = {r->hi_x[j], r->hi_y[j], r->hi_z[j]};
-        for (int k = 0; k < 3; k++) {
-            lo[k] = any ? imin_(lo[k], bl[k]) : bl[k];
-            hi[k] = any ? imax_(hi[k], bh[k]) : bh[k];
-        }
-        any = true;
-    }
-    return any;
-}
-
 __device__ __forceinline__ void leaf_span(int32_t ref, uint32_t& first, uint32_t& count)
 {
     const uint32_t l = (uint32_t)~ref;
@@ -62,25 +45,17 @@ __device__ __forceinline__ void leaf_span(int32_t ref, uint32_t& first, uint32_t
     count = (l >> kLeafCountShift) + 1u;
 }
 
-// one record: its slots from the leaves' triangles or from the (already refitted) records below, then its quantised form
+// one record: its slots from the leaves' triangles or from the (already refitted) records below (jpt_mesh_math.h), then its
+// quantised form
 __device__ void refit_record(const MeshRefitArgs& a, uint32_t ri, float pad)
 {
     WideNode4* node = a.nodes4 + ri;
-    for (int k = 0; k < 4; k++) {
-        const int32_t c = node->child[k];
-        if (c == kEmptyChild) continue;
-        float lo[3], hi[3];
-        if (c < 0) {
-            uint32_t first, count;
-            leaf_span(c, first, count);
-            leaf_box(a, first, count, lo, hi);
-            for (int j = 0; j < 3; j++) lo[j] = lo[j] - pad, hi[j] = hi[j] + pad;
-        } else if (!record_box(a.nodes4 + c, lo, hi)) {
-            continue;
-        }
-        node->lo_x[k] = lo[0]; node->lo_y[k] = lo[1]; node->lo_z[k] = lo[2];
-        node->hi_x[k] = hi[0]; node->hi_y[k] = hi[1]; node->hi_z[k] = hi[2];
-    }
+    refit_slots(*node, a.nodes4, [&](int32_t ref, float* lo, float* hi) {
+        uint32_t first, count;
+        leaf_span(ref, first, count);
+        leaf_box(a, first, count, lo, hi);
+        for (int j = 0; j < 3; j++) lo[j] = lo[j] - pad, hi[j] = hi[j] + pad;
+    });
     WideNodeQ q;
     quantize_node4(*node, q);
     a.nodesq[ri] = q;
@@ -168,7 +143,7 @@ __global__ __launch_bounds__(256) void mesh_root_kernel(MeshRefitArgs a)
         float lo[3], hi[3];
         bool any = true;
         if (a.root4 >= 0) {
-            any = record_box(a.nodes4 + a.root4, lo, hi);
+            any = record_union(a.nodes4[a.root4], lo, hi);
         } else {
             uint32_t first, count;
             leaf_span(a.root4, first, count);

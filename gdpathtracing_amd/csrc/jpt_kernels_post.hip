@@ -3,7 +3,7 @@
 // scattered back to image rows, and the display image (ACES of the mean, progressive_rendering.glsl:39-45)
 // is re-derived from the assembled sums.  No reference counterpart (the reference is single-device).
 #include "jpt_kernels.h"
-#include "jpt_instance_math.h"
+#include "jpt_mesh_math.h"
 
 namespace jpt {
 
@@ -98,12 +98,13 @@ void launch_queue_spin(hipStream_t stream, long long ticks) { hipLaunchKernelGGL
 
 // ---- device-side refit of the instance level (jpt_scene_refit_tlas) -------------------------------------------------
 
-// one thread per instance: the BLASInstance record (jpt_instance_math.h, the host builder's own code) and the hot
-// traversal records' inverse matrices
+// one thread per instance: the BLASInstance record (jpt_instance_math.h, the host builder's own code), tightened by the cut boxes
+// of its mesh the host chose at the last commit (jpt_mesh_math.h, InstanceCuts::tighten's code; affine transforms only, which is
+// what a Transform3D is), and the hot traversal records' inverse matrices
 __global__ __launch_bounds__(256) void instance_refit_kernel(const float* __restrict__ t12, uint32_t n, const RefBvhNode* __restrict__ bvh,
-                                                             RefInstance* __restrict__ ref_inst, WideInstance* __restrict__ winst,
-                                                             WideInstance* __restrict__ winst4, ReachInst* __restrict__ reach,
-                                                             const float* __restrict__ cut_boxes, const uint32_t* __restrict__ cut_range)
+                                                             RefInstance* __restrict__ ref_inst, WideInstance* __restrict__ winst4,
+                                                             ReachInst* __restrict__ reach, const float* __restrict__ cut_boxes,
+                                                             const uint32_t* __restrict__ cut_range)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -121,78 +122,33 @@ __global__ __launch_bounds__(256) void instance_refit_kernel(const float* __rest
         reach[i] = r;
     }
     instance_record(t, root.aabbMin, root.aabbMax, true, inst);
-    // ... bound more tightly by the boxes of the mesh's tree the host chose at the last commit (jpt_builder.cpp, InstanceCuts::tighten:
-    // the same arithmetic -- centre' -+ |M| half extent, the union padded, intersected with the root rule's box); affine transforms
-    // only, which is what a Transform3D is
     const uint32_t n_cut = cut_range ? cut_range[2 * i + 1] : 0u;
     if (n_cut >= 2u) {
-        const float* m = inst.transform;   // column-major 4 x 4
-        float am[9];
-        for (int r = 0; r < 3; r++)
-            for (int k = 0; k < 3; k++) am[k * 3 + r] = __builtin_fabsf(m[k * 4 + r]);
-        float lo[3] = {1e34f, 1e34f, 1e34f}, hi[3] = {-1e34f, -1e34f, -1e34f};
-        const float* b = cut_boxes + (size_t)cut_range[2 * i] * 6;
-        for (uint32_t k = 0; k < n_cut; k++, b += 6)
-            for (int r = 0; r < 3; r++) {
-                const float wc = m[r] * b[0] + m[4 + r] * b[1] + m[8 + r] * b[2] + m[12 + r];
-                const float we = am[r] * b[3] + am[3 + r] * b[4] + am[6 + r] * b[5];
-                lo[r] = fminf(lo[r], wc - we);
-                hi[r] = fmaxf(hi[r], wc + we);
-            }
-        float big = 0.0f;
-        for (int r = 0; r < 3; r++) big = fmaxf(big, fmaxf(__builtin_fabsf(lo[r]), __builtin_fabsf(hi[r])));
-        const float pad = big * 4e-6f;
-        if (lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2]) {
-            inst.aabbMin = Vec4{fmaxf(inst.aabbMin.x, lo[0] - pad), fmaxf(inst.aabbMin.y, lo[1] - pad), fmaxf(inst.aabbMin.z, lo[2] - pad), inst.aabbMin.w};
-            inst.aabbMax = Vec4{fminf(inst.aabbMax.x, hi[0] + pad), fminf(inst.aabbMax.y, hi[1] + pad), fminf(inst.aabbMax.z, hi[2] + pad), inst.aabbMax.w};
-        }
+        float lo[3], hi[3];
+        affine_cut_box(inst.transform, cut_boxes + (size_t)cut_range[2 * i] * 6, n_cut, lo, hi);
+        clip_world_box(inst, lo, hi);
     }
     ref_inst[i] = inst;
     for (int c = 0; c < 4; c++)
-        for (int r = 0; r < 3; r++) {
-            const float v = inst.inverse_transform[c * 4 + r];
-            if (winst) winst[i].inv[c * 3 + r] = v;
-            if (winst4) winst4[i].inv[c * 3 + r] = v;
-        }
+        for (int r = 0; r < 3; r++)
+            if (winst4) winst4[i].inv[c * 3 + r] = inst.inverse_transform[c * 4 + r];
 }
 
 // One block walks the levels of the TLAS deepest first: the box of a child slot is the instance's world box, or the
-// union of the boxes of the record below (min / max are exact, so these are the boxes a host build of the same
-// topology stores).  A level only reads records of deeper levels; __syncthreads orders the levels.
+// union of the boxes of the record below (refit_slots, jpt_mesh_math.h).  A level only reads records of deeper levels;
+// __syncthreads orders the levels.
 __global__ __launch_bounds__(1024) void tlas4_refit_kernel(WideNode4* __restrict__ nodes4, uint32_t nb, const uint32_t* __restrict__ order,
                                                            const uint32_t* __restrict__ level_start, uint32_t n_levels,
                                                            const RefInstance* __restrict__ inst)
 {
     for (uint32_t l = 0; l < n_levels; l++) {
-        for (uint32_t i = level_start[l] + threadIdx.x; i < level_start[l + 1]; i += blockDim.x) {
-            WideNode4* node = nodes4 + nb + order[i];
-            for (int k = 0; k < 4; k++) {
-                const int32_t c = node->child[k];
-                if (c == kEmptyChild) continue;
-                float lo[3], hi[3];
-                if (c < 0) {
-                    const RefInstance& in = inst[(uint32_t)~c];
-                    lo[0] = in.aabbMin.x; lo[1] = in.aabbMin.y; lo[2] = in.aabbMin.z;
-                    hi[0] = in.aabbMax.x; hi[1] = in.aabbMax.y; hi[2] = in.aabbMax.z;
-                } else {
-                    const WideNode4* below = nodes4 + c;  // (internal references already count from the array's start)
-                    bool any = false;
-                    for (int j = 0; j < 4; j++) {
-                        if (below->child[j] == kEmptyChild) continue;
-                        const float bl[3] = {below->lo_x[j], below->lo_y[j], below->lo_z[j]};
-                        const float bh[3] = {below->hi_x[j], below->hi_y[j], below->hi_z[j]};
-                        for (int a = 0; a < 3; a++) {
-                            lo[a] = any ? imin_(lo[a], bl[a]) : bl[a];
-                            hi[a] = any ? imax_(hi[a], bh[a]) : bh[a];
-                        }
-                        any = true;
-                    }
-                    if (!any) continue;
-                }
-                node->lo_x[k] = lo[0]; node->lo_y[k] = lo[1]; node->lo_z[k] = lo[2];
-                node->hi_x[k] = hi[0]; node->hi_y[k] = hi[1]; node->hi_z[k] = hi[2];
-            }
-        }
+        for (uint32_t i = level_start[l] + threadIdx.x; i < level_start[l + 1]; i += blockDim.x)
+            // (internal references already count from the array's start)
+            refit_slots(nodes4[nb + order[i]], nodes4, [&](int32_t ref, float* lo, float* hi) {
+                const RefInstance& in = inst[(uint32_t)~ref];
+                lo[0] = in.aabbMin.x; lo[1] = in.aabbMin.y; lo[2] = in.aabbMin.z;
+                hi[0] = in.aabbMax.x; hi[1] = in.aabbMax.y; hi[2] = in.aabbMax.z;
+            });
         __syncthreads();
     }
 }
@@ -208,20 +164,17 @@ __global__ __launch_bounds__(256) void quantize_tail_kernel(const WideNode4* __r
     nodesq[first + i] = q;
 }
 
-void launch_tlas4_refit(hipStream_t stream, const float* transforms12, uint32_t n_instances, const RefBvhNode* bvh,
-                        RefInstance* ref_instances, WideInstance* wide_instances, WideInstance* wide_instances4, WideNode4* nodes4,
-                        uint32_t n_blas_records, const uint32_t* order, const uint32_t* level_start, uint32_t n_levels, ReachInst* reach,
-                        WideNodeQ* nodesq, uint32_t n_tlas_records, const float* cut_boxes, const uint32_t* cut_range)
+void launch_tlas4_refit(hipStream_t stream, const Tlas4RefitArgs& a)
 {
-    if (n_instances == 0) return;
-    hipLaunchKernelGGL(instance_refit_kernel, dim3((n_instances + 255) / 256), dim3(256), 0, stream, transforms12, n_instances, bvh,
-                       ref_instances, wide_instances, wide_instances4, reach, cut_boxes, cut_range);
-    if (n_levels) {
-        hipLaunchKernelGGL(tlas4_refit_kernel, dim3(1), dim3(1024), 0, stream, nodes4, n_blas_records, order, level_start, n_levels,
-                           ref_instances);
-        if (nodesq && n_tlas_records)
-            hipLaunchKernelGGL(quantize_tail_kernel, dim3((n_tlas_records + 255) / 256), dim3(256), 0, stream, nodes4, nodesq, n_blas_records,
-                               n_tlas_records);
+    if (a.n_instances == 0) return;
+    hipLaunchKernelGGL(instance_refit_kernel, dim3((a.n_instances + 255) / 256), dim3(256), 0, stream, a.transforms12, a.n_instances, a.bvh,
+                       a.instances, a.wide_instances4, a.reach, a.cut_boxes, a.cut_range);
+    if (a.n_levels) {
+        hipLaunchKernelGGL(tlas4_refit_kernel, dim3(1), dim3(1024), 0, stream, a.nodes4, a.n_blas_records, a.order, a.level_start, a.n_levels,
+                           a.instances);
+        if (a.nodesq && a.n_tlas_records)
+            hipLaunchKernelGGL(quantize_tail_kernel, dim3((a.n_tlas_records + 255) / 256), dim3(256), 0, stream, a.nodes4, a.nodesq,
+                               a.n_blas_records, a.n_tlas_records);
     }
 }
 
