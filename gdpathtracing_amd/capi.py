@@ -42,6 +42,8 @@ SYMBOLS = [
     "jpt_multi_update_reference_tlas", "jpt_multi_update_mesh", "jpt_multi_set_params", "jpt_multi_set_camera", "jpt_multi_accum_reset", "jpt_multi_set_gather",
     "jpt_multi_render", "jpt_multi_sync", "jpt_multi_gather_plan", "jpt_multi_read_ldr_rgba8", "jpt_multi_read_accum_f32",
     "jpt_debug_quantize_nodes4", "jpt_debug_node_step4", "jpt_debug_last_error", "jpt_debug_mesh_records",
+    "jpt_set_environment", "jpt_set_environment_params", "jpt_multi_set_environment", "jpt_multi_set_environment_params",
+    "jpt_debug_env_lookup",
 ]
 
 
@@ -191,6 +193,11 @@ def lib():
     L.jpt_debug_node_step4.argtypes = [C.c_int, vp, u32, vp, u32, i32, vp]
     L.jpt_debug_last_error.restype = C.c_char_p
     L.jpt_debug_mesh_records.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, C.POINTER(i32)]
+    L.jpt_set_environment.argtypes = [vp, vp, i32, i32]
+    L.jpt_set_environment_params.argtypes = [vp, vp, C.c_float]
+    L.jpt_multi_set_environment.argtypes = [vp, vp, i32, i32]
+    L.jpt_multi_set_environment_params.argtypes = [vp, vp, C.c_float]
+    L.jpt_debug_env_lookup.argtypes = [C.c_int, vp, i32, i32, vp, C.c_float, vp, u32, vp]
     _lib = L
     return L
 

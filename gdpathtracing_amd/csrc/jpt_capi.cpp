@@ -260,6 +260,14 @@ struct jpt_ctx {
     bool readback_pending = false;
     bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
 
+    // the environment map (jpt_set_environment): the context's, like its params; the renders pass env_view by value
+    DevBuf<float4> d_env;
+    bool env_set = false;
+    int32_t env_w = 0, env_h = 0;
+    float env_rot[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    float env_intensity = 1.0f;
+    EnvDev env_view;
+
     jpt_stats stats;
 };
 
@@ -1002,6 +1010,19 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     return JPT_OK;
 }
 
+// the environment map the renders of `c` see, or null (sample_sky); a view of the context's own copy, valid until the next call
+const EnvDev* environment_of(jpt_ctx* c)
+{
+    if (!c->env_set) return nullptr;
+    EnvDev& e = c->env_view;
+    e.texels = c->d_env.p;
+    e.w = c->env_w;
+    e.h = c->env_h;
+    std::memcpy(e.rot, c->env_rot, sizeof e.rot);
+    e.intensity = c->env_intensity;
+    return &e;
+}
+
 // What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
 // stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.
 int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefront, Wf2Render& r)
@@ -1048,9 +1069,11 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     }
     c->trace_events_used = (int32_t)need_ev;
     compute_sky_cull(c, r.cull);
+    r.env = environment_of(c);
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
-    // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed
-    if (c->accum_mode == JPT_ACCUM_REF_LDR8 && n_frames > 1) {
+    // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
+    // (With an environment map the accumulation makes up culled pixels exactly, frame by frame: the cells bound the gradient only.)
+    if (c->accum_mode == JPT_ACCUM_REF_LDR8 && n_frames > 1 && !r.env) {
         const int32_t key[5] = {c->width, c->height, c->local_rows, c->rank, c->world};
         RefCamera cam_key = c->camera;
         cam_key.frame_index = 0;
@@ -1084,7 +1107,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt);
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, c->debug_steps ? nullptr : environment_of(c));
         }
         return JPT_OK;
     }
@@ -2151,6 +2174,96 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
     c->params_set = true;
     c->depth_valid = false;
     return alloc_framebuffers(c);
+}
+
+extern "C++" {
+namespace jpt {
+
+int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why)
+{
+    if (width <= 0 || height <= 0) {
+        why = "jpt_set_environment: width and height must be positive";
+        return JPT_E_INVALID;
+    }
+    if (width > kEnvMaxWidth || height > kEnvMaxHeight) {
+        why = "jpt_set_environment: the map is larger than 16384 x 8192 texels";
+        return JPT_E_LIMIT;
+    }
+    const size_t n = (size_t)width * (size_t)height * 3u;
+    for (size_t i = 0; i < n; i++) {
+        const float v = rgb[i];
+        if (!(v >= 0.0f) || !std::isfinite(v)) {
+            why = "jpt_set_environment: texel value " + std::to_string(i) + " is negative, infinite or NaN";
+            return JPT_E_INVALID;
+        }
+    }
+    return JPT_OK;
+}
+
+int check_env_params(const float* rotation9, float intensity, std::string& why)
+{
+    if (rotation9)
+        for (int k = 0; k < 9; k++)
+            if (!std::isfinite(rotation9[k])) {
+                why = "jpt_set_environment_params: the rotation has a non-finite entry";
+                return JPT_E_INVALID;
+            }
+    if (!std::isfinite(intensity) || !(intensity >= 0.0f)) {
+        why = "jpt_set_environment_params: the intensity must be finite and >= 0";
+        return JPT_E_INVALID;
+    }
+    return JPT_OK;
+}
+
+void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out)
+{
+    const size_t n = (size_t)width * (size_t)height;
+    out.resize(n);
+    for (size_t i = 0; i < n; i++) out[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
+}
+
+}  // namespace jpt
+}  // extern "C++"
+
+int jpt_set_environment(jpt_ctx* c, const float* rgb, int32_t width, int32_t height)
+{
+    if (!c) return JPT_E_INVALID;
+    std::string why;
+    if (rgb) {
+        const int rc = check_env_map(rgb, width, height, why);
+        if (rc != JPT_OK) return fail(c, rc, why);
+    }
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // the renders already queued read the old map: they finish first (every one of them ends with work on the context's stream)
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!rgb) {
+        c->env_set = false;
+        c->d_env.release();
+        return JPT_OK;
+    }
+    std::vector<float4> texels;
+    pack_env_texels(rgb, width, height, texels);
+    c->env_set = false;
+    HIP_TRY(c, c->d_env.resize(texels.size()));
+    HIP_TRY(c, hipMemcpy(c->d_env.p, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice));
+    c->env_w = width;
+    c->env_h = height;
+    c->env_set = true;
+    return JPT_OK;
+}
+
+int jpt_set_environment_params(jpt_ctx* c, const float* rotation9, float intensity)
+{
+    if (!c) return JPT_E_INVALID;
+    std::string why;
+    const int rc = check_env_params(rotation9, intensity, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
+    static const float kIdentity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    std::memcpy(c->env_rot, rotation9 ? rotation9 : kIdentity, sizeof c->env_rot);
+    c->env_intensity = intensity;
+    return JPT_OK;
 }
 
 int jpt_set_partition(jpt_ctx* c, int32_t rank, int32_t world)

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "jpt_kernels.h"
 #include "jpt_nodeq.h"
 #include "jpt_trace_core.h"
 
@@ -107,6 +108,17 @@ uint8_t node_step4_host(const WideNodeQ& q, const StepCase& c, int rcp_ulps)
     return (uint8_t)mask;
 }
 
+// jpt_debug_env_lookup: the environment lookup the tracing kernels inline (env_radiance, jpt_shade.h), one direction per thread
+__global__ void env_lookup_probe(EnvDev env, const float* __restrict__ dirs3, uint32_t n, float* __restrict__ rgb_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = env_radiance(env, mk3(dirs3[3 * (size_t)i], dirs3[3 * (size_t)i + 1], dirs3[3 * (size_t)i + 2]));
+    rgb_out[3 * (size_t)i] = c.x;
+    rgb_out[3 * (size_t)i + 1] = c.y;
+    rgb_out[3 * (size_t)i + 2] = c.z;
+}
+
 }  // namespace
 
 extern "C" {
@@ -172,6 +184,61 @@ int jpt_debug_node_step4(int device_id, const void* nodes4, uint32_t n_nodes, co
     if (d_nodes) (void)hipFree(d_nodes);
     if (d_cases) (void)hipFree(d_cases);
     if (d_taken) (void)hipFree(d_taken);
+    return rc;
+}
+
+int jpt_debug_env_lookup(int device_id, const float* rgb, int32_t width, int32_t height, const float* rotation9, float intensity,
+                         const float* dirs3, uint32_t n, float* rgb_out)
+{
+    if (!rgb || (n && (!dirs3 || !rgb_out))) {
+        g_debug_error = "null argument";
+        return JPT_E_INVALID;
+    }
+    int rc = check_env_map(rgb, width, height, g_debug_error);
+    if (rc == JPT_OK) rc = check_env_params(rotation9, intensity, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    std::vector<float4> texels;
+    pack_env_texels(rgb, width, height, texels);
+    EnvDev env;
+    env.w = width;
+    env.h = height;
+    static const float kIdentity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    std::memcpy(env.rot, rotation9 ? rotation9 : kIdentity, sizeof env.rot);
+    env.intensity = intensity;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        env.texels = texels.data();
+        for (uint32_t i = 0; i < n; i++) {
+            const f3 c = env_radiance(env, f3{dirs3[3 * (size_t)i], dirs3[3 * (size_t)i + 1], dirs3[3 * (size_t)i + 2]});
+            rgb_out[3 * (size_t)i] = c.x;
+            rgb_out[3 * (size_t)i + 1] = c.y;
+            rgb_out[3 * (size_t)i + 2] = c.z;
+        }
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (n == 0) return JPT_OK;
+    float4* d_tex = nullptr;
+    float *d_dirs = nullptr, *d_out = nullptr;
+    const size_t vec_bytes = (size_t)n * 3u * sizeof(float);
+    if ((e = hipMalloc((void**)&d_tex, texels.size() * sizeof(float4))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && (e = hipMalloc((void**)&d_dirs, vec_bytes)) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && (e = hipMalloc((void**)&d_out, vec_bytes)) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && (e = hipMemcpy(d_tex, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_dirs, dirs3, vec_bytes, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        env.texels = d_tex;
+        hipLaunchKernelGGL(env_lookup_probe, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, env, d_dirs, n, d_out);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "env_lookup_probe");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(rgb_out, d_out, vec_bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (d_tex) (void)hipFree(d_tex);
+    if (d_dirs) (void)hipFree(d_dirs);
+    if (d_out) (void)hipFree(d_out);
     return rc;
 }
 

@@ -79,6 +79,33 @@ __device__ __forceinline__ void sincos_(float x, float& s_out, float& c_out)
     c_out = c;
 }
 
+// atan2(y, x) with + - * /, fabs, comparisons and selects only (the environment lookup, jpt_shade.h): r = min(|x|,|y|) /
+// max(|x|,|y|) in [0, 1], a single-precision minimax odd polynomial r * P(r^2) of degree 17 for atan(r), then the octant.
+// Within 3.3e-7 rad of the float64 atan2; atan2_(0, 0) = 0, and a NaN (or two infinities) gives 0.  Host and device run the
+// same operations (tests/test_environment_host.py restates them in numpy).
+__host__ __device__ __forceinline__ float atan2_(float y, float x)
+{
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+    const bool steep = ay > ax;
+    const float mx = steep ? ay : ax, mn = steep ? ax : ay;
+    const float r = mn / mx;
+    const float z = r * r;
+    float p = 2.456719521433115e-3f;
+    p = p * z - 1.4401350170373917e-2f;
+    p = p * z + 3.978123888373375e-2f;
+    p = p * z - 7.234862446784973e-2f;
+    p = p * z + 1.0498950630426407e-1f;
+    p = p * z - 1.4161232113838196e-1f;
+    p = p * z + 1.9985906779766083e-1f;
+    p = p * z - 3.3332598209381104e-1f;
+    p = p * z + 9.999998807907104e-1f;
+    float a = p * r;
+    if (steep) a = 1.57079637f - a;
+    if (x < 0.0f) a = 3.14159274f - a;
+    if (y < 0.0f) a = -a;
+    return a == a ? a : 0.0f;
+}
+
 // rgba8 UNORM store / load
 __device__ __forceinline__ uint32_t unorm8(float x)
 {

@@ -4,7 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
 #include <type_traits>
+#include <vector>
 
 #include "jpt_nodeq.h"
 #include "jpt_shade.h"
@@ -193,9 +195,15 @@ __device__ __forceinline__ void count_walk(DevCounters& c, uint32_t steps)
 }
 #endif
 
+// the checks of jpt_set_environment / jpt_set_environment_params (jpt_capi.cpp), also run by jpt_debug_env_lookup: JPT_OK, or a
+// JPT_E_* code and the reason in `why`; and the map's device layout, (r, g, b, 0) per texel
+int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why);
+int check_env_params(const float* rotation9, float intensity, std::string& why);
+void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out);
+
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env = nullptr);
 
 // The persistent-block pipeline (jpt_kernels_wf2.hip): one render of fp.n_frames frames over the flattened layout;
 // fp.frame_index / fp.frame_count are those of the FIRST frame.  The first (max_bounces + 2) *
@@ -230,6 +238,8 @@ struct Wf2Render {
     hipEvent_t before_acc = nullptr;       // the accumulation kernel waits for this event (whatever its stream)
     const uint32_t* sky_tiles = nullptr;   // per 8 x 8 tile of the context's share of the image: its one rgba8 sky cell, if it has one
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
+    const EnvDev* env = nullptr;           // the environment map the misses see (jpt_set_environment); null: sample_sky.  The
+                                           // launches then take the *_env kernels, and the accumulation uses no sky cells
 };
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block

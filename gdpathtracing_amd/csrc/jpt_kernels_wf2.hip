@@ -16,6 +16,8 @@
 //   wf2_accumulate  frames IN ORDER per pixel (progressive_rendering.glsl:33-37), display image, depth.
 //   (large scenes: the tracing kernels' TAIL instantiations finish their few very long walks with a whole wave per ray,
 //   coop_walk_call)
+// wf2_primary, wf2_shade, wf2_finish and wf2_accumulate see the paths' misses: they live in jpt_wf2_paths.h, included twice --
+// as themselves, and as the *_env kernels that light the misses with an environment map (jpt_set_environment).
 //
 // Tracing kernels keep every lane busy: a lane whose ray is finished takes the next ray of the block's
 // segment (cursor in LDS) while its neighbours keep walking -- the wave never waits for its slowest ray.
@@ -411,153 +413,6 @@ __device__ __attribute__((noinline)) void coop_walk_call(const WideSceneDev* __r
     *out = coop_walk<COUNT>(sc, st, pool, mk3(ox, oy, oz), mk3(dx, dy, dz), COUNT ? *cntp : none, (uint32_t)kTraceBlock);
 }
 
-// ---- bounce 0: generate + trace ------------------------------------------------------------------------
-
-template <bool COUNT, bool W4, bool TAIL = false>   // TAIL: the wave finishes its last, long walks itself, all lanes on one ray (coop_walk_call)
-__global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void wf2_primary(WideSceneDev sc, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, RefCamera cam,
-                                                      WfTune tune, SkyCull cull, DevCounters* __restrict__ counters)
-{
-    __shared__ int32_t stack[kStackLds * kBlock];
-    __shared__ uint32_t s_cursor, s_out;
-    const int lane = threadIdx.x & 63;
-    const uint32_t seg = blockIdx.x;
-    // runs seg, seg + G, seg + 2G, ... of 2^run_shift consecutive chunks belong to this block
-    const uint32_t run_mask = (1u << dm.run_shift) - 1u;
-    const uint32_t n_runs = (dm.n_chunks + run_mask) >> dm.run_shift;
-    const uint32_t my_runs = seg < n_runs ? (n_runs - seg + kSegments - 1u) / kSegments : 0u;
-    const uint32_t n = (my_runs << dm.run_shift) * 64u;  // (the last run of the image may be short: checked per entry)
-    if (threadIdx.x == 0) {
-        s_cursor = 0;
-        s_out = 0;
-    }
-    // The queue sizes of bounces >= 1 are accumulated with atomics by wf2_shade and must start from zero: block s clears segment s's
-    // word of every later row (and block 0 the set-aside counts behind them) -- this launch completes before the first wf2_shade
-    // starts, and one launch fewer per render is one link less in a chain of a dozen (a memset used to do this).
-    if ((int)threadIdx.x >= 1 && (int)threadIdx.x <= fp.max_bounces + 1) wb.qcount[(size_t)threadIdx.x * kSegments + seg] = 0u;
-    if (seg == 0 && threadIdx.x >= 192u) wb.redo_count[threadIdx.x - 192u] = 0u;
-    __syncthreads();
-    int32_t spill[kStackSpill];
-    const typename Traversal<COUNT, W4>::Stack my_stack{&stack[threadIdx.x], spill, kTraceBlock, kStackLds};
-    const size_t seg_base = (size_t)seg * dm.seg_cap;
-    uint32_t dry_rounds = 0;   // (TAIL: rounds of this wave since the block's queue ran dry; wave-uniform)
-    DevCounters cnt = {};
-    Traversal<COUNT, W4> tr;
-    bool active = false, exhausted = false;
-    bool unsaved = false;   // this lane's finished walk has not left its result yet (see wf2_trace: written when the wave refills)
-    uint32_t path = 0;
-    uint32_t walk_steps = 0;   // (counting builds: record steps of this lane's ray)
-    auto save_results = [&]() {
-        // hits are packed into the segment's bounce-0 queue (main.glsl:349), one counter update per wave
-        const bool is_hit = unsaved && tr.hit.t < 1e9f;
-        const unsigned long long hm = __ballot(is_hit);
-        if (hm) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(&s_out, (uint32_t)__popcll(hm));
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            if (is_hit) {
-                const uint32_t j = base + lanes_below(hm, lane);
-                stream_st4(&wb.ray_o[0][seg_base + j], make_float4(tr.wo.x, tr.wo.y, tr.wo.z, 0.0f));
-                stream_st4(&wb.ray_d[0][seg_base + j], make_float4(tr.wd.x, tr.wd.y, tr.wd.z, __uint_as_float(path)));
-                stream_st4(&wb.hit_a[seg_base + j], make_float4(tr.hit.t, tr.hit.u, tr.hit.v, __uint_as_float(tr.hit.tri)));
-                stream_stu(&wb.hit_b[seg_base + j], tr.hit.inst | (tr.hit.front ? 0x80000000u : 0u));
-            }
-        }
-        if (unsaved && !is_hit) {   // sky: radiance += 1 * sampleSky(d), path over (main.glsl:380,395-397)
-            uint32_t pslot, f;
-            path_slot_frame(path, dm, (uint32_t)fp.n_frames, pslot, f);
-            const f3 sky = mk3(0.0f, 0.0f, 0.0f) + mk3(1.0f, 1.0f, 1.0f) * sample_sky(tr.wd);
-            store_final(wb, fp.accum_mode, path, sky);
-            if ((int)f == fp.depth_frame) wb.first_depth[pslot] = cam.far_;
-        }
-        unsaved = false;
-    };
-
-    for (;;) {
-        const unsigned long long idle = __ballot(!active);
-        const int n_idle = __popcll(idle);
-        if (!exhausted && n_idle >= tune.primary_refill_idle) {
-            if (__any(unsaved)) save_results();
-            uint32_t start = 0;
-            if (lane == 0) start = atomicAdd(&s_cursor, (uint32_t)n_idle);
-            start = (uint32_t)__builtin_amdgcn_readfirstlane((int)start);
-            if (start + (uint32_t)n_idle >= n) exhausted = true;
-            if (start < n && !active) {
-                const uint32_t idx = start + lanes_below(idle, lane);
-                if (idx < n) {
-                    const uint32_t j = idx >> 6;  // local chunk number: run j >> run_shift, position j & run_mask
-                    const uint32_t chunk = ((seg + (j >> dm.run_shift) * kSegments) << dm.run_shift) + (j & run_mask);
-                    // a wave takes 64 consecutive path ids: chunk c is (tile c / F, part c % F), its lanes the samples part * 64 + lane of that
-                    // tile, sample s being frame s % F of the tile's pixel s / F
-                    uint32_t slot = 0, f = 0;
-                    if (chunk < dm.n_chunks) path_slot_frame(chunk * 64u + (idx & 63u), dm, (uint32_t)fp.n_frames, slot, f);
-                    int px, ly;
-                    slot_to_pixel(slot, dm, px, ly);
-                    if (chunk < dm.n_chunks && px < fp.width && ly < fp.local_rows) {
-                        const int py = local_to_global_row(ly, fp);
-                        path = slot * (uint32_t)fp.n_frames + f;
-                        if (COUNT) cnt.rays++;
-                        // a pixel outside the screen rectangles of all the boxes the TLAS root offers: the walk would
-                        // expand the root, fail every box test and end in the sky -- nothing is generated, traced or
-                        // stored for it here; wf2_accumulate makes up its colour from (x, y, frame)
-                        if (sky_culled(cull, px, py)) {
-                            if (COUNT) {
-                                cnt.tlas_expand++;
-                                cnt.phase[7]++;
-                            }
-                        } else {
-                            uint32_t sx, sy;
-                            const Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index + f, sx, sy);
-                            tr.begin(sc, ray.o, ray.d);
-                            active = true;
-                            walk_steps = 0;
-                        }
-                    }
-                }
-            }
-        }
-        if (!__any(active)) {
-            if (exhausted) break;
-            continue;
-        }
-        {
-            if (walk_round<COUNT, W4>(tr, active, sc, my_stack, cnt, tune, walk_steps)) {
-                active = false;
-                unsaved = true;
-                if (COUNT) count_walk(cnt, walk_steps);
-            }
-            if constexpr (TAIL && W4) {
-                if (exhausted && ++dry_rounds >= (uint32_t)tune.tail_rounds && __popcll(__ballot(active)) <= tune.tail_lanes) break;
-            }
-        }
-    }
-    if constexpr (TAIL && W4) {
-        // tail phase (coop_walk_call): the few rays this wave still holds, each walked by the whole wave
-        unsigned long long left = __ballot(active);
-        if (left) {
-            if (__any(unsaved)) save_results();   // (the finished lanes' hits leave the registers the call is free to use)
-            const int wave_col = (int)(threadIdx.x & ~63u);
-            while (left) {
-                const int src = __ffsll((long long)left) - 1;
-                left &= left - 1ull;
-                TraceHit h;
-                const WideSceneDev sc_tail = sc;   // (a copy of its own: `sc` itself must not have its address taken, or the hot loop reads it from scratch)
-                coop_walk_call<COUNT>(&sc_tail, &stack[threadIdx.x], &stack[(kStackLds - 2) * kTraceBlock + wave_col], __shfl(tr.wo.x, src),
-                                      __shfl(tr.wo.y, src), __shfl(tr.wo.z, src), __shfl(tr.wd.x, src), __shfl(tr.wd.y, src), __shfl(tr.wd.z, src),
-                                      COUNT ? &cnt : nullptr, &h);
-                if (lane == src) {
-                    tr.hit = h;
-                    active = false;
-                    unsaved = true;
-                }
-            }
-        }
-    }
-    if (__any(unsaved)) save_results();
-    __syncthreads();
-    if (threadIdx.x == 0) wb.qcount[0 * kSegments + seg] = s_out;
-    if (COUNT) flush_counters(cnt, counters);
-}
-
 // ---- bounces >= 1: trace the segment's ray queue ----------------------------------------------------------
 
 // `chain` consecutive segments are one block's queue (entries of segment seg0, then seg0 + 1, ...): the grid is
@@ -690,246 +545,6 @@ __global__ __launch_bounds__(kBlock, JPT_WAVES_PER_SIMD) void wf2_trace(WideScen
     if (COUNT) flush_counters(cnt, counters);
 }
 
-// ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
-
-#ifndef JPT_SHADE_WAVES
-#define JPT_SHADE_WAVES 5   // 96 VGPRs: two fewer than the body wants, five waves per SIMD instead of four for a kernel that waits on gathers (C3 +4 %); 6 spills
-#endif
-// One path vertex (main.glsl:378-397): the queue entry's ray and closest hit in, radiance / throughput / seeds of the path
-// updated, returns true when the path goes on (no / nd = its next ray).  With reach records (JPT_BUILD_SAH) and
-// check_reach, a hit the reference's own traversal could not have reached -- the world ray fails the world box the
-// reference gives the instance, or the local ray fails the box of the triangle's reference leaf (jpt_types.h) -- is
-// not shaded: the vertex is set aside (redo_rec; its state parked in the path's thr / rad words), `unreachable` comes back
-// true, and the path leaves the wavefront to be finished by wf2_finish.
-// LAST: the vertex is known to be the path's last (bounce == max_bounces): emission or sky is added and the path ends -- no BRDF
-// sample, no next ray -- so the instantiation carries none of that code (wf2_shade's final launch).
-template <bool COUNT, bool LAST = false, int TEX = 3>
-__device__ __forceinline__ bool shade_entry(const SceneShading& sh, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& fp, float cam_far,
-                                            int bounce, const float4 ro, const float4 rd, const float4 tin, const float4 ha, const uint32_t hb,
-                                            bool check_reach, bool& unreachable, float4& no, float4& nd, float4& nt, DevCounters& cnt)
-{
-    unreachable = false;
-    const uint32_t p = __float_as_uint(rd.w) & kPathMask;
-    const bool had_radiance = (__float_as_uint(rd.w) & kHasRadiance) != 0u;
-    f3 throughput, radiance;
-    uint32_t sx, sy;
-    uint32_t slot, f;
-    path_slot_frame(p, dm, (uint32_t)fp.n_frames, slot, f);
-    Ray ray;
-    ray.o = mk3(ro.x, ro.y, ro.z);
-    ray.d = mk3(rd.x, rd.y, rd.z);
-    const bool is_hit = ha.x < 1e9f;  // main.glsl:349
-    // The kernel waits on gathers, so everything whose address is known once the queue entry is here is asked for at
-    // once, ahead of the branches that use it: the path's state now, the instance and the reach boxes below.
-    const float4 t4 = tin;   // (the entry's throughput and seed.x: came with the ray)
-    float4 r4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (bounce > 0 && had_radiance) r4 = wb.rad[p];
-    Hit h;
-    ShadeTriRegs stri;
-    uint32_t found_in = 0;
-    if (is_hit) {
-        h.t = ha.x;
-        h.u = ha.y;
-        h.v = ha.z;
-        h.tri = __float_as_uint(ha.w);
-        h.inst = hb & kInstMask;                   // hitInfo.blas
-        found_in = (hb >> kInstBits) & kInstMask;  // the instance whose local ray found the triangle
-        const bool check = check_reach && sh.reach_tri != nullptr;
-        stri = load_shade_tri(sh, h.tri);
-        float4 ta, tb, ia, ib;
-        if (check) {   // (whole records, unconditionally: a flag test first would put two round trips in a row)
-            ta = ld4(&sh.reach_tri[h.tri].lo[0]);
-            tb = ld4(&sh.reach_tri[h.tri].hi[0]);
-            if (sh.n_instances > 1u) {
-                ia = ld4(&sh.reach_inst[found_in].lo[0]);
-                ib = ld4(&sh.reach_inst[found_in].hi[0]);
-            }
-        }
-        // the hit instance's local ray: the expression ray_trace_tlas evaluates (main.glsl:319-320)
-        const RefInstance& b = sh.instances[found_in];
-        h.lo = xform_point(b.inverse_transform, ray.o);
-        h.ld = xform_dir(b.inverse_transform, ray.d);
-        if (check) {
-            bool reached = __float_as_uint(ta.w) != 0u || slab(h.lo, rcp3(h.ld), ta.x, ta.y, ta.z, tb.x, tb.y, tb.z) < 1e30f;
-            if (reached && sh.n_instances > 1u) reached = slab(ray.o, rcp3(ray.d), ia.x, ia.y, ia.z, ib.x, ib.y, ib.z) < 1e30f;
-            // (an exact distance tie is as undecidable on the native tree as a crack: with the reference's trees at hand
-            // it is decided where the reference decides it)
-            if (sh.retrace_ties && (hb & kHitTied) != 0u) reached = false;
-            if (!reached) {
-                // a few paths in 10^7: the path leaves the wavefront here and is finished, exactly, by wf2_finish -- unless
-                // the set-aside buffer is full (pathological scenes): then the hit is shaded as found, and counted
-                const uint32_t k = atomicAdd(&wb.redo_count[0], 1u);
-                if (k < wb.redo_cap) {
-                    float4 rd2 = rd;
-                    if (bounce > 0) {   // its seed.y (the entry's origin.w) waits in rad[path].w, beside the radiance so far
-                        wb.rad[p] = make_float4(r4.x, r4.y, r4.z, ro.w);
-                        wb.thr[p] = tin;
-                        rd2.w = __uint_as_float(p | kHasRadiance);
-                    }
-                    wb.redo_rec[2 * (size_t)k] = make_float4(ro.x, ro.y, ro.z, __uint_as_float((uint32_t)bounce));
-                    wb.redo_rec[2 * (size_t)k + 1] = rd2;
-                    unreachable = true;
-                    return false;
-                }
-                atomicAdd(&wb.redo_count[1], 1u);
-            }
-        }
-    }
-    if (bounce == 0) {
-        // fresh path: the seed after the jitter draw (main.glsl:409-411), recomputed from (x, y, frame)
-        int px, ly;
-        slot_to_pixel(slot, dm, px, ly);
-        prng_seed((uint32_t)px, (uint32_t)local_to_global_row(ly, fp), fp.frame_index + f, sx, sy);
-        float r0, r1;
-        pcg2d(sx, sy, r0, r1);
-        throughput = mk3(1.0f, 1.0f, 1.0f);
-        radiance = mk3(0.0f, 0.0f, 0.0f);
-    } else {
-        throughput = mk3(t4.x, t4.y, t4.z);
-        radiance = mk3(r4.x, r4.y, r4.z);
-        sx = __float_as_uint(t4.w);
-        sy = __float_as_uint(ro.w);
-    }
-    const f3 radiance_in = radiance;
-    if (COUNT && bounce > 0) cnt.rays++;
-    bool alive = false;
-    if (!is_hit) {
-        radiance = radiance + throughput * sample_sky(ray.d);
-        if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = cam_far;  // (only a redone primary hit can turn into a miss here)
-    } else {
-        if (COUNT) cnt.shaded_hits++;
-        const Shading s = get_shading_data<TEX>(sh, h, (hb >> 31) != 0u, stri);
-        radiance = radiance + throughput * s.emission;
-        if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = length3(s.position - ray.o);
-        if (!LAST && bounce < fp.max_bounces) alive = bounce_step(s, sx, sy, ray, throughput);
-        if (COUNT && alive && throughput.x == 0.0f && throughput.y == 0.0f && throughput.z == 0.0f) cnt.zero_thr++;
-    }
-    if (alive) {
-        // (radiance starts as +0 and +0 + x is x or +0, never -0: "unchanged and never written" means exactly +0)
-        const bool changed = radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
-        if (changed) wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
-        nt = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(sx));
-        no = make_float4(ray.o.x, ray.o.y, ray.o.z, __uint_as_float(sy));
-        nd = make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(p | ((had_radiance || changed) ? kHasRadiance : 0u)));
-    } else {
-        store_final(wb, fp.accum_mode, p, radiance);
-    }
-    return alive;
-}
-
-#ifndef JPT_SHADE_NOTEX_WAVES
-#define JPT_SHADE_NOTEX_WAVES 7   // without the sampler code the body takes 67 VGPRs by itself
-#endif
-template <bool COUNT, bool LAST = false, int TEX = 3>
-__global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVES : JPT_SHADE_WAVES)) void wf2_shade(SceneShading sh, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, float cam_far, int bounce,
-                                                    DevCounters* __restrict__ counters)
-{
-    // grid = (chunks per segment, segments): every 256-entry chunk of every segment is its own block, so the
-    // launch is balanced however unevenly the segments are filled; blocks past a segment's end exit at once.
-    const int lane = threadIdx.x & 63;
-    const uint32_t seg = blockIdx.y;
-    const uint32_t n = wb.qcount[(size_t)bounce * kSegments + seg];
-    const uint32_t base = blockIdx.x * kBlock;
-    if (base >= n) return;
-    const size_t seg_base = (size_t)seg * dm.seg_cap;
-    const int in = bounce & 1, out = (bounce + 1) & 1;
-    DevCounters cnt = {};
-    const uint32_t i = base + threadIdx.x;
-    bool alive = false;
-    float4 no, nd, nt;
-    if (i < n) {
-        const float4 ro = stream_ld4(&wb.ray_o[in][seg_base + i]), rd = stream_ld4(&wb.ray_d[in][seg_base + i]);
-        const float4 tin = bounce > 0 ? stream_ld4(&wb.thr_q[in][seg_base + i]) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-        const float4 ha = stream_ld4(&wb.hit_a[seg_base + i]);
-        const uint32_t hb = stream_ldu(&wb.hit_b[seg_base + i]);
-        bool unreachable;   // (set aside inside shade_entry: nothing more to do here)
-        alive = shade_entry<COUNT, LAST, TEX>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, true, unreachable, no, nd, nt, cnt);
-    }
-    if (LAST) {   // (no path goes on: nothing to pack)
-        if (COUNT) flush_counters(cnt, counters);
-        return;
-    }
-    // active-ray packing: wave ballot + prefix popcount, one atomic per wave on the SEGMENT's counter (1792
-    // different words: no hot address); the order inside the next queue is irrelevant
-    const unsigned long long m = __ballot(alive);
-    if (m) {
-        uint32_t wbase = 0;
-        if (lane == 0) wbase = atomicAdd(&wb.qcount[(size_t)(bounce + 1) * kSegments + seg], (uint32_t)__popcll(m));
-        wbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)wbase);
-        if (alive) {
-            const size_t j = seg_base + wbase + lanes_below(m, lane);
-            stream_st4(&wb.ray_o[out][j], no);
-            stream_st4(&wb.ray_d[out][j], nd);
-            stream_st4(&wb.thr_q[out][j], nt);
-        }
-    }
-    if (COUNT) flush_counters(cnt, counters);
-}
-
-// The paths wf2_shade set aside: their hit is one the reference's traversal cannot reach.  Each is finished here, after
-// the render's last bounce launch and before the accumulation: from the vertex where it left the wavefront the path is
-// traced with the reach tests applied to every instance entry and every accepted triangle (Traversal<.., REACH = true>:
-// the closest hit among the triangles the reference can reach, i.e. the reference's answer) and shaded bounce after
-// bounce by the same shade_entry, its state passing through the path's own thr / rad words.  A handful of paths per
-// render, so one small grid of single-wave blocks with the whole stack in scratch; one launch per render.
-template <bool COUNT, bool W4, bool EXACT>
-__global__ __launch_bounds__(64) void wf2_finish(WideSceneDev sc, TieShadowDev sx, SceneShading sh, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, float cam_far,
-                                                 DevCounters* __restrict__ counters)
-{
-    const uint32_t n = wb.redo_count[0] < wb.redo_cap ? wb.redo_count[0] : wb.redo_cap;
-    if (blockIdx.x >= n) return;
-    constexpr int kDepth = kStackLds + kStackSpill;
-    int32_t stack_mem[kDepth];   // (the whole stack in scratch; in LDS instead: no difference, profiles/r03/r03z_finish_probe.txt)
-    // Every segment of a set-aside path is traced on the native tree with the two reach tests applied inside the walk: the
-    // closest hit among the triangles the reference can reach.  EXACT (`sx` = the reference's own trees): when that walk
-    // met a second reachable triangle at exactly the closest distance, the tie is decided where the reference decides it
-    // (jpt_tie_walk.h).
-    using Walk = Traversal<COUNT, W4, true>;
-    const typename Walk::Stack st{nullptr, stack_mem, 0, 0, kDepth};
-    DevCounters cnt = {};
-    // (records are dealt to the BLOCKS first -- record k to block k % grid, lane k / grid: a handful of set-aside paths run as
-    // one lane each of as many waves, side by side, instead of as divergent lanes of one wave, one after another)
-    for (uint32_t k = threadIdx.x * gridDim.x + blockIdx.x; k < n; k += gridDim.x * 64u) {
-        float4 ro = wb.redo_rec[2 * (size_t)k], rd = wb.redo_rec[2 * (size_t)k + 1];
-        const int first = (int)__float_as_uint(ro.w);
-        float4 tin = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-        if (first > 0) {   // the seed.y and the throughput parked when the path was set aside
-            ro.w = wb.rad[__float_as_uint(rd.w) & kPathMask].w;
-            tin = wb.thr[__float_as_uint(rd.w) & kPathMask];
-        }
-        for (int bounce = first;; bounce++) {
-            const f3 o3 = mk3(ro.x, ro.y, ro.z), d3 = mk3(rd.x, rd.y, rd.z);
-            Walk tr;
-            tr.begin(sc, o3, d3);
-            while (tr.step(sc, st, cnt)) {
-            }
-            TraceHit hit = tr.hit;
-            if (EXACT && hit.t < 1e9f && (hit.inst & kHitTied) != 0u) {
-                TieLeaves tl;
-                tie_leaves<COUNT, W4>(sc, sx, st, o3, d3, hit.t, tl, cnt);
-                TraceHit xh;
-                if (tl.n > 0 && tie_walk(sx, sh.instances, sx.tlas_current, tl, o3, d3, xh) && xh.t == hit.t) {
-                    // (xh.t differs only if a float accident kept the reference's walk from the tying leaves: then the native
-                    // walk's answer stands)
-                    hit = xh;
-                    hit.tri = sx.tri_native[xh.tri];   // shading and reach records are in the native order
-                }
-            }
-            // (the ray-segment count the host reads is the sum of the queue sizes: this path's later segments are in no queue)
-            if (bounce > first) atomicAdd(&wb.qcount[(size_t)bounce * kSegments], 1u);
-            const float4 ha = make_float4(hit.t, hit.u, hit.v, __uint_as_float(hit.tri));
-            const uint32_t hb = (hit.inst & ~kHitTied) | (hit.front ? 0x80000000u : 0u);
-            bool unreachable;
-            float4 no, nd, nt;
-            if (!shade_entry<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt)) break;
-            ro = no;
-            rd = nd;
-            tin = nt;
-        }
-    }
-    if (COUNT) flush_counters(cnt, counters);
-}
-
 // ---- the sky cells of culled pixels (wf2_accumulate; the argument is there) -------------------------------------------------
 constexpr float kCellMargin = 0.01f;
 // values * 255 + 0.5 of the sky along the ray through a raster position, per channel; false: the camera block does not behave
@@ -1000,223 +615,13 @@ __global__ __launch_bounds__(kBlock) void wf2_sky_tiles(Wf2Dims dm, FrameParams 
     tile_cell[t] = ok ? cell : 0u;
 }
 
-// ---- per pixel: frames in order -> accumulation buffer, display image, depth ----------------------------------
-
-__global__ __launch_bounds__(kBlock) void wf2_accumulate(Wf2Buffers wb, Wf2Dims dm, FrameParams fp, RefCamera cam, SkyCull cull,
-                                                         float4* __restrict__ accum, uint32_t* __restrict__ ldr,
-                                                         float* __restrict__ depth_out, const uint32_t* __restrict__ tile_cell)
-{
-    // one thread per pixel of the context's share of the image, tile by tile (a wave = one 8 x 8 tile); `slot` is the
-    // pixel's place in the window
-    constexpr int kSharedFrames = 16;                       // most frames per render the shared exact route below holds
-    __shared__ uint32_t s_who[kBlock / 64][64];            // per wave: the pixels that need it, px | py << 16
-    __shared__ uint32_t s_val[kBlock / 64][64 * kSharedFrames];   // ... and their frames' rgba8 sky values
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t full_slot = blockIdx.x * kBlock + threadIdx.x;
-    const uint32_t ftile = full_slot >> 6, flane = full_slot & 63u;
-    const uint32_t fty = fdiv(ftile, dm.by_full_tiles_x), ftx = ftile - fty * (uint32_t)dm.full_tiles_x;
-    if ((int)fty >= dm.full_tiles_y) return;   // (the whole wave)
-    const int px = (int)(ftx * 8u + (flane & 7u)), ly = (int)(fty * 8u + (flane >> 3));
-    const bool valid = px < fp.width && ly < fp.local_rows;   // (lanes past the image's edge still help with the shared route)
-    const int wtx = (int)ftx - dm.tile_x0, wty = (int)fty - dm.tile_y0;
-    const bool in_window = wtx >= 0 && wtx < dm.tiles_x && wty >= 0 && wty < dm.tiles_y;
-    const uint32_t in_tile = flane;
-    const uint32_t slot = in_window ? ((uint32_t)wty * (uint32_t)dm.tiles_x + (uint32_t)wtx) * 64u + in_tile : 0u;
-    const size_t idx = valid ? (size_t)ly * fp.width + px : 0;
-    // fp.frame_count = ProgressiveRendering frame_count of the FIRST frame of this render
-    f3 sum = mk3(0.0f, 0.0f, 0.0f);
-    bool have_prev = fp.frame_count > 1;
-    if (have_prev && valid) {
-        const float4 prev = stream_ld4(&accum[idx]);
-        sum = mk3(prev.x, prev.y, prev.z);
-    }
-    f3 last = mk3(0.0f, 0.0f, 0.0f);
-    // the primary launch neither traced nor stored the paths of a sky-culled pixel: their radiance is the sky along the
-    // primary ray of (x, y, frame) (main.glsl:380,395-397 with throughput 1), made up here
-    const int py = local_to_global_row(ly, fp);
-    const bool culled = valid && (!in_window || sky_culled(cull, px, py));
-    // A culled pixel's frames all see the sky, whose colour depends on the ray's d.y alone and changes by a hundredth of an
-    // rgba8 step across a pixel: in REF_LDR8 mode nearly every pixel has ONE rgba8 sky value for all its frames.  The
-    // jittered sample of a frame lies on the quarter circle (px + cos, py + sin), inside the pixel's square.  A pinhole
-    // maps raster lines to great circles, so the directions through the square fill the spherical quadrilateral of its four
-    // corner rays, and along a great circle d.y = A cos(s + phi): f'' = -f.  Every point of the quadrilateral lies on an
-    // arc between two points of its edges, so d.y leaves the range of the four corner values by at most
-    //     2 * (theta^2 / 8) * max |d.y|        (theta: the quadrilateral's diameter; two levels of interpolation)
-    // -- nothing for the narrow pixels of the benchmark cameras (1e-6), but NOT nothing for a wide lens looking at the
-    // zenith, where d.y has its maximum INSIDE the square (0.06 of a cell for an 8 x 8 tile at fov 150).  The
-    // corner range is therefore widened by that bound, in cell units (d value / d d.y <= 255 * 0.05 * 0.5 = 6.4,
-    // main.glsl:189-192), before it is asked to lie inside ONE integer cell of value * 255 + 0.5, `kCellMargin` away from
-    // the cell's ends (float rounding of the ray set-up: 1e-5 of a cell); a quadrilateral wider than half a radian is not
-    // tried.  When that holds every frame quantises to that cell and the eight primary rays -- seed, sincos, 4 x 4
-    // transform, three divisions, a normalisation each -- need not be made.  Pixels near a cell boundary (a few per cent:
-    // horizontal bands) and cameras whose clip-space w changes sign inside the pixel take the exact per-frame route below.
-    bool sky_constant = false;
-    f3 sky_value = mk3(0.0f, 0.0f, 0.0f);
-    uint32_t sky_word = 0u;   // ... as the rgba8 word it is converted from
-    const float two_over_w = 2.0f / (float)fp.width, two_over_h = 2.0f / (float)fp.height;
-    const bool want_cells = fp.accum_mode == 0 && fp.n_frames > 1;
-    // First for the whole TILE at once (a wave is one 8 x 8 tile, eight consecutive image rows): do its four corner rays agree on the
-    // cells?  Then every culled pixel of the tile has that value.  (The same argument over eight pixels instead of one; theta is
-    // eight times larger, so wide lenses fail here and pass pixel by pixel.)  Decided by wf2_sky_tiles, one lane per tile, while
-    // the render's paths were traced: here one word per wave.
-    bool tile_constant = false;
-    if (want_cells && tile_cell != nullptr && __any(culled)) {
-        const uint32_t tc = tile_cell[__builtin_amdgcn_readfirstlane((int)ftile)];
-        if (tc & 0x80000000u) {
-            tile_constant = true;
-            if (culled) {
-                sky_constant = true;
-                sky_word = tc & 0xffffffu;
-                sky_value = mk3(from_unorm8(tc & 255u), from_unorm8((tc >> 8) & 255u), from_unorm8((tc >> 16) & 255u));
-            }
-        }
-    }
-    // ... then, in the tiles that straddle a cell boundary, pixel by pixel.  (Sharing the tile's 9 x 9 corners through LDS -- two
-    // passes of the set-up instead of four -- left the kernel at 49.5 us and cost queued renders 1-5 %: profiles/r04/r04ak_acc_corners.txt)
-    if (culled && want_cells && !tile_constant) {
-        float lo[3] = {1e30f, 1e30f, 1e30f}, hi[3] = {-1e30f, -1e30f, -1e30f};
-        bool sane = true;
-        float w_first = 1.0f;
-        f3 cd[4];
-        for (int corner = 0; corner < 4; corner++) {
-            float ww, v[3];
-            const bool ok = sky_cells_at(cam, two_over_w, two_over_h, (float)(px + (corner & 1)), (float)(py + (corner >> 1)), w_first, ww, v, cd[corner]);
-            if (corner == 0) w_first = ww;
-            sane = sane && (corner == 0 ? (ww == ww) : ok);
-            for (int k = 0; k < 3; k++) {
-                lo[k] = fmin_(lo[k], v[k]);
-                hi[k] = fmax_(hi[k], v[k]);
-            }
-        }
-        const float excess = sky_interior_excess(cd);
-        bool same = sane;
-        float cell[3];
-        for (int k = 0; k < 3; k++) {
-            lo[k] -= excess;
-            hi[k] += excess;
-            cell[k] = __builtin_floorf(lo[k]);
-            same = same && (lo[k] - cell[k] >= kCellMargin) && (hi[k] - cell[k] <= 1.0f - kCellMargin) && (hi[k] - lo[k] < 0.5f);
-        }
-        if (same) {
-            sky_constant = true;
-            sky_word = ((uint32_t)cell[0] & 255u) | (((uint32_t)cell[1] & 255u) << 8) | (((uint32_t)cell[2] & 255u) << 16);
-            sky_value = mk3(from_unorm8(sky_word & 255u), from_unorm8((sky_word >> 8) & 255u), from_unorm8((sky_word >> 16) & 255u));
-        }
-    }
-    // The culled pixels that did not pass (near a cell boundary) need their frames' exact values -- eight primary rays
-    // each.  A wave runs that code for all 64 lanes as soon as ONE pixel of its tile needs it, frame after frame; instead
-    // the tile's (pixel, frame) pairs that need it are dealt to the wave's 64 lanes, one pair each, so a tile with eight
-    // such pixels makes one pass (64 pairs), not eight.  The values go through LDS to the pixel that sums them, in frame
-    // order.  (REF_LDR8, 2..kSharedFrames frames per render; otherwise every lane walks its own frames, as before.)
-    const bool shared_route = fp.accum_mode == 0 && fp.n_frames > 1 && fp.n_frames <= kSharedFrames;
-    const bool slow = culled && !sky_constant && shared_route;
-    uint32_t my_rank = 0;
-    {
-        const unsigned long long sm = __ballot(slow);
-        if (sm) {
-            my_rank = lanes_below(sm, lane);
-            if (slow) s_who[wave][my_rank] = (uint32_t)px | ((uint32_t)py << 16);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t total = (uint32_t)__popcll(sm) * (uint32_t)fp.n_frames;
-            for (uint32_t base = 0; base < total; base += 64u) {
-                const uint32_t item = base + (uint32_t)lane;
-                if (item < total) {
-                    const uint32_t p = fdiv(item, dm.by_frames), f = item - p * (uint32_t)fp.n_frames;
-                    const uint32_t who = s_who[wave][p];
-                    uint32_t sx, sy;
-                    const Ray ray = primary_ray(cam, fp.width, fp.height, (int)(who & 0xffffu), (int)(who >> 16), fp.frame_index + f, sx, sy);
-                    const f3 c = mk3(0.0f, 0.0f, 0.0f) + mk3(1.0f, 1.0f, 1.0f) * sample_sky(ray.d);
-                    s_val[wave][item] = unorm8(c.x) | (unorm8(c.y) << 8) | (unorm8(c.z) << 16);   // rgba8 store of main.glsl:434
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    if (!valid) return;
-    // the frames of group g are a block of their own in rad / fin8: [slot][frame of the group] behind the earlier groups' blocks
-    const int g_base = fp.n_frames / dm.acc_groups, g_extra = fp.n_frames % dm.acc_groups;
-    int g = 0, g_f0 = 0, g_nf = g_base + (g_extra > 0 ? 1 : 0);
-    // The usual case first -- rgba8 samples, one frame group, 4 / 8 / 12 / 16 frames: a pixel's frames are 16 to 64 consecutive bytes of
-    // fin8, fetched as one to four 16-byte loads that are all in flight together.  (The loop below waits for a 4-byte load per frame,
-    // eight trips to the cache one after another: the kernel was bound by that latency, not by its 53 MB -- round 5.)
-    const bool packed_frames = fp.accum_mode == 0 && dm.acc_groups == 1 && fp.n_frames >= 4 && fp.n_frames <= kSharedFrames && (fp.n_frames & 3) == 0;
-    if (packed_frames) {
-        // every lane's frames as rgba8 words first -- the window's pixels from fin8, a culled pixel's from its one sky cell or from
-        // the wave's shared exact values -- then ONE conversion-and-add per frame for all of them
-        uint4 q[kSharedFrames / 4];
-        const uint4* mine = reinterpret_cast<const uint4*>(wb.fin8 + (size_t)slot * (size_t)fp.n_frames);
-        const uint4* shared = reinterpret_cast<const uint4*>(&s_val[wave][my_rank * (uint32_t)fp.n_frames]);
-#pragma unroll
-        for (int c = 0; c < kSharedFrames / 4; c++) {
-            q[c] = make_uint4(sky_word, sky_word, sky_word, sky_word);
-            if (c * 4 < fp.n_frames) {
-                if (!culled) q[c] = stream_ldu4(&mine[c]);
-                else if (slow) q[c] = shared[c];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < kSharedFrames / 4; c++) {
-            if (c * 4 >= fp.n_frames) break;
-            const uint32_t qs[4] = {q[c].x, q[c].y, q[c].z, q[c].w};
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const f3 cur = mk3(from_unorm8(qs[j] & 255u), from_unorm8((qs[j] >> 8) & 255u), from_unorm8((qs[j] >> 16) & 255u));
-                last = cur;
-                sum = have_prev ? cur + sum : cur;  // progressive_rendering.glsl:34-36
-                have_prev = true;
-            }
-        }
-    }
-    for (int f = 0; f < fp.n_frames && !packed_frames; f++) {
-        if (f >= g_f0 + g_nf) {
-            g++;
-            g_f0 += g_nf;
-            g_nf = g_base + (g < g_extra ? 1 : 0);
-        }
-        const size_t at = (size_t)g_f0 * dm.slots_per_frame + (size_t)slot * (size_t)g_nf + (size_t)(f - g_f0);
-        f3 cur;
-        if (sky_constant) {
-            cur = sky_value;
-            last = cur;
-        } else if (slow) {   // rgba8 load of progressive_rendering.glsl:33
-            const uint32_t q = s_val[wave][my_rank * (uint32_t)fp.n_frames + (uint32_t)f];
-            cur = mk3(from_unorm8(q & 255u), from_unorm8((q >> 8) & 255u), from_unorm8((q >> 16) & 255u));
-            last = cur;
-        } else if (culled) {
-            uint32_t sx, sy;
-            const Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index + (uint32_t)f, sx, sy);
-            cur = mk3(0.0f, 0.0f, 0.0f) + mk3(1.0f, 1.0f, 1.0f) * sample_sky(ray.d);
-            if (fp.accum_mode == 0) {  // rgba8 store of main.glsl:434, load of progressive_rendering.glsl:33
-                last = mk3(from_unorm8(unorm8(cur.x)), from_unorm8(unorm8(cur.y)), from_unorm8(unorm8(cur.z)));
-                cur = last;
-            } else {
-                last = cur;
-            }
-        } else if (fp.accum_mode == 0) {
-            const uint32_t q = stream_ldu(&wb.fin8[at]);
-            cur = mk3(from_unorm8(q & 255u), from_unorm8((q >> 8) & 255u), from_unorm8((q >> 16) & 255u));
-            last = cur;   // (display_mode 1 shows the last frame's rgba8 image itself: quantising it again gives the same bytes)
-        } else {
-            const float4 r = stream_ld4(&wb.rad[at]);
-            cur = mk3(r.x, r.y, r.z);
-            last = cur;
-        }
-        sum = have_prev ? cur + sum : cur;  // progressive_rendering.glsl:34-36
-        have_prev = true;
-    }
-    if (fp.n_frames > 0) {
-        stream_st4(&accum[idx], make_float4(sum.x, sum.y, sum.z, 1.0f));
-        const float fc = (float)(fp.frame_count + (uint32_t)fp.n_frames - 1u);
-        const f3 col = fp.display_mode == 1 ? last : aces_film(mk3(sum.x / fc, sum.y / fc, sum.z / fc) * 1.0f);
-        stream_stu(&ldr[idx], unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u);
-        if (depth_out) {
-            const float dist = culled ? cam.far_ : wb.first_depth[slot];
-            stream_stf(&depth_out[idx], cam.far_ / (cam.far_ - cam.near_) * (1.0f - cam.near_ / dist));  // main.glsl:432
-        }
-    }
-}
+// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, then the *_env ones
+#define JPT_ENV 0
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
 
 // the window of a render (local tiles): x0, y0, nx, ny
 struct TileWindow {
@@ -1436,6 +841,7 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     // wf2_finish decides exact distance ties on the reference's own trees (EXACT) where the scene keeps them, four-child walks only
     const TieShadowDev& sx = ds.x;
     const int finish_walk = !w4 ? 0 : (sx.ok ? 2 : 1);
+    const EnvDev* env = r.env;   // an environment map: the *_env kernels (jpt_wf2_paths.h)
     // the pipeline of one group on one stream
     auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, hipEvent_t* ev) {
         // (the queue sizes of bounces >= 1 and the set-aside counts start from zero: wf2_primary clears them)
@@ -1446,12 +852,18 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         const dim3 sgrid(((dm.seg_cap + kBlock - 1) / kBlock) | 1u, kSegments);
         if (ev) (void)hipEventRecord(ev[0], st);
         with_consts<2, 3>([&](auto C, auto W) {
-            hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
+            if (env)
+                hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
+            else
+                hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
         }, count, walk);
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {
             with_consts<2, 2, 3>([&](auto C, auto LAST, auto TEX) {
-                hipLaunchKernelGGL((wf2_shade<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters);
+                if (env)
+                    hipLaunchKernelGGL((wf2_shade_env<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env);
+                else
+                    hipLaunchKernelGGL((wf2_shade<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters);
             }, count, b == gp.max_bounces, texmode);
             if (b == gp.max_bounces) break;
             if (ev) (void)hipEventRecord(ev[2 * (b + 1)], st);
@@ -1463,7 +875,10 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (sh.reach_tri) {  // the paths set aside because their hit is undecidable on the native tree: finished exactly
             const dim3 rgrid(256), rblock(64);   // (blocks past the set-aside count exit at once; more records than threads: grid-stride)
             with_consts<2, 3>([&](auto C, auto W) {
-                hipLaunchKernelGGL((wf2_finish<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
+                if (env)
+                    hipLaunchKernelGGL((wf2_finish_env<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env);
+                else
+                    hipLaunchKernelGGL((wf2_finish<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
             }, count, finish_walk);
         }
     };
@@ -1495,7 +910,10 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     // the accumulation touches the framebuffers: it waits for whatever ordered the context's renders before this one (before_acc)
     if (r.before_acc) (void)hipStreamWaitEvent(stream, r.before_acc, 0);
     const uint32_t ablocks = ((uint32_t)dm_all.full_tiles_x * (uint32_t)dm_all.full_tiles_y * 64u + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(wf2_accumulate, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, r.sky_tiles);
+    if (env)   // (no sky cells)
+        hipLaunchKernelGGL(wf2_accumulate_env, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, nullptr, *env);
+    else
+        hipLaunchKernelGGL(wf2_accumulate, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, r.sky_tiles);
 }
 
 uint64_t wf2_pixels_outside_window(const SkyCull& cull, const FrameParams& fp)

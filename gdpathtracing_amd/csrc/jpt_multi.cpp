@@ -251,6 +251,26 @@ int jpt_multi_set_params(jpt_multi* m, int32_t width, int32_t height, int32_t ma
     return JPT_OK;
 }
 
+int jpt_multi_set_environment(jpt_multi* m, const float* rgb, int32_t width, int32_t height)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_environment(m->ctx[r], rgb, width, height);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
+int jpt_multi_set_environment_params(jpt_multi* m, const float* rotation9, float intensity)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_environment_params(m->ctx[r], rotation9, intensity);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_set_camera(jpt_multi* m, const void* camera160)
 {
     if (!m) return JPT_E_INVALID;

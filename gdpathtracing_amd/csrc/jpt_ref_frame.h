@@ -1,0 +1,89 @@
+// jpt_ref_frame.h -- ref_frame_kernel, the audit route's one kernel (jpt_kernels_ref.hip), which sees the paths' misses.  Included
+// twice by jpt_kernels_ref.hip, as jpt_wf2_paths.h is by jpt_kernels_wf2.hip:
+//   JPT_ENV 0   ref_frame_kernel, main.glsl's gradient (sample_sky): the same source, token for token, as before the map existed;
+//   JPT_ENV 1   ref_frame_kernel_env (jpt_set_environment): one more parameter, the map, and env_radiance at the miss.
+// (No include guard: that is the point.)
+#if JPT_ENV
+#define JPT_ENV_NAME(name) name##_env
+#define JPT_ENV_PARAM , EnvDev env
+#define JPT_SKY(d) env_radiance(env, d)
+#else
+#define JPT_ENV_NAME(name) name
+#define JPT_ENV_PARAM
+#define JPT_SKY(d) sample_sky(d)
+#endif
+
+// One dispatch of main.glsl (main.glsl:404-436) fused with one dispatch of progressive_rendering.glsl
+// (:28-46) for the pixels of this context's partition.
+template <bool COUNT, bool TIES>
+__global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefSceneDev sc, TieShadowDev shadow, SceneShading sh, FrameParams fp, RefCamera cam,
+                                                        float4* __restrict__ accum, uint32_t* __restrict__ ldr,
+                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters JPT_ENV_PARAM)
+{
+    // 8x32 pixel tiles: a wave covers 8x8 pixels
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int px = blockIdx.x * 32 + wave * 8 + (lane & 7);
+    const int ly = blockIdx.y * 8 + (lane >> 3);  // local row
+    DevCounters cnt = {};
+    if (px < fp.width && ly < fp.local_rows) {
+        const int py = local_to_global_row(ly, fp);
+        uint32_t sx, sy;
+        Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index, sx, sy);
+        float depth = cam.far_;
+        f3 radiance = mk3(0.0f, 0.0f, 0.0f);
+        f3 throughput = mk3(1.0f, 1.0f, 1.0f);
+        if (fp.debug_steps) {   // #ifdef DEBUG_STEPS (main.glsl:358-361, 423-427): the primary ray's triangle tests / 256, depth = far
+            RefHit hit;
+            if (COUNT) cnt.rays++;
+            (void)ray_trace_tlas<COUNT>(sc, ray, hit, cnt);
+            const float g = clamp_((float)hit.steps / 256.0f, 0.0f, 1.0f);
+            radiance = mk3(g, g, g);
+        } else
+        for (int i = 0; i < fp.max_bounces + 1; i++) {  // main.glsl:377
+            RefHit hit;
+            if (COUNT) cnt.rays++;
+            const bool is_hit = ray_trace_tlas<COUNT>(sc, ray, hit, cnt);
+            if (!is_hit) {
+                radiance = radiance + throughput * JPT_SKY(ray.d);
+                break;
+            }
+            if (TIES && hit.tied) {
+                // an exact distance tie: decided where the reference decides it (jpt_tie_walk.h) -- the leaves that hold
+                // the tying triangles from one more walk with hitInfo.t preset, then the reference's own walk through
+                // their ancestors (event counters: not those of a reference tree anyway)
+                TieLeaves tl;
+                RefHit again;
+                DevCounters none = {};
+                (void)ray_trace_tlas<false>(sc, ray, again, none, &shadow, &tl, hit.t);
+                TraceHit xh;
+                if (tl.n > 0 && tie_walk(shadow, sh.instances, shadow.tlas_current, tl, ray.o, ray.d, xh) && xh.t == hit.t) {
+                    const uint32_t found_in = (xh.inst >> kInstBits) & kInstMask;
+                    hit.u = xh.u;
+                    hit.v = xh.v;
+                    hit.tri = shadow.tri_native[xh.tri];
+                    hit.front = xh.front;
+                    hit.inst = xh.inst & kInstMask;
+                    const RefInstance& fb = sc.instances[found_in];
+                    hit.lo = xform_point(fb.inverse_transform, ray.o);
+                    hit.ld = xform_dir(fb.inverse_transform, ray.d);
+                }
+            }
+            if (COUNT) cnt.shaded_hits++;
+            Hit h;
+            h.t = hit.t; h.u = hit.u; h.v = hit.v; h.tri = hit.tri; h.inst = hit.inst; h.lo = hit.lo; h.ld = hit.ld;
+            const Shading s = get_shading_data(sh, h, hit.front, load_shade_tri(sh, h.tri));
+            radiance = radiance + throughput * s.emission;
+            if (i == 0) depth = length3(s.position - ray.o);
+            if (!bounce_step(s, sx, sy, ray, throughput)) break;
+        }
+        depth = cam.far_ / (cam.far_ - cam.near_) * (1.0f - cam.near_ / depth);
+        const size_t idx = (size_t)ly * fp.width + px;
+        accumulate_pixel(fp, idx, radiance, accum, ldr);
+        if (depth_out) depth_out[idx] = depth;
+    }
+    if (COUNT) flush_counters(cnt, counters);
+}
+
+#undef JPT_ENV_NAME
+#undef JPT_ENV_PARAM
+#undef JPT_SKY

@@ -44,6 +44,60 @@ struct SceneShading {  // cold, once-per-hit data: kept in the reference layout
     int32_t sampler_mode;  // JPT_SAMPLER_*: bit 0 repeat, bit 1 linear
 };
 
+// ---- the environment map (jpt_set_environment): what a ray that leaves the scene sees instead of sample_sky -------------------
+
+constexpr int32_t kEnvMaxWidth = 16384, kEnvMaxHeight = 8192;
+
+// The map as the kernels see it, passed by value with every render: w x h texels (r, g, b, 0), row-major, row 0 the +y pole;
+// `rot` the row-major world -> map rotation, `intensity` the scale of every texel.
+struct EnvDev {
+    const float4* __restrict__ texels;
+    int32_t w, h;
+    float rot[9];
+    float intensity;
+};
+
+// the column / row of a floor()ed texel coordinate: columns wrap modulo w, rows clamp to [0, h - 1], a NaN is 0 (tex_index's rules)
+__host__ __device__ __forceinline__ int32_t env_column(float f, int32_t w)
+{
+    if (f != f || f >= 1073741824.0f || f <= -1073741824.0f) return 0;
+    const int32_t i = (int32_t)f % w;
+    return i < 0 ? i + w : i;
+}
+__host__ __device__ __forceinline__ int32_t env_row(float f, int32_t h)
+{
+    if (f != f) return 0;
+    if (f >= (float)(h - 1)) return h - 1;
+    return f <= 0.0f ? 0 : (int32_t)f;
+}
+__host__ __device__ __forceinline__ float env_lerp(float p, float q, float t) { return p + t * (q - p); }
+
+// The radiance the map sends along world direction d (DESIGN.md "Pinned semantics": a fixed sequence of binary32 operations,
+// restated in numpy by tests/test_environment_host.py).  m = R d; phi = atan2(m.x, -m.z), theta = atan2(|m.xz|, m.y); bilinear
+// between the texel centres around ((phi / 2pi + 1/2) w - 1/2, theta / pi h - 1/2), times the intensity.  The device and the host
+// mirror (jpt_debug_env_lookup) run this one function.
+__host__ __device__ __forceinline__ f3 env_radiance(const EnvDev& e, f3 d)
+{
+    const float mx = e.rot[0] * d.x + e.rot[1] * d.y + e.rot[2] * d.z;
+    const float my = e.rot[3] * d.x + e.rot[4] * d.y + e.rot[5] * d.z;
+    const float mz = e.rot[6] * d.x + e.rot[7] * d.y + e.rot[8] * d.z;
+    const float phi = atan2_(mx, -mz);
+    const float theta = atan2_(__builtin_sqrtf(mx * mx + mz * mz), my);
+    const float fu = (phi * 0.159154943f + 0.5f) * (float)e.w - 0.5f;   // 1 / 2pi
+    const float fv = theta * 0.318309886f * (float)e.h - 0.5f;          // 1 / pi
+    const float i0 = __builtin_floorf(fu), j0 = __builtin_floorf(fv);
+    float a = fu - i0, b = fv - j0;
+    if (a != a) a = 0.0f;
+    if (b != b) b = 0.0f;
+    const uint32_t x0 = (uint32_t)env_column(i0, e.w), x1 = (uint32_t)env_column(i0 + 1.0f, e.w);
+    const uint32_t r0 = (uint32_t)env_row(j0, e.h) * (uint32_t)e.w, r1 = (uint32_t)env_row(j0 + 1.0f, e.h) * (uint32_t)e.w;
+    const float4 t00 = e.texels[r0 + x0], t10 = e.texels[r0 + x1], t01 = e.texels[r1 + x0], t11 = e.texels[r1 + x1];
+    const float cx = env_lerp(env_lerp(t00.x, t10.x, a), env_lerp(t01.x, t11.x, a), b);
+    const float cy = env_lerp(env_lerp(t00.y, t10.y, a), env_lerp(t01.y, t11.y, a), b);
+    const float cz = env_lerp(env_lerp(t00.z, t10.z, a), env_lerp(t01.z, t11.z, a), b);
+    return f3{cx * e.intensity, cy * e.intensity, cz * e.intensity};
+}
+
 #if defined(__HIPCC__)   // (everything below is device code; the host layer -- jpt_capi.cpp, jpt_multi.cpp -- sees the structs above only)
 
 // ---- RNG (main.glsl:163-181) -----------------------------------------------------------------

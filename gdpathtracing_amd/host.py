@@ -49,6 +49,22 @@ def _close_live_contexts():
             pass
 
 
+def _env_map(rgb):
+    """An environment map as the C ABI takes it: float32 [height, width, 3], C order (None stays None)."""
+    if rgb is None:
+        return None, 0, 0
+    a = np.ascontiguousarray(rgb, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("an environment map is a [height, width, 3] array")
+    return a, a.shape[1], a.shape[0]
+
+
+def _env_rotation(rotation):
+    if rotation is None:
+        return None
+    return np.ascontiguousarray(rotation, dtype=np.float32).reshape(9)
+
+
 class Context:
     """One jpt_ctx (one GPU).  Thin, explicit wrapper: every method is one C-ABI call."""
 
@@ -225,6 +241,18 @@ class Context:
     def set_params(self, width, height, max_bounces=4, accum_mode=capi.ACCUM_REF_LDR8, sampler_mode=0):
         self._ck(self._lib.jpt_set_params(self.h, width, height, max_bounces, accum_mode, sampler_mode), "jpt_set_params")
         self.width, self.height = width, height
+
+    def set_environment(self, rgb):
+        """jpt_set_environment: light the scene with an HDR environment map, float32 [height, width, 3] (equirectangular, row 0
+        the +y pole; hdrio.load_hdr reads one), or None for main.glsl's sky gradient.  Waits for the renders already queued."""
+        a, w, h = _env_map(rgb)
+        self._ck(self._lib.jpt_set_environment(self.h, None if a is None else _ptr(a), w, h), "jpt_set_environment")
+
+    def set_environment_params(self, rotation=None, intensity: float = 1.0):
+        """jpt_set_environment_params: row-major 3x3 world -> map rotation (None: identity) and intensity, for later renders."""
+        r = _env_rotation(rotation)
+        self._ck(self._lib.jpt_set_environment_params(self.h, None if r is None else _ptr(r), float(intensity)),
+                 "jpt_set_environment_params")
 
     def set_kernel(self, variant):
         self._ck(self._lib.jpt_set_kernel(self.h, variant), "jpt_set_kernel")
@@ -523,6 +551,15 @@ class MultiContext:
     def set_params(self, width, height, max_bounces=4, accum_mode=capi.ACCUM_REF_LDR8, sampler_mode=0):
         self._ck(self._lib.jpt_multi_set_params(self.h, width, height, max_bounces, accum_mode, sampler_mode), "jpt_multi_set_params")
         self.width, self.height = width, height
+
+    def set_environment(self, rgb):
+        a, w, h = _env_map(rgb)
+        self._ck(self._lib.jpt_multi_set_environment(self.h, None if a is None else _ptr(a), w, h), "jpt_multi_set_environment")
+
+    def set_environment_params(self, rotation=None, intensity: float = 1.0):
+        r = _env_rotation(rotation)
+        self._ck(self._lib.jpt_multi_set_environment_params(self.h, None if r is None else _ptr(r), float(intensity)),
+                 "jpt_multi_set_environment_params")
 
     def set_camera(self, camera_block):
         cam = np.ascontiguousarray(camera_block, dtype=wire.CAMERA).reshape(1)

@@ -333,6 +333,30 @@ int jpt_scene_update_reference_tlas(jpt_ctx *ctx, const void *blas_instances, ui
 int jpt_set_params(jpt_ctx *ctx, int32_t width, int32_t height, int32_t max_bounces,
                    int32_t accum_mode, int32_t sampler_mode);
 
+/* Lighting from an HDR environment map instead of main.glsl's fixed sky gradient (no reference counterpart; the reference
+ * lists a sky HDRI among its wanted features).  Without a map -- the default, and after jpt_set_environment(ctx, NULL, 0, 0)
+ * -- every render is exactly what it was: the same kernels, the same bits.
+ *   rgb: `height` rows of `width` texels, 3 linear floats each, finite and >= 0, row 0 the +y pole, columns the longitude
+ *        (equirectangular, the layout of a Radiance .hdr panorama; gdpathtracing_amd.hdrio / jpt_host.hpp load_hdr read one).
+ *        At most 16384 x 8192 texels (JPT_E_LIMIT beyond); bad sizes, NaN, infinities or negative texels: JPT_E_INVALID.
+ *        The map belongs to the context, like jpt_set_params: it survives scene commits, uploads, jpt_scene_update_tlas,
+ *        jpt_scene_refit_tlas and jpt_scene_update_mesh; jpt_scene_share does not copy it.  The call WAITS for the renders the
+ *        context has queued (they finish with the old map) before it frees the old map and copies the new one (16 B per texel
+ *        on the device).  Host-only contexts: JPT_E_DEVICE after the checks.
+ * A ray that leaves the scene adds throughput * env_radiance(d), d its world direction: m = R d, phi = atan2(m.x, -m.z),
+ * theta = atan2(|m.xz|, m.y), bilinear between the texel centres at ((phi / 2pi + 1/2) width - 1/2, theta / pi height - 1/2),
+ * columns wrapping, rows clamped, times the intensity -- a fixed sequence of binary32 operations, the same
+ * on every kernel, tree kind, upload route and denoising mode.  In JPT_ACCUM_REF_LDR8 mode each frame is clamped to 8 bits as
+ * always, so a bright sun in the map is clamped per frame to 1.0; use JPT_ACCUM_HDR_F32 to keep its energy.  The map is
+ * reached by BRDF sampling alone (no importance sampling of the map, no next-event estimation): small bright suns converge
+ * slowly.  The debug-steps image has no sky and ignores the map. */
+int jpt_set_environment(jpt_ctx *ctx, const float *rgb, int32_t width, int32_t height);
+/* rotation9: row-major 3x3 world -> map (NULL: identity; each row's dot product is summed left to right), intensity: finite
+ * and >= 0 (default 1).  Passed by value with every later render: changing them (a time-of-day rotation every frame) never
+ * waits for queued renders.  Non-finite entries or a negative intensity: JPT_E_INVALID; host-only contexts: JPT_E_DEVICE
+ * after the checks. */
+int jpt_set_environment_params(jpt_ctx *ctx, const float *rotation9, float intensity);
+
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
  *   REFERENCE_LAYOUT   one thread per pixel straight over the six reference-layout buffers, node for node
@@ -483,6 +507,9 @@ int jpt_multi_update_reference_tlas(jpt_multi *m, const void *blas_instances, ui
 /* jpt_scene_update_mesh on every rank's replica */
 int jpt_multi_update_mesh(jpt_multi *m, uint32_t mesh_id, const jpt_surface *surfaces, int32_t n_surfaces);
 int jpt_multi_set_params(jpt_multi *m, int32_t width, int32_t height, int32_t max_bounces, int32_t accum_mode, int32_t sampler_mode);
+/* jpt_set_environment / jpt_set_environment_params on every rank */
+int jpt_multi_set_environment(jpt_multi *m, const float *rgb, int32_t width, int32_t height);
+int jpt_multi_set_environment_params(jpt_multi *m, const float *rotation9, float intensity);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -514,6 +541,12 @@ int jpt_debug_quantize_nodes4(const void *nodes4, uint32_t n_nodes, void *nodesq
 int jpt_debug_node_step4(int device_id, const void *nodes4, uint32_t n_nodes, const void *cases32, uint32_t n_cases,
                          int32_t host_rcp_ulps, uint8_t *taken_out);
 const char *jpt_debug_last_error(void);
+/* The environment lookup (jpt_set_environment) for n directions: rgb_out[3 i .. 3 i + 2] = env_radiance of dirs3[3 i .. 3 i + 2]
+ * with the map (rgb, width, height), rotation9 (NULL: identity) and intensity, checked as jpt_set_environment /
+ * jpt_set_environment_params check them.  device_id >= 0: the function the kernels inline, on that device;
+ * JPT_DEVICE_HOST_ONLY: the same function compiled for the host. */
+int jpt_debug_env_lookup(int device_id, const float *rgb, int32_t width, int32_t height, const float *rotation9,
+                         float intensity, const float *dirs3, uint32_t n, float *rgb_out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

@@ -19,6 +19,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -330,6 +331,76 @@ inline void load_obj(const std::string& text, ArrayMesh& mesh, std::vector<std::
             mesh.surfaces.push_back(std::move(groups[name].s));
             surface_materials.push_back(name);
         }
+}
+
+// Radiance RGBE (.hdr) panorama -> `height` rows of `width` texels, 3 linear floats each (jpt_set_environment's layout), from
+// the file's bytes.  The `-Y H +X W` orientation only (row 0 the top row: the +y pole of the map), flat or new-style run-length
+// scanlines; anything else throws std::runtime_error.  Ward's decoding, (m + 0.5) * 2^(e - 136) and 0 for e == 0, rounded once
+// to float: the floats of gdpathtracing_amd/hdrio.py load_hdr.
+inline void load_hdr(const std::string& bytes, std::vector<float>& rgb, int32_t& width, int32_t& height)
+{
+    auto bad = [](const char* why) { throw std::runtime_error(std::string("load_hdr: ") + why); };
+    const auto* d = reinterpret_cast<const unsigned char*>(bytes.data());
+    const size_t n = bytes.size();
+    if (bytes.compare(0, 10, "#?RADIANCE") != 0 && bytes.compare(0, 6, "#?RGBE") != 0) bad("not a Radiance file");
+    size_t pos = 0;
+    auto next_line = [&](std::string& line) {
+        const size_t end = bytes.find('\n', pos);
+        if (end == std::string::npos) bad("truncated header");
+        line = bytes.substr(pos, end - pos);
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        pos = end + 1;
+    };
+    std::string line;
+    for (;;) {
+        next_line(line);
+        if (line.empty()) break;
+        if (line.compare(0, 7, "FORMAT=") == 0 && line != "FORMAT=32-bit_rle_rgbe") bad("unsupported pixel format");
+    }
+    next_line(line);
+    long h = 0, w = 0;
+    char tail = 0;
+    if (std::sscanf(line.c_str(), "-Y %ld +X %ld%c", &h, &w, &tail) != 2 || line.compare(0, 3, "-Y ") != 0) bad("unsupported resolution line (only -Y H +X W)");
+    if (h <= 0 || w <= 0 || h > 1000000 || w > 1000000) bad("bad image size");
+    std::vector<unsigned char> row((size_t)w * 4), planes((size_t)w * 4);
+    rgb.assign((size_t)w * (size_t)h * 3, 0.0f);
+    for (long y = 0; y < h; y++) {
+        if (w >= 8 && w <= 0x7fff && pos + 4 <= n && d[pos] == 2 && d[pos + 1] == 2 && (d[pos + 2] & 0x80) == 0) {
+            if (((long)d[pos + 2] << 8 | d[pos + 3]) != w) bad("run-length scanline of the wrong width");
+            pos += 4;
+            for (int c = 0; c < 4; c++) {
+                for (long x = 0; x < w;) {
+                    if (pos >= n) bad("truncated run-length scanline");
+                    long k = d[pos++];
+                    if (k > 128) {
+                        k -= 128;
+                        if (x + k > w || pos >= n) bad("bad run in a scanline");
+                        std::memset(&planes[(size_t)c * w + x], d[pos++], (size_t)k);
+                    } else {
+                        if (k == 0 || x + k > w || pos + k > n) bad("bad literal in a scanline");
+                        std::memcpy(&planes[(size_t)c * w + x], d + pos, (size_t)k);
+                        pos += k;
+                    }
+                    x += k;
+                }
+            }
+            for (long x = 0; x < w; x++)
+                for (int c = 0; c < 4; c++) row[(size_t)x * 4 + c] = planes[(size_t)c * w + x];
+        } else {
+            if (pos + (size_t)w * 4 > n) bad("truncated scanline");
+            std::memcpy(row.data(), d + pos, (size_t)w * 4);
+            pos += (size_t)w * 4;
+            for (long x = 0; x < w; x++)
+                if (row[x * 4] == 1 && row[x * 4 + 1] == 1 && row[x * 4 + 2] == 1) bad("old-style run-length scanlines are not supported");
+        }
+        for (long x = 0; x < w; x++) {
+            const int e = row[(size_t)x * 4 + 3];
+            for (int c = 0; c < 3; c++)
+                rgb[((size_t)y * w + x) * 3 + c] = e == 0 ? 0.0f : (float)std::ldexp((double)row[(size_t)x * 4 + c] + 0.5, e - 136);
+        }
+    }
+    width = (int32_t)w;
+    height = (int32_t)h;
 }
 
 // Wavefront MTL -> StandardMaterial3D (the fields GeometryGroup3D converts to GpuMaterial, geometry_group3d.cpp:271-292):
@@ -676,6 +747,13 @@ class PathTracingCamera {
     void set_denoising_mode(Denoising m) { denoising_mode = m; }
     void set_global_transform(const Transform3D& t) { global_transform = t; }
     jpt_ctx* context() const { return ctx; }
+    // jpt_set_environment / jpt_set_environment_params (no reference counterpart: the reference's sky is main.glsl's gradient).
+    // rgb = nullptr: back to the gradient.  rotation9: row-major world -> map, nullptr the identity.
+    void set_environment(const float* rgb, int32_t w, int32_t h) { check(ctx, jpt_set_environment(ctx, rgb, w, h), "jpt_set_environment"); }
+    void set_environment_params(const float* rotation9, float intensity = 1.0f)
+    {
+        check(ctx, jpt_set_environment_params(ctx, rotation9, intensity), "jpt_set_environment_params");
+    }
 
     int max_bounces = 4;                    // the literal 5 of main.glsl:377 is max_bounces + 1
     int accum_mode = JPT_ACCUM_REF_LDR8;    // what the reference does (rgba8 screen image before the sum)
