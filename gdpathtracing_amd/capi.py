@@ -23,6 +23,7 @@ KERNEL_WAVEFRONT, KERNEL_REFERENCE_LAYOUT = 0, 1
 SAMPLER_NEAREST_CLAMP, SAMPLER_NEAREST_REPEAT, SAMPLER_LINEAR_CLAMP, SAMPLER_LINEAR_REPEAT = 0, 1, 2, 3
 DENOISE_PROGRESSIVE, DENOISE_TEMPORAL, DENOISE_NONE = 0, 1, 2
 OUTPUT_DEPTH = 1
+ENV_SAMPLING_BRDF, ENV_SAMPLING_MIS = 0, 1
 UPLOAD_NATIVE_TREE, UPLOAD_WALK_AS_GIVEN = 0, 1
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
@@ -44,6 +45,7 @@ SYMBOLS = [
     "jpt_debug_quantize_nodes4", "jpt_debug_node_step4", "jpt_debug_last_error", "jpt_debug_mesh_records",
     "jpt_set_environment", "jpt_set_environment_params", "jpt_multi_set_environment", "jpt_multi_set_environment_params",
     "jpt_debug_env_lookup",
+    "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
 ]
 
 
@@ -198,6 +200,12 @@ def lib():
     L.jpt_multi_set_environment.argtypes = [vp, vp, i32, i32]
     L.jpt_multi_set_environment_params.argtypes = [vp, vp, C.c_float]
     L.jpt_debug_env_lookup.argtypes = [C.c_int, vp, i32, i32, vp, C.c_float, vp, u32, vp]
+    if hasattr(L, "jpt_set_environment_sampling") or "JPT_LIB" not in os.environ:
+        L.jpt_set_environment_sampling.argtypes = [vp, i32]
+        L.jpt_multi_set_environment_sampling.argtypes = [vp, i32]
+        L.jpt_debug_env_tables.argtypes = [C.c_int, vp, i32, i32, vp, vp, vp]
+        L.jpt_debug_env_sample.argtypes = [C.c_int, vp, i32, i32, vp, vp, u32, vp, vp]
+        L.jpt_debug_env_pdf.argtypes = [C.c_int, vp, i32, i32, vp, vp, u32, vp]
     _lib = L
     return L
 

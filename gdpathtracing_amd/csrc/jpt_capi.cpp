@@ -267,6 +267,13 @@ struct jpt_ctx {
     float env_rot[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
     float env_intensity = 1.0f;
     EnvDev env_view;
+    // its importance sampling (jpt_set_environment_sampling): the mode, also the context's, and the map's tables -- built once per
+    // map while the mode is JPT_ENV_SAMPLING_MIS, then kept until the map changes
+    int32_t env_sampling = JPT_ENV_SAMPLING_BRDF;
+    DevBuf<float> d_env_cond, d_env_marg;   // h rows of w conditional CDF entries; the marginal CDF's h entries, then the total
+    bool env_tables = false;
+    float env_total = 0.0f;
+    EnvSampDev env_samp_view;
 
     jpt_stats stats;
 };
@@ -697,12 +704,18 @@ void compute_sky_cull(const jpt_ctx* c, SkyCull& out)
 
 int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking);
 
+// does a render of `c` now take the MIS kernels (and their workspace)?
+bool env_mis_render(const jpt_ctx* c)
+{
+    return c->env_sampling == JPT_ENV_SAMPLING_MIS && c->env_set && c->env_tables && c->env_total > 0.0f && !c->debug_steps;
+}
+
 // frames of one wavefront render that fit the workspace budget (all frames of a batch are in flight at once)
 int32_t frames_per_batch(const jpt_ctx* c, int32_t n_frames)
 {
     const size_t budget = c->workspace_budget ? (size_t)c->workspace_budget : (size_t)tuning().workspace_budget_mb << 20;
     if (c->kernel_variant == JPT_KERNEL_REFERENCE_LAYOUT || c->debug_steps || n_frames <= 1) return n_frames;
-    const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces);
+    const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c));
     const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(one, 1));
     return (int32_t)std::min<size_t>((size_t)n_frames, fit);
 }
@@ -730,7 +743,7 @@ int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool cou
         return do_render_batch(c, n_frames, first_frame_index, counted, blocking);  // reports the error / no-op
     // a budget the caller set is a cap, not a hint: one frame is the smallest batch there is
     if (c->workspace_budget && c->kernel_variant != JPT_KERNEL_REFERENCE_LAYOUT && !c->debug_steps) {
-        const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces);
+        const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c));
         if (one > c->workspace_budget)
             return fail(c, JPT_E_LIMIT, "jpt_set_memory_policy: one frame of this resolution needs a workspace of " + std::to_string(one) +
                                             " bytes, the budget is " + std::to_string(c->workspace_budget) +
@@ -912,7 +925,7 @@ LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, b
     // launches on every size tried: C3 1.32 vs 1.45 ms, C2 0.36 vs 0.46, 1 frame 0.30 vs 0.37, 1920x136 0.185 vs
     // 0.193, 4K x 16 spp 11.1 vs 11.1.  Renders whose workspace exceeds 24 GiB keep two slots and full-width launches
     // (4 x 24 GiB of workspaces is where this stops).
-    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces) > ((size_t)24 << 30);
+    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, env_mis_render(c)) > ((size_t)24 << 30);
     // ... six where the slots' streams have six hardware queues to themselves (six_queues_probe), four otherwise
     const bool may_queue = tuning().pipelining && !blocking && !counted;
     const int slots = forced_slots ? forced_slots : (huge ? 2 : ((may_queue && dev.six_queues(c)) ? 6 : 4));
@@ -1010,6 +1023,17 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     return JPT_OK;
 }
 
+// the map's sampling tables the renders of `c` take, or null: BRDF sampling alone (JPT_ENV_SAMPLING_BRDF, no map, or a black map,
+// whose MIS render is the BRDF-mode render: no map samples, every weight 1).  A view, valid until the next call.
+const EnvSampDev* env_sampling_of(jpt_ctx* c)
+{
+    if (!env_mis_render(c)) return nullptr;
+    c->env_samp_view.cond = c->d_env_cond.p;
+    c->env_samp_view.marg = c->d_env_marg.p;
+    c->env_samp_view.total = c->env_total;
+    return &c->env_samp_view;
+}
+
 // the environment map the renders of `c` see, or null (sample_sky); a view of the context's own copy, valid until the next call
 const EnvDev* environment_of(jpt_ctx* c)
 {
@@ -1053,7 +1077,7 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     if (counted) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(DevCounters), s));
     const bool wf2 = wavefront && c->local_rows > 0 && c->width > 0 && n_frames > 0;
     if (wf2) {
-        const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces);
+        const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces, env_mis_render(c));
         if (c->slot[0].workspace.n < need) {
             HIP_TRY(c, hipStreamSynchronize(s));
             HIP_TRY(c, c->slot[0].workspace.resize(need));
@@ -1070,6 +1094,7 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     c->trace_events_used = (int32_t)need_ev;
     compute_sky_cull(c, r.cull);
     r.env = environment_of(c);
+    r.env_samp = r.env ? env_sampling_of(c) : nullptr;
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
     // (With an environment map the accumulation makes up culled pixels exactly, frame by frame: the cells bound the gradient only.)
@@ -1107,7 +1132,8 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, c->debug_steps ? nullptr : environment_of(c));
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, c->debug_steps ? nullptr : environment_of(c),
+                             c->debug_steps ? nullptr : env_sampling_of(c));
         }
         return JPT_OK;
     }
@@ -1118,7 +1144,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
     }
     // a queued render: path kernels and accumulation on the slot's stream with the slot's workspace
     PipeSlot& ps = c->slot[p.slot];
-    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces);
+    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, r.env_samp != nullptr);
     bool slots_ready = true;
     for (int k = 0; k < p.slots; k++) slots_ready = slots_ready && c->slot[k].stream && c->slot[k].workspace.n >= need;
     if (!slots_ready) {
@@ -2215,6 +2241,16 @@ int check_env_params(const float* rotation9, float intensity, std::string& why)
     return JPT_OK;
 }
 
+bool env_rotation_orthonormal(const float* r)
+{
+    for (int a = 0; a < 3; a++)
+        for (int b = 0; b < 3; b++) {
+            const double d = (double)r[3 * a] * r[3 * b] + (double)r[3 * a + 1] * r[3 * b + 1] + (double)r[3 * a + 2] * r[3 * b + 2];
+            if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= kEnvOrthoTol)) return false;
+        }
+    return true;
+}
+
 void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out)
 {
     const size_t n = (size_t)width * (size_t)height;
@@ -2224,6 +2260,8 @@ void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vecto
 
 }  // namespace jpt
 }  // extern "C++"
+
+static int build_env_tables(jpt_ctx* c);
 
 int jpt_set_environment(jpt_ctx* c, const float* rgb, int32_t width, int32_t height)
 {
@@ -2237,6 +2275,9 @@ int jpt_set_environment(jpt_ctx* c, const float* rgb, int32_t width, int32_t hei
     HIP_TRY(c, hipSetDevice(c->device));
     // the renders already queued read the old map: they finish first (every one of them ends with work on the context's stream)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->env_tables = false;
+    c->d_env_cond.release();
+    c->d_env_marg.release();
     if (!rgb) {
         c->env_set = false;
         c->d_env.release();
@@ -2250,6 +2291,39 @@ int jpt_set_environment(jpt_ctx* c, const float* rgb, int32_t width, int32_t hei
     c->env_w = width;
     c->env_h = height;
     c->env_set = true;
+    if (c->env_sampling == JPT_ENV_SAMPLING_MIS) return build_env_tables(c);
+    return JPT_OK;
+}
+
+// the sampling tables of the context's map, on its stream (after the renders queued there: none of them reads the tables), and the
+// total weight read back -- the one wait of jpt_set_environment_sampling
+static int build_env_tables(jpt_ctx* c)
+{
+    const size_t w = (size_t)c->env_w, h = (size_t)c->env_h;
+    HIP_TRY(c, c->d_env_cond.resize(w * h));
+    HIP_TRY(c, c->d_env_marg.resize(h + 1));
+    launch_env_tables(c->stream, c->d_env.p, c->env_w, c->env_h, c->d_env_cond.p, c->d_env_marg.p, c->d_env_marg.p + h);
+    HIP_TRY(c, hipGetLastError());
+    float total = 0.0f;
+    HIP_TRY(c, hipMemcpyAsync(&total, c->d_env_marg.p + h, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->env_total = total;
+    c->env_tables = true;
+    return JPT_OK;
+}
+
+int jpt_set_environment_sampling(jpt_ctx* c, int32_t mode)
+{
+    if (!c) return JPT_E_INVALID;
+    if (mode != JPT_ENV_SAMPLING_BRDF && mode != JPT_ENV_SAMPLING_MIS) return fail(c, JPT_E_INVALID, "jpt_set_environment_sampling: unknown mode");
+    if (mode == JPT_ENV_SAMPLING_MIS && !env_rotation_orthonormal(c->env_rot))
+        return fail(c, JPT_E_INVALID, "jpt_set_environment_sampling: the map sampler needs an orthonormal rotation (jpt_set_environment_params)");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
+    c->env_sampling = mode;
+    if (mode == JPT_ENV_SAMPLING_MIS && c->env_set && !c->env_tables) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        return build_env_tables(c);
+    }
     return JPT_OK;
 }
 
@@ -2259,6 +2333,8 @@ int jpt_set_environment_params(jpt_ctx* c, const float* rotation9, float intensi
     std::string why;
     const int rc = check_env_params(rotation9, intensity, why);
     if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->env_sampling == JPT_ENV_SAMPLING_MIS && rotation9 && !env_rotation_orthonormal(rotation9))
+        return fail(c, JPT_E_INVALID, "jpt_set_environment_params: with JPT_ENV_SAMPLING_MIS the rotation must be orthonormal");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
     static const float kIdentity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
     std::memcpy(c->env_rot, rotation9 ? rotation9 : kIdentity, sizeof c->env_rot);

@@ -119,6 +119,107 @@ __global__ void env_lookup_probe(EnvDev env, const float* __restrict__ dirs3, ui
     rgb_out[3 * (size_t)i + 2] = c.z;
 }
 
+// jpt_debug_env_sample / jpt_debug_env_pdf: the sampler the MIS kernels inline (env_sample / env_pdf, jpt_shade.h), one item per thread
+__global__ void env_sample_probe(EnvDev env, EnvSampDev es, const float* __restrict__ in, uint32_t n, int sample, float* __restrict__ dirs_out,
+                                 float* __restrict__ pdf_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (sample) {
+        float pdf;
+        const f3 d = env_sample(env, es, in[2 * (size_t)i], in[2 * (size_t)i + 1], pdf);
+        dirs_out[3 * (size_t)i] = d.x;
+        dirs_out[3 * (size_t)i + 1] = d.y;
+        dirs_out[3 * (size_t)i + 2] = d.z;
+        pdf_out[i] = pdf;
+    } else {
+        pdf_out[i] = env_pdf(env, es, mk3(in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2]));
+    }
+}
+
+// The three env-sampling audit entries: the map's tables built on the device (launch_env_tables) or on the host (env_build_row /
+// env_build_marginal), then `what` = 0 nothing more, 1 env_sample of n (xi0, xi1) pairs, 2 env_pdf of n directions
+int env_sampling_debug(int device_id, const float* rgb, int32_t width, int32_t height, const float* rotation9, int what, const float* in,
+                       uint32_t n, float* dirs_out, float* pdf_out, float* cond_out, float* marg_out, float* total_out)
+{
+    if (!rgb || (n && (!in || !pdf_out || (what == 1 && !dirs_out)))) {
+        g_debug_error = "null argument";
+        return JPT_E_INVALID;
+    }
+    int rc = check_env_map(rgb, width, height, g_debug_error);
+    if (rc == JPT_OK) rc = check_env_params(rotation9, 1.0f, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    if (rotation9 && !env_rotation_orthonormal(rotation9)) {
+        g_debug_error = "the map sampler needs an orthonormal rotation";
+        return JPT_E_INVALID;
+    }
+    std::vector<float4> texels;
+    pack_env_texels(rgb, width, height, texels);
+    EnvDev env;
+    env.w = width;
+    env.h = height;
+    static const float kIdentity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    std::memcpy(env.rot, rotation9 ? rotation9 : kIdentity, sizeof env.rot);
+    env.intensity = 1.0f;
+    const size_t wh = (size_t)width * (size_t)height;
+    const size_t in_floats = (size_t)n * (what == 1 ? 2u : 3u);
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        std::vector<float> cond(wh), marg(height);
+        for (int32_t i = 0; i < height; i++) marg[i] = env_build_row(texels.data(), width, height, i, cond.data() + (size_t)i * width);
+        const float total = env_build_marginal(marg.data(), height);
+        if (cond_out) std::memcpy(cond_out, cond.data(), wh * sizeof(float));
+        if (marg_out) std::memcpy(marg_out, marg.data(), (size_t)height * sizeof(float));
+        if (total_out) *total_out = total;
+        env.texels = texels.data();
+        const EnvSampDev es{cond.data(), marg.data(), total};
+        for (uint32_t i = 0; i < n && what == 1; i++) {
+            const f3 d = env_sample(env, es, in[2 * (size_t)i], in[2 * (size_t)i + 1], pdf_out[i]);
+            dirs_out[3 * (size_t)i] = d.x;
+            dirs_out[3 * (size_t)i + 1] = d.y;
+            dirs_out[3 * (size_t)i + 2] = d.z;
+        }
+        for (uint32_t i = 0; i < n && what == 2; i++)
+            pdf_out[i] = env_pdf(env, es, f3{in[3 * (size_t)i], in[3 * (size_t)i + 1], in[3 * (size_t)i + 2]});
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* w) {
+        g_debug_error = std::string(w) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    float4* d_tex = nullptr;
+    float *d_cond = nullptr, *d_marg = nullptr, *d_in = nullptr, *d_dirs = nullptr, *d_pdf = nullptr;
+    if ((e = hipMalloc((void**)&d_tex, wh * sizeof(float4))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && (e = hipMalloc((void**)&d_cond, wh * sizeof(float))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && (e = hipMalloc((void**)&d_marg, ((size_t)height + 1) * sizeof(float))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && n && (e = hipMalloc((void**)&d_in, in_floats * sizeof(float))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && n && (e = hipMalloc((void**)&d_dirs, (size_t)n * 3u * sizeof(float))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && n && (e = hipMalloc((void**)&d_pdf, (size_t)n * sizeof(float))) != hipSuccess) rc = hip_fail(e, "hipMalloc");
+    if (rc == JPT_OK && (e = hipMemcpy(d_tex, texels.data(), wh * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && n && (e = hipMemcpy(d_in, in, in_floats * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    float total = 0.0f;
+    if (rc == JPT_OK) {
+        launch_env_tables(nullptr, d_tex, width, height, d_cond, d_marg, d_marg + height);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "launch_env_tables");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(&total, d_marg + height, sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && n && what) {
+        env.texels = d_tex;
+        const EnvSampDev es{d_cond, d_marg, total};
+        hipLaunchKernelGGL(env_sample_probe, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, env, es, d_in, n, what == 1 ? 1 : 0, d_dirs, d_pdf);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "env_sample_probe");
+    }
+    if (rc == JPT_OK && cond_out && (e = hipMemcpy(cond_out, d_cond, wh * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && marg_out && (e = hipMemcpy(marg_out, d_marg, (size_t)height * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && total_out) *total_out = total;
+    if (rc == JPT_OK && n && what == 1 && (e = hipMemcpy(dirs_out, d_dirs, (size_t)n * 3u * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && n && what && (e = hipMemcpy(pdf_out, d_pdf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    for (void* p : {(void*)d_tex, (void*)d_cond, (void*)d_marg, (void*)d_in, (void*)d_dirs, (void*)d_pdf})
+        if (p) (void)hipFree(p);
+    return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -240,6 +341,23 @@ int jpt_debug_env_lookup(int device_id, const float* rgb, int32_t width, int32_t
     if (d_dirs) (void)hipFree(d_dirs);
     if (d_out) (void)hipFree(d_out);
     return rc;
+}
+
+int jpt_debug_env_tables(int device_id, const float* rgb, int32_t width, int32_t height, float* cond_out, float* marg_out, float* total_out)
+{
+    return env_sampling_debug(device_id, rgb, width, height, nullptr, 0, nullptr, 0, nullptr, nullptr, cond_out, marg_out, total_out);
+}
+
+int jpt_debug_env_sample(int device_id, const float* rgb, int32_t width, int32_t height, const float* rotation9, const float* xi2, uint32_t n,
+                         float* dirs_out, float* pdf_out)
+{
+    return env_sampling_debug(device_id, rgb, width, height, rotation9, 1, xi2, n, dirs_out, pdf_out, nullptr, nullptr, nullptr);
+}
+
+int jpt_debug_env_pdf(int device_id, const float* rgb, int32_t width, int32_t height, const float* rotation9, const float* dirs3, uint32_t n,
+                      float* pdf_out)
+{
+    return env_sampling_debug(device_id, rgb, width, height, rotation9, 2, dirs3, n, nullptr, pdf_out, nullptr, nullptr, nullptr);
 }
 
 }  // extern "C"

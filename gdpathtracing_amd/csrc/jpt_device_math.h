@@ -57,7 +57,7 @@ __device__ __forceinline__ f3 xform_dir(const float* __restrict__ m, f3 d)
 
 // sin and cos of x (|x| small, here [0, 2*pi]): octant j = floor(|x| * 4/pi) rounded up to even,
 // three-constant Cody-Waite reduction by pi/4, single-precision minimax polynomials on [-pi/4, pi/4].
-__device__ __forceinline__ void sincos_(float x, float& s_out, float& c_out)
+__host__ __device__ __forceinline__ void sincos_(float x, float& s_out, float& c_out)
 {
     const float ax = __builtin_fabsf(x);
     float y = __builtin_floorf(ax * 1.27323954473516f);

@@ -200,10 +200,17 @@ __device__ __forceinline__ void count_walk(DevCounters& c, uint32_t steps)
 int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why);
 int check_env_params(const float* rotation9, float intensity, std::string& why);
 void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out);
+// the map's sampling tables built on the device (jpt_kernels_post.hip), on `stream`: cond (w * h floats), marg (h floats) and the
+// total weight (one float), all device memory: one thread per row (env_build_row), then one thread for the marginal
+void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int32_t h, float* cond, float* marg, float* total);
+// JPT_ENV_SAMPLING_MIS needs an orthonormal rotation: every entry of R R^T within kEnvOrthoTol of the identity's
+constexpr double kEnvOrthoTol = 1e-4;
+bool env_rotation_orthonormal(const float* rotation9);
 
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env = nullptr);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env = nullptr,
+                      const EnvSampDev* env_samp = nullptr);
 
 // The persistent-block pipeline (jpt_kernels_wf2.hip): one render of fp.n_frames frames over the flattened layout;
 // fp.frame_index / fp.frame_count are those of the FIRST frame.  The first (max_bounces + 2) *
@@ -217,7 +224,7 @@ void launch_sky_tiles(hipStream_t stream, const FrameParams& fp, const RefCamera
 uint32_t wf2_segments();
 uint32_t trace_stack_capacity();  // entries a lane's traversal stack can hold (LDS + scratch)
 // bytes of the workspace a render of this size carves (wf2_layout), for any frame-group count and window
-size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces);
+size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis = false);   // mis: + the shadow queues (Wf2Nee)
 // Screen rectangles (pixels, inclusive) of the boxes the TLAS root offers a ray; a primary ray through a pixel
 // outside all of them is known to fail all of the root's box tests, i.e. to reach the sky after exactly one TLAS
 // expansion, without being traced.  n < 0: unknown, trace everything.  Filled on the host (jpt_capi.cpp).
@@ -238,6 +245,8 @@ struct Wf2Render {
     hipEvent_t before_acc = nullptr;       // the accumulation kernel waits for this event (whatever its stream)
     const uint32_t* sky_tiles = nullptr;   // per 8 x 8 tile of the context's share of the image: its one rgba8 sky cell, if it has one
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
+    const EnvSampDev* env_samp = nullptr;  // with `env`: its sampling tables (JPT_ENV_SAMPLING_MIS, a map of non-zero weight): the *_mis
+                                           // kernels and wf2_occlude, and the workspace's MIS buffers
     const EnvDev* env = nullptr;           // the environment map the misses see (jpt_set_environment); null: sample_sky.  The
                                            // launches then take the *_env kernels, and the accumulation uses no sky cells
 };

@@ -204,4 +204,25 @@ void launch_assemble(hipStream_t stream, const float4* gathered, const float4* o
                        accum_full, ldr_full, frame_count);
 }
 
+// ---- the environment map's sampling tables (jpt_set_environment_sampling): env_build_row / env_build_marginal, jpt_shade.h -------
+// Sequential sums per row and over the rows: the same bits on every run and device, and those of the host build.  A 16384-texel
+// row is one thread's loop; the build runs once per map.
+__global__ __launch_bounds__(64) void env_rows_kernel(const float4* __restrict__ texels, int32_t w, int32_t h, float* __restrict__ cond,
+                                                      float* __restrict__ rows)
+{
+    const int32_t i = (int32_t)(blockIdx.x * 64u + threadIdx.x);
+    if (i >= h) return;
+    rows[i] = env_build_row(texels, w, h, i, cond + (size_t)i * (size_t)w);
+}
+__global__ __launch_bounds__(64) void env_marginal_kernel(float* __restrict__ rows, int32_t h, float* __restrict__ total)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) *total = env_build_marginal(rows, h);
+}
+void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int32_t h, float* cond, float* marg, float* total)
+{
+    if (w <= 0 || h <= 0) return;
+    hipLaunchKernelGGL(env_rows_kernel, dim3(((uint32_t)h + 63u) / 64u), dim3(64), 0, stream, texels, w, h, cond, marg);
+    hipLaunchKernelGGL(env_marginal_kernel, dim3(1), dim3(64), 0, stream, marg, h, total);
+}
+
 }  // namespace jpt

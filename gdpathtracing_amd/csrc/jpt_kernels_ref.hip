@@ -188,16 +188,19 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 }
 
 
-// the frame kernel (jpt_ref_frame.h): the default one, then ref_frame_kernel_env
+// the frame kernel (jpt_ref_frame.h): the default one, then ref_frame_kernel_env, then ref_frame_kernel_mis
 #define JPT_ENV 0
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
 #define JPT_ENV 1
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
+#define JPT_ENV 2
+#include "jpt_ref_frame.h"
+#undef JPT_ENV
 
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env)
+                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env, const EnvSampDev* env_samp)
 {
     RefSceneDev sc;
     sc.tri_geom = ds.ref_tri_geom;
@@ -212,7 +215,9 @@ void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FramePara
     dim3 grid((fp.width + 31) / 32, (fp.local_rows + 7) / 8), block(256);
     const bool ties = ds.x.ok && ds.reach_tri != nullptr && !fp.debug_steps;
     with_consts<2, 2>([&](auto C, auto TIES) {
-        if (env)
+        if (env && env_samp)
+            hipLaunchKernelGGL((ref_frame_kernel_mis<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, *env, *env_samp);
+        else if (env)
             hipLaunchKernelGGL((ref_frame_kernel_env<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, *env);
         else
             hipLaunchKernelGGL((ref_frame_kernel<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters);

@@ -615,11 +615,63 @@ __global__ __launch_bounds__(kBlock) void wf2_sky_tiles(Wf2Dims dm, FrameParams 
     tile_cell[t] = ok ? cell : 0u;
 }
 
-// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, then the *_env ones
+// ---- next-event estimation of the environment map (JPT_ENV_SAMPLING_MIS) ----------------------------------------------------
+
+// The MIS pipeline's own buffers, carved behind the rest of the layout (wf2_layout) and passed to its kernels only
+struct Wf2Nee {
+    float4* sh_o;       // shadow queue entry ([segment][entry], as the ray queues): origin.xyz, w = path id bits | kNeeFinal
+    float4* sh_d;       // the map direction
+    float4* sh_c;       // the contribution if unoccluded
+    uint32_t* scount;   // [max_bounces][kSegments] shadow rays queued by wf2_shade_mis of bounce b (zeroed at the render's start)
+    float* pdf;         // per path: the BRDF density of its last sampled direction (the weight of a miss at the next vertex)
+};
+constexpr uint32_t kNeeFinal = 0x80000000u;   // the path ended at the vertex that cast the shadow ray: its final value is stored here
+
+// a shadow ray has been traced: the unoccluded contribution joins rad[path]; a path that ended at the vertex is stored
+__device__ __forceinline__ void nee_land(const Wf2Buffers& wb, int accum_mode, const float4 so, const float4 sc4, bool blocked)
+{
+    const uint32_t w = __float_as_uint(so.w), p = w & kPathMask;
+    const float4 r4 = wb.rad[p];
+    f3 r = mk3(r4.x, r4.y, r4.z);
+    if (!blocked) r = r + mk3(sc4.x, sc4.y, sc4.z);
+    if (w & kNeeFinal) store_final(wb, accum_mode, p, r);
+    else if (!blocked) wb.rad[p] = make_float4(r.x, r.y, r.z, 0.0f);
+}
+
+// The shadow rays wf2_shade_mis queued at `bounce`: one lane per ray, the closest-hit walk of the native tree stopped at its first
+// accepted triangle ("blocked": some triangle's Moller-Trumbore test accepts t <= 1e9, no reach or tie logic -- on the native tree
+// the brute-force answer).  The whole stack is in LDS (one wave per block): no scratch.  Runs between wf2_shade_mis of `bounce` and
+// that of bounce + 1, so the contributions join each path's radiance in vertex order.
+constexpr int kOccBlock = 64;
+template <bool COUNT, bool W4>
+__global__ __launch_bounds__(kOccBlock) void wf2_occlude(WideSceneDev sc, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, int bounce, Wf2Nee nee,
+                                                         DevCounters* __restrict__ counters)
+{
+    constexpr int kDepth = kStackLds + kStackSpill;
+    __shared__ int32_t stack[kDepth * kOccBlock];
+    const uint32_t seg = blockIdx.y;
+    const uint32_t i = blockIdx.x * kOccBlock + threadIdx.x;
+    if (i >= nee.scount[(size_t)bounce * kSegments + seg]) return;
+    const size_t at = (size_t)seg * dm.seg_cap + i;
+    const float4 so = stream_ld4(&nee.sh_o[at]), sd = stream_ld4(&nee.sh_d[at]), sc4 = stream_ld4(&nee.sh_c[at]);
+    const typename Traversal<COUNT, W4>::Stack st{&stack[threadIdx.x], nullptr, kOccBlock, kDepth, 0};
+    DevCounters cnt = {};
+    Traversal<COUNT, W4> tr;
+    tr.begin(sc, mk3(so.x, so.y, so.z), mk3(sd.x, sd.y, sd.z));
+    while (tr.hit.t >= 1e9f && tr.step(sc, st, cnt)) {
+    }
+    nee_land(wb, fp.accum_mode, so, sc4, tr.hit.t < 1e9f);
+    if (COUNT) flush_counters(cnt, counters);
+}
+
+// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, the *_env ones, then the *_mis ones
 #define JPT_ENV 0
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 2
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 
@@ -731,9 +783,10 @@ struct Wf2Layout {
     float4* rad;          // all groups' blocks, [slot][frame of the group] each
     uint32_t* fin8;
     float* first_depth;
+    Wf2Nee gnee[kMaxGroups];   // (MIS renders only: carved behind everything else, so the other buffers stay where they are)
     size_t bytes = 0;     // the end of the last buffer
 };
-static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window)
+static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window, bool mis = false)
 {
     Wf2Layout L;
     auto carve = [&](size_t bytes) {
@@ -776,10 +829,22 @@ static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const
         L.gfp[g].n_frames = nf;
         L.gfp[g].depth_frame = (fp.depth_frame >= 0 && f0 + nf == fp.n_frames) ? nf - 1 : -1;  // the render's last frame writes the depth image (when there is one: jpt_set_outputs)
     }
+    for (int g = 0; g < groups && mis; g++) {
+        int f0, nf;
+        group_frames(fp.n_frames, groups, g, f0, nf);
+        const size_t q = (size_t)L.gdm[g].seg_cap * kSegments;
+        const size_t paths = (size_t)L.gdm[g].slots_per_frame * (size_t)nf;
+        Wf2Nee& ne = L.gnee[g];
+        ne.sh_o = (float4*)carve(q * sizeof(float4));
+        ne.sh_d = (float4*)carve(q * sizeof(float4));
+        ne.sh_c = (float4*)carve(q * sizeof(float4));
+        ne.scount = (uint32_t*)carve((size_t)(fp.max_bounces > 0 ? fp.max_bounces : 1) * kSegments * sizeof(uint32_t));
+        ne.pdf = (float*)carve(paths * sizeof(float));
+    }
     return L;
 }
 
-size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces)
+size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis)
 {
     // every layout a render of this size may use: the largest of 1..kMaxGroups groups over the whole image
     FrameParams fp{};
@@ -789,7 +854,7 @@ size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_boun
     fp.max_bounces = max_bounces;
     size_t worst = 0;
     for (int groups = 1; groups <= kMaxGroups && groups <= (n_frames < 1 ? 1 : n_frames); groups++)
-        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows)).bytes);
+        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows), mis).bytes);
     return worst;
 }
 
@@ -808,7 +873,8 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     const TileWindow window = cull_window(r.cull, fp);
     const Wf2Dims dm_all = make_dims(fp.width, fp.local_rows, fp.n_frames, window);
     if (dm_all.n_chunks == 0) return;
-    const Wf2Layout L = wf2_layout(workspace, fp, groups, window);
+    const EnvSampDev* es = r.env ? r.env_samp : nullptr;   // the MIS kernels (jpt_wf2_paths.h, JPT_ENV 2)
+    const Wf2Layout L = wf2_layout(workspace, fp, groups, window, es != nullptr);
     const int nq = fp.max_bounces + 2;
 
     const bool w4 = ds.use4;
@@ -843,13 +909,14 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     const int finish_walk = !w4 ? 0 : (sx.ok ? 2 : 1);
     const EnvDev* env = r.env;   // an environment map: the *_env kernels (jpt_wf2_paths.h)
     // the pipeline of one group on one stream
-    auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, hipEvent_t* ev) {
+    auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, const Wf2Nee& nee, hipEvent_t* ev) {
         // (the queue sizes of bounces >= 1 and the set-aside counts start from zero: wf2_primary clears them)
         // Blocks go to the 8 XCDs round-robin by linear index (y * grid.x + x), and the chunks of a segment are far from
         // alike (the first ones are full, the last ones empty): with grid.x a multiple of 8 every XCD would always get
         // the same chunk position.  An odd grid.x deals every position to every XCD (capping C3's grid.x from 37 to 8
         // cost 9 %).
         const dim3 sgrid(((dm.seg_cap + kBlock - 1) / kBlock) | 1u, kSegments);
+        if (es && gp.max_bounces > 0) (void)hipMemsetAsync(nee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
         if (ev) (void)hipEventRecord(ev[0], st);
         with_consts<2, 3>([&](auto C, auto W) {
             if (env)
@@ -860,12 +927,20 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {
             with_consts<2, 2, 3>([&](auto C, auto LAST, auto TEX) {
-                if (env)
+                if (es)
+                    hipLaunchKernelGGL((wf2_shade_mis<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env, *es, nee);
+                else if (env)
                     hipLaunchKernelGGL((wf2_shade_env<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env);
                 else
                     hipLaunchKernelGGL((wf2_shade<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters);
             }, count, b == gp.max_bounces, texmode);
             if (b == gp.max_bounces) break;
+            if (es) {
+                const dim3 ogrid(((dm.seg_cap + kOccBlock - 1) / kOccBlock) | 1u, kSegments);
+                with_consts<2, 3>([&](auto C, auto W) {
+                    hipLaunchKernelGGL((wf2_occlude<C, W != 0>), ogrid, dim3(kOccBlock), 0, st, sc, wb, dm, gp, b, nee, counters);
+                }, count, walk);
+            }
             if (ev) (void)hipEventRecord(ev[2 * (b + 1)], st);
             with_consts<2, 3>([&](auto C, auto W) {
                 hipLaunchKernelGGL((wf2_trace<C, W != 0, W == 2>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
@@ -875,7 +950,9 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (sh.reach_tri) {  // the paths set aside because their hit is undecidable on the native tree: finished exactly
             const dim3 rgrid(256), rblock(64);   // (blocks past the set-aside count exit at once; more records than threads: grid-stride)
             with_consts<2, 3>([&](auto C, auto W) {
-                if (env)
+                if (es)
+                    hipLaunchKernelGGL((wf2_finish_mis<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env, *es, nee);
+                else if (env)
                     hipLaunchKernelGGL((wf2_finish_env<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env);
                 else
                     hipLaunchKernelGGL((wf2_finish<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
@@ -884,14 +961,14 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     };
 
     if (groups == 1) {
-        run_group(stream, L.gb[0], L.gdm[0], L.gfp[0], trace_events);
+        run_group(stream, L.gb[0], L.gdm[0], L.gfp[0], L.gnee[0], trace_events);
     } else {
         // fork: the helper streams start after everything already queued on the context's stream
         (void)hipEventRecord(streams.fork, stream);
         for (int g = 1; g < groups; g++) (void)hipStreamWaitEvent(streams.aux_stream[g - 1], streams.fork, 0);
         // issue the groups' launches interleaved, so none of the streams runs ahead of the others on the host side
         // (run_group enqueues a whole pipeline; the hardware queues of the streams drain concurrently)
-        for (int g = 0; g < groups; g++) run_group(g == 0 ? stream : streams.aux_stream[g - 1], L.gb[g], L.gdm[g], L.gfp[g], nullptr);
+        for (int g = 0; g < groups; g++) run_group(g == 0 ? stream : streams.aux_stream[g - 1], L.gb[g], L.gdm[g], L.gfp[g], L.gnee[g], nullptr);
         // join, then fold the other groups' queue sizes into group 0's (the host reads those for the ray count)
         for (int g = 1; g < groups; g++) {
             (void)hipEventRecord(streams.join[g - 1], streams.aux_stream[g - 1]);

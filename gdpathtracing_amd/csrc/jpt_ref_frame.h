@@ -1,9 +1,16 @@
 // jpt_ref_frame.h -- ref_frame_kernel, the audit route's one kernel (jpt_kernels_ref.hip), which sees the paths' misses.  Included
 // twice by jpt_kernels_ref.hip, as jpt_wf2_paths.h is by jpt_kernels_wf2.hip:
 //   JPT_ENV 0   ref_frame_kernel, main.glsl's gradient (sample_sky): the same source, token for token, as before the map existed;
-//   JPT_ENV 1   ref_frame_kernel_env (jpt_set_environment): one more parameter, the map, and env_radiance at the miss.
+//   JPT_ENV 1   ref_frame_kernel_env (jpt_set_environment): one more parameter, the map, and env_radiance at the miss;
+//   JPT_ENV 2   ref_frame_kernel_mis (JPT_ENV_SAMPLING_MIS): also the map's sampling tables; below the last bounce each vertex casts
+//               its map sample's shadow ray at once (ray_trace_tlas on the reference layout: a hit there is "blocked"), and a
+//               miss at bounce >= 1 is weighted against that strategy -- the arithmetic of jpt_wf2_paths.h's *_mis kernels.
 // (No include guard: that is the point.)
-#if JPT_ENV
+#if JPT_ENV == 2
+#define JPT_ENV_NAME(name) name##_mis
+#define JPT_ENV_PARAM , EnvDev env, EnvSampDev es
+#define JPT_SKY(d) env_radiance(env, d)
+#elif JPT_ENV
 #define JPT_ENV_NAME(name) name##_env
 #define JPT_ENV_PARAM , EnvDev env
 #define JPT_SKY(d) env_radiance(env, d)
@@ -32,6 +39,9 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
         float depth = cam.far_;
         f3 radiance = mk3(0.0f, 0.0f, 0.0f);
         f3 throughput = mk3(1.0f, 1.0f, 1.0f);
+#if JPT_ENV == 2
+        float p_brdf = 0.0f;   // the BRDF density of the current ray's direction (bounces >= 1)
+#endif
         if (fp.debug_steps) {   // #ifdef DEBUG_STEPS (main.glsl:358-361, 423-427): the primary ray's triangle tests / 256, depth = far
             RefHit hit;
             if (COUNT) cnt.rays++;
@@ -44,6 +54,10 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             if (COUNT) cnt.rays++;
             const bool is_hit = ray_trace_tlas<COUNT>(sc, ray, hit, cnt);
             if (!is_hit) {
+#if JPT_ENV == 2
+                if (i > 0) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, p_brdf);
+                else
+#endif
                 radiance = radiance + throughput * JPT_SKY(ray.d);
                 break;
             }
@@ -74,7 +88,23 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             const Shading s = get_shading_data(sh, h, hit.front, load_shade_tri(sh, h.tri));
             radiance = radiance + throughput * s.emission;
             if (i == 0) depth = length3(s.position - ray.o);
+#if JPT_ENV == 2
+            if (i < fp.max_bounces) {
+                f3 l, c;
+                if (env_nee(s, env, es, sx, sy, throughput, l, c)) {
+                    Ray sray;
+                    sray.o = s.position + s.normal * 0.001f;
+                    sray.d = l;
+                    sray.rD = rcp3(l);
+                    RefHit sh_hit;
+                    DevCounters none = {};
+                    if (!ray_trace_tlas<false>(sc, sray, sh_hit, none)) radiance = radiance + c;
+                }
+            }
+            if (!bounce_step_pdf(s, sx, sy, ray, throughput, p_brdf)) break;
+#else
             if (!bounce_step(s, sx, sy, ray, throughput)) break;
+#endif
         }
         depth = cam.far_ / (cam.far_ - cam.near_) * (1.0f - cam.near_ / depth);
         const size_t idx = (size_t)ly * fp.width + px;

@@ -98,6 +98,111 @@ __host__ __device__ __forceinline__ f3 env_radiance(const EnvDev& e, f3 d)
     return f3{cx * e.intensity, cy * e.intensity, cz * e.intensity};
 }
 
+// ---- importance sampling of the map (jpt_set_environment_sampling, JPT_ENV_SAMPLING_MIS) -------------------------------------
+//
+// A piecewise-constant distribution over the texels: texel (i, j) of row i weighs lum(i, j) * sin(theta_i), theta_i the row
+// centre's polar angle, lum = 0.2126 r + 0.7152 g + 0.0722 b (the intensity scales every texel alike: the tables are the map's).
+// Per row a conditional CDF over its columns, and a marginal CDF over the rows, both normalised sequential prefix sums whose last
+// entry is exactly 1 (a row of weight 0 is all 1s).  Built by one function, on the device (env_tables_rows / env_tables_marginal,
+// jpt_kernels_post.hip) and on the host (jpt_debug_env_tables), so the two give the same bits.
+
+struct EnvSampDev {   // the tables of the context's map, passed by value with every MIS render
+    const float* __restrict__ cond;   // h rows of w entries
+    const float* __restrict__ marg;   // h entries
+    float total;                      // sum of all weights; 0: the map is black and is never sampled (pdf 0)
+};
+
+__host__ __device__ __forceinline__ float env_row_sin(int32_t i, int32_t h)
+{
+    float s, c;
+    sincos_(((float)i + 0.5f) / (float)h * 3.14159274f, s, c);
+    return s;
+}
+__host__ __device__ __forceinline__ float env_weight(const float4 t, float row_sin)
+{
+    return (0.2126f * t.x + 0.7152f * t.y + 0.0722f * t.z) * row_sin;
+}
+// row i of the conditional CDF (w entries at `out`); returns the row's weight
+__host__ __device__ __forceinline__ float env_build_row(const float4* texels, int32_t w, int32_t h, int32_t i, float* out)
+{
+    const float rs = env_row_sin(i, h);
+    float sum = 0.0f;
+    for (int32_t j = 0; j < w; j++) {
+        sum = sum + env_weight(texels[(size_t)i * (size_t)w + (size_t)j], rs);
+        out[j] = sum;
+    }
+    for (int32_t j = 0; j < w - 1; j++) out[j] = sum > 0.0f ? out[j] / sum : 1.0f;
+    out[w - 1] = 1.0f;
+    return sum;
+}
+// the marginal CDF from the rows' weights (in place, h entries); returns the total
+__host__ __device__ __forceinline__ float env_build_marginal(float* rows, int32_t h)
+{
+    float sum = 0.0f;
+    for (int32_t i = 0; i < h; i++) {
+        sum = sum + rows[i];
+        rows[i] = sum;
+    }
+    for (int32_t i = 0; i < h - 1; i++) rows[i] = sum > 0.0f ? rows[i] / sum : 1.0f;
+    rows[h - 1] = 1.0f;
+    return sum;
+}
+// the first k in [0, n) with cdf[k] > x (np.searchsorted(cdf, x, side="right")), for x < cdf[n - 1] = 1
+__host__ __device__ __forceinline__ int32_t env_upper_bound(const float* cdf, int32_t n, float x)
+{
+    int32_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (cdf[mid] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    return lo;
+}
+// The density, per unit solid angle, with which env_sample draws world direction d: (weight_ij / total) * w h / (2 pi^2 sin theta),
+// (i, j) the texel the lookup's mapping puts d in (m = R d, u = phi / 2pi + 1/2, v = theta / pi), sin theta = |m.xz|.  0 when
+// sin theta = 0 or the map is black.
+__host__ __device__ __forceinline__ float env_pdf(const EnvDev& e, const EnvSampDev& s, f3 d)
+{
+    if (!(s.total > 0.0f)) return 0.0f;
+    const float mx = e.rot[0] * d.x + e.rot[1] * d.y + e.rot[2] * d.z;
+    const float my = e.rot[3] * d.x + e.rot[4] * d.y + e.rot[5] * d.z;
+    const float mz = e.rot[6] * d.x + e.rot[7] * d.y + e.rot[8] * d.z;
+    const float sin_t = __builtin_sqrtf(mx * mx + mz * mz);
+    if (!(sin_t > 0.0f)) return 0.0f;
+    const float phi = atan2_(mx, -mz);
+    const float theta = atan2_(sin_t, my);
+    const int32_t j = env_column(__builtin_floorf((phi * 0.159154943f + 0.5f) * (float)e.w), e.w);
+    const int32_t i = env_row(__builtin_floorf(theta * 0.318309886f * (float)e.h), e.h);
+    const float wt = env_weight(e.texels[(size_t)i * (size_t)e.w + (size_t)j], env_row_sin(i, e.h));
+    return wt / s.total * ((float)e.w * (float)e.h) / (19.7392088f * sin_t);   // 2 pi^2
+}
+// A world direction drawn with the tables from (xi0, xi1) in [0, 1] (each clamped below 1): the row by xi1 on the marginal CDF,
+// the column by xi0 on the row's conditional CDF, the point inside the texel by where xi falls between the texel's CDF entries;
+// u, v -> phi = (u - 1/2) 2pi, theta = v pi -> m = (sin theta sin phi, cos theta, -sin theta cos phi), d = R^T m.  pdf_out =
+// env_pdf(d).  A black map: d = 0, pdf 0.
+__host__ __device__ __forceinline__ f3 env_sample(const EnvDev& e, const EnvSampDev& s, float xi0, float xi1, float& pdf_out)
+{
+    pdf_out = 0.0f;
+    if (!(s.total > 0.0f)) return f3{0.0f, 0.0f, 0.0f};
+    xi0 = xi0 < 0.99999994f ? xi0 : 0.99999994f;
+    xi1 = xi1 < 0.99999994f ? xi1 : 0.99999994f;
+    const int32_t i = env_upper_bound(s.marg, e.h, xi1);
+    const float m0 = i > 0 ? s.marg[i - 1] : 0.0f, m1 = s.marg[i];
+    const float* row = s.cond + (size_t)i * (size_t)e.w;
+    const int32_t j = env_upper_bound(row, e.w, xi0);
+    const float c0 = j > 0 ? row[j - 1] : 0.0f, c1 = row[j];
+    const float dv = (xi1 - m0) / (m1 - m0), du = (xi0 - c0) / (c1 - c0);
+    const float u = ((float)j + du) / (float)e.w, v = ((float)i + dv) / (float)e.h;
+    float st, ct, sp, cp;
+    sincos_(v * 3.14159274f, st, ct);
+    sincos_((u - 0.5f) * 6.28318548f, sp, cp);
+    const float mx = st * sp, my = ct, mz = -(st * cp);
+    const f3 d{e.rot[0] * mx + e.rot[3] * my + e.rot[6] * mz, e.rot[1] * mx + e.rot[4] * my + e.rot[7] * mz,
+               e.rot[2] * mx + e.rot[5] * my + e.rot[8] * mz};
+    pdf_out = env_pdf(e, s, d);
+    return d;
+}
+
 #if defined(__HIPCC__)   // (everything below is device code; the host layer -- jpt_capi.cpp, jpt_multi.cpp -- sees the structs above only)
 
 // ---- RNG (main.glsl:163-181) -----------------------------------------------------------------
@@ -431,6 +536,51 @@ __device__ __forceinline__ bool bounce_step(const Shading& s, uint32_t& sx, uint
     const f3 f = (brdf_eval(s, ray.d) * lambert_in) / density;
     throughput = throughput * f;
     return true;
+}
+
+// ---- next-event estimation of the map (JPT_ENV_SAMPLING_MIS) ----------------------------------------------------------------
+//
+// bounce_step with the BRDF density of the sampled direction handed out: the MIS weight of the next vertex's miss needs it
+__device__ __forceinline__ bool bounce_step_pdf(const Shading& s, uint32_t& sx, uint32_t& sy, Ray& ray, f3& throughput, float& density)
+{
+    ray.o = s.position + s.normal * 0.001f;
+    float xi0, xi1;
+    pcg2d(sx, sy, xi0, xi1);
+    ray.d = sample_brdf(s, xi0, xi1);
+    ray.rD = rcp3(ray.d);
+    density = brdf_density(s, ray.d);
+    const float lambert_in = dot3(s.normal, ray.d);
+    if (lambert_in <= 0.0f) return false;
+    const f3 f = (brdf_eval(s, ray.d) * lambert_in) / density;
+    throughput = throughput * f;
+    return true;
+}
+// The map sample of a path vertex: its randoms come from a COPY of the vertex's seeds (taken before bounce_step draws), hashed by
+// one pcg2d round of (sx ^ 0x68bc21eb, sy ^ 0x02e5be93) -- the path's own sequence does not advance.  True when a shadow ray
+// is to be cast from s.position + s.normal * 0.001 along `l`: n.l > 0 and a non-zero contribution, which is then
+//     ((throughput * (brdf_eval(l) * n.l)) * L_env(l)) * (w_env / p_env),   w_env = p_env^2 / (p_env^2 + p_brdf(l)^2).
+__device__ __forceinline__ bool env_nee(const Shading& s, const EnvDev& e, const EnvSampDev& es, uint32_t sx, uint32_t sy, f3 throughput,
+                                        f3& l, f3& contrib)
+{
+    uint32_t hx = sx ^ 0x68bc21ebu, hy = sy ^ 0x02e5be93u;
+    float xi0, xi1;
+    pcg2d(hx, hy, xi0, xi1);
+    float pe;
+    l = env_sample(e, es, xi0, xi1, pe);
+    if (!(pe > 0.0f)) return false;
+    const float ndl = dot3(s.normal, l);
+    if (!(ndl > 0.0f)) return false;
+    const float pb = brdf_density(s, l);
+    const float w = (pe * pe) / (pe * pe + pb * pb);
+    contrib = ((throughput * (brdf_eval(s, l) * ndl)) * env_radiance(e, l)) * (w / pe);
+    return contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f;
+}
+// the weight of a BRDF-sampled miss at bounce >= 1 (p_brdf: the previous vertex's density of d): p_brdf^2 / (p_brdf^2 + p_env(d)^2)
+__device__ __forceinline__ float env_miss_weight(const EnvDev& e, const EnvSampDev& es, f3 d, float p_brdf)
+{
+    const float pe = env_pdf(e, es, d);
+    if (!(pe > 0.0f)) return 1.0f;
+    return (p_brdf * p_brdf) / (p_brdf * p_brdf + pe * pe);
 }
 
 __device__ __forceinline__ f3 aces_film(f3 x)  // progressive_rendering.glsl:19-26

@@ -5,19 +5,37 @@
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
 //               every miss.  wf2_primary_env queues its misses with its hits, for wf2_shade_env to look up (it takes no map);
 //               wf2_accumulate_env makes up every sky-culled pixel exactly, frame by frame: the sky cells bound the gradient only.
+//   JPT_ENV 2   the *_mis kernels (jpt_set_environment_sampling, JPT_ENV_SAMPLING_MIS): shade_entry_mis, wf2_shade_mis and
+//               wf2_finish_mis, which also take the map's sampling tables (EnvSampDev) and the shadow queue (Wf2Nee).  A vertex
+//               below the last bounce draws one map direction (env_nee) and queues a shadow ray for wf2_occlude; a miss at bounce
+//               >= 1 is weighted against that strategy (env_miss_weight).  The primary and accumulation launches are the *_env
+//               ones: a primary miss has weight 1.
 // A run-time branch on the map in the default kernels would cost them registers; a template parameter would change their names.
 // (No include guard: that is the point.)
-#if JPT_ENV
+#if JPT_ENV == 2
+#define JPT_ENV_NAME(name) name##_mis
+#define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, Wf2Nee nee
+#define JPT_ENV_ARG , env, es, nee
+#define JPT_NEE_PARAM , bool& shadow, float4& so, float4& sd, float4& sc4
+#define JPT_NEE_ARG , shadow, so, sd, sc4
+#define JPT_SKY(d) env_radiance(env, d)
+#elif JPT_ENV
 #define JPT_ENV_NAME(name) name##_env
 #define JPT_ENV_PARAM , EnvDev env
 #define JPT_ENV_ARG , env
+#define JPT_NEE_PARAM
+#define JPT_NEE_ARG
 #define JPT_SKY(d) env_radiance(env, d)
 #else
 #define JPT_ENV_NAME(name) name
 #define JPT_ENV_PARAM
 #define JPT_ENV_ARG
+#define JPT_NEE_PARAM
+#define JPT_NEE_ARG
 #define JPT_SKY(d) sample_sky(d)
 #endif
+
+#if JPT_ENV != 2   // (the MIS pipeline runs wf2_primary_env)
 
 // ---- bounce 0: generate + trace ------------------------------------------------------------------------
 
@@ -174,6 +192,8 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_pr
     if (COUNT) flush_counters(cnt, counters);
 }
 
+#endif  // JPT_ENV != 2
+
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
 #ifndef JPT_SHADE_WAVES
@@ -190,9 +210,14 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_pr
 template <bool COUNT, bool LAST = false, int TEX = 3>
 __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& fp, float cam_far,
                                             int bounce, const float4 ro, const float4 rd, const float4 tin, const float4 ha, const uint32_t hb,
-                                            bool check_reach, bool& unreachable, float4& no, float4& nd, float4& nt, DevCounters& cnt JPT_ENV_PARAM)
+                                            bool check_reach, bool& unreachable, float4& no, float4& nd, float4& nt, DevCounters& cnt JPT_ENV_PARAM JPT_NEE_PARAM)
 {
     unreachable = false;
+#if JPT_ENV == 2
+    // (MIS: a shadow ray of this vertex, for wf2_occlude: so = origin.xyz | path id + kNeeFinal when the path ends here, sd = the map
+    // direction, sc4 = the contribution if unoccluded.  rad[path] then holds the radiance so far, which the shadow ray adds to.)
+    shadow = false;
+#endif
     const uint32_t p = __float_as_uint(rd.w) & kPathMask;
     const bool had_radiance = (__float_as_uint(rd.w) & kHasRadiance) != 0u;
     f3 throughput, radiance;
@@ -278,6 +303,10 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
     if (COUNT && bounce > 0) cnt.rays++;
     bool alive = false;
     if (!is_hit) {
+#if JPT_ENV == 2
+        if (bounce > 0) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, nee.pdf[p]);
+        else
+#endif
         radiance = radiance + throughput * JPT_SKY(ray.d);
         if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = cam_far;  // (only a redone primary hit can turn into a miss here)
     } else {
@@ -285,17 +314,43 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
         const Shading s = get_shading_data<TEX>(sh, h, (hb >> 31) != 0u, stri);
         radiance = radiance + throughput * s.emission;
         if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = length3(s.position - ray.o);
+#if JPT_ENV == 2
+        if (!LAST && bounce < fp.max_bounces) {
+            f3 l, c;
+            shadow = env_nee(s, env, es, sx, sy, throughput, l, c);
+            if (shadow) {
+                const f3 so3 = s.position + s.normal * 0.001f;
+                so = make_float4(so3.x, so3.y, so3.z, __uint_as_float(p));
+                sd = make_float4(l.x, l.y, l.z, 0.0f);
+                sc4 = make_float4(c.x, c.y, c.z, 0.0f);
+            }
+            float density;
+            alive = bounce_step_pdf(s, sx, sy, ray, throughput, density);
+            if (alive) nee.pdf[p] = density;
+        }
+#else
         if (!LAST && bounce < fp.max_bounces) alive = bounce_step(s, sx, sy, ray, throughput);
+#endif
         if (COUNT && alive && throughput.x == 0.0f && throughput.y == 0.0f && throughput.z == 0.0f) cnt.zero_thr++;
     }
     if (alive) {
         // (radiance starts as +0 and +0 + x is x or +0, never -0: "unchanged and never written" means exactly +0)
+#if JPT_ENV == 2
+        const bool changed = shadow || radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
+#else
         const bool changed = radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
+#endif
         if (changed) wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
         nt = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(sx));
         no = make_float4(ray.o.x, ray.o.y, ray.o.z, __uint_as_float(sy));
         nd = make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(p | ((had_radiance || changed) ? kHasRadiance : 0u)));
     } else {
+#if JPT_ENV == 2
+        if (shadow) {   // the path ends here, but its shadow ray has yet to land: wf2_occlude stores its final value
+            wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+            so.w = __uint_as_float(p | kNeeFinal);
+        } else
+#endif
         store_final(wb, fp.accum_mode, p, radiance);
     }
     return alive;
@@ -321,14 +376,34 @@ __global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVE
     const uint32_t i = base + threadIdx.x;
     bool alive = false;
     float4 no, nd, nt;
+#if JPT_ENV == 2
+    bool shadow = false;
+    float4 so, sd, sc4;
+#endif
     if (i < n) {
         const float4 ro = stream_ld4(&wb.ray_o[in][seg_base + i]), rd = stream_ld4(&wb.ray_d[in][seg_base + i]);
         const float4 tin = bounce > 0 ? stream_ld4(&wb.thr_q[in][seg_base + i]) : make_float4(1.0f, 1.0f, 1.0f, 0.0f);
         const float4 ha = stream_ld4(&wb.hit_a[seg_base + i]);
         const uint32_t hb = stream_ldu(&wb.hit_b[seg_base + i]);
         bool unreachable;   // (set aside inside shade_entry: nothing more to do here)
-        alive = JPT_ENV_NAME(shade_entry)<COUNT, LAST, TEX>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, true, unreachable, no, nd, nt, cnt JPT_ENV_ARG);
+        alive = JPT_ENV_NAME(shade_entry)<COUNT, LAST, TEX>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, true, unreachable, no, nd, nt, cnt JPT_ENV_ARG JPT_NEE_ARG);
     }
+#if JPT_ENV == 2
+    if (!LAST) {   // the shadow rays, packed into the segment's shadow queue of this bounce as the next rays are below
+        const unsigned long long sm = __ballot(shadow);
+        if (sm) {
+            uint32_t sbase = 0;
+            if (lane == 0) sbase = atomicAdd(&nee.scount[(size_t)bounce * kSegments + seg], (uint32_t)__popcll(sm));
+            sbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)sbase);
+            if (shadow) {
+                const size_t j = seg_base + sbase + lanes_below(sm, lane);
+                stream_st4(&nee.sh_o[j], so);
+                stream_st4(&nee.sh_d[j], sd);
+                stream_st4(&nee.sh_c[j], sc4);
+            }
+        }
+    }
+#endif
     if (LAST) {   // (no path goes on: nothing to pack)
         if (COUNT) flush_counters(cnt, counters);
         return;
@@ -405,7 +480,22 @@ __global__ __launch_bounds__(64) void JPT_ENV_NAME(wf2_finish)(WideSceneDev sc, 
             const uint32_t hb = (hit.inst & ~kHitTied) | (hit.front ? 0x80000000u : 0u);
             bool unreachable;
             float4 no, nd, nt;
+#if JPT_ENV == 2
+            bool shadow;
+            float4 so, sd, sc4;
+            const bool alive = shade_entry_mis<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt JPT_ENV_ARG JPT_NEE_ARG);
+            if (shadow) {   // the shadow ray at once, on the native tree without reach tests (wf2_occlude's walk)
+                Traversal<COUNT, W4> occ;
+                const typename Traversal<COUNT, W4>::Stack ost{nullptr, stack_mem, 0, 0, kDepth};
+                occ.begin(sc, mk3(so.x, so.y, so.z), mk3(sd.x, sd.y, sd.z));
+                while (occ.hit.t >= 1e9f && occ.step(sc, ost, cnt)) {
+                }
+                nee_land(wb, fp.accum_mode, so, sc4, occ.hit.t < 1e9f);
+            }
+            if (!alive) break;
+#else
             if (!JPT_ENV_NAME(shade_entry)<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt JPT_ENV_ARG)) break;
+#endif
             ro = no;
             rd = nd;
             tin = nt;
@@ -414,6 +504,7 @@ __global__ __launch_bounds__(64) void JPT_ENV_NAME(wf2_finish)(WideSceneDev sc, 
     if (COUNT) flush_counters(cnt, counters);
 }
 
+#if JPT_ENV != 2
 // ---- per pixel: frames in order -> accumulation buffer, display image, depth ----------------------------------
 
 __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffers wb, Wf2Dims dm, FrameParams fp, RefCamera cam, SkyCull cull,
@@ -632,7 +723,11 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
     }
 }
 
+#endif  // JPT_ENV != 2
+
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM
 #undef JPT_ENV_ARG
+#undef JPT_NEE_PARAM
+#undef JPT_NEE_ARG
 #undef JPT_SKY

@@ -254,6 +254,11 @@ class Context:
         self._ck(self._lib.jpt_set_environment_params(self.h, None if r is None else _ptr(r), float(intensity)),
                  "jpt_set_environment_params")
 
+    def set_environment_sampling(self, mode):
+        """jpt_set_environment_sampling: capi.ENV_SAMPLING_BRDF (default) or capi.ENV_SAMPLING_MIS (importance sampling of the map
+        with shadow rays, combined with BRDF sampling by the power heuristic), for later renders."""
+        self._ck(self._lib.jpt_set_environment_sampling(self.h, int(mode)), "jpt_set_environment_sampling")
+
     def set_kernel(self, variant):
         self._ck(self._lib.jpt_set_kernel(self.h, variant), "jpt_set_kernel")
 
@@ -560,6 +565,9 @@ class MultiContext:
         r = _env_rotation(rotation)
         self._ck(self._lib.jpt_multi_set_environment_params(self.h, None if r is None else _ptr(r), float(intensity)),
                  "jpt_multi_set_environment_params")
+
+    def set_environment_sampling(self, mode):
+        self._ck(self._lib.jpt_multi_set_environment_sampling(self.h, int(mode)), "jpt_multi_set_environment_sampling")
 
     def set_camera(self, camera_block):
         cam = np.ascontiguousarray(camera_block, dtype=wire.CAMERA).reshape(1)

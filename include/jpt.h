@@ -348,14 +348,42 @@ int jpt_set_params(jpt_ctx *ctx, int32_t width, int32_t height, int32_t max_boun
  * columns wrapping, rows clamped, times the intensity -- a fixed sequence of binary32 operations, the same
  * on every kernel, tree kind, upload route and denoising mode.  In JPT_ACCUM_REF_LDR8 mode each frame is clamped to 8 bits as
  * always, so a bright sun in the map is clamped per frame to 1.0; use JPT_ACCUM_HDR_F32 to keep its energy.  The map is
- * reached by BRDF sampling alone (no importance sampling of the map, no next-event estimation): small bright suns converge
- * slowly.  The debug-steps image has no sky and ignores the map. */
+ * reached by BRDF sampling alone unless jpt_set_environment_sampling(ctx, JPT_ENV_SAMPLING_MIS) adds importance sampling of
+ * the map with shadow rays (below): without it small bright suns converge slowly.  The debug-steps image has no sky and ignores the map. */
 int jpt_set_environment(jpt_ctx *ctx, const float *rgb, int32_t width, int32_t height);
 /* rotation9: row-major 3x3 world -> map (NULL: identity; each row's dot product is summed left to right), intensity: finite
  * and >= 0 (default 1).  Passed by value with every later render: changing them (a time-of-day rotation every frame) never
  * waits for queued renders.  Non-finite entries or a negative intensity: JPT_E_INVALID; host-only contexts: JPT_E_DEVICE
  * after the checks. */
 int jpt_set_environment_params(jpt_ctx *ctx, const float *rotation9, float intensity);
+
+/* Importance sampling of the environment map (no reference counterpart; the reference lists next-event estimation among its
+ * wanted features).  The mode belongs to the context, like the map: it survives scene commits, uploads, jpt_scene_update_tlas,
+ * jpt_scene_refit_tlas and jpt_scene_update_mesh; jpt_scene_share does not copy it.  Each render takes it by value: queued
+ * renders keep the mode of their own call.
+ *   JPT_ENV_SAMPLING_BRDF (default)  the map is reached by BRDF sampling alone: the same kernels and bits as without this call.
+ *   JPT_ENV_SAMPLING_MIS             every hit below the last bounce (bounce < max_bounces) also draws one direction l from the
+ *        map's own distribution and casts a shadow ray from position + normal * 0.001 (no t limit); unoccluded and with n.l > 0
+ *        it adds throughput * brdf(l) * n.l * L_env(l) * w_env / p_env(l); a BRDF-sampled miss at bounce >= 1 adds its
+ *        radiance times w_brdf = p_brdf^2 / (p_brdf^2 + p_env^2) (the power heuristic; a primary miss keeps weight 1).  Where
+ *        p_env = 0 the BRDF sample covers the direction alone: the estimator stays unbiased and small bright suns converge in
+ *        a few frames.  The distribution is piecewise constant over the texels, each weighing its luminance (0.2126 r +
+ *        0.7152 g + 0.0722 b) times sin theta at its row's centre; p_env(d) = (weight / total) * width * height /
+ *        (2 pi^2 sin theta), the texel being the one the lookup's mapping puts d in.  The NEE randoms
+ *        come from a hashed copy of the vertex's seeds, so every BRDF-sampled continuation is the one BRDF mode takes.
+ *        "Blocked" means the pipeline's closest-hit query along the shadow ray finds a triangle (t <= 1e9): on the native
+ *        trees the brute-force answer, on the reference-layout tree (JPT_KERNEL_REFERENCE_LAYOUT) that tree's answer, without
+ *        reach or tie logic in either.  The sampler needs an orthonormal rotation: with MIS on, jpt_set_environment_params
+ *        refuses one whose R R^T is further than 1e-4 from the identity in any entry (JPT_E_INVALID), and so does this call
+ *        when it enables MIS.  Without a map, or with an all-black one, MIS renders are BRDF renders.
+ * The tables (4 B per texel + 4 B per row on the device) are built on the device when they are first needed -- at this call
+ * with a map present, or at jpt_set_environment while MIS is on -- and this is the one case in which the call waits for the
+ * context's queued renders; they are kept until the map changes, so switching back and forth never waits.  An MIS render's
+ * workspace holds a shadow-ray queue (48 B per queue entry) and 4 B per path more (jpt_get_workspace_bytes counts them
+ * while MIS is on).  A bad mode: JPT_E_INVALID; host-only contexts: JPT_E_DEVICE after the checks. */
+#define JPT_ENV_SAMPLING_BRDF 0
+#define JPT_ENV_SAMPLING_MIS  1
+int jpt_set_environment_sampling(jpt_ctx *ctx, int32_t mode);
 
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
@@ -510,6 +538,7 @@ int jpt_multi_set_params(jpt_multi *m, int32_t width, int32_t height, int32_t ma
 /* jpt_set_environment / jpt_set_environment_params on every rank */
 int jpt_multi_set_environment(jpt_multi *m, const float *rgb, int32_t width, int32_t height);
 int jpt_multi_set_environment_params(jpt_multi *m, const float *rotation9, float intensity);
+int jpt_multi_set_environment_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -547,6 +576,20 @@ const char *jpt_debug_last_error(void);
  * JPT_DEVICE_HOST_ONLY: the same function compiled for the host. */
 int jpt_debug_env_lookup(int device_id, const float *rgb, int32_t width, int32_t height, const float *rotation9,
                          float intensity, const float *dirs3, uint32_t n, float *rgb_out);
+/* The map sampler of JPT_ENV_SAMPLING_MIS for the map (rgb, width, height) and rotation9 (NULL: identity; checked as
+ * jpt_set_environment_params checks it with MIS on), device_id >= 0 on that device (tables built by the kernels the context
+ * uses), JPT_DEVICE_HOST_ONLY the same functions compiled for the host:
+ *   _tables: cond_out[height * width] the per-row conditional CDFs, marg_out[height] the marginal CDF, total_out[0] the total
+ *            weight (any output may be NULL);
+ *   _sample: for xi2[2 i], xi2[2 i + 1] (column and row randoms in [0, 1]): dirs_out[3 i ..] the world direction and pdf_out[i]
+ *            its density per steradian (0 and a zero direction for a black map);
+ *   _pdf:    pdf_out[i] = the density of world direction dirs3[3 i ..]. */
+int jpt_debug_env_tables(int device_id, const float *rgb, int32_t width, int32_t height, float *cond_out, float *marg_out,
+                         float *total_out);
+int jpt_debug_env_sample(int device_id, const float *rgb, int32_t width, int32_t height, const float *rotation9,
+                         const float *xi2, uint32_t n, float *dirs_out, float *pdf_out);
+int jpt_debug_env_pdf(int device_id, const float *rgb, int32_t width, int32_t height, const float *rotation9,
+                      const float *dirs3, uint32_t n, float *pdf_out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form
