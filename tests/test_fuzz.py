@@ -18,6 +18,19 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
+def forty_coincident_copies():
+    """coincident soup 3 (two meshes, four instances) with forty coincident copies of one large triangle, with different
+    normals and uvs, in every mesh"""
+    import copy
+    sc = copy.deepcopy(scenes.random_scene(3, n_meshes=2, n_instances=4, tris_per_surface=60, coincident=True))
+    for mesh in sc.meshes:
+        surf = mesh.surfaces[0]
+        v = np.asarray(surf.vertices, dtype=np.float32).reshape(-1, 3, 3).copy()
+        v[4:44] = np.array([[-1.5, -1.2, 0.1], [1.6, -1.1, -0.2], [0.1, 1.7, 0.3]], dtype=np.float32)
+        surf.vertices = v.reshape(-1, 3)
+    return sc
+
+
 @pytest.mark.parametrize("seed", SEEDS + [100, 101, 102, 103])
 def test_builder_arrays_equal_the_oracles(hiplib, oracle, seed):
     sc = scenes.random_scene(seed, n_meshes=3 + seed % 3, n_instances=5 + seed % 7, tris_per_surface=17 + 13 * (seed % 5))
@@ -194,13 +207,7 @@ def test_many_coincident_copies_fall_back_to_the_whole_reference_walk(oracle, hi
     least ten leaves: more than the tie walk's list holds (8).  Such a vertex is decided by the reference's WHOLE walk of
     its own trees (jpt_tie_walk.h, `overflow`) -- slow, exact: the native routes still equal the oracle's normal walk bit
     for bit."""
-    import copy
-    sc = copy.deepcopy(scenes.random_scene(3, n_meshes=2, n_instances=4, tris_per_surface=60, coincident=True))
-    for mesh in sc.meshes:
-        surf = mesh.surfaces[0]
-        v = np.asarray(surf.vertices, dtype=np.float32).reshape(-1, 3, 3).copy()
-        v[4:44] = np.array([[-1.5, -1.2, 0.1], [1.6, -1.1, -0.2], [0.1, 1.7, 0.3]], dtype=np.float32)
-        surf.vertices = v.reshape(-1, 3)
+    sc = forty_coincident_copies()
     w, h, bounces, frames = 96, 64, 2, 2
     cam = scenes.camera_block(sc.camera, w, h)
     ref = oracle.build_scene(sc)
@@ -232,15 +239,8 @@ def test_instance_of_an_empty_mesh_shows_what_the_reference_shows(oracle, hiplib
     triangles in its place.  With forty coincident copies in that mesh the tie walk runs in its whole-walk mode, where every
     instance is visited (an empty leaf read as an interior node sent the ray through node 0 by accident; now the
     instance IS an instance of that mesh, in the oracle's arrays and in the product's)."""
-    import copy
     from tests.test_oracle_builder import with_empty_mesh
-    sc = copy.deepcopy(scenes.random_scene(3, n_meshes=2, n_instances=4, tris_per_surface=60, coincident=True))
-    for mesh in sc.meshes:
-        surf = mesh.surfaces[0]
-        v = np.asarray(surf.vertices, dtype=np.float32).reshape(-1, 3, 3).copy()
-        v[4:44] = np.array([[-1.5, -1.2, 0.1], [1.6, -1.1, -0.2], [0.1, 1.7, 0.3]], dtype=np.float32)
-        surf.vertices = v.reshape(-1, 3)
-    sc = with_empty_mesh(sc, "last")
+    sc = with_empty_mesh(forty_coincident_copies(), "last")
     w, h, bounces, frames = 96, 64, 2, 2
     cam = scenes.camera_block(sc.camera, w, h)
     ref = oracle.build_scene(sc)
