@@ -24,6 +24,7 @@ SAMPLER_NEAREST_CLAMP, SAMPLER_NEAREST_REPEAT, SAMPLER_LINEAR_CLAMP, SAMPLER_LIN
 DENOISE_PROGRESSIVE, DENOISE_TEMPORAL, DENOISE_NONE = 0, 1, 2
 OUTPUT_DEPTH = 1
 ENV_SAMPLING_BRDF, ENV_SAMPLING_MIS = 0, 1
+LIGHT_SAMPLING_BRDF, LIGHT_SAMPLING_MIS = 0, 1
 UPLOAD_NATIVE_TREE, UPLOAD_WALK_AS_GIVEN = 0, 1
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
@@ -46,6 +47,7 @@ SYMBOLS = [
     "jpt_set_environment", "jpt_set_environment_params", "jpt_multi_set_environment", "jpt_multi_set_environment_params",
     "jpt_debug_env_lookup",
     "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
+    "jpt_set_light_sampling", "jpt_multi_set_light_sampling", "jpt_debug_light_tables", "jpt_debug_light_sample", "jpt_debug_light_pdf",
 ]
 
 
@@ -206,6 +208,12 @@ def lib():
         L.jpt_debug_env_tables.argtypes = [C.c_int, vp, i32, i32, vp, vp, vp]
         L.jpt_debug_env_sample.argtypes = [C.c_int, vp, i32, i32, vp, vp, u32, vp, vp]
         L.jpt_debug_env_pdf.argtypes = [C.c_int, vp, i32, i32, vp, vp, u32, vp]
+    if hasattr(L, "jpt_set_light_sampling") or "JPT_LIB" not in os.environ:
+        L.jpt_set_light_sampling.argtypes = [vp, i32]
+        L.jpt_multi_set_light_sampling.argtypes = [vp, i32]
+        L.jpt_debug_light_tables.argtypes = [vp, u32, vp, vp, vp, vp, vp]
+        L.jpt_debug_light_sample.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+        L.jpt_debug_light_pdf.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
     _lib = L
     return L
 

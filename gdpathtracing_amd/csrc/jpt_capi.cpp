@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
@@ -274,11 +275,23 @@ struct jpt_ctx {
     bool env_tables = false;
     float env_total = 0.0f;
     EnvSampDev env_samp_view;
+    // importance sampling of the emissive triangles (jpt_set_light_sampling): the mode, the context's like the map's; the emitters
+    // (instance, triangle pairs from c->ref, host) and their device tables -- both made at the first render that needs them after
+    // the scene changed (light_cand_stale: its instances or materials; light_table_stale: also its geometry, refits included)
+    int32_t light_sampling = JPT_LIGHT_SAMPLING_BRDF;
+    std::vector<uint32_t> light_cand_h;
+    bool light_cand_stale = true, light_cand_uploaded = false, light_table_stale = true;
+    DevBuf<uint32_t> d_light_cand;
+    DevBuf<float4> d_light_tri;
+    DevBuf<float> d_light_cdf, d_light_marg;   // per emitter; the marginal CDF's n_blocks entries, then the total power
+    LightDev light_view;
 
     jpt_stats stats;
 };
 
 namespace {
+
+void lights_stale(jpt_ctx* c, bool listed);
 
 int fail(jpt_ctx* c, int code, const std::string& msg)
 {
@@ -514,6 +527,7 @@ int upload_shadow(jpt_ctx* c, bool instances_only)
 // host RefScene (+ flatten) -> device
 int upload_scene(jpt_ctx* c)
 {
+    lights_stale(c, true);
     std::string err;
     if (!flatten(c->ref, c->wide, err)) return fail(c, JPT_E_INVALID, "flatten: " + err);
     const bool use4 = walks_nodes4(c);
@@ -710,12 +724,20 @@ bool env_mis_render(const jpt_ctx* c)
     return c->env_sampling == JPT_ENV_SAMPLING_MIS && c->env_set && c->env_tables && c->env_total > 0.0f && !c->debug_steps;
 }
 
+// will a render of `c` take the light-sampling kernels?  (Before the emitter list is made: yes if the mode asks for them -- a bound
+// for sizing only; light_render decides.)
+bool light_render_bound(const jpt_ctx* c)
+{
+    return c->light_sampling == JPT_LIGHT_SAMPLING_MIS && !c->debug_steps && c->device >= 0 && c->scene_ready &&
+           (c->light_cand_stale || !c->light_cand_h.empty());
+}
+
 // frames of one wavefront render that fit the workspace budget (all frames of a batch are in flight at once)
 int32_t frames_per_batch(const jpt_ctx* c, int32_t n_frames)
 {
     const size_t budget = c->workspace_budget ? (size_t)c->workspace_budget : (size_t)tuning().workspace_budget_mb << 20;
     if (c->kernel_variant == JPT_KERNEL_REFERENCE_LAYOUT || c->debug_steps || n_frames <= 1) return n_frames;
-    const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c));
+    const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c), light_render_bound(c));
     const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(one, 1));
     return (int32_t)std::min<size_t>((size_t)n_frames, fit);
 }
@@ -743,7 +765,7 @@ int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool cou
         return do_render_batch(c, n_frames, first_frame_index, counted, blocking);  // reports the error / no-op
     // a budget the caller set is a cap, not a hint: one frame is the smallest batch there is
     if (c->workspace_budget && c->kernel_variant != JPT_KERNEL_REFERENCE_LAYOUT && !c->debug_steps) {
-        const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c));
+        const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c), light_render_bound(c));
         if (one > c->workspace_budget)
             return fail(c, JPT_E_LIMIT, "jpt_set_memory_policy: one frame of this resolution needs a workspace of " + std::to_string(one) +
                                             " bytes, the budget is " + std::to_string(c->workspace_budget) +
@@ -925,7 +947,7 @@ LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, b
     // launches on every size tried: C3 1.32 vs 1.45 ms, C2 0.36 vs 0.46, 1 frame 0.30 vs 0.37, 1920x136 0.185 vs
     // 0.193, 4K x 16 spp 11.1 vs 11.1.  Renders whose workspace exceeds 24 GiB keep two slots and full-width launches
     // (4 x 24 GiB of workspaces is where this stops).
-    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, env_mis_render(c)) > ((size_t)24 << 30);
+    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, env_mis_render(c), light_render_bound(c)) > ((size_t)24 << 30);
     // ... six where the slots' streams have six hardware queues to themselves (six_queues_probe), four otherwise
     const bool may_queue = tuning().pipelining && !blocking && !counted;
     const int slots = forced_slots ? forced_slots : (huge ? 2 : ((may_queue && dev.six_queues(c)) ? 6 : 4));
@@ -1034,6 +1056,130 @@ const EnvSampDev* env_sampling_of(jpt_ctx* c)
     return &c->env_samp_view;
 }
 
+// The scene changed: the emitter tables are rebuilt at the next render that samples them -- and the emitter list too when the
+// instances or materials may have changed (`listed`); a refit or a mesh update moves the geometry only.  Costs nothing else.
+void lights_stale(jpt_ctx* c, bool listed)
+{
+    c->light_table_stale = true;
+    if (listed) c->light_cand_stale = true;
+}
+
+// The emitters of c->ref, instance-major, each instance's triangles (the leaves under its BLAS root, each triangle once) in
+// ascending index: those whose Le (light_emission) has lum(Le) > 0.  True when there is one.
+bool light_candidates(jpt_ctx* c)
+{
+    if (!c->light_cand_stale) return !c->light_cand_h.empty();
+    const RefScene& r = c->ref;
+    c->light_cand_h.clear();
+    c->light_cand_stale = false;
+    c->light_cand_uploaded = false;
+    if (r.materials.empty()) return false;
+    std::vector<uint32_t> tris, stack;
+    std::vector<char> emits(r.materials.size(), 0);
+    bool any = false;
+    for (size_t m = 0; m < r.materials.size(); m++) {   // (a scene none of whose materials emits has no emitter: no walk)
+        const Vec4& e = r.materials[m].emission;
+        const float em = e.w > 0.0f ? e.w : 0.0f;
+        emits[m] = light_lum(e.x * em, e.y * em, e.z * em) > 0.0f;
+        any = any || emits[m];
+    }
+    if (!any) return false;
+    const uint32_t n_inst = (uint32_t)r.instances.size(), n_nodes = (uint32_t)r.bvh_nodes.size();
+    uint32_t cached_root = 0xffffffffu;
+    for (uint32_t i = 0; i < n_inst; i++) {
+        const uint32_t root = r.instances[i].blas_index;
+        if (root != cached_root) {
+            tris.clear();
+            stack.assign(1, root);
+            size_t visits = 0;
+            while (!stack.empty() && visits++ <= n_nodes) {
+                const uint32_t k = stack.back();
+                stack.pop_back();
+                if (k >= n_nodes) continue;
+                const RefBvhNode& nd = r.bvh_nodes[k];
+                if (nd.tri_count > 0) {
+                    for (uint32_t t = 0; t < nd.tri_count; t++)
+                        if ((size_t)nd.first_tri_index + t < r.tri_data.size()) tris.push_back(nd.first_tri_index + t);
+                } else {
+                    stack.push_back(nd.right_child);
+                    stack.push_back(nd.left_child);
+                }
+            }
+            std::sort(tris.begin(), tris.end());
+            tris.erase(std::unique(tris.begin(), tris.end()), tris.end());
+            cached_root = root;
+        }
+        for (const uint32_t t : tris) {
+            float le[3];
+            light_emission(r.instances.data(), n_inst, r.materials.data(), (uint32_t)r.materials.size(), i, r.tri_data[t].material_index, le);
+            if (light_lum(le[0], le[1], le[2]) > 0.0f) {
+                c->light_cand_h.push_back(i);
+                c->light_cand_h.push_back(t);
+            }
+        }
+    }
+    return !c->light_cand_h.empty();
+}
+
+// does a render of `c` now take the light-sampling kernels (and their workspace)?
+bool light_render(jpt_ctx* c)
+{
+    return c->light_sampling == JPT_LIGHT_SAMPLING_MIS && !c->debug_steps && c->device >= 0 && c->scene_ready && light_candidates(c);
+}
+
+// The emitter tables, built on the context's stream when stale: after every render queued so far (each ends with work there), so
+// no render in flight reads them while they change; the next render of every slot waits for the context's stream.
+int ensure_light_tables(jpt_ctx* c)
+{
+    if (!c->light_table_stale && c->light_cand_uploaded) return JPT_OK;
+    hipStream_t s = c->stream;
+    const uint32_t n = (uint32_t)(c->light_cand_h.size() / 2), nb = (n + kLightBlock - 1) / kLightBlock;
+    if (c->d_light_tri.n != 3 * (size_t)n || c->d_light_marg.n != (size_t)nb + 1 || !c->light_cand_uploaded)
+        HIP_TRY(c, hipStreamSynchronize(s));   // (buffers of another size: renders in flight may read the old ones)
+    if (!c->light_cand_uploaded) {
+        HIP_TRY(c, c->d_light_cand.upload(c->light_cand_h, s));
+        c->light_cand_uploaded = true;
+    }
+    HIP_TRY(c, c->d_light_tri.resize(3 * (size_t)n));
+    HIP_TRY(c, c->d_light_cdf.resize(n));
+    HIP_TRY(c, c->d_light_marg.resize((size_t)nb + 1));
+    LightBuildArgs a;
+    a.cand = c->d_light_cand.p;
+    a.n = n;
+    a.n_blocks = nb;
+    a.instances = c->ds.ref_instances;
+    a.n_instances = c->ds.n_instances;
+    a.n_materials = c->ds.n_materials;
+    a.materials = c->ds.ref_materials;
+    a.wtris = c->ds.wide_tris;
+    a.shade = c->ds.shade_tris;
+    a.tri = c->d_light_tri.p;
+    a.cdf = c->d_light_cdf.p;
+    a.marg = c->d_light_marg.p;
+    launch_light_tables(s, a);
+    HIP_TRY(c, hipGetLastError());
+    for (PipeSlot& ps : c->slot) ps.acc_done_valid = false;
+    c->light_table_stale = false;
+    return JPT_OK;
+}
+
+// the emitter tables the renders of `c` take, or null (BRDF sampling alone); made if stale.  A view, valid until the next call.
+const LightDev* lights_of(jpt_ctx* c, int& rc)
+{
+    rc = JPT_OK;
+    if (!light_render(c)) return nullptr;
+    rc = ensure_light_tables(c);
+    if (rc != JPT_OK) return nullptr;
+    LightDev& v = c->light_view;
+    v.tri = c->d_light_tri.p;
+    v.cdf = c->d_light_cdf.p;
+    v.marg = c->d_light_marg.p;
+    v.wtris = c->ds.wide_tris;
+    v.n = (uint32_t)(c->light_cand_h.size() / 2);
+    v.n_blocks = (v.n + kLightBlock - 1) / kLightBlock;
+    return &v;
+}
+
 // the environment map the renders of `c` see, or null (sample_sky); a view of the context's own copy, valid until the next call
 const EnvDev* environment_of(jpt_ctx* c)
 {
@@ -1053,6 +1199,9 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
 {
     hipStream_t s = c->stream;
     const int32_t n_frames = fp.n_frames;
+    int lrc = JPT_OK;
+    r.lights = lights_of(c, lrc);   // (the emitter tables, made here if stale: on `s`, before the render)
+    if (lrc != JPT_OK) return lrc;
     if (c->denoise == JPT_DENOISE_TEMPORAL) {
         // the pass runs once per displayed frame and reads other pixels' depth and history (temporal_reprojection.glsl:57-61)
         if (n_frames > 1) return fail(c, JPT_E_INVALID, "temporal reprojection renders one frame per call");
@@ -1077,7 +1226,7 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     if (counted) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(DevCounters), s));
     const bool wf2 = wavefront && c->local_rows > 0 && c->width > 0 && n_frames > 0;
     if (wf2) {
-        const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces, env_mis_render(c));
+        const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces, env_mis_render(c), r.lights != nullptr);
         if (c->slot[0].workspace.n < need) {
             HIP_TRY(c, hipStreamSynchronize(s));
             HIP_TRY(c, c->slot[0].workspace.resize(need));
@@ -1133,7 +1282,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.n_frames = 1;
             one.depth_frame = 0;
             launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, c->debug_steps ? nullptr : environment_of(c),
-                             c->debug_steps ? nullptr : env_sampling_of(c));
+                             c->debug_steps ? nullptr : env_sampling_of(c), c->debug_steps ? nullptr : r.lights);
         }
         return JPT_OK;
     }
@@ -1144,7 +1293,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
     }
     // a queued render: path kernels and accumulation on the slot's stream with the slot's workspace
     PipeSlot& ps = c->slot[p.slot];
-    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, r.env_samp != nullptr);
+    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, r.env_samp != nullptr, r.lights != nullptr);
     bool slots_ready = true;
     for (int k = 0; k < p.slots; k++) slots_ready = slots_ready && c->slot[k].stream && c->slot[k].workspace.n >= need;
     if (!slots_ready) {
@@ -1689,6 +1838,7 @@ namespace {
 // instances / TLAS of c->ref changed (BLASes did not): re-flatten that part and upload it
 int upload_tlas_update(jpt_ctx* c)
 {
+    lights_stale(c, true);
     std::string err;
     const bool use4 = walks_nodes4(c);
     if (!reflatten_tlas(c->ref, c->wide, use4, err)) return fail(c, JPT_E_INVALID, "tlas update: " + err);
@@ -1738,6 +1888,7 @@ int ensure_refit_stream(jpt_ctx* c)
 // from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
 int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances)
 {
+    lights_stale(c, false);
     hipStream_t s = c->stream;
     SceneBufs& b = c->dev;
     if (!c->set_b_ready) {
@@ -2050,6 +2201,106 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     return JPT_OK;
 }
 
+// the emitter tables for the jpt_debug_light_* entries, whatever the mode: made if stale; null when the scene has no emitter
+static int debug_lights(jpt_ctx* c, const LightDev*& out)
+{
+    out = nullptr;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the emitter tables are on the device");
+    if (!c->scene_ready) return fail(c, JPT_E_STATE, "no scene");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!light_candidates(c)) return JPT_OK;
+    const int32_t mode = c->light_sampling;
+    const bool dbg = c->debug_steps;
+    c->light_sampling = JPT_LIGHT_SAMPLING_MIS;
+    c->debug_steps = false;
+    int rc = JPT_OK;
+    out = lights_of(c, rc);
+    c->light_sampling = mode;
+    c->debug_steps = dbg;
+    if (rc == JPT_OK) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return rc;
+}
+
+int jpt_debug_light_tables(jpt_ctx* c, uint32_t capacity, uint32_t* n_out, uint32_t* pairs_out, float* tri_out, float* cdf_out, float* marg_out)
+{
+    if (!c || !n_out) return JPT_E_INVALID;
+    const LightDev* lt = nullptr;
+    const int rc = debug_lights(c, lt);
+    if (rc != JPT_OK) return rc;
+    n_out[0] = lt ? lt->n : 0u;
+    n_out[1] = lt ? lt->n_blocks : 0u;
+    if (!lt || capacity < lt->n) return JPT_OK;
+    if (pairs_out) std::memcpy(pairs_out, c->light_cand_h.data(), (size_t)lt->n * 2 * sizeof(uint32_t));
+    if (tri_out) HIP_TRY(c, hipMemcpy(tri_out, lt->tri, (size_t)lt->n * 3 * sizeof(float4), hipMemcpyDeviceToHost));
+    if (cdf_out) HIP_TRY(c, hipMemcpy(cdf_out, lt->cdf, (size_t)lt->n * sizeof(float), hipMemcpyDeviceToHost));
+    if (marg_out) HIP_TRY(c, hipMemcpy(marg_out, lt->marg, ((size_t)lt->n_blocks + 1) * sizeof(float), hipMemcpyDeviceToHost));
+    return JPT_OK;
+}
+
+static int light_probe_call(jpt_ctx* c, int what, const float* xi4, const uint32_t* inst, const uint32_t* tri, const float* points3,
+                            const float* origins3, const float* dirs3, uint32_t n, float* points_out, float* dirs_out, float* pdf_out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (n && (!origins3 || !pdf_out || (what == 1 && (!xi4 || !points_out || !dirs_out)) || (what == 2 && (!inst || !tri || !points3 || !dirs3))))
+        return fail(c, JPT_E_INVALID, "null argument");
+    const LightDev* lt = nullptr;
+    const int rc = debug_lights(c, lt);
+    if (rc != JPT_OK) return rc;
+    if (n == 0) return JPT_OK;
+    if (!lt) {   // no emitter: density 0 (and no sample)
+        for (uint32_t i = 0; i < n; i++) pdf_out[i] = 0.0f;
+        if (what == 1) {
+            std::memset(points_out, 0, (size_t)n * 3 * sizeof(float));
+            std::memset(dirs_out, 0, (size_t)n * 3 * sizeof(float));
+        }
+        return JPT_OK;
+    }
+    if (what == 2)
+        for (uint32_t i = 0; i < n; i++)
+            if (inst[i] >= c->ds.n_instances || tri[i] >= c->ds.n_tris) return fail(c, JPT_E_INVALID, "no such instance or triangle");
+    const size_t n3 = (size_t)n * 3;
+    DevBuf<float> d_in, d_o, d_d, d_p, d_po, d_do, d_pdf;
+    DevBuf<uint32_t> d_inst, d_tri;
+    HIP_TRY(c, d_o.resize(n3));
+    HIP_TRY(c, d_pdf.resize(n));
+    HIP_TRY(c, hipMemcpy(d_o.p, origins3, n3 * sizeof(float), hipMemcpyHostToDevice));
+    if (what == 1) {
+        HIP_TRY(c, d_in.resize((size_t)n * 4));
+        HIP_TRY(c, d_po.resize(n3));
+        HIP_TRY(c, d_do.resize(n3));
+        HIP_TRY(c, hipMemcpy(d_in.p, xi4, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        HIP_TRY(c, d_d.resize(n3));
+        HIP_TRY(c, d_p.resize(n3));
+        HIP_TRY(c, d_inst.resize(n));
+        HIP_TRY(c, d_tri.resize(n));
+        HIP_TRY(c, hipMemcpy(d_d.p, dirs3, n3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(d_p.p, points3, n3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(d_inst.p, inst, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(d_tri.p, tri, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    launch_light_probe(c->stream, *lt, c->ds.shading(), what, d_in.p, d_o.p, d_d.p, d_p.p, d_inst.p, d_tri.p, n, d_po.p, d_do.p, d_pdf.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(pdf_out, d_pdf.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    if (what == 1) {
+        HIP_TRY(c, hipMemcpy(points_out, d_po.p, n3 * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(dirs_out, d_do.p, n3 * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    return JPT_OK;
+}
+
+int jpt_debug_light_sample(jpt_ctx* c, const float* xi4, const float* origins3, uint32_t n, float* points_out, float* dirs_out, float* pdf_out)
+{
+    return light_probe_call(c, 1, xi4, nullptr, nullptr, nullptr, origins3, nullptr, n, points_out, dirs_out, pdf_out);
+}
+
+int jpt_debug_light_pdf(jpt_ctx* c, const uint32_t* inst, const uint32_t* tri, const float* points3, const float* origins3, const float* dirs3,
+                        uint32_t n, float* pdf_out)
+{
+    return light_probe_call(c, 2, nullptr, inst, tri, points3, origins3, dirs3, n, nullptr, nullptr, pdf_out);
+}
+
 int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void* nodesq_out, uint32_t node_capacity, void* tris_out,
                            void* shade_out, uint32_t tri_capacity, int32_t* info_out)
 {
@@ -2324,6 +2575,15 @@ int jpt_set_environment_sampling(jpt_ctx* c, int32_t mode)
         HIP_TRY(c, hipSetDevice(c->device));
         return build_env_tables(c);
     }
+    return JPT_OK;
+}
+
+int jpt_set_light_sampling(jpt_ctx* c, int32_t mode)
+{
+    if (!c) return JPT_E_INVALID;
+    if (mode != JPT_LIGHT_SAMPLING_BRDF && mode != JPT_LIGHT_SAMPLING_MIS) return fail(c, JPT_E_INVALID, "jpt_set_light_sampling: unknown mode");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: light sampling runs on the device");
+    c->light_sampling = mode;   // (the tables are made at the first render that samples them)
     return JPT_OK;
 }
 

@@ -119,6 +119,58 @@ __global__ void env_lookup_probe(EnvDev env, const float* __restrict__ dirs3, ui
     rgb_out[3 * (size_t)i + 2] = c.z;
 }
 
+}  // namespace
+
+// jpt_debug_light_sample / jpt_debug_light_pdf (entry points in jpt_capi.cpp, which owns the context): the emitter sampler and
+// density the light-sampling kernels inline (light_sample / light_cos / light_pdf, jpt_shade.h), one item per thread
+__global__ void light_probe(LightDev lt, SceneShading sh, int what, const float* __restrict__ xi4, const float* __restrict__ origins,
+                            const float* __restrict__ dirs, const float* __restrict__ points, const uint32_t* __restrict__ inst,
+                            const uint32_t* __restrict__ tri, uint32_t n, float* __restrict__ points_out, float* __restrict__ dirs_out,
+                            float* __restrict__ pdf_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float total = lt.marg[lt.n_blocks];
+    const f3 o = mk3(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2]);
+    if (what == 1) {
+        const LightSample ls = light_sample(lt, xi4[4 * (size_t)i], xi4[4 * (size_t)i + 1], xi4[4 * (size_t)i + 2], xi4[4 * (size_t)i + 3]);
+        const f3 dv = ls.y - o;
+        const float d2 = dot3(dv, dv);
+        const f3 l = normalize3(dv);
+        const float c = light_cos(ls.e1, ls.e2, l);
+        points_out[3 * (size_t)i] = ls.y.x;
+        points_out[3 * (size_t)i + 1] = ls.y.y;
+        points_out[3 * (size_t)i + 2] = ls.y.z;
+        dirs_out[3 * (size_t)i] = l.x;
+        dirs_out[3 * (size_t)i + 1] = l.y;
+        dirs_out[3 * (size_t)i + 2] = l.z;
+        pdf_out[i] = (c > 0.0f && total > 0.0f) ? light_pdf(ls.le, total, d2, c) : 0.0f;
+    } else {
+        float le[3];
+        light_emission(sh.instances, sh.n_instances, sh.materials, sh.n_materials, inst[i], sh.tri_data[tri[i]].material_index, le);
+        const WideTri& w = lt.wtris[tri[i]];
+        const RefInstance& b = sh.instances[inst[i]];
+        const f3 e1 = xform_dir(b.transform, mk3(w.e1[0], w.e1[1], w.e1[2])), e2 = xform_dir(b.transform, mk3(w.e2[0], w.e2[1], w.e2[2]));
+        const f3 dv = mk3(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]) - o;
+        const f3 d = mk3(dirs[3 * (size_t)i], dirs[3 * (size_t)i + 1], dirs[3 * (size_t)i + 2]);
+        const bool emits = light_lum(le[0], le[1], le[2]) > 0.0f && total > 0.0f;
+        pdf_out[i] = emits ? light_pdf(mk3(le[0], le[1], le[2]), total, dot3(dv, dv), light_cos(e1, e2, d)) : 0.0f;
+    }
+}
+
+namespace jpt {
+void launch_light_probe(hipStream_t stream, const LightDev& lt, const SceneShading& sh, int what, const float* xi4, const float* origins,
+                        const float* dirs, const float* points, const uint32_t* inst, const uint32_t* tri, uint32_t n, float* points_out,
+                        float* dirs_out, float* pdf_out)
+{
+    if (n == 0) return;
+    hipLaunchKernelGGL(light_probe, dim3((n + 63u) / 64u), dim3(64), 0, stream, lt, sh, what, xi4, origins, dirs, points, inst, tri, n,
+                       points_out, dirs_out, pdf_out);
+}
+}  // namespace jpt
+
+namespace {
+
 // jpt_debug_env_sample / jpt_debug_env_pdf: the sampler the MIS kernels inline (env_sample / env_pdf, jpt_shade.h), one item per thread
 __global__ void env_sample_probe(EnvDev env, EnvSampDev es, const float* __restrict__ in, uint32_t n, int sample, float* __restrict__ dirs_out,
                                  float* __restrict__ pdf_out)

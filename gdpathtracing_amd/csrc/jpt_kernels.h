@@ -210,7 +210,28 @@ bool env_rotation_orthonormal(const float* rotation9);
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
                       uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env = nullptr,
-                      const EnvSampDev* env_samp = nullptr);
+                      const EnvSampDev* env_samp = nullptr, const LightDev* lights = nullptr);
+
+// The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
+// tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory
+struct LightBuildArgs {
+    const uint32_t* cand;
+    uint32_t n, n_blocks;
+    const RefInstance* instances;
+    uint32_t n_instances, n_materials;
+    const RefMaterial* materials;
+    const WideTri* wtris;
+    const ShadeTri* shade;
+    float4* tri;
+    float* cdf;
+    float* marg;
+};
+void launch_light_tables(hipStream_t stream, const LightBuildArgs& a);
+// the audit probe of jpt_debug_light_sample (what 1: xi4, origins) / jpt_debug_light_pdf (what 2: inst, tri, points, origins,
+// dirs), device pointers, on `stream` (jpt_debug.hip)
+void launch_light_probe(hipStream_t stream, const LightDev& lt, const SceneShading& sh, int what, const float* xi4, const float* origins,
+                        const float* dirs, const float* points, const uint32_t* inst, const uint32_t* tri, uint32_t n, float* points_out,
+                        float* dirs_out, float* pdf_out);
 
 // The persistent-block pipeline (jpt_kernels_wf2.hip): one render of fp.n_frames frames over the flattened layout;
 // fp.frame_index / fp.frame_count are those of the FIRST frame.  The first (max_bounces + 2) *
@@ -224,7 +245,8 @@ void launch_sky_tiles(hipStream_t stream, const FrameParams& fp, const RefCamera
 uint32_t wf2_segments();
 uint32_t trace_stack_capacity();  // entries a lane's traversal stack can hold (LDS + scratch)
 // bytes of the workspace a render of this size carves (wf2_layout), for any frame-group count and window
-size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis = false);   // mis: + the shadow queues (Wf2Nee)
+size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis = false,
+                           bool lights = false);   // mis: + the map's shadow queues (Wf2Nee); lights: + the emitters' queues
 // Screen rectangles (pixels, inclusive) of the boxes the TLAS root offers a ray; a primary ray through a pixel
 // outside all of them is known to fail all of the root's box tests, i.e. to reach the sky after exactly one TLAS
 // expansion, without being traced.  n < 0: unknown, trace everything.  Filled on the host (jpt_capi.cpp).
@@ -247,6 +269,8 @@ struct Wf2Render {
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
     const EnvSampDev* env_samp = nullptr;  // with `env`: its sampling tables (JPT_ENV_SAMPLING_MIS, a map of non-zero weight): the *_mis
                                            // kernels and wf2_occlude, and the workspace's MIS buffers
+    const LightDev* lights = nullptr;      // the emitter tables (JPT_LIGHT_SAMPLING_MIS, a scene with emitters): the *_lt kernels,
+                                           // wf2_occlude_lt and the workspace's light queues, whatever the miss model
     const EnvDev* env = nullptr;           // the environment map the misses see (jpt_set_environment); null: sample_sky.  The
                                            // launches then take the *_env kernels, and the accumulation uses no sky cells
 };

@@ -225,4 +225,46 @@ void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int3
     hipLaunchKernelGGL(env_marginal_kernel, dim3(1), dim3(64), 0, stream, marg, h, total);
 }
 
+// ---- the emitter tables (jpt_set_light_sampling): light_emission / env_build_marginal, jpt_shade.h ------------------------------
+// One thread per emitter: world vertex 0 and edges (xform_point / xform_dir of the triangle record's v0, e1, e2 with the
+// instance's transform), Le, and the power lum(Le) * 0.5 |E1 x E2| (0 unless finite and > 0) into cdf; then one thread per
+// block of kLightBlock for its sequential sums, then one thread for the marginal -- the same bits on every run and device.
+__global__ __launch_bounds__(256) void light_entries_kernel(LightBuildArgs a)
+{
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= a.n) return;
+    const uint32_t inst = a.cand[2 * (size_t)k], tri = a.cand[2 * (size_t)k + 1];
+    const RefInstance& b = a.instances[inst];
+    const WideTri w = a.wtris[tri];
+    float le[3];
+    light_emission(a.instances, a.n_instances, a.materials, a.n_materials, inst, a.shade[tri].material_index, le);
+    const f3 p0 = xform_point(b.transform, mk3(w.v0[0], w.v0[1], w.v0[2]));
+    const f3 e1 = xform_dir(b.transform, mk3(w.e1[0], w.e1[1], w.e1[2])), e2 = xform_dir(b.transform, mk3(w.e2[0], w.e2[1], w.e2[2]));
+    const float area = 0.5f * length3(cross3(e1, e2));
+    float power = light_lum(le[0], le[1], le[2]) * area;
+    if (!(power > 0.0f) || !(power <= 3.40282347e38f)) power = 0.0f;
+    a.tri[3 * (size_t)k] = make_float4(p0.x, p0.y, p0.z, le[0]);
+    a.tri[3 * (size_t)k + 1] = make_float4(e1.x, e1.y, e1.z, le[1]);
+    a.tri[3 * (size_t)k + 2] = make_float4(e2.x, e2.y, e2.z, le[2]);
+    a.cdf[k] = power;
+}
+__global__ __launch_bounds__(64) void light_blocks_kernel(LightBuildArgs a)
+{
+    const uint32_t b = blockIdx.x * 64u + threadIdx.x;
+    if (b >= a.n_blocks) return;
+    const uint32_t first = b * kLightBlock, cnt = a.n - first < kLightBlock ? a.n - first : kLightBlock;
+    a.marg[b] = env_build_marginal(a.cdf + first, (int32_t)cnt);
+}
+__global__ __launch_bounds__(64) void light_marginal_kernel(LightBuildArgs a)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) a.marg[a.n_blocks] = env_build_marginal(a.marg, (int32_t)a.n_blocks);
+}
+void launch_light_tables(hipStream_t stream, const LightBuildArgs& a)
+{
+    if (a.n == 0) return;
+    hipLaunchKernelGGL(light_entries_kernel, dim3((a.n + 255u) / 256u), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(light_blocks_kernel, dim3((a.n_blocks + 63u) / 64u), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(light_marginal_kernel, dim3(1), dim3(64), 0, stream, a);
+}
+
 }  // namespace jpt

@@ -198,9 +198,13 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 #define JPT_ENV 2
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
+#define JPT_ENV 3
+#include "jpt_ref_frame.h"
+#undef JPT_ENV
 
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env, const EnvSampDev* env_samp)
+                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env, const EnvSampDev* env_samp,
+                      const LightDev* lights)
 {
     RefSceneDev sc;
     sc.tri_geom = ds.ref_tri_geom;
@@ -215,7 +219,13 @@ void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FramePara
     dim3 grid((fp.width + 31) / 32, (fp.local_rows + 7) / 8), block(256);
     const bool ties = ds.x.ok && ds.reach_tri != nullptr && !fp.debug_steps;
     with_consts<2, 2>([&](auto C, auto TIES) {
-        if (env && env_samp)
+        if (lights) {
+            const EnvDev e0 = env ? *env : EnvDev{};
+            const EnvSampDev s0 = (env && env_samp) ? *env_samp : EnvSampDev{};
+            const int env_mode = env ? (env_samp ? 2 : 1) : 0;
+            hipLaunchKernelGGL((ref_frame_kernel_lt<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, e0, s0, *lights,
+                               env_mode);
+        } else if (env && env_samp)
             hipLaunchKernelGGL((ref_frame_kernel_mis<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, *env, *env_samp);
         else if (env)
             hipLaunchKernelGGL((ref_frame_kernel_env<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, *env);

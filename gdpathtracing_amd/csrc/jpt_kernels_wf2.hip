@@ -664,7 +664,34 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude(WideSceneDev sc, Wf2Buf
     if (COUNT) flush_counters(cnt, counters);
 }
 
-// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, the *_env ones, then the *_mis ones
+// The emitters' shadow rays (JPT_LIGHT_SAMPLING_MIS) that wf2_shade_lt queued at `bounce`: wf2_occlude's walk, started with
+// hit.t = tmax (the entry's direction w), so boxes and triangles beyond it are pruned: "blocked" when some triangle's
+// Moller-Trumbore test accepts t < tmax (the walk ends with hit.t < tmax).  Runs after that bounce's wf2_occlude (the map's shadow
+// rays of the same vertices): two rays of one vertex never share a launch.
+template <bool COUNT, bool W4>
+__global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, int bounce, Wf2Nee nee,
+                                                            DevCounters* __restrict__ counters)
+{
+    constexpr int kDepth = kStackLds + kStackSpill;
+    __shared__ int32_t stack[kDepth * kOccBlock];
+    const uint32_t seg = blockIdx.y;
+    const uint32_t i = blockIdx.x * kOccBlock + threadIdx.x;
+    if (i >= nee.scount[(size_t)bounce * kSegments + seg]) return;
+    const size_t at = (size_t)seg * dm.seg_cap + i;
+    const float4 so = stream_ld4(&nee.sh_o[at]), sd = stream_ld4(&nee.sh_d[at]), sc4 = stream_ld4(&nee.sh_c[at]);
+    const typename Traversal<COUNT, W4>::Stack st{&stack[threadIdx.x], nullptr, kOccBlock, kDepth, 0};
+    DevCounters cnt = {};
+    Traversal<COUNT, W4> tr;
+    tr.begin(sc, mk3(so.x, so.y, so.z), mk3(sd.x, sd.y, sd.z));
+    const float tmax = sd.w;
+    tr.hit.t = tmax;
+    while (tr.hit.t >= tmax && tr.step(sc, st, cnt)) {
+    }
+    nee_land(wb, fp.accum_mode, so, sc4, tr.hit.t < tmax);
+    if (COUNT) flush_counters(cnt, counters);
+}
+
+// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, the *_env ones, the *_mis ones, then the *_lt ones
 #define JPT_ENV 0
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
@@ -672,6 +699,9 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude(WideSceneDev sc, Wf2Buf
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #define JPT_ENV 2
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 3
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 
@@ -784,9 +814,10 @@ struct Wf2Layout {
     uint32_t* fin8;
     float* first_depth;
     Wf2Nee gnee[kMaxGroups];   // (MIS renders only: carved behind everything else, so the other buffers stay where they are)
+    Wf2Nee glnee[kMaxGroups];  // (light-sampling renders only: behind those; pdf shared with gnee when both are carved)
     size_t bytes = 0;     // the end of the last buffer
 };
-static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window, bool mis = false)
+static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window, bool mis = false, bool lights = false)
 {
     Wf2Layout L;
     auto carve = [&](size_t bytes) {
@@ -841,10 +872,23 @@ static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const
         ne.scount = (uint32_t*)carve((size_t)(fp.max_bounces > 0 ? fp.max_bounces : 1) * kSegments * sizeof(uint32_t));
         ne.pdf = (float*)carve(paths * sizeof(float));
     }
+    for (int g = 0; g < groups && lights; g++) {
+        int f0, nf;
+        group_frames(fp.n_frames, groups, g, f0, nf);
+        const size_t q = (size_t)L.gdm[g].seg_cap * kSegments;
+        const size_t paths = (size_t)L.gdm[g].slots_per_frame * (size_t)nf;
+        Wf2Nee& ne = L.glnee[g];
+        ne.sh_o = (float4*)carve(q * sizeof(float4));
+        ne.sh_d = (float4*)carve(q * sizeof(float4));
+        ne.sh_c = (float4*)carve(q * sizeof(float4));
+        ne.scount = (uint32_t*)carve((size_t)(fp.max_bounces > 0 ? fp.max_bounces : 1) * kSegments * sizeof(uint32_t));
+        ne.pdf = mis ? L.gnee[g].pdf : (float*)carve(paths * sizeof(float));
+        if (!mis) L.gnee[g] = Wf2Nee{nullptr, nullptr, nullptr, nullptr, ne.pdf};
+    }
     return L;
 }
 
-size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis)
+size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis, bool lights)
 {
     // every layout a render of this size may use: the largest of 1..kMaxGroups groups over the whole image
     FrameParams fp{};
@@ -854,7 +898,7 @@ size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_boun
     fp.max_bounces = max_bounces;
     size_t worst = 0;
     for (int groups = 1; groups <= kMaxGroups && groups <= (n_frames < 1 ? 1 : n_frames); groups++)
-        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows), mis).bytes);
+        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows), mis, lights).bytes);
     return worst;
 }
 
@@ -874,7 +918,11 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     const Wf2Dims dm_all = make_dims(fp.width, fp.local_rows, fp.n_frames, window);
     if (dm_all.n_chunks == 0) return;
     const EnvSampDev* es = r.env ? r.env_samp : nullptr;   // the MIS kernels (jpt_wf2_paths.h, JPT_ENV 2)
-    const Wf2Layout L = wf2_layout(workspace, fp, groups, window, es != nullptr);
+    const LightDev* lt = r.lights;   // the light-sampling kernels (jpt_wf2_paths.h, JPT_ENV 3), whatever the miss model
+    const Wf2Layout L = wf2_layout(workspace, fp, groups, window, es != nullptr, lt != nullptr);
+    const EnvDev env0 = r.env ? *r.env : EnvDev{};
+    const EnvSampDev es0 = es ? *es : EnvSampDev{};
+    const int env_mode = r.env ? (es ? 2 : 1) : 0;
     const int nq = fp.max_bounces + 2;
 
     const bool w4 = ds.use4;
@@ -909,7 +957,8 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     const int finish_walk = !w4 ? 0 : (sx.ok ? 2 : 1);
     const EnvDev* env = r.env;   // an environment map: the *_env kernels (jpt_wf2_paths.h)
     // the pipeline of one group on one stream
-    auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, const Wf2Nee& nee, hipEvent_t* ev) {
+    auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, const Wf2Nee& nee, const Wf2Nee& lnee,
+                         hipEvent_t* ev) {
         // (the queue sizes of bounces >= 1 and the set-aside counts start from zero: wf2_primary clears them)
         // Blocks go to the 8 XCDs round-robin by linear index (y * grid.x + x), and the chunks of a segment are far from
         // alike (the first ones are full, the last ones empty): with grid.x a multiple of 8 every XCD would always get
@@ -917,6 +966,7 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         // cost 9 %).
         const dim3 sgrid(((dm.seg_cap + kBlock - 1) / kBlock) | 1u, kSegments);
         if (es && gp.max_bounces > 0) (void)hipMemsetAsync(nee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
+        if (lt && gp.max_bounces > 0) (void)hipMemsetAsync(lnee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
         if (ev) (void)hipEventRecord(ev[0], st);
         with_consts<2, 3>([&](auto C, auto W) {
             if (env)
@@ -927,7 +977,10 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {
             with_consts<2, 2, 3>([&](auto C, auto LAST, auto TEX) {
-                if (es)
+                if (lt)
+                    hipLaunchKernelGGL((wf2_shade_lt<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, env0, es0, *lt, nee, lnee,
+                                       env_mode);
+                else if (es)
                     hipLaunchKernelGGL((wf2_shade_mis<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env, *es, nee);
                 else if (env)
                     hipLaunchKernelGGL((wf2_shade_env<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env);
@@ -941,6 +994,12 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
                     hipLaunchKernelGGL((wf2_occlude<C, W != 0>), ogrid, dim3(kOccBlock), 0, st, sc, wb, dm, gp, b, nee, counters);
                 }, count, walk);
             }
+            if (lt) {   // (after the map's: the emitters' shadow ray of a vertex lands second)
+                const dim3 ogrid(((dm.seg_cap + kOccBlock - 1) / kOccBlock) | 1u, kSegments);
+                with_consts<2, 3>([&](auto C, auto W) {
+                    hipLaunchKernelGGL((wf2_occlude_lt<C, W != 0>), ogrid, dim3(kOccBlock), 0, st, sc, wb, dm, gp, b, lnee, counters);
+                }, count, walk);
+            }
             if (ev) (void)hipEventRecord(ev[2 * (b + 1)], st);
             with_consts<2, 3>([&](auto C, auto W) {
                 hipLaunchKernelGGL((wf2_trace<C, W != 0, W == 2>), tgrid, block, 0, st, sc, wb, dm, b + 1, tune, chain, counters);
@@ -950,7 +1009,10 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (sh.reach_tri) {  // the paths set aside because their hit is undecidable on the native tree: finished exactly
             const dim3 rgrid(256), rblock(64);   // (blocks past the set-aside count exit at once; more records than threads: grid-stride)
             with_consts<2, 3>([&](auto C, auto W) {
-                if (es)
+                if (lt)
+                    hipLaunchKernelGGL((wf2_finish_lt<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, env0, es0, *lt, nee,
+                                       lnee, env_mode);
+                else if (es)
                     hipLaunchKernelGGL((wf2_finish_mis<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env, *es, nee);
                 else if (env)
                     hipLaunchKernelGGL((wf2_finish_env<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env);
@@ -961,14 +1023,14 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     };
 
     if (groups == 1) {
-        run_group(stream, L.gb[0], L.gdm[0], L.gfp[0], L.gnee[0], trace_events);
+        run_group(stream, L.gb[0], L.gdm[0], L.gfp[0], L.gnee[0], L.glnee[0], trace_events);
     } else {
         // fork: the helper streams start after everything already queued on the context's stream
         (void)hipEventRecord(streams.fork, stream);
         for (int g = 1; g < groups; g++) (void)hipStreamWaitEvent(streams.aux_stream[g - 1], streams.fork, 0);
         // issue the groups' launches interleaved, so none of the streams runs ahead of the others on the host side
         // (run_group enqueues a whole pipeline; the hardware queues of the streams drain concurrently)
-        for (int g = 0; g < groups; g++) run_group(g == 0 ? stream : streams.aux_stream[g - 1], L.gb[g], L.gdm[g], L.gfp[g], L.gnee[g], nullptr);
+        for (int g = 0; g < groups; g++) run_group(g == 0 ? stream : streams.aux_stream[g - 1], L.gb[g], L.gdm[g], L.gfp[g], L.gnee[g], L.glnee[g], nullptr);
         // join, then fold the other groups' queue sizes into group 0's (the host reads those for the ray count)
         for (int g = 1; g < groups; g++) {
             (void)hipEventRecord(streams.join[g - 1], streams.aux_stream[g - 1]);

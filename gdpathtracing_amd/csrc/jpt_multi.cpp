@@ -281,6 +281,16 @@ int jpt_multi_set_environment_sampling(jpt_multi* m, int32_t mode)
     return JPT_OK;
 }
 
+int jpt_multi_set_light_sampling(jpt_multi* m, int32_t mode)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_light_sampling(m->ctx[r], mode);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_set_camera(jpt_multi* m, const void* camera160)
 {
     if (!m) return JPT_E_INVALID;

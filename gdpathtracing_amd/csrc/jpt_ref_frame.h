@@ -4,9 +4,17 @@
 //   JPT_ENV 1   ref_frame_kernel_env (jpt_set_environment): one more parameter, the map, and env_radiance at the miss;
 //   JPT_ENV 2   ref_frame_kernel_mis (JPT_ENV_SAMPLING_MIS): also the map's sampling tables; below the last bounce each vertex casts
 //               its map sample's shadow ray at once (ray_trace_tlas on the reference layout: a hit there is "blocked"), and a
-//               miss at bounce >= 1 is weighted against that strategy -- the arithmetic of jpt_wf2_paths.h's *_mis kernels.
+//               miss at bounce >= 1 is weighted against that strategy -- the arithmetic of jpt_wf2_paths.h's *_mis kernels;
+//   JPT_ENV 3   ref_frame_kernel_lt (JPT_LIGHT_SAMPLING_MIS): the emitter tables and the miss model as a run-time value (env_mode
+//               0 gradient, 1 map, 2 map with JPT_ENV_SAMPLING_MIS); each vertex below the last bounce casts the map's shadow ray
+//               (env_mode 2), then the emitters' (ray_trace_tlas with hitInfo.t preset to tmax: blocked when it ends below
+//               tmax), and emission found at bounce >= 1 is weighted -- the arithmetic of jpt_wf2_paths.h's *_lt kernels.
 // (No include guard: that is the point.)
-#if JPT_ENV == 2
+#if JPT_ENV == 3
+#define JPT_ENV_NAME(name) name##_lt
+#define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, LightDev lt, int env_mode
+#define JPT_SKY(d) (env_mode != 0 ? env_radiance(env, d) : sample_sky(d))
+#elif JPT_ENV == 2
 #define JPT_ENV_NAME(name) name##_mis
 #define JPT_ENV_PARAM , EnvDev env, EnvSampDev es
 #define JPT_SKY(d) env_radiance(env, d)
@@ -39,8 +47,11 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
         float depth = cam.far_;
         f3 radiance = mk3(0.0f, 0.0f, 0.0f);
         f3 throughput = mk3(1.0f, 1.0f, 1.0f);
-#if JPT_ENV == 2
+#if JPT_ENV >= 2
         float p_brdf = 0.0f;   // the BRDF density of the current ray's direction (bounces >= 1)
+#endif
+#if JPT_ENV == 3
+        const float ltotal = lt.marg[lt.n_blocks];
 #endif
         if (fp.debug_steps) {   // #ifdef DEBUG_STEPS (main.glsl:358-361, 423-427): the primary ray's triangle tests / 256, depth = far
             RefHit hit;
@@ -56,6 +67,9 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             if (!is_hit) {
 #if JPT_ENV == 2
                 if (i > 0) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, p_brdf);
+                else
+#elif JPT_ENV == 3
+                if (i > 0 && env_mode == 2) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, p_brdf);
                 else
 #endif
                 radiance = radiance + throughput * JPT_SKY(ray.d);
@@ -86,12 +100,20 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             Hit h;
             h.t = hit.t; h.u = hit.u; h.v = hit.v; h.tri = hit.tri; h.inst = hit.inst; h.lo = hit.lo; h.ld = hit.ld;
             const Shading s = get_shading_data(sh, h, hit.front, load_shade_tri(sh, h.tri));
+#if JPT_ENV == 3
+            if (i > 0) radiance = radiance + (throughput * s.emission) * light_hit_weight(lt, ltotal, sh, h, s, ray.o, ray.d, &p_brdf);
+            else
+#endif
             radiance = radiance + throughput * s.emission;
             if (i == 0) depth = length3(s.position - ray.o);
-#if JPT_ENV == 2
+#if JPT_ENV >= 2
             if (i < fp.max_bounces) {
                 f3 l, c;
+#if JPT_ENV == 3
+                if (env_mode == 2 && env_nee(s, env, es, sx, sy, throughput, l, c)) {
+#else
                 if (env_nee(s, env, es, sx, sy, throughput, l, c)) {
+#endif
                     Ray sray;
                     sray.o = s.position + s.normal * 0.001f;
                     sray.d = l;
@@ -100,6 +122,20 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
                     DevCounters none = {};
                     if (!ray_trace_tlas<false>(sc, sray, sh_hit, none)) radiance = radiance + c;
                 }
+#if JPT_ENV == 3
+                f3 lo3, ll, lc;
+                float tmax;
+                if (ltotal > 0.0f && light_nee(s, lt, ltotal, sx, sy, throughput, lo3, ll, tmax, lc)) {
+                    Ray sray;
+                    sray.o = lo3;
+                    sray.d = ll;
+                    sray.rD = rcp3(ll);
+                    RefHit sh_hit;
+                    DevCounters none = {};
+                    (void)ray_trace_tlas<false>(sc, sray, sh_hit, none, nullptr, nullptr, tmax);
+                    if (!(sh_hit.t < tmax)) radiance = radiance + lc;
+                }
+#endif
             }
             if (!bounce_step_pdf(s, sx, sy, ray, throughput, p_brdf)) break;
 #else

@@ -203,6 +203,42 @@ __host__ __device__ __forceinline__ f3 env_sample(const EnvDev& e, const EnvSamp
     return d;
 }
 
+// ---- importance sampling of the emissive triangles (jpt_set_light_sampling, JPT_LIGHT_SAMPLING_MIS) ---------------------------
+//
+// An emitter is an (instance, triangle) pair whose emission Le (get_shading_data's material lookup: emission.rgb * max(0,
+// emission.w)) has luminance lum(Le) = 0.2126 r + 0.7152 g + 0.0722 b > 0; the host lists them (instance-major, triangles in
+// ascending index), the device derives their world geometry and power, lum(Le) * world area, from the arrays the renders read
+// (light_tables_*, jpt_kernels_post.hip).  A power that is not finite and > 0 (zero-area, degenerate) is 0: never drawn.
+// Emitters fall into blocks of kLightBlock; per block a normalised sequential prefix sum (the last entry exactly 1, a block of
+// power 0 all 1s), then the same over the block totals -- env_build_marginal on both levels.
+
+constexpr uint32_t kLightBlock = 256;
+
+struct LightDev {   // the tables of the context's scene, passed by value with every light-sampling render
+    const float4* __restrict__ tri;   // per emitter three entries: (P0, Le.r), (E1, Le.g), (E2, Le.b) -- world vertex 0 and edges
+    const float* __restrict__ cdf;    // per emitter: the conditional CDF of its block
+    const float* __restrict__ marg;   // per block: the marginal CDF; marg[n_blocks] = the total power
+    const WideTri* __restrict__ wtris;   // the scene's triangle records: the hit triangle's edges (light_hit_weight)
+    uint32_t n, n_blocks;
+};
+
+__host__ __device__ __forceinline__ float light_lum(float r, float g, float b) { return 0.2126f * r + 0.7152f * g + 0.0722f * b; }
+
+// Le of triangle slot `slot` of instance `inst`: get_shading_data's lookup (an unchecked slot reads on into the next instance's
+// record, a word past the array is material 0, an out-of-range index is material 0)
+__host__ __device__ __forceinline__ void light_emission(const RefInstance* instances, uint32_t n_instances, const RefMaterial* materials,
+                                                       uint32_t n_materials, uint32_t inst, uint32_t slot, float* le)
+{
+    const unsigned long long word = (unsigned long long)inst * 44ull + 41ull + (unsigned long long)slot;
+    uint32_t mat_id = word < (unsigned long long)n_instances * 44ull ? reinterpret_cast<const uint32_t*>(instances)[word] : 0u;
+    if (mat_id >= n_materials) mat_id = 0;
+    const RefMaterial& m = materials[mat_id];
+    const float em = m.emission.w > 0.0f ? m.emission.w : 0.0f;   // fmax(0, w), NaN -> 0
+    le[0] = m.emission.x * em;
+    le[1] = m.emission.y * em;
+    le[2] = m.emission.z * em;
+}
+
 #if defined(__HIPCC__)   // (everything below is device code; the host layer -- jpt_capi.cpp, jpt_multi.cpp -- sees the structs above only)
 
 // ---- RNG (main.glsl:163-181) -----------------------------------------------------------------
@@ -581,6 +617,85 @@ __device__ __forceinline__ float env_miss_weight(const EnvDev& e, const EnvSampD
     const float pe = env_pdf(e, es, d);
     if (!(pe > 0.0f)) return 1.0f;
     return (p_brdf * p_brdf) / (p_brdf * p_brdf + pe * pe);
+}
+
+// ---- next-event estimation of the emissive triangles (JPT_LIGHT_SAMPLING_MIS) -------------------------------------------------
+//
+// One emitter and a point on it from four randoms: the block by xi0 on the marginal CDF, the emitter by xi1 on its block's
+// conditional CDF (both clamped below 1, first entry > xi), then with s = sqrt(xi2) the point y = (P0 + E1 * (s * (1 - xi3)))
+// + E2 * (s * xi3), uniform on the world triangle.
+struct LightSample {
+    f3 y, e1, e2, le;
+};
+__device__ __forceinline__ LightSample light_sample(const LightDev& lt, float xi0, float xi1, float xi2, float xi3)
+{
+    xi0 = xi0 < 0.99999994f ? xi0 : 0.99999994f;
+    xi1 = xi1 < 0.99999994f ? xi1 : 0.99999994f;
+    const uint32_t b = (uint32_t)env_upper_bound(lt.marg, (int32_t)lt.n_blocks, xi0);
+    const uint32_t first = b * kLightBlock;
+    const uint32_t cnt = lt.n - first < kLightBlock ? lt.n - first : kLightBlock;
+    const uint32_t k = first + (uint32_t)env_upper_bound(lt.cdf + first, (int32_t)cnt, xi1);
+    const float4 q0 = lt.tri[3 * (size_t)k], q1 = lt.tri[3 * (size_t)k + 1], q2 = lt.tri[3 * (size_t)k + 2];
+    LightSample ls;
+    ls.e1 = mk3(q1.x, q1.y, q1.z);
+    ls.e2 = mk3(q2.x, q2.y, q2.z);
+    ls.le = mk3(q0.w, q1.w, q2.w);
+    const float s = __builtin_sqrtf(xi2);
+    ls.y = (mk3(q0.x, q0.y, q0.z) + ls.e1 * (s * (1.0f - xi3))) + ls.e2 * (s * xi3);
+    return ls;
+}
+// |cos| between the emitter's geometric normal normalize(E1 x E2) and l (emission is two-sided)
+__device__ __forceinline__ float light_cos(f3 e1, f3 e2, f3 l) { return __builtin_fabsf(dot3(normalize3(cross3(e1, e2)), l)); }
+// The density per unit solid angle of the point the sampler drew, seen at squared distance d2 under light_cos c:
+//     p_L = (lum(Le) * d2) / (total * c)      (the area cancels: power / total picks the emitter, 1 / area the point)
+__device__ __forceinline__ float light_pdf(f3 le, float total, float d2, float c) { return (light_lum(le.x, le.y, le.z) * d2) / (total * c); }
+
+constexpr float kLightShadowScale = 0.9999f;   // tmax = |y - o| * (1 - 1e-4): the shadow ray stops short of the emitter
+
+// The emitter sample of a path vertex: randoms from a COPY of the vertex's seeds hashed by two pcg2d rounds of (sx ^ 0x2c1b3c6d,
+// sy ^ 0x297a2d39) -- the path's own sequence does not advance.  o = position + normal * 0.001, l = normalize(y - o), d2 =
+// |y - o|^2.  True when a shadow ray (o, l, tmax = sqrt(d2) * kLightShadowScale) is to be cast: n.l > 0, light_cos > 0, and a
+// contribution that is finite with a component > 0:
+//     ((throughput * (brdf_eval(l) * n.l)) * Le) * (w_L / p_L),   w_L = p_L^2 / (p_L^2 + p_brdf(l)^2).
+__device__ __forceinline__ bool light_nee(const Shading& s, const LightDev& lt, float total, uint32_t sx, uint32_t sy, f3 throughput,
+                                          f3& o, f3& l, float& tmax, f3& contrib)
+{
+    uint32_t hx = sx ^ 0x2c1b3c6du, hy = sy ^ 0x297a2d39u;
+    float xi0, xi1, xi2, xi3;
+    pcg2d(hx, hy, xi0, xi1);
+    pcg2d(hx, hy, xi2, xi3);
+    const LightSample ls = light_sample(lt, xi0, xi1, xi2, xi3);
+    o = s.position + s.normal * 0.001f;
+    const f3 dv = ls.y - o;
+    const float d2 = dot3(dv, dv);
+    l = normalize3(dv);
+    const float ndl = dot3(s.normal, l);
+    if (!(ndl > 0.0f)) return false;
+    const float c = light_cos(ls.e1, ls.e2, l);
+    if (!(c > 0.0f)) return false;
+    const float pl = light_pdf(ls.le, total, d2, c);
+    const float pb = brdf_density(s, l);
+    const float w = (pl * pl) / (pl * pl + pb * pb);
+    contrib = ((throughput * (brdf_eval(s, l) * ndl)) * ls.le) * (w / pl);
+    if (!__builtin_isfinite(contrib.x) || !__builtin_isfinite(contrib.y) || !__builtin_isfinite(contrib.z)) return false;
+    tmax = __builtin_sqrtf(d2) * kLightShadowScale;
+    return contrib.x > 0.0f || contrib.y > 0.0f || contrib.z > 0.0f;
+}
+// The weight of the emission a BRDF-sampled ray (origin o, direction d) at bounce >= 1 finds at a hit: 1 unless lum(Le) > 0 and
+// total > 0, else p_brdf^2 / (p_brdf^2 + p_L^2) with p_L of the hit point (d2 = |position - o|^2, the hit triangle's world edges
+// xform_dir(transform, e1 / e2)); a NaN weight (both densities infinite) is 1.  p_brdf: read only then.
+__device__ __forceinline__ float light_hit_weight(const LightDev& lt, float total, const SceneShading& sh, const Hit& h, const Shading& s,
+                                                 f3 o, f3 d, const float* p_brdf)
+{
+    if (!(light_lum(s.emission.x, s.emission.y, s.emission.z) > 0.0f) || !(total > 0.0f)) return 1.0f;
+    const WideTri& w = lt.wtris[h.tri];
+    const RefInstance& b = sh.instances[h.inst];
+    const f3 e1 = xform_dir(b.transform, mk3(w.e1[0], w.e1[1], w.e1[2])), e2 = xform_dir(b.transform, mk3(w.e2[0], w.e2[1], w.e2[2]));
+    const f3 dv = s.position - o;
+    const float pl = light_pdf(s.emission, total, dot3(dv, dv), light_cos(e1, e2, d));
+    const float pb = *p_brdf;
+    const float wt = (pb * pb) / (pb * pb + pl * pl);
+    return wt == wt ? wt : 1.0f;
 }
 
 __device__ __forceinline__ f3 aces_film(f3 x)  // progressive_rendering.glsl:19-26

@@ -10,15 +10,30 @@
 //               below the last bounce draws one map direction (env_nee) and queues a shadow ray for wf2_occlude; a miss at bounce
 //               >= 1 is weighted against that strategy (env_miss_weight).  The primary and accumulation launches are the *_env
 //               ones: a primary miss has weight 1.
+//   JPT_ENV 3   the *_lt kernels (jpt_set_light_sampling, JPT_LIGHT_SAMPLING_MIS): shade_entry_lt, wf2_shade_lt and wf2_finish_lt,
+//               which take the emitter tables (LightDev), both shadow queues (Wf2Nee: the map's, the emitters') and the miss model
+//               as a run-time value, env_mode: 0 the gradient, 1 the map, 2 the map with JPT_ENV_SAMPLING_MIS.  A vertex below the
+//               last bounce queues the map's shadow ray (env_mode 2) and the emitters' (light_nee, bounded by tmax); a hit at
+//               bounce >= 1 weighs its emission against the emitter strategy (light_hit_weight).  They pair with the primary and
+//               accumulation launches of the miss model in use.
 // A run-time branch on the map in the default kernels would cost them registers; a template parameter would change their names.
 // (No include guard: that is the point.)
-#if JPT_ENV == 2
+#if JPT_ENV == 3
+#define JPT_ENV_NAME(name) name##_lt
+#define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, LightDev lt, Wf2Nee nee, Wf2Nee lnee, int env_mode
+#define JPT_ENV_ARG , env, es, lt, nee, lnee, env_mode
+#define JPT_NEE_PARAM , bool& shadow, float4& so, float4& sd, float4& sc4, bool& lshadow, float4& lso, float4& lsd, float4& lsc
+#define JPT_NEE_ARG , shadow, so, sd, sc4, lshadow, lso, lsd, lsc
+#define JPT_SKY(d) (env_mode != 0 ? env_radiance(env, d) : sample_sky(d))
+#define JPT_PDF lnee.pdf
+#elif JPT_ENV == 2
 #define JPT_ENV_NAME(name) name##_mis
 #define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, Wf2Nee nee
 #define JPT_ENV_ARG , env, es, nee
 #define JPT_NEE_PARAM , bool& shadow, float4& so, float4& sd, float4& sc4
 #define JPT_NEE_ARG , shadow, so, sd, sc4
 #define JPT_SKY(d) env_radiance(env, d)
+#define JPT_PDF nee.pdf
 #elif JPT_ENV
 #define JPT_ENV_NAME(name) name##_env
 #define JPT_ENV_PARAM , EnvDev env
@@ -35,7 +50,7 @@
 #define JPT_SKY(d) sample_sky(d)
 #endif
 
-#if JPT_ENV != 2   // (the MIS pipeline runs wf2_primary_env)
+#if JPT_ENV < 2   // (the MIS and light pipelines run the primary launch of their miss model)
 
 // ---- bounce 0: generate + trace ------------------------------------------------------------------------
 
@@ -192,7 +207,7 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_pr
     if (COUNT) flush_counters(cnt, counters);
 }
 
-#endif  // JPT_ENV != 2
+#endif  // JPT_ENV < 2
 
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
@@ -217,6 +232,11 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
     // (MIS: a shadow ray of this vertex, for wf2_occlude: so = origin.xyz | path id + kNeeFinal when the path ends here, sd = the map
     // direction, sc4 = the contribution if unoccluded.  rad[path] then holds the radiance so far, which the shadow ray adds to.)
     shadow = false;
+#elif JPT_ENV == 3
+    // (lights: the map's shadow ray as above when env_mode is 2, and the emitters' in lso / lsd (direction, tmax) / lsc; when both
+    // are cast the map's lands first, and the one that lands last stores a path that ends here)
+    shadow = false;
+    lshadow = false;
 #endif
     const uint32_t p = __float_as_uint(rd.w) & kPathMask;
     const bool had_radiance = (__float_as_uint(rd.w) & kHasRadiance) != 0u;
@@ -306,16 +326,27 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
 #if JPT_ENV == 2
         if (bounce > 0) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, nee.pdf[p]);
         else
+#elif JPT_ENV == 3
+        if (bounce > 0 && env_mode == 2) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, lnee.pdf[p]);
+        else
 #endif
         radiance = radiance + throughput * JPT_SKY(ray.d);
         if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = cam_far;  // (only a redone primary hit can turn into a miss here)
     } else {
         if (COUNT) cnt.shaded_hits++;
         const Shading s = get_shading_data<TEX>(sh, h, (hb >> 31) != 0u, stri);
+#if JPT_ENV == 3
+        const float ltotal = lt.marg[lt.n_blocks];
+        if (bounce > 0) radiance = radiance + (throughput * s.emission) * light_hit_weight(lt, ltotal, sh, h, s, ray.o, ray.d, lnee.pdf + p);
+        else
+#endif
         radiance = radiance + throughput * s.emission;
         if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = length3(s.position - ray.o);
-#if JPT_ENV == 2
+#if JPT_ENV >= 2
         if (!LAST && bounce < fp.max_bounces) {
+#if JPT_ENV == 3
+          if (env_mode == 2) {
+#endif
             f3 l, c;
             shadow = env_nee(s, env, es, sx, sy, throughput, l, c);
             if (shadow) {
@@ -324,9 +355,22 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
                 sd = make_float4(l.x, l.y, l.z, 0.0f);
                 sc4 = make_float4(c.x, c.y, c.z, 0.0f);
             }
+#if JPT_ENV == 3
+          }
+            if (ltotal > 0.0f) {
+                f3 lo3, ll, lc;
+                float tmax;
+                lshadow = light_nee(s, lt, ltotal, sx, sy, throughput, lo3, ll, tmax, lc);
+                if (lshadow) {
+                    lso = make_float4(lo3.x, lo3.y, lo3.z, __uint_as_float(p));
+                    lsd = make_float4(ll.x, ll.y, ll.z, tmax);
+                    lsc = make_float4(lc.x, lc.y, lc.z, 0.0f);
+                }
+            }
+#endif
             float density;
             alive = bounce_step_pdf(s, sx, sy, ray, throughput, density);
-            if (alive) nee.pdf[p] = density;
+            if (alive) JPT_PDF[p] = density;
         }
 #else
         if (!LAST && bounce < fp.max_bounces) alive = bounce_step(s, sx, sy, ray, throughput);
@@ -335,7 +379,9 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
     }
     if (alive) {
         // (radiance starts as +0 and +0 + x is x or +0, never -0: "unchanged and never written" means exactly +0)
-#if JPT_ENV == 2
+#if JPT_ENV == 3
+        const bool changed = shadow || lshadow || radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
+#elif JPT_ENV == 2
         const bool changed = shadow || radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
 #else
         const bool changed = radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
@@ -349,6 +395,12 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
         if (shadow) {   // the path ends here, but its shadow ray has yet to land: wf2_occlude stores its final value
             wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
             so.w = __uint_as_float(p | kNeeFinal);
+        } else
+#elif JPT_ENV == 3
+        if (shadow || lshadow) {   // the path ends here: the shadow ray that lands last (the emitters') stores its final value
+            wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
+            if (lshadow) lso.w = __uint_as_float(p | kNeeFinal);
+            else so.w = __uint_as_float(p | kNeeFinal);
         } else
 #endif
         store_final(wb, fp.accum_mode, p, radiance);
@@ -376,9 +428,13 @@ __global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVE
     const uint32_t i = base + threadIdx.x;
     bool alive = false;
     float4 no, nd, nt;
-#if JPT_ENV == 2
+#if JPT_ENV >= 2
     bool shadow = false;
     float4 so, sd, sc4;
+#endif
+#if JPT_ENV == 3
+    bool lshadow = false;
+    float4 lso, lsd, lsc;
 #endif
     if (i < n) {
         const float4 ro = stream_ld4(&wb.ray_o[in][seg_base + i]), rd = stream_ld4(&wb.ray_d[in][seg_base + i]);
@@ -388,7 +444,7 @@ __global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVE
         bool unreachable;   // (set aside inside shade_entry: nothing more to do here)
         alive = JPT_ENV_NAME(shade_entry)<COUNT, LAST, TEX>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, true, unreachable, no, nd, nt, cnt JPT_ENV_ARG JPT_NEE_ARG);
     }
-#if JPT_ENV == 2
+#if JPT_ENV >= 2
     if (!LAST) {   // the shadow rays, packed into the segment's shadow queue of this bounce as the next rays are below
         const unsigned long long sm = __ballot(shadow);
         if (sm) {
@@ -400,6 +456,22 @@ __global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVE
                 stream_st4(&nee.sh_o[j], so);
                 stream_st4(&nee.sh_d[j], sd);
                 stream_st4(&nee.sh_c[j], sc4);
+            }
+        }
+    }
+#endif
+#if JPT_ENV == 3
+    if (!LAST) {   // the emitters' shadow rays, into their own queue (traced after the map's: the two never share a launch)
+        const unsigned long long lm = __ballot(lshadow);
+        if (lm) {
+            uint32_t lbase = 0;
+            if (lane == 0) lbase = atomicAdd(&lnee.scount[(size_t)bounce * kSegments + seg], (uint32_t)__popcll(lm));
+            lbase = (uint32_t)__builtin_amdgcn_readfirstlane((int)lbase);
+            if (lshadow) {
+                const size_t j = seg_base + lbase + lanes_below(lm, lane);
+                stream_st4(&lnee.sh_o[j], lso);
+                stream_st4(&lnee.sh_d[j], lsd);
+                stream_st4(&lnee.sh_c[j], lsc);
             }
         }
     }
@@ -493,6 +565,28 @@ __global__ __launch_bounds__(64) void JPT_ENV_NAME(wf2_finish)(WideSceneDev sc, 
                 nee_land(wb, fp.accum_mode, so, sc4, occ.hit.t < 1e9f);
             }
             if (!alive) break;
+#elif JPT_ENV == 3
+            bool shadow, lshadow;
+            float4 so, sd, sc4, lso, lsd, lsc;
+            const bool alive = shade_entry_lt<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt JPT_ENV_ARG JPT_NEE_ARG);
+            if (shadow) {   // the map's shadow ray at once (wf2_occlude's walk), then the emitters' (wf2_occlude_lt's, bounded by tmax)
+                Traversal<COUNT, W4> occ;
+                const typename Traversal<COUNT, W4>::Stack ost{nullptr, stack_mem, 0, 0, kDepth};
+                occ.begin(sc, mk3(so.x, so.y, so.z), mk3(sd.x, sd.y, sd.z));
+                while (occ.hit.t >= 1e9f && occ.step(sc, ost, cnt)) {
+                }
+                nee_land(wb, fp.accum_mode, so, sc4, occ.hit.t < 1e9f);
+            }
+            if (lshadow) {
+                Traversal<COUNT, W4> occ;
+                const typename Traversal<COUNT, W4>::Stack ost{nullptr, stack_mem, 0, 0, kDepth};
+                occ.begin(sc, mk3(lso.x, lso.y, lso.z), mk3(lsd.x, lsd.y, lsd.z));
+                occ.hit.t = lsd.w;
+                while (occ.hit.t >= lsd.w && occ.step(sc, ost, cnt)) {
+                }
+                nee_land(wb, fp.accum_mode, lso, lsc, occ.hit.t < lsd.w);
+            }
+            if (!alive) break;
 #else
             if (!JPT_ENV_NAME(shade_entry)<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt JPT_ENV_ARG)) break;
 #endif
@@ -504,7 +598,7 @@ __global__ __launch_bounds__(64) void JPT_ENV_NAME(wf2_finish)(WideSceneDev sc, 
     if (COUNT) flush_counters(cnt, counters);
 }
 
-#if JPT_ENV != 2
+#if JPT_ENV < 2
 // ---- per pixel: frames in order -> accumulation buffer, display image, depth ----------------------------------
 
 __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffers wb, Wf2Dims dm, FrameParams fp, RefCamera cam, SkyCull cull,
@@ -723,7 +817,7 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
     }
 }
 
-#endif  // JPT_ENV != 2
+#endif  // JPT_ENV < 2
 
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM
@@ -731,3 +825,6 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 #undef JPT_NEE_PARAM
 #undef JPT_NEE_ARG
 #undef JPT_SKY
+#ifdef JPT_PDF
+#undef JPT_PDF
+#endif

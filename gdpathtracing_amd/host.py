@@ -259,6 +259,42 @@ class Context:
         with shadow rays, combined with BRDF sampling by the power heuristic), for later renders."""
         self._ck(self._lib.jpt_set_environment_sampling(self.h, int(mode)), "jpt_set_environment_sampling")
 
+    def set_light_sampling(self, mode):
+        """jpt_set_light_sampling: capi.LIGHT_SAMPLING_BRDF (default) or capi.LIGHT_SAMPLING_MIS (emissive triangles sampled with
+        shadow rays, combined with BRDF sampling by the power heuristic), for later renders."""
+        self._ck(self._lib.jpt_set_light_sampling(self.h, int(mode)), "jpt_set_light_sampling")
+
+    def debug_light_tables(self):
+        """jpt_debug_light_tables: (pairs [n, 2] uint32, tri [n, 3, 4] float32, cdf [n], marg [blocks + 1]) of the emitter tables"""
+        n = np.zeros(2, np.uint32)
+        self._ck(self._lib.jpt_debug_light_tables(self.h, 0, _ptr(n), None, None, None, None), "jpt_debug_light_tables")
+        pairs = np.zeros((int(n[0]), 2), np.uint32)
+        tri = np.zeros((int(n[0]), 3, 4), np.float32)
+        cdf = np.zeros(int(n[0]), np.float32)
+        marg = np.zeros(int(n[1]) + 1, np.float32)
+        self._ck(self._lib.jpt_debug_light_tables(self.h, int(n[0]), _ptr(n), _ptr(pairs), _ptr(tri), _ptr(cdf), _ptr(marg)),
+                 "jpt_debug_light_tables")
+        return pairs, tri, cdf, marg
+
+    def debug_light_sample(self, xi4, origins):
+        """jpt_debug_light_sample: (points [n, 3], dirs [n, 3], pdf [n]) for randoms xi4 [n, 4] seen from origins [n, 3]"""
+        xi4 = np.ascontiguousarray(xi4, np.float32).reshape(-1, 4)
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        n = len(xi4)
+        pts, dirs, pdf = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        self._ck(self._lib.jpt_debug_light_sample(self.h, _ptr(xi4), _ptr(o), n, _ptr(pts), _ptr(dirs), _ptr(pdf)), "jpt_debug_light_sample")
+        return pts, dirs, pdf
+
+    def debug_light_pdf(self, inst, tri, points, origins, dirs):
+        """jpt_debug_light_pdf: p_L [n] of hit points on (instance, triangle) seen from origins along dirs"""
+        inst = np.ascontiguousarray(inst, np.uint32).reshape(-1)
+        tri = np.ascontiguousarray(tri, np.uint32).reshape(-1)
+        p, o, d = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (points, origins, dirs))
+        pdf = np.zeros(len(inst), np.float32)
+        self._ck(self._lib.jpt_debug_light_pdf(self.h, _ptr(inst), _ptr(tri), _ptr(p), _ptr(o), _ptr(d), len(inst), _ptr(pdf)),
+                 "jpt_debug_light_pdf")
+        return pdf
+
     def set_kernel(self, variant):
         self._ck(self._lib.jpt_set_kernel(self.h, variant), "jpt_set_kernel")
 
@@ -568,6 +604,9 @@ class MultiContext:
 
     def set_environment_sampling(self, mode):
         self._ck(self._lib.jpt_multi_set_environment_sampling(self.h, int(mode)), "jpt_multi_set_environment_sampling")
+
+    def set_light_sampling(self, mode):
+        self._ck(self._lib.jpt_multi_set_light_sampling(self.h, int(mode)), "jpt_multi_set_light_sampling")
 
     def set_camera(self, camera_block):
         cam = np.ascontiguousarray(camera_block, dtype=wire.CAMERA).reshape(1)

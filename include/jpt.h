@@ -385,6 +385,45 @@ int jpt_set_environment_params(jpt_ctx *ctx, const float *rotation9, float inten
 #define JPT_ENV_SAMPLING_MIS  1
 int jpt_set_environment_sampling(jpt_ctx *ctx, int32_t mode);
 
+/* Importance sampling of the emissive triangles (no reference counterpart; the reference lists next-event estimation among its
+ * wanted features).  The mode belongs to the context, like the map's: it survives scene commits, uploads and updates;
+ * jpt_scene_share does not copy it.  Each render takes it by value: queued renders keep the mode of their own call.
+ *   JPT_LIGHT_SAMPLING_BRDF (default)  emitters are reached by BRDF sampling alone: the same kernels and bits as without this call.
+ *   JPT_LIGHT_SAMPLING_MIS             the emitters are sampled directly and combined with BRDF sampling by the power heuristic.
+ * Emitters: every (instance, triangle) pair whose Le -- emission.rgb * max(0, emission.w) of the material get_shading_data looks
+ *   up for it (an out-of-range index: material 0) -- has lum(Le) = 0.2126 r + 0.7152 g + 0.0722 b > 0, listed instance by
+ *   instance, each instance's triangles (those under its BLAS root) in ascending index.  Power = lum(Le) * world area, the area
+ *   0.5 |E1 x E2| of the world edges E1 = xform_dir(transform, v1 - v0), E2 likewise, vertex 0 P0 = xform_point(transform, v0);
+ *   a power that is not finite and > 0 (zero-area, degenerate) is 0 and never drawn.  Tables: blocks of 256 emitters, per block
+ *   a sequential prefix sum of the powers normalised by the block's total (the last entry exactly 1; a block of power 0: all 1s),
+ *   and the same over the block totals in block order; their sum is the total.  When the scene's total is 0 (no emitter) MIS
+ *   renders are BRDF renders.
+ * Estimator, at every hit with bounce < max_bounces (total > 0): randoms from a copy of the vertex's seeds hashed by two pcg2d
+ *   rounds of (sx ^ 0x2c1b3c6d, sy ^ 0x297a2d39) -- the path's own sequence, so its BRDF continuation, is that of BRDF mode;
+ *   xi0 (clamped below 1) picks the block on the marginal CDF and xi1 (clamped) the emitter on the block's CDF (the first entry
+ *   > xi); s = sqrt(xi2), y = (P0 + E1 * (s * (1 - xi3))) + E2 * (s * xi3).  o = position + normal * 0.001, l = normalize(y - o),
+ *   d2 = dot(y - o, y - o), c = |normalize(E1 x E2) . l| (emission is two-sided);
+ *   p_L = (lum(Le) * d2) / (total * c), w_L = p_L^2 / (p_L^2 + p_brdf(l)^2).  When n.l > 0, c > 0 and the contribution
+ *   ((throughput * (brdf(l) * n.l)) * Le) * (w_L / p_L) is finite with a component > 0, a shadow ray (o, l) with
+ *   tmax = sqrt(d2) * 0.9999f is cast; it is blocked when some triangle's Moller-Trumbore test accepts t < tmax (the closest-hit
+ *   walk started with t = tmax ends below it): on the native trees the brute-force answer, on the reference-layout tree
+ *   (JPT_KERNEL_REFERENCE_LAYOUT) that tree's answer, without reach or tie logic.  Unblocked, the contribution is added.
+ *   Emission that a BRDF-sampled ray (origin o, direction d) finds at bounce >= 1 is weighted by p_brdf^2 / (p_brdf^2 + p_L^2),
+ *   p_brdf the previous vertex's density of d, p_L as above with d2 = |position - o|^2 and the hit triangle's world edges (a NaN
+ *   weight is 1); non-emitters and primary hits keep weight 1.  With JPT_ENV_SAMPLING_MIS as well, a vertex casts the map's
+ *   shadow ray and then the emitters' and their contributions join the path in that order; each estimator is weighted against
+ *   BRDF sampling alone.
+ * The emitter list follows the scene the renders see: it is made from the committed or uploaded scene (and again after
+ * jpt_scene_update_tlas / jpt_scene_update_reference_tlas); the tables are rebuilt on the device at the first render that samples
+ * them after any change, jpt_scene_refit_tlas and jpt_scene_update_mesh included, ordered after the renders already queued.  In
+ * BRDF mode none of this runs.  Memory: 8 B per emitter for the list (on the host and on the device), 52 B per emitter and 4 B
+ * per 256 for the tables; a
+ * light-sampling render's workspace holds a second shadow-ray queue (48 B per queue entry) and, without map MIS, 4 B per path
+ * (jpt_get_workspace_bytes counts them).  A bad mode: JPT_E_INVALID; host-only contexts: JPT_E_DEVICE after the checks. */
+#define JPT_LIGHT_SAMPLING_BRDF 0
+#define JPT_LIGHT_SAMPLING_MIS  1
+int jpt_set_light_sampling(jpt_ctx *ctx, int32_t mode);
+
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
  *   REFERENCE_LAYOUT   one thread per pixel straight over the six reference-layout buffers, node for node
@@ -539,6 +578,7 @@ int jpt_multi_set_params(jpt_multi *m, int32_t width, int32_t height, int32_t ma
 int jpt_multi_set_environment(jpt_multi *m, const float *rgb, int32_t width, int32_t height);
 int jpt_multi_set_environment_params(jpt_multi *m, const float *rotation9, float intensity);
 int jpt_multi_set_environment_sampling(jpt_multi *m, int32_t mode);
+int jpt_multi_set_light_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -590,6 +630,22 @@ int jpt_debug_env_sample(int device_id, const float *rgb, int32_t width, int32_t
                          const float *xi2, uint32_t n, float *dirs_out, float *pdf_out);
 int jpt_debug_env_pdf(int device_id, const float *rgb, int32_t width, int32_t height, const float *rotation9,
                       const float *dirs3, uint32_t n, float *pdf_out);
+/* The emitter tables of JPT_LIGHT_SAMPLING_MIS as the context's next render would take them (made now if stale; the context needs
+ * a scene): n_out[0] = emitters, n_out[1] = blocks; then, each output may be NULL and is filled only if its capacity (in emitters)
+ * is at least the count:
+ *   _tables: pairs_out[2 i ..] (instance, triangle), tri_out[12 i ..] P0.xyz Le.r E1.xyz Le.g E2.xyz Le.b, cdf_out[i], and
+ *            marg_out[0 .. blocks] (the marginal CDF, then the total);
+ *   _sample: for xi4[4 i .. 4 i + 3] and origins3[3 i ..] (o, as the estimator's): points_out[3 i ..] = y, dirs_out[3 i ..] = l,
+ *            pdf_out[i] = p_L (0 when c = 0 or the total is 0);
+ *   _pdf:    pdf_out[i] = p_L of hit point points3[3 i ..] on triangle tri[i] of instance inst[i] seen from origins3[3 i ..]
+ *            along dirs3[3 i ..] (the weight's density; 0 when lum(Le) = 0).
+ * Host-only contexts: JPT_E_DEVICE. */
+int jpt_debug_light_tables(jpt_ctx *ctx, uint32_t capacity, uint32_t *n_out, uint32_t *pairs_out, float *tri_out, float *cdf_out,
+                           float *marg_out);
+int jpt_debug_light_sample(jpt_ctx *ctx, const float *xi4, const float *origins3, uint32_t n, float *points_out, float *dirs_out,
+                           float *pdf_out);
+int jpt_debug_light_pdf(jpt_ctx *ctx, const uint32_t *inst, const uint32_t *tri, const float *points3, const float *origins3,
+                        const float *dirs3, uint32_t n, float *pdf_out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

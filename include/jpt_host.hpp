@@ -756,6 +756,8 @@ class PathTracingCamera {
     }
     // jpt_set_environment_sampling: JPT_ENV_SAMPLING_BRDF (default) or JPT_ENV_SAMPLING_MIS (shadow rays towards map samples)
     void set_environment_sampling(int32_t mode) { check(ctx, jpt_set_environment_sampling(ctx, mode), "jpt_set_environment_sampling"); }
+    // jpt_set_light_sampling: JPT_LIGHT_SAMPLING_BRDF (default) or JPT_LIGHT_SAMPLING_MIS (shadow rays towards emitter samples)
+    void set_light_sampling(int32_t mode) { check(ctx, jpt_set_light_sampling(ctx, mode), "jpt_set_light_sampling"); }
 
     int max_bounces = 4;                    // the literal 5 of main.glsl:377 is max_bounces + 1
     int accum_mode = JPT_ACCUM_REF_LDR8;    // what the reference does (rgba8 screen image before the sum)
