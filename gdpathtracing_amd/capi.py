@@ -48,6 +48,7 @@ SYMBOLS = [
     "jpt_debug_env_lookup",
     "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
     "jpt_set_light_sampling", "jpt_multi_set_light_sampling", "jpt_debug_light_tables", "jpt_debug_light_sample", "jpt_debug_light_pdf",
+    "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
 ]
 
 
@@ -58,6 +59,14 @@ class JptError(RuntimeError):
 class Surface(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p), ("indices", C.c_void_p),
                 ("n_vertices", C.c_int32), ("n_indices", C.c_int32)]
+
+
+class DenoiseParams(C.Structure):
+    """jpt_denoise_params; the defaults are the library's"""
+    _fields_ = [("passes", C.c_int32), ("normal_power_log2", C.c_int32), ("sigma_plane", C.c_float), ("sigma_color", C.c_float)]
+
+    def __init__(self, passes=5, normal_power_log2=6, sigma_plane=0.02, sigma_color=4.0):
+        super().__init__(passes, normal_power_log2, sigma_plane, sigma_color)
 
 
 class Stats(C.Structure):
@@ -214,6 +223,13 @@ def lib():
         L.jpt_debug_light_tables.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.jpt_debug_light_sample.argtypes = [vp, vp, vp, u32, vp, vp, vp]
         L.jpt_debug_light_pdf.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
+    if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
+        L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
+        L.jpt_denoise.argtypes = [vp]
+        L.jpt_read_denoised_f32.argtypes = [vp, vp]
+        L.jpt_read_denoised_rgba8.argtypes = [vp, vp]
+        L.jpt_read_guides_f32.argtypes = [vp, vp, vp, vp]
+        L.jpt_debug_atrous.argtypes = [C.c_int, i32, i32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
     _lib = L
     return L
 

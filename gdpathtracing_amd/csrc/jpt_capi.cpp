@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "jpt_builder.h"
+#include "jpt_denoise.h"
 #include "jpt_kernels.h"
 #include "jpt_instance_math.h"
 #include "jpt_mesh_math.h"
@@ -285,6 +286,13 @@ struct jpt_ctx {
     DevBuf<float4> d_light_tri;
     DevBuf<float> d_light_cdf, d_light_marg;   // per emitter; the marginal CDF's n_blocks entries, then the total power
     LightDev light_view;
+
+    // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
+    // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution
+    AtrousParams dn_params;
+    DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
+    DevBuf<uint32_t> d_dn_ldr;
+    bool dn_valid = false;
 
     jpt_stats stats;
 };
@@ -2442,6 +2450,17 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
     if (sampler_mode < JPT_SAMPLER_NEAREST_CLAMP || sampler_mode > JPT_SAMPLER_LINEAR_REPEAT) return fail(c, JPT_E_INVALID, "unknown sampler_mode");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no framebuffers");
     HIP_TRY(c, hipSetDevice(c->device));
+    if ((width != c->width || height != c->height) && c->d_dn_ping.p) {
+        // jpt_denoise's images are of the old size: given back once the work that uses them has run
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->d_dn_pos.release();
+        c->d_dn_nrm.release();
+        c->d_dn_alb.release();
+        c->d_dn_ping.release();
+        c->d_dn_pong.release();
+        c->d_dn_ldr.release();
+    }
+    if (width != c->width || height != c->height) c->dn_valid = false;
     c->width = width;
     c->height = height;
     c->max_bounces = max_bounces;
@@ -2800,6 +2819,117 @@ int jpt_read_accum_f32(jpt_ctx* c, float* out)
     else {
         std::memset(out, 0, full * 16);
         scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 4);
+    }
+    return JPT_OK;
+}
+
+extern "C++" {
+namespace jpt {
+int check_denoise_params(const AtrousParams& p, std::string& why)
+{
+    if (p.passes < 1 || p.passes > kAtrousMaxPasses) why = "jpt_denoise_params: passes must be in [1, 6]";
+    else if (p.normal_power_log2 < 0 || p.normal_power_log2 > 8) why = "jpt_denoise_params: normal_power_log2 must be in [0, 8]";
+    else if (!std::isfinite(p.sigma_plane) || !(p.sigma_plane > 0.0f)) why = "jpt_denoise_params: sigma_plane must be finite and > 0";
+    else if (!std::isfinite(p.sigma_color) || !(p.sigma_color > 0.0f)) why = "jpt_denoise_params: sigma_color must be finite and > 0";
+    else return JPT_OK;
+    return JPT_E_INVALID;
+}
+}  // namespace jpt
+}
+
+int jpt_set_denoise_params(jpt_ctx* c, const jpt_denoise_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    AtrousParams p;
+    if (params) {
+        p.passes = params->passes;
+        p.normal_power_log2 = params->normal_power_log2;
+        p.sigma_plane = params->sigma_plane;
+        p.sigma_color = params->sigma_color;
+    }
+    std::string why;
+    const int rc = check_denoise_params(p, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
+    c->dn_params = p;
+    return JPT_OK;
+}
+
+int jpt_denoise(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_denoise filters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_denoise: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_denoise needs the whole image on one context (world == 1)");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
+    if (!c->scene_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
+    if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_denoise: jpt_set_params / jpt_set_camera not called");
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_denoise: no frame accumulated since the last reset");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->width * c->height;
+    if (c->d_dn_ping.n != npx || !c->d_dn_ping.p) {
+        HIP_TRY(c, c->d_dn_pos.resize(npx));
+        HIP_TRY(c, c->d_dn_nrm.resize(npx));
+        HIP_TRY(c, c->d_dn_alb.resize(npx));
+        HIP_TRY(c, c->d_dn_ping.resize(npx));
+        HIP_TRY(c, c->d_dn_pong.resize(npx));
+        HIP_TRY(c, c->d_dn_ldr.resize(npx));
+    }
+    // On the context's stream: it is ordered behind the accumulation of every render queued so far (launch_render) and behind the
+    // device refits (queue_instance_refit), and the accumulation of every later render waits for what it holds.
+    hipStream_t s = c->stream;
+    if (npx) {
+        launch_guides(s, c->ds, c->camera, c->width, c->height, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p);
+        launch_atrous(s, c->dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p,
+                      c->d_dn_ping.p, c->d_dn_pong.p, c->d_dn_ldr.p);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->dn_valid = true;
+    return JPT_OK;
+}
+
+static int read_denoise_common(jpt_ctx* c, bool have_out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!have_out) return fail(c, JPT_E_INVALID, "null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
+    if (!c->dn_valid) return fail(c, JPT_E_STATE, "no jpt_denoise at the current resolution yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return JPT_OK;
+}
+
+int jpt_read_denoised_f32(jpt_ctx* c, float* out)
+{
+    int rc = read_denoise_common(c, out != nullptr);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    if ((rc = staged_read(c, c->d_dn_ping.p, bytes)) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+int jpt_read_denoised_rgba8(jpt_ctx* c, uint8_t* out)
+{
+    int rc = read_denoise_common(c, out != nullptr);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->width * c->height * sizeof(uint32_t);
+    if ((rc = staged_read(c, c->d_dn_ldr.p, bytes)) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+int jpt_read_guides_f32(jpt_ctx* c, float* position_t, float* normal, float* albedo)
+{
+    int rc = read_denoise_common(c, true);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    float* outs[3] = {position_t, normal, albedo};
+    const float4* src[3] = {c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p};
+    for (int k = 0; k < 3; k++) {
+        if (!outs[k]) continue;
+        if ((rc = staged_read(c, src[k], bytes)) != JPT_OK) return rc;
+        std::memcpy(outs[k], c->h_read_pinned.p, bytes);
     }
     return JPT_OK;
 }

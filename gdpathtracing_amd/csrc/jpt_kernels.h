@@ -335,6 +335,18 @@ void launch_mesh_refit(hipStream_t stream, const MeshRefitArgs& args, const uint
 void launch_temporal(hipStream_t stream, const RefTemporalParams& tp, uint32_t* screen, const float* depth, float4* hist1,
                      float4* hist2);
 
+// jpt_denoise (jpt_kernels_denoise.hip; the arithmetic: jpt_denoise.h).  The checks of jpt_set_denoise_params, also run by
+// jpt_debug_atrous; the guide images of the whole image -- one primary ray per pixel through the pixel centre over the arrays the
+// wavefront kernels walk, (position.xyz, hit distance | -1), (normal, 0), (albedo, 0) per pixel --; and the filter passes: from the
+// sums and frame_count to the denoised image in `ping` ((r, g, b, 1); `pong` is scratch) and its display image in `ldr` (may be
+// null).  Every pointer is a device pointer of width * height elements; nothing else is written.
+struct AtrousParams;
+int check_denoise_params(const AtrousParams& p, std::string& why);
+void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& cam, int width, int height, float4* position_t,
+                   float4* normal, float4* albedo);
+void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int height, const float4* sums, float frame_count,
+                   const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr);
+
 // pixels of this context's share of the image that lie outside the render's window (the tile-aligned bounding rectangle
 // of the sky cull's screen rectangles): the primary launch does not even enumerate them (their rays are sky by the
 // cull's argument; the event counters are completed with their number on the host)

@@ -361,6 +361,35 @@ class Context:
         self._ck(self._lib.jpt_read_depth_f32(self.h, _ptr(out)), "jpt_read_depth_f32")
         return out
 
+    # ---- spatial denoising (jpt_denoise)
+    def set_denoise_params(self, params: Optional[capi.DenoiseParams] = None, **fields):
+        """jpt_set_denoise_params: a capi.DenoiseParams, or its fields by name (passes, normal_power_log2, sigma_plane,
+        sigma_color; the rest at the defaults); nothing: the defaults"""
+        if params is None and fields:
+            params = capi.DenoiseParams(**fields)
+        self._ck(self._lib.jpt_set_denoise_params(self.h, None if params is None else C.byref(params)), "jpt_set_denoise_params")
+
+    def denoise(self):
+        """jpt_denoise: queue the guide pass and the filter passes over the accumulation as it is after the renders queued so
+        far; the accumulation itself is not touched"""
+        self._ck(self._lib.jpt_denoise(self.h), "jpt_denoise")
+
+    def read_denoised(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self._lib.jpt_read_denoised_f32(self.h, _ptr(out)), "jpt_read_denoised_f32")
+        return out
+
+    def read_denoised_ldr(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._ck(self._lib.jpt_read_denoised_rgba8(self.h, _ptr(out)), "jpt_read_denoised_rgba8")
+        return out
+
+    def read_guides(self):
+        """jpt_read_guides_f32: (position_t, normal, albedo), float32 [height, width, 4] each"""
+        g = [np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(3)]
+        self._ck(self._lib.jpt_read_guides_f32(self.h, _ptr(g[0]), _ptr(g[1]), _ptr(g[2])), "jpt_read_guides_f32")
+        return tuple(g)
+
     def device_accum(self):
         n = C.c_size_t()
         p = self._lib.jpt_device_accum(self.h, C.byref(n))
@@ -502,7 +531,9 @@ class PathTracingCamera:
         self.geometry_group.build(self.ctx)
         self.ctx.set_params(width, height, self.max_bounces, self.accum_mode)
 
-    def render(self, n_frames: int = 1):                            # path_tracing_camera.cpp:193-232
+    def render(self, n_frames: int = 1, denoise: bool = False):     # path_tracing_camera.cpp:193-232
+        """denoise: the returned screen is jpt_denoise's view of the accumulation (progressive mode only; the accumulation goes on
+        unbiased underneath)"""
         self.ctx.set_denoising_mode(self.denoising_mode)            # the switch at :207-225
         self.ctx.set_outputs(depth=self.denoising_mode == self.TEMPORAL_REPROJECTION)   # (main.glsl:435's image has one reader)
         self.ctx.set_camera(scenes.camera_block(self.camera_desc, self.width, self.height))
@@ -522,6 +553,9 @@ class PathTracingCamera:
             self.ctx.set_temporal_params(self.temporal_reprojection.render(vp))   # :220
         self.ctx.render(n_frames, first)
         self.frame_index += n_frames
+        if denoise:
+            self.ctx.denoise()
+            return self.ctx.read_denoised_ldr()
         return self.ctx.read_ldr()                                  # get_image_uniform_buffer (:228-229)
 
 

@@ -200,7 +200,9 @@ int jpt_renders_in_flight(const jpt_ctx *ctx);
  * workspace is the two images of one frame).
  * Host side: the blocking read-backs (jpt_read_*) go through one PINNED staging buffer per context, as large as the
  * largest read-back made so far (133 MB after a jpt_read_accum_f32 of a 3840x2160 image); this call and every change of
- * resolution or partition give it back, the next read-back allocates what it needs.  It is not part of the bytes reported. */
+ * resolution or partition give it back, the next read-back allocates what it needs.  It is not part of the bytes reported.
+ * Nor are jpt_denoise's own images (84 bytes per pixel, from the first jpt_denoise at a resolution until jpt_set_params with
+ * another size or jpt_destroy): jpt_get_workspace_bytes keeps reporting the renders' workspaces alone. */
 int jpt_set_memory_policy(jpt_ctx *ctx, int32_t renders_in_flight, uint64_t workspace_budget_bytes);
 int jpt_get_workspace_bytes(jpt_ctx *ctx, uint64_t *bytes_out);
 
@@ -508,6 +510,42 @@ int jpt_set_temporal_params(jpt_ctx *ctx, const void *render_parameters88);
 enum { JPT_OUTPUT_DEPTH = 1 };
 int jpt_set_outputs(jpt_ctx *ctx, uint32_t outputs);
 
+/* ---- spatial denoising of the accumulation (no reference counterpart; the reference lists a denoiser among its wanted features) --
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the running mean of the progressive accumulation, guided by
+ * first-hit position, normal and albedo images, as an explicit call: nothing runs unless the host asks, and without jpt_denoise
+ * every render, buffer and read-back is exactly what it is without this section.  The arithmetic is pinned in DESIGN.md section 2
+ * (gdpathtracing_amd/csrc/jpt_denoise.h; tests/np_denoise.py restates it bit for bit).
+ *
+ * jpt_denoise enqueues, on the context's stream, behind every render queued before it and ahead of those queued after it:
+ *   the guide pass   one un-jittered primary ray per pixel centre, with the camera, scene and sampler mode current at the call, over
+ *                    the arrays the wavefront kernels walk (whatever jpt_set_kernel says; it follows jpt_scene_refit_tlas and
+ *                    jpt_scene_update_mesh).  Closest hit = the smallest accepted Moller-Trumbore t, no reach or tie logic.
+ *                    position_t = (position, distance from the camera), normal = (shading normal, 0), albedo = (diffuse albedo +
+ *                    fresnel_0, 0), or (1, 1, 1, 0) on an emitter; a miss: (0, 0, 0, -1), 0, (1, 1, 1, 0).
+ *   `passes` filter passes, pass k with tap spacing 2^k, over (accum / frame_count) / max(albedo, 1/64), then the product with
+ *                    that albedo again (the denoised image, linear) and its display image unorm8(ACES(.)).
+ * It READS the accumulation and the frame count and writes only its own images (3 guides, 2 colour images, one rgba8 image: 84
+ * bytes per pixel, allocated at the first call at a resolution, freed by jpt_set_params with another size and by jpt_destroy):
+ * jpt_read_accum_f32 / _ldr_rgba8 / _depth_f32, the split read-back and every later render are bit for bit what they are without
+ * the call -- the accumulation goes on unbiased underneath, the denoised image is a view of it.
+ * JPT_E_STATE: no scene; no frame accumulated since the last reset; a denoising mode other than JPT_DENOISE_PROGRESSIVE; the
+ * DEBUG_STEPS mode; a screen partition (whole image on one context, as JPT_DENOISE_TEMPORAL); jpt_read_denoised_* /
+ * jpt_read_guides_f32 before a jpt_denoise at the current resolution.  Host-only contexts: JPT_E_DEVICE.
+ * The parameters are the context's (like jpt_set_params'): they survive scene changes, each jpt_denoise takes them by value,
+ * jpt_scene_share does not copy them.  JPT_E_INVALID outside the ranges below or for a non-finite sigma. */
+typedef struct jpt_denoise_params {
+    int32_t passes;             /* 1..6, default 5: pass k uses tap spacing 2^k */
+    int32_t normal_power_log2;  /* 0..8, default 6: the normal weight max(0, n.n') is squared this many times */
+    float   sigma_plane;        /* > 0, default 0.02: tolerated distance from the centre's tangent plane, relative to its hit distance */
+    float   sigma_color;        /* > 0, default 4.0: colour tolerance in units of the demodulated mean; halves every pass */
+} jpt_denoise_params;
+int jpt_set_denoise_params(jpt_ctx *ctx, const jpt_denoise_params *params);   /* NULL: the defaults */
+int jpt_denoise(jpt_ctx *ctx);
+/* The read-backs wait for the work queued on the context, through its pinned staging buffer like the other jpt_read_*. */
+int jpt_read_denoised_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats (r, g, b, 1), linear */
+int jpt_read_denoised_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes: unorm8(ACES(denoised)), alpha 255 */
+int jpt_read_guides_f32(jpt_ctx *ctx, float *position_t, float *normal, float *albedo);   /* each W*H*4 floats, or NULL */
+
 /* ---- outputs ---------------------------------------------------------------------------------- */
 
 /* replaces: cs->get_image_uniform_buffer(output_texture_rid) (path_tracing_camera.cpp:228-229):
@@ -646,6 +684,12 @@ int jpt_debug_light_sample(jpt_ctx *ctx, const float *xi4, const float *origins3
                            float *pdf_out);
 int jpt_debug_light_pdf(jpt_ctx *ctx, const uint32_t *inst, const uint32_t *tri, const float *points3, const float *origins3,
                         const float *dirs3, uint32_t n, float *pdf_out);
+/* The filter of jpt_denoise alone, on caller-made images of width x height pixels, 4 floats per pixel each: mean4 = (mean r, g, b,
+ * unused), the three guide images as jpt_read_guides_f32 lays them out, out = the denoised image (r, g, b, 1).  params NULL: the
+ * defaults; checked as jpt_set_denoise_params checks them (JPT_E_INVALID; this call leaves no message).  device_id >= 0: the
+ * kernels jpt_denoise launches, on that device; JPT_DEVICE_HOST_ONLY: the same weight function compiled for the host. */
+int jpt_debug_atrous(int device_id, int32_t width, int32_t height, const jpt_denoise_params *params, const float *mean4,
+                     const float *position_t, const float *normal, const float *albedo, float *out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

@@ -758,6 +758,17 @@ class PathTracingCamera {
     void set_environment_sampling(int32_t mode) { check(ctx, jpt_set_environment_sampling(ctx, mode), "jpt_set_environment_sampling"); }
     // jpt_set_light_sampling: JPT_LIGHT_SAMPLING_BRDF (default) or JPT_LIGHT_SAMPLING_MIS (shadow rays towards emitter samples)
     void set_light_sampling(int32_t mode) { check(ctx, jpt_set_light_sampling(ctx, mode), "jpt_set_light_sampling"); }
+    // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
+    void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
+    void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
+    PackedByteArray read_denoised_ldr()
+    {
+        PackedByteArray out((size_t)width * height * 4);
+        check(ctx, jpt_read_denoised_rgba8(ctx, out.data()), "jpt_read_denoised_rgba8");
+        return out;
+    }
+    void read_denoised(float* out) { check(ctx, jpt_read_denoised_f32(ctx, out), "jpt_read_denoised_f32"); }
+    void read_guides(float* position_t, float* normal, float* albedo) { check(ctx, jpt_read_guides_f32(ctx, position_t, normal, albedo), "jpt_read_guides_f32"); }
 
     int max_bounces = 4;                    // the literal 5 of main.glsl:377 is max_bounces + 1
     int accum_mode = JPT_ACCUM_REF_LDR8;    // what the reference does (rgba8 screen image before the sum)
@@ -774,12 +785,17 @@ class PathTracingCamera {
         ready = true;
     }
 
-    // path_tracing_camera.cpp:193-232: one frame; returns the RGBA8 screen image (get_image_uniform_buffer)
-    PackedByteArray render()
+    // path_tracing_camera.cpp:193-232: one frame; returns the RGBA8 screen image (get_image_uniform_buffer).  with_denoise: the
+    // screen is jpt_denoise's view of the accumulation (progressive mode; no reference counterpart)
+    PackedByteArray render(bool with_denoise = false)
     {
         if (!ready) return {};                                                      // :195
         advance_frame();
         check(ctx, jpt_render(ctx, 1, camera.frame_index), "jpt_render");           // :204 + the post-processing pass
+        if (with_denoise) {
+            denoise();
+            return read_denoised_ldr();
+        }
         PackedByteArray out((size_t)width * height * 4);
         check(ctx, jpt_read_ldr_rgba8(ctx, out.data()), "jpt_read_ldr_rgba8");      // :228-229
         return out;
