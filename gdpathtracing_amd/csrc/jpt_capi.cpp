@@ -1,322 +1,22 @@
 // jpt_capi.cpp -- the C ABI of include/jpt.h over the HIP kernels and the host builder.
-#include "../../include/jpt.h"
-
-#include <hip/hip_runtime.h>
+#include "jpt_ctx.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
-#include "jpt_builder.h"
-#include "jpt_denoise.h"
-#include "jpt_kernels.h"
 #include "jpt_instance_math.h"
 #include "jpt_mesh_math.h"
 #include "jpt_tuning.h"
 
-using namespace jpt;
-
 namespace {
 
 thread_local std::string g_create_error;
-
-template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    ~DevBuf() { release(); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-    hipError_t resize(size_t count)
-    {
-        if (count == n && (p || count == 0)) return hipSuccess;
-        release();
-        if (count == 0) return hipSuccess;
-        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
-        if (e == hipSuccess) n = count;
-        return e;
-    }
-    hipError_t upload(const std::vector<T>& v, hipStream_t s)
-    {
-        hipError_t e = resize(v.size());
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
-    }
-};
-
-// A grow-only pinned host buffer (hipHostMalloc), given back by its destructor or release()
-struct PinnedBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    ~PinnedBuf() { release(); }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    hipError_t reserve(size_t want)
-    {
-        if (bytes >= want) return hipSuccess;
-        release();
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = want;
-        return e;
-    }
-    template <typename T>
-    T* as() const { return static_cast<T*>(p); }
-};
-
-// A ring of pinned staging buffers, so that the host can queue device refits ahead of the device: a stage is written again once
-// the work that last read it has run (its `copied` event)
-constexpr int kRefitStages = 4;   // refits the host may queue before it has to wait for a copy to leave its buffer
-struct StagingRing {
-    PinnedBuf buf[kRefitStages];
-    hipEvent_t copied[kRefitStages] = {};
-    uint64_t seq = 0;
-    ~StagingRing()
-    {
-        for (hipEvent_t e : copied)
-            if (e) (void)hipEventDestroy(e);
-    }
-    // the next stage, of at least `bytes`, once the work that used it last has run
-    hipError_t next(size_t bytes, int& st)
-    {
-        st = (int)(seq++ % (uint64_t)kRefitStages);
-        hipError_t e = copied[st] ? hipEventSynchronize(copied[st]) : hipEventCreateWithFlags(&copied[st], hipEventDisableTiming);
-        return e == hipSuccess ? buf[st].reserve(bytes) : e;
-    }
-};
-
-// Several copies of the instance level (RefInstance + WideInstance arrays, TLAS tail of the four-child records): a refit writes a
-// copy the renders in flight do NOT read, so the renders after a refit overlap with the renders before it.
-constexpr int kInstanceSets = 8;   // as many as renders in flight can be: a queue of animation steps stays pipelined
-
-// Every scene array on the device; the view the kernels take (jpt_ctx::ds) points into these (set_scene_view)
-struct SceneBufs {
-    // reference layout
-    DevBuf<RefTriGeometry> tri_geom;
-    DevBuf<ShadeTri> shade_tris;
-    DevBuf<RefMaterial> materials;
-    DevBuf<RefBvhNode> bvh;
-    DevBuf<RefTlasNode> tlas;
-    DevBuf<uint8_t> tex;
-    // flattened layout
-    DevBuf<WideNode> wblas, wtlas;
-    DevBuf<WideTri> wtris;
-    DevBuf<WideInstance> winst;
-    DevBuf<WideNode4> nodes4;   // four-child records: BLAS part, then one TLAS tail per copy of the instance level (one index space)
-    DevBuf<WideNodeQ> nodesq;   // their quantised form (jpt_nodeq.h), same indices: what the kernels walk
-    // the instance level, one copy per kInstanceSets; copy 0 is the one uploads write (the reach records: JPT_BUILD_SAH)
-    struct InstanceSet {
-        DevBuf<RefInstance> inst;
-        DevBuf<WideInstance> winst4;
-        DevBuf<ReachInst> reach;
-    } set[kInstanceSets];
-    DevBuf<ReachTri> reach_tri;   // reach records per triangle
-    DevBuf<float> cut_boxes;      // RefScene::inst_cut_boxes / inst_cut_range (device refits)
-    DevBuf<uint32_t> cut_range;
-    // the reference's own trees beside a native scene (ExactShadow): two-child records + the triangle map
-    DevBuf<RefBvhNode> x_bvh;
-    DevBuf<RefTriGeometry> x_tri_geom;
-    DevBuf<RefInstance> x_inst;
-    DevBuf<RefTlasNode> x_tlas;
-    DevBuf<uint32_t> x_tri_native, x_native_ref, x_tri_leaf, x_subtree_end, x_tlas_parent, x_inst_leaf;
-};
-
-// One render in flight (jpt_render_async): its stream, its workspace and the events that order it.  Slot 0's workspace is
-// also the one renders on the context's own stream use.
-struct PipeSlot {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_paths_done = nullptr, ev_acc_done = nullptr;
-    bool acc_done_valid = false;   // ev_acc_done follows the last accumulation that read `workspace`
-    uint64_t refit_seen = 0;       // the refit (jpt_ctx::refit_wait_seq) the slot's stream has last waited for
-    DevBuf<char> workspace;
-};
-
-}  // namespace
-
-struct jpt_ctx {
-    int device = 0;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Wf2Streams group_streams;  // helper streams / events of the frame groups (launch_wf2_render)
-    std::string error;
-
-    // host scene
-    SceneBuilder builder;
-    RefScene ref;
-    WideScene wide;
-    bool building = false, scene_ready = false, tlas_dirty = false;
-    int32_t tree = JPT_TREE_NONE;   // the JPT_TREE_* of the scene in c->ref (jpt_scene_tree_kind answers it once host_scene_ready)
-    bool host_scene_ready = false;  // c->ref / c->wide hold a complete scene (also true on host-only contexts)
-    bool from_commit = false;       // the scene came from jpt_scene_commit: c->builder holds its meshes and transforms
-    int32_t upload_mode = JPT_UPLOAD_NATIVE_TREE;  // jpt_set_upload_mode
-    int32_t slot_priority = JPT_STREAM_PRIORITY_DEFAULT;  // jpt_set_stream_priority
-    int32_t max_slots = 0;              // jpt_set_memory_policy: renders in flight (0: the library's rule)
-    uint64_t workspace_budget = 0;      // ... and bytes per workspace (0: tuning().workspace_budget_mb)
-    std::string upload_note;        // why the last reference-layout upload is walked as given (empty: it is not)
-    std::string ties_note;          // why exact distance ties fall to the native tree's order (empty: they are decided exactly)
-    std::vector<RefMaterial> pending_materials;
-    std::vector<uint8_t> pending_tex;
-    int32_t pending_tex_res = 0, pending_layers = 0;
-
-    // device scene
-    SceneBufs dev;
-    DeviceScene ds;
-
-    // per-render state
-    bool params_set = false, camera_set = false;
-    int32_t width = 0, height = 0, max_bounces = 4, accum_mode = 0, sampler_mode = 0;
-    int32_t rank = 0, world = 1, local_rows = 0;
-    RefCamera camera;
-    uint32_t frame_count = 0;  // frames accumulated since reset
-    int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
-    bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
-    uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
-    bool depth_valid = false;              // d_depth holds the last render's depth image
-    // render pipelining (jpt_render_async): consecutive asynchronous renders run their path kernels on the slots' streams
-    // with their own workspaces, so one render's launch tails overlap the next render's kernels; the accumulation
-    // kernels are ordered on the context's stream
-    static constexpr int kPipeSlots = 8;   // the most; the rule is 4, or 6 where six of the slots' streams run side by side (six_queues_probe)
-    PipeSlot slot[kPipeSlots];
-    int six_queues = -1;                   // -1: not probed yet; 0 / 1
-    int last_pipe_slots = 0;               // jpt_renders_in_flight
-    bool aux_borrowed[kMaxGroups - 1] = {};   // group_streams.aux_stream[k] is slot[k].stream (ensure_group_streams): not destroyed on its own
-    uint64_t async_seq = 0;
-    std::vector<uint32_t> h_qcount;  // per-bounce queue sizes of the last wavefront render
-    std::vector<hipEvent_t> trace_events;  // pairs around each wf_trace launch of the last render
-    int32_t trace_events_used = 0;
-    bool kernel_timing = false;
-
-    // framebuffers (local rows of this partition)
-    DevBuf<float4> d_accum;
-    DevBuf<uint32_t> d_ldr;
-    DevBuf<float> d_depth;
-    DevBuf<DevCounters> d_counters;
-    // the tiles' sky cells (launch_sky_tiles): a function of the camera, the image size and the partition -- made when one of them
-    // changes, read by every accumulation until then
-    DevBuf<uint32_t> d_sky_tiles;
-    RefCamera sky_tiles_camera;
-    int32_t sky_tiles_key[5] = {0, 0, 0, 0, 0};   // width, height, local_rows, rank, world
-    bool sky_tiles_valid = false;
-    // assembled full image on the gathering rank
-    DevBuf<float4> d_full_accum;
-    DevBuf<uint32_t> d_full_ldr;
-    bool assembled = false;      // d_full_accum + d_full_ldr hold the whole image (jpt_assemble_from_ranks)
-    bool assembled_ldr = false;  // d_full_ldr only (jpt_assemble_ldr_from_ranks)
-
-    // post-processing mode (PathTracingCamera::Denoising) and the temporal pass's state
-    int32_t denoise = JPT_DENOISE_PROGRESSIVE;
-    RefTemporalParams temporal;
-    bool temporal_set = false, hist_valid = false;
-    DevBuf<float4> d_hist1, d_hist2;   // frameBuffer1 / frameBuffer2 of temporal_reprojection.glsl:16-17
-    float4* hist_written = nullptr;    // the one the last temporal pass wrote
-
-    // device refit of the instance level (jpt_scene_refit_tlas)
-    StagingRing refit_stage;           // pinned staging for the transforms
-    size_t tlas4_cap = 0;              // records reserved per TLAS tail
-    int cur_set = 0;                   // which copy new renders read
-    bool set_b_ready = false;          // copies 1.. exist and mirror the last host upload
-    hipStream_t refit_stream = nullptr;
-    hipEvent_t ev_set_retired[kInstanceSets] = {}, ev_refit_done = nullptr;
-    bool set_retired_valid[kInstanceSets] = {};
-    uint64_t refit_wait_seq = 0;
-    int idle_streak = 0;   // queued renders in a row that found nothing in flight (plan_launch)
-    DevBuf<uint32_t> d_tlas4_order, d_tlas4_levels;
-    uint32_t n_tlas4_levels = 0;
-    bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
-    bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
-    std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
-    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in dev.nodes4 and its schedule
-    // (refit4_schedule), made at the first update after an upload
-    struct MeshRefit {
-        bool has_tree = false;              // an instance names the mesh and it has triangles: the device holds its tree
-        int32_t root4 = 0;                  // its root reference in dev.nodes4
-        uint32_t bvh_root = 0;              // its root in dev.bvh (RefScene::mesh_roots)
-        uint32_t tri_first = 0, n_tris = 0;
-        uint32_t rec_first = 0, n_recs = 0;  // the span of dev.nodes4 its records occupy
-        uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
-    };
-    std::vector<MeshRefit> mesh_refit;
-    bool mesh_refit_ready = false;
-    std::vector<uint32_t> mesh_order_h, mesh_levels_h;
-    DevBuf<uint32_t> d_mesh_order, d_mesh_levels, d_tri_vidx;
-    DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
-    StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
-    hipEvent_t ev_mesh_drain = nullptr;
-    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
-    PinnedBuf h_ldr_pinned;    // the split read-back of the display image
-    PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
-    hipEvent_t ev_readback = nullptr;
-    bool readback_pending = false;
-    bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
-
-    // the environment map (jpt_set_environment): the context's, like its params; the renders pass env_view by value
-    DevBuf<float4> d_env;
-    bool env_set = false;
-    int32_t env_w = 0, env_h = 0;
-    float env_rot[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    float env_intensity = 1.0f;
-    EnvDev env_view;
-    // its importance sampling (jpt_set_environment_sampling): the mode, also the context's, and the map's tables -- built once per
-    // map while the mode is JPT_ENV_SAMPLING_MIS, then kept until the map changes
-    int32_t env_sampling = JPT_ENV_SAMPLING_BRDF;
-    DevBuf<float> d_env_cond, d_env_marg;   // h rows of w conditional CDF entries; the marginal CDF's h entries, then the total
-    bool env_tables = false;
-    float env_total = 0.0f;
-    EnvSampDev env_samp_view;
-    // importance sampling of the emissive triangles (jpt_set_light_sampling): the mode, the context's like the map's; the emitters
-    // (instance, triangle pairs from c->ref, host) and their device tables -- both made at the first render that needs them after
-    // the scene changed (light_cand_stale: its instances or materials; light_table_stale: also its geometry, refits included)
-    int32_t light_sampling = JPT_LIGHT_SAMPLING_BRDF;
-    std::vector<uint32_t> light_cand_h;
-    bool light_cand_stale = true, light_cand_uploaded = false, light_table_stale = true;
-    DevBuf<uint32_t> d_light_cand;
-    DevBuf<float4> d_light_tri;
-    DevBuf<float> d_light_cdf, d_light_marg;   // per emitter; the marginal CDF's n_blocks entries, then the total power
-    LightDev light_view;
-
-    // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
-    // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution
-    AtrousParams dn_params;
-    DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
-    DevBuf<uint32_t> d_dn_ldr;
-    bool dn_valid = false;
-
-    jpt_stats stats;
-};
-
-namespace {
-
-void lights_stale(jpt_ctx* c, bool listed);
-
-int fail(jpt_ctx* c, int code, const std::string& msg)
-{
-    if (c) c->error = msg;
-    return code;
-}
-
-int hip_fail(jpt_ctx* c, hipError_t e, const char* what)
-{
-    return fail(c, JPT_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(c, expr)                                          \
-    do {                                                          \
-        hipError_t e_ = (expr);                                   \
-        if (e_ != hipSuccess) return hip_fail((c), e_, #expr);    \
-    } while (0)
 
 int32_t rows_of_rank(int32_t height, int32_t rank, int32_t world)
 {
@@ -726,26 +426,12 @@ void compute_sky_cull(const jpt_ctx* c, SkyCull& out)
 
 int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking);
 
-// does a render of `c` now take the MIS kernels (and their workspace)?
-bool env_mis_render(const jpt_ctx* c)
-{
-    return c->env_sampling == JPT_ENV_SAMPLING_MIS && c->env_set && c->env_tables && c->env_total > 0.0f && !c->debug_steps;
-}
-
-// will a render of `c` take the light-sampling kernels?  (Before the emitter list is made: yes if the mode asks for them -- a bound
-// for sizing only; light_render decides.)
-bool light_render_bound(const jpt_ctx* c)
-{
-    return c->light_sampling == JPT_LIGHT_SAMPLING_MIS && !c->debug_steps && c->device >= 0 && c->scene_ready &&
-           (c->light_cand_stale || !c->light_cand_h.empty());
-}
-
 // frames of one wavefront render that fit the workspace budget (all frames of a batch are in flight at once)
 int32_t frames_per_batch(const jpt_ctx* c, int32_t n_frames)
 {
     const size_t budget = c->workspace_budget ? (size_t)c->workspace_budget : (size_t)tuning().workspace_budget_mb << 20;
     if (c->kernel_variant == JPT_KERNEL_REFERENCE_LAYOUT || c->debug_steps || n_frames <= 1) return n_frames;
-    const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c), light_render_bound(c));
+    const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, lighting_bound(c));
     const size_t fit = std::max<size_t>(1, budget / std::max<size_t>(one, 1));
     return (int32_t)std::min<size_t>((size_t)n_frames, fit);
 }
@@ -773,7 +459,7 @@ int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool cou
         return do_render_batch(c, n_frames, first_frame_index, counted, blocking);  // reports the error / no-op
     // a budget the caller set is a cap, not a hint: one frame is the smallest batch there is
     if (c->workspace_budget && c->kernel_variant != JPT_KERNEL_REFERENCE_LAYOUT && !c->debug_steps) {
-        const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, env_mis_render(c), light_render_bound(c));
+        const size_t one = wf2_workspace_bytes(c->width, c->local_rows, 1, c->max_bounces, lighting_bound(c));
         if (one > c->workspace_budget)
             return fail(c, JPT_E_LIMIT, "jpt_set_memory_policy: one frame of this resolution needs a workspace of " + std::to_string(one) +
                                             " bytes, the budget is " + std::to_string(c->workspace_budget) +
@@ -940,8 +626,8 @@ struct PlanDevice {
 const PlanDevice kPlanDevice{six_queues_probe, pipeline_idle, ensure_pipe_slot, ensure_group_streams};
 
 // Every rule of a render's launch shape, in one place.  Makes no HIP call of its own; keeps c->last_pipe_slots and
-// c->idle_streak.  fp: the render's frame_params; cull: its sky cull.
-LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, bool counted, bool blocking, const PlanDevice& dev)
+// c->idle_streak.  fp: the render's frame_params; r: its sky cull and lighting.
+LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const Wf2Render& r, bool counted, bool blocking, const PlanDevice& dev)
 {
     LaunchPlan p;
     if (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps) return p;   // (DEBUG_STEPS exists in the audit kernel only)
@@ -955,7 +641,7 @@ LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, b
     // launches on every size tried: C3 1.32 vs 1.45 ms, C2 0.36 vs 0.46, 1 frame 0.30 vs 0.37, 1920x136 0.185 vs
     // 0.193, 4K x 16 spp 11.1 vs 11.1.  Renders whose workspace exceeds 24 GiB keep two slots and full-width launches
     // (4 x 24 GiB of workspaces is where this stops).
-    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, env_mis_render(c), light_render_bound(c)) > ((size_t)24 << 30);
+    const bool huge = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, r.lighting) > ((size_t)24 << 30);
     // ... six where the slots' streams have six hardware queues to themselves (six_queues_probe), four otherwise
     const bool may_queue = tuning().pipelining && !blocking && !counted;
     const int slots = forced_slots ? forced_slots : (huge ? 2 : ((may_queue && dev.six_queues(c)) ? 6 : 4));
@@ -1008,7 +694,7 @@ LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const SkyCull& cull, b
     // 0.673 -> 0.648).  Not for windows of millions of paths (C3 in one group: 1.39 -> 1.51 ms) nor for scenes
     // past the caches, which are bound by the latency of their fetches and want every wave they can get (1 M
     // triangles, 2 spp: 9.49 -> 9.93 ms): one segment per block (profiles/r03/r03ao_lone_chain.txt).
-    const uint64_t window_paths = ((uint64_t)c->width * (uint64_t)c->local_rows - wf2_pixels_outside_window(cull, fp)) * (uint64_t)fp.n_frames;
+    const uint64_t window_paths = ((uint64_t)c->width * (uint64_t)c->local_rows - wf2_pixels_outside_window(r.cull, fp)) * (uint64_t)fp.n_frames;
     const size_t walked_bytes = c->wide.blas_nodes4.size() * sizeof(WideNodeQ) + c->wide.tris.size() * sizeof(WideTri);
     const bool small = window_paths <= 1500000u && walked_bytes <= ((size_t)32 << 20);
     p.chain = (p.groups == 2 || (walks_nodes4(c) && small)) ? 2 : 1;
@@ -1053,163 +739,12 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     return JPT_OK;
 }
 
-// the map's sampling tables the renders of `c` take, or null: BRDF sampling alone (JPT_ENV_SAMPLING_BRDF, no map, or a black map,
-// whose MIS render is the BRDF-mode render: no map samples, every weight 1).  A view, valid until the next call.
-const EnvSampDev* env_sampling_of(jpt_ctx* c)
-{
-    if (!env_mis_render(c)) return nullptr;
-    c->env_samp_view.cond = c->d_env_cond.p;
-    c->env_samp_view.marg = c->d_env_marg.p;
-    c->env_samp_view.total = c->env_total;
-    return &c->env_samp_view;
-}
-
-// The scene changed: the emitter tables are rebuilt at the next render that samples them -- and the emitter list too when the
-// instances or materials may have changed (`listed`); a refit or a mesh update moves the geometry only.  Costs nothing else.
-void lights_stale(jpt_ctx* c, bool listed)
-{
-    c->light_table_stale = true;
-    if (listed) c->light_cand_stale = true;
-}
-
-// The emitters of c->ref, instance-major, each instance's triangles (the leaves under its BLAS root, each triangle once) in
-// ascending index: those whose Le (light_emission) has lum(Le) > 0.  True when there is one.
-bool light_candidates(jpt_ctx* c)
-{
-    if (!c->light_cand_stale) return !c->light_cand_h.empty();
-    const RefScene& r = c->ref;
-    c->light_cand_h.clear();
-    c->light_cand_stale = false;
-    c->light_cand_uploaded = false;
-    if (r.materials.empty()) return false;
-    std::vector<uint32_t> tris, stack;
-    std::vector<char> emits(r.materials.size(), 0);
-    bool any = false;
-    for (size_t m = 0; m < r.materials.size(); m++) {   // (a scene none of whose materials emits has no emitter: no walk)
-        const Vec4& e = r.materials[m].emission;
-        const float em = e.w > 0.0f ? e.w : 0.0f;
-        emits[m] = light_lum(e.x * em, e.y * em, e.z * em) > 0.0f;
-        any = any || emits[m];
-    }
-    if (!any) return false;
-    const uint32_t n_inst = (uint32_t)r.instances.size(), n_nodes = (uint32_t)r.bvh_nodes.size();
-    uint32_t cached_root = 0xffffffffu;
-    for (uint32_t i = 0; i < n_inst; i++) {
-        const uint32_t root = r.instances[i].blas_index;
-        if (root != cached_root) {
-            tris.clear();
-            stack.assign(1, root);
-            size_t visits = 0;
-            while (!stack.empty() && visits++ <= n_nodes) {
-                const uint32_t k = stack.back();
-                stack.pop_back();
-                if (k >= n_nodes) continue;
-                const RefBvhNode& nd = r.bvh_nodes[k];
-                if (nd.tri_count > 0) {
-                    for (uint32_t t = 0; t < nd.tri_count; t++)
-                        if ((size_t)nd.first_tri_index + t < r.tri_data.size()) tris.push_back(nd.first_tri_index + t);
-                } else {
-                    stack.push_back(nd.right_child);
-                    stack.push_back(nd.left_child);
-                }
-            }
-            std::sort(tris.begin(), tris.end());
-            tris.erase(std::unique(tris.begin(), tris.end()), tris.end());
-            cached_root = root;
-        }
-        for (const uint32_t t : tris) {
-            float le[3];
-            light_emission(r.instances.data(), n_inst, r.materials.data(), (uint32_t)r.materials.size(), i, r.tri_data[t].material_index, le);
-            if (light_lum(le[0], le[1], le[2]) > 0.0f) {
-                c->light_cand_h.push_back(i);
-                c->light_cand_h.push_back(t);
-            }
-        }
-    }
-    return !c->light_cand_h.empty();
-}
-
-// does a render of `c` now take the light-sampling kernels (and their workspace)?
-bool light_render(jpt_ctx* c)
-{
-    return c->light_sampling == JPT_LIGHT_SAMPLING_MIS && !c->debug_steps && c->device >= 0 && c->scene_ready && light_candidates(c);
-}
-
-// The emitter tables, built on the context's stream when stale: after every render queued so far (each ends with work there), so
-// no render in flight reads them while they change; the next render of every slot waits for the context's stream.
-int ensure_light_tables(jpt_ctx* c)
-{
-    if (!c->light_table_stale && c->light_cand_uploaded) return JPT_OK;
-    hipStream_t s = c->stream;
-    const uint32_t n = (uint32_t)(c->light_cand_h.size() / 2), nb = (n + kLightBlock - 1) / kLightBlock;
-    if (c->d_light_tri.n != 3 * (size_t)n || c->d_light_marg.n != (size_t)nb + 1 || !c->light_cand_uploaded)
-        HIP_TRY(c, hipStreamSynchronize(s));   // (buffers of another size: renders in flight may read the old ones)
-    if (!c->light_cand_uploaded) {
-        HIP_TRY(c, c->d_light_cand.upload(c->light_cand_h, s));
-        c->light_cand_uploaded = true;
-    }
-    HIP_TRY(c, c->d_light_tri.resize(3 * (size_t)n));
-    HIP_TRY(c, c->d_light_cdf.resize(n));
-    HIP_TRY(c, c->d_light_marg.resize((size_t)nb + 1));
-    LightBuildArgs a;
-    a.cand = c->d_light_cand.p;
-    a.n = n;
-    a.n_blocks = nb;
-    a.instances = c->ds.ref_instances;
-    a.n_instances = c->ds.n_instances;
-    a.n_materials = c->ds.n_materials;
-    a.materials = c->ds.ref_materials;
-    a.wtris = c->ds.wide_tris;
-    a.shade = c->ds.shade_tris;
-    a.tri = c->d_light_tri.p;
-    a.cdf = c->d_light_cdf.p;
-    a.marg = c->d_light_marg.p;
-    launch_light_tables(s, a);
-    HIP_TRY(c, hipGetLastError());
-    for (PipeSlot& ps : c->slot) ps.acc_done_valid = false;
-    c->light_table_stale = false;
-    return JPT_OK;
-}
-
-// the emitter tables the renders of `c` take, or null (BRDF sampling alone); made if stale.  A view, valid until the next call.
-const LightDev* lights_of(jpt_ctx* c, int& rc)
-{
-    rc = JPT_OK;
-    if (!light_render(c)) return nullptr;
-    rc = ensure_light_tables(c);
-    if (rc != JPT_OK) return nullptr;
-    LightDev& v = c->light_view;
-    v.tri = c->d_light_tri.p;
-    v.cdf = c->d_light_cdf.p;
-    v.marg = c->d_light_marg.p;
-    v.wtris = c->ds.wide_tris;
-    v.n = (uint32_t)(c->light_cand_h.size() / 2);
-    v.n_blocks = (v.n + kLightBlock - 1) / kLightBlock;
-    return &v;
-}
-
-// the environment map the renders of `c` see, or null (sample_sky); a view of the context's own copy, valid until the next call
-const EnvDev* environment_of(jpt_ctx* c)
-{
-    if (!c->env_set) return nullptr;
-    EnvDev& e = c->env_view;
-    e.texels = c->d_env.p;
-    e.w = c->env_w;
-    e.h = c->env_h;
-    std::memcpy(e.rot, c->env_rot, sizeof e.rot);
-    e.intensity = c->env_intensity;
-    return &e;
-}
-
 // What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
-// stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.
+// stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.  r.lighting is the render's.
 int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefront, Wf2Render& r)
 {
     hipStream_t s = c->stream;
     const int32_t n_frames = fp.n_frames;
-    int lrc = JPT_OK;
-    r.lights = lights_of(c, lrc);   // (the emitter tables, made here if stale: on `s`, before the render)
-    if (lrc != JPT_OK) return lrc;
     if (c->denoise == JPT_DENOISE_TEMPORAL) {
         // the pass runs once per displayed frame and reads other pixels' depth and history (temporal_reprojection.glsl:57-61)
         if (n_frames > 1) return fail(c, JPT_E_INVALID, "temporal reprojection renders one frame per call");
@@ -1234,7 +769,7 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     if (counted) HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(DevCounters), s));
     const bool wf2 = wavefront && c->local_rows > 0 && c->width > 0 && n_frames > 0;
     if (wf2) {
-        const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces, env_mis_render(c), r.lights != nullptr);
+        const size_t need = wf2_workspace_bytes(c->width, c->local_rows, n_frames, c->max_bounces, r.lighting);
         if (c->slot[0].workspace.n < need) {
             HIP_TRY(c, hipStreamSynchronize(s));
             HIP_TRY(c, c->slot[0].workspace.resize(need));
@@ -1250,12 +785,10 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     }
     c->trace_events_used = (int32_t)need_ev;
     compute_sky_cull(c, r.cull);
-    r.env = environment_of(c);
-    r.env_samp = r.env ? env_sampling_of(c) : nullptr;
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
     // (With an environment map the accumulation makes up culled pixels exactly, frame by frame: the cells bound the gradient only.)
-    if (c->accum_mode == JPT_ACCUM_REF_LDR8 && n_frames > 1 && !r.env) {
+    if (c->accum_mode == JPT_ACCUM_REF_LDR8 && n_frames > 1 && r.lighting.env_mode == 0) {
         const int32_t key[5] = {c->width, c->height, c->local_rows, c->rank, c->world};
         RefCamera cam_key = c->camera;
         cam_key.frame_index = 0;
@@ -1289,8 +822,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, c->debug_steps ? nullptr : environment_of(c),
-                             c->debug_steps ? nullptr : env_sampling_of(c), c->debug_steps ? nullptr : r.lights);
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting);
         }
         return JPT_OK;
     }
@@ -1301,7 +833,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
     }
     // a queued render: path kernels and accumulation on the slot's stream with the slot's workspace
     PipeSlot& ps = c->slot[p.slot];
-    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, r.env_samp != nullptr, r.lights != nullptr);
+    const size_t need = wf2_workspace_bytes(c->width, c->local_rows, fp.n_frames, c->max_bounces, r.lighting);
     bool slots_ready = true;
     for (int k = 0; k < p.slots; k++) slots_ready = slots_ready && c->slot[k].stream && c->slot[k].workspace.n >= need;
     if (!slots_ready) {
@@ -1398,11 +930,12 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
     const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
     Wf2Render r;
+    if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
     if (c->local_rows > 0 && c->width > 0 && n_frames > 0) {
         c->depth_valid = want_depth;
-        const LaunchPlan p = plan_launch(c, fp, r.cull, counted, blocking, kPlanDevice);
+        const LaunchPlan p = plan_launch(c, fp, r, counted, blocking, kPlanDevice);
         rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->d_depth.p : nullptr);
         if (rc != JPT_OK) return rc;
         pipelined = p.route == LaunchPlan::kSlot;
@@ -2209,106 +1742,6 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     return JPT_OK;
 }
 
-// the emitter tables for the jpt_debug_light_* entries, whatever the mode: made if stale; null when the scene has no emitter
-static int debug_lights(jpt_ctx* c, const LightDev*& out)
-{
-    out = nullptr;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the emitter tables are on the device");
-    if (!c->scene_ready) return fail(c, JPT_E_STATE, "no scene");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!light_candidates(c)) return JPT_OK;
-    const int32_t mode = c->light_sampling;
-    const bool dbg = c->debug_steps;
-    c->light_sampling = JPT_LIGHT_SAMPLING_MIS;
-    c->debug_steps = false;
-    int rc = JPT_OK;
-    out = lights_of(c, rc);
-    c->light_sampling = mode;
-    c->debug_steps = dbg;
-    if (rc == JPT_OK) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return rc;
-}
-
-int jpt_debug_light_tables(jpt_ctx* c, uint32_t capacity, uint32_t* n_out, uint32_t* pairs_out, float* tri_out, float* cdf_out, float* marg_out)
-{
-    if (!c || !n_out) return JPT_E_INVALID;
-    const LightDev* lt = nullptr;
-    const int rc = debug_lights(c, lt);
-    if (rc != JPT_OK) return rc;
-    n_out[0] = lt ? lt->n : 0u;
-    n_out[1] = lt ? lt->n_blocks : 0u;
-    if (!lt || capacity < lt->n) return JPT_OK;
-    if (pairs_out) std::memcpy(pairs_out, c->light_cand_h.data(), (size_t)lt->n * 2 * sizeof(uint32_t));
-    if (tri_out) HIP_TRY(c, hipMemcpy(tri_out, lt->tri, (size_t)lt->n * 3 * sizeof(float4), hipMemcpyDeviceToHost));
-    if (cdf_out) HIP_TRY(c, hipMemcpy(cdf_out, lt->cdf, (size_t)lt->n * sizeof(float), hipMemcpyDeviceToHost));
-    if (marg_out) HIP_TRY(c, hipMemcpy(marg_out, lt->marg, ((size_t)lt->n_blocks + 1) * sizeof(float), hipMemcpyDeviceToHost));
-    return JPT_OK;
-}
-
-static int light_probe_call(jpt_ctx* c, int what, const float* xi4, const uint32_t* inst, const uint32_t* tri, const float* points3,
-                            const float* origins3, const float* dirs3, uint32_t n, float* points_out, float* dirs_out, float* pdf_out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (n && (!origins3 || !pdf_out || (what == 1 && (!xi4 || !points_out || !dirs_out)) || (what == 2 && (!inst || !tri || !points3 || !dirs3))))
-        return fail(c, JPT_E_INVALID, "null argument");
-    const LightDev* lt = nullptr;
-    const int rc = debug_lights(c, lt);
-    if (rc != JPT_OK) return rc;
-    if (n == 0) return JPT_OK;
-    if (!lt) {   // no emitter: density 0 (and no sample)
-        for (uint32_t i = 0; i < n; i++) pdf_out[i] = 0.0f;
-        if (what == 1) {
-            std::memset(points_out, 0, (size_t)n * 3 * sizeof(float));
-            std::memset(dirs_out, 0, (size_t)n * 3 * sizeof(float));
-        }
-        return JPT_OK;
-    }
-    if (what == 2)
-        for (uint32_t i = 0; i < n; i++)
-            if (inst[i] >= c->ds.n_instances || tri[i] >= c->ds.n_tris) return fail(c, JPT_E_INVALID, "no such instance or triangle");
-    const size_t n3 = (size_t)n * 3;
-    DevBuf<float> d_in, d_o, d_d, d_p, d_po, d_do, d_pdf;
-    DevBuf<uint32_t> d_inst, d_tri;
-    HIP_TRY(c, d_o.resize(n3));
-    HIP_TRY(c, d_pdf.resize(n));
-    HIP_TRY(c, hipMemcpy(d_o.p, origins3, n3 * sizeof(float), hipMemcpyHostToDevice));
-    if (what == 1) {
-        HIP_TRY(c, d_in.resize((size_t)n * 4));
-        HIP_TRY(c, d_po.resize(n3));
-        HIP_TRY(c, d_do.resize(n3));
-        HIP_TRY(c, hipMemcpy(d_in.p, xi4, (size_t)n * 4 * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-        HIP_TRY(c, d_d.resize(n3));
-        HIP_TRY(c, d_p.resize(n3));
-        HIP_TRY(c, d_inst.resize(n));
-        HIP_TRY(c, d_tri.resize(n));
-        HIP_TRY(c, hipMemcpy(d_d.p, dirs3, n3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(d_p.p, points3, n3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(d_inst.p, inst, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(d_tri.p, tri, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    launch_light_probe(c->stream, *lt, c->ds.shading(), what, d_in.p, d_o.p, d_d.p, d_p.p, d_inst.p, d_tri.p, n, d_po.p, d_do.p, d_pdf.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(pdf_out, d_pdf.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
-    if (what == 1) {
-        HIP_TRY(c, hipMemcpy(points_out, d_po.p, n3 * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(dirs_out, d_do.p, n3 * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return JPT_OK;
-}
-
-int jpt_debug_light_sample(jpt_ctx* c, const float* xi4, const float* origins3, uint32_t n, float* points_out, float* dirs_out, float* pdf_out)
-{
-    return light_probe_call(c, 1, xi4, nullptr, nullptr, nullptr, origins3, nullptr, n, points_out, dirs_out, pdf_out);
-}
-
-int jpt_debug_light_pdf(jpt_ctx* c, const uint32_t* inst, const uint32_t* tri, const float* points3, const float* origins3, const float* dirs3,
-                        uint32_t n, float* pdf_out)
-{
-    return light_probe_call(c, 2, nullptr, inst, tri, points3, origins3, dirs3, n, nullptr, nullptr, pdf_out);
-}
-
 int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void* nodesq_out, uint32_t node_capacity, void* tris_out,
                            void* shade_out, uint32_t tri_capacity, int32_t* info_out)
 {
@@ -2470,155 +1903,6 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
     c->params_set = true;
     c->depth_valid = false;
     return alloc_framebuffers(c);
-}
-
-extern "C++" {
-namespace jpt {
-
-int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why)
-{
-    if (width <= 0 || height <= 0) {
-        why = "jpt_set_environment: width and height must be positive";
-        return JPT_E_INVALID;
-    }
-    if (width > kEnvMaxWidth || height > kEnvMaxHeight) {
-        why = "jpt_set_environment: the map is larger than 16384 x 8192 texels";
-        return JPT_E_LIMIT;
-    }
-    const size_t n = (size_t)width * (size_t)height * 3u;
-    for (size_t i = 0; i < n; i++) {
-        const float v = rgb[i];
-        if (!(v >= 0.0f) || !std::isfinite(v)) {
-            why = "jpt_set_environment: texel value " + std::to_string(i) + " is negative, infinite or NaN";
-            return JPT_E_INVALID;
-        }
-    }
-    return JPT_OK;
-}
-
-int check_env_params(const float* rotation9, float intensity, std::string& why)
-{
-    if (rotation9)
-        for (int k = 0; k < 9; k++)
-            if (!std::isfinite(rotation9[k])) {
-                why = "jpt_set_environment_params: the rotation has a non-finite entry";
-                return JPT_E_INVALID;
-            }
-    if (!std::isfinite(intensity) || !(intensity >= 0.0f)) {
-        why = "jpt_set_environment_params: the intensity must be finite and >= 0";
-        return JPT_E_INVALID;
-    }
-    return JPT_OK;
-}
-
-bool env_rotation_orthonormal(const float* r)
-{
-    for (int a = 0; a < 3; a++)
-        for (int b = 0; b < 3; b++) {
-            const double d = (double)r[3 * a] * r[3 * b] + (double)r[3 * a + 1] * r[3 * b + 1] + (double)r[3 * a + 2] * r[3 * b + 2];
-            if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= kEnvOrthoTol)) return false;
-        }
-    return true;
-}
-
-void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out)
-{
-    const size_t n = (size_t)width * (size_t)height;
-    out.resize(n);
-    for (size_t i = 0; i < n; i++) out[i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
-}
-
-}  // namespace jpt
-}  // extern "C++"
-
-static int build_env_tables(jpt_ctx* c);
-
-int jpt_set_environment(jpt_ctx* c, const float* rgb, int32_t width, int32_t height)
-{
-    if (!c) return JPT_E_INVALID;
-    std::string why;
-    if (rgb) {
-        const int rc = check_env_map(rgb, width, height, why);
-        if (rc != JPT_OK) return fail(c, rc, why);
-    }
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
-    HIP_TRY(c, hipSetDevice(c->device));
-    // the renders already queued read the old map: they finish first (every one of them ends with work on the context's stream)
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->env_tables = false;
-    c->d_env_cond.release();
-    c->d_env_marg.release();
-    if (!rgb) {
-        c->env_set = false;
-        c->d_env.release();
-        return JPT_OK;
-    }
-    std::vector<float4> texels;
-    pack_env_texels(rgb, width, height, texels);
-    c->env_set = false;
-    HIP_TRY(c, c->d_env.resize(texels.size()));
-    HIP_TRY(c, hipMemcpy(c->d_env.p, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice));
-    c->env_w = width;
-    c->env_h = height;
-    c->env_set = true;
-    if (c->env_sampling == JPT_ENV_SAMPLING_MIS) return build_env_tables(c);
-    return JPT_OK;
-}
-
-// the sampling tables of the context's map, on its stream (after the renders queued there: none of them reads the tables), and the
-// total weight read back -- the one wait of jpt_set_environment_sampling
-static int build_env_tables(jpt_ctx* c)
-{
-    const size_t w = (size_t)c->env_w, h = (size_t)c->env_h;
-    HIP_TRY(c, c->d_env_cond.resize(w * h));
-    HIP_TRY(c, c->d_env_marg.resize(h + 1));
-    launch_env_tables(c->stream, c->d_env.p, c->env_w, c->env_h, c->d_env_cond.p, c->d_env_marg.p, c->d_env_marg.p + h);
-    HIP_TRY(c, hipGetLastError());
-    float total = 0.0f;
-    HIP_TRY(c, hipMemcpyAsync(&total, c->d_env_marg.p + h, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->env_total = total;
-    c->env_tables = true;
-    return JPT_OK;
-}
-
-int jpt_set_environment_sampling(jpt_ctx* c, int32_t mode)
-{
-    if (!c) return JPT_E_INVALID;
-    if (mode != JPT_ENV_SAMPLING_BRDF && mode != JPT_ENV_SAMPLING_MIS) return fail(c, JPT_E_INVALID, "jpt_set_environment_sampling: unknown mode");
-    if (mode == JPT_ENV_SAMPLING_MIS && !env_rotation_orthonormal(c->env_rot))
-        return fail(c, JPT_E_INVALID, "jpt_set_environment_sampling: the map sampler needs an orthonormal rotation (jpt_set_environment_params)");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
-    c->env_sampling = mode;
-    if (mode == JPT_ENV_SAMPLING_MIS && c->env_set && !c->env_tables) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        return build_env_tables(c);
-    }
-    return JPT_OK;
-}
-
-int jpt_set_light_sampling(jpt_ctx* c, int32_t mode)
-{
-    if (!c) return JPT_E_INVALID;
-    if (mode != JPT_LIGHT_SAMPLING_BRDF && mode != JPT_LIGHT_SAMPLING_MIS) return fail(c, JPT_E_INVALID, "jpt_set_light_sampling: unknown mode");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: light sampling runs on the device");
-    c->light_sampling = mode;   // (the tables are made at the first render that samples them)
-    return JPT_OK;
-}
-
-int jpt_set_environment_params(jpt_ctx* c, const float* rotation9, float intensity)
-{
-    if (!c) return JPT_E_INVALID;
-    std::string why;
-    const int rc = check_env_params(rotation9, intensity, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->env_sampling == JPT_ENV_SAMPLING_MIS && rotation9 && !env_rotation_orthonormal(rotation9))
-        return fail(c, JPT_E_INVALID, "jpt_set_environment_params: with JPT_ENV_SAMPLING_MIS the rotation must be orthonormal");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no environment map");
-    static const float kIdentity[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
-    std::memcpy(c->env_rot, rotation9 ? rotation9 : kIdentity, sizeof c->env_rot);
-    c->env_intensity = intensity;
-    return JPT_OK;
 }
 
 int jpt_set_partition(jpt_ctx* c, int32_t rank, int32_t world)

@@ -1,0 +1,310 @@
+// jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
+// (jpt_capi.cpp, jpt_lighting.cpp).
+#pragma once
+#include "../../include/jpt.h"
+#include "jpt_builder.h"
+#include "jpt_denoise.h"
+#include "jpt_kernels.h"
+
+namespace jpt {
+
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    ~DevBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+    hipError_t resize(size_t count)
+    {
+        if (count == n && (p || count == 0)) return hipSuccess;
+        release();
+        if (count == 0) return hipSuccess;
+        hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    hipError_t upload(const std::vector<T>& v, hipStream_t s)
+    {
+        hipError_t e = resize(v.size());
+        if (e != hipSuccess || v.empty()) return e;
+        return hipMemcpyAsync(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
+    }
+};
+
+// A grow-only pinned host buffer (hipHostMalloc), given back by its destructor or release()
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~PinnedBuf() { release(); }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    hipError_t reserve(size_t want)
+    {
+        if (bytes >= want) return hipSuccess;
+        release();
+        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
+        if (e == hipSuccess) bytes = want;
+        return e;
+    }
+    template <typename T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// A ring of pinned staging buffers, so that the host can queue device refits ahead of the device: a stage is written again once
+// the work that last read it has run (its `copied` event)
+constexpr int kRefitStages = 4;   // refits the host may queue before it has to wait for a copy to leave its buffer
+struct StagingRing {
+    PinnedBuf buf[kRefitStages];
+    hipEvent_t copied[kRefitStages] = {};
+    uint64_t seq = 0;
+    ~StagingRing()
+    {
+        for (hipEvent_t e : copied)
+            if (e) (void)hipEventDestroy(e);
+    }
+    // the next stage, of at least `bytes`, once the work that used it last has run
+    hipError_t next(size_t bytes, int& st)
+    {
+        st = (int)(seq++ % (uint64_t)kRefitStages);
+        hipError_t e = copied[st] ? hipEventSynchronize(copied[st]) : hipEventCreateWithFlags(&copied[st], hipEventDisableTiming);
+        return e == hipSuccess ? buf[st].reserve(bytes) : e;
+    }
+};
+
+// Several copies of the instance level (RefInstance + WideInstance arrays, TLAS tail of the four-child records): a refit writes a
+// copy the renders in flight do NOT read, so the renders after a refit overlap with the renders before it.
+constexpr int kInstanceSets = 8;   // as many as renders in flight can be: a queue of animation steps stays pipelined
+
+// Every scene array on the device; the view the kernels take (jpt_ctx::ds) points into these (set_scene_view)
+struct SceneBufs {
+    // reference layout
+    DevBuf<RefTriGeometry> tri_geom;
+    DevBuf<ShadeTri> shade_tris;
+    DevBuf<RefMaterial> materials;
+    DevBuf<RefBvhNode> bvh;
+    DevBuf<RefTlasNode> tlas;
+    DevBuf<uint8_t> tex;
+    // flattened layout
+    DevBuf<WideNode> wblas, wtlas;
+    DevBuf<WideTri> wtris;
+    DevBuf<WideInstance> winst;
+    DevBuf<WideNode4> nodes4;   // four-child records: BLAS part, then one TLAS tail per copy of the instance level (one index space)
+    DevBuf<WideNodeQ> nodesq;   // their quantised form (jpt_nodeq.h), same indices: what the kernels walk
+    // the instance level, one copy per kInstanceSets; copy 0 is the one uploads write (the reach records: JPT_BUILD_SAH)
+    struct InstanceSet {
+        DevBuf<RefInstance> inst;
+        DevBuf<WideInstance> winst4;
+        DevBuf<ReachInst> reach;
+    } set[kInstanceSets];
+    DevBuf<ReachTri> reach_tri;   // reach records per triangle
+    DevBuf<float> cut_boxes;      // RefScene::inst_cut_boxes / inst_cut_range (device refits)
+    DevBuf<uint32_t> cut_range;
+    // the reference's own trees beside a native scene (ExactShadow): two-child records + the triangle map
+    DevBuf<RefBvhNode> x_bvh;
+    DevBuf<RefTriGeometry> x_tri_geom;
+    DevBuf<RefInstance> x_inst;
+    DevBuf<RefTlasNode> x_tlas;
+    DevBuf<uint32_t> x_tri_native, x_native_ref, x_tri_leaf, x_subtree_end, x_tlas_parent, x_inst_leaf;
+};
+
+// One render in flight (jpt_render_async): its stream, its workspace and the events that order it.  Slot 0's workspace is
+// also the one renders on the context's own stream use.
+struct PipeSlot {
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_paths_done = nullptr, ev_acc_done = nullptr;
+    bool acc_done_valid = false;   // ev_acc_done follows the last accumulation that read `workspace`
+    uint64_t refit_seen = 0;       // the refit (jpt_ctx::refit_wait_seq) the slot's stream has last waited for
+    DevBuf<char> workspace;
+};
+
+// What the context holds of its renders' lighting: written by the setters, read by lighting_bound and resolve_lighting (all in
+// jpt_lighting.cpp), which turn it into the one value the renders take (Lighting, jpt_kernels.h)
+struct LightingState {
+    // the environment map (jpt_set_environment): the context's, like its params
+    DevBuf<float4> d_env;
+    bool env_set = false;
+    int32_t env_w = 0, env_h = 0;
+    float env_rot[9] = {1.0f, 0.0f, 0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 1.0f};
+    float env_intensity = 1.0f;
+    // the map's importance sampling (jpt_set_environment_sampling): the mode, also the context's, and the map's tables -- built once per
+    // map while the mode is JPT_ENV_SAMPLING_MIS, then kept until the map changes
+    int32_t env_sampling = JPT_ENV_SAMPLING_BRDF;
+    DevBuf<float> d_env_cond, d_env_marg;   // h rows of w conditional CDF entries; the marginal CDF's h entries, then the total
+    bool env_tables = false;
+    float env_total = 0.0f;
+    // importance sampling of the emissive triangles (jpt_set_light_sampling): the mode, the context's like the map's; the emitters
+    // (instance, triangle pairs from c->ref, host) and their device tables -- both made at the first render that needs them after
+    // the scene changed (light_cand_stale: its instances or materials; light_table_stale: also its geometry, refits included)
+    int32_t light_sampling = JPT_LIGHT_SAMPLING_BRDF;
+    std::vector<uint32_t> light_cand_h;
+    bool light_cand_stale = true, light_cand_uploaded = false, light_table_stale = true;
+    DevBuf<uint32_t> d_light_cand;
+    DevBuf<float4> d_light_tri;
+    DevBuf<float> d_light_cdf, d_light_marg;   // per emitter; the marginal CDF's n_blocks entries, then the total power
+};
+// The scene changed: the emitter tables are rebuilt at the next render that samples them -- and the emitter list too when the
+// instances or materials may have changed (`listed`); a refit or a mesh update moves the geometry only.  Costs nothing else.
+void lights_stale(jpt_ctx* c, bool listed);
+// The lighting a render of `c` would take now, for sizing: kind and miss model, no tables, no side effect.  A bound: while the
+// emitter list is stale the answer is kEmitters whenever the mode asks for them (resolve_lighting decides).
+Lighting lighting_bound(const jpt_ctx* c);
+// The lighting of one render of `c`, once it is validated; makes the emitter tables on the context's stream when they are stale.
+int resolve_lighting(jpt_ctx* c, Lighting& out);
+
+}  // namespace jpt
+
+using namespace jpt;   // (jpt_ctx is the name include/jpt.h gives it: global)
+
+struct jpt_ctx {
+    int device = 0;
+    hipStream_t own_stream = nullptr, stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Wf2Streams group_streams;  // helper streams / events of the frame groups (launch_wf2_render)
+    std::string error;
+
+    // host scene
+    SceneBuilder builder;
+    RefScene ref;
+    WideScene wide;
+    bool building = false, scene_ready = false, tlas_dirty = false;
+    int32_t tree = JPT_TREE_NONE;   // the JPT_TREE_* of the scene in c->ref (jpt_scene_tree_kind answers it once host_scene_ready)
+    bool host_scene_ready = false;  // c->ref / c->wide hold a complete scene (also true on host-only contexts)
+    bool from_commit = false;       // the scene came from jpt_scene_commit: c->builder holds its meshes and transforms
+    int32_t upload_mode = JPT_UPLOAD_NATIVE_TREE;  // jpt_set_upload_mode
+    int32_t slot_priority = JPT_STREAM_PRIORITY_DEFAULT;  // jpt_set_stream_priority
+    int32_t max_slots = 0;              // jpt_set_memory_policy: renders in flight (0: the library's rule)
+    uint64_t workspace_budget = 0;      // ... and bytes per workspace (0: tuning().workspace_budget_mb)
+    std::string upload_note;        // why the last reference-layout upload is walked as given (empty: it is not)
+    std::string ties_note;          // why exact distance ties fall to the native tree's order (empty: they are decided exactly)
+    std::vector<RefMaterial> pending_materials;
+    std::vector<uint8_t> pending_tex;
+    int32_t pending_tex_res = 0, pending_layers = 0;
+
+    // device scene
+    SceneBufs dev;
+    DeviceScene ds;
+
+    // per-render state
+    bool params_set = false, camera_set = false;
+    int32_t width = 0, height = 0, max_bounces = 4, accum_mode = 0, sampler_mode = 0;
+    int32_t rank = 0, world = 1, local_rows = 0;
+    RefCamera camera;
+    uint32_t frame_count = 0;  // frames accumulated since reset
+    int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
+    bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
+    uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
+    bool depth_valid = false;              // d_depth holds the last render's depth image
+    // render pipelining (jpt_render_async): consecutive asynchronous renders run their path kernels on the slots' streams
+    // with their own workspaces, so one render's launch tails overlap the next render's kernels; the accumulation
+    // kernels are ordered on the context's stream
+    static constexpr int kPipeSlots = 8;   // the most; the rule is 4, or 6 where six of the slots' streams run side by side (six_queues_probe)
+    PipeSlot slot[kPipeSlots];
+    int six_queues = -1;                   // -1: not probed yet; 0 / 1
+    int last_pipe_slots = 0;               // jpt_renders_in_flight
+    bool aux_borrowed[kMaxGroups - 1] = {};   // group_streams.aux_stream[k] is slot[k].stream (ensure_group_streams): not destroyed on its own
+    uint64_t async_seq = 0;
+    std::vector<uint32_t> h_qcount;  // per-bounce queue sizes of the last wavefront render
+    std::vector<hipEvent_t> trace_events;  // pairs around each wf_trace launch of the last render
+    int32_t trace_events_used = 0;
+    bool kernel_timing = false;
+
+    // framebuffers (local rows of this partition)
+    DevBuf<float4> d_accum;
+    DevBuf<uint32_t> d_ldr;
+    DevBuf<float> d_depth;
+    DevBuf<DevCounters> d_counters;
+    // the tiles' sky cells (launch_sky_tiles): a function of the camera, the image size and the partition -- made when one of them
+    // changes, read by every accumulation until then
+    DevBuf<uint32_t> d_sky_tiles;
+    RefCamera sky_tiles_camera;
+    int32_t sky_tiles_key[5] = {0, 0, 0, 0, 0};   // width, height, local_rows, rank, world
+    bool sky_tiles_valid = false;
+    // assembled full image on the gathering rank
+    DevBuf<float4> d_full_accum;
+    DevBuf<uint32_t> d_full_ldr;
+    bool assembled = false;      // d_full_accum + d_full_ldr hold the whole image (jpt_assemble_from_ranks)
+    bool assembled_ldr = false;  // d_full_ldr only (jpt_assemble_ldr_from_ranks)
+
+    // post-processing mode (PathTracingCamera::Denoising) and the temporal pass's state
+    int32_t denoise = JPT_DENOISE_PROGRESSIVE;
+    RefTemporalParams temporal;
+    bool temporal_set = false, hist_valid = false;
+    DevBuf<float4> d_hist1, d_hist2;   // frameBuffer1 / frameBuffer2 of temporal_reprojection.glsl:16-17
+    float4* hist_written = nullptr;    // the one the last temporal pass wrote
+
+    // device refit of the instance level (jpt_scene_refit_tlas)
+    StagingRing refit_stage;           // pinned staging for the transforms
+    size_t tlas4_cap = 0;              // records reserved per TLAS tail
+    int cur_set = 0;                   // which copy new renders read
+    bool set_b_ready = false;          // copies 1.. exist and mirror the last host upload
+    hipStream_t refit_stream = nullptr;
+    hipEvent_t ev_set_retired[kInstanceSets] = {}, ev_refit_done = nullptr;
+    bool set_retired_valid[kInstanceSets] = {};
+    uint64_t refit_wait_seq = 0;
+    int idle_streak = 0;   // queued renders in a row that found nothing in flight (plan_launch)
+    DevBuf<uint32_t> d_tlas4_order, d_tlas4_levels;
+    uint32_t n_tlas4_levels = 0;
+    bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
+    bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
+    std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
+    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in dev.nodes4 and its schedule
+    // (refit4_schedule), made at the first update after an upload
+    struct MeshRefit {
+        bool has_tree = false;              // an instance names the mesh and it has triangles: the device holds its tree
+        int32_t root4 = 0;                  // its root reference in dev.nodes4
+        uint32_t bvh_root = 0;              // its root in dev.bvh (RefScene::mesh_roots)
+        uint32_t tri_first = 0, n_tris = 0;
+        uint32_t rec_first = 0, n_recs = 0;  // the span of dev.nodes4 its records occupy
+        uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
+    };
+    std::vector<MeshRefit> mesh_refit;
+    bool mesh_refit_ready = false;
+    std::vector<uint32_t> mesh_order_h, mesh_levels_h;
+    DevBuf<uint32_t> d_mesh_order, d_mesh_levels, d_tri_vidx;
+    DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
+    StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
+    hipEvent_t ev_mesh_drain = nullptr;
+    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
+    PinnedBuf h_ldr_pinned;    // the split read-back of the display image
+    PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
+    hipEvent_t ev_readback = nullptr;
+    bool readback_pending = false;
+    bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
+
+    LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
+
+    // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
+    // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution
+    AtrousParams dn_params;
+    DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
+    DevBuf<uint32_t> d_dn_ldr;
+    bool dn_valid = false;
+
+    jpt_stats stats;
+};
+
+static inline int fail(jpt_ctx* c, int code, const std::string& msg)
+{
+    if (c) c->error = msg;
+    return code;
+}
+
+static inline int hip_fail(jpt_ctx* c, hipError_t e, const char* what)
+{
+    return fail(c, JPT_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(c, expr)                                          \
+    do {                                                          \
+        hipError_t e_ = (expr);                                   \
+        if (e_ != hipSuccess) return hip_fail((c), e_, #expr);    \
+    } while (0)

@@ -121,7 +121,7 @@ __global__ void env_lookup_probe(EnvDev env, const float* __restrict__ dirs3, ui
 
 }  // namespace
 
-// jpt_debug_light_sample / jpt_debug_light_pdf (entry points in jpt_capi.cpp, which owns the context): the emitter sampler and
+// jpt_debug_light_sample / jpt_debug_light_pdf (entry points in jpt_lighting.cpp, beside the context's tables): the emitter sampler and
 // density the light-sampling kernels inline (light_sample / light_cos / light_pdf, jpt_shade.h), one item per thread
 __global__ void light_probe(LightDev lt, SceneShading sh, int what, const float* __restrict__ xi4, const float* __restrict__ origins,
                             const float* __restrict__ dirs, const float* __restrict__ points, const uint32_t* __restrict__ inst,

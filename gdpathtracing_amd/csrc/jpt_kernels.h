@@ -1,4 +1,4 @@
-// jpt_kernels.h -- what the host layer (jpt_capi.cpp) sees of the device code.
+// jpt_kernels.h -- what the host layer (jpt_capi.cpp, jpt_lighting.cpp) sees of the device code.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -195,7 +195,7 @@ __device__ __forceinline__ void count_walk(DevCounters& c, uint32_t steps)
 }
 #endif
 
-// the checks of jpt_set_environment / jpt_set_environment_params (jpt_capi.cpp), also run by jpt_debug_env_lookup: JPT_OK, or a
+// the checks of jpt_set_environment / jpt_set_environment_params (jpt_lighting.cpp), also run by jpt_debug_env_lookup: JPT_OK, or a
 // JPT_E_* code and the reason in `why`; and the map's device layout, (r, g, b, 0) per texel
 int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why);
 int check_env_params(const float* rotation9, float intensity, std::string& why);
@@ -207,10 +207,22 @@ void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int3
 constexpr double kEnvOrthoTol = 1e-4;
 bool env_rotation_orthonormal(const float* rotation9);
 
+// What the misses and the shadow rays of one render see -- the whole answer, made once per render (resolve_lighting, jpt_lighting.cpp)
+// and read by everything that sizes or launches it.  Host side only: the kernels take env, samp, lights and env_mode as they are.
+struct Lighting {
+    // the kernel family: the default kernels, *_env, *_mis, *_lt (emitter sampling over a scene with emitters, whatever the miss model)
+    enum Kind { kSky, kMap, kMapMis, kEmitters } kind = kSky;
+    int env_mode = 0;        // the miss model, a run-time value of the *_lt kernels: 0 the gradient, 1 the map, 2 the map with MIS
+    EnvDev env = {};         // the map (env_mode != 0; zeroed otherwise)
+    EnvSampDev samp = {};    // its sampling tables (env_mode == 2)
+    LightDev lights = {};    // the emitter tables (kEmitters)
+    bool map_queues() const { return env_mode == 2; }           // the workspace holds the map's shadow queues (wf2_occlude) ...
+    bool emitter_queues() const { return kind == kEmitters; }   // ... the emitters' (wf2_occlude_lt)
+};
+
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env = nullptr,
-                      const EnvSampDev* env_samp = nullptr, const LightDev* lights = nullptr);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg);
 
 // The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
 // tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory
@@ -245,8 +257,7 @@ void launch_sky_tiles(hipStream_t stream, const FrameParams& fp, const RefCamera
 uint32_t wf2_segments();
 uint32_t trace_stack_capacity();  // entries a lane's traversal stack can hold (LDS + scratch)
 // bytes of the workspace a render of this size carves (wf2_layout), for any frame-group count and window
-size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis = false,
-                           bool lights = false);   // mis: + the map's shadow queues (Wf2Nee); lights: + the emitters' queues
+size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, const Lighting& lg);   // lg: its shadow queues
 // Screen rectangles (pixels, inclusive) of the boxes the TLAS root offers a ray; a primary ray through a pixel
 // outside all of them is known to fail all of the root's box tests, i.e. to reach the sky after exactly one TLAS
 // expansion, without being traced.  n < 0: unknown, trace everything.  Filled on the host (jpt_capi.cpp).
@@ -267,12 +278,7 @@ struct Wf2Render {
     hipEvent_t before_acc = nullptr;       // the accumulation kernel waits for this event (whatever its stream)
     const uint32_t* sky_tiles = nullptr;   // per 8 x 8 tile of the context's share of the image: its one rgba8 sky cell, if it has one
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
-    const EnvSampDev* env_samp = nullptr;  // with `env`: its sampling tables (JPT_ENV_SAMPLING_MIS, a map of non-zero weight): the *_mis
-                                           // kernels and wf2_occlude, and the workspace's MIS buffers
-    const LightDev* lights = nullptr;      // the emitter tables (JPT_LIGHT_SAMPLING_MIS, a scene with emitters): the *_lt kernels,
-                                           // wf2_occlude_lt and the workspace's light queues, whatever the miss model
-    const EnvDev* env = nullptr;           // the environment map the misses see (jpt_set_environment); null: sample_sky.  The
-                                           // launches then take the *_env kernels, and the accumulation uses no sky cells
+    Lighting lighting;                     // the kernel family of its launches and the workspace's shadow queues (no sky cells with a map)
 };
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block

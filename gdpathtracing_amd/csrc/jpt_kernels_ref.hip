@@ -188,7 +188,7 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 }
 
 
-// the frame kernel (jpt_ref_frame.h): the default one, then ref_frame_kernel_env, then ref_frame_kernel_mis
+// the frame kernel (jpt_ref_frame.h): the default one, then ref_frame_kernel_env, ref_frame_kernel_mis, ref_frame_kernel_lt
 #define JPT_ENV 0
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
@@ -203,8 +203,7 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 #undef JPT_ENV
 
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const EnvDev* env, const EnvSampDev* env_samp,
-                      const LightDev* lights)
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg)
 {
     RefSceneDev sc;
     sc.tri_geom = ds.ref_tri_geom;
@@ -219,18 +218,21 @@ void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FramePara
     dim3 grid((fp.width + 31) / 32, (fp.local_rows + 7) / 8), block(256);
     const bool ties = ds.x.ok && ds.reach_tri != nullptr && !fp.debug_steps;
     with_consts<2, 2>([&](auto C, auto TIES) {
-        if (lights) {
-            const EnvDev e0 = env ? *env : EnvDev{};
-            const EnvSampDev s0 = (env && env_samp) ? *env_samp : EnvSampDev{};
-            const int env_mode = env ? (env_samp ? 2 : 1) : 0;
-            hipLaunchKernelGGL((ref_frame_kernel_lt<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, e0, s0, *lights,
-                               env_mode);
-        } else if (env && env_samp)
-            hipLaunchKernelGGL((ref_frame_kernel_mis<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, *env, *env_samp);
-        else if (env)
-            hipLaunchKernelGGL((ref_frame_kernel_env<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, *env);
-        else
+        switch (lg.kind) {
+        case Lighting::kEmitters:
+            hipLaunchKernelGGL((ref_frame_kernel_lt<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lg.env, lg.samp,
+                               lg.lights, lg.env_mode);
+            break;
+        case Lighting::kMapMis:
+            hipLaunchKernelGGL((ref_frame_kernel_mis<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lg.env, lg.samp);
+            break;
+        case Lighting::kMap:
+            hipLaunchKernelGGL((ref_frame_kernel_env<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lg.env);
+            break;
+        case Lighting::kSky:
             hipLaunchKernelGGL((ref_frame_kernel<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters);
+            break;
+        }
     }, counters != nullptr, ties);
 }
 

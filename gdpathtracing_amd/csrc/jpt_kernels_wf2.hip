@@ -817,7 +817,7 @@ struct Wf2Layout {
     Wf2Nee glnee[kMaxGroups];  // (light-sampling renders only: behind those; pdf shared with gnee when both are carved)
     size_t bytes = 0;     // the end of the last buffer
 };
-static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window, bool mis = false, bool lights = false)
+static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const TileWindow& window, const Lighting& lg)
 {
     Wf2Layout L;
     auto carve = [&](size_t bytes) {
@@ -860,35 +860,28 @@ static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const
         L.gfp[g].n_frames = nf;
         L.gfp[g].depth_frame = (fp.depth_frame >= 0 && f0 + nf == fp.n_frames) ? nf - 1 : -1;  // the render's last frame writes the depth image (when there is one: jpt_set_outputs)
     }
-    for (int g = 0; g < groups && mis; g++) {
-        int f0, nf;
-        group_frames(fp.n_frames, groups, g, f0, nf);
+    // the shadow queues of group g; their per-path densities are `shared`'s, or carved behind them
+    auto carve_nee = [&](int g, const Wf2Nee* shared) {
         const size_t q = (size_t)L.gdm[g].seg_cap * kSegments;
-        const size_t paths = (size_t)L.gdm[g].slots_per_frame * (size_t)nf;
-        Wf2Nee& ne = L.gnee[g];
+        const size_t paths = (size_t)L.gdm[g].slots_per_frame * (size_t)L.gfp[g].n_frames;
+        Wf2Nee ne;
         ne.sh_o = (float4*)carve(q * sizeof(float4));
         ne.sh_d = (float4*)carve(q * sizeof(float4));
         ne.sh_c = (float4*)carve(q * sizeof(float4));
         ne.scount = (uint32_t*)carve((size_t)(fp.max_bounces > 0 ? fp.max_bounces : 1) * kSegments * sizeof(uint32_t));
-        ne.pdf = (float*)carve(paths * sizeof(float));
-    }
-    for (int g = 0; g < groups && lights; g++) {
-        int f0, nf;
-        group_frames(fp.n_frames, groups, g, f0, nf);
-        const size_t q = (size_t)L.gdm[g].seg_cap * kSegments;
-        const size_t paths = (size_t)L.gdm[g].slots_per_frame * (size_t)nf;
-        Wf2Nee& ne = L.glnee[g];
-        ne.sh_o = (float4*)carve(q * sizeof(float4));
-        ne.sh_d = (float4*)carve(q * sizeof(float4));
-        ne.sh_c = (float4*)carve(q * sizeof(float4));
-        ne.scount = (uint32_t*)carve((size_t)(fp.max_bounces > 0 ? fp.max_bounces : 1) * kSegments * sizeof(uint32_t));
-        ne.pdf = mis ? L.gnee[g].pdf : (float*)carve(paths * sizeof(float));
-        if (!mis) L.gnee[g] = Wf2Nee{nullptr, nullptr, nullptr, nullptr, ne.pdf};
+        ne.pdf = shared ? shared->pdf : (float*)carve(paths * sizeof(float));
+        return ne;
+    };
+    const bool mis = lg.map_queues();
+    for (int g = 0; g < groups && mis; g++) L.gnee[g] = carve_nee(g, nullptr);
+    for (int g = 0; g < groups && lg.emitter_queues(); g++) {
+        L.glnee[g] = carve_nee(g, mis ? &L.gnee[g] : nullptr);
+        if (!mis) L.gnee[g] = Wf2Nee{nullptr, nullptr, nullptr, nullptr, L.glnee[g].pdf};
     }
     return L;
 }
 
-size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, bool mis, bool lights)
+size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_bounces, const Lighting& lg)
 {
     // every layout a render of this size may use: the largest of 1..kMaxGroups groups over the whole image
     FrameParams fp{};
@@ -898,7 +891,7 @@ size_t wf2_workspace_bytes(int width, int local_rows, int n_frames, int max_boun
     fp.max_bounces = max_bounces;
     size_t worst = 0;
     for (int groups = 1; groups <= kMaxGroups && groups <= (n_frames < 1 ? 1 : n_frames); groups++)
-        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows), mis, lights).bytes);
+        worst = std::max(worst, wf2_layout(nullptr, fp, groups, full_window(width, local_rows), lg).bytes);
     return worst;
 }
 
@@ -917,12 +910,8 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     const TileWindow window = cull_window(r.cull, fp);
     const Wf2Dims dm_all = make_dims(fp.width, fp.local_rows, fp.n_frames, window);
     if (dm_all.n_chunks == 0) return;
-    const EnvSampDev* es = r.env ? r.env_samp : nullptr;   // the MIS kernels (jpt_wf2_paths.h, JPT_ENV 2)
-    const LightDev* lt = r.lights;   // the light-sampling kernels (jpt_wf2_paths.h, JPT_ENV 3), whatever the miss model
-    const Wf2Layout L = wf2_layout(workspace, fp, groups, window, es != nullptr, lt != nullptr);
-    const EnvDev env0 = r.env ? *r.env : EnvDev{};
-    const EnvSampDev es0 = es ? *es : EnvSampDev{};
-    const int env_mode = r.env ? (es ? 2 : 1) : 0;
+    const Lighting& lg = r.lighting;   // which of the kernel families of jpt_wf2_paths.h the launches take, and what they pass
+    const Wf2Layout L = wf2_layout(workspace, fp, groups, window, lg);
     const int nq = fp.max_bounces + 2;
 
     const bool w4 = ds.use4;
@@ -955,7 +944,6 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     // wf2_finish decides exact distance ties on the reference's own trees (EXACT) where the scene keeps them, four-child walks only
     const TieShadowDev& sx = ds.x;
     const int finish_walk = !w4 ? 0 : (sx.ok ? 2 : 1);
-    const EnvDev* env = r.env;   // an environment map: the *_env kernels (jpt_wf2_paths.h)
     // the pipeline of one group on one stream
     auto run_group = [&](hipStream_t st, const Wf2Buffers& wb, const Wf2Dims& dm, const FrameParams& gp, const Wf2Nee& nee, const Wf2Nee& lnee,
                          hipEvent_t* ev) {
@@ -964,12 +952,12 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         // alike (the first ones are full, the last ones empty): with grid.x a multiple of 8 every XCD would always get
         // the same chunk position.  An odd grid.x deals every position to every XCD (capping C3's grid.x from 37 to 8
         // cost 9 %).
-        const dim3 sgrid(((dm.seg_cap + kBlock - 1) / kBlock) | 1u, kSegments);
-        if (es && gp.max_bounces > 0) (void)hipMemsetAsync(nee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
-        if (lt && gp.max_bounces > 0) (void)hipMemsetAsync(lnee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
+        const dim3 sgrid(((dm.seg_cap + kBlock - 1) / kBlock) | 1u, kSegments), ogrid(((dm.seg_cap + kOccBlock - 1) / kOccBlock) | 1u, kSegments);
+        if (lg.map_queues() && gp.max_bounces > 0) (void)hipMemsetAsync(nee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
+        if (lg.emitter_queues() && gp.max_bounces > 0) (void)hipMemsetAsync(lnee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
         if (ev) (void)hipEventRecord(ev[0], st);
         with_consts<2, 3>([&](auto C, auto W) {
-            if (env)
+            if (lg.env_mode != 0)   // (the primary launch is its miss model's: a primary miss has weight 1)
                 hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
             else
                 hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
@@ -977,25 +965,29 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {
             with_consts<2, 2, 3>([&](auto C, auto LAST, auto TEX) {
-                if (lt)
-                    hipLaunchKernelGGL((wf2_shade_lt<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, env0, es0, *lt, nee, lnee,
-                                       env_mode);
-                else if (es)
-                    hipLaunchKernelGGL((wf2_shade_mis<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env, *es, nee);
-                else if (env)
-                    hipLaunchKernelGGL((wf2_shade_env<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, *env);
-                else
+                switch (lg.kind) {
+                case Lighting::kEmitters:
+                    hipLaunchKernelGGL((wf2_shade_lt<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, lg.env, lg.samp, lg.lights, nee,
+                                       lnee, lg.env_mode);
+                    break;
+                case Lighting::kMapMis:
+                    hipLaunchKernelGGL((wf2_shade_mis<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, lg.env, lg.samp, nee);
+                    break;
+                case Lighting::kMap:
+                    hipLaunchKernelGGL((wf2_shade_env<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, lg.env);
+                    break;
+                case Lighting::kSky:
                     hipLaunchKernelGGL((wf2_shade<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters);
+                    break;
+                }
             }, count, b == gp.max_bounces, texmode);
             if (b == gp.max_bounces) break;
-            if (es) {
-                const dim3 ogrid(((dm.seg_cap + kOccBlock - 1) / kOccBlock) | 1u, kSegments);
+            if (lg.map_queues()) {
                 with_consts<2, 3>([&](auto C, auto W) {
                     hipLaunchKernelGGL((wf2_occlude<C, W != 0>), ogrid, dim3(kOccBlock), 0, st, sc, wb, dm, gp, b, nee, counters);
                 }, count, walk);
             }
-            if (lt) {   // (after the map's: the emitters' shadow ray of a vertex lands second)
-                const dim3 ogrid(((dm.seg_cap + kOccBlock - 1) / kOccBlock) | 1u, kSegments);
+            if (lg.emitter_queues()) {   // (after the map's: the emitters' shadow ray of a vertex lands second)
                 with_consts<2, 3>([&](auto C, auto W) {
                     hipLaunchKernelGGL((wf2_occlude_lt<C, W != 0>), ogrid, dim3(kOccBlock), 0, st, sc, wb, dm, gp, b, lnee, counters);
                 }, count, walk);
@@ -1009,15 +1001,21 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (sh.reach_tri) {  // the paths set aside because their hit is undecidable on the native tree: finished exactly
             const dim3 rgrid(256), rblock(64);   // (blocks past the set-aside count exit at once; more records than threads: grid-stride)
             with_consts<2, 3>([&](auto C, auto W) {
-                if (lt)
-                    hipLaunchKernelGGL((wf2_finish_lt<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, env0, es0, *lt, nee,
-                                       lnee, env_mode);
-                else if (es)
-                    hipLaunchKernelGGL((wf2_finish_mis<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env, *es, nee);
-                else if (env)
-                    hipLaunchKernelGGL((wf2_finish_env<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, *env);
-                else
+                switch (lg.kind) {
+                case Lighting::kEmitters:
+                    hipLaunchKernelGGL((wf2_finish_lt<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, lg.env, lg.samp,
+                                       lg.lights, nee, lnee, lg.env_mode);
+                    break;
+                case Lighting::kMapMis:
+                    hipLaunchKernelGGL((wf2_finish_mis<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, lg.env, lg.samp, nee);
+                    break;
+                case Lighting::kMap:
+                    hipLaunchKernelGGL((wf2_finish_env<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, lg.env);
+                    break;
+                case Lighting::kSky:
                     hipLaunchKernelGGL((wf2_finish<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters);
+                    break;
+                }
             }, count, finish_walk);
         }
     };
@@ -1049,8 +1047,8 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     // the accumulation touches the framebuffers: it waits for whatever ordered the context's renders before this one (before_acc)
     if (r.before_acc) (void)hipStreamWaitEvent(stream, r.before_acc, 0);
     const uint32_t ablocks = ((uint32_t)dm_all.full_tiles_x * (uint32_t)dm_all.full_tiles_y * 64u + kBlock - 1) / kBlock;
-    if (env)   // (no sky cells)
-        hipLaunchKernelGGL(wf2_accumulate_env, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, nullptr, *env);
+    if (lg.env_mode != 0)   // (the accumulation is its miss model's too; with a map: no sky cells)
+        hipLaunchKernelGGL(wf2_accumulate_env, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, nullptr, lg.env);
     else
         hipLaunchKernelGGL(wf2_accumulate, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, r.sky_tiles);
 }

@@ -1,5 +1,5 @@
 // jpt_ref_frame.h -- ref_frame_kernel, the audit route's one kernel (jpt_kernels_ref.hip), which sees the paths' misses.  Included
-// twice by jpt_kernels_ref.hip, as jpt_wf2_paths.h is by jpt_kernels_wf2.hip:
+// four times by jpt_kernels_ref.hip, as jpt_wf2_paths.h is by jpt_kernels_wf2.hip; launch_ref_frame switches on Lighting::kind:
 //   JPT_ENV 0   ref_frame_kernel, main.glsl's gradient (sample_sky): the same source, token for token, as before the map existed;
 //   JPT_ENV 1   ref_frame_kernel_env (jpt_set_environment): one more parameter, the map, and env_radiance at the miss;
 //   JPT_ENV 2   ref_frame_kernel_mis (JPT_ENV_SAMPLING_MIS): also the map's sampling tables; below the last bounce each vertex casts

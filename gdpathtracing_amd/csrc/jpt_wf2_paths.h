@@ -1,5 +1,5 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
-// which wf2_finish shares), wf2_finish and wf2_accumulate.  Included twice by jpt_kernels_wf2.hip, inside its anonymous namespace:
+// which wf2_finish shares), wf2_finish and wf2_accumulate.  Included four times by jpt_kernels_wf2.hip, inside its anonymous namespace:
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -17,7 +17,7 @@
 //               bounce >= 1 weighs its emission against the emitter strategy (light_hit_weight).  They pair with the primary and
 //               accumulation launches of the miss model in use.
 // A run-time branch on the map in the default kernels would cost them registers; a template parameter would change their names.
-// (No include guard: that is the point.)
+// (No include guard: that is the point.)  Which family a render launches: Lighting::kind (jpt_kernels.h), decided on the host.
 #if JPT_ENV == 3
 #define JPT_ENV_NAME(name) name##_lt
 #define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, LightDev lt, Wf2Nee nee, Wf2Nee lnee, int env_mode
