@@ -26,6 +26,9 @@ OUTPUT_DEPTH = 1
 ENV_SAMPLING_BRDF, ENV_SAMPLING_MIS = 0, 1
 LIGHT_SAMPLING_BRDF, LIGHT_SAMPLING_MIS = 0, 1
 UPLOAD_NATIVE_TREE, UPLOAD_WALK_AS_GIVEN = 0, 1
+DISPLAY_SOURCE_ACCUM, DISPLAY_SOURCE_DENOISED = 0, 1
+TONEMAP_ACES_REF, TONEMAP_REINHARD, TONEMAP_CLAMP = 0, 1, 2
+TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
 BUF_TRI_GEOMETRY, BUF_TRI_DATA, BUF_MATERIALS, BUF_BVH_NODES, BUF_INSTANCES, BUF_TLAS_NODES, BUF_TRIANGLES, BUF_REACH_TRIANGLES, BUF_REACH_INSTANCES = range(9)
@@ -49,6 +52,7 @@ SYMBOLS = [
     "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
     "jpt_set_light_sampling", "jpt_multi_set_light_sampling", "jpt_debug_light_tables", "jpt_debug_light_sample", "jpt_debug_light_pdf",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
+    "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
 ]
 
 
@@ -67,6 +71,16 @@ class DenoiseParams(C.Structure):
 
     def __init__(self, passes=5, normal_power_log2=6, sigma_plane=0.02, sigma_color=4.0):
         super().__init__(passes, normal_power_log2, sigma_plane, sigma_color)
+
+
+class DisplayParams(C.Structure):
+    """jpt_display_params; the defaults are the library's"""
+    _fields_ = [("source", C.c_int32), ("tonemap", C.c_int32), ("transfer", C.c_int32), ("bloom_levels", C.c_int32),
+                ("exposure", C.c_float), ("white", C.c_float), ("bloom_threshold", C.c_float), ("bloom_strength", C.c_float)]
+
+    def __init__(self, source=DISPLAY_SOURCE_ACCUM, tonemap=TONEMAP_ACES_REF, transfer=TRANSFER_LINEAR, bloom_levels=0, exposure=1.0,
+                 white=4.0, bloom_threshold=1.0, bloom_strength=0.25):
+        super().__init__(source, tonemap, transfer, bloom_levels, exposure, white, bloom_threshold, bloom_strength)
 
 
 class Stats(C.Structure):
@@ -230,6 +244,13 @@ def lib():
         L.jpt_read_denoised_rgba8.argtypes = [vp, vp]
         L.jpt_read_guides_f32.argtypes = [vp, vp, vp, vp]
         L.jpt_debug_atrous.argtypes = [C.c_int, i32, i32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
+    if hasattr(L, "jpt_display") or "JPT_LIB" not in os.environ:
+        L.jpt_set_display_params.argtypes = [vp, C.POINTER(DisplayParams)]
+        L.jpt_display.argtypes = [vp]
+        L.jpt_read_display_rgba8.argtypes = [vp, vp]
+        L.jpt_read_display_f32.argtypes = [vp, vp]
+        L.jpt_debug_display.argtypes = [C.c_int, i32, i32, C.POINTER(DisplayParams), vp, vp, vp]
+        L.jpt_debug_display_srgb_table.argtypes = [vp]
     _lib = L
     return L
 

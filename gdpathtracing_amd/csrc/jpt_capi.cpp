@@ -1893,7 +1893,14 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
         c->d_dn_pong.release();
         c->d_dn_ldr.release();
     }
-    if (width != c->width || height != c->height) c->dn_valid = false;
+    if ((width != c->width || height != c->height) && (c->d_disp_f32.p || c->d_disp_pyramid.p)) {
+        // jpt_display's buffers likewise
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->d_disp_f32.release();
+        c->d_disp_ldr.release();
+        c->d_disp_pyramid.release();
+    }
+    if (width != c->width || height != c->height) c->dn_valid = c->disp_valid = false;
     c->width = width;
     c->height = height;
     c->max_bounces = max_bounces;
@@ -2215,6 +2222,89 @@ int jpt_read_guides_f32(jpt_ctx* c, float* position_t, float* normal, float* alb
         if ((rc = staged_read(c, src[k], bytes)) != JPT_OK) return rc;
         std::memcpy(outs[k], c->h_read_pinned.p, bytes);
     }
+    return JPT_OK;
+}
+
+// ---- jpt_display ------------------------------------------------------------------------------------------------------------
+int jpt_set_display_params(jpt_ctx* c, const jpt_display_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    DisplayParams p;
+    if (params) {
+        p.source = params->source;
+        p.tonemap = params->tonemap;
+        p.transfer = params->transfer;
+        p.bloom_levels = params->bloom_levels;
+        p.exposure = params->exposure;
+        p.white = params->white;
+        p.bloom_threshold = params->bloom_threshold;
+        p.bloom_strength = params->bloom_strength;
+    }
+    std::string why;
+    const int rc = check_display_params(p, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_display runs on the device");
+    c->disp_params = p;
+    return JPT_OK;
+}
+
+int jpt_display(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_display grades the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_display: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1)
+        return fail(c, JPT_E_STATE, "jpt_display needs the whole image on one context (world == 1): the bloom reads rows a partition does not hold");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_display runs on the device");
+    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_display: jpt_set_params not called");
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_display: no frame accumulated since the last reset");
+    const DisplayParams prm = c->disp_params;
+    const bool denoised = prm.source == JPT_DISPLAY_SOURCE_DENOISED;
+    if (denoised && !c->dn_valid) return fail(c, JPT_E_STATE, "jpt_display: JPT_DISPLAY_SOURCE_DENOISED and no jpt_denoise at the current resolution yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->width * c->height;
+    HIP_TRY(c, c->d_disp_f32.resize(npx));
+    HIP_TRY(c, c->d_disp_ldr.resize(npx));
+    if (prm.bloom_levels > 0) HIP_TRY(c, c->d_disp_pyramid.resize(display_pyramid_elems(c->width, c->height, kDisplayMaxLevels, nullptr)));
+    // On the context's stream, as jpt_denoise: behind the accumulation of every render queued so far and behind a jpt_denoise queued
+    // before it; the accumulation of every later render (and a later jpt_denoise) waits for what it holds.
+    if (npx) {
+        launch_display(c->stream, prm, c->width, c->height, denoised ? c->d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count,
+                       c->d_disp_pyramid.p, c->d_disp_f32.p, c->d_disp_ldr.p);
+        HIP_TRY(c, hipGetLastError());
+    }
+    c->disp_valid = true;
+    return JPT_OK;
+}
+
+static int read_display_common(jpt_ctx* c, bool have_out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!have_out) return fail(c, JPT_E_INVALID, "null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_display runs on the device");
+    if (!c->disp_valid) return fail(c, JPT_E_STATE, "no jpt_display at the current resolution yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    return JPT_OK;
+}
+
+int jpt_read_display_rgba8(jpt_ctx* c, uint8_t* out)
+{
+    int rc = read_display_common(c, out != nullptr);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->width * c->height * sizeof(uint32_t);
+    if ((rc = staged_read(c, c->d_disp_ldr.p, bytes)) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+int jpt_read_display_f32(jpt_ctx* c, float* out)
+{
+    int rc = read_display_common(c, out != nullptr);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    if ((rc = staged_read(c, c->d_disp_f32.p, bytes)) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
     return JPT_OK;
 }
 

@@ -4,6 +4,7 @@
 #include "../../include/jpt.h"
 #include "jpt_builder.h"
 #include "jpt_denoise.h"
+#include "jpt_display.h"
 #include "jpt_kernels.h"
 
 namespace jpt {
@@ -288,6 +289,14 @@ struct jpt_ctx {
     DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
     DevBuf<uint32_t> d_dn_ldr;
     bool dn_valid = false;
+
+    // jpt_display: the context's parameters, and its own buffers -- the two images made at the first jpt_display at a resolution,
+    // the pyramid (six levels' worth) at the first one with bloom, kept until jpt_set_params names another size; disp_valid: the
+    // images hold the result of a jpt_display at the current resolution
+    DisplayParams disp_params;
+    DevBuf<float4> d_disp_f32, d_disp_pyramid;
+    DevBuf<uint32_t> d_disp_ldr;
+    bool disp_valid = false;
 
     jpt_stats stats;
 };

@@ -384,6 +384,30 @@ class Context:
         self._ck(self._lib.jpt_read_denoised_rgba8(self.h, _ptr(out)), "jpt_read_denoised_rgba8")
         return out
 
+    # ---- the display transform (jpt_display)
+    def set_display_params(self, params: Optional[capi.DisplayParams] = None, **fields):
+        """jpt_set_display_params: a capi.DisplayParams, or its fields by name (source, tonemap, transfer, bloom_levels, exposure,
+        white, bloom_threshold, bloom_strength; the rest at the defaults); nothing: the defaults"""
+        if params is None and fields:
+            params = capi.DisplayParams(**fields)
+        self._ck(self._lib.jpt_set_display_params(self.h, None if params is None else C.byref(params)), "jpt_set_display_params")
+
+    def display(self):
+        """jpt_display: queue exposure, bloom, tone map and transfer over the accumulation as it is after the renders queued so far
+        (or over jpt_denoise's image); neither is touched"""
+        self._ck(self._lib.jpt_display(self.h), "jpt_display")
+
+    def read_display(self) -> np.ndarray:
+        """the tone-mapped image before the transfer, float32 [height, width, 4] = (r, g, b, 1)"""
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        self._ck(self._lib.jpt_read_display_f32(self.h, _ptr(out)), "jpt_read_display_f32")
+        return out
+
+    def read_display_ldr(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
+        self._ck(self._lib.jpt_read_display_rgba8(self.h, _ptr(out)), "jpt_read_display_rgba8")
+        return out
+
     def read_guides(self):
         """jpt_read_guides_f32: (position_t, normal, albedo), float32 [height, width, 4] each"""
         g = [np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(3)]

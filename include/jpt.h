@@ -202,7 +202,8 @@ int jpt_renders_in_flight(const jpt_ctx *ctx);
  * largest read-back made so far (133 MB after a jpt_read_accum_f32 of a 3840x2160 image); this call and every change of
  * resolution or partition give it back, the next read-back allocates what it needs.  It is not part of the bytes reported.
  * Nor are jpt_denoise's own images (84 bytes per pixel, from the first jpt_denoise at a resolution until jpt_set_params with
- * another size or jpt_destroy): jpt_get_workspace_bytes keeps reporting the renders' workspaces alone. */
+ * another size or jpt_destroy), nor jpt_display's (25.4 bytes per pixel, likewise): jpt_get_workspace_bytes keeps reporting the
+ * renders' workspaces alone. */
 int jpt_set_memory_policy(jpt_ctx *ctx, int32_t renders_in_flight, uint64_t workspace_budget_bytes);
 int jpt_get_workspace_bytes(jpt_ctx *ctx, uint64_t *bytes_out);
 
@@ -546,6 +547,53 @@ int jpt_read_denoised_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats (r, g
 int jpt_read_denoised_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes: unorm8(ACES(denoised)), alpha 255 */
 int jpt_read_guides_f32(jpt_ctx *ctx, float *position_t, float *normal, float *albedo);   /* each W*H*4 floats, or NULL */
 
+/* ---- the display transform: exposure, bloom, selectable tone mapping (no reference counterpart; the reference lists "simple post
+ * processing (e.g. bloom, controllable tone-mapping)" among its wanted features) ------------------------------------------------
+ * A graded display image from the progressive accumulation or from jpt_denoise's image, as an explicit call: nothing runs unless
+ * the host asks, and without jpt_display every render, buffer and read-back is exactly what it is without this section.  The
+ * arithmetic is pinned in DESIGN.md section 2 (gdpathtracing_amd/csrc/jpt_display.h; tests/np_display.py restates it bit for bit):
+ *   base        c = (accum / frame_count) * exposure           (JPT_DISPLAY_SOURCE_DENOISED: jpt_denoise's image * exposure)
+ *   bloom       (bloom_levels = N > 0) what of c lies over bloom_threshold by luminance (a pixel with a non-finite channel gives
+ *               nothing), halved N times with a 4 x 4 binomial filter, summed back up with a 2 x tent filter;
+ *               o = c + bloom * (bloom_strength / N)
+ *   tone map    JPT_TONEMAP_ACES_REF: the reference's ACES fit; _REINHARD: clamp(o (1 + o / white^2) / (1 + o), 0, 1);
+ *               _CLAMP: clamp(o, 0, 1).  A NaN gives 0.
+ *   transfer    JPT_TRANSFER_LINEAR: unorm8, as the reference stores; _SRGB: the sRGB code nearest to the encoded value (a search of
+ *               the 255 code boundaries jpt_debug_display_srgb_table hands out; IEC 61966-2-1).
+ * With the default parameters the rgba8 image equals jpt_read_ldr_rgba8 byte for byte; with source = DENOISED and the rest at the
+ * defaults it equals jpt_read_denoised_rgba8.
+ *
+ * jpt_display enqueues its kernels on the context's stream, ordered as jpt_denoise is: behind every render (and jpt_denoise) queued
+ * before it and ahead of those queued after it.  It READS the accumulation and the frame count, or jpt_denoise's image, and writes
+ * only its own buffers: the tone-mapped image (16 bytes per pixel) and the encoded image (4 bytes per pixel), allocated at the first
+ * call at a resolution, and the bloom pyramid (16 bytes for each of the ~0.34 pyramid pixels per image pixel of six levels: 5.4
+ * bytes per pixel), allocated at the first call with bloom_levels > 0 -- 25.4 bytes per pixel in all, freed by jpt_set_params with
+ * another size and by jpt_destroy.
+ * JPT_E_STATE: a denoising mode other than JPT_DENOISE_PROGRESSIVE; the DEBUG_STEPS mode; a screen partition (the bloom reads rows
+ * the context does not hold); jpt_set_params not called; no frame accumulated since the last reset; source = DENOISED without a
+ * jpt_denoise at the current resolution; jpt_read_display_* before a jpt_display at the current resolution.  Host-only contexts:
+ * JPT_E_DEVICE, after the checks that need no device.
+ * The parameters are the context's: they survive scene changes, each jpt_display takes them by value, jpt_scene_share does not copy
+ * them.  JPT_E_INVALID outside the ranges below or for a non-finite value. */
+enum { JPT_DISPLAY_SOURCE_ACCUM = 0, JPT_DISPLAY_SOURCE_DENOISED = 1 };
+enum { JPT_TONEMAP_ACES_REF = 0, JPT_TONEMAP_REINHARD = 1, JPT_TONEMAP_CLAMP = 2 };
+enum { JPT_TRANSFER_LINEAR = 0, JPT_TRANSFER_SRGB = 1 };
+typedef struct jpt_display_params {
+    int32_t source;          /* default JPT_DISPLAY_SOURCE_ACCUM */
+    int32_t tonemap;         /* default JPT_TONEMAP_ACES_REF: progressive_rendering.glsl:19-26 */
+    int32_t transfer;        /* default JPT_TRANSFER_LINEAR: what the reference stores */
+    int32_t bloom_levels;    /* 0..6, default 0 = no bloom */
+    float   exposure;        /* finite, >= 0, default 1 */
+    float   white;           /* JPT_TONEMAP_REINHARD's white point, finite, > 0, default 4 */
+    float   bloom_threshold; /* finite, >= 0, default 1 */
+    float   bloom_strength;  /* finite, >= 0, default 0.25 */
+} jpt_display_params;
+int jpt_set_display_params(jpt_ctx *ctx, const jpt_display_params *params);   /* NULL: the defaults */
+int jpt_display(jpt_ctx *ctx);
+/* The read-backs wait for the work queued on the context, through its pinned staging buffer like the other jpt_read_*. */
+int jpt_read_display_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes, alpha 255 */
+int jpt_read_display_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: the tone-mapped value before the transfer, (r, g, b, 1) */
+
 /* ---- outputs ---------------------------------------------------------------------------------- */
 
 /* replaces: cs->get_image_uniform_buffer(output_texture_rid) (path_tracing_camera.cpp:228-229):
@@ -690,6 +738,16 @@ int jpt_debug_light_pdf(jpt_ctx *ctx, const uint32_t *inst, const uint32_t *tri,
  * kernels jpt_denoise launches, on that device; JPT_DEVICE_HOST_ONLY: the same weight function compiled for the host. */
 int jpt_debug_atrous(int device_id, int32_t width, int32_t height, const jpt_denoise_params *params, const float *mean4,
                      const float *position_t, const float *normal, const float *albedo, float *out);
+/* jpt_display's transform alone, on a caller-made image of width x height pixels, 4 floats per pixel: mean4 = (r, g, b, unused) is
+ * taken as the image itself (frame count 1; params->source is checked and otherwise ignored).  out_f32 = the tone-mapped image (r,
+ * g, b, 1), out_rgba8 = the encoded image; either may be NULL, not both.  params NULL: the defaults; checked as
+ * jpt_set_display_params checks them (JPT_E_INVALID; this call leaves no message).  device_id >= 0: the kernels jpt_display
+ * launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
+int jpt_debug_display(int device_id, int32_t width, int32_t height, const jpt_display_params *params, const float *mean4,
+                      float *out_f32, uint8_t *out_rgba8);
+/* The 255 code boundaries of JPT_TRANSFER_SRGB: out255[k - 1] = T[k], k = 1..255, the binary32 nearest to the sRGB decoding of
+ * (k - 0.5) / 255; a value v is stored as the number of entries <= v. */
+int jpt_debug_display_srgb_table(float *out255);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

@@ -768,6 +768,17 @@ class PathTracingCamera {
         return out;
     }
     void read_denoised(float* out) { check(ctx, jpt_read_denoised_f32(ctx, out), "jpt_read_denoised_f32"); }
+    // jpt_display and its parameters (nullptr: the defaults): exposure, bloom, tone map and transfer over the accumulation or over
+    // jpt_denoise's image
+    void set_display_params(const jpt_display_params* params) { check(ctx, jpt_set_display_params(ctx, params), "jpt_set_display_params"); }
+    void display() { check(ctx, jpt_display(ctx), "jpt_display"); }
+    PackedByteArray read_display_ldr()
+    {
+        PackedByteArray out((size_t)width * height * 4);
+        check(ctx, jpt_read_display_rgba8(ctx, out.data()), "jpt_read_display_rgba8");
+        return out;
+    }
+    void read_display(float* out) { check(ctx, jpt_read_display_f32(ctx, out), "jpt_read_display_f32"); }
     void read_guides(float* position_t, float* normal, float* albedo) { check(ctx, jpt_read_guides_f32(ctx, position_t, normal, albedo), "jpt_read_guides_f32"); }
 
     int max_bounces = 4;                    // the literal 5 of main.glsl:377 is max_bounces + 1
