@@ -25,6 +25,7 @@ DENOISE_PROGRESSIVE, DENOISE_TEMPORAL, DENOISE_NONE = 0, 1, 2
 OUTPUT_DEPTH = 1
 ENV_SAMPLING_BRDF, ENV_SAMPLING_MIS = 0, 1
 LIGHT_SAMPLING_BRDF, LIGHT_SAMPLING_MIS = 0, 1
+MATERIAL_EXT_NONE, MATERIAL_EXT_TRANSMISSION = 0, 1
 UPLOAD_NATIVE_TREE, UPLOAD_WALK_AS_GIVEN = 0, 1
 DISPLAY_SOURCE_ACCUM, DISPLAY_SOURCE_DENOISED = 0, 1
 TONEMAP_ACES_REF, TONEMAP_REINHARD, TONEMAP_CLAMP = 0, 1, 2
@@ -51,6 +52,7 @@ SYMBOLS = [
     "jpt_debug_env_lookup",
     "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
     "jpt_set_light_sampling", "jpt_multi_set_light_sampling", "jpt_debug_light_tables", "jpt_debug_light_sample", "jpt_debug_light_pdf",
+    "jpt_set_material_extensions", "jpt_multi_set_material_extensions", "jpt_debug_dielectric",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
 ]
@@ -237,6 +239,10 @@ def lib():
         L.jpt_debug_light_tables.argtypes = [vp, u32, vp, vp, vp, vp, vp]
         L.jpt_debug_light_sample.argtypes = [vp, vp, vp, u32, vp, vp, vp]
         L.jpt_debug_light_pdf.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp]
+    if hasattr(L, "jpt_set_material_extensions") or "JPT_LIB" not in os.environ:
+        L.jpt_set_material_extensions.argtypes = [vp, u32]
+        L.jpt_multi_set_material_extensions.argtypes = [vp, u32]
+        L.jpt_debug_dielectric.argtypes = [C.c_int, vp, vp, vp, vp, vp, u32, vp, vp, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

@@ -151,9 +151,14 @@ struct LightingState {
     DevBuf<uint32_t> d_light_cand;
     DevBuf<float4> d_light_tri;
     DevBuf<float> d_light_cdf, d_light_marg;   // per emitter; the marginal CDF's n_blocks entries, then the total power
+    // material extensions (jpt_set_material_extensions): the flags, the context's like the modes; and whether some material of the
+    // host's mirror (c->ref.materials) has a sanitised transmission > 0, scanned whenever the materials may have changed
+    uint32_t material_ext = JPT_MATERIAL_EXT_NONE;
+    bool transmissive_materials = false;
 };
 // The scene changed: the emitter tables are rebuilt at the next render that samples them -- and the emitter list too when the
-// instances or materials may have changed (`listed`); a refit or a mesh update moves the geometry only.  Costs nothing else.
+// instances or materials may have changed (`listed`: the materials are then scanned for a transmissive one as well); a refit or a
+// mesh update moves the geometry only.  Costs nothing else.
 void lights_stale(jpt_ctx* c, bool listed);
 // The lighting a render of `c` would take now, for sizing: kind and miss model, no tables, no side effect.  A bound: while the
 // emitter list is stale the answer is kEmitters whenever the mode asks for them (resolve_lighting decides).

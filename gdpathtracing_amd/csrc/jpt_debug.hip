@@ -119,6 +119,25 @@ __global__ void env_lookup_probe(EnvDev env, const float* __restrict__ dirs3, ui
     rgb_out[3 * (size_t)i + 2] = c.z;
 }
 
+// jpt_debug_dielectric: the dielectric event the *_tx kernels inline (dielectric_event, jpt_shade.h), one case per thread
+__global__ void dielectric_probe(const float* __restrict__ normals3, const float* __restrict__ out_dirs3, const float* __restrict__ ior,
+                                 const uint8_t* __restrict__ front, const float* __restrict__ xi_f, uint32_t n, float* __restrict__ dirs_out,
+                                 float* __restrict__ fresnel_out, uint8_t* __restrict__ event_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 d;
+    float fresnel;
+    const int ev = dielectric_event(f3{normals3[3 * (size_t)i], normals3[3 * (size_t)i + 1], normals3[3 * (size_t)i + 2]},
+                                    f3{out_dirs3[3 * (size_t)i], out_dirs3[3 * (size_t)i + 1], out_dirs3[3 * (size_t)i + 2]}, ior[i], front[i] != 0,
+                                    xi_f[i], d, fresnel);
+    dirs_out[3 * (size_t)i] = d.x;
+    dirs_out[3 * (size_t)i + 1] = d.y;
+    dirs_out[3 * (size_t)i + 2] = d.z;
+    fresnel_out[i] = fresnel;
+    event_out[i] = (uint8_t)ev;
+}
+
 }  // namespace
 
 // jpt_debug_light_sample / jpt_debug_light_pdf (entry points in jpt_lighting.cpp, beside the context's tables): the emitter sampler and
@@ -392,6 +411,56 @@ int jpt_debug_env_lookup(int device_id, const float* rgb, int32_t width, int32_t
     if (d_tex) (void)hipFree(d_tex);
     if (d_dirs) (void)hipFree(d_dirs);
     if (d_out) (void)hipFree(d_out);
+    return rc;
+}
+
+int jpt_debug_dielectric(int device_id, const float* normals3, const float* out_dirs3, const float* ior, const uint8_t* front, const float* xi_f,
+                         uint32_t n, float* dirs_out, float* fresnel_out, uint8_t* event_out)
+{
+    if (n && (!normals3 || !out_dirs3 || !ior || !front || !xi_f || !dirs_out || !fresnel_out || !event_out)) {
+        g_debug_error = "null argument";
+        return JPT_E_INVALID;
+    }
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        for (uint32_t i = 0; i < n; i++) {
+            f3 d;
+            const int ev = dielectric_event(f3{normals3[3 * (size_t)i], normals3[3 * (size_t)i + 1], normals3[3 * (size_t)i + 2]},
+                                            f3{out_dirs3[3 * (size_t)i], out_dirs3[3 * (size_t)i + 1], out_dirs3[3 * (size_t)i + 2]}, ior[i],
+                                            front[i] != 0, xi_f[i], d, fresnel_out[i]);
+            dirs_out[3 * (size_t)i] = d.x;
+            dirs_out[3 * (size_t)i + 1] = d.y;
+            dirs_out[3 * (size_t)i + 2] = d.z;
+            event_out[i] = (uint8_t)ev;
+        }
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    if (n == 0) return JPT_OK;
+    // one allocation: normals, out directions, directions out (3 n floats each), ior, xi_f, fresnel out (n each), front, event out (n bytes each)
+    const size_t f = (size_t)n * sizeof(float);
+    char* d_all = nullptr;
+    int rc = JPT_OK;
+    if ((e = hipMalloc((void**)&d_all, 12 * f + 2 * (size_t)n)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    float *d_n = (float*)d_all, *d_v = d_n + 3 * (size_t)n, *d_d = d_v + 3 * (size_t)n, *d_ior = d_d + 3 * (size_t)n, *d_xi = d_ior + n, *d_f = d_xi + n;
+    uint8_t *d_front = (uint8_t*)(d_f + n), *d_ev = d_front + n;
+    if ((e = hipMemcpy(d_n, normals3, 3 * f, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_v, out_dirs3, 3 * f, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_ior, ior, f, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_xi, xi_f, f, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_front, front, n, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        hipLaunchKernelGGL(dielectric_probe, dim3((n + 255u) / 256u), dim3(256), 0, nullptr, d_n, d_v, d_ior, d_front, d_xi, n, d_d, d_f, d_ev);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "dielectric_probe");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(dirs_out, d_d, 3 * f, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(fresnel_out, d_f, f, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(event_out, d_ev, n, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
     return rc;
 }
 

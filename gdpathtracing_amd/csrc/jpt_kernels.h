@@ -215,7 +215,11 @@ struct Lighting {
     int env_mode = 0;        // the miss model, a run-time value of the *_lt kernels: 0 the gradient, 1 the map, 2 the map with MIS
     EnvDev env = {};         // the map (env_mode != 0; zeroed otherwise)
     EnvSampDev samp = {};    // its sampling tables (env_mode == 2)
-    LightDev lights = {};    // the emitter tables (kEmitters)
+    LightDev lights = {};    // the emitter tables (kEmitters; zeroed otherwise: n == 0)
+    // The scene has a transmissive material and the context reads the extension words (jpt_set_material_extensions): the launches
+    // that shade take the general *_tx kernels instead of `kind`'s, with env_mode and `lights` as they are; the primary, trace,
+    // occlude and accumulate launches stay those of `kind` and the miss model.
+    bool transmissive = false;
     bool map_queues() const { return env_mode == 2; }           // the workspace holds the map's shadow queues (wf2_occlude) ...
     bool emitter_queues() const { return kind == kEmitters; }   // ... the emitters' (wf2_occlude_lt)
 };

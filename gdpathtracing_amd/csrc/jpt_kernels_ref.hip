@@ -188,7 +188,7 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 }
 
 
-// the frame kernel (jpt_ref_frame.h): the default one, then ref_frame_kernel_env, ref_frame_kernel_mis, ref_frame_kernel_lt
+// the frame kernel (jpt_ref_frame.h): the default one, then ref_frame_kernel_env, ref_frame_kernel_mis, ref_frame_kernel_lt, ref_frame_kernel_tx
 #define JPT_ENV 0
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
@@ -199,6 +199,9 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
 #define JPT_ENV 3
+#include "jpt_ref_frame.h"
+#undef JPT_ENV
+#define JPT_ENV 4
 #include "jpt_ref_frame.h"
 #undef JPT_ENV
 
@@ -218,6 +221,11 @@ void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FramePara
     dim3 grid((fp.width + 31) / 32, (fp.local_rows + 7) / 8), block(256);
     const bool ties = ds.x.ok && ds.reach_tri != nullptr && !fp.debug_steps;
     with_consts<2, 2>([&](auto C, auto TIES) {
+        if (lg.transmissive) {
+            hipLaunchKernelGGL((ref_frame_kernel_tx<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lg.env, lg.samp,
+                               lg.lights, lg.env_mode);
+            return;
+        }
         switch (lg.kind) {
         case Lighting::kEmitters:
             hipLaunchKernelGGL((ref_frame_kernel_lt<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lg.env, lg.samp,

@@ -691,7 +691,7 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
     if (COUNT) flush_counters(cnt, counters);
 }
 
-// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, the *_env ones, the *_mis ones, then the *_lt ones
+// the kernels that see the paths' misses (jpt_wf2_paths.h): the default ones, the *_env ones, the *_mis ones, the *_lt ones, then the *_tx ones
 #define JPT_ENV 0
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
@@ -702,6 +702,9 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #define JPT_ENV 3
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 4
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 
@@ -878,6 +881,12 @@ static Wf2Layout wf2_layout(void* base, const FrameParams& fp, int groups, const
         L.glnee[g] = carve_nee(g, mis ? &L.gnee[g] : nullptr);
         if (!mis) L.gnee[g] = Wf2Nee{nullptr, nullptr, nullptr, nullptr, L.glnee[g].pdf};
     }
+    // (a *_tx render without emitter queues: its kernels queue no emitter shadow ray, but keep the per-path densities there)
+    for (int g = 0; g < groups && lg.transmissive && !lg.emitter_queues(); g++) {
+        float* pdf = mis ? L.gnee[g].pdf : (float*)carve((size_t)L.gdm[g].slots_per_frame * (size_t)L.gfp[g].n_frames * sizeof(float));
+        L.glnee[g] = Wf2Nee{nullptr, nullptr, nullptr, nullptr, pdf};
+        if (!mis) L.gnee[g] = L.glnee[g];
+    }
     return L;
 }
 
@@ -965,6 +974,11 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {
             with_consts<2, 2, 3>([&](auto C, auto LAST, auto TEX) {
+                if (lg.transmissive) {
+                    hipLaunchKernelGGL((wf2_shade_tx<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, lg.env, lg.samp, lg.lights, nee,
+                                       lnee, lg.env_mode);
+                    return;
+                }
                 switch (lg.kind) {
                 case Lighting::kEmitters:
                     hipLaunchKernelGGL((wf2_shade_lt<C, LAST, TEX>), sgrid, block, 0, st, sh, wb, dm, gp, cam.far_, b, counters, lg.env, lg.samp, lg.lights, nee,
@@ -1001,6 +1015,11 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (sh.reach_tri) {  // the paths set aside because their hit is undecidable on the native tree: finished exactly
             const dim3 rgrid(256), rblock(64);   // (blocks past the set-aside count exit at once; more records than threads: grid-stride)
             with_consts<2, 3>([&](auto C, auto W) {
+                if (lg.transmissive) {
+                    hipLaunchKernelGGL((wf2_finish_tx<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, lg.env, lg.samp,
+                                       lg.lights, nee, lnee, lg.env_mode);
+                    return;
+                }
                 switch (lg.kind) {
                 case Lighting::kEmitters:
                     hipLaunchKernelGGL((wf2_finish_lt<C, W != 0, W == 2>), rgrid, rblock, 0, st, sc, sx, sh, wb, dm, gp, cam.far_, counters, lg.env, lg.samp,

@@ -119,7 +119,11 @@ namespace jpt {
 void lights_stale(jpt_ctx* c, bool listed)
 {
     c->lighting.light_table_stale = true;
-    if (listed) c->lighting.light_cand_stale = true;
+    if (!listed) return;
+    c->lighting.light_cand_stale = true;
+    bool any = false;
+    for (const RefMaterial& m : c->ref.materials) any = any || material_transmission(m.padding[0]) > 0.0f;
+    c->lighting.transmissive_materials = any;
 }
 
 Lighting lighting_bound(const jpt_ctx* c)
@@ -132,6 +136,8 @@ Lighting lighting_bound(const jpt_ctx* c)
     const bool emitters = l.light_sampling == JPT_LIGHT_SAMPLING_MIS && c->device >= 0 && c->scene_ready && (l.light_cand_stale || !l.light_cand_h.empty());
     lg.env_mode = mis ? 2 : (l.env_set ? 1 : 0);
     lg.kind = emitters ? Lighting::kEmitters : (mis ? Lighting::kMapMis : (l.env_set ? Lighting::kMap : Lighting::kSky));
+    // (the extension words are read only when the flag says so AND some material then transmits: otherwise today's kernels)
+    lg.transmissive = (l.material_ext & JPT_MATERIAL_EXT_TRANSMISSION) != 0u && l.transmissive_materials && c->device >= 0 && c->scene_ready;
     return lg;
 }
 
@@ -378,6 +384,15 @@ int jpt_set_light_sampling(jpt_ctx* c, int32_t mode)
     if (mode != JPT_LIGHT_SAMPLING_BRDF && mode != JPT_LIGHT_SAMPLING_MIS) return fail(c, JPT_E_INVALID, "jpt_set_light_sampling: unknown mode");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: light sampling runs on the device");
     c->lighting.light_sampling = mode;   // (the tables are made at the first render that samples them)
+    return JPT_OK;
+}
+
+int jpt_set_material_extensions(jpt_ctx* c, uint32_t flags)
+{
+    if (!c) return JPT_E_INVALID;
+    if ((flags & ~(uint32_t)JPT_MATERIAL_EXT_TRANSMISSION) != 0u) return fail(c, JPT_E_INVALID, "jpt_set_material_extensions: unknown flag");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: material extensions are read on the device");
+    c->lighting.material_ext = flags;   // (whether a render takes the *_tx kernels: lighting_bound, from this and the materials)
     return JPT_OK;
 }
 

@@ -291,6 +291,16 @@ int jpt_multi_set_light_sampling(jpt_multi* m, int32_t mode)
     return JPT_OK;
 }
 
+int jpt_multi_set_material_extensions(jpt_multi* m, uint32_t flags)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_material_extensions(m->ctx[r], flags);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_set_camera(jpt_multi* m, const void* camera160)
 {
     if (!m) return JPT_E_INVALID;

@@ -1,5 +1,5 @@
 // jpt_ref_frame.h -- ref_frame_kernel, the audit route's one kernel (jpt_kernels_ref.hip), which sees the paths' misses.  Included
-// four times by jpt_kernels_ref.hip, as jpt_wf2_paths.h is by jpt_kernels_wf2.hip; launch_ref_frame switches on Lighting::kind:
+// five times by jpt_kernels_ref.hip, as jpt_wf2_paths.h is by jpt_kernels_wf2.hip; launch_ref_frame switches on Lighting::kind:
 //   JPT_ENV 0   ref_frame_kernel, main.glsl's gradient (sample_sky): the same source, token for token, as before the map existed;
 //   JPT_ENV 1   ref_frame_kernel_env (jpt_set_environment): one more parameter, the map, and env_radiance at the miss;
 //   JPT_ENV 2   ref_frame_kernel_mis (JPT_ENV_SAMPLING_MIS): also the map's sampling tables; below the last bounce each vertex casts
@@ -9,9 +9,22 @@
 //               0 gradient, 1 map, 2 map with JPT_ENV_SAMPLING_MIS); each vertex below the last bounce casts the map's shadow ray
 //               (env_mode 2), then the emitters' (ray_trace_tlas with hitInfo.t preset to tmax: blocked when it ends below
 //               tmax), and emission found at bounce >= 1 is weighted -- the arithmetic of jpt_wf2_paths.h's *_lt kernels.
+//   JPT_ENV 4   ref_frame_kernel_tx (JPT_MATERIAL_EXT_TRANSMISSION over a scene with a transmissive material): ref_frame_kernel_lt with
+//               emitter sampling on or off at run time (lt.n == 0) and the transmission lobe at every hit (transmission_step) --
+//               the arithmetic of jpt_wf2_paths.h's *_tx kernels.
 // (No include guard: that is the point.)
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
+#if JPT_ENV == 4
+#define JPT_ENV_NAME(name) name##_tx
+#define JPT_LTOTAL (lt.n != 0u ? lt.marg[lt.n_blocks] : 0.0f)
+#define JPT_MISS_WEIGHT env_miss_weight_tx
+#define JPT_HIT_WEIGHT light_hit_weight_tx
+#else
 #define JPT_ENV_NAME(name) name##_lt
+#define JPT_LTOTAL lt.marg[lt.n_blocks]
+#define JPT_MISS_WEIGHT env_miss_weight
+#define JPT_HIT_WEIGHT light_hit_weight
+#endif
 #define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, LightDev lt, int env_mode
 #define JPT_SKY(d) (env_mode != 0 ? env_radiance(env, d) : sample_sky(d))
 #elif JPT_ENV == 2
@@ -50,8 +63,8 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
 #if JPT_ENV >= 2
         float p_brdf = 0.0f;   // the BRDF density of the current ray's direction (bounces >= 1)
 #endif
-#if JPT_ENV == 3
-        const float ltotal = lt.marg[lt.n_blocks];
+#if JPT_ENV >= 3
+        const float ltotal = JPT_LTOTAL;
 #endif
         if (fp.debug_steps) {   // #ifdef DEBUG_STEPS (main.glsl:358-361, 423-427): the primary ray's triangle tests / 256, depth = far
             RefHit hit;
@@ -68,8 +81,8 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
 #if JPT_ENV == 2
                 if (i > 0) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, p_brdf);
                 else
-#elif JPT_ENV == 3
-                if (i > 0 && env_mode == 2) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, p_brdf);
+#elif JPT_ENV >= 3
+                if (i > 0 && env_mode == 2) radiance = radiance + (throughput * JPT_SKY(ray.d)) * JPT_MISS_WEIGHT(env, es, ray.d, p_brdf);
                 else
 #endif
                 radiance = radiance + throughput * JPT_SKY(ray.d);
@@ -100,16 +113,23 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             Hit h;
             h.t = hit.t; h.u = hit.u; h.v = hit.v; h.tri = hit.tri; h.inst = hit.inst; h.lo = hit.lo; h.ld = hit.ld;
             const Shading s = get_shading_data(sh, h, hit.front, load_shade_tri(sh, h.tri));
-#if JPT_ENV == 3
-            if (i > 0) radiance = radiance + (throughput * s.emission) * light_hit_weight(lt, ltotal, sh, h, s, ray.o, ray.d, &p_brdf);
+#if JPT_ENV >= 3
+            if (i > 0) radiance = radiance + (throughput * s.emission) * JPT_HIT_WEIGHT(lt, ltotal, sh, h, s, ray.o, ray.d, &p_brdf);
             else
 #endif
             radiance = radiance + throughput * s.emission;
             if (i == 0) depth = length3(s.position - ray.o);
+#if JPT_ENV == 4
+            // (the transmission lobe: a dielectric vertex casts no shadow ray, never ends the path and leaves the sentinel density)
+            if (transmission_step(s, material_ext(sh, h, load_shade_tri(sh, h.tri)), hit.front, sx, sy, ray, throughput)) {
+                p_brdf = kDeltaDensity;
+                continue;
+            }
+#endif
 #if JPT_ENV >= 2
             if (i < fp.max_bounces) {
                 f3 l, c;
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
                 if (env_mode == 2 && env_nee(s, env, es, sx, sy, throughput, l, c)) {
 #else
                 if (env_nee(s, env, es, sx, sy, throughput, l, c)) {
@@ -122,7 +142,7 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
                     DevCounters none = {};
                     if (!ray_trace_tlas<false>(sc, sray, sh_hit, none)) radiance = radiance + c;
                 }
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
                 f3 lo3, ll, lc;
                 float tmax;
                 if (ltotal > 0.0f && light_nee(s, lt, ltotal, sx, sy, throughput, lo3, ll, tmax, lc)) {
@@ -153,3 +173,8 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM
 #undef JPT_SKY
+#ifdef JPT_LTOTAL
+#undef JPT_LTOTAL
+#undef JPT_MISS_WEIGHT
+#undef JPT_HIT_WEIGHT
+#endif

@@ -239,6 +239,67 @@ __host__ __device__ __forceinline__ void light_emission(const RefInstance* insta
     le[2] = m.emission.z * em;
 }
 
+// ---- transparent materials (jpt_set_material_extensions, JPT_MATERIAL_EXT_TRANSMISSION) --------------------------------------
+//
+// GpuMaterial's padding[0] / padding[1] as transmission / ior, sanitised here: what the *_tx kernels and the host's scan of its
+// materials mirror (lighting_bound, jpt_lighting.cpp) both run.
+__host__ __device__ __forceinline__ float material_transmission(float t)   // NaN -> 0, then [0, 1]
+{
+    t = t == t ? t : 0.0f;
+    return t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+}
+__host__ __device__ __forceinline__ float material_ior(float i)   // NaN -> 1, then [1, 4]
+{
+    i = i == i ? i : 1.0f;
+    return i < 1.0f ? 1.0f : (i > 4.0f ? 4.0f : i);
+}
+
+// What a dielectric vertex leaves where the BRDF density of its sampled direction would go (Wf2Nee::pdf, the audit kernel's
+// p_brdf): the next vertex's emission and miss weights are exactly 1.  No density is -1 (they are >= 0 or NaN).
+constexpr float kDeltaDensity = -1.0f;
+
+// One smooth dielectric event (DESIGN.md "Pinned semantics": a fixed sequence of binary32 operations; tests/np_transmission.py
+// restates it).  n: the facing shading normal, v: the direction back along the ray (both unit), ior: the material's (sanitised
+// here), front: the ray arrives from outside.  m = n, or -n when n.v < 0 (a shading normal tilted past the ray: the event happens
+// on the side the ray is on); c = min(|n.v|, 1); eta = 1 / ior (front) or ior, eta' its inverse ratio, ior or 1 / ior;
+// k = 1 - (eta eta)(1 - c c).  k < 0: total internal reflection, F = 1, returns 2.  Otherwise ct = sqrt(k),
+// F = 0.5 (rs rs + rp rp), rs = (c - eta' ct) / (c + eta' ct), rp = (ct - eta' c) / (ct + eta' c); an F that is not <= 1 (0 / 0 at
+// grazing incidence with ior 1) is 1.  xi_f < F: reflection, returns 1; else refraction, returns 0.
+// Reflection (1, 2): d = m (2 c) - v, as it is.  Refraction: d = normalize(m (eta c - ct) - v eta).  No NaN from unit n, v.
+__host__ __device__ __forceinline__ int dielectric_event(f3 n, f3 v, float ior, bool front, float xi_f, f3& d, float& fresnel)
+{
+    ior = material_ior(ior);
+    const float ndv = n.x * v.x + n.y * v.y + n.z * v.z;
+    const bool below = ndv < 0.0f;
+    const f3 m{below ? -n.x : n.x, below ? -n.y : n.y, below ? -n.z : n.z};
+    float c = __builtin_fabsf(ndv);
+    c = c < 1.0f ? c : 1.0f;
+    const float inv = 1.0f / ior;
+    const float eta = front ? inv : ior, etap = front ? ior : inv;
+    const float k = 1.0f - (eta * eta) * (1.0f - c * c);
+    int event = 2;
+    float ct = 0.0f;
+    fresnel = 1.0f;
+    if (!(k < 0.0f)) {
+        ct = __builtin_sqrtf(k);
+        const float a = etap * ct, b = etap * c;
+        const float rs = (c - a) / (c + a), rp = (ct - b) / (ct + b);
+        const float f = 0.5f * (rs * rs + rp * rp);
+        fresnel = f <= 1.0f ? f : 1.0f;
+        event = xi_f < fresnel ? 1 : 0;
+    }
+    if (event != 0) {
+        const float t = 2.0f * c;
+        d = f3{m.x * t - v.x, m.y * t - v.y, m.z * t - v.z};
+    } else {
+        const float g = eta * c - ct;
+        const f3 r{m.x * g - v.x * eta, m.y * g - v.y * eta, m.z * g - v.z * eta};
+        const float il = 1.0f / __builtin_sqrtf(r.x * r.x + r.y * r.y + r.z * r.z);
+        d = f3{r.x * il, r.y * il, r.z * il};
+    }
+    return event;
+}
+
 #if defined(__HIPCC__)   // (everything below is device code; the host layer -- jpt_capi.cpp, jpt_multi.cpp -- sees the structs above only)
 
 // ---- RNG (main.glsl:163-181) -----------------------------------------------------------------
@@ -696,6 +757,76 @@ __device__ __forceinline__ float light_hit_weight(const LightDev& lt, float tota
     const float pb = *p_brdf;
     const float wt = (pb * pb) / (pb * pb + pl * pl);
     return wt == wt ? wt : 1.0f;
+}
+
+// ---- the transmission lobe (JPT_MATERIAL_EXT_TRANSMISSION, the *_tx kernels) ---------------------------------------------------
+//
+// What the lobe reads of the hit's material beside the Shading record: the tint (albedo times its texture, as get_shading_data
+// forms it) and the two extension words, sanitised.  The lookup and the texture fetch are get_shading_data's own, written again
+// so that its source stays what the other kernel families compile; after inlining the compiler keeps one copy of each.
+struct MaterialExt {
+    f3 tint;
+    float transmission, ior;
+};
+template <int TEX = 3>
+__device__ __forceinline__ MaterialExt material_ext(const SceneShading& sc, const Hit& h, const ShadeTriRegs& tr)
+{
+    const float4 q2 = tr.q2, q3 = tr.q3;
+    const uint32_t slot = __float_as_uint(q3.w);
+    const unsigned long long word = (unsigned long long)h.inst * 44ull + 41ull + (unsigned long long)slot;
+    uint32_t mat_id = word < (unsigned long long)sc.n_instances * 44ull ? reinterpret_cast<const uint32_t*>(sc.instances)[word] : 0u;
+    if (mat_id >= sc.n_materials) mat_id = 0;
+    const RefMaterial& material = sc.materials[mat_id];
+    const float u = h.u, v = h.v;
+    const float w0 = 1.0f - u - v;
+    f3 albedo = mk3(material.albedo.x, material.albedo.y, material.albedo.z);
+    if (material.albedo_texture_index >= 0) {
+        const float uvx = q2.y * w0 + q2.w * u + q3.y * v;
+        const float uvy = q2.z * w0 + q3.x * u + q3.z * v;
+        albedo = albedo * (TEX == 0 ? mk3(0.0f, 0.0f, 0.0f) : sample_texture<(TEX == 3 ? 0 : TEX)>(sc, uvx, uvy, material.albedo_texture_index));
+    }
+    return MaterialExt{albedo, material_transmission(material.padding[0]), material_ior(material.padding[1])};
+}
+
+// The lobe choice and, when it falls on the lobe, the dielectric vertex.  (xi_t, xi_f): one pcg2d round of a COPY of the vertex's
+// seeds hashed as (sx ^ 0x5bd1e995, sy ^ 0x1b873593) -- constants of its own, the path's sequence does not advance.  xi_t >=
+// transmission: false, nothing is touched: the vertex is the opaque one (NEE, bounce_step).  Otherwise true: `ray` is the next
+// segment (dielectric_event; origin position + normal * 0.001 when reflected, - when refracted), a refracted path's throughput
+// is tinted, and the path's own draw for this vertex is taken and discarded: one sequence position per vertex either way.
+// The lanes of a wave choose at random: the hashed draw, the tint (fetched with the shading record) and the offset origin are
+// made outside the branch on the event.
+__device__ __forceinline__ bool transmission_step(const Shading& s, const MaterialExt& me, bool front, uint32_t& sx, uint32_t& sy, Ray& ray,
+                                                  f3& throughput)
+{
+    uint32_t hx = sx ^ 0x5bd1e995u, hy = sy ^ 0x1b873593u;
+    float xi_t, xi_f;
+    pcg2d(hx, hy, xi_t, xi_f);
+    if (!(xi_t < me.transmission)) return false;
+    f3 d;
+    float fresnel;
+    const int event = dielectric_event(s.normal, s.out_dir, me.ior, front, xi_f, d, fresnel);
+    const bool refracted = event == 0;
+    ray.o = s.position + s.normal * (refracted ? -0.001f : 0.001f);
+    ray.d = d;
+    ray.rD = rcp3(d);
+    const f3 tinted = throughput * me.tint;
+    if (refracted) throughput = tinted;
+    float r0, r1;
+    pcg2d(sx, sy, r0, r1);
+    return true;
+}
+// env_miss_weight / light_hit_weight behind a vertex that may have been a dielectric one: its sentinel density means weight 1
+__device__ __forceinline__ float env_miss_weight_tx(const EnvDev& e, const EnvSampDev& es, f3 d, float p_brdf)
+{
+    if (p_brdf == kDeltaDensity) return 1.0f;
+    return env_miss_weight(e, es, d, p_brdf);
+}
+__device__ __forceinline__ float light_hit_weight_tx(const LightDev& lt, float total, const SceneShading& sh, const Hit& h, const Shading& s,
+                                                    f3 o, f3 d, const float* p_brdf)
+{
+    if (!(light_lum(s.emission.x, s.emission.y, s.emission.z) > 0.0f) || !(total > 0.0f)) return 1.0f;
+    if (*p_brdf == kDeltaDensity) return 1.0f;
+    return light_hit_weight(lt, total, sh, h, s, o, d, p_brdf);
 }
 
 __device__ __forceinline__ f3 aces_film(f3 x)  // progressive_rendering.glsl:19-26

@@ -1,5 +1,5 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
-// which wf2_finish shares), wf2_finish and wf2_accumulate.  Included four times by jpt_kernels_wf2.hip, inside its anonymous namespace:
+// which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace:
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -16,10 +16,25 @@
 //               last bounce queues the map's shadow ray (env_mode 2) and the emitters' (light_nee, bounded by tmax); a hit at
 //               bounce >= 1 weighs its emission against the emitter strategy (light_hit_weight).  They pair with the primary and
 //               accumulation launches of the miss model in use.
+//   JPT_ENV 4   the *_tx kernels (jpt_set_material_extensions, JPT_MATERIAL_EXT_TRANSMISSION over a scene with a transmissive material):
+//               shade_entry_tx, wf2_shade_tx and wf2_finish_tx, the general family: the *_lt kernels with emitter sampling on or
+//               off at run time (lt.n == 0: no table is read) and the transmission lobe at every hit below the last bounce
+//               (transmission_step, jpt_shade.h): a dielectric vertex queues no shadow ray and leaves kDeltaDensity where the
+//               BRDF density goes, so the next vertex's weights are 1.  One family for every lighting a glass scene is put under.
 // A run-time branch on the map in the default kernels would cost them registers; a template parameter would change their names.
-// (No include guard: that is the point.)  Which family a render launches: Lighting::kind (jpt_kernels.h), decided on the host.
-#if JPT_ENV == 3
+// (No include guard: that is the point.)  Which family a render launches: Lighting::kind, or *_tx with Lighting::transmissive (jpt_kernels.h), decided on the host.
+#if JPT_ENV >= 3
+#if JPT_ENV == 4
+#define JPT_ENV_NAME(name) name##_tx
+#define JPT_LTOTAL (lt.n != 0u ? lt.marg[lt.n_blocks] : 0.0f)   // (emitter sampling off: no tables, nothing is read through them)
+#define JPT_MISS_WEIGHT env_miss_weight_tx
+#define JPT_HIT_WEIGHT light_hit_weight_tx
+#else
 #define JPT_ENV_NAME(name) name##_lt
+#define JPT_LTOTAL lt.marg[lt.n_blocks]
+#define JPT_MISS_WEIGHT env_miss_weight
+#define JPT_HIT_WEIGHT light_hit_weight
+#endif
 #define JPT_ENV_PARAM , EnvDev env, EnvSampDev es, LightDev lt, Wf2Nee nee, Wf2Nee lnee, int env_mode
 #define JPT_ENV_ARG , env, es, lt, nee, lnee, env_mode
 #define JPT_NEE_PARAM , bool& shadow, float4& so, float4& sd, float4& sc4, bool& lshadow, float4& lso, float4& lsd, float4& lsc
@@ -232,7 +247,7 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
     // (MIS: a shadow ray of this vertex, for wf2_occlude: so = origin.xyz | path id + kNeeFinal when the path ends here, sd = the map
     // direction, sc4 = the contribution if unoccluded.  rad[path] then holds the radiance so far, which the shadow ray adds to.)
     shadow = false;
-#elif JPT_ENV == 3
+#elif JPT_ENV >= 3
     // (lights: the map's shadow ray as above when env_mode is 2, and the emitters' in lso / lsd (direction, tmax) / lsc; when both
     // are cast the map's lands first, and the one that lands last stores a path that ends here)
     shadow = false;
@@ -326,8 +341,8 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
 #if JPT_ENV == 2
         if (bounce > 0) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, nee.pdf[p]);
         else
-#elif JPT_ENV == 3
-        if (bounce > 0 && env_mode == 2) radiance = radiance + (throughput * JPT_SKY(ray.d)) * env_miss_weight(env, es, ray.d, lnee.pdf[p]);
+#elif JPT_ENV >= 3
+        if (bounce > 0 && env_mode == 2) radiance = radiance + (throughput * JPT_SKY(ray.d)) * JPT_MISS_WEIGHT(env, es, ray.d, lnee.pdf[p]);
         else
 #endif
         radiance = radiance + throughput * JPT_SKY(ray.d);
@@ -335,16 +350,23 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
     } else {
         if (COUNT) cnt.shaded_hits++;
         const Shading s = get_shading_data<TEX>(sh, h, (hb >> 31) != 0u, stri);
-#if JPT_ENV == 3
-        const float ltotal = lt.marg[lt.n_blocks];
-        if (bounce > 0) radiance = radiance + (throughput * s.emission) * light_hit_weight(lt, ltotal, sh, h, s, ray.o, ray.d, lnee.pdf + p);
+#if JPT_ENV >= 3
+        const float ltotal = JPT_LTOTAL;
+        if (bounce > 0) radiance = radiance + (throughput * s.emission) * JPT_HIT_WEIGHT(lt, ltotal, sh, h, s, ray.o, ray.d, lnee.pdf + p);
         else
 #endif
         radiance = radiance + throughput * s.emission;
         if (bounce == 0 && (int)f == fp.depth_frame) wb.first_depth[slot] = length3(s.position - ray.o);
 #if JPT_ENV >= 2
         if (!LAST && bounce < fp.max_bounces) {
-#if JPT_ENV == 3
+#if JPT_ENV == 4
+          // (the transmission lobe: a dielectric vertex casts no shadow ray, never ends the path and leaves the sentinel density)
+          if (transmission_step(s, material_ext<TEX>(sh, h, stri), (hb >> 31) != 0u, sx, sy, ray, throughput)) {
+            alive = true;
+            JPT_PDF[p] = kDeltaDensity;
+          } else {
+#endif
+#if JPT_ENV >= 3
           if (env_mode == 2) {
 #endif
             f3 l, c;
@@ -355,7 +377,7 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
                 sd = make_float4(l.x, l.y, l.z, 0.0f);
                 sc4 = make_float4(c.x, c.y, c.z, 0.0f);
             }
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
           }
             if (ltotal > 0.0f) {
                 f3 lo3, ll, lc;
@@ -371,6 +393,9 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
             float density;
             alive = bounce_step_pdf(s, sx, sy, ray, throughput, density);
             if (alive) JPT_PDF[p] = density;
+#if JPT_ENV == 4
+          }
+#endif
         }
 #else
         if (!LAST && bounce < fp.max_bounces) alive = bounce_step(s, sx, sy, ray, throughput);
@@ -379,7 +404,7 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
     }
     if (alive) {
         // (radiance starts as +0 and +0 + x is x or +0, never -0: "unchanged and never written" means exactly +0)
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
         const bool changed = shadow || lshadow || radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
 #elif JPT_ENV == 2
         const bool changed = shadow || radiance.x != radiance_in.x || radiance.y != radiance_in.y || radiance.z != radiance_in.z;
@@ -396,7 +421,7 @@ __device__ __forceinline__ bool JPT_ENV_NAME(shade_entry)(const SceneShading& sh
             wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
             so.w = __uint_as_float(p | kNeeFinal);
         } else
-#elif JPT_ENV == 3
+#elif JPT_ENV >= 3
         if (shadow || lshadow) {   // the path ends here: the shadow ray that lands last (the emitters') stores its final value
             wb.rad[p] = make_float4(radiance.x, radiance.y, radiance.z, 0.0f);
             if (lshadow) lso.w = __uint_as_float(p | kNeeFinal);
@@ -432,7 +457,7 @@ __global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVE
     bool shadow = false;
     float4 so, sd, sc4;
 #endif
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
     bool lshadow = false;
     float4 lso, lsd, lsc;
 #endif
@@ -460,7 +485,7 @@ __global__ __launch_bounds__(kBlock, LAST ? 8 : (TEX == 0 ? JPT_SHADE_NOTEX_WAVE
         }
     }
 #endif
-#if JPT_ENV == 3
+#if JPT_ENV >= 3
     if (!LAST) {   // the emitters' shadow rays, into their own queue (traced after the map's: the two never share a launch)
         const unsigned long long lm = __ballot(lshadow);
         if (lm) {
@@ -565,10 +590,10 @@ __global__ __launch_bounds__(64) void JPT_ENV_NAME(wf2_finish)(WideSceneDev sc, 
                 nee_land(wb, fp.accum_mode, so, sc4, occ.hit.t < 1e9f);
             }
             if (!alive) break;
-#elif JPT_ENV == 3
+#elif JPT_ENV >= 3
             bool shadow, lshadow;
             float4 so, sd, sc4, lso, lsd, lsc;
-            const bool alive = shade_entry_lt<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt JPT_ENV_ARG JPT_NEE_ARG);
+            const bool alive = JPT_ENV_NAME(shade_entry)<COUNT>(sh, wb, dm, fp, cam_far, bounce, ro, rd, tin, ha, hb, false, unreachable, no, nd, nt, cnt JPT_ENV_ARG JPT_NEE_ARG);
             if (shadow) {   // the map's shadow ray at once (wf2_occlude's walk), then the emitters' (wf2_occlude_lt's, bounded by tmax)
                 Traversal<COUNT, W4> occ;
                 const typename Traversal<COUNT, W4>::Stack ost{nullptr, stack_mem, 0, 0, kDepth};
@@ -827,4 +852,9 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 #undef JPT_SKY
 #ifdef JPT_PDF
 #undef JPT_PDF
+#endif
+#ifdef JPT_LTOTAL
+#undef JPT_LTOTAL
+#undef JPT_MISS_WEIGHT
+#undef JPT_HIT_WEIGHT
 #endif

@@ -65,6 +65,23 @@ def _env_rotation(rotation):
     return np.ascontiguousarray(rotation, dtype=np.float32).reshape(9)
 
 
+def debug_dielectric(device_id, normals, out_dirs, ior, front, xi_f):
+    """jpt_debug_dielectric: the dielectric event of capi.MATERIAL_EXT_TRANSMISSION for n cases -- (dirs [n, 3] float32, fresnel [n]
+    float32, event [n] uint8: 0 refract, 1 reflect, 2 total internal reflection).  device_id -1: the host's copy of the function."""
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    out = np.ascontiguousarray(out_dirs, np.float32).reshape(-1, 3)
+    n = len(nrm)
+    ior = np.ascontiguousarray(np.broadcast_to(np.asarray(ior, np.float32), (n,)))
+    front = np.ascontiguousarray(np.broadcast_to(np.asarray(front), (n,)).astype(np.uint8))
+    xi_f = np.ascontiguousarray(np.broadcast_to(np.asarray(xi_f, np.float32), (n,)))
+    dirs, fresnel, event = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    L = capi.lib()
+    rc = L.jpt_debug_dielectric(int(device_id), _ptr(nrm), _ptr(out), _ptr(ior), _ptr(front), _ptr(xi_f), n, _ptr(dirs), _ptr(fresnel), _ptr(event))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_dielectric failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return dirs, fresnel, event
+
+
 class Context:
     """One jpt_ctx (one GPU).  Thin, explicit wrapper: every method is one C-ABI call."""
 
@@ -263,6 +280,11 @@ class Context:
         """jpt_set_light_sampling: capi.LIGHT_SAMPLING_BRDF (default) or capi.LIGHT_SAMPLING_MIS (emissive triangles sampled with
         shadow rays, combined with BRDF sampling by the power heuristic), for later renders."""
         self._ck(self._lib.jpt_set_light_sampling(self.h, int(mode)), "jpt_set_light_sampling")
+
+    def set_material_extensions(self, flags):
+        """jpt_set_material_extensions: capi.MATERIAL_EXT_NONE (default) or capi.MATERIAL_EXT_TRANSMISSION (padding[0:2] of every
+        material are its transmission and ior), for later renders."""
+        self._ck(self._lib.jpt_set_material_extensions(self.h, int(flags)), "jpt_set_material_extensions")
 
     def debug_light_tables(self):
         """jpt_debug_light_tables: (pairs [n, 2] uint32, tri [n, 3, 4] float32, cdf [n], marg [blocks + 1]) of the emitter tables"""
@@ -665,6 +687,9 @@ class MultiContext:
 
     def set_light_sampling(self, mode):
         self._ck(self._lib.jpt_multi_set_light_sampling(self.h, int(mode)), "jpt_multi_set_light_sampling")
+
+    def set_material_extensions(self, flags):
+        self._ck(self._lib.jpt_multi_set_material_extensions(self.h, int(flags)), "jpt_multi_set_material_extensions")
 
     def set_camera(self, camera_block):
         cam = np.ascontiguousarray(camera_block, dtype=wire.CAMERA).reshape(1)

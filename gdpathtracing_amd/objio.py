@@ -105,11 +105,13 @@ def pack_texture_array(images, resolution: int) -> np.ndarray:
     return np.stack(layers)
 
 
-def load_mtl(text: str):
+def load_mtl(text: str, transmission: bool = False):
     """Wavefront MTL -> (dict name -> GpuMaterial record (wire.MATERIAL), list of albedo map file names), with the
     conventions of include/jpt_host.hpp::load_mtl (the C++ product code; this is its test mirror): Kd -> albedo; Ke ->
     emission colour, energy multiplier 1 or the largest component when that exceeds 1; Pr -> roughness, else
-    sqrt(2 / (Ns + 2)) from the Phong exponent; Pm -> metallic; map_Kd -> albedo texture index in order of first use."""
+    sqrt(2 / (Ns + 2)) from the Phong exponent; Pm -> metallic; map_Kd -> albedo texture index in order of first use.
+    transmission (off by default: the result is then what it was before the extension existed): Ni -> ior, and d x -> transmission
+    = 1 - x, Tr x -> transmission = x, whichever comes last (capi.MATERIAL_EXT_TRANSMISSION)."""
     from .scenes import material
     out, maps = {}, []
     cur = None
@@ -118,7 +120,8 @@ def load_mtl(text: str):
         if not p or p[0].startswith("#"):
             continue
         if p[0] == "newmtl":
-            cur = dict(albedo=(1.0, 1.0, 1.0), emission=(0.0, 0.0, 0.0), energy=1.0, metallic=0.0, roughness=1.0, texture=-1, has_pr=False)
+            cur = dict(albedo=(1.0, 1.0, 1.0), emission=(0.0, 0.0, 0.0), energy=1.0, metallic=0.0, roughness=1.0, texture=-1, has_pr=False,
+                       transmission=np.float32(0.0), ior=np.float32(0.0))
             out[p[1] if len(p) > 1 else ""] = cur
         elif cur is None:
             continue
@@ -137,10 +140,17 @@ def load_mtl(text: str):
             cur["roughness"] = np.sqrt(np.float32(2.0) / (max(np.float32(p[1]), np.float32(0.0)) + np.float32(2.0)))
         elif p[0] == "Pm":
             cur["metallic"] = np.float32(p[1])
+        elif transmission and p[0] == "Ni":
+            cur["ior"] = np.float32(p[1])
+        elif transmission and p[0] == "d":
+            cur["transmission"] = np.float32(1.0) - np.float32(p[1])
+        elif transmission and p[0] == "Tr":
+            cur["transmission"] = np.float32(p[1])
         elif p[0] == "map_Kd":
             if p[1] not in maps:
                 maps.append(p[1])
             cur["texture"] = maps.index(p[1])
     recs = {k: material(albedo=v["albedo"], emission=v["emission"], energy=float(v["energy"]), metallic=float(v["metallic"]),
-                        roughness=float(v["roughness"]), texture=v["texture"]) for k, v in out.items()}
+                        roughness=float(v["roughness"]), texture=v["texture"], transmission=float(v["transmission"]),
+                        ior=float(v["ior"])) for k, v in out.items()}
     return recs, maps

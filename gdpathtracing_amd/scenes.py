@@ -89,14 +89,17 @@ def rot_y(deg: float) -> np.ndarray:
 
 
 def material(albedo=(1.0, 1.0, 1.0), emission=(0.0, 0.0, 0.0), energy=1.0, metallic=0.0, roughness=1.0,
-             texture=-1) -> np.ndarray:
-    """StandardMaterial3D -> GpuMaterial (geometry_group3d.cpp:279-290)."""
+             texture=-1, transmission=0.0, ior=0.0) -> np.ndarray:
+    """StandardMaterial3D -> GpuMaterial (geometry_group3d.cpp:279-290).  transmission, ior: padding[0:2], read only by a context
+    with capi.MATERIAL_EXT_TRANSMISSION set (the defaults leave all five padding words zero)."""
     m = np.zeros((), dtype=wire.MATERIAL)
     m["albedo"] = (*albedo, 1.0)
     m["emission"] = (*emission, energy)
     m["metallic"] = metallic
     m["roughness"] = roughness
     m["albedo_texture_index"] = texture
+    m["padding"][0] = transmission
+    m["padding"][1] = ior
     return m
 
 
@@ -227,6 +230,27 @@ def cornell_scene() -> Scene:
         Instance(3, transform12(rot_y(20.0), (-1.0, -3.0 + 1.7, -0.9)), [2]),
     ]
     return Scene("cornell", meshes, inst, _demo_materials(), _demo_camera())
+
+
+def glass_cornell_scene() -> Scene:
+    """cornell_scene with its short block made of clear glass (transmission 1, ior 1.5, albedo 1): for contexts with
+    capi.MATERIAL_EXT_TRANSMISSION set."""
+    sc = cornell_scene()
+    sc.name = "glass_cornell"
+    sc.materials = np.concatenate([sc.materials, material(transmission=1.0, ior=1.5)[None]])
+    sc.instances[2].material_ids = [len(sc.materials) - 1]
+    return sc
+
+
+def with_transmissive_materials(scene: Scene, which, transmission=0.7, ior=1.5) -> Scene:
+    """a copy of `scene` whose materials `which` (indices) are transmissive; transmission and ior: one value or one per index"""
+    import copy
+    sc = copy.deepcopy(scene)
+    sc.materials = sc.materials.copy()
+    which = list(which)
+    sc.materials["padding"][which, 0] = np.broadcast_to(np.asarray(transmission, np.float32), (len(which),))
+    sc.materials["padding"][which, 1] = np.broadcast_to(np.asarray(ior, np.float32), (len(which),))
+    return sc
 
 
 def demo_scene(n_tris=51200, seed=1) -> Scene:

@@ -427,6 +427,34 @@ int jpt_set_environment_sampling(jpt_ctx *ctx, int32_t mode);
 #define JPT_LIGHT_SAMPLING_MIS  1
 int jpt_set_light_sampling(jpt_ctx *ctx, int32_t mode);
 
+/* Material extensions: transparent materials (no reference counterpart; the reference lists them among its wanted features).
+ * GpuMaterial ends in float padding[5], which a stock addon leaves uninitialised: by default those bytes are never read.  With
+ * JPT_MATERIAL_EXT_TRANSMISSION set, padding[0] is `transmission` and padding[1] is `ior` of every material (jpt_material_ext), on
+ * both ingest routes; the device sanitises them: transmission NaN -> 0, then clamped to [0, 1]; ior NaN -> 1, then clamped to [1, 4].
+ * The flags belong to the context, like the sampling modes: they survive scene commits, uploads and updates; jpt_scene_share does
+ * not copy them.  Each render takes them by value: queued renders keep the flags of their own call.  With the flag off, or on over
+ * a scene none of whose materials has a sanitised transmission > 0, a render launches the kernels and gives the bits it gives
+ * without this call; otherwise it launches the general *_tx kernels, whatever the lighting.
+ * The vertex, at a hit whose material has T = transmission > 0, after emission is added as always: one pcg2d round of a copy of
+ *   the vertex's seeds hashed as (sx ^ 0x5bd1e995, sy ^ 0x1b873593) gives (xi_t, xi_f); the path's own sequence does not advance
+ *   for this.  xi_t >= T: the vertex is the opaque vertex, unchanged (probability 1 - T and weight 1 - T cancel).  Otherwise a
+ *   smooth dielectric event (dielectric_event, csrc/jpt_shade.h; DESIGN.md section 2 pins every operation): n the facing shading
+ *   normal, v the direction back along the ray, m = n (or -n when n.v < 0), c = min(|n.v|, 1), eta = 1 / ior at a front face, ior
+ *   at a back face, k = 1 - eta^2 (1 - c^2).  k < 0: total internal reflection.  Otherwise ct = sqrt(k) and F the exact
+ *   unpolarised Fresnel reflectance (not finite or > 1: 1).  TIR or xi_f < F: d = 2 c m - v from position + n * 0.001, throughput
+ *   unchanged.  Otherwise d = normalize((eta c - ct) m - eta v) from position - n * 0.001, throughput *= albedo (the material's
+ *   albedo times its texture: the tint).  Radiance is NOT scaled by eta^2 across the interface.  The path never ends at such a
+ *   vertex; its own pcg2d draw is taken and discarded.  A dielectric vertex casts no shadow ray, and the emission or the miss the
+ *   next vertex finds has MIS weight exactly 1.  Shadow rays stay opaque to glass: light through glass arrives by BSDF sampling.
+ * Unknown bits: JPT_E_INVALID; host-only contexts: JPT_E_DEVICE after the checks.  Memory: a *_tx render's workspace holds 4 B
+ * per path more than the same lighting's without it, unless that already holds them (jpt_get_workspace_bytes counts them). */
+enum { JPT_MATERIAL_EXT_NONE = 0, JPT_MATERIAL_EXT_TRANSMISSION = 1 };
+typedef struct jpt_material_ext {   /* documentation of GpuMaterial's first two padding words under JPT_MATERIAL_EXT_TRANSMISSION */
+    float transmission;             /* padding[0]: the probability of the dielectric lobe, [0, 1] */
+    float ior;                      /* padding[1]: the index of refraction of the inside, [1, 4] */
+} jpt_material_ext;
+int jpt_set_material_extensions(jpt_ctx *ctx, uint32_t flags);
+
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
  *   REFERENCE_LAYOUT   one thread per pixel straight over the six reference-layout buffers, node for node
@@ -665,6 +693,7 @@ int jpt_multi_set_environment(jpt_multi *m, const float *rgb, int32_t width, int
 int jpt_multi_set_environment_params(jpt_multi *m, const float *rotation9, float intensity);
 int jpt_multi_set_environment_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_light_sampling(jpt_multi *m, int32_t mode);
+int jpt_multi_set_material_extensions(jpt_multi *m, uint32_t flags);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -732,6 +761,13 @@ int jpt_debug_light_sample(jpt_ctx *ctx, const float *xi4, const float *origins3
                            float *pdf_out);
 int jpt_debug_light_pdf(jpt_ctx *ctx, const uint32_t *inst, const uint32_t *tri, const float *points3, const float *origins3,
                         const float *dirs3, uint32_t n, float *pdf_out);
+/* The dielectric event of JPT_MATERIAL_EXT_TRANSMISSION for n cases: facing normal normals3[3 i ..], out direction out_dirs3[3 i ..],
+ * ior[i] (sanitised as the materials' is), front[i] != 0 for a front face and the lobe random xi_f[i]: dirs_out[3 i ..] = the next
+ * direction, fresnel_out[i] = F (1 under total internal reflection), event_out[i] = 0 refract, 1 reflect, 2 total internal
+ * reflection.  device_id >= 0: the function the kernels inline, on that device; JPT_DEVICE_HOST_ONLY: the same function compiled
+ * for the host. */
+int jpt_debug_dielectric(int device_id, const float *normals3, const float *out_dirs3, const float *ior, const uint8_t *front,
+                         const float *xi_f, uint32_t n, float *dirs_out, float *fresnel_out, uint8_t *event_out);
 /* The filter of jpt_denoise alone, on caller-made images of width x height pixels, 4 floats per pixel each: mean4 = (mean r, g, b,
  * unused), the three guide images as jpt_read_guides_f32 lays them out, out = the denoised image (r, g, b, 1).  params NULL: the
  * defaults; checked as jpt_set_denoise_params checks them (JPT_E_INVALID; this call leaves no message).  device_id >= 0: the

@@ -194,6 +194,10 @@ struct StandardMaterial3D {  // the properties GeometryGroup3D reads (geometry_g
     Color emission{0, 0, 0, 1};
     float emission_energy_multiplier = 1.0f;
     int albedo_texture = -1;  // index into GeometryGroup3D::textures, -1 = none
+    // JPT_MATERIAL_EXT_TRANSMISSION (jpt.h; no reference counterpart): GpuMaterial's padding[0] / padding[1].  0, 0: an opaque
+    // material, the padding words zero as before.  Read only by a context whose jpt_set_material_extensions says so.
+    float transmission = 0.0f;
+    float ior = 0.0f;
 };
 
 struct Surface {
@@ -407,7 +411,9 @@ inline void load_hdr(const std::string& bytes, std::vector<float>& rgb, int32_t&
 // Kd -> albedo; Ke -> emission colour (energy multiplier 1, or the largest component when it exceeds 1, the colour
 // scaled back into [0,1]); Pr -> roughness, else from the Phong exponent Ns as sqrt(2 / (Ns + 2)); Pm -> metallic (else 0);
 // map_Kd -> albedo_texture = index of that file name in `albedo_maps` (appended on first use).
-inline std::map<std::string, StandardMaterial3D> load_mtl(const std::string& text, std::vector<std::string>& albedo_maps)
+// transmission (off by default: the result is then what it was before the extension existed): Ni -> ior, and d x -> transmission =
+// 1 - x, Tr x -> transmission = x, whichever comes last.
+inline std::map<std::string, StandardMaterial3D> load_mtl(const std::string& text, std::vector<std::string>& albedo_maps, bool transmission = false)
 {
     std::map<std::string, StandardMaterial3D> out;
     StandardMaterial3D* cur = nullptr;
@@ -448,6 +454,14 @@ inline std::map<std::string, StandardMaterial3D> load_mtl(const std::string& tex
             cur->roughness = std::sqrt(2.0f / (std::max(ns, 0.0f) + 2.0f));
         } else if (tag == "Pm") {
             ls >> cur->metallic;
+        } else if (transmission && tag == "Ni") {
+            ls >> cur->ior;
+        } else if (transmission && tag == "d") {
+            float d = 1;
+            ls >> d;
+            cur->transmission = 1.0f - d;
+        } else if (transmission && tag == "Tr") {
+            ls >> cur->transmission;
         } else if (tag == "map_Kd") {
             std::string file;
             ls >> file;
@@ -506,6 +520,13 @@ class GeometryGroup3D {
     // rank 0's context and shares, and update_transforms() reaches EVERY rank's replica (jpt_multi_set_instance_transform,
     // jpt_multi_update_tlas / jpt_multi_refit_tlas) -- not just the context the scene was built on.
     void attach_multi(jpt_multi* m) { multi_ = m; }
+    // jpt_set_material_extensions (JPT_MATERIAL_EXT_*): whether the devices read StandardMaterial3D::transmission / ior.  Forwarded
+    // at once when the scene is built already, and by every build().
+    void set_material_extensions(uint32_t flags)
+    {
+        material_extensions_ = flags;
+        if (ctx_) forward_material_extensions(ctx_);
+    }
 
     // geometry_group3d.cpp:228-366: collect instances, dedup meshes / materials by pointer, convert materials,
     // then builder + instances + TLAS + upload (the jpt_scene_* calls)
@@ -544,8 +565,11 @@ class GeometryGroup3D {
             g.emission[0] = m->emission.r; g.emission[1] = m->emission.g; g.emission[2] = m->emission.b;
             g.emission[3] = m->emission_energy_multiplier;
             g.albedo_texture_index = m->albedo_texture;
+            g.padding[0] = m->transmission;
+            g.padding[1] = m->ior;
             materials_.push_back(g);
         }
+        if (material_extensions_) forward_material_extensions(ctx);
         check(ctx, jpt_scene_begin(ctx), "jpt_scene_begin");
         std::vector<uint32_t> ids;
         for (const ArrayMesh* mesh : meshes) {  // :308-313
@@ -660,6 +684,16 @@ class GeometryGroup3D {
     {
         if (rc != JPT_OK) throw std::runtime_error(std::string(what) + ": " + jpt_multi_last_error(multi_));
     }
+    void forward_material_extensions(jpt_ctx* ctx)
+    {
+        if (multi_) {
+            if (jpt_multi_set_material_extensions(multi_, material_extensions_) != JPT_OK)
+                throw std::runtime_error(std::string("jpt_multi_set_material_extensions: ") + jpt_multi_last_error(multi_));
+        } else {
+            check(ctx, jpt_set_material_extensions(ctx, material_extensions_), "jpt_set_material_extensions");
+        }
+    }
+    uint32_t material_extensions_ = JPT_MATERIAL_EXT_NONE;
     jpt_multi* multi_ = nullptr;
     std::vector<MeshInstance3D> children;
     std::vector<GpuMaterial> materials_;
@@ -758,6 +792,8 @@ class PathTracingCamera {
     void set_environment_sampling(int32_t mode) { check(ctx, jpt_set_environment_sampling(ctx, mode), "jpt_set_environment_sampling"); }
     // jpt_set_light_sampling: JPT_LIGHT_SAMPLING_BRDF (default) or JPT_LIGHT_SAMPLING_MIS (shadow rays towards emitter samples)
     void set_light_sampling(int32_t mode) { check(ctx, jpt_set_light_sampling(ctx, mode), "jpt_set_light_sampling"); }
+    // jpt_set_material_extensions: JPT_MATERIAL_EXT_NONE (default) or JPT_MATERIAL_EXT_TRANSMISSION (transmission / ior are read)
+    void set_material_extensions(uint32_t flags) { check(ctx, jpt_set_material_extensions(ctx, flags), "jpt_set_material_extensions"); }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
