@@ -53,6 +53,7 @@ SYMBOLS = [
     "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
     "jpt_set_light_sampling", "jpt_multi_set_light_sampling", "jpt_debug_light_tables", "jpt_debug_light_sample", "jpt_debug_light_pdf",
     "jpt_set_material_extensions", "jpt_multi_set_material_extensions", "jpt_debug_dielectric",
+    "jpt_set_lens", "jpt_multi_set_lens", "jpt_debug_lens_rays", "jpt_debug_lens_sample",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
 ]
@@ -243,6 +244,11 @@ def lib():
         L.jpt_set_material_extensions.argtypes = [vp, u32]
         L.jpt_multi_set_material_extensions.argtypes = [vp, u32]
         L.jpt_debug_dielectric.argtypes = [C.c_int, vp, vp, vp, vp, vp, u32, vp, vp, vp]
+    if hasattr(L, "jpt_set_lens") or "JPT_LIB" not in os.environ:
+        L.jpt_set_lens.argtypes = [vp, C.c_float, C.c_float]
+        L.jpt_multi_set_lens.argtypes = [vp, C.c_float, C.c_float]
+        L.jpt_debug_lens_rays.argtypes = [C.c_int, vp, i32, i32, u32, C.c_float, C.c_float, vp, vp]
+        L.jpt_debug_lens_sample.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, u32, vp, vp, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

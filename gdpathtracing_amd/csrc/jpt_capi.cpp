@@ -739,6 +739,39 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     return JPT_OK;
 }
 
+}  // namespace
+
+int jpt::check_lens(float aperture_radius, float focus_distance, std::string& why)
+{
+    if (!std::isfinite(aperture_radius) || aperture_radius < 0.0f) {
+        why = "jpt_set_lens: aperture_radius must be finite and >= 0";
+        return JPT_E_INVALID;
+    }
+    if (aperture_radius > 0.0f && (!std::isfinite(focus_distance) || !(focus_distance > 0.0f))) {
+        why = "jpt_set_lens: focus_distance must be finite and > 0";
+        return JPT_E_INVALID;
+    }
+    if (!std::isfinite(focus_distance) || focus_distance < 0.0f) {   // (not read with radius 0, but never kept as garbage)
+        why = "jpt_set_lens: focus_distance must be finite and > 0";
+        return JPT_E_INVALID;
+    }
+    return JPT_OK;
+}
+
+int jpt::resolve_lens(jpt_ctx* c, LensDev& out)
+{
+    out = LensDev{};
+    if (!(c->lens_radius > 0.0f) || c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the lens, as it ignores lighting)
+    if (c->denoise == JPT_DENOISE_TEMPORAL)
+        return fail(c, JPT_E_STATE, "temporal reprojection assumes one centre of projection: set the lens radius to 0 (jpt_set_lens) or another denoising mode");
+    out.radius = c->lens_radius;
+    out.focus = c->lens_focus;
+    if (!lens_basis(c->camera, out)) return fail(c, JPT_E_STATE, "jpt_set_lens: the camera basis derived from camera160 (ivp, position) is not finite");
+    return JPT_OK;
+}
+
+namespace {
+
 // What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
 // stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.  r.lighting is the render's.
 int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefront, Wf2Render& r)
@@ -784,6 +817,9 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
         c->trace_events.push_back(e);
     }
     c->trace_events_used = (int32_t)need_ev;
+    // (a lens render has no sky cull and no sky cells: a pixel outside every box's screen rectangle may still see geometry from a
+    // point of the aperture -- r.cull stays off, n < 0, and r.sky_tiles null)
+    if (r.lens.radius > 0.0f) return JPT_OK;
     compute_sky_cull(c, r.cull);
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
@@ -822,7 +858,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting);
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.lens);
         }
         return JPT_OK;
     }
@@ -930,6 +966,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
     const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
     Wf2Render r;
+    if ((rc = resolve_lens(c, r.lens)) != JPT_OK) return rc;
     if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
@@ -1953,6 +1990,18 @@ int jpt_set_kernel(jpt_ctx* c, int32_t variant)
     if (!c) return JPT_E_INVALID;
     if (variant != JPT_KERNEL_WAVEFRONT && variant != JPT_KERNEL_REFERENCE_LAYOUT) return fail(c, JPT_E_INVALID, "unknown kernel variant");
     c->kernel_variant = variant;
+    return JPT_OK;
+}
+
+int jpt_set_lens(jpt_ctx* c, float aperture_radius, float focus_distance)
+{
+    if (!c) return JPT_E_INVALID;
+    std::string why;
+    const int rc = check_lens(aperture_radius, focus_distance, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the lens is a property of device renders");
+    c->lens_radius = aperture_radius;   // (each render takes them by value: resolve_lens)
+    c->lens_focus = focus_distance;
     return JPT_OK;
 }
 

@@ -165,6 +165,9 @@ void lights_stale(jpt_ctx* c, bool listed);
 Lighting lighting_bound(const jpt_ctx* c);
 // The lighting of one render of `c`, once it is validated; makes the emitter tables on the context's stream when they are stale.
 int resolve_lighting(jpt_ctx* c, Lighting& out);
+// The lens of one render of `c` (jpt_set_lens; jpt_capi.cpp): radius 0 without one or with DEBUG_STEPS, else the basis derived from
+// the camera as it is now.  JPT_E_STATE: the basis is not finite, or the temporal pass is on.
+int resolve_lens(jpt_ctx* c, LensDev& out);
 
 }  // namespace jpt
 
@@ -206,6 +209,7 @@ struct jpt_ctx {
     RefCamera camera;
     uint32_t frame_count = 0;  // frames accumulated since reset
     int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
+    float lens_radius = 0.0f, lens_focus = 1.0f;   // jpt_set_lens: the context's, like the sampling modes; radius 0 is the pinhole
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
     bool depth_valid = false;              // d_depth holds the last render's depth image

@@ -138,6 +138,24 @@ __global__ void dielectric_probe(const float* __restrict__ normals3, const float
     event_out[i] = (uint8_t)ev;
 }
 
+// jpt_debug_lens_rays: the ray generation of a lens render (primary_ray, then lens_ray unless the radius is 0), one pixel per thread
+__global__ void lens_rays_probe(RefCamera cam, int width, int height, uint32_t frame, LensDev lens, float* __restrict__ origins_out,
+                                float* __restrict__ dirs_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)width * (uint32_t)height) return;
+    const int px = (int)(i % (uint32_t)width), py = (int)(i / (uint32_t)width);
+    uint32_t sx, sy;
+    Ray ray = primary_ray(cam, width, height, px, py, frame, sx, sy);
+    if (lens.radius > 0.0f) lens_ray(lens, sx, sy, ray);
+    origins_out[3 * (size_t)i] = ray.o.x;
+    origins_out[3 * (size_t)i + 1] = ray.o.y;
+    origins_out[3 * (size_t)i + 2] = ray.o.z;
+    dirs_out[3 * (size_t)i] = ray.d.x;
+    dirs_out[3 * (size_t)i + 1] = ray.d.y;
+    dirs_out[3 * (size_t)i + 2] = ray.d.z;
+}
+
 }  // namespace
 
 // jpt_debug_light_sample / jpt_debug_light_pdf (entry points in jpt_lighting.cpp, beside the context's tables): the emitter sampler and
@@ -462,6 +480,101 @@ int jpt_debug_dielectric(int device_id, const float* normals3, const float* out_
     if (rc == JPT_OK && (e = hipMemcpy(event_out, d_ev, n, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
     return rc;
+}
+
+int jpt_debug_lens_rays(int device_id, const void* camera160, int32_t width, int32_t height, uint32_t frame_index, float aperture_radius,
+                        float focus_distance, float* origins3_out, float* dirs3_out)
+{
+    if (!camera160 || !origins3_out || !dirs3_out) {
+        g_debug_error = "null argument";
+        return JPT_E_INVALID;
+    }
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) {
+        g_debug_error = "jpt_debug_lens_rays: width and height must be in 1..65535";
+        return JPT_E_INVALID;
+    }
+    const int rc0 = check_lens(aperture_radius, focus_distance, g_debug_error);
+    if (rc0 != JPT_OK) return rc0;
+    RefCamera cam;
+    std::memcpy(&cam, camera160, sizeof cam);
+    LensDev lens;
+    if (aperture_radius > 0.0f) {
+        lens.radius = aperture_radius;
+        lens.focus = focus_distance;
+        if (!lens_basis(cam, lens)) {
+            g_debug_error = "the camera basis derived from camera160 is not finite";
+            return JPT_E_STATE;
+        }
+    }
+    const size_t n = (size_t)width * (size_t)height;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        for (size_t i = 0; i < n; i++) {
+            uint32_t sx, sy;
+            Ray ray = primary_ray(cam, width, height, (int)(i % (size_t)width), (int)(i / (size_t)width), frame_index, sx, sy);
+            if (lens.radius > 0.0f) lens_ray(lens, sx, sy, ray);
+            origins3_out[3 * i] = ray.o.x;
+            origins3_out[3 * i + 1] = ray.o.y;
+            origins3_out[3 * i + 2] = ray.o.z;
+            dirs3_out[3 * i] = ray.d.x;
+            dirs3_out[3 * i + 1] = ray.d.y;
+            dirs3_out[3 * i + 2] = ray.d.z;
+        }
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t bytes = n * 3u * sizeof(float);
+    float* d_all = nullptr;   // origins, then directions
+    if ((e = hipMalloc((void**)&d_all, 2 * bytes)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    int rc = JPT_OK;
+    hipLaunchKernelGGL(lens_rays_probe, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, cam, width, height, frame_index, lens, d_all,
+                       d_all + n * 3u);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "lens_rays_probe");
+    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + n * 3u, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_lens_sample(const void* camera160, float aperture_radius, float focus_distance, const float* origins3, const float* dirs3,
+                          const float* xi2, uint32_t n, float* origins3_out, float* dirs3_out, float* basis9_out)
+{
+    if (!camera160 || (n && (!origins3 || !dirs3 || !xi2 || !origins3_out || !dirs3_out))) {
+        g_debug_error = "null argument";
+        return JPT_E_INVALID;
+    }
+    RefCamera cam;
+    std::memcpy(&cam, camera160, sizeof cam);
+    LensDev lens;
+    lens.radius = aperture_radius;
+    lens.focus = focus_distance;
+    const bool finite = lens_basis(cam, lens);
+    if (basis9_out) {
+        const float b[9] = {lens.f.x, lens.f.y, lens.f.z, lens.r.x, lens.r.y, lens.r.z, lens.u.x, lens.u.y, lens.u.z};
+        std::memcpy(basis9_out, b, sizeof b);
+    }
+    if (!finite) {
+        g_debug_error = "the camera basis derived from camera160 is not finite";
+        return JPT_E_STATE;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        Ray ray;
+        ray.o = f3{origins3[3 * (size_t)i], origins3[3 * (size_t)i + 1], origins3[3 * (size_t)i + 2]};
+        ray.d = f3{dirs3[3 * (size_t)i], dirs3[3 * (size_t)i + 1], dirs3[3 * (size_t)i + 2]};
+        ray.rD = rcp3(ray.d);
+        lens_apply(lens, xi2[2 * (size_t)i], xi2[2 * (size_t)i + 1], ray);
+        origins3_out[3 * (size_t)i] = ray.o.x;
+        origins3_out[3 * (size_t)i + 1] = ray.o.y;
+        origins3_out[3 * (size_t)i + 2] = ray.o.z;
+        dirs3_out[3 * (size_t)i] = ray.d.x;
+        dirs3_out[3 * (size_t)i + 1] = ray.d.y;
+        dirs3_out[3 * (size_t)i + 2] = ray.d.z;
+    }
+    return JPT_OK;
 }
 
 int jpt_debug_env_tables(int device_id, const float* rgb, int32_t width, int32_t height, float* cond_out, float* marg_out, float* total_out)

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "jpt_nodeq.h"
+#include "jpt_lens.h"
 #include "jpt_shade.h"
 #include "jpt_types.h"
 
@@ -200,6 +201,8 @@ __device__ __forceinline__ void count_walk(DevCounters& c, uint32_t steps)
 int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why);
 int check_env_params(const float* rotation9, float intensity, std::string& why);
 void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out);
+// the checks of jpt_set_lens (jpt_capi.cpp), also run by jpt_debug_lens_rays
+int check_lens(float aperture_radius, float focus_distance, std::string& why);
 // the map's sampling tables built on the device (jpt_kernels_post.hip), on `stream`: cond (w * h floats), marg (h floats) and the
 // total weight (one float), all device memory: one thread per row (env_build_row), then one thread for the marginal
 void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int32_t h, float* cond, float* marg, float* total);
@@ -226,7 +229,7 @@ struct Lighting {
 
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens);
 
 // The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
 // tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory
@@ -283,6 +286,8 @@ struct Wf2Render {
     const uint32_t* sky_tiles = nullptr;   // per 8 x 8 tile of the context's share of the image: its one rgba8 sky cell, if it has one
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
     Lighting lighting;                     // the kernel family of its launches and the workspace's shadow queues (no sky cells with a map)
+    LensDev lens;                          // jpt_set_lens, resolved for this render (resolve_lens): radius > 0 takes the lens forms of the
+                                           // primary launch, with `cull` off (n < 0) and no sky tiles
 };
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block

@@ -707,6 +707,15 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
 #define JPT_ENV 4
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
+// ... and the lens forms of the two bounce-0 kernels (jpt_set_lens): wf2_primary_lens, wf2_primary_env_lens
+#define JPT_LENS 1
+#define JPT_ENV 0
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#undef JPT_LENS
 
 // the window of a render (local tiles): x0, y0, nx, ny
 struct TileWindow {
@@ -966,7 +975,12 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (lg.emitter_queues() && gp.max_bounces > 0) (void)hipMemsetAsync(lnee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
         if (ev) (void)hipEventRecord(ev[0], st);
         with_consts<2, 3>([&](auto C, auto W) {
-            if (lg.env_mode != 0)   // (the primary launch is its miss model's: a primary miss has weight 1)
+            if (r.lens.radius > 0.0f) {   // (jpt_set_lens: the lens forms; r.cull is off)
+                if (lg.env_mode != 0)
+                    hipLaunchKernelGGL((wf2_primary_env_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.lens, counters);
+                else
+                    hipLaunchKernelGGL((wf2_primary_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.lens, counters);
+            } else if (lg.env_mode != 0)   // (the primary launch is its miss model's: a primary miss has weight 1)
                 hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
             else
                 hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);

@@ -304,7 +304,7 @@ __host__ __device__ __forceinline__ int dielectric_event(f3 n, f3 v, float ior, 
 
 // ---- RNG (main.glsl:163-181) -----------------------------------------------------------------
 
-__device__ __forceinline__ void pcg2d(uint32_t& sx, uint32_t& sy, float& rx, float& ry)
+__host__ __device__ __forceinline__ void pcg2d(uint32_t& sx, uint32_t& sy, float& rx, float& ry)
 {
     uint32_t x = 1664525u * sx + 1013904223u;
     uint32_t y = 1664525u * sy + 1013904223u;
@@ -322,7 +322,7 @@ __device__ __forceinline__ void pcg2d(uint32_t& sx, uint32_t& sy, float& rx, flo
     ry = (float)y * 2.32830643654e-10f;
 }
 
-__device__ __forceinline__ void prng_seed(uint32_t px, uint32_t py, uint32_t frame, uint32_t& sx, uint32_t& sy)
+__host__ __device__ __forceinline__ void prng_seed(uint32_t px, uint32_t py, uint32_t frame, uint32_t& sx, uint32_t& sy)
 {
     uint32_t x = px * 0x9e3779b9u + frame;
     uint32_t y = py * 0x9e3779b9u + frame;
@@ -334,7 +334,7 @@ __device__ __forceinline__ void prng_seed(uint32_t px, uint32_t py, uint32_t fra
 
 // ---- primary ray (main.glsl:405-421, box_muller :183-187) -------------------------------------
 
-__device__ __forceinline__ Ray primary_ray(const RefCamera& cam, int width, int height, int px, int py, uint32_t frame,
+__host__ __device__ __forceinline__ Ray primary_ray(const RefCamera& cam, int width, int height, int px, int py, uint32_t frame,
                                            uint32_t& sx, uint32_t& sy)
 {
     prng_seed((uint32_t)px, (uint32_t)py, frame, sx, sy);

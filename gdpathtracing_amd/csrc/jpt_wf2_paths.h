@@ -1,5 +1,6 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
-// which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace:
+// which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace
+// (and twice more with JPT_LENS defined, for the lens forms of wf2_primary alone: see there):
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -69,9 +70,27 @@
 
 // ---- bounce 0: generate + trace ------------------------------------------------------------------------
 
+// JPT_LENS defined (with JPT_ENV 0 or 1: two more inclusions, of this kernel alone): the lens forms wf2_primary_lens and
+// wf2_primary_env_lens (jpt_set_lens) -- the lens (LensDev, by value) where the sky cull was, the thin-lens step (lens_ray,
+// jpt_lens.h) after primary_ray, and no cull: a pixel outside the screen rectangles of the root's boxes may still see geometry from
+// a point of the aperture.  The body is shared by the preprocessor, like the miss models, and for the same reason: as a
+// __forceinline__ template called from both kernels it cost wf2_primary its register allocation (different code, measured on the
+// ISA); this way the pinhole kernels' source is what it was, token for token.
+#ifdef JPT_LENS
+#if JPT_ENV
+#define JPT_PRIMARY_NAME wf2_primary_env_lens
+#else
+#define JPT_PRIMARY_NAME wf2_primary_lens
+#endif
+#define JPT_PRIMARY_PARAM LensDev lens
+#else
+#define JPT_PRIMARY_NAME JPT_ENV_NAME(wf2_primary)
+#define JPT_PRIMARY_PARAM SkyCull cull
+#endif
+
 template <bool COUNT, bool W4, bool TAIL = false>   // TAIL: the wave finishes its last, long walks itself, all lanes on one ray (coop_walk_call)
-__global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_primary)(WideSceneDev sc, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, RefCamera cam,
-                                                      WfTune tune, SkyCull cull, DevCounters* __restrict__ counters)
+__global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(WideSceneDev sc, Wf2Buffers wb, Wf2Dims dm, FrameParams fp, RefCamera cam,
+                                                      WfTune tune, JPT_PRIMARY_PARAM, DevCounters* __restrict__ counters)
 {
     __shared__ int32_t stack[kStackLds * kBlock];
     __shared__ uint32_t s_cursor, s_out;
@@ -163,6 +182,12 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_pr
                         // a pixel outside the screen rectangles of all the boxes the TLAS root offers: the walk would
                         // expand the root, fail every box test and end in the sky -- nothing is generated, traced or
                         // stored for it here; wf2_accumulate makes up its colour from (x, y, frame)
+#ifdef JPT_LENS
+                        {
+                            uint32_t sx, sy;
+                            Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index + f, sx, sy);
+                            lens_ray(lens, sx, sy, ray);
+#else
                         if (sky_culled(cull, px, py)) {
                             if (COUNT) {
                                 cnt.tlas_expand++;
@@ -171,6 +196,7 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_pr
                         } else {
                             uint32_t sx, sy;
                             const Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index + f, sx, sy);
+#endif
                             tr.begin(sc, ray.o, ray.d);
                             active = true;
                             walk_steps = 0;
@@ -222,7 +248,11 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_ENV_NAME(wf2_pr
     if (COUNT) flush_counters(cnt, counters);
 }
 
+#undef JPT_PRIMARY_NAME
+#undef JPT_PRIMARY_PARAM
 #endif  // JPT_ENV < 2
+
+#ifndef JPT_LENS   // (everything below: once per miss model)
 
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
@@ -843,6 +873,8 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 }
 
 #endif  // JPT_ENV < 2
+
+#endif  // JPT_LENS
 
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM

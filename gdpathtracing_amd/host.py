@@ -82,6 +82,39 @@ def debug_dielectric(device_id, normals, out_dirs, ior, front, xi_f):
     return dirs, fresnel, event
 
 
+def debug_lens_rays(device_id, camera160, width, height, frame_index, aperture_radius, focus_distance):
+    """jpt_debug_lens_rays: the ray generation of a render with set_lens(aperture_radius, focus_distance) for every pixel of one frame
+    -- (origins [height, width, 3], dirs [height, width, 3]) float32.  device_id -1: the host's copy of the functions."""
+    cam = np.ascontiguousarray(camera160).tobytes()
+    if len(cam) != 160:
+        raise ValueError("camera160 is the 160-byte Camera block")
+    origins, dirs = np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_lens_rays(int(device_id), cam, int(width), int(height), int(frame_index), float(aperture_radius), float(focus_distance),
+                               _ptr(origins), _ptr(dirs))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_lens_rays failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return origins, dirs
+
+
+def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
+    """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
+    [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
+    cam = np.ascontiguousarray(camera160).tobytes()
+    if len(cam) != 160:
+        raise ValueError("camera160 is the 160-byte Camera block")
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    xi = np.ascontiguousarray(xi2, np.float32).reshape(-1, 2)
+    n = len(o)
+    o2, d2, basis = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((3, 3), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_lens_sample(cam, float(aperture_radius), float(focus_distance), _ptr(o), _ptr(d), _ptr(xi), n, _ptr(o2), _ptr(d2), _ptr(basis))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_lens_sample failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return o2, d2, basis
+
+
 class Context:
     """One jpt_ctx (one GPU).  Thin, explicit wrapper: every method is one C-ABI call."""
 
@@ -280,6 +313,11 @@ class Context:
         """jpt_set_light_sampling: capi.LIGHT_SAMPLING_BRDF (default) or capi.LIGHT_SAMPLING_MIS (emissive triangles sampled with
         shadow rays, combined with BRDF sampling by the power heuristic), for later renders."""
         self._ck(self._lib.jpt_set_light_sampling(self.h, int(mode)), "jpt_set_light_sampling")
+
+    def set_lens(self, aperture_radius, focus_distance):
+        """jpt_set_lens: a thin lens of `aperture_radius` world units focused `focus_distance` along the camera's forward axis; radius
+        0 (the default) is the pinhole.  The context's, like the sampling modes; each render takes it by value."""
+        self._ck(self._lib.jpt_set_lens(self.h, float(aperture_radius), float(focus_distance)), "jpt_set_lens")
 
     def set_material_extensions(self, flags):
         """jpt_set_material_extensions: capi.MATERIAL_EXT_NONE (default) or capi.MATERIAL_EXT_TRANSMISSION (padding[0:2] of every
@@ -687,6 +725,9 @@ class MultiContext:
 
     def set_light_sampling(self, mode):
         self._ck(self._lib.jpt_multi_set_light_sampling(self.h, int(mode)), "jpt_multi_set_light_sampling")
+
+    def set_lens(self, aperture_radius, focus_distance):
+        self._ck(self._lib.jpt_multi_set_lens(self.h, float(aperture_radius), float(focus_distance)), "jpt_multi_set_lens")
 
     def set_material_extensions(self, flags):
         self._ck(self._lib.jpt_multi_set_material_extensions(self.h, int(flags)), "jpt_multi_set_material_extensions")

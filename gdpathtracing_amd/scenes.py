@@ -408,6 +408,15 @@ def camera_block(cam: CameraDesc, width: int, height: int, frame_index: int = 0)
     return c
 
 
+def lens_from_physical(focal_length_mm: float, f_stop: float, focus_distance_m: float):
+    """(aperture_radius, focus_distance) for Context.set_lens from a physical camera (Godot's CameraAttributesPhysical:
+    frustum_focal_length in mm, exposure_aperture in f-stops, frustum_focus_distance in m): the entrance pupil's diameter is
+    focal_length / N, so the radius is focal_length / (2 N), in metres -- one world unit is one metre."""
+    if not (focal_length_mm > 0.0 and f_stop > 0.0 and focus_distance_m > 0.0):
+        raise ValueError("focal length, f-stop and focus distance must be positive")
+    return float(focal_length_mm) * 1e-3 / (2.0 * float(f_stop)), float(focus_distance_m)
+
+
 def view_projection(cam: CameraDesc, width: int, height: int) -> np.ndarray:
     """projection_matrix * Projection(get_global_transform().affine_inverse()) -- the `vp` of
     TemporalReprojection::render (temporal_reprojection.cpp:62; arguments from path_tracing_camera.cpp:220)."""

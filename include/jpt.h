@@ -455,6 +455,32 @@ typedef struct jpt_material_ext {   /* documentation of GpuMaterial's first two 
 } jpt_material_ext;
 int jpt_set_material_extensions(jpt_ctx *ctx, uint32_t flags);
 
+/* The thin-lens camera: depth of field (no reference counterpart; Godot's CameraAttributesPhysical / Practical carry a focus
+ * distance and an aperture -- INTEGRATION.md maps them onto this call).  aperture_radius: the radius of the lens disk in world
+ * units, finite and >= 0; 0 (the default) is the pinhole.  focus_distance: the distance from cam.position, along the camera's
+ * forward axis, of the plane that stays sharp, finite and > 0; not read when the radius is 0.  Anything else: JPT_E_INVALID;
+ * host-only contexts: JPT_E_DEVICE after the checks.
+ * The lens belongs to the context, like the sampling modes: it survives scene commits, uploads and updates, jpt_set_camera and
+ * jpt_set_params; jpt_scene_share does not copy it.  Each render takes it by value: queued renders keep the lens of their own
+ * call, and setting it never waits.  With radius 0 a render launches the kernels it launches without this call and gives the same
+ * bits.  With a lens the bounce-0 launch is the lens form of its kernel (wf2_primary_lens / wf2_primary_env_lens; the audit kernel
+ * branches) and the render has no sky cull (jpt_stats.sky_culled is 0): a pixel whose pinhole ray misses every box may still see
+ * geometry from a point of the aperture.  Every later launch, the workspace and jpt_get_workspace_bytes are the pinhole's.
+ * The camera basis is derived from camera160 at each render (a host that moves the camera calls nothing extra): with unproject(nx,
+ *   ny) = ivp * (nx, ny, 1, 1) / w as the primary ray forms it, c0 = unproject(0, 0), f = normalize(c0 - position), c1 =
+ *   unproject(1, 0), r0 = c1 - c0, r = normalize(r0 - f (r0 . f)), u = r x f -- for a Godot camera forward -z, right +x, up +y.
+ *   A basis with a non-finite component: the render calls return JPT_E_STATE with a message.
+ * The path, after the pinhole ray (o, d) of its pixel and frame is made and the jitter draw has left the seeds (sx, sy): one pcg2d
+ *   round of a copy of the seeds hashed as (sx ^ 0x85ebca6b, sy ^ 0xc2b2ae35) gives (xi0, xi1); the path's own sequence does not
+ *   advance, so every later vertex draws what it draws under the pinhole.  rad = radius sqrt(xi0), (lu, lv) = rad (cos, sin)(2 pi
+ *   xi1); cf = d . f; !(cf > 0): the pinhole ray is kept.  Otherwise p = o + d (focus / cf), o' = (o + r lu) + u lv, d' =
+ *   normalize(p - o') (csrc/jpt_lens.h; DESIGN.md section 2 pins every operation).
+ * JPT_DENOISE_TEMPORAL with a lens: the render calls return JPT_E_STATE (the reprojection assumes one centre of projection).
+ * jpt_set_debug_steps ignores the lens, as it ignores lighting.  jpt_denoise runs on a lens render; its guide pass stays the
+ * un-jittered pinhole ray through the pixel centre (guides of the sharp scene: a blurred edge is filtered as the edge it is in
+ * focus).  The depth image holds the distance from the ray's origin on the lens, not from cam.position. */
+int jpt_set_lens(jpt_ctx *ctx, float aperture_radius, float focus_distance);
+
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
  *   REFERENCE_LAYOUT   one thread per pixel straight over the six reference-layout buffers, node for node
@@ -694,6 +720,8 @@ int jpt_multi_set_environment_params(jpt_multi *m, const float *rotation9, float
 int jpt_multi_set_environment_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_light_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_material_extensions(jpt_multi *m, uint32_t flags);
+/* jpt_set_lens on every rank */
+int jpt_multi_set_lens(jpt_multi *m, float aperture_radius, float focus_distance);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -768,6 +796,19 @@ int jpt_debug_light_pdf(jpt_ctx *ctx, const uint32_t *inst, const uint32_t *tri,
  * for the host. */
 int jpt_debug_dielectric(int device_id, const float *normals3, const float *out_dirs3, const float *ior, const uint8_t *front,
                          const float *xi_f, uint32_t n, float *dirs_out, float *fresnel_out, uint8_t *event_out);
+/* The ray generation of a render with jpt_set_lens(aperture_radius, focus_distance) (radius 0: the pinhole's) for every pixel of
+ * one frame of a width x height image seen through camera160: origins3_out / dirs3_out[3 (y width + x) ..] = the origin and the
+ * direction of the path of pixel (x, y) and frame frame_index.  Lens arguments are checked as jpt_set_lens checks them; a basis
+ * that is not finite: JPT_E_STATE.  device_id >= 0: the functions the kernels inline, on that device; JPT_DEVICE_HOST_ONLY: the same
+ * functions compiled for the host. */
+int jpt_debug_lens_rays(int device_id, const void *camera160, int32_t width, int32_t height, uint32_t frame_index,
+                        float aperture_radius, float focus_distance, float *origins3_out, float *dirs3_out);
+/* The lens step alone, on the host, from caller-made randoms: for pinhole ray (origins3[3 i ..], dirs3[3 i ..]) and (xi2[2 i], xi2[2
+ * i + 1]) the ray the lens of camera160 sends out (origins3_out, dirs3_out; either input ray kept when it does not point forward).
+ * basis9_out (may be NULL): f, r, u.  The radius and the focus are taken as they are; a basis that is not finite is still returned,
+ * with JPT_E_STATE. */
+int jpt_debug_lens_sample(const void *camera160, float aperture_radius, float focus_distance, const float *origins3,
+                          const float *dirs3, const float *xi2, uint32_t n, float *origins3_out, float *dirs3_out, float *basis9_out);
 /* The filter of jpt_denoise alone, on caller-made images of width x height pixels, 4 floats per pixel each: mean4 = (mean r, g, b,
  * unused), the three guide images as jpt_read_guides_f32 lays them out, out = the denoised image (r, g, b, 1).  params NULL: the
  * defaults; checked as jpt_set_denoise_params checks them (JPT_E_INVALID; this call leaves no message).  device_id >= 0: the

@@ -794,6 +794,14 @@ class PathTracingCamera {
     void set_light_sampling(int32_t mode) { check(ctx, jpt_set_light_sampling(ctx, mode), "jpt_set_light_sampling"); }
     // jpt_set_material_extensions: JPT_MATERIAL_EXT_NONE (default) or JPT_MATERIAL_EXT_TRANSMISSION (transmission / ior are read)
     void set_material_extensions(uint32_t flags) { check(ctx, jpt_set_material_extensions(ctx, flags), "jpt_set_material_extensions"); }
+    // jpt_set_lens: a thin lens of `aperture_radius` world units focused `focus_distance` down the camera's axis (radius 0, the default:
+    // the pinhole).  From CameraAttributesPhysical: set_lens_physical(frustum_focal_length [mm], exposure_aperture [f-stops],
+    // frustum_focus_distance [m]) -- the radius is focal_length / (2 N), in metres.
+    void set_lens(float aperture_radius, float focus_distance) { check(ctx, jpt_set_lens(ctx, aperture_radius, focus_distance), "jpt_set_lens"); }
+    void set_lens_physical(float focal_length_mm, float f_stop, float focus_distance_m)
+    {
+        set_lens(focal_length_mm * 1e-3f / (2.0f * f_stop), focus_distance_m);
+    }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
