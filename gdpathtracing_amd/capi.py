@@ -32,6 +32,8 @@ TONEMAP_ACES_REF, TONEMAP_REINHARD, TONEMAP_CLAMP = 0, 1, 2
 TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
+QUERY_CLOSEST, QUERY_ANY = 0, 1
+HIT_VALID, HIT_FRONT, HIT_BAD_RAY = 1, 2, 4
 BUF_TRI_GEOMETRY, BUF_TRI_DATA, BUF_MATERIALS, BUF_BVH_NODES, BUF_INSTANCES, BUF_TLAS_NODES, BUF_TRIANGLES, BUF_REACH_TRIANGLES, BUF_REACH_INSTANCES = range(9)
 
 # every symbol include/jpt.h declares
@@ -56,6 +58,7 @@ SYMBOLS = [
     "jpt_set_lens", "jpt_multi_set_lens", "jpt_debug_lens_rays", "jpt_debug_lens_sample",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
+    "jpt_query_rays", "jpt_query_rays_device", "jpt_query_pixels",
 ]
 
 
@@ -84,6 +87,18 @@ class DisplayParams(C.Structure):
     def __init__(self, source=DISPLAY_SOURCE_ACCUM, tonemap=TONEMAP_ACES_REF, transfer=TRANSFER_LINEAR, bloom_levels=0, exposure=1.0,
                  white=4.0, bloom_threshold=1.0, bloom_strength=0.25):
         super().__init__(source, tonemap, transfer, bloom_levels, exposure, white, bloom_threshold, bloom_strength)
+
+
+class Ray(C.Structure):
+    """jpt_ray (wire.RAY)"""
+    _fields_ = [("origin", C.c_float * 3), ("tmax", C.c_float), ("dir", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    """jpt_ray_hit (wire.RAY_HIT)"""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("instance", C.c_int32), ("triangle", C.c_uint32),
+                ("material", C.c_int32), ("flags", C.c_uint32), ("position", C.c_float * 3), ("normal", C.c_float * 3),
+                ("uv", C.c_float * 2), ("reserved", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -263,6 +278,10 @@ def lib():
         L.jpt_read_display_f32.argtypes = [vp, vp]
         L.jpt_debug_display.argtypes = [C.c_int, i32, i32, C.POINTER(DisplayParams), vp, vp, vp]
         L.jpt_debug_display_srgb_table.argtypes = [vp]
+    if hasattr(L, "jpt_query_rays") or "JPT_LIB" not in os.environ:
+        L.jpt_query_rays.argtypes = [vp, i32, vp, u32, vp, vp]
+        L.jpt_query_rays_device.argtypes = [vp, i32, vp, u32, vp, vp]
+        L.jpt_query_pixels.argtypes = [vp, vp, u32, vp]
     _lib = L
     return L
 

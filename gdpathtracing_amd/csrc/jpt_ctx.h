@@ -307,6 +307,9 @@ struct jpt_ctx {
     DevBuf<uint32_t> d_disp_ldr;
     bool disp_valid = false;
 
+    // jpt_query_rays / jpt_query_pixels (host forms): one chunk's rays, hits and occlusion bytes on the device, grow-only
+    DevBuf<char> d_query;
+
     jpt_stats stats;
 };
 

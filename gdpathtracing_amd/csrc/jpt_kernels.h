@@ -362,6 +362,13 @@ void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& c
 void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int height, const float4* sums, float frame_count,
                    const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr);
 
+// jpt_query_rays / jpt_query_pixels (jpt_kernels_query.hip): n jpt_ray records walked over the arrays the wavefront kernels walk,
+// one lane per ray; closest: a jpt_ray_hit per ray into `hits` and, unless null, a byte per ray into `occluded`; any: the byte alone
+// (`hits` is not touched).  And the rays of n raster positions (x, y pairs) from the camera, as jpt_query_pixels forms them.  Every
+// pointer is a device pointer, 16-byte aligned.
+void launch_query(hipStream_t stream, const DeviceScene& ds, bool any, const void* rays, uint32_t n, void* hits, void* occluded);
+void launch_query_pixel_rays(hipStream_t stream, const RefCamera& cam, int width, int height, const void* xy, uint32_t n, void* rays);
+
 // pixels of this context's share of the image that lie outside the render's window (the tile-aligned bounding rectangle
 // of the sky cull's screen rectangles): the primary launch does not even enumerate them (their rays are sky by the
 // cull's argument; the event counters are completed with their number on the host)

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/jpt.h"
+
 namespace jpt {
 
 // ---- reference wire formats -------------------------------------------------------------------
@@ -96,6 +98,7 @@ static_assert(sizeof(RefTriGeometry) == 48, "GpuTriangleGeometry");
 static_assert(sizeof(RefTriData) == 80, "GpuTriangleData");
 static_assert(sizeof(RefMaterial) == 64, "GpuMaterial");
 static_assert(sizeof(RefCamera) == 160, "Camera");
+static_assert(sizeof(jpt_ray) == 32 && sizeof(jpt_ray_hit) == 64, "jpt_ray / jpt_ray_hit (include/jpt.h: two and four 16-byte words)");
 
 // ---- flattened device layout (native kernels) -------------------------------------------------
 //

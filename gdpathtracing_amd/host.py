@@ -115,6 +115,18 @@ def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs,
     return o2, d2, basis
 
 
+def make_rays(origins, dirs, tmax=None) -> np.ndarray:
+    """a wire.RAY array (jpt_ray) from origins and dirs [n, 3] and tmax (a scalar or [n]; None: 0, which the library reads as
+    unbounded)"""
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    rays = np.zeros(len(o), wire.RAY)
+    rays["origin"] = o
+    rays["dir"] = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    if tmax is not None:
+        rays["tmax"] = np.broadcast_to(np.asarray(tmax, np.float32), (len(o),))
+    return rays
+
+
 class Context:
     """One jpt_ctx (one GPU).  Thin, explicit wrapper: every method is one C-ABI call."""
 
@@ -473,6 +485,52 @@ class Context:
         g = [np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(3)]
         self._ck(self._lib.jpt_read_guides_f32(self.h, _ptr(g[0]), _ptr(g[1]), _ptr(g[2])), "jpt_read_guides_f32")
         return tuple(g)
+
+    # ---- ray queries (jpt_query_rays / jpt_query_pixels)
+    def query_rays(self, origins, dirs, tmax=None, mode=capi.QUERY_CLOSEST):
+        """jpt_query_rays: n rays (origins, dirs [n, 3]; tmax a scalar or [n], None: unbounded) against the device's scene, blocking.
+        QUERY_CLOSEST: (hits, occluded) -- a wire.RAY_HIT array and uint8 [n]; QUERY_ANY: occluded alone."""
+        rays = make_rays(origins, dirs, tmax)
+        n = len(rays)
+        occ = np.zeros(n, np.uint8)
+        hits = np.zeros(n, wire.RAY_HIT) if mode == capi.QUERY_CLOSEST else None
+        self._ck(self._lib.jpt_query_rays(self.h, int(mode), _ptr(rays), n, _ptr(hits), _ptr(occ)), "jpt_query_rays")
+        return occ if hits is None else (hits, occ)
+
+    def query_pixels(self, xy) -> np.ndarray:
+        """jpt_query_pixels: the closest hit of the un-jittered pinhole ray through each raster position xy [n, 2] (x + 0.5, y + 0.5:
+        the centre of pixel (x, y)), a wire.RAY_HIT array; blocking"""
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        hits = np.zeros(len(xy), wire.RAY_HIT)
+        self._ck(self._lib.jpt_query_pixels(self.h, _ptr(xy), len(xy), _ptr(hits)), "jpt_query_pixels")
+        return hits
+
+    def query_rays_device(self, rays, hits=None, occluded=None, mode=capi.QUERY_CLOSEST, n=None):
+        """jpt_query_rays_device: rays already on the device -- a torch tensor (n * 32 bytes of wire.RAY records, any dtype and
+        shape, contiguous) or a raw device pointer with `n`.  With `hits` / `occluded` given (tensors or pointers, written in
+        place) the call only enqueues on the context's stream and returns None: sync() or work on get_stream()'s stream orders
+        against it.  With neither, torch tensors are made for the results, the context is synchronised and they are returned as
+        query_rays returns them."""
+        def ptr_of(a):
+            return None if a is None else int(a) if isinstance(a, int) else int(a.data_ptr())
+        if n is None:
+            if isinstance(rays, int):
+                raise ValueError("a raw pointer needs n")
+            n = rays.numel() * rays.element_size() // wire.RAY.itemsize
+        own = hits is None and occluded is None
+        if own:
+            import torch
+            occluded = torch.zeros(max(n, 1), dtype=torch.uint8, device=rays.device)
+            if mode == capi.QUERY_CLOSEST:
+                hits = torch.zeros(max(n, 1) * wire.RAY_HIT.itemsize, dtype=torch.uint8, device=rays.device)
+            torch.cuda.synchronize(rays.device)   # (the tensors are made on torch's stream, the query runs on the context's)
+        self._ck(self._lib.jpt_query_rays_device(self.h, int(mode), ptr_of(rays), int(n), ptr_of(hits), ptr_of(occluded)),
+                 "jpt_query_rays_device")
+        if not own:
+            return None
+        self.sync()
+        occ = occluded.cpu().numpy()[:n]
+        return occ if hits is None else (hits.cpu().numpy().view(wire.RAY_HIT)[:n], occ)
 
     def device_accum(self):
         n = C.c_size_t()

@@ -9,6 +9,7 @@ Byte-compatible with the reference structs (sizes in SURVEY.md 8(a) T-1..T-11):
   GpuTriangleData          render_parameters.h:64-71                 80 B
   GpuMaterial              render_parameters.h:49-57                 64 B
   Camera                   render_parameters.h:14-21                160 B
+and the two records of the ray queries (include/jpt.h, no reference counterpart): jpt_ray 32 B, jpt_ray_hit 64 B.
 """
 import numpy as np
 
@@ -39,9 +40,15 @@ CAMERA = np.dtype([
     ("vp", "<f4", (16,)), ("ivp", "<f4", (16,)), ("position", "<f4", (4,)), ("frame_index", "<u4"),
     ("near", "<f4"), ("far", "<f4"), ("_pad", "<u4")])
 
+RAY = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])   # jpt_ray (include/jpt.h)
+RAY_HIT = np.dtype([   # jpt_ray_hit
+    ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("instance", "<i4"), ("triangle", "<u4"), ("material", "<i4"), ("flags", "<u4"),
+    ("position", "<f4", (3,)), ("normal", "<f4", (3,)), ("uv", "<f4", (2,)), ("reserved", "<u4")])
+
 assert TRIANGLE.itemsize == 144 and BVH_NODE.itemsize == 48 and TLAS_NODE.itemsize == 32
 assert BLAS_INSTANCE.itemsize == 176 and TRI_GEOMETRY.itemsize == 48 and TRI_DATA.itemsize == 80
 assert MATERIAL.itemsize == 64 and CAMERA.itemsize == 160
+assert RAY.itemsize == 32 and RAY_HIT.itemsize == 64
 
 ACCUM_REF_LDR8 = 0   # per-frame clamp + 8-bit quantise before the sum (what the reference does)
 ACCUM_HDR_F32 = 1    # pure float sum

@@ -648,6 +648,60 @@ int jpt_display(jpt_ctx *ctx);
 int jpt_read_display_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes, alpha 255 */
 int jpt_read_display_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: the tone-mapped value before the transfer, (r, g, b, 1) */
 
+/* ---- ray queries: what does this ray hit? (no reference counterpart) ---------------------------------------------------------------
+ * Caller-supplied rays against the scene the device holds, as an explicit call: nothing runs unless the host asks, queries change no
+ * statistic of jpt_stats and no buffer a render or a read-back reads.  For picking, autofocus, line of sight and
+ * probe rays against the scene the renderer shows, device-side refits and mesh updates included.
+ *
+ * The scene walked: the arrays the wavefront kernels walk, whatever jpt_set_kernel says -- the four-child records of a native tree,
+ *   the two-child records of a JPT_BUILD_REFERENCE_EXACT or as-given tree -- with the copy of the instance level current at the call,
+ *   chosen as jpt_denoise's guide pass chooses it: queries follow jpt_scene_refit_tlas, jpt_scene_update_tlas,
+ *   jpt_scene_update_reference_tlas and jpt_scene_update_mesh (after which they WORK, unlike the host mirrors).
+ * The hit rule: the guide pass's -- the smallest Moller-Trumbore t that intersectTriangle (main.glsl:224-257) accepts, no reach records
+ *   and no tie walk.  At an exact distance tie ANY of the tying triangles may be returned.  On the reference's own trees a float crack
+ *   between boxes can hide a triangle (the walk gives that tree's answer), as for the guides.  Glass blocks, as for shadow rays.
+ * The ray: `dir` is used as given, not normalised; t is in units of its length, exactly as the kernels treat a ray.  The walk starts
+ *   with hit.t = tmax, and a hit is a final hit.t < tmax.  A tmax that is NaN, <= 0 or >= 1e9 (infinity included) is taken as 1e9, the
+ *   pipeline's miss sentinel.  A ray with a non-finite origin or direction component, or an all-zero direction, is not walked: its hit
+ *   is the miss encoding with flags = JPT_HIT_BAD_RAY, its occlusion byte 0 (checked on the device: both forms behave alike).
+ * JPT_QUERY_CLOSEST fills hits_out; occluded_out may be NULL, else one byte per ray: 1 on a hit, 0 otherwise.
+ *   a miss: t = -1, instance = -1, flags = 0, everything else 0.
+ *   a hit:  t, u, v as the walk found them; `instance` the instance whose local ray found the triangle; `triangle` in the device's
+ *           triangle order = the order of JPT_BUF_TRI_GEOMETRY / JPT_BUF_TRI_DATA as jpt_scene_get_reference_buffer hands them out
+ *           (after a native upload: the native order, not the caller's) and of jpt_debug_light_tables' pairs; `material` the index
+ *           get_shading_data resolves (the instance's slot of the triangle's material_index; out of range: 0); flags =
+ *           JPT_HIT_VALID | (JPT_HIT_FRONT when dot(cross(e1, e2), dir) > 0 in the instance's space); the world `position`, the
+ *           facing shading `normal` and the interpolated `uv` of the shading record -- the call the guide pass makes, so position
+ *           and normal of a pixel-centre ray equal jpt_read_guides_f32's texel bit for bit.
+ * JPT_QUERY_ANY stops at the first accepted triangle with t < tmax and writes occluded_out only; hits_out must be NULL.
+ * jpt_query_pixels: xy[2i], xy[2i + 1] are raster coordinates in pixels (x + 0.5, y + 0.5 is the centre of pixel (x, y)); the ray is
+ *   cam.position and the un-jittered pinhole direction of the guide pass, mode CLOSEST, tmax 1e9.  It ignores jpt_set_lens, as the
+ *   guide pass does.  Coordinates outside [0, width] x [0, height] are allowed (a ray is a ray); a non-finite one: JPT_HIT_BAD_RAY.
+ * Ordering: all three enqueue on the context's stream, behind every render, refit, mesh update and jpt_denoise queued before them and
+ *   ahead of what is queued after; jpt_scene_update_mesh's device-side wait covers the queries queued before it.  The host forms
+ *   block: rays and results travel through the context's pinned staging buffer in chunks of at most 2^20 rays (n is unbounded, the
+ *   memory is not: 97 B per ray of a chunk, pinned and on the device).  jpt_query_rays_device is asynchronous: the three pointers are
+ *   device memory of the context's device, 16-byte aligned, n jpt_ray / n jpt_ray_hit / n bytes; jpt_sync, or work queued on
+ *   jpt_get_stream's stream, orders against it.
+ * n = 0 succeeds and touches nothing.  JPT_E_INVALID: an unknown mode, NULL where an array is required, hits_out with JPT_QUERY_ANY, a
+ * misaligned or non-device pointer.  Host-only contexts: JPT_E_DEVICE, after those checks.  JPT_E_STATE: no scene; jpt_query_pixels
+ * before jpt_set_params and jpt_set_camera. */
+typedef struct jpt_ray {
+    float origin[3]; float tmax;
+    float dir[3];    uint32_t reserved;   /* not read */
+} jpt_ray;                                /* 32 B */
+typedef struct jpt_ray_hit {
+    float t, u, v; int32_t instance;
+    uint32_t triangle; int32_t material; uint32_t flags;
+    float position[3]; float normal[3]; float uv[2];
+    uint32_t reserved;                    /* written 0 */
+} jpt_ray_hit;                            /* 64 B */
+enum { JPT_HIT_VALID = 1, JPT_HIT_FRONT = 2, JPT_HIT_BAD_RAY = 4 };
+enum { JPT_QUERY_CLOSEST = 0, JPT_QUERY_ANY = 1 };
+int jpt_query_rays(jpt_ctx *ctx, int32_t mode, const jpt_ray *rays, uint32_t n, jpt_ray_hit *hits_out, uint8_t *occluded_out);
+int jpt_query_rays_device(jpt_ctx *ctx, int32_t mode, const void *d_rays, uint32_t n, void *d_hits_out, void *d_occluded_out);
+int jpt_query_pixels(jpt_ctx *ctx, const float *xy, uint32_t n, jpt_ray_hit *hits_out);
+
 /* ---- outputs ---------------------------------------------------------------------------------- */
 
 /* replaces: cs->get_image_uniform_buffer(output_texture_rid) (path_tracing_camera.cpp:228-229):

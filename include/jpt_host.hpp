@@ -824,6 +824,30 @@ class PathTracingCamera {
     }
     void read_display(float* out) { check(ctx, jpt_read_display_f32(ctx, out), "jpt_read_display_f32"); }
     void read_guides(float* position_t, float* normal, float* albedo) { check(ctx, jpt_read_guides_f32(ctx, position_t, normal, albedo), "jpt_read_guides_f32"); }
+    // Ray queries against the scene the device holds (picking, line of sight, autofocus: INTEGRATION.md).  query_rays: n closest hits
+    // (occluded may be null); occluded_rays: JPT_QUERY_ANY, one byte per ray; query_pixels: the un-jittered pinhole ray through each
+    // raster position (x + 0.5, y + 0.5: a pixel's centre); query_rays_device: device pointers, asynchronous on the context's stream.
+    void query_rays(const jpt_ray* rays, uint32_t n, jpt_ray_hit* hits, uint8_t* occluded = nullptr)
+    {
+        check(ctx, jpt_query_rays(ctx, JPT_QUERY_CLOSEST, rays, n, hits, occluded), "jpt_query_rays");
+    }
+    void occluded_rays(const jpt_ray* rays, uint32_t n, uint8_t* occluded) { check(ctx, jpt_query_rays(ctx, JPT_QUERY_ANY, rays, n, nullptr, occluded), "jpt_query_rays"); }
+    void query_pixels(const float* xy, uint32_t n, jpt_ray_hit* hits) { check(ctx, jpt_query_pixels(ctx, xy, n, hits), "jpt_query_pixels"); }
+    void query_rays_device(int32_t mode, const void* d_rays, uint32_t n, void* d_hits, void* d_occluded)
+    {
+        check(ctx, jpt_query_rays_device(ctx, mode, d_rays, n, d_hits, d_occluded), "jpt_query_rays_device");
+    }
+    // autofocus: the focus distance of set_lens from the hit under a raster position (0 on a miss) -- t * dot(dir, forward), which for the
+    // pinhole ray through the screen centre is t itself
+    float focus_distance_at(float x, float y, const float forward[3])
+    {
+        const float xy[2] = {x, y};
+        jpt_ray_hit h;
+        query_pixels(xy, 1, &h);
+        if (!(h.flags & JPT_HIT_VALID)) return 0.0f;
+        const float dx = h.position[0] - camera.position[0], dy = h.position[1] - camera.position[1], dz = h.position[2] - camera.position[2];
+        return dx * forward[0] + dy * forward[1] + dz * forward[2];
+    }
 
     int max_bounces = 4;                    // the literal 5 of main.glsl:377 is max_bounces + 1
     int accum_mode = JPT_ACCUM_REF_LDR8;    // what the reference does (rgba8 screen image before the sum)
