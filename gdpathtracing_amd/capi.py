@@ -30,6 +30,8 @@ UPLOAD_NATIVE_TREE, UPLOAD_WALK_AS_GIVEN = 0, 1
 DISPLAY_SOURCE_ACCUM, DISPLAY_SOURCE_DENOISED = 0, 1
 TONEMAP_ACES_REF, TONEMAP_REINHARD, TONEMAP_CLAMP = 0, 1, 2
 TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
+METER_AVERAGE, METER_CENTER_WEIGHTED = 0, 1
+METER_EMPTY, METER_FIRST = 1, 2
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
 QUERY_CLOSEST, QUERY_ANY = 0, 1
@@ -58,6 +60,7 @@ SYMBOLS = [
     "jpt_set_lens", "jpt_multi_set_lens", "jpt_debug_lens_rays", "jpt_debug_lens_sample",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
+    "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
     "jpt_query_rays", "jpt_query_rays_device", "jpt_query_pixels",
 ]
 
@@ -87,6 +90,25 @@ class DisplayParams(C.Structure):
     def __init__(self, source=DISPLAY_SOURCE_ACCUM, tonemap=TONEMAP_ACES_REF, transfer=TRANSFER_LINEAR, bloom_levels=0, exposure=1.0,
                  white=4.0, bloom_threshold=1.0, bloom_strength=0.25):
         super().__init__(source, tonemap, transfer, bloom_levels, exposure, white, bloom_threshold, bloom_strength)
+
+
+class MeterParams(C.Structure):
+    """jpt_meter_params; the defaults are the library's"""
+    _fields_ = [("source", C.c_int32), ("mode", C.c_int32), ("low_permille", C.c_int32), ("high_permille", C.c_int32),
+                ("key", C.c_float), ("min_exposure", C.c_float), ("max_exposure", C.c_float), ("adapt", C.c_float)]
+
+    def __init__(self, source=DISPLAY_SOURCE_ACCUM, mode=METER_AVERAGE, low_permille=100, high_permille=900, key=0.18, min_exposure=1.0 / 64.0,
+                 max_exposure=64.0, adapt=1.0):
+        super().__init__(source, mode, low_permille, high_permille, key, min_exposure, max_exposure, adapt)
+
+
+class MeterResult(C.Structure):
+    """jpt_meter_result (32 bytes)"""
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("luminance", C.c_float), ("flags", C.c_uint32),
+                ("weight", C.c_uint64), ("used", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class Ray(C.Structure):
@@ -278,6 +300,13 @@ def lib():
         L.jpt_read_display_f32.argtypes = [vp, vp]
         L.jpt_debug_display.argtypes = [C.c_int, i32, i32, C.POINTER(DisplayParams), vp, vp, vp]
         L.jpt_debug_display_srgb_table.argtypes = [vp]
+    if hasattr(L, "jpt_meter") or "JPT_LIB" not in os.environ:
+        L.jpt_set_meter_params.argtypes = [vp, C.POINTER(MeterParams)]
+        L.jpt_meter.argtypes = [vp]
+        L.jpt_meter_reset.argtypes = [vp]
+        L.jpt_read_meter.argtypes = [vp, C.POINTER(MeterResult), vp]
+        L.jpt_set_auto_exposure.argtypes = [vp, i32]
+        L.jpt_debug_meter.argtypes = [C.c_int, i32, i32, C.POINTER(MeterParams), vp, C.c_float, vp, C.POINTER(MeterResult)]
     if hasattr(L, "jpt_query_rays") or "JPT_LIB" not in os.environ:
         L.jpt_query_rays.argtypes = [vp, i32, vp, u32, vp, vp]
         L.jpt_query_rays_device.argtypes = [vp, i32, vp, u32, vp, vp]

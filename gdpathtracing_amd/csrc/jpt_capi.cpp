@@ -1937,7 +1937,7 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
         c->d_disp_ldr.release();
         c->d_disp_pyramid.release();
     }
-    if (width != c->width || height != c->height) c->dn_valid = c->disp_valid = false;
+    if (width != c->width || height != c->height) c->dn_valid = c->disp_valid = c->meter_valid = false;
     c->width = width;
     c->height = height;
     c->max_bounces = max_bounces;
@@ -2312,6 +2312,8 @@ int jpt_display(jpt_ctx* c)
     const DisplayParams prm = c->disp_params;
     const bool denoised = prm.source == JPT_DISPLAY_SOURCE_DENOISED;
     if (denoised && !c->dn_valid) return fail(c, JPT_E_STATE, "jpt_display: JPT_DISPLAY_SOURCE_DENOISED and no jpt_denoise at the current resolution yet");
+    if (c->auto_exposure && !c->meter_valid)
+        return fail(c, JPT_E_STATE, "jpt_display: auto-exposure is on (jpt_set_auto_exposure) and no jpt_meter ran since the metering state was reset");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->width * c->height;
     HIP_TRY(c, c->d_disp_f32.resize(npx));
@@ -2321,7 +2323,7 @@ int jpt_display(jpt_ctx* c)
     // before it; the accumulation of every later render (and a later jpt_denoise) waits for what it holds.
     if (npx) {
         launch_display(c->stream, prm, c->width, c->height, denoised ? c->d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count,
-                       c->d_disp_pyramid.p, c->d_disp_f32.p, c->d_disp_ldr.p);
+                       c->d_disp_pyramid.p, c->d_disp_f32.p, c->d_disp_ldr.p, c->auto_exposure ? &c->d_meter_state.p->exposure : nullptr);
         HIP_TRY(c, hipGetLastError());
     }
     c->disp_valid = true;
@@ -2355,6 +2357,93 @@ int jpt_read_display_f32(jpt_ctx* c, float* out)
     const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
     if ((rc = staged_read(c, c->d_disp_f32.p, bytes)) != JPT_OK) return rc;
     std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+// ---- jpt_meter ----------------------------------------------------------------------------------------------------------------
+int jpt_set_meter_params(jpt_ctx* c, const jpt_meter_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    MeterParams p;
+    if (params) {
+        p.source = params->source;
+        p.mode = params->mode;
+        p.low_permille = params->low_permille;
+        p.high_permille = params->high_permille;
+        p.key = params->key;
+        p.min_exposure = params->min_exposure;
+        p.max_exposure = params->max_exposure;
+        p.adapt = params->adapt;
+    }
+    std::string why;
+    const int rc = check_meter_params(p, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
+    c->meter_params = p;
+    return JPT_OK;
+}
+
+int jpt_set_auto_exposure(jpt_ctx* c, int32_t enable)
+{
+    if (!c) return JPT_E_INVALID;
+    if (enable != 0 && enable != 1) return fail(c, JPT_E_INVALID, "jpt_set_auto_exposure: enable must be 0 or 1");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
+    c->auto_exposure = enable != 0;
+    return JPT_OK;
+}
+
+int jpt_meter_reset(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
+    c->meter_valid = false;
+    return JPT_OK;
+}
+
+int jpt_meter(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_meter meters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_meter: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_meter needs the whole image on one context (world == 1)");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
+    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_meter: jpt_set_params not called");
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_meter: no frame accumulated since the last reset");
+    const MeterParams prm = c->meter_params;
+    const bool denoised = prm.source == JPT_DISPLAY_SOURCE_DENOISED;
+    if (denoised && !c->dn_valid) return fail(c, JPT_E_STATE, "jpt_meter: JPT_DISPLAY_SOURCE_DENOISED and no jpt_denoise at the current resolution yet");
+    if (c->width <= 0 || c->height <= 0) return fail(c, JPT_E_STATE, "jpt_meter: the image has no pixels");
+    if ((uint64_t)c->width * (uint64_t)c->height > (1ull << 30))
+        return fail(c, JPT_E_LIMIT, "jpt_meter: more than 2^30 pixels (a weight is at most 4 and a bin is a uint32)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_meter_bins.resize(kMeterBinWords));
+    HIP_TRY(c, c->d_meter_state.resize(1));
+    // On the context's stream, as jpt_display: behind the accumulation of every render, a jpt_denoise and a jpt_display queued before
+    // it; a later jpt_display with auto-exposure reads the state record behind the resolve.
+    const bool first = !c->meter_valid;
+    launch_meter(c->stream, prm, c->width, c->height, denoised ? c->d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count, first,
+                 c->d_meter_bins.p, c->d_meter_state.p);
+    HIP_TRY(c, hipGetLastError());
+    c->meter_valid = true;
+    return JPT_OK;
+}
+
+int jpt_read_meter(jpt_ctx* c, jpt_meter_result* out, uint32_t* hist256)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
+    if (!c->meter_valid) return fail(c, JPT_E_STATE, "no jpt_meter since the metering state was reset");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    static_assert(sizeof(jpt_meter_result) == sizeof(MeterState), "the state record is jpt_meter_result");
+    if ((rc = staged_read(c, c->d_meter_state.p, sizeof(MeterState))) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, sizeof(MeterState));
+    if (hist256) {
+        if ((rc = staged_read(c, c->d_meter_bins.p, kMeterBins * sizeof(uint32_t))) != JPT_OK) return rc;
+        std::memcpy(hist256, c->h_read_pinned.p, kMeterBins * sizeof(uint32_t));
+    }
     return JPT_OK;
 }
 

@@ -5,6 +5,7 @@
 #include "jpt_builder.h"
 #include "jpt_denoise.h"
 #include "jpt_display.h"
+#include "jpt_meter.h"
 #include "jpt_kernels.h"
 
 namespace jpt {
@@ -306,6 +307,15 @@ struct jpt_ctx {
     DevBuf<float4> d_disp_f32, d_disp_pyramid;
     DevBuf<uint32_t> d_disp_ldr;
     bool disp_valid = false;
+
+    // jpt_meter: the context's parameters and the auto-exposure switch of jpt_display, and its own buffers -- the published bins, the working sets (kMeterBinWords) and the state
+    // record, made at the first jpt_meter, kept until jpt_destroy; meter_valid: the record holds the state a jpt_meter left since
+    // the last reset (jpt_meter_reset, jpt_set_params with another size), so the next jpt_meter is not a FIRST one
+    MeterParams meter_params;
+    bool auto_exposure = false;
+    DevBuf<uint32_t> d_meter_bins;
+    DevBuf<MeterState> d_meter_state;
+    bool meter_valid = false;
 
     // jpt_query_rays / jpt_query_pixels (host forms): one chunk's rays, hits and occlusion bytes on the device, grow-only
     DevBuf<char> d_query;

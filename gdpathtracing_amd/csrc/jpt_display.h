@@ -278,7 +278,9 @@ inline void display_host(int32_t width, int32_t height, const DisplayParams& prm
 // jpt_display's launches (jpt_kernels_display.hip), on `stream`: from `src` (width * height sums, or an image with fc = 1) to the
 // tone-mapped image `out_f32` ((r, g, b, 1)) and its encoded image `out_rgba8`.  `pyramid` holds display_pyramid_elems(width,
 // height, bloom_levels) elements and is written only when bloom_levels > 0 (else it may be null).  Nothing else is written.
+// `metered` (jpt_set_auto_exposure; else null): the device's metered exposure, read by kernels of their own as the launches run;
+// the exposure is then prm.exposure * *metered, one binary32 multiply, in the bloom's base and in the resolve.
 void launch_display(hipStream_t stream, const DisplayParams& prm, int width, int height, const float4* src, float fc, float4* pyramid,
-                    float4* out_f32, uint32_t* out_rgba8);
+                    float4* out_f32, uint32_t* out_rgba8, const float* metered = nullptr);
 
 }  // namespace jpt

@@ -20,8 +20,8 @@ struct Level {
 // D_1 from the source: one lane per pixel of D_1, 32 x 8 of them per block.  The block stages the 66 x 18 source pixels its taps
 // touch (indices clamped to the image) in LDS with 16-byte accesses, as bright-pass values: base and bright pass run once per
 // staged pixel, not once per tap, and B is never stored in memory.
-__global__ __launch_bounds__(kDisplayBlock) void display_down0_kernel(const float4* __restrict__ src, int32_t width, int32_t height, float fc,
-                                                                      float exposure, float threshold, Level out)
+__device__ __forceinline__ void display_down0_body(const float4* __restrict__ src, int32_t width, int32_t height, float fc, float exposure,
+                                                   float threshold, Level out)
 {
     constexpr int SW = 2 * kTileW + 2, SH = 2 * kTileH + 2;
     __shared__ float4 tile[SW * SH];
@@ -43,6 +43,19 @@ __global__ __launch_bounds__(kDisplayBlock) void display_down0_kernel(const floa
         for (int i = 0; i < 4; i++) s.tap(tile[(2 * ly + j) * SW + 2 * lx + i], display_w4(j) * display_w4(i));
     }
     out.p[(size_t)y * (size_t)out.w + (size_t)x] = make_float4(s.r, s.g, s.b, 0.0f);
+}
+__global__ __launch_bounds__(kDisplayBlock) void display_down0_kernel(const float4* __restrict__ src, int32_t width, int32_t height, float fc,
+                                                                      float exposure, float threshold, Level out)
+{
+    display_down0_body(src, width, height, fc, exposure, threshold, out);
+}
+// the auto-exposure form (jpt_set_auto_exposure): the exposure is the parameter times the metered one, read from jpt_meter's state
+// record -- every lane loads the same address.  An instantiation of its own: the kernel above is what it is without metering.
+__global__ __launch_bounds__(kDisplayBlock) void display_down0_ae_kernel(const float4* __restrict__ src, int32_t width, int32_t height, float fc,
+                                                                         float exposure, const float* __restrict__ metered, float threshold,
+                                                                         Level out)
+{
+    display_down0_body(src, width, height, fc, exposure * metered[0], threshold, out);
 }
 
 // D_k+1 from D_k, k >= 1: one lane per pixel of D_k+1, 16 gathers of 16 bytes (a quarter of the image and less: they hit in L2)
@@ -73,9 +86,8 @@ __global__ __launch_bounds__(kDisplayBlock) void display_up_kernel(Level coarse,
 
 // T(U_1), the composite, the tone map and the transfer: one lane per pixel.  The sRGB table is searched in LDS.
 template <bool HAVE_BLOOM>
-__global__ __launch_bounds__(kDisplayBlock) void display_resolve_kernel(const float4* __restrict__ src, int32_t width, int32_t height, float fc,
-                                                                        DisplayConsts k, Level u1, float4* __restrict__ out_f32,
-                                                                        uint32_t* __restrict__ out_rgba8)
+__device__ __forceinline__ void display_resolve_body(const float4* __restrict__ src, int32_t width, int32_t height, float fc, const DisplayConsts& k,
+                                                     Level u1, float4* __restrict__ out_f32, uint32_t* __restrict__ out_rgba8)
 {
     __shared__ float table[256];
     if (k.transfer == JPT_TRANSFER_SRGB) {
@@ -93,13 +105,28 @@ __global__ __launch_bounds__(kDisplayBlock) void display_resolve_kernel(const fl
     out_f32[idx] = v;
     out_rgba8[idx] = q;
 }
+template <bool HAVE_BLOOM>
+__global__ __launch_bounds__(kDisplayBlock) void display_resolve_kernel(const float4* __restrict__ src, int32_t width, int32_t height, float fc,
+                                                                        DisplayConsts k, Level u1, float4* __restrict__ out_f32,
+                                                                        uint32_t* __restrict__ out_rgba8)
+{
+    display_resolve_body<HAVE_BLOOM>(src, width, height, fc, k, u1, out_f32, out_rgba8);
+}
+template <bool HAVE_BLOOM>   // the auto-exposure form, as display_down0_ae_kernel
+__global__ __launch_bounds__(kDisplayBlock) void display_resolve_ae_kernel(const float4* __restrict__ src, int32_t width, int32_t height, float fc,
+                                                                           DisplayConsts k, const float* __restrict__ metered, Level u1,
+                                                                           float4* __restrict__ out_f32, uint32_t* __restrict__ out_rgba8)
+{
+    k.exposure = k.exposure * metered[0];
+    display_resolve_body<HAVE_BLOOM>(src, width, height, fc, k, u1, out_f32, out_rgba8);
+}
 
 dim3 grid_of(int w, int h) { return dim3((unsigned)((w + kTileW - 1) / kTileW), (unsigned)((h + kTileH - 1) / kTileH)); }
 
 }  // namespace
 
 void launch_display(hipStream_t stream, const DisplayParams& prm, int width, int height, const float4* src, float fc, float4* pyramid,
-                    float4* out_f32, uint32_t* out_rgba8)
+                    float4* out_f32, uint32_t* out_rgba8, const float* metered)
 {
     if (width <= 0 || height <= 0) return;
     const DisplayConsts k = display_consts(prm);
@@ -115,12 +142,21 @@ void launch_display(hipStream_t stream, const DisplayParams& prm, int width, int
             h = display_level_size(h);
             lv[l] = Level{pyramid + off[l], w, h};
         }
-        hipLaunchKernelGGL(display_down0_kernel, grid_of(lv[1].w, lv[1].h), block, 0, stream, src, width, height, fc, k.exposure, k.threshold, lv[1]);
+        if (metered)
+            hipLaunchKernelGGL(display_down0_ae_kernel, grid_of(lv[1].w, lv[1].h), block, 0, stream, src, width, height, fc, k.exposure, metered,
+                               k.threshold, lv[1]);
+        else
+            hipLaunchKernelGGL(display_down0_kernel, grid_of(lv[1].w, lv[1].h), block, 0, stream, src, width, height, fc, k.exposure, k.threshold, lv[1]);
         for (int l = 1; l < N; l++) hipLaunchKernelGGL(display_down_kernel, grid_of(lv[l + 1].w, lv[l + 1].h), block, 0, stream, lv[l], lv[l + 1]);
         for (int l = N - 1; l >= 1; l--) hipLaunchKernelGGL(display_up_kernel, grid_of(lv[l].w, lv[l].h), block, 0, stream, lv[l + 1], lv[l]);
-        hipLaunchKernelGGL((display_resolve_kernel<true>), grid_of(width, height), block, 0, stream, src, width, height, fc, k, lv[1], out_f32, out_rgba8);
+    }
+    const dim3 grid = grid_of(width, height);
+    if (metered) {
+        if (N > 0) hipLaunchKernelGGL((display_resolve_ae_kernel<true>), grid, block, 0, stream, src, width, height, fc, k, metered, lv[1], out_f32, out_rgba8);
+        else hipLaunchKernelGGL((display_resolve_ae_kernel<false>), grid, block, 0, stream, src, width, height, fc, k, metered, lv[1], out_f32, out_rgba8);
     } else {
-        hipLaunchKernelGGL((display_resolve_kernel<false>), grid_of(width, height), block, 0, stream, src, width, height, fc, k, lv[1], out_f32, out_rgba8);
+        if (N > 0) hipLaunchKernelGGL((display_resolve_kernel<true>), grid, block, 0, stream, src, width, height, fc, k, lv[1], out_f32, out_rgba8);
+        else hipLaunchKernelGGL((display_resolve_kernel<false>), grid, block, 0, stream, src, width, height, fc, k, lv[1], out_f32, out_rgba8);
     }
 }
 

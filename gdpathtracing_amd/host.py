@@ -480,6 +480,34 @@ class Context:
         self._ck(self._lib.jpt_read_display_rgba8(self.h, _ptr(out)), "jpt_read_display_rgba8")
         return out
 
+    # ---- metering and auto-exposure (jpt_meter)
+    def set_meter_params(self, params: Optional[capi.MeterParams] = None, **fields):
+        """jpt_set_meter_params: a capi.MeterParams, or its fields by name (source, mode, low_permille, high_permille, key,
+        min_exposure, max_exposure, adapt; the rest at the defaults); nothing: the defaults.  The metering state is kept."""
+        if params is None and fields:
+            params = capi.MeterParams(**fields)
+        self._ck(self._lib.jpt_set_meter_params(self.h, None if params is None else C.byref(params)), "jpt_set_meter_params")
+
+    def meter(self):
+        """jpt_meter: queue the luminance histogram of the accumulation as it is after the renders queued so far (or of jpt_denoise's
+        image) and its resolve into the exposure state; neither image is touched"""
+        self._ck(self._lib.jpt_meter(self.h), "jpt_meter")
+
+    def meter_reset(self):
+        """jpt_meter_reset: the next meter() starts from its target instead of adapting"""
+        self._ck(self._lib.jpt_meter_reset(self.h), "jpt_meter_reset")
+
+    def read_meter(self, histogram: bool = True):
+        """jpt_read_meter: (the capi.MeterResult as a dict, the 256 bins as uint32 or None)"""
+        res = capi.MeterResult()
+        hist = np.zeros(256, dtype=np.uint32) if histogram else None
+        self._ck(self._lib.jpt_read_meter(self.h, C.byref(res), None if hist is None else _ptr(hist)), "jpt_read_meter")
+        return res.as_dict(), hist
+
+    def set_auto_exposure(self, enable: bool):
+        """jpt_set_auto_exposure: display() multiplies its exposure by the metered one, read on the device"""
+        self._ck(self._lib.jpt_set_auto_exposure(self.h, 1 if enable else 0), "jpt_set_auto_exposure")
+
     def read_guides(self):
         """jpt_read_guides_f32: (position_t, normal, albedo), float32 [height, width, 4] each"""
         g = [np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(3)]

@@ -648,6 +648,68 @@ int jpt_display(jpt_ctx *ctx);
 int jpt_read_display_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes, alpha 255 */
 int jpt_read_display_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: the tone-mapped value before the transfer, (r, g, b, 1) */
 
+/* ---- metering: a luminance histogram and auto-exposure on the device (no reference counterpart; Godot's
+ * CameraAttributes.auto_exposure_*) -----------------------------------------------------------------------------------
+ * jpt_meter builds a 256-bin log-luminance histogram of the running mean and resolves it, on the device, into one exposure value;
+ * jpt_set_auto_exposure lets jpt_display multiply by that value straight from device memory.  The host never waits and never reads an
+ * image; it may read the 1 KB histogram and the 32-byte result for a UI.  An explicit call: nothing runs unless the host asks, and
+ * with the switch off, or with none of these calls made, every render, buffer, read-back and jpt_display image and
+ * jpt_get_workspace_bytes are exactly what they are without this section.  The arithmetic is pinned in DESIGN.md section 2
+ * (gdpathtracing_amd/csrc/jpt_meter.h; tests/np_meter.py restates it bit for bit):
+ *   per pixel   m = accum.rgb / frame_count (JPT_DISPLAY_SOURCE_DENOISED: jpt_denoise's image); lum = 0.2126 m.r + 0.7152 m.g +
+ *               0.0722 m.b; a pixel with a non-finite channel or without lum > 0 is skipped; bin = clamp((bits(lum) >> 20) - 856,
+ *               0, 255): eight bins per octave, bin 0 from 2^-20, bin 255 to 2^12, darker and brighter values in the end bins;
+ *               hist[bin] += 1, or 4 under JPT_METER_CENTER_WEIGHTED where 4x >= W, 4x < 3W, 4y >= H and 4y < 3H
+ *   resolve     (uint64) total = sum of the bins; lo = total * low_permille / 1000; hi = total * high_permille / 1000; of each bin,
+ *               in ascending order, the part c[b] of its weight between lo and hi; used = sum c[b]; S = sum c[b] (2b + 1).
+ *               used == 0 (JPT_METER_EMPTY): the exposure stays (a FIRST call: clamp(1, min, max)).  Else p = S * 32768 / used,
+ *               L_avg = the binary32 with the bits 0x35800000 + (p << 4), target = clamp(key / L_avg, min_exposure, max_exposure);
+ *               a FIRST call takes the target, any other exposure = prev + (target - prev) * adapt.
+ *
+ * jpt_meter enqueues on the context's stream, ordered as jpt_display is: behind every render, jpt_denoise and jpt_display queued
+ * before it and ahead of what follows.  It READS the accumulation and the frame count, or jpt_denoise's image, and writes only its
+ * own buffers: the 256 uint32 bins, 16 working sets of them (17 KB in all) and a 32-byte state record, allocated at the first call,
+ * freed by jpt_destroy; jpt_get_workspace_bytes does not count them.  The state is reset
+ * (the next jpt_meter is a FIRST one) by jpt_set_params with another size and by jpt_meter_reset.  jpt_read_meter waits for the work
+ * queued on the context and reads through its pinned staging buffer.
+ * JPT_E_STATE: a denoising mode other than JPT_DENOISE_PROGRESSIVE; the DEBUG_STEPS mode; a screen partition; jpt_set_params not
+ * called; no frame accumulated since the last reset; source = DENOISED without a jpt_denoise at the current resolution; an image
+ * without pixels; jpt_read_meter without a jpt_meter since the state was reset.  JPT_E_LIMIT: width * height > 2^30 (a weight is at
+ * most 4 and a bin is a uint32).  JPT_E_INVALID outside the ranges below or for a non-finite value.  Host-only contexts:
+ * JPT_E_DEVICE, after the checks that need no device.  The parameters and the auto-exposure switch are the context's: they survive
+ * scene changes, each call takes them by value, jpt_scene_share does not copy them; jpt_set_meter_params never resets the state.
+ *
+ * jpt_set_auto_exposure(ctx, 1): jpt_display uses params.exposure * state.exposure wherever it uses exposure (the bloom's base and
+ * the resolve; one binary32 multiply per use), so that params.exposure becomes the exposure compensation.  state.exposure is read
+ * on the device, as the last jpt_meter before the jpt_display on the stream left it.  JPT_E_STATE from jpt_display when no jpt_meter
+ * ran since the state was reset.  There is no jpt_multi_* form and nothing under a partition, as for jpt_display. */
+enum { JPT_METER_AVERAGE = 0, JPT_METER_CENTER_WEIGHTED = 1 };
+enum { JPT_METER_EMPTY = 1, JPT_METER_FIRST = 2 };           /* jpt_meter_result.flags */
+typedef struct jpt_meter_params {
+    int32_t source;          /* JPT_DISPLAY_SOURCE_ACCUM (default) or _DENOISED */
+    int32_t mode;            /* default JPT_METER_AVERAGE */
+    int32_t low_permille;    /* 0..1000, default 100: this share of the weight, from the dark end, is ignored */
+    int32_t high_permille;   /* low < high <= 1000, default 900 */
+    float   key;             /* finite, > 0, default 0.18: the luminance the metered value is mapped to */
+    float   min_exposure;    /* finite, > 0, default 1/64 */
+    float   max_exposure;    /* finite, >= min, default 64 */
+    float   adapt;           /* [0, 1], default 1: share of the way to the target taken per jpt_meter
+                                (the host passes 1 - exp(-dt * speed)) */
+} jpt_meter_params;
+typedef struct jpt_meter_result {
+    float exposure;          /* the state after the call */
+    float target;            /* the target of this call (exposure when EMPTY) */
+    float luminance;         /* L_avg (0 when EMPTY) */
+    uint32_t flags;
+    uint64_t weight;         /* total histogram weight */
+    uint64_t used;           /* weight left after the clipping */
+} jpt_meter_result;          /* 32 B */
+int jpt_set_meter_params(jpt_ctx *ctx, const jpt_meter_params *params);   /* NULL: the defaults; never resets the state */
+int jpt_meter(jpt_ctx *ctx);                                              /* enqueue; ordered as jpt_display is */
+int jpt_meter_reset(jpt_ctx *ctx);                                        /* the next jpt_meter is a FIRST one */
+int jpt_read_meter(jpt_ctx *ctx, jpt_meter_result *out, uint32_t *hist256 /* may be NULL */);
+int jpt_set_auto_exposure(jpt_ctx *ctx, int32_t enable);                  /* default 0 */
+
 /* ---- ray queries: what does this ray hit? (no reference counterpart) ---------------------------------------------------------------
  * Caller-supplied rays against the scene the device holds, as an explicit call: nothing runs unless the host asks, queries change no
  * statistic of jpt_stats and no buffer a render or a read-back reads.  For picking, autofocus, line of sight and
@@ -879,6 +941,14 @@ int jpt_debug_display(int device_id, int32_t width, int32_t height, const jpt_di
 /* The 255 code boundaries of JPT_TRANSFER_SRGB: out255[k - 1] = T[k], k = 1..255, the binary32 nearest to the sRGB decoding of
  * (k - 0.5) / 255; a value v is stored as the number of entries <= v. */
 int jpt_debug_display_srgb_table(float *out255);
+/* jpt_meter's pass alone, on a caller-made image of width x height pixels, 4 floats per pixel: mean4 = (r, g, b, unused) is taken as
+ * the image itself (frame count 1; params->source is checked and otherwise ignored).  prev_exposure: the state before the call, or a
+ * NaN for a FIRST call (an infinity: JPT_E_INVALID).  hist256_out (may be NULL): the 256 bins; result_out: the state after the
+ * call.  params NULL: the defaults; checked as jpt_set_meter_params checks them (JPT_E_INVALID; this call leaves no message);
+ * JPT_E_LIMIT for width * height > 2^30, reported after those refusals, so only for otherwise valid arguments.  device_id >= 0:
+ * the kernels jpt_meter launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
+int jpt_debug_meter(int device_id, int32_t width, int32_t height, const jpt_meter_params *params, const float *mean4,
+                    float prev_exposure, uint32_t *hist256_out, jpt_meter_result *result_out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

@@ -823,6 +823,45 @@ class PathTracingCamera {
         return out;
     }
     void read_display(float* out) { check(ctx, jpt_read_display_f32(ctx, out), "jpt_read_display_f32"); }
+    // Metering and auto-exposure (jpt_meter).  From CameraAttributes: set_auto_exposure(auto_exposure_scale,
+    // auto_exposure_speed, min, max) sets key = 0.18 * scale and the exposure range and turns jpt_display's auto-exposure on (the
+    // other metering parameters stay as set_meter_params left them); meter(dt), once per displayed frame ahead of display(), takes
+    // the share 1 - exp(-dt * speed) of the way to the target (dt in seconds).  meter() alone uses params.adapt as it stands.
+    jpt_meter_params meter_params{JPT_DISPLAY_SOURCE_ACCUM, JPT_METER_AVERAGE, 100, 900, 0.18f, 1.0f / 64.0f, 64.0f, 1.0f};
+    float auto_exposure_speed = 0.0f;   // <= 0: no adaptation, every meter(dt) takes its target
+    void set_meter_params(const jpt_meter_params* params)
+    {
+        if (params) meter_params = *params;
+        else meter_params = jpt_meter_params{JPT_DISPLAY_SOURCE_ACCUM, JPT_METER_AVERAGE, 100, 900, 0.18f, 1.0f / 64.0f, 64.0f, 1.0f};
+        check(ctx, jpt_set_meter_params(ctx, &meter_params), "jpt_set_meter_params");
+    }
+    void set_auto_exposure(float scale, float speed, float min_exposure, float max_exposure)
+    {
+        jpt_meter_params p = meter_params;
+        p.key = 0.18f * scale;
+        p.min_exposure = min_exposure;
+        p.max_exposure = max_exposure;
+        set_meter_params(&p);
+        auto_exposure_speed = speed;
+        check(ctx, jpt_set_auto_exposure(ctx, 1), "jpt_set_auto_exposure");
+    }
+    void disable_auto_exposure() { check(ctx, jpt_set_auto_exposure(ctx, 0), "jpt_set_auto_exposure"); }
+    void meter() { check(ctx, jpt_meter(ctx), "jpt_meter"); }
+    void meter(float dt)
+    {
+        jpt_meter_params p = meter_params;
+        p.adapt = auto_exposure_speed > 0.0f ? 1.0f - std::exp(-dt * auto_exposure_speed) : 1.0f;
+        if (!(p.adapt >= 0.0f)) p.adapt = 0.0f;
+        set_meter_params(&p);
+        meter();
+    }
+    void meter_reset() { check(ctx, jpt_meter_reset(ctx), "jpt_meter_reset"); }
+    jpt_meter_result read_meter(uint32_t* hist256 = nullptr)
+    {
+        jpt_meter_result r;
+        check(ctx, jpt_read_meter(ctx, &r, hist256), "jpt_read_meter");
+        return r;
+    }
     void read_guides(float* position_t, float* normal, float* albedo) { check(ctx, jpt_read_guides_f32(ctx, position_t, normal, albedo), "jpt_read_guides_f32"); }
     // Ray queries against the scene the device holds (picking, line of sight, autofocus: INTEGRATION.md).  query_rays: n closest hits
     // (occluded may be null); occluded_rays: JPT_QUERY_ANY, one byte per ray; query_pixels: the un-jittered pinhole ray through each
