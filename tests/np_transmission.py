@@ -6,6 +6,7 @@ import numpy as np
 
 import np_env
 import np_env_sampling as nes
+import np_lens
 import np_light_sampling as nls
 import np_path
 import np_restatement as npr
@@ -119,9 +120,11 @@ def shading(ref, plain, tri, blas, lpos, lout, u, v, front, textures=None, sampl
 
 
 def trace_tx(ref, cam, width, height, max_bounces, ext_flags, rgb=None, rot=None, intensity=1.0, env_mis=False, light_tabs=None,
-             textures=None, sampler_mode=0):
+             textures=None, sampler_mode=0, lens=None):
     """the path of the *_tx kernels: radiance [H, W, 3] float32.  ext_flags: JPT_MATERIAL_EXT_*; rgb None: the gradient sky;
-    env_mis: the map's NEE too; light_tabs: np_light_sampling.tables(ref) for JPT_LIGHT_SAMPLING_MIS, None for emitter sampling off"""
+    env_mis: the map's NEE too; light_tabs: np_light_sampling.tables(ref) for JPT_LIGHT_SAMPLING_MIS, None for emitter sampling off;
+    lens: (radius, focus) of jpt_set_lens, None or radius 0 for the pinhole (the lens draws from a hashed copy of the seed after the
+    jitter draw and does not advance it: np_lens.lens_xi)"""
     P = np_path
     plain = _Untextured(ref)
     total = F(0) if light_tabs is None else light_tabs["total"]
@@ -150,6 +153,8 @@ def trace_tx(ref, cam, width, height, max_bounces, ext_flags, rgb=None, rot=None
         cpos = np.array([cam["position"][k] for k in range(3)], dtype=F)
         o = np.broadcast_to(cpos, (n, 3)).astype(F)
         d = P._normalize(world - cpos[None, :])
+        if lens is not None and float(lens[0]) > 0.0:
+            o, d = np_lens.lens_apply(np_lens.basis(cam), lens[0], lens[1], o, d, np_lens.lens_xi(seed))
         radiance = np.zeros((n, 3), dtype=F)
         throughput = np.ones((n, 3), dtype=F)
         alive = np.ones(n, dtype=bool)

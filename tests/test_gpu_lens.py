@@ -12,7 +12,9 @@ import pytest
 from gdpathtracing_amd import capi, host, scenes
 
 import np_lens as nl
-from test_gpu_transmission import np_sum, sun_map
+import np_light_sampling as nls
+import np_transmission as ntx
+from test_gpu_transmission import glass_random_scene, host_ref, np_sum, sun_map
 from test_lens_host import look_at
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 E_STATE = -4   # JPT_E_STATE
 LENS = (0.25, 6.5)   # radius, focus of the whole-path tests
+CORNELL_LENS = (0.25, 9.0)   # the box spans 6.8 to 12.8 units down the camera's axis: the focal plane lies inside it
 
 
 def _u32(a):
@@ -123,6 +126,61 @@ def test_whole_paths_equal_numpy(hiplib, soup_want, builder):
             assert len(bad) == 0, "accum %d kernel %d builder %d: %d pixels differ, first %s: %s vs %s" % (
                 accum, kernel, builder, len(bad), bad[:3].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
             assert np.array_equal(_u32(depth), _u32(want_depth)), "depth: accum %d kernel %d builder %d" % (accum, kernel, builder)
+
+
+# ---- 2b. whole paths against numpy under every other lighting, glass included ---------------------------------------------------------------------
+
+@pytest.mark.parametrize("lighting", ["map", "map_mis", "emitters", "map_mis_emitters"])
+@pytest.mark.parametrize("which", ["cornell", "glass_random"])
+def test_whole_paths_under_every_lighting_equal_numpy(oracle, hiplib, which, lighting):
+    """np_transmission.trace_tx with the lens rays of np_lens (the lens does not advance the path's seed): a yardstick that shares no
+    lens code with the kernels, where test_wavefront_equals_reference_layout_under_every_lighting compares two kernels that do.
+    glass_random is textured and partly transmissive and renders with the flag on; one numpy render per distinct emitter order."""
+    glass = which == "glass_random"
+    sc = glass_random_scene() if glass else scenes.cornell_scene()
+    lens = LENS if glass else CORNELL_LENS
+    flags = capi.MATERIAL_EXT_TRANSMISSION if glass else None
+    w = h = 32
+    bounces, frames = 6, 2
+    builders = (capi.BUILD_REFERENCE_EXACT, capi.BUILD_SAH)
+    ref = oracle.build_scene(sc)
+    cam = scenes.camera_block(sc.camera, w, h).copy()
+
+    def np_frames(tabs):
+        out = []
+        for f in range(frames):
+            cam["frame_index"] = 1 + f
+            out.append(ntx.trace_tx(ref, cam, w, h, bounces, capi.MATERIAL_EXT_TRANSMISSION if glass else 0,
+                                    rgb=sun_map() if lighting.startswith("map") else None, env_mis="mis" in lighting,
+                                    light_tabs=tabs, textures=sc.textures, lens=lens))
+        return np_sum(out, False)
+
+    def device(builder, kernel, ln):
+        ctx = make_ctx(sc, w, h, builder, capi.ACCUM_HDR_F32, bounces, kernel, lighting, ln, flags=flags)
+        try:
+            ctx.render(frames, 1)
+            return ctx.read_accum()[..., :3]
+        finally:
+            ctx.close()
+
+    wants = []   # (emitter order, the sum of the frames)
+    for builder in builders:
+        tabs = nls.tables(host_ref(sc, builder)) if "emitters" in lighting else None
+        key = None if tabs is None else tabs["pairs"].tobytes()
+        want = next((x for k, x in wants if k == key), None)
+        if want is None:
+            want = np_frames(tabs)
+            wants.append((key, want))
+        for kernel in (capi.KERNEL_WAVEFRONT, capi.KERNEL_REFERENCE_LAYOUT):
+            got = device(builder, kernel, lens)
+            bad = np.argwhere(~same(got, want).all(axis=-1))
+            changed = (~same(got, device(builder, kernel, None))).any(axis=-1).mean()
+            print("%s %s builder %d kernel %d: %d pixels differ from numpy; the lens changed %.1f %% of the pixels" % (
+                which, lighting, builder, kernel, len(bad), 100.0 * changed))
+            assert changed > 0.03, changed
+            assert len(bad) == 0, "%s %s kernel %d builder %d: %d pixels differ, first %s: %s vs %s" % (
+                which, lighting, kernel, builder, len(bad), bad[:3].tolist(), got[tuple(bad[0])], want[tuple(bad[0])])
+    print("%s %s: %d numpy render(s) for %d builders" % (which, lighting, len(wants), len(builders)))
 
 
 # ---- 3. every family: the wavefront kernels against the audit kernel ------------------------------------------------------------------------------

@@ -222,3 +222,23 @@ def test_set_lens_checks_its_arguments_on_a_host_only_context():
         host.debug_lens_rays(-1, cam, 8, 8, 0, -1.0, 1.0)
     with pytest.raises(capi.JptError, match="focus_distance"):
         host.debug_lens_rays(-1, cam, 8, 8, 0, 0.5, 0.0)
+
+
+def test_np_transmission_takes_the_lens_rays_of_np_lens(oracle):
+    """np_transmission.trace_tx(lens=...) against np_lens.trace_frame, which the device's lens renders are checked with: under the
+    sky, with no transmissive material and no texture, the two are one path tracer.  lens=None and radius 0 are the pinhole."""
+    import np_transmission as ntx
+    sc = scenes.random_scene(3, n_meshes=3, n_instances=5, tris_per_surface=14, textured=False, coincident=False)
+    sc.camera = scenes.CameraDesc(scenes.transform12(None, (0.0, 0.5, 7.0)), fov_deg=70.0)
+    ref = oracle.build_scene(sc)
+    w, h = 24, 16
+    cam = scenes.camera_block(sc.camera, w, h).copy()
+    cam["frame_index"] = 3
+    lens = (0.25, 6.5)
+    want = nl.trace_frame(ref, cam, w, h, 4, *lens)[0]
+    got = ntx.trace_tx(ref, cam, w, h, 4, capi.MATERIAL_EXT_TRANSMISSION, lens=lens)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    pin = ntx.trace_tx(ref, cam, w, h, 4, capi.MATERIAL_EXT_TRANSMISSION)
+    assert np.array_equal(ntx.trace_tx(ref, cam, w, h, 4, capi.MATERIAL_EXT_TRANSMISSION, lens=(0.0, 6.5)).view(np.uint32), pin.view(np.uint32))
+    assert np.array_equal(pin.view(np.uint32), nl.trace_frame(ref, cam, w, h, 4, 0.0, 1.0)[0].view(np.uint32))
+    assert (got != pin).any(axis=-1).mean() > 0.03
