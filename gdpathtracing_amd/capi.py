@@ -35,6 +35,7 @@ METER_EMPTY, METER_FIRST = 1, 2
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+CAMERA_PINHOLE, CAMERA_PROJECTIVE, CAMERA_EQUIRECT = 0, 1, 2
 HIT_VALID, HIT_FRONT, HIT_BAD_RAY = 1, 2, 4
 BUF_TRI_GEOMETRY, BUF_TRI_DATA, BUF_MATERIALS, BUF_BVH_NODES, BUF_INSTANCES, BUF_TLAS_NODES, BUF_TRIANGLES, BUF_REACH_TRIANGLES, BUF_REACH_INSTANCES = range(9)
 
@@ -58,6 +59,7 @@ SYMBOLS = [
     "jpt_set_light_sampling", "jpt_multi_set_light_sampling", "jpt_debug_light_tables", "jpt_debug_light_sample", "jpt_debug_light_pdf",
     "jpt_set_material_extensions", "jpt_multi_set_material_extensions", "jpt_debug_dielectric",
     "jpt_set_lens", "jpt_multi_set_lens", "jpt_debug_lens_rays", "jpt_debug_lens_sample",
+    "jpt_set_camera_model", "jpt_multi_set_camera_model", "jpt_debug_camera_rays",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
@@ -286,6 +288,10 @@ def lib():
         L.jpt_multi_set_lens.argtypes = [vp, C.c_float, C.c_float]
         L.jpt_debug_lens_rays.argtypes = [C.c_int, vp, i32, i32, u32, C.c_float, C.c_float, vp, vp]
         L.jpt_debug_lens_sample.argtypes = [vp, C.c_float, C.c_float, vp, vp, vp, u32, vp, vp, vp]
+    if hasattr(L, "jpt_set_camera_model") or "JPT_LIB" not in os.environ:
+        L.jpt_set_camera_model.argtypes = [vp, i32]
+        L.jpt_multi_set_camera_model.argtypes = [vp, i32]
+        L.jpt_debug_camera_rays.argtypes = [C.c_int, vp, i32, i32, u32, i32, vp, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

@@ -770,6 +770,60 @@ int jpt::resolve_lens(jpt_ctx* c, LensDev& out)
     return JPT_OK;
 }
 
+static_assert(JPT_CAMERA_PINHOLE == kCamPinhole && JPT_CAMERA_PROJECTIVE == kCamProjective && JPT_CAMERA_EQUIRECT == kCamEquirect,
+              "jpt_camera.h restates the enum of jpt.h");
+
+int jpt::make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out, std::string& why)
+{
+    out = CamModelDev{};
+    if (model != JPT_CAMERA_PINHOLE && model != JPT_CAMERA_PROJECTIVE && model != JPT_CAMERA_EQUIRECT) {
+        why = "jpt_set_camera_model: model must be JPT_CAMERA_PINHOLE, JPT_CAMERA_PROJECTIVE or JPT_CAMERA_EQUIRECT";
+        return JPT_E_INVALID;
+    }
+    if (model == JPT_CAMERA_EQUIRECT) {
+        LensDev basis;
+        if (!lens_basis(cam, basis)) {
+            why = "jpt_set_camera_model: the camera basis derived from camera160 (ivp, position) is not finite";
+            return JPT_E_STATE;
+        }
+        out.f = basis.f;
+        out.r = basis.r;
+        out.u = basis.u;
+    }
+    if (model == JPT_CAMERA_PROJECTIVE)
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(cam.ivp[k])) {
+                why = "jpt_set_camera_model: the ivp of camera160 is not finite";
+                return JPT_E_STATE;
+            }
+    out.model = model;
+    return JPT_OK;
+}
+
+namespace {
+
+// The context's model seen through its camera as both are now: what the guides and jpt_query_pixels follow (no render's refusals
+// apply to them), and the last step of a render's resolution
+int camera_model_now(jpt_ctx* c, CamModelDev& out)
+{
+    std::string why;
+    const int rc = make_camera_model(c->camera_model, c->camera, out, why);
+    return rc == JPT_OK ? JPT_OK : fail(c, rc, why);
+}
+
+}  // namespace
+
+int jpt::resolve_camera_model(jpt_ctx* c, const LensDev& lens, CamModelDev& out)
+{
+    out = CamModelDev{};
+    if (c->camera_model == JPT_CAMERA_PINHOLE || c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the model, as it ignores the lens)
+    if (lens.radius > 0.0f)
+        return fail(c, JPT_E_STATE, "the lens disk is defined around one centre of projection: set the lens radius to 0 (jpt_set_lens) or JPT_CAMERA_PINHOLE (jpt_set_camera_model)");
+    if (c->denoise == JPT_DENOISE_TEMPORAL)
+        return fail(c, JPT_E_STATE, "temporal reprojection assumes the pinhole: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or another denoising mode");
+    return camera_model_now(c, out);
+}
+
 namespace {
 
 // What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
@@ -820,6 +874,8 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     // (a lens render has no sky cull and no sky cells: a pixel outside every box's screen rectangle may still see geometry from a
     // point of the aperture -- r.cull stays off, n < 0, and r.sky_tiles null)
     if (r.lens.radius > 0.0f) return JPT_OK;
+    // (nor has a render under another camera model: the rectangles are the pinhole's projection of the boxes)
+    if (r.cam_model.model != kCamPinhole) return JPT_OK;
     compute_sky_cull(c, r.cull);
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
@@ -858,7 +914,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.lens);
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.lens, r.cam_model);
         }
         return JPT_OK;
     }
@@ -967,6 +1023,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
     Wf2Render r;
     if ((rc = resolve_lens(c, r.lens)) != JPT_OK) return rc;
+    if ((rc = resolve_camera_model(c, r.lens, r.cam_model)) != JPT_OK) return rc;
     if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
@@ -2006,6 +2063,16 @@ int jpt_set_lens(jpt_ctx* c, float aperture_radius, float focus_distance)
     return JPT_OK;
 }
 
+int jpt_set_camera_model(jpt_ctx* c, int32_t model)
+{
+    if (!c) return JPT_E_INVALID;
+    if (model != JPT_CAMERA_PINHOLE && model != JPT_CAMERA_PROJECTIVE && model != JPT_CAMERA_EQUIRECT)
+        return fail(c, JPT_E_INVALID, "jpt_set_camera_model: model must be JPT_CAMERA_PINHOLE, JPT_CAMERA_PROJECTIVE or JPT_CAMERA_EQUIRECT");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the camera model is a property of device renders");
+    c->camera_model = model;   // (each render takes it by value: resolve_camera_model)
+    return JPT_OK;
+}
+
 int jpt_set_debug_steps(jpt_ctx* c, int32_t enable)
 {
     if (!c) return JPT_E_INVALID;
@@ -2207,6 +2274,9 @@ int jpt_denoise(jpt_ctx* c)
     if (!c->scene_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
     if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_denoise: jpt_set_params / jpt_set_camera not called");
     if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_denoise: no frame accumulated since the last reset");
+    CamModelDev cm;   // (the guides are the first hits of the view the renders took: jpt_set_camera_model)
+    const int rc_cm = camera_model_now(c, cm);
+    if (rc_cm != JPT_OK) return rc_cm;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->width * c->height;
     if (c->d_dn_ping.n != npx || !c->d_dn_ping.p) {
@@ -2221,7 +2291,7 @@ int jpt_denoise(jpt_ctx* c)
     // device refits (queue_instance_refit), and the accumulation of every later render waits for what it holds.
     hipStream_t s = c->stream;
     if (npx) {
-        launch_guides(s, c->ds, c->camera, c->width, c->height, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p);
+        launch_guides(s, c->ds, c->camera, cm, c->width, c->height, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p);
         launch_atrous(s, c->dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p,
                       c->d_dn_ping.p, c->d_dn_pong.p, c->d_dn_ldr.p);
         HIP_TRY(c, hipGetLastError());
@@ -2491,7 +2561,10 @@ static int query_chunk(jpt_ctx* c, bool any, bool pixels, const void* in, uint32
     if (pixels) {   // 8 B per ray go up, into the hits' part; the rays are made from them in place on the device
         std::memcpy(h, in, (size_t)m * 2 * sizeof(float));
         HIP_TRY(c, hipMemcpyAsync(d_hits, h, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-        launch_query_pixel_rays(s, c->camera, c->width, c->height, d_hits, m, d_rays);
+        CamModelDev cm;   // (jpt_set_camera_model: picking follows the model)
+        const int rc_cm = camera_model_now(c, cm);
+        if (rc_cm != JPT_OK) return rc_cm;
+        launch_query_pixel_rays(s, c->camera, cm, c->width, c->height, d_hits, m, d_rays);
     } else {
         std::memcpy(h, in, (size_t)m * sizeof(jpt_ray));
         HIP_TRY(c, hipMemcpyAsync(d_rays, h, (size_t)m * sizeof(jpt_ray), hipMemcpyHostToDevice, s));

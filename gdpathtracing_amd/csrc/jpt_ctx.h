@@ -169,6 +169,10 @@ int resolve_lighting(jpt_ctx* c, Lighting& out);
 // The lens of one render of `c` (jpt_set_lens; jpt_capi.cpp): radius 0 without one or with DEBUG_STEPS, else the basis derived from
 // the camera as it is now.  JPT_E_STATE: the basis is not finite, or the temporal pass is on.
 int resolve_lens(jpt_ctx* c, LensDev& out);
+// The camera model of one render of `c` (jpt_set_camera_model; jpt_capi.cpp), after its lens: the pinhole without one or with
+// DEBUG_STEPS, else the model with the basis derived from the camera as it is now.  JPT_E_STATE: a lens radius > 0 or the temporal
+// pass with a model other than the pinhole, EQUIRECT's basis or PROJECTIVE's ivp not finite.
+int resolve_camera_model(jpt_ctx* c, const LensDev& lens, CamModelDev& out);
 
 }  // namespace jpt
 
@@ -210,6 +214,7 @@ struct jpt_ctx {
     RefCamera camera;
     uint32_t frame_count = 0;  // frames accumulated since reset
     int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
+    int32_t camera_model = JPT_CAMERA_PINHOLE;   // jpt_set_camera_model: the context's, like the lens; each render takes it by value
     float lens_radius = 0.0f, lens_focus = 1.0f;   // jpt_set_lens: the context's, like the sampling modes; radius 0 is the pinhole
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour

@@ -156,6 +156,24 @@ __global__ void lens_rays_probe(RefCamera cam, int width, int height, uint32_t f
     dirs_out[3 * (size_t)i + 2] = ray.d.z;
 }
 
+// jpt_debug_camera_rays: the ray generation of a render under a camera model (primary_ray for the pinhole, else camera_ray), one
+// pixel per thread
+__global__ void camera_rays_probe(RefCamera cam, int width, int height, uint32_t frame, CamModelDev cm, float* __restrict__ origins_out,
+                                  float* __restrict__ dirs_out)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint32_t)width * (uint32_t)height) return;
+    const int px = (int)(i % (uint32_t)width), py = (int)(i / (uint32_t)width);
+    uint32_t sx, sy;
+    const Ray ray = cm.model != kCamPinhole ? camera_ray(cam, cm, width, height, px, py, frame, sx, sy) : primary_ray(cam, width, height, px, py, frame, sx, sy);
+    origins_out[3 * (size_t)i] = ray.o.x;
+    origins_out[3 * (size_t)i + 1] = ray.o.y;
+    origins_out[3 * (size_t)i + 2] = ray.o.z;
+    dirs_out[3 * (size_t)i] = ray.d.x;
+    dirs_out[3 * (size_t)i + 1] = ray.d.y;
+    dirs_out[3 * (size_t)i + 2] = ray.d.z;
+}
+
 }  // namespace
 
 // jpt_debug_light_sample / jpt_debug_light_pdf (entry points in jpt_lighting.cpp, beside the context's tables): the emitter sampler and
@@ -534,6 +552,57 @@ int jpt_debug_lens_rays(int device_id, const void* camera160, int32_t width, int
     hipLaunchKernelGGL(lens_rays_probe, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, cam, width, height, frame_index, lens, d_all,
                        d_all + n * 3u);
     if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "lens_rays_probe");
+    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + n * 3u, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_camera_rays(int device_id, const void* camera160, int32_t width, int32_t height, uint32_t frame_index, int32_t model,
+                          float* origins3_out, float* dirs3_out)
+{
+    if (!camera160 || !origins3_out || !dirs3_out) {
+        g_debug_error = "null argument";
+        return JPT_E_INVALID;
+    }
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) {
+        g_debug_error = "jpt_debug_camera_rays: width and height must be in 1..65535";
+        return JPT_E_INVALID;
+    }
+    RefCamera cam;
+    std::memcpy(&cam, camera160, sizeof cam);
+    CamModelDev cm;
+    const int rc0 = make_camera_model(model, cam, cm, g_debug_error);
+    if (rc0 != JPT_OK) return rc0;
+    const size_t n = (size_t)width * (size_t)height;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        for (size_t i = 0; i < n; i++) {
+            const int px = (int)(i % (size_t)width), py = (int)(i / (size_t)width);
+            uint32_t sx, sy;
+            const Ray ray = cm.model != kCamPinhole ? camera_ray(cam, cm, width, height, px, py, frame_index, sx, sy)
+                                                    : primary_ray(cam, width, height, px, py, frame_index, sx, sy);
+            origins3_out[3 * i] = ray.o.x;
+            origins3_out[3 * i + 1] = ray.o.y;
+            origins3_out[3 * i + 2] = ray.o.z;
+            dirs3_out[3 * i] = ray.d.x;
+            dirs3_out[3 * i + 1] = ray.d.y;
+            dirs3_out[3 * i + 2] = ray.d.z;
+        }
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t bytes = n * 3u * sizeof(float);
+    float* d_all = nullptr;   // origins, then directions
+    if ((e = hipMalloc((void**)&d_all, 2 * bytes)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    int rc = JPT_OK;
+    hipLaunchKernelGGL(camera_rays_probe, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, cam, width, height, frame_index, cm, d_all,
+                       d_all + n * 3u);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "camera_rays_probe");
     if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + n * 3u, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);

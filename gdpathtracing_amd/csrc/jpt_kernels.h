@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "jpt_nodeq.h"
+#include "jpt_camera.h"
 #include "jpt_lens.h"
 #include "jpt_shade.h"
 #include "jpt_types.h"
@@ -203,6 +204,9 @@ int check_env_params(const float* rotation9, float intensity, std::string& why);
 void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out);
 // the checks of jpt_set_lens (jpt_capi.cpp), also run by jpt_debug_lens_rays
 int check_lens(float aperture_radius, float focus_distance, std::string& why);
+// the camera model of `model` seen through `cam` (jpt_capi.cpp; jpt_set_camera_model, also run by jpt_debug_camera_rays): the basis
+// for EQUIRECT.  JPT_E_INVALID: no such model; JPT_E_STATE: EQUIRECT's basis or PROJECTIVE's ivp is not finite.
+int make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out, std::string& why);
 // the map's sampling tables built on the device (jpt_kernels_post.hip), on `stream`: cond (w * h floats), marg (h floats) and the
 // total weight (one float), all device memory: one thread per row (env_build_row), then one thread for the marginal
 void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int32_t h, float* cond, float* marg, float* total);
@@ -229,7 +233,7 @@ struct Lighting {
 
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens, const CamModelDev& cm);
 
 // The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
 // tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory
@@ -288,6 +292,8 @@ struct Wf2Render {
     Lighting lighting;                     // the kernel family of its launches and the workspace's shadow queues (no sky cells with a map)
     LensDev lens;                          // jpt_set_lens, resolved for this render (resolve_lens): radius > 0 takes the lens forms of the
                                            // primary launch, with `cull` off (n < 0) and no sky tiles
+    CamModelDev cam_model;                 // jpt_set_camera_model, resolved for this render (resolve_camera_model): a model other than the
+                                           // pinhole takes the *_cam forms of the primary launch, again with no cull and no sky tiles
 };
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block
@@ -357,8 +363,8 @@ void launch_temporal(hipStream_t stream, const RefTemporalParams& tp, uint32_t* 
 // null).  Every pointer is a device pointer of width * height elements; nothing else is written.
 struct AtrousParams;
 int check_denoise_params(const AtrousParams& p, std::string& why);
-void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& cam, int width, int height, float4* position_t,
-                   float4* normal, float4* albedo);
+void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& cam, const CamModelDev& cm, int width, int height,
+                   float4* position_t, float4* normal, float4* albedo);
 void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int height, const float4* sums, float frame_count,
                    const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr);
 
@@ -367,7 +373,8 @@ void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int h
 // (`hits` is not touched).  And the rays of n raster positions (x, y pairs) from the camera, as jpt_query_pixels forms them.  Every
 // pointer is a device pointer, 16-byte aligned.
 void launch_query(hipStream_t stream, const DeviceScene& ds, bool any, const void* rays, uint32_t n, void* hits, void* occluded);
-void launch_query_pixel_rays(hipStream_t stream, const RefCamera& cam, int width, int height, const void* xy, uint32_t n, void* rays);
+void launch_query_pixel_rays(hipStream_t stream, const RefCamera& cam, const CamModelDev& cm, int width, int height, const void* xy, uint32_t n,
+                             void* rays);
 
 // pixels of this context's share of the image that lie outside the render's window (the tile-aligned bounding rectangle
 // of the sky cull's screen rectangles): the primary launch does not even enumerate them (their rays are sky by the

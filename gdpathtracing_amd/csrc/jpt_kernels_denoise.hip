@@ -16,46 +16,10 @@ namespace {
 // block, no scratch), then the shading gather.  The closest hit is the walk's geometric answer -- the smallest accepted
 // Moller-Trumbore t, no reach or tie logic.
 constexpr int kGuideBlock = 64;
-template <bool W4>
-__global__ __launch_bounds__(kGuideBlock) void guide_kernel(WideSceneDev sc, SceneShading sh, RefCamera cam, int width, int height,
-                                                            float4* __restrict__ position_t, float4* __restrict__ normal,
-                                                            float4* __restrict__ albedo)
-{
-    constexpr int kDepth = kStackLds + kStackSpill;
-    __shared__ int32_t stack[kDepth * kGuideBlock];
-    const int x = (int)blockIdx.x * 8 + ((int)threadIdx.x & 7), y = (int)blockIdx.y * 8 + ((int)threadIdx.x >> 3);
-    if (x >= width || y >= height) return;
-    const size_t idx = (size_t)y * (size_t)width + (size_t)x;
-    const f3 o = mk3(cam.position.x, cam.position.y, cam.position.z);
-    float ww;
-    const f3 d = raster_direction(cam, width, height, (float)x + 0.5f, (float)y + 0.5f, ww);
-    const typename Traversal<false, W4>::Stack st{&stack[threadIdx.x], nullptr, kGuideBlock, kDepth, 0};
-    DevCounters cnt = {};
-    Traversal<false, W4> tr;
-    tr.begin(sc, o, d);
-    while (tr.step(sc, st, cnt)) {
-    }
-    float4 gp = make_float4(0.0f, 0.0f, 0.0f, -1.0f), gn = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ga = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-    if (tr.hit.t < 1e9f) {
-        Hit h;
-        h.t = tr.hit.t;
-        h.u = tr.hit.u;
-        h.v = tr.hit.v;
-        h.tri = tr.hit.tri;
-        h.inst = (tr.hit.inst >> kInstBits) & kInstMask;   // the instance whose local ray found the triangle kept
-        const RefInstance& b = sh.instances[h.inst];
-        h.lo = xform_point(b.inverse_transform, o);
-        h.ld = xform_dir(b.inverse_transform, d);
-        const Shading s = get_shading_data<3>(sh, h, tr.hit.front, load_shade_tri(sh, h.tri));
-        gp = make_float4(s.position.x, s.position.y, s.position.z, length3(s.position - o));
-        gn = make_float4(s.normal.x, s.normal.y, s.normal.z, 0.0f);
-        if (!(light_lum(s.emission.x, s.emission.y, s.emission.z) > 0.0f))   // (a light's face is not divided by its albedo)
-            ga = make_float4(s.diffuse_albedo.x + s.fresnel_0.x, s.diffuse_albedo.y + s.fresnel_0.y, s.diffuse_albedo.z + s.fresnel_0.z, 0.0f);
-    }
-    position_t[idx] = gp;
-    normal[idx] = gn;
-    albedo[idx] = ga;
-}
+#include "jpt_guide_kernel.h"
+#define JPT_CAMERA_MODEL 1
+#include "jpt_guide_kernel.h"
+#undef JPT_CAMERA_MODEL
 
 // ---- filter -----------------------------------------------------------------------------------------------------------------
 struct AtrousArgs {
@@ -174,8 +138,8 @@ void launch_pass(hipStream_t stream, const AtrousArgs& a, bool last)
 
 }  // namespace
 
-void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& cam, int width, int height, float4* position_t,
-                   float4* normal, float4* albedo)
+void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& cam, const CamModelDev& cm, int width, int height,
+                   float4* position_t, float4* normal, float4* albedo)
 {
     if (width <= 0 || height <= 0) return;
     const bool w4 = ds.use4;
@@ -191,6 +155,11 @@ void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& c
     sc.reach_inst = ds.reach_inst;
     const SceneShading sh = ds.shading();
     const dim3 grid((unsigned)((width + 7) / 8), (unsigned)((height + 7) / 8)), block(kGuideBlock);
+    if (cm.model != kCamPinhole) {   // (jpt_set_camera_model: the guides of the view the render took)
+        if (w4) hipLaunchKernelGGL((guide_cam_kernel<true>), grid, block, 0, stream, sc, sh, cam, width, height, position_t, normal, albedo, cm);
+        else hipLaunchKernelGGL((guide_cam_kernel<false>), grid, block, 0, stream, sc, sh, cam, width, height, position_t, normal, albedo, cm);
+        return;
+    }
     if (w4) hipLaunchKernelGGL((guide_kernel<true>), grid, block, 0, stream, sc, sh, cam, width, height, position_t, normal, albedo);
     else hipLaunchKernelGGL((guide_kernel<false>), grid, block, 0, stream, sc, sh, cam, width, height, position_t, normal, albedo);
 }

@@ -101,6 +101,20 @@ __global__ __launch_bounds__(256) void query_pixel_rays(RefCamera cam, int width
     rays[2 * i + 1] = make_float4(d.x, d.y, d.z, 0.0f);
 }
 
+// ... and under a camera model other than the pinhole (jpt_set_camera_model): the model's ray of the exact position
+// (camera_raster_ray), so picking hits what the picture shows
+__global__ __launch_bounds__(256) void query_pixel_rays_cam(RefCamera cam, CamModelDev cm, int width, int height, const float2* __restrict__ xy,
+                                                            uint32_t n, float4* __restrict__ rays)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float2 p = xy[i];
+    Ray ray = camera_raster_ray(cam, cm, width, height, p.x, p.y);
+    if (!(finite_(p.x) && finite_(p.y))) ray.d = mk3(__uint_as_float(0x7fc00000u), 0.0f, 0.0f);
+    rays[2 * i] = make_float4(ray.o.x, ray.o.y, ray.o.z, kQueryMiss);
+    rays[2 * i + 1] = make_float4(ray.d.x, ray.d.y, ray.d.z, 0.0f);
+}
+
 }  // namespace
 
 void launch_query(hipStream_t stream, const DeviceScene& ds, bool any, const void* rays, uint32_t n, void* hits, void* occluded)
@@ -125,11 +139,15 @@ void launch_query(hipStream_t stream, const DeviceScene& ds, bool any, const voi
     }, w4 ? 1 : 0, any ? 1 : 0);
 }
 
-void launch_query_pixel_rays(hipStream_t stream, const RefCamera& cam, int width, int height, const void* xy, uint32_t n, void* rays)
+void launch_query_pixel_rays(hipStream_t stream, const RefCamera& cam, const CamModelDev& cm, int width, int height, const void* xy, uint32_t n,
+                             void* rays)
 {
     if (n == 0) return;
-    hipLaunchKernelGGL(query_pixel_rays, dim3(n / 256u + (n % 256u != 0 ? 1u : 0u)), dim3(256), 0, stream, cam, width, height, static_cast<const float2*>(xy), n,
-                       static_cast<float4*>(rays));
+    const dim3 grid(n / 256u + (n % 256u != 0 ? 1u : 0u)), block(256);
+    if (cm.model != kCamPinhole)
+        hipLaunchKernelGGL(query_pixel_rays_cam, grid, block, 0, stream, cam, cm, width, height, static_cast<const float2*>(xy), n, static_cast<float4*>(rays));
+    else
+        hipLaunchKernelGGL(query_pixel_rays, grid, block, 0, stream, cam, width, height, static_cast<const float2*>(xy), n, static_cast<float4*>(rays));
 }
 
 }  // namespace jpt

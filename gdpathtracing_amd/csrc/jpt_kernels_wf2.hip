@@ -716,6 +716,15 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #undef JPT_LENS
+// ... and their camera-model forms (jpt_set_camera_model): wf2_primary_cam, wf2_primary_env_cam
+#define JPT_CAMERA_MODEL 1
+#define JPT_ENV 0
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#undef JPT_CAMERA_MODEL
 
 // the window of a render (local tiles): x0, y0, nx, ny
 struct TileWindow {
@@ -980,6 +989,11 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
                     hipLaunchKernelGGL((wf2_primary_env_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.lens, counters);
                 else
                     hipLaunchKernelGGL((wf2_primary_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.lens, counters);
+            } else if (r.cam_model.model != kCamPinhole) {   // (jpt_set_camera_model: the model's forms; r.cull is off)
+                if (lg.env_mode != 0)
+                    hipLaunchKernelGGL((wf2_primary_env_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cam_model, counters);
+                else
+                    hipLaunchKernelGGL((wf2_primary_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cam_model, counters);
             } else if (lg.env_mode != 0)   // (the primary launch is its miss model's: a primary miss has weight 1)
                 hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
             else

@@ -311,6 +311,16 @@ int jpt_multi_set_lens(jpt_multi* m, float aperture_radius, float focus_distance
     return JPT_OK;
 }
 
+int jpt_multi_set_camera_model(jpt_multi* m, int32_t model)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_camera_model(m->ctx[r], model);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_set_camera(jpt_multi* m, const void* camera160)
 {
     if (!m) return JPT_E_INVALID;

@@ -46,7 +46,7 @@
 template <bool COUNT, bool TIES>
 __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefSceneDev sc, TieShadowDev shadow, SceneShading sh, FrameParams fp, RefCamera cam,
                                                         float4* __restrict__ accum, uint32_t* __restrict__ ldr,
-                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters, LensDev lens JPT_ENV_PARAM)
+                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters, LensDev lens, CamModelDev cm JPT_ENV_PARAM)
 {
     // 8x32 pixel tiles: a wave covers 8x8 pixels
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -58,6 +58,7 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
         uint32_t sx, sy;
         Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index, sx, sy);
         if (lens.radius > 0.0f) lens_ray(lens, sx, sy, ray);   // (jpt_set_lens; the host passes radius 0 with DEBUG_STEPS)
+        if (cm.model != kCamPinhole) ray = camera_ray(cam, cm, fp.width, fp.height, px, py, fp.frame_index, sx, sy);   // (jpt_set_camera_model; likewise)
         float depth = cam.far_;
         f3 radiance = mk3(0.0f, 0.0f, 0.0f);
         f3 throughput = mk3(1.0f, 1.0f, 1.0f);

@@ -1,6 +1,7 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
 // which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace
-// (and twice more with JPT_LENS defined, for the lens forms of wf2_primary alone: see there):
+// (and twice more with JPT_LENS defined, and twice with JPT_CAMERA_MODEL, for the lens and camera-model forms of wf2_primary alone:
+// see there):
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -76,6 +77,10 @@
 // a point of the aperture.  The body is shared by the preprocessor, like the miss models, and for the same reason: as a
 // __forceinline__ template called from both kernels it cost wf2_primary its register allocation (different code, measured on the
 // ISA); this way the pinhole kernels' source is what it was, token for token.
+//
+// JPT_CAMERA_MODEL defined (likewise): the forms wf2_primary_cam and wf2_primary_env_cam (jpt_set_camera_model) -- the model
+// (CamModelDev, by value) where the sky cull was, camera_ray (jpt_camera.h) in place of primary_ray, and no cull: the rectangles are
+// the pinhole's.  The model is a kernel argument, so the branch between its two recipes is a scalar one.
 #ifdef JPT_LENS
 #if JPT_ENV
 #define JPT_PRIMARY_NAME wf2_primary_env_lens
@@ -83,6 +88,13 @@
 #define JPT_PRIMARY_NAME wf2_primary_lens
 #endif
 #define JPT_PRIMARY_PARAM LensDev lens
+#elif defined(JPT_CAMERA_MODEL)
+#if JPT_ENV
+#define JPT_PRIMARY_NAME wf2_primary_env_cam
+#else
+#define JPT_PRIMARY_NAME wf2_primary_cam
+#endif
+#define JPT_PRIMARY_PARAM CamModelDev cm
 #else
 #define JPT_PRIMARY_NAME JPT_ENV_NAME(wf2_primary)
 #define JPT_PRIMARY_PARAM SkyCull cull
@@ -187,6 +199,10 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
                             uint32_t sx, sy;
                             Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index + f, sx, sy);
                             lens_ray(lens, sx, sy, ray);
+#elif defined(JPT_CAMERA_MODEL)
+                        {
+                            uint32_t sx, sy;
+                            const Ray ray = camera_ray(cam, cm, fp.width, fp.height, px, py, fp.frame_index + f, sx, sy);
 #else
                         if (sky_culled(cull, px, py)) {
                             if (COUNT) {
@@ -252,7 +268,7 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
 #undef JPT_PRIMARY_PARAM
 #endif  // JPT_ENV < 2
 
-#ifndef JPT_LENS   // (everything below: once per miss model)
+#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL)   // (everything below: once per miss model)
 
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
@@ -874,7 +890,7 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 
 #endif  // JPT_ENV < 2
 
-#endif  // JPT_LENS
+#endif  // JPT_LENS, JPT_CAMERA_MODEL
 
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM

@@ -97,6 +97,20 @@ def debug_lens_rays(device_id, camera160, width, height, frame_index, aperture_r
     return origins, dirs
 
 
+def debug_camera_rays(device_id, camera160, width, height, frame_index, model):
+    """jpt_debug_camera_rays: the ray generation of a render with set_camera_model(model) for every pixel of one frame -- (origins
+    [height, width, 3], dirs [height, width, 3]) float32.  device_id -1: the host's copy of the functions."""
+    cam = np.ascontiguousarray(camera160).tobytes()
+    if len(cam) != 160:
+        raise ValueError("camera160 is the 160-byte Camera block")
+    origins, dirs = np.zeros((height, width, 3), np.float32), np.zeros((height, width, 3), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_camera_rays(int(device_id), cam, int(width), int(height), int(frame_index), int(model), _ptr(origins), _ptr(dirs))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_camera_rays failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return origins, dirs
+
+
 def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
     """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
     [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
@@ -330,6 +344,12 @@ class Context:
         """jpt_set_lens: a thin lens of `aperture_radius` world units focused `focus_distance` along the camera's forward axis; radius
         0 (the default) is the pinhole.  The context's, like the sampling modes; each render takes it by value."""
         self._ck(self._lib.jpt_set_lens(self.h, float(aperture_radius), float(focus_distance)), "jpt_set_lens")
+
+    def set_camera_model(self, model):
+        """jpt_set_camera_model: capi.CAMERA_PINHOLE (default), capi.CAMERA_PROJECTIVE (near-plane point towards far-plane point: exact
+        for an orthographic matrix) or capi.CAMERA_EQUIRECT (the full sphere, in the environment map's layout).  The context's, like the
+        lens; each render takes it by value."""
+        self._ck(self._lib.jpt_set_camera_model(self.h, int(model)), "jpt_set_camera_model")
 
     def set_material_extensions(self, flags):
         """jpt_set_material_extensions: capi.MATERIAL_EXT_NONE (default) or capi.MATERIAL_EXT_TRANSMISSION (padding[0:2] of every
@@ -814,6 +834,9 @@ class MultiContext:
 
     def set_lens(self, aperture_radius, focus_distance):
         self._ck(self._lib.jpt_multi_set_lens(self.h, float(aperture_radius), float(focus_distance)), "jpt_multi_set_lens")
+
+    def set_camera_model(self, model):
+        self._ck(self._lib.jpt_multi_set_camera_model(self.h, int(model)), "jpt_multi_set_camera_model")
 
     def set_material_extensions(self, flags):
         self._ck(self._lib.jpt_multi_set_material_extensions(self.h, int(flags)), "jpt_multi_set_material_extensions")

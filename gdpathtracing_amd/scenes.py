@@ -408,6 +408,38 @@ def camera_block(cam: CameraDesc, width: int, height: int, frame_index: int = 0)
     return c
 
 
+def orthogonal(size: float, aspect: float, near: float, far: float) -> np.ndarray:
+    """Projection::create_orthogonal(size, aspect, near, far, false) (a Camera3D with PROJECTION_ORTHOGONAL and keep-height): the
+    vertical extent is `size`, the horizontal size * aspect; godot-cpp is absent, this is its published algorithm."""
+    top, right = size / 2.0, size * aspect / 2.0
+    left, bottom = -right, -top
+    p = np.zeros((4, 4))
+    p[0, 0] = 2.0 / (right - left)
+    p[1, 1] = 2.0 / (top - bottom)
+    p[2, 2] = -2.0 / (far - near)
+    p[0, 3] = -(right + left) / (right - left)
+    p[1, 3] = -(top + bottom) / (top - bottom)
+    p[2, 3] = -(far + near) / (far - near)
+    p[3, 3] = 1.0
+    return p
+
+
+def camera_block_orthogonal(cam: CameraDesc, size: float, width: int, height: int, frame_index: int = 0) -> np.ndarray:
+    """camera_block for a Camera3D with PROJECTION_ORTHOGONAL of vertical extent `size` (cam.fov_deg is not read): render it with
+    Context.set_camera_model(capi.CAMERA_PROJECTIVE) -- the pinhole model shoots a fan from `position` through this matrix."""
+    m = _t12_to_mat4(cam.transform)
+    vp = orthogonal(size, float(width) / float(height), cam.near, cam.far) @ np.linalg.inv(m)
+    ivp = np.linalg.inv(vp)
+    c = np.zeros((), dtype=wire.CAMERA)
+    c["vp"] = vp.T.reshape(-1).astype(np.float32)    # column-major
+    c["ivp"] = ivp.T.reshape(-1).astype(np.float32)
+    c["position"] = (*m[:3, 3], 1.0)
+    c["frame_index"] = frame_index
+    c["near"] = cam.near
+    c["far"] = cam.far
+    return c
+
+
 def lens_from_physical(focal_length_mm: float, f_stop: float, focus_distance_m: float):
     """(aperture_radius, focus_distance) for Context.set_lens from a physical camera (Godot's CameraAttributesPhysical:
     frustum_focal_length in mm, exposure_aperture in f-stops, frustum_focus_distance in m): the entrance pupil's diameter is

@@ -481,6 +481,35 @@ int jpt_set_material_extensions(jpt_ctx *ctx, uint32_t flags);
  * focus).  The depth image holds the distance from the ray's origin on the lens, not from cam.position. */
 int jpt_set_lens(jpt_ctx *ctx, float aperture_radius, float focus_distance);
 
+/* The camera model: how a raster position becomes a primary ray (no reference counterpart: the reference, too, shoots every ray
+ * from cam.position, which is a wrong picture under an orthographic matrix).
+ *   PINHOLE      (default) from cam.position towards ivp * (nx, ny, 1, 1): right for a perspective Projection.  The launches, the
+ *                kernels and the bits of a context that never made this call.
+ *   PROJECTIVE   from the position's point on the near plane, ivp * (nx, ny, -1, 1), towards its point on the far plane, ivp * (nx,
+ *                ny, +1, 1) (each divided by its own w; the GL-style z range of Godot's Projection).  Exact for Godot's
+ *                PROJECTION_ORTHOGONAL (parallel rays); for a perspective matrix the pinhole's directions with near-plane clipping;
+ *                right for PROJECTION_FRUSTUM and any other invertible projection.
+ *   EQUIRECT     the full sphere around cam.position, in the layout jpt_set_environment reads: with u = x / width, v = y / height,
+ *                phi = (u - 1/2) 2 pi, theta = v pi, the direction r sin(theta) sin(phi) + u cos(theta) + f sin(theta) cos(phi) over the
+ *                camera basis (f, r, u) jpt_set_lens derives from camera160 -- row 0 is the camera's up pole, the centre column
+ *                forward, columns increase to the right.  With the identity camera this is the map's (sin theta sin phi, cos theta,
+ *                -sin theta cos phi): a panorama rendered at a point is, as it is, an environment map for that point.
+ * The seed and the jitter of a path are the pinhole's, draw for draw, so every later vertex draws what it draws under the pinhole
+ * (csrc/jpt_camera.h; DESIGN.md section 2 pins every operation).  A value that is none of the three: JPT_E_INVALID; host-only
+ * contexts: JPT_E_DEVICE after the check.
+ * The model belongs to the context, like the lens: it survives scene commits, uploads, refits and mesh updates, jpt_set_camera and
+ * jpt_set_params; jpt_scene_share does not copy it.  Each render takes it by value: queued renders keep the model of their own call.
+ * A render under PROJECTIVE or EQUIRECT launches the model's form of its bounce-0 kernel (wf2_primary_cam / wf2_primary_env_cam; the
+ * audit kernel branches) and has no sky cull (jpt_stats.sky_culled is 0); every later launch, the workspace and
+ * jpt_get_workspace_bytes are the pinhole's.  The depth image holds the distance from the ray's own origin.
+ * The render calls return JPT_E_STATE, with a message, for a model other than PINHOLE with a lens radius > 0 (the disk is defined
+ * around one centre of projection) or under JPT_DENOISE_TEMPORAL, for EQUIRECT with a basis that is not finite and for PROJECTIVE
+ * with an ivp that is not finite.  jpt_set_debug_steps ignores the model, as it ignores the lens.
+ * jpt_denoise builds its guides from the model's ray through the pixel centre, and jpt_query_pixels forms the model's ray of each
+ * raster position (the same two JPT_E_STATE cases apply to both); jpt_query_rays and jpt_query_rays_device take rays as given. */
+enum { JPT_CAMERA_PINHOLE = 0, JPT_CAMERA_PROJECTIVE = 1, JPT_CAMERA_EQUIRECT = 2 };
+int jpt_set_camera_model(jpt_ctx *ctx, int32_t model);
+
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
  *   REFERENCE_LAYOUT   one thread per pixel straight over the six reference-layout buffers, node for node
@@ -738,7 +767,8 @@ int jpt_set_auto_exposure(jpt_ctx *ctx, int32_t enable);                  /* def
  * JPT_QUERY_ANY stops at the first accepted triangle with t < tmax and writes occluded_out only; hits_out must be NULL.
  * jpt_query_pixels: xy[2i], xy[2i + 1] are raster coordinates in pixels (x + 0.5, y + 0.5 is the centre of pixel (x, y)); the ray is
  *   cam.position and the un-jittered pinhole direction of the guide pass, mode CLOSEST, tmax 1e9.  It ignores jpt_set_lens, as the
- *   guide pass does.  Coordinates outside [0, width] x [0, height] are allowed (a ray is a ray); a non-finite one: JPT_HIT_BAD_RAY.
+ *   guide pass does, and follows jpt_set_camera_model, as the guide pass does: under PROJECTIVE or EQUIRECT the ray is the model's
+ *   ray of the exact position, from its own origin.  Coordinates outside [0, width] x [0, height] are allowed (a ray is a ray); a non-finite one: JPT_HIT_BAD_RAY.
  * Ordering: all three enqueue on the context's stream, behind every render, refit, mesh update and jpt_denoise queued before them and
  *   ahead of what is queued after; jpt_scene_update_mesh's device-side wait covers the queries queued before it.  The host forms
  *   block: rays and results travel through the context's pinned staging buffer in chunks of at most 2^20 rays (n is unbounded, the
@@ -838,6 +868,8 @@ int jpt_multi_set_light_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_material_extensions(jpt_multi *m, uint32_t flags);
 /* jpt_set_lens on every rank */
 int jpt_multi_set_lens(jpt_multi *m, float aperture_radius, float focus_distance);
+/* jpt_set_camera_model on every rank */
+int jpt_multi_set_camera_model(jpt_multi *m, int32_t model);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -919,6 +951,12 @@ int jpt_debug_dielectric(int device_id, const float *normals3, const float *out_
  * functions compiled for the host. */
 int jpt_debug_lens_rays(int device_id, const void *camera160, int32_t width, int32_t height, uint32_t frame_index,
                         float aperture_radius, float focus_distance, float *origins3_out, float *dirs3_out);
+/* The ray generation of a render under jpt_set_camera_model(model) (PINHOLE: primary_ray's) for every pixel of one frame of a width
+ * x height image seen through camera160, laid out as jpt_debug_lens_rays lays its rays out.  The model is checked as
+ * jpt_set_camera_model checks it; EQUIRECT with a basis, or PROJECTIVE with an ivp, that is not finite: JPT_E_STATE.  device_id >= 0:
+ * the functions the kernels inline, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
+int jpt_debug_camera_rays(int device_id, const void *camera160, int32_t width, int32_t height, uint32_t frame_index, int32_t model,
+                          float *origins3_out, float *dirs3_out);
 /* The lens step alone, on the host, from caller-made randoms: for pinhole ray (origins3[3 i ..], dirs3[3 i ..]) and (xi2[2 i], xi2[2
  * i + 1]) the ray the lens of camera160 sends out (origins3_out, dirs3_out; either input ray kept when it does not point forward).
  * basis9_out (may be NULL): f, r, u.  The radius and the focus are taken as they are; a basis that is not finite is still returned,

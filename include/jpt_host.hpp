@@ -102,6 +102,21 @@ struct Projection {  // godot: columns[4][4]
         p.columns[3][3] = 0;
         return p;
     }
+    // a Camera3D with PROJECTION_ORTHOGONAL: vertical extent `size`, horizontal size * aspect.  Render it with
+    // PathTracingCamera::set_camera_model(JPT_CAMERA_PROJECTIVE): the pinhole model shoots a fan from the camera's origin.
+    static Projection create_orthogonal(float size, float aspect, float z_near, float z_far, bool /*flip_fov*/ = false)
+    {
+        Projection p;
+        const float right = size * aspect / 2.0f, left = -right, top = size / 2.0f, bottom = -top;
+        p.columns[0][0] = 2.0f / (right - left);
+        p.columns[3][0] = -((right + left) / (right - left));
+        p.columns[1][1] = 2.0f / (top - bottom);
+        p.columns[3][1] = -((top + bottom) / (top - bottom));
+        p.columns[2][2] = -2.0f / (z_far - z_near);
+        p.columns[3][2] = -((z_far + z_near) / (z_far - z_near));
+        p.columns[3][3] = 1.0f;
+        return p;
+    }
     Projection() = default;
     // Projection(const Transform3D&): the transform promoted to a 4x4 with last row 0 0 0 1
     explicit Projection(const Transform3D& t)
@@ -802,6 +817,10 @@ class PathTracingCamera {
     {
         set_lens(focal_length_mm * 1e-3f / (2.0f * f_stop), focus_distance_m);
     }
+    // jpt_set_camera_model: JPT_CAMERA_PINHOLE (default), JPT_CAMERA_PROJECTIVE (a Camera3D with PROJECTION_ORTHOGONAL or
+    // PROJECTION_FRUSTUM: pass get_camera_projection() as it is) or JPT_CAMERA_EQUIRECT (a 360-degree panorama in the environment
+    // map's layout)
+    void set_camera_model(int32_t model) { check(ctx, jpt_set_camera_model(ctx, model), "jpt_set_camera_model"); }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
