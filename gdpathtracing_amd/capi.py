@@ -60,6 +60,8 @@ SYMBOLS = [
     "jpt_set_material_extensions", "jpt_multi_set_material_extensions", "jpt_debug_dielectric",
     "jpt_set_lens", "jpt_multi_set_lens", "jpt_debug_lens_rays", "jpt_debug_lens_sample",
     "jpt_set_camera_model", "jpt_multi_set_camera_model", "jpt_debug_camera_rays",
+    "jpt_set_bake_texels", "jpt_bake_begin", "jpt_bake_add_surface", "jpt_read_bake_texels", "jpt_multi_set_bake_texels",
+    "jpt_debug_bake_rays", "jpt_debug_bake_raster",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
@@ -292,6 +294,14 @@ def lib():
         L.jpt_set_camera_model.argtypes = [vp, i32]
         L.jpt_multi_set_camera_model.argtypes = [vp, i32]
         L.jpt_debug_camera_rays.argtypes = [C.c_int, vp, i32, i32, u32, i32, vp, vp]
+    if hasattr(L, "jpt_set_bake_texels") or "JPT_LIB" not in os.environ:
+        L.jpt_set_bake_texels.argtypes = [vp, vp, vp, i32, i32]
+        L.jpt_bake_begin.argtypes = [vp, i32, i32]
+        L.jpt_bake_add_surface.argtypes = [vp, C.POINTER(Surface), vp, vp]
+        L.jpt_read_bake_texels.argtypes = [vp, vp, vp]
+        L.jpt_multi_set_bake_texels.argtypes = [vp, vp, vp, i32, i32]
+        L.jpt_debug_bake_rays.argtypes = [C.c_int, vp, vp, i32, i32, u32, vp, vp, vp]
+        L.jpt_debug_bake_raster.argtypes = [C.c_int, C.POINTER(Surface), vp, vp, i32, i32, vp, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

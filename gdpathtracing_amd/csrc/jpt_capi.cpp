@@ -824,6 +824,24 @@ int jpt::resolve_camera_model(jpt_ctx* c, const LensDev& lens, CamModelDev& out)
     return camera_model_now(c, out);
 }
 
+int jpt::resolve_bake(jpt_ctx* c, BakeDev& out)
+{
+    out = BakeDev{};
+    if (!c->d_bake_nrm.p || c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the images, as it ignores the lens)
+    if (c->bake_w != c->width || c->bake_h != c->height)
+        return fail(c, JPT_E_STATE, "the bake images are " + std::to_string(c->bake_w) + " x " + std::to_string(c->bake_h) + " texels but jpt_set_params says " +
+                                        std::to_string(c->width) + " x " + std::to_string(c->height) + ": a bake render has one path per texel (jpt_set_bake_texels)");
+    if (c->lens_radius > 0.0f)
+        return fail(c, JPT_E_STATE, "a bake render has no lens: set the lens radius to 0 (jpt_set_lens) or free the bake images (jpt_set_bake_texels)");
+    if (c->camera_model != JPT_CAMERA_PINHOLE)
+        return fail(c, JPT_E_STATE, "a bake render has no camera model: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or free the bake images (jpt_set_bake_texels)");
+    if (c->denoise == JPT_DENOISE_TEMPORAL)
+        return fail(c, JPT_E_STATE, "temporal reprojection assumes a camera: set another denoising mode or free the bake images (jpt_set_bake_texels)");
+    out.position = c->d_bake_pos.p;
+    out.normal = c->d_bake_nrm.p;
+    return JPT_OK;
+}
+
 namespace {
 
 // What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
@@ -876,6 +894,8 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     if (r.lens.radius > 0.0f) return JPT_OK;
     // (nor has a render under another camera model: the rectangles are the pinhole's projection of the boxes)
     if (r.cam_model.model != kCamPinhole) return JPT_OK;
+    // (nor has a bake render: its paths start on the surfaces)
+    if (r.bake.normal != nullptr) return JPT_OK;
     compute_sky_cull(c, r.cull);
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
@@ -914,7 +934,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.lens, r.cam_model);
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.lens, r.cam_model, r.bake);
         }
         return JPT_OK;
     }
@@ -1022,6 +1042,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
     const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
     Wf2Render r;
+    if ((rc = resolve_bake(c, r.bake)) != JPT_OK) return rc;
     if ((rc = resolve_lens(c, r.lens)) != JPT_OK) return rc;
     if ((rc = resolve_camera_model(c, r.lens, r.cam_model)) != JPT_OK) return rc;
     if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
@@ -2073,6 +2094,136 @@ int jpt_set_camera_model(jpt_ctx* c, int32_t model)
     return JPT_OK;
 }
 
+// ---- lightmap baking: the context's texel images (jpt_bake.h) -------------------------------------------------------------------
+
+// the renders already queued read the old images: they finish first (every one of them ends with work on the context's stream)
+static int bake_wait(jpt_ctx* c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return JPT_OK;
+}
+
+static void bake_release(jpt_ctx* c)
+{
+    c->d_bake_pos.release();
+    c->d_bake_nrm.release();
+    c->d_bake_winner.release();
+    c->d_bake_in.release();
+    c->bake_w = c->bake_h = 0;
+}
+
+static int bake_alloc(jpt_ctx* c, int32_t width, int32_t height)
+{
+    const size_t n = (size_t)width * (size_t)height;
+    hipError_t e = c->d_bake_pos.resize(n);
+    if (e == hipSuccess) e = c->d_bake_nrm.resize(n);
+    if (e != hipSuccess) {
+        bake_release(c);
+        return hip_fail(c, e, "hipMalloc of the bake images");
+    }
+    c->bake_w = width;
+    c->bake_h = height;
+    return JPT_OK;
+}
+
+int jpt_set_bake_texels(jpt_ctx* c, const float* position4, const float* normal4, int32_t width, int32_t height)
+{
+    if (!c) return JPT_E_INVALID;
+    const bool freeing = !position4 && !normal4 && width == 0 && height == 0;
+    if (!freeing) {
+        if (!position4 || !normal4) return fail(c, JPT_E_INVALID, "jpt_set_bake_texels: position4 and normal4 are both given, or (NULL, NULL, 0, 0) frees the images");
+        std::string why;
+        int rc = check_bake_size("jpt_set_bake_texels", width, height, why);
+        if (rc == JPT_OK) rc = check_bake_texels("jpt_set_bake_texels", position4, normal4, (size_t)width * (size_t)height, why);
+        if (rc != JPT_OK) return fail(c, rc, why);
+    }
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_texels: host-only context has no bake images");
+    int rc = bake_wait(c);
+    if (rc != JPT_OK) return rc;
+    if (freeing) {
+        bake_release(c);
+        return JPT_OK;
+    }
+    if ((rc = bake_alloc(c, width, height)) != JPT_OK) return rc;
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
+    HIP_TRY(c, hipMemcpy(c->d_bake_pos.p, position4, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_bake_nrm.p, normal4, bytes, hipMemcpyHostToDevice));
+    return JPT_OK;
+}
+
+int jpt_bake_begin(jpt_ctx* c, int32_t width, int32_t height)
+{
+    if (!c) return JPT_E_INVALID;
+    std::string why;
+    int rc = check_bake_size("jpt_bake_begin", width, height, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_begin: host-only context has no bake images");
+    if ((rc = bake_wait(c)) != JPT_OK) return rc;
+    if ((rc = bake_alloc(c, width, height)) != JPT_OK) return rc;
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
+    HIP_TRY(c, hipMemsetAsync(c->d_bake_pos.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_bake_nrm.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return JPT_OK;
+}
+
+int jpt_bake_add_surface(jpt_ctx* c, const jpt_surface* surface, const float* uv2, const float* transform12)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!surface) return fail(c, JPT_E_INVALID, "jpt_bake_add_surface: null surface");
+    std::string why;
+    int rc = check_bake_surface("jpt_bake_add_surface", surface->vertices, surface->normals, surface->indices, surface->n_vertices, surface->n_indices, uv2,
+                                transform12, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_add_surface: host-only context has no bake images");
+    if (!c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_bake_add_surface: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    if ((rc = bake_wait(c)) != JPT_OK) return rc;
+    const uint32_t n_tris = (uint32_t)(surface->n_indices / 3);
+    if (n_tris == 0) return JPT_OK;
+    // the surface staged in one device buffer: vertices, normals, uv2, indices (each a multiple of 4 bytes)
+    const size_t nv = (size_t)surface->n_vertices;
+    const size_t b_v = nv * 3 * sizeof(float), b_uv = nv * 2 * sizeof(float), b_i = (size_t)n_tris * 3 * sizeof(int32_t);
+    const size_t need = 2 * b_v + b_uv + b_i;
+    if (c->d_bake_in.n < need) HIP_TRY(c, c->d_bake_in.resize(need));
+    const size_t npx = (size_t)c->bake_w * (size_t)c->bake_h;
+    if (c->d_bake_winner.n < npx) HIP_TRY(c, c->d_bake_winner.resize(npx));
+    char* base = c->d_bake_in.p;
+    HIP_TRY(c, hipMemcpy(base, surface->vertices, b_v, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(base + b_v, surface->normals, b_v, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(base + 2 * b_v, uv2, b_uv, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(base + 2 * b_v + b_uv, surface->indices, b_i, hipMemcpyHostToDevice));
+    BakeSurfaceDev sd;
+    sd.vertices = reinterpret_cast<const float*>(base);
+    sd.normals = reinterpret_cast<const float*>(base + b_v);
+    sd.uv2 = reinterpret_cast<const float*>(base + 2 * b_v);
+    sd.indices = reinterpret_cast<const int32_t*>(base + 2 * b_v + b_uv);
+    sd.n_tris = n_tris;
+    transform12_to_mat16(transform12, sd.transform);
+    launch_bake_raster(c->stream, sd, c->bake_w, c->bake_h, c->d_bake_winner.p, c->d_bake_pos.p, c->d_bake_nrm.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return JPT_OK;
+}
+
+int jpt_read_bake_texels(jpt_ctx* c, float* position4, float* normal4)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_bake_texels: host-only context has no bake images");
+    if (!c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_read_bake_texels: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->bake_w * (size_t)c->bake_h * sizeof(float4);
+    float* const out[2] = {position4, normal4};
+    const float4* const src[2] = {c->d_bake_pos.p, c->d_bake_nrm.p};
+    for (int k = 0; k < 2; k++) {
+        if (!out[k]) continue;
+        const int rc = staged_read(c, src[k], bytes);
+        if (rc != JPT_OK) return rc;
+        std::memcpy(out[k], c->h_read_pinned.p, bytes);
+    }
+    return JPT_OK;
+}
+
 int jpt_set_debug_steps(jpt_ctx* c, int32_t enable)
 {
     if (!c) return JPT_E_INVALID;
@@ -2274,6 +2425,7 @@ int jpt_denoise(jpt_ctx* c)
     if (!c->scene_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
     if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_denoise: jpt_set_params / jpt_set_camera not called");
     if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_denoise: no frame accumulated since the last reset");
+    if (c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_denoise: the guides are camera rays, and the context holds bake images (jpt_set_bake_texels)");
     CamModelDev cm;   // (the guides are the first hits of the view the renders took: jpt_set_camera_model)
     const int rc_cm = camera_model_now(c, cm);
     if (rc_cm != JPT_OK) return rc_cm;
@@ -2633,6 +2785,7 @@ int jpt_query_pixels(jpt_ctx* c, const float* xy, uint32_t n, jpt_ray_hit* hits_
     if (rc != JPT_OK || done) return rc;
     if ((rc = query_state(c, "jpt_query_pixels")) != JPT_OK) return rc;
     if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_query_pixels: jpt_set_params / jpt_set_camera not called");
+    if (c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_query_pixels: picking rays are camera rays, and the context holds bake images (jpt_set_bake_texels)");
     return query_host(c, false, true, xy, n, hits_out, nullptr);
 }
 

@@ -173,6 +173,9 @@ int resolve_lens(jpt_ctx* c, LensDev& out);
 // DEBUG_STEPS, else the model with the basis derived from the camera as it is now.  JPT_E_STATE: a lens radius > 0 or the temporal
 // pass with a model other than the pinhole, EQUIRECT's basis or PROJECTIVE's ivp not finite.
 int resolve_camera_model(jpt_ctx* c, const LensDev& lens, CamModelDev& out);
+// The texel images of one render of `c` (jpt_set_bake_texels; jpt_capi.cpp), before its lens: null without images or with
+// DEBUG_STEPS.  JPT_E_STATE: the images' size is not the render's, a lens radius > 0, a model other than the pinhole, the temporal pass.
+int resolve_bake(jpt_ctx* c, BakeDev& out);
 
 }  // namespace jpt
 
@@ -215,6 +218,12 @@ struct jpt_ctx {
     uint32_t frame_count = 0;  // frames accumulated since reset
     int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
     int32_t camera_model = JPT_CAMERA_PINHOLE;   // jpt_set_camera_model: the context's, like the lens; each render takes it by value
+    // jpt_set_bake_texels / jpt_bake_begin: the context's, like the environment map; present images make every render a bake render.
+    // The rasteriser's winner image and staged surface (jpt_bake_add_surface) are grow-only
+    DevBuf<float4> d_bake_pos, d_bake_nrm;
+    int32_t bake_w = 0, bake_h = 0;
+    DevBuf<uint32_t> d_bake_winner;
+    DevBuf<char> d_bake_in;
     float lens_radius = 0.0f, lens_focus = 1.0f;   // jpt_set_lens: the context's, like the sampling modes; radius 0 is the pinhole
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "jpt_instance_math.h"
 #include "jpt_kernels.h"
 #include "jpt_nodeq.h"
 #include "jpt_trace_core.h"
@@ -605,6 +606,106 @@ int jpt_debug_camera_rays(int device_id, const void* camera160, int32_t width, i
     if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "camera_rays_probe");
     if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + n * 3u, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_bake_rays(int device_id, const float* position4, const float* normal4, int32_t width, int32_t height, uint32_t frame_index,
+                        float* origins3_out, float* dirs3_out, uint8_t* valid_out)
+{
+    if (!position4 || !normal4 || !origins3_out || !dirs3_out || !valid_out) {
+        g_debug_error = "jpt_debug_bake_rays: null argument";
+        return JPT_E_INVALID;
+    }
+    const int rc0 = check_bake_size("jpt_debug_bake_rays", width, height, g_debug_error);
+    if (rc0 != JPT_OK) return rc0;
+    const size_t n = (size_t)width * (size_t)height;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        bake_rays_host(reinterpret_cast<const float4*>(position4), reinterpret_cast<const float4*>(normal4), width, height, frame_index, origins3_out,
+                       dirs3_out, valid_out);
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t b_img = n * sizeof(float4), b_ray = n * 3u * sizeof(float);
+    char* d_all = nullptr;   // position4, normal4, origins, directions, valid
+    if ((e = hipMalloc((void**)&d_all, 2 * b_img + 2 * b_ray + n)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    int rc = JPT_OK;
+    if ((e = hipMemcpy(d_all, position4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_all + b_img, normal4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        BakeDev bake;
+        bake.position = reinterpret_cast<const float4*>(d_all);
+        bake.normal = reinterpret_cast<const float4*>(d_all + b_img);
+        launch_bake_rays_probe(nullptr, bake, width, height, frame_index, reinterpret_cast<float*>(d_all + 2 * b_img),
+                               reinterpret_cast<float*>(d_all + 2 * b_img + b_ray), reinterpret_cast<uint8_t*>(d_all + 2 * b_img + 2 * b_ray));
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "bake_rays_probe");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all + 2 * b_img, b_ray, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + 2 * b_img + b_ray, b_ray, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(valid_out, d_all + 2 * b_img + 2 * b_ray, n, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_bake_raster(int device_id, const jpt_surface* surface, const float* uv2, const float* transform12, int32_t width, int32_t height,
+                          float* position4_out, float* normal4_out)
+{
+    if (!surface || !position4_out || !normal4_out) {
+        g_debug_error = "jpt_debug_bake_raster: null argument";
+        return JPT_E_INVALID;
+    }
+    int rc = check_bake_size("jpt_debug_bake_raster", width, height, g_debug_error);
+    if (rc == JPT_OK)
+        rc = check_bake_surface("jpt_debug_bake_raster", surface->vertices, surface->normals, surface->indices, surface->n_vertices, surface->n_indices, uv2,
+                                transform12, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    const size_t n = (size_t)width * (size_t)height, b_img = n * sizeof(float4);
+    std::memset(position4_out, 0, b_img);
+    std::memset(normal4_out, 0, b_img);
+    BakeSurfaceDev sd;
+    sd.n_tris = (uint32_t)(surface->n_indices / 3);
+    transform12_to_mat16(transform12, sd.transform);
+    if (sd.n_tris == 0) return JPT_OK;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        sd.vertices = surface->vertices;
+        sd.normals = surface->normals;
+        sd.uv2 = uv2;
+        sd.indices = surface->indices;
+        bake_raster_host(sd, width, height, reinterpret_cast<float4*>(position4_out), reinterpret_cast<float4*>(normal4_out));
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t nv = (size_t)surface->n_vertices;
+    const size_t b_v = nv * 3 * sizeof(float), b_uv = nv * 2 * sizeof(float), b_i = (size_t)sd.n_tris * 3 * sizeof(int32_t), b_win = n * sizeof(uint32_t);
+    char* d_all = nullptr;   // position4, normal4, winner, vertices, normals, uv2, indices (16-byte images first)
+    if ((e = hipMalloc((void**)&d_all, 2 * b_img + b_win + 2 * b_v + b_uv + b_i)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    char* d_in = d_all + 2 * b_img + b_win;
+    if ((e = hipMemset(d_all, 0, 2 * b_img)) != hipSuccess) rc = hip_fail(e, "hipMemset");
+    if (rc == JPT_OK && (e = hipMemcpy(d_in, surface->vertices, b_v, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_in + b_v, surface->normals, b_v, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_in + 2 * b_v, uv2, b_uv, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_in + 2 * b_v + b_uv, surface->indices, b_i, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        sd.vertices = reinterpret_cast<const float*>(d_in);
+        sd.normals = reinterpret_cast<const float*>(d_in + b_v);
+        sd.uv2 = reinterpret_cast<const float*>(d_in + 2 * b_v);
+        sd.indices = reinterpret_cast<const int32_t*>(d_in + 2 * b_v + b_uv);
+        launch_bake_raster(nullptr, sd, width, height, reinterpret_cast<uint32_t*>(d_all + 2 * b_img), reinterpret_cast<float4*>(d_all),
+                           reinterpret_cast<float4*>(d_all + b_img));
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "bake raster kernels");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(position4_out, d_all, b_img, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(normal4_out, d_all + b_img, b_img, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
     return rc;
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "jpt_nodeq.h"
+#include "jpt_bake.h"
 #include "jpt_camera.h"
 #include "jpt_lens.h"
 #include "jpt_shade.h"
@@ -233,7 +234,29 @@ struct Lighting {
 
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens, const CamModelDev& cm);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens, const CamModelDev& cm,
+                      const BakeDev& bake);
+
+// The UV2 rasteriser of jpt_bake_add_surface (jpt_kernels_bake.hip), on `stream`: clears `winner` (width * height words), lets every
+// triangle of `surf` claim the texels whose centres it covers (atomicMin of its index), then writes the texels that have a winner
+// into position4 / normal4 (bake_resolve, jpt_bake.h) and leaves the others as they are.  Every pointer is device memory.
+void launch_bake_raster(hipStream_t stream, const BakeSurfaceDev& surf, int32_t width, int32_t height, uint32_t* winner, float4* position4,
+                        float4* normal4);
+// the same on the host, over host memory: a plain loop over texels and triangles calling the same coverage and resolve functions
+void bake_raster_host(const BakeSurfaceDev& surf, int32_t width, int32_t height, float4* position4, float4* normal4);
+// the first rays of a bake render's paths (bake_ray) for every texel of one frame, on `stream`: device pointers, n = width * height
+void launch_bake_rays_probe(hipStream_t stream, const BakeDev& bake, int32_t width, int32_t height, uint32_t frame, float* origins3, float* dirs3,
+                            uint8_t* valid);
+void bake_rays_host(const float4* position4, const float4* normal4, int32_t width, int32_t height, uint32_t frame, float* origins3, float* dirs3,
+                    uint8_t* valid);
+// the checks of jpt_set_bake_texels / jpt_bake_begin on the size (jpt_capi.cpp), also run by the jpt_debug_bake_* entry points
+int check_bake_size(const char* call, int32_t width, int32_t height, std::string& why);
+// ... of jpt_set_bake_texels on the images: a valid texel with a non-finite position or normal component is JPT_E_INVALID
+int check_bake_texels(const char* call, const float* position4, const float* normal4, size_t n, std::string& why);
+// ... and of jpt_bake_add_surface on the surface: null arrays, n_indices no multiple of 3, an index out of range (JPT_E_INVALID), more
+// than 2^24 triangles (JPT_E_LIMIT)
+int check_bake_surface(const char* call, const float* vertices, const float* normals, const int32_t* indices, int32_t n_vertices, int32_t n_indices,
+                       const float* uv2, const float* transform12, std::string& why);
 
 // The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
 // tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory
@@ -294,6 +317,8 @@ struct Wf2Render {
                                            // primary launch, with `cull` off (n < 0) and no sky tiles
     CamModelDev cam_model;                 // jpt_set_camera_model, resolved for this render (resolve_camera_model): a model other than the
                                            // pinhole takes the *_cam forms of the primary launch, again with no cull and no sky tiles
+    BakeDev bake;                          // jpt_set_bake_texels, resolved for this render (resolve_bake): images present take the *_bake
+                                           // forms of the primary launch, again with no cull and no sky tiles
 };
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block

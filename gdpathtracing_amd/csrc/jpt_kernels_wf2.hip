@@ -725,6 +725,15 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #undef JPT_CAMERA_MODEL
+// ... and their bake forms (jpt_set_bake_texels): wf2_primary_bake, wf2_primary_env_bake
+#define JPT_BAKE 1
+#define JPT_ENV 0
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#undef JPT_BAKE
 
 // the window of a render (local tiles): x0, y0, nx, ny
 struct TileWindow {
@@ -994,6 +1003,11 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
                     hipLaunchKernelGGL((wf2_primary_env_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cam_model, counters);
                 else
                     hipLaunchKernelGGL((wf2_primary_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cam_model, counters);
+            } else if (r.bake.normal != nullptr) {   // (jpt_set_bake_texels: the bake forms; r.cull is off)
+                if (lg.env_mode != 0)
+                    hipLaunchKernelGGL((wf2_primary_env_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.bake, counters);
+                else
+                    hipLaunchKernelGGL((wf2_primary_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.bake, counters);
             } else if (lg.env_mode != 0)   // (the primary launch is its miss model's: a primary miss has weight 1)
                 hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
             else

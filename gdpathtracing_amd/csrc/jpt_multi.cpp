@@ -321,6 +321,16 @@ int jpt_multi_set_camera_model(jpt_multi* m, int32_t model)
     return JPT_OK;
 }
 
+int jpt_multi_set_bake_texels(jpt_multi* m, const float* position4, const float* normal4, int32_t width, int32_t height)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_bake_texels(m->ctx[r], position4, normal4, width, height);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_set_camera(jpt_multi* m, const void* camera160)
 {
     if (!m) return JPT_E_INVALID;

@@ -46,7 +46,7 @@
 template <bool COUNT, bool TIES>
 __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefSceneDev sc, TieShadowDev shadow, SceneShading sh, FrameParams fp, RefCamera cam,
                                                         float4* __restrict__ accum, uint32_t* __restrict__ ldr,
-                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters, LensDev lens, CamModelDev cm JPT_ENV_PARAM)
+                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters, LensDev lens, CamModelDev cm, BakeDev bake JPT_ENV_PARAM)
 {
     // 8x32 pixel tiles: a wave covers 8x8 pixels
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -59,6 +59,14 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
         Ray ray = primary_ray(cam, fp.width, fp.height, px, py, fp.frame_index, sx, sy);
         if (lens.radius > 0.0f) lens_ray(lens, sx, sy, ray);   // (jpt_set_lens; the host passes radius 0 with DEBUG_STEPS)
         if (cm.model != kCamPinhole) ray = camera_ray(cam, cm, fp.width, fp.height, px, py, fp.frame_index, sx, sy);   // (jpt_set_camera_model; likewise)
+        bool lit = true;   // (jpt_set_bake_texels: an invalid texel traces nothing -- radiance 0, depth far; null images: a camera render,
+                           // which the host also passes with DEBUG_STEPS)
+        if (bake.normal != nullptr) {
+            const size_t texel = (size_t)py * (size_t)fp.width + (size_t)px;
+            const float4 bake_n = bake.normal[texel];
+            lit = bake_texel_valid(bake_n);
+            if (lit) ray = bake_ray(bake.position[texel], bake_n, px, py, fp.frame_index, sx, sy);
+        }
         float depth = cam.far_;
         f3 radiance = mk3(0.0f, 0.0f, 0.0f);
         f3 throughput = mk3(1.0f, 1.0f, 1.0f);
@@ -75,7 +83,7 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             const float g = clamp_((float)hit.steps / 256.0f, 0.0f, 1.0f);
             radiance = mk3(g, g, g);
         } else
-        for (int i = 0; i < fp.max_bounces + 1; i++) {  // main.glsl:377
+        for (int i = 0; lit && i < fp.max_bounces + 1; i++) {  // main.glsl:377
             RefHit hit;
             if (COUNT) cnt.rays++;
             const bool is_hit = ray_trace_tlas<COUNT>(sc, ray, hit, cnt);

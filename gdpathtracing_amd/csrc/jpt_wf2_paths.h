@@ -1,7 +1,7 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
 // which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace
-// (and twice more with JPT_LENS defined, and twice with JPT_CAMERA_MODEL, for the lens and camera-model forms of wf2_primary alone:
-// see there):
+// (and twice more with JPT_LENS defined, twice with JPT_CAMERA_MODEL and twice with JPT_BAKE, for the lens, camera-model and bake
+// forms of wf2_primary alone: see there):
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -81,6 +81,11 @@
 // JPT_CAMERA_MODEL defined (likewise): the forms wf2_primary_cam and wf2_primary_env_cam (jpt_set_camera_model) -- the model
 // (CamModelDev, by value) where the sky cull was, camera_ray (jpt_camera.h) in place of primary_ray, and no cull: the rectangles are
 // the pinhole's.  The model is a kernel argument, so the branch between its two recipes is a scalar one.
+//
+// JPT_BAKE defined (likewise): the forms wf2_primary_bake and wf2_primary_env_bake (jpt_set_bake_texels) -- the texel images
+// (BakeDev, by value) where the sky cull was; at refill the lane reads its texel's normal (16 B) and, for a valid texel, its position
+// (16 B) and starts the path with bake_ray (jpt_bake.h).  An invalid texel traces nothing: its path ends here with radiance 0 and
+// first-hit distance cam.far_, as a sky path of the default kernel ends in save_results, and is not counted as a ray.  No cull.
 #ifdef JPT_LENS
 #if JPT_ENV
 #define JPT_PRIMARY_NAME wf2_primary_env_lens
@@ -95,6 +100,13 @@
 #define JPT_PRIMARY_NAME wf2_primary_cam
 #endif
 #define JPT_PRIMARY_PARAM CamModelDev cm
+#elif defined(JPT_BAKE)
+#if JPT_ENV
+#define JPT_PRIMARY_NAME wf2_primary_env_bake
+#else
+#define JPT_PRIMARY_NAME wf2_primary_bake
+#endif
+#define JPT_PRIMARY_PARAM BakeDev bake
 #else
 #define JPT_PRIMARY_NAME JPT_ENV_NAME(wf2_primary)
 #define JPT_PRIMARY_PARAM SkyCull cull
@@ -203,6 +215,16 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
                         {
                             uint32_t sx, sy;
                             const Ray ray = camera_ray(cam, cm, fp.width, fp.height, px, py, fp.frame_index + f, sx, sy);
+#elif defined(JPT_BAKE)
+                        const size_t texel = (size_t)py * (size_t)fp.width + (size_t)px;
+                        const float4 bake_n = bake.normal[texel];
+                        if (!bake_texel_valid(bake_n)) {
+                            if (COUNT) cnt.rays--;   // (no ray: the count above is taken back)
+                            store_final(wb, fp.accum_mode, path, mk3(0.0f, 0.0f, 0.0f));
+                            if ((int)f == fp.depth_frame) wb.first_depth[slot] = cam.far_;
+                        } else {
+                            uint32_t sx, sy;
+                            const Ray ray = bake_ray(bake.position[texel], bake_n, px, py, fp.frame_index + f, sx, sy);
 #else
                         if (sky_culled(cull, px, py)) {
                             if (COUNT) {
@@ -268,7 +290,7 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
 #undef JPT_PRIMARY_PARAM
 #endif  // JPT_ENV < 2
 
-#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL)   // (everything below: once per miss model)
+#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL) && !defined(JPT_BAKE)   // (everything below: once per miss model)
 
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
@@ -890,7 +912,7 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 
 #endif  // JPT_ENV < 2
 
-#endif  // JPT_LENS, JPT_CAMERA_MODEL
+#endif  // JPT_LENS, JPT_CAMERA_MODEL, JPT_BAKE
 
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM

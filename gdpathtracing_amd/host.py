@@ -111,6 +111,51 @@ def debug_camera_rays(device_id, camera160, width, height, frame_index, model):
     return origins, dirs
 
 
+def _bake_surface(surface, uv2, transform12):
+    """(jpt_surface, uv2 [n, 2], transform12 [12]) for jpt_bake_add_surface / jpt_debug_bake_raster; the caller keeps the tuple alive"""
+    uv = np.ascontiguousarray(uv2, dtype=np.float32).reshape(-1, 2)
+    if len(uv) != len(surface.vertices):
+        raise ValueError("uv2 has one (u, v) per vertex")
+    t12 = np.ascontiguousarray(transform12, dtype=np.float32).reshape(12)
+    s = capi.Surface()
+    s.vertices, s.normals, s.uvs, s.indices = _ptr(surface.vertices), _ptr(surface.normals), _ptr(surface.uvs), _ptr(surface.indices)
+    s.n_vertices, s.n_indices = len(surface.vertices), len(surface.indices)
+    return s, uv, t12
+
+
+def _bake_images(position4, normal4):
+    p = np.ascontiguousarray(position4, dtype=np.float32)
+    n = np.ascontiguousarray(normal4, dtype=np.float32)
+    if p.ndim != 3 or p.shape[2] != 4 or n.shape != p.shape:
+        raise ValueError("position4 and normal4 are float32 [height, width, 4]")
+    return p, n
+
+
+def debug_bake_rays(device_id, position4, normal4, frame_index):
+    """jpt_debug_bake_rays: the first rays of a bake render's paths for every texel of one frame -- (origins [height, width, 3], dirs
+    [height, width, 3]) float32 and valid [height, width] uint8 (an invalid texel: zeros).  device_id -1: the host's copy."""
+    p, n = _bake_images(position4, normal4)
+    h, w = p.shape[:2]
+    origins, dirs, valid = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.uint8)
+    L = capi.lib()
+    rc = L.jpt_debug_bake_rays(int(device_id), _ptr(p), _ptr(n), w, h, int(frame_index), _ptr(origins), _ptr(dirs), _ptr(valid))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_bake_rays failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return origins, dirs, valid
+
+
+def debug_bake_raster(device_id, surface, uv2, transform12, width, height):
+    """jpt_debug_bake_raster: jpt_bake_add_surface on all-invalid images -- (position4, normal4) float32 [height, width, 4].
+    device_id -1: a plain host loop over texels and triangles calling the same functions."""
+    s, uv, t12 = _bake_surface(surface, uv2, transform12)
+    p, n = np.zeros((height, width, 4), np.float32), np.zeros((height, width, 4), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_bake_raster(int(device_id), C.byref(s), _ptr(uv), _ptr(t12), int(width), int(height), _ptr(p), _ptr(n))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_bake_raster failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return p, n
+
+
 def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
     """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
     [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
@@ -350,6 +395,37 @@ class Context:
         for an orthographic matrix) or capi.CAMERA_EQUIRECT (the full sphere, in the environment map's layout).  The context's, like the
         lens; each render takes it by value."""
         self._ck(self._lib.jpt_set_camera_model(self.h, int(model)), "jpt_set_camera_model")
+
+    # ---- lightmap baking (jpt_set_bake_texels, jpt_bake_begin / jpt_bake_add_surface)
+    def set_bake_texels(self, position4, normal4):
+        """jpt_set_bake_texels: float32 [height, width, 4] each -- (world position, w) and (world normal, w); a texel is valid when its
+        normal's xyz is not zero.  While images are present every render is a bake render (one path per texel, cosine-distributed
+        about the normal).  (None, None) frees them.  Waits for the renders already queued."""
+        if position4 is None and normal4 is None:
+            self._ck(self._lib.jpt_set_bake_texels(self.h, None, None, 0, 0), "jpt_set_bake_texels")
+            self._bake_size = None
+            return
+        p, n = _bake_images(position4, normal4)
+        self._ck(self._lib.jpt_set_bake_texels(self.h, _ptr(p), _ptr(n), p.shape[1], p.shape[0]), "jpt_set_bake_texels")
+        self._bake_size = (p.shape[1], p.shape[0])
+
+    def bake_begin(self, width, height):
+        """jpt_bake_begin: width x height images, every texel invalid, for bake_add_surface to fill"""
+        self._ck(self._lib.jpt_bake_begin(self.h, int(width), int(height)), "jpt_bake_begin")
+        self._bake_size = (int(width), int(height))
+
+    def bake_add_surface(self, surface, uv2, transform12):
+        """jpt_bake_add_surface: rasterise one scenes.Surface's UV2 triangles (uv2 [n_vertices, 2]) through the instance's transform12
+        into the images, on the device; the lowest triangle index wins a texel, a later call replaces what it covers"""
+        s, uv, t12 = _bake_surface(surface, uv2, transform12)
+        self._ck(self._lib.jpt_bake_add_surface(self.h, C.byref(s), _ptr(uv), _ptr(t12)), "jpt_bake_add_surface")
+
+    def read_bake_texels(self):
+        """jpt_read_bake_texels: (position4, normal4) float32 [height, width, 4], the size the images were made with by this object"""
+        width, height = getattr(self, "_bake_size", None) or (1, 1)   # (without images the call answers E_STATE before it writes)
+        p, n = np.zeros((height, width, 4), np.float32), np.zeros((height, width, 4), np.float32)
+        self._ck(self._lib.jpt_read_bake_texels(self.h, _ptr(p), _ptr(n)), "jpt_read_bake_texels")
+        return p, n
 
     def set_material_extensions(self, flags):
         """jpt_set_material_extensions: capi.MATERIAL_EXT_NONE (default) or capi.MATERIAL_EXT_TRANSMISSION (padding[0:2] of every
@@ -837,6 +913,13 @@ class MultiContext:
 
     def set_camera_model(self, model):
         self._ck(self._lib.jpt_multi_set_camera_model(self.h, int(model)), "jpt_multi_set_camera_model")
+
+    def set_bake_texels(self, position4, normal4):
+        if position4 is None and normal4 is None:
+            self._ck(self._lib.jpt_multi_set_bake_texels(self.h, None, None, 0, 0), "jpt_multi_set_bake_texels")
+            return
+        p, n = _bake_images(position4, normal4)
+        self._ck(self._lib.jpt_multi_set_bake_texels(self.h, _ptr(p), _ptr(n), p.shape[1], p.shape[0]), "jpt_multi_set_bake_texels")
 
     def set_material_extensions(self, flags):
         self._ck(self._lib.jpt_multi_set_material_extensions(self.h, int(flags)), "jpt_multi_set_material_extensions")

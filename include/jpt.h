@@ -510,6 +510,53 @@ int jpt_set_lens(jpt_ctx *ctx, float aperture_radius, float focus_distance);
 enum { JPT_CAMERA_PINHOLE = 0, JPT_CAMERA_PROJECTIVE = 1, JPT_CAMERA_EQUIRECT = 2 };
 int jpt_set_camera_model(jpt_ctx *ctx, int32_t model);
 
+/* Lightmap baking: paths from surface texels instead of camera pixels (no reference counterpart; Godot's LightmapGI wants a lightmap
+ * per mesh over its UV2 channel).  Two device images of width * height * 4 floats each say where the texels are -- 32 B per texel of
+ * device memory, not counted by jpt_get_workspace_bytes:
+ *   position4 = (world position, w)      normal4 = (world normal, w)       (w is not read; the rasteriser writes the triangle, and 1)
+ * A texel is VALID when dot(n.xyz, n.xyz) > 0 (NaN fails the test); all zeros is the canonical invalid texel.  While a context holds
+ * images its renders are BAKE RENDERS: the path of texel (x, y) starts at position + nh * 0.001, nh the normalised normal, leaves in
+ * a cosine-distributed direction about nh and carries throughput 1, so accum.rgb / frame_count in JPT_ACCUM_HDR_F32 mode converges
+ * to E / pi, E the irradiance at the texel: the radiance a white Lambertian surface sends back, which is what a lightmap stores
+ * (multiply by the albedo in the engine).  An invalid texel traces nothing: radiance 0, first-hit distance far, no ray counted.
+ * The seed and the jitter draw of a path are the camera's, draw for draw; the direction's two randoms come from one pcg2d round of a
+ * copy of the seeds hashed as (sx ^ 0x3c6ef372, sy ^ 0xa54ff53a), so every later vertex draws what it draws under a camera
+ * (csrc/jpt_bake.h; DESIGN.md section 2 pins every operation).  Nothing downstream of the first ray knows: the shading, occlusion and
+ * accumulation kernels, environment maps, both MIS modes, glass, the 8-row partition, jpt_multi, every read-back, jpt_display and
+ * jpt_meter work on a bake render as on a picture.  The depth image holds the usual reversed-Z value of the distance from the ray's
+ * origin.  A bake render launches the bake form of its bounce-0 kernel (wf2_primary_bake / wf2_primary_env_bake; the audit kernel
+ * branches), has no sky cull (jpt_stats.sky_culled is 0), and every later launch and the workspace are the camera's.
+ *
+ * jpt_set_bake_texels    uploads both images; (NULL, NULL, 0, 0) frees them: renders are camera renders again, with the launches and
+ *                        the bits of a context that never baked.  A valid texel with a non-finite position or normal component:
+ *                        JPT_E_INVALID.
+ * jpt_bake_begin         allocates width x height images, every texel invalid, for jpt_bake_add_surface to fill.
+ * jpt_bake_add_surface   rasterises one surface's UV2 triangles (uv2: n_vertices * 2 floats, Mesh::ARRAY_TEX_UV2, the image is [0, 1]^2,
+ *                        row 0 at v = 0) through transform12 (the instance's, as jpt_scene_add_instance reads it) into the images, on
+ *                        the device: a texel whose CENTRE (x + 1/2, y + 1/2) lies inside or on the edge of a triangle with a UV2 area
+ *                        other than 0 gets the position and the normalised normal interpolated there (position4.w = the triangle's
+ *                        number, normal4.w = 1), or becomes invalid when a component is not finite.  Within a call the lowest
+ *                        triangle number wins a texel; a later call replaces what its own triangles cover and leaves the rest; the
+ *                        result does not depend on the order the device's threads run in.  surface->uvs is not read.  n_indices no
+ *                        multiple of 3, an index out of range or a null array: JPT_E_INVALID; more than 2^24 triangles: JPT_E_LIMIT.
+ * jpt_read_bake_texels   copies the images out; either pointer may be NULL.
+ * All sizes must be >= 1 (JPT_E_INVALID) and width * height at most 2^26 texels (JPT_E_LIMIT).  jpt_bake_add_surface and
+ * jpt_read_bake_texels without images: JPT_E_STATE.  Host-only contexts: JPT_E_DEVICE after the checks.
+ * The three writing calls WAIT for the renders the context has queued, which finish with the old images, and return when the images
+ * are written: queued renders keep the images of their own call.  The images belong to the context, like the environment map: they
+ * survive scene commits, uploads, refits and mesh updates; jpt_scene_share does not copy them.
+ * The render calls return JPT_E_STATE, with a message, while images are present and their size is not jpt_set_params' width x height
+ * (every rank of a partition holds the whole images), the lens radius is > 0, the camera model is not JPT_CAMERA_PINHOLE or the
+ * denoising mode is JPT_DENOISE_TEMPORAL.  jpt_set_debug_steps ignores the images, as it ignores the lens.  jpt_denoise and
+ * jpt_query_pixels return JPT_E_STATE while images are present: their guide and picking rays are camera rays.
+ * Out of scope: conservative coverage (a triangle that covers no texel centre leaves no texel), dilation of the finished map (do it
+ * on the host), atlas packing, next-event estimation at the texel itself (direct light reaches a texel by its first ray alone, so
+ * small emitters converge slowly), lightmap-aware denoiser guides and SH probes. */
+int jpt_set_bake_texels(jpt_ctx *ctx, const float *position4, const float *normal4, int32_t width, int32_t height);
+int jpt_bake_begin(jpt_ctx *ctx, int32_t width, int32_t height);
+int jpt_bake_add_surface(jpt_ctx *ctx, const jpt_surface *surface, const float *uv2, const float *transform12);
+int jpt_read_bake_texels(jpt_ctx *ctx, float *position4, float *normal4);
+
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
  *   REFERENCE_LAYOUT   one thread per pixel straight over the six reference-layout buffers, node for node
@@ -870,6 +917,8 @@ int jpt_multi_set_material_extensions(jpt_multi *m, uint32_t flags);
 int jpt_multi_set_lens(jpt_multi *m, float aperture_radius, float focus_distance);
 /* jpt_set_camera_model on every rank */
 int jpt_multi_set_camera_model(jpt_multi *m, int32_t model);
+/* jpt_set_bake_texels on every rank (each holds the whole images) */
+int jpt_multi_set_bake_texels(jpt_multi *m, const float *position4, const float *normal4, int32_t width, int32_t height);
 int jpt_multi_set_camera(jpt_multi *m, const void *camera160);
 int jpt_multi_accum_reset(jpt_multi *m);
 /* what crosses the links each render: 0 (default) the float4 accumulation rows (16 B per pixel; BASELINE.json's exchange),
@@ -957,6 +1006,17 @@ int jpt_debug_lens_rays(int device_id, const void *camera160, int32_t width, int
  * the functions the kernels inline, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
 int jpt_debug_camera_rays(int device_id, const void *camera160, int32_t width, int32_t height, uint32_t frame_index, int32_t model,
                           float *origins3_out, float *dirs3_out);
+/* The first rays of a bake render's paths (jpt_set_bake_texels) for every texel of frame frame_index of width x height images:
+ * origins3_out / dirs3_out [3 (y * width + x) ..] and valid_out[y * width + x] = 1, or zeros and 0 for an invalid texel.  The size is
+ * checked as jpt_set_bake_texels checks it; the texels are taken as they are.  device_id >= 0: the function the kernels inline, on that
+ * device; JPT_DEVICE_HOST_ONLY: the same function compiled for the host. */
+int jpt_debug_bake_rays(int device_id, const float *position4, const float *normal4, int32_t width, int32_t height,
+                        uint32_t frame_index, float *origins3_out, float *dirs3_out, uint8_t *valid_out);
+/* jpt_bake_add_surface on all-invalid width x height images, which it returns: the arguments are checked as that call checks them.
+ * device_id >= 0: the kernels the context runs, on that device; JPT_DEVICE_HOST_ONLY: a plain loop over texels and triangles calling
+ * the same coverage and resolve functions compiled for the host. */
+int jpt_debug_bake_raster(int device_id, const jpt_surface *surface, const float *uv2, const float *transform12,
+                          int32_t width, int32_t height, float *position4_out, float *normal4_out);
 /* The lens step alone, on the host, from caller-made randoms: for pinhole ray (origins3[3 i ..], dirs3[3 i ..]) and (xi2[2 i], xi2[2
  * i + 1]) the ray the lens of camera160 sends out (origins3_out, dirs3_out; either input ray kept when it does not point forward).
  * basis9_out (may be NULL): f, r, u.  The radius and the focus are taken as they are; a basis that is not finite is still returned,

@@ -821,6 +821,19 @@ class PathTracingCamera {
     // PROJECTION_FRUSTUM: pass get_camera_projection() as it is) or JPT_CAMERA_EQUIRECT (a 360-degree panorama in the environment
     // map's layout)
     void set_camera_model(int32_t model) { check(ctx, jpt_set_camera_model(ctx, model), "jpt_set_camera_model"); }
+    // Lightmap baking (LightmapGI): with texel images present every render is a bake render -- one path per texel, leaving the
+    // surface point the texel covers.  bake_begin + one bake_add_surface per surface (uv2 = Mesh::ARRAY_TEX_UV2, transform12 the
+    // instance's) rasterise the images on the device; set_bake_texels uploads images made elsewhere, (nullptr, nullptr, 0, 0) frees them.
+    void set_bake_texels(const float* position4, const float* normal4, int32_t w, int32_t h)
+    {
+        check(ctx, jpt_set_bake_texels(ctx, position4, normal4, w, h), "jpt_set_bake_texels");
+    }
+    void bake_begin(int32_t w, int32_t h) { check(ctx, jpt_bake_begin(ctx, w, h), "jpt_bake_begin"); }
+    void bake_add_surface(const jpt_surface& surface, const float* uv2, const float* transform12)
+    {
+        check(ctx, jpt_bake_add_surface(ctx, &surface, uv2, transform12), "jpt_bake_add_surface");
+    }
+    void read_bake_texels(float* position4, float* normal4) { check(ctx, jpt_read_bake_texels(ctx, position4, normal4), "jpt_read_bake_texels"); }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
