@@ -16,7 +16,7 @@
 
 namespace jpt {
 
-constexpr int32_t kCamPinhole = 0, kCamProjective = 1, kCamEquirect = 2;   // JPT_CAMERA_* of include/jpt.h (asserted in jpt_capi.cpp)
+constexpr int32_t kCamPinhole = 0, kCamProjective = 1, kCamEquirect = 2;   // JPT_CAMERA_* of include/jpt.h (asserted in jpt_primary.cpp)
 
 // The model of one render, passed by value to its bounce-0 launch: model 0 is the pinhole (nothing else is read then).
 struct CamModelDev {

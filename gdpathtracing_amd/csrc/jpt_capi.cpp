@@ -739,113 +739,8 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     return JPT_OK;
 }
 
-}  // namespace
-
-int jpt::check_lens(float aperture_radius, float focus_distance, std::string& why)
-{
-    if (!std::isfinite(aperture_radius) || aperture_radius < 0.0f) {
-        why = "jpt_set_lens: aperture_radius must be finite and >= 0";
-        return JPT_E_INVALID;
-    }
-    if (aperture_radius > 0.0f && (!std::isfinite(focus_distance) || !(focus_distance > 0.0f))) {
-        why = "jpt_set_lens: focus_distance must be finite and > 0";
-        return JPT_E_INVALID;
-    }
-    if (!std::isfinite(focus_distance) || focus_distance < 0.0f) {   // (not read with radius 0, but never kept as garbage)
-        why = "jpt_set_lens: focus_distance must be finite and > 0";
-        return JPT_E_INVALID;
-    }
-    return JPT_OK;
-}
-
-int jpt::resolve_lens(jpt_ctx* c, LensDev& out)
-{
-    out = LensDev{};
-    if (!(c->lens_radius > 0.0f) || c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the lens, as it ignores lighting)
-    if (c->denoise == JPT_DENOISE_TEMPORAL)
-        return fail(c, JPT_E_STATE, "temporal reprojection assumes one centre of projection: set the lens radius to 0 (jpt_set_lens) or another denoising mode");
-    out.radius = c->lens_radius;
-    out.focus = c->lens_focus;
-    if (!lens_basis(c->camera, out)) return fail(c, JPT_E_STATE, "jpt_set_lens: the camera basis derived from camera160 (ivp, position) is not finite");
-    return JPT_OK;
-}
-
-static_assert(JPT_CAMERA_PINHOLE == kCamPinhole && JPT_CAMERA_PROJECTIVE == kCamProjective && JPT_CAMERA_EQUIRECT == kCamEquirect,
-              "jpt_camera.h restates the enum of jpt.h");
-
-int jpt::make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out, std::string& why)
-{
-    out = CamModelDev{};
-    if (model != JPT_CAMERA_PINHOLE && model != JPT_CAMERA_PROJECTIVE && model != JPT_CAMERA_EQUIRECT) {
-        why = "jpt_set_camera_model: model must be JPT_CAMERA_PINHOLE, JPT_CAMERA_PROJECTIVE or JPT_CAMERA_EQUIRECT";
-        return JPT_E_INVALID;
-    }
-    if (model == JPT_CAMERA_EQUIRECT) {
-        LensDev basis;
-        if (!lens_basis(cam, basis)) {
-            why = "jpt_set_camera_model: the camera basis derived from camera160 (ivp, position) is not finite";
-            return JPT_E_STATE;
-        }
-        out.f = basis.f;
-        out.r = basis.r;
-        out.u = basis.u;
-    }
-    if (model == JPT_CAMERA_PROJECTIVE)
-        for (int k = 0; k < 16; k++)
-            if (!std::isfinite(cam.ivp[k])) {
-                why = "jpt_set_camera_model: the ivp of camera160 is not finite";
-                return JPT_E_STATE;
-            }
-    out.model = model;
-    return JPT_OK;
-}
-
-namespace {
-
-// The context's model seen through its camera as both are now: what the guides and jpt_query_pixels follow (no render's refusals
-// apply to them), and the last step of a render's resolution
-int camera_model_now(jpt_ctx* c, CamModelDev& out)
-{
-    std::string why;
-    const int rc = make_camera_model(c->camera_model, c->camera, out, why);
-    return rc == JPT_OK ? JPT_OK : fail(c, rc, why);
-}
-
-}  // namespace
-
-int jpt::resolve_camera_model(jpt_ctx* c, const LensDev& lens, CamModelDev& out)
-{
-    out = CamModelDev{};
-    if (c->camera_model == JPT_CAMERA_PINHOLE || c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the model, as it ignores the lens)
-    if (lens.radius > 0.0f)
-        return fail(c, JPT_E_STATE, "the lens disk is defined around one centre of projection: set the lens radius to 0 (jpt_set_lens) or JPT_CAMERA_PINHOLE (jpt_set_camera_model)");
-    if (c->denoise == JPT_DENOISE_TEMPORAL)
-        return fail(c, JPT_E_STATE, "temporal reprojection assumes the pinhole: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or another denoising mode");
-    return camera_model_now(c, out);
-}
-
-int jpt::resolve_bake(jpt_ctx* c, BakeDev& out)
-{
-    out = BakeDev{};
-    if (!c->d_bake_nrm.p || c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the images, as it ignores the lens)
-    if (c->bake_w != c->width || c->bake_h != c->height)
-        return fail(c, JPT_E_STATE, "the bake images are " + std::to_string(c->bake_w) + " x " + std::to_string(c->bake_h) + " texels but jpt_set_params says " +
-                                        std::to_string(c->width) + " x " + std::to_string(c->height) + ": a bake render has one path per texel (jpt_set_bake_texels)");
-    if (c->lens_radius > 0.0f)
-        return fail(c, JPT_E_STATE, "a bake render has no lens: set the lens radius to 0 (jpt_set_lens) or free the bake images (jpt_set_bake_texels)");
-    if (c->camera_model != JPT_CAMERA_PINHOLE)
-        return fail(c, JPT_E_STATE, "a bake render has no camera model: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or free the bake images (jpt_set_bake_texels)");
-    if (c->denoise == JPT_DENOISE_TEMPORAL)
-        return fail(c, JPT_E_STATE, "temporal reprojection assumes a camera: set another denoising mode or free the bake images (jpt_set_bake_texels)");
-    out.position = c->d_bake_pos.p;
-    out.normal = c->d_bake_nrm.p;
-    return JPT_OK;
-}
-
-namespace {
-
 // What a render needs before it is planned: the temporal pass's history, zeroed counters, the workspace of the context's
-// stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.  r.lighting is the render's.
+// stream, the timing events, and (wavefront renders) the sky cull and the tiles' sky cells in r.  r.lighting and r.primary are the render's.
 int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefront, Wf2Render& r)
 {
     hipStream_t s = c->stream;
@@ -889,13 +784,7 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
         c->trace_events.push_back(e);
     }
     c->trace_events_used = (int32_t)need_ev;
-    // (a lens render has no sky cull and no sky cells: a pixel outside every box's screen rectangle may still see geometry from a
-    // point of the aperture -- r.cull stays off, n < 0, and r.sky_tiles null)
-    if (r.lens.radius > 0.0f) return JPT_OK;
-    // (nor has a render under another camera model: the rectangles are the pinhole's projection of the boxes)
-    if (r.cam_model.model != kCamPinhole) return JPT_OK;
-    // (nor has a bake render: its paths start on the surfaces)
-    if (r.bake.normal != nullptr) return JPT_OK;
+    if (!r.primary.sky_cull()) return JPT_OK;   // (r.cull stays off, n < 0, and r.sky_tiles null)
     compute_sky_cull(c, r.cull);
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
@@ -934,7 +823,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.lens, r.cam_model, r.bake);
+            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.primary);
         }
         return JPT_OK;
     }
@@ -1042,9 +931,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
     const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
     Wf2Render r;
-    if ((rc = resolve_bake(c, r.bake)) != JPT_OK) return rc;
-    if ((rc = resolve_lens(c, r.lens)) != JPT_OK) return rc;
-    if ((rc = resolve_camera_model(c, r.lens, r.cam_model)) != JPT_OK) return rc;
+    if ((rc = resolve_primary(c, r.primary)) != JPT_OK) return rc;
     if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
@@ -1090,20 +977,6 @@ void scatter_rows(const std::vector<T>& local, T* out, int32_t width, int32_t he
     scatter_rows(local.data(), out, width, height, rank, world, comps);
 }
 
-// Blocking read-backs (jpt_read_ldr_rgba8 / accum_f32 / depth_f32): device -> the context's pinned read buffer -> the caller's
-// memory.  A device-to-host copy straight into pageable memory runs at ~3 GB/s (8 MB of display image: 2.7 ms; 33 MB of float4
-// sums: 11 ms); through pinned memory the copy runs at the link's rate and the host copy at memory speed.  (A buffer of its
-// own: the split read-back's staging buffer may hold an image in flight.)
-int staged_read(jpt_ctx* c, const void* src, size_t bytes)
-{
-    HIP_TRY(c, c->h_read_pinned.reserve(bytes));
-    if (bytes) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_read_pinned.p, src, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return JPT_OK;
-}
-
 // the pinned staging buffer of the display image's split read-backs (one full image)
 int ensure_ldr_pinned(jpt_ctx* c)
 {
@@ -1135,6 +1008,20 @@ void release_streams(jpt_ctx* c)
 }
 
 }  // namespace
+
+// Blocking read-backs (jpt_read_ldr_rgba8 / accum_f32 / depth_f32): device -> the context's pinned read buffer -> the caller's
+// memory.  A device-to-host copy straight into pageable memory runs at ~3 GB/s (8 MB of display image: 2.7 ms; 33 MB of float4
+// sums: 11 ms); through pinned memory the copy runs at the link's rate and the host copy at memory speed.  (A buffer of its
+// own: the split read-back's staging buffer may hold an image in flight.)
+int jpt::staged_read(jpt_ctx* c, const void* src, size_t bytes)
+{
+    HIP_TRY(c, c->h_read_pinned.reserve(bytes));
+    if (bytes) {
+        HIP_TRY(c, hipMemcpyAsync(c->h_read_pinned.p, src, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return JPT_OK;
+}
 
 extern "C" {
 
@@ -2072,158 +1959,6 @@ int jpt_set_kernel(jpt_ctx* c, int32_t variant)
     return JPT_OK;
 }
 
-int jpt_set_lens(jpt_ctx* c, float aperture_radius, float focus_distance)
-{
-    if (!c) return JPT_E_INVALID;
-    std::string why;
-    const int rc = check_lens(aperture_radius, focus_distance, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the lens is a property of device renders");
-    c->lens_radius = aperture_radius;   // (each render takes them by value: resolve_lens)
-    c->lens_focus = focus_distance;
-    return JPT_OK;
-}
-
-int jpt_set_camera_model(jpt_ctx* c, int32_t model)
-{
-    if (!c) return JPT_E_INVALID;
-    if (model != JPT_CAMERA_PINHOLE && model != JPT_CAMERA_PROJECTIVE && model != JPT_CAMERA_EQUIRECT)
-        return fail(c, JPT_E_INVALID, "jpt_set_camera_model: model must be JPT_CAMERA_PINHOLE, JPT_CAMERA_PROJECTIVE or JPT_CAMERA_EQUIRECT");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the camera model is a property of device renders");
-    c->camera_model = model;   // (each render takes it by value: resolve_camera_model)
-    return JPT_OK;
-}
-
-// ---- lightmap baking: the context's texel images (jpt_bake.h) -------------------------------------------------------------------
-
-// the renders already queued read the old images: they finish first (every one of them ends with work on the context's stream)
-static int bake_wait(jpt_ctx* c)
-{
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return JPT_OK;
-}
-
-static void bake_release(jpt_ctx* c)
-{
-    c->d_bake_pos.release();
-    c->d_bake_nrm.release();
-    c->d_bake_winner.release();
-    c->d_bake_in.release();
-    c->bake_w = c->bake_h = 0;
-}
-
-static int bake_alloc(jpt_ctx* c, int32_t width, int32_t height)
-{
-    const size_t n = (size_t)width * (size_t)height;
-    hipError_t e = c->d_bake_pos.resize(n);
-    if (e == hipSuccess) e = c->d_bake_nrm.resize(n);
-    if (e != hipSuccess) {
-        bake_release(c);
-        return hip_fail(c, e, "hipMalloc of the bake images");
-    }
-    c->bake_w = width;
-    c->bake_h = height;
-    return JPT_OK;
-}
-
-int jpt_set_bake_texels(jpt_ctx* c, const float* position4, const float* normal4, int32_t width, int32_t height)
-{
-    if (!c) return JPT_E_INVALID;
-    const bool freeing = !position4 && !normal4 && width == 0 && height == 0;
-    if (!freeing) {
-        if (!position4 || !normal4) return fail(c, JPT_E_INVALID, "jpt_set_bake_texels: position4 and normal4 are both given, or (NULL, NULL, 0, 0) frees the images");
-        std::string why;
-        int rc = check_bake_size("jpt_set_bake_texels", width, height, why);
-        if (rc == JPT_OK) rc = check_bake_texels("jpt_set_bake_texels", position4, normal4, (size_t)width * (size_t)height, why);
-        if (rc != JPT_OK) return fail(c, rc, why);
-    }
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_texels: host-only context has no bake images");
-    int rc = bake_wait(c);
-    if (rc != JPT_OK) return rc;
-    if (freeing) {
-        bake_release(c);
-        return JPT_OK;
-    }
-    if ((rc = bake_alloc(c, width, height)) != JPT_OK) return rc;
-    const size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
-    HIP_TRY(c, hipMemcpy(c->d_bake_pos.p, position4, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_bake_nrm.p, normal4, bytes, hipMemcpyHostToDevice));
-    return JPT_OK;
-}
-
-int jpt_bake_begin(jpt_ctx* c, int32_t width, int32_t height)
-{
-    if (!c) return JPT_E_INVALID;
-    std::string why;
-    int rc = check_bake_size("jpt_bake_begin", width, height, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_begin: host-only context has no bake images");
-    if ((rc = bake_wait(c)) != JPT_OK) return rc;
-    if ((rc = bake_alloc(c, width, height)) != JPT_OK) return rc;
-    const size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
-    HIP_TRY(c, hipMemsetAsync(c->d_bake_pos.p, 0, bytes, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_bake_nrm.p, 0, bytes, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return JPT_OK;
-}
-
-int jpt_bake_add_surface(jpt_ctx* c, const jpt_surface* surface, const float* uv2, const float* transform12)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!surface) return fail(c, JPT_E_INVALID, "jpt_bake_add_surface: null surface");
-    std::string why;
-    int rc = check_bake_surface("jpt_bake_add_surface", surface->vertices, surface->normals, surface->indices, surface->n_vertices, surface->n_indices, uv2,
-                                transform12, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_add_surface: host-only context has no bake images");
-    if (!c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_bake_add_surface: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
-    if ((rc = bake_wait(c)) != JPT_OK) return rc;
-    const uint32_t n_tris = (uint32_t)(surface->n_indices / 3);
-    if (n_tris == 0) return JPT_OK;
-    // the surface staged in one device buffer: vertices, normals, uv2, indices (each a multiple of 4 bytes)
-    const size_t nv = (size_t)surface->n_vertices;
-    const size_t b_v = nv * 3 * sizeof(float), b_uv = nv * 2 * sizeof(float), b_i = (size_t)n_tris * 3 * sizeof(int32_t);
-    const size_t need = 2 * b_v + b_uv + b_i;
-    if (c->d_bake_in.n < need) HIP_TRY(c, c->d_bake_in.resize(need));
-    const size_t npx = (size_t)c->bake_w * (size_t)c->bake_h;
-    if (c->d_bake_winner.n < npx) HIP_TRY(c, c->d_bake_winner.resize(npx));
-    char* base = c->d_bake_in.p;
-    HIP_TRY(c, hipMemcpy(base, surface->vertices, b_v, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(base + b_v, surface->normals, b_v, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(base + 2 * b_v, uv2, b_uv, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(base + 2 * b_v + b_uv, surface->indices, b_i, hipMemcpyHostToDevice));
-    BakeSurfaceDev sd;
-    sd.vertices = reinterpret_cast<const float*>(base);
-    sd.normals = reinterpret_cast<const float*>(base + b_v);
-    sd.uv2 = reinterpret_cast<const float*>(base + 2 * b_v);
-    sd.indices = reinterpret_cast<const int32_t*>(base + 2 * b_v + b_uv);
-    sd.n_tris = n_tris;
-    transform12_to_mat16(transform12, sd.transform);
-    launch_bake_raster(c->stream, sd, c->bake_w, c->bake_h, c->d_bake_winner.p, c->d_bake_pos.p, c->d_bake_nrm.p);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return JPT_OK;
-}
-
-int jpt_read_bake_texels(jpt_ctx* c, float* position4, float* normal4)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_bake_texels: host-only context has no bake images");
-    if (!c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_read_bake_texels: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->bake_w * (size_t)c->bake_h * sizeof(float4);
-    float* const out[2] = {position4, normal4};
-    const float4* const src[2] = {c->d_bake_pos.p, c->d_bake_nrm.p};
-    for (int k = 0; k < 2; k++) {
-        if (!out[k]) continue;
-        const int rc = staged_read(c, src[k], bytes);
-        if (rc != JPT_OK) return rc;
-        std::memcpy(out[k], c->h_read_pinned.p, bytes);
-    }
-    return JPT_OK;
-}
-
 int jpt_set_debug_steps(jpt_ctx* c, int32_t enable)
 {
     if (!c) return JPT_E_INVALID;
@@ -2425,9 +2160,8 @@ int jpt_denoise(jpt_ctx* c)
     if (!c->scene_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
     if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_denoise: jpt_set_params / jpt_set_camera not called");
     if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_denoise: no frame accumulated since the last reset");
-    if (c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_denoise: the guides are camera rays, and the context holds bake images (jpt_set_bake_texels)");
     CamModelDev cm;   // (the guides are the first hits of the view the renders took: jpt_set_camera_model)
-    const int rc_cm = camera_model_now(c, cm);
+    const int rc_cm = view_now(c, "jpt_denoise", "the guides", cm);
     if (rc_cm != JPT_OK) return rc_cm;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->width * c->height;
@@ -2700,9 +2434,9 @@ static int query_state(jpt_ctx* c, const char* what)
     return JPT_OK;
 }
 
-// One chunk of a host form: `m` rays (or, pixels: raster positions) from `in` up, the walk, the results back into hits / occluded
+// One chunk of a host form: `m` rays (or, pixels: raster positions seen through that model) from `in` up, the walk, the results back into hits / occluded
 // (either may be null).  Device layout of d_query: [rays 32 B][hits 64 B][bytes 1 B] per ray of a chunk, each part 16-byte aligned.
-static int query_chunk(jpt_ctx* c, bool any, bool pixels, const void* in, uint32_t m, jpt_ray_hit* hits, uint8_t* occluded)
+static int query_chunk(jpt_ctx* c, bool any, const CamModelDev* pixels, const void* in, uint32_t m, jpt_ray_hit* hits, uint8_t* occluded)
 {
     const size_t cap = c->d_query.n / 97;
     char* d_rays = c->d_query.p;
@@ -2713,10 +2447,7 @@ static int query_chunk(jpt_ctx* c, bool any, bool pixels, const void* in, uint32
     if (pixels) {   // 8 B per ray go up, into the hits' part; the rays are made from them in place on the device
         std::memcpy(h, in, (size_t)m * 2 * sizeof(float));
         HIP_TRY(c, hipMemcpyAsync(d_hits, h, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, s));
-        CamModelDev cm;   // (jpt_set_camera_model: picking follows the model)
-        const int rc_cm = camera_model_now(c, cm);
-        if (rc_cm != JPT_OK) return rc_cm;
-        launch_query_pixel_rays(s, c->camera, cm, c->width, c->height, d_hits, m, d_rays);
+        launch_query_pixel_rays(s, c->camera, *pixels, c->width, c->height, d_hits, m, d_rays);
     } else {
         std::memcpy(h, in, (size_t)m * sizeof(jpt_ray));
         HIP_TRY(c, hipMemcpyAsync(d_rays, h, (size_t)m * sizeof(jpt_ray), hipMemcpyHostToDevice, s));
@@ -2732,7 +2463,7 @@ static int query_chunk(jpt_ctx* c, bool any, bool pixels, const void* in, uint32
     return JPT_OK;
 }
 
-static int query_host(jpt_ctx* c, bool any, bool pixels, const void* in, uint32_t n, jpt_ray_hit* hits, uint8_t* occluded)
+static int query_host(jpt_ctx* c, bool any, const CamModelDev* pixels, const void* in, uint32_t n, jpt_ray_hit* hits, uint8_t* occluded)
 {
     const size_t cap = ((size_t)(n < kQueryChunk ? n : kQueryChunk) + 15) & ~(size_t)15;
     if (c->d_query.n < cap * 97) HIP_TRY(c, c->d_query.resize(cap * 97));
@@ -2753,7 +2484,7 @@ int jpt_query_rays(jpt_ctx* c, int32_t mode, const jpt_ray* rays, uint32_t n, jp
     int rc = query_checks(c, mode, rays, n, hits_out, occluded_out, "jpt_query_rays", done);
     if (rc != JPT_OK || done) return rc;
     if ((rc = query_state(c, "jpt_query_rays")) != JPT_OK) return rc;
-    return query_host(c, mode == JPT_QUERY_ANY, false, rays, n, hits_out, occluded_out);
+    return query_host(c, mode == JPT_QUERY_ANY, nullptr, rays, n, hits_out, occluded_out);
 }
 
 int jpt_query_rays_device(jpt_ctx* c, int32_t mode, const void* d_rays, uint32_t n, void* d_hits_out, void* d_occluded_out)
@@ -2785,8 +2516,9 @@ int jpt_query_pixels(jpt_ctx* c, const float* xy, uint32_t n, jpt_ray_hit* hits_
     if (rc != JPT_OK || done) return rc;
     if ((rc = query_state(c, "jpt_query_pixels")) != JPT_OK) return rc;
     if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_query_pixels: jpt_set_params / jpt_set_camera not called");
-    if (c->d_bake_nrm.p) return fail(c, JPT_E_STATE, "jpt_query_pixels: picking rays are camera rays, and the context holds bake images (jpt_set_bake_texels)");
-    return query_host(c, false, true, xy, n, hits_out, nullptr);
+    CamModelDev cm;   // (jpt_set_camera_model: picking follows the model)
+    if ((rc = view_now(c, "jpt_query_pixels", "picking rays", cm)) != JPT_OK) return rc;
+    return query_host(c, false, &cm, xy, n, hits_out, nullptr);
 }
 
 int jpt_read_depth_f32(jpt_ctx* c, float* out)

@@ -1,5 +1,5 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_lighting.cpp).
+// (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp).
 #pragma once
 #include "../../include/jpt.h"
 #include "jpt_builder.h"
@@ -166,16 +166,32 @@ void lights_stale(jpt_ctx* c, bool listed);
 Lighting lighting_bound(const jpt_ctx* c);
 // The lighting of one render of `c`, once it is validated; makes the emitter tables on the context's stream when they are stale.
 int resolve_lighting(jpt_ctx* c, Lighting& out);
-// The lens of one render of `c` (jpt_set_lens; jpt_capi.cpp): radius 0 without one or with DEBUG_STEPS, else the basis derived from
-// the camera as it is now.  JPT_E_STATE: the basis is not finite, or the temporal pass is on.
-int resolve_lens(jpt_ctx* c, LensDev& out);
-// The camera model of one render of `c` (jpt_set_camera_model; jpt_capi.cpp), after its lens: the pinhole without one or with
-// DEBUG_STEPS, else the model with the basis derived from the camera as it is now.  JPT_E_STATE: a lens radius > 0 or the temporal
-// pass with a model other than the pinhole, EQUIRECT's basis or PROJECTIVE's ivp not finite.
-int resolve_camera_model(jpt_ctx* c, const LensDev& lens, CamModelDev& out);
-// The texel images of one render of `c` (jpt_set_bake_texels; jpt_capi.cpp), before its lens: null without images or with
-// DEBUG_STEPS.  JPT_E_STATE: the images' size is not the render's, a lens radius > 0, a model other than the pinhole, the temporal pass.
-int resolve_bake(jpt_ctx* c, BakeDev& out);
+
+// What the context holds of where its renders' paths start: written by the setters, read by resolve_primary and view_now (all in
+// jpt_primary.cpp), which turn it into the one value the renders take (PrimaryRays, jpt_kernels.h)
+struct PrimaryState {
+    float lens_radius = 0.0f, lens_focus = 1.0f;   // jpt_set_lens: the context's, like the sampling modes; radius 0 is the pinhole
+    int32_t camera_model = JPT_CAMERA_PINHOLE;     // jpt_set_camera_model: the context's, like the lens
+    // jpt_set_bake_texels / jpt_bake_begin: the context's, like the environment map; present images make every render a bake render.
+    // The rasteriser's winner image and staged surface (jpt_bake_add_surface) are grow-only
+    DevBuf<float4> d_bake_pos, d_bake_nrm;
+    int32_t bake_w = 0, bake_h = 0;
+    DevBuf<uint32_t> d_bake_winner;
+    DevBuf<char> d_bake_in;
+    bool has_bake() const { return d_bake_nrm.p != nullptr; }
+};
+// Where the paths of one render of `c` start, once it is validated: the one of the four sources the context's state names, with the
+// others zeroed; kPinhole with DEBUG_STEPS, which ignores the lens, the model and the images as it ignores lighting.  In this order --
+// bake images: JPT_E_STATE when their size is not the render's, with a lens radius > 0, a model other than the pinhole or the
+// temporal pass; a lens radius > 0: JPT_E_STATE with the temporal pass, a basis that is not finite or a model other than the
+// pinhole; a model other than the pinhole: JPT_E_STATE with the temporal pass, EQUIRECT's basis or PROJECTIVE's ivp not finite.
+int resolve_primary(jpt_ctx* c, PrimaryRays& out);
+// The view of an entry point that takes it without rendering (`call`: jpt_denoise's guides, jpt_query_pixels' picking rays): the
+// context's model seen through its camera as both are now -- no render's refusals apply.  JPT_E_STATE while the context holds bake
+// images (`rays`: what the call's rays are, for the message).
+int view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& out);
+// Blocking read-backs: device -> the context's pinned read buffer (h_read_pinned), on the context's stream (jpt_capi.cpp)
+int staged_read(jpt_ctx* c, const void* src, size_t bytes);
 
 }  // namespace jpt
 
@@ -217,14 +233,6 @@ struct jpt_ctx {
     RefCamera camera;
     uint32_t frame_count = 0;  // frames accumulated since reset
     int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
-    int32_t camera_model = JPT_CAMERA_PINHOLE;   // jpt_set_camera_model: the context's, like the lens; each render takes it by value
-    // jpt_set_bake_texels / jpt_bake_begin: the context's, like the environment map; present images make every render a bake render.
-    // The rasteriser's winner image and staged surface (jpt_bake_add_surface) are grow-only
-    DevBuf<float4> d_bake_pos, d_bake_nrm;
-    int32_t bake_w = 0, bake_h = 0;
-    DevBuf<uint32_t> d_bake_winner;
-    DevBuf<char> d_bake_in;
-    float lens_radius = 0.0f, lens_focus = 1.0f;   // jpt_set_lens: the context's, like the sampling modes; radius 0 is the pinhole
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
     bool depth_valid = false;              // d_depth holds the last render's depth image
@@ -306,6 +314,7 @@ struct jpt_ctx {
     bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
 
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
+    PrimaryState primary;     // the lens, the camera model and the bake images (jpt_primary.cpp)
 
     // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
     // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution

@@ -20,6 +20,7 @@
 #include "jpt_instance_math.h"
 #include "jpt_kernels.h"
 #include "jpt_nodeq.h"
+#include "jpt_primary_ray.h"
 #include "jpt_trace_core.h"
 
 using namespace jpt;
@@ -139,40 +140,22 @@ __global__ void dielectric_probe(const float* __restrict__ normals3, const float
     event_out[i] = (uint8_t)ev;
 }
 
-// jpt_debug_lens_rays: the ray generation of a lens render (primary_ray, then lens_ray unless the radius is 0), one pixel per thread
-__global__ void lens_rays_probe(RefCamera cam, int width, int height, uint32_t frame, LensDev lens, float* __restrict__ origins_out,
-                                float* __restrict__ dirs_out)
+// jpt_debug_lens_rays / _camera_rays / _bake_rays: the first rays of a render under `p` (first_ray, jpt_primary_ray.h), one pixel per
+// thread; `valid` may be null
+__global__ void primary_rays_probe(PrimaryRays p, RefCamera cam, int width, int height, uint32_t frame, float* __restrict__ origins_out,
+                                   float* __restrict__ dirs_out, uint8_t* __restrict__ valid)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (uint32_t)width * (uint32_t)height) return;
-    const int px = (int)(i % (uint32_t)width), py = (int)(i / (uint32_t)width);
-    uint32_t sx, sy;
-    Ray ray = primary_ray(cam, width, height, px, py, frame, sx, sy);
-    if (lens.radius > 0.0f) lens_ray(lens, sx, sy, ray);
+    Ray ray;
+    const bool ok = first_ray(p, cam, width, height, (int)(i % (uint32_t)width), (int)(i / (uint32_t)width), frame, ray);
     origins_out[3 * (size_t)i] = ray.o.x;
     origins_out[3 * (size_t)i + 1] = ray.o.y;
     origins_out[3 * (size_t)i + 2] = ray.o.z;
     dirs_out[3 * (size_t)i] = ray.d.x;
     dirs_out[3 * (size_t)i + 1] = ray.d.y;
     dirs_out[3 * (size_t)i + 2] = ray.d.z;
-}
-
-// jpt_debug_camera_rays: the ray generation of a render under a camera model (primary_ray for the pinhole, else camera_ray), one
-// pixel per thread
-__global__ void camera_rays_probe(RefCamera cam, int width, int height, uint32_t frame, CamModelDev cm, float* __restrict__ origins_out,
-                                  float* __restrict__ dirs_out)
-{
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (uint32_t)width * (uint32_t)height) return;
-    const int px = (int)(i % (uint32_t)width), py = (int)(i / (uint32_t)width);
-    uint32_t sx, sy;
-    const Ray ray = cm.model != kCamPinhole ? camera_ray(cam, cm, width, height, px, py, frame, sx, sy) : primary_ray(cam, width, height, px, py, frame, sx, sy);
-    origins_out[3 * (size_t)i] = ray.o.x;
-    origins_out[3 * (size_t)i + 1] = ray.o.y;
-    origins_out[3 * (size_t)i + 2] = ray.o.z;
-    dirs_out[3 * (size_t)i] = ray.d.x;
-    dirs_out[3 * (size_t)i + 1] = ray.d.y;
-    dirs_out[3 * (size_t)i + 2] = ray.d.z;
+    if (valid) valid[i] = ok ? 1 : 0;
 }
 
 }  // namespace
@@ -325,6 +308,56 @@ int env_sampling_debug(int device_id, const float* rgb, int32_t width, int32_t h
     if (rc == JPT_OK && n && what && (e = hipMemcpy(pdf_out, d_pdf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     for (void* p : {(void*)d_tex, (void*)d_cond, (void*)d_marg, (void*)d_in, (void*)d_dirs, (void*)d_pdf})
         if (p) (void)hipFree(p);
+    return rc;
+}
+
+// The first rays of one frame under `p`, every pixel in raster order: the host loop with JPT_DEVICE_HOST_ONLY, else primary_rays_probe
+// on `device_id` -- one allocation for the bake images (host memory in `p`, uploaded here), the origins, the directions and the
+// valid bytes (valid_out may be null).  `what` names the probe in a device error.
+int primary_rays_debug(int device_id, const char* what, PrimaryRays p, const RefCamera& cam, int32_t width, int32_t height, uint32_t frame,
+                       float* origins3_out, float* dirs3_out, uint8_t* valid_out)
+{
+    const size_t n = (size_t)width * (size_t)height;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        for (size_t i = 0; i < n; i++) {
+            Ray ray;
+            const bool ok = first_ray(p, cam, width, height, (int)(i % (size_t)width), (int)(i / (size_t)width), frame, ray);
+            origins3_out[3 * i] = ray.o.x;
+            origins3_out[3 * i + 1] = ray.o.y;
+            origins3_out[3 * i + 2] = ray.o.z;
+            dirs3_out[3 * i] = ray.d.x;
+            dirs3_out[3 * i + 1] = ray.d.y;
+            dirs3_out[3 * i + 2] = ray.d.z;
+            if (valid_out) valid_out[i] = ok ? 1 : 0;
+        }
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t b_img = p.kind == PrimaryRays::kBake ? n * sizeof(float4) : 0, b_ray = n * 3u * sizeof(float);
+    char* d_all = nullptr;   // position4, normal4 (16-byte images first), origins, directions, valid
+    if ((e = hipMalloc((void**)&d_all, 2 * b_img + 2 * b_ray + (valid_out ? n : 0))) != hipSuccess) return hip_fail(e, "hipMalloc");
+    float *d_o = reinterpret_cast<float*>(d_all + 2 * b_img), *d_d = reinterpret_cast<float*>(d_all + 2 * b_img + b_ray);
+    uint8_t* d_valid = valid_out ? reinterpret_cast<uint8_t*>(d_all + 2 * b_img + 2 * b_ray) : nullptr;
+    int rc = JPT_OK;
+    if (b_img) {
+        if ((e = hipMemcpy(d_all, p.bake.position, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+        if (rc == JPT_OK && (e = hipMemcpy(d_all + b_img, p.bake.normal, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+        p.bake.position = reinterpret_cast<const float4*>(d_all);
+        p.bake.normal = reinterpret_cast<const float4*>(d_all + b_img);
+    }
+    if (rc == JPT_OK) {
+        hipLaunchKernelGGL(primary_rays_probe, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, p, cam, width, height, frame, d_o, d_d, d_valid);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, what);
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_o, b_ray, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_d, b_ray, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && valid_out && (e = hipMemcpy(valid_out, d_valid, n, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
     return rc;
 }
 
@@ -516,47 +549,17 @@ int jpt_debug_lens_rays(int device_id, const void* camera160, int32_t width, int
     if (rc0 != JPT_OK) return rc0;
     RefCamera cam;
     std::memcpy(&cam, camera160, sizeof cam);
-    LensDev lens;
+    PrimaryRays p;
     if (aperture_radius > 0.0f) {
-        lens.radius = aperture_radius;
-        lens.focus = focus_distance;
-        if (!lens_basis(cam, lens)) {
+        p.kind = PrimaryRays::kLens;
+        p.lens.radius = aperture_radius;
+        p.lens.focus = focus_distance;
+        if (!lens_basis(cam, p.lens)) {
             g_debug_error = "the camera basis derived from camera160 is not finite";
             return JPT_E_STATE;
         }
     }
-    const size_t n = (size_t)width * (size_t)height;
-    if (device_id == JPT_DEVICE_HOST_ONLY) {
-        for (size_t i = 0; i < n; i++) {
-            uint32_t sx, sy;
-            Ray ray = primary_ray(cam, width, height, (int)(i % (size_t)width), (int)(i / (size_t)width), frame_index, sx, sy);
-            if (lens.radius > 0.0f) lens_ray(lens, sx, sy, ray);
-            origins3_out[3 * i] = ray.o.x;
-            origins3_out[3 * i + 1] = ray.o.y;
-            origins3_out[3 * i + 2] = ray.o.z;
-            dirs3_out[3 * i] = ray.d.x;
-            dirs3_out[3 * i + 1] = ray.d.y;
-            dirs3_out[3 * i + 2] = ray.d.z;
-        }
-        return JPT_OK;
-    }
-    auto hip_fail = [](hipError_t e, const char* what) {
-        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
-        return JPT_E_DEVICE;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t bytes = n * 3u * sizeof(float);
-    float* d_all = nullptr;   // origins, then directions
-    if ((e = hipMalloc((void**)&d_all, 2 * bytes)) != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = JPT_OK;
-    hipLaunchKernelGGL(lens_rays_probe, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, cam, width, height, frame_index, lens, d_all,
-                       d_all + n * 3u);
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "lens_rays_probe");
-    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + n * 3u, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    (void)hipFree(d_all);
-    return rc;
+    return primary_rays_debug(device_id, "lens_rays_probe", p, cam, width, height, frame_index, origins3_out, dirs3_out, nullptr);
 }
 
 int jpt_debug_camera_rays(int device_id, const void* camera160, int32_t width, int32_t height, uint32_t frame_index, int32_t model,
@@ -572,42 +575,11 @@ int jpt_debug_camera_rays(int device_id, const void* camera160, int32_t width, i
     }
     RefCamera cam;
     std::memcpy(&cam, camera160, sizeof cam);
-    CamModelDev cm;
-    const int rc0 = make_camera_model(model, cam, cm, g_debug_error);
+    PrimaryRays p;
+    const int rc0 = make_camera_model(model, cam, p.cam_model, g_debug_error);
     if (rc0 != JPT_OK) return rc0;
-    const size_t n = (size_t)width * (size_t)height;
-    if (device_id == JPT_DEVICE_HOST_ONLY) {
-        for (size_t i = 0; i < n; i++) {
-            const int px = (int)(i % (size_t)width), py = (int)(i / (size_t)width);
-            uint32_t sx, sy;
-            const Ray ray = cm.model != kCamPinhole ? camera_ray(cam, cm, width, height, px, py, frame_index, sx, sy)
-                                                    : primary_ray(cam, width, height, px, py, frame_index, sx, sy);
-            origins3_out[3 * i] = ray.o.x;
-            origins3_out[3 * i + 1] = ray.o.y;
-            origins3_out[3 * i + 2] = ray.o.z;
-            dirs3_out[3 * i] = ray.d.x;
-            dirs3_out[3 * i + 1] = ray.d.y;
-            dirs3_out[3 * i + 2] = ray.d.z;
-        }
-        return JPT_OK;
-    }
-    auto hip_fail = [](hipError_t e, const char* what) {
-        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
-        return JPT_E_DEVICE;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t bytes = n * 3u * sizeof(float);
-    float* d_all = nullptr;   // origins, then directions
-    if ((e = hipMalloc((void**)&d_all, 2 * bytes)) != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = JPT_OK;
-    hipLaunchKernelGGL(camera_rays_probe, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, nullptr, cam, width, height, frame_index, cm, d_all,
-                       d_all + n * 3u);
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "camera_rays_probe");
-    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + n * 3u, bytes, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    (void)hipFree(d_all);
-    return rc;
+    if (p.cam_model.model != kCamPinhole) p.kind = PrimaryRays::kCamModel;
+    return primary_rays_debug(device_id, "camera_rays_probe", p, cam, width, height, frame_index, origins3_out, dirs3_out, nullptr);
 }
 
 int jpt_debug_bake_rays(int device_id, const float* position4, const float* normal4, int32_t width, int32_t height, uint32_t frame_index,
@@ -619,37 +591,11 @@ int jpt_debug_bake_rays(int device_id, const float* position4, const float* norm
     }
     const int rc0 = check_bake_size("jpt_debug_bake_rays", width, height, g_debug_error);
     if (rc0 != JPT_OK) return rc0;
-    const size_t n = (size_t)width * (size_t)height;
-    if (device_id == JPT_DEVICE_HOST_ONLY) {
-        bake_rays_host(reinterpret_cast<const float4*>(position4), reinterpret_cast<const float4*>(normal4), width, height, frame_index, origins3_out,
-                       dirs3_out, valid_out);
-        return JPT_OK;
-    }
-    auto hip_fail = [](hipError_t e, const char* what) {
-        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
-        return JPT_E_DEVICE;
-    };
-    hipError_t e;
-    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
-    const size_t b_img = n * sizeof(float4), b_ray = n * 3u * sizeof(float);
-    char* d_all = nullptr;   // position4, normal4, origins, directions, valid
-    if ((e = hipMalloc((void**)&d_all, 2 * b_img + 2 * b_ray + n)) != hipSuccess) return hip_fail(e, "hipMalloc");
-    int rc = JPT_OK;
-    if ((e = hipMemcpy(d_all, position4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    if (rc == JPT_OK && (e = hipMemcpy(d_all + b_img, normal4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    if (rc == JPT_OK) {
-        BakeDev bake;
-        bake.position = reinterpret_cast<const float4*>(d_all);
-        bake.normal = reinterpret_cast<const float4*>(d_all + b_img);
-        launch_bake_rays_probe(nullptr, bake, width, height, frame_index, reinterpret_cast<float*>(d_all + 2 * b_img),
-                               reinterpret_cast<float*>(d_all + 2 * b_img + b_ray), reinterpret_cast<uint8_t*>(d_all + 2 * b_img + 2 * b_ray));
-        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "bake_rays_probe");
-    }
-    if (rc == JPT_OK && (e = hipMemcpy(origins3_out, d_all + 2 * b_img, b_ray, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    if (rc == JPT_OK && (e = hipMemcpy(dirs3_out, d_all + 2 * b_img + b_ray, b_ray, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    if (rc == JPT_OK && (e = hipMemcpy(valid_out, d_all + 2 * b_img + 2 * b_ray, n, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
-    (void)hipFree(d_all);
-    return rc;
+    PrimaryRays p;   // (the images are host memory here: primary_rays_debug uploads them for a device)
+    p.kind = PrimaryRays::kBake;
+    p.bake.position = reinterpret_cast<const float4*>(position4);
+    p.bake.normal = reinterpret_cast<const float4*>(normal4);
+    return primary_rays_debug(device_id, "bake_rays_probe", p, RefCamera{}, width, height, frame_index, origins3_out, dirs3_out, valid_out);
 }
 
 int jpt_debug_bake_raster(int device_id, const jpt_surface* surface, const float* uv2, const float* transform12, int32_t width, int32_t height,

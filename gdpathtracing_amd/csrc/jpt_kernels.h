@@ -1,4 +1,5 @@
-// jpt_kernels.h -- what the host layer (jpt_capi.cpp, jpt_lighting.cpp) sees of the device code.
+// jpt_kernels.h -- what the host layer (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp) sees of the device code, and the two values a
+// render's launches read: its Lighting and its PrimaryRays.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -203,9 +204,9 @@ __device__ __forceinline__ void count_walk(DevCounters& c, uint32_t steps)
 int check_env_map(const float* rgb, int32_t width, int32_t height, std::string& why);
 int check_env_params(const float* rotation9, float intensity, std::string& why);
 void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out);
-// the checks of jpt_set_lens (jpt_capi.cpp), also run by jpt_debug_lens_rays
+// the checks of jpt_set_lens (jpt_primary.cpp), also run by jpt_debug_lens_rays
 int check_lens(float aperture_radius, float focus_distance, std::string& why);
-// the camera model of `model` seen through `cam` (jpt_capi.cpp; jpt_set_camera_model, also run by jpt_debug_camera_rays): the basis
+// the camera model of `model` seen through `cam` (jpt_primary.cpp; jpt_set_camera_model, also run by jpt_debug_camera_rays): the basis
 // for EQUIRECT.  JPT_E_INVALID: no such model; JPT_E_STATE: EQUIRECT's basis or PROJECTIVE's ivp is not finite.
 int make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out, std::string& why);
 // the map's sampling tables built on the device (jpt_kernels_post.hip), on `stream`: cond (w * h floats), marg (h floats) and the
@@ -232,10 +233,25 @@ struct Lighting {
     bool emitter_queues() const { return kind == kEmitters; }   // ... the emitters' (wf2_occlude_lt)
 };
 
+// Where the paths of one render start -- the whole answer, made once per render (resolve_primary, jpt_primary.cpp) and read by
+// everything that prepares or launches it.  The members `kind` does not use are zeroed: radius 0, kCamPinhole, null images.  Host side
+// only: the kernels take lens, cam_model and bake as they are.
+struct PrimaryRays {
+    // the pinhole; the thin lens (jpt_set_lens: the *_lens forms of the primary launch); a camera model other than the pinhole
+    // (jpt_set_camera_model: the *_cam forms); the texel images (jpt_set_bake_texels: the *_bake forms)
+    enum Kind { kPinhole, kLens, kCamModel, kBake } kind = kPinhole;
+    LensDev lens = {};
+    CamModelDev cam_model = {};
+    BakeDev bake = {};
+    // The sky cull, the tiles' sky cells and the cull window apply: the rectangles are the pinhole's projection of the boxes -- from a
+    // point of the aperture a pixel outside them may still see geometry, another model projects otherwise, a bake's paths start on
+    // the surfaces.  False: Wf2Render::cull stays off (n < 0) and sky_tiles null.
+    bool sky_cull() const { return kind == kPinhole; }
+};
+
 // one frame over the reference layout (jpt_kernels_ref.hip); counters may be null
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens, const CamModelDev& cm,
-                      const BakeDev& bake);
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const PrimaryRays& primary);
 
 // The UV2 rasteriser of jpt_bake_add_surface (jpt_kernels_bake.hip), on `stream`: clears `winner` (width * height words), lets every
 // triangle of `surf` claim the texels whose centres it covers (atomicMin of its index), then writes the texels that have a winner
@@ -244,12 +260,7 @@ void launch_bake_raster(hipStream_t stream, const BakeSurfaceDev& surf, int32_t 
                         float4* normal4);
 // the same on the host, over host memory: a plain loop over texels and triangles calling the same coverage and resolve functions
 void bake_raster_host(const BakeSurfaceDev& surf, int32_t width, int32_t height, float4* position4, float4* normal4);
-// the first rays of a bake render's paths (bake_ray) for every texel of one frame, on `stream`: device pointers, n = width * height
-void launch_bake_rays_probe(hipStream_t stream, const BakeDev& bake, int32_t width, int32_t height, uint32_t frame, float* origins3, float* dirs3,
-                            uint8_t* valid);
-void bake_rays_host(const float4* position4, const float4* normal4, int32_t width, int32_t height, uint32_t frame, float* origins3, float* dirs3,
-                    uint8_t* valid);
-// the checks of jpt_set_bake_texels / jpt_bake_begin on the size (jpt_capi.cpp), also run by the jpt_debug_bake_* entry points
+// the checks of jpt_set_bake_texels / jpt_bake_begin on the size (jpt_primary.cpp), also run by the jpt_debug_bake_* entry points
 int check_bake_size(const char* call, int32_t width, int32_t height, std::string& why);
 // ... of jpt_set_bake_texels on the images: a valid texel with a non-finite position or normal component is JPT_E_INVALID
 int check_bake_texels(const char* call, const float* position4, const float* normal4, size_t n, std::string& why);
@@ -313,12 +324,7 @@ struct Wf2Render {
     const uint32_t* sky_tiles = nullptr;   // per 8 x 8 tile of the context's share of the image: its one rgba8 sky cell, if it has one
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
     Lighting lighting;                     // the kernel family of its launches and the workspace's shadow queues (no sky cells with a map)
-    LensDev lens;                          // jpt_set_lens, resolved for this render (resolve_lens): radius > 0 takes the lens forms of the
-                                           // primary launch, with `cull` off (n < 0) and no sky tiles
-    CamModelDev cam_model;                 // jpt_set_camera_model, resolved for this render (resolve_camera_model): a model other than the
-                                           // pinhole takes the *_cam forms of the primary launch, again with no cull and no sky tiles
-    BakeDev bake;                          // jpt_set_bake_texels, resolved for this render (resolve_bake): images present take the *_bake
-                                           // forms of the primary launch, again with no cull and no sky tiles
+    PrimaryRays primary;                   // which form of the primary launch it takes, and that form's argument
 };
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block

@@ -1,7 +1,7 @@
-// jpt_kernels_bake.hip -- lightmap baking's own kernels (jpt_bake.h has the arithmetic): the UV2 rasteriser of jpt_bake_add_surface,
-// the probe of jpt_debug_bake_rays, their host forms (the same __host__ __device__ functions in plain loops) and the argument checks
-// the context's calls and the debug entry points share.  The bake forms of the bounce-0 kernels are in jpt_kernels_wf2.hip
-// (jpt_wf2_paths.h, JPT_BAKE), the audit kernel's branch in jpt_ref_frame.h.
+// jpt_kernels_bake.hip -- lightmap baking's own kernels (jpt_bake.h has the arithmetic): the UV2 rasteriser of jpt_bake_add_surface
+// and its host form (the same __host__ __device__ functions in a plain loop).  The bake forms of the bounce-0 kernels are in
+// jpt_kernels_wf2.hip (jpt_wf2_paths.h, JPT_BAKE), the audit kernel's branch in jpt_ref_frame.h; the argument checks and the
+// context's entry points in jpt_primary.cpp; the probe of jpt_debug_bake_rays in jpt_debug.hip.
 //
 // The rasteriser is three launches on one stream:
 //   bake_clear    winner[i] = 0xffffffff for every texel;
@@ -60,26 +60,6 @@ __global__ __launch_bounds__(kBakeBlock) void bake_write_kernel(BakeSurfaceDev s
     normal4[i] = n4;
 }
 
-__global__ __launch_bounds__(kBakeBlock) void bake_rays_probe(BakeDev bake, int32_t width, int32_t height, uint32_t frame, float* __restrict__ origins3,
-                                                              float* __restrict__ dirs3, uint8_t* __restrict__ valid)
-{
-    const uint32_t i = blockIdx.x * (uint32_t)kBakeBlock + threadIdx.x;
-    if (i >= (uint32_t)width * (uint32_t)height) return;
-    const float4 n4 = bake.normal[i];
-    const bool ok = bake_texel_valid(n4);
-    Ray ray;
-    ray.o = ray.d = ray.rD = mk3(0.0f, 0.0f, 0.0f);
-    uint32_t sx, sy;
-    if (ok) ray = bake_ray(bake.position[i], n4, (int)(i % (uint32_t)width), (int)(i / (uint32_t)width), frame, sx, sy);
-    origins3[3 * (size_t)i] = ray.o.x;
-    origins3[3 * (size_t)i + 1] = ray.o.y;
-    origins3[3 * (size_t)i + 2] = ray.o.z;
-    dirs3[3 * (size_t)i] = ray.d.x;
-    dirs3[3 * (size_t)i + 1] = ray.d.y;
-    dirs3[3 * (size_t)i + 2] = ray.d.z;
-    valid[i] = ok ? 1 : 0;
-}
-
 unsigned blocks_for(size_t n) { return (unsigned)((n + (size_t)kBakeBlock - 1) / (size_t)kBakeBlock); }
 
 }  // namespace
@@ -108,86 +88,6 @@ void bake_raster_host(const BakeSurfaceDev& surf, int32_t width, int32_t height,
                 bake_resolve(surf, t, width, height, x, y, position4[i], normal4[i]);
                 break;
             }
-}
-
-void launch_bake_rays_probe(hipStream_t stream, const BakeDev& bake, int32_t width, int32_t height, uint32_t frame, float* origins3, float* dirs3,
-                            uint8_t* valid)
-{
-    if (width <= 0 || height <= 0) return;
-    const size_t n = (size_t)width * (size_t)height;
-    hipLaunchKernelGGL(bake_rays_probe, dim3(blocks_for(n)), dim3(kBakeBlock), 0, stream, bake, width, height, frame, origins3, dirs3, valid);
-}
-
-void bake_rays_host(const float4* position4, const float4* normal4, int32_t width, int32_t height, uint32_t frame, float* origins3, float* dirs3,
-                    uint8_t* valid)
-{
-    const size_t n = (size_t)width * (size_t)height;
-    for (size_t i = 0; i < n; i++) {
-        const bool ok = bake_texel_valid(normal4[i]);
-        Ray ray;
-        ray.o = ray.d = ray.rD = mk3(0.0f, 0.0f, 0.0f);
-        uint32_t sx, sy;
-        if (ok) ray = bake_ray(position4[i], normal4[i], (int)(i % (size_t)width), (int)(i / (size_t)width), frame, sx, sy);
-        origins3[3 * i] = ray.o.x;
-        origins3[3 * i + 1] = ray.o.y;
-        origins3[3 * i + 2] = ray.o.z;
-        dirs3[3 * i] = ray.d.x;
-        dirs3[3 * i + 1] = ray.d.y;
-        dirs3[3 * i + 2] = ray.d.z;
-        valid[i] = ok ? 1 : 0;
-    }
-}
-
-int check_bake_size(const char* call, int32_t width, int32_t height, std::string& why)
-{
-    if (width < 1 || height < 1) {
-        why = std::string(call) + ": width and height must be >= 1";
-        return JPT_E_INVALID;
-    }
-    if ((uint64_t)width * (uint64_t)height > kBakeMaxTexels) {
-        why = std::string(call) + ": more than 2^26 texels";
-        return JPT_E_LIMIT;
-    }
-    return JPT_OK;
-}
-
-int check_bake_texels(const char* call, const float* position4, const float* normal4, size_t n, std::string& why)
-{
-    for (size_t i = 0; i < n; i++) {
-        const float* nn = normal4 + 4 * i;
-        const float* pp = position4 + 4 * i;
-        if (!(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2] > 0.0f)) continue;   // (an invalid texel: nothing of it is read)
-        bool finite = true;
-        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(nn[k]) && std::isfinite(pp[k]);
-        if (!finite) {
-            why = std::string(call) + ": valid texel " + std::to_string(i) + " has a non-finite position or normal component";
-            return JPT_E_INVALID;
-        }
-    }
-    return JPT_OK;
-}
-
-int check_bake_surface(const char* call, const float* vertices, const float* normals, const int32_t* indices, int32_t n_vertices, int32_t n_indices,
-                       const float* uv2, const float* transform12, std::string& why)
-{
-    if (!vertices || !normals || !indices || !uv2 || !transform12) {
-        why = std::string(call) + ": null argument (vertices, normals, indices, uv2 and transform12 are read)";
-        return JPT_E_INVALID;
-    }
-    if (n_vertices < 0 || n_indices < 0 || n_indices % 3 != 0) {
-        why = std::string(call) + ": n_vertices must be >= 0 and n_indices a multiple of 3";
-        return JPT_E_INVALID;
-    }
-    if ((uint32_t)(n_indices / 3) > kBakeMaxTriangles) {
-        why = std::string(call) + ": more than 2^24 triangles in one call";
-        return JPT_E_LIMIT;
-    }
-    for (int32_t k = 0; k < n_indices; k++)
-        if (indices[k] < 0 || indices[k] >= n_vertices) {
-            why = std::string(call) + ": index " + std::to_string(k) + " is out of range";
-            return JPT_E_INVALID;
-        }
-    return JPT_OK;
 }
 
 }  // namespace jpt

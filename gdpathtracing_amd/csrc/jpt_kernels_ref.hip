@@ -206,9 +206,11 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 #undef JPT_ENV
 
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
-                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const LensDev& lens, const CamModelDev& cm,
-                      const BakeDev& bake)
+                      uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const PrimaryRays& primary)
 {
+    const LensDev& lens = primary.lens;   // (the one kernel takes all three members and branches at run time)
+    const CamModelDev& cm = primary.cam_model;
+    const BakeDev& bake = primary.bake;
     RefSceneDev sc;
     sc.tri_geom = ds.ref_tri_geom;
     sc.bvh = ds.ref_bvh;

@@ -993,25 +993,25 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         if (lg.emitter_queues() && gp.max_bounces > 0) (void)hipMemsetAsync(lnee.scount, 0, (size_t)gp.max_bounces * kSegments * sizeof(uint32_t), st);
         if (ev) (void)hipEventRecord(ev[0], st);
         with_consts<2, 3>([&](auto C, auto W) {
-            if (r.lens.radius > 0.0f) {   // (jpt_set_lens: the lens forms; r.cull is off)
-                if (lg.env_mode != 0)
-                    hipLaunchKernelGGL((wf2_primary_env_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.lens, counters);
-                else
-                    hipLaunchKernelGGL((wf2_primary_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.lens, counters);
-            } else if (r.cam_model.model != kCamPinhole) {   // (jpt_set_camera_model: the model's forms; r.cull is off)
-                if (lg.env_mode != 0)
-                    hipLaunchKernelGGL((wf2_primary_env_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cam_model, counters);
-                else
-                    hipLaunchKernelGGL((wf2_primary_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cam_model, counters);
-            } else if (r.bake.normal != nullptr) {   // (jpt_set_bake_texels: the bake forms; r.cull is off)
-                if (lg.env_mode != 0)
-                    hipLaunchKernelGGL((wf2_primary_env_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.bake, counters);
-                else
-                    hipLaunchKernelGGL((wf2_primary_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.bake, counters);
-            } else if (lg.env_mode != 0)   // (the primary launch is its miss model's: a primary miss has weight 1)
-                hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
-            else
-                hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
+            const bool env = lg.env_mode != 0;   // (the primary launch is its miss model's: a primary miss has weight 1)
+            switch (r.primary.kind) {   // (r.cull is off for every kind but the pinhole)
+            case PrimaryRays::kLens:
+                if (env) hipLaunchKernelGGL((wf2_primary_env_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.lens, counters);
+                else hipLaunchKernelGGL((wf2_primary_lens<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.lens, counters);
+                break;
+            case PrimaryRays::kCamModel:
+                if (env) hipLaunchKernelGGL((wf2_primary_env_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.cam_model, counters);
+                else hipLaunchKernelGGL((wf2_primary_cam<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.cam_model, counters);
+                break;
+            case PrimaryRays::kBake:
+                if (env) hipLaunchKernelGGL((wf2_primary_env_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.bake, counters);
+                else hipLaunchKernelGGL((wf2_primary_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.bake, counters);
+                break;
+            case PrimaryRays::kPinhole:
+                if (env) hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
+                else hipLaunchKernelGGL((wf2_primary<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);
+                break;
+            }
         }, count, walk);
         if (ev) (void)hipEventRecord(ev[1], st);
         for (int b = 0; b <= gp.max_bounces; b++) {

@@ -1,0 +1,321 @@
+// jpt_primary.cpp -- where a context's renders start their paths: the thin lens, the camera model and the bake images (PrimaryState,
+// jpt_ctx.h), the one resolver that turns them into a render's PrimaryRays (jpt_kernels.h), the view of the entry points that take
+// one without rendering, and the C entries that set them.  Host C++: the kernels are jpt_kernels_bake.hip's and jpt_debug.hip's.
+#include "jpt_ctx.h"
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "jpt_instance_math.h"
+
+int jpt::check_lens(float aperture_radius, float focus_distance, std::string& why)
+{
+    if (!std::isfinite(aperture_radius) || aperture_radius < 0.0f) {
+        why = "jpt_set_lens: aperture_radius must be finite and >= 0";
+        return JPT_E_INVALID;
+    }
+    if (aperture_radius > 0.0f && (!std::isfinite(focus_distance) || !(focus_distance > 0.0f))) {
+        why = "jpt_set_lens: focus_distance must be finite and > 0";
+        return JPT_E_INVALID;
+    }
+    if (!std::isfinite(focus_distance) || focus_distance < 0.0f) {   // (not read with radius 0, but never kept as garbage)
+        why = "jpt_set_lens: focus_distance must be finite and > 0";
+        return JPT_E_INVALID;
+    }
+    return JPT_OK;
+}
+
+static_assert(JPT_CAMERA_PINHOLE == kCamPinhole && JPT_CAMERA_PROJECTIVE == kCamProjective && JPT_CAMERA_EQUIRECT == kCamEquirect,
+              "jpt_camera.h restates the enum of jpt.h");
+
+int jpt::make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out, std::string& why)
+{
+    out = CamModelDev{};
+    if (model != JPT_CAMERA_PINHOLE && model != JPT_CAMERA_PROJECTIVE && model != JPT_CAMERA_EQUIRECT) {
+        why = "jpt_set_camera_model: model must be JPT_CAMERA_PINHOLE, JPT_CAMERA_PROJECTIVE or JPT_CAMERA_EQUIRECT";
+        return JPT_E_INVALID;
+    }
+    if (model == JPT_CAMERA_EQUIRECT) {
+        LensDev basis;
+        if (!lens_basis(cam, basis)) {
+            why = "jpt_set_camera_model: the camera basis derived from camera160 (ivp, position) is not finite";
+            return JPT_E_STATE;
+        }
+        out.f = basis.f;
+        out.r = basis.r;
+        out.u = basis.u;
+    }
+    if (model == JPT_CAMERA_PROJECTIVE)
+        for (int k = 0; k < 16; k++)
+            if (!std::isfinite(cam.ivp[k])) {
+                why = "jpt_set_camera_model: the ivp of camera160 is not finite";
+                return JPT_E_STATE;
+            }
+    out.model = model;
+    return JPT_OK;
+}
+
+// One decision, in this order: DEBUG_STEPS, the bake images, the lens, the model.  The sources exclude one another, and a refusal
+// names the first of them in that order: a bake render with a lens is refused as a bake and not for the lens's own reasons.
+int jpt::resolve_primary(jpt_ctx* c, PrimaryRays& out)
+{
+    const PrimaryState& p = c->primary;
+    out = PrimaryRays{};
+    if (c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the images, the lens and the model, as it ignores lighting)
+    const bool lens = p.lens_radius > 0.0f, model = p.camera_model != JPT_CAMERA_PINHOLE, temporal = c->denoise == JPT_DENOISE_TEMPORAL;
+    if (p.has_bake()) {
+        if (p.bake_w != c->width || p.bake_h != c->height)
+            return fail(c, JPT_E_STATE, "the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) + " texels but jpt_set_params says " +
+                                            std::to_string(c->width) + " x " + std::to_string(c->height) + ": a bake render has one path per texel (jpt_set_bake_texels)");
+        if (lens) return fail(c, JPT_E_STATE, "a bake render has no lens: set the lens radius to 0 (jpt_set_lens) or free the bake images (jpt_set_bake_texels)");
+        if (model)
+            return fail(c, JPT_E_STATE, "a bake render has no camera model: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or free the bake images (jpt_set_bake_texels)");
+        if (temporal) return fail(c, JPT_E_STATE, "temporal reprojection assumes a camera: set another denoising mode or free the bake images (jpt_set_bake_texels)");
+        out.kind = PrimaryRays::kBake;
+        out.bake.position = p.d_bake_pos.p;
+        out.bake.normal = p.d_bake_nrm.p;
+    } else if (lens) {
+        if (temporal)
+            return fail(c, JPT_E_STATE, "temporal reprojection assumes one centre of projection: set the lens radius to 0 (jpt_set_lens) or another denoising mode");
+        LensDev l;
+        l.radius = p.lens_radius;
+        l.focus = p.lens_focus;
+        if (!lens_basis(c->camera, l)) return fail(c, JPT_E_STATE, "jpt_set_lens: the camera basis derived from camera160 (ivp, position) is not finite");
+        if (model)
+            return fail(c, JPT_E_STATE, "the lens disk is defined around one centre of projection: set the lens radius to 0 (jpt_set_lens) or JPT_CAMERA_PINHOLE (jpt_set_camera_model)");
+        out.kind = PrimaryRays::kLens;
+        out.lens = l;
+    } else if (model) {
+        if (temporal) return fail(c, JPT_E_STATE, "temporal reprojection assumes the pinhole: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or another denoising mode");
+        std::string why;
+        const int rc = make_camera_model(p.camera_model, c->camera, out.cam_model, why);
+        if (rc != JPT_OK) return fail(c, rc, why);
+        out.kind = PrimaryRays::kCamModel;
+    }
+    return JPT_OK;
+}
+
+int jpt::view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& out)
+{
+    if (c->primary.has_bake())
+        return fail(c, JPT_E_STATE, std::string(call) + ": " + rays + " are camera rays, and the context holds bake images (jpt_set_bake_texels)");
+    std::string why;
+    const int rc = make_camera_model(c->primary.camera_model, c->camera, out, why);
+    return rc == JPT_OK ? JPT_OK : fail(c, rc, why);
+}
+
+// ---- the checks of the bake entry points, also run by the jpt_debug_bake_* ones -------------------------------------------------
+
+int jpt::check_bake_size(const char* call, int32_t width, int32_t height, std::string& why)
+{
+    if (width < 1 || height < 1) {
+        why = std::string(call) + ": width and height must be >= 1";
+        return JPT_E_INVALID;
+    }
+    if ((uint64_t)width * (uint64_t)height > kBakeMaxTexels) {
+        why = std::string(call) + ": more than 2^26 texels";
+        return JPT_E_LIMIT;
+    }
+    return JPT_OK;
+}
+
+int jpt::check_bake_texels(const char* call, const float* position4, const float* normal4, size_t n, std::string& why)
+{
+    for (size_t i = 0; i < n; i++) {
+        const float* nn = normal4 + 4 * i;
+        const float* pp = position4 + 4 * i;
+        if (!(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2] > 0.0f)) continue;   // (an invalid texel: nothing of it is read)
+        bool finite = true;
+        for (int k = 0; k < 3; k++) finite = finite && std::isfinite(nn[k]) && std::isfinite(pp[k]);
+        if (!finite) {
+            why = std::string(call) + ": valid texel " + std::to_string(i) + " has a non-finite position or normal component";
+            return JPT_E_INVALID;
+        }
+    }
+    return JPT_OK;
+}
+
+int jpt::check_bake_surface(const char* call, const float* vertices, const float* normals, const int32_t* indices, int32_t n_vertices, int32_t n_indices,
+                            const float* uv2, const float* transform12, std::string& why)
+{
+    if (!vertices || !normals || !indices || !uv2 || !transform12) {
+        why = std::string(call) + ": null argument (vertices, normals, indices, uv2 and transform12 are read)";
+        return JPT_E_INVALID;
+    }
+    if (n_vertices < 0 || n_indices < 0 || n_indices % 3 != 0) {
+        why = std::string(call) + ": n_vertices must be >= 0 and n_indices a multiple of 3";
+        return JPT_E_INVALID;
+    }
+    if ((uint32_t)(n_indices / 3) > kBakeMaxTriangles) {
+        why = std::string(call) + ": more than 2^24 triangles in one call";
+        return JPT_E_LIMIT;
+    }
+    for (int32_t k = 0; k < n_indices; k++)
+        if (indices[k] < 0 || indices[k] >= n_vertices) {
+            why = std::string(call) + ": index " + std::to_string(k) + " is out of range";
+            return JPT_E_INVALID;
+        }
+    return JPT_OK;
+}
+
+namespace {
+
+// the renders already queued read the old images: they finish first (every one of them ends with work on the context's stream)
+int bake_wait(jpt_ctx* c)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return JPT_OK;
+}
+
+void bake_release(jpt_ctx* c)
+{
+    PrimaryState& p = c->primary;
+    p.d_bake_pos.release();
+    p.d_bake_nrm.release();
+    p.d_bake_winner.release();
+    p.d_bake_in.release();
+    p.bake_w = p.bake_h = 0;
+}
+
+int bake_alloc(jpt_ctx* c, int32_t width, int32_t height)
+{
+    const size_t n = (size_t)width * (size_t)height;
+    hipError_t e = c->primary.d_bake_pos.resize(n);
+    if (e == hipSuccess) e = c->primary.d_bake_nrm.resize(n);
+    if (e != hipSuccess) {
+        bake_release(c);
+        return hip_fail(c, e, "hipMalloc of the bake images");
+    }
+    c->primary.bake_w = width;
+    c->primary.bake_h = height;
+    return JPT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpt_set_lens(jpt_ctx* c, float aperture_radius, float focus_distance)
+{
+    if (!c) return JPT_E_INVALID;
+    std::string why;
+    const int rc = check_lens(aperture_radius, focus_distance, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the lens is a property of device renders");
+    c->primary.lens_radius = aperture_radius;   // (each render takes them by value: resolve_primary)
+    c->primary.lens_focus = focus_distance;
+    return JPT_OK;
+}
+
+int jpt_set_camera_model(jpt_ctx* c, int32_t model)
+{
+    if (!c) return JPT_E_INVALID;
+    if (model != JPT_CAMERA_PINHOLE && model != JPT_CAMERA_PROJECTIVE && model != JPT_CAMERA_EQUIRECT)
+        return fail(c, JPT_E_INVALID, "jpt_set_camera_model: model must be JPT_CAMERA_PINHOLE, JPT_CAMERA_PROJECTIVE or JPT_CAMERA_EQUIRECT");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the camera model is a property of device renders");
+    c->primary.camera_model = model;   // (each render takes it by value: resolve_primary)
+    return JPT_OK;
+}
+
+// ---- lightmap baking: the context's texel images (jpt_bake.h) -------------------------------------------------------------------
+
+int jpt_set_bake_texels(jpt_ctx* c, const float* position4, const float* normal4, int32_t width, int32_t height)
+{
+    if (!c) return JPT_E_INVALID;
+    const bool freeing = !position4 && !normal4 && width == 0 && height == 0;
+    if (!freeing) {
+        if (!position4 || !normal4) return fail(c, JPT_E_INVALID, "jpt_set_bake_texels: position4 and normal4 are both given, or (NULL, NULL, 0, 0) frees the images");
+        std::string why;
+        int rc = check_bake_size("jpt_set_bake_texels", width, height, why);
+        if (rc == JPT_OK) rc = check_bake_texels("jpt_set_bake_texels", position4, normal4, (size_t)width * (size_t)height, why);
+        if (rc != JPT_OK) return fail(c, rc, why);
+    }
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_texels: host-only context has no bake images");
+    int rc = bake_wait(c);
+    if (rc != JPT_OK) return rc;
+    if (freeing) {
+        bake_release(c);
+        return JPT_OK;
+    }
+    if ((rc = bake_alloc(c, width, height)) != JPT_OK) return rc;
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
+    HIP_TRY(c, hipMemcpy(c->primary.d_bake_pos.p, position4, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->primary.d_bake_nrm.p, normal4, bytes, hipMemcpyHostToDevice));
+    return JPT_OK;
+}
+
+int jpt_bake_begin(jpt_ctx* c, int32_t width, int32_t height)
+{
+    if (!c) return JPT_E_INVALID;
+    std::string why;
+    int rc = check_bake_size("jpt_bake_begin", width, height, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_begin: host-only context has no bake images");
+    if ((rc = bake_wait(c)) != JPT_OK) return rc;
+    if ((rc = bake_alloc(c, width, height)) != JPT_OK) return rc;
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(float4);
+    HIP_TRY(c, hipMemsetAsync(c->primary.d_bake_pos.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->primary.d_bake_nrm.p, 0, bytes, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return JPT_OK;
+}
+
+int jpt_bake_add_surface(jpt_ctx* c, const jpt_surface* surface, const float* uv2, const float* transform12)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!surface) return fail(c, JPT_E_INVALID, "jpt_bake_add_surface: null surface");
+    std::string why;
+    int rc = check_bake_surface("jpt_bake_add_surface", surface->vertices, surface->normals, surface->indices, surface->n_vertices, surface->n_indices, uv2,
+                                transform12, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_add_surface: host-only context has no bake images");
+    if (!c->primary.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_add_surface: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    if ((rc = bake_wait(c)) != JPT_OK) return rc;
+    const uint32_t n_tris = (uint32_t)(surface->n_indices / 3);
+    if (n_tris == 0) return JPT_OK;
+    // the surface staged in one device buffer: vertices, normals, uv2, indices (each a multiple of 4 bytes)
+    const size_t nv = (size_t)surface->n_vertices;
+    const size_t b_v = nv * 3 * sizeof(float), b_uv = nv * 2 * sizeof(float), b_i = (size_t)n_tris * 3 * sizeof(int32_t);
+    const size_t need = 2 * b_v + b_uv + b_i;
+    if (c->primary.d_bake_in.n < need) HIP_TRY(c, c->primary.d_bake_in.resize(need));
+    const size_t npx = (size_t)c->primary.bake_w * (size_t)c->primary.bake_h;
+    if (c->primary.d_bake_winner.n < npx) HIP_TRY(c, c->primary.d_bake_winner.resize(npx));
+    char* base = c->primary.d_bake_in.p;
+    HIP_TRY(c, hipMemcpy(base, surface->vertices, b_v, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(base + b_v, surface->normals, b_v, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(base + 2 * b_v, uv2, b_uv, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(base + 2 * b_v + b_uv, surface->indices, b_i, hipMemcpyHostToDevice));
+    BakeSurfaceDev sd;
+    sd.vertices = reinterpret_cast<const float*>(base);
+    sd.normals = reinterpret_cast<const float*>(base + b_v);
+    sd.uv2 = reinterpret_cast<const float*>(base + 2 * b_v);
+    sd.indices = reinterpret_cast<const int32_t*>(base + 2 * b_v + b_uv);
+    sd.n_tris = n_tris;
+    transform12_to_mat16(transform12, sd.transform);
+    launch_bake_raster(c->stream, sd, c->primary.bake_w, c->primary.bake_h, c->primary.d_bake_winner.p, c->primary.d_bake_pos.p, c->primary.d_bake_nrm.p);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return JPT_OK;
+}
+
+int jpt_read_bake_texels(jpt_ctx* c, float* position4, float* normal4)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_bake_texels: host-only context has no bake images");
+    if (!c->primary.has_bake()) return fail(c, JPT_E_STATE, "jpt_read_bake_texels: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->primary.bake_w * (size_t)c->primary.bake_h * sizeof(float4);
+    float* const out[2] = {position4, normal4};
+    const float4* const src[2] = {c->primary.d_bake_pos.p, c->primary.d_bake_nrm.p};
+    for (int k = 0; k < 2; k++) {
+        if (!out[k]) continue;
+        const int rc = staged_read(c, src[k], bytes);
+        if (rc != JPT_OK) return rc;
+        std::memcpy(out[k], c->h_read_pinned.p, bytes);
+    }
+    return JPT_OK;
+}
+
+}  // extern "C"

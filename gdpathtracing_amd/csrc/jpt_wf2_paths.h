@@ -86,6 +86,8 @@
 // (BakeDev, by value) where the sky cull was; at refill the lane reads its texel's normal (16 B) and, for a valid texel, its position
 // (16 B) and starts the path with bake_ray (jpt_bake.h).  An invalid texel traces nothing: its path ends here with radiance 0 and
 // first-hit distance cam.far_, as a sky path of the default kernel ends in save_results, and is not counted as a ray.  No cull.
+//
+// launch_wf2_render takes one of these eight forms by the kind of the render's PrimaryRays (jpt_kernels.h) and its miss model.
 #ifdef JPT_LENS
 #if JPT_ENV
 #define JPT_PRIMARY_NAME wf2_primary_env_lens
