@@ -115,6 +115,74 @@ __device__ __forceinline__ bool walk_round(Traversal<COUNT, W4>& tr, bool active
     return active && tr.finished();
 }
 
+// A lane mask as a per-lane predicate: costs nothing (the mask IS the predicate's register form).
+__device__ __forceinline__ bool in_mask(const unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+
+// The same round for the tracing launches (trace_queue), with the wave's bookkeeping on the SCALAR side.  `act` is the wave-uniform
+// mask of the lanes that hold a ray; the round returns the mask of the lanes whose walk it completed.  Same steps per ray, same
+// phase decisions and counters as walk_round; what differs is how the wave arrives at them:
+//  - a ballot of a loop-carried flag, or of a conjunction, compiles to v_cndmask 0/1 + v_cmp_ne (2 x 4.2 cycles of VALU issue),
+//    a ballot of ONE comparison to the comparison alone.  So the phase masks are built from ballot(cur < 0), ballot(sp > 0) and
+//    the two flags `have` and `in_blas`, combined with scalar and / andn2, instead of one ballot per conjunction (five);
+//  - `active` is not balloted at all: it is `act`, and the per-lane predicates come back from masks (in_mask);
+//  - the finished lanes need no look at `have` after the phases: leaf_step leaves have = false and the stack as it was,
+//    instance_step (not REACH) leaves have = true, everyone else is untouched -- have-after = (have & ~leaves) | instances;
+//  - pop_next restores the world ray's slab constants on demand (pop_next<true>), not once per round in the loop's pre-header.
+template <bool COUNT, bool W4>
+__device__ __forceinline__ unsigned long long walk_round_masked(Traversal<COUNT, W4>& tr, const unsigned long long act, const WideSceneDev& sc,
+                                                                const typename Traversal<COUNT, W4>::Stack& st, DevCounters& cnt, const WfTune& tune,
+                                                                uint32_t& steps)
+{
+    const int kNodeMinLanes = tune.node_min_lanes;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    const bool active = in_mask(act);
+    if (COUNT && lane0) cnt.phase[0]++;
+    const int na = __popcll(act);
+    const int cap = (na * tune.phase_frac16) >> 4;   // (the thresholds' caps: see walk_round)
+    const int lmin = tune.leaf_min_lanes < cap ? tune.leaf_min_lanes : cap;
+    const int imin = tune.inst_min_lanes < cap ? tune.inst_min_lanes : cap;
+    for (int it = 0; it < 64; it++) {
+        if (active && !tr.have && tr.sp > 0) tr.template pop_next<true>(st);
+        const bool want = active && tr.wants_node();
+        const unsigned long long m = __ballot(want);
+        if (m == 0 || (it > 0 && __popcll(m) < kNodeMinLanes)) break;
+        if (COUNT && lane0) {
+            cnt.phase[1]++;
+            cnt.phase[2] += (unsigned long long)__popcll(m);
+        }
+        if (want) tr.node_step(sc, st, cnt);
+        if (COUNT && want) steps++;
+    }
+    const unsigned long long hm = __ballot(tr.have), bm = __ballot(tr.in_blas);   // (the two flags)
+    const unsigned long long lf = __ballot(tr.cur < 0), sm = __ballot(tr.sp > 0);
+    const unsigned long long hv = act & hm;
+    unsigned long long wlm = hv & lf & bm, wim = hv & lf & ~bm;   // wants_leaf(), wants_instance()
+    if (W4 && (tune.leaf_min_lanes > 1 || tune.inst_min_lanes > 1)) {
+        const int nl = __popcll(wlm), ni = __popcll(wim);
+        const bool nodes_left = ((hv & ~lf) | (act & ~hm & sm)) != 0ull;
+        const bool run_l = nl >= lmin || !(nodes_left || ni >= imin);
+        const bool run_i = ni >= imin || !(nodes_left || (run_l && nl > 0));
+        wlm = run_l ? wlm : 0ull;
+        wim = run_i ? wim : 0ull;
+    }
+    if (COUNT) {
+        const int nl = __popcll(wlm), ni = __popcll(wim);
+        if (lane0 && nl) {
+            cnt.phase[3]++;
+            cnt.phase[4] += (unsigned long long)nl;
+        }
+        if (lane0 && ni) {
+            cnt.phase[5]++;
+            cnt.phase[6] += (unsigned long long)ni;
+        }
+    }
+    const bool wl = in_mask(wlm), wi = in_mask(wim);
+    if (wl) tr.leaf_step(sc, cnt);
+    if (wi) tr.instance_step(sc, st, cnt);
+    if (COUNT && (wl || wi)) steps++;
+    return act & ~((hm & ~wlm) | wim) & ~sm;   // active && !have && sp == 0, see above
+}
+
 // What a render writes once and reads once -- ray and hit queues, finished paths' colours, the framebuffers -- goes past the caches
 // with the non-temporal hint (`nt` on the load / store), so that 200 MB of hand-offs per launch do not push the tree's records out
 // of the 4 MB L2s (C3 -2.5 %, the 4 M-triangle scene -3 %: round 5).
@@ -437,8 +505,14 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
     const float4* __restrict__ qo = wb.ray_o[bounce & 1];
     const float4* __restrict__ qd = wb.ray_d[bounce & 1];
     Traversal<COUNT, W4> tr;
-    bool active = false, exhausted = false;
-    bool unsaved = false;   // this lane's finished walk has not written its hit yet
+    tr.have = tr.in_blas = false;   // (walk_round_masked ballots these members of every lane and masks the answers with `act`)
+    tr.cur = 0;
+    tr.sp = 0;
+    // The wave's bookkeeping is wave-uniform and lives in scalars: `act`, the lanes that hold a ray -- the round takes the
+    // finished ones out, the refill adds the ones it filled; idle lanes, the exit tests and the tail's lanes all derive from it --
+    // and `unsaved`, the lanes whose finished walk has not written its hit yet.
+    unsigned long long act = 0ull, unsaved = 0ull;
+    bool exhausted = false;
     size_t my_loc = 0;
     uint32_t walk_steps = 0;   // (counting builds: record steps of this lane's ray)
     // A finished walk's hit stays in the lane's registers until the lane takes its next ray: the hits are written when the
@@ -450,20 +524,19 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
     };
 
     for (;;) {
-        const unsigned long long idle = __ballot(!active);
+        const unsigned long long idle = ~act;
         const int n_idle = __popcll(idle);
         if (!exhausted && n_idle >= tune.refill_idle) {
-            if (unsaved) {
-                save_hit();
-                unsaved = false;
-            }
+            if (in_mask(unsaved)) save_hit();
+            unsaved = 0ull;
             uint32_t start = 0;
             if (lane == 0) start = atomicAdd(s_cursor, (uint32_t)n_idle);
             start = (uint32_t)__builtin_amdgcn_readfirstlane((int)start);
             if (start + (uint32_t)n_idle >= n) exhausted = true;
-            if (start < n && !active) {
+            if (start < n) {
                 const uint32_t idx = start + lanes_below(idle, lane);
-                if (idx < n) {
+                const unsigned long long fill = idle & __ballot(idx < n);
+                if (in_mask(fill)) {
                     // which of the chained segments holds entry idx
                     uint32_t k = 0, first = 0;
                     for (int j = 0; j < kMaxChain - 1; j++)
@@ -475,34 +548,33 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
                     const float4 ro = stream_ld4(&qo[loc]), rd = stream_ld4(&qd[loc]);
                     tr.begin(sc, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z));
                     my_loc = loc;
-                    active = true;
                     walk_steps = 0;
                 }
+                act |= fill;
             }
         }
-        if (!__any(active)) {
+        if (act == 0ull) {
             if (exhausted) break;
             continue;
         }
         {
-            if (walk_round<COUNT, W4>(tr, active, sc, my_stack, cnt, tune, walk_steps)) {
-                active = false;
-                unsaved = true;
-                if (COUNT) count_walk(cnt, walk_steps);
+            const unsigned long long done = walk_round_masked<COUNT, W4>(tr, act, sc, my_stack, cnt, tune, walk_steps);
+            act &= ~done;
+            unsaved |= done;
+            if (COUNT) {
+                if (in_mask(done)) count_walk(cnt, walk_steps);
             }
             if constexpr (TAIL && W4) {
-                if (exhausted && ++dry_rounds >= (uint32_t)tune.tail_rounds && __popcll(__ballot(active)) <= tune.tail_lanes) break;
+                if (exhausted && ++dry_rounds >= (uint32_t)tune.tail_rounds && __popcll(act) <= tune.tail_lanes) break;
             }
         }
     }
     if constexpr (TAIL && W4) {
         // tail phase (see wf2_primary)
-        unsigned long long left = __ballot(active);
+        unsigned long long left = act;
         if (left) {
-            if (unsaved) {
-                save_hit();
-                unsaved = false;
-            }
+            if (in_mask(unsaved)) save_hit();
+            unsaved = 0ull;
             const int wave_col = (int)(threadIdx.x & ~63u);
             while (left) {
                 const int src = __ffsll((long long)left) - 1;
@@ -514,13 +586,12 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
                                       COUNT ? &cnt : nullptr, &h);
                 if (lane == src) {
                     tr.hit = h;
-                    active = false;
                     save_hit();
                 }
             }
         }
     }
-    if (unsaved) save_hit();
+    if (in_mask(unsaved)) save_hit();
 }
 
 template <bool COUNT, bool W4, bool TAIL = false>

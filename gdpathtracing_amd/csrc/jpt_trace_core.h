@@ -408,6 +408,14 @@ struct Traversal {
 
     // take the next record off the stack (precondition: !have && sp > 0).  Leaving an instance restores
     // the world ray.  Afterwards either `have` or finished().
+    //
+    // ON_DEMAND (the tracing launches' rounds, walk_round_masked): the restore's set_level() stays HERE, under the branch that
+    // needs it.  Its inputs wo / wd do not change during a walk, so the compiler otherwise hoists the three v_rcp_f32, three
+    // v_med3_f32 and three v_mul_f32 into the pre-header of the round's record loop, where the whole wave pays them in every
+    // round -- for values that are used only when a lane leaves an instance into a TLAS record (never, on a TLAS of one
+    // record).  The empty asm makes d opaque at this point: nothing to hoist.  The other callers (step(): occlusion, query,
+    // guide, finish and audit kernels; the primary launch) keep the form their register budgets were set with.
+    template <bool ON_DEMAND = false>
     __device__ __forceinline__ void pop_next(const Stack& st)
     {
         cur = pop(st);
@@ -421,6 +429,7 @@ struct Traversal {
             if (!kLean || cur >= 0) {   // (C3 -1.5 %, close-up -1.7 %: profiles/r03/r03i_ab_pop_restore.txt)
                 o = wo;
                 d = wd;
+                if (kLean && ON_DEMAND) asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
                 if (kLean) set_level();   // (recomputed rather than kept: three v_rcp_f32 per instance left, registers saved)
                 else rD = wrD;
             }
