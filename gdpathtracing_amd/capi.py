@@ -62,6 +62,7 @@ SYMBOLS = [
     "jpt_set_camera_model", "jpt_multi_set_camera_model", "jpt_debug_camera_rays",
     "jpt_set_bake_texels", "jpt_bake_begin", "jpt_bake_add_surface", "jpt_read_bake_texels", "jpt_multi_set_bake_texels",
     "jpt_debug_bake_rays", "jpt_debug_bake_raster",
+    "jpt_set_bake_finish_params", "jpt_bake_finish", "jpt_read_lightmap_f32", "jpt_debug_bake_finish",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
@@ -84,6 +85,15 @@ class DenoiseParams(C.Structure):
 
     def __init__(self, passes=5, normal_power_log2=6, sigma_plane=0.02, sigma_color=4.0):
         super().__init__(passes, normal_power_log2, sigma_plane, sigma_color)
+
+
+class BakeFinishParams(C.Structure):
+    """jpt_bake_finish_params; the defaults are the library's"""
+    _fields_ = [("passes", C.c_int32), ("normal_power_log2", C.c_int32), ("dilate", C.c_int32), ("sigma_distance", C.c_float),
+                ("sigma_plane", C.c_float), ("sigma_color", C.c_float)]
+
+    def __init__(self, passes=3, normal_power_log2=4, dilate=4, sigma_distance=4.0, sigma_plane=1.0, sigma_color=4.0):
+        super().__init__(passes, normal_power_log2, dilate, sigma_distance, sigma_plane, sigma_color)
 
 
 class DisplayParams(C.Structure):
@@ -302,6 +312,11 @@ def lib():
         L.jpt_multi_set_bake_texels.argtypes = [vp, vp, vp, i32, i32]
         L.jpt_debug_bake_rays.argtypes = [C.c_int, vp, vp, i32, i32, u32, vp, vp, vp]
         L.jpt_debug_bake_raster.argtypes = [C.c_int, C.POINTER(Surface), vp, vp, i32, i32, vp, vp]
+    if hasattr(L, "jpt_bake_finish") or "JPT_LIB" not in os.environ:
+        L.jpt_set_bake_finish_params.argtypes = [vp, C.POINTER(BakeFinishParams)]
+        L.jpt_bake_finish.argtypes = [vp]
+        L.jpt_read_lightmap_f32.argtypes = [vp, vp]
+        L.jpt_debug_bake_finish.argtypes = [C.c_int, i32, i32, C.POINTER(BakeFinishParams), vp, vp, vp, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

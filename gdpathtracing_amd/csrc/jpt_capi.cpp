@@ -1895,6 +1895,11 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
         c->d_dn_pong.release();
         c->d_dn_ldr.release();
     }
+    if ((width != c->width || height != c->height) && c->d_lm_ping.p) {
+        // jpt_bake_finish's images likewise
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->lightmap_release();
+    }
     if ((width != c->width || height != c->height) && (c->d_disp_f32.p || c->d_disp_pyramid.p)) {
         // jpt_display's buffers likewise
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2228,6 +2233,90 @@ int jpt_read_guides_f32(jpt_ctx* c, float* position_t, float* normal, float* alb
         if ((rc = staged_read(c, src[k], bytes)) != JPT_OK) return rc;
         std::memcpy(outs[k], c->h_read_pinned.p, bytes);
     }
+    return JPT_OK;
+}
+
+// ---- jpt_bake_finish: the chart-aware filter and the dilation of a baked lightmap (jpt_lightmap.h) -----------------------------
+
+extern "C++" {
+namespace jpt {
+int check_bake_finish_params(const char* call, const LightmapParams& p, std::string& why)
+{
+    const std::string who = std::string(call) + ": ";
+    if (p.passes < 0 || p.passes > kLightmapMaxPasses) why = who + "passes must be in [0, 6]";
+    else if (p.normal_power_log2 < 0 || p.normal_power_log2 > 8) why = who + "normal_power_log2 must be in [0, 8]";
+    else if (p.dilate < 0 || p.dilate > kLightmapMaxDilate) why = who + "dilate must be in [0, 64]";
+    else if (!std::isfinite(p.sigma_distance) || !(p.sigma_distance > 0.0f)) why = who + "sigma_distance must be finite and > 0";
+    else if (!std::isfinite(p.sigma_plane) || !(p.sigma_plane > 0.0f)) why = who + "sigma_plane must be finite and > 0";
+    else if (!std::isfinite(p.sigma_color) || !(p.sigma_color > 0.0f)) why = who + "sigma_color must be finite and > 0";
+    else return JPT_OK;
+    return JPT_E_INVALID;
+}
+}  // namespace jpt
+}
+
+int jpt_set_bake_finish_params(jpt_ctx* c, const jpt_bake_finish_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    LightmapParams p;
+    if (params) {
+        p.passes = params->passes;
+        p.normal_power_log2 = params->normal_power_log2;
+        p.dilate = params->dilate;
+        p.sigma_distance = params->sigma_distance;
+        p.sigma_plane = params->sigma_plane;
+        p.sigma_color = params->sigma_color;
+    }
+    std::string why;
+    const int rc = check_bake_finish_params("jpt_set_bake_finish_params", p, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_finish_params: host-only context: jpt_bake_finish runs on the device");
+    c->lm_params = p;
+    return JPT_OK;
+}
+
+int jpt_bake_finish(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_bake_finish filters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_bake_finish: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_bake_finish needs the whole image on one context (world == 1)");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_finish: host-only context: it runs on the device");
+    const PrimaryState& p = c->primary;
+    if (!p.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_finish: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    if (!c->params_set || p.bake_w != c->width || p.bake_h != c->height)
+        return fail(c, JPT_E_STATE, "jpt_bake_finish: the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) +
+                                        " texels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_bake_finish: no frame accumulated since the last reset");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->width * c->height;   // (>= 1: the images have at least one texel)
+    if (c->d_lm_ping.n != npx || !c->d_lm_ping.p) {
+        c->lm_result = nullptr;
+        HIP_TRY(c, c->d_lm_xg.resize(npx));
+        HIP_TRY(c, c->d_lm_ng.resize(npx));
+        HIP_TRY(c, c->d_lm_ping.resize(npx));
+        HIP_TRY(c, c->d_lm_pong.resize(npx));
+    }
+    // On the context's stream, as jpt_denoise: behind the accumulation of every render queued so far, and the accumulation of every
+    // later render waits for what it holds.
+    c->lm_result = launch_lightmap_finish(c->stream, c->lm_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, p.d_bake_pos.p, p.d_bake_nrm.p,
+                                          c->d_lm_xg.p, c->d_lm_ng.p, c->d_lm_ping.p, c->d_lm_pong.p);
+    HIP_TRY(c, hipGetLastError());
+    return JPT_OK;
+}
+
+int jpt_read_lightmap_f32(jpt_ctx* c, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_lightmap_f32: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_lightmap_f32: host-only context: jpt_bake_finish runs on the device");
+    if (!c->lm_result) return fail(c, JPT_E_STATE, "jpt_read_lightmap_f32: no jpt_bake_finish at the current size and bake images yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
+    const int rc = staged_read(c, c->lm_result, bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
     return JPT_OK;
 }
 

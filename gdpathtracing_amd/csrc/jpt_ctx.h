@@ -5,6 +5,7 @@
 #include "jpt_builder.h"
 #include "jpt_denoise.h"
 #include "jpt_display.h"
+#include "jpt_lightmap.h"
 #include "jpt_meter.h"
 #include "jpt_kernels.h"
 
@@ -322,6 +323,21 @@ struct jpt_ctx {
     DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
     DevBuf<uint32_t> d_dn_ldr;
     bool dn_valid = false;
+
+    // jpt_bake_finish: the context's parameters, and its own images (two guides, a colour ping and pong: 64 B per texel) -- made at
+    // the first jpt_bake_finish at a size, kept until jpt_set_params names another size or a call writes the bake images
+    // (lightmap_release); lm_result: the one of ping / pong that holds the lightmap of a jpt_bake_finish at the current size and images
+    LightmapParams lm_params;
+    DevBuf<float4> d_lm_xg, d_lm_ng, d_lm_ping, d_lm_pong;
+    const float4* lm_result = nullptr;
+    void lightmap_release()
+    {
+        d_lm_xg.release();
+        d_lm_ng.release();
+        d_lm_ping.release();
+        d_lm_pong.release();
+        lm_result = nullptr;
+    }
 
     // jpt_display: the context's parameters, and its own buffers -- the two images made at the first jpt_display at a resolution,
     // the pyramid (six levels' worth) at the first one with bloom, kept until jpt_set_params names another size; disp_valid: the

@@ -19,6 +19,7 @@
 
 #include "jpt_instance_math.h"
 #include "jpt_kernels.h"
+#include "jpt_lightmap.h"
 #include "jpt_nodeq.h"
 #include "jpt_primary_ray.h"
 #include "jpt_trace_core.h"
@@ -653,6 +654,52 @@ int jpt_debug_bake_raster(int device_id, const jpt_surface* surface, const float
     if (rc == JPT_OK && (e = hipMemcpy(position4_out, d_all, b_img, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     if (rc == JPT_OK && (e = hipMemcpy(normal4_out, d_all + b_img, b_img, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_bake_finish(int device_id, int32_t width, int32_t height, const jpt_bake_finish_params* params, const float* mean4,
+                          const float* position4, const float* normal4, float* out)
+{
+    if (!mean4 || !position4 || !normal4 || !out) {
+        g_debug_error = "jpt_debug_bake_finish: null argument";
+        return JPT_E_INVALID;
+    }
+    LightmapParams prm;
+    if (params) {
+        prm.passes = params->passes;
+        prm.normal_power_log2 = params->normal_power_log2;
+        prm.dilate = params->dilate;
+        prm.sigma_distance = params->sigma_distance;
+        prm.sigma_plane = params->sigma_plane;
+        prm.sigma_color = params->sigma_color;
+    }
+    int rc = check_bake_finish_params("jpt_debug_bake_finish", prm, g_debug_error);
+    if (rc == JPT_OK) rc = check_bake_size("jpt_debug_bake_finish", width, height, g_debug_error);
+    const size_t n = (size_t)width * (size_t)height, b_img = n * sizeof(float4);
+    if (rc == JPT_OK) rc = check_bake_texels("jpt_debug_bake_finish", position4, normal4, n, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        lightmap_finish_host(width, height, prm, reinterpret_cast<const float4*>(mean4), reinterpret_cast<const float4*>(position4),
+                             reinterpret_cast<const float4*>(normal4), reinterpret_cast<float4*>(out));
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    float4* buf = nullptr;   // mean, position4, normal4, xg, ng, ping, pong
+    if ((e = hipMalloc((void**)&buf, 7 * b_img)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    if ((e = hipMemcpy(buf, mean4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(buf + n, position4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(buf + 2 * n, normal4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        const float4* result = launch_lightmap_finish(nullptr, prm, width, height, buf, 1.0f, buf + n, buf + 2 * n, buf + 3 * n, buf + 4 * n, buf + 5 * n, buf + 6 * n);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "bake finish kernels");
+        if (rc == JPT_OK && (e = hipMemcpy(out, result, b_img, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    }
+    (void)hipFree(buf);
     return rc;
 }
 

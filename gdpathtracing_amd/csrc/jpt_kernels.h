@@ -399,6 +399,15 @@ void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& c
 void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int height, const float4* sums, float frame_count,
                    const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr);
 
+// jpt_bake_finish (jpt_kernels_lightmap.hip; the arithmetic: jpt_lightmap.h).  The checks of jpt_set_bake_finish_params, also run by
+// jpt_debug_bake_finish; and the whole transform on `stream`: the guides (xg, ng) from the bake images, `passes` filter passes from
+// the sums and frame_count, `dilate` dilation passes -- ping-pong between `ping` and `pong`; the one that holds the lightmap ((r, g,
+// b, coverage) per texel) is returned.  Every pointer is a device pointer of width * height elements; nothing else is written.
+struct LightmapParams;
+int check_bake_finish_params(const char* call, const LightmapParams& p, std::string& why);
+float4* launch_lightmap_finish(hipStream_t stream, const LightmapParams& prm, int width, int height, const float4* sums, float frame_count,
+                               const float4* position4, const float4* normal4, float4* xg, float4* ng, float4* ping, float4* pong);
+
 // jpt_query_rays / jpt_query_pixels (jpt_kernels_query.hip): n jpt_ray records walked over the arrays the wavefront kernels walk,
 // one lane per ray; closest: a jpt_ray_hit per ray into `hits` and, unless null, a byte per ray into `occluded`; any: the byte alone
 // (`hits` is not touched).  And the rays of n raster positions (x, y pairs) from the camera, as jpt_query_pixels forms them.  Every

@@ -161,11 +161,13 @@ int jpt::check_bake_surface(const char* call, const float* vertices, const float
 
 namespace {
 
-// the renders already queued read the old images: they finish first (every one of them ends with work on the context's stream)
+// the renders (and a jpt_bake_finish) already queued read the old images: they finish first (every one of them ends with work on the
+// context's stream); jpt_bake_finish's own images go with them
 int bake_wait(jpt_ctx* c)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->lightmap_release();   // (every caller goes on to write the images: a jpt_bake_finish of the old ones is no longer the lightmap)
     return JPT_OK;
 }
 

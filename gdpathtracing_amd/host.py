@@ -156,6 +156,24 @@ def debug_bake_raster(device_id, surface, uv2, transform12, width, height):
     return p, n
 
 
+def debug_bake_finish(device_id, mean4, position4, normal4, params=None, **fields):
+    """jpt_debug_bake_finish: the whole transform of jpt_bake_finish (guides, filter passes, dilation) on caller-made images, float32
+    [height, width, 4] each, mean4 taken as the mean itself -- the lightmap (r, g, b, coverage) float32 [height, width, 4].  params: a
+    capi.BakeFinishParams, or its fields by name.  device_id -1: the host's copy of the functions, in plain loops."""
+    p, n = _bake_images(position4, normal4)
+    m = np.ascontiguousarray(mean4, dtype=np.float32)
+    if m.shape != p.shape:
+        raise ValueError("mean4 is float32 [height, width, 4], the size of the texel images")
+    if params is None and fields:
+        params = capi.BakeFinishParams(**fields)
+    out = np.zeros(p.shape, np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_bake_finish(int(device_id), p.shape[1], p.shape[0], None if params is None else C.byref(params), _ptr(m), _ptr(p), _ptr(n), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_bake_finish failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
 def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
     """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
     [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
@@ -426,6 +444,26 @@ class Context:
         p, n = np.zeros((height, width, 4), np.float32), np.zeros((height, width, 4), np.float32)
         self._ck(self._lib.jpt_read_bake_texels(self.h, _ptr(p), _ptr(n)), "jpt_read_bake_texels")
         return p, n
+
+    # ---- finishing a baked lightmap (jpt_bake_finish)
+    def set_bake_finish_params(self, params: Optional[capi.BakeFinishParams] = None, **fields):
+        """jpt_set_bake_finish_params: a capi.BakeFinishParams, or its fields by name (passes, normal_power_log2, dilate,
+        sigma_distance, sigma_plane, sigma_color; the rest at the defaults); nothing: the defaults"""
+        if params is None and fields:
+            params = capi.BakeFinishParams(**fields)
+        self._ck(self._lib.jpt_set_bake_finish_params(self.h, None if params is None else C.byref(params)), "jpt_set_bake_finish_params")
+
+    def bake_finish(self):
+        """jpt_bake_finish: queue the chart-aware filter passes and the dilation over the accumulation of the bake renders queued so
+        far, guided by the texel images; the accumulation itself is not touched"""
+        self._ck(self._lib.jpt_bake_finish(self.h), "jpt_bake_finish")
+
+    def read_lightmap(self) -> np.ndarray:
+        """jpt_read_lightmap_f32: (r, g, b, coverage) float32 [height, width, 4]; coverage 1 a texel of a chart, 0.5 a dilated one, 0
+        an untouched one"""
+        out = np.zeros((max(self.height, 1), max(self.width, 1), 4), dtype=np.float32)   # (without a size the call answers before it writes)
+        self._ck(self._lib.jpt_read_lightmap_f32(self.h, _ptr(out)), "jpt_read_lightmap_f32")
+        return out
 
     def set_material_extensions(self, flags):
         """jpt_set_material_extensions: capi.MATERIAL_EXT_NONE (default) or capi.MATERIAL_EXT_TRANSMISSION (padding[0:2] of every

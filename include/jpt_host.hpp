@@ -834,6 +834,14 @@ class PathTracingCamera {
         check(ctx, jpt_bake_add_surface(ctx, &surface, uv2, transform12), "jpt_bake_add_surface");
     }
     void read_bake_texels(float* position4, float* normal4) { check(ctx, jpt_read_bake_texels(ctx, position4, normal4), "jpt_read_bake_texels"); }
+    // jpt_bake_finish and its parameters (nullptr: the defaults): the chart-aware filter and the dilation of the accumulated bake, on
+    // the device; read_lightmap: width * height * 4 floats (r, g, b, coverage -- 1 a texel of a chart, 0.5 a dilated one, 0 untouched)
+    void set_bake_finish_params(const jpt_bake_finish_params* params)
+    {
+        check(ctx, jpt_set_bake_finish_params(ctx, params), "jpt_set_bake_finish_params");
+    }
+    void bake_finish() { check(ctx, jpt_bake_finish(ctx), "jpt_bake_finish"); }
+    void read_lightmap(float* out) { check(ctx, jpt_read_lightmap_f32(ctx, out), "jpt_read_lightmap_f32"); }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
