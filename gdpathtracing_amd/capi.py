@@ -36,6 +36,7 @@ STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PR
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 CAMERA_PINHOLE, CAMERA_PROJECTIVE, CAMERA_EQUIRECT = 0, 1, 2
+PROBE_RADIANCE, PROBE_IRRADIANCE = 0, 1
 HIT_VALID, HIT_FRONT, HIT_BAD_RAY = 1, 2, 4
 BUF_TRI_GEOMETRY, BUF_TRI_DATA, BUF_MATERIALS, BUF_BVH_NODES, BUF_INSTANCES, BUF_TLAS_NODES, BUF_TRIANGLES, BUF_REACH_TRIANGLES, BUF_REACH_INSTANCES = range(9)
 
@@ -62,6 +63,8 @@ SYMBOLS = [
     "jpt_set_camera_model", "jpt_multi_set_camera_model", "jpt_debug_camera_rays",
     "jpt_set_bake_texels", "jpt_bake_begin", "jpt_bake_add_surface", "jpt_read_bake_texels", "jpt_multi_set_bake_texels",
     "jpt_debug_bake_rays", "jpt_debug_bake_raster",
+    "jpt_set_probes", "jpt_get_probe_image_size", "jpt_read_probes", "jpt_probe_project", "jpt_read_probe_sh_f32",
+    "jpt_debug_probe_rays", "jpt_debug_probe_basis", "jpt_debug_probe_project",
     "jpt_set_bake_finish_params", "jpt_bake_finish", "jpt_read_lightmap_f32", "jpt_debug_bake_finish",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
@@ -317,6 +320,15 @@ def lib():
         L.jpt_bake_finish.argtypes = [vp]
         L.jpt_read_lightmap_f32.argtypes = [vp, vp]
         L.jpt_debug_bake_finish.argtypes = [C.c_int, i32, i32, C.POINTER(BakeFinishParams), vp, vp, vp, vp]
+    if hasattr(L, "jpt_set_probes") or "JPT_LIB" not in os.environ:
+        L.jpt_set_probes.argtypes = [vp, vp, i32, i32, i32, i32]
+        L.jpt_get_probe_image_size.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        L.jpt_read_probes.argtypes = [vp, vp]
+        L.jpt_probe_project.argtypes = [vp, i32]
+        L.jpt_read_probe_sh_f32.argtypes = [vp, vp]
+        L.jpt_debug_probe_rays.argtypes = [C.c_int, vp, i32, i32, i32, i32, u32, vp, vp, vp]
+        L.jpt_debug_probe_basis.argtypes = [i32, i32, i32, vp]
+        L.jpt_debug_probe_project.argtypes = [C.c_int, vp, u32, i32, i32, i32, i32, vp, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

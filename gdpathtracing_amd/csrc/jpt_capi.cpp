@@ -1895,6 +1895,7 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
         c->d_dn_pong.release();
         c->d_dn_ldr.release();
     }
+    if (width != c->width || height != c->height) c->primary.sh_valid = false;   // (jpt_probe_project's coefficients are of the old size)
     if ((width != c->width || height != c->height) && c->d_lm_ping.p) {
         // jpt_bake_finish's images likewise
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2285,6 +2286,7 @@ int jpt_bake_finish(jpt_ctx* c)
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_finish: host-only context: it runs on the device");
     const PrimaryState& p = c->primary;
     if (!p.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_finish: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    if (p.has_probes()) return fail(c, JPT_E_STATE, "jpt_bake_finish: the lightmap is made of texel images, and the context holds probes (jpt_set_probes)");
     if (!c->params_set || p.bake_w != c->width || p.bake_h != c->height)
         return fail(c, JPT_E_STATE, "jpt_bake_finish: the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) +
                                         " texels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));

@@ -180,16 +180,27 @@ struct PrimaryState {
     DevBuf<uint32_t> d_bake_winner;
     DevBuf<char> d_bake_in;
     bool has_bake() const { return d_bake_nrm.p != nullptr; }
+    // jpt_set_probes: the context's, like the bake images; present probes make every render a probe render (probe_w x probe_h pixels).
+    // jpt_probe_project's own buffers: the quadrature table of (probe_tw, probe_th, table_flags) and the coefficients, 144 B per probe;
+    // sh_valid: they hold a projection of the probes and the size as they are now
+    DevBuf<float> d_probe_pos;
+    int32_t probe_n = 0, probe_tw = 0, probe_th = 0, probe_per_row = 0, probe_w = 0, probe_h = 0;
+    DevBuf<float> d_probe_table;
+    int32_t table_tw = 0, table_th = 0, table_flags = -1;
+    DevBuf<float4> d_probe_sh;
+    bool sh_valid = false;
+    bool has_probes() const { return d_probe_pos.p != nullptr; }
+    ProbeDev probe_dev() const { return make_probe_dev(d_probe_pos.p, probe_n, probe_tw, probe_th, probe_per_row); }
 };
-// Where the paths of one render of `c` start, once it is validated: the one of the four sources the context's state names, with the
-// others zeroed; kPinhole with DEBUG_STEPS, which ignores the lens, the model and the images as it ignores lighting.  In this order --
-// bake images: JPT_E_STATE when their size is not the render's, with a lens radius > 0, a model other than the pinhole or the
-// temporal pass; a lens radius > 0: JPT_E_STATE with the temporal pass, a basis that is not finite or a model other than the
+// Where the paths of one render of `c` start, once it is validated: the one of the five sources the context's state names, with the
+// others zeroed; kPinhole with DEBUG_STEPS, which ignores the lens, the model, the images and the probes as it ignores lighting.  In
+// this order -- bake images: JPT_E_STATE when their size is not the render's, with a lens radius > 0, a model other than the pinhole
+// or the temporal pass (probes beside them are ignored: refused or rendered as a bake); probes: the same four refusals; a lens radius > 0: JPT_E_STATE with the temporal pass, a basis that is not finite or a model other than the
 // pinhole; a model other than the pinhole: JPT_E_STATE with the temporal pass, EQUIRECT's basis or PROJECTIVE's ivp not finite.
 int resolve_primary(jpt_ctx* c, PrimaryRays& out);
 // The view of an entry point that takes it without rendering (`call`: jpt_denoise's guides, jpt_query_pixels' picking rays): the
 // context's model seen through its camera as both are now -- no render's refusals apply.  JPT_E_STATE while the context holds bake
-// images (`rays`: what the call's rays are, for the message).
+// images or probes (`rays`: what the call's rays are, for the message).
 int view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& out);
 // Blocking read-backs: device -> the context's pinned read buffer (h_read_pinned), on the context's stream (jpt_capi.cpp)
 int staged_read(jpt_ctx* c, const void* src, size_t bytes);
@@ -315,7 +326,7 @@ struct jpt_ctx {
     bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
 
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
-    PrimaryState primary;     // the lens, the camera model and the bake images (jpt_primary.cpp)
+    PrimaryState primary;     // the lens, the camera model, the bake images and the probes (jpt_primary.cpp)
 
     // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
     // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution

@@ -313,7 +313,7 @@ int env_sampling_debug(int device_id, const float* rgb, int32_t width, int32_t h
 }
 
 // The first rays of one frame under `p`, every pixel in raster order: the host loop with JPT_DEVICE_HOST_ONLY, else primary_rays_probe
-// on `device_id` -- one allocation for the bake images (host memory in `p`, uploaded here), the origins, the directions and the
+// on `device_id` -- one allocation for the bake images or the probe positions (host memory in `p`, uploaded here), the origins, the directions and the
 // valid bytes (valid_out may be null).  `what` names the probe in a device error.
 int primary_rays_debug(int device_id, const char* what, PrimaryRays p, const RefCamera& cam, int32_t width, int32_t height, uint32_t frame,
                        float* origins3_out, float* dirs3_out, uint8_t* valid_out)
@@ -340,11 +340,16 @@ int primary_rays_debug(int device_id, const char* what, PrimaryRays p, const Ref
     hipError_t e;
     if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
     const size_t b_img = p.kind == PrimaryRays::kBake ? n * sizeof(float4) : 0, b_ray = n * 3u * sizeof(float);
-    char* d_all = nullptr;   // position4, normal4 (16-byte images first), origins, directions, valid
-    if ((e = hipMalloc((void**)&d_all, 2 * b_img + 2 * b_ray + (valid_out ? n : 0))) != hipSuccess) return hip_fail(e, "hipMalloc");
-    float *d_o = reinterpret_cast<float*>(d_all + 2 * b_img), *d_d = reinterpret_cast<float*>(d_all + 2 * b_img + b_ray);
-    uint8_t* d_valid = valid_out ? reinterpret_cast<uint8_t*>(d_all + 2 * b_img + 2 * b_ray) : nullptr;
+    const size_t b_pos = p.kind == PrimaryRays::kProbe ? (size_t)p.probe.n * 3u * sizeof(float) : 0;   // (a probe render's positions, at the front: 4-byte data)
+    char* d_all = nullptr;   // position4, normal4 (16-byte images first) or the probe positions, origins, directions, valid
+    if ((e = hipMalloc((void**)&d_all, 2 * b_img + b_pos + 2 * b_ray + (valid_out ? n : 0))) != hipSuccess) return hip_fail(e, "hipMalloc");
+    float *d_o = reinterpret_cast<float*>(d_all + 2 * b_img + b_pos), *d_d = reinterpret_cast<float*>(d_all + 2 * b_img + b_pos + b_ray);
+    uint8_t* d_valid = valid_out ? reinterpret_cast<uint8_t*>(d_all + 2 * b_img + b_pos + 2 * b_ray) : nullptr;
     int rc = JPT_OK;
+    if (b_pos) {
+        if ((e = hipMemcpy(d_all, p.probe.position, b_pos, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+        p.probe.position = reinterpret_cast<const float*>(d_all);
+    }
     if (b_img) {
         if ((e = hipMemcpy(d_all, p.bake.position, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
         if (rc == JPT_OK && (e = hipMemcpy(d_all + b_img, p.bake.normal, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
@@ -597,6 +602,81 @@ int jpt_debug_bake_rays(int device_id, const float* position4, const float* norm
     p.bake.position = reinterpret_cast<const float4*>(position4);
     p.bake.normal = reinterpret_cast<const float4*>(normal4);
     return primary_rays_debug(device_id, "bake_rays_probe", p, RefCamera{}, width, height, frame_index, origins3_out, dirs3_out, valid_out);
+}
+
+int jpt_debug_probe_rays(int device_id, const float* position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row,
+                         uint32_t frame_index, float* origins3_out, float* dirs3_out, uint8_t* valid_out)
+{
+    if (!position3 || !origins3_out || !dirs3_out || !valid_out) {
+        g_debug_error = "jpt_debug_probe_rays: null argument";
+        return JPT_E_INVALID;
+    }
+    const int rc0 = check_probes("jpt_debug_probe_rays", position3, n_probes, tile_w, tile_h, probes_per_row, g_debug_error);
+    if (rc0 != JPT_OK) return rc0;
+    uint64_t w, h;
+    probe_image_size(n_probes, tile_w, tile_h, probes_per_row, w, h);
+    PrimaryRays p;   // (the positions are host memory here: primary_rays_debug uploads them for a device)
+    p.kind = PrimaryRays::kProbe;
+    p.probe = make_probe_dev(position3, n_probes, tile_w, tile_h, probes_per_row);
+    return primary_rays_debug(device_id, "probe_rays_probe", p, RefCamera{}, (int32_t)w, (int32_t)h, frame_index, origins3_out, dirs3_out, valid_out);
+}
+
+int jpt_debug_probe_basis(int32_t tile_w, int32_t tile_h, int32_t flags, float* table_out)
+{
+    if (!table_out) {
+        g_debug_error = "jpt_debug_probe_basis: null argument";
+        return JPT_E_INVALID;
+    }
+    if (flags != JPT_PROBE_RADIANCE && flags != JPT_PROBE_IRRADIANCE) {
+        g_debug_error = "jpt_debug_probe_basis: flags must be JPT_PROBE_RADIANCE or JPT_PROBE_IRRADIANCE";
+        return JPT_E_INVALID;
+    }
+    const int rc0 = check_probes("jpt_debug_probe_basis", nullptr, 1, tile_w, tile_h, 1, g_debug_error);
+    if (rc0 != JPT_OK) return rc0;
+    std::vector<float> table;
+    probe_basis_table(tile_w, tile_h, flags, table);
+    std::memcpy(table_out, table.data(), table.size() * sizeof(float));
+    return JPT_OK;
+}
+
+int jpt_debug_probe_project(int device_id, const float* accum4, uint32_t frame_count, int32_t n_probes, int32_t tile_w, int32_t tile_h,
+                            int32_t probes_per_row, const float* table, float* sh_out)
+{
+    if (!accum4 || !table || !sh_out) {
+        g_debug_error = "jpt_debug_probe_project: null argument";
+        return JPT_E_INVALID;
+    }
+    if (frame_count == 0) {
+        g_debug_error = "jpt_debug_probe_project: frame_count must be >= 1";
+        return JPT_E_INVALID;
+    }
+    int rc = check_probes("jpt_debug_probe_project", nullptr, n_probes, tile_w, tile_h, probes_per_row, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        probe_project_host(accum4, frame_count, n_probes, tile_w, tile_h, probes_per_row, table, sh_out);
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    uint64_t w, h;
+    probe_image_size(n_probes, tile_w, tile_h, probes_per_row, w, h);
+    const size_t b_img = (size_t)(w * h) * sizeof(float4), b_sh = (size_t)n_probes * 9 * sizeof(float4), b_tab = (size_t)tile_w * tile_h * 9 * sizeof(float);
+    char* d_all = nullptr;   // the accumulation image, the coefficients (16-byte data first), the table
+    if ((e = hipMalloc((void**)&d_all, b_img + b_sh + b_tab)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    if ((e = hipMemcpy(d_all, accum4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_all + b_img + b_sh, table, b_tab, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        launch_probe_project(nullptr, make_probe_dev(nullptr, n_probes, tile_w, tile_h, probes_per_row), reinterpret_cast<const float4*>(d_all), (float)frame_count,
+                             reinterpret_cast<const float*>(d_all + b_img + b_sh), reinterpret_cast<float4*>(d_all + b_img));
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "probe_project_kernel");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(sh_out, d_all + b_img, b_sh, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
 }
 
 int jpt_debug_bake_raster(int device_id, const jpt_surface* surface, const float* uv2, const float* transform12, int32_t width, int32_t height,

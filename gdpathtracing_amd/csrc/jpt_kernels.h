@@ -13,6 +13,7 @@
 #include "jpt_bake.h"
 #include "jpt_camera.h"
 #include "jpt_lens.h"
+#include "jpt_probe.h"
 #include "jpt_shade.h"
 #include "jpt_types.h"
 
@@ -235,17 +236,19 @@ struct Lighting {
 
 // Where the paths of one render start -- the whole answer, made once per render (resolve_primary, jpt_primary.cpp) and read by
 // everything that prepares or launches it.  The members `kind` does not use are zeroed: radius 0, kCamPinhole, null images.  Host side
-// only: the kernels take lens, cam_model and bake as they are.
+// only: the kernels take lens, cam_model, bake and probe as they are.
 struct PrimaryRays {
     // the pinhole; the thin lens (jpt_set_lens: the *_lens forms of the primary launch); a camera model other than the pinhole
-    // (jpt_set_camera_model: the *_cam forms); the texel images (jpt_set_bake_texels: the *_bake forms)
-    enum Kind { kPinhole, kLens, kCamModel, kBake } kind = kPinhole;
+    // (jpt_set_camera_model: the *_cam forms); the texel images (jpt_set_bake_texels: the *_bake forms); the probes (jpt_set_probes:
+    // the *_probe forms)
+    enum Kind { kPinhole, kLens, kCamModel, kBake, kProbe } kind = kPinhole;
     LensDev lens = {};
     CamModelDev cam_model = {};
     BakeDev bake = {};
+    ProbeDev probe = {};
     // The sky cull, the tiles' sky cells and the cull window apply: the rectangles are the pinhole's projection of the boxes -- from a
     // point of the aperture a pixel outside them may still see geometry, another model projects otherwise, a bake's paths start on
-    // the surfaces.  False: Wf2Render::cull stays off (n < 0) and sky_tiles null.
+    // the surfaces and a probe's at the probe.  False: Wf2Render::cull stays off (n < 0) and sky_tiles null.
     bool sky_cull() const { return kind == kPinhole; }
 };
 
@@ -268,6 +271,15 @@ int check_bake_texels(const char* call, const float* position4, const float* nor
 // than 2^24 triangles (JPT_E_LIMIT)
 int check_bake_surface(const char* call, const float* vertices, const float* normals, const int32_t* indices, int32_t n_vertices, int32_t n_indices,
                        const float* uv2, const float* transform12, std::string& why);
+
+// jpt_set_probes / jpt_probe_project (jpt_probe.h).  The checks of jpt_set_probes (jpt_primary.cpp), also run by the jpt_debug_probe_*
+// entry points: the tile and the counts, then (unless null) the positions.
+int check_probes(const char* call, const float* position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row, std::string& why);
+// the quadrature table of (tile_w, tile_h, flags): tile_w * tile_h * 9 floats, made in double (jpt_primary.cpp)
+void probe_basis_table(int32_t tile_w, int32_t tile_h, int32_t flags, std::vector<float>& out);
+// The projection (jpt_kernels_probe.hip), on `stream`: one wave per probe over the accumulation image (pd.per_row * pd.tile_w pixels
+// wide; pd.position is not read), `table` as above, 9 float4 per probe into `out`.  Every pointer is device memory.
+void launch_probe_project(hipStream_t stream, const ProbeDev& pd, const float4* accum, float frame_count, const float* table, float4* out);
 
 // The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
 // tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory

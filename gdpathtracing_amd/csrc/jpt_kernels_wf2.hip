@@ -805,6 +805,15 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #undef JPT_BAKE
+// ... and their probe forms (jpt_set_probes): wf2_primary_probe, wf2_primary_env_probe
+#define JPT_PROBE 1
+#define JPT_ENV 0
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#undef JPT_PROBE
 
 // the window of a render (local tiles): x0, y0, nx, ny
 struct TileWindow {
@@ -1077,6 +1086,10 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
             case PrimaryRays::kBake:
                 if (env) hipLaunchKernelGGL((wf2_primary_env_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.bake, counters);
                 else hipLaunchKernelGGL((wf2_primary_bake<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.bake, counters);
+                break;
+            case PrimaryRays::kProbe:
+                if (env) hipLaunchKernelGGL((wf2_primary_env_probe<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.probe, counters);
+                else hipLaunchKernelGGL((wf2_primary_probe<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.probe, counters);
                 break;
             case PrimaryRays::kPinhole:
                 if (env) hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);

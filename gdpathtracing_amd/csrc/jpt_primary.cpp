@@ -1,4 +1,4 @@
-// jpt_primary.cpp -- where a context's renders start their paths: the thin lens, the camera model and the bake images (PrimaryState,
+// jpt_primary.cpp -- where a context's renders start their paths: the thin lens, the camera model, the bake images and the probes (PrimaryState,
 // jpt_ctx.h), the one resolver that turns them into a render's PrimaryRays (jpt_kernels.h), the view of the entry points that take
 // one without rendering, and the C entries that set them.  Host C++: the kernels are jpt_kernels_bake.hip's and jpt_debug.hip's.
 #include "jpt_ctx.h"
@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "jpt_instance_math.h"
 
@@ -56,8 +57,9 @@ int jpt::make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out
     return JPT_OK;
 }
 
-// One decision, in this order: DEBUG_STEPS, the bake images, the lens, the model.  The sources exclude one another, and a refusal
-// names the first of them in that order: a bake render with a lens is refused as a bake and not for the lens's own reasons.
+// One decision, in this order: DEBUG_STEPS, the bake images, the probes, the lens, the model.  The sources exclude one another, and a
+// refusal names the first of them in that order: a bake render with a lens is refused as a bake and not for the lens's own reasons,
+// and probes beside bake images are refused (or rendered) as a bake.
 int jpt::resolve_primary(jpt_ctx* c, PrimaryRays& out)
 {
     const PrimaryState& p = c->primary;
@@ -75,6 +77,15 @@ int jpt::resolve_primary(jpt_ctx* c, PrimaryRays& out)
         out.kind = PrimaryRays::kBake;
         out.bake.position = p.d_bake_pos.p;
         out.bake.normal = p.d_bake_nrm.p;
+    } else if (p.has_probes()) {
+        if (p.probe_w != c->width || p.probe_h != c->height)
+            return fail(c, JPT_E_STATE, "the probe tiles make an image of " + std::to_string(p.probe_w) + " x " + std::to_string(p.probe_h) + " pixels but jpt_set_params says " +
+                                            std::to_string(c->width) + " x " + std::to_string(c->height) + ": a probe render has one path per tile cell (jpt_set_probes)");
+        if (lens) return fail(c, JPT_E_STATE, "a probe render has no lens: set the lens radius to 0 (jpt_set_lens) or free the probes (jpt_set_probes)");
+        if (model) return fail(c, JPT_E_STATE, "a probe render has no camera model: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or free the probes (jpt_set_probes)");
+        if (temporal) return fail(c, JPT_E_STATE, "temporal reprojection assumes a camera: set another denoising mode or free the probes (jpt_set_probes)");
+        out.kind = PrimaryRays::kProbe;
+        out.probe = p.probe_dev();
     } else if (lens) {
         if (temporal)
             return fail(c, JPT_E_STATE, "temporal reprojection assumes one centre of projection: set the lens radius to 0 (jpt_set_lens) or another denoising mode");
@@ -100,6 +111,7 @@ int jpt::view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& o
 {
     if (c->primary.has_bake())
         return fail(c, JPT_E_STATE, std::string(call) + ": " + rays + " are camera rays, and the context holds bake images (jpt_set_bake_texels)");
+    if (c->primary.has_probes()) return fail(c, JPT_E_STATE, std::string(call) + ": " + rays + " are camera rays, and the context holds probes (jpt_set_probes)");
     std::string why;
     const int rc = make_camera_model(c->primary.camera_model, c->camera, out, why);
     return rc == JPT_OK ? JPT_OK : fail(c, rc, why);
@@ -157,6 +169,109 @@ int jpt::check_bake_surface(const char* call, const float* vertices, const float
             return JPT_E_INVALID;
         }
     return JPT_OK;
+}
+
+// ---- the checks of jpt_set_probes, also run by the jpt_debug_probe_* entry points, and the quadrature table -------------------------
+
+int jpt::check_probes(const char* call, const float* position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row, std::string& why)
+{
+    const std::string who = std::string(call) + ": ";
+    if (tile_w < kProbeTileWMin || tile_w > kProbeTileWMax) {
+        why = who + "tile_w must be in [4, 64]";
+        return JPT_E_INVALID;
+    }
+    if (tile_h < kProbeTileHMin || tile_h > kProbeTileHMax) {
+        why = who + "tile_h must be in [2, 32]";
+        return JPT_E_INVALID;
+    }
+    if (tile_w * tile_h > kProbeMaxCells) {
+        why = who + "tile_w * tile_h must be at most 1024";
+        return JPT_E_INVALID;
+    }
+    if (n_probes < 1 || n_probes > kProbeMaxProbes) {
+        why = who + "n_probes must be in [1, 2^20]";
+        return JPT_E_LIMIT;
+    }
+    if (probes_per_row < 1) {
+        why = who + "probes_per_row must be >= 1";
+        return JPT_E_INVALID;
+    }
+    uint64_t w, h;
+    probe_image_size(n_probes, tile_w, tile_h, probes_per_row, w, h);
+    if (w > kProbeMaxPixels || w * h > kProbeMaxPixels) {
+        why = who + "the image of the tiles has more than 2^26 pixels";
+        return JPT_E_LIMIT;
+    }
+    if (position3)
+        for (size_t k = 0; k < 3 * (size_t)n_probes; k++)
+            if (!std::isfinite(position3[k])) {
+                why = who + "probe " + std::to_string(k / 3) + " has a non-finite position component";
+                return JPT_E_INVALID;
+            }
+    return JPT_OK;
+}
+
+// Cell means of the basis of jpt_probe.h: with z the polar coordinate (world y), r = sqrt(1 - z^2) and phi the map's azimuth the nine
+// functions are k0; k1 r sin; k1 z; k1 r cos; k2 r^2 sin 2phi / 2; k2 z r sin; k3 (3 z^2 - 1); k2 z r cos; k4 r^2 cos 2phi -- a product
+// of a mean over the cell's z interval and one over its phi interval, each an antiderivative's difference over the interval's length.
+void jpt::probe_basis_table(int32_t tile_w, int32_t tile_h, int32_t flags, std::vector<float>& out)
+{
+    const double pi = 3.14159265358979323846;
+    const double k0 = 0.28209479177387814, k1 = 0.4886025119029199, k2 = 1.0925484305920792, k3 = 0.31539156525252005, k4 = 0.5462742152960396;
+    const int cells = tile_w * tile_h;
+    std::vector<double> mz(tile_h), mz2(tile_h), mr(tile_h), mzr(tile_h), mr2(tile_h), ms(tile_w), mc(tile_w), ms2(tile_w), mc2(tile_w);
+    auto fr = [](double z) {
+        const double q = 1.0 - z * z, r = std::sqrt(q > 0.0 ? q : 0.0);
+        return 0.5 * (z * r + std::asin(z < -1.0 ? -1.0 : (z > 1.0 ? 1.0 : z)));
+    };
+    auto fzr = [](double z) {
+        const double q = 1.0 - z * z, qq = q > 0.0 ? q : 0.0;
+        return -(qq * std::sqrt(qq)) / 3.0;
+    };
+    for (int j = 0; j < tile_h; j++) {
+        const double z0 = 1.0 - 2.0 * (double)j / (double)tile_h, z1 = 1.0 - 2.0 * (double)(j + 1) / (double)tile_h, dz = z0 - z1;
+        mz[j] = (z0 * z0 / 2.0 - z1 * z1 / 2.0) / dz;
+        mz2[j] = (z0 * z0 * z0 / 3.0 - z1 * z1 * z1 / 3.0) / dz;
+        mr[j] = (fr(z0) - fr(z1)) / dz;
+        mzr[j] = (fzr(z0) - fzr(z1)) / dz;
+        mr2[j] = 1.0 - mz2[j];
+    }
+    for (int i = 0; i < tile_w; i++) {
+        const double p0 = ((double)i / (double)tile_w - 0.5) * 2.0 * pi, p1 = ((double)(i + 1) / (double)tile_w - 0.5) * 2.0 * pi, dp = p1 - p0;
+        ms[i] = (-std::cos(p1) - -std::cos(p0)) / dp;
+        mc[i] = (std::sin(p1) - std::sin(p0)) / dp;
+        ms2[i] = (-std::cos(2.0 * p1) / 2.0 - -std::cos(2.0 * p0) / 2.0) / dp;
+        mc2[i] = (std::sin(2.0 * p1) / 2.0 - std::sin(2.0 * p0) / 2.0) / dp;
+    }
+    std::vector<double> y((size_t)cells * 9);
+    double gram[9] = {};
+    const double w = 4.0 * pi / (double)cells;
+    for (int j = 0; j < tile_h; j++)
+        for (int i = 0; i < tile_w; i++) {
+            double* t = &y[((size_t)j * tile_w + i) * 9];
+            t[0] = k0;
+            t[1] = k1 * (mr[j] * ms[i]);
+            t[2] = k1 * mz[j];
+            t[3] = k1 * (mr[j] * mc[i]);
+            t[4] = k2 * (mr2[j] * (ms2[i] * 0.5));
+            t[5] = k2 * (mzr[j] * ms[i]);
+            t[6] = k3 * (3.0 * mz2[j] - 1.0);
+            t[7] = k2 * (mzr[j] * mc[i]);
+            t[8] = k4 * (mr2[j] * mc2[i]);
+        }
+    for (int c = 0; c < cells; c++)
+        for (int k = 0; k < 9; k++) gram[k] += w * (y[(size_t)c * 9 + k] * y[(size_t)c * 9 + k]);
+    const double band[3] = {pi, 2.0 * pi / 3.0, pi / 4.0};
+    out.resize((size_t)cells * 9);
+    for (int c = 0; c < cells; c++)
+        for (int k = 0; k < 9; k++) {
+            // A function whose cell means all vanish on this grid cannot be resolved by it, and its column is zero: Y6 with tile_h = 2
+            // (the mean of z^2 over either half is 1/3) and Y8 with tile_w = 4 (the mean of cos 2 phi over a quarter turn is 0) -- G_kk
+            // is then 0 or rounding noise (~ 1e-34) against 0.2 .. 1 for every column a grid resolves (kProbeGramMin, jpt_probe.h)
+            double v = gram[k] < kProbeGramMin ? 0.0 : w * y[(size_t)c * 9 + k] / gram[k];
+            if (flags & JPT_PROBE_IRRADIANCE) v = v * band[k == 0 ? 0 : (k < 4 ? 1 : 2)];
+            out[(size_t)c * 9 + k] = (float)v;
+        }
 }
 
 namespace {
@@ -317,6 +432,133 @@ int jpt_read_bake_texels(jpt_ctx* c, float* position4, float* normal4)
         if (rc != JPT_OK) return rc;
         std::memcpy(out[k], c->h_read_pinned.p, bytes);
     }
+    return JPT_OK;
+}
+
+// ---- light probes: the context's positions (jpt_probe.h) and their projection -------------------------------------------------------
+
+int jpt_set_probes(jpt_ctx* c, const float* position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row)
+{
+    if (!c) return JPT_E_INVALID;
+    const bool freeing = !position3 && n_probes == 0 && tile_w == 0 && tile_h == 0 && probes_per_row == 0;
+    if (!freeing) {
+        if (!position3) return fail(c, JPT_E_INVALID, "jpt_set_probes: position3 is given, or (NULL, 0, 0, 0, 0) frees the probes");
+        std::string why;
+        const int rc = check_probes("jpt_set_probes", position3, n_probes, tile_w, tile_h, probes_per_row, why);
+        if (rc != JPT_OK) return fail(c, rc, why);
+    }
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_probes: host-only context has no probes");
+    // the renders (and a jpt_probe_project) already queued read the old positions: they finish first
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    PrimaryState& p = c->primary;
+    p.sh_valid = false;
+    if (freeing) {
+        p.d_probe_pos.release();
+        p.d_probe_sh.release();
+        p.d_probe_table.release();
+        p.table_flags = -1;
+        p.probe_n = p.probe_tw = p.probe_th = p.probe_per_row = p.probe_w = p.probe_h = 0;
+        return JPT_OK;
+    }
+    const hipError_t e = p.d_probe_pos.resize(3 * (size_t)n_probes);
+    if (e != hipSuccess) {
+        p.probe_n = p.probe_tw = p.probe_th = p.probe_per_row = p.probe_w = p.probe_h = 0;
+        return hip_fail(c, e, "hipMalloc of the probe positions");
+    }
+    uint64_t w, h;
+    probe_image_size(n_probes, tile_w, tile_h, probes_per_row, w, h);
+    p.probe_n = n_probes;
+    p.probe_tw = tile_w;
+    p.probe_th = tile_h;
+    p.probe_per_row = probes_per_row;
+    p.probe_w = (int32_t)w;
+    p.probe_h = (int32_t)h;
+    const hipError_t ec = hipMemcpy(p.d_probe_pos.p, position3, 3 * (size_t)n_probes * sizeof(float), hipMemcpyHostToDevice);
+    if (ec != hipSuccess) {   // (no probes rather than probes at positions nobody wrote)
+        p.d_probe_pos.release();
+        p.probe_n = p.probe_tw = p.probe_th = p.probe_per_row = p.probe_w = p.probe_h = 0;
+        return hip_fail(c, ec, "hipMemcpy of the probe positions");
+    }
+    return JPT_OK;
+}
+
+int jpt_get_probe_image_size(jpt_ctx* c, int32_t* width, int32_t* height)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!width || !height) return fail(c, JPT_E_INVALID, "jpt_get_probe_image_size: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_get_probe_image_size: host-only context has no probes");
+    if (!c->primary.has_probes()) return fail(c, JPT_E_STATE, "jpt_get_probe_image_size: no probes (jpt_set_probes first)");
+    *width = c->primary.probe_w;
+    *height = c->primary.probe_h;
+    return JPT_OK;
+}
+
+int jpt_read_probes(jpt_ctx* c, float* position3)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!position3) return fail(c, JPT_E_INVALID, "jpt_read_probes: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_probes: host-only context has no probes");
+    if (!c->primary.has_probes()) return fail(c, JPT_E_STATE, "jpt_read_probes: no probes (jpt_set_probes first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = 3 * (size_t)c->primary.probe_n * sizeof(float);
+    const int rc = staged_read(c, c->primary.d_probe_pos.p, bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(position3, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+int jpt_probe_project(jpt_ctx* c, int32_t flags)
+{
+    if (!c) return JPT_E_INVALID;
+    if (flags != JPT_PROBE_RADIANCE && flags != JPT_PROBE_IRRADIANCE) return fail(c, JPT_E_INVALID, "jpt_probe_project: flags must be JPT_PROBE_RADIANCE or JPT_PROBE_IRRADIANCE");
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_probe_project projects the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_probe_project: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_probe_project needs the whole image on one context (world == 1): the gathering context projects");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_probe_project: host-only context: it runs on the device");
+    PrimaryState& p = c->primary;
+    if (!p.has_probes()) return fail(c, JPT_E_STATE, "jpt_probe_project: no probes (jpt_set_probes first)");
+    if (!c->params_set || p.probe_w != c->width || p.probe_h != c->height)
+        return fail(c, JPT_E_STATE, "jpt_probe_project: the probe tiles make an image of " + std::to_string(p.probe_w) + " x " + std::to_string(p.probe_h) +
+                                        " pixels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_probe_project: no frame accumulated since the last reset");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (p.table_tw != p.probe_tw || p.table_th != p.probe_th || p.table_flags != flags || !p.d_probe_table.p) {
+        // (an earlier projection on the stream may still read the old table)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<float> table;
+        probe_basis_table(p.probe_tw, p.probe_th, flags, table);
+        p.table_flags = -1;
+        HIP_TRY(c, p.d_probe_table.resize(table.size()));
+        HIP_TRY(c, hipMemcpy(p.d_probe_table.p, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice));
+        p.table_tw = p.probe_tw;
+        p.table_th = p.probe_th;
+        p.table_flags = flags;
+    }
+    if (p.d_probe_sh.n != 9 * (size_t)p.probe_n || !p.d_probe_sh.p) {
+        p.sh_valid = false;
+        HIP_TRY(c, p.d_probe_sh.resize(9 * (size_t)p.probe_n));
+    }
+    // On the context's stream, as jpt_bake_finish: behind the accumulation of every render queued so far, and the accumulation of every
+    // later render waits for what it reads.
+    launch_probe_project(c->stream, p.probe_dev(), c->d_accum.p, (float)c->frame_count, p.d_probe_table.p, p.d_probe_sh.p);
+    HIP_TRY(c, hipGetLastError());
+    p.sh_valid = true;
+    return JPT_OK;
+}
+
+int jpt_read_probe_sh_f32(jpt_ctx* c, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_probe_sh_f32: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_probe_sh_f32: host-only context: jpt_probe_project runs on the device");
+    if (!c->primary.sh_valid) return fail(c, JPT_E_STATE, "jpt_read_probe_sh_f32: no jpt_probe_project of the current probes and size yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = 9 * (size_t)c->primary.probe_n * sizeof(float4);
+    const int rc = staged_read(c, c->primary.d_probe_sh.p, bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
     return JPT_OK;
 }
 

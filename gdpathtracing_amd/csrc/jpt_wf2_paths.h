@@ -1,7 +1,7 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
 // which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace
-// (and twice more with JPT_LENS defined, twice with JPT_CAMERA_MODEL and twice with JPT_BAKE, for the lens, camera-model and bake
-// forms of wf2_primary alone: see there):
+// (and twice more with JPT_LENS defined, twice with JPT_CAMERA_MODEL, twice with JPT_BAKE and twice with JPT_PROBE, for the lens,
+// camera-model, bake and probe forms of wf2_primary alone: see there):
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -87,7 +87,12 @@
 // (16 B) and starts the path with bake_ray (jpt_bake.h).  An invalid texel traces nothing: its path ends here with radiance 0 and
 // first-hit distance cam.far_, as a sky path of the default kernel ends in save_results, and is not counted as a ray.  No cull.
 //
-// launch_wf2_render takes one of these eight forms by the kind of the render's PrimaryRays (jpt_kernels.h) and its miss model.
+// JPT_PROBE defined (likewise): the forms wf2_primary_probe and wf2_primary_env_probe (jpt_set_probes) -- the probes (ProbeDev, by
+// value) where the sky cull was; at refill the lane divides its pixel into (probe, i, j) -- two v_mul_hi_u32 by reciprocals the host
+// made, the divisors being kernel arguments -- reads the probe's position (12 B) and starts the path with probe_ray (jpt_probe.h).  A
+// pixel of a tile without a probe traces nothing, like an invalid texel.  No cull.
+//
+// launch_wf2_render takes one of these ten forms by the kind of the render's PrimaryRays (jpt_kernels.h) and its miss model.
 #ifdef JPT_LENS
 #if JPT_ENV
 #define JPT_PRIMARY_NAME wf2_primary_env_lens
@@ -109,6 +114,13 @@
 #define JPT_PRIMARY_NAME wf2_primary_bake
 #endif
 #define JPT_PRIMARY_PARAM BakeDev bake
+#elif defined(JPT_PROBE)
+#if JPT_ENV
+#define JPT_PRIMARY_NAME wf2_primary_env_probe
+#else
+#define JPT_PRIMARY_NAME wf2_primary_probe
+#endif
+#define JPT_PRIMARY_PARAM ProbeDev probe
 #else
 #define JPT_PRIMARY_NAME JPT_ENV_NAME(wf2_primary)
 #define JPT_PRIMARY_PARAM SkyCull cull
@@ -227,6 +239,31 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
                         } else {
                             uint32_t sx, sy;
                             const Ray ray = bake_ray(bake.position[texel], bake_n, px, py, fp.frame_index + f, sx, sy);
+#elif defined(JPT_PROBE)
+                        uint32_t probe_q, probe_i, probe_j;
+                        if (!probe_cell(probe, px, py, probe_q, probe_i, probe_j)) {
+                            if (COUNT) cnt.rays--;   // (no ray: the count above is taken back)
+                            store_final(wb, fp.accum_mode, path, mk3(0.0f, 0.0f, 0.0f));
+                            if ((int)f == fp.depth_frame) wb.first_depth[slot] = cam.far_;
+                        } else {
+                            // (probe_ray, jpt_probe.h, taken apart)
+                            uint32_t sx, sy;
+                            float xi0, xi1;
+                            probe_draw(px, py, fp.frame_index + f, sx, sy, xi0, xi1);
+                            Ray ray;
+                            // (the tile's sides enter vector registers here, per refill: as loop invariants their float forms were
+                            // hoisted out of the persistent loop into registers of their own, which the walk then spilled)
+                            uint32_t tile_w = probe.tile_w(), tile_h = probe.tile_h();
+                            asm volatile("" : "+v"(tile_w), "+v"(tile_h));
+                            // (where the position's load stands decides what the TAIL instantiation spills: 92 scratch instructions this
+                            // way round and 97 the other without a map, 98 and 96 with one -- tests/test_probe_budgets.py holds both)
+#if JPT_ENV
+                            ray.d = probe_direction(probe_i, probe_j, tile_w, tile_h, xi0, xi1);
+                            ray.o = probe_position(probe, probe_q);
+#else
+                            ray.o = probe_position(probe, probe_q);
+                            ray.d = probe_direction(probe_i, probe_j, tile_w, tile_h, xi0, xi1);
+#endif
 #else
                         if (sky_culled(cull, px, py)) {
                             if (COUNT) {
@@ -292,7 +329,7 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
 #undef JPT_PRIMARY_PARAM
 #endif  // JPT_ENV < 2
 
-#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL) && !defined(JPT_BAKE)   // (everything below: once per miss model)
+#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL) && !defined(JPT_BAKE) && !defined(JPT_PROBE)   // (everything below: once per miss model)
 
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
@@ -914,7 +951,7 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 
 #endif  // JPT_ENV < 2
 
-#endif  // JPT_LENS, JPT_CAMERA_MODEL, JPT_BAKE
+#endif  // JPT_LENS, JPT_CAMERA_MODEL, JPT_BAKE, JPT_PROBE
 
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM

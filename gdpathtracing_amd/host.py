@@ -174,6 +174,52 @@ def debug_bake_finish(device_id, mean4, position4, normal4, params=None, **field
     return out
 
 
+def probe_image_size(n_probes, tile_w, tile_h, probes_per_row):
+    """(width, height) of the image n_probes tiles make, probes_per_row to a row (jpt_get_probe_image_size's rule)"""
+    return int(probes_per_row) * int(tile_w), -(-int(n_probes) // int(probes_per_row)) * int(tile_h)
+
+
+def debug_probe_rays(device_id, positions, tile_w, tile_h, probes_per_row, frame_index):
+    """jpt_debug_probe_rays: the first rays of a probe render's paths for every pixel of one frame -- (origins [height, width, 3], dirs
+    [height, width, 3]) float32 and valid [height, width] uint8 (a tile without a probe: zeros).  device_id -1: the host's copy."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    w, h = probe_image_size(max(len(pos), 1), max(int(tile_w), 1), max(int(tile_h), 1), max(int(probes_per_row), 1))
+    origins, dirs, valid = np.zeros((h, w, 3), np.float32), np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.uint8)
+    L = capi.lib()
+    rc = L.jpt_debug_probe_rays(int(device_id), _ptr(pos), len(pos), int(tile_w), int(tile_h), int(probes_per_row), int(frame_index), _ptr(origins), _ptr(dirs),
+                                _ptr(valid))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_probe_rays failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return origins, dirs, valid
+
+
+def debug_probe_basis(tile_w, tile_h, flags=capi.PROBE_RADIANCE):
+    """jpt_debug_probe_basis: the host's quadrature table of (tile_w, tile_h, flags), float32 [tile_h, tile_w, 9]"""
+    out = np.zeros((max(int(tile_h), 1), max(int(tile_w), 1), 9), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_probe_basis(int(tile_w), int(tile_h), int(flags), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_probe_basis failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
+def debug_probe_project(device_id, accum4, frame_count, n_probes, tile_w, tile_h, probes_per_row, table):
+    """jpt_debug_probe_project: the projection over a caller-made accumulation image (float32 [height, width, 4], the size the probes
+    make), frame count and table ([tile_h, tile_w, 9]) -- float32 [n_probes, 9, 4], (r, g, b, 0) per coefficient.  device_id -1: the
+    same sum in plain loops on the host."""
+    a = np.ascontiguousarray(accum4, dtype=np.float32)
+    t = np.ascontiguousarray(table, dtype=np.float32)
+    w, h = probe_image_size(n_probes, tile_w, tile_h, probes_per_row)
+    if a.shape != (h, w, 4) or t.size != int(tile_w) * int(tile_h) * 9:
+        raise ValueError("accum4 is float32 [%d, %d, 4] and the table [tile_h, tile_w, 9]" % (h, w))
+    out = np.zeros((int(n_probes), 9, 4), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_probe_project(int(device_id), _ptr(a), int(frame_count), int(n_probes), int(tile_w), int(tile_h), int(probes_per_row), _ptr(t), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_probe_project failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
 def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
     """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
     [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
@@ -220,6 +266,7 @@ class Context:
                 raise capi.JptError("jpt_create failed (%d): %s" % (rc, msg.decode() if msg else "?"))
             self.h = h
         self.width = self.height = 0
+        self._n_probes = 0   # what set_probes last gave the context: sizes read_probes / read_probe_sh
         self._keep = []
         if self._owned:
             _live_contexts.add(self)
@@ -463,6 +510,45 @@ class Context:
         an untouched one"""
         out = np.zeros((max(self.height, 1), max(self.width, 1), 4), dtype=np.float32)   # (without a size the call answers before it writes)
         self._ck(self._lib.jpt_read_lightmap_f32(self.h, _ptr(out)), "jpt_read_lightmap_f32")
+        return out
+
+    # ---- light probes (jpt_set_probes, jpt_probe_project)
+    def set_probes(self, positions, tile_w=0, tile_h=0, probes_per_row=0):
+        """jpt_set_probes: float32 [n, 3] world positions; while probes are present every render is a probe render, one tile_w x tile_h
+        sphere tile per probe, probes_per_row to a row (probe_image_size: the size for set_params).  None frees them.  Waits for the
+        renders already queued."""
+        if positions is None:
+            self._ck(self._lib.jpt_set_probes(self.h, None, 0, 0, 0, 0), "jpt_set_probes")
+            self._n_probes = 0
+            return
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        self._ck(self._lib.jpt_set_probes(self.h, _ptr(pos), len(pos), int(tile_w), int(tile_h), int(probes_per_row)), "jpt_set_probes")
+        self._n_probes = len(pos)
+
+    def probe_image_size(self):
+        """jpt_get_probe_image_size: (width, height) of the image the context's probes make"""
+        w, h = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.jpt_get_probe_image_size(self.h, C.byref(w), C.byref(h)), "jpt_get_probe_image_size")
+        return w.value, h.value
+
+    def read_probes(self, n_probes=None):
+        """jpt_read_probes: the positions the context holds, float32 [n, 3].  n_probes: the count the context holds, by default the one
+        this object's set_probes gave it (give it when the probes were set through the handle: the call writes that many)"""
+        n = self._n_probes if n_probes is None else int(n_probes)
+        out = np.zeros((max(n, 1), 3), np.float32)   # (without probes the call answers E_STATE before it writes)
+        self._ck(self._lib.jpt_read_probes(self.h, _ptr(out)), "jpt_read_probes")
+        return out
+
+    def probe_project(self, flags=capi.PROBE_RADIANCE):
+        """jpt_probe_project: queue the projection of every probe's tile of the accumulation to nine L2 SH coefficients per channel
+        (capi.PROBE_IRRADIANCE: convolved with the cosine lobe); the accumulation itself is not touched"""
+        self._ck(self._lib.jpt_probe_project(self.h, int(flags)), "jpt_probe_project")
+
+    def read_probe_sh(self, n_probes=None) -> np.ndarray:
+        """jpt_read_probe_sh_f32: float32 [n_probes, 9, 4], (r, g, b, 0) per coefficient; n_probes as in read_probes"""
+        n = self._n_probes if n_probes is None else int(n_probes)
+        out = np.zeros((max(n, 1), 9, 4), np.float32)
+        self._ck(self._lib.jpt_read_probe_sh_f32(self.h, _ptr(out)), "jpt_read_probe_sh_f32")
         return out
 
     def set_material_extensions(self, flags):

@@ -552,7 +552,7 @@ int jpt_set_camera_model(jpt_ctx *ctx, int32_t model);
  * jpt_bake_finish (below) filters and dilates the accumulated map on the device.
  * Out of scope: conservative coverage (a triangle that covers no texel centre leaves no texel), seam stitching across UV islands,
  * atlas packing, next-event estimation at the texel itself (direct light reaches a texel by its first ray alone, so small emitters
- * converge slowly), directional (SH) lightmaps and SH probes. */
+ * converge slowly), directional (SH) lightmaps.  (Light probes: jpt_set_probes, below.) */
 int jpt_set_bake_texels(jpt_ctx *ctx, const float *position4, const float *normal4, int32_t width, int32_t height);
 int jpt_bake_begin(jpt_ctx *ctx, int32_t width, int32_t height);
 int jpt_bake_add_surface(jpt_ctx *ctx, const jpt_surface *surface, const float *uv2, const float *transform12);
@@ -600,6 +600,60 @@ typedef struct jpt_bake_finish_params {
 int jpt_set_bake_finish_params(jpt_ctx *ctx, const jpt_bake_finish_params *params);   /* NULL: the defaults */
 int jpt_bake_finish(jpt_ctx *ctx);
 int jpt_read_lightmap_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: (r, g, b, coverage) */
+
+/* ---- light probes: a sphere tile per probe, projected to L2 spherical harmonics on the device (no reference counterpart; the probes
+ * of Godot's LightmapGI that light dynamic objects) ----
+ * With probes present every render is a PROBE render: the image holds one tile_w x tile_h tile per probe, side by side, and one render
+ * captures them all.  Probe p owns the tile whose top-left pixel is ((p % probes_per_row) * tile_w, (p / probes_per_row) * tile_h); the
+ * image is probes_per_row * tile_w wide and ceil(n_probes / probes_per_row) * tile_h high (jpt_get_probe_image_size) -- the size to
+ * give jpt_set_params.  A pixel of a tile with index >= n_probes has no path: radiance 0, first-hit distance far, no ray counted, like
+ * an invalid bake texel.  Nothing downstream of ray generation knows: both kernels, the environment map and both sampling modes,
+ * emitter sampling, glass, the partition, jpt_multi (jpt_set_probes on every rank's jpt_multi_ctx), the read-backs, jpt_display and
+ * jpt_meter work on a probe render as on a picture.
+ * The ray of cell (i, j) of a tile, frame f (pinned; gdpathtracing_amd/csrc/jpt_probe.h; tests/np_probe.py): the
+ * seeds and the jitter draw of a camera ray, taken and discarded; (xi0, xi1) from one pcg2d round of a copy of the seeds hashed with
+ * (0x510e527f, 0x9b05688c);
+ *     u = (i + xi0) / tile_w, v = (j + xi1) / tile_h, phi = (u - 0.5) * 6.2831853, z = 1 - 2 v, r = sqrt(1 - z z),
+ *     d = (r sin phi, z, r cos phi)   in world axes, not renormalised;   o = the probe's position, no offset.
+ * This is the cylindrical equal-area map: every cell subtends 4 pi / (tile_w * tile_h).  The polar axis is world +Y, row 0 is the up
+ * pole and the centre column is +Z: the orientation of JPT_CAMERA_EQUIRECT with an identity basis.
+ * Limits: tile_w in 4..64, tile_h in 2..32, tile_w * tile_h <= 1024, probes_per_row >= 1, a non-finite position: JPT_E_INVALID;
+ * n_probes in 1..2^20 and at most 2^26 pixels of image: JPT_E_LIMIT; host-only contexts: JPT_E_DEVICE after these checks.
+ * jpt_set_probes WAITS for the renders the context has queued, as jpt_set_bake_texels does; (NULL, 0, 0, 0, 0) frees the probes, after
+ * which a render is bit for bit that of a context that never held any.  The positions belong to the context: they survive scene
+ * changes, and jpt_scene_share does not copy them.  jpt_read_probes returns them (n_probes * 3 floats).
+ * The render calls return JPT_E_STATE, with a message, while probes are present and their image size is not jpt_set_params' width x
+ * height, the lens radius is > 0, the camera model is not JPT_CAMERA_PINHOLE or the denoising mode is JPT_DENOISE_TEMPORAL; with bake
+ * images also present the render is a bake render (and refused as one).  jpt_set_debug_steps ignores the probes.  jpt_denoise,
+ * jpt_query_pixels and jpt_bake_finish return JPT_E_STATE while probes are present: their rays are camera rays or texel images.
+ *
+ * jpt_probe_project reduces every tile of the accumulation to nine SH coefficients per colour channel, as an explicit call like
+ * jpt_bake_finish: enqueued on the context's stream, it READS the accumulation and the frame count and writes only its own buffer, 144
+ * B per probe, which jpt_read_probe_sh_f32 returns: n_probes * 9 * 4 floats, (r, g, b, 0) per coefficient.
+ * Basis: real SH of bands 0..2 in the order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2), in the frame of the map
+ * (X, Y, Z) = (d.z, d.x, d.y) -- Z the polar axis (world +Y), the azimuth from X (world +Z) towards Y (world +X):
+ *     Y0 = 0.2820948          Y1 = 0.4886025 d.x       Y2 = 0.4886025 d.y                 Y3 = 0.4886025 d.z
+ *     Y4 = 1.0925484 d.z d.x  Y5 = 1.0925484 d.x d.y   Y6 = 0.3153916 (3 d.y d.y - 1)     Y7 = 1.0925484 d.z d.y
+ *     Y8 = 0.5462742 (d.z d.z - d.x d.x)
+ * Quadrature: a table made on the host in double -- the MEAN of each basis function over each cell (closed forms), times the cell's
+ * solid angle, divided by the Gram diagonal sum_cells w mean_k^2 (the off-diagonal terms vanish by symmetry), so constant radiance
+ * gives exactly zero above coefficient 0 and any band-limited radiance is recovered exactly from its cell means.  A function whose
+ * cell means all vanish on the grid cannot be resolved and its coefficient is 0: Y6 with tile_h = 2, Y8 with tile_w = 4.  With
+ * JPT_PROBE_IRRADIANCE band l is multiplied by pi, 2 pi / 3, pi / 4: the coefficients of the irradiance as a function of the normal.
+ * The sum is pinned: mean = accum.rgb / frame_count; one wave per probe, lane l adds mean * t (a multiply, then an add) for the cells
+ * l, l + 64, ... in raster order into accumulators starting at +0; six butterfly steps v + v[lane ^ s], s = 32 .. 1.
+ * JPT_E_STATE, with a message naming the call: no probes; their image size is not jpt_set_params'; no frame accumulated since the
+ * last reset; a denoising mode other than JPT_DENOISE_PROGRESSIVE; DEBUG_STEPS mode; a screen partition (the gathering context
+ * projects, as with jpt_display).  jpt_read_probe_sh_f32 before a jpt_probe_project of the current probes and size: JPT_E_STATE.
+ * Unknown flags: JPT_E_INVALID.  There is no jpt_multi_* form.
+ * Out of scope: directional (per-texel SH) lightmaps, probe placement and detection of probes inside geometry (jpt_query_rays answers
+ * that), band 3 and above, octahedral or cube tiles, half-float output. */
+enum { JPT_PROBE_RADIANCE = 0, JPT_PROBE_IRRADIANCE = 1 };
+int jpt_set_probes(jpt_ctx *ctx, const float *position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row);
+int jpt_get_probe_image_size(jpt_ctx *ctx, int32_t *width, int32_t *height);
+int jpt_read_probes(jpt_ctx *ctx, float *position3);       /* what the context holds: n_probes * 3 floats */
+int jpt_probe_project(jpt_ctx *ctx, int32_t flags);
+int jpt_read_probe_sh_f32(jpt_ctx *ctx, float *out);       /* n_probes * 9 * 4 floats: (r, g, b, 0) per coefficient */
 
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
@@ -1068,6 +1122,20 @@ int jpt_debug_bake_raster(int device_id, const jpt_surface *surface, const float
  * jpt_bake_finish launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host, in plain loops. */
 int jpt_debug_bake_finish(int device_id, int32_t width, int32_t height, const jpt_bake_finish_params *params,
                           const float *mean4, const float *position4, const float *normal4, float *out);
+/* The first rays of a probe render's paths (jpt_set_probes) for every pixel of frame frame_index of the image the probes make (width
+ * = probes_per_row * tile_w, height = ceil(n_probes / probes_per_row) * tile_h): origins3_out / dirs3_out [3 (y * width + x) ..] and
+ * valid_out[y * width + x] = 1, or zeros and 0 for a pixel of a tile without a probe.  The arguments are checked as jpt_set_probes
+ * checks them.  device_id >= 0: the function the kernels inline, on that device; JPT_DEVICE_HOST_ONLY: the same, compiled for the host. */
+int jpt_debug_probe_rays(int device_id, const float *position3, int32_t n_probes, int32_t tile_w, int32_t tile_h,
+                         int32_t probes_per_row, uint32_t frame_index, float *origins3_out, float *dirs3_out, uint8_t *valid_out);
+/* The quadrature table jpt_probe_project makes on the host for (tile_w, tile_h, flags): tile_w * tile_h * 9 floats, cell-major
+ * (c = j * tile_w + i), the nine coefficients of a cell together. */
+int jpt_debug_probe_basis(int32_t tile_w, int32_t tile_h, int32_t flags, float *table_out);
+/* The projection of jpt_probe_project over a caller-made accumulation image (4 floats per pixel, the size the probes make), frame
+ * count (>= 1) and table: sh_out = n_probes * 9 * 4 floats.  device_id >= 0: the kernel jpt_probe_project launches, on that device;
+ * JPT_DEVICE_HOST_ONLY: the same sum in plain loops on the host. */
+int jpt_debug_probe_project(int device_id, const float *accum4, uint32_t frame_count, int32_t n_probes, int32_t tile_w, int32_t tile_h,
+                            int32_t probes_per_row, const float *table, float *sh_out);
 /* The lens step alone, on the host, from caller-made randoms: for pinhole ray (origins3[3 i ..], dirs3[3 i ..]) and (xi2[2 i], xi2[2
  * i + 1]) the ray the lens of camera160 sends out (origins3_out, dirs3_out; either input ray kept when it does not point forward).
  * basis9_out (may be NULL): f, r, u.  The radius and the focus are taken as they are; a basis that is not finite is still returned,

@@ -842,6 +842,18 @@ class PathTracingCamera {
     }
     void bake_finish() { check(ctx, jpt_bake_finish(ctx), "jpt_bake_finish"); }
     void read_lightmap(float* out) { check(ctx, jpt_read_lightmap_f32(ctx, out), "jpt_read_lightmap_f32"); }
+    // Light probes (LightmapGI's probes for dynamic objects): with probes present every render is a probe render -- one tile_w x
+    // tile_h sphere tile per probe, probes_per_row to a row; probe_image_size: the size for set_params.  (nullptr, 0, 0, 0, 0) frees
+    // them.  probe_project reduces every tile of the accumulation to nine L2 SH coefficients per channel on the device (flags:
+    // JPT_PROBE_RADIANCE or JPT_PROBE_IRRADIANCE); read_probe_sh: n_probes * 9 * 4 floats, (r, g, b, 0) per coefficient.
+    void set_probes(const float* position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row)
+    {
+        check(ctx, jpt_set_probes(ctx, position3, n_probes, tile_w, tile_h, probes_per_row), "jpt_set_probes");
+    }
+    void probe_image_size(int32_t* w, int32_t* h) { check(ctx, jpt_get_probe_image_size(ctx, w, h), "jpt_get_probe_image_size"); }
+    void read_probes(float* position3) { check(ctx, jpt_read_probes(ctx, position3), "jpt_read_probes"); }
+    void probe_project(int32_t flags) { check(ctx, jpt_probe_project(ctx, flags), "jpt_probe_project"); }
+    void read_probe_sh(float* out) { check(ctx, jpt_read_probe_sh_f32(ctx, out), "jpt_read_probe_sh_f32"); }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
