@@ -65,6 +65,9 @@ SYMBOLS = [
     "jpt_debug_bake_rays", "jpt_debug_bake_raster",
     "jpt_set_probes", "jpt_get_probe_image_size", "jpt_read_probes", "jpt_probe_project", "jpt_read_probe_sh_f32",
     "jpt_debug_probe_rays", "jpt_debug_probe_basis", "jpt_debug_probe_project",
+    "jpt_set_reflection_probes", "jpt_get_reflection_image_size", "jpt_read_reflection_probes", "jpt_set_reflection_params", "jpt_reflection_prefilter",
+    "jpt_get_reflection_chain_size", "jpt_read_reflection_f32", "jpt_get_reflection_timing",
+    "jpt_debug_cube_rays", "jpt_debug_reflection_samples", "jpt_debug_reflection_prefilter",
     "jpt_set_bake_finish_params", "jpt_bake_finish", "jpt_read_lightmap_f32", "jpt_debug_bake_finish",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
@@ -97,6 +100,14 @@ class BakeFinishParams(C.Structure):
 
     def __init__(self, passes=3, normal_power_log2=4, dilate=4, sigma_distance=4.0, sigma_plane=1.0, sigma_color=4.0):
         super().__init__(passes, normal_power_log2, dilate, sigma_distance, sigma_plane, sigma_color)
+
+
+class ReflectionParams(C.Structure):
+    """jpt_reflection_params; the defaults are the library's (n_levels 0: every level down to 1 x 1)"""
+    _fields_ = [("n_levels", C.c_int32), ("samples", C.c_int32)]
+
+    def __init__(self, n_levels=0, samples=64):
+        super().__init__(n_levels, samples)
 
 
 class DisplayParams(C.Structure):
@@ -329,6 +340,18 @@ def lib():
         L.jpt_debug_probe_rays.argtypes = [C.c_int, vp, i32, i32, i32, i32, u32, vp, vp, vp]
         L.jpt_debug_probe_basis.argtypes = [i32, i32, i32, vp]
         L.jpt_debug_probe_project.argtypes = [C.c_int, vp, u32, i32, i32, i32, i32, vp, vp]
+    if hasattr(L, "jpt_set_reflection_probes") or "JPT_LIB" not in os.environ:
+        L.jpt_set_reflection_probes.argtypes = [vp, vp, i32, i32, i32]
+        L.jpt_get_reflection_image_size.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        L.jpt_read_reflection_probes.argtypes = [vp, vp]
+        L.jpt_set_reflection_params.argtypes = [vp, C.POINTER(ReflectionParams)]
+        L.jpt_reflection_prefilter.argtypes = [vp]
+        L.jpt_get_reflection_chain_size.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(C.c_uint64)]
+        L.jpt_read_reflection_f32.argtypes = [vp, i32, vp]
+        L.jpt_get_reflection_timing.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.jpt_debug_cube_rays.argtypes = [C.c_int, vp, i32, i32, i32, u32, vp]
+        L.jpt_debug_reflection_samples.argtypes = [i32, i32, i32, i32, vp, vp]
+        L.jpt_debug_reflection_prefilter.argtypes = [C.c_int, vp, u32, i32, i32, i32, C.POINTER(ReflectionParams), i32, vp]
     if hasattr(L, "jpt_denoise") or "JPT_LIB" not in os.environ:
         L.jpt_set_denoise_params.argtypes = [vp, C.POINTER(DenoiseParams)]
         L.jpt_denoise.argtypes = [vp]

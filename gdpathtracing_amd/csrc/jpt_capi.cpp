@@ -1083,6 +1083,7 @@ void jpt_destroy(jpt_ctx* c)
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->trace_events) (void)hipEventDestroy(e);
     if (c->ev_readback) (void)hipEventDestroy(c->ev_readback);
+    for (hipEvent_t e : c->primary.refl_ev) if (e) (void)hipEventDestroy(e);
     if (c->refit_stream) { (void)hipStreamSynchronize(c->refit_stream); (void)hipStreamDestroy(c->refit_stream); }
     for (hipEvent_t e : c->ev_set_retired) if (e) (void)hipEventDestroy(e);
     if (c->ev_refit_done) (void)hipEventDestroy(c->ev_refit_done);
@@ -1896,6 +1897,7 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
         c->d_dn_ldr.release();
     }
     if (width != c->width || height != c->height) c->primary.sh_valid = false;   // (jpt_probe_project's coefficients are of the old size)
+    if (width != c->width || height != c->height) c->primary.refl_valid = false;   // (jpt_reflection_prefilter's chain likewise)
     if ((width != c->width || height != c->height) && c->d_lm_ping.p) {
         // jpt_bake_finish's images likewise
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2287,6 +2289,8 @@ int jpt_bake_finish(jpt_ctx* c)
     const PrimaryState& p = c->primary;
     if (!p.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_finish: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
     if (p.has_probes()) return fail(c, JPT_E_STATE, "jpt_bake_finish: the lightmap is made of texel images, and the context holds probes (jpt_set_probes)");
+    if (p.has_cubes())
+        return fail(c, JPT_E_STATE, "jpt_bake_finish: the lightmap is made of texel images, and the context holds reflection probes (jpt_set_reflection_probes)");
     if (!c->params_set || p.bake_w != c->width || p.bake_h != c->height)
         return fail(c, JPT_E_STATE, "jpt_bake_finish: the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) +
                                         " texels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));

@@ -191,16 +191,37 @@ struct PrimaryState {
     bool sh_valid = false;
     bool has_probes() const { return d_probe_pos.p != nullptr; }
     ProbeDev probe_dev() const { return make_probe_dev(d_probe_pos.p, probe_n, probe_tw, probe_th, probe_per_row); }
+    // jpt_set_reflection_probes: the context's, like the probes; present reflection probes make every render a cube render (cube_w x
+    // cube_h pixels).  jpt_set_reflection_params: the context's (refl_levels 0: every level down to 1 x 1).  jpt_reflection_prefilter's
+    // own buffers: the sample tables of (table_face, table_levels, table_samples), the source chain and the output chain (jpt_reflection.h);
+    // refl_valid: the output chain holds refl_made levels of the probes and the size as they are now.  refl_ev: three events around the
+    // two steps of the last jpt_reflection_prefilter under jpt_set_kernel_timing (refl_timed), made at the first such call.
+    DevBuf<float> d_cube_pos;
+    int32_t cube_n = 0, cube_face = 0, cube_per_row = 0, cube_w = 0, cube_h = 0;
+    int32_t refl_levels = 0, refl_samples = kReflSamplesDefault;
+    DevBuf<float4> d_refl_table;
+    DevBuf<uint8_t> d_refl_lvl;
+    uint32_t refl_count[kReflLevelsMax] = {};
+    int32_t table_face = 0, table_levels = 0, table_samples = 0;
+    DevBuf<float4> d_refl_chain, d_refl_out;
+    int32_t refl_made = 0;
+    bool refl_valid = false;
+    hipEvent_t refl_ev[3] = {nullptr, nullptr, nullptr};
+    bool refl_timed = false;
+    bool has_cubes() const { return d_cube_pos.p != nullptr; }
+    CubeDev cube_dev() const { return make_cube_dev(d_cube_pos.p, cube_n, cube_face, cube_per_row); }
+    // the levels a jpt_reflection_prefilter of the probes makes now
+    int32_t refl_levels_now() const { return refl_levels ? refl_levels : cube_log2(cube_face) + 1; }
 };
-// Where the paths of one render of `c` start, once it is validated: the one of the five sources the context's state names, with the
+// Where the paths of one render of `c` start, once it is validated: the one of the six sources the context's state names, with the
 // others zeroed; kPinhole with DEBUG_STEPS, which ignores the lens, the model, the images and the probes as it ignores lighting.  In
 // this order -- bake images: JPT_E_STATE when their size is not the render's, with a lens radius > 0, a model other than the pinhole
-// or the temporal pass (probes beside them are ignored: refused or rendered as a bake); probes: the same four refusals; a lens radius > 0: JPT_E_STATE with the temporal pass, a basis that is not finite or a model other than the
+// or the temporal pass (probes beside them are ignored: refused or rendered as a bake); reflection probes: JPT_E_STATE beside bake images or probes, then the same four refusals; probes: the same four refusals; a lens radius > 0: JPT_E_STATE with the temporal pass, a basis that is not finite or a model other than the
 // pinhole; a model other than the pinhole: JPT_E_STATE with the temporal pass, EQUIRECT's basis or PROJECTIVE's ivp not finite.
 int resolve_primary(jpt_ctx* c, PrimaryRays& out);
 // The view of an entry point that takes it without rendering (`call`: jpt_denoise's guides, jpt_query_pixels' picking rays): the
 // context's model seen through its camera as both are now -- no render's refusals apply.  JPT_E_STATE while the context holds bake
-// images or probes (`rays`: what the call's rays are, for the message).
+// images, probes or reflection probes (`rays`: what the call's rays are, for the message).
 int view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& out);
 // Blocking read-backs: device -> the context's pinned read buffer (h_read_pinned), on the context's stream (jpt_capi.cpp)
 int staged_read(jpt_ctx* c, const void* src, size_t bytes);
@@ -326,7 +347,7 @@ struct jpt_ctx {
     bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
 
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
-    PrimaryState primary;     // the lens, the camera model, the bake images and the probes (jpt_primary.cpp)
+    PrimaryState primary;     // the lens, the camera model, the bake images, the probes and the reflection probes (jpt_primary.cpp)
 
     // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
     // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution

@@ -141,7 +141,7 @@ __global__ void dielectric_probe(const float* __restrict__ normals3, const float
     event_out[i] = (uint8_t)ev;
 }
 
-// jpt_debug_lens_rays / _camera_rays / _bake_rays: the first rays of a render under `p` (first_ray, jpt_primary_ray.h), one pixel per
+// jpt_debug_lens_rays / _camera_rays / _bake_rays / _probe_rays / _cube_rays: the first rays of a render under `p` (first_ray, jpt_primary_ray.h), one pixel per
 // thread; `valid` may be null
 __global__ void primary_rays_probe(PrimaryRays p, RefCamera cam, int width, int height, uint32_t frame, float* __restrict__ origins_out,
                                    float* __restrict__ dirs_out, uint8_t* __restrict__ valid)
@@ -340,13 +340,17 @@ int primary_rays_debug(int device_id, const char* what, PrimaryRays p, const Ref
     hipError_t e;
     if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
     const size_t b_img = p.kind == PrimaryRays::kBake ? n * sizeof(float4) : 0, b_ray = n * 3u * sizeof(float);
-    const size_t b_pos = p.kind == PrimaryRays::kProbe ? (size_t)p.probe.n * 3u * sizeof(float) : 0;   // (a probe render's positions, at the front: 4-byte data)
+    // (a probe or cube render's positions, at the front: 4-byte data)
+    const size_t b_pos = p.kind == PrimaryRays::kProbe ? (size_t)p.probe.n * 3u * sizeof(float) : (p.kind == PrimaryRays::kCube ? (size_t)p.cube.n * 3u * sizeof(float) : 0);
     char* d_all = nullptr;   // position4, normal4 (16-byte images first) or the probe positions, origins, directions, valid
     if ((e = hipMalloc((void**)&d_all, 2 * b_img + b_pos + 2 * b_ray + (valid_out ? n : 0))) != hipSuccess) return hip_fail(e, "hipMalloc");
     float *d_o = reinterpret_cast<float*>(d_all + 2 * b_img + b_pos), *d_d = reinterpret_cast<float*>(d_all + 2 * b_img + b_pos + b_ray);
     uint8_t* d_valid = valid_out ? reinterpret_cast<uint8_t*>(d_all + 2 * b_img + b_pos + 2 * b_ray) : nullptr;
     int rc = JPT_OK;
-    if (b_pos) {
+    if (b_pos && p.kind == PrimaryRays::kCube) {
+        if ((e = hipMemcpy(d_all, p.cube.position, b_pos, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+        p.cube.position = reinterpret_cast<const float*>(d_all);
+    } else if (b_pos) {
         if ((e = hipMemcpy(d_all, p.probe.position, b_pos, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
         p.probe.position = reinterpret_cast<const float*>(d_all);
     }
@@ -675,6 +679,122 @@ int jpt_debug_probe_project(int device_id, const float* accum4, uint32_t frame_c
         if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "probe_project_kernel");
     }
     if (rc == JPT_OK && (e = hipMemcpy(sh_out, d_all + b_img, b_sh, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_cube_rays(int device_id, const float* position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row, uint32_t frame_index,
+                        float* rays_out)
+{
+    if (!position3 || !rays_out) {
+        g_debug_error = "jpt_debug_cube_rays: null argument";
+        return JPT_E_INVALID;
+    }
+    const int rc0 = check_reflection_probes("jpt_debug_cube_rays", position3, n_probes, face_size, probes_per_row, g_debug_error);
+    if (rc0 != JPT_OK) return rc0;
+    uint64_t w, h;
+    cube_image_size(n_probes, face_size, probes_per_row, w, h);
+    PrimaryRays p;   // (the positions are host memory here: primary_rays_debug uploads them for a device)
+    p.kind = PrimaryRays::kCube;
+    p.cube = make_cube_dev(position3, n_probes, face_size, probes_per_row);
+    const size_t n = (size_t)(w * h);
+    std::vector<float> o(3 * n), d(3 * n);
+    const int rc = primary_rays_debug(device_id, "cube_rays_probe", p, RefCamera{}, (int32_t)w, (int32_t)h, frame_index, o.data(), d.data(), nullptr);
+    if (rc != JPT_OK) return rc;
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < 3; k++) {
+            rays_out[6 * i + k] = o[3 * i + k];
+            rays_out[6 * i + 3 + k] = d[3 * i + k];
+        }
+    return JPT_OK;
+}
+
+int jpt_debug_reflection_samples(int32_t face_size, int32_t n_levels, int32_t samples, int32_t level, float* table_out, uint8_t* src_level_out)
+{
+    if (!table_out || !src_level_out) {
+        g_debug_error = "jpt_debug_reflection_samples: null argument";
+        return JPT_E_INVALID;
+    }
+    int rc = check_reflection_probes("jpt_debug_reflection_samples", nullptr, 1, face_size, 1, g_debug_error);
+    if (rc == JPT_OK) rc = check_reflection_params("jpt_debug_reflection_samples", n_levels, samples, face_size, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    if (n_levels == 0) n_levels = cube_log2(face_size) + 1;
+    if (level < 1 || level >= n_levels) {
+        g_debug_error = "jpt_debug_reflection_samples: level must be in [1, n_levels): level 0 is a copy and has no samples";
+        return JPT_E_INVALID;
+    }
+    std::vector<float4> table;
+    std::vector<uint8_t> levels;
+    uint32_t count[kReflLevelsMax];
+    reflection_sample_table(face_size, n_levels, samples, table, levels, count);
+    std::memcpy(table_out, &table[(size_t)level * samples], (size_t)samples * sizeof(float4));
+    std::memcpy(src_level_out, &levels[(size_t)level * samples], (size_t)samples);
+    return JPT_OK;
+}
+
+int jpt_debug_reflection_prefilter(int device_id, const float* accum4, uint32_t frame_count, int32_t n_probes, int32_t face_size, int32_t probes_per_row,
+                                   const jpt_reflection_params* params, int32_t level, float* out)
+{
+    if (!accum4 || !out) {
+        g_debug_error = "jpt_debug_reflection_prefilter: null argument";
+        return JPT_E_INVALID;
+    }
+    if (frame_count == 0) {
+        g_debug_error = "jpt_debug_reflection_prefilter: frame_count must be >= 1";
+        return JPT_E_INVALID;
+    }
+    int rc = check_reflection_probes("jpt_debug_reflection_prefilter", nullptr, n_probes, face_size, probes_per_row, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    int32_t n_levels = params ? params->n_levels : 0;
+    const int32_t samples = params ? params->samples : kReflSamplesDefault;
+    rc = check_reflection_params("jpt_debug_reflection_prefilter", n_levels, samples, face_size, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    if (n_levels == 0) n_levels = cube_log2(face_size) + 1;
+    if (level < 0 || level >= n_levels) {
+        g_debug_error = "jpt_debug_reflection_prefilter: level must be in [0, n_levels)";
+        return JPT_E_INVALID;
+    }
+    ReflDev rd;
+    rd.n = (uint32_t)n_probes;
+    rd.per_row = (uint32_t)probes_per_row;
+    rd.shift = (uint32_t)cube_log2(face_size);
+    rd.n_levels = (uint32_t)n_levels;
+    rd.samples = (uint32_t)samples;
+    std::vector<float4> table;
+    std::vector<uint8_t> levels;
+    reflection_sample_table(face_size, n_levels, samples, table, levels, rd.count);
+    const size_t n_chain = (size_t)((uint64_t)rd.n * refl_probe_texels(rd.shift)), n_out = (size_t)refl_out_texels(rd.n, rd.shift, rd.n_levels);
+    const size_t s = (size_t)(face_size >> level), n_level = (size_t)n_probes * 6u * s * s, at = (size_t)refl_out_offset(rd.n, rd.shift, (uint32_t)level);
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        std::vector<float4> chain(n_chain), all(n_out);
+        reflection_prefilter_host(accum4, frame_count, rd, table.data(), levels.data(), chain.data(), all.data());
+        std::memcpy(out, &all[at], n_level * sizeof(float4));
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    uint64_t w, h;
+    cube_image_size(n_probes, face_size, probes_per_row, w, h);
+    const size_t b_img = (size_t)(w * h) * sizeof(float4), b_chain = n_chain * sizeof(float4), b_out = n_out * sizeof(float4), b_tab = table.size() * sizeof(float4);
+    char* d_all = nullptr;   // the accumulation image, the source chain, the output chain, the entries (16-byte data first), the level bytes
+    if ((e = hipMalloc((void**)&d_all, b_img + b_chain + b_out + b_tab + levels.size())) != hipSuccess) return hip_fail(e, "hipMalloc");
+    float4* d_chain = reinterpret_cast<float4*>(d_all + b_img);
+    float4* d_out = reinterpret_cast<float4*>(d_all + b_img + b_chain);
+    float4* d_tab = reinterpret_cast<float4*>(d_all + b_img + b_chain + b_out);
+    uint8_t* d_lvl = reinterpret_cast<uint8_t*>(d_all + b_img + b_chain + b_out + b_tab);
+    if ((e = hipMemcpy(d_all, accum4, b_img, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_tab, table.data(), b_tab, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(d_lvl, levels.data(), levels.size(), hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        launch_reflection_chain(nullptr, rd, reinterpret_cast<const float4*>(d_all), (float)frame_count, d_chain);
+        launch_reflection_prefilter(nullptr, rd, d_chain, d_tab, d_lvl, d_out);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "refl_prefilter_kernel");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(out, d_out + at, n_level * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
     return rc;
 }

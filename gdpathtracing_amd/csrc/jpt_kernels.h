@@ -14,6 +14,7 @@
 #include "jpt_camera.h"
 #include "jpt_lens.h"
 #include "jpt_probe.h"
+#include "jpt_reflection.h"
 #include "jpt_shade.h"
 #include "jpt_types.h"
 
@@ -236,19 +237,20 @@ struct Lighting {
 
 // Where the paths of one render start -- the whole answer, made once per render (resolve_primary, jpt_primary.cpp) and read by
 // everything that prepares or launches it.  The members `kind` does not use are zeroed: radius 0, kCamPinhole, null images.  Host side
-// only: the kernels take lens, cam_model, bake and probe as they are.
+// only: the kernels take lens, cam_model, bake, probe and cube as they are.
 struct PrimaryRays {
     // the pinhole; the thin lens (jpt_set_lens: the *_lens forms of the primary launch); a camera model other than the pinhole
     // (jpt_set_camera_model: the *_cam forms); the texel images (jpt_set_bake_texels: the *_bake forms); the probes (jpt_set_probes:
-    // the *_probe forms)
-    enum Kind { kPinhole, kLens, kCamModel, kBake, kProbe } kind = kPinhole;
+    // the *_probe forms); the reflection probes (jpt_set_reflection_probes: the *_cube forms)
+    enum Kind { kPinhole, kLens, kCamModel, kBake, kProbe, kCube } kind = kPinhole;
     LensDev lens = {};
     CamModelDev cam_model = {};
     BakeDev bake = {};
     ProbeDev probe = {};
+    CubeDev cube = {};
     // The sky cull, the tiles' sky cells and the cull window apply: the rectangles are the pinhole's projection of the boxes -- from a
     // point of the aperture a pixel outside them may still see geometry, another model projects otherwise, a bake's paths start on
-    // the surfaces and a probe's at the probe.  False: Wf2Render::cull stays off (n < 0) and sky_tiles null.
+    // the surfaces and a probe's (of either kind) at the probe.  False: Wf2Render::cull stays off (n < 0) and sky_tiles null.
     bool sky_cull() const { return kind == kPinhole; }
 };
 
@@ -280,6 +282,22 @@ void probe_basis_table(int32_t tile_w, int32_t tile_h, int32_t flags, std::vecto
 // The projection (jpt_kernels_probe.hip), on `stream`: one wave per probe over the accumulation image (pd.per_row * pd.tile_w pixels
 // wide; pd.position is not read), `table` as above, 9 float4 per probe into `out`.  Every pointer is device memory.
 void launch_probe_project(hipStream_t stream, const ProbeDev& pd, const float4* accum, float frame_count, const float* table, float4* out);
+
+// jpt_set_reflection_probes / jpt_reflection_prefilter (jpt_cube.h, jpt_reflection.h).  The checks of jpt_set_reflection_probes
+// (jpt_primary.cpp), also run by the jpt_debug_cube_rays / jpt_debug_reflection_* entry points: the face size and the counts, then
+// (unless null) the positions; and those of jpt_set_reflection_params against a face size (0: none known yet).
+int check_reflection_probes(const char* call, const float* position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row, std::string& why);
+int check_reflection_params(const char* call, int32_t n_levels, int32_t samples, int32_t face_size, std::string& why);
+// The sample tables of (face_size, n_levels, samples), made in double (jpt_primary.cpp): n_levels * samples entries (L_x, L_y, L_z, w)
+// and source levels, level l's at l * samples, the kept ones first and zeros / kReflNoSample behind them (level 0 has none);
+// count[l]: how many are kept
+void reflection_sample_table(int32_t face_size, int32_t n_levels, int32_t samples, std::vector<float4>& table, std::vector<uint8_t>& levels,
+                             uint32_t count[kReflLevelsMax]);
+// The two steps of jpt_reflection_prefilter (jpt_kernels_reflection.hip), on `stream`: the source chain of every probe from the
+// accumulation image (rd.per_row * 6 * rd.face_size() pixels wide), then the output chain from it and the tables.  Every pointer is
+// device memory; the layouts are jpt_reflection.h's.
+void launch_reflection_chain(hipStream_t stream, const ReflDev& rd, const float4* accum, float frame_count, float4* chain);
+void launch_reflection_prefilter(hipStream_t stream, const ReflDev& rd, const float4* chain, const float4* table, const uint8_t* levels, float4* out);
 
 // The emitter tables (jpt_kernels_post.hip), on `stream`, from the scene's device arrays: cand holds n (instance, triangle) pairs;
 // tri (3 n float4), cdf (n floats), marg (n_blocks + 1 floats: the marginal CDF, then the total power) are device memory

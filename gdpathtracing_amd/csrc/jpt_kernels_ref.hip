@@ -208,10 +208,11 @@ __device__ __forceinline__ bool ray_trace_tlas(const RefSceneDev& sc, const Ray&
 void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, float4* accum,
                       uint32_t* ldr, float* depth, DevCounters* counters, const Lighting& lg, const PrimaryRays& primary)
 {
-    const LensDev& lens = primary.lens;   // (the one kernel takes all four members and branches at run time)
+    const LensDev& lens = primary.lens;   // (the one kernel takes all five members and branches at run time)
     const CamModelDev& cm = primary.cam_model;
     const BakeDev& bake = primary.bake;
     const ProbeDev& probe = primary.probe;
+    const CubeDev& cube = primary.cube;
     RefSceneDev sc;
     sc.tri_geom = ds.ref_tri_geom;
     sc.bvh = ds.ref_bvh;
@@ -226,23 +227,23 @@ void launch_ref_frame(hipStream_t stream, const DeviceScene& ds, const FramePara
     const bool ties = ds.x.ok && ds.reach_tri != nullptr && !fp.debug_steps;
     with_consts<2, 2>([&](auto C, auto TIES) {
         if (lg.transmissive) {
-            hipLaunchKernelGGL((ref_frame_kernel_tx<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, lg.env, lg.samp,
+            hipLaunchKernelGGL((ref_frame_kernel_tx<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, cube, lg.env, lg.samp,
                                lg.lights, lg.env_mode);
             return;
         }
         switch (lg.kind) {
         case Lighting::kEmitters:
-            hipLaunchKernelGGL((ref_frame_kernel_lt<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, lg.env, lg.samp,
+            hipLaunchKernelGGL((ref_frame_kernel_lt<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, cube, lg.env, lg.samp,
                                lg.lights, lg.env_mode);
             break;
         case Lighting::kMapMis:
-            hipLaunchKernelGGL((ref_frame_kernel_mis<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, lg.env, lg.samp);
+            hipLaunchKernelGGL((ref_frame_kernel_mis<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, cube, lg.env, lg.samp);
             break;
         case Lighting::kMap:
-            hipLaunchKernelGGL((ref_frame_kernel_env<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, lg.env);
+            hipLaunchKernelGGL((ref_frame_kernel_env<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, cube, lg.env);
             break;
         case Lighting::kSky:
-            hipLaunchKernelGGL((ref_frame_kernel<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe);
+            hipLaunchKernelGGL((ref_frame_kernel<C, TIES>), grid, block, 0, stream, sc, ds.x, sh, fp, cam, accum, ldr, depth, counters, lens, cm, bake, probe, cube);
             break;
         }
     }, counters != nullptr, ties);

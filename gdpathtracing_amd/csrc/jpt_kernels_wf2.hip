@@ -814,6 +814,15 @@ __global__ __launch_bounds__(kOccBlock) void wf2_occlude_lt(WideSceneDev sc, Wf2
 #include "jpt_wf2_paths.h"
 #undef JPT_ENV
 #undef JPT_PROBE
+// ... and their cube forms (jpt_set_reflection_probes): wf2_primary_cube, wf2_primary_env_cube
+#define JPT_CUBE 1
+#define JPT_ENV 0
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#define JPT_ENV 1
+#include "jpt_wf2_paths.h"
+#undef JPT_ENV
+#undef JPT_CUBE
 
 // the window of a render (local tiles): x0, y0, nx, ny
 struct TileWindow {
@@ -1090,6 +1099,10 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
             case PrimaryRays::kProbe:
                 if (env) hipLaunchKernelGGL((wf2_primary_env_probe<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.probe, counters);
                 else hipLaunchKernelGGL((wf2_primary_probe<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.probe, counters);
+                break;
+            case PrimaryRays::kCube:
+                if (env) hipLaunchKernelGGL((wf2_primary_env_cube<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.cube, counters);
+                else hipLaunchKernelGGL((wf2_primary_cube<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.primary.cube, counters);
                 break;
             case PrimaryRays::kPinhole:
                 if (env) hipLaunchKernelGGL((wf2_primary_env<C, W != 0, W == 2>), pgrid, block, 0, st, sc, wb, dm, gp, cam, tune, r.cull, counters);

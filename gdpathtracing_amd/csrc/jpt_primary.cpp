@@ -1,4 +1,4 @@
-// jpt_primary.cpp -- where a context's renders start their paths: the thin lens, the camera model, the bake images and the probes (PrimaryState,
+// jpt_primary.cpp -- where a context's renders start their paths: the thin lens, the camera model, the bake images, the probes and the reflection probes (PrimaryState,
 // jpt_ctx.h), the one resolver that turns them into a render's PrimaryRays (jpt_kernels.h), the view of the entry points that take
 // one without rendering, and the C entries that set them.  Host C++: the kernels are jpt_kernels_bake.hip's and jpt_debug.hip's.
 #include "jpt_ctx.h"
@@ -57,16 +57,31 @@ int jpt::make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out
     return JPT_OK;
 }
 
-// One decision, in this order: DEBUG_STEPS, the bake images, the probes, the lens, the model.  The sources exclude one another, and a
+// One decision, in this order: DEBUG_STEPS, the reflection probes, the bake images, the probes, the lens, the model.  The sources exclude one another, and a
 // refusal names the first of them in that order: a bake render with a lens is refused as a bake and not for the lens's own reasons,
-// and probes beside bake images are refused (or rendered) as a bake.
+// and probes beside bake images are refused (or rendered) as a bake.  Reflection probes beside bake images or probes are refused:
+// neither image layout is the other's.
 int jpt::resolve_primary(jpt_ctx* c, PrimaryRays& out)
 {
     const PrimaryState& p = c->primary;
     out = PrimaryRays{};
     if (c->debug_steps) return JPT_OK;   // (DEBUG_STEPS ignores the images, the lens and the model, as it ignores lighting)
     const bool lens = p.lens_radius > 0.0f, model = p.camera_model != JPT_CAMERA_PINHOLE, temporal = c->denoise == JPT_DENOISE_TEMPORAL;
-    if (p.has_bake()) {
+    if (p.has_cubes()) {
+        if (p.has_bake())
+            return fail(c, JPT_E_STATE, "the context holds reflection probes and bake images: free one of them (jpt_set_reflection_probes, jpt_set_bake_texels)");
+        if (p.has_probes()) return fail(c, JPT_E_STATE, "the context holds reflection probes and light probes: free one of them (jpt_set_reflection_probes, jpt_set_probes)");
+        if (p.cube_w != c->width || p.cube_h != c->height)
+            return fail(c, JPT_E_STATE, "the reflection probes' strips make an image of " + std::to_string(p.cube_w) + " x " + std::to_string(p.cube_h) +
+                                            " pixels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height) +
+                                            ": a cube render has one path per face texel (jpt_set_reflection_probes)");
+        if (lens) return fail(c, JPT_E_STATE, "a cube render has no lens: set the lens radius to 0 (jpt_set_lens) or free the reflection probes (jpt_set_reflection_probes)");
+        if (model)
+            return fail(c, JPT_E_STATE, "a cube render has no camera model: set JPT_CAMERA_PINHOLE (jpt_set_camera_model) or free the reflection probes (jpt_set_reflection_probes)");
+        if (temporal) return fail(c, JPT_E_STATE, "temporal reprojection assumes a camera: set another denoising mode or free the reflection probes (jpt_set_reflection_probes)");
+        out.kind = PrimaryRays::kCube;
+        out.cube = p.cube_dev();
+    } else if (p.has_bake()) {
         if (p.bake_w != c->width || p.bake_h != c->height)
             return fail(c, JPT_E_STATE, "the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) + " texels but jpt_set_params says " +
                                             std::to_string(c->width) + " x " + std::to_string(c->height) + ": a bake render has one path per texel (jpt_set_bake_texels)");
@@ -112,6 +127,8 @@ int jpt::view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& o
     if (c->primary.has_bake())
         return fail(c, JPT_E_STATE, std::string(call) + ": " + rays + " are camera rays, and the context holds bake images (jpt_set_bake_texels)");
     if (c->primary.has_probes()) return fail(c, JPT_E_STATE, std::string(call) + ": " + rays + " are camera rays, and the context holds probes (jpt_set_probes)");
+    if (c->primary.has_cubes())
+        return fail(c, JPT_E_STATE, std::string(call) + ": " + rays + " are camera rays, and the context holds reflection probes (jpt_set_reflection_probes)");
     std::string why;
     const int rc = make_camera_model(c->primary.camera_model, c->camera, out, why);
     return rc == JPT_OK ? JPT_OK : fail(c, rc, why);
@@ -272,6 +289,100 @@ void jpt::probe_basis_table(int32_t tile_w, int32_t tile_h, int32_t flags, std::
             if (flags & JPT_PROBE_IRRADIANCE) v = v * band[k == 0 ? 0 : (k < 4 ? 1 : 2)];
             out[(size_t)c * 9 + k] = (float)v;
         }
+}
+
+// ---- the checks of jpt_set_reflection_probes / jpt_set_reflection_params, also run by the debug entry points, and the sample tables ----
+
+int jpt::check_reflection_probes(const char* call, const float* position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row, std::string& why)
+{
+    const std::string who = std::string(call) + ": ";
+    if (face_size < kCubeFaceMin || face_size > kCubeFaceMax || (face_size & (face_size - 1)) != 0) {
+        why = who + "face_size must be a power of two in [4, 256]";
+        return JPT_E_INVALID;
+    }
+    if (n_probes < 1 || n_probes > kCubeMaxProbes) {
+        why = who + "n_probes must be in [1, 2^20]";
+        return JPT_E_LIMIT;
+    }
+    if (probes_per_row < 1) {
+        why = who + "probes_per_row must be >= 1";
+        return JPT_E_INVALID;
+    }
+    uint64_t w, h;
+    cube_image_size(n_probes, face_size, probes_per_row, w, h);
+    if (w > kCubeMaxPixels || w * h > kCubeMaxPixels) {
+        why = who + "the image of the strips has more than 2^26 pixels";
+        return JPT_E_LIMIT;
+    }
+    if (position3)
+        for (size_t k = 0; k < 3 * (size_t)n_probes; k++)
+            if (!std::isfinite(position3[k])) {
+                why = who + "probe " + std::to_string(k / 3) + " has a non-finite position component";
+                return JPT_E_INVALID;
+            }
+    return JPT_OK;
+}
+
+int jpt::check_reflection_params(const char* call, int32_t n_levels, int32_t samples, int32_t face_size, std::string& why)
+{
+    const std::string who = std::string(call) + ": ";
+    const int32_t most = face_size ? cube_log2(face_size) + 1 : kReflLevelsMax;
+    if (n_levels != 0 && (n_levels < kReflLevelsMin || n_levels > most)) {
+        why = who + "n_levels must be 0 (every level down to 1 x 1) or in [2, " + std::to_string(most) + "]" +
+              (face_size ? ": log2(face_size) + 1 of the face size " + std::to_string(face_size) : "");
+        return JPT_E_INVALID;
+    }
+    if (samples < kReflSamplesMin || samples > kReflSamplesMax) {
+        why = who + "samples must be in [8, 256]";
+        return JPT_E_INVALID;
+    }
+    return JPT_OK;
+}
+
+// The construction of jpt_reflection.h, in double; an entry is rounded to float once.
+void jpt::reflection_sample_table(int32_t face_size, int32_t n_levels, int32_t samples, std::vector<float4>& table, std::vector<uint8_t>& levels,
+                                  uint32_t count[kReflLevelsMax])
+{
+    const double pi = 3.14159265358979323846;
+    const int K = samples, top = cube_log2(face_size);
+    table.assign((size_t)n_levels * K, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    levels.assign((size_t)n_levels * K, kReflNoSample);
+    for (int l = 0; l < kReflLevelsMax; l++) count[l] = 0;
+    const double omega0 = 4.0 * pi / (6.0 * (double)face_size * (double)face_size);
+    std::vector<double> lx(K), ly(K), lz(K);
+    std::vector<int> lv(K);
+    for (int l = 1; l < n_levels; l++) {
+        const double alpha = (double)l / (double)(n_levels - 1), a2 = alpha * alpha;
+        double sum = 0.0;
+        for (int k = 0; k < K; k++) {
+            const double u1 = ((double)k + 0.5) / (double)K;
+            double u2 = 0.0, digit = 0.5;
+            for (int b = k; b; b >>= 1, digit *= 0.5)
+                if (b & 1) u2 += digit;
+            const double ct = std::sqrt((1.0 - u1) / (1.0 + (a2 - 1.0) * u1));
+            const double st = std::sqrt(1.0 - ct * ct);
+            const double phi = 2.0 * pi * u2;
+            const double hx = st * std::cos(phi), hy = st * std::sin(phi), hz = ct;
+            lx[k] = 2.0 * hz * hx;
+            ly[k] = 2.0 * hz * hy;
+            lz[k] = 2.0 * hz * hz - 1.0;
+            const double den = hz * hz * (a2 - 1.0) + 1.0;
+            const double ndf = a2 / (pi * den * den);
+            const double omega_s = 4.0 / ((double)K * ndf);
+            double m = std::floor(0.5 * std::log2(omega_s / omega0) + 0.5) + 1.0;
+            m = m < 0.0 ? 0.0 : (m > (double)top ? (double)top : m);
+            lv[k] = (int)m;
+            if (lz[k] > 0.0) sum += lz[k];
+        }
+        uint32_t kept = 0;
+        for (int k = 0; k < K; k++) {
+            if (!(lz[k] > 0.0)) continue;
+            table[(size_t)l * K + kept] = make_float4((float)lx[k], (float)ly[k], (float)lz[k], (float)(lz[k] / sum));
+            levels[(size_t)l * K + kept] = (uint8_t)lv[k];
+            kept++;
+        }
+        count[l] = kept;
+    }
 }
 
 namespace {
@@ -519,6 +630,8 @@ int jpt_probe_project(jpt_ctx* c, int32_t flags)
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_probe_project: host-only context: it runs on the device");
     PrimaryState& p = c->primary;
     if (!p.has_probes()) return fail(c, JPT_E_STATE, "jpt_probe_project: no probes (jpt_set_probes first)");
+    if (p.has_cubes())
+        return fail(c, JPT_E_STATE, "jpt_probe_project: the context also holds reflection probes (jpt_set_reflection_probes), and no render of it is a probe render");
     if (!c->params_set || p.probe_w != c->width || p.probe_h != c->height)
         return fail(c, JPT_E_STATE, "jpt_probe_project: the probe tiles make an image of " + std::to_string(p.probe_w) + " x " + std::to_string(p.probe_h) +
                                         " pixels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
@@ -559,6 +672,224 @@ int jpt_read_probe_sh_f32(jpt_ctx* c, float* out)
     const int rc = staged_read(c, c->primary.d_probe_sh.p, bytes);
     if (rc != JPT_OK) return rc;
     std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+// ---- reflection probes: the context's positions (jpt_cube.h) and their prefiltered mip chain (jpt_reflection.h) ---------------------
+
+namespace {
+
+void forget_cubes(PrimaryState& p)
+{
+    p.d_cube_pos.release();
+    p.d_refl_chain.release();
+    p.d_refl_out.release();
+    p.d_refl_table.release();
+    p.d_refl_lvl.release();
+    p.table_face = p.table_levels = p.table_samples = 0;
+    p.cube_n = p.cube_face = p.cube_per_row = p.cube_w = p.cube_h = 0;
+    p.refl_made = 0;
+}
+
+}  // namespace
+
+int jpt_set_reflection_probes(jpt_ctx* c, const float* position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row)
+{
+    if (!c) return JPT_E_INVALID;
+    const bool freeing = !position3 && n_probes == 0 && face_size == 0 && probes_per_row == 0;
+    if (!freeing) {
+        if (!position3) return fail(c, JPT_E_INVALID, "jpt_set_reflection_probes: position3 is given, or (NULL, 0, 0, 0) frees the reflection probes");
+        std::string why;
+        const int rc = check_reflection_probes("jpt_set_reflection_probes", position3, n_probes, face_size, probes_per_row, why);
+        if (rc != JPT_OK) return fail(c, rc, why);
+    }
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_reflection_probes: host-only context has no reflection probes");
+    // the renders (and a jpt_reflection_prefilter) already queued read the old positions and images: they finish first
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    PrimaryState& p = c->primary;
+    p.refl_valid = false;
+    if (freeing) {
+        forget_cubes(p);
+        return JPT_OK;
+    }
+    const hipError_t e = p.d_cube_pos.resize(3 * (size_t)n_probes);
+    if (e != hipSuccess) {
+        forget_cubes(p);
+        return hip_fail(c, e, "hipMalloc of the reflection probes' positions");
+    }
+    uint64_t w, h;
+    cube_image_size(n_probes, face_size, probes_per_row, w, h);
+    p.cube_n = n_probes;
+    p.cube_face = face_size;
+    p.cube_per_row = probes_per_row;
+    p.cube_w = (int32_t)w;
+    p.cube_h = (int32_t)h;
+    const hipError_t ec = hipMemcpy(p.d_cube_pos.p, position3, 3 * (size_t)n_probes * sizeof(float), hipMemcpyHostToDevice);
+    if (ec != hipSuccess) {   // (no probes rather than probes at positions nobody wrote)
+        forget_cubes(p);
+        return hip_fail(c, ec, "hipMemcpy of the reflection probes' positions");
+    }
+    return JPT_OK;
+}
+
+int jpt_get_reflection_image_size(jpt_ctx* c, int32_t* width, int32_t* height)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!width || !height) return fail(c, JPT_E_INVALID, "jpt_get_reflection_image_size: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_get_reflection_image_size: host-only context has no reflection probes");
+    if (!c->primary.has_cubes()) return fail(c, JPT_E_STATE, "jpt_get_reflection_image_size: no reflection probes (jpt_set_reflection_probes first)");
+    *width = c->primary.cube_w;
+    *height = c->primary.cube_h;
+    return JPT_OK;
+}
+
+int jpt_read_reflection_probes(jpt_ctx* c, float* position3)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!position3) return fail(c, JPT_E_INVALID, "jpt_read_reflection_probes: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_reflection_probes: host-only context has no reflection probes");
+    if (!c->primary.has_cubes()) return fail(c, JPT_E_STATE, "jpt_read_reflection_probes: no reflection probes (jpt_set_reflection_probes first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = 3 * (size_t)c->primary.cube_n * sizeof(float);
+    const int rc = staged_read(c, c->primary.d_cube_pos.p, bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(position3, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+int jpt_set_reflection_params(jpt_ctx* c, const jpt_reflection_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    jpt_reflection_params q;
+    q.n_levels = 0;
+    q.samples = kReflSamplesDefault;
+    if (params) q = *params;
+    std::string why;
+    const int rc = check_reflection_params("jpt_set_reflection_params", q.n_levels, q.samples, c->primary.cube_face, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_reflection_params: host-only context: jpt_reflection_prefilter runs on the device");
+    c->primary.refl_valid = false;   // (no jpt_reflection_prefilter with these parameters yet)
+    c->primary.refl_levels = q.n_levels;
+    c->primary.refl_samples = q.samples;
+    return JPT_OK;
+}
+
+int jpt_reflection_prefilter(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter filters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1)
+        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter needs the whole image on one context (world == 1): the gathering context filters");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_reflection_prefilter: host-only context: it runs on the device");
+    PrimaryState& p = c->primary;
+    if (!p.has_cubes()) return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: no reflection probes (jpt_set_reflection_probes first)");
+    if (p.has_bake() || p.has_probes())
+        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: the context also holds bake images or light probes, and no render of it is a cube render");
+    if (!c->params_set || p.cube_w != c->width || p.cube_h != c->height)
+        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: the reflection probes' strips make an image of " + std::to_string(p.cube_w) + " x " +
+                                        std::to_string(p.cube_h) + " pixels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: no frame accumulated since the last reset");
+    if (p.refl_levels > cube_log2(p.cube_face) + 1)   // (the parameters were set before these probes: checked against no face size)
+        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: n_levels is " + std::to_string(p.refl_levels) + " (jpt_set_reflection_params) but a face of " +
+                                        std::to_string(p.cube_face) + " texels has " + std::to_string(cube_log2(p.cube_face) + 1) + " levels");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int32_t n_levels = p.refl_levels_now(), K = p.refl_samples;
+    if (p.table_face != p.cube_face || p.table_levels != n_levels || p.table_samples != K || !p.d_refl_table.p) {
+        // (an earlier prefilter on the stream may still read the old tables)
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<float4> table;
+        std::vector<uint8_t> levels;
+        reflection_sample_table(p.cube_face, n_levels, K, table, levels, p.refl_count);
+        p.table_face = 0;
+        HIP_TRY(c, p.d_refl_table.resize(table.size()));
+        HIP_TRY(c, p.d_refl_lvl.resize(levels.size()));
+        HIP_TRY(c, hipMemcpy(p.d_refl_table.p, table.data(), table.size() * sizeof(float4), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(p.d_refl_lvl.p, levels.data(), levels.size(), hipMemcpyHostToDevice));
+        p.table_face = p.cube_face;
+        p.table_levels = n_levels;
+        p.table_samples = K;
+    }
+    ReflDev rd;
+    rd.n = (uint32_t)p.cube_n;
+    rd.per_row = (uint32_t)p.cube_per_row;
+    rd.shift = (uint32_t)cube_log2(p.cube_face);
+    rd.n_levels = (uint32_t)n_levels;
+    rd.samples = (uint32_t)K;
+    for (int l = 0; l < kReflLevelsMax; l++) rd.count[l] = p.refl_count[l];
+    const size_t n_chain = (size_t)((uint64_t)rd.n * refl_probe_texels(rd.shift)), n_out = (size_t)refl_out_texels(rd.n, rd.shift, rd.n_levels);
+    if (p.d_refl_chain.n != n_chain || !p.d_refl_chain.p || p.d_refl_out.n != n_out || !p.d_refl_out.p) {
+        p.refl_valid = false;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an earlier prefilter may still write the old images)
+        HIP_TRY(c, p.d_refl_chain.resize(n_chain));
+        HIP_TRY(c, p.d_refl_out.resize(n_out));
+    }
+    const bool timed = c->kernel_timing;
+    if (timed)
+        for (hipEvent_t& e : p.refl_ev)
+            if (!e) HIP_TRY(c, hipEventCreate(&e));
+    // On the context's stream, as jpt_probe_project: behind the accumulation of every render queued so far, and the accumulation of
+    // every later render waits for what it reads.
+    if (timed) HIP_TRY(c, hipEventRecord(p.refl_ev[0], c->stream));
+    launch_reflection_chain(c->stream, rd, c->d_accum.p, (float)c->frame_count, p.d_refl_chain.p);
+    if (timed) HIP_TRY(c, hipEventRecord(p.refl_ev[1], c->stream));
+    launch_reflection_prefilter(c->stream, rd, p.d_refl_chain.p, p.d_refl_table.p, p.d_refl_lvl.p, p.d_refl_out.p);
+    if (timed) HIP_TRY(c, hipEventRecord(p.refl_ev[2], c->stream));
+    HIP_TRY(c, hipGetLastError());
+    p.refl_timed = timed;
+    p.refl_made = n_levels;
+    p.refl_valid = true;
+    return JPT_OK;
+}
+
+int jpt_get_reflection_chain_size(jpt_ctx* c, int32_t level, int32_t* face_size, uint64_t* offset_texels)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!face_size || !offset_texels) return fail(c, JPT_E_INVALID, "jpt_get_reflection_chain_size: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_get_reflection_chain_size: host-only context has no reflection probes");
+    const PrimaryState& p = c->primary;
+    if (!p.has_cubes()) return fail(c, JPT_E_STATE, "jpt_get_reflection_chain_size: no reflection probes (jpt_set_reflection_probes first)");
+    const int32_t most = cube_log2(p.cube_face) + 1;
+    const int32_t n_levels = p.refl_valid ? p.refl_made : (p.refl_levels_now() < most ? p.refl_levels_now() : most);
+    if (level < 0 || level >= n_levels)
+        return fail(c, JPT_E_INVALID, "jpt_get_reflection_chain_size: level must be in [0, " + std::to_string(n_levels) + ")");
+    const uint32_t shift = (uint32_t)cube_log2(p.cube_face);
+    *face_size = p.cube_face >> level;
+    *offset_texels = refl_out_offset((uint32_t)p.cube_n, shift, (uint32_t)level);
+    return JPT_OK;
+}
+
+int jpt_read_reflection_f32(jpt_ctx* c, int32_t level, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_reflection_f32: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_reflection_f32: host-only context: jpt_reflection_prefilter runs on the device");
+    const PrimaryState& p = c->primary;
+    if (!p.refl_valid) return fail(c, JPT_E_STATE, "jpt_read_reflection_f32: no jpt_reflection_prefilter of the current reflection probes and size yet");
+    if (level < 0 || level >= p.refl_made) return fail(c, JPT_E_INVALID, "jpt_read_reflection_f32: level must be in [0, " + std::to_string(p.refl_made) + ")");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t shift = (uint32_t)cube_log2(p.cube_face);
+    const size_t s = (size_t)(p.cube_face >> level), bytes = (size_t)p.cube_n * 6u * s * s * sizeof(float4);
+    const int rc = staged_read(c, p.d_refl_out.p + refl_out_offset((uint32_t)p.cube_n, shift, (uint32_t)level), bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+int jpt_get_reflection_timing(jpt_ctx* c, float* chain_ms, float* prefilter_ms)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!chain_ms || !prefilter_ms) return fail(c, JPT_E_INVALID, "jpt_get_reflection_timing: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_get_reflection_timing: host-only context: jpt_reflection_prefilter runs on the device");
+    PrimaryState& p = c->primary;
+    if (!p.refl_valid || !p.refl_timed)
+        return fail(c, JPT_E_STATE, "jpt_get_reflection_timing: the last jpt_reflection_prefilter did not run under jpt_set_kernel_timing");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipEventSynchronize(p.refl_ev[2]));
+    HIP_TRY(c, hipEventElapsedTime(chain_ms, p.refl_ev[0], p.refl_ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(prefilter_ms, p.refl_ev[1], p.refl_ev[2]));
     return JPT_OK;
 }
 

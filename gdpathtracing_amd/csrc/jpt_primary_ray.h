@@ -1,5 +1,5 @@
 // jpt_primary_ray.h -- the first ray of (pixel, frame) under a PrimaryRays value (jpt_kernels.h), for host and device: what the
-// jpt_debug_*_rays entry points show of a render's ray generation (jpt_debug.hip).  It calls the functions the ten primary kernels
+// jpt_debug_*_rays entry points show of a render's ray generation (jpt_debug.hip).  It calls the functions the twelve primary kernels
 // and the audit kernel inline, in their combinations; those kernels do not call it (jpt_wf2_paths.h, jpt_ref_frame.h).
 #pragma once
 
@@ -9,7 +9,7 @@ namespace jpt {
 
 #if defined(__HIPCC__)
 
-// False: the pixel has no path (an invalid texel of a bake render, a tile without a probe of a probe render), and `ray` is all zeros.
+// False: the pixel has no path (an invalid texel of a bake render, a tile or a strip without a probe of a probe or cube render), and `ray` is all zeros.
 __host__ __device__ __forceinline__ bool first_ray(const PrimaryRays& p, const RefCamera& cam, int width, int height, int px, int py, uint32_t frame, Ray& ray)
 {
     uint32_t sx, sy;
@@ -37,6 +37,14 @@ __host__ __device__ __forceinline__ bool first_ray(const PrimaryRays& p, const R
         uint32_t q, i, j;
         if (probe_cell(p.probe, px, py, q, i, j)) {
             ray = probe_ray(probe_position(p.probe, q), i, j, p.probe.tile_w(), p.probe.tile_h(), px, py, frame, sx, sy);
+            return true;
+        }
+        break;
+    }
+    case PrimaryRays::kCube: {
+        uint32_t q, f, i, j;
+        if (cube_cell(p.cube, px, py, q, f, i, j)) {
+            ray = cube_ray(cube_position(p.cube, q), f, i, j, p.cube.face_size(), px, py, frame, sx, sy);
             return true;
         }
         break;

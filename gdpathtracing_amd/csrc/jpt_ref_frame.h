@@ -46,7 +46,7 @@
 template <bool COUNT, bool TIES>
 __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefSceneDev sc, TieShadowDev shadow, SceneShading sh, FrameParams fp, RefCamera cam,
                                                         float4* __restrict__ accum, uint32_t* __restrict__ ldr,
-                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters, LensDev lens, CamModelDev cm, BakeDev bake, ProbeDev probe JPT_ENV_PARAM)
+                                                        float* __restrict__ depth_out, DevCounters* __restrict__ counters, LensDev lens, CamModelDev cm, BakeDev bake, ProbeDev probe, CubeDev cube JPT_ENV_PARAM)
 {
     // 8x32 pixel tiles: a wave covers 8x8 pixels
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -71,6 +71,11 @@ __global__ __launch_bounds__(256, 5) void JPT_ENV_NAME(ref_frame_kernel)(RefScen
             uint32_t q, ci, cj;
             lit = probe_cell(probe, px, py, q, ci, cj);
             if (lit) ray = probe_ray(probe_position(probe, q), ci, cj, probe.tile_w(), probe.tile_h(), px, py, fp.frame_index, sx, sy);
+        }
+        if (cube.position != nullptr) {   // (jpt_set_reflection_probes: a strip without a probe traces nothing, likewise; null: no cube render)
+            uint32_t q, cf, ci, cj;
+            lit = cube_cell(cube, px, py, q, cf, ci, cj);
+            if (lit) ray = cube_ray(cube_position(cube, q), cf, ci, cj, cube.face_size(), px, py, fp.frame_index, sx, sy);
         }
         float depth = cam.far_;
         f3 radiance = mk3(0.0f, 0.0f, 0.0f);

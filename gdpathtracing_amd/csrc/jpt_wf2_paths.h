@@ -1,7 +1,7 @@
 // jpt_wf2_paths.h -- the kernels of jpt_kernels_wf2.hip that see the misses of the paths: wf2_primary, wf2_shade (and shade_entry,
 // which wf2_finish shares), wf2_finish and wf2_accumulate.  Included five times by jpt_kernels_wf2.hip, inside its anonymous namespace
-// (and twice more with JPT_LENS defined, twice with JPT_CAMERA_MODEL, twice with JPT_BAKE and twice with JPT_PROBE, for the lens,
-// camera-model, bake and probe forms of wf2_primary alone: see there):
+// (and twice more with JPT_LENS defined, twice with JPT_CAMERA_MODEL, twice with JPT_BAKE, twice with JPT_PROBE and twice with JPT_CUBE, for the lens,
+// camera-model, bake, probe and cube forms of wf2_primary alone: see there):
 //   JPT_ENV 0   the default kernels, whose misses see main.glsl's gradient (sample_sky): the same source, token for token, and
 //               so the same gfx950 code as before the environment map existed;
 //   JPT_ENV 1   the *_env kernels (jpt_set_environment): one more parameter, the map (EnvDev, by value), and env_radiance at
@@ -92,7 +92,12 @@
 // made, the divisors being kernel arguments -- reads the probe's position (12 B) and starts the path with probe_ray (jpt_probe.h).  A
 // pixel of a tile without a probe traces nothing, like an invalid texel.  No cull.
 //
-// launch_wf2_render takes one of these ten forms by the kind of the render's PrimaryRays (jpt_kernels.h) and its miss model.
+// JPT_CUBE defined (likewise): the forms wf2_primary_cube and wf2_primary_env_cube (jpt_set_reflection_probes) -- the reflection
+// probes (CubeDev, by value) where the sky cull was; at refill the lane divides its pixel into (probe, face, i, j) -- shifts and masks
+// by a kernel argument and one v_mul_hi_u32 for the / 6 --, reads the probe's position (12 B) and starts the path with cube_ray
+// (jpt_cube.h).  A pixel of a strip without a probe traces nothing, like an invalid texel.  No cull.
+//
+// launch_wf2_render takes one of these twelve forms by the kind of the render's PrimaryRays (jpt_kernels.h) and its miss model.
 #ifdef JPT_LENS
 #if JPT_ENV
 #define JPT_PRIMARY_NAME wf2_primary_env_lens
@@ -121,6 +126,13 @@
 #define JPT_PRIMARY_NAME wf2_primary_probe
 #endif
 #define JPT_PRIMARY_PARAM ProbeDev probe
+#elif defined(JPT_CUBE)
+#if JPT_ENV
+#define JPT_PRIMARY_NAME wf2_primary_env_cube
+#else
+#define JPT_PRIMARY_NAME wf2_primary_cube
+#endif
+#define JPT_PRIMARY_PARAM CubeDev cube
 #else
 #define JPT_PRIMARY_NAME JPT_ENV_NAME(wf2_primary)
 #define JPT_PRIMARY_PARAM SkyCull cull
@@ -264,6 +276,31 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
                             ray.o = probe_position(probe, probe_q);
                             ray.d = probe_direction(probe_i, probe_j, tile_w, tile_h, xi0, xi1);
 #endif
+#elif defined(JPT_CUBE)
+                        uint32_t cube_q, cube_f, cube_i, cube_j;
+                        if (!cube_cell(cube, px, py, cube_q, cube_f, cube_i, cube_j)) {
+                            if (COUNT) cnt.rays--;   // (no ray: the count above is taken back)
+                            store_final(wb, fp.accum_mode, path, mk3(0.0f, 0.0f, 0.0f));
+                            if ((int)f == fp.depth_frame) wb.first_depth[slot] = cam.far_;
+                        } else {
+                            // (cube_ray, jpt_cube.h, taken apart)
+                            uint32_t sx, sy;
+                            float xi0, xi1;
+                            cube_draw(px, py, fp.frame_index + f, sx, sy, xi0, xi1);
+                            Ray ray;
+                            // (the face size enters a vector register here, per refill, as the probe forms' tile sides do: as a loop
+                            // invariant its float form would be hoisted out of the persistent loop into a register of its own)
+                            uint32_t face_size = cube.face_size();
+                            asm volatile("" : "+v"(face_size));
+                            // (the position's load stands where the probe forms' does, by miss model: with a map and the load first the
+                            // TAIL instantiation has one scratch instruction more than the lens forms' budget -- tests/test_reflection_budgets.py)
+#if JPT_ENV
+                            ray.d = cube_direction(cube_f, cube_i, cube_j, face_size, xi0, xi1);
+                            ray.o = cube_position(cube, cube_q);
+#else
+                            ray.o = cube_position(cube, cube_q);
+                            ray.d = cube_direction(cube_f, cube_i, cube_j, face_size, xi0, xi1);
+#endif
 #else
                         if (sky_culled(cull, px, py)) {
                             if (COUNT) {
@@ -329,7 +366,7 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
 #undef JPT_PRIMARY_PARAM
 #endif  // JPT_ENV < 2
 
-#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL) && !defined(JPT_BAKE) && !defined(JPT_PROBE)   // (everything below: once per miss model)
+#if !defined(JPT_LENS) && !defined(JPT_CAMERA_MODEL) && !defined(JPT_BAKE) && !defined(JPT_PROBE) && !defined(JPT_CUBE)   // (everything below: once per miss model)
 
 // ---- shading: one path vertex per queue entry (main.glsl:378-397) -------------------------------------------
 
@@ -951,7 +988,7 @@ __global__ __launch_bounds__(kBlock) void JPT_ENV_NAME(wf2_accumulate)(Wf2Buffer
 
 #endif  // JPT_ENV < 2
 
-#endif  // JPT_LENS, JPT_CAMERA_MODEL, JPT_BAKE, JPT_PROBE
+#endif  // JPT_LENS, JPT_CAMERA_MODEL, JPT_BAKE, JPT_PROBE, JPT_CUBE
 
 #undef JPT_ENV_NAME
 #undef JPT_ENV_PARAM

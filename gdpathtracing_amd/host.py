@@ -220,6 +220,57 @@ def debug_probe_project(device_id, accum4, frame_count, n_probes, tile_w, tile_h
     return out
 
 
+def reflection_image_size(n_probes, face_size, probes_per_row):
+    """(width, height) of the image n_probes strips of six faces make, probes_per_row to a row (jpt_get_reflection_image_size's rule)"""
+    return int(probes_per_row) * 6 * int(face_size), -(-int(n_probes) // int(probes_per_row)) * int(face_size)
+
+
+def debug_cube_rays(device_id, positions, face_size, probes_per_row, frame_index):
+    """jpt_debug_cube_rays: the first rays of a cube render's paths for every pixel of one frame -- float32 [height, width, 6], the
+    origin then the direction (a strip without a probe: zeros).  device_id -1: the host's copy."""
+    pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    w, h = reflection_image_size(max(len(pos), 1), max(int(face_size), 1), max(int(probes_per_row), 1))
+    rays = np.zeros((h, w, 6), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_cube_rays(int(device_id), _ptr(pos), len(pos), int(face_size), int(probes_per_row), int(frame_index), _ptr(rays))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_cube_rays failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return rays
+
+
+def debug_reflection_samples(face_size, n_levels, samples, level):
+    """jpt_debug_reflection_samples: the host's sample table of output level `level` -- (entries float32 [kept, 4]: L_x, L_y, L_z, w;
+    source levels uint8 [kept]); kept <= samples (the library pads with level byte 0xff, cut off here)"""
+    table = np.zeros((max(int(samples), 1), 4), np.float32)
+    lvl = np.zeros(max(int(samples), 1), np.uint8)
+    L = capi.lib()
+    rc = L.jpt_debug_reflection_samples(int(face_size), int(n_levels), int(samples), int(level), _ptr(table), _ptr(lvl))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_reflection_samples failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    kept = int((lvl != 0xff).sum())
+    assert (lvl[:kept] != 0xff).all() and not table[kept:].any()
+    return table[:kept].copy(), lvl[:kept].copy()
+
+
+def debug_reflection_prefilter(device_id, accum4, frame_count, n_probes, face_size, probes_per_row, level, params=None, **fields):
+    """jpt_debug_reflection_prefilter: level `level` of the chain of a caller-made accumulation image (float32 [height, width, 4], the
+    size the probes make) -- float32 [n_probes, 6, s, s, 4], s = face_size >> level.  device_id -1: the same in plain loops on the host."""
+    a = np.ascontiguousarray(accum4, dtype=np.float32)
+    w, h = reflection_image_size(n_probes, face_size, probes_per_row)
+    if a.shape != (h, w, 4):
+        raise ValueError("accum4 is float32 [%d, %d, 4]" % (h, w))
+    if params is None:
+        params = capi.ReflectionParams(**fields)
+    s = max(int(face_size) >> max(int(level), 0), 1)
+    out = np.zeros((int(n_probes), 6, s, s, 4), np.float32)
+    L = capi.lib()
+    rc = L.jpt_debug_reflection_prefilter(int(device_id), _ptr(a), int(frame_count), int(n_probes), int(face_size), int(probes_per_row), C.byref(params),
+                                          int(level), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_reflection_prefilter failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
 def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
     """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
     [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
@@ -267,6 +318,7 @@ class Context:
             self.h = h
         self.width = self.height = 0
         self._n_probes = 0   # what set_probes last gave the context: sizes read_probes / read_probe_sh
+        self._n_cubes = 0    # likewise set_reflection_probes: sizes read_reflection_probes / read_reflection
         self._keep = []
         if self._owned:
             _live_contexts.add(self)
@@ -550,6 +602,63 @@ class Context:
         out = np.zeros((max(n, 1), 9, 4), np.float32)
         self._ck(self._lib.jpt_read_probe_sh_f32(self.h, _ptr(out)), "jpt_read_probe_sh_f32")
         return out
+
+    # ---- reflection probes (jpt_set_reflection_probes, jpt_reflection_prefilter)
+    def set_reflection_probes(self, positions, face_size=0, probes_per_row=0):
+        """jpt_set_reflection_probes: float32 [n, 3] world positions; while they are present every render is a cube render, one strip of
+        six face_size x face_size faces per probe, probes_per_row to a row (reflection_image_size: the size for set_params).  None
+        frees them.  Waits for the renders already queued."""
+        if positions is None:
+            self._ck(self._lib.jpt_set_reflection_probes(self.h, None, 0, 0, 0), "jpt_set_reflection_probes")
+            self._n_cubes = 0
+            return
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        self._ck(self._lib.jpt_set_reflection_probes(self.h, _ptr(pos), len(pos), int(face_size), int(probes_per_row)), "jpt_set_reflection_probes")
+        self._n_cubes = len(pos)
+
+    def reflection_image_size(self):
+        """jpt_get_reflection_image_size: (width, height) of the image the context's reflection probes make"""
+        w, h = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.jpt_get_reflection_image_size(self.h, C.byref(w), C.byref(h)), "jpt_get_reflection_image_size")
+        return w.value, h.value
+
+    def read_reflection_probes(self, n_probes=None):
+        """jpt_read_reflection_probes: the positions the context holds, float32 [n, 3]; n_probes as in read_probes"""
+        n = self._n_cubes if n_probes is None else int(n_probes)
+        out = np.zeros((max(n, 1), 3), np.float32)   # (without probes the call answers E_STATE before it writes)
+        self._ck(self._lib.jpt_read_reflection_probes(self.h, _ptr(out)), "jpt_read_reflection_probes")
+        return out
+
+    def set_reflection_params(self, params=None, **fields):
+        """jpt_set_reflection_params: a capi.ReflectionParams, or its fields by name (n_levels, samples); nothing: the defaults"""
+        if params is None and fields:
+            params = capi.ReflectionParams(**fields)
+        self._ck(self._lib.jpt_set_reflection_params(self.h, None if params is None else C.byref(params)), "jpt_set_reflection_params")
+
+    def reflection_prefilter(self):
+        """jpt_reflection_prefilter: queue the GGX-prefiltered mip chain of every probe's strip of the accumulation; the accumulation
+        itself is not touched"""
+        self._ck(self._lib.jpt_reflection_prefilter(self.h), "jpt_reflection_prefilter")
+
+    def reflection_chain_size(self, level):
+        """jpt_get_reflection_chain_size: (face size of the level, where it starts in the chain in texels)"""
+        s, off = C.c_int32(0), C.c_uint64(0)
+        self._ck(self._lib.jpt_get_reflection_chain_size(self.h, int(level), C.byref(s), C.byref(off)), "jpt_get_reflection_chain_size")
+        return s.value, off.value
+
+    def read_reflection(self, level, n_probes=None) -> np.ndarray:
+        """jpt_read_reflection_f32: one level of the chain, float32 [n_probes, 6, s, s, 4], (r, g, b, 1) per texel"""
+        n = self._n_cubes if n_probes is None else int(n_probes)
+        s, _ = self.reflection_chain_size(level)
+        out = np.zeros((max(n, 1), 6, s, s, 4), np.float32)
+        self._ck(self._lib.jpt_read_reflection_f32(self.h, int(level), _ptr(out)), "jpt_read_reflection_f32")
+        return out
+
+    def reflection_timing(self):
+        """jpt_get_reflection_timing: (source chain ms, prefilter ms) of the last reflection_prefilter under set_kernel_timing"""
+        a, b = C.c_float(0), C.c_float(0)
+        self._ck(self._lib.jpt_get_reflection_timing(self.h, C.byref(a), C.byref(b)), "jpt_get_reflection_timing")
+        return a.value, b.value
 
     def set_material_extensions(self, flags):
         """jpt_set_material_extensions: capi.MATERIAL_EXT_NONE (default) or capi.MATERIAL_EXT_TRANSMISSION (padding[0:2] of every

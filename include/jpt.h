@@ -647,13 +647,76 @@ int jpt_read_lightmap_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: (r, 
  * projects, as with jpt_display).  jpt_read_probe_sh_f32 before a jpt_probe_project of the current probes and size: JPT_E_STATE.
  * Unknown flags: JPT_E_INVALID.  There is no jpt_multi_* form.
  * Out of scope: directional (per-texel SH) lightmaps, probe placement and detection of probes inside geometry (jpt_query_rays answers
- * that), band 3 and above, octahedral or cube tiles, half-float output. */
+ * that), band 3 and above, octahedral tiles, half-float output.  (Cube captures: jpt_set_reflection_probes, below.) */
 enum { JPT_PROBE_RADIANCE = 0, JPT_PROBE_IRRADIANCE = 1 };
 int jpt_set_probes(jpt_ctx *ctx, const float *position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row);
 int jpt_get_probe_image_size(jpt_ctx *ctx, int32_t *width, int32_t *height);
 int jpt_read_probes(jpt_ctx *ctx, float *position3);       /* what the context holds: n_probes * 3 floats */
 int jpt_probe_project(jpt_ctx *ctx, int32_t flags);
 int jpt_read_probe_sh_f32(jpt_ctx *ctx, float *out);       /* n_probes * 9 * 4 floats: (r, g, b, 0) per coefficient */
+
+/* ---- reflection probes: a cube capture per probe and a GGX-prefiltered mip chain made on the device (no reference counterpart; the
+ * ReflectionProbe that glossy and dynamic objects of a baked Godot scene read) ----
+ * With reflection probes present every render is a CUBE render.  With S = face_size, probe p owns the strip 6 S wide and S high whose
+ * top-left pixel is ((p % probes_per_row) * 6 S, (p / probes_per_row) * S); face f of the strip is the S x S square at x = f * S.  The
+ * image is probes_per_row * 6 S wide and ceil(n_probes / probes_per_row) * S high (jpt_get_reflection_image_size) -- the size to give
+ * jpt_set_params.  A pixel of a strip with index >= n_probes has no path: radiance 0, first-hit distance far, no ray counted, like a
+ * tile without a light probe.  Nothing downstream of ray generation knows: both kernels, the environment map and both sampling modes,
+ * emitter sampling, glass, the partition, the read-backs, jpt_display and jpt_meter work on a cube render as on a picture.
+ * The ray of texel (i, j) of face f, frame n (pinned; gdpathtracing_amd/csrc/jpt_cube.h; tests/np_reflection.py):
+ * the seeds and the jitter draw of a camera ray, taken and discarded; (xi0, xi1) from one pcg2d round of a copy of the seeds hashed
+ * with (0x1f83d9ab, 0x5be0cd19);
+ *     a = 2 ((i + xi0) / S) - 1,  b = 2 ((j + xi1) / S) - 1,  d = normalize3 of the OpenGL cube-map face table (Godot's):
+ *     face 0 = +X ( 1, -b, -a)   face 1 = -X (-1, -b,  a)   face 2 = +Y ( a,  1,  b)
+ *     face 3 = -Y ( a, -1, -b)   face 4 = +Z ( a, -b,  1)   face 5 = -Z (-a, -b, -1);        o = the probe's position, no offset.
+ * A texel's accumulated mean is thus its box-filtered radiance in face coordinates.
+ * Limits: face_size a power of two in 4..256, probes_per_row >= 1, a non-finite position: JPT_E_INVALID; n_probes in 1..2^20 and at
+ * most 2^26 pixels of image: JPT_E_LIMIT; host-only contexts: JPT_E_DEVICE after these checks.
+ * jpt_set_reflection_probes WAITS for the renders the context has queued, as jpt_set_probes does; (NULL, 0, 0, 0) frees the probes and
+ * the chain, after which a render is bit for bit that of a context that never held any.  The positions belong to the context: they
+ * survive scene changes, and jpt_scene_share does not copy them.  jpt_read_reflection_probes returns them (n_probes * 3 floats).
+ * The render calls return JPT_E_STATE, with a message, while reflection probes are present and the context also holds light probes
+ * (jpt_set_probes) or bake images, their image size is not jpt_set_params' width x height, the lens radius is > 0, the camera model
+ * is not JPT_CAMERA_PINHOLE or the denoising mode is JPT_DENOISE_TEMPORAL.  jpt_set_debug_steps ignores the probes.  jpt_denoise,
+ * jpt_query_pixels, jpt_bake_finish and jpt_probe_project return JPT_E_STATE while reflection probes are present.
+ *
+ * jpt_reflection_prefilter makes the mip chain, as an explicit call like jpt_probe_project: enqueued on the context's stream, it READS
+ * the accumulation and the frame count and writes only its own images; every render, buffer and read-back is bit for bit what it is
+ * without the call.  Level l of the chain has faces of s_l = S >> l texels and holds the radiance convolved with the GGX lobe of
+ * roughness l / (n_levels - 1): a material of roughness r reads mip r * (n_levels - 1).  The radiance is linear and not pre-multiplied
+ * by any BRDF term.  jpt_read_reflection_f32 returns one level: n_probes * 6 * s_l^2 float4 (r, g, b, 1), probe-major, then face,
+ * row, column; jpt_get_reflection_chain_size gives s_l and where the level starts in the chain, in texels (n_probes * 8 (S^2 - s_l^2)).
+ * jpt_set_reflection_params: n_levels in 2..log2(S) + 1, or 0 for every level down to 1 x 1 (the default); samples (K) in 8..256,
+ * default 64; NULL: the defaults; anything else JPT_E_INVALID (n_levels is checked against the probes the context holds then, and again
+ * by jpt_reflection_prefilter: JPT_E_STATE).
+ * Arithmetic (pinned; gdpathtracing_amd/csrc/jpt_reflection.h):
+ *   source chain per probe and face: level 0 = accum.rgb / (float)frame_count; level m + 1 = ((a + b) + (c + d)) * 0.25 of the 2 x 2
+ *     block, down to 1 x 1;
+ *   output level 0 = source level 0 with alpha 1; level l >= 1: alpha = l / (n_levels - 1) (the renderer's convention: roughness^2 is
+ *     alpha^2; the standard GGX NDF), a table of K samples made on the host in double: u1 = (k + 0.5) / K, u2 the base-2 radical
+ *     inverse of k, cos t = sqrt((1 - u1) / (1 + (alpha^2 - 1) u1)), phi = 2 pi u2, h = (sin t cos phi, sin t sin phi, cos t), L = (2 h_z
+ *     h_x, 2 h_z h_y, 2 h_z^2 - 1) (view = normal = the texel's direction); samples with L_z <= 0 are dropped; w = L_z / sum L_z; the
+ *     sample reads source level clamp(floor(0.5 log2(O_s / O_0) + 0.5) + 1, 0, log2 S) with O_s = 4 / (K D(h_z)), O_0 = 4 pi / (6 S^2);
+ *   output texel (f, i, j) of a level of size s: N = normalize3(face table at a = (2 (i + 0.5)) / s - 1, b likewise); the branch-free
+ *     tangent frame of Duff et al.; d = (T L_x + B L_y) + N L_z; the nearest texel of the source level in direction d (major axis by
+ *     |x| >= |y| && |x| >= |z|, else |y| >= |z|, else z); acc = acc + c * w_k for k ascending, from +0.
+ * JPT_E_STATE, with a message naming the call: no reflection probes; light probes or bake images beside them; their image size is not
+ * jpt_set_params'; no frame accumulated since the last reset; a denoising mode other than JPT_DENOISE_PROGRESSIVE; DEBUG_STEPS mode; a
+ * screen partition.  jpt_read_reflection_f32 before a jpt_reflection_prefilter of the current probes, size and parameters: JPT_E_STATE.
+ * jpt_get_reflection_timing: the kernel time of the last jpt_reflection_prefilter's two steps (the source chain, the prefilter) in ms,
+ * when it ran under jpt_set_kernel_timing (else JPT_E_STATE); it waits for them.
+ * Out of scope: box projection / parallax correction, blending between probes, bilinear or cross-face filtering of the source, the
+ * BRDF split-sum LUT, an octahedral layout, half-float or RGBE output, a jpt_multi_* form, anisotropy, any change to how materials
+ * are shaded. */
+typedef struct { int32_t n_levels; int32_t samples; } jpt_reflection_params;   /* defaults: every level down to 1x1 (0); 64 */
+int jpt_set_reflection_probes(jpt_ctx *ctx, const float *position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row);
+int jpt_get_reflection_image_size(jpt_ctx *ctx, int32_t *width, int32_t *height);
+int jpt_read_reflection_probes(jpt_ctx *ctx, float *position3);   /* what the context holds: n_probes * 3 floats */
+int jpt_set_reflection_params(jpt_ctx *ctx, const jpt_reflection_params *params);   /* NULL: the defaults */
+int jpt_reflection_prefilter(jpt_ctx *ctx);
+int jpt_get_reflection_chain_size(jpt_ctx *ctx, int32_t level, int32_t *face_size, uint64_t *offset_texels);
+int jpt_read_reflection_f32(jpt_ctx *ctx, int32_t level, float *out);   /* n_probes * 6 * s_l^2 float4 (r, g, b, 1), s_l = S >> level */
+int jpt_get_reflection_timing(jpt_ctx *ctx, float *chain_ms, float *prefilter_ms);
 
 /* Which device pipeline renders (no reference counterpart; both give the same image):
  *   WAVEFRONT          queue-based path tracer over the flattened 64-byte-node layout (default, fast);
@@ -1136,6 +1199,22 @@ int jpt_debug_probe_basis(int32_t tile_w, int32_t tile_h, int32_t flags, float *
  * JPT_DEVICE_HOST_ONLY: the same sum in plain loops on the host. */
 int jpt_debug_probe_project(int device_id, const float *accum4, uint32_t frame_count, int32_t n_probes, int32_t tile_w, int32_t tile_h,
                             int32_t probes_per_row, const float *table, float *sh_out);
+/* The first rays of a cube render's paths (jpt_set_reflection_probes) for every pixel of frame frame_index of the image the probes make
+ * (width = probes_per_row * 6 * face_size, height = ceil(n_probes / probes_per_row) * face_size): rays_out[6 (y * width + x) ..] = the
+ * origin, then the direction; six zeros for a pixel of a strip without a probe.  The arguments are checked as
+ * jpt_set_reflection_probes checks them.  device_id >= 0: the function the kernels inline, on that device; JPT_DEVICE_HOST_ONLY: the
+ * same, compiled for the host. */
+int jpt_debug_cube_rays(int device_id, const float *position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row,
+                        uint32_t frame_index, float *rays_out);
+/* The sample table jpt_reflection_prefilter makes on the host for output level `level` (1 .. n_levels - 1; n_levels 0: log2(face_size)
+ * + 1) of (face_size, n_levels, samples): table_out = samples * 4 floats (L_x, L_y, L_z, w), src_level_out = samples bytes.  The kept
+ * samples stand first, k ascending; the entries behind them are zeros with level byte 0xff, so the bytes say how many are kept. */
+int jpt_debug_reflection_samples(int32_t face_size, int32_t n_levels, int32_t samples, int32_t level, float *table_out, uint8_t *src_level_out);
+/* jpt_reflection_prefilter over a caller-made accumulation image (4 floats per pixel, the size the probes make) and frame count
+ * (>= 1): out = level `level` of the chain, n_probes * 6 * s^2 float4.  params NULL: the defaults.  device_id >= 0: the kernels
+ * jpt_reflection_prefilter launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions in plain loops on the host. */
+int jpt_debug_reflection_prefilter(int device_id, const float *accum4, uint32_t frame_count, int32_t n_probes, int32_t face_size,
+                                   int32_t probes_per_row, const jpt_reflection_params *params, int32_t level, float *out);
 /* The lens step alone, on the host, from caller-made randoms: for pinhole ray (origins3[3 i ..], dirs3[3 i ..]) and (xi2[2 i], xi2[2
  * i + 1]) the ray the lens of camera160 sends out (origins3_out, dirs3_out; either input ray kept when it does not point forward).
  * basis9_out (may be NULL): f, r, u.  The radius and the focus are taken as they are; a basis that is not finite is still returned,

@@ -854,6 +854,23 @@ class PathTracingCamera {
     void read_probes(float* position3) { check(ctx, jpt_read_probes(ctx, position3), "jpt_read_probes"); }
     void probe_project(int32_t flags) { check(ctx, jpt_probe_project(ctx, flags), "jpt_probe_project"); }
     void read_probe_sh(float* out) { check(ctx, jpt_read_probe_sh_f32(ctx, out), "jpt_read_probe_sh_f32"); }
+    // Reflection probes (ReflectionProbe): with them present every render is a cube render -- one strip of six face_size x face_size
+    // faces per probe, probes_per_row to a row; reflection_image_size: the size for set_params.  (nullptr, 0, 0, 0) frees them.
+    // reflection_prefilter makes the GGX-prefiltered mip chain on the device (mip = roughness * (n_levels - 1); linear radiance);
+    // read_reflection: one level, n_probes * 6 * s^2 float4 (r, g, b, 1) with s = face_size >> level.
+    void set_reflection_probes(const float* position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row)
+    {
+        check(ctx, jpt_set_reflection_probes(ctx, position3, n_probes, face_size, probes_per_row), "jpt_set_reflection_probes");
+    }
+    void reflection_image_size(int32_t* w, int32_t* h) { check(ctx, jpt_get_reflection_image_size(ctx, w, h), "jpt_get_reflection_image_size"); }
+    void read_reflection_probes(float* position3) { check(ctx, jpt_read_reflection_probes(ctx, position3), "jpt_read_reflection_probes"); }
+    void set_reflection_params(const jpt_reflection_params* params) { check(ctx, jpt_set_reflection_params(ctx, params), "jpt_set_reflection_params"); }
+    void reflection_prefilter() { check(ctx, jpt_reflection_prefilter(ctx), "jpt_reflection_prefilter"); }
+    void reflection_chain_size(int32_t level, int32_t* face_size, uint64_t* offset_texels)
+    {
+        check(ctx, jpt_get_reflection_chain_size(ctx, level, face_size, offset_texels), "jpt_get_reflection_chain_size");
+    }
+    void read_reflection(int32_t level, float* out) { check(ctx, jpt_read_reflection_f32(ctx, level, out), "jpt_read_reflection_f32"); }
     // jpt_denoise and its parameters (nullptr: the defaults): the spatially denoised view of the progressive accumulation
     void set_denoise_params(const jpt_denoise_params* params) { check(ctx, jpt_set_denoise_params(ctx, params), "jpt_set_denoise_params"); }
     void denoise() { check(ctx, jpt_denoise(ctx), "jpt_denoise"); }
