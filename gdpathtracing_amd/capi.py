@@ -73,6 +73,8 @@ SYMBOLS = [
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
     "jpt_query_rays", "jpt_query_rays_device", "jpt_query_pixels",
+    "jpt_scene_set_mesh_rig", "jpt_scene_pose_mesh", "jpt_scene_clear_mesh_rig", "jpt_multi_set_mesh_rig", "jpt_multi_pose_mesh", "jpt_multi_clear_mesh_rig",
+    "jpt_debug_skin",
 ]
 
 
@@ -83,6 +85,11 @@ class JptError(RuntimeError):
 class Surface(C.Structure):
     _fields_ = [("vertices", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p), ("indices", C.c_void_p),
                 ("n_vertices", C.c_int32), ("n_indices", C.c_int32)]
+
+
+class SurfaceRig(C.Structure):
+    """jpt_surface_rig: one surface's bones, weights and blend-shape deltas (jpt_scene_set_mesh_rig)"""
+    _fields_ = [("bones", C.c_void_p), ("weights", C.c_void_p), ("position_deltas", C.c_void_p), ("normal_deltas", C.c_void_p)]
 
 
 class DenoiseParams(C.Structure):
@@ -377,6 +384,14 @@ def lib():
         L.jpt_query_rays.argtypes = [vp, i32, vp, u32, vp, vp]
         L.jpt_query_rays_device.argtypes = [vp, i32, vp, u32, vp, vp]
         L.jpt_query_pixels.argtypes = [vp, vp, u32, vp]
+    if hasattr(L, "jpt_scene_pose_mesh") or "JPT_LIB" not in os.environ:
+        for n in ("jpt_scene_set_mesh_rig", "jpt_multi_set_mesh_rig"):
+            getattr(L, n).argtypes = [vp, u32, C.POINTER(Surface), C.POINTER(SurfaceRig), i32, i32, i32]
+        for n in ("jpt_scene_pose_mesh", "jpt_multi_pose_mesh"):
+            getattr(L, n).argtypes = [vp, u32, vp, u32, vp, u32]
+        L.jpt_scene_clear_mesh_rig.argtypes = [vp, u32]
+        L.jpt_multi_clear_mesh_rig.argtypes = [vp, u32]
+        L.jpt_debug_skin.argtypes = [C.c_int, vp, vp, u32, vp, vp, i32, vp, vp, i32, vp, u32, vp, vp, vp]
     _lib = L
     return L
 

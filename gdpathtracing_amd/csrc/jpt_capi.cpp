@@ -232,9 +232,21 @@ int upload_shadow(jpt_ctx* c, bool instances_only)
     return JPT_OK;
 }
 
+// The rigs of jpt_scene_set_mesh_rig leave with the scene they were set for (a queued pose may still read them: the refit stream first)
+void drop_mesh_rigs(jpt_ctx* c)
+{
+    if (c->mesh_rigs.empty()) return;
+    if (c->device >= 0 && c->refit_stream) {
+        (void)hipSetDevice(c->device);
+        (void)hipStreamSynchronize(c->refit_stream);
+    }
+    c->mesh_rigs.clear();
+}
+
 // host RefScene (+ flatten) -> device
 int upload_scene(jpt_ctx* c)
 {
+    drop_mesh_rigs(c);   // (before anything can refuse the scene: no rig outlives the scene it was set for)
     lights_stale(c, true);
     std::string err;
     if (!flatten(c->ref, c->wide, err)) return fail(c, JPT_E_INVALID, "flatten: " + err);
@@ -1190,6 +1202,7 @@ int jpt_scene_upload_reference_layout(jpt_ctx* c, const void* tri_geometry, uint
     const auto t0 = std::chrono::steady_clock::now();
     c->scene_ready = c->host_scene_ready = false;
     c->from_commit = false;
+    drop_mesh_rigs(c);   // the scene they were set for is gone from here on, whether or not this upload is accepted
     c->upload_note.clear();
     RefScene up;
     auto put = [](auto& vec, const void* src, uint32_t n) {
@@ -1269,6 +1282,7 @@ int jpt_scene_ties_exact(jpt_ctx* c, const char** why_out)
 int jpt_scene_begin(jpt_ctx* c)
 {
     if (!c) return JPT_E_INVALID;
+    drop_mesh_rigs(c);
     c->builder.begin();
     c->pending_materials.clear();
     c->pending_tex.clear();
@@ -1334,6 +1348,7 @@ int jpt_scene_commit(jpt_ctx* c, int32_t builder)
     const BuildMode mode = builder == JPT_BUILD_SAH ? BuildMode::Sah : (builder == JPT_BUILD_SAH_WATERTIGHT ? BuildMode::SahWatertight : BuildMode::ReferenceExact);
     const auto t0 = std::chrono::steady_clock::now();
     c->scene_ready = c->host_scene_ready = false;
+    drop_mesh_rigs(c);
     std::string err;
     if (!c->builder.commit(mode, c->ref, err))
         return fail(c, JPT_E_LIMIT, err);
@@ -1365,6 +1380,7 @@ int jpt_scene_share(jpt_ctx* dst, jpt_ctx* src)
     }
     const auto t0 = std::chrono::steady_clock::now();
     dst->scene_ready = dst->host_scene_ready = false;
+    drop_mesh_rigs(dst);
     dst->builder = src->builder;   // so that jpt_scene_set_instance_transform / update_tlas keep working on the copy
     dst->ref = src->ref;
     dst->tree = src->tree;
@@ -1639,13 +1655,14 @@ int ensure_mesh_refit(jpt_ctx* c)
     return JPT_OK;
 }
 
-}  // namespace
-
-int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+// The state and argument checks of a call that gives new arrays for a committed mesh (`call`: jpt_scene_update_mesh,
+// jpt_scene_set_mesh_rig): a JPT_BUILD_SAH_WATERTIGHT commit, the mesh's own topology, normals for every surface or for none
+// (with_normals: whether they came).  sv: the surfaces as the builder views them.
+int check_mesh_arrays(jpt_ctx* c, const char* call, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces, std::vector<SurfaceView>& sv,
+                      int& with_normals)
 {
-    if (!c) return JPT_E_INVALID;
     if (!c->host_scene_ready || c->building || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_update_mesh needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
+        return fail(c, JPT_E_STATE, std::string(call) + " needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
     if (!walks_nodes4(c))
         return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_REFERENCE_EXACT: its trees are the reference's own, which a refit "
                                     "would not keep (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
@@ -1654,8 +1671,9 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
                                     "tree of the committed vertices (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
     if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
     if (n_surfaces < 0 || (n_surfaces && !surfaces)) return fail(c, JPT_E_INVALID, "bad surface array");
-    std::vector<SurfaceView> sv((size_t)n_surfaces);
-    int with_normals = 0, with_vertices = 0;
+    sv.assign((size_t)n_surfaces, SurfaceView{});
+    int with_vertices = 0;
+    with_normals = 0;
     for (int32_t i = 0; i < n_surfaces; i++) {
         const jpt_surface& x = surfaces[i];
         if (x.n_vertices > 0) {
@@ -1667,11 +1685,66 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     }
     if (!c->builder.same_topology(mesh_id, sv.data(), n_surfaces)) return fail(c, JPT_E_INVALID, "topology changed: commit the scene again");
     if (with_normals != 0 && with_normals != with_vertices) return fail(c, JPT_E_INVALID, "give normals for every surface of the mesh or for none");
+    return JPT_OK;
+}
+
+// What jpt_scene_update_mesh and jpt_scene_pose_mesh do once the mesh's new vertices (and normals, or null: they stay) are on their way
+// into d_mesh_in behind its bounds head, on the refit stream and behind the pipeline drain: the mesh's records refitted from them,
+// then the instance level over the new root boxes with the current transforms (`dev_transforms`: the stage's copy, as the device sees
+// it), as jpt_scene_refit_tlas does; the stage `st` of mesh_stage is free again once all of it has run.
+int queue_mesh_refit(jpt_ctx* c, const jpt_ctx::MeshRefit& mr, const float* verts, const float* normals, const float* dev_transforms, int st,
+                     std::chrono::steady_clock::time_point t0)
+{
+    hipStream_t rs = c->refit_stream;
+    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    MeshRefitArgs a;
+    a.bounds = reinterpret_cast<int32_t*>(c->d_mesh_in.p);
+    a.verts = verts;
+    a.normals = normals;
+    a.vidx = c->d_tri_vidx.p;
+    a.tri_first = mr.tri_first;
+    a.n_tris = mr.n_tris;
+    const SceneBufs& b = c->dev;
+    a.wtris = b.wtris.p;
+    a.shade = b.shade_tris.p;
+    a.nodes4 = b.nodes4.p;
+    a.nodesq = b.nodesq.p;
+    a.order = c->d_mesh_order.p;
+    a.level_start = c->d_mesh_levels.p + mr.level_first;
+    a.root4 = mr.root4;
+    a.bvh = b.bvh.p;
+    a.bvh_root = mr.bvh_root;
+    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->ref.inst_cut_boxes.empty();
+    a.cut_range = cuts ? b.cut_range.p : nullptr;
+    a.instances = b.set[0].inst.p;   // (blas_index is the same in every copy of the instance level)
+    a.n_instances = n_inst;
+    launch_mesh_refit(rs, a, c->mesh_levels_h.data() + mr.level_first, mr.n_levels);
+    HIP_TRY(c, hipGetLastError());
+    // the instance level over the new root boxes, with the current transforms, as jpt_scene_refit_tlas does
+    const int rc = queue_instance_refit(c, dev_transforms, n_inst);
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipEventRecord(c->mesh_stage.copied[st], rs));
+    c->cull_boxes_current = false;   // the host's TLAS boxes are stale: no sky cull until the next upload
+    c->refit_active = true;
+    c->ds.x.tlas_current = false;
+    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return JPT_OK;
+}
+
+}  // namespace
+
+int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+{
+    if (!c) return JPT_E_INVALID;
+    std::vector<SurfaceView> sv;
+    int with_normals = 0;
+    int rc = check_mesh_arrays(c, "jpt_scene_update_mesh", mesh_id, surfaces, n_surfaces, sv, with_normals);
+    if (rc != JPT_OK) return rc;
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the update runs on the device");
     if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_mesh_refit(c);
+    rc = ensure_mesh_refit(c);
     if (rc != JPT_OK) return rc;
     c->mesh_deformed = true;   // (the host's arrays describe the committed vertices from here on)
     const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
@@ -1711,38 +1784,147 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     HIP_TRY(c, hipEventRecord(c->ev_mesh_drain, s));
     HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_mesh_drain, 0));
     HIP_TRY(c, hipMemcpyAsync(c->d_mesh_in.p, h, dev_bytes, hipMemcpyHostToDevice, rs));
-    MeshRefitArgs a;
-    a.bounds = reinterpret_cast<int32_t*>(c->d_mesh_in.p);
-    a.verts = reinterpret_cast<const float*>(c->d_mesh_in.p + head);
-    a.normals = with_normals ? reinterpret_cast<const float*>(c->d_mesh_in.p + head + vbytes) : nullptr;
-    a.vidx = c->d_tri_vidx.p;
-    a.tri_first = mr.tri_first;
-    a.n_tris = mr.n_tris;
-    const SceneBufs& b = c->dev;
-    a.wtris = b.wtris.p;
-    a.shade = b.shade_tris.p;
-    a.nodes4 = b.nodes4.p;
-    a.nodesq = b.nodesq.p;
-    a.order = c->d_mesh_order.p;
-    a.level_start = c->d_mesh_levels.p + mr.level_first;
-    a.root4 = mr.root4;
-    a.bvh = b.bvh.p;
-    a.bvh_root = mr.bvh_root;
-    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->ref.inst_cut_boxes.empty();
-    a.cut_range = cuts ? b.cut_range.p : nullptr;
-    a.instances = b.set[0].inst.p;   // (blas_index is the same in every copy of the instance level)
-    a.n_instances = n_inst;
-    launch_mesh_refit(rs, a, c->mesh_levels_h.data() + mr.level_first, mr.n_levels);
-    HIP_TRY(c, hipGetLastError());
-    // the instance level over the new root boxes, with the current transforms, as jpt_scene_refit_tlas does
-    rc = queue_instance_refit(c, reinterpret_cast<const float*>(hdev + dev_bytes), n_inst);
+    return queue_mesh_refit(c, mr, reinterpret_cast<const float*>(c->d_mesh_in.p + head),
+                            with_normals ? reinterpret_cast<const float*>(c->d_mesh_in.p + head + vbytes) : nullptr,
+                            reinterpret_cast<const float*>(hdev + dev_bytes), st, t0);
+}
+
+int jpt_scene_set_mesh_rig(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* bind, const jpt_surface_rig* rigs, int32_t n_surfaces, int32_t influences,
+                           int32_t n_blend_shapes)
+{
+    if (!c) return JPT_E_INVALID;
+    std::vector<SurfaceView> sv;
+    int with_normals = 0;
+    int rc = check_mesh_arrays(c, "jpt_scene_set_mesh_rig", mesh_id, bind, n_surfaces, sv, with_normals);
     if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->mesh_stage.copied[st], rs));
-    c->cull_boxes_current = false;   // the host's TLAS boxes are stale: no sky cull until the next upload
-    c->refit_active = true;
-    c->ds.x.tlas_current = false;
-    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (n_surfaces && !rigs) return fail(c, JPT_E_INVALID, "jpt_scene_set_mesh_rig: bad rig array");
+    std::vector<SkinPiece> pieces((size_t)n_surfaces);
+    for (int32_t i = 0; i < n_surfaces; i++) {
+        SkinPiece& x = pieces[(size_t)i];
+        x.n_vertices = bind[i].n_vertices;
+        x.positions = bind[i].vertices;
+        x.normals = bind[i].normals;
+        x.bones = rigs[i].bones;
+        x.weights = rigs[i].weights;
+        x.dpos = rigs[i].position_deltas;
+        x.dnrm = rigs[i].normal_deltas;
+    }
+    SkinRigInfo info;
+    std::string why;
+    rc = check_skin_rig("jpt_scene_set_mesh_rig", pieces.data(), n_surfaces, influences, n_blend_shapes, with_normals != 0, info, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the rig is kept on the device");
+    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = ensure_mesh_refit(c);
+    if (rc != JPT_OK) return rc;
+    {
+        auto old = c->mesh_rigs.find(mesh_id);
+        if (old != c->mesh_rigs.end()) {
+            if (old->second.d_rig.p) HIP_TRY(c, hipStreamSynchronize(c->refit_stream));   // (a queued pose may still read the rig this one replaces)
+            c->mesh_rigs.erase(old);
+        }
+    }
+    jpt_ctx::MeshRig& rig = c->mesh_rigs[mesh_id];
+    rig.info = info;
+    if (!c->mesh_refit[mesh_id].has_tree || info.bytes == 0) return JPT_OK;   // no instance names the mesh: nothing of it on the device
+    std::vector<char> block(info.bytes);
+    pack_skin_rig(info, pieces.data(), n_surfaces, block.data());
+    hipError_t e = rig.d_rig.resize(info.bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(rig.d_rig.p, block.data(), info.bytes, hipMemcpyHostToDevice, c->refit_stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->refit_stream);   // pageable host memory
+    if (e != hipSuccess) {
+        c->mesh_rigs.erase(mesh_id);
+        return hip_fail(c, e, "jpt_scene_set_mesh_rig: the rig's copy");
+    }
     return JPT_OK;
+}
+
+int jpt_scene_clear_mesh_rig(jpt_ctx* c, uint32_t mesh_id)
+{
+    if (!c) return JPT_E_INVALID;
+    auto it = c->mesh_rigs.find(mesh_id);
+    if (it == c->mesh_rigs.end()) return JPT_OK;
+    if (it->second.d_rig.p) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        if (c->refit_stream) HIP_TRY(c, hipStreamSynchronize(c->refit_stream));   // (a queued pose may still read it)
+    }
+    c->mesh_rigs.erase(it);
+    return JPT_OK;
+}
+
+int jpt_scene_pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
+{
+    if (!c) return JPT_E_INVALID;
+    // jpt_scene_update_mesh's state rules, on their own account: a rig is dropped with its scene, but a pose does not rely on that
+    if (!c->host_scene_ready || c->building || !c->from_commit || !walks_nodes4(c) || c->tree != JPT_TREE_NATIVE_WATERTIGHT)
+        return fail(c, JPT_E_STATE, "jpt_scene_pose_mesh needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
+    auto it = c->mesh_rigs.find(mesh_id);
+    if (it == c->mesh_rigs.end()) return fail(c, JPT_E_STATE, "jpt_scene_pose_mesh: the mesh has no rig (jpt_scene_set_mesh_rig; a commit or an upload drops it)");
+    const jpt_ctx::MeshRig& rig = it->second;
+    const SkinRigInfo& info = rig.info;
+    std::vector<SkinShape> active;
+    std::string why;
+    int rc = check_skin_pose("jpt_scene_pose_mesh", info, bone_transforms12, n_bones, blend_weights, n_blend_weights, active, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the pose runs on the device");
+    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(c, hipSetDevice(c->device));
+    rc = ensure_mesh_refit(c);
+    if (rc != JPT_OK) return rc;
+    const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
+    // no instance names the mesh: the device holds nothing of it, nothing changes anywhere and the host's copy of the scene stays current
+    if (!mr.has_tree || !rig.d_rig.p) return JPT_OK;
+    c->mesh_deformed = true;   // (as jpt_scene_update_mesh: the host's arrays describe the committed vertices from here on)
+    hipStream_t s = c->stream, rs = c->refit_stream;
+    // staging: [6 ordered keys + pad: 32 B][palette: the bones the rig can name][active shapes, padded to 16 B][transforms]; the first
+    // three parts are copied to the head of d_mesh_in, where the vertices and normals the skin kernel writes follow them
+    const size_t nv = info.n_vertices;
+    const uint32_t n_pal = info.influences ? (uint32_t)(info.max_bone + 1) : 0u;
+    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    const size_t head = 32, pbytes = (size_t)n_pal * 48, abytes = (active.size() * sizeof(SkinShape) + 15u) & ~(size_t)15u;
+    const size_t in_bytes = head + pbytes + abytes, vbytes = (nv * 3 * sizeof(float) + 15u) & ~(size_t)15u, nbytes = info.with_normals ? vbytes : 0;
+    const size_t dev_bytes = in_bytes + vbytes + nbytes, tbytes = (size_t)n_inst * 12 * sizeof(float);
+    int st = 0;
+    HIP_TRY(c, c->mesh_stage.next(in_bytes + tbytes, st));
+    if (!c->ev_mesh_drain) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_drain, hipEventDisableTiming));
+    char* h = c->mesh_stage.buf[st].as<char>();
+    {
+        int32_t keys[8] = {ordered_key(FLT_MAX), ordered_key(FLT_MAX), ordered_key(FLT_MAX),
+                           ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), 0, 0};
+        std::memcpy(h, keys, sizeof keys);
+        if (pbytes) std::memcpy(h + head, bone_transforms12, pbytes);
+        std::memset(h + head + pbytes, 0, abytes);
+        if (!active.empty()) std::memcpy(h + head + pbytes, active.data(), active.size() * sizeof(SkinShape));
+        for (uint32_t i = 0; i < n_inst; i++) std::memcpy(h + in_bytes + (size_t)i * 48, c->builder.instance_transform(i), 48);
+    }
+    if (c->d_mesh_in.n < dev_bytes) {
+        HIP_TRY(c, hipStreamSynchronize(rs));   // (an earlier update may still read the old buffer)
+        HIP_TRY(c, c->d_mesh_in.resize(dev_bytes));
+    }
+    char* hdev = nullptr;
+    HIP_TRY(c, hipHostGetDevicePointer((void**)&hdev, h, 0));
+    // d_mesh_in is read and written by work on the refit stream alone (the copies and kernels of the updates and poses; no render, read-back or
+    // instance refit touches it), and that stream runs in order: the pose's copy and the skin kernel are queued AHEAD of the drain wait,
+    // so they run beside the renders still in flight; only the refit of the shared records waits for them.
+    HIP_TRY(c, hipMemcpyAsync(c->d_mesh_in.p, h, in_bytes, hipMemcpyHostToDevice, rs));
+    SkinArgs a;
+    a.rig = skin_rig_view(info, rig.d_rig.p);
+    a.influences = info.influences;
+    a.palette = reinterpret_cast<const float*>(c->d_mesh_in.p + head);
+    a.n_bones = n_pal;
+    a.active = reinterpret_cast<const SkinShape*>(c->d_mesh_in.p + head + pbytes);
+    a.n_active = (uint32_t)active.size();
+    a.verts_out = reinterpret_cast<float*>(c->d_mesh_in.p + in_bytes);
+    a.normals_out = info.with_normals ? reinterpret_cast<float*>(c->d_mesh_in.p + in_bytes + vbytes) : nullptr;
+    launch_mesh_skin(rs, a);
+    HIP_TRY(c, hipGetLastError());
+    // The BLAS records, triangle records and root boxes are shared by every copy of the instance level: one pipeline drain on the
+    // device, as jpt_scene_update_mesh
+    HIP_TRY(c, hipEventRecord(c->ev_mesh_drain, s));
+    HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_mesh_drain, 0));
+    return queue_mesh_refit(c, mr, a.verts_out, a.normals_out, reinterpret_cast<const float*>(hdev + in_bytes), st, t0);
 }
 
 int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void* nodesq_out, uint32_t node_capacity, void* tris_out,

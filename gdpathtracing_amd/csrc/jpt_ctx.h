@@ -2,6 +2,9 @@
 // (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp).
 #pragma once
 #include "../../include/jpt.h"
+
+#include <map>
+
 #include "jpt_builder.h"
 #include "jpt_denoise.h"
 #include "jpt_display.h"
@@ -340,6 +343,13 @@ struct jpt_ctx {
     StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
     hipEvent_t ev_mesh_drain = nullptr;
     bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
+    // posing committed meshes on the device (jpt_scene_set_mesh_rig / jpt_scene_pose_mesh): per rigged mesh the rig's layout and, when
+    // an instance names the mesh, its block on the device (jpt_kernels_skin.hip); dropped by jpt_scene_begin and every upload
+    struct MeshRig {
+        SkinRigInfo info;
+        DevBuf<char> d_rig;   // empty for a mesh no instance names
+    };
+    std::map<uint32_t, MeshRig> mesh_rigs;
     PinnedBuf h_ldr_pinned;    // the split read-back of the display image
     PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
     hipEvent_t ev_readback = nullptr;

@@ -799,6 +799,72 @@ int jpt_debug_reflection_prefilter(int device_id, const float* accum4, uint32_t 
     return rc;
 }
 
+int jpt_debug_skin(int device_id, const float* bind_positions3, const float* bind_normals3, uint32_t n_vertices, const int32_t* bones, const float* weights,
+                   int32_t influences, const float* position_deltas, const float* normal_deltas, int32_t n_blend_shapes, const float* bone_transforms12,
+                   uint32_t n_bones, const float* blend_weights, float* positions3_out, float* normals3_out)
+{
+    if (!bind_positions3 || !positions3_out || (bind_normals3 && !normals3_out) || n_vertices == 0 || n_vertices > 0x7fffffffu) {
+        g_debug_error = "jpt_debug_skin: null argument or no vertices";
+        return JPT_E_INVALID;
+    }
+    SkinPiece piece;
+    piece.n_vertices = (int32_t)n_vertices;
+    piece.positions = bind_positions3;
+    piece.normals = bind_normals3;
+    piece.bones = bones;
+    piece.weights = weights;
+    piece.dpos = position_deltas;
+    piece.dnrm = normal_deltas;
+    SkinRigInfo info;
+    int rc = check_skin_rig("jpt_debug_skin", &piece, 1, influences, n_blend_shapes, bind_normals3 != nullptr, info, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    std::vector<SkinShape> active;
+    rc = check_skin_pose("jpt_debug_skin", info, bone_transforms12, n_bones, blend_weights, (uint32_t)n_blend_shapes, active, g_debug_error);
+    if (rc != JPT_OK) return rc;
+    std::vector<char> block(info.bytes);
+    pack_skin_rig(info, &piece, 1, block.data());
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        skin_host(skin_rig_view(info, block.data()), influences, active.data(), (uint32_t)active.size(), bone_transforms12, positions3_out, normals3_out);
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // one block: the rig, the palette, the active shapes, the outputs -- every part 16-byte aligned
+    auto up16 = [](size_t x) { return (x + 15u) & ~(size_t)15u; };
+    const uint32_t n_pal = influences ? n_bones : 0u;
+    const size_t b_pal = (size_t)n_pal * 48, b_act = up16(active.size() * sizeof(SkinShape)), b_out = up16((size_t)n_vertices * 3 * sizeof(float));
+    const size_t o_pal = info.bytes, o_act = o_pal + b_pal, o_pos = o_act + b_act, o_nrm = o_pos + b_out, total = o_nrm + (bind_normals3 ? b_out : 0);
+    char* d_all = nullptr;
+    if ((e = hipMalloc((void**)&d_all, total)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    if ((e = hipMemcpy(d_all, block.data(), info.bytes, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && b_pal && (e = hipMemcpy(d_all + o_pal, bone_transforms12, b_pal, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && !active.empty() && (e = hipMemcpy(d_all + o_act, active.data(), active.size() * sizeof(SkinShape), hipMemcpyHostToDevice)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        SkinArgs a;
+        a.rig = skin_rig_view(info, d_all);
+        a.influences = influences;
+        a.palette = reinterpret_cast<const float*>(d_all + o_pal);
+        a.n_bones = n_pal;
+        a.active = reinterpret_cast<const SkinShape*>(d_all + o_act);
+        a.n_active = (uint32_t)active.size();
+        a.verts_out = reinterpret_cast<float*>(d_all + o_pos);
+        a.normals_out = bind_normals3 ? reinterpret_cast<float*>(d_all + o_nrm) : nullptr;
+        launch_mesh_skin(nullptr, a);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "mesh_skin_kernel");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(positions3_out, d_all + o_pos, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && bind_normals3 && (e = hipMemcpy(normals3_out, d_all + o_nrm, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
 int jpt_debug_bake_raster(int device_id, const jpt_surface* surface, const float* uv2, const float* transform12, int32_t width, int32_t height,
                           float* position4_out, float* normal4_out)
 {

@@ -16,6 +16,7 @@
 #include "jpt_probe.h"
 #include "jpt_reflection.h"
 #include "jpt_shade.h"
+#include "jpt_skin.h"
 #include "jpt_types.h"
 
 namespace jpt {
@@ -411,6 +412,49 @@ struct MeshRefitArgs {
     uint32_t n_instances = 0;
 };
 void launch_mesh_refit(hipStream_t stream, const MeshRefitArgs& args, const uint32_t* h_level_start, uint32_t n_levels);
+
+// Posing a committed mesh on the device (jpt_scene_pose_mesh, jpt_kernels_skin.hip; the arithmetic: jpt_skin.h): one thread per vertex
+// of the mesh writes packed float3 positions -- and normals, when the rig has them -- where the mesh refit reads them
+// (MeshRefitArgs::verts / normals); the lanes gather their bones from the palette in global memory.  Every pointer is a device pointer, 16-byte aligned; no bone index of the rig
+// may reach n_bones (the host checks: check_skin_pose).
+struct SkinArgs {
+    SkinRig rig;
+    int32_t influences = 0;               // 0, 4 or 8
+    const float* palette = nullptr;       // n_bones x 12 floats (transform12 layout)
+    uint32_t n_bones = 0;
+    const SkinShape* active = nullptr;    // the pose's shapes with a weight != 0, ascending
+    uint32_t n_active = 0;
+    float* verts_out = nullptr;
+    float* normals_out = nullptr;         // written when rig.bind_nrm is set
+};
+void launch_mesh_skin(hipStream_t stream, const SkinArgs& args);
+// The host halves, shared by the context calls and jpt_debug_skin.  A rig arrives as pieces (one per surface, host pointers, vertices end
+// to end); check_skin_rig runs jpt_scene_set_mesh_rig's argument checks on them (`with_normals`: the bind pose carries normals) and lays
+// the rig out as one block of `bytes`; pack_skin_rig fills such a block (bone indices to 16 bits, deltas shape-major over the whole
+// mesh); skin_rig_view points into a block at `base` (host or device).  check_skin_pose runs jpt_scene_pose_mesh's checks and compacts
+// the blend weights into the active list.
+struct SkinPiece {
+    int32_t n_vertices = 0;
+    const float* positions = nullptr;
+    const float* normals = nullptr;
+    const int32_t* bones = nullptr;
+    const float* weights = nullptr;
+    const float* dpos = nullptr;
+    const float* dnrm = nullptr;
+};
+struct SkinRigInfo {
+    uint32_t n_vertices = 0;
+    int32_t influences = 0, n_shapes = 0;
+    int32_t max_bone = -1;                // the largest bone index the rig names (-1: none)
+    bool with_normals = false, with_dnrm = false;
+    size_t off_pos = 0, off_nrm = 0, off_bones = 0, off_weights = 0, off_dpos = 0, off_dnrm = 0, bytes = 0;
+};
+int check_skin_rig(const char* call, const SkinPiece* pieces, int32_t n_pieces, int32_t influences, int32_t n_shapes, bool with_normals,
+                   SkinRigInfo& info, std::string& why);
+void pack_skin_rig(const SkinRigInfo& info, const SkinPiece* pieces, int32_t n_pieces, char* out);
+SkinRig skin_rig_view(const SkinRigInfo& info, const char* base);
+int check_skin_pose(const char* call, const SkinRigInfo& info, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights,
+                    uint32_t n_blend_weights, std::vector<SkinShape>& active, std::string& why);
 
 // one dispatch of temporal_reprojection.glsl over a whole image (jpt_kernels_post.hip): screen rgba8 in/out, depth
 // read-only, hist1 / hist2 the two rgba32f history images

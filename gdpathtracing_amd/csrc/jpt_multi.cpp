@@ -229,6 +229,40 @@ int jpt_multi_update_mesh(jpt_multi* m, uint32_t mesh_id, const jpt_surface* sur
     return JPT_OK;
 }
 
+int jpt_multi_set_mesh_rig(jpt_multi* m, uint32_t mesh_id, const jpt_surface* bind, const jpt_surface_rig* rigs, int32_t n_surfaces, int32_t influences,
+                           int32_t n_blend_shapes)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        (void)hipSetDevice(m->devices[r]);
+        const int rc = jpt_scene_set_mesh_rig(m->ctx[r], mesh_id, bind, rigs, n_surfaces, influences, n_blend_shapes);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
+int jpt_multi_pose_mesh(jpt_multi* m, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        (void)hipSetDevice(m->devices[r]);
+        const int rc = jpt_scene_pose_mesh(m->ctx[r], mesh_id, bone_transforms12, n_bones, blend_weights, n_blend_weights);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
+int jpt_multi_clear_mesh_rig(jpt_multi* m, uint32_t mesh_id)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        (void)hipSetDevice(m->devices[r]);
+        const int rc = jpt_scene_clear_mesh_rig(m->ctx[r], mesh_id);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_update_reference_tlas(jpt_multi* m, const void* blas_instances, uint32_t n_instances, const void* tlas_nodes, uint32_t n_tlas_nodes)
 {
     if (!m) return JPT_E_INVALID;

@@ -38,6 +38,49 @@ def _update_surfaces(mesh: scenes.Mesh, with_normals: bool = True):
     return arr
 
 
+class SurfaceRig:
+    """One surface's part of a rig (jpt_surface_rig): bones int32 [n_vertices, influences] and weights float32 of the same shape (None
+    without bones), position_deltas float32 [n_blend_shapes, n_vertices, 3] (None without shapes), normal_deltas the same or None."""
+
+    def __init__(self, bones=None, weights=None, position_deltas=None, normal_deltas=None):
+        c = lambda a, t: None if a is None else np.ascontiguousarray(a, dtype=t)
+        self.bones, self.weights = c(bones, np.int32), c(weights, np.float32)
+        self.position_deltas, self.normal_deltas = c(position_deltas, np.float32), c(normal_deltas, np.float32)
+
+
+def _rig_surfaces(rigs):
+    """jpt_surface_rig array of a list of SurfaceRig; the caller keeps `rigs` alive"""
+    arr = (capi.SurfaceRig * len(rigs))()
+    for i, r in enumerate(rigs):
+        arr[i].bones, arr[i].weights = _ptr(r.bones), _ptr(r.weights)
+        arr[i].position_deltas, arr[i].normal_deltas = _ptr(r.position_deltas), _ptr(r.normal_deltas)
+    return arr
+
+
+def _pose_arrays(bone_transforms12, blend_weights):
+    b = None if bone_transforms12 is None else np.ascontiguousarray(bone_transforms12, dtype=np.float32).reshape(-1, 12)
+    w = None if blend_weights is None else np.ascontiguousarray(blend_weights, dtype=np.float32).reshape(-1)
+    return b, (0 if b is None else len(b)), w, (0 if w is None else len(w))
+
+
+def debug_skin(device_id, bind_positions, bind_normals, rig: "SurfaceRig", influences, n_blend_shapes, bone_transforms12=None, blend_weights=None):
+    """jpt_debug_skin: jpt_scene_pose_mesh's arithmetic alone on one caller-made surface -- (positions, normals) float32 [n_vertices, 3]
+    each (normals None without bind normals).  device_id -1: the host's copy of the functions, in plain loops.  A refusal raises
+    capi.JptError with the library's code as its second argument."""
+    L = capi.lib()
+    pos = np.ascontiguousarray(bind_positions, dtype=np.float32).reshape(-1, 3)
+    nrm = None if bind_normals is None else np.ascontiguousarray(bind_normals, dtype=np.float32).reshape(-1, 3)
+    b, nb, w, _ = _pose_arrays(bone_transforms12, blend_weights)
+    out_p = np.zeros_like(pos)
+    out_n = None if nrm is None else np.zeros_like(nrm)
+    rc = L.jpt_debug_skin(device_id, _ptr(pos), _ptr(nrm), len(pos), _ptr(rig.bones), _ptr(rig.weights), influences, _ptr(rig.position_deltas),
+                          _ptr(rig.normal_deltas), n_blend_shapes, _ptr(b), nb, _ptr(w), _ptr(out_p), _ptr(out_n))
+    if rc != capi.OK:
+        msg = L.jpt_debug_last_error()
+        raise capi.JptError("jpt_debug_skin failed (%d): %s" % (rc, msg.decode() if msg else ""), rc)
+    return out_p, out_n
+
+
 @atexit.register
 def _close_live_contexts():
     # contexts the caller forgot to close are destroyed while the HIP runtime is still up (this handler is registered
@@ -448,6 +491,23 @@ class Context:
         the device (jpt_scene_update_mesh); no host rebuild, no synchronisation."""
         arr = _update_surfaces(mesh, with_normals)
         self._ck(self._lib.jpt_scene_update_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_scene_update_mesh")
+
+    def set_mesh_rig(self, mesh_id: int, bind: scenes.Mesh, rigs, influences: int, n_blend_shapes: int, with_normals: bool = True):
+        """The rig of a committed mesh, kept on the device (jpt_scene_set_mesh_rig): `bind` is the bind-pose mesh (same surfaces, vertex
+        counts and index arrays as committed; with_normals False: the committed normals stay), `rigs` one SurfaceRig per surface."""
+        arr, rarr = _update_surfaces(bind, with_normals), _rig_surfaces(rigs)
+        self._ck(self._lib.jpt_scene_set_mesh_rig(self.h, mesh_id, arr, rarr, len(bind.surfaces), influences, n_blend_shapes), "jpt_scene_set_mesh_rig")
+
+    def pose_mesh(self, mesh_id: int, bone_transforms12=None, blend_weights=None):
+        """One pose of a rigged mesh (jpt_scene_pose_mesh): float32 [n_bones, 12] bone transforms (bone pose x inverse bind, transform12
+        layout) and one weight per blend shape; the vertices are computed and the mesh refitted on the device, no synchronisation."""
+        b, nb, w, nw = _pose_arrays(bone_transforms12, blend_weights)
+        self._ck(self._lib.jpt_scene_pose_mesh(self.h, mesh_id, _ptr(b), nb, _ptr(w), nw), "jpt_scene_pose_mesh")
+
+    def clear_mesh_rig(self, mesh_id: int):
+        self._ck(self._lib.jpt_scene_clear_mesh_rig(self.h, mesh_id), "jpt_scene_clear_mesh_rig")
+
+    debug_skin = staticmethod(debug_skin)
 
     def debug_mesh_records(self, mesh_id: int):
         """The device's records of one mesh (jpt_debug_mesh_records): dict with the info words and, when the device holds a
@@ -956,6 +1016,19 @@ class GeometryGroup3D:
             self.scene.meshes[mesh_index] = mesh
         self.ctx.update_mesh(mesh_index, mesh)
 
+    def set_mesh_rig(self, mesh_index: int, rigs, influences: int, n_blend_shapes: int, bind: Optional[scenes.Mesh] = None, with_normals: bool = True):
+        """The rig of one of the group's meshes (Skeleton3D / Skin and blend shapes): `bind` (default: the scene's own mesh) is its bind pose"""
+        self.ctx.set_mesh_rig(mesh_index, self.scene.meshes[mesh_index] if bind is None else bind, rigs, influences, n_blend_shapes, with_normals)
+
+    def pose_mesh(self, mesh_index: int, bone_transforms12=None, blend_weights=None):
+        """A rigged mesh posed on the device, without build() again; the scene's own mesh object keeps its bind pose"""
+        self.ctx.pose_mesh(mesh_index, bone_transforms12, blend_weights)
+
+    def clear_mesh_rig(self, mesh_index: int):
+        self.ctx.clear_mesh_rig(mesh_index)
+
+    debug_skin = staticmethod(debug_skin)
+
     def get_triangles_geometry_buffer(self):            # geometry_group3d.cpp:40
         return self.ctx.reference_buffer(capi.BUF_TRI_GEOMETRY, wire.TRI_GEOMETRY)
 
@@ -1121,6 +1194,23 @@ class MultiContext:
     def update_mesh(self, mesh_id: int, mesh: scenes.Mesh, with_normals: bool = True):
         arr = _update_surfaces(mesh, with_normals)
         self._ck(self._lib.jpt_multi_update_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_multi_update_mesh")
+
+    def set_mesh_rig(self, mesh_id: int, bind: scenes.Mesh, rigs, influences: int, n_blend_shapes: int, with_normals: bool = True):
+        """The rig of a committed mesh, kept on the device (jpt_multi_set_mesh_rig: every rank's replica): `bind` is the bind-pose mesh (same surfaces, vertex
+        counts and index arrays as committed; with_normals False: the committed normals stay), `rigs` one SurfaceRig per surface."""
+        arr, rarr = _update_surfaces(bind, with_normals), _rig_surfaces(rigs)
+        self._ck(self._lib.jpt_multi_set_mesh_rig(self.h, mesh_id, arr, rarr, len(bind.surfaces), influences, n_blend_shapes), "jpt_multi_set_mesh_rig")
+
+    def pose_mesh(self, mesh_id: int, bone_transforms12=None, blend_weights=None):
+        """One pose of a rigged mesh (jpt_multi_pose_mesh: every rank's replica): float32 [n_bones, 12] bone transforms (bone pose x inverse bind, transform12
+        layout) and one weight per blend shape; the vertices are computed and the mesh refitted on the device, no synchronisation."""
+        b, nb, w, nw = _pose_arrays(bone_transforms12, blend_weights)
+        self._ck(self._lib.jpt_multi_pose_mesh(self.h, mesh_id, _ptr(b), nb, _ptr(w), nw), "jpt_multi_pose_mesh")
+
+    def clear_mesh_rig(self, mesh_id: int):
+        self._ck(self._lib.jpt_multi_clear_mesh_rig(self.h, mesh_id), "jpt_multi_clear_mesh_rig")
+
+    debug_skin = staticmethod(debug_skin)
 
     def set_params(self, width, height, max_bounces=4, accum_mode=capi.ACCUM_REF_LDR8, sampler_mode=0):
         self._ck(self._lib.jpt_multi_set_params(self.h, width, height, max_bounces, accum_mode, sampler_mode), "jpt_multi_set_params")

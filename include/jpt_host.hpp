@@ -220,6 +220,13 @@ struct Surface {
     std::vector<int32_t> indices;
 };
 
+// One surface's part of a rig (jpt_surface_rig): Mesh::ARRAY_BONES / ARRAY_WEIGHTS (influences per vertex) and the blend shapes as
+// deltas, shape-major (n_blend_shapes x n_vertices x 3; normal_deltas empty: normals are not morphed)
+struct SurfaceRig {
+    std::vector<int32_t> bones;
+    std::vector<float> weights, position_deltas, normal_deltas;
+};
+
 struct ArrayMesh {
     std::vector<Surface> surfaces;
     int get_surface_count() const { return (int)surfaces.size(); }
@@ -673,6 +680,44 @@ class GeometryGroup3D {
         else check(ctx_, jpt_scene_update_mesh(ctx_, (uint32_t)id, sv.data(), (int32_t)sv.size()), "jpt_scene_update_mesh");
     }
 
+    // A skinned or morphed mesh (Skeleton3D with Skin, ArrayMesh blend shapes), posed on the device.  set_mesh_rig: `mesh` is one of the
+    // ArrayMesh objects the last build() collected, in its bind pose, `rigs` one SurfaceRig per surface (jpt_scene_set_mesh_rig).
+    // pose_mesh: bone_transforms12 = bone pose x inverse bind per bone, 12 floats each (transform12 layout), and one weight per blend
+    // shape (jpt_scene_pose_mesh).  Every rank's replica under attach_multi.  Needs builder == JPT_BUILD_SAH_WATERTIGHT.
+    void set_mesh_rig(const ArrayMesh* mesh, const std::vector<SurfaceRig>& rigs, int32_t influences, int32_t n_blend_shapes)
+    {
+        const uint32_t id = built_mesh_id(mesh, "set_mesh_rig");
+        if (rigs.size() != mesh->surfaces.size()) throw std::runtime_error("GeometryGroup3D::set_mesh_rig: one SurfaceRig per surface");
+        std::vector<jpt_surface> sv;
+        std::vector<jpt_surface_rig> rv;
+        for (size_t i = 0; i < rigs.size(); i++) {
+            const Surface& x = mesh->surfaces[i];
+            const SurfaceRig& r = rigs[i];
+            sv.push_back(jpt_surface{x.vertices.data(), x.normals.empty() ? nullptr : x.normals.data(), nullptr, x.indices.data(),
+                                     (int32_t)(x.vertices.size() / 3), (int32_t)x.indices.size()});
+            rv.push_back(jpt_surface_rig{r.bones.empty() ? nullptr : r.bones.data(), r.weights.empty() ? nullptr : r.weights.data(),
+                                         r.position_deltas.empty() ? nullptr : r.position_deltas.data(),
+                                         r.normal_deltas.empty() ? nullptr : r.normal_deltas.data()});
+        }
+        if (multi_) mcheck(jpt_multi_set_mesh_rig(multi_, id, sv.data(), rv.data(), (int32_t)sv.size(), influences, n_blend_shapes), "jpt_multi_set_mesh_rig");
+        else check(ctx_, jpt_scene_set_mesh_rig(ctx_, id, sv.data(), rv.data(), (int32_t)sv.size(), influences, n_blend_shapes), "jpt_scene_set_mesh_rig");
+    }
+    void pose_mesh(const ArrayMesh* mesh, const std::vector<float>& bone_transforms12, const std::vector<float>& blend_weights)
+    {
+        const uint32_t id = built_mesh_id(mesh, "pose_mesh");
+        const float* b = bone_transforms12.empty() ? nullptr : bone_transforms12.data();
+        const float* w = blend_weights.empty() ? nullptr : blend_weights.data();
+        const uint32_t nb = (uint32_t)(bone_transforms12.size() / 12), nw = (uint32_t)blend_weights.size();
+        if (multi_) mcheck(jpt_multi_pose_mesh(multi_, id, b, nb, w, nw), "jpt_multi_pose_mesh");
+        else check(ctx_, jpt_scene_pose_mesh(ctx_, id, b, nb, w, nw), "jpt_scene_pose_mesh");
+    }
+    void clear_mesh_rig(const ArrayMesh* mesh)
+    {
+        const uint32_t id = built_mesh_id(mesh, "clear_mesh_rig");
+        if (multi_) mcheck(jpt_multi_clear_mesh_rig(multi_, id), "jpt_multi_clear_mesh_rig");
+        else check(ctx_, jpt_scene_clear_mesh_rig(ctx_, id), "jpt_scene_clear_mesh_rig");
+    }
+
     // geometry_group3d.cpp:40-68 (bytes as the reference emits them after a REFERENCE_EXACT build)
     PackedByteArray get_triangles_geometry_buffer() const { return get_buffer(JPT_BUF_TRI_GEOMETRY); }
     PackedByteArray get_triangles_data_buffer() const { return get_buffer(JPT_BUF_TRI_DATA); }
@@ -687,6 +732,13 @@ class GeometryGroup3D {
     int get_tlas_node_count() const { return (int)(get_tlas_buffer().size() / 32); }                // :27
 
   private:
+    uint32_t built_mesh_id(const ArrayMesh* mesh, const char* call) const
+    {
+        if (!ctx_) throw std::runtime_error(std::string("GeometryGroup3D::") + call + " before build");
+        const size_t id = std::find(built_meshes_.begin(), built_meshes_.end(), mesh) - built_meshes_.begin();
+        if (id == built_meshes_.size()) throw std::runtime_error(std::string("GeometryGroup3D::") + call + ": the mesh is not part of the last build()");
+        return (uint32_t)id;
+    }
     PackedByteArray get_buffer(int which) const
     {
         size_t n = 0;
