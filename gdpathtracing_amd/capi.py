@@ -37,6 +37,9 @@ TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_W
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 CAMERA_PINHOLE, CAMERA_PROJECTIVE, CAMERA_EQUIRECT = 0, 1, 2
 PROBE_RADIANCE, PROBE_IRRADIANCE = 0, 1
+ENCODE_RGBA16F, ENCODE_RGB9E5, ENCODE_RGBE8 = 1, 2, 3
+ENCODE_SOURCE_MEAN, ENCODE_SOURCE_DENOISED, ENCODE_SOURCE_DISPLAY, ENCODE_SOURCE_LIGHTMAP, ENCODE_SOURCE_REFLECTION, ENCODE_SOURCE_PROBE_SH = range(6)
+ENCODE_ALL_LEVELS = -1
 HIT_VALID, HIT_FRONT, HIT_BAD_RAY = 1, 2, 4
 BUF_TRI_GEOMETRY, BUF_TRI_DATA, BUF_MATERIALS, BUF_BVH_NODES, BUF_INSTANCES, BUF_TLAS_NODES, BUF_TRIANGLES, BUF_REACH_TRIANGLES, BUF_REACH_INSTANCES = range(9)
 
@@ -75,6 +78,8 @@ SYMBOLS = [
     "jpt_query_rays", "jpt_query_rays_device", "jpt_query_pixels",
     "jpt_scene_set_mesh_rig", "jpt_scene_pose_mesh", "jpt_scene_clear_mesh_rig", "jpt_multi_set_mesh_rig", "jpt_multi_pose_mesh", "jpt_multi_clear_mesh_rig",
     "jpt_debug_skin",
+    "jpt_encode", "jpt_get_encoded_info", "jpt_read_encoded", "jpt_readback_encoded_begin", "jpt_readback_encoded_end", "jpt_device_encoded",
+    "jpt_get_encode_timing", "jpt_debug_encode",
 ]
 
 
@@ -144,6 +149,27 @@ class MeterResult(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class EncodedInfo(C.Structure):
+    """jpt_encoded_info"""
+    _fields_ = [("source", C.c_int32), ("format", C.c_int32), ("level", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("n_texels", C.c_uint64), ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def encoded_array(fmt: int, n_texels: int):
+    """a numpy array for n_texels texels of a jpt_encode format: RGBA16F float16 [n, 4], RGB9E5 uint32 [n], RGBE8 uint8 [n, 4]"""
+    import numpy as np
+    if fmt == ENCODE_RGBA16F:
+        return np.zeros((n_texels, 4), np.float16)
+    if fmt == ENCODE_RGB9E5:
+        return np.zeros(n_texels, np.uint32)
+    if fmt == ENCODE_RGBE8:
+        return np.zeros((n_texels, 4), np.uint8)
+    raise ValueError("unknown encode format %r" % (fmt,))
 
 
 class Ray(C.Structure):
@@ -392,6 +418,16 @@ def lib():
         L.jpt_scene_clear_mesh_rig.argtypes = [vp, u32]
         L.jpt_multi_clear_mesh_rig.argtypes = [vp, u32]
         L.jpt_debug_skin.argtypes = [C.c_int, vp, vp, u32, vp, vp, i32, vp, vp, i32, vp, u32, vp, vp, vp]
+    if hasattr(L, "jpt_encode") or "JPT_LIB" not in os.environ:
+        L.jpt_encode.argtypes = [vp, i32, i32, i32]
+        L.jpt_get_encoded_info.argtypes = [vp, C.POINTER(EncodedInfo)]
+        L.jpt_read_encoded.argtypes = [vp, vp, C.c_size_t]
+        L.jpt_readback_encoded_begin.argtypes = [vp]
+        L.jpt_readback_encoded_end.argtypes = [vp, vp, C.c_size_t]
+        L.jpt_device_encoded.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.jpt_device_encoded.restype = vp
+        L.jpt_get_encode_timing.argtypes = [vp, C.POINTER(C.c_float)]
+        L.jpt_debug_encode.argtypes = [C.c_int, vp, C.c_uint64, C.c_float, i32, i32, vp]
     _lib = L
     return L
 

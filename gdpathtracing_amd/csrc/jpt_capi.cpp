@@ -1096,6 +1096,8 @@ void jpt_destroy(jpt_ctx* c)
     for (hipEvent_t e : c->trace_events) (void)hipEventDestroy(e);
     if (c->ev_readback) (void)hipEventDestroy(c->ev_readback);
     for (hipEvent_t e : c->primary.refl_ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->enc_ev) if (e) (void)hipEventDestroy(e);
+    if (c->ev_enc_readback) (void)hipEventDestroy(c->ev_enc_readback);
     if (c->refit_stream) { (void)hipStreamSynchronize(c->refit_stream); (void)hipStreamDestroy(c->refit_stream); }
     for (hipEvent_t e : c->ev_set_retired) if (e) (void)hipEventDestroy(e);
     if (c->ev_refit_done) (void)hipEventDestroy(c->ev_refit_done);

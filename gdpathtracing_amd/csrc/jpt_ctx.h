@@ -1,5 +1,5 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp).
+// (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_encode.cpp).
 #pragma once
 #include "../../include/jpt.h"
 
@@ -388,6 +388,20 @@ struct jpt_ctx {
     DevBuf<float4> d_disp_f32, d_disp_pyramid;
     DevBuf<uint32_t> d_disp_ldr;
     bool disp_valid = false;
+
+    // jpt_encode (jpt_encode.cpp): its own buffer, grow-only and kept until jpt_destroy -- a snapshot that no other call writes;
+    // enc_valid: it holds the texels enc_info describes.  enc_ev: two events around the last jpt_encode's kernel under
+    // jpt_set_kernel_timing (enc_timed), made at the first such call.  The split read-back of it has a pinned buffer, an event and a
+    // pending flag of its own (the display image's: h_ldr_pinned, ev_readback); enc_read_bytes: what the read-back in flight copies.
+    DevBuf<char> d_encoded;
+    jpt_encoded_info enc_info = {};
+    bool enc_valid = false;
+    hipEvent_t enc_ev[2] = {nullptr, nullptr};
+    bool enc_timed = false;
+    PinnedBuf h_enc_pinned;
+    hipEvent_t ev_enc_readback = nullptr;
+    bool enc_readback_pending = false;
+    size_t enc_read_bytes = 0;
 
     // jpt_meter: the context's parameters and the auto-exposure switch of jpt_display, and its own buffers -- the published bins, the working sets (kMeterBinWords) and the state
     // record, made at the first jpt_meter, kept until jpt_destroy; meter_valid: the record holds the state a jpt_meter left since

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "jpt_encode.h"
 #include "jpt_instance_math.h"
 #include "jpt_kernels.h"
 #include "jpt_lightmap.h"
@@ -861,6 +862,50 @@ int jpt_debug_skin(int device_id, const float* bind_positions3, const float* bin
         rc = hip_fail(e, "hipMemcpy");
     if (rc == JPT_OK && bind_normals3 && (e = hipMemcpy(normals3_out, d_all + o_nrm, (size_t)n_vertices * 3 * sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
         rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_encode(int device_id, const float* src4, uint64_t n_texels, float divisor, int32_t alpha_one, int32_t format, void* out)
+{
+    if (!encode_format_known(format)) {
+        g_debug_error = "jpt_debug_encode: format must be JPT_ENCODE_RGBA16F, _RGB9E5 or _RGBE8";
+        return JPT_E_INVALID;
+    }
+    if (!std::isfinite(divisor) || !(divisor > 0.0f)) {
+        g_debug_error = "jpt_debug_encode: divisor must be finite and > 0";
+        return JPT_E_INVALID;
+    }
+    if (n_texels == 0) return JPT_OK;
+    if (!src4 || !out) {
+        g_debug_error = "jpt_debug_encode: null argument";
+        return JPT_E_INVALID;
+    }
+    if (n_texels > (1ull << 30)) {
+        g_debug_error = "jpt_debug_encode: more than 2^30 texels";
+        return JPT_E_LIMIT;
+    }
+    const float4* src = reinterpret_cast<const float4*>(src4);
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        encode_host(format, src, n_texels, divisor, alpha_one != 0, out);
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    const size_t b_in = (size_t)n_texels * sizeof(float4), b_out = (size_t)n_texels * encode_texel_bytes(format);
+    char* d_all = nullptr;   // the texels, then the encoded texels (both 16-byte aligned)
+    if ((e = hipMalloc((void**)&d_all, b_in + b_out)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    int rc = JPT_OK;
+    if ((e = hipMemcpy(d_all, src4, b_in, hipMemcpyHostToDevice)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        launch_encode(nullptr, format, reinterpret_cast<const float4*>(d_all), n_texels, divisor, alpha_one != 0, d_all + b_in);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "encode_kernel");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(out, d_all + b_in, b_out, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
     return rc;
 }

@@ -29,7 +29,8 @@
 //         0.5; index min((int)(s01 size), size - 1), likewise t; term = c.ch * w_k, acc = acc + term from +0; stored as (r, g, b, 1).
 //
 // Out of scope: box projection / parallax correction, blending between probes, bilinear or cross-face filtering of the source, the BRDF
-// split-sum LUT, an octahedral layout, half-float or RGBE output, a jpt_multi_* form, anisotropy, any change to how materials are shaded.
+// split-sum LUT, an octahedral layout, a jpt_multi_* form, anisotropy, any change to how materials are shaded.  (Half-float and RGBE
+// output: jpt_encode.h.)
 #pragma once
 
 #include "jpt_cube.h"

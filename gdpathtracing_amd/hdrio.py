@@ -132,8 +132,16 @@ def save_hdr(path, rgb, rle: bool = True) -> None:
     rgb = np.asarray(rgb)
     if rgb.ndim != 3 or rgb.shape[2] != 3:
         raise ValueError("save_hdr takes a [height, width, 3] array")
-    h, w = rgb.shape[:2]
-    px = encode_rgbe(rgb)
+    save_hdr_rgbe(path, encode_rgbe(rgb), rle)
+
+
+def save_hdr_rgbe(path, rgbe, rle: bool = True) -> None:
+    """already-encoded texels, uint8 [height, width, 4] (r, g, b mantissas and the exponent byte: encode_rgbe's, or a
+    JPT_ENCODE_RGBE8 read-back reshaped to the image) -> a Radiance .hdr file as save_hdr writes it, with no conversion"""
+    px = np.asarray(rgbe)
+    if px.ndim != 3 or px.shape[2] != 4 or px.dtype != np.uint8:
+        raise ValueError("save_hdr_rgbe takes a uint8 [height, width, 4] array")
+    h, w = px.shape[:2]
     out = bytearray(b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n" % (h, w))
     use_rle = rle and 8 <= w <= 0x7FFF
     for y in range(h):

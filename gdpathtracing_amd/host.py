@@ -314,6 +314,18 @@ def debug_reflection_prefilter(device_id, accum4, frame_count, n_probes, face_si
     return out
 
 
+def debug_encode(device_id, texels4, fmt, divisor=1.0, alpha_one=False):
+    """jpt_debug_encode: float32 [n, 4] texels in a jpt_encode format (rgb / divisor when it is not 1, alpha as given or 1) -- float16
+    [n, 4] (ENCODE_RGBA16F), uint32 [n] (ENCODE_RGB9E5) or uint8 [n, 4] (ENCODE_RGBE8).  device_id -1: the same functions on the host."""
+    t = np.ascontiguousarray(texels4, dtype=np.float32).reshape(-1, 4)
+    L = capi.lib()
+    out = capi.encoded_array(int(fmt), len(t)) if int(fmt) in (1, 2, 3) else np.zeros(1, np.uint8)
+    rc = L.jpt_debug_encode(int(device_id), _ptr(t), len(t), float(divisor), 1 if alpha_one else 0, int(fmt), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_encode failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
 def debug_lens_sample(camera160, aperture_radius, focus_distance, origins, dirs, xi2):
     """jpt_debug_lens_sample: the lens step alone, on the host, for n pinhole rays and n (xi0, xi1) pairs -- (origins [n, 3], dirs
     [n, 3], basis [3, 3]: f, r, u) float32.  A basis that is not finite raises JptError (code E_STATE)."""
@@ -868,6 +880,53 @@ class Context:
         out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
         self._ck(self._lib.jpt_read_display_rgba8(self.h, _ptr(out)), "jpt_read_display_rgba8")
         return out
+
+    # ---- encoded outputs (jpt_encode)
+    def encode(self, source, fmt, level=0):
+        """jpt_encode: queue the packing of one of the context's float4 images (capi.ENCODE_SOURCE_*; `level` for the reflection chain,
+        capi.ENCODE_ALL_LEVELS for all of it) into capi.ENCODE_RGBA16F / _RGB9E5 / _RGBE8, in a buffer of its own: a snapshot that
+        stays readable until the next encode"""
+        self._ck(self._lib.jpt_encode(self.h, int(source), int(level), int(fmt)), "jpt_encode")
+
+    def encoded_info(self) -> dict:
+        """jpt_get_encoded_info: source, format, level, width, height, n_texels, bytes of the snapshot"""
+        info = capi.EncodedInfo()
+        self._ck(self._lib.jpt_get_encoded_info(self.h, C.byref(info)), "jpt_get_encoded_info")
+        return info.as_dict()
+
+    def read_encoded(self) -> np.ndarray:
+        """jpt_read_encoded: the snapshot -- float16 [n, 4], uint32 [n] or uint8 [n, 4] by its format (capi.encoded_array), n texels in
+        the source's own order; blocking"""
+        info = self.encoded_info()
+        out = capi.encoded_array(info["format"], info["n_texels"])
+        self._ck(self._lib.jpt_read_encoded(self.h, _ptr(out), out.nbytes), "jpt_read_encoded")
+        return out
+
+    def readback_encoded_begin(self):
+        """jpt_readback_encoded_begin: queue the copy of the snapshot to pinned memory"""
+        info = self.encoded_info()
+        self._ck(self._lib.jpt_readback_encoded_begin(self.h), "jpt_readback_encoded_begin")
+        self._enc_pending = (info["format"], info["n_texels"])
+
+    def readback_encoded_end(self) -> np.ndarray:
+        """jpt_readback_encoded_end: wait for that copy alone and return it, as read_encoded returns the snapshot it was begun on"""
+        fmt, n = getattr(self, "_enc_pending", None) or (capi.ENCODE_RGBE8, 0)
+        out = capi.encoded_array(fmt, n)
+        self._ck(self._lib.jpt_readback_encoded_end(self.h, _ptr(out), out.nbytes), "jpt_readback_encoded_end")
+        self._enc_pending = None
+        return out
+
+    def device_encoded(self):
+        """jpt_device_encoded: (device pointer, bytes) of the snapshot; (None, 0) before any encode"""
+        n = C.c_size_t()
+        p = self._lib.jpt_device_encoded(self.h, C.byref(n))
+        return p, n.value
+
+    def encode_timing(self) -> float:
+        """jpt_get_encode_timing: kernel ms of the last encode under set_kernel_timing"""
+        ms = C.c_float(0)
+        self._ck(self._lib.jpt_get_encode_timing(self.h, C.byref(ms)), "jpt_get_encode_timing")
+        return ms.value
 
     # ---- metering and auto-exposure (jpt_meter)
     def set_meter_params(self, params: Optional[capi.MeterParams] = None, **fields):

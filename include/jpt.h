@@ -637,7 +637,7 @@ int jpt_read_bake_texels(jpt_ctx *ctx, float *position4, float *normal4);
  * contexts: JPT_E_DEVICE after the checks that need no device.  There is no jpt_multi_* form, as for jpt_denoise.
  * The parameters are the context's (like jpt_set_denoise_params'): they survive scene changes, each jpt_bake_finish takes them by
  * value, jpt_scene_share does not copy them.
- * Out of scope: seam stitching across UV islands, half-float or RGBE output. */
+ * Out of scope: seam stitching across UV islands.  (Half-float, RGB9E5 and RGBE output: jpt_encode, below.) */
 typedef struct jpt_bake_finish_params {
     int32_t passes;             /* 0..6, default 3: a-trous passes, pass k with tap spacing 2^k; 0 = no filter */
     int32_t normal_power_log2;  /* 0..8, default 4 */
@@ -696,7 +696,7 @@ int jpt_read_lightmap_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: (r, 
  * projects, as with jpt_display).  jpt_read_probe_sh_f32 before a jpt_probe_project of the current probes and size: JPT_E_STATE.
  * Unknown flags: JPT_E_INVALID.  There is no jpt_multi_* form.
  * Out of scope: directional (per-texel SH) lightmaps, probe placement and detection of probes inside geometry (jpt_query_rays answers
- * that), band 3 and above, octahedral tiles, half-float output.  (Cube captures: jpt_set_reflection_probes, below.) */
+ * that), band 3 and above, octahedral tiles.  (Cube captures: jpt_set_reflection_probes, below; half-float output: jpt_encode, below.) */
 enum { JPT_PROBE_RADIANCE = 0, JPT_PROBE_IRRADIANCE = 1 };
 int jpt_set_probes(jpt_ctx *ctx, const float *position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row);
 int jpt_get_probe_image_size(jpt_ctx *ctx, int32_t *width, int32_t *height);
@@ -755,8 +755,8 @@ int jpt_read_probe_sh_f32(jpt_ctx *ctx, float *out);       /* n_probes * 9 * 4 f
  * jpt_get_reflection_timing: the kernel time of the last jpt_reflection_prefilter's two steps (the source chain, the prefilter) in ms,
  * when it ran under jpt_set_kernel_timing (else JPT_E_STATE); it waits for them.
  * Out of scope: box projection / parallax correction, blending between probes, bilinear or cross-face filtering of the source, the
- * BRDF split-sum LUT, an octahedral layout, half-float or RGBE output, a jpt_multi_* form, anisotropy, any change to how materials
- * are shaded. */
+ * BRDF split-sum LUT, an octahedral layout, a jpt_multi_* form, anisotropy, any change to how materials are shaded.  (Half-float,
+ * RGB9E5 and RGBE output: jpt_encode, below.) */
 typedef struct { int32_t n_levels; int32_t samples; } jpt_reflection_params;   /* defaults: every level down to 1x1 (0); 64 */
 int jpt_set_reflection_probes(jpt_ctx *ctx, const float *position3, int32_t n_probes, int32_t face_size, int32_t probes_per_row);
 int jpt_get_reflection_image_size(jpt_ctx *ctx, int32_t *width, int32_t *height);
@@ -933,6 +933,62 @@ int jpt_display(jpt_ctx *ctx);
 /* The read-backs wait for the work queued on the context, through its pinned staging buffer like the other jpt_read_*. */
 int jpt_read_display_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes, alpha 255 */
 int jpt_read_display_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: the tone-mapped value before the transfer, (r, g, b, 1) */
+
+/* ---- encoded outputs: half-float, RGB9E5 and RGBE read-backs made on the device (no reference counterpart: the reference hands its
+ * images to the engine as float4) ------------------------------------------------------------------------------------------------------
+ * Every image the library makes on the device is 16 bytes per texel; an engine stores none of them so (a Godot lightmap or panorama is
+ * Image.FORMAT_RGBE9995 or FORMAT_RGBAH, a reflection atlas and an HDR viewport texture are half float, an environment map on disk is a
+ * Radiance .hdr: INTEGRATION.md).  jpt_encode packs one of those images into such a format on the device, so that 8 or 4 bytes per texel
+ * cross the bus instead of 16.  An explicit call: without it every render, buffer and read-back is bit for bit what it is without this
+ * section.
+ *   source        what is read (always float4)                                                                       texels
+ *   MEAN          the accumulation: rgb / (float)frame_count, one IEEE division per channel; alpha written as 1       W x H
+ *   DENOISED      what jpt_read_denoised_f32 reads                                                                   W x H
+ *   DISPLAY       what jpt_read_display_f32 reads                                                                    W x H
+ *   LIGHTMAP      what jpt_read_lightmap_f32 reads (alpha is coverage: 0, 0.5 and 1 are exact in half)                W x H
+ *   REFLECTION    level >= 0: that level as jpt_read_reflection_f32 lays it out; JPT_ENCODE_ALL_LEVELS: the whole chain, level l
+ *                 starting at offset_texels(l) * bytes per texel (jpt_get_reflection_chain_size)
+ *   PROBE_SH      what jpt_read_probe_sh_f32 reads: n_probes * 9 texels, in the tile-frame order.  Signed: JPT_ENCODE_RGBA16F only
+ * `level` must be 0 for every source but REFLECTION.  Each source refuses with the code and the words of its own read-back when its
+ * image is not there (JPT_E_STATE); MEAN refuses what jpt_display refuses: a denoising mode other than JPT_DENOISE_PROGRESSIVE, the
+ * DEBUG_STEPS mode, a screen partition, jpt_set_params not called, no frame accumulated since the last reset.  An unknown source or
+ * format, PROBE_SH with another format than RGBA16F, a level that is not there: JPT_E_INVALID.  Host-only contexts: JPT_E_DEVICE after
+ * the argument checks.  There is no jpt_multi_* form.
+ * The formats (pinned; gdpathtracing_amd/csrc/jpt_encode.h; tests/np_encode.py restates them bit for bit):
+ *   RGBA16F   8 B per texel, r g b a in ascending addresses.  Per channel NaN -> +0, clamp to [-65504, 65504] (so +-inf saturate), round
+ *             to nearest even; subnormal halves are kept and -0 stays -0.
+ *   RGB9E5    4 B per texel, r | g << 9 | b << 18 | e << 27 (VK_FORMAT_E5B9G9R9_UFLOAT_PACK32, GL_RGB9_E5); alpha is dropped.  Per
+ *             channel NaN -> 0, clamp to [0, 65408]; e and the mantissas as the extension's specification rounds them.  A channel decodes
+ *             as mantissa * 2^(e - 24), within (0.5 + 2^-16) * 2^(e - 24) of the clamped value.
+ *   RGBE8     4 B per texel, Ward's r g b mantissas and exponent byte in ascending addresses (a Radiance .hdr file's texels); alpha is
+ *             dropped.  Per channel NaN -> 0, clamp to [0, the largest float below 2^127]; mantissas truncated, as float2rgbe does; a
+ *             texel whose largest channel is below 1e-32f is four zero bytes.
+ * jpt_encode enqueues one kernel on the context's stream, ordered as jpt_display is: behind everything queued before it and ahead of
+ * everything queued after it.  It reads its source and writes a buffer of its own (grown when needed, freed by jpt_destroy), which is
+ * a SNAPSHOT: it stays readable, with its jpt_encoded_info, until the next jpt_encode or jpt_destroy, whatever happens to the context
+ * in between (jpt_set_params with another size included).  jpt_encoded_info: width x height are W x H for the flat sources, the face
+ * size of the level (of level 0 for the whole chain) for REFLECTION, and 9 x n_probes for PROBE_SH; n_texels and bytes are the whole
+ * buffer's.
+ * jpt_read_encoded waits for the work queued on the context and copies through the pinned staging buffer of the other jpt_read_*;
+ * jpt_readback_encoded_begin / _end are its split form, as jpt_readback_ldr_begin / _end, with a pinned buffer, an event and a pending
+ * flag of their own: begin while one is pending is JPT_E_STATE, end without one too; a jpt_encode while one is pending is legal (the
+ * copy was queued first).  `capacity` below the encoded size: JPT_E_INVALID (a pending read-back stays pending).  Before any jpt_encode:
+ * JPT_E_STATE.  jpt_device_encoded: the buffer's device pointer and size (NULL and 0 before any jpt_encode), for interop without the
+ * host; work that reads it must be ordered behind the context's stream.  jpt_get_encode_timing: the kernel time of the last jpt_encode
+ * in ms, when it ran under jpt_set_kernel_timing (else JPT_E_STATE); it waits for it.
+ * Not covered: BC6H or any block compression, R11G11B10F, a jpt_multi_* form, the guide and bake-texel images, dithering. */
+typedef enum { JPT_ENCODE_RGBA16F = 1, JPT_ENCODE_RGB9E5 = 2, JPT_ENCODE_RGBE8 = 3 } jpt_encode_format;
+typedef enum { JPT_ENCODE_SOURCE_MEAN = 0, JPT_ENCODE_SOURCE_DENOISED = 1, JPT_ENCODE_SOURCE_DISPLAY = 2,
+               JPT_ENCODE_SOURCE_LIGHTMAP = 3, JPT_ENCODE_SOURCE_REFLECTION = 4, JPT_ENCODE_SOURCE_PROBE_SH = 5 } jpt_encode_source;
+#define JPT_ENCODE_ALL_LEVELS (-1)
+typedef struct { int32_t source, format, level, width, height; uint64_t n_texels, bytes; } jpt_encoded_info;
+int   jpt_encode(jpt_ctx *ctx, int32_t source, int32_t level, int32_t format);
+int   jpt_get_encoded_info(jpt_ctx *ctx, jpt_encoded_info *out);
+int   jpt_read_encoded(jpt_ctx *ctx, void *out, size_t capacity);
+int   jpt_readback_encoded_begin(jpt_ctx *ctx);
+int   jpt_readback_encoded_end(jpt_ctx *ctx, void *out, size_t capacity);
+void *jpt_device_encoded(jpt_ctx *ctx, size_t *bytes_out);
+int   jpt_get_encode_timing(jpt_ctx *ctx, float *ms);
 
 /* ---- metering: a luminance histogram and auto-exposure on the device (no reference counterpart; Godot's
  * CameraAttributes.auto_exposure_*) -----------------------------------------------------------------------------------
@@ -1320,6 +1376,12 @@ int jpt_debug_skin(int device_id, const float *bind_positions3, const float *bin
                    const float *position_deltas, const float *normal_deltas, int32_t n_blend_shapes,
                    const float *bone_transforms12, uint32_t n_bones, const float *blend_weights,
                    float *positions3_out, float *normals3_out);
+
+/* jpt_encode's arithmetic alone, over n_texels caller-made float4 texels: rgb / divisor when divisor is not 1 (finite and > 0 required),
+ * alpha as given or 1 (alpha_one != 0), then `format`; `out` takes n_texels * 8 (RGBA16F) or * 4 bytes.  n_texels = 0 succeeds and
+ * writes nothing; more than 2^30 texels: JPT_E_LIMIT.  device_id >= 0: the kernel jpt_encode launches, on that device;
+ * JPT_DEVICE_HOST_ONLY: the same functions compiled for the host, in a plain loop. */
+int jpt_debug_encode(int device_id, const float *src4, uint64_t n_texels, float divisor, int32_t alpha_one, int32_t format, void *out);
 
 /* ---- environment ------------------------------------------------------------------------------------------------------
  * The library READS these once per process (at the first jpt_create; gdpathtracing_amd/csrc/jpt_tuning.h) and never writes the

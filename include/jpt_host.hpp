@@ -944,6 +944,41 @@ class PathTracingCamera {
         return out;
     }
     void read_display(float* out) { check(ctx, jpt_read_display_f32(ctx, out), "jpt_read_display_f32"); }
+    // Encoded outputs (jpt_encode): one of the context's float4 images (JPT_ENCODE_SOURCE_*; `level` for the reflection chain,
+    // JPT_ENCODE_ALL_LEVELS for all of it) packed on the device into JPT_ENCODE_RGBA16F (Image.FORMAT_RGBAH), _RGB9E5
+    // (FORMAT_RGBE9995) or _RGBE8 (a Radiance .hdr file's texels), in a buffer of its own: a snapshot that stays readable until the next
+    // encode.  read_encoded: its bytes, ready for Image::create_from_data; readback_encoded_begin / _end: the split form.
+    void encode(int32_t source, int32_t format, int32_t level = 0) { check(ctx, jpt_encode(ctx, source, level, format), "jpt_encode"); }
+    jpt_encoded_info encoded_info()
+    {
+        jpt_encoded_info info;
+        check(ctx, jpt_get_encoded_info(ctx, &info), "jpt_get_encoded_info");
+        return info;
+    }
+    PackedByteArray read_encoded()
+    {
+        PackedByteArray out((size_t)encoded_info().bytes);
+        check(ctx, jpt_read_encoded(ctx, out.data(), out.size()), "jpt_read_encoded");
+        return out;
+    }
+    void readback_encoded_begin()
+    {
+        encoded_pending_bytes = (size_t)encoded_info().bytes;
+        check(ctx, jpt_readback_encoded_begin(ctx), "jpt_readback_encoded_begin");
+    }
+    PackedByteArray readback_encoded_end()
+    {
+        PackedByteArray out(encoded_pending_bytes);
+        check(ctx, jpt_readback_encoded_end(ctx, out.data(), out.size()), "jpt_readback_encoded_end");
+        return out;
+    }
+    void* device_encoded(size_t* bytes_out) { return jpt_device_encoded(ctx, bytes_out); }
+    float encode_timing()
+    {
+        float ms = 0.0f;
+        check(ctx, jpt_get_encode_timing(ctx, &ms), "jpt_get_encode_timing");
+        return ms;
+    }
     // Metering and auto-exposure (jpt_meter).  From CameraAttributes: set_auto_exposure(auto_exposure_scale,
     // auto_exposure_speed, min, max) sets key = 0.18 * scale and the exposure range and turns jpt_display's auto-exposure on (the
     // other metering parameters stay as set_meter_params left them); meter(dt), once per displayed frame ahead of display(), takes
@@ -1104,6 +1139,7 @@ class PathTracingCamera {
     float fov = 90.0f;  // path_tracing_camera.h:80
     int width = 0, height = 0;
     bool ready = false, temporal_ready = false, readback_queued = false;
+    size_t encoded_pending_bytes = 0;   // what readback_encoded_begin queued
 };
 
 // PathTracingCamera over several GPUs of one node, from this one process (jpt.h, jpt_multi_*): the scene is built once
