@@ -40,6 +40,7 @@ PROBE_RADIANCE, PROBE_IRRADIANCE = 0, 1
 ENCODE_RGBA16F, ENCODE_RGB9E5, ENCODE_RGBE8 = 1, 2, 3
 ENCODE_SOURCE_MEAN, ENCODE_SOURCE_DENOISED, ENCODE_SOURCE_DISPLAY, ENCODE_SOURCE_LIGHTMAP, ENCODE_SOURCE_REFLECTION, ENCODE_SOURCE_PROBE_SH = range(6)
 ENCODE_ALL_LEVELS = -1
+SUN_RADIANCE, SUN_IRRADIANCE = 0, 1
 HIT_VALID, HIT_FRONT, HIT_BAD_RAY = 1, 2, 4
 BUF_TRI_GEOMETRY, BUF_TRI_DATA, BUF_MATERIALS, BUF_BVH_NODES, BUF_INSTANCES, BUF_TLAS_NODES, BUF_TRIANGLES, BUF_REACH_TRIANGLES, BUF_REACH_INSTANCES = range(9)
 
@@ -80,6 +81,7 @@ SYMBOLS = [
     "jpt_debug_skin",
     "jpt_encode", "jpt_get_encoded_info", "jpt_read_encoded", "jpt_readback_encoded_begin", "jpt_readback_encoded_end", "jpt_device_encoded",
     "jpt_get_encode_timing", "jpt_debug_encode",
+    "jpt_sky_defaults", "jpt_set_sky", "jpt_read_environment_f32", "jpt_multi_set_sky", "jpt_debug_sky", "jpt_debug_sky_radiance", "jpt_debug_pow01",
 ]
 
 
@@ -170,6 +172,48 @@ def encoded_array(fmt: int, n_texels: int):
     if fmt == ENCODE_RGBE8:
         return np.zeros((n_texels, 4), np.uint8)
     raise ValueError("unknown encode format %r" % (fmt,))
+
+
+class SkySun(C.Structure):
+    """jpt_sky_sun: direction (towards the sun, any length), angular_radius (radians), color, energy, mode (SUN_RADIANCE / SUN_IRRADIANCE)"""
+    _fields_ = [("direction", C.c_float * 3), ("angular_radius", C.c_float), ("color", C.c_float * 3), ("energy", C.c_float), ("mode", C.c_int32)]
+
+
+class SkyParams(C.Structure):
+    """jpt_sky_params (jpt_set_sky); sky_params() returns one filled with the library's defaults"""
+    _fields_ = [("sky_top_color", C.c_float * 3), ("sky_curve", C.c_float), ("sky_horizon_color", C.c_float * 3), ("sky_energy", C.c_float),
+                ("ground_bottom_color", C.c_float * 3), ("ground_curve", C.c_float), ("ground_horizon_color", C.c_float * 3), ("ground_energy", C.c_float),
+                ("sun_angle_max", C.c_float), ("sun_curve", C.c_float), ("exposure", C.c_float), ("n_suns", C.c_int32), ("suns", SkySun * 4)]
+
+
+def sky_params(suns=(), **fields) -> "SkyParams":
+    """a SkyParams with jpt_sky_defaults' values, then `fields` by name (colours as 3-sequences) and `suns`: up to four dicts or SkySun
+    (direction, angular_radius, color, energy, mode)"""
+    p = SkyParams()
+    lib().jpt_sky_defaults(C.byref(p))
+    for name, v in fields.items():
+        if name.endswith("_color"):
+            setattr(p, name, (C.c_float * 3)(*[float(x) for x in v]))
+        else:
+            setattr(p, name, v)
+    suns = list(suns)
+    if len(suns) > 4:
+        raise ValueError("at most four suns")
+    for k, sun in enumerate(suns):
+        if isinstance(sun, SkySun):
+            p.suns[k] = sun
+            continue
+        q = SkySun(energy=1.0, mode=SUN_RADIANCE)
+        q.color = (C.c_float * 3)(1.0, 1.0, 1.0)
+        for name, v in sun.items():
+            if name in ("direction", "color"):
+                setattr(q, name, (C.c_float * 3)(*[float(x) for x in v]))
+            else:
+                setattr(q, name, v)
+        p.suns[k] = q
+    if suns or "n_suns" not in fields:
+        p.n_suns = len(suns)
+    return p
 
 
 class Ray(C.Structure):
@@ -428,6 +472,16 @@ def lib():
         L.jpt_device_encoded.restype = vp
         L.jpt_get_encode_timing.argtypes = [vp, C.POINTER(C.c_float)]
         L.jpt_debug_encode.argtypes = [C.c_int, vp, C.c_uint64, C.c_float, i32, i32, vp]
+    if hasattr(L, "jpt_set_sky") or "JPT_LIB" not in os.environ:
+        sp = C.POINTER(SkyParams)
+        L.jpt_sky_defaults.argtypes = [sp]
+        L.jpt_sky_defaults.restype = None
+        L.jpt_set_sky.argtypes = [vp, sp, i32, i32, i32]
+        L.jpt_read_environment_f32.argtypes = [vp, vp, C.POINTER(i32), C.POINTER(i32)]
+        L.jpt_multi_set_sky.argtypes = [vp, sp, i32, i32, i32]
+        L.jpt_debug_sky.argtypes = [C.c_int, sp, i32, i32, i32, vp]
+        L.jpt_debug_sky_radiance.argtypes = [sp, vp, u32, vp]
+        L.jpt_debug_pow01.argtypes = [vp, vp, u32, vp]
     _lib = L
     return L
 

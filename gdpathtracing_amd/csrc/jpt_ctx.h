@@ -135,7 +135,7 @@ struct PipeSlot {
 // What the context holds of its renders' lighting: written by the setters, read by lighting_bound and resolve_lighting (all in
 // jpt_lighting.cpp), which turn it into the one value the renders take (Lighting, jpt_kernels.h)
 struct LightingState {
-    // the environment map (jpt_set_environment): the context's, like its params
+    // the environment map (jpt_set_environment uploads it, jpt_set_sky writes it in place with a kernel): the context's, like its params
     DevBuf<float4> d_env;
     bool env_set = false;
     int32_t env_w = 0, env_h = 0;

@@ -374,6 +374,8 @@ int primary_rays_debug(int device_id, const char* what, PrimaryRays p, const Ref
 
 }  // namespace
 
+void jpt::set_debug_error(const std::string& why) { g_debug_error = why; }
+
 extern "C" {
 
 const char* jpt_debug_last_error(void) { return g_debug_error.c_str(); }

@@ -17,6 +17,7 @@
 #include "jpt_reflection.h"
 #include "jpt_shade.h"
 #include "jpt_skin.h"
+#include "jpt_sky.h"
 #include "jpt_types.h"
 
 namespace jpt {
@@ -215,6 +216,16 @@ int make_camera_model(int32_t model, const RefCamera& cam, CamModelDev& out, std
 // the map's sampling tables built on the device (jpt_kernels_post.hip), on `stream`: cond (w * h floats), marg (h floats) and the
 // total weight (one float), all device memory: one thread per row (env_build_row), then one thread for the marginal
 void launch_env_tables(hipStream_t stream, const float4* texels, int32_t w, int32_t h, float* cond, float* marg, float* total);
+// jpt_set_sky's launch (jpt_kernels_sky.hip), on `stream`: the w x h texels of `out` (16-byte aligned), (r, g, b, 0) each, from n x n
+// subsamples of sky_radiance (jpt_sky.h).  Nothing else is written and nothing is read.  1 <= n <= kSkyMaxSamples; w, h within the map's limits.
+void launch_sky(hipStream_t stream, const SkyDev& P, int32_t w, int32_t h, int32_t n, float4* out);
+// the checks of jpt_set_sky (jpt_lighting.cpp), also run by the jpt_debug_sky entries, and what the kernel takes: JPT_OK and `out`, or a
+// JPT_E_* code and the reason in `why`.  params NULL: the defaults.  The size and sample checks are sky_size_check's.
+int sky_params_dev(const jpt_sky_params* params, SkyDev& out, std::string& why);
+int sky_size_check(int32_t width, int32_t height, int32_t samples, std::string& why);
+void jpt_sky_default_params(jpt_sky_params& out);
+// the message jpt_debug_last_error returns (jpt_debug.hip), for the debug entries that live elsewhere
+void set_debug_error(const std::string& why);
 // JPT_ENV_SAMPLING_MIS needs an orthonormal rotation: every entry of R R^T within kEnvOrthoTol of the identity's
 constexpr double kEnvOrthoTol = 1e-4;
 bool env_rotation_orthonormal(const float* rotation9);

@@ -1,6 +1,7 @@
 // jpt_lighting.cpp -- what a context's renders see at their misses and sample with shadow rays: the environment map and its sampling
 // tables, the emitter list and its tables (LightingState, jpt_ctx.h), the one resolver that turns them into a render's Lighting
-// (jpt_kernels.h), and the C entries that set or probe them.  Host C++: the kernels are jpt_kernels_post.hip's and jpt_debug.hip's.
+// (jpt_kernels.h), and the C entries that set or probe them -- jpt_set_sky and its debug forms among them: the map of a procedural sky
+// (jpt_sky.h) made on the device.  Host C++: the kernels are jpt_kernels_post.hip's, jpt_kernels_sky.hip's and jpt_debug.hip's.
 #include "jpt_ctx.h"
 
 #include <algorithm>
@@ -205,6 +206,112 @@ bool env_rotation_orthonormal(const float* r)
     return true;
 }
 
+// ---- the procedural sky (jpt_set_sky; the arithmetic: jpt_sky.h) ----
+
+void jpt_sky_default_params(jpt_sky_params& p)
+{
+    std::memset(&p, 0, sizeof p);
+    const float top[3] = {0.385f, 0.454f, 0.55f}, horizon[3] = {0.6463f, 0.6558f, 0.6708f}, bottom[3] = {0.2f, 0.169f, 0.133f};
+    for (int k = 0; k < 3; k++) {
+        p.sky_top_color[k] = top[k];
+        p.sky_horizon_color[k] = horizon[k];
+        p.ground_bottom_color[k] = bottom[k];
+        p.ground_horizon_color[k] = horizon[k];
+    }
+    p.sky_curve = 0.15f;
+    p.ground_curve = 0.02f;
+    p.sun_curve = 0.15f;
+    p.sky_energy = p.ground_energy = p.exposure = 1.0f;
+    p.sun_angle_max = (float)(30.0 * 3.14159265358979323846 / 180.0);
+    p.n_suns = 0;
+}
+
+int sky_size_check(int32_t width, int32_t height, int32_t samples, std::string& why)
+{
+    if (width <= 0 || height <= 0) {
+        why = "jpt_set_sky: width and height must be positive";
+        return JPT_E_INVALID;
+    }
+    if (samples < 1 || samples > kSkyMaxSamples) {
+        why = "jpt_set_sky: samples must lie in 1..8";
+        return JPT_E_INVALID;
+    }
+    if (width > kEnvMaxWidth || height > kEnvMaxHeight) {
+        why = "jpt_set_sky: the map is larger than 16384 x 8192 texels";
+        return JPT_E_LIMIT;
+    }
+    return JPT_OK;
+}
+
+int sky_params_dev(const jpt_sky_params* params, SkyDev& out, std::string& why)
+{
+    jpt_sky_params p;
+    if (params) p = *params;
+    else jpt_sky_default_params(p);
+    auto bad = [&why](const std::string& field, const char* rule) {
+        why = "jpt_set_sky: " + field + " " + rule;
+        return JPT_E_INVALID;
+    };
+    auto level = [](float v) { return std::isfinite(v) && v >= 0.0f; };
+    const struct { const char* name; const float* v; } colours[4] = {{"sky_top_color", p.sky_top_color}, {"sky_horizon_color", p.sky_horizon_color},
+        {"ground_bottom_color", p.ground_bottom_color}, {"ground_horizon_color", p.ground_horizon_color}};
+    for (const auto& c : colours)
+        for (int k = 0; k < 3; k++)
+            if (!level(c.v[k])) return bad(c.name, "must be finite and >= 0");
+    const struct { const char* name; float v; } levels[3] = {{"sky_energy", p.sky_energy}, {"ground_energy", p.ground_energy}, {"exposure", p.exposure}};
+    for (const auto& e : levels)
+        if (!level(e.v)) return bad(e.name, "must be finite and >= 0");
+    const struct { const char* name; float v; } curves[3] = {{"sky_curve", p.sky_curve}, {"ground_curve", p.ground_curve}, {"sun_curve", p.sun_curve}};
+    for (const auto& c : curves)
+        if (!(c.v >= 0.015625f && c.v <= 8.0f)) return bad(c.name, "must lie in [1/64, 8]");
+    if (!(p.sun_angle_max >= 0.0f && p.sun_angle_max <= kSkyPi)) return bad("sun_angle_max", "must lie in [0, pi]");
+    if (p.n_suns < 0 || p.n_suns > kSkyMaxSuns) return bad("n_suns", "must lie in 0..4");
+    SkyDev d;
+    std::memset(&d, 0, sizeof d);
+    for (int k = 0; k < 3; k++) {
+        d.sky_top[k] = p.sky_top_color[k];
+        d.sky_horizon[k] = p.sky_horizon_color[k];
+        d.ground_bottom[k] = p.ground_bottom_color[k];
+        d.ground_horizon[k] = p.ground_horizon_color[k];
+    }
+    d.sky_energy = p.sky_energy;
+    d.ground_energy = p.ground_energy;
+    d.exposure = p.exposure;
+    d.inv_sky_curve = 1.0f / p.sky_curve;
+    d.inv_ground_curve = 1.0f / p.ground_curve;
+    d.inv_sun_curve = 1.0f / p.sun_curve;
+    d.n_suns = p.n_suns;
+    for (int s = 0; s < p.n_suns; s++) {
+        const jpt_sky_sun& in = p.suns[s];
+        const std::string name = "suns[" + std::to_string(s) + "].";
+        const double x = in.direction[0], y = in.direction[1], z = in.direction[2];
+        const double len = std::sqrt(x * x + y * y + z * z);
+        if (!std::isfinite(in.direction[0]) || !std::isfinite(in.direction[1]) || !std::isfinite(in.direction[2]) || !(len > 0.0))
+            return bad(name + "direction", "must be finite and non-zero");
+        if (!(in.angular_radius > 0.0f && in.angular_radius <= kSkyHalfPi)) return bad(name + "angular_radius", "must lie in (0, pi/2]");
+        for (int k = 0; k < 3; k++)
+            if (!level(in.color[k])) return bad(name + "color", "must be finite and >= 0");
+        if (!level(in.energy)) return bad(name + "energy", "must be finite and >= 0");
+        if (in.mode != JPT_SUN_RADIANCE && in.mode != JPT_SUN_IRRADIANCE) return bad(name + "mode", "must be JPT_SUN_RADIANCE or JPT_SUN_IRRADIANCE");
+        SkySunDev& o = d.suns[s];
+        o.dir[0] = (float)(x / len);
+        o.dir[1] = (float)(y / len);
+        o.dir[2] = (float)(z / len);
+        o.r = in.angular_radius;
+        o.amax = p.sun_angle_max > o.r ? p.sun_angle_max : o.r;
+        const float span = o.amax - o.r;
+        o.inv_span = span > 0.0f ? 1.0f / span : 0.0f;
+        // the cap's solid angle in double: 2 pi (1 - cos r)
+        const double cap = 2.0 * 3.14159265358979323846 * (1.0 - std::cos((double)o.r));
+        for (int k = 0; k < 3; k++) {
+            o.rad[k] = in.mode == JPT_SUN_IRRADIANCE ? (float)((double)in.color[k] * (double)in.energy / cap) : in.color[k] * in.energy;
+            if (!std::isfinite(o.rad[k])) return bad(name + "color", "times energy overflows the disk's radiance");
+        }
+    }
+    out = d;
+    return JPT_OK;
+}
+
 void pack_env_texels(const float* rgb, int32_t width, int32_t height, std::vector<float4>& out)
 {
     const size_t n = (size_t)width * (size_t)height;
@@ -359,6 +466,151 @@ int jpt_set_environment(jpt_ctx* c, const float* rgb, int32_t width, int32_t hei
     l.env_h = height;
     l.env_set = true;
     if (l.env_sampling == JPT_ENV_SAMPLING_MIS) return build_env_tables(c);
+    return JPT_OK;
+}
+
+void jpt_sky_defaults(jpt_sky_params* out)
+{
+    if (out) jpt_sky_default_params(*out);
+}
+
+// The map of a procedural sky, written into d_env by the kernel.  A map of this size already there (made by either call): queued on the
+// context's stream -- behind every render queued so far, each of which ends with work there -- and the next render of every slot waits
+// for that stream (as ensure_light_tables orders its build): no wait on the host.  Otherwise as jpt_set_environment: wait, allocate.
+int jpt_set_sky(jpt_ctx* c, const jpt_sky_params* params, int32_t width, int32_t height, int32_t samples)
+{
+    if (!c) return JPT_E_INVALID;
+    LightingState& l = c->lighting;
+    std::string why;
+    SkyDev P;
+    int rc = sky_params_dev(params, P, why);
+    if (rc == JPT_OK) rc = sky_size_check(width, height, samples, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_sky: host-only context has no environment map");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * (size_t)height;
+    if (!(l.env_set && l.env_w == width && l.env_h == height && l.d_env.n == n)) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (renders in flight read the old buffer)
+        l.env_set = false;
+        l.d_env_cond.release();
+        l.d_env_marg.release();
+        HIP_TRY(c, l.d_env.resize(n));
+        l.env_w = width;
+        l.env_h = height;
+    }
+    l.env_tables = false;   // (the tables' buffers stay: a rebuild of the same size reuses them, on this stream)
+    launch_sky(c->stream, P, width, height, samples, l.d_env.p);
+    HIP_TRY(c, hipGetLastError());
+    for (PipeSlot& ps : c->slot) ps.acc_done_valid = false;
+    l.env_set = true;
+    if (l.env_sampling == JPT_ENV_SAMPLING_MIS) return build_env_tables(c);
+    return JPT_OK;
+}
+
+int jpt_read_environment_f32(jpt_ctx* c, float* rgb, int32_t* width, int32_t* height)
+{
+    if (!c) return JPT_E_INVALID;
+    const LightingState& l = c->lighting;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_environment_f32: host-only context has no environment map");
+    if (!l.env_set) return fail(c, JPT_E_STATE, "jpt_read_environment_f32: no environment map");
+    if (width) *width = l.env_w;
+    if (height) *height = l.env_h;
+    if (!rgb) return JPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t n = (size_t)l.env_w * (size_t)l.env_h, kChunk = (size_t)1 << 20;
+    std::vector<float4> part(std::min(n, kChunk));
+    for (size_t at = 0; at < n; at += kChunk) {
+        const size_t m = std::min(kChunk, n - at);
+        HIP_TRY(c, hipMemcpy(part.data(), l.d_env.p + at, m * sizeof(float4), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < m; i++) {
+            rgb[3 * (at + i)] = part[i].x;
+            rgb[3 * (at + i) + 1] = part[i].y;
+            rgb[3 * (at + i) + 2] = part[i].z;
+        }
+    }
+    return JPT_OK;
+}
+
+int jpt_debug_sky(int device_id, const jpt_sky_params* params, int32_t width, int32_t height, int32_t samples, float* rgb_out)
+{
+    std::string why;
+    SkyDev P;
+    int rc = sky_params_dev(params, P, why);
+    if (rc == JPT_OK) rc = sky_size_check(width, height, samples, why);
+    if (rc == JPT_OK && !rgb_out) {
+        why = "jpt_debug_sky: null argument";
+        rc = JPT_E_INVALID;
+    }
+    if (rc != JPT_OK) {
+        set_debug_error(why);
+        return rc;
+    }
+    const size_t n = (size_t)width * (size_t)height;
+    if (device_id == JPT_DEVICE_HOST_ONLY) {
+        for (int32_t j = 0; j < height; j++)
+            for (int32_t i = 0; i < width; i++) {
+                const f3 t = sky_texel(P, width, height, samples, i, j);
+                float* o = rgb_out + 3 * ((size_t)j * (size_t)width + (size_t)i);
+                o[0] = t.x;
+                o[1] = t.y;
+                o[2] = t.z;
+            }
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        set_debug_error(std::string(what) + ": " + hipGetErrorString(e));
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    float4* d_map = nullptr;
+    if ((e = hipMalloc((void**)&d_map, n * sizeof(float4))) != hipSuccess) return hip_fail(e, "hipMalloc");
+    std::vector<float4> texels(n);
+    launch_sky(nullptr, P, width, height, samples, d_map);
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "sky_kernel");
+    if (rc == JPT_OK && (e = hipMemcpy(texels.data(), d_map, n * sizeof(float4), hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_map);
+    if (rc != JPT_OK) return rc;
+    for (size_t i = 0; i < n; i++) {
+        rgb_out[3 * i] = texels[i].x;
+        rgb_out[3 * i + 1] = texels[i].y;
+        rgb_out[3 * i + 2] = texels[i].z;
+    }
+    return JPT_OK;
+}
+
+int jpt_debug_sky_radiance(const jpt_sky_params* params, const float* dirs3, uint32_t n, float* rgb_out)
+{
+    std::string why;
+    SkyDev P;
+    int rc = sky_params_dev(params, P, why);
+    if (rc == JPT_OK && n && (!dirs3 || !rgb_out)) {
+        why = "jpt_debug_sky_radiance: null argument";
+        rc = JPT_E_INVALID;
+    }
+    if (rc != JPT_OK) {
+        set_debug_error(why);
+        return rc;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const f3 d = mk3(dirs3[3 * (size_t)i], dirs3[3 * (size_t)i + 1], dirs3[3 * (size_t)i + 2]);
+        const float theta = atan2_(__builtin_sqrtf(d.x * d.x + d.z * d.z), d.y);
+        const f3 c = sky_radiance(P, theta, d);
+        rgb_out[3 * (size_t)i] = c.x;
+        rgb_out[3 * (size_t)i + 1] = c.y;
+        rgb_out[3 * (size_t)i + 2] = c.z;
+    }
+    return JPT_OK;
+}
+
+int jpt_debug_pow01(const float* b, const float* e, uint32_t n, float* out)
+{
+    if (n && (!b || !e || !out)) {
+        set_debug_error("jpt_debug_pow01: null argument");
+        return JPT_E_INVALID;
+    }
+    for (uint32_t i = 0; i < n; i++) out[i] = pow01_(b[i], e[i]);
     return JPT_OK;
 }
 

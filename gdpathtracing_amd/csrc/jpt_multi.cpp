@@ -315,6 +315,16 @@ int jpt_multi_set_environment_sampling(jpt_multi* m, int32_t mode)
     return JPT_OK;
 }
 
+int jpt_multi_set_sky(jpt_multi* m, const jpt_sky_params* params, int32_t width, int32_t height, int32_t samples)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        const int rc = jpt_set_sky(m->ctx[r], params, width, height, samples);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_set_light_sampling(jpt_multi* m, int32_t mode)
 {
     if (!m) return JPT_E_INVALID;

@@ -108,6 +108,44 @@ def _env_rotation(rotation):
     return np.ascontiguousarray(rotation, dtype=np.float32).reshape(9)
 
 
+def _sky_ref(params):
+    return None if params is None else C.byref(params)
+
+
+def debug_sky(device_id, params, width, height, samples):
+    """jpt_debug_sky: the width x height map of the procedural sky `params` (a capi.SkyParams; None: the defaults), float32 [height,
+    width, 3].  device_id >= 0: jpt_set_sky's kernel on that device; -1: the same functions in a host loop."""
+    L = capi.lib()
+    out = np.zeros((max(int(height), 0), max(int(width), 0), 3), np.float32)
+    rc = L.jpt_debug_sky(int(device_id), _sky_ref(params), int(width), int(height), int(samples), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_sky failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
+def debug_sky_radiance(params, dirs):
+    """jpt_debug_sky_radiance: sky_radiance of n unit directions [n, 3] (theta = atan2_(|d.xz|, d.y)), on the host -- float32 [n, 3]"""
+    L = capi.lib()
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    out = np.zeros((len(d), 3), np.float32)
+    rc = L.jpt_debug_sky_radiance(_sky_ref(params), _ptr(d), len(d), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_sky_radiance failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
+def debug_pow01(b, e):
+    """jpt_debug_pow01: the pinned b^e (b in [0, 1], e in [1/8, 64]) of the procedural sky, on the host -- float32 [n]"""
+    L = capi.lib()
+    b = np.ascontiguousarray(b, np.float32).reshape(-1)
+    e = np.ascontiguousarray(np.broadcast_to(np.asarray(e, np.float32), b.shape))
+    out = np.zeros(len(b), np.float32)
+    rc = L.jpt_debug_pow01(_ptr(b), _ptr(e), len(b), _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_pow01 failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
 def debug_dielectric(device_id, normals, out_dirs, ior, front, xi_f):
     """jpt_debug_dielectric: the dielectric event of capi.MATERIAL_EXT_TRANSMISSION for n cases -- (dirs [n, 3] float32, fresnel [n]
     float32, event [n] uint8: 0 refract, 1 reflect, 2 total internal reflection).  device_id -1: the host's copy of the function."""
@@ -557,6 +595,22 @@ class Context:
         the +y pole; hdrio.load_hdr reads one), or None for main.glsl's sky gradient.  Waits for the renders already queued."""
         a, w, h = _env_map(rgb)
         self._ck(self._lib.jpt_set_environment(self.h, None if a is None else _ptr(a), w, h), "jpt_set_environment")
+
+    def set_sky(self, params=None, width=2048, height=1024, samples=4):
+        """jpt_set_sky: make the environment map of a procedural sky on the device -- `params` a capi.SkyParams (capi.sky_params builds
+        one; None: Godot's defaults), samples x samples subsamples per texel.  With a map of this size already present the kernel is
+        queued behind the renders already queued and the call does not wait (unless capi.ENV_SAMPLING_MIS is on: the tables' rebuild
+        waits); otherwise it waits and allocates like set_environment."""
+        self._ck(self._lib.jpt_set_sky(self.h, _sky_ref(params), int(width), int(height), int(samples)), "jpt_set_sky")
+
+    def read_environment(self) -> np.ndarray:
+        """jpt_read_environment_f32: the map the context holds (from set_environment or set_sky), float32 [height, width, 3]; waits for
+        the context's stream.  Without a map: JptError (E_STATE)."""
+        w, h = C.c_int32(0), C.c_int32(0)
+        self._ck(self._lib.jpt_read_environment_f32(self.h, None, C.byref(w), C.byref(h)), "jpt_read_environment_f32")
+        out = np.zeros((h.value, w.value, 3), np.float32)
+        self._ck(self._lib.jpt_read_environment_f32(self.h, _ptr(out), C.byref(w), C.byref(h)), "jpt_read_environment_f32")
+        return out
 
     def set_environment_params(self, rotation=None, intensity: float = 1.0):
         """jpt_set_environment_params: row-major 3x3 world -> map rotation (None: identity) and intensity, for later renders."""
@@ -1278,6 +1332,9 @@ class MultiContext:
     def set_environment(self, rgb):
         a, w, h = _env_map(rgb)
         self._ck(self._lib.jpt_multi_set_environment(self.h, None if a is None else _ptr(a), w, h), "jpt_multi_set_environment")
+
+    def set_sky(self, params=None, width=2048, height=1024, samples=4):
+        self._ck(self._lib.jpt_multi_set_sky(self.h, _sky_ref(params), int(width), int(height), int(samples)), "jpt_multi_set_sky")
 
     def set_environment_params(self, rotation=None, intensity: float = 1.0):
         r = _env_rotation(rotation)

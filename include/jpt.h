@@ -437,6 +437,54 @@ int jpt_set_environment_params(jpt_ctx *ctx, const float *rotation9, float inten
 #define JPT_ENV_SAMPLING_MIS  1
 int jpt_set_environment_sampling(jpt_ctx *ctx, int32_t mode);
 
+/* A procedural sky made on the device (no reference counterpart): the environment map of a gradient sky -- the form of Godot 4's
+ * ProceduralSkyMaterial without its cover texture -- written into the context's map buffer by a kernel, from about 200 bytes of
+ * parameters.  After the call the context holds an environment map like any other: the lookup, jpt_set_environment_params,
+ * jpt_set_environment_sampling, every camera, bake and probe form, jpt_scene_share not copying it and
+ * jpt_set_environment(ctx, NULL, 0, 0) clearing it behave as for an uploaded map; jpt_set_environment(rgb) replaces it.
+ *   Texel (i, j) is the mean of samples x samples values of sky_radiance at the directions the lookup maps to an even grid inside
+ *   the texel (csrc/jpt_sky.h).  For a unit direction d at polar angle theta from +y, b = theta / (pi / 2):
+ *     d.y >= 0: c = mix(sky_horizon, sky_top, w(b, sky_curve)) * sky_energy; then for each sun in order, a the angle between d and
+ *               the sun: a < radius: c = the disk's radiance; else a < amax = max(sun_angle_max, radius):
+ *               c = mix(disk, c, w(1 - (a - radius) / (amax - radius), sun_curve));
+ *     d.y <  0: c = mix(ground_horizon, ground_bottom, w(2 - b, ground_curve)) * ground_energy (suns do not show below the horizon);
+ *     w(b, curve) = clamp(1 - pow(clamp(b, 0, 1), 1 / curve), 0, 1); the result is c * exposure.
+ *   A fixed sequence of binary32 operations, the same on the device and in the host forms below.
+ * Checks (JPT_E_INVALID, the message names the field): colours, energies and exposure finite and >= 0; curves in [1/64, 8];
+ * sun_angle_max in [0, pi]; n_suns in 0..4; a sun's direction finite and non-zero, its radius in (0, pi/2], its mode known; samples
+ * in 1..8; sizes positive.  Beyond 16384 x 8192 texels: JPT_E_LIMIT.  Host-only contexts: JPT_E_DEVICE after the checks.
+ * When the context already holds a map of this size (made by either call) the kernel is queued on the context's stream, behind the
+ * renders already queued, and the next render of every pipeline slot is ordered after it: the host does NOT wait, a render queued
+ * before the call shows the old sky, one queued after it the new one -- a time-of-day animation costs a kernel per change.
+ * Otherwise the call waits for the queued renders and allocates, as jpt_set_environment does.  With JPT_ENV_SAMPLING_MIS on, the
+ * sampling tables are rebuilt at this call and the call waits for their total, as jpt_set_environment does.
+ * Through JPT_ENV_SAMPLING_MIS a sun disk in the map is a directional light with soft shadows; its sharpness is limited by the
+ * texel size (a 0.27 degree sun wants 4096 x 2048 or more).  Use JPT_ACCUM_HDR_F32 to keep a sun's energy. */
+enum { JPT_SUN_RADIANCE = 0, JPT_SUN_IRRADIANCE = 1 };
+typedef struct jpt_sky_sun {
+    float direction[3];     /* from the scene towards the sun, map frame (world when the rotation is identity); any length > 0 */
+    float angular_radius;   /* radians, (0, pi/2] */
+    float color[3];         /* linear, finite, >= 0 */
+    float energy;           /* finite, >= 0 */
+    int32_t mode;           /* RADIANCE: the disk's radiance is color*energy (Godot's look).  IRRADIANCE: color*energy /
+                               (2 pi (1 - cos r)), computed in double: the disk alone sends color*energy of irradiance onto a
+                               surface that faces it -- the stand-in for a DirectionalLight3D */
+} jpt_sky_sun;
+typedef struct jpt_sky_params {
+    float sky_top_color[3], sky_curve, sky_horizon_color[3], sky_energy;
+    float ground_bottom_color[3], ground_curve, ground_horizon_color[3], ground_energy;
+    float sun_angle_max, sun_curve, exposure;
+    int32_t n_suns;         /* 0..4 */
+    jpt_sky_sun suns[4];
+} jpt_sky_params;
+/* Godot 4's defaults: sky top (0.385, 0.454, 0.55), both horizons (0.6463, 0.6558, 0.6708), ground bottom (0.2, 0.169, 0.133), sky
+ * and sun curve 0.15, ground curve 0.02, energies and exposure 1, sun_angle_max 30 degrees, no sun */
+void jpt_sky_defaults(jpt_sky_params *out);
+int jpt_set_sky(jpt_ctx *ctx, const jpt_sky_params *params /* NULL: the defaults */, int32_t width, int32_t height, int32_t samples);
+/* The map the context holds, made by jpt_set_environment or jpt_set_sky: three floats per texel in jpt_set_environment's layout.
+ * rgb may be NULL (sizes only).  Waits for the context's stream.  Without a map: JPT_E_STATE. */
+int jpt_read_environment_f32(jpt_ctx *ctx, float *rgb /* may be NULL: sizes only */, int32_t *width, int32_t *height);
+
 /* Importance sampling of the emissive triangles (no reference counterpart; the reference lists next-event estimation among its
  * wanted features).  The mode belongs to the context, like the map's: it survives scene commits, uploads and updates;
  * jpt_scene_share does not copy it.  Each render takes it by value: queued renders keep the mode of their own call.
@@ -1183,6 +1231,8 @@ int jpt_multi_set_params(jpt_multi *m, int32_t width, int32_t height, int32_t ma
 int jpt_multi_set_environment(jpt_multi *m, const float *rgb, int32_t width, int32_t height);
 int jpt_multi_set_environment_params(jpt_multi *m, const float *rotation9, float intensity);
 int jpt_multi_set_environment_sampling(jpt_multi *m, int32_t mode);
+/* jpt_set_sky on every rank */
+int jpt_multi_set_sky(jpt_multi *m, const jpt_sky_params *params, int32_t width, int32_t height, int32_t samples);
 int jpt_multi_set_light_sampling(jpt_multi *m, int32_t mode);
 int jpt_multi_set_material_extensions(jpt_multi *m, uint32_t flags);
 /* jpt_set_lens on every rank */
@@ -1242,6 +1292,14 @@ int jpt_debug_env_sample(int device_id, const float *rgb, int32_t width, int32_t
                          const float *xi2, uint32_t n, float *dirs_out, float *pdf_out);
 int jpt_debug_env_pdf(int device_id, const float *rgb, int32_t width, int32_t height, const float *rotation9,
                       const float *dirs3, uint32_t n, float *pdf_out);
+/* The procedural sky of jpt_set_sky, checked as that call checks its arguments (params NULL: the defaults):
+ *   _sky:          rgb_out[3 (j width + i) ..] = texel (i, j) of the width x height map; device_id >= 0 launches the kernel on that
+ *                  device, JPT_DEVICE_HOST_ONLY runs the same functions in a host loop;
+ *   _sky_radiance: rgb_out[3 i ..] = sky_radiance of the unit direction dirs3[3 i ..], one sample, on the host;
+ *   _pow01:        out[i] = pow01_(b[i], e[i]), the pinned b^e for b in [0, 1] and e in [1/8, 64], on the host. */
+int jpt_debug_sky(int device_id, const jpt_sky_params *params, int32_t width, int32_t height, int32_t samples, float *rgb_out);
+int jpt_debug_sky_radiance(const jpt_sky_params *params, const float *dirs3, uint32_t n, float *rgb_out);  /* host; theta = atan2_(|d.xz|, d.y) */
+int jpt_debug_pow01(const float *b, const float *e, uint32_t n, float *out);                              /* host */
 /* The emitter tables of JPT_LIGHT_SAMPLING_MIS as the context's next render would take them (made now if stale; the context needs
  * a scene): n_out[0] = emitters, n_out[1] = blocks; then, each output may be NULL and is filled only if its capacity (in emitters)
  * is at least the count:

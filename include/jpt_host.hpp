@@ -855,6 +855,21 @@ class PathTracingCamera {
     {
         check(ctx, jpt_set_environment_params(ctx, rotation9, intensity), "jpt_set_environment_params");
     }
+    // jpt_set_sky: the environment map of a procedural sky made on the device (INTEGRATION.md "Lighting from a procedural sky": a
+    // ProceduralSkyMaterial's properties and one jpt_sky_sun per DirectionalLight3D).  params = nullptr: Godot's defaults.  With a
+    // map of this size already there the call does not wait for queued renders.  read_environment: the map the context holds,
+    // three floats per texel, whichever call made it (w, h: its size).
+    void set_sky(const jpt_sky_params* params = nullptr, int32_t w = 2048, int32_t h = 1024, int32_t samples = 4)
+    {
+        check(ctx, jpt_set_sky(ctx, params, w, h, samples), "jpt_set_sky");
+    }
+    std::vector<float> read_environment(int32_t& w, int32_t& h)
+    {
+        check(ctx, jpt_read_environment_f32(ctx, nullptr, &w, &h), "jpt_read_environment_f32");
+        std::vector<float> rgb((size_t)w * (size_t)h * 3u);
+        check(ctx, jpt_read_environment_f32(ctx, rgb.data(), &w, &h), "jpt_read_environment_f32");
+        return rgb;
+    }
     // jpt_set_environment_sampling: JPT_ENV_SAMPLING_BRDF (default) or JPT_ENV_SAMPLING_MIS (shadow rays towards map samples)
     void set_environment_sampling(int32_t mode) { check(ctx, jpt_set_environment_sampling(ctx, mode), "jpt_set_environment_sampling"); }
     // jpt_set_light_sampling: JPT_LIGHT_SAMPLING_BRDF (default) or JPT_LIGHT_SAMPLING_MIS (shadow rays towards emitter samples)
