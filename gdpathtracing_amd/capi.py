@@ -73,6 +73,8 @@ SYMBOLS = [
     "jpt_get_reflection_chain_size", "jpt_read_reflection_f32", "jpt_get_reflection_timing",
     "jpt_debug_cube_rays", "jpt_debug_reflection_samples", "jpt_debug_reflection_prefilter",
     "jpt_set_bake_finish_params", "jpt_bake_finish", "jpt_read_lightmap_f32", "jpt_debug_bake_finish",
+    "jpt_set_bake_directional", "jpt_read_bake_directional_f32", "jpt_device_bake_directional", "jpt_bake_finish_directional",
+    "jpt_read_lightmap_directional_f32", "jpt_debug_bake_moments",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
@@ -408,6 +410,14 @@ def lib():
         L.jpt_bake_finish.argtypes = [vp]
         L.jpt_read_lightmap_f32.argtypes = [vp, vp]
         L.jpt_debug_bake_finish.argtypes = [C.c_int, i32, i32, C.POINTER(BakeFinishParams), vp, vp, vp, vp]
+    if hasattr(L, "jpt_set_bake_directional") or "JPT_LIB" not in os.environ:
+        L.jpt_set_bake_directional.argtypes = [vp, i32]
+        L.jpt_read_bake_directional_f32.argtypes = [vp, vp]
+        L.jpt_device_bake_directional.restype = vp
+        L.jpt_device_bake_directional.argtypes = [vp, i32, C.POINTER(C.c_size_t)]
+        L.jpt_bake_finish_directional.argtypes = [vp]
+        L.jpt_read_lightmap_directional_f32.argtypes = [vp, vp]
+        L.jpt_debug_bake_moments.argtypes = [vp, vp, i32, i32, vp, i32, u32, u32, i32, vp]
     if hasattr(L, "jpt_set_probes") or "JPT_LIB" not in os.environ:
         L.jpt_set_probes.argtypes = [vp, vp, i32, i32, i32, i32]
         L.jpt_get_probe_image_size.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

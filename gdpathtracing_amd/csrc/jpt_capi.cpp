@@ -931,6 +931,34 @@ int read_back_stats(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefr
     return JPT_OK;
 }
 
+// jpt_set_bake_directional: what a render with the switch on and bake images present refuses -- the moment kernel reads the per-frame
+// values the wavefront route keeps, of radiance, summed progressively.  Without bake images the switch has no effect.
+int check_bake_directional(jpt_ctx* c)
+{
+    if (!c->bake_dir || !c->primary.has_bake()) return JPT_OK;
+    if (c->kernel_variant != JPT_KERNEL_WAVEFRONT)
+        return fail(c, JPT_E_STATE, "jpt_set_bake_directional: the reference-layout kernel adds frame by frame and keeps no per-frame values: set "
+                                    "JPT_KERNEL_WAVEFRONT (jpt_set_kernel) or switch the directional planes off");
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_set_bake_directional: the moments follow the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE "
+                                    "(temporal reprojection and JPT_DENOISE_NONE keep no sum)");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_set_bake_directional: a DEBUG_STEPS render holds step counts, not radiance (jpt_set_debug_steps)");
+    return JPT_OK;
+}
+
+// the three moment planes at the size of the context's rows, made (and zeroed, so that a sum continued without a reset starts from
+// +0) when they are missing or of another size
+int ensure_bake_dir(jpt_ctx* c)
+{
+    const size_t need = 3u * (size_t)c->width * (size_t)c->local_rows;
+    if (c->d_bake_dir.p && c->d_bake_dir.n == need) return JPT_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (renders in flight may write the old planes: every one ends with work on the stream)
+    c->bake_dir_valid = false;
+    HIP_TRY(c, c->d_bake_dir.resize(need));
+    if (need) HIP_TRY(c, hipMemsetAsync(c->d_bake_dir.p, 0, need * sizeof(float4), c->stream));
+    return JPT_OK;
+}
+
 // validate -> prepare -> plan -> launch -> read back
 int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
 {
@@ -943,8 +971,13 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
     const FrameParams fp = frame_params(c, n_frames, first_frame_index, want_depth);
     Wf2Render r;
+    if ((rc = check_bake_directional(c)) != JPT_OK) return rc;
     if ((rc = resolve_primary(c, r.primary)) != JPT_OK) return rc;
     if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
+    if (c->bake_dir && r.primary.kind == PrimaryRays::kBake && c->local_rows > 0 && n_frames > 0) {
+        if ((rc = ensure_bake_dir(c)) != JPT_OK) return rc;
+        r.bake_dir = c->d_bake_dir.p;
+    }
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
     if (c->local_rows > 0 && c->width > 0 && n_frames > 0) {
@@ -952,6 +985,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
         const LaunchPlan p = plan_launch(c, fp, r, counted, blocking, kPlanDevice);
         rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->d_depth.p : nullptr);
         if (rc != JPT_OK) return rc;
+        if (r.bake_dir) c->bake_dir_valid = true;
         pipelined = p.route == LaunchPlan::kSlot;
         if (c->denoise == JPT_DENOISE_TEMPORAL) {
             // TemporalReprojection::render's dispatch (temporal_reprojection.cpp:71): screen + depth of this frame in,
@@ -2082,8 +2116,8 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
     }
     if (width != c->width || height != c->height) c->primary.sh_valid = false;   // (jpt_probe_project's coefficients are of the old size)
     if (width != c->width || height != c->height) c->primary.refl_valid = false;   // (jpt_reflection_prefilter's chain likewise)
-    if ((width != c->width || height != c->height) && c->d_lm_ping.p) {
-        // jpt_bake_finish's images likewise
+    if ((width != c->width || height != c->height) && (c->d_lm_ping.p || c->d_lmd_out.p)) {
+        // jpt_bake_finish's images likewise, and jpt_bake_finish_directional's
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->lightmap_release();
     }
@@ -2505,6 +2539,130 @@ int jpt_read_lightmap_f32(jpt_ctx* c, float* out)
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
     const int rc = staged_read(c, c->lm_result, bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+// ---- directional lightmaps: the first moments of the incoming light per texel (jpt_bake_dir.h, jpt_kernels_bake_dir.hip) ----------
+
+int jpt_set_bake_directional(jpt_ctx* c, int32_t enable)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_directional: host-only context: the moments are made on the device");
+    const bool on = enable != 0;
+    if (on == c->bake_dir) return JPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->d_bake_dir.p || c->d_lmd_out.p) {
+        // the renders queued so far add to the planes: they finish first, then the planes and what was finished from them go
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->bake_dir_release();
+        c->d_lmd_xg.release();
+        c->d_lmd_ng.release();
+        c->d_lmd_ping.release();
+        c->d_lmd_pong.release();
+        c->d_lmd_out.release();
+    }
+    c->lmd_valid = false;
+    c->bake_dir_valid = false;
+    c->bake_dir = on;
+    return jpt_accum_reset(c);   // the sum and the moments are of the same frames: both start over
+}
+
+// the planes of a read: JPT_OK, or the refusal
+static int bake_directional_ready(jpt_ctx* c, const char* call)
+{
+    const std::string who = std::string(call) + ": ";
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, who + "host-only context: the moments are made on the device");
+    if (!c->bake_dir) return fail(c, JPT_E_STATE, who + "the directional planes are switched off (jpt_set_bake_directional)");
+    if (!c->primary.has_bake()) return fail(c, JPT_E_STATE, who + "no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    if (!c->d_bake_dir.p || !c->bake_dir_valid || c->d_bake_dir.n != 3u * (size_t)c->width * (size_t)c->local_rows)
+        return fail(c, JPT_E_STATE, who + "no bake render with the switch on at the current size yet");
+    return JPT_OK;
+}
+
+int jpt_read_bake_directional_f32(jpt_ctx* c, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_bake_directional_f32: null output");
+    int rc = bake_directional_ready(c, "jpt_read_bake_directional_f32");
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the renders queued so far, as jpt_read_accum_f32)
+    const size_t bytes = c->d_bake_dir.n * sizeof(float4);
+    if ((rc = staged_read(c, c->d_bake_dir.p, bytes)) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+void* jpt_device_bake_directional(jpt_ctx* c, int32_t finished, size_t* bytes_out)
+{
+    if (bytes_out) *bytes_out = 0;
+    if (!c || c->device < 0 || !c->bake_dir) return nullptr;
+    if (finished) {
+        if (!c->lmd_valid || !c->d_lmd_out.p) return nullptr;
+        if (bytes_out) *bytes_out = c->d_lmd_out.n * sizeof(float4);
+        return c->d_lmd_out.p;
+    }
+    if (!c->d_bake_dir.p || !c->bake_dir_valid) return nullptr;
+    if (bytes_out) *bytes_out = c->d_bake_dir.n * sizeof(float4);
+    return c->d_bake_dir.p;
+}
+
+int jpt_bake_finish_directional(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    const char* who = "jpt_bake_finish_directional";
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_bake_finish_directional filters the progressive moments: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: DEBUG_STEPS renders make no moments (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional needs the whole image on one context (world == 1)");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_finish_directional: host-only context: it runs on the device");
+    const PrimaryState& p = c->primary;
+    if (!c->bake_dir) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: the directional planes are switched off (jpt_set_bake_directional)");
+    if (!p.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
+    if (p.has_probes()) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: the lightmap is made of texel images, and the context holds probes (jpt_set_probes)");
+    if (p.has_cubes())
+        return fail(c, JPT_E_STATE,
+                    "jpt_bake_finish_directional: the lightmap is made of texel images, and the context holds reflection probes (jpt_set_reflection_probes)");
+    if (!c->params_set || p.bake_w != c->width || p.bake_h != c->height)
+        return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) +
+                                        " texels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: no frame accumulated since the last reset");
+    const int rc = bake_directional_ready(c, who);
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)c->width * c->height;   // (>= 1; world == 1: the planes are npx texels each)
+    if (c->d_lmd_out.n != 3 * npx || !c->d_lmd_out.p) {
+        c->lmd_valid = false;
+        HIP_TRY(c, c->d_lmd_xg.resize(npx));
+        HIP_TRY(c, c->d_lmd_ng.resize(npx));
+        HIP_TRY(c, c->d_lmd_ping.resize(npx));
+        HIP_TRY(c, c->d_lmd_pong.resize(npx));
+        HIP_TRY(c, c->d_lmd_out.resize(3 * npx));
+    }
+    // On the context's stream, as jpt_bake_finish: each plane is the "accumulation" of one run of the same filter and dilation, with
+    // the same frame count, images and parameters; the planes are filtered independently of one another and of the L0 map.
+    for (int k = 0; k < 3; k++) {
+        const float4* res = launch_lightmap_finish(c->stream, c->lm_params, c->width, c->height, c->d_bake_dir.p + (size_t)k * npx, (float)c->frame_count,
+                                                   p.d_bake_pos.p, p.d_bake_nrm.p, c->d_lmd_xg.p, c->d_lmd_ng.p, c->d_lmd_ping.p, c->d_lmd_pong.p);
+        HIP_TRY(c, hipMemcpyAsync(c->d_lmd_out.p + (size_t)k * npx, res, npx * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+    }
+    HIP_TRY(c, hipGetLastError());
+    c->lmd_valid = true;
+    return JPT_OK;
+}
+
+int jpt_read_lightmap_directional_f32(jpt_ctx* c, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_lightmap_directional_f32: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_lightmap_directional_f32: host-only context: jpt_bake_finish_directional runs on the device");
+    if (!c->lmd_valid || !c->d_lmd_out.p)
+        return fail(c, JPT_E_STATE, "jpt_read_lightmap_directional_f32: no jpt_bake_finish_directional at the current size and bake images yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = c->d_lmd_out.n * sizeof(float4);
+    const int rc = staged_read(c, c->d_lmd_out.p, bytes);
     if (rc != JPT_OK) return rc;
     std::memcpy(out, c->h_read_pinned.p, bytes);
     return JPT_OK;

@@ -379,6 +379,28 @@ struct jpt_ctx {
         d_lm_ping.release();
         d_lm_pong.release();
         lm_result = nullptr;
+        d_lmd_xg.release();
+        d_lmd_ng.release();
+        d_lmd_ping.release();
+        d_lmd_pong.release();
+        d_lmd_out.release();
+        lmd_valid = false;
+    }
+
+    // jpt_set_bake_directional: the switch, and the three moment planes a bake render adds to (jpt_bake_dir.h; 48 B per texel of the
+    // context's rows) -- made by the first bake render with the switch on at a size (ensure_bake_dir, jpt_capi.cpp), given back when
+    // the switch goes off or the bake images are freed (bake_dir_release); bake_dir_valid: a bake render has written them.
+    // jpt_bake_finish_directional: guides and working images of its own (jpt_bake_finish's lightmap stays what it is) and the three
+    // finished planes, 112 B per texel in all, kept and given back as jpt_bake_finish's are; lmd_valid as lm_result.
+    bool bake_dir = false;
+    DevBuf<float4> d_bake_dir;
+    bool bake_dir_valid = false;
+    DevBuf<float4> d_lmd_xg, d_lmd_ng, d_lmd_ping, d_lmd_pong, d_lmd_out;
+    bool lmd_valid = false;
+    void bake_dir_release()
+    {
+        d_bake_dir.release();
+        bake_dir_valid = false;
     }
 
     // jpt_display: the context's parameters, and its own buffers -- the two images made at the first jpt_display at a resolution,

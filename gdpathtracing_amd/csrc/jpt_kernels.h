@@ -367,7 +367,22 @@ struct Wf2Render {
                                            // (launch_sky_tiles; null: wf2_accumulate decides every culled pixel by itself)
     Lighting lighting;                     // the kernel family of its launches and the workspace's shadow queues (no sky cells with a map)
     PrimaryRays primary;                   // which form of the primary launch it takes, and that form's argument
+    float4* bake_dir = nullptr;            // jpt_set_bake_directional: the three moment planes a bake render adds to (launch_bake_moments
+                                           // behind the accumulation); null: off, and no launch or argument differs
 };
+// What the moment kernel of one bake render reads and writes (jpt_kernels_bake_dir.hip; the arithmetic: jpt_bake_dir.h): the
+// per-(slot, frame) values wf2_accumulate reads, in its layout, and the three planes.  Every pointer is device memory.
+struct BakeDirArgs {
+    const float4* rad = nullptr;       // JPT_ACCUM_HDR_F32: the finished radiance per (slot, frame)
+    const uint32_t* fin8 = nullptr;    // JPT_ACCUM_REF_LDR8: the same as rgba8 words
+    const float4* normal = nullptr;    // the bake normal image, width x height (the whole image)
+    float4* planes = nullptr;          // three planes of width x local_rows float4, plane k at k * width * local_rows
+    int32_t full_tiles_x = 0, full_tiles_y = 0;   // the context's share of the image in 8 x 8 tiles: a bake render's window is all of it
+    uint32_t slots_per_frame = 0;      // full_tiles_x * full_tiles_y * 64
+    int32_t groups = 1;                // the frame groups whose blocks of rad / fin8 are read
+};
+// on `stream`: one thread per texel of the share; fp is the render's (frame_index / frame_count of its FIRST frame)
+void launch_bake_moments(hipStream_t stream, const BakeDirArgs& a, const FrameParams& fp);
 // `groups` frame groups (1..kMaxGroups, at most n_frames; groups > 1 needs streams.aux_stream[0 .. groups - 2]); `chain`: consecutive
 // segments per tracing block
 void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FrameParams& fp, const RefCamera& cam, void* workspace,

@@ -1209,6 +1209,20 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
         hipLaunchKernelGGL(wf2_accumulate_env, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, nullptr, lg.env);
     else
         hipLaunchKernelGGL(wf2_accumulate, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, r.sky_tiles);
+    // directional lightmaps (jpt_set_bake_directional): the moments of the same per-frame values, while the workspace still holds them
+    // (a bake render has no sky cull: its window is the whole share, and a slot is a texel's place in the share)
+    if (r.bake_dir != nullptr && r.primary.kind == PrimaryRays::kBake) {
+        BakeDirArgs da;
+        da.rad = L.rad;
+        da.fin8 = L.fin8;
+        da.normal = r.primary.bake.normal;
+        da.planes = r.bake_dir;
+        da.full_tiles_x = dm_all.full_tiles_x;
+        da.full_tiles_y = dm_all.full_tiles_y;
+        da.slots_per_frame = dm_all.slots_per_frame;
+        da.groups = groups;
+        launch_bake_moments(stream, da, fp);
+    }
 }
 
 uint64_t wf2_pixels_outside_window(const SkyCull& cull, const FrameParams& fp)

@@ -405,6 +405,7 @@ void bake_release(jpt_ctx* c)
     p.d_bake_winner.release();
     p.d_bake_in.release();
     p.bake_w = p.bake_h = 0;
+    c->bake_dir_release();   // (jpt_set_bake_directional's planes exist only beside the images; every caller has waited: bake_wait)
 }
 
 int bake_alloc(jpt_ctx* c, int32_t width, int32_t height)

@@ -255,6 +255,25 @@ def debug_bake_finish(device_id, mean4, position4, normal4, params=None, **field
     return out
 
 
+def debug_bake_moments(position4, normal4, radiance, first_frame_index, accum_mode=capi.ACCUM_HDR_F32, frame_count=1, moments=None):
+    """jpt_debug_bake_moments: the moments of jpt_set_bake_directional on the host, over texel images float32 [height, width, 4] and
+    radiance float32 [n_frames, height, width, 3] (frame f is frame first_frame_index + f) -- float32 [3, height, width, 4], plane k =
+    (M_k.r, M_k.g, M_k.b, 0).  frame_count > 1 continues the sums of `moments` (a copy is returned)."""
+    p, n = _bake_images(position4, normal4)
+    r = np.ascontiguousarray(radiance, dtype=np.float32)
+    if r.ndim != 4 or r.shape[1:] != (p.shape[0], p.shape[1], 3):
+        raise ValueError("radiance is float32 [n_frames, height, width, 3], the size of the texel images")
+    out = np.zeros((3,) + p.shape, np.float32) if moments is None else np.array(moments, dtype=np.float32, order="C")
+    if out.shape != (3,) + p.shape:
+        raise ValueError("moments is float32 [3, height, width, 4]")
+    L = capi.lib()
+    rc = L.jpt_debug_bake_moments(_ptr(p), _ptr(n), p.shape[1], p.shape[0], _ptr(r), r.shape[0], int(first_frame_index), int(frame_count), int(accum_mode),
+                                  _ptr(out))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_bake_moments failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return out
+
+
 def probe_image_size(n_probes, tile_w, tile_h, probes_per_row):
     """(width, height) of the image n_probes tiles make, probes_per_row to a row (jpt_get_probe_image_size's rule)"""
     return int(probes_per_row) * int(tile_w), -(-int(n_probes) // int(probes_per_row)) * int(tile_h)
@@ -688,6 +707,36 @@ class Context:
         an untouched one"""
         out = np.zeros((max(self.height, 1), max(self.width, 1), 4), dtype=np.float32)   # (without a size the call answers before it writes)
         self._ck(self._lib.jpt_read_lightmap_f32(self.h, _ptr(out)), "jpt_read_lightmap_f32")
+        return out
+
+    # ---- directional lightmaps (jpt_set_bake_directional)
+    def set_bake_directional(self, enable=True):
+        """jpt_set_bake_directional: bake renders also keep the three first moments of the incoming light per texel, sum of (frame's
+        value * the world x, y, z of the direction its path left the surface in).  A change of the value resets the accumulation."""
+        self._ck(self._lib.jpt_set_bake_directional(self.h, 1 if enable else 0), "jpt_set_bake_directional")
+
+    def read_bake_directional(self) -> np.ndarray:
+        """jpt_read_bake_directional_f32: the raw sums, float32 [3, local rows, width, 4] -- plane k holds (M_k.r, M_k.g, M_k.b, 0), k =
+        world x, y, z, over the context's own rows in their local order.  Divide by the frame count for the mean."""
+        out = np.zeros((3, max(self.local_rows(), 1), max(self.width, 1), 4), dtype=np.float32)   # (without a size the call answers before it writes)
+        self._ck(self._lib.jpt_read_bake_directional_f32(self.h, _ptr(out)), "jpt_read_bake_directional_f32")
+        return out
+
+    def device_bake_directional(self, finished=False):
+        """jpt_device_bake_directional: (device pointer or None, bytes) of the raw or the finished planes"""
+        n = C.c_size_t(0)
+        p = self._lib.jpt_device_bake_directional(self.h, 1 if finished else 0, C.byref(n))
+        return p, int(n.value)
+
+    def bake_finish_directional(self):
+        """jpt_bake_finish_directional: jpt_bake_finish's filter and dilation over each of the three planes, with the same frame count,
+        images and parameters; the planes themselves and the L0 lightmap are not touched"""
+        self._ck(self._lib.jpt_bake_finish_directional(self.h), "jpt_bake_finish_directional")
+
+    def read_lightmap_directional(self) -> np.ndarray:
+        """jpt_read_lightmap_directional_f32: float32 [3, height, width, 4] -- plane k holds (the filtered mean of M_k, coverage)"""
+        out = np.zeros((3, max(self.height, 1), max(self.width, 1), 4), dtype=np.float32)
+        self._ck(self._lib.jpt_read_lightmap_directional_f32(self.h, _ptr(out)), "jpt_read_lightmap_directional_f32")
         return out
 
     # ---- light probes (jpt_set_probes, jpt_probe_project)

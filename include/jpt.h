@@ -649,7 +649,7 @@ int jpt_set_camera_model(jpt_ctx *ctx, int32_t model);
  * jpt_bake_finish (below) filters and dilates the accumulated map on the device.
  * Out of scope: conservative coverage (a triangle that covers no texel centre leaves no texel), seam stitching across UV islands,
  * atlas packing, next-event estimation at the texel itself (direct light reaches a texel by its first ray alone, so small emitters
- * converge slowly), directional (SH) lightmaps.  (Light probes: jpt_set_probes, below.) */
+ * converge slowly).  (Directional lightmaps: jpt_set_bake_directional, below.  Light probes: jpt_set_probes, below.) */
 int jpt_set_bake_texels(jpt_ctx *ctx, const float *position4, const float *normal4, int32_t width, int32_t height);
 int jpt_bake_begin(jpt_ctx *ctx, int32_t width, int32_t height);
 int jpt_bake_add_surface(jpt_ctx *ctx, const jpt_surface *surface, const float *uv2, const float *transform12);
@@ -698,6 +698,44 @@ int jpt_set_bake_finish_params(jpt_ctx *ctx, const jpt_bake_finish_params *param
 int jpt_bake_finish(jpt_ctx *ctx);
 int jpt_read_lightmap_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: (r, g, b, coverage) */
 
+/* ---- directional lightmaps: the first moments of the incoming light per texel (no reference counterpart; the other half of Godot's
+ * LightmapGI with `directional` on, which lets a normal-mapped surface lit by the lightmap keep its relief) ----
+ * With the switch on a bake render keeps, beside the sum of a texel's frames, three more sums:
+ *     M_k.c  =  sum over the frames f, in frame order, of  cur_f.c * d_f.k          k = world x, y, z;   c = r, g, b
+ * cur_f the frame's value exactly as the accumulation adds it (in JPT_ACCUM_REF_LDR8 the rgba8 value read back) and d_f the direction
+ * in which the texel's path of frame f left the surface, not renormalised.  Each term is one binary32 multiply and one add, in the
+ * accumulation's order; the first render after jpt_accum_reset overwrites; an invalid texel holds +0 in all nine values (DESIGN.md
+ * section 2; gdpathtracing_amd/csrc/jpt_bake_dir.h; tests/np_bake_dir.py restates it bit for bit).  M_k / frame_count estimates
+ * (1 / pi) * integral of L(w) w_k cos(theta) dw: the first moment of what accum / frame_count is the zeroth moment of.  No SH constant
+ * is folded in (INTEGRATION.md has the mapping to L1 coefficients).
+ *
+ * One kernel of its own, launched behind the accumulation of every bake render on the default kernel; no path kernel differs, and with
+ * the switch off no launch, argument or allocation of any render differs.  The switch has no effect on a render without bake images.
+ * jpt_set_bake_directional     a CHANGE of the value resets the accumulation as jpt_accum_reset does.  The planes, 48 B per texel of the
+ *                              context's rows, exist only while the switch is on and bake images are present.
+ * jpt_read_bake_directional_f32  3 * width * local_rows * 4 floats of raw sums: plane k at k * width * local_rows texels, (M_k.r, M_k.g,
+ *                              M_k.b, 0) per texel, the context's own rows in their local order.  Waits for the renders queued so far.
+ * jpt_device_bake_directional  the device pointer of the raw (finished == 0) or the finished planes and their size; NULL and 0 bytes
+ *                              when there are none.
+ * jpt_bake_finish_directional  jpt_bake_finish's filter and dilation, once per plane: the plane is the accumulation, the frame count,
+ *                              the bake images and jpt_set_bake_finish_params' parameters are the same.  The planes are filtered
+ *                              independently of one another and of the L0 map, as Godot denoises its layers.  Guides, working images
+ *                              and results of its own, 112 B per texel, kept and freed as jpt_bake_finish's.
+ * jpt_read_lightmap_directional_f32  3 * W * H * 4 floats: plane k holds (x, y, z of M_k's filtered mean read as r, g, b; coverage).
+ * JPT_E_STATE, with a message naming jpt_set_bake_directional: a render with the switch on and bake images present under
+ * JPT_KERNEL_REFERENCE_LAYOUT (it adds frame by frame and keeps no per-frame values), a denoising mode other than
+ * JPT_DENOISE_PROGRESSIVE, or jpt_set_debug_steps.  jpt_read_bake_directional_f32: JPT_E_STATE with the switch off, without bake images or
+ * before a bake render with the switch on.  jpt_bake_finish_directional: jpt_bake_finish's refusals, and the switch off.
+ * jpt_read_lightmap_directional_f32 before a jpt_bake_finish_directional at the current size and images: JPT_E_STATE.  Host-only contexts:
+ * JPT_E_DEVICE.  There is no jpt_multi_* form.
+ * Not covered: the reference-layout kernel, jpt_multi, encoded output (jpt_encode has no source for the planes), joint filtering with
+ * the L0 map, SH above band 1. */
+int jpt_set_bake_directional(jpt_ctx *ctx, int32_t enable);
+int jpt_read_bake_directional_f32(jpt_ctx *ctx, float *out);
+void *jpt_device_bake_directional(jpt_ctx *ctx, int32_t finished, size_t *bytes_out);
+int jpt_bake_finish_directional(jpt_ctx *ctx);
+int jpt_read_lightmap_directional_f32(jpt_ctx *ctx, float *out);
+
 /* ---- light probes: a sphere tile per probe, projected to L2 spherical harmonics on the device (no reference counterpart; the probes
  * of Godot's LightmapGI that light dynamic objects) ----
  * With probes present every render is a PROBE render: the image holds one tile_w x tile_h tile per probe, side by side, and one render
@@ -743,7 +781,7 @@ int jpt_read_lightmap_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats: (r, 
  * last reset; a denoising mode other than JPT_DENOISE_PROGRESSIVE; DEBUG_STEPS mode; a screen partition (the gathering context
  * projects, as with jpt_display).  jpt_read_probe_sh_f32 before a jpt_probe_project of the current probes and size: JPT_E_STATE.
  * Unknown flags: JPT_E_INVALID.  There is no jpt_multi_* form.
- * Out of scope: directional (per-texel SH) lightmaps, probe placement and detection of probes inside geometry (jpt_query_rays answers
+ * Out of scope: probe placement and detection of probes inside geometry (jpt_query_rays answers
  * that), band 3 and above, octahedral tiles.  (Cube captures: jpt_set_reflection_probes, below; half-float output: jpt_encode, below.) */
 enum { JPT_PROBE_RADIANCE = 0, JPT_PROBE_IRRADIANCE = 1 };
 int jpt_set_probes(jpt_ctx *ctx, const float *position3, int32_t n_probes, int32_t tile_w, int32_t tile_h, int32_t probes_per_row);
@@ -1354,6 +1392,14 @@ int jpt_debug_bake_raster(int device_id, const jpt_surface *surface, const float
  * jpt_bake_finish launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host, in plain loops. */
 int jpt_debug_bake_finish(int device_id, int32_t width, int32_t height, const jpt_bake_finish_params *params,
                           const float *mean4, const float *position4, const float *normal4, float *out);
+/* The moments of jpt_set_bake_directional on the host: the functions the moment kernel inlines (jpt_bake_dir.h), compiled for the host,
+ * in a plain loop over the texels of width x height images and the n_frames frames of radiance3 [3 ((f * height + y) * width + x) ..],
+ * frame f being frame first_frame_index + f.  accum_mode: JPT_ACCUM_HDR_F32 takes a frame's value as it is, JPT_ACCUM_REF_LDR8 through
+ * the rgba8 store and load.  frame_count >= 1 is that of the first frame: 1 overwrites moments_inout, more continues the sums it holds.
+ * moments_inout: 3 * width * height * 4 floats, laid out as jpt_read_bake_directional_f32's.  The size and the images are checked as
+ * jpt_set_bake_texels checks them. */
+int jpt_debug_bake_moments(const float *position4, const float *normal4, int32_t width, int32_t height, const float *radiance3,
+                           int32_t n_frames, uint32_t first_frame_index, uint32_t frame_count, int32_t accum_mode, float *moments_inout);
 /* The first rays of a probe render's paths (jpt_set_probes) for every pixel of frame frame_index of the image the probes make (width
  * = probes_per_row * tile_w, height = ceil(n_probes / probes_per_row) * tile_h): origins3_out / dirs3_out [3 (y * width + x) ..] and
  * valid_out[y * width + x] = 1, or zeros and 0 for a pixel of a tile without a probe.  The arguments are checked as jpt_set_probes
