@@ -122,44 +122,73 @@ __device__ __forceinline__ bool in_mask(const unsigned long long m) { return __b
 // mask of the lanes that hold a ray; the round returns the mask of the lanes whose walk it completed.  Same steps per ray, same
 // phase decisions and counters as walk_round; what differs is how the wave arrives at them:
 //  - a ballot of a loop-carried flag, or of a conjunction, compiles to v_cndmask 0/1 + v_cmp_ne (2 x 4.2 cycles of VALU issue),
-//    a ballot of ONE comparison to the comparison alone.  So the phase masks are built from ballot(cur < 0), ballot(sp > 0) and
-//    the two flags `have` and `in_blas`, combined with scalar and / andn2, instead of one ballot per conjunction (five);
+//    a ballot of ONE comparison to the comparison alone.  So nothing but single comparisons is balloted: cur < 0, cur >= 0,
+//    cur == kSentinel, top > base, k0 < kNoChild; everything else is scalar and / andn2 / or on masks;
 //  - `active` is not balloted at all: it is `act`, and the per-lane predicates come back from masks (in_mask);
-//  - the finished lanes need no look at `have` after the phases: leaf_step leaves have = false and the stack as it was,
-//    instance_step (not REACH) leaves have = true, everyone else is untouched -- have-after = (have & ~leaves) | instances;
-//  - pop_next restores the world ray's slab constants on demand (pop_next<true>), not once per round in the loop's pre-header.
+//  - the walk's flags `have` and `in_blas` are not per-lane values but the two wave-uniform masks of WalkMasks, carried by
+//    trace_queue from round to round.  Every update is made in wave-uniform control flow, from the mask of the branch the
+//    lanes' step ran under: a pop sets the popping lanes' `have` (but for a sentinel that was the last entry), a sentinel clears
+//    their `in_blas`, a record step leaves have = ballot(k0 < kNoChild) for its takers, a leaf step clears `have`, an instance
+//    entry sets both, a refill sets `have` from n_instances != 0 and clears `in_blas` (trace_queue);
+//  - the stack position is the LDS address of the lane's next entry (Traversal::Masked::top), sp > 0 is top > base;
+//  - pop_next is written out here in two pieces, the pop and what follows a sentinel, each under the mask of its takers, with
+//    the world ray's slab constants restored on demand (Traversal::restore_world: pop_next<true>'s restore), not once per round
+//    in the loop's pre-header.
+struct WalkMasks {
+    unsigned long long have = 0ull, in_blas = 0ull;
+};
 template <bool COUNT, bool W4>
-__device__ __forceinline__ unsigned long long walk_round_masked(Traversal<COUNT, W4>& tr, const unsigned long long act, const WideSceneDev& sc,
+__device__ __forceinline__ unsigned long long walk_round_masked(Traversal<COUNT, W4>& tr, typename Traversal<COUNT, W4>::Masked& ml, WalkMasks& wm,
+                                                                const unsigned long long act, const WideSceneDev& sc,
                                                                 const typename Traversal<COUNT, W4>::Stack& st, DevCounters& cnt, const WfTune& tune,
                                                                 uint32_t& steps)
 {
+    using Walk = Traversal<COUNT, W4>;
     const int kNodeMinLanes = tune.node_min_lanes;
     const bool lane0 = (threadIdx.x & 63) == 0;
-    const bool active = in_mask(act);
     if (COUNT && lane0) cnt.phase[0]++;
     const int na = __popcll(act);
     const int cap = (na * tune.phase_frac16) >> 4;   // (the thresholds' caps: see walk_round)
     const int lmin = tune.leaf_min_lanes < cap ? tune.leaf_min_lanes : cap;
     const int imin = tune.inst_min_lanes < cap ? tune.inst_min_lanes : cap;
+    const uint32_t base = Walk::lds_base(st);
+    unsigned long long have_m = wm.have, blas_m = wm.in_blas;
     for (int it = 0; it < 64; it++) {
-        if (active && !tr.have && tr.sp > 0) tr.template pop_next<true>(st);
-        const bool want = active && tr.wants_node();
-        const unsigned long long m = __ballot(want);
+        // pop_next for the lanes that hold no record and have entries left (active && !have && sp > 0)
+        const unsigned long long pm = act & ~have_m & __ballot(ml.top > base);
+        if (pm) {
+            if (in_mask(pm)) tr.cur = tr.pop_at(st, ml.top);
+            const unsigned long long sent = pm & __ballot(tr.cur == kSentinel);
+            have_m |= pm & ~sent;
+            if (sent) {
+                // out of the instance; if the sentinel was the last entry the walk is over (cur stays kSentinel, have false)
+                blas_m &= ~sent;
+                const unsigned long long more = sent & __ballot(ml.top > base);
+                if (in_mask(more)) {
+                    tr.cur = tr.pop_at(st, ml.top);
+                    if (!Walk::kLean || tr.cur >= 0) tr.restore_world();   // (only a TLAS record reads the current-level ray: pop_next)
+                }
+                have_m |= more;
+            }
+        }
+        const unsigned long long m = act & have_m & __ballot(tr.cur >= 0);   // wants_node()
         if (m == 0 || (it > 0 && __popcll(m) < kNodeMinLanes)) break;
         if (COUNT && lane0) {
             cnt.phase[1]++;
             cnt.phase[2] += (unsigned long long)__popcll(m);
         }
-        if (want) tr.node_step(sc, st, cnt);
+        const bool want = in_mask(m);
+        ml.in_blas = in_mask(blas_m);
+        if (want) tr.template node_step<true>(sc, st, cnt, &ml);
         if (COUNT && want) steps++;
+        have_m = (have_m & ~m) | (m & __ballot(ml.k0 < Walk::kNoChild));
     }
-    const unsigned long long hm = __ballot(tr.have), bm = __ballot(tr.in_blas);   // (the two flags)
-    const unsigned long long lf = __ballot(tr.cur < 0), sm = __ballot(tr.sp > 0);
-    const unsigned long long hv = act & hm;
-    unsigned long long wlm = hv & lf & bm, wim = hv & lf & ~bm;   // wants_leaf(), wants_instance()
+    const unsigned long long lf = __ballot(tr.cur < 0), sm = __ballot(ml.top > base);
+    const unsigned long long hv = act & have_m;
+    unsigned long long wlm = hv & lf & blas_m, wim = hv & lf & ~blas_m;   // wants_leaf(), wants_instance()
     if (W4 && (tune.leaf_min_lanes > 1 || tune.inst_min_lanes > 1)) {
         const int nl = __popcll(wlm), ni = __popcll(wim);
-        const bool nodes_left = ((hv & ~lf) | (act & ~hm & sm)) != 0ull;
+        const bool nodes_left = ((hv & ~lf) | (act & ~have_m & sm)) != 0ull;
         const bool run_l = nl >= lmin || !(nodes_left || ni >= imin);
         const bool run_i = ni >= imin || !(nodes_left || (run_l && nl > 0));
         wlm = run_l ? wlm : 0ull;
@@ -178,9 +207,14 @@ __device__ __forceinline__ unsigned long long walk_round_masked(Traversal<COUNT,
     }
     const bool wl = in_mask(wlm), wi = in_mask(wim);
     if (wl) tr.leaf_step(sc, cnt);
-    if (wi) tr.instance_step(sc, st, cnt);
+    if (wi) tr.template instance_step<true>(sc, st, cnt, &ml);
     if (COUNT && (wl || wi)) steps++;
-    return act & ~((hm & ~wlm) | wim) & ~sm;   // active && !have && sp == 0, see above
+    // a leaf step leaves have = false and the stack as it was, an instance entry have = in_blas = true; everyone else is untouched
+    have_m = (have_m & ~wlm) | wim;
+    blas_m |= wim;
+    wm.have = have_m;
+    wm.in_blas = blas_m;
+    return act & ~have_m & ~sm;   // active && !have && sp == 0 (an instance entry's push changes sp, but those lanes `have`)
 }
 
 // What a render writes once and reads once -- ray and hit queues, finished paths' colours, the framebuffers -- goes past the caches
@@ -505,9 +539,13 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
     const float4* __restrict__ qo = wb.ray_o[bounce & 1];
     const float4* __restrict__ qd = wb.ray_d[bounce & 1];
     Traversal<COUNT, W4> tr;
-    tr.have = tr.in_blas = false;   // (walk_round_masked ballots these members of every lane and masks the answers with `act`)
     tr.cur = 0;
-    tr.sp = 0;
+    // the walk's flags as lane masks and the stack position as an LDS address (walk_round_masked); tr.have / in_blas / sp are not used
+    WalkMasks wm;
+    typename Traversal<COUNT, W4>::Masked ml;
+    ml.top = Traversal<COUNT, W4>::lds_base(my_stack);
+    ml.k0 = 0u;
+    ml.in_blas = false;
     // The wave's bookkeeping is wave-uniform and lives in scalars: `act`, the lanes that hold a ray -- the round takes the
     // finished ones out, the refill adds the ones it filled; idle lanes, the exit tests and the tail's lanes all derive from it --
     // and `unsaved`, the lanes whose finished walk has not written its hit yet.
@@ -547,10 +585,13 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
                     const size_t loc = (size_t)(seg0 + k) * dm.seg_cap + (idx - first);
                     const float4 ro = stream_ld4(&qo[loc]), rd = stream_ld4(&qd[loc]);
                     tr.begin(sc, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z));
+                    ml.top = Traversal<COUNT, W4>::lds_base(my_stack);   // begin()'s sp = 0
                     my_loc = loc;
                     walk_steps = 0;
                 }
                 act |= fill;
+                wm.have = sc.n_instances != 0 ? (wm.have | fill) : (wm.have & ~fill);   // begin()'s have and in_blas
+                wm.in_blas &= ~fill;
             }
         }
         if (act == 0ull) {
@@ -558,7 +599,7 @@ __device__ __forceinline__ void trace_queue(const WideSceneDev& sc, const Wf2Buf
             continue;
         }
         {
-            const unsigned long long done = walk_round_masked<COUNT, W4>(tr, act, sc, my_stack, cnt, tune, walk_steps);
+            const unsigned long long done = walk_round_masked<COUNT, W4>(tr, ml, wm, act, sc, my_stack, cnt, tune, walk_steps);
             act &= ~done;
             unsaved |= done;
             if (COUNT) {

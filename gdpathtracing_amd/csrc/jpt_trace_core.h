@@ -125,6 +125,56 @@ struct Traversal {
         return v;
     }
 
+    // ---- the masked form of the walk's state (the tracing launches' rounds, walk_round_masked) ----------------------------
+    //
+    // There `have` and `in_blas` are not members but two wave-uniform lane masks kept in scalars by the round, and the stack
+    // position is not `sp` but the LDS BYTE ADDRESS of the lane's next free entry, top = column + sp * stride * 4: a pop is one
+    // subtract (and the clamp) in front of the read, a push the write and one add, instead of a shift-or per access.  The
+    // spill region is the one of push / pop -- entries lds_entries .. lds_entries + spill_entries in scratch, the sentinel
+    // past capacity, the LDS read issued unconditionally on the clamped row -- reached through ONE comparison of the
+    // address with the lane's limit.  What a lane has to tell the round comes back in `Masked`; the members `have`, `in_blas`
+    // and `sp` are not read on this path (begin() and leaf_step() still write them: dead stores).
+    typedef __attribute__((address_space(3))) int32_t LdsWord;
+    struct Masked {
+        uint32_t top;    // LDS byte address of the next free entry of this lane's column
+        uint32_t k0;     // after a record step: the nearest child's key; the lane holds a record iff k0 < kNoChild
+        bool in_blas;    // the lane's bit of the round's in_blas mask (counting builds and two-child records read it)
+    };
+    static constexpr uint32_t kNoChild = 0x7f800000u;   // (the record step's kInvalid)
+    static __device__ __forceinline__ uint32_t lds_base(const Stack& st) { return (uint32_t)(uintptr_t)(LdsWord*)st.lds; }
+    static __device__ __forceinline__ uint32_t lds_limit(const Stack& st) { return lds_base(st) + (uint32_t)(st.lds_entries * st.stride) * 4u; }
+    static __device__ __forceinline__ LdsWord* lds_at(uint32_t a) { return (LdsWord*)(uintptr_t)a; }
+    __device__ __forceinline__ void push_at(const Stack& st, uint32_t& top, int32_t v) const
+    {
+        const uint32_t lim = lds_limit(st);
+        if (__builtin_expect(top < lim, 1)) *lds_at(top) = v;
+        else {
+            const int k = (int)((top - lim) / ((uint32_t)st.stride * 4u));
+            if (k < st.spill_entries) st.spill[k] = v;
+        }
+        top += (uint32_t)st.stride * 4u;
+    }
+    __device__ __forceinline__ int32_t pop_at(const Stack& st, uint32_t& top) const
+    {
+        const uint32_t lim = lds_limit(st), last = lim - (uint32_t)st.stride * 4u;
+        top -= (uint32_t)st.stride * 4u;
+        int32_t v = *lds_at(top < last ? top : last);
+        if (__builtin_expect(top >= lim, 0)) {
+            const int k = (int)((top - lim) / ((uint32_t)st.stride * 4u));
+            v = k < st.spill_entries ? st.spill[k] : kSentinel;
+        }
+        return v;
+    }
+    // pop_next's restore of the world ray (its ON_DEMAND form: see there)
+    __device__ __forceinline__ void restore_world()
+    {
+        o = wo;
+        d = wd;
+        if (kLean) asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
+        if (kLean) set_level();
+        else rD = wrD;
+    }
+
     __device__ __forceinline__ void begin(const WideSceneDev& sc, f3 ro, f3 rd)
     {
         wo = ro;
@@ -173,7 +223,8 @@ struct Traversal {
 
     // four-child record: four box tests on the quantised planes, children visited nearest first.  The order among
     // children is a performance choice only (the closest hit does not depend on it).
-    __device__ __forceinline__ void node_step4(const WideSceneDev& sc, const Stack& st, DevCounters& cnt)
+    template <bool MASKED = false>
+    __device__ __forceinline__ void node_step4(const WideSceneDev& sc, const Stack& st, DevCounters& cnt, Masked* ms = nullptr)
     {
         const char* __restrict__ base = reinterpret_cast<const char*>(sc.nodesq);
         const uint32_t rec = (uint32_t)cur << 6;
@@ -181,14 +232,17 @@ struct Traversal {
         const float4 h1 = ld4(base + (rec + 16u));   // scale.y, scale.z, lo_x, lo_y
         const float4 h2 = ld4(base + (rec + 32u));   // lo_z, hi_x, hi_y, hi_z
         const float4 cf = ld4(base + (rec + 48u));   // child references
-        node_step4_rec(h0, h1, h2, cf, st, cnt);
+        node_step4_rec<MASKED>(h0, h1, h2, cf, st, cnt, ms);
     }
-    // ... the step itself, on a record that is already in registers (the pooled launches ask for the records of their NEXT turn
-    // before they compute the current one: wf2_trace_pool)
-    __device__ __forceinline__ void node_step4_rec(const float4 h0, const float4 h1, const float4 h2, const float4 cf, const Stack& st, DevCounters& cnt)
+    // ... the step itself, on a record that is already in registers (node_step4 is its one caller today).  MASKED (the tracing
+    // launches' rounds): `have` is not written -- the round reads it off ms->k0 -- and the pushes go through the stack's address.
+    template <bool MASKED = false>
+    __device__ __forceinline__ void node_step4_rec(const float4 h0, const float4 h1, const float4 h2, const float4 cf, const Stack& st, DevCounters& cnt,
+                                                   Masked* ms = nullptr)
     {
+        static_assert(!(MASKED && REACH), "the masked rounds do not walk with reach records");
         if (COUNT) {
-            if (in_blas) cnt.blas_expand++;
+            if (MASKED ? ms->in_blas : in_blas) cnt.blas_expand++;
             else cnt.tlas_expand++;
         }
         // t = (origin + q * scale - o) * rD = q * (scale * rD) + (origin * rD + ood)
@@ -237,24 +291,38 @@ struct Traversal {
         cswap(k1, k3, r1, r3);
         cswap(k1, k2, r1, r2);
         // usable children are now a prefix: descend into the nearest, push the others farthest first
-        have = k0 < kInvalid;
-        cur = have ? r0 : cur;
-        if (k1 < kInvalid) {
-            if (k2 < kInvalid) {
-                if (k3 < kInvalid) push(st, r3);
-                push(st, r2);
+        if constexpr (MASKED) {
+            ms->k0 = k0;
+            cur = k0 < kInvalid ? r0 : cur;
+            if (k1 < kInvalid) {
+                if (k2 < kInvalid) {
+                    if (k3 < kInvalid) push_at(st, ms->top, r3);
+                    push_at(st, ms->top, r2);
+                }
+                push_at(st, ms->top, r1);
             }
-            push(st, r1);
+        } else {
+            have = k0 < kInvalid;
+            cur = have ? r0 : cur;
+            if (k1 < kInvalid) {
+                if (k2 < kInvalid) {
+                    if (k3 < kInvalid) push(st, r3);
+                    push(st, r2);
+                }
+                push(st, r1);
+            }
         }
     }
 
     // internal record: both children's boxes in one 64-byte fetch; descends into the nearer valid child
-    __device__ __forceinline__ void node_step(const WideSceneDev& sc, const Stack& st, DevCounters& cnt)
+    template <bool MASKED = false>
+    __device__ __forceinline__ void node_step(const WideSceneDev& sc, const Stack& st, DevCounters& cnt, Masked* ms = nullptr)
     {
         if (W4) {
-            node_step4(sc, st, cnt);
+            node_step4<MASKED>(sc, st, cnt, ms);
             return;
         }
+        const bool in_blas = MASKED ? ms->in_blas : this->in_blas;
         const WideNode* n = (in_blas ? sc.blas_nodes : sc.tlas_nodes) + cur;
         const float4 a = ld4(&n->lmin[0]);  // lmin.xyz lmax.x
         const float4 b = ld4(&n->lmax[1]);  // lmax.yz rmin.xy
@@ -272,14 +340,24 @@ struct Traversal {
         const bool left_first = d1 < d2;
         const int32_t near_ref = left_first ? left : right, far_ref = left_first ? right : left;
         const bool near_v = left_first ? lv : rv, far_v = left_first ? rv : lv;
-        have = false;
-        if (near_v) {
-            if (far_v) push(st, far_ref);
-            cur = near_ref;
-            have = true;
-        } else if (far_v) {
-            cur = far_ref;
-            have = true;
+        if constexpr (MASKED) {
+            if (near_v) {
+                if (far_v) push_at(st, ms->top, far_ref);
+                cur = near_ref;
+            } else if (far_v) {
+                cur = far_ref;
+            }
+            ms->k0 = (near_v || far_v) ? 0u : kNoChild;
+        } else {
+            have = false;
+            if (near_v) {
+                if (far_v) push(st, far_ref);
+                cur = near_ref;
+                have = true;
+            } else if (far_v) {
+                cur = far_ref;
+                have = true;
+            }
         }
     }
 
@@ -368,8 +446,11 @@ struct Traversal {
     }
 
     // TLAS leaf: enter the instance (main.glsl:316-322)
-    __device__ __forceinline__ void instance_step(const WideSceneDev& sc, const Stack& st, DevCounters& cnt)
+    // (MASKED: the round sets the takers' bits of both of its masks itself)
+    template <bool MASKED = false>
+    __device__ __forceinline__ void instance_step(const WideSceneDev& sc, const Stack& st, DevCounters& cnt, Masked* ms = nullptr)
     {
+        static_assert(!(MASKED && REACH), "the masked rounds do not walk with reach records");
         cur_inst = (uint32_t)~cur;
         if (REACH) {
             // the reference enters the instance only through its TLAS leaf's box (no test when the TLAS is one leaf)
@@ -400,10 +481,15 @@ struct Traversal {
         d = mk3(m0.x * wd.x + m0.w * wd.y + m1.z * wd.z, m0.y * wd.x + m1.x * wd.y + m1.w * wd.z,
                 m0.z * wd.x + m1.y * wd.y + m2.x * wd.z);
         set_level();
-        in_blas = true;
-        push(st, kSentinel);
-        cur = root;
-        have = true;
+        if constexpr (MASKED) {
+            push_at(st, ms->top, kSentinel);
+            cur = root;
+        } else {
+            in_blas = true;
+            push(st, kSentinel);
+            cur = root;
+            have = true;
+        }
     }
 
     // take the next record off the stack (precondition: !have && sp > 0).  Leaving an instance restores

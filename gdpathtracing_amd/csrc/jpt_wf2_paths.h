@@ -158,6 +158,10 @@ __global__ __launch_bounds__(kBlock, JPT_PRIMARY_WAVES) void JPT_PRIMARY_NAME(Wi
     // The queue sizes of bounces >= 1 are accumulated with atomics by wf2_shade and must start from zero: block s clears segment s's
     // word of every later row (and block 0 the set-aside counts behind them) -- this launch completes before the first wf2_shade
     // starts, and one launch fewer per render is one link less in a chain of a dozen (a memset used to do this).
+    // (Thread t clears row t, threads 192.. of block 0 the 64 set-aside words: the two ranges must stay apart and inside the block.
+    // jpt_set_params refuses max_bounces > kMaxBounces; the same two conditions stand at the carve, wf2_layout.)
+    static_assert(kBlock >= 192 + 64, "threads 192 .. 255 of block 0 clear the 64 set-aside words");
+    static_assert(kMaxBounces + 1 < 192, "threads 1 .. max_bounces + 1 clear the queue-size rows: they must end below thread 192");
     if ((int)threadIdx.x >= 1 && (int)threadIdx.x <= fp.max_bounces + 1) wb.qcount[(size_t)threadIdx.x * kSegments + seg] = 0u;
     if (seg == 0 && threadIdx.x >= 192u) wb.redo_count[threadIdx.x - 192u] = 0u;
     __syncthreads();
