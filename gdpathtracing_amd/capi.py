@@ -32,6 +32,7 @@ TONEMAP_ACES_REF, TONEMAP_REINHARD, TONEMAP_CLAMP = 0, 1, 2
 TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
 METER_AVERAGE, METER_CENTER_WEIGHTED = 0, 1
 METER_EMPTY, METER_FIRST = 1, 2
+NOISE_EMPTY, NOISE_CONVERGED = 1, 2
 STREAM_PRIORITY_DEFAULT, STREAM_PRIORITY_NORMAL, STREAM_PRIORITY_HIGH, STREAM_PRIORITY_LOW = 0, 1, 2, 3
 TREE_NONE, TREE_AS_GIVEN, TREE_REFERENCE_EXACT, TREE_NATIVE_REACH, TREE_NATIVE_WATERTIGHT = range(5)
 QUERY_CLOSEST, QUERY_ANY = 0, 1
@@ -78,6 +79,8 @@ SYMBOLS = [
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
+    "jpt_set_variance", "jpt_read_variance_f32", "jpt_device_variance", "jpt_set_noise_params", "jpt_noise_estimate", "jpt_read_noise",
+    "jpt_read_noise_tiles_f32", "jpt_device_noise_tiles", "jpt_render_converge", "jpt_debug_variance_moments", "jpt_debug_noise_estimate",
     "jpt_query_rays", "jpt_query_rays_device", "jpt_query_pixels",
     "jpt_scene_set_mesh_rig", "jpt_scene_pose_mesh", "jpt_scene_clear_mesh_rig", "jpt_multi_set_mesh_rig", "jpt_multi_pose_mesh", "jpt_multi_clear_mesh_rig",
     "jpt_debug_skin",
@@ -150,6 +153,23 @@ class MeterResult(C.Structure):
     """jpt_meter_result (32 bytes)"""
     _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("luminance", C.c_float), ("flags", C.c_uint32),
                 ("weight", C.c_uint64), ("used", C.c_uint64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class NoiseParams(C.Structure):
+    """jpt_noise_params; the defaults are the library's"""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("percentile_permille", C.c_int32), ("allowed_permille", C.c_int32)]
+
+    def __init__(self, threshold=0.05, floor=0.01, percentile_permille=950, allowed_permille=0):
+        super().__init__(threshold, floor, percentile_permille, allowed_permille)
+
+
+class NoiseResult(C.Structure):
+    """jpt_noise_result (32 bytes)"""
+    _fields_ = [("error", C.c_float), ("max_error", C.c_float), ("flags", C.c_uint32), ("tiles_above", C.c_uint32),
+                ("counted", C.c_uint64), ("above", C.c_uint64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -460,6 +480,20 @@ def lib():
         L.jpt_read_meter.argtypes = [vp, C.POINTER(MeterResult), vp]
         L.jpt_set_auto_exposure.argtypes = [vp, i32]
         L.jpt_debug_meter.argtypes = [C.c_int, i32, i32, C.POINTER(MeterParams), vp, C.c_float, vp, C.POINTER(MeterResult)]
+    if hasattr(L, "jpt_set_variance") or "JPT_LIB" not in os.environ:
+        L.jpt_set_variance.argtypes = [vp, i32]
+        L.jpt_read_variance_f32.argtypes = [vp, vp]
+        L.jpt_device_variance.restype = vp
+        L.jpt_device_variance.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.jpt_set_noise_params.argtypes = [vp, C.POINTER(NoiseParams)]
+        L.jpt_noise_estimate.argtypes = [vp]
+        L.jpt_read_noise.argtypes = [vp, C.POINTER(NoiseResult), vp]
+        L.jpt_read_noise_tiles_f32.argtypes = [vp, vp]
+        L.jpt_device_noise_tiles.restype = vp
+        L.jpt_device_noise_tiles.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.jpt_render_converge.argtypes = [vp, i32, i32, u32, C.POINTER(i32), C.POINTER(NoiseResult)]
+        L.jpt_debug_variance_moments.argtypes = [vp, i32, u32, i32, vp, vp, i32, i32]
+        L.jpt_debug_noise_estimate.argtypes = [C.c_int, i32, i32, C.POINTER(NoiseParams), vp, vp, u32, vp, vp, vp, C.POINTER(NoiseResult)]
     if hasattr(L, "jpt_query_rays") or "JPT_LIB" not in os.environ:
         L.jpt_query_rays.argtypes = [vp, i32, vp, u32, vp, vp]
         L.jpt_query_rays_device.argtypes = [vp, i32, vp, u32, vp, vp]

@@ -58,6 +58,7 @@ int alloc_framebuffers(jpt_ctx* c)
     }
     c->frame_count = 0;
     c->assembled = c->assembled_ldr = false;
+    c->variance_valid = c->noise_valid = false;   // (jpt_set_variance's plane is of the frames before; the next render overwrites it)
     return JPT_OK;
 }
 
@@ -797,6 +798,7 @@ int prepare_render(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefro
     }
     c->trace_events_used = (int32_t)need_ev;
     if (!r.primary.sky_cull()) return JPT_OK;   // (r.cull stays off, n < 0, and r.sky_tiles null)
+    if (r.variance) return JPT_OK;   // (likewise: jpt_set_variance's kernel reads every pixel's frames, and a culled pixel's are never stored)
     compute_sky_cull(c, r.cull);
     // the sky cells of whole tiles, for wf2_accumulate (REF_LDR8 sums of several frames): on the context's stream, which every
     // accumulation is ordered behind; again only when the camera (its frame index aside), the image size or the partition changed.
@@ -959,6 +961,33 @@ int ensure_bake_dir(jpt_ctx* c)
     return JPT_OK;
 }
 
+// jpt_set_variance: what a render with the switch on refuses -- the moment kernel reads the per-frame values the wavefront route
+// keeps, of radiance, summed progressively
+int check_variance(jpt_ctx* c)
+{
+    if (!c->variance) return JPT_OK;
+    if (c->kernel_variant != JPT_KERNEL_WAVEFRONT)
+        return fail(c, JPT_E_STATE, "jpt_set_variance: the reference-layout kernel adds frame by frame and keeps no per-frame values: set "
+                                    "JPT_KERNEL_WAVEFRONT (jpt_set_kernel) or switch the variance plane off");
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_set_variance: the moment follows the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE "
+                                    "(temporal reprojection and JPT_DENOISE_NONE keep no sum)");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_set_variance: a DEBUG_STEPS render holds step counts, not radiance (jpt_set_debug_steps)");
+    return JPT_OK;
+}
+
+// the plane at the size of the context's rows, made (and zeroed) when it is missing or of another size
+int ensure_variance(jpt_ctx* c)
+{
+    const size_t need = (size_t)c->width * (size_t)c->local_rows;
+    if (c->d_variance.p && c->d_variance.n == need) return JPT_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (renders in flight may write the old plane: every one ends with work on the stream)
+    c->variance_valid = c->noise_valid = false;
+    HIP_TRY(c, c->d_variance.resize(need));
+    if (need) HIP_TRY(c, hipMemsetAsync(c->d_variance.p, 0, need * sizeof(float4), c->stream));
+    return JPT_OK;
+}
+
 // validate -> prepare -> plan -> launch -> read back
 int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
 {
@@ -978,6 +1007,11 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
         if ((rc = ensure_bake_dir(c)) != JPT_OK) return rc;
         r.bake_dir = c->d_bake_dir.p;
     }
+    if ((rc = check_variance(c)) != JPT_OK) return rc;
+    if (c->variance && c->local_rows > 0 && c->width > 0 && n_frames > 0) {
+        if ((rc = ensure_variance(c)) != JPT_OK) return rc;
+        r.variance = c->d_variance.p;
+    }
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
     if (c->local_rows > 0 && c->width > 0 && n_frames > 0) {
@@ -986,6 +1020,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
         rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->d_depth.p : nullptr);
         if (rc != JPT_OK) return rc;
         if (r.bake_dir) c->bake_dir_valid = true;
+        if (r.variance) c->variance_valid = true;
         pipelined = p.route == LaunchPlan::kSlot;
         if (c->denoise == JPT_DENOISE_TEMPORAL) {
             // TemporalReprojection::render's dispatch (temporal_reprojection.cpp:71): screen + depth of this frame in,
@@ -2836,6 +2871,182 @@ int jpt_read_meter(jpt_ctx* c, jpt_meter_result* out, uint32_t* hist256)
     if (hist256) {
         if ((rc = staged_read(c, c->d_meter_bins.p, kMeterBins * sizeof(uint32_t))) != JPT_OK) return rc;
         std::memcpy(hist256, c->h_read_pinned.p, kMeterBins * sizeof(uint32_t));
+    }
+    return JPT_OK;
+}
+
+// ---- jpt_set_variance, jpt_noise_estimate, jpt_render_converge (jpt_variance.h, jpt_kernels_variance.hip) -------------------------
+
+int jpt_set_variance(jpt_ctx* c, int32_t enable)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_variance: host-only context: the moment is made on the device");
+    const bool on = enable != 0;
+    if (on == c->variance) return JPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->d_variance.p || c->d_noise_tiles.p) {
+        // the renders queued so far add to the plane: they finish first, then the plane and the tile map go
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->variance_release();
+    }
+    c->variance_valid = c->noise_valid = false;
+    c->variance = on;
+    return jpt_accum_reset(c);   // the sum and the moment are of the same frames: both start over
+}
+
+// the plane of a read or of an estimate: JPT_OK, or the refusal
+static int variance_ready(jpt_ctx* c, const char* call)
+{
+    const std::string who = std::string(call) + ": ";
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, who + "host-only context: the moment is made on the device");
+    if (!c->variance) return fail(c, JPT_E_STATE, who + "the variance plane is switched off (jpt_set_variance)");
+    if (!c->d_variance.p || !c->variance_valid || c->d_variance.n != (size_t)c->width * (size_t)c->local_rows)
+        return fail(c, JPT_E_STATE, who + "no render with the switch on at the current size yet");
+    return JPT_OK;
+}
+
+int jpt_read_variance_f32(jpt_ctx* c, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_variance_f32: null output");
+    int rc = variance_ready(c, "jpt_read_variance_f32");
+    if (rc != JPT_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the renders queued so far, as jpt_read_accum_f32)
+    const size_t n = c->d_variance.n * 4;   // floats
+    if ((rc = staged_read(c, c->d_variance.p, n * sizeof(float))) != JPT_OK) return rc;
+    if (c->world == 1) std::memcpy(out, c->h_read_pinned.p, n * sizeof(float));
+    else {
+        std::memset(out, 0, (size_t)c->width * c->height * 16);
+        scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 4);
+    }
+    return JPT_OK;
+}
+
+void* jpt_device_variance(jpt_ctx* c, size_t* bytes_out)
+{
+    if (bytes_out) *bytes_out = 0;
+    if (!c || c->device < 0 || !c->variance || !c->d_variance.p || !c->variance_valid) return nullptr;
+    if (bytes_out) *bytes_out = c->d_variance.n * sizeof(float4);
+    return c->d_variance.p;
+}
+
+int jpt_set_noise_params(jpt_ctx* c, const jpt_noise_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    NoiseParams p;
+    if (params) {
+        p.threshold = params->threshold;
+        p.floor = params->floor;
+        p.percentile_permille = params->percentile_permille;
+        p.allowed_permille = params->allowed_permille;
+    }
+    std::string why;
+    const int rc = check_noise_params(p, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
+    c->noise_params = p;
+    return JPT_OK;
+}
+
+int jpt_noise_estimate(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
+        return fail(c, JPT_E_STATE, "jpt_noise_estimate reads the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
+    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_noise_estimate: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
+    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_noise_estimate needs the whole image on one context (world == 1)");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
+    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_noise_estimate: jpt_set_params not called");
+    int rc = variance_ready(c, "jpt_noise_estimate");
+    if (rc != JPT_OK) return rc;
+    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_noise_estimate: no frame accumulated since the last reset");
+    if ((uint64_t)c->width * (uint64_t)c->height > (1ull << 30)) return fail(c, JPT_E_LIMIT, "jpt_noise_estimate: more than 2^30 pixels (a bin is a uint32)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t n_tiles = (size_t)((c->width + 7) / 8) * (size_t)((c->height + 7) / 8);
+    if (c->d_noise_tiles.n != n_tiles || !c->d_noise_tiles.p) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an estimate in flight may write the old map)
+        c->noise_valid = false;
+        HIP_TRY(c, c->d_noise_tiles.resize(n_tiles));
+    }
+    if (!c->d_noise_bins.p) {
+        // the resolve leaves the working sets cleared: only fresh buffers are cleared here
+        HIP_TRY(c, c->d_noise_bins.resize(kNoiseBinWords));
+        HIP_TRY(c, c->d_noise_result.resize(1));
+        HIP_TRY(c, hipMemsetAsync(c->d_noise_bins.p, 0, kNoiseBinWords * sizeof(uint32_t), c->stream));
+    }
+    // On the context's stream, as jpt_meter: behind the accumulation of every render queued before it.  In a bake render a texel
+    // without a surface is not counted.
+    const PrimaryState& p = c->primary;
+    const float4* normal = p.has_bake() && !p.has_cubes() && p.bake_w == c->width && p.bake_h == c->height ? p.d_bake_nrm.p : nullptr;   // (resolve_primary's bake render)
+    launch_noise_estimate(c->stream, c->noise_params, c->width, c->height, c->d_accum.p, c->d_variance.p, c->frame_count, normal, c->d_noise_bins.p,
+                          c->d_noise_tiles.p, c->d_noise_result.p);
+    HIP_TRY(c, hipGetLastError());
+    c->noise_valid = true;
+    return JPT_OK;
+}
+
+int jpt_read_noise(jpt_ctx* c, jpt_noise_result* out, uint32_t* hist256)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_noise: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
+    if (!c->noise_valid) return fail(c, JPT_E_STATE, "jpt_read_noise: no jpt_noise_estimate at the current size yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc;
+    static_assert(sizeof(jpt_noise_result) == sizeof(NoiseResult), "the record is jpt_noise_result");
+    if ((rc = staged_read(c, c->d_noise_result.p, sizeof(NoiseResult))) != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, sizeof(NoiseResult));
+    if (hist256) {
+        if ((rc = staged_read(c, c->d_noise_bins.p, kMeterBins * sizeof(uint32_t))) != JPT_OK) return rc;
+        std::memcpy(hist256, c->h_read_pinned.p, kMeterBins * sizeof(uint32_t));
+    }
+    return JPT_OK;
+}
+
+int jpt_read_noise_tiles_f32(jpt_ctx* c, float* out)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_noise_tiles_f32: null output");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
+    if (!c->noise_valid) return fail(c, JPT_E_STATE, "jpt_read_noise_tiles_f32: no jpt_noise_estimate at the current size yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = c->d_noise_tiles.n * sizeof(float);
+    const int rc = staged_read(c, c->d_noise_tiles.p, bytes);
+    if (rc != JPT_OK) return rc;
+    std::memcpy(out, c->h_read_pinned.p, bytes);
+    return JPT_OK;
+}
+
+void* jpt_device_noise_tiles(jpt_ctx* c, size_t* bytes_out)
+{
+    if (bytes_out) *bytes_out = 0;
+    if (!c || c->device < 0 || !c->noise_valid || !c->d_noise_tiles.p) return nullptr;
+    if (bytes_out) *bytes_out = c->d_noise_tiles.n * sizeof(float);
+    return c->d_noise_tiles.p;
+}
+
+// the loop a caller would write: render a step, estimate, read 32 bytes, until converged or max_frames
+int jpt_render_converge(jpt_ctx* c, int32_t frames_per_step, int32_t max_frames, uint32_t first_frame_index, int32_t* frames_done, jpt_noise_result* last)
+{
+    if (!c) return JPT_E_INVALID;
+    if (frames_done) *frames_done = 0;
+    if (frames_per_step <= 0 || max_frames <= 0) return fail(c, JPT_E_INVALID, "jpt_render_converge: frames_per_step and max_frames must be > 0");
+    if (!c->variance && c->device >= 0) return fail(c, JPT_E_STATE, "jpt_render_converge: the variance plane is switched off (jpt_set_variance)");
+    jpt_noise_result res;
+    std::memset(&res, 0, sizeof res);
+    res.flags = JPT_NOISE_EMPTY;
+    int32_t done = 0;
+    while (done < max_frames) {
+        const int32_t step = std::min(frames_per_step, max_frames - done);   // (the last step is shortened to land on max_frames)
+        int rc = jpt_render_async(c, step, first_frame_index + (uint32_t)done);
+        if (rc != JPT_OK) return rc;
+        done += step;
+        if (frames_done) *frames_done = done;
+        if ((rc = jpt_noise_estimate(c)) != JPT_OK) return rc;
+        if ((rc = jpt_read_noise(c, &res, nullptr)) != JPT_OK) return rc;   // the one wait of the step, for 32 bytes
+        if (last) *last = res;
+        if (res.flags & JPT_NOISE_CONVERGED) break;
     }
     return JPT_OK;
 }

@@ -10,6 +10,7 @@
 #include "jpt_display.h"
 #include "jpt_lightmap.h"
 #include "jpt_meter.h"
+#include "jpt_variance.h"
 #include "jpt_kernels.h"
 
 namespace jpt {
@@ -433,6 +434,26 @@ struct jpt_ctx {
     DevBuf<uint32_t> d_meter_bins;
     DevBuf<MeterState> d_meter_state;
     bool meter_valid = false;
+
+    // jpt_set_variance: the switch, and the plane of second moments every render adds to (jpt_variance.h; 16 B per pixel of the
+    // context's rows) -- made by the first render with the switch on at a size (ensure_variance, jpt_capi.cpp), given back when the
+    // switch goes off; variance_valid: a render has written it.  jpt_noise_estimate: the context's parameters, and its own buffers --
+    // the tile map (4 B per 8 x 8 tile), the published bins and the working sets (kNoiseBinWords words, 17.3 KB) and the 32-byte
+    // record, made at the first jpt_noise_estimate at a size; noise_valid: they hold the result of one at the current size.
+    bool variance = false;
+    DevBuf<float4> d_variance;
+    bool variance_valid = false;
+    NoiseParams noise_params;
+    DevBuf<float> d_noise_tiles;
+    DevBuf<uint32_t> d_noise_bins;
+    DevBuf<NoiseResult> d_noise_result;
+    bool noise_valid = false;
+    void variance_release()
+    {
+        d_variance.release();
+        d_noise_tiles.release();
+        variance_valid = noise_valid = false;
+    }
 
     // jpt_query_rays / jpt_query_pixels (host forms): one chunk's rays, hits and occlusion bytes on the device, grow-only
     DevBuf<char> d_query;

@@ -369,6 +369,8 @@ struct Wf2Render {
     PrimaryRays primary;                   // which form of the primary launch it takes, and that form's argument
     float4* bake_dir = nullptr;            // jpt_set_bake_directional: the three moment planes a bake render adds to (launch_bake_moments
                                            // behind the accumulation); null: off, and no launch or argument differs
+    float4* variance = nullptr;            // jpt_set_variance: the plane of second moments a render adds to (launch_variance_moments, jpt_variance.h,
+                                           // in front of the accumulation; `cull` then stays off and `sky_tiles` null); null: off, likewise
 };
 // What the moment kernel of one bake render reads and writes (jpt_kernels_bake_dir.hip; the arithmetic: jpt_bake_dir.h): the
 // per-(slot, frame) values wf2_accumulate reads, in its layout, and the three planes.  Every pointer is device memory.

@@ -31,6 +31,7 @@
 #include "jpt_trace_core.h"
 #include "jpt_tie_walk.h"
 #include "jpt_tuning.h"
+#include "jpt_variance.h"
 
 // the primary kernel carries the ray set-up and the sky-cull test besides the walk: 74 VGPRs on its own.  Round 1 (float
 // records) ran it at 6 waves/SIMD because 72 registers spilled; with the quantised records two registers are all the
@@ -1245,6 +1246,21 @@ void launch_wf2_render(hipStream_t stream, const DeviceScene& ds, const FramePar
     wb_all.first_depth = L.first_depth;
     // the accumulation touches the framebuffers: it waits for whatever ordered the context's renders before this one (before_acc)
     if (r.before_acc) (void)hipStreamWaitEvent(stream, r.before_acc, 0);
+    // per-pixel variance (jpt_set_variance): the second moment of the per-frame values the accumulation is about to add, against the
+    // sum as it stands BEFORE this render -- so in front of wf2_accumulate, on its stream (such a render has no sky cull: its window
+    // is the whole share, and a slot is a pixel's place in the share)
+    if (r.variance != nullptr) {
+        VarianceArgs va;
+        va.rad = L.rad;
+        va.fin8 = L.fin8;
+        va.accum = accum;
+        va.plane = r.variance;
+        va.full_tiles_x = dm_all.full_tiles_x;
+        va.full_tiles_y = dm_all.full_tiles_y;
+        va.slots_per_frame = dm_all.slots_per_frame;
+        va.groups = groups;
+        launch_variance_moments(stream, va, fp);
+    }
     const uint32_t ablocks = ((uint32_t)dm_all.full_tiles_x * (uint32_t)dm_all.full_tiles_y * 64u + kBlock - 1) / kBlock;
     if (lg.env_mode != 0)   // (the accumulation is its miss model's too; with a map: no sky cells)
         hipLaunchKernelGGL(wf2_accumulate_env, dim3(ablocks), block, 0, stream, wb_all, dm_acc, fp, cam, r.cull, accum, ldr, depth, nullptr, lg.env);

@@ -274,6 +274,50 @@ def debug_bake_moments(position4, normal4, radiance, first_frame_index, accum_mo
     return out
 
 
+def debug_variance_moments(radiance, accum_mode=capi.ACCUM_HDR_F32, frame_count=1, sum4=None, m2=None):
+    """jpt_debug_variance_moments: the update of jpt_set_variance on the host over radiance float32 [n_frames, height, width, 3] --
+    (sum, m2), float32 [height, width, 4] each: (sum.rgb, 1) as the accumulation holds it and (M2.rgb, 0).  frame_count is that of the
+    first frame: 1 overwrites `sum4` / `m2` whatever they hold, more continues them (copies are returned)."""
+    r = np.ascontiguousarray(radiance, dtype=np.float32)
+    if r.ndim != 4 or r.shape[3] != 3:
+        raise ValueError("radiance is float32 [n_frames, height, width, 3]")
+    shape = (r.shape[1], r.shape[2], 4)
+    s = np.zeros(shape, np.float32) if sum4 is None else np.array(sum4, dtype=np.float32, order="C")
+    m = np.zeros(shape, np.float32) if m2 is None else np.array(m2, dtype=np.float32, order="C")
+    if s.shape != shape or m.shape != shape:
+        raise ValueError("sum4 and m2 are float32 [height, width, 4]")
+    L = capi.lib()
+    rc = L.jpt_debug_variance_moments(_ptr(r), r.shape[0], int(frame_count), int(accum_mode), _ptr(s), _ptr(m), shape[1], shape[0])
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_variance_moments failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return s, m
+
+
+def debug_noise_estimate(device_id, sum4, m2, frame_count, params=None, valid=None, **fields):
+    """jpt_debug_noise_estimate: jpt_noise_estimate's pass over caller-made planes float32 [height, width, 4], on a device or
+    (device_id -1, JPT_DEVICE_HOST_ONLY) on the host --(the capi.NoiseResult as a dict, hist uint32 [256], tiles float32 [ceil(h / 8), ceil(w / 8)]).
+    valid: bool [height, width], False = a texel without a surface, or None."""
+    s = np.ascontiguousarray(sum4, dtype=np.float32)
+    m = np.ascontiguousarray(m2, dtype=np.float32)
+    if s.ndim != 3 or s.shape[2] != 4 or m.shape != s.shape:
+        raise ValueError("sum4 and m2 are float32 [height, width, 4]")
+    if params is None and fields:
+        params = capi.NoiseParams(**fields)
+    h, w = s.shape[:2]
+    v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+    if v is not None and v.shape != (h, w):
+        raise ValueError("valid is [height, width]")
+    hist = np.zeros(256, np.uint32)
+    tiles = np.zeros((-(-h // 8), -(-w // 8)), np.float32)
+    res = capi.NoiseResult()
+    L = capi.lib()
+    rc = L.jpt_debug_noise_estimate(int(device_id), w, h, None if params is None else C.byref(params), _ptr(s), _ptr(m), int(frame_count), _ptr(v),
+                                    _ptr(hist), _ptr(tiles), C.byref(res))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_noise_estimate failed (%d): %s" % (rc, (L.jpt_debug_last_error() or b"?").decode()))
+    return res.as_dict(), hist, tiles
+
+
 def probe_image_size(n_probes, tile_w, tile_h, probes_per_row):
     """(width, height) of the image n_probes tiles make, probes_per_row to a row (jpt_get_probe_image_size's rule)"""
     return int(probes_per_row) * int(tile_w), -(-int(n_probes) // int(probes_per_row)) * int(tile_h)
@@ -1058,6 +1102,65 @@ class Context:
     def set_auto_exposure(self, enable: bool):
         """jpt_set_auto_exposure: display() multiplies its exposure by the metered one, read on the device"""
         self._ck(self._lib.jpt_set_auto_exposure(self.h, 1 if enable else 0), "jpt_set_auto_exposure")
+
+    # ---- per-pixel noise (jpt_set_variance, jpt_noise_estimate, jpt_render_converge)
+    def set_variance(self, enable=True):
+        """jpt_set_variance: renders also keep the second central moment of a pixel's frames, (M2.r, M2.g, M2.b, 0) per pixel.  A
+        change of the value resets the accumulation."""
+        self._ck(self._lib.jpt_set_variance(self.h, 1 if enable else 0), "jpt_set_variance")
+
+    def read_variance(self) -> np.ndarray:
+        """jpt_read_variance_f32: float32 [height, width, 4], the context's rows scattered to image rows as read_accum's.  M2 / (n - 1)
+        is the sample variance of a frame, M2 / (n (n - 1)) the variance of the mean."""
+        out = np.zeros((max(self.height, 1), max(self.width, 1), 4), dtype=np.float32)   # (without a size the call answers before it writes)
+        self._ck(self._lib.jpt_read_variance_f32(self.h, _ptr(out)), "jpt_read_variance_f32")
+        return out
+
+    def device_variance(self):
+        """jpt_device_variance: (device pointer or None, bytes) of the plane"""
+        n = C.c_size_t(0)
+        p = self._lib.jpt_device_variance(self.h, C.byref(n))
+        return p, int(n.value)
+
+    def set_noise_params(self, params: Optional[capi.NoiseParams] = None, **fields):
+        """jpt_set_noise_params: a capi.NoiseParams, or its fields by name (threshold, floor, percentile_permille, allowed_permille;
+        the rest at the defaults); nothing: the defaults"""
+        if params is None and fields:
+            params = capi.NoiseParams(**fields)
+        self._ck(self._lib.jpt_set_noise_params(self.h, None if params is None else C.byref(params)), "jpt_set_noise_params")
+
+    def noise_estimate(self):
+        """jpt_noise_estimate: queue the reduction of the accumulation and the variance plane, as they are after the renders queued so
+        far, to the histogram, the tile map and the result; neither plane is touched"""
+        self._ck(self._lib.jpt_noise_estimate(self.h), "jpt_noise_estimate")
+
+    def read_noise(self, histogram: bool = True):
+        """jpt_read_noise: (the capi.NoiseResult as a dict, the 256 bins as uint32 or None)"""
+        res = capi.NoiseResult()
+        hist = np.zeros(256, dtype=np.uint32) if histogram else None
+        self._ck(self._lib.jpt_read_noise(self.h, C.byref(res), None if hist is None else _ptr(hist)), "jpt_read_noise")
+        return res.as_dict(), hist
+
+    def read_noise_tiles(self) -> np.ndarray:
+        """jpt_read_noise_tiles_f32: float32 [ceil(height / 8), ceil(width / 8)], the largest relative error of each 8 x 8 tile"""
+        out = np.zeros((max(-(-self.height // 8), 1), max(-(-self.width // 8), 1)), dtype=np.float32)
+        self._ck(self._lib.jpt_read_noise_tiles_f32(self.h, _ptr(out)), "jpt_read_noise_tiles_f32")
+        return out
+
+    def device_noise_tiles(self):
+        """jpt_device_noise_tiles: (device pointer or None, bytes) of the tile map"""
+        n = C.c_size_t(0)
+        p = self._lib.jpt_device_noise_tiles(self.h, C.byref(n))
+        return p, int(n.value)
+
+    def render_converge(self, frames_per_step: int, max_frames: int, first_frame_index: int = 0):
+        """jpt_render_converge: render frames_per_step frames at a time until the noise estimate says converged or max_frames are
+        done -- (frames rendered, the last capi.NoiseResult as a dict)"""
+        done = C.c_int32(0)
+        res = capi.NoiseResult()
+        self._ck(self._lib.jpt_render_converge(self.h, int(frames_per_step), int(max_frames), int(first_frame_index), C.byref(done), C.byref(res)),
+                 "jpt_render_converge")
+        return int(done.value), res.as_dict()
 
     def read_guides(self):
         """jpt_read_guides_f32: (position_t, normal, albedo), float32 [height, width, 4] each"""

@@ -1138,6 +1138,93 @@ int jpt_meter_reset(jpt_ctx *ctx);                                        /* the
 int jpt_read_meter(jpt_ctx *ctx, jpt_meter_result *out, uint32_t *hist256 /* may be NULL */);
 int jpt_set_auto_exposure(jpt_ctx *ctx, int32_t enable);                  /* default 0 */
 
+/* ---- per-pixel noise: is the image finished? (no reference counterpart; the noise threshold of a production progressive renderer,
+ * and the stop criterion of a LightmapGI-style bake: INTEGRATION.md) -------------------------------------------------------------------
+ * With jpt_set_variance on, every render on the default kernel keeps one more float4 per pixel of the context's rows beside the
+ * accumulation: (M2.r, M2.g, M2.b, 0), M2 = sum over the frames of (cur_f - mean)^2 per channel, cur_f the frame's value exactly as the
+ * accumulation adds it (in JPT_ACCUM_REF_LDR8 the rgba8 value read back).  jpt_noise_estimate reduces the two planes, on the device,
+ * to a histogram, a map of 8 x 8 tiles and one 32-byte answer; jpt_render_converge is the loop a caller would write around them.  The
+ * host never reads a pixel.  The arithmetic is pinned in DESIGN.md section 2 (gdpathtracing_amd/csrc/jpt_variance.h;
+ * tests/np_variance.py restates it bit for bit); every operation is one binary32 operation in the order written:
+ *   per frame   k = the frame's count since the reset (1: the first); sum = the accumulation's own sum with this frame added
+ *               (k == 1: cur; else cur + sum).  k == 1: m2 = +0, whatever the plane held.  k >= 2: kf = (float)k;
+ *               d = kf * cur - sum;  w = 1.0f / (kf * (kf - 1.0f));  m2 = m2 + (d * d) * w.
+ *               In real arithmetic this is Welford's update, (x - mean_old)(x - mean_new) = (k x - sum_k)^2 / (k (k - 1)); no term is
+ *               negative, so m2 never is.  A pixel whose frames are all equal need not give exactly 0: k * x and x + x + ... round
+ *               differently, and the result is of order x^2 * 2^-48.  The divisor is the caller's: M2 / (n - 1) is the sample variance
+ *               of a frame, M2 / (n (n - 1)) the variance of the mean.
+ *   per pixel   nf = (float)frame_count;  q = nf * (nf - 1.0f);  mean.c = sum.c / nf;  v.c = m2.c / q;
+ *               lm = 0.2126f * mean.r + 0.7152f * mean.g + 0.0722f * mean.b;  lv = the same of v;  e = sqrt(lv) / (lm + floor): the
+ *               relative standard error of the mean (lv is a noise measure, not the variance of the luminance: no covariance is kept).
+ *               Counted: the six inputs finite, lm >= 0 and, in a bake render, a valid texel.  A counted pixel's bin is
+ *               clamp((bits(e) >> 20) - 856, 0, 255): eight bins per octave from 2^-20, e = 0 in bin 0; it is "above" when
+ *               e > threshold.  A pixel that is not counted contributes to nothing.
+ *   outputs     hist[256], uint32, of the counted pixels; tiles[ceil(W / 8) * ceil(H / 8)], float, row-major: the largest e > 0 of
+ *               the tile's counted pixels, or 0; the result: `error` = the upper edge, the binary32 with the bits (b + 1 + 856) << 20,
+ *               of the first bin b at which the cumulative count reaches ceil(counted * percentile_permille / 1000); `max_error` = the
+ *               maximum over the tile map; `tiles_above` = the tiles whose value is > threshold.  JPT_NOISE_EMPTY: frame_count < 2 or
+ *               counted == 0; then error = max_error = 0 and the result is not converged.  JPT_NOISE_CONVERGED: not empty and
+ *               above * 1000 <= counted * allowed_permille.  Sums are integers and maxima are of non-negative floats: nothing depends
+ *               on the order the pixels arrive in.
+ *
+ * jpt_set_variance             a switch of the context, as jpt_set_bake_directional: it survives commits and uploads, jpt_scene_share
+ *                              does not copy it, and a CHANGE of the value resets the accumulation as jpt_accum_reset does.  With the
+ *                              switch on a render launches one kernel of its own in front of its accumulation (no path kernel
+ *                              differs) and a pinhole render takes no sky cull, as a lens render: every pixel's frames are then kept
+ *                              until the accumulation has read them.  The accumulation, display and depth images stay bit for bit
+ *                              what they are with the switch off; with the switch off no launch, argument, allocation or output of
+ *                              any render differs.  Works with every kind of primary ray, lighting family, both accumulation modes,
+ *                              queued renders and a partition (each rank keeps its own rows).
+ * jpt_read_variance_f32        W * H * 4 floats, scattered to image rows as jpt_read_accum_f32 does.  Waits for the renders queued so far.
+ * jpt_device_variance          the plane's device pointer and size (the context's own rows, local order); NULL and 0 when there is none.
+ * jpt_set_noise_params         NULL: the defaults.  JPT_E_INVALID outside the ranges below.
+ * jpt_noise_estimate           enqueues on the context's stream, ordered as jpt_meter is; it READS the accumulation, the plane, the
+ *                              frame count and (bake renders) the normal image and writes only its own buffers.
+ * jpt_read_noise               waits, and reads the 32-byte result and, optionally, the 1 KB histogram.
+ * jpt_read_noise_tiles_f32     the tile map; jpt_device_noise_tiles: its device pointer, for a later pass on the device.
+ * jpt_render_converge          repeats jpt_render_async(frames_per_step) at consecutive frame indices from first_frame_index,
+ *                              jpt_noise_estimate and jpt_read_noise until the result is converged or max_frames frames are done (the
+ *                              last step is shortened to land on it): the host waits once per step, for 32 bytes.  *frames_done: the
+ *                              frames rendered by the call; *last: the last result.  Either may be NULL.  The accumulation is not
+ *                              reset: the frames add to those already there.
+ * Memory (jpt_get_workspace_bytes is about the workspace and does not count these): 16 B per pixel of the context's rows for the
+ * plane, made by the first render with the switch on, freed when it goes off; 4 B per 8 x 8 tile for the tile map; 17.3 KB of bins
+ * (256 published, 16 working sets) and the 32-byte record, made by the first jpt_noise_estimate.
+ * JPT_E_STATE, with a message naming jpt_set_variance: a render with the switch on under JPT_KERNEL_REFERENCE_LAYOUT (it adds frame
+ * by frame and keeps no per-frame values), a denoising mode other than JPT_DENOISE_PROGRESSIVE, or jpt_set_debug_steps.
+ * jpt_read_variance_f32 / jpt_device_variance with the switch off or before the first render with it on: JPT_E_STATE / NULL.
+ * jpt_noise_estimate: jpt_meter's refusals (the mode, DEBUG_STEPS, a screen partition, jpt_set_params not called, no frame), the switch
+ * off, no render with it on at the current size.  jpt_read_noise / jpt_read_noise_tiles_f32 before a jpt_noise_estimate at the current
+ * size: JPT_E_STATE.  jpt_render_converge: an argument <= 0 is JPT_E_INVALID; otherwise the refusals of the calls it makes.
+ * Host-only contexts: JPT_E_DEVICE.  There is no jpt_multi_* form.
+ * Not covered: adaptive sampling (skipping converged tiles would edit the primary launch), variance-guided weights in jpt_denoise,
+ * jpt_multi and an estimate under a partition, a jpt_encode source for the plane, the reference-layout kernel, per-channel covariance. */
+enum { JPT_NOISE_EMPTY = 1, JPT_NOISE_CONVERGED = 2 };       /* jpt_noise_result.flags */
+typedef struct jpt_noise_params {
+    float   threshold;            /* default 0.05: a pixel, or a tile, is "above" when its e is greater */
+    float   floor;                /* finite, > 0, default 0.01: added to the mean luminance, so that dark pixels do not rule */
+    int32_t percentile_permille;  /* 1..1000, default 950: `error` is this percentile of e over the counted pixels */
+    int32_t allowed_permille;     /* 0..1000, default 0: the share of counted pixels that may stay above the threshold */
+} jpt_noise_params;
+typedef struct jpt_noise_result {
+    float error;             /* the percentile of e, as the upper edge of its bin (0 when EMPTY) */
+    float max_error;         /* the largest e of any counted pixel (0 when EMPTY) */
+    uint32_t flags;
+    uint32_t tiles_above;    /* tiles whose largest e is > threshold */
+    uint64_t counted;        /* pixels counted */
+    uint64_t above;          /* ... of which e > threshold */
+} jpt_noise_result;          /* 32 B */
+int   jpt_set_variance(jpt_ctx *ctx, int32_t enable);                        /* default 0 */
+int   jpt_read_variance_f32(jpt_ctx *ctx, float *out);                       /* W*H*4 floats: (M2.r, M2.g, M2.b, 0) */
+void *jpt_device_variance(jpt_ctx *ctx, size_t *bytes_out);
+int   jpt_set_noise_params(jpt_ctx *ctx, const jpt_noise_params *params);    /* NULL: the defaults */
+int   jpt_noise_estimate(jpt_ctx *ctx);                                      /* enqueue; ordered as jpt_meter is */
+int   jpt_read_noise(jpt_ctx *ctx, jpt_noise_result *out, uint32_t *hist256 /* may be NULL */);
+int   jpt_read_noise_tiles_f32(jpt_ctx *ctx, float *out);                    /* ceil(W/8) * ceil(H/8) floats */
+void *jpt_device_noise_tiles(jpt_ctx *ctx, size_t *bytes_out);
+int   jpt_render_converge(jpt_ctx *ctx, int32_t frames_per_step, int32_t max_frames, uint32_t first_frame_index, int32_t *frames_done,
+                          jpt_noise_result *last);
+
 /* ---- ray queries: what does this ray hit? (no reference counterpart) ---------------------------------------------------------------
  * Caller-supplied rays against the scene the device holds, as an explicit call: nothing runs unless the host asks, queries change no
  * statistic of jpt_stats and no buffer a render or a read-back reads.  For picking, autofocus, line of sight and
@@ -1460,6 +1547,20 @@ int jpt_debug_display_srgb_table(float *out255);
  * the kernels jpt_meter launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
 int jpt_debug_meter(int device_id, int32_t width, int32_t height, const jpt_meter_params *params, const float *mean4,
                     float prev_exposure, uint32_t *hist256_out, jpt_meter_result *result_out);
+/* The update of jpt_set_variance on the host: the function the moment kernel inlines (jpt_variance.h), compiled for the host, in a
+ * plain loop over the pixels of a width x height image and the n_frames frames of radiance3 [3 ((f * height + y) * width + x) ..].
+ * accum_mode: JPT_ACCUM_HDR_F32 takes a frame's value as it is, JPT_ACCUM_REF_LDR8 through the rgba8 store and load.  frame_count >= 1
+ * is that of the first frame: 1 overwrites sum_inout and m2_inout (whatever they held), more continues them.  Both are width *
+ * height * 4 floats: (sum.r, sum.g, sum.b, 1) as the accumulation holds it, and (M2.r, M2.g, M2.b, 0). */
+int jpt_debug_variance_moments(const float *radiance3, int32_t n_frames, uint32_t frame_count, int32_t accum_mode, float *sum_inout,
+                               float *m2_inout, int32_t width, int32_t height);
+/* jpt_noise_estimate's pass alone, on caller-made planes of width x height pixels, 4 floats per pixel: sum4 the accumulation, m2_4 the
+ * plane, frame_count >= 1 the frames in them.  valid_or_null: one byte per pixel, 0 = a texel without a surface (a bake render), or
+ * NULL for none.  hist256_out and tiles_out (ceil(width / 8) * ceil(height / 8) floats) may be NULL.  device >= 0: the kernels
+ * jpt_noise_estimate launches, on that device; JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
+int jpt_debug_noise_estimate(int device_id, int32_t width, int32_t height, const jpt_noise_params *params, const float *sum4,
+                             const float *m2_4, uint32_t frame_count, const uint8_t *valid_or_null, uint32_t *hist256_out,
+                             float *tiles_out, jpt_noise_result *result_out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

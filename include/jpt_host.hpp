@@ -1033,6 +1033,28 @@ class PathTracingCamera {
         check(ctx, jpt_read_meter(ctx, &r, hist256), "jpt_read_meter");
         return r;
     }
+    // Per-pixel noise (jpt_set_variance, jpt_noise_estimate): the second moment of a pixel's frames kept beside the accumulation, its
+    // reduction on the device to a 32-byte answer, and render_converge, which renders frames_per_step frames at a time until that
+    // answer says converged or max_frames are done and returns the frames it rendered (stopping a bake or a still).
+    void set_variance(bool enable) { check(ctx, jpt_set_variance(ctx, enable ? 1 : 0), "jpt_set_variance"); }
+    void read_variance(float* out) { check(ctx, jpt_read_variance_f32(ctx, out), "jpt_read_variance_f32"); }
+    void* device_variance(size_t* bytes = nullptr) { return jpt_device_variance(ctx, bytes); }
+    void set_noise_params(const jpt_noise_params* params) { check(ctx, jpt_set_noise_params(ctx, params), "jpt_set_noise_params"); }
+    void noise_estimate() { check(ctx, jpt_noise_estimate(ctx), "jpt_noise_estimate"); }
+    jpt_noise_result read_noise(uint32_t* hist256 = nullptr)
+    {
+        jpt_noise_result r;
+        check(ctx, jpt_read_noise(ctx, &r, hist256), "jpt_read_noise");
+        return r;
+    }
+    void read_noise_tiles(float* out) { check(ctx, jpt_read_noise_tiles_f32(ctx, out), "jpt_read_noise_tiles_f32"); }
+    void* device_noise_tiles(size_t* bytes = nullptr) { return jpt_device_noise_tiles(ctx, bytes); }
+    int32_t render_converge(int32_t frames_per_step, int32_t max_frames, uint32_t first_frame_index, jpt_noise_result* last = nullptr)
+    {
+        int32_t done = 0;
+        check(ctx, jpt_render_converge(ctx, frames_per_step, max_frames, first_frame_index, &done, last), "jpt_render_converge");
+        return done;
+    }
     void read_guides(float* position_t, float* normal, float* albedo) { check(ctx, jpt_read_guides_f32(ctx, position_t, normal, albedo), "jpt_read_guides_f32"); }
     // Ray queries against the scene the device holds (picking, line of sight, autofocus: INTEGRATION.md).  query_rays: n closest hits
     // (occluded may be null); occluded_rays: JPT_QUERY_ANY, one byte per ray; query_pixels: the un-jittered pinhole ray through each
