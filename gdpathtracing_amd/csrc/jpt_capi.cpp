@@ -58,7 +58,7 @@ int alloc_framebuffers(jpt_ctx* c)
     }
     c->frame_count = 0;
     c->assembled = c->assembled_ldr = false;
-    c->variance_valid = c->noise_valid = false;   // (jpt_set_variance's plane is of the frames before; the next render overwrites it)
+    c->post.framebuffers_remade(false);
     return JPT_OK;
 }
 
@@ -933,61 +933,6 @@ int read_back_stats(jpt_ctx* c, const FrameParams& fp, bool counted, bool wavefr
     return JPT_OK;
 }
 
-// jpt_set_bake_directional: what a render with the switch on and bake images present refuses -- the moment kernel reads the per-frame
-// values the wavefront route keeps, of radiance, summed progressively.  Without bake images the switch has no effect.
-int check_bake_directional(jpt_ctx* c)
-{
-    if (!c->bake_dir || !c->primary.has_bake()) return JPT_OK;
-    if (c->kernel_variant != JPT_KERNEL_WAVEFRONT)
-        return fail(c, JPT_E_STATE, "jpt_set_bake_directional: the reference-layout kernel adds frame by frame and keeps no per-frame values: set "
-                                    "JPT_KERNEL_WAVEFRONT (jpt_set_kernel) or switch the directional planes off");
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_set_bake_directional: the moments follow the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE "
-                                    "(temporal reprojection and JPT_DENOISE_NONE keep no sum)");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_set_bake_directional: a DEBUG_STEPS render holds step counts, not radiance (jpt_set_debug_steps)");
-    return JPT_OK;
-}
-
-// the three moment planes at the size of the context's rows, made (and zeroed, so that a sum continued without a reset starts from
-// +0) when they are missing or of another size
-int ensure_bake_dir(jpt_ctx* c)
-{
-    const size_t need = 3u * (size_t)c->width * (size_t)c->local_rows;
-    if (c->d_bake_dir.p && c->d_bake_dir.n == need) return JPT_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (renders in flight may write the old planes: every one ends with work on the stream)
-    c->bake_dir_valid = false;
-    HIP_TRY(c, c->d_bake_dir.resize(need));
-    if (need) HIP_TRY(c, hipMemsetAsync(c->d_bake_dir.p, 0, need * sizeof(float4), c->stream));
-    return JPT_OK;
-}
-
-// jpt_set_variance: what a render with the switch on refuses -- the moment kernel reads the per-frame values the wavefront route
-// keeps, of radiance, summed progressively
-int check_variance(jpt_ctx* c)
-{
-    if (!c->variance) return JPT_OK;
-    if (c->kernel_variant != JPT_KERNEL_WAVEFRONT)
-        return fail(c, JPT_E_STATE, "jpt_set_variance: the reference-layout kernel adds frame by frame and keeps no per-frame values: set "
-                                    "JPT_KERNEL_WAVEFRONT (jpt_set_kernel) or switch the variance plane off");
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_set_variance: the moment follows the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE "
-                                    "(temporal reprojection and JPT_DENOISE_NONE keep no sum)");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_set_variance: a DEBUG_STEPS render holds step counts, not radiance (jpt_set_debug_steps)");
-    return JPT_OK;
-}
-
-// the plane at the size of the context's rows, made (and zeroed) when it is missing or of another size
-int ensure_variance(jpt_ctx* c)
-{
-    const size_t need = (size_t)c->width * (size_t)c->local_rows;
-    if (c->d_variance.p && c->d_variance.n == need) return JPT_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (renders in flight may write the old plane: every one ends with work on the stream)
-    c->variance_valid = c->noise_valid = false;
-    HIP_TRY(c, c->d_variance.resize(need));
-    if (need) HIP_TRY(c, hipMemsetAsync(c->d_variance.p, 0, need * sizeof(float4), c->stream));
-    return JPT_OK;
-}
-
 // validate -> prepare -> plan -> launch -> read back
 int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
 {
@@ -1003,14 +948,14 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     if ((rc = check_bake_directional(c)) != JPT_OK) return rc;
     if ((rc = resolve_primary(c, r.primary)) != JPT_OK) return rc;
     if ((rc = resolve_lighting(c, r.lighting)) != JPT_OK) return rc;
-    if (c->bake_dir && r.primary.kind == PrimaryRays::kBake && c->local_rows > 0 && n_frames > 0) {
+    if (c->post.bake_dir && r.primary.kind == PrimaryRays::kBake && c->local_rows > 0 && n_frames > 0) {
         if ((rc = ensure_bake_dir(c)) != JPT_OK) return rc;
-        r.bake_dir = c->d_bake_dir.p;
+        r.bake_dir = c->post.d_bake_dir.p;
     }
     if ((rc = check_variance(c)) != JPT_OK) return rc;
-    if (c->variance && c->local_rows > 0 && c->width > 0 && n_frames > 0) {
+    if (c->post.variance && c->local_rows > 0 && c->width > 0 && n_frames > 0) {
         if ((rc = ensure_variance(c)) != JPT_OK) return rc;
-        r.variance = c->d_variance.p;
+        r.variance = c->post.d_variance.p;
     }
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
@@ -1019,8 +964,8 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
         const LaunchPlan p = plan_launch(c, fp, r, counted, blocking, kPlanDevice);
         rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->d_depth.p : nullptr);
         if (rc != JPT_OK) return rc;
-        if (r.bake_dir) c->bake_dir_valid = true;
-        if (r.variance) c->variance_valid = true;
+        if (r.bake_dir) c->post.bake_dir_valid = true;
+        if (r.variance) c->post.variance_valid = true;
         pipelined = p.route == LaunchPlan::kSlot;
         if (c->denoise == JPT_DENOISE_TEMPORAL) {
             // TemporalReprojection::render's dispatch (temporal_reprojection.cpp:71): screen + depth of this frame in,
@@ -1101,6 +1046,24 @@ int jpt::staged_read(jpt_ctx* c, const void* src, size_t bytes)
         HIP_TRY(c, hipMemcpyAsync(c->h_read_pinned.p, src, bytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
+    return JPT_OK;
+}
+
+int jpt::read_out(jpt_ctx* c, const void* src, size_t bytes, void* out)
+{
+    const int rc = staged_read(c, src, bytes);
+    if (rc == JPT_OK && bytes) std::memcpy(out, c->h_read_pinned.p, bytes);
+    return rc;
+}
+
+int jpt::read_rows_out(jpt_ctx* c, const void* src, size_t elem, int comps, bool whole, void* out)
+{
+    const size_t px_bytes = elem * (size_t)comps, full = (size_t)c->width * c->height * px_bytes;
+    if (whole || c->world == 1) return read_out(c, src, whole ? full : (size_t)c->local_rows * c->width * px_bytes, out);
+    const int rc = staged_read(c, src, (size_t)c->local_rows * c->width * px_bytes);
+    if (rc != JPT_OK) return rc;
+    std::memset(out, 0, full);
+    scatter_rows(c->h_read_pinned.as<const char>(), static_cast<char*>(out), c->width, c->height, c->rank, c->world, (int)px_bytes);
     return JPT_OK;
 }
 
@@ -2139,31 +2102,12 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
     if (sampler_mode < JPT_SAMPLER_NEAREST_CLAMP || sampler_mode > JPT_SAMPLER_LINEAR_REPEAT) return fail(c, JPT_E_INVALID, "unknown sampler_mode");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no framebuffers");
     HIP_TRY(c, hipSetDevice(c->device));
-    if ((width != c->width || height != c->height) && c->d_dn_ping.p) {
-        // jpt_denoise's images are of the old size: given back once the work that uses them has run
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->d_dn_pos.release();
-        c->d_dn_nrm.release();
-        c->d_dn_alb.release();
-        c->d_dn_ping.release();
-        c->d_dn_pong.release();
-        c->d_dn_ldr.release();
+    if (width != c->width || height != c->height) {
+        // the post stages' images are of the old size: given back once the work that uses them has run
+        if (c->post.sized_buffers()) HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->post.framebuffers_remade(true);
+        c->primary.sh_valid = c->primary.refl_valid = false;   // (jpt_probe_project's coefficients and jpt_reflection_prefilter's chain likewise)
     }
-    if (width != c->width || height != c->height) c->primary.sh_valid = false;   // (jpt_probe_project's coefficients are of the old size)
-    if (width != c->width || height != c->height) c->primary.refl_valid = false;   // (jpt_reflection_prefilter's chain likewise)
-    if ((width != c->width || height != c->height) && (c->d_lm_ping.p || c->d_lmd_out.p)) {
-        // jpt_bake_finish's images likewise, and jpt_bake_finish_directional's
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->lightmap_release();
-    }
-    if ((width != c->width || height != c->height) && (c->d_disp_f32.p || c->d_disp_pyramid.p)) {
-        // jpt_display's buffers likewise
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->d_disp_f32.release();
-        c->d_disp_ldr.release();
-        c->d_disp_pyramid.release();
-    }
-    if (width != c->width || height != c->height) c->dn_valid = c->disp_valid = c->meter_valid = false;
     c->width = width;
     c->height = height;
     c->max_bounces = max_bounces;
@@ -2299,20 +2243,11 @@ static int read_common(jpt_ctx* c, void* out)
 
 int jpt_read_ldr_rgba8(jpt_ctx* c, uint8_t* out)
 {
-    int rc = read_common(c, out);
+    const int rc = read_common(c, out);
     if (rc) return rc;
     // What the reference does every frame (get_image_uniform_buffer, path_tracing_camera.cpp:228-229): through staged_read.
-    const size_t full = (size_t)c->width * c->height;
     const bool whole = c->assembled || c->assembled_ldr;
-    const size_t px = whole ? full : (size_t)c->local_rows * c->width;
-    rc = staged_read(c, whole ? c->d_full_ldr.p : c->d_ldr.p, px * 4);
-    if (rc) return rc;
-    if (whole || c->world == 1) std::memcpy(out, c->h_read_pinned.p, px * 4);
-    else {
-        std::memset(out, 0, full * 4);
-        scatter_rows(c->h_read_pinned.as<const uint32_t>(), reinterpret_cast<uint32_t*>(out), c->width, c->height, c->rank, c->world, 1);
-    }
-    return JPT_OK;
+    return read_rows_out(c, whole ? c->d_full_ldr.p : c->d_ldr.p, sizeof(uint32_t), 1, whole, out);
 }
 
 int jpt_readback_ldr_begin(jpt_ctx* c)
@@ -2356,699 +2291,14 @@ int jpt_readback_ldr_end(jpt_ctx* c, uint8_t* out)
 
 int jpt_read_accum_f32(jpt_ctx* c, float* out)
 {
-    int rc = read_common(c, out);
+    const int rc = read_common(c, out);
     if (rc) return rc;
-    const size_t full = (size_t)c->width * c->height;
     if (c->denoise == JPT_DENOISE_TEMPORAL) {
         // the rgba32f image of this mode is the history image the last pass wrote
         if (!c->hist_written) return fail(c, JPT_E_STATE, "no temporal pass has run since the last reset");
-        rc = staged_read(c, c->hist_written, full * sizeof(float4));
-        if (rc) return rc;
-        std::memcpy(out, c->h_read_pinned.p, full * sizeof(float4));
-        return JPT_OK;
+        return read_out(c, c->hist_written, (size_t)c->width * c->height * sizeof(float4), out);
     }
-    const size_t n = c->assembled ? full * 4 : (size_t)c->local_rows * c->width * 4;   // floats
-    rc = staged_read(c, c->assembled ? (const void*)c->d_full_accum.p : (const void*)c->d_accum.p, n * sizeof(float));
-    if (rc) return rc;
-    if (c->assembled || c->world == 1) std::memcpy(out, c->h_read_pinned.p, n * sizeof(float));
-    else {
-        std::memset(out, 0, full * 16);
-        scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 4);
-    }
-    return JPT_OK;
-}
-
-extern "C++" {
-namespace jpt {
-int check_denoise_params(const AtrousParams& p, std::string& why)
-{
-    if (p.passes < 1 || p.passes > kAtrousMaxPasses) why = "jpt_denoise_params: passes must be in [1, 6]";
-    else if (p.normal_power_log2 < 0 || p.normal_power_log2 > 8) why = "jpt_denoise_params: normal_power_log2 must be in [0, 8]";
-    else if (!std::isfinite(p.sigma_plane) || !(p.sigma_plane > 0.0f)) why = "jpt_denoise_params: sigma_plane must be finite and > 0";
-    else if (!std::isfinite(p.sigma_color) || !(p.sigma_color > 0.0f)) why = "jpt_denoise_params: sigma_color must be finite and > 0";
-    else return JPT_OK;
-    return JPT_E_INVALID;
-}
-}  // namespace jpt
-}
-
-int jpt_set_denoise_params(jpt_ctx* c, const jpt_denoise_params* params)
-{
-    if (!c) return JPT_E_INVALID;
-    AtrousParams p;
-    if (params) {
-        p.passes = params->passes;
-        p.normal_power_log2 = params->normal_power_log2;
-        p.sigma_plane = params->sigma_plane;
-        p.sigma_color = params->sigma_color;
-    }
-    std::string why;
-    const int rc = check_denoise_params(p, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
-    c->dn_params = p;
-    return JPT_OK;
-}
-
-int jpt_denoise(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_denoise filters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_denoise: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_denoise needs the whole image on one context (world == 1)");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
-    if (!c->scene_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
-    if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_denoise: jpt_set_params / jpt_set_camera not called");
-    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_denoise: no frame accumulated since the last reset");
-    CamModelDev cm;   // (the guides are the first hits of the view the renders took: jpt_set_camera_model)
-    const int rc_cm = view_now(c, "jpt_denoise", "the guides", cm);
-    if (rc_cm != JPT_OK) return rc_cm;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->width * c->height;
-    if (c->d_dn_ping.n != npx || !c->d_dn_ping.p) {
-        HIP_TRY(c, c->d_dn_pos.resize(npx));
-        HIP_TRY(c, c->d_dn_nrm.resize(npx));
-        HIP_TRY(c, c->d_dn_alb.resize(npx));
-        HIP_TRY(c, c->d_dn_ping.resize(npx));
-        HIP_TRY(c, c->d_dn_pong.resize(npx));
-        HIP_TRY(c, c->d_dn_ldr.resize(npx));
-    }
-    // On the context's stream: it is ordered behind the accumulation of every render queued so far (launch_render) and behind the
-    // device refits (queue_instance_refit), and the accumulation of every later render waits for what it holds.
-    hipStream_t s = c->stream;
-    if (npx) {
-        launch_guides(s, c->ds, c->camera, cm, c->width, c->height, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p);
-        launch_atrous(s, c->dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p,
-                      c->d_dn_ping.p, c->d_dn_pong.p, c->d_dn_ldr.p);
-        HIP_TRY(c, hipGetLastError());
-    }
-    c->dn_valid = true;
-    return JPT_OK;
-}
-
-static int read_denoise_common(jpt_ctx* c, bool have_out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!have_out) return fail(c, JPT_E_INVALID, "null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
-    if (!c->dn_valid) return fail(c, JPT_E_STATE, "no jpt_denoise at the current resolution yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return JPT_OK;
-}
-
-int jpt_read_denoised_f32(jpt_ctx* c, float* out)
-{
-    int rc = read_denoise_common(c, out != nullptr);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
-    if ((rc = staged_read(c, c->d_dn_ping.p, bytes)) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-int jpt_read_denoised_rgba8(jpt_ctx* c, uint8_t* out)
-{
-    int rc = read_denoise_common(c, out != nullptr);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->width * c->height * sizeof(uint32_t);
-    if ((rc = staged_read(c, c->d_dn_ldr.p, bytes)) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-int jpt_read_guides_f32(jpt_ctx* c, float* position_t, float* normal, float* albedo)
-{
-    int rc = read_denoise_common(c, true);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
-    float* outs[3] = {position_t, normal, albedo};
-    const float4* src[3] = {c->d_dn_pos.p, c->d_dn_nrm.p, c->d_dn_alb.p};
-    for (int k = 0; k < 3; k++) {
-        if (!outs[k]) continue;
-        if ((rc = staged_read(c, src[k], bytes)) != JPT_OK) return rc;
-        std::memcpy(outs[k], c->h_read_pinned.p, bytes);
-    }
-    return JPT_OK;
-}
-
-// ---- jpt_bake_finish: the chart-aware filter and the dilation of a baked lightmap (jpt_lightmap.h) -----------------------------
-
-extern "C++" {
-namespace jpt {
-int check_bake_finish_params(const char* call, const LightmapParams& p, std::string& why)
-{
-    const std::string who = std::string(call) + ": ";
-    if (p.passes < 0 || p.passes > kLightmapMaxPasses) why = who + "passes must be in [0, 6]";
-    else if (p.normal_power_log2 < 0 || p.normal_power_log2 > 8) why = who + "normal_power_log2 must be in [0, 8]";
-    else if (p.dilate < 0 || p.dilate > kLightmapMaxDilate) why = who + "dilate must be in [0, 64]";
-    else if (!std::isfinite(p.sigma_distance) || !(p.sigma_distance > 0.0f)) why = who + "sigma_distance must be finite and > 0";
-    else if (!std::isfinite(p.sigma_plane) || !(p.sigma_plane > 0.0f)) why = who + "sigma_plane must be finite and > 0";
-    else if (!std::isfinite(p.sigma_color) || !(p.sigma_color > 0.0f)) why = who + "sigma_color must be finite and > 0";
-    else return JPT_OK;
-    return JPT_E_INVALID;
-}
-}  // namespace jpt
-}
-
-int jpt_set_bake_finish_params(jpt_ctx* c, const jpt_bake_finish_params* params)
-{
-    if (!c) return JPT_E_INVALID;
-    LightmapParams p;
-    if (params) {
-        p.passes = params->passes;
-        p.normal_power_log2 = params->normal_power_log2;
-        p.dilate = params->dilate;
-        p.sigma_distance = params->sigma_distance;
-        p.sigma_plane = params->sigma_plane;
-        p.sigma_color = params->sigma_color;
-    }
-    std::string why;
-    const int rc = check_bake_finish_params("jpt_set_bake_finish_params", p, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_finish_params: host-only context: jpt_bake_finish runs on the device");
-    c->lm_params = p;
-    return JPT_OK;
-}
-
-int jpt_bake_finish(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_bake_finish filters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_bake_finish: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_bake_finish needs the whole image on one context (world == 1)");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_finish: host-only context: it runs on the device");
-    const PrimaryState& p = c->primary;
-    if (!p.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_finish: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
-    if (p.has_probes()) return fail(c, JPT_E_STATE, "jpt_bake_finish: the lightmap is made of texel images, and the context holds probes (jpt_set_probes)");
-    if (p.has_cubes())
-        return fail(c, JPT_E_STATE, "jpt_bake_finish: the lightmap is made of texel images, and the context holds reflection probes (jpt_set_reflection_probes)");
-    if (!c->params_set || p.bake_w != c->width || p.bake_h != c->height)
-        return fail(c, JPT_E_STATE, "jpt_bake_finish: the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) +
-                                        " texels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
-    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_bake_finish: no frame accumulated since the last reset");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->width * c->height;   // (>= 1: the images have at least one texel)
-    if (c->d_lm_ping.n != npx || !c->d_lm_ping.p) {
-        c->lm_result = nullptr;
-        HIP_TRY(c, c->d_lm_xg.resize(npx));
-        HIP_TRY(c, c->d_lm_ng.resize(npx));
-        HIP_TRY(c, c->d_lm_ping.resize(npx));
-        HIP_TRY(c, c->d_lm_pong.resize(npx));
-    }
-    // On the context's stream, as jpt_denoise: behind the accumulation of every render queued so far, and the accumulation of every
-    // later render waits for what it holds.
-    c->lm_result = launch_lightmap_finish(c->stream, c->lm_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, p.d_bake_pos.p, p.d_bake_nrm.p,
-                                          c->d_lm_xg.p, c->d_lm_ng.p, c->d_lm_ping.p, c->d_lm_pong.p);
-    HIP_TRY(c, hipGetLastError());
-    return JPT_OK;
-}
-
-int jpt_read_lightmap_f32(jpt_ctx* c, float* out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_lightmap_f32: null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_lightmap_f32: host-only context: jpt_bake_finish runs on the device");
-    if (!c->lm_result) return fail(c, JPT_E_STATE, "jpt_read_lightmap_f32: no jpt_bake_finish at the current size and bake images yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
-    const int rc = staged_read(c, c->lm_result, bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-// ---- directional lightmaps: the first moments of the incoming light per texel (jpt_bake_dir.h, jpt_kernels_bake_dir.hip) ----------
-
-int jpt_set_bake_directional(jpt_ctx* c, int32_t enable)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_bake_directional: host-only context: the moments are made on the device");
-    const bool on = enable != 0;
-    if (on == c->bake_dir) return JPT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->d_bake_dir.p || c->d_lmd_out.p) {
-        // the renders queued so far add to the planes: they finish first, then the planes and what was finished from them go
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->bake_dir_release();
-        c->d_lmd_xg.release();
-        c->d_lmd_ng.release();
-        c->d_lmd_ping.release();
-        c->d_lmd_pong.release();
-        c->d_lmd_out.release();
-    }
-    c->lmd_valid = false;
-    c->bake_dir_valid = false;
-    c->bake_dir = on;
-    return jpt_accum_reset(c);   // the sum and the moments are of the same frames: both start over
-}
-
-// the planes of a read: JPT_OK, or the refusal
-static int bake_directional_ready(jpt_ctx* c, const char* call)
-{
-    const std::string who = std::string(call) + ": ";
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, who + "host-only context: the moments are made on the device");
-    if (!c->bake_dir) return fail(c, JPT_E_STATE, who + "the directional planes are switched off (jpt_set_bake_directional)");
-    if (!c->primary.has_bake()) return fail(c, JPT_E_STATE, who + "no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
-    if (!c->d_bake_dir.p || !c->bake_dir_valid || c->d_bake_dir.n != 3u * (size_t)c->width * (size_t)c->local_rows)
-        return fail(c, JPT_E_STATE, who + "no bake render with the switch on at the current size yet");
-    return JPT_OK;
-}
-
-int jpt_read_bake_directional_f32(jpt_ctx* c, float* out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_bake_directional_f32: null output");
-    int rc = bake_directional_ready(c, "jpt_read_bake_directional_f32");
-    if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the renders queued so far, as jpt_read_accum_f32)
-    const size_t bytes = c->d_bake_dir.n * sizeof(float4);
-    if ((rc = staged_read(c, c->d_bake_dir.p, bytes)) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-void* jpt_device_bake_directional(jpt_ctx* c, int32_t finished, size_t* bytes_out)
-{
-    if (bytes_out) *bytes_out = 0;
-    if (!c || c->device < 0 || !c->bake_dir) return nullptr;
-    if (finished) {
-        if (!c->lmd_valid || !c->d_lmd_out.p) return nullptr;
-        if (bytes_out) *bytes_out = c->d_lmd_out.n * sizeof(float4);
-        return c->d_lmd_out.p;
-    }
-    if (!c->d_bake_dir.p || !c->bake_dir_valid) return nullptr;
-    if (bytes_out) *bytes_out = c->d_bake_dir.n * sizeof(float4);
-    return c->d_bake_dir.p;
-}
-
-int jpt_bake_finish_directional(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    const char* who = "jpt_bake_finish_directional";
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_bake_finish_directional filters the progressive moments: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: DEBUG_STEPS renders make no moments (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional needs the whole image on one context (world == 1)");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_bake_finish_directional: host-only context: it runs on the device");
-    const PrimaryState& p = c->primary;
-    if (!c->bake_dir) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: the directional planes are switched off (jpt_set_bake_directional)");
-    if (!p.has_bake()) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: no bake images (jpt_bake_begin or jpt_set_bake_texels first)");
-    if (p.has_probes()) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: the lightmap is made of texel images, and the context holds probes (jpt_set_probes)");
-    if (p.has_cubes())
-        return fail(c, JPT_E_STATE,
-                    "jpt_bake_finish_directional: the lightmap is made of texel images, and the context holds reflection probes (jpt_set_reflection_probes)");
-    if (!c->params_set || p.bake_w != c->width || p.bake_h != c->height)
-        return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: the bake images are " + std::to_string(p.bake_w) + " x " + std::to_string(p.bake_h) +
-                                        " texels but jpt_set_params says " + std::to_string(c->width) + " x " + std::to_string(c->height));
-    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_bake_finish_directional: no frame accumulated since the last reset");
-    const int rc = bake_directional_ready(c, who);
-    if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->width * c->height;   // (>= 1; world == 1: the planes are npx texels each)
-    if (c->d_lmd_out.n != 3 * npx || !c->d_lmd_out.p) {
-        c->lmd_valid = false;
-        HIP_TRY(c, c->d_lmd_xg.resize(npx));
-        HIP_TRY(c, c->d_lmd_ng.resize(npx));
-        HIP_TRY(c, c->d_lmd_ping.resize(npx));
-        HIP_TRY(c, c->d_lmd_pong.resize(npx));
-        HIP_TRY(c, c->d_lmd_out.resize(3 * npx));
-    }
-    // On the context's stream, as jpt_bake_finish: each plane is the "accumulation" of one run of the same filter and dilation, with
-    // the same frame count, images and parameters; the planes are filtered independently of one another and of the L0 map.
-    for (int k = 0; k < 3; k++) {
-        const float4* res = launch_lightmap_finish(c->stream, c->lm_params, c->width, c->height, c->d_bake_dir.p + (size_t)k * npx, (float)c->frame_count,
-                                                   p.d_bake_pos.p, p.d_bake_nrm.p, c->d_lmd_xg.p, c->d_lmd_ng.p, c->d_lmd_ping.p, c->d_lmd_pong.p);
-        HIP_TRY(c, hipMemcpyAsync(c->d_lmd_out.p + (size_t)k * npx, res, npx * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-    }
-    HIP_TRY(c, hipGetLastError());
-    c->lmd_valid = true;
-    return JPT_OK;
-}
-
-int jpt_read_lightmap_directional_f32(jpt_ctx* c, float* out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_lightmap_directional_f32: null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_read_lightmap_directional_f32: host-only context: jpt_bake_finish_directional runs on the device");
-    if (!c->lmd_valid || !c->d_lmd_out.p)
-        return fail(c, JPT_E_STATE, "jpt_read_lightmap_directional_f32: no jpt_bake_finish_directional at the current size and bake images yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = c->d_lmd_out.n * sizeof(float4);
-    const int rc = staged_read(c, c->d_lmd_out.p, bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-// ---- jpt_display ------------------------------------------------------------------------------------------------------------
-int jpt_set_display_params(jpt_ctx* c, const jpt_display_params* params)
-{
-    if (!c) return JPT_E_INVALID;
-    DisplayParams p;
-    if (params) {
-        p.source = params->source;
-        p.tonemap = params->tonemap;
-        p.transfer = params->transfer;
-        p.bloom_levels = params->bloom_levels;
-        p.exposure = params->exposure;
-        p.white = params->white;
-        p.bloom_threshold = params->bloom_threshold;
-        p.bloom_strength = params->bloom_strength;
-    }
-    std::string why;
-    const int rc = check_display_params(p, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_display runs on the device");
-    c->disp_params = p;
-    return JPT_OK;
-}
-
-int jpt_display(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_display grades the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_display: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1)
-        return fail(c, JPT_E_STATE, "jpt_display needs the whole image on one context (world == 1): the bloom reads rows a partition does not hold");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_display runs on the device");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_display: jpt_set_params not called");
-    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_display: no frame accumulated since the last reset");
-    const DisplayParams prm = c->disp_params;
-    const bool denoised = prm.source == JPT_DISPLAY_SOURCE_DENOISED;
-    if (denoised && !c->dn_valid) return fail(c, JPT_E_STATE, "jpt_display: JPT_DISPLAY_SOURCE_DENOISED and no jpt_denoise at the current resolution yet");
-    if (c->auto_exposure && !c->meter_valid)
-        return fail(c, JPT_E_STATE, "jpt_display: auto-exposure is on (jpt_set_auto_exposure) and no jpt_meter ran since the metering state was reset");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)c->width * c->height;
-    HIP_TRY(c, c->d_disp_f32.resize(npx));
-    HIP_TRY(c, c->d_disp_ldr.resize(npx));
-    if (prm.bloom_levels > 0) HIP_TRY(c, c->d_disp_pyramid.resize(display_pyramid_elems(c->width, c->height, kDisplayMaxLevels, nullptr)));
-    // On the context's stream, as jpt_denoise: behind the accumulation of every render queued so far and behind a jpt_denoise queued
-    // before it; the accumulation of every later render (and a later jpt_denoise) waits for what it holds.
-    if (npx) {
-        launch_display(c->stream, prm, c->width, c->height, denoised ? c->d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count,
-                       c->d_disp_pyramid.p, c->d_disp_f32.p, c->d_disp_ldr.p, c->auto_exposure ? &c->d_meter_state.p->exposure : nullptr);
-        HIP_TRY(c, hipGetLastError());
-    }
-    c->disp_valid = true;
-    return JPT_OK;
-}
-
-static int read_display_common(jpt_ctx* c, bool have_out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!have_out) return fail(c, JPT_E_INVALID, "null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_display runs on the device");
-    if (!c->disp_valid) return fail(c, JPT_E_STATE, "no jpt_display at the current resolution yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    return JPT_OK;
-}
-
-int jpt_read_display_rgba8(jpt_ctx* c, uint8_t* out)
-{
-    int rc = read_display_common(c, out != nullptr);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->width * c->height * sizeof(uint32_t);
-    if ((rc = staged_read(c, c->d_disp_ldr.p, bytes)) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-int jpt_read_display_f32(jpt_ctx* c, float* out)
-{
-    int rc = read_display_common(c, out != nullptr);
-    if (rc) return rc;
-    const size_t bytes = (size_t)c->width * c->height * sizeof(float4);
-    if ((rc = staged_read(c, c->d_disp_f32.p, bytes)) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-// ---- jpt_meter ----------------------------------------------------------------------------------------------------------------
-int jpt_set_meter_params(jpt_ctx* c, const jpt_meter_params* params)
-{
-    if (!c) return JPT_E_INVALID;
-    MeterParams p;
-    if (params) {
-        p.source = params->source;
-        p.mode = params->mode;
-        p.low_permille = params->low_permille;
-        p.high_permille = params->high_permille;
-        p.key = params->key;
-        p.min_exposure = params->min_exposure;
-        p.max_exposure = params->max_exposure;
-        p.adapt = params->adapt;
-    }
-    std::string why;
-    const int rc = check_meter_params(p, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
-    c->meter_params = p;
-    return JPT_OK;
-}
-
-int jpt_set_auto_exposure(jpt_ctx* c, int32_t enable)
-{
-    if (!c) return JPT_E_INVALID;
-    if (enable != 0 && enable != 1) return fail(c, JPT_E_INVALID, "jpt_set_auto_exposure: enable must be 0 or 1");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
-    c->auto_exposure = enable != 0;
-    return JPT_OK;
-}
-
-int jpt_meter_reset(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
-    c->meter_valid = false;
-    return JPT_OK;
-}
-
-int jpt_meter(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_meter meters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_meter: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_meter needs the whole image on one context (world == 1)");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_meter: jpt_set_params not called");
-    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_meter: no frame accumulated since the last reset");
-    const MeterParams prm = c->meter_params;
-    const bool denoised = prm.source == JPT_DISPLAY_SOURCE_DENOISED;
-    if (denoised && !c->dn_valid) return fail(c, JPT_E_STATE, "jpt_meter: JPT_DISPLAY_SOURCE_DENOISED and no jpt_denoise at the current resolution yet");
-    if (c->width <= 0 || c->height <= 0) return fail(c, JPT_E_STATE, "jpt_meter: the image has no pixels");
-    if ((uint64_t)c->width * (uint64_t)c->height > (1ull << 30))
-        return fail(c, JPT_E_LIMIT, "jpt_meter: more than 2^30 pixels (a weight is at most 4 and a bin is a uint32)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, c->d_meter_bins.resize(kMeterBinWords));
-    HIP_TRY(c, c->d_meter_state.resize(1));
-    // On the context's stream, as jpt_display: behind the accumulation of every render, a jpt_denoise and a jpt_display queued before
-    // it; a later jpt_display with auto-exposure reads the state record behind the resolve.
-    const bool first = !c->meter_valid;
-    launch_meter(c->stream, prm, c->width, c->height, denoised ? c->d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count, first,
-                 c->d_meter_bins.p, c->d_meter_state.p);
-    HIP_TRY(c, hipGetLastError());
-    c->meter_valid = true;
-    return JPT_OK;
-}
-
-int jpt_read_meter(jpt_ctx* c, jpt_meter_result* out, uint32_t* hist256)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_meter runs on the device");
-    if (!c->meter_valid) return fail(c, JPT_E_STATE, "no jpt_meter since the metering state was reset");
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    static_assert(sizeof(jpt_meter_result) == sizeof(MeterState), "the state record is jpt_meter_result");
-    if ((rc = staged_read(c, c->d_meter_state.p, sizeof(MeterState))) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, sizeof(MeterState));
-    if (hist256) {
-        if ((rc = staged_read(c, c->d_meter_bins.p, kMeterBins * sizeof(uint32_t))) != JPT_OK) return rc;
-        std::memcpy(hist256, c->h_read_pinned.p, kMeterBins * sizeof(uint32_t));
-    }
-    return JPT_OK;
-}
-
-// ---- jpt_set_variance, jpt_noise_estimate, jpt_render_converge (jpt_variance.h, jpt_kernels_variance.hip) -------------------------
-
-int jpt_set_variance(jpt_ctx* c, int32_t enable)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_set_variance: host-only context: the moment is made on the device");
-    const bool on = enable != 0;
-    if (on == c->variance) return JPT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->d_variance.p || c->d_noise_tiles.p) {
-        // the renders queued so far add to the plane: they finish first, then the plane and the tile map go
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->variance_release();
-    }
-    c->variance_valid = c->noise_valid = false;
-    c->variance = on;
-    return jpt_accum_reset(c);   // the sum and the moment are of the same frames: both start over
-}
-
-// the plane of a read or of an estimate: JPT_OK, or the refusal
-static int variance_ready(jpt_ctx* c, const char* call)
-{
-    const std::string who = std::string(call) + ": ";
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, who + "host-only context: the moment is made on the device");
-    if (!c->variance) return fail(c, JPT_E_STATE, who + "the variance plane is switched off (jpt_set_variance)");
-    if (!c->d_variance.p || !c->variance_valid || c->d_variance.n != (size_t)c->width * (size_t)c->local_rows)
-        return fail(c, JPT_E_STATE, who + "no render with the switch on at the current size yet");
-    return JPT_OK;
-}
-
-int jpt_read_variance_f32(jpt_ctx* c, float* out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_variance_f32: null output");
-    int rc = variance_ready(c, "jpt_read_variance_f32");
-    if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the renders queued so far, as jpt_read_accum_f32)
-    const size_t n = c->d_variance.n * 4;   // floats
-    if ((rc = staged_read(c, c->d_variance.p, n * sizeof(float))) != JPT_OK) return rc;
-    if (c->world == 1) std::memcpy(out, c->h_read_pinned.p, n * sizeof(float));
-    else {
-        std::memset(out, 0, (size_t)c->width * c->height * 16);
-        scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 4);
-    }
-    return JPT_OK;
-}
-
-void* jpt_device_variance(jpt_ctx* c, size_t* bytes_out)
-{
-    if (bytes_out) *bytes_out = 0;
-    if (!c || c->device < 0 || !c->variance || !c->d_variance.p || !c->variance_valid) return nullptr;
-    if (bytes_out) *bytes_out = c->d_variance.n * sizeof(float4);
-    return c->d_variance.p;
-}
-
-int jpt_set_noise_params(jpt_ctx* c, const jpt_noise_params* params)
-{
-    if (!c) return JPT_E_INVALID;
-    NoiseParams p;
-    if (params) {
-        p.threshold = params->threshold;
-        p.floor = params->floor;
-        p.percentile_permille = params->percentile_permille;
-        p.allowed_permille = params->allowed_permille;
-    }
-    std::string why;
-    const int rc = check_noise_params(p, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
-    c->noise_params = p;
-    return JPT_OK;
-}
-
-int jpt_noise_estimate(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_noise_estimate reads the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_noise_estimate: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_noise_estimate needs the whole image on one context (world == 1)");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_noise_estimate: jpt_set_params not called");
-    int rc = variance_ready(c, "jpt_noise_estimate");
-    if (rc != JPT_OK) return rc;
-    if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_noise_estimate: no frame accumulated since the last reset");
-    if ((uint64_t)c->width * (uint64_t)c->height > (1ull << 30)) return fail(c, JPT_E_LIMIT, "jpt_noise_estimate: more than 2^30 pixels (a bin is a uint32)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t n_tiles = (size_t)((c->width + 7) / 8) * (size_t)((c->height + 7) / 8);
-    if (c->d_noise_tiles.n != n_tiles || !c->d_noise_tiles.p) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (an estimate in flight may write the old map)
-        c->noise_valid = false;
-        HIP_TRY(c, c->d_noise_tiles.resize(n_tiles));
-    }
-    if (!c->d_noise_bins.p) {
-        // the resolve leaves the working sets cleared: only fresh buffers are cleared here
-        HIP_TRY(c, c->d_noise_bins.resize(kNoiseBinWords));
-        HIP_TRY(c, c->d_noise_result.resize(1));
-        HIP_TRY(c, hipMemsetAsync(c->d_noise_bins.p, 0, kNoiseBinWords * sizeof(uint32_t), c->stream));
-    }
-    // On the context's stream, as jpt_meter: behind the accumulation of every render queued before it.  In a bake render a texel
-    // without a surface is not counted.
-    const PrimaryState& p = c->primary;
-    const float4* normal = p.has_bake() && !p.has_cubes() && p.bake_w == c->width && p.bake_h == c->height ? p.d_bake_nrm.p : nullptr;   // (resolve_primary's bake render)
-    launch_noise_estimate(c->stream, c->noise_params, c->width, c->height, c->d_accum.p, c->d_variance.p, c->frame_count, normal, c->d_noise_bins.p,
-                          c->d_noise_tiles.p, c->d_noise_result.p);
-    HIP_TRY(c, hipGetLastError());
-    c->noise_valid = true;
-    return JPT_OK;
-}
-
-int jpt_read_noise(jpt_ctx* c, jpt_noise_result* out, uint32_t* hist256)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_noise: null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
-    if (!c->noise_valid) return fail(c, JPT_E_STATE, "jpt_read_noise: no jpt_noise_estimate at the current size yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    static_assert(sizeof(jpt_noise_result) == sizeof(NoiseResult), "the record is jpt_noise_result");
-    if ((rc = staged_read(c, c->d_noise_result.p, sizeof(NoiseResult))) != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, sizeof(NoiseResult));
-    if (hist256) {
-        if ((rc = staged_read(c, c->d_noise_bins.p, kMeterBins * sizeof(uint32_t))) != JPT_OK) return rc;
-        std::memcpy(hist256, c->h_read_pinned.p, kMeterBins * sizeof(uint32_t));
-    }
-    return JPT_OK;
-}
-
-int jpt_read_noise_tiles_f32(jpt_ctx* c, float* out)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!out) return fail(c, JPT_E_INVALID, "jpt_read_noise_tiles_f32: null output");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_noise_estimate runs on the device");
-    if (!c->noise_valid) return fail(c, JPT_E_STATE, "jpt_read_noise_tiles_f32: no jpt_noise_estimate at the current size yet");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = c->d_noise_tiles.n * sizeof(float);
-    const int rc = staged_read(c, c->d_noise_tiles.p, bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
-}
-
-void* jpt_device_noise_tiles(jpt_ctx* c, size_t* bytes_out)
-{
-    if (bytes_out) *bytes_out = 0;
-    if (!c || c->device < 0 || !c->noise_valid || !c->d_noise_tiles.p) return nullptr;
-    if (bytes_out) *bytes_out = c->d_noise_tiles.n * sizeof(float);
-    return c->d_noise_tiles.p;
-}
-
-// the loop a caller would write: render a step, estimate, read 32 bytes, until converged or max_frames
-int jpt_render_converge(jpt_ctx* c, int32_t frames_per_step, int32_t max_frames, uint32_t first_frame_index, int32_t* frames_done, jpt_noise_result* last)
-{
-    if (!c) return JPT_E_INVALID;
-    if (frames_done) *frames_done = 0;
-    if (frames_per_step <= 0 || max_frames <= 0) return fail(c, JPT_E_INVALID, "jpt_render_converge: frames_per_step and max_frames must be > 0");
-    if (!c->variance && c->device >= 0) return fail(c, JPT_E_STATE, "jpt_render_converge: the variance plane is switched off (jpt_set_variance)");
-    jpt_noise_result res;
-    std::memset(&res, 0, sizeof res);
-    res.flags = JPT_NOISE_EMPTY;
-    int32_t done = 0;
-    while (done < max_frames) {
-        const int32_t step = std::min(frames_per_step, max_frames - done);   // (the last step is shortened to land on max_frames)
-        int rc = jpt_render_async(c, step, first_frame_index + (uint32_t)done);
-        if (rc != JPT_OK) return rc;
-        done += step;
-        if (frames_done) *frames_done = done;
-        if ((rc = jpt_noise_estimate(c)) != JPT_OK) return rc;
-        if ((rc = jpt_read_noise(c, &res, nullptr)) != JPT_OK) return rc;   // the one wait of the step, for 32 bytes
-        if (last) *last = res;
-        if (res.flags & JPT_NOISE_CONVERGED) break;
-    }
-    return JPT_OK;
+    return read_rows_out(c, c->assembled ? c->d_full_accum.p : c->d_accum.p, sizeof(float), 4, c->assembled, out);
 }
 
 // ---- jpt_query_rays / jpt_query_pixels -----------------------------------------------------------------------------------------
@@ -3176,16 +2426,7 @@ int jpt_read_depth_f32(jpt_ctx* c, float* out)
     if (!c->depth_valid)
         return fail(c, JPT_E_STATE, (c->outputs & JPT_OUTPUT_DEPTH) ? "no render has written the depth image yet"
                                                                      : "the depth image is switched off (jpt_set_outputs): no render writes it");
-    const size_t full = (size_t)c->width * c->height;
-    const size_t n = (size_t)c->local_rows * c->width;
-    rc = staged_read(c, c->d_depth.p, n * sizeof(float));
-    if (rc) return rc;
-    if (c->world == 1) std::memcpy(out, c->h_read_pinned.p, n * sizeof(float));
-    else {
-        std::memset(out, 0, full * 4);
-        scatter_rows(c->h_read_pinned.as<const float>(), out, c->width, c->height, c->rank, c->world, 1);
-    }
-    return JPT_OK;
+    return read_rows_out(c, c->d_depth.p, sizeof(float), 1, false, out);
 }
 
 void* jpt_device_accum(jpt_ctx* c, size_t* bytes_out)

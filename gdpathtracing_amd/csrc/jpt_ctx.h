@@ -1,5 +1,5 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_encode.cpp).
+// (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
 #pragma once
 #include "../../include/jpt.h"
 
@@ -227,8 +227,91 @@ int resolve_primary(jpt_ctx* c, PrimaryRays& out);
 // context's model seen through its camera as both are now -- no render's refusals apply.  JPT_E_STATE while the context holds bake
 // images, probes or reflection probes (`rays`: what the call's rays are, for the message).
 int view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& out);
-// Blocking read-backs: device -> the context's pinned read buffer (h_read_pinned), on the context's stream (jpt_capi.cpp)
+// Blocking read-backs: device -> the context's pinned read buffer (h_read_pinned), on the context's stream (jpt_capi.cpp) ...
 int staged_read(jpt_ctx* c, const void* src, size_t bytes);
+// ... and on to the caller's memory: `bytes` at `out` (nothing is copied when bytes == 0)
+int read_out(jpt_ctx* c, const void* src, size_t bytes, void* out);
+// ... of an image of `comps` elements of `elem` bytes per pixel: `src` holds the whole image (`whole`), or the context's rows, which are
+// scattered to their image rows of a zeroed `out` when the context is a partition (world > 1)
+int read_rows_out(jpt_ctx* c, const void* src, size_t elem, int comps, bool whole, void* out);
+
+// What the context holds of its post stages, the calls that read the progressive sum on the context's stream and keep what they make in
+// buffers of their own: written and read by those calls and their read-backs (jpt_post.cpp; jpt_encode.cpp reads three of the images)
+struct PostState {
+    // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
+    // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution
+    AtrousParams dn_params;
+    DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
+    DevBuf<uint32_t> d_dn_ldr;
+    bool dn_valid = false;
+    // jpt_bake_finish: the context's parameters, and its own images (two guides, a colour ping and pong: 64 B per texel) -- made at
+    // the first jpt_bake_finish at a size, kept until jpt_set_params names another size or a call writes the bake images
+    // (lightmap_release); lm_result: the one of ping / pong that holds the lightmap of a jpt_bake_finish at the current size and images
+    LightmapParams lm_params;
+    DevBuf<float4> d_lm_xg, d_lm_ng, d_lm_ping, d_lm_pong;
+    const float4* lm_result = nullptr;
+    // jpt_set_bake_directional: the switch, and the three moment planes a bake render adds to (jpt_bake_dir.h; 48 B per texel of the
+    // context's rows) -- made by the first bake render with the switch on at a size (ensure_bake_dir), given back when the switch goes
+    // off or the bake images are freed (bake_dir_release); bake_dir_valid: a bake render has written them at the current size.
+    // jpt_bake_finish_directional: guides and working images of its own (jpt_bake_finish's lightmap stays what it is) and the three
+    // finished planes, 112 B per texel in all, kept and given back as jpt_bake_finish's are (lmd_release); lmd_valid as lm_result.
+    bool bake_dir = false;
+    DevBuf<float4> d_bake_dir;
+    bool bake_dir_valid = false;
+    DevBuf<float4> d_lmd_xg, d_lmd_ng, d_lmd_ping, d_lmd_pong, d_lmd_out;
+    bool lmd_valid = false;
+    // jpt_display: the context's parameters, and its own buffers -- the two images made at the first jpt_display at a resolution,
+    // the pyramid (six levels' worth) at the first one with bloom, kept until jpt_set_params names another size; disp_valid: the
+    // images hold the result of a jpt_display at the current resolution
+    DisplayParams disp_params;
+    DevBuf<float4> d_disp_f32, d_disp_pyramid;
+    DevBuf<uint32_t> d_disp_ldr;
+    bool disp_valid = false;
+    // jpt_meter: the context's parameters and the auto-exposure switch of jpt_display, and its own buffers -- the published bins, the
+    // working sets (kMeterBinWords) and the state record, made at the first jpt_meter, kept until jpt_destroy; meter_valid: the record
+    // holds the state a jpt_meter left since the last reset (jpt_meter_reset, jpt_set_params with another size), so the next jpt_meter
+    // is not a FIRST one
+    MeterParams meter_params;
+    bool auto_exposure = false;
+    DevBuf<uint32_t> d_meter_bins;
+    DevBuf<MeterState> d_meter_state;
+    bool meter_valid = false;
+    // jpt_set_variance: the switch, and the plane of second moments every render adds to (jpt_variance.h; 16 B per pixel of the
+    // context's rows) -- made by the first render with the switch on at a size (ensure_variance), given back when the switch goes off
+    // (variance_release); variance_valid: a render has written it.  jpt_noise_estimate: the context's parameters, and its own buffers --
+    // the tile map (4 B per 8 x 8 tile), the published bins and the working sets (kNoiseBinWords words, 17.3 KB) and the 32-byte
+    // record, made at the first jpt_noise_estimate at a size; noise_valid: they hold the result of one at the current size.
+    bool variance = false;
+    DevBuf<float4> d_variance;
+    bool variance_valid = false;
+    NoiseParams noise_params;
+    DevBuf<float> d_noise_tiles;
+    DevBuf<uint32_t> d_noise_bins;
+    DevBuf<NoiseResult> d_noise_result;
+    bool noise_valid = false;
+
+    void lightmap_release();   // jpt_bake_finish's images and result, and lmd_release
+    void lmd_release();        // jpt_bake_finish_directional's images and result
+    void bake_dir_release() { d_bake_dir.release(); bake_dir_valid = false; }
+    void variance_release() { d_variance.release(); d_noise_tiles.release(); variance_valid = noise_valid = false; }   // the plane and the tile map
+    // The one place that says what re-made framebuffers do to this state (alloc_framebuffers: the plane and the estimate are of frames
+    // that are gone) and, `resized`, what another image size does on top (jpt_set_params): every image of that size is given back and
+    // every result of that size forgotten.  sized_buffers: whether one of the buffers it then frees exists -- work on the context's
+    // stream may still use it, so the caller waits for the stream first.
+    bool sized_buffers() const { return d_dn_ping.p || d_lm_ping.p || d_lmd_out.p || d_disp_f32.p || d_disp_pyramid.p; }
+    void framebuffers_remade(bool resized);
+};
+// What a render refuses with the directional planes (the variance plane) switched on, and the planes (the plane) at the size of the
+// context's rows for it: do_render_batch's (jpt_post.cpp)
+int check_bake_directional(jpt_ctx* c);
+int ensure_bake_dir(jpt_ctx* c);
+int check_variance(jpt_ctx* c);
+int ensure_variance(jpt_ctx* c);
+// The refusals every call that reads the progressive sum opens with, in their order: a denoising mode other than progressive ("<call><what>:
+// the denoising mode must be ..."), DEBUG_STEPS (`steps`: the call's own sentence), a partition ("<call> needs the whole image ...<whole>")
+// and, unless `host_only` is null, a host-only context, in the call's own words.  sum_ready: no jpt_set_params, no frame since the reset.
+int reads_sum(jpt_ctx* c, const char* call, const char* what, const char* host_only, const char* whole = "", const char* steps = nullptr);
+int sum_ready(jpt_ctx* c, const char* call);
 
 }  // namespace jpt
 
@@ -359,58 +442,7 @@ struct jpt_ctx {
 
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
     PrimaryState primary;     // the lens, the camera model, the bake images, the probes and the reflection probes (jpt_primary.cpp)
-
-    // jpt_denoise: the context's parameters, and its own images -- made at the first jpt_denoise at a resolution, kept until
-    // jpt_set_params names another size; dn_valid: they hold the result of a jpt_denoise at the current resolution
-    AtrousParams dn_params;
-    DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
-    DevBuf<uint32_t> d_dn_ldr;
-    bool dn_valid = false;
-
-    // jpt_bake_finish: the context's parameters, and its own images (two guides, a colour ping and pong: 64 B per texel) -- made at
-    // the first jpt_bake_finish at a size, kept until jpt_set_params names another size or a call writes the bake images
-    // (lightmap_release); lm_result: the one of ping / pong that holds the lightmap of a jpt_bake_finish at the current size and images
-    LightmapParams lm_params;
-    DevBuf<float4> d_lm_xg, d_lm_ng, d_lm_ping, d_lm_pong;
-    const float4* lm_result = nullptr;
-    void lightmap_release()
-    {
-        d_lm_xg.release();
-        d_lm_ng.release();
-        d_lm_ping.release();
-        d_lm_pong.release();
-        lm_result = nullptr;
-        d_lmd_xg.release();
-        d_lmd_ng.release();
-        d_lmd_ping.release();
-        d_lmd_pong.release();
-        d_lmd_out.release();
-        lmd_valid = false;
-    }
-
-    // jpt_set_bake_directional: the switch, and the three moment planes a bake render adds to (jpt_bake_dir.h; 48 B per texel of the
-    // context's rows) -- made by the first bake render with the switch on at a size (ensure_bake_dir, jpt_capi.cpp), given back when
-    // the switch goes off or the bake images are freed (bake_dir_release); bake_dir_valid: a bake render has written them.
-    // jpt_bake_finish_directional: guides and working images of its own (jpt_bake_finish's lightmap stays what it is) and the three
-    // finished planes, 112 B per texel in all, kept and given back as jpt_bake_finish's are; lmd_valid as lm_result.
-    bool bake_dir = false;
-    DevBuf<float4> d_bake_dir;
-    bool bake_dir_valid = false;
-    DevBuf<float4> d_lmd_xg, d_lmd_ng, d_lmd_ping, d_lmd_pong, d_lmd_out;
-    bool lmd_valid = false;
-    void bake_dir_release()
-    {
-        d_bake_dir.release();
-        bake_dir_valid = false;
-    }
-
-    // jpt_display: the context's parameters, and its own buffers -- the two images made at the first jpt_display at a resolution,
-    // the pyramid (six levels' worth) at the first one with bloom, kept until jpt_set_params names another size; disp_valid: the
-    // images hold the result of a jpt_display at the current resolution
-    DisplayParams disp_params;
-    DevBuf<float4> d_disp_f32, d_disp_pyramid;
-    DevBuf<uint32_t> d_disp_ldr;
-    bool disp_valid = false;
+    PostState post;           // the parameters, buffers and validity flags of the calls that read the progressive sum (jpt_post.cpp)
 
     // jpt_encode (jpt_encode.cpp): its own buffer, grow-only and kept until jpt_destroy -- a snapshot that no other call writes;
     // enc_valid: it holds the texels enc_info describes.  enc_ev: two events around the last jpt_encode's kernel under
@@ -425,35 +457,6 @@ struct jpt_ctx {
     hipEvent_t ev_enc_readback = nullptr;
     bool enc_readback_pending = false;
     size_t enc_read_bytes = 0;
-
-    // jpt_meter: the context's parameters and the auto-exposure switch of jpt_display, and its own buffers -- the published bins, the working sets (kMeterBinWords) and the state
-    // record, made at the first jpt_meter, kept until jpt_destroy; meter_valid: the record holds the state a jpt_meter left since
-    // the last reset (jpt_meter_reset, jpt_set_params with another size), so the next jpt_meter is not a FIRST one
-    MeterParams meter_params;
-    bool auto_exposure = false;
-    DevBuf<uint32_t> d_meter_bins;
-    DevBuf<MeterState> d_meter_state;
-    bool meter_valid = false;
-
-    // jpt_set_variance: the switch, and the plane of second moments every render adds to (jpt_variance.h; 16 B per pixel of the
-    // context's rows) -- made by the first render with the switch on at a size (ensure_variance, jpt_capi.cpp), given back when the
-    // switch goes off; variance_valid: a render has written it.  jpt_noise_estimate: the context's parameters, and its own buffers --
-    // the tile map (4 B per 8 x 8 tile), the published bins and the working sets (kNoiseBinWords words, 17.3 KB) and the 32-byte
-    // record, made at the first jpt_noise_estimate at a size; noise_valid: they hold the result of one at the current size.
-    bool variance = false;
-    DevBuf<float4> d_variance;
-    bool variance_valid = false;
-    NoiseParams noise_params;
-    DevBuf<float> d_noise_tiles;
-    DevBuf<uint32_t> d_noise_bins;
-    DevBuf<NoiseResult> d_noise_result;
-    bool noise_valid = false;
-    void variance_release()
-    {
-        d_variance.release();
-        d_noise_tiles.release();
-        variance_valid = noise_valid = false;
-    }
 
     // jpt_query_rays / jpt_query_pixels (host forms): one chunk's rays, hits and occlusion bytes on the device, grow-only
     DevBuf<char> d_query;

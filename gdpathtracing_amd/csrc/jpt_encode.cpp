@@ -27,28 +27,26 @@ int resolve_source(jpt_ctx* c, int32_t source, int32_t level, EncodeSource& s)
     s.height = c->height;
     s.n = (uint64_t)c->width * (uint64_t)c->height;
     switch (source) {
-    case JPT_ENCODE_SOURCE_MEAN:
-        if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-            return fail(c, JPT_E_STATE, "jpt_encode: the mean is of the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-        if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_encode: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-        if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_encode needs the whole image on one context (world == 1)");
-        if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_encode: jpt_set_params not called");
-        if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_encode: no frame accumulated since the last reset");
+    case JPT_ENCODE_SOURCE_MEAN: {
+        int rc = reads_sum(c, "jpt_encode", ": the mean is of the progressive accumulation", nullptr);   // (the device: jpt_encode has asked)
+        if (rc == JPT_OK) rc = sum_ready(c, "jpt_encode");
+        if (rc != JPT_OK) return rc;
         s.src = c->d_accum.p;
         s.divisor = (float)c->frame_count;
         s.alpha_one = true;
         return JPT_OK;
+    }
     case JPT_ENCODE_SOURCE_DENOISED:
-        if (!c->dn_valid) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_denoise at the current resolution yet");
-        s.src = c->d_dn_ping.p;
+        if (!c->post.dn_valid) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_denoise at the current resolution yet");
+        s.src = c->post.d_dn_ping.p;
         return JPT_OK;
     case JPT_ENCODE_SOURCE_DISPLAY:
-        if (!c->disp_valid) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_display at the current resolution yet");
-        s.src = c->d_disp_f32.p;
+        if (!c->post.disp_valid) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_display at the current resolution yet");
+        s.src = c->post.d_disp_f32.p;
         return JPT_OK;
     case JPT_ENCODE_SOURCE_LIGHTMAP:
-        if (!c->lm_result) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_bake_finish at the current size and bake images yet");
-        s.src = c->lm_result;
+        if (!c->post.lm_result) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_bake_finish at the current size and bake images yet");
+        s.src = c->post.lm_result;
         return JPT_OK;
     case JPT_ENCODE_SOURCE_REFLECTION: {
         if (!p.refl_valid) return fail(c, JPT_E_STATE, "jpt_encode: no jpt_reflection_prefilter of the current reflection probes and size yet");
@@ -148,9 +146,7 @@ int jpt_read_encoded(jpt_ctx* c, void* out, size_t capacity)
     const size_t bytes = (size_t)c->enc_info.bytes;
     if (capacity < bytes) return fail(c, JPT_E_INVALID, "jpt_read_encoded: capacity is " + std::to_string(capacity) + " bytes and the encoded image has " + std::to_string(bytes));
     HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = staged_read(c, c->d_encoded.p, bytes)) != JPT_OK) return rc;
-    if (bytes) std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
+    return read_out(c, c->d_encoded.p, bytes, out);
 }
 
 int jpt_readback_encoded_begin(jpt_ctx* c)

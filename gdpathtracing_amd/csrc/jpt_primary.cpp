@@ -393,7 +393,7 @@ int bake_wait(jpt_ctx* c)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->lightmap_release();   // (every caller goes on to write the images: a jpt_bake_finish of the old ones is no longer the lightmap)
+    c->post.lightmap_release();   // (every caller goes on to write the images: a jpt_bake_finish of the old ones is no longer the lightmap)
     return JPT_OK;
 }
 
@@ -405,7 +405,7 @@ void bake_release(jpt_ctx* c)
     p.d_bake_winner.release();
     p.d_bake_in.release();
     p.bake_w = p.bake_h = 0;
-    c->bake_dir_release();   // (jpt_set_bake_directional's planes exist only beside the images; every caller has waited: bake_wait)
+    c->post.bake_dir_release();   // (jpt_set_bake_directional's planes exist only beside the images; every caller has waited: bake_wait)
 }
 
 int bake_alloc(jpt_ctx* c, int32_t width, int32_t height)
@@ -540,9 +540,8 @@ int jpt_read_bake_texels(jpt_ctx* c, float* position4, float* normal4)
     const float4* const src[2] = {c->primary.d_bake_pos.p, c->primary.d_bake_nrm.p};
     for (int k = 0; k < 2; k++) {
         if (!out[k]) continue;
-        const int rc = staged_read(c, src[k], bytes);
+        const int rc = read_out(c, src[k], bytes, out[k]);
         if (rc != JPT_OK) return rc;
-        std::memcpy(out[k], c->h_read_pinned.p, bytes);
     }
     return JPT_OK;
 }
@@ -614,21 +613,16 @@ int jpt_read_probes(jpt_ctx* c, float* position3)
     if (!c->primary.has_probes()) return fail(c, JPT_E_STATE, "jpt_read_probes: no probes (jpt_set_probes first)");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = 3 * (size_t)c->primary.probe_n * sizeof(float);
-    const int rc = staged_read(c, c->primary.d_probe_pos.p, bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(position3, c->h_read_pinned.p, bytes);
-    return JPT_OK;
+    return read_out(c, c->primary.d_probe_pos.p, bytes, position3);
 }
 
 int jpt_probe_project(jpt_ctx* c, int32_t flags)
 {
     if (!c) return JPT_E_INVALID;
     if (flags != JPT_PROBE_RADIANCE && flags != JPT_PROBE_IRRADIANCE) return fail(c, JPT_E_INVALID, "jpt_probe_project: flags must be JPT_PROBE_RADIANCE or JPT_PROBE_IRRADIANCE");
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_probe_project projects the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_probe_project: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1) return fail(c, JPT_E_STATE, "jpt_probe_project needs the whole image on one context (world == 1): the gathering context projects");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_probe_project: host-only context: it runs on the device");
+    const int rc = reads_sum(c, "jpt_probe_project", " projects the progressive accumulation", "jpt_probe_project: host-only context: it runs on the device",
+                             ": the gathering context projects");
+    if (rc != JPT_OK) return rc;
     PrimaryState& p = c->primary;
     if (!p.has_probes()) return fail(c, JPT_E_STATE, "jpt_probe_project: no probes (jpt_set_probes first)");
     if (p.has_cubes())
@@ -670,10 +664,7 @@ int jpt_read_probe_sh_f32(jpt_ctx* c, float* out)
     if (!c->primary.sh_valid) return fail(c, JPT_E_STATE, "jpt_read_probe_sh_f32: no jpt_probe_project of the current probes and size yet");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = 9 * (size_t)c->primary.probe_n * sizeof(float4);
-    const int rc = staged_read(c, c->primary.d_probe_sh.p, bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
+    return read_out(c, c->primary.d_probe_sh.p, bytes, out);
 }
 
 // ---- reflection probes: the context's positions (jpt_cube.h) and their prefiltered mip chain (jpt_reflection.h) ---------------------
@@ -753,10 +744,7 @@ int jpt_read_reflection_probes(jpt_ctx* c, float* position3)
     if (!c->primary.has_cubes()) return fail(c, JPT_E_STATE, "jpt_read_reflection_probes: no reflection probes (jpt_set_reflection_probes first)");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = 3 * (size_t)c->primary.cube_n * sizeof(float);
-    const int rc = staged_read(c, c->primary.d_cube_pos.p, bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(position3, c->h_read_pinned.p, bytes);
-    return JPT_OK;
+    return read_out(c, c->primary.d_cube_pos.p, bytes, position3);
 }
 
 int jpt_set_reflection_params(jpt_ctx* c, const jpt_reflection_params* params)
@@ -779,12 +767,9 @@ int jpt_set_reflection_params(jpt_ctx* c, const jpt_reflection_params* params)
 int jpt_reflection_prefilter(jpt_ctx* c)
 {
     if (!c) return JPT_E_INVALID;
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter filters the progressive accumulation: the denoising mode must be JPT_DENOISE_PROGRESSIVE");
-    if (c->debug_steps) return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: the accumulation holds DEBUG_STEPS counts, not radiance (jpt_set_debug_steps)");
-    if (c->rank != 0 || c->world != 1)
-        return fail(c, JPT_E_STATE, "jpt_reflection_prefilter needs the whole image on one context (world == 1): the gathering context filters");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_reflection_prefilter: host-only context: it runs on the device");
+    const int rc = reads_sum(c, "jpt_reflection_prefilter", " filters the progressive accumulation", "jpt_reflection_prefilter: host-only context: it runs on the device",
+                             ": the gathering context filters");
+    if (rc != JPT_OK) return rc;
     PrimaryState& p = c->primary;
     if (!p.has_cubes()) return fail(c, JPT_E_STATE, "jpt_reflection_prefilter: no reflection probes (jpt_set_reflection_probes first)");
     if (p.has_bake() || p.has_probes())
@@ -873,10 +858,7 @@ int jpt_read_reflection_f32(jpt_ctx* c, int32_t level, float* out)
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t shift = (uint32_t)cube_log2(p.cube_face);
     const size_t s = (size_t)(p.cube_face >> level), bytes = (size_t)p.cube_n * 6u * s * s * sizeof(float4);
-    const int rc = staged_read(c, p.d_refl_out.p + refl_out_offset((uint32_t)p.cube_n, shift, (uint32_t)level), bytes);
-    if (rc != JPT_OK) return rc;
-    std::memcpy(out, c->h_read_pinned.p, bytes);
-    return JPT_OK;
+    return read_out(c, p.d_refl_out.p + refl_out_offset((uint32_t)p.cube_n, shift, (uint32_t)level), bytes, out);
 }
 
 int jpt_get_reflection_timing(jpt_ctx* c, float* chain_ms, float* prefilter_ms)
