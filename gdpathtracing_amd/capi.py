@@ -77,6 +77,7 @@ SYMBOLS = [
     "jpt_set_bake_directional", "jpt_read_bake_directional_f32", "jpt_device_bake_directional", "jpt_bake_finish_directional",
     "jpt_read_lightmap_directional_f32", "jpt_debug_bake_moments",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
+    "jpt_set_denoise_variance", "jpt_read_denoised_variance_f32", "jpt_debug_atrous_variance",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
     "jpt_set_variance", "jpt_read_variance_f32", "jpt_device_variance", "jpt_set_noise_params", "jpt_noise_estimate", "jpt_read_noise",
@@ -110,6 +111,14 @@ class DenoiseParams(C.Structure):
 
     def __init__(self, passes=5, normal_power_log2=6, sigma_plane=0.02, sigma_color=4.0):
         super().__init__(passes, normal_power_log2, sigma_plane, sigma_color)
+
+
+class DenoiseVarianceParams(C.Structure):
+    """jpt_denoise_variance_params; the defaults are the library's (the guidance off)"""
+    _fields_ = [("enable", C.c_int32), ("sigma_variance", C.c_float), ("variance_floor", C.c_float), ("reserved", C.c_int32)]
+
+    def __init__(self, enable=0, sigma_variance=2.0, variance_floor=1e-6, reserved=0):
+        super().__init__(enable, sigma_variance, variance_floor, reserved)
 
 
 class BakeFinishParams(C.Structure):
@@ -466,6 +475,10 @@ def lib():
         L.jpt_read_denoised_rgba8.argtypes = [vp, vp]
         L.jpt_read_guides_f32.argtypes = [vp, vp, vp, vp]
         L.jpt_debug_atrous.argtypes = [C.c_int, i32, i32, C.POINTER(DenoiseParams), vp, vp, vp, vp, vp]
+    if hasattr(L, "jpt_set_denoise_variance") or "JPT_LIB" not in os.environ:
+        L.jpt_set_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarianceParams)]
+        L.jpt_read_denoised_variance_f32.argtypes = [vp, vp]
+        L.jpt_debug_atrous_variance.argtypes = [C.c_int, i32, i32, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceParams), vp, vp, u32, vp, vp, vp, vp, vp]
     if hasattr(L, "jpt_display") or "JPT_LIB" not in os.environ:
         L.jpt_set_display_params.argtypes = [vp, C.POINTER(DisplayParams)]
         L.jpt_display.argtypes = [vp]

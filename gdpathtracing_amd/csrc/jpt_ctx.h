@@ -7,6 +7,7 @@
 
 #include "jpt_builder.h"
 #include "jpt_denoise.h"
+#include "jpt_denoise_var.h"
 #include "jpt_display.h"
 #include "jpt_lightmap.h"
 #include "jpt_meter.h"
@@ -244,6 +245,12 @@ struct PostState {
     DevBuf<float4> d_dn_pos, d_dn_nrm, d_dn_alb, d_dn_ping, d_dn_pong;
     DevBuf<uint32_t> d_dn_ldr;
     bool dn_valid = false;
+    // jpt_set_denoise_variance: the context's parameters (dn_var.enable: the switch), and the plane of the variance the last pass leaves
+    // (jpt_denoise_var.h; 4 B per pixel) -- made at the first guided jpt_denoise at a resolution, kept as jpt_denoise's images are;
+    // dn_var_valid: the images hold the result of a guided jpt_denoise
+    AtrousVarParams dn_var;
+    DevBuf<float> d_dn_var;
+    bool dn_var_valid = false;
     // jpt_bake_finish: the context's parameters, and its own images (two guides, a colour ping and pong: 64 B per texel) -- made at
     // the first jpt_bake_finish at a size, kept until jpt_set_params names another size or a call writes the bake images
     // (lightmap_release); lm_result: the one of ping / pong that holds the lightmap of a jpt_bake_finish at the current size and images

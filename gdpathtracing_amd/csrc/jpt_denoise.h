@@ -48,22 +48,25 @@ __host__ __device__ __forceinline__ float4 atrous_demodulate(const float4& sum, 
     return make_float4((sum.x / fc) / a.x, (sum.y / fc) / a.y, (sum.z / fc) / a.z, 0.0f);
 }
 
+// the geometric weight e of tap q seen from centre p: misses see only misses; else the normal weight times the plane weight
+__host__ __device__ __forceinline__ float atrous_geom_weight(const AtrousPixel& p, const AtrousPixel& q, int npow, float sigma_plane)
+{
+    const bool pm = p.x.w < 0.0f, qm = q.x.w < 0.0f;
+    if (pm && qm) return 1.0f;
+    if (pm || qm) return 0.0f;
+    float wn = atrous_pos(p.n.x * q.n.x + p.n.y * q.n.y + p.n.z * q.n.z);
+    for (int k = 0; k < npow; k++) wn = wn * wn;
+    const float dx = q.x.x - p.x.x, dy = q.x.y - p.x.y, dz = q.x.z - p.x.z;
+    const float rz = __builtin_fabsf(p.n.x * dx + p.n.y * dy + p.n.z * dz) / (sigma_plane * p.x.w);
+    const float g = atrous_pos(1.0f - rz);
+    return wn * (g * g);
+}
+
 // e * wc of tap q seen from centre p (not the centre tap itself, whose e * wc is 1 by definition); sc2 = sc * sc, sc = sigma_color
 // halved once per pass
 __host__ __device__ __forceinline__ float atrous_edge_weight(const AtrousPixel& p, const AtrousPixel& q, int npow, float sigma_plane, float sc2)
 {
-    const bool pm = p.x.w < 0.0f, qm = q.x.w < 0.0f;
-    float e;
-    if (pm && qm) e = 1.0f;
-    else if (pm || qm) e = 0.0f;
-    else {
-        float wn = atrous_pos(p.n.x * q.n.x + p.n.y * q.n.y + p.n.z * q.n.z);
-        for (int k = 0; k < npow; k++) wn = wn * wn;
-        const float dx = q.x.x - p.x.x, dy = q.x.y - p.x.y, dz = q.x.z - p.x.z;
-        const float rz = __builtin_fabsf(p.n.x * dx + p.n.y * dy + p.n.z * dz) / (sigma_plane * p.x.w);
-        const float g = atrous_pos(1.0f - rz);
-        e = wn * (g * g);
-    }
+    const float e = atrous_geom_weight(p, q, npow, sigma_plane);
     const float cx = q.c.x - p.c.x, cy = q.c.y - p.c.y, cz = q.c.z - p.c.z;
     const float wc = 1.0f / (1.0f + (cx * cx + cy * cy + cz * cz) / sc2);
     return e * wc;

@@ -500,6 +500,13 @@ void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& c
                    float4* position_t, float4* normal, float4* albedo);
 void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int height, const float4* sums, float frame_count,
                    const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr);
+// jpt_denoise with jpt_set_denoise_variance on (jpt_kernels_denoise_var.hip; the arithmetic: jpt_denoise_var.h): launch_atrous' passes
+// with the colour weight measured against the variance of the mean -- also reads `m2`, the plane of jpt_set_variance, of frame_count >= 2
+// frames, and also writes `var_out`, width * height floats: the variance the last pass leaves.  sigma_color is not read.
+struct AtrousVarParams;
+void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* sums,
+                            const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
+                            float4* pong, uint32_t* ldr, float* var_out);
 
 // jpt_bake_finish (jpt_kernels_lightmap.hip; the arithmetic: jpt_lightmap.h).  The checks of jpt_set_bake_finish_params, also run by
 // jpt_debug_bake_finish; and the whole transform on `stream`: the guides (xg, ng) from the bake images, `passes` filter passes from

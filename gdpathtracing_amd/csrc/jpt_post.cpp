@@ -33,9 +33,10 @@ void PostState::framebuffers_remade(bool resized)
     bake_dir_valid = false;
     for (DevBuf<float4>* b : {&d_dn_pos, &d_dn_nrm, &d_dn_alb, &d_dn_ping, &d_dn_pong, &d_disp_f32, &d_disp_pyramid}) b->release();
     d_dn_ldr.release();
+    d_dn_var.release();
     d_disp_ldr.release();
     lightmap_release();
-    dn_valid = disp_valid = meter_valid = false;
+    dn_valid = dn_var_valid = disp_valid = meter_valid = false;
 }
 
 int reads_sum(jpt_ctx* c, const char* call, const char* what, const char* host_only, const char* whole, const char* steps)
@@ -226,24 +227,64 @@ int jpt_denoise(jpt_ctx* c)
     CamModelDev cm;   // (the guides are the first hits of the view the renders took: jpt_set_camera_model)
     const int rc_cm = view_now(c, "jpt_denoise", "the guides", cm);
     if (rc_cm != JPT_OK) return rc_cm;
-    HIP_TRY(c, hipSetDevice(c->device));
     PostState& q = c->post;
+    const bool guided = q.dn_var.enable != 0;
+    if (guided) {   // (jpt_set_denoise_variance: refused, never filtered with the fixed tolerance instead)
+        const int rc_v = variance_ready(c, "jpt_denoise with jpt_set_denoise_variance on");
+        if (rc_v != JPT_OK) return rc_v;
+        if (c->frame_count < 2)
+            return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_variance on: one frame accumulated since the last reset, and a variance needs two");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
     const size_t npx = (size_t)c->width * c->height;
     if (q.d_dn_ping.n != npx || !q.d_dn_ping.p) {
         for (DevBuf<float4>* b : {&q.d_dn_pos, &q.d_dn_nrm, &q.d_dn_alb, &q.d_dn_ping, &q.d_dn_pong}) HIP_TRY(c, b->resize(npx));
         HIP_TRY(c, q.d_dn_ldr.resize(npx));
     }
+    if (guided) HIP_TRY(c, q.d_dn_var.resize(npx));
     // On the context's stream: it is ordered behind the accumulation of every render queued so far (launch_render) and behind the
     // device refits (queue_instance_refit), and the accumulation of every later render waits for what it holds.
     hipStream_t s = c->stream;
     if (npx) {
         launch_guides(s, c->ds, c->camera, cm, c->width, c->height, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p);
-        launch_atrous(s, q.dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
-                      q.d_dn_pong.p, q.d_dn_ldr.p);
+        if (guided)
+            launch_atrous_variance(s, q.dn_params, q.dn_var, c->width, c->height, c->d_accum.p, q.d_variance.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
+                                   q.d_dn_alb.p, q.d_dn_ping.p, q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
+        else
+            launch_atrous(s, q.dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
+                          q.d_dn_pong.p, q.d_dn_ldr.p);
         HIP_TRY(c, hipGetLastError());
     }
     q.dn_valid = true;
+    q.dn_var_valid = guided;
     return JPT_OK;
+}
+
+int jpt_set_denoise_variance(jpt_ctx* c, const jpt_denoise_variance_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    AtrousVarParams p;
+    int32_t reserved = 0;
+    if (params) {
+        p.enable = params->enable;
+        p.sigma_variance = params->sigma_variance;
+        p.variance_floor = params->variance_floor;
+        reserved = params->reserved;
+    }
+    std::string why;
+    const int rc = check_denoise_variance_params(p, reserved, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
+    c->post.dn_var = p;
+    return JPT_OK;
+}
+
+int jpt_read_denoised_variance_f32(jpt_ctx* c, float* out)
+{
+    int rc = read_denoise_common(c, out != nullptr);
+    if (rc) return rc;
+    if (!c->post.dn_var_valid) return fail(c, JPT_E_STATE, "jpt_read_denoised_variance_f32: the last jpt_denoise ran without jpt_set_denoise_variance");
+    return read_out(c, c->post.d_dn_var.p, (size_t)c->width * c->height * sizeof(float), out);
 }
 
 int jpt_read_denoised_f32(jpt_ctx* c, float* out)

@@ -293,6 +293,23 @@ def debug_variance_moments(radiance, accum_mode=capi.ACCUM_HDR_F32, frame_count=
     return s, m
 
 
+def debug_atrous_variance(device_id, sum4, m2, frame_count, position_t, normal, albedo, params=None, vparams=None):
+    """jpt_debug_atrous_variance: the variance-guided filter of jpt_denoise over caller-made planes float32 [height, width, 4], on a
+    device or (device_id -1, JPT_DEVICE_HOST_ONLY) on the host -- (the denoised image float32 [height, width, 4], the variance the last
+    pass leaves float32 [height, width]).  params: a capi.DenoiseParams, vparams: a capi.DenoiseVarianceParams, or None for the defaults."""
+    arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in (sum4, m2, position_t, normal, albedo)]
+    h, w = arrays[0].shape[:2]
+    if any(a.shape != (h, w, 4) for a in arrays):
+        raise ValueError("every plane is float32 [height, width, 4]")
+    out, var = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32)
+    s, m, x, n, a = arrays
+    rc = capi.lib().jpt_debug_atrous_variance(int(device_id), w, h, None if params is None else C.byref(params), None if vparams is None else C.byref(vparams),
+                                              _ptr(s), _ptr(m), int(frame_count), _ptr(x), _ptr(n), _ptr(a), _ptr(out), _ptr(var))
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_atrous_variance failed (%d)" % rc)
+    return out, var
+
+
 def debug_noise_estimate(device_id, sum4, m2, frame_count, params=None, valid=None, **fields):
     """jpt_debug_noise_estimate: jpt_noise_estimate's pass over caller-made planes float32 [height, width, 4], on a device or
     (device_id -1, JPT_DEVICE_HOST_ONLY) on the host --(the capi.NoiseResult as a dict, hist uint32 [256], tiles float32 [ceil(h / 8), ceil(w / 8)]).
@@ -1002,6 +1019,21 @@ class Context:
     def read_denoised_ldr(self) -> np.ndarray:
         out = np.zeros((self.height, self.width, 4), dtype=np.uint8)
         self._ck(self._lib.jpt_read_denoised_rgba8(self.h, _ptr(out)), "jpt_read_denoised_rgba8")
+        return out
+
+    def set_denoise_variance(self, params: Optional[capi.DenoiseVarianceParams] = None, **fields):
+        """jpt_set_denoise_variance: a capi.DenoiseVarianceParams, or its fields by name (enable, sigma_variance, variance_floor; the
+        rest at the defaults); nothing: the defaults, the guidance off.  With it on, denoise() measures colour differences against
+        the variance plane of set_variance() and refuses without one of at least two frames."""
+        if params is None and fields:
+            params = capi.DenoiseVarianceParams(**fields)
+        self._ck(self._lib.jpt_set_denoise_variance(self.h, None if params is None else C.byref(params)), "jpt_set_denoise_variance")
+
+    def read_denoised_variance(self) -> np.ndarray:
+        """jpt_read_denoised_variance_f32: float32 [height, width], the variance of the demodulated mean a guided denoise() leaves
+        after its last pass"""
+        out = np.zeros((self.height, self.width), dtype=np.float32)
+        self._ck(self._lib.jpt_read_denoised_variance_f32(self.h, _ptr(out)), "jpt_read_denoised_variance_f32")
         return out
 
     # ---- the display transform (jpt_display)

@@ -973,6 +973,43 @@ int jpt_read_denoised_f32(jpt_ctx *ctx, float *out);       /* W*H*4 floats (r, g
 int jpt_read_denoised_rgba8(jpt_ctx *ctx, uint8_t *out);   /* W*H*4 bytes: unorm8(ACES(denoised)), alpha 255 */
 int jpt_read_guides_f32(jpt_ctx *ctx, float *position_t, float *normal, float *albedo);   /* each W*H*4 floats, or NULL */
 
+/* ---- variance guidance of jpt_denoise (no reference counterpart; the colour weight of SVGF, Schied et al. 2017) ------------------
+ * A fixed colour tolerance cannot tell noise from signal: it blurs a shadow edge on a flat wall, where no guide has an edge, and it
+ * biases an image that is already clean.  With the guidance on, jpt_denoise measures colour differences against the variance of the
+ * mean, from the plane of jpt_set_variance (below), instead of against sigma_color.  Off, the default, jpt_denoise launches what it
+ * launches without this section, and every output is bit for bit the same.  The arithmetic is pinned in DESIGN.md section 2
+ * (gdpathtracing_amd/csrc/jpt_denoise_var.h; tests/np_denoise_var.py restates it bit for bit); every operation is one binary32
+ * operation in the order written.  With nf = (float)frame_count, q = nf * (nf - 1), a = max(albedo, 1/64) per channel:
+ *   first       i_0 = (accum / nf) / a;  v_0 = m2.r / q / (a.r * a.r) + m2.g / q / (a.g * a.g) + m2.b / q / (a.b * a.b), left to right; a
+ *               v_0 that is not finite or not > 0 is +0.  It is the variance of the demodulated mean summed over the channels, as
+ *               |dc|^2 below is a sum over the channels.  Pass k carries (i_k, v_k).
+ *   per pass    gv = the 3 x 3 binomial (1 2 1)/4 x (1 2 1)/4 of v_k around the pixel, tap spacing 1 in every pass, over the taps
+ *               inside the image, divided by the sum of the weights used;  den = (sigma_variance * sigma_variance) * gv +
+ *               variance_floor;  the colour weight of tap q is 1 / (1 + |c_q - c_p|^2 / den) -- den is not halved per pass, the
+ *               shrinking v_k does that -- and everything else is jpt_denoise's: the geometric weight, the binomial taps and their
+ *               order, a tap of weight 0 is not multiplied, the rules for colours that are not finite.
+ *               i_k+1 = sum wt c_q / sum wt;  v_k+1 = sum (wt * wt) v_q / (sum wt * sum wt).  A centre whose colour is not finite
+ *               keeps its colour and its v.
+ *   last        the denoised image (i * a, 1) and its rgba8 image as without the guidance -- jpt_display, jpt_meter and jpt_encode
+ *               read them as they read jpt_denoise's -- and v of the last pass in a plane of its own (4 B per pixel, in demodulated
+ *               units, allocated by the first guided jpt_denoise at a resolution): jpt_read_denoised_variance_f32.
+ * The parameters are the context's, as jpt_set_denoise_params': they survive scene changes and jpt_scene_share does not copy them.
+ * JPT_E_INVALID: enable not 0 or 1, a sigma_variance or variance_floor that is not finite or not > 0, reserved != 0.  With the
+ * guidance on jpt_denoise answers JPT_E_STATE -- it never falls back to the fixed tolerance -- when the variance plane is switched
+ * off (jpt_set_variance), when no render has written it at the current size, and when fewer than two frames are accumulated; it is
+ * otherwise ordered on the stream as without the guidance, READS the accumulation, the frame count and the plane and writes only its
+ * own images.  jpt_read_denoised_variance_f32: JPT_E_STATE unless the last jpt_denoise at the current resolution was a guided one.
+ * Host-only contexts: JPT_E_DEVICE.  Not covered: jpt_bake_finish, a temporal component, a partition or jpt_multi, a jpt_encode
+ * source for the variance image, per-channel variance. */
+typedef struct jpt_denoise_variance_params {
+    int32_t enable;          /* 0 or 1, default 0 */
+    float   sigma_variance;  /* finite, > 0, default 2.0: colour tolerance in standard deviations of the mean */
+    float   variance_floor;  /* finite, > 0, default 1e-6: added to the scaled variance, so that a clean pixel still has a tolerance */
+    int32_t reserved;        /* 0 */
+} jpt_denoise_variance_params;
+int jpt_set_denoise_variance(jpt_ctx *ctx, const jpt_denoise_variance_params *params);   /* NULL: the defaults */
+int jpt_read_denoised_variance_f32(jpt_ctx *ctx, float *out);                            /* W*H floats: v of the last pass */
+
 /* ---- the display transform: exposure, bloom, selectable tone mapping (no reference counterpart; the reference lists "simple post
  * processing (e.g. bloom, controllable tone-mapping)" among its wanted features) ------------------------------------------------
  * A graded display image from the progressive accumulation or from jpt_denoise's image, as an explicit call: nothing runs unless
@@ -1197,7 +1234,7 @@ int jpt_set_auto_exposure(jpt_ctx *ctx, int32_t enable);                  /* def
  * off, no render with it on at the current size.  jpt_read_noise / jpt_read_noise_tiles_f32 before a jpt_noise_estimate at the current
  * size: JPT_E_STATE.  jpt_render_converge: an argument <= 0 is JPT_E_INVALID; otherwise the refusals of the calls it makes.
  * Host-only contexts: JPT_E_DEVICE.  There is no jpt_multi_* form.
- * Not covered: adaptive sampling (skipping converged tiles would edit the primary launch), variance-guided weights in jpt_denoise,
+ * Not covered: adaptive sampling (skipping converged tiles would edit the primary launch),
  * jpt_multi and an estimate under a partition, a jpt_encode source for the plane, the reference-layout kernel, per-channel covariance. */
 enum { JPT_NOISE_EMPTY = 1, JPT_NOISE_CONVERGED = 2 };       /* jpt_noise_result.flags */
 typedef struct jpt_noise_params {
@@ -1561,6 +1598,15 @@ int jpt_debug_variance_moments(const float *radiance3, int32_t n_frames, uint32_
 int jpt_debug_noise_estimate(int device_id, int32_t width, int32_t height, const jpt_noise_params *params, const float *sum4,
                              const float *m2_4, uint32_t frame_count, const uint8_t *valid_or_null, uint32_t *hist256_out,
                              float *tiles_out, jpt_noise_result *result_out);
+/* The filter of jpt_denoise with jpt_set_denoise_variance on, alone, on caller-made images of width x height pixels, 4 floats per
+ * pixel each: sum4 the accumulation and m2_4 the plane of jpt_set_variance of frame_count >= 2 frames, the three guide images, out4 =
+ * the denoised image (r, g, b, 1); var_out = width * height floats, v of the last pass.  params and vparams NULL: the defaults;
+ * checked as their setters check them; vparams->enable is checked and otherwise ignored (JPT_E_INVALID, also for frame_count < 2;
+ * this call leaves no message).  device_id >= 0: the kernels the guided jpt_denoise launches, on that device;
+ * JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
+int jpt_debug_atrous_variance(int device_id, int32_t width, int32_t height, const jpt_denoise_params *params,
+                              const jpt_denoise_variance_params *vparams, const float *sum4, const float *m2_4, uint32_t frame_count,
+                              const float *position_t, const float *normal, const float *albedo, float *out4, float *var_out);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

@@ -948,6 +948,9 @@ class PathTracingCamera {
         return out;
     }
     void read_denoised(float* out) { check(ctx, jpt_read_denoised_f32(ctx, out), "jpt_read_denoised_f32"); }
+    // the variance guidance of jpt_denoise (nullptr: the defaults, off); on, denoise() needs set_variance(true) and two frames
+    void set_denoise_variance(const jpt_denoise_variance_params* params) { check(ctx, jpt_set_denoise_variance(ctx, params), "jpt_set_denoise_variance"); }
+    void read_denoised_variance(float* out) { check(ctx, jpt_read_denoised_variance_f32(ctx, out), "jpt_read_denoised_variance_f32"); }
     // jpt_display and its parameters (nullptr: the defaults): exposure, bloom, tone map and transfer over the accumulation or over
     // jpt_denoise's image
     void set_display_params(const jpt_display_params* params) { check(ctx, jpt_set_display_params(ctx, params), "jpt_set_display_params"); }
