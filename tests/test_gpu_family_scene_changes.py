@@ -1,0 +1,651 @@
+"""The primary-ray families other than the pinhole -- the thin lens, the orthographic and equirect camera models, bake renders from
+surface texels, light-probe tiles and reflection-probe cubes -- across every way a scene changes under a live context:
+jpt_scene_update_tlas, a non-rigid jpt_scene_refit_tlas, jpt_scene_update_mesh, jpt_scene_pose_mesh, a second jpt_scene_commit with
+another triangle and instance count, jpt_scene_share, and queues of renders and changes with no read-back in between.  What is read
+back is the accumulation, the depth and the family's post-stage outputs: the display image, the directional planes, the variance
+plane and the finished lightmap of a bake, jpt_probe_project's coefficients, jpt_reflection_prefilter's last level.
+
+Yardsticks.  (a) A FRESH context committed in the final state through the family's own file's helper (test_gpu_camera.make_ctx,
+test_gpu_bake.bake_ctx, test_gpu_probe.probe_ctx, test_gpu_reflection.cube_ctx): every array equal bit for bit, NaN matching NaN.
+A device refit is compared on JPT_BUILD_SAH_WATERTIGHT, for which test_gpu_mesh_update.py, test_gpu_skin.py and the refits of
+test_gpu_light_scene_changes.py / test_gpu_tx_scene_changes.py establish that a refit and a new build give the same bits.  (b) The
+numpy whole-path restatement over the oracle's build of the starting and of the final scene (changes 1 and 3, HDR, gradient sky).
+(c) Every case asserts that the change moved the accumulation and a post-stage output.  (d) The post-stage outputs of the changed
+context equal their numpy restatements applied to what that context read back.
+
+Camera families render 48 x 32; the bake 33 x 17 (test_bake_host.atlas); two light probes of 8 x 4 cells, three to a row (24 x 4, the
+third tile without a probe); two reflection probes of face size 4, three to a row (72 x 4, the third strip without a probe).  2 frames,
+3 bounces; the gradient sky, and sun_map() with both kinds of MIS (the cubes: the map alone, as in test_gpu_reflection.py)."""
+import copy
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from gdpathtracing_amd import capi, host, scenes
+
+import np_bake as nb
+import np_bake_dir as nbd
+import np_camera as nc
+import np_lens as nlens
+import np_lightmap as nl
+import np_probe as npb
+import np_reflection as nrf
+import np_skin
+import np_variance as nv
+from test_bake_host import atlas, atlas_scene
+from test_gpu_bake import bake_ctx
+from test_gpu_camera import make_ctx
+from test_gpu_light_scene_changes import all_transforms, pose as light_pose, with_transform
+from test_gpu_mesh_update import deform, with_mesh
+from test_gpu_probe import POSITIONS as PROBE_POSITIONS, probe_ctx
+from test_gpu_reflection import POSITIONS as CUBE_POSITIONS, cube_ctx, np_chain_level
+from test_gpu_skin import TUBE, host_rigs, pose as skin_pose, small_scene, tube_rigs
+from test_gpu_transmission import sun_map
+from test_gpu_tx_scene_changes import LENS
+from test_probe_host import TILES
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+E_STATE = -4   # JPT_E_STATE
+FRAMES, BOUNCES = 2, 3
+WF, AUDIT = capi.KERNEL_WAVEFRONT, capi.KERNEL_REFERENCE_LAYOUT
+KERNELS = (WF, AUDIT)
+HDR, LDR8 = capi.ACCUM_HDR_F32, capi.ACCUM_REF_LDR8
+SAH, WATERTIGHT = capi.BUILD_SAH, capi.BUILD_SAH_WATERTIGHT
+
+CAMERAS = ("lens", "ortho", "equirect")
+FAMILIES = CAMERAS + ("bake", "probe", "cube")
+MODEL = {"ortho": capi.CAMERA_PROJECTIVE, "equirect": capi.CAMERA_EQUIRECT}
+ON_THE_ATLAS = ("bake", "probe")            # these trace test_bake_host.atlas_scene, the others Cornell's box
+ACCUM = {"lens": LDR8, "ortho": LDR8, "equirect": LDR8, "bake": HDR, "probe": HDR, "cube": HDR}
+LIGHTINGS = {f: ("sky", "map" if f == "cube" else "map_mis_emitters") for f in FAMILIES}
+CASES = [pytest.param(f, l, id="%s-%s" % (f, l)) for f in FAMILIES for l in LIGHTINGS[f]]
+
+TILE = min(TILES)                              # 8 x 4 cells
+PROBES = PROBE_POSITIONS[[1, 4]].copy()        # beside the hanging box, and just above the floor
+CUBES = CUBE_POSITIONS[:2].copy()              # over Cornell's short block
+PER_ROW = 3                                    # two probes, three to a row: the last tile (strip) has no probe
+FACE, LEVELS, SAMPLES = 4, 3, 16
+POST = {"lens": ("display",), "ortho": ("display",), "equirect": ("display",), "bake": ("directional", "variance", "lightmap"),
+        "probe": ("sh",), "cube": ("chain",)}
+
+
+def size(family):
+    if family in CAMERAS:
+        return 48, 32
+    if family == "bake":
+        return 33, 17
+    if family == "probe":
+        return npb.image_size(len(PROBES), TILE[0], TILE[1], PER_ROW)
+    return nrf.image_size(len(CUBES), FACE, PER_ROW)
+
+
+def texels():
+    _, p4, n4 = atlas(33, 17)
+    return p4, n4
+
+
+# ---- the scenes -----------------------------------------------------------------------------------------------------------------------
+
+class Stage:
+    """a starting scene and what moves in it: `box` the instance that is moved, `box_mesh` its mesh (no other instance names it),
+    `tube_mesh` the skinned tube of test_gpu_skin.small_scene (None without it)"""
+
+    def __init__(self, scene, box, box_mesh, tube_mesh):
+        self.scene, self.box, self.box_mesh, self.tube_mesh = scene, box, box_mesh, tube_mesh
+
+
+def stage(family, tube=True):
+    """Cornell's box (its short block moves), or the bakes' atlas scene (its hanging box, which carries atlas texels, moves); the tube
+    lies in front of the blocks / over the floor beside the lower probe.  Both scenes have emitters, and nothing that emits is moved
+    or deformed: a fresh build of a deformed emissive mesh orders the emitter tables by its own tree, so under light sampling it
+    draws other samples than the refit (test_gpu_skin.py compares that case with jpt_scene_update_mesh, test_gpu_tx_scene_changes.py
+    scales by a power of two); the tables across scene changes are test_gpu_light_scene_changes.py's subject.  The panorama is taken from
+    inside Cornell's box, the blocks and the tube around it: from the pinhole's place the box fills a few pixels of it."""
+    if family in ON_THE_ATLAS:
+        sc, _ = atlas_scene()
+        at, turn, materials = (0.5, -1.4, 1.5), 40.0, [0, 2]
+    else:
+        sc = scenes.cornell_scene()
+        at, turn, materials = (-0.2, -0.6, 1.6), 30.0, [3, 2]
+        if family == "equirect":
+            sc.camera = scenes.CameraDesc(scenes.transform12(scenes.rot_y(25.0), (0.2, -0.3, 2.6)))
+    sc.meshes, sc.instances = list(sc.meshes), list(sc.instances)
+    box = len(sc.instances) - 1 if family in ON_THE_ATLAS else 2
+    box_mesh = sc.instances[box].mesh
+    assert sum(1 for i in sc.instances if i.mesh == box_mesh) == 1
+    if not tube:
+        return Stage(sc, box, box_mesh, None)
+    assert not sc.materials["emission"][materials][:, :3].any()
+    sc.meshes.append(small_scene().meshes[TUBE])
+    sc.instances.append(scenes.Instance(len(sc.meshes) - 1, scenes.transform12(scenes.rot_y(turn), at), materials))
+    return Stage(sc, box, box_mesh, len(sc.meshes) - 1)
+
+
+def box_pose(st, k):
+    """test_gpu_light_scene_changes.pose, which moves and stretches instance 0, applied to the box: non-rigid for every k > 0"""
+    view = copy.copy(st.scene)
+    view.instances = [st.scene.instances[st.box]]
+    return light_pose(view, k)
+
+
+def box_moved(st, k):
+    return with_transform(st.scene, st.box, box_pose(st, k))
+
+
+def box_deformed(st, k):
+    """test_gpu_mesh_update.deform: a wobble, and the x > 0 half pushed out of the committed boxes"""
+    new = deform(st.scene.meshes[st.box_mesh], k)
+    return new, with_mesh(st.scene, st.box_mesh, new)
+
+
+# ---- the per-render state and what is read back ---------------------------------------------------------------------------------------
+
+def set_planes(ctx, family, on):
+    if family == "bake":
+        ctx.set_bake_directional(on)
+        ctx.set_variance(on)
+
+
+def prepare(ctx, scene, family, lighting, accum=None):
+    """the per-render state, on a context that got or will get its scene some way: test_gpu_camera.make_ctx's, then the family's"""
+    w, h = size(family)
+    ctx.set_params(w, h, BOUNCES, ACCUM[family] if accum is None else accum)
+    ctx.set_camera(scenes.camera_block(scene.camera, w, h))
+    if lighting.startswith("map"):
+        ctx.set_environment(sun_map())
+        if "mis" in lighting:
+            ctx.set_environment_sampling(capi.ENV_SAMPLING_MIS)
+    if "emitters" in lighting:
+        ctx.set_light_sampling(capi.LIGHT_SAMPLING_MIS)
+    if family == "lens":
+        ctx.set_lens(*LENS)
+    elif family in MODEL:
+        ctx.set_camera_model(MODEL[family])
+    elif family == "bake":
+        ctx.set_bake_texels(*texels())
+        set_planes(ctx, family, True)
+    elif family == "probe":
+        ctx.set_probes(PROBES, TILE[0], TILE[1], PER_ROW)
+    else:
+        ctx.set_reflection_probes(CUBES, FACE, PER_ROW)
+        ctx.set_reflection_params(n_levels=LEVELS, samples=SAMPLES)
+
+
+def ctx_for(scene, family, lighting, builder=SAH, accum=None):
+    """the context under test: committed, then prepared"""
+    ctx = host.Context(0)
+    try:
+        ctx.build_scene(scene, builder)
+        prepare(ctx, scene, family, lighting, accum)
+    except Exception:
+        ctx.close()
+        raise
+    return ctx
+
+
+def fresh_ctx(scene, family, lighting, builder=SAH, kernel=WF, accum=None, planes=True):
+    """the yardstick's context: made by the helper of the family's own file"""
+    w, h = size(family)
+    kw = dict(builder=builder, accum=ACCUM[family] if accum is None else accum, bounces=BOUNCES, kernel=kernel, lighting=lighting)
+    if family in CAMERAS:
+        ctx = make_ctx(scene, None, w, h, model=MODEL.get(family), **kw)
+    elif family == "bake":
+        ctx = bake_ctx(scene, *texels(), **kw)
+    elif family == "probe":
+        ctx = probe_ctx(scene, TILE, positions=PROBES, per_row=PER_ROW, **kw)
+    else:
+        ctx = cube_ctx(scene, s=FACE, positions=CUBES, per_row=PER_ROW, **kw)
+    try:
+        if family == "lens":
+            ctx.set_lens(*LENS)
+        elif family == "bake":
+            set_planes(ctx, family, planes)
+        elif family == "cube":
+            ctx.set_reflection_params(n_levels=LEVELS, samples=SAMPLES)
+    except Exception:
+        ctx.close()
+        raise
+    return ctx
+
+
+def read_back(ctx, family, planes=True):
+    """what a render left, and the post stages run over it"""
+    out = {"accumulation": ctx.read_accum(), "depth": ctx.read_depth()}
+    if family in CAMERAS:
+        out["display"] = ctx.read_ldr()
+    elif family == "bake":
+        if planes:
+            out["directional"], out["variance"] = ctx.read_bake_directional(), ctx.read_variance()
+        ctx.bake_finish()
+        out["lightmap"] = ctx.read_lightmap()
+    elif family == "probe":
+        ctx.probe_project(capi.PROBE_IRRADIANCE)
+        out["sh"] = ctx.read_probe_sh()
+    else:
+        ctx.reflection_prefilter()
+        out["chain"] = ctx.read_reflection(LEVELS - 1)
+    return out
+
+
+def state(ctx, family, kernel=WF):
+    """(the audit kernel keeps no per-frame values: it is refused with the bake's planes on, so they are off for its render)"""
+    planes = kernel == WF
+    if not planes:
+        set_planes(ctx, family, False)
+    try:
+        ctx.set_kernel(kernel)
+        ctx.accum_reset()
+        ctx.render(FRAMES, 1)
+        return read_back(ctx, family, planes)
+    finally:
+        if not planes:
+            ctx.set_kernel(WF)
+            set_planes(ctx, family, True)
+
+
+def fresh_state(scene, family, lighting, builder=SAH, kernel=WF):
+    ctx = fresh_ctx(scene, family, lighting, builder, kernel, planes=kernel == WF)
+    try:
+        return state(ctx, family, kernel)
+    finally:
+        ctx.close()
+
+
+def differing(a, b):
+    """how many values differ: bit for bit, NaN matching NaN"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.shape == b.shape and a.dtype == b.dtype, (a.shape, b.shape, a.dtype, b.dtype)
+    if a.dtype == F:
+        return int((~((a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b)))).sum())
+    return int((a != b).sum())
+
+
+def assert_state(got, want, what):
+    assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+    n = {name: differing(got[name], want[name]) for name in sorted(got)}
+    print("%s: values differing from the yardstick: %s" % (what, n))
+    assert not any(n.values()), "%s: values differing from the yardstick: %s" % (what, n)
+
+
+def assert_moved(after, before, family, what):
+    """the sensitivity of a case: the change moved the accumulation and at least one post-stage output"""
+    n = {name: differing(after[name], before[name]) for name in ("accumulation",) + POST[family]}
+    print("%s moved: %s" % (what, n))
+    assert n["accumulation"] > 0 and any(n[name] > 0 for name in POST[family]), "%s moved nothing: %s" % (what, n)
+
+
+def device_frames(ctx, first, n=FRAMES, planes_of=None):
+    """the values of frames first .. first + n - 1 as the accumulation adds them: one-frame renders after a reset.  planes_of: the
+    family of a context under test, whose bake planes are off for these renders (the render path without their kernels) and on again
+    afterwards.  [n, H, W, 3]"""
+    set_planes(ctx, planes_of, False)
+    out = []
+    for f in range(n):
+        ctx.accum_reset()
+        ctx.render(1, first + f)
+        out.append(ctx.read_accum()[..., :3].copy())
+    set_planes(ctx, planes_of, True)
+    return out
+
+
+def np_continue(acc, frames, ldr8):
+    """the accumulation `acc` (None: none yet, the first frame overwrites) continued by `frames`, as wf2_accumulate adds them"""
+    acc = None if acc is None else np.array(acc[..., :3], F)
+    with np.errstate(all="ignore"):
+        for cur in frames:
+            cur = nv.frame_value(cur, ldr8)[..., :3]
+            acc = cur.copy() if acc is None else (cur + acc).astype(F)
+    return acc
+
+
+def assert_post(ctx, got, family, what, n_frames=FRAMES, frames=None):
+    """the post-stage outputs in `got` equal their numpy restatements over what the context read back; frames: the per-frame values
+    behind got's accumulation (None: read from `ctx` by one-frame renders)"""
+    accum = got["accumulation"]
+    if family == "probe":
+        table = host.debug_probe_basis(TILE[0], TILE[1], capi.PROBE_IRRADIANCE)
+        want = npb.project(accum, n_frames, len(PROBES), TILE[0], TILE[1], PER_ROW, table)
+        assert got["sh"].shape == (len(PROBES), 9, 4) and differing(got["sh"], want) == 0, "%s: jpt_probe_project" % what
+        assert (got["sh"][:, 0, :3] > 0).all()
+    elif family == "cube":
+        want = np_chain_level(accum, n_frames, len(CUBES), FACE, PER_ROW, LEVELS, SAMPLES, LEVELS - 1)
+        assert got["chain"].shape == (len(CUBES), 6, 1, 1, 4) and differing(got["chain"], want) == 0, "%s: jpt_reflection_prefilter" % what
+        assert (got["chain"][..., :3] > 0).any()
+    elif family == "bake":
+        p4, n4 = texels()
+        with np.errstate(all="ignore"):
+            mean = (accum / F(n_frames)).astype(F)
+        assert nl.same_bits(got["lightmap"], nl.finish(mean, p4, n4)).all(), "%s: jpt_bake_finish" % what
+        if frames is None:
+            frames = device_frames(ctx, 1, n_frames, planes_of=family)
+        s, m2 = nv.moments(frames, False)
+        assert differing(accum[..., :3], s) == 0, "%s: the accumulation against its frames" % what
+        assert differing(got["variance"], nv.plane(m2)) == 0, "%s: the variance plane" % what
+        assert differing(got["directional"], nbd.moments(p4, n4, frames, 1, False)) == 0, "%s: the directional planes" % what
+        valid = nb.texel_valid(n4)
+        assert not valid.all() and (got["variance"][valid][:, :3] > 0).any() and (got["directional"][:, valid][..., :3] != 0).any()
+
+
+def assert_audit_refused(ctx, family, word):
+    """validate_render's refusal of the audit kernel, in this family too (the bake's planes off: they refuse that kernel on their own)"""
+    set_planes(ctx, family, False)
+    ctx.set_kernel(AUDIT)
+    try:
+        for call in (ctx._lib.jpt_render, ctx._lib.jpt_render_async):
+            assert call(ctx.h, 1, 1) == E_STATE
+            assert word in ctx._lib.jpt_last_error(ctx.h), ctx._lib.jpt_last_error(ctx.h)
+    finally:
+        ctx.set_kernel(WF)
+        set_planes(ctx, family, True)
+
+
+# ---- 1. jpt_scene_set_instance_transform + jpt_scene_update_tlas ----------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_update_tlas_equals_a_fresh_commit(hiplib, family, lighting):
+    st = stage(family)
+    sc2 = box_moved(st, 1)
+    ctx = ctx_for(st.scene, family, lighting)
+    try:
+        before = state(ctx, family)
+        ctx.set_instance_transform(st.box, sc2.instances[st.box].transform)
+        ctx.update_tlas()
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting), "update_tlas")
+        assert_moved(after, before, family, "update_tlas")
+        assert_post(ctx, after, family, "update_tlas")
+        assert_state(state(ctx, family, AUDIT), fresh_state(sc2, family, lighting, kernel=AUDIT), "update_tlas, audit kernel")
+    finally:
+        ctx.close()
+
+
+# ---- 2. a non-rigid jpt_scene_refit_tlas ----------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_refit_tlas_equals_a_fresh_commit_and_refuses_the_audit_kernel(hiplib, family, lighting):
+    st = stage(family)
+    sc2 = box_moved(st, 2)
+    ctx = ctx_for(st.scene, family, lighting, WATERTIGHT)
+    try:
+        before = state(ctx, family)
+        ctx.refit_tlas(all_transforms(sc2))
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting, WATERTIGHT), "refit_tlas")
+        assert_moved(after, before, family, "refit_tlas")
+        assert_post(ctx, after, family, "refit_tlas")
+        assert_audit_refused(ctx, family, b"jpt_scene_refit_tlas")
+        assert_state(state(ctx, family), after, "refit_tlas, after the refused renders")
+        ctx.update_tlas()   # brings the other kernel's records up to date
+        assert_state(state(ctx, family, AUDIT), fresh_state(sc2, family, lighting, WATERTIGHT, AUDIT), "refit_tlas + update_tlas, audit kernel")
+        assert_state(state(ctx, family), after, "refit_tlas + update_tlas")
+    finally:
+        ctx.close()
+
+
+# ---- 3. jpt_scene_update_mesh ---------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_update_mesh_equals_a_fresh_commit_and_refuses_the_audit_kernel(hiplib, family, lighting):
+    st = stage(family)
+    new, sc2 = box_deformed(st, 2)
+    ctx = ctx_for(st.scene, family, lighting, WATERTIGHT)
+    try:
+        before = state(ctx, family)
+        ctx.update_mesh(st.box_mesh, new, with_normals=True)
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting, WATERTIGHT), "update_mesh")
+        assert_moved(after, before, family, "update_mesh")
+        assert_post(ctx, after, family, "update_mesh")
+        assert_audit_refused(ctx, family, b"jpt_scene_update_mesh")
+        assert_state(state(ctx, family), after, "update_mesh, after the refused renders")
+    finally:
+        ctx.close()
+
+
+# ---- 4. jpt_scene_set_mesh_rig + jpt_scene_pose_mesh, then jpt_scene_clear_mesh_rig ---------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_pose_mesh_equals_a_fresh_commit_and_outlives_its_rig(hiplib, family, lighting):
+    st = stage(family)
+    bind = st.scene.meshes[st.tube_mesh]
+    rigs = tube_rigs(bind)
+    pal, bw = skin_pose(1)
+    sc2 = with_mesh(st.scene, st.tube_mesh, np_skin.skin_mesh(bind, rigs, 4, pal, bw))
+    ctx = ctx_for(st.scene, family, lighting, WATERTIGHT)
+    try:
+        before = state(ctx, family)
+        ctx.set_mesh_rig(st.tube_mesh, bind, host_rigs(rigs), 4, 2)
+        assert_state(state(ctx, family), before, "set_mesh_rig alone")
+        ctx.pose_mesh(st.tube_mesh, pal, bw)
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting, WATERTIGHT), "pose_mesh")
+        assert_moved(after, before, family, "pose_mesh")
+        assert_post(ctx, after, family, "pose_mesh")
+        ctx.clear_mesh_rig(st.tube_mesh)
+        with pytest.raises(capi.JptError, match="no rig"):
+            ctx.pose_mesh(st.tube_mesh, pal, bw)
+        assert_state(state(ctx, family), after, "clear_mesh_rig: the pose stays")
+        assert_audit_refused(ctx, family, b"jpt_scene_update_mesh")
+    finally:
+        ctx.close()
+
+
+# ---- 5. a second jpt_scene_commit -----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_second_commit_keeps_the_family_state_and_continues_the_accumulation(hiplib, family, lighting):
+    """the family's state is set before the second commit and not again; the second scene has the tube (502 triangles and an instance
+    more) and the box elsewhere.  A commit does not reset the accumulation of a pinhole render, nor this one: the first render after it
+    continues the sum, which is restated from the first scene's accumulation and the second scene's own frames."""
+    first_stage, second_stage = stage(family, tube=False), stage(family)
+    sc1, sc2 = first_stage.scene, box_moved(second_stage, 3)
+    assert len(sc1.instances) != len(sc2.instances) and sum(m.n_tris for m in sc1.meshes) != sum(m.n_tris for m in sc2.meshes)
+    ldr8 = ACCUM[family] == LDR8
+    ctx = ctx_for(sc1, family, lighting)
+    try:
+        first = state(ctx, family)
+        assert_state(first, fresh_state(sc1, family, lighting), "first commit")
+        ctx.build_scene(sc2, SAH)
+        ctx.render(FRAMES, FRAMES + 1)                      # no reset, nothing set again
+        continued = ctx.read_accum()
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting), "second commit")
+        assert_moved(after, first, family, "second commit")
+        assert_post(ctx, after, family, "second commit")
+        assert_state(state(ctx, family, AUDIT), fresh_state(sc2, family, lighting, kernel=AUDIT), "second commit, audit kernel")
+        other = fresh_ctx(sc2, family, lighting, planes=False)
+        try:
+            frames = device_frames(other, FRAMES + 1)
+        finally:
+            other.close()
+        n = differing(continued[..., :3], np_continue(first["accumulation"], frames, ldr8))
+        assert n == 0, "the accumulation continued across the commit differs from its restatement at %d values" % n
+    finally:
+        ctx.close()
+
+
+# ---- 6. jpt_scene_share ---------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_share_into_a_prepared_context(hiplib, family, lighting):
+    """everything set on the receiving context before it has a scene, nothing afterwards; the source's later commit leaves it alone"""
+    st = stage(family)
+    sc2 = box_moved(st, 1)
+    src = ctx_for(sc2, family, lighting)
+    dst = host.Context(0)
+    try:
+        prepare(dst, sc2, family, lighting)
+        dst.share_scene_from(src)
+        shared = state(dst, family)
+        assert_state(shared, fresh_state(sc2, family, lighting), "shared scene")
+        assert_post(dst, shared, family, "shared scene")
+        assert_state(state(dst, family, AUDIT), fresh_state(sc2, family, lighting, kernel=AUDIT), "shared scene, audit kernel")
+        src.build_scene(st.scene, SAH)
+        theirs = state(src, family)
+        assert_state(theirs, fresh_state(st.scene, family, lighting), "the source after its commit")
+        assert_moved(theirs, shared, family, "the source's commit")
+        assert_state(state(dst, family), shared, "shared scene after the source's commit")
+    finally:
+        src.close()
+        dst.close()
+
+
+# ---- 7. queues with no read-back in between ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("lighting", ["sky", "map_mis_emitters"])
+@pytest.mark.parametrize("change", ["refit_tlas", "update_mesh"])
+@pytest.mark.parametrize("family", ["bake", "probe"])
+def test_queued_renders_around_a_change_each_see_their_own_scene(hiplib, family, change, lighting):
+    """render, change, render, change back, render: all queued, one sync at the end.  A second context makes the same calls blocking,
+    frame by frame with a reset before each: the values every queued frame must have contributed.  The sum, the last depth and the
+    post-stage outputs (the bake's extra kernels read per-frame values) are restated from those."""
+    st = stage(family)
+    if change == "refit_tlas":
+        sc2 = box_moved(st, 2)
+        steps = [lambda c: None, lambda c: c.refit_tlas(all_transforms(sc2)), lambda c: c.refit_tlas(all_transforms(st.scene))]
+    else:
+        new, _ = box_deformed(st, 2)
+        steps = [lambda c: None, lambda c: c.update_mesh(st.box_mesh, new, with_normals=True),
+                 lambda c: c.update_mesh(st.box_mesh, st.scene.meshes[st.box_mesh], with_normals=True)]
+    queued = ctx_for(st.scene, family, lighting, WATERTIGHT, HDR)
+    blocking = fresh_ctx(st.scene, family, lighting, WATERTIGHT, accum=HDR, planes=False)
+    try:
+        for k, step in enumerate(steps):
+            step(queued)
+            queued.render(FRAMES, 1 + FRAMES * k, asynchronous=True)
+        queued.sync()
+        got = read_back(queued, family)
+        frames = []
+        for k, step in enumerate(steps):
+            step(blocking)
+            frames += device_frames(blocking, 1 + FRAMES * k)
+        depth = blocking.read_depth()
+        unchanged = device_frames(blocking, 1 + FRAMES)     # the second render's frames had nothing changed
+    finally:
+        queued.close()
+        blocking.close()
+    n = differing(got["accumulation"][..., :3], np_continue(None, frames, False))
+    assert n == 0, "queued %s: the sum differs from the blocking frames' at %d values" % (change, n)
+    assert differing(got["depth"], depth) == 0
+    assert_post(None, got, family, "queued %s" % change, n_frames=len(frames), frames=frames)
+    assert sum(differing(a, b) for a, b in zip(frames[FRAMES:2 * FRAMES], unchanged)) > 0, "the change moved nothing"
+
+
+def test_two_pipeline_slots_give_the_same_queues(hiplib):
+    """JPT_PIPE_SLOTS is read once per process: a fresh child process runs the queued cases under two slots (tests/test_gpu_variance.py
+    sets JPT_GROUPS the same way)"""
+    env = dict(os.environ)
+    env["JPT_PIPE_SLOTS"] = "2"
+    p = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-k", "test_queued_renders_around_a_change and sky"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-3000:]
+    assert "4 passed" in p.stdout and "failed" not in p.stdout
+
+
+# ---- 8. what was finished before a change stays readable ----------------------------------------------------------------------------------
+
+def finished(ctx, family):
+    """the post stages' outputs as they lie in the context: nothing is rendered or run"""
+    if family == "bake":
+        return {"directional": ctx.read_bake_directional(), "variance": ctx.read_variance(), "lightmap": ctx.read_lightmap()}
+    if family == "probe":
+        return {"sh": ctx.read_probe_sh()}
+    return {"chain": ctx.read_reflection(LEVELS - 1)}
+
+
+@pytest.mark.parametrize("family", ["bake", "probe", "cube"])
+def test_finished_outputs_stay_readable_across_scene_changes(hiplib, family):
+    """a scene change neither drops nor rewrites what the post stages made of the last render ("Deforming meshes"): the
+    planes, the lightmap, the coefficients and the chain hold that render until the next render or post-stage call"""
+    st = stage(family)
+    new, _ = box_deformed(st, 2)
+    rigs = tube_rigs(st.scene.meshes[st.tube_mesh])
+    ctx = ctx_for(st.scene, family, "sky", WATERTIGHT)
+    try:
+        want = {name: got for name, got in state(ctx, family).items() if name in POST[family]}
+        accum = ctx.read_accum()
+        changes = [("set_instance_transform + update_tlas", lambda: (ctx.set_instance_transform(st.box, box_pose(st, 1)), ctx.update_tlas())),
+                   ("refit_tlas", lambda: ctx.refit_tlas(all_transforms(box_moved(st, 2)))),
+                   ("update_mesh", lambda: ctx.update_mesh(st.box_mesh, new, with_normals=True)),
+                   ("pose_mesh", lambda: (ctx.set_mesh_rig(st.tube_mesh, st.scene.meshes[st.tube_mesh], host_rigs(rigs), 4, 2),
+                                          ctx.pose_mesh(st.tube_mesh, *skin_pose(1)))),
+                   ("a second commit", lambda: ctx.build_scene(stage(family, tube=False).scene, SAH))]
+        for what, change in changes:
+            change()
+            assert_state(finished(ctx, family), want, "after %s, before the next render" % what)
+            assert differing(ctx.read_accum(), accum) == 0, what
+        after = state(ctx, family)
+        assert_moved(after, dict(want, accumulation=accum), family, "the render after the changes")
+    finally:
+        ctx.close()
+
+
+# ---- the library-independent anchor -----------------------------------------------------------------------------------------------------
+
+_REFERENCE = {}
+
+
+def reference(oracle, family, which):
+    """(scene, the two frames, the last frame's depth) by the numpy whole-path restatement over the oracle's build, under the gradient
+    sky; which: "start", "moved" (change 1) or "deformed" (change 3).  Traced once."""
+    if (family, which) not in _REFERENCE:
+        st = stage(family)
+        sc = {"start": lambda: st.scene, "moved": lambda: box_moved(st, 1), "deformed": lambda: box_deformed(st, 2)[1]}[which]()
+        ref = oracle.build_scene(sc)
+        w, h = size(family)
+        cam = scenes.camera_block(sc.camera, w, h).copy()
+        frames, depth = [], None
+        for f in range(FRAMES):
+            cam["frame_index"] = 1 + f
+            if family == "lens":
+                img, depth = nlens.trace_frame(ref, cam, w, h, BOUNCES, *LENS)
+            elif family in MODEL:
+                img, depth = nc.trace_frame(ref, cam, w, h, BOUNCES, MODEL[family])
+            elif family == "bake":
+                img, depth = nb.trace_frame(ref, *texels(), cam, BOUNCES)
+            elif family == "probe":
+                img, depth = npb.trace_frame(ref, PROBES, TILE[0], TILE[1], PER_ROW, cam, BOUNCES)
+            else:
+                img, depth = nrf.trace_frame(ref, CUBES, FACE, PER_ROW, cam, BOUNCES)
+            frames.append(img)
+        _REFERENCE[family, which] = (sc, frames, np.asarray(depth, F).reshape(h, w))
+    return _REFERENCE[family, which]
+
+
+def assert_numpy(got, want, what):
+    _, frames, depth = want
+    n = differing(got["accumulation"][..., :3], np_continue(None, frames, False))
+    assert n == 0, "%s: the accumulation differs from numpy's at %d values" % (what, n)
+    assert differing(got["depth"], depth) == 0, "%s: the depth differs from numpy's" % what
+
+
+def references_differ(a, b):
+    return sum(differing(x, y) for x, y in zip(a[1], b[1])) > 0
+
+
+@pytest.mark.parametrize("change", ["update_tlas", "update_mesh"])
+@pytest.mark.parametrize("family", FAMILIES)
+def test_the_scene_before_and_after_a_change_equals_numpy(oracle, hiplib, family, change):
+    """the restatement is tree-independent: update_tlas also on JPT_BUILD_REFERENCE_EXACT"""
+    st = stage(family)
+    start, final = reference(oracle, family, "start"), reference(oracle, family, "moved" if change == "update_tlas" else "deformed")
+    assert references_differ(start, final)
+    for builder in ((capi.BUILD_REFERENCE_EXACT, SAH) if change == "update_tlas" else (WATERTIGHT,)):
+        ctx = ctx_for(st.scene, family, "sky", builder, HDR)
+        try:
+            for kernel in KERNELS:
+                assert_numpy(state(ctx, family, kernel), start, "the starting scene, builder %d kernel %d" % (builder, kernel))
+            if change == "update_tlas":
+                ctx.set_instance_transform(st.box, final[0].instances[st.box].transform)
+                ctx.update_tlas()
+            else:
+                ctx.update_mesh(st.box_mesh, final[0].meshes[st.box_mesh], with_normals=True)
+            for kernel in KERNELS if change == "update_tlas" else (WF,):
+                assert_numpy(state(ctx, family, kernel), final, "%s, builder %d kernel %d" % (change, builder, kernel))
+        finally:
+            ctx.close()
