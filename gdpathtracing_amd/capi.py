@@ -78,6 +78,7 @@ SYMBOLS = [
     "jpt_read_lightmap_directional_f32", "jpt_debug_bake_moments",
     "jpt_set_denoise_params", "jpt_denoise", "jpt_read_denoised_f32", "jpt_read_denoised_rgba8", "jpt_read_guides_f32", "jpt_debug_atrous",
     "jpt_set_denoise_variance", "jpt_read_denoised_variance_f32", "jpt_debug_atrous_variance",
+    "jpt_set_denoise_history", "jpt_denoise_history_reset", "jpt_read_denoise_history_f32", "jpt_debug_denoise_history",
     "jpt_set_display_params", "jpt_display", "jpt_read_display_rgba8", "jpt_read_display_f32", "jpt_debug_display", "jpt_debug_display_srgb_table",
     "jpt_set_meter_params", "jpt_meter", "jpt_meter_reset", "jpt_read_meter", "jpt_set_auto_exposure", "jpt_debug_meter",
     "jpt_set_variance", "jpt_read_variance_f32", "jpt_device_variance", "jpt_set_noise_params", "jpt_noise_estimate", "jpt_read_noise",
@@ -119,6 +120,14 @@ class DenoiseVarianceParams(C.Structure):
 
     def __init__(self, enable=0, sigma_variance=2.0, variance_floor=1e-6, reserved=0):
         super().__init__(enable, sigma_variance, variance_floor, reserved)
+
+
+class DenoiseHistoryParams(C.Structure):
+    """jpt_denoise_history_params; the defaults are the library's (the history off)"""
+    _fields_ = [("enable", C.c_int32), ("max_history", C.c_int32), ("min_history", C.c_int32), ("sigma_plane", C.c_float), ("reserved", C.c_int32 * 4)]
+
+    def __init__(self, enable=0, max_history=32, min_history=4, sigma_plane=0.05, reserved=(0, 0, 0, 0)):
+        super().__init__(enable, max_history, min_history, sigma_plane, (C.c_int32 * 4)(*reserved))
 
 
 class BakeFinishParams(C.Structure):
@@ -479,6 +488,12 @@ def lib():
         L.jpt_set_denoise_variance.argtypes = [vp, C.POINTER(DenoiseVarianceParams)]
         L.jpt_read_denoised_variance_f32.argtypes = [vp, vp]
         L.jpt_debug_atrous_variance.argtypes = [C.c_int, i32, i32, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceParams), vp, vp, u32, vp, vp, vp, vp, vp]
+    if hasattr(L, "jpt_set_denoise_history") or "JPT_LIB" not in os.environ:
+        L.jpt_set_denoise_history.argtypes = [vp, C.POINTER(DenoiseHistoryParams)]
+        L.jpt_denoise_history_reset.argtypes = [vp]
+        L.jpt_read_denoise_history_f32.argtypes = [vp, vp, vp]
+        L.jpt_debug_denoise_history.argtypes = [C.c_int, i32, i32, C.POINTER(DenoiseParams), C.POINTER(DenoiseHistoryParams), vp, u32, vp, vp, vp, vp, i32,
+                                                vp, vp, vp, vp, vp, vp]
     if hasattr(L, "jpt_display") or "JPT_LIB" not in os.environ:
         L.jpt_set_display_params.argtypes = [vp, C.POINTER(DisplayParams)]
         L.jpt_display.argtypes = [vp]

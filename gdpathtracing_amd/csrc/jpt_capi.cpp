@@ -57,6 +57,7 @@ int alloc_framebuffers(jpt_ctx* c)
         HIP_TRY(c, hipMemsetAsync(c->d_depth.p, 0, npx * sizeof(float), c->stream));
     }
     c->frame_count = 0;
+    c->accum_restarts++;
     c->assembled = c->assembled_ldr = false;
     c->post.framebuffers_remade(false);
     return JPT_OK;
@@ -2183,6 +2184,7 @@ int jpt_accum_reset(jpt_ctx* c)
 {
     if (!c) return JPT_E_INVALID;
     c->frame_count = 0;  // frame_count == 1 on the next frame overwrites the sum (progressive_rendering.glsl:34)
+    c->accum_restarts++;
     c->stats.frames = 0;
     c->assembled = c->assembled_ldr = false;
     c->hist_valid = false;  // temporal mode: history images start from zero again (a new TemporalReprojection object)
@@ -2194,6 +2196,7 @@ int jpt_set_progressive_frame_count(jpt_ctx* c, uint32_t next_frame_count)
     if (!c) return JPT_E_INVALID;
     if (next_frame_count == 0) return fail(c, JPT_E_INVALID, "frame_count starts at 1 (progressive_rendering.cpp:20)");
     c->frame_count = next_frame_count - 1u;
+    c->accum_restarts++;
     c->stats.frames = c->frame_count;
     c->assembled = c->assembled_ldr = false;
     return JPT_OK;
@@ -2207,6 +2210,7 @@ int jpt_set_denoising_mode(jpt_ctx* c, int32_t mode)
     if (mode != c->denoise) {
         // the modes do not share state: the progressive sum and the temporal history both start over
         c->frame_count = 0;
+        c->accum_restarts++;
         c->stats.frames = 0;
         c->hist_valid = false;
         c->assembled = c->assembled_ldr = false;

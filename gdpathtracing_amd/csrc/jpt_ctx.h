@@ -8,6 +8,7 @@
 #include "jpt_builder.h"
 #include "jpt_denoise.h"
 #include "jpt_denoise_var.h"
+#include "jpt_denoise_history.h"
 #include "jpt_display.h"
 #include "jpt_lightmap.h"
 #include "jpt_meter.h"
@@ -251,6 +252,19 @@ struct PostState {
     AtrousVarParams dn_var;
     DevBuf<float> d_dn_var;
     bool dn_var_valid = false;
+    // jpt_set_denoise_history: the context's parameters (dn_hist.enable: the switch), and the stage's own images (jpt_denoise_history.h) --
+    // two history sets of three planes each ((m, N), (n, S), position_t: the stage keeps its own copies of the guides, so a jpt_denoise
+    // without history in between does not touch them) and the (m, v_0) image the filter reads, 112 B per pixel, made at the first
+    // history call at a resolution; dh_cur: the set the last history call wrote, dh_have: it holds one (dropped by
+    // jpt_denoise_history_reset, another size, switching enable), seen from dh_camera; dh_called / dh_restarts: a history call has
+    // consumed the frames of accumulation restart dh_restarts (jpt_ctx::accum_restarts); dh_read: d_dh_iv and set dh_cur hold a
+    // history call's result at the current resolution (jpt_read_denoise_history_f32)
+    HistoryParams dn_hist;
+    DevBuf<float4> d_dh_set[2][3], d_dh_iv;
+    int dh_cur = 0;
+    bool dh_have = false, dh_called = false, dh_read = false;
+    uint64_t dh_restarts = 0;
+    RefCamera dh_camera;
     // jpt_bake_finish: the context's parameters, and its own images (two guides, a colour ping and pong: 64 B per texel) -- made at
     // the first jpt_bake_finish at a size, kept until jpt_set_params names another size or a call writes the bake images
     // (lightmap_release); lm_result: the one of ping / pong that holds the lightmap of a jpt_bake_finish at the current size and images
@@ -300,12 +314,13 @@ struct PostState {
     void lightmap_release();   // jpt_bake_finish's images and result, and lmd_release
     void lmd_release();        // jpt_bake_finish_directional's images and result
     void bake_dir_release() { d_bake_dir.release(); bake_dir_valid = false; }
+    void history_drop() { dh_have = dh_read = false; }   // the next history call starts without history (the planes stay)
     void variance_release() { d_variance.release(); d_noise_tiles.release(); variance_valid = noise_valid = false; }   // the plane and the tile map
     // The one place that says what re-made framebuffers do to this state (alloc_framebuffers: the plane and the estimate are of frames
     // that are gone) and, `resized`, what another image size does on top (jpt_set_params): every image of that size is given back and
     // every result of that size forgotten.  sized_buffers: whether one of the buffers it then frees exists -- work on the context's
     // stream may still use it, so the caller waits for the stream first.
-    bool sized_buffers() const { return d_dn_ping.p || d_lm_ping.p || d_lmd_out.p || d_disp_f32.p || d_disp_pyramid.p; }
+    bool sized_buffers() const { return d_dn_ping.p || d_dh_iv.p || d_lm_ping.p || d_lmd_out.p || d_disp_f32.p || d_disp_pyramid.p; }
     void framebuffers_remade(bool resized);
 };
 // What a render refuses with the directional planes (the variance plane) switched on, and the planes (the plane) at the size of the
@@ -359,6 +374,7 @@ struct jpt_ctx {
     int32_t rank = 0, world = 1, local_rows = 0;
     RefCamera camera;
     uint32_t frame_count = 0;  // frames accumulated since reset
+    uint64_t accum_restarts = 0;   // how often the accumulation started over or was re-positioned (what a history call of jpt_denoise remembers)
     int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour

@@ -507,6 +507,21 @@ struct AtrousVarParams;
 void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* sums,
                             const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
                             float4* pong, uint32_t* ldr, float* var_out);
+// ... from pass `first_pass` >= 1 on, which reads `src`, an (i, v) image (neither `ping` nor `pong` when passes - first_pass is even)
+void launch_atrous_variance_from(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass,
+                                 const float4* src, const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong,
+                                 uint32_t* ldr, float* var_out);
+// jpt_denoise with jpt_set_denoise_history on (jpt_kernels_denoise_history.hip; the arithmetic: jpt_denoise_history.h).  The stage: from
+// the sums, frame_count, this call's guides and the previous history set (three planes, or three nulls) seen from `prev_view` (not read
+// with `same_view`) to the new set and the (m, v_0) image `iv`; and the filter over `iv`: a first pass of its own, then
+// launch_atrous_variance_from -- outputs as launch_atrous_variance's.  `iv` is neither `ping` nor `pong`.
+struct HistoryParams;
+struct HistoryView;
+void launch_denoise_history(hipStream_t stream, const HistoryParams& hp, int normal_power_log2, int width, int height, const float4* sums, uint32_t frame_count,
+                            const float4* position_t, const float4* normal, const float4* albedo, const HistoryView& prev_view, bool same_view,
+                            const float4* prev_a, const float4* prev_b, const float4* prev_x, float4* new_a, float4* new_b, float4* new_x, float4* iv);
+void launch_atrous_history(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* iv,
+                           const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr, float* var_out);
 
 // jpt_bake_finish (jpt_kernels_lightmap.hip; the arithmetic: jpt_lightmap.h).  The checks of jpt_set_bake_finish_params, also run by
 // jpt_debug_bake_finish; and the whole transform on `stream`: the guides (xg, ng) from the bake images, `passes` filter passes from

@@ -151,9 +151,10 @@ void launch_var_pass(hipStream_t stream, const AtrousVarArgs& a, bool last)
 
 }  // namespace
 
-void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* sums,
-                            const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
-                            float4* pong, uint32_t* ldr, float* var_out)
+// passes first_pass .. passes - 1 of the filter; `src`: what pass first_pass reads (pass 0: the sums, with `m2` and `frame_count`)
+static void launch_var_passes(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass, const float4* src,
+                              const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
+                              float4* pong, uint32_t* ldr, float* var_out)
 {
     if (width <= 0 || height <= 0) return;
     AtrousVarArgs a;
@@ -172,10 +173,9 @@ void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const A
     a.sv2 = vprm.sigma_variance * vprm.sigma_variance;
     a.floor = vprm.variance_floor;
     // the last pass writes `ping` (launch_atrous' arrangement)
-    float4* dst = (prm.passes & 1) ? ping : pong;
-    float4* other = (prm.passes & 1) ? pong : ping;
-    const float4* src = sums;
-    for (int k = 0; k < prm.passes; k++) {
+    float4* dst = ((prm.passes - first_pass) & 1) ? ping : pong;
+    float4* other = ((prm.passes - first_pass) & 1) ? pong : ping;
+    for (int k = first_pass; k < prm.passes; k++) {
         a.in = src;
         a.out = dst;
         a.step = 1 << k;
@@ -188,6 +188,20 @@ void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const A
         dst = other;
         other = t;
     }
+}
+
+void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* sums,
+                            const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
+                            float4* pong, uint32_t* ldr, float* var_out)
+{
+    launch_var_passes(stream, prm, vprm, width, height, 0, sums, m2, frame_count, position_t, normal, albedo, ping, pong, ldr, var_out);
+}
+
+void launch_atrous_variance_from(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass,
+                                 const float4* src, const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong,
+                                 uint32_t* ldr, float* var_out)
+{
+    launch_var_passes(stream, prm, vprm, width, height, first_pass, src, nullptr, 2u, position_t, normal, albedo, ping, pong, ldr, var_out);
 }
 
 }  // namespace jpt

@@ -28,12 +28,16 @@ void PostState::framebuffers_remade(bool resized)
 {
     variance_valid = noise_valid = false;   // (jpt_set_variance's plane is of the frames before; the next render overwrites it)
     if (!resized) return;
-    // the images of jpt_denoise, jpt_bake_finish, jpt_bake_finish_directional and jpt_display are of the old size, the metering state and
+    // the images of jpt_denoise and its history, jpt_bake_finish, jpt_bake_finish_directional and jpt_display are of the old size, the metering state and
     // what the directional planes hold too (the planes themselves, like the variance plane, are re-made by the next render: ensure_bake_dir)
     bake_dir_valid = false;
     for (DevBuf<float4>* b : {&d_dn_pos, &d_dn_nrm, &d_dn_alb, &d_dn_ping, &d_dn_pong, &d_disp_f32, &d_disp_pyramid}) b->release();
     d_dn_ldr.release();
     d_dn_var.release();
+    for (auto& set : d_dh_set)
+        for (DevBuf<float4>& b : set) b.release();
+    d_dh_iv.release();
+    history_drop();
     d_disp_ldr.release();
     lightmap_release();
     dn_valid = dn_var_valid = disp_valid = meter_valid = false;
@@ -228,7 +232,17 @@ int jpt_denoise(jpt_ctx* c)
     const int rc_cm = view_now(c, "jpt_denoise", "the guides", cm);
     if (rc_cm != JPT_OK) return rc_cm;
     PostState& q = c->post;
-    const bool guided = q.dn_var.enable != 0;
+    const bool history = q.dn_hist.enable != 0;
+    if (history) {   // (jpt_set_denoise_history: bake images, probes and reflection probes are view_now's refusals)
+        if (c->primary.lens_radius > 0.0f)
+            return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_history on: the lens radius is > 0 (jpt_set_lens): the history is reprojected through a pinhole");
+        if (c->primary.camera_model != JPT_CAMERA_PINHOLE)
+            return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_history on: the camera model must be JPT_CAMERA_PINHOLE (jpt_set_camera_model)");
+        if (q.dh_called && q.dh_restarts == c->accum_restarts)
+            return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_history on: the history already holds the frames accumulated since the last reset, and a "
+                                        "second call would count them twice (jpt_accum_reset or jpt_denoise_history_reset first)");
+    }
+    const bool guided = !history && q.dn_var.enable != 0;
     if (guided) {   // (jpt_set_denoise_variance: refused, never filtered with the fixed tolerance instead)
         const int rc_v = variance_ready(c, "jpt_denoise with jpt_set_denoise_variance on");
         if (rc_v != JPT_OK) return rc_v;
@@ -241,13 +255,32 @@ int jpt_denoise(jpt_ctx* c)
         for (DevBuf<float4>* b : {&q.d_dn_pos, &q.d_dn_nrm, &q.d_dn_alb, &q.d_dn_ping, &q.d_dn_pong}) HIP_TRY(c, b->resize(npx));
         HIP_TRY(c, q.d_dn_ldr.resize(npx));
     }
-    if (guided) HIP_TRY(c, q.d_dn_var.resize(npx));
+    if (guided || history) HIP_TRY(c, q.d_dn_var.resize(npx));
+    if (history && (q.d_dh_iv.n != npx || !q.d_dh_iv.p)) {
+        q.history_drop();
+        for (auto& set : q.d_dh_set)
+            for (DevBuf<float4>& b : set) HIP_TRY(c, b.resize(npx));
+        HIP_TRY(c, q.d_dh_iv.resize(npx));
+    }
     // On the context's stream: it is ordered behind the accumulation of every render queued so far (launch_render) and behind the
     // device refits (queue_instance_refit), and the accumulation of every later render waits for what it holds.
     hipStream_t s = c->stream;
     if (npx) {
         launch_guides(s, c->ds, c->camera, cm, c->width, c->height, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p);
-        if (guided)
+        if (history) {
+            // the previous set seen from the previous call's view; a view that is bit for bit this one reprojects every pixel onto itself
+            DevBuf<float4>* prev = q.d_dh_set[q.dh_cur];
+            DevBuf<float4>* next = q.d_dh_set[q.dh_cur ^ 1];
+            const bool same_view = q.dh_have && std::memcmp(q.dh_camera.vp, c->camera.vp, sizeof c->camera.vp) == 0 &&
+                                   std::memcmp(&q.dh_camera.position, &c->camera.position, sizeof c->camera.position) == 0;
+            HistoryView view;
+            std::memcpy(view.vp, q.dh_camera.vp, sizeof view.vp);
+            launch_denoise_history(s, q.dn_hist, q.dn_params.normal_power_log2, c->width, c->height, c->d_accum.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
+                                   q.d_dn_alb.p, view, same_view, q.dh_have ? prev[0].p : nullptr, q.dh_have ? prev[1].p : nullptr,
+                                   q.dh_have ? prev[2].p : nullptr, next[0].p, next[1].p, next[2].p, q.d_dh_iv.p);
+            launch_atrous_history(s, q.dn_params, q.dn_var, c->width, c->height, q.d_dh_iv.p, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
+                                  q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
+        } else if (guided)
             launch_atrous_variance(s, q.dn_params, q.dn_var, c->width, c->height, c->d_accum.p, q.d_variance.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
                                    q.d_dn_alb.p, q.d_dn_ping.p, q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
         else
@@ -255,8 +288,63 @@ int jpt_denoise(jpt_ctx* c)
                           q.d_dn_pong.p, q.d_dn_ldr.p);
         HIP_TRY(c, hipGetLastError());
     }
+    if (history) {
+        q.dh_cur ^= 1;
+        q.dh_have = q.dh_called = q.dh_read = true;
+        q.dh_restarts = c->accum_restarts;
+        q.dh_camera = c->camera;
+    }
     q.dn_valid = true;
-    q.dn_var_valid = guided;
+    q.dn_var_valid = guided || history;
+    return JPT_OK;
+}
+
+int jpt_set_denoise_history(jpt_ctx* c, const jpt_denoise_history_params* params)
+{
+    if (!c) return JPT_E_INVALID;
+    HistoryParams p;
+    int32_t reserved[4] = {0, 0, 0, 0};
+    if (params) {
+        p.enable = params->enable;
+        p.max_history = params->max_history;
+        p.min_history = params->min_history;
+        p.sigma_plane = params->sigma_plane;
+        for (int k = 0; k < 4; k++) reserved[k] = params->reserved[k];
+    }
+    std::string why;
+    const int rc = check_denoise_history_params(p, reserved, why);
+    if (rc != JPT_OK) return fail(c, rc, why);
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
+    if (p.enable != c->post.dn_hist.enable) {   // switching drops the history, and the frames of this accumulation are no longer counted
+        c->post.history_drop();
+        c->post.dh_called = false;
+    }
+    c->post.dn_hist = p;
+    return JPT_OK;
+}
+
+int jpt_denoise_history_reset(jpt_ctx* c)
+{
+    if (!c) return JPT_E_INVALID;
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: jpt_denoise runs on the device");
+    c->post.history_drop();
+    c->post.dh_called = false;   // (nothing is left that could count the frames of this accumulation twice)
+    return JPT_OK;
+}
+
+int jpt_read_denoise_history_f32(jpt_ctx* c, float* integrated4, float* length)
+{
+    int rc = read_denoise_common(c, true);
+    if (rc) return rc;
+    const PostState& q = c->post;
+    if (!q.dh_read) return fail(c, JPT_E_STATE, "jpt_read_denoise_history_f32: no jpt_denoise with jpt_set_denoise_history on since the history was dropped");
+    const size_t npx = (size_t)c->width * c->height;
+    if (integrated4 && (rc = read_out(c, q.d_dh_iv.p, npx * sizeof(float4), integrated4)) != JPT_OK) return rc;
+    if (length) {   // the .w of the (m, N) plane
+        if ((rc = staged_read(c, q.d_dh_set[q.dh_cur][0].p, npx * sizeof(float4))) != JPT_OK) return rc;
+        const float4* mn = c->h_read_pinned.as<float4>();
+        for (size_t i = 0; i < npx; i++) length[i] = mn[i].w;
+    }
     return JPT_OK;
 }
 

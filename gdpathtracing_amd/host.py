@@ -310,6 +310,28 @@ def debug_atrous_variance(device_id, sum4, m2, frame_count, position_t, normal, 
     return out, var
 
 
+def debug_denoise_history(device_id, sum4, frame_count, position_t, normal, albedo, prev=None, prev_vp=None, same_view=False, params=None, hparams=None):
+    """jpt_debug_denoise_history: the history stage of jpt_denoise over caller-made planes float32 [height, width, 4], on a device or
+    (device_id -1, JPT_DEVICE_HOST_ONLY) on the host.  prev: the previous history set (integrated = (m.rgb, N), normal_s = (normal, S),
+    position_t) or None; prev_vp: the previous call's view-projection matrix, 16 floats column-major (not read with same_view).
+    Returns (iv = (m.rgb, v_0), integrated, normal_s): what the filter reads and the new set's first two planes (its third is
+    position_t).  params: a capi.DenoiseParams, hparams: a capi.DenoiseHistoryParams, or None for the defaults."""
+    arrays = [np.ascontiguousarray(a, dtype=np.float32) for a in (sum4, position_t, normal, albedo)]
+    h, w = arrays[0].shape[:2]
+    old = [None, None, None] if prev is None else [np.ascontiguousarray(a, dtype=np.float32) for a in prev]
+    if any(a.shape != (h, w, 4) for a in arrays + [a for a in old if a is not None]):
+        raise ValueError("every plane is float32 [height, width, 4]")
+    vp16 = None if prev_vp is None else np.ascontiguousarray(prev_vp, dtype=np.float32).reshape(16)
+    outs = [np.zeros((h, w, 4), np.float32) for _ in range(3)]
+    s, x, n, a = arrays
+    rc = capi.lib().jpt_debug_denoise_history(int(device_id), w, h, None if params is None else C.byref(params), None if hparams is None else C.byref(hparams),
+                                              _ptr(s), int(frame_count), _ptr(x), _ptr(n), _ptr(a), None if vp16 is None else _ptr(vp16), int(bool(same_view)),
+                                              *[None if o is None else _ptr(o) for o in old], *[_ptr(o) for o in outs])
+    if rc != capi.OK:
+        raise capi.JptError("jpt_debug_denoise_history failed (%d)" % rc)
+    return tuple(outs)
+
+
 def debug_noise_estimate(device_id, sum4, m2, frame_count, params=None, valid=None, **fields):
     """jpt_debug_noise_estimate: jpt_noise_estimate's pass over caller-made planes float32 [height, width, 4], on a device or
     (device_id -1, JPT_DEVICE_HOST_ONLY) on the host --(the capi.NoiseResult as a dict, hist uint32 [256], tiles float32 [ceil(h / 8), ceil(w / 8)]).
@@ -1035,6 +1057,25 @@ class Context:
         out = np.zeros((self.height, self.width), dtype=np.float32)
         self._ck(self._lib.jpt_read_denoised_variance_f32(self.h, _ptr(out)), "jpt_read_denoised_variance_f32")
         return out
+
+    def set_denoise_history(self, params: Optional[capi.DenoiseHistoryParams] = None, **fields):
+        """jpt_set_denoise_history: a capi.DenoiseHistoryParams, or its fields by name (enable, max_history, min_history, sigma_plane;
+        the rest at the defaults); nothing: the defaults, the history off.  With it on, each denoise() integrates the frames accumulated
+        since the last reset into a reprojected per-pixel history and filters that, guided by the history's own variance."""
+        if params is None and fields:
+            params = capi.DenoiseHistoryParams(**fields)
+        self._ck(self._lib.jpt_set_denoise_history(self.h, None if params is None else C.byref(params)), "jpt_set_denoise_history")
+
+    def denoise_history_reset(self):
+        """jpt_denoise_history_reset: the next denoise() starts without history"""
+        self._ck(self._lib.jpt_denoise_history_reset(self.h), "jpt_denoise_history_reset")
+
+    def read_denoise_history(self):
+        """jpt_read_denoise_history_f32: (float32 [height, width, 4] = (m.rgb demodulated, v_0), float32 [height, width] = the history
+        length N) of the last denoise() with the history on"""
+        iv, length = np.zeros((self.height, self.width, 4), dtype=np.float32), np.zeros((self.height, self.width), dtype=np.float32)
+        self._ck(self._lib.jpt_read_denoise_history_f32(self.h, _ptr(iv), _ptr(length)), "jpt_read_denoise_history_f32")
+        return iv, length
 
     # ---- the display transform (jpt_display)
     def set_display_params(self, params: Optional[capi.DisplayParams] = None, **fields):

@@ -999,8 +999,8 @@ int jpt_read_guides_f32(jpt_ctx *ctx, float *position_t, float *normal, float *a
  * off (jpt_set_variance), when no render has written it at the current size, and when fewer than two frames are accumulated; it is
  * otherwise ordered on the stream as without the guidance, READS the accumulation, the frame count and the plane and writes only its
  * own images.  jpt_read_denoised_variance_f32: JPT_E_STATE unless the last jpt_denoise at the current resolution was a guided one.
- * Host-only contexts: JPT_E_DEVICE.  Not covered: jpt_bake_finish, a temporal component, a partition or jpt_multi, a jpt_encode
- * source for the variance image, per-channel variance. */
+ * Host-only contexts: JPT_E_DEVICE.  Not covered: jpt_bake_finish, a partition or jpt_multi, a jpt_encode source for the variance
+ * image, per-channel variance.  (The temporal component is jpt_set_denoise_history, below.) */
 typedef struct jpt_denoise_variance_params {
     int32_t enable;          /* 0 or 1, default 0 */
     float   sigma_variance;  /* finite, > 0, default 2.0: colour tolerance in standard deviations of the mean */
@@ -1009,6 +1009,55 @@ typedef struct jpt_denoise_variance_params {
 } jpt_denoise_variance_params;
 int jpt_set_denoise_variance(jpt_ctx *ctx, const jpt_denoise_variance_params *params);   /* NULL: the defaults */
 int jpt_read_denoised_variance_f32(jpt_ctx *ctx, float *out);                            /* W*H floats: v of the last pass */
+
+/* ---- history for jpt_denoise: past frames reprojected through the guides (no reference counterpart; the temporal stage of SVGF) ----
+ * An interactive viewport renders one sample per pixel per frame under a moving camera (jpt_accum_reset, jpt_render(1), show): the
+ * progressive mean never gets past one frame and the variance plane has nothing to measure.  With the history on, each jpt_denoise
+ * integrates the mean of the frames accumulated since the last reset into a per-pixel history that follows the surfaces: it is
+ * reprojected from the previous call's view, validated against the previous call's position and normal guides, and its variance feeds
+ * the variance-guided passes above.  Off, the default, jpt_denoise launches what it launches without this section.  The arithmetic is
+ * pinned in DESIGN.md section 2 (gdpathtracing_amd/csrc/jpt_denoise_history.h; tests/np_denoise_history.py restates it bit for bit);
+ * every operation is one binary32 operation in the order written.  One call, on the context's stream as jpt_denoise is ordered:
+ *   guides      the guide pass, unchanged: X = position_t, n, albedo; a = max(albedo, 1/64)
+ *   history     per pixel, nf = (float)frame_count: the sample c = (accum / nf) / a.  A miss or a c that is not finite takes no
+ *               history and leaves none (length 0; the filter gets (c, +0)).  Previous view (RefCamera vp and position) bit-identical
+ *               to this one: the one tap is the pixel's own previous texel, taken as it is.  Else clip = vp_prev * (X, 1), clip.w > 0,
+ *               u = (clip.x / clip.w + 1) / 2 * W, v = (1 - clip.y / clip.w) / 2 * H, and the four bilinear taps around (u - 0.5,
+ *               v - 0.5) inside the image.  A tap weighs its bilinear weight times the geometric weight of jpt_denoise (normal_power_log2
+ *               of jpt_set_denoise_params, sigma_plane of this struct) of the previous call's position and normal at the tap seen from
+ *               this pixel; a tap of history length 0, or whose m or S is not finite, weighs 0.  Sum of weights > 0: m_h, S_h, N_h are the weighted means.
+ *               N = max(min(N_h + nf, max_history), nf), al = nf / N, d = c - m_h, m = m_h + al * d, S = (1 - al) * (S_h + al * |d|^2)
+ *               (West's update: no raw second moments).  No history: m = c, S = 0, N = nf.
+ *               N_h >= min_history: v_0 = S * al / (1 - al), the variance of m summed over the channels -- exactly m2 / (k (k - 1))
+ *               while the history grows, twice the steady-state variance once it is capped.  Else the variance of c over the accepted
+ *               taps of the pixel's 5 x 5 window (inside the image, finite, geometric weight > 0) times al; fewer than two taps: +0.
+ *   filter      the passes of jpt_set_denoise_variance over (m, v_0), with its sigma_variance and variance_floor; neither its enable
+ *               nor jpt_set_variance needs to be on.  The outputs are jpt_denoise's: the denoised image, its rgba8 image and the v
+ *               plane (jpt_read_denoised_*, jpt_read_denoised_variance_f32, jpt_display, jpt_meter, jpt_encode with DENOISED).
+ * A call consumes its frames: a second history call with none of jpt_accum_reset, jpt_set_progressive_frame_count, jpt_set_params
+ * (or jpt_set_partition, which re-makes the framebuffers too) and a jpt_set_denoising_mode that changes the mode -- the calls that
+ * restart or re-position the accumulation -- in between would count them twice and answers JPT_E_STATE; jpt_denoise_history_reset
+ * and switching enable release the frames with the history they were counted in.  With the history on jpt_denoise also answers JPT_E_STATE with a lens
+ * radius > 0, a camera model other than JPT_CAMERA_PINHOLE, bake images, probes or reflection probes, beside what it refuses anyway.
+ * The history (three planes of 16 B per pixel, twice, and the (m, v_0) image: 112 B per pixel, from the first history call at a
+ * resolution) is dropped by jpt_denoise_history_reset, by jpt_set_params with another size, by switching enable and by jpt_destroy --
+ * not by scene changes: where a surface moved the geometric test rejects the tap and the pixel starts over (there are no motion
+ * vectors).  A jpt_denoise with the history off leaves it untouched.  The parameters are the context's, as jpt_set_denoise_params':
+ * they survive scene changes and jpt_scene_share does not copy them.  JPT_E_INVALID: enable not 0 or 1, max_history outside
+ * [1, 65536], min_history outside [1, max_history], a sigma_plane that is not finite or not > 0, reserved != 0.  Host-only contexts:
+ * JPT_E_DEVICE after the checks that need no device.  Not covered: motion vectors, feedback of the filtered image into the history,
+ * a 3 x 3 search when all four taps fail, neighbourhood colour clamping, lens and non-pinhole views, bakes and probes, a partition
+ * or jpt_multi, jpt_bake_finish, reprojection of sky pixels. */
+typedef struct jpt_denoise_history_params {
+    int32_t enable;          /* 0 or 1, default 0 */
+    int32_t max_history;     /* 1..65536 frames, default 32: the history length is capped here (an exponential average from then on) */
+    int32_t min_history;     /* 1..max_history frames, default 4: below it the variance is the spatial estimate */
+    float   sigma_plane;     /* finite, > 0, default 0.05: tolerated distance of a history tap from the pixel's tangent plane, relative to its hit distance */
+    int32_t reserved[4];     /* 0 */
+} jpt_denoise_history_params;
+int jpt_set_denoise_history(jpt_ctx *ctx, const jpt_denoise_history_params *params);   /* NULL: the defaults */
+int jpt_denoise_history_reset(jpt_ctx *ctx);                                            /* the next jpt_denoise starts without history */
+int jpt_read_denoise_history_f32(jpt_ctx *ctx, float *integrated4, float *length);      /* W*H*4 (m.rgb demodulated, v_0) and W*H floats (N); either may be NULL */
 
 /* ---- the display transform: exposure, bloom, selectable tone mapping (no reference counterpart; the reference lists "simple post
  * processing (e.g. bloom, controllable tone-mapping)" among its wanted features) ------------------------------------------------
@@ -1607,6 +1656,19 @@ int jpt_debug_noise_estimate(int device_id, int32_t width, int32_t height, const
 int jpt_debug_atrous_variance(int device_id, int32_t width, int32_t height, const jpt_denoise_params *params,
                               const jpt_denoise_variance_params *vparams, const float *sum4, const float *m2_4, uint32_t frame_count,
                               const float *position_t, const float *normal, const float *albedo, float *out4, float *var_out);
+/* The history stage of jpt_denoise alone (jpt_set_denoise_history), on caller-made planes of width x height pixels, 4 floats per
+ * pixel each: sum4 the accumulation of frame_count >= 1 frames and the three guide images of this call; the previous history set as
+ * three planes -- prev_integrated4 = (m.rgb, N), prev_normal_s4 = (normal, S), prev_position_t -- or three NULLs for none;
+ * prev_vp16 the previous call's RefCamera vp, column-major (not read with same_view = 1 or without a previous set).  Outputs:
+ * iv_out4 = (m.rgb, v_0), what the filter reads; integrated_out4 and normal_s_out4, the new set's first two planes (its third is
+ * position_t).  params (normal_power_log2 is read) and hparams NULL: the defaults; checked as their setters check them; hparams->enable
+ * is checked and otherwise ignored (JPT_E_INVALID; this call leaves no message).  device_id >= 0: history_kernel, on that device;
+ * JPT_DEVICE_HOST_ONLY: the same functions compiled for the host. */
+int jpt_debug_denoise_history(int device_id, int32_t width, int32_t height, const jpt_denoise_params *params,
+                              const jpt_denoise_history_params *hparams, const float *sum4, uint32_t frame_count, const float *position_t,
+                              const float *normal, const float *albedo, const float *prev_vp16, int32_t same_view,
+                              const float *prev_integrated4, const float *prev_normal_s4, const float *prev_position_t, float *iv_out4,
+                              float *integrated_out4, float *normal_s_out4);
 /* The device's records of mesh `mesh_id` of a JPT_BUILD_SAH_WATERTIGHT commit, as stored (tests of jpt_scene_update_mesh):
  * info_out[6] = {1 if the device holds a tree for the mesh (an instance names it) else 0, its root reference, first record,
  * record count, first triangle, triangle count}.  Records: the float four-child records (128 B) and their quantised form

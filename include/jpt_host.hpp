@@ -951,6 +951,11 @@ class PathTracingCamera {
     // the variance guidance of jpt_denoise (nullptr: the defaults, off); on, denoise() needs set_variance(true) and two frames
     void set_denoise_variance(const jpt_denoise_variance_params* params) { check(ctx, jpt_set_denoise_variance(ctx, params), "jpt_set_denoise_variance"); }
     void read_denoised_variance(float* out) { check(ctx, jpt_read_denoised_variance_f32(ctx, out), "jpt_read_denoised_variance_f32"); }
+    // the history of jpt_denoise (nullptr: the defaults, off); on, each denoise() integrates the frames since the last reset into a
+    // reprojected per-pixel history: the interactive loop is set_camera, accum_reset, render(1), denoise, display(DENOISED)
+    void set_denoise_history(const jpt_denoise_history_params* params) { check(ctx, jpt_set_denoise_history(ctx, params), "jpt_set_denoise_history"); }
+    void denoise_history_reset() { check(ctx, jpt_denoise_history_reset(ctx), "jpt_denoise_history_reset"); }
+    void read_denoise_history(float* integrated4, float* length) { check(ctx, jpt_read_denoise_history_f32(ctx, integrated4, length), "jpt_read_denoise_history_f32"); }
     // jpt_display and its parameters (nullptr: the defaults): exposure, bloom, tone map and transfer over the accumulation or over
     // jpt_denoise's image
     void set_display_params(const jpt_display_params* params) { check(ctx, jpt_set_display_params(ctx, params), "jpt_set_display_params"); }
