@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "jpt_encode.h"
+#include "jpt_atrous_pass.h"
 #include "jpt_instance_math.h"
 #include "jpt_kernels.h"
 #include "jpt_lightmap.h"
@@ -968,6 +969,35 @@ int jpt_debug_bake_raster(int device_id, const jpt_surface* surface, const float
     if (rc == JPT_OK && (e = hipMemcpy(normal4_out, d_all + b_img, b_img, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
     return rc;
+}
+
+// the whole transform on the host (jpt_debug_bake_finish with JPT_DEVICE_HOST_ONLY): out = (r, g, b, coverage)
+static void lightmap_finish_host(int32_t width, int32_t height, const LightmapParams& prm, const float4* mean4, const float4* position4,
+                                 const float4* normal4, float4* out)
+{
+    const size_t n = (size_t)width * height;
+    std::vector<float4> xg(n), ng(n), i0(n), scratch(n);
+    for (int32_t y = 0; y < height; y++)
+        for (int32_t x = 0; x < width; x++) {
+            const size_t ip = (size_t)y * width + x;
+            lightmap_guides(position4, normal4, width, height, x, y, xg[ip], ng[ip]);
+            i0[ip] = lightmap_colour0(mean4[ip], 1.0f, xg[ip]);
+        }
+    float sc = prm.sigma_color;
+    float4* a = atrous_passes_host(prm.passes, width, height, xg.data(), ng.data(), i0.data(), scratch.data(), [&](int k) {
+        const LightmapTaps taps{{1 << k, prm.normal_power_log2, prm.sigma_distance * prm.sigma_distance, prm.sigma_plane * prm.sigma_plane, sc * sc}};
+        sc = sc * 0.5f;
+        return taps;
+    });
+    float4* b = a == i0.data() ? scratch.data() : i0.data();
+    for (int k = 0; k < prm.dilate; k++) {
+        for (int32_t y = 0; y < height; y++)
+            for (int32_t x = 0; x < width; x++) b[(size_t)y * width + x] = lightmap_dilate(a, width, height, x, y);
+        float4* t = a;
+        a = b;
+        b = t;
+    }
+    for (size_t i = 0; i < n; i++) out[i] = a[i];
 }
 
 int jpt_debug_bake_finish(int device_id, int32_t width, int32_t height, const jpt_bake_finish_params* params, const float* mean4,

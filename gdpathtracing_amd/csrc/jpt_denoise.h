@@ -2,8 +2,11 @@
 // wavelet filter (Dammertz et al. 2010) over the demodulated running mean, guided by first-hit position, normal and albedo.
 // No reference counterpart (the reference lists a denoiser among its wanted features).  Everything is + - * /, fabs, compares and
 // selects, one binary32 operation each in source order: the device kernels (jpt_kernels_denoise.hip) and the host form of
-// jpt_debug_atrous run these functions, and tests/np_denoise.py restates them in float32 numpy bit for bit.
+// jpt_debug_atrous run these functions through the one pass body of jpt_atrous_pass.h, and tests/np_denoise.py restates them in
+// float32 numpy bit for bit.
 #pragma once
+
+#include "../../include/jpt.h"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +22,11 @@ struct AtrousParams {   // jpt_denoise_params
     float sigma_plane = 0.02f;
     float sigma_color = 4.0f;
 };
+// (null: the defaults) -- for jpt_set_denoise_params and the jpt_debug_* entries alike
+inline AtrousParams denoise_params_of(const jpt_denoise_params* p)
+{
+    return p ? AtrousParams{p->passes, p->normal_power_log2, p->sigma_plane, p->sigma_color} : AtrousParams();
+}
 
 // what a filter pass holds of one pixel: colour i_k, position_t (xyz, hit distance; t < 0: a miss) and normal
 struct AtrousPixel {
@@ -95,43 +103,24 @@ struct AtrousSum {
     }
 };
 
-// the whole filter on the host (jpt_debug_atrous with device -1): mean4 = (m.rgb, .) per pixel; out = (i_passes * amod, 1)
-inline void atrous_host(int32_t width, int32_t height, const AtrousParams& prm, const float4* mean4, const float4* position_t,
-                        const float4* normal, const float4* albedo, float4* out)
-{
-    const size_t n = (size_t)width * height;
-    float4* a = new float4[n];
-    float4* b = new float4[n];
-    for (size_t i = 0; i < n; i++) a[i] = atrous_demodulate(mean4[i], 1.0f, albedo[i]);
-    float sc = prm.sigma_color;
-    for (int k = 0; k < prm.passes; k++, sc = sc * 0.5f) {
-        const int s = 1 << k;
-        const float sc2 = sc * sc;
-        for (int32_t y = 0; y < height; y++)
-            for (int32_t x = 0; x < width; x++) {
-                const size_t ip = (size_t)y * width + x;
-                const AtrousPixel p{a[ip], position_t[ip], normal[ip]};
-                AtrousSum sum;
-                for (int dy = -2; dy <= 2; dy++)
-                    for (int dx = -2; dx <= 2; dx++) {
-                        const int64_t qx = (int64_t)x + (int64_t)s * dx, qy = (int64_t)y + (int64_t)s * dy;
-                        if (qx < 0 || qy < 0 || qx >= width || qy >= height) continue;
-                        const size_t iq = (size_t)qy * width + (size_t)qx;
-                        const AtrousPixel q{a[iq], position_t[iq], normal[iq]};
-                        sum.tap(p, q, dx, dy, prm.normal_power_log2, prm.sigma_plane, sc2);
-                    }
-                b[ip] = sum.result(p);
-            }
-        float4* t = a;
-        a = b;
-        b = t;
+// ---- what the one pass body (jpt_atrous_pass.h: atrous_pass on the device, atrous_passes_host on the host) asks of a filter -----
+// A filter's Taps holds the constants of one pass and names its Pixel, Sum and Prefilter (AtrousNoPrefilter: none).  skip(x): a
+// centre with guide x is written as zeros; centre(s, pre): what the taps of one centre share, from the tap spacing and the fed
+// prefilter; tap(): Sum::tap with it.
+struct AtrousNoPrefilter {};
+
+struct AtrousTaps {
+    using Pixel = AtrousPixel;
+    using Sum = AtrousSum;
+    using Prefilter = AtrousNoPrefilter;
+    int32_t npow;
+    float sigma_plane, sc2;   // sc2 = sc * sc, sc = sigma_color halved once per pass
+    __host__ __device__ __forceinline__ bool skip(const float4&) const { return false; }
+    __host__ __device__ __forceinline__ float centre(int, const Prefilter&) const { return sc2; }
+    __host__ __device__ __forceinline__ void tap(Sum& sum, const Pixel& p, const Pixel& q, int dx, int dy, float c) const
+    {
+        sum.tap(p, q, dx, dy, npow, sigma_plane, c);
     }
-    for (size_t i = 0; i < n; i++) {
-        const float4 am = atrous_amod(albedo[i]);
-        out[i] = make_float4(a[i].x * am.x, a[i].y * am.y, a[i].z * am.z, 1.0f);
-    }
-    delete[] a;
-    delete[] b;
-}
+};
 
 }  // namespace jpt

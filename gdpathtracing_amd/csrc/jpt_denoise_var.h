@@ -17,7 +17,8 @@
 // sigma_color is not read.  After the last pass the image is (i * a, 1) as jpt_denoise's, and v of the last pass is an output.
 //
 // Each + - * / is one binary32 operation in the order written (-ffp-contract=off): the device kernels (jpt_kernels_denoise_var.hip)
-// and the host form of jpt_debug_atrous_variance run these functions, and tests/np_denoise_var.py restates them bit for bit.
+// and the host form of jpt_debug_atrous_variance run these functions through the one pass body of jpt_atrous_pass.h, and
+// tests/np_denoise_var.py restates them bit for bit.
 #pragma once
 
 #include "jpt_denoise.h"
@@ -32,6 +33,12 @@ struct AtrousVarParams {   // jpt_denoise_variance_params
     float sigma_variance = 2.0f;
     float variance_floor = 1e-6f;
 };
+// (null: the defaults; `reserved`: the struct's last field) -- for jpt_set_denoise_variance and jpt_debug_atrous_variance alike
+inline AtrousVarParams denoise_variance_params_of(const jpt_denoise_variance_params* p, int32_t& reserved)
+{
+    reserved = p ? p->reserved : 0;
+    return p ? AtrousVarParams{p->enable, p->sigma_variance, p->variance_floor} : AtrousVarParams();
+}
 
 // the checks of jpt_set_denoise_variance, also run by jpt_debug_atrous_variance (`reserved`: the struct's last field)
 inline int check_denoise_variance_params(const AtrousVarParams& p, int32_t reserved, std::string& why)
@@ -99,52 +106,19 @@ struct AtrousVarSum {
     }
 };
 
-// the whole filter on the host (jpt_debug_atrous_variance with JPT_DEVICE_HOST_ONLY): out = (i_passes * amod, 1), var_out = v_passes
-inline void atrous_var_host(int32_t width, int32_t height, const AtrousParams& prm, const AtrousVarParams& vprm, const float4* sum4, const float4* m2,
-                            uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* out, float* var_out)
-{
-    const size_t n = (size_t)width * height;
-    const float nf = (float)frame_count, q = nf * (nf - 1.0f);
-    const float sv2 = vprm.sigma_variance * vprm.sigma_variance;
-    float4* a = new float4[n];
-    float4* b = new float4[n];
-    for (size_t i = 0; i < n; i++) a[i] = atrous_var_first(sum4[i], m2[i], nf, q, albedo[i]);
-    for (int k = 0; k < prm.passes; k++) {
-        const int s = 1 << k;
-        for (int32_t y = 0; y < height; y++)
-            for (int32_t x = 0; x < width; x++) {
-                const size_t ip = (size_t)y * width + x;
-                const AtrousPixel p{a[ip], position_t[ip], normal[ip]};
-                AtrousVarPrefilter pre;
-                for (int dy = -1; dy <= 1; dy++)
-                    for (int dx = -1; dx <= 1; dx++) {
-                        const int32_t qx = x + dx, qy = y + dy;
-                        if (qx < 0 || qy < 0 || qx >= width || qy >= height) continue;
-                        pre.tap(a[(size_t)qy * width + (size_t)qx].w, dx, dy);
-                    }
-                const float den = pre.den(sv2, vprm.variance_floor);
-                AtrousVarSum sum;
-                for (int dy = -2; dy <= 2; dy++)
-                    for (int dx = -2; dx <= 2; dx++) {
-                        const int64_t qx = (int64_t)x + (int64_t)s * dx, qy = (int64_t)y + (int64_t)s * dy;
-                        if (qx < 0 || qy < 0 || qx >= width || qy >= height) continue;
-                        const size_t iq = (size_t)qy * width + (size_t)qx;
-                        const AtrousPixel t{a[iq], position_t[iq], normal[iq]};
-                        sum.tap(p, t, dx, dy, prm.normal_power_log2, prm.sigma_plane, den);
-                    }
-                b[ip] = sum.result(p);
-            }
-        float4* t = a;
-        a = b;
-        b = t;
+// what the pass body asks of this filter (AtrousTaps' members): the prefilter, and den is what the taps of a centre share
+struct AtrousVarTaps {
+    using Pixel = AtrousPixel;
+    using Sum = AtrousVarSum;
+    using Prefilter = AtrousVarPrefilter;
+    int32_t npow;
+    float sigma_plane, sv2, floor;   // sv2 = sigma_variance * sigma_variance
+    __host__ __device__ __forceinline__ bool skip(const float4&) const { return false; }
+    __host__ __device__ __forceinline__ float centre(int, const Prefilter& pre) const { return pre.den(sv2, floor); }
+    __host__ __device__ __forceinline__ void tap(Sum& sum, const Pixel& p, const Pixel& q, int dx, int dy, float den) const
+    {
+        sum.tap(p, q, dx, dy, npow, sigma_plane, den);
     }
-    for (size_t i = 0; i < n; i++) {
-        const float4 am = atrous_amod(albedo[i]);
-        out[i] = make_float4(a[i].x * am.x, a[i].y * am.y, a[i].z * am.z, 1.0f);
-        var_out[i] = a[i].w;
-    }
-    delete[] a;
-    delete[] b;
-}
+};
 
 }  // namespace jpt

@@ -501,20 +501,18 @@ void launch_guides(hipStream_t stream, const DeviceScene& ds, const RefCamera& c
 void launch_atrous(hipStream_t stream, const AtrousParams& prm, int width, int height, const float4* sums, float frame_count,
                    const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr);
 // jpt_denoise with jpt_set_denoise_variance on (jpt_kernels_denoise_var.hip; the arithmetic: jpt_denoise_var.h): launch_atrous' passes
-// with the colour weight measured against the variance of the mean -- also reads `m2`, the plane of jpt_set_variance, of frame_count >= 2
-// frames, and also writes `var_out`, width * height floats: the variance the last pass leaves.  sigma_color is not read.
+// with the colour weight measured against the variance of the mean, from pass `first_pass` on, which reads `src` -- pass 0: the sums, and
+// with them `m2`, the plane of jpt_set_variance, of frame_count >= 2 frames; a later pass: an (i, v) image (neither `ping` nor `pong` when
+// passes - first_pass is even), m2 and frame_count not read.  Also writes `var_out`, width * height floats: the variance the last pass
+// leaves.  sigma_color is not read.
 struct AtrousVarParams;
-void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* sums,
+void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass, const float4* src,
                             const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
                             float4* pong, uint32_t* ldr, float* var_out);
-// ... from pass `first_pass` >= 1 on, which reads `src`, an (i, v) image (neither `ping` nor `pong` when passes - first_pass is even)
-void launch_atrous_variance_from(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass,
-                                 const float4* src, const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong,
-                                 uint32_t* ldr, float* var_out);
 // jpt_denoise with jpt_set_denoise_history on (jpt_kernels_denoise_history.hip; the arithmetic: jpt_denoise_history.h).  The stage: from
 // the sums, frame_count, this call's guides and the previous history set (three planes, or three nulls) seen from `prev_view` (not read
 // with `same_view`) to the new set and the (m, v_0) image `iv`; and the filter over `iv`: a first pass of its own, then
-// launch_atrous_variance_from -- outputs as launch_atrous_variance's.  `iv` is neither `ping` nor `pong`.
+// launch_atrous_variance from pass 1 -- outputs as launch_atrous_variance's.  `iv` is neither `ping` nor `pong`.
 struct HistoryParams;
 struct HistoryView;
 void launch_denoise_history(hipStream_t stream, const HistoryParams& hp, int normal_power_log2, int width, int height, const float4* sums, uint32_t frame_count,

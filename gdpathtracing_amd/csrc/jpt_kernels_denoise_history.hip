@@ -1,10 +1,10 @@
 // jpt_kernels_denoise_history.hip -- jpt_denoise with jpt_set_denoise_history on: the history stage (history_kernel) and the first
 // variance-guided a-trous pass over the (m, v_0) image the stage leaves (atrous_var_pre_kernel); the later passes are those of
-// jpt_kernels_denoise_var.hip (launch_atrous_variance_from).  No reference counterpart.  The arithmetic is pinned in
+// jpt_kernels_denoise_var.hip (launch_atrous_variance from pass 1).  No reference counterpart.  The arithmetic is pinned in
 // jpt_denoise_history.h and jpt_denoise_var.h / DESIGN.md section 2; nothing here writes a buffer a render reads.
 #include "../../include/jpt.h"
 #include "jpt_denoise_history.h"
-#include "jpt_denoise_var.h"
+#include "jpt_atrous_pass.h"
 #include "jpt_kernels.h"
 #include "jpt_trace_core.h"
 
@@ -12,14 +12,14 @@ namespace jpt {
 
 namespace {
 
-constexpr int kTileW = 32, kTileH = 8, kBlock = kTileW * kTileH, kHalo = 2;
-constexpr int kTW = kTileW + 2 * kHalo, kTH = kTileH + 2 * kHalo;
+constexpr int kTileW = kAtrousTileW, kTileH = kAtrousTileH, kBlock = kAtrousBlock, kHalo = 2;
+constexpr int kTW = AtrousTiles<kHalo>::TW;
 
 struct HistoryArgs {
     const float4* __restrict__ sum;          // the accumulation (sums)
     const float4* __restrict__ albedo;
-    const float4* __restrict__ position_t;
-    const float4* __restrict__ normal;
+    const float4* __restrict__ x;            // position_t
+    const float4* __restrict__ n;            // normal
     const float4* __restrict__ pa;           // the previous set (null: none): (m, N), (n, S), position_t
     const float4* __restrict__ pb;
     const float4* __restrict__ px;
@@ -31,11 +31,15 @@ struct HistoryArgs {
     float nf;
     HistoryParams hp;
     HistoryView view;
+    // what the stage's tiles hold beside the guides x and n (atrous_stage's Source): the demodulated mean
+    static __device__ __forceinline__ float4 outside_x() { return make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    __device__ __forceinline__ float4 colour(size_t g, const float4&) const { return atrous_demodulate(sum[g], nf, albedo[g]); }
 };
 
 // One lane per pixel, 32 x 8 pixels per block.  Every lane gathers and integrates its history from memory (up to four taps of three
 // 16-byte loads, neighbouring lanes on neighbouring texels).  Only a pixel whose history is shorter than min_history needs the 5 x 5
-// estimate: the block votes, and only a block with such a pixel stages its tile and a 2-pixel halo of (c, X, n) in LDS and runs the taps.
+// estimate: the block votes, and only a block with such a pixel stages its tile and a 2-pixel halo of (c, X, n) in LDS (atrous_stage,
+// jpt_atrous_pass.h) and runs the taps.
 __global__ __launch_bounds__(kBlock) void history_kernel(HistoryArgs a)
 {
     const int lx = (int)threadIdx.x & (kTileW - 1), ly = (int)threadIdx.x / kTileW;
@@ -47,8 +51,8 @@ __global__ __launch_bounds__(kBlock) void history_kernel(HistoryArgs a)
     float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), X = c, n = c;
     bool need = false;
     if (inside) {
-        X = a.position_t[idx];
-        n = a.normal[idx];
+        X = a.x[idx];
+        n = a.n[idx];
         c = atrous_demodulate(a.sum[idx], a.nf, a.albedo[idx]);
         auto prev = [&](int qx, int qy) {
             const size_t g = (size_t)qy * (size_t)a.width + (size_t)qx;
@@ -58,21 +62,7 @@ __global__ __launch_bounds__(kBlock) void history_kernel(HistoryArgs a)
         need = live && o.spatial;
     }
     if (__syncthreads_or(need ? 1 : 0)) {   // (every lane of the block arrives: nothing above returns)
-        __shared__ float4 tc[kTW * kTH], tx[kTW * kTH], tn[kTW * kTH];
-        for (int i = (int)threadIdx.x; i < kTW * kTH; i += kBlock) {
-            const int gx = x0 - kHalo + i % kTW, gy = y0 - kHalo + i / kTW;
-            float4 sc = make_float4(0.0f, 0.0f, 0.0f, 0.0f), sx = sc, sn = sc;
-            if (gx >= 0 && gy >= 0 && gx < a.width && gy < a.height) {
-                const size_t g = (size_t)gy * (size_t)a.width + (size_t)gx;
-                sc = atrous_demodulate(a.sum[g], a.nf, a.albedo[g]);
-                sx = a.position_t[g];
-                sn = a.normal[g];
-            }
-            tc[i] = sc;
-            tx[i] = sx;
-            tn[i] = sn;
-        }
-        __syncthreads();
+        const AtrousTiles<kHalo> t = atrous_stage<kHalo>(a, x0, y0, a.width, a.height);
         if (need) {
             const int ci = (ly + kHalo) * kTW + (lx + kHalo);
             const AtrousPixel p{c, X, n};
@@ -85,7 +75,7 @@ __global__ __launch_bounds__(kBlock) void history_kernel(HistoryArgs a)
                     const int qx = x + dx, qy = y + dy;
                     if (qx < 0 || qy < 0 || qx >= a.width || qy >= a.height) continue;
                     const int qi = ci + dy * kTW + dx;
-                    const AtrousPixel q{tc[qi], tx[qi], tn[qi]};
+                    const AtrousPixel q{t.c[qi], t.x[qi], t.n[qi]};
                     if (!history_spatial_accept(p, q, dx, dy, a.npow, a.hp.sigma_plane)) continue;
                     taken |= 1u << ((dy + 2) * 5 + (dx + 2));
                     sp.mean_tap(q.c);
@@ -96,7 +86,7 @@ __global__ __launch_bounds__(kBlock) void history_kernel(HistoryArgs a)
             for (int dy = -2; dy <= 2; dy++) {
 #pragma unroll
                 for (int dx = -2; dx <= 2; dx++)
-                    if (taken & (1u << ((dy + 2) * 5 + (dx + 2)))) sp.dist_tap(tc[ci + dy * kTW + dx]);
+                    if (taken & (1u << ((dy + 2) * 5 + (dx + 2)))) sp.dist_tap(t.c[ci + dy * kTW + dx]);
             }
             o.m.w = sp.result(o.al);
         }
@@ -108,82 +98,12 @@ __global__ __launch_bounds__(kBlock) void history_kernel(HistoryArgs a)
     a.nx[idx] = X;
 }
 
-struct AtrousPreArgs {
-    const float4* __restrict__ in;           // (i_0, v_0)
-    const float4* __restrict__ position_t;
-    const float4* __restrict__ normal;
-    const float4* __restrict__ albedo;       // LAST: the remodulation
-    float4* __restrict__ out;                // (i_1, v_1); LAST: the denoised image (r, g, b, 1)
-    uint32_t* __restrict__ ldr;              // LAST: unorm8(ACES(denoised)) (may be null)
-    float* __restrict__ var_out;             // LAST: v of the pass
-    int32_t width, height, npow;
-    float sigma_plane, sv2, floor;
-};
-
-// Pass 0 of the variance-guided filter over a pre-formed (i, v) image: atrous_var_kernel<2, ...>'s tiled shape and arithmetic
-// (jpt_kernels_denoise_var.hip), which forms (i_0, v_0) from the sums and the plane of second moments instead.
+// Pass 0 of the variance-guided filter over a pre-formed (i, v) image: the tiled pass of jpt_atrous_pass.h with the input as it is
+// (atrous_var_kernel<2, true, ...> of jpt_kernels_denoise_var.hip forms (i_0, v_0) from the sums and the plane of second moments).
 template <bool LAST>
-__global__ __launch_bounds__(kBlock) void atrous_var_pre_kernel(AtrousPreArgs a)
+__global__ __launch_bounds__(kBlock) void atrous_var_pre_kernel(AtrousVarFilter<false, LAST> f)
 {
-    const int lx = (int)threadIdx.x & (kTileW - 1), ly = (int)threadIdx.x / kTileW;
-    const int x0 = (int)blockIdx.x * kTileW, y0 = (int)blockIdx.y * kTileH;
-    const int x = x0 + lx, y = y0 + ly;
-    const bool inside = x < a.width && y < a.height;
-    const size_t idx = (size_t)y * (size_t)a.width + (size_t)x;
-    __shared__ float4 tc[kTW * kTH], tx[kTW * kTH], tn[kTW * kTH];
-    for (int i = (int)threadIdx.x; i < kTW * kTH; i += kBlock) {
-        const int gx = x0 - kHalo + i % kTW, gy = y0 - kHalo + i / kTW;
-        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), px = c, nn = c;
-        if (gx >= 0 && gy >= 0 && gx < a.width && gy < a.height) {
-            const size_t g = (size_t)gy * (size_t)a.width + (size_t)gx;
-            c = a.in[g];
-            px = a.position_t[g];
-            nn = a.normal[g];
-        }
-        tc[i] = c;
-        tx[i] = px;
-        tn[i] = nn;
-    }
-    __syncthreads();
-    if (!inside) return;
-    const int ci = (ly + kHalo) * kTW + (lx + kHalo);
-    const AtrousPixel p{tc[ci], tx[ci], tn[ci]};
-    AtrousVarPrefilter pre;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-        for (int dx = -1; dx <= 1; dx++) {
-            const int qx = x + dx, qy = y + dy;
-            if (qx < 0 || qy < 0 || qx >= a.width || qy >= a.height) continue;
-            pre.tap(tc[ci + dy * kTW + dx].w, dx, dy);
-        }
-    }
-    const float den = pre.den(a.sv2, a.floor);
-    AtrousVarSum sum;
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const int qx = x + dx, qy = y + dy;
-            if (qx < 0 || qy < 0 || qx >= a.width || qy >= a.height) continue;
-            const int qi = ci + dy * kTW + dx;
-            const AtrousPixel q{tc[qi], tx[qi], tn[qi]};
-            sum.tap(p, q, dx, dy, a.npow, a.sigma_plane, den);
-        }
-    }
-    const float4 r = sum.result(p);
-    if (!LAST) {
-        a.out[idx] = r;
-        return;
-    }
-    const float4 am = atrous_amod(a.albedo[idx]);
-    const f3 den3 = mk3(r.x * am.x, r.y * am.y, r.z * am.z);
-    a.out[idx] = make_float4(den3.x, den3.y, den3.z, 1.0f);
-    a.var_out[idx] = r.w;
-    if (a.ldr) {
-        const f3 col = aces_film(den3);
-        a.ldr[idx] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
-    }
+    atrous_pass<kHalo>(f, f.width, f.height, f.step);
 }
 
 }  // namespace
@@ -196,8 +116,8 @@ void launch_denoise_history(hipStream_t stream, const HistoryParams& hp, int nor
     HistoryArgs a;
     a.sum = sums;
     a.albedo = albedo;
-    a.position_t = position_t;
-    a.normal = normal;
+    a.x = position_t;
+    a.n = normal;
     a.pa = prev_a;
     a.pb = prev_b;
     a.px = prev_x;
@@ -220,24 +140,18 @@ void launch_atrous_history(hipStream_t stream, const AtrousParams& prm, const At
                            const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong, uint32_t* ldr, float* var_out)
 {
     if (width <= 0 || height <= 0) return;
-    AtrousPreArgs a;
-    a.in = iv;
-    a.position_t = position_t;
-    a.normal = normal;
-    a.albedo = albedo;
-    a.out = (prm.passes & 1) ? ping : pong;   // the last pass writes `ping` (launch_atrous' arrangement)
-    a.ldr = ldr;
-    a.var_out = var_out;
-    a.width = width;
-    a.height = height;
-    a.npow = prm.normal_power_log2;
-    a.sigma_plane = prm.sigma_plane;
-    a.sv2 = vprm.sigma_variance * vprm.sigma_variance;
-    a.floor = vprm.variance_floor;
-    const dim3 grid((unsigned)((width + kTileW - 1) / kTileW), (unsigned)((height + kTileH - 1) / kTileH)), block(kBlock);
-    if (prm.passes == 1) hipLaunchKernelGGL(atrous_var_pre_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(atrous_var_pre_kernel<false>, grid, block, 0, stream, a);
-    if (prm.passes > 1) launch_atrous_variance_from(stream, prm, vprm, width, height, 1, a.out, position_t, normal, albedo, ping, pong, ldr, var_out);
+    AtrousVarArgs a = atrous_var_args(prm, vprm, width, height, nullptr, 2u, position_t, normal, albedo, ldr, var_out);
+    const float4* i1 = atrous_launch_passes(0, 1, prm.passes, false, width, height, iv, ping, pong,
+                                            [&](auto halo, int, const float4* in, float4* out, bool last, dim3 grid, dim3 block) {
+                                                if constexpr (decltype(halo)::value == kHalo) {
+                                                    a.in = in;
+                                                    a.out = out;
+                                                    a.step = 1;
+                                                    if (last) hipLaunchKernelGGL(atrous_var_pre_kernel<true>, grid, block, 0, stream, AtrousVarFilter<false, true>{a});
+                                                    else hipLaunchKernelGGL(atrous_var_pre_kernel<false>, grid, block, 0, stream, AtrousVarFilter<false, false>{a});
+                                                }
+                                            });
+    launch_atrous_variance(stream, prm, vprm, width, height, 1, i1, nullptr, 2u, position_t, normal, albedo, ping, pong, ldr, var_out);
 }
 
 }  // namespace jpt
@@ -255,13 +169,7 @@ extern "C" int jpt_debug_denoise_history(int device, int32_t width, int32_t heig
     const bool have_prev = prev_integrated4 != nullptr;
     if ((prev_normal_s4 != nullptr) != have_prev || (prev_position_t != nullptr) != have_prev) return JPT_E_INVALID;   // a set is three planes
     if (have_prev && !same_view && !prev_vp16) return JPT_E_INVALID;
-    AtrousParams prm;
-    if (params) {
-        prm.passes = params->passes;
-        prm.normal_power_log2 = params->normal_power_log2;
-        prm.sigma_plane = params->sigma_plane;
-        prm.sigma_color = params->sigma_color;
-    }
+    const AtrousParams prm = denoise_params_of(params);
     HistoryParams hp;
     int32_t reserved[4] = {0, 0, 0, 0};
     if (hparams) {

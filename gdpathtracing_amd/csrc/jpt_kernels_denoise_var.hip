@@ -2,7 +2,7 @@
 // colour weight measured against the variance of the mean, which travels through the passes in the .w of the colour.  No reference
 // counterpart.  The arithmetic is pinned in jpt_denoise_var.h / DESIGN.md section 2; nothing here writes a buffer a render reads.
 #include "../../include/jpt.h"
-#include "jpt_denoise_var.h"
+#include "jpt_atrous_pass.h"
 #include "jpt_kernels.h"
 #include "jpt_trace_core.h"
 
@@ -10,198 +10,50 @@ namespace jpt {
 
 namespace {
 
-struct AtrousVarArgs {
-    const float4* __restrict__ in;        // FIRST: the accumulation (sums); else (i_k, v_k)
-    const float4* __restrict__ m2;        // FIRST: the plane of jpt_set_variance
-    const float4* __restrict__ position_t;
-    const float4* __restrict__ normal;
-    const float4* __restrict__ albedo;    // read by the first pass (demodulation) and the last (remodulation)
-    float4* __restrict__ out;             // (i_k+1, v_k+1); LAST: the denoised image (r, g, b, 1)
-    uint32_t* __restrict__ ldr;           // LAST: unorm8(ACES(denoised)) (may be null)
-    float* __restrict__ var_out;          // LAST: v of the last pass
-    int32_t width, height, step;
-    float nf, q;                          // FIRST: (float)frame_count and nf * (nf - 1)
-    int32_t npow;
-    float sigma_plane, sv2, floor;
-};
-
-constexpr int kTileW = 32, kTileH = 8, kAtrousBlock = kTileW * kTileH;
-
-template <bool FIRST>
-__device__ __forceinline__ float4 atrous_var_colour(const AtrousVarArgs& a, size_t idx)
-{
-    const float4 v = a.in[idx];
-    if (!FIRST) return v;
-    return atrous_var_first(v, a.m2[idx], a.nf, a.q, a.albedo[idx]);
-}
-
-template <bool LAST>
-__device__ __forceinline__ void atrous_var_write(const AtrousVarArgs& a, size_t idx, float4 r)
-{
-    if (!LAST) {
-        a.out[idx] = r;
-        return;
-    }
-    const float4 am = atrous_amod(a.albedo[idx]);
-    const f3 den = mk3(r.x * am.x, r.y * am.y, r.z * am.z);
-    a.out[idx] = make_float4(den.x, den.y, den.z, 1.0f);
-    a.var_out[idx] = r.w;
-    if (a.ldr) {
-        const f3 col = aces_film(den);
-        a.ldr[idx] = unorm8(col.x) | (unorm8(col.y) << 8) | (unorm8(col.z) << 16) | 0xFF000000u;
-    }
-}
-
-// One pass, atrous_kernel's shape: one lane per pixel, 32 x 8 pixels per block.  HALO = 2 * step > 0 (steps 1 and 2): the block stages
-// its tile and a HALO-pixel border of (colour, v), position_t and normal in LDS (the first pass demodulates and forms v_0 while it
-// stages, reading the plane once per staged pixel) and reads the 3 x 3 prefilter and its 25 taps from there -- the prefilter's
-// spacing is 1 and HALO >= 2 covers it.  HALO = 0 (steps >= 4): 16-byte gathers straight from memory, and nine 4-byte loads of v.
+// One pass (jpt_atrous_pass.h, whose AtrousVarFilter says what it reads and writes).  Tiled: the first pass demodulates and forms v_0
+// while it stages, reading the plane once per staged pixel, and the prefilter reads the staged v.  Gathered: nine 4-byte loads of v.
 template <int HALO, bool FIRST, bool LAST>
-__global__ __launch_bounds__(kAtrousBlock) void atrous_var_kernel(AtrousVarArgs a)
+__global__ __launch_bounds__(kAtrousBlock) void atrous_var_kernel(AtrousVarFilter<FIRST, LAST> f)
 {
     static_assert(HALO > 0 || !FIRST, "the first pass is a tiled one: the gather form reads v from the .w of its input");
-    const int lx = (int)threadIdx.x & (kTileW - 1), ly = (int)threadIdx.x / kTileW;
-    const int x0 = (int)blockIdx.x * kTileW, y0 = (int)blockIdx.y * kTileH;
-    const int x = x0 + lx, y = y0 + ly;
-    const bool inside = x < a.width && y < a.height;
-    const size_t idx = (size_t)y * (size_t)a.width + (size_t)x;
-    if (HALO > 0) {
-        constexpr int TW = kTileW + 2 * HALO, TH = kTileH + 2 * HALO, s = HALO / 2;
-        __shared__ float4 tc[TW * TH], tx[TW * TH], tn[TW * TH];
-        for (int i = (int)threadIdx.x; i < TW * TH; i += kAtrousBlock) {
-            const int gx = x0 - HALO + i % TW, gy = y0 - HALO + i / TW;
-            float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), px = c, nn = c;
-            if (gx >= 0 && gy >= 0 && gx < a.width && gy < a.height) {
-                const size_t g = (size_t)gy * (size_t)a.width + (size_t)gx;
-                c = atrous_var_colour<FIRST>(a, g);
-                px = a.position_t[g];
-                nn = a.normal[g];
-            }
-            tc[i] = c;
-            tx[i] = px;
-            tn[i] = nn;
-        }
-        __syncthreads();
-        if (!inside) return;
-        const int ci = (ly + HALO) * TW + (lx + HALO);
-        const AtrousPixel p{tc[ci], tx[ci], tn[ci]};
-        AtrousVarPrefilter pre;
-#pragma unroll
-        for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-            for (int dx = -1; dx <= 1; dx++) {
-                const int qx = x + dx, qy = y + dy;
-                if (qx < 0 || qy < 0 || qx >= a.width || qy >= a.height) continue;
-                pre.tap(tc[ci + dy * TW + dx].w, dx, dy);
-            }
-        }
-        const float den = pre.den(a.sv2, a.floor);
-        AtrousVarSum sum;
-#pragma unroll
-        for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-            for (int dx = -2; dx <= 2; dx++) {
-                const int qx = x + s * dx, qy = y + s * dy;
-                if (qx < 0 || qy < 0 || qx >= a.width || qy >= a.height) continue;
-                const int qi = ci + s * dy * TW + s * dx;
-                const AtrousPixel q{tc[qi], tx[qi], tn[qi]};
-                sum.tap(p, q, dx, dy, a.npow, a.sigma_plane, den);
-            }
-        }
-        atrous_var_write<LAST>(a, idx, sum.result(p));
-    } else {
-        if (!inside) return;
-        const int s = a.step;
-        const AtrousPixel p{atrous_var_colour<FIRST>(a, idx), a.position_t[idx], a.normal[idx]};
-        AtrousVarPrefilter pre;
-#pragma unroll
-        for (int dy = -1; dy <= 1; dy++) {
-#pragma unroll
-            for (int dx = -1; dx <= 1; dx++) {
-                const int qx = x + dx, qy = y + dy;
-                if (qx < 0 || qy < 0 || qx >= a.width || qy >= a.height) continue;
-                pre.tap(a.in[(size_t)qy * (size_t)a.width + (size_t)qx].w, dx, dy);
-            }
-        }
-        const float den = pre.den(a.sv2, a.floor);
-        AtrousVarSum sum;
-        for (int dy = -2; dy <= 2; dy++) {
-            const int qy = y + s * dy;
-            if (qy < 0 || qy >= a.height) continue;
-#pragma unroll
-            for (int dx = -2; dx <= 2; dx++) {
-                const int qx = x + s * dx;
-                if (qx < 0 || qx >= a.width) continue;
-                const size_t g = (size_t)qy * (size_t)a.width + (size_t)qx;
-                const AtrousPixel q{atrous_var_colour<FIRST>(a, g), a.position_t[g], a.normal[g]};
-                sum.tap(p, q, dx, dy, a.npow, a.sigma_plane, den);
-            }
-        }
-        atrous_var_write<LAST>(a, idx, sum.result(p));
-    }
-}
-
-template <int HALO, bool FIRST>
-void launch_var_pass(hipStream_t stream, const AtrousVarArgs& a, bool last)
-{
-    const dim3 grid((unsigned)((a.width + kTileW - 1) / kTileW), (unsigned)((a.height + kTileH - 1) / kTileH)), block(kAtrousBlock);
-    if (last) hipLaunchKernelGGL((atrous_var_kernel<HALO, FIRST, true>), grid, block, 0, stream, a);
-    else hipLaunchKernelGGL((atrous_var_kernel<HALO, FIRST, false>), grid, block, 0, stream, a);
+    atrous_pass<HALO>(f, f.width, f.height, f.step);
 }
 
 }  // namespace
 
-// passes first_pass .. passes - 1 of the filter; `src`: what pass first_pass reads (pass 0: the sums, with `m2` and `frame_count`)
-static void launch_var_passes(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass, const float4* src,
-                              const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
-                              float4* pong, uint32_t* ldr, float* var_out)
-{
-    if (width <= 0 || height <= 0) return;
-    AtrousVarArgs a;
-    a.m2 = m2;
-    a.position_t = position_t;
-    a.normal = normal;
-    a.albedo = albedo;
-    a.ldr = ldr;
-    a.var_out = var_out;
-    a.width = width;
-    a.height = height;
-    a.nf = (float)frame_count;
-    a.q = a.nf * (a.nf - 1.0f);
-    a.npow = prm.normal_power_log2;
-    a.sigma_plane = prm.sigma_plane;
-    a.sv2 = vprm.sigma_variance * vprm.sigma_variance;
-    a.floor = vprm.variance_floor;
-    // the last pass writes `ping` (launch_atrous' arrangement)
-    float4* dst = ((prm.passes - first_pass) & 1) ? ping : pong;
-    float4* other = ((prm.passes - first_pass) & 1) ? pong : ping;
-    for (int k = first_pass; k < prm.passes; k++) {
-        a.in = src;
-        a.out = dst;
-        a.step = 1 << k;
-        const bool last = k + 1 == prm.passes;
-        if (k == 0) launch_var_pass<2, true>(stream, a, last);
-        else if (k == 1) launch_var_pass<4, false>(stream, a, last);
-        else launch_var_pass<0, false>(stream, a, last);
-        src = dst;
-        float4* t = dst;
-        dst = other;
-        other = t;
-    }
-}
-
-void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, const float4* sums,
+void launch_atrous_variance(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass, const float4* src,
                             const float4* m2, uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* ping,
                             float4* pong, uint32_t* ldr, float* var_out)
 {
-    launch_var_passes(stream, prm, vprm, width, height, 0, sums, m2, frame_count, position_t, normal, albedo, ping, pong, ldr, var_out);
+    if (width <= 0 || height <= 0) return;
+    AtrousVarArgs a = atrous_var_args(prm, vprm, width, height, m2, frame_count, position_t, normal, albedo, ldr, var_out);
+    atrous_launch_passes(first_pass, prm.passes, prm.passes, false, width, height, src, ping, pong,
+                         [&](auto halo, int k, const float4* in, float4* out, bool last, dim3 grid, dim3 block) {
+                             constexpr int HALO = decltype(halo)::value;
+                             constexpr bool FIRST = HALO == 2;
+                             a.in = in;
+                             a.out = out;
+                             a.step = 1 << k;
+                             if (last) hipLaunchKernelGGL((atrous_var_kernel<HALO, FIRST, true>), grid, block, 0, stream, AtrousVarFilter<FIRST, true>{a});
+                             else hipLaunchKernelGGL((atrous_var_kernel<HALO, FIRST, false>), grid, block, 0, stream, AtrousVarFilter<FIRST, false>{a});
+                         });
 }
 
-void launch_atrous_variance_from(hipStream_t stream, const AtrousParams& prm, const AtrousVarParams& vprm, int width, int height, int first_pass,
-                                 const float4* src, const float4* position_t, const float4* normal, const float4* albedo, float4* ping, float4* pong,
-                                 uint32_t* ldr, float* var_out)
+// the whole filter on the host (jpt_debug_atrous_variance with JPT_DEVICE_HOST_ONLY): out = (i_passes * amod, 1), var_out = v_passes
+static void atrous_var_host(int32_t width, int32_t height, const AtrousParams& prm, const AtrousVarParams& vprm, const float4* sum4, const float4* m2,
+                            uint32_t frame_count, const float4* position_t, const float4* normal, const float4* albedo, float4* out, float* var_out)
 {
-    launch_var_passes(stream, prm, vprm, width, height, first_pass, src, nullptr, 2u, position_t, normal, albedo, ping, pong, ldr, var_out);
+    const size_t n = (size_t)width * height;
+    const float nf = (float)frame_count, q = nf * (nf - 1.0f);
+    std::vector<float4> a(n), b(n);
+    for (size_t i = 0; i < n; i++) a[i] = atrous_var_first(sum4[i], m2[i], nf, q, albedo[i]);
+    const AtrousVarTaps taps{prm.normal_power_log2, prm.sigma_plane, vprm.sigma_variance * vprm.sigma_variance, vprm.variance_floor};
+    const float4* r = atrous_passes_host(prm.passes, width, height, position_t, normal, a.data(), b.data(), [&](int) { return taps; });
+    for (size_t i = 0; i < n; i++) {
+        const float4 am = atrous_amod(albedo[i]);
+        out[i] = make_float4(r[i].x * am.x, r[i].y * am.y, r[i].z * am.z, 1.0f);
+        var_out[i] = r[i].w;
+    }
 }
 
 }  // namespace jpt
@@ -215,21 +67,9 @@ extern "C" int jpt_debug_atrous_variance(int device, int32_t width, int32_t heig
     if (!sum4 || !m2_4 || !position_t || !normal || !albedo || !out4 || !var_out || width <= 0 || height <= 0 || width > 65536 || height > 65536 ||
         frame_count < 2u)
         return JPT_E_INVALID;
-    AtrousParams prm;
-    if (params) {
-        prm.passes = params->passes;
-        prm.normal_power_log2 = params->normal_power_log2;
-        prm.sigma_plane = params->sigma_plane;
-        prm.sigma_color = params->sigma_color;
-    }
-    AtrousVarParams vprm;
+    const AtrousParams prm = denoise_params_of(params);
     int32_t reserved = 0;
-    if (vparams) {
-        vprm.enable = vparams->enable;
-        vprm.sigma_variance = vparams->sigma_variance;
-        vprm.variance_floor = vparams->variance_floor;
-        reserved = vparams->reserved;
-    }
+    const AtrousVarParams vprm = denoise_variance_params_of(vparams, reserved);
     std::string why;
     if (check_denoise_params(prm, why) != JPT_OK || check_denoise_variance_params(vprm, reserved, why) != JPT_OK) return JPT_E_INVALID;
     const size_t n = (size_t)width * height, bytes = n * sizeof(float4);
@@ -246,7 +86,7 @@ extern "C" int jpt_debug_atrous_variance(int device, int32_t width, int32_t heig
     bool ok = true;
     for (int k = 0; k < 5 && ok; k++) ok = hipMemcpy(buf + (size_t)k * n, in[k], bytes, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
-        launch_atrous_variance(nullptr, prm, vprm, width, height, buf, buf + n, frame_count, buf + 2 * n, buf + 3 * n, buf + 4 * n, buf + 5 * n, buf + 6 * n,
+        launch_atrous_variance(nullptr, prm, vprm, width, height, 0, buf, buf + n, frame_count, buf + 2 * n, buf + 3 * n, buf + 4 * n, buf + 5 * n, buf + 6 * n,
                                nullptr, var);
         ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out4, buf + 5 * n, bytes, hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(var_out, var, n * sizeof(float), hipMemcpyDeviceToHost) == hipSuccess;

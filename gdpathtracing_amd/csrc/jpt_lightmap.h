@@ -3,7 +3,8 @@
 // pass is traced: position4 / normal4 ARE the first hits), then a dilation that grows the charts outwards into the invalid texels.
 // No reference counterpart.  Everything is + - * /, sqrt (the normal's length, once per texel), fabs, compares and selects, one
 // binary32 operation each in source order: the device kernels (jpt_kernels_lightmap.hip) and the host form of jpt_debug_bake_finish
-// run these functions, and tests/np_lightmap.py restates them in float32 numpy bit for bit.
+// run these functions (the filter through the one pass body of jpt_atrous_pass.h), and tests/np_lightmap.py restates them in float32
+// numpy bit for bit.
 //
 // Corner cases, as settled here:
 //   * an invalid texel's guides are (0, 0, 0, -1) and (0, 0, 0, 0) whatever its images hold (NaN included); its colour is (0, 0, 0, 0)
@@ -135,6 +136,25 @@ struct LightmapSum {
     }
 };
 
+// what the pass body asks of this filter (AtrousTaps' members): an invalid centre is skipped, and the taps share the pass itself
+struct LightmapTaps {
+    using Pixel = LightmapTexel;
+    using Sum = LightmapSum;
+    using Prefilter = AtrousNoPrefilter;
+    LightmapPass ps;   // (ps.step: read by the gathered form alone; centre() sets the spacing the taps are at)
+    __host__ __device__ __forceinline__ bool skip(const float4& xg) const { return xg.w < 0.0f; }
+    __host__ __device__ __forceinline__ LightmapPass centre(int s, const Prefilter&) const
+    {
+        LightmapPass p = ps;
+        p.step = s;
+        return p;
+    }
+    __host__ __device__ __forceinline__ void tap(Sum& sum, const Pixel& p, const Pixel& q, int dx, int dy, const LightmapPass& c) const
+    {
+        sum.tap(p, q, dx, dy, c);
+    }
+};
+
 // ---- 3. dilate: one texel of one pass, reading only the previous pass's image ------------------------------------------------------------
 // A texel of state 0 with a neighbour of state > 0 and finite colour among its 8 takes their weighted mean (2 for the four edge
 // neighbours, 1 for the diagonals; dy = -1..1 outer, dx inner) and state 0.5; every other texel is copied.
@@ -158,66 +178,6 @@ __host__ __device__ __forceinline__ float4 lightmap_dilate(const float4* in, int
         }
     if (!(w > 0.0f)) return c;
     return make_float4(r / w, g / w, b / w, 0.5f);
-}
-
-// the whole transform on the host (jpt_debug_bake_finish with JPT_DEVICE_HOST_ONLY): out = (r, g, b, coverage)
-inline void lightmap_finish_host(int32_t width, int32_t height, const LightmapParams& prm, const float4* mean4, const float4* position4,
-                                 const float4* normal4, float4* out)
-{
-    const size_t n = (size_t)width * height;
-    float4* xg = new float4[n];
-    float4* ng = new float4[n];
-    float4* a = new float4[n];
-    float4* b = new float4[n];
-    for (int32_t y = 0; y < height; y++)
-        for (int32_t x = 0; x < width; x++) {
-            const size_t ip = (size_t)y * width + x;
-            lightmap_guides(position4, normal4, width, height, x, y, xg[ip], ng[ip]);
-            a[ip] = lightmap_colour0(mean4[ip], 1.0f, xg[ip]);
-        }
-    LightmapPass ps;
-    ps.npow = prm.normal_power_log2;
-    ps.sd2 = prm.sigma_distance * prm.sigma_distance;
-    ps.sp2 = prm.sigma_plane * prm.sigma_plane;
-    float sc = prm.sigma_color;
-    for (int k = 0; k < prm.passes; k++, sc = sc * 0.5f) {
-        ps.step = 1 << k;
-        ps.sc2 = sc * sc;
-        for (int32_t y = 0; y < height; y++)
-            for (int32_t x = 0; x < width; x++) {
-                const size_t ip = (size_t)y * width + x;
-                if (xg[ip].w < 0.0f) {
-                    b[ip] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                    continue;
-                }
-                const LightmapTexel p{a[ip], xg[ip], ng[ip]};
-                LightmapSum sum;
-                for (int dy = -2; dy <= 2; dy++)
-                    for (int dx = -2; dx <= 2; dx++) {
-                        const int64_t qx = (int64_t)x + (int64_t)ps.step * dx, qy = (int64_t)y + (int64_t)ps.step * dy;
-                        if (qx < 0 || qy < 0 || qx >= width || qy >= height) continue;
-                        const size_t iq = (size_t)qy * width + (size_t)qx;
-                        const LightmapTexel q{a[iq], xg[iq], ng[iq]};
-                        sum.tap(p, q, dx, dy, ps);
-                    }
-                b[ip] = sum.result(p);
-            }
-        float4* t = a;
-        a = b;
-        b = t;
-    }
-    for (int k = 0; k < prm.dilate; k++) {
-        for (int32_t y = 0; y < height; y++)
-            for (int32_t x = 0; x < width; x++) b[(size_t)y * width + x] = lightmap_dilate(a, width, height, x, y);
-        float4* t = a;
-        a = b;
-        b = t;
-    }
-    for (size_t i = 0; i < n; i++) out[i] = a[i];
-    delete[] xg;
-    delete[] ng;
-    delete[] a;
-    delete[] b;
 }
 
 }  // namespace jpt

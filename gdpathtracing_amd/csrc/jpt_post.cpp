@@ -205,13 +205,7 @@ extern "C" {
 int jpt_set_denoise_params(jpt_ctx* c, const jpt_denoise_params* params)
 {
     if (!c) return JPT_E_INVALID;
-    AtrousParams p;
-    if (params) {
-        p.passes = params->passes;
-        p.normal_power_log2 = params->normal_power_log2;
-        p.sigma_plane = params->sigma_plane;
-        p.sigma_color = params->sigma_color;
-    }
+    const AtrousParams p = denoise_params_of(params);
     std::string why;
     const int rc = check_denoise_params(p, why);
     if (rc != JPT_OK) return fail(c, rc, why);
@@ -281,7 +275,7 @@ int jpt_denoise(jpt_ctx* c)
             launch_atrous_history(s, q.dn_params, q.dn_var, c->width, c->height, q.d_dh_iv.p, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
                                   q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
         } else if (guided)
-            launch_atrous_variance(s, q.dn_params, q.dn_var, c->width, c->height, c->d_accum.p, q.d_variance.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
+            launch_atrous_variance(s, q.dn_params, q.dn_var, c->width, c->height, 0, c->d_accum.p, q.d_variance.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
                                    q.d_dn_alb.p, q.d_dn_ping.p, q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
         else
             launch_atrous(s, q.dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
@@ -351,14 +345,8 @@ int jpt_read_denoise_history_f32(jpt_ctx* c, float* integrated4, float* length)
 int jpt_set_denoise_variance(jpt_ctx* c, const jpt_denoise_variance_params* params)
 {
     if (!c) return JPT_E_INVALID;
-    AtrousVarParams p;
     int32_t reserved = 0;
-    if (params) {
-        p.enable = params->enable;
-        p.sigma_variance = params->sigma_variance;
-        p.variance_floor = params->variance_floor;
-        reserved = params->reserved;
-    }
+    const AtrousVarParams p = denoise_variance_params_of(params, reserved);
     std::string why;
     const int rc = check_denoise_variance_params(p, reserved, why);
     if (rc != JPT_OK) return fail(c, rc, why);
