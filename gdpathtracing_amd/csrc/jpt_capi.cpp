@@ -2108,6 +2108,10 @@ int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounce
         if (c->post.sized_buffers()) HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->post.framebuffers_remade(true);
         c->primary.sh_valid = c->primary.refl_valid = false;   // (jpt_probe_project's coefficients and jpt_reflection_prefilter's chain likewise)
+        // the temporal history is of the old size too (a new TemporalReprojection object): zeros at the next pass, and nothing to
+        // read until then -- the pixel count alone does not tell (32 x 32 -> 16 x 64), and hist_written is sized by the old one
+        c->hist_valid = false;
+        c->hist_written = nullptr;
     }
     c->width = width;
     c->height = height;
@@ -2188,6 +2192,7 @@ int jpt_accum_reset(jpt_ctx* c)
     c->stats.frames = 0;
     c->assembled = c->assembled_ldr = false;
     c->hist_valid = false;  // temporal mode: history images start from zero again (a new TemporalReprojection object)
+    c->hist_written = nullptr;   // (and jpt_read_accum_f32 has nothing to show until a pass has run)
     return JPT_OK;
 }
 
@@ -2213,6 +2218,7 @@ int jpt_set_denoising_mode(jpt_ctx* c, int32_t mode)
         c->accum_restarts++;
         c->stats.frames = 0;
         c->hist_valid = false;
+        c->hist_written = nullptr;
         c->assembled = c->assembled_ldr = false;
     }
     c->denoise = mode;

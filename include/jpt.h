@@ -900,7 +900,9 @@ int jpt_render_async(jpt_ctx *ctx, int32_t n_frames, uint32_t first_frame_index)
 int jpt_sync(jpt_ctx *ctx);
 
 /* replaces: camera_moved -> frame_count = 1 (progressive_rendering.cpp:53-57).  In temporal mode: the history
- * images start from zero again, as for a newly created TemporalReprojection (temporal_reprojection.cpp:42-43). */
+ * images start from zero again, as for a newly created TemporalReprojection (temporal_reprojection.cpp:42-43), and
+ * jpt_read_accum_f32 answers JPT_E_STATE until the next pass has written one.  A change of mode and jpt_set_params with
+ * another width or height do the same. */
 int jpt_accum_reset(jpt_ctx *ctx);
 /* replaces: the frame_count word of ProgressiveRendering's Params (progressive_rendering.cpp:53-61, read at
  * progressive_rendering.glsl:34,39), for hosts that keep that counter themselves (the gdcs-shaped adapter hands over

@@ -178,10 +178,11 @@ def sky(d):  # M:189-192
     return lo * (1 - t[..., None]) + hi * t[..., None]
 
 
-def temporal_reproject(delta_colmajor, frame_count, screen_u8, depth, fb1, fb2):
+def temporal_reproject(delta_colmajor, frame_count, screen_u8, depth, fb1, fb2, detail=None):
     """temporal_reprojection.glsl:30-72 (T) vectorised in float32, one operation per numpy call so the rounding
     sequence is the shader's.  Returns (new_screen u8, written history f32, which) with which = 1 or 2 for the
-    history image written."""
+    history image written.  detail: a dict that receives u * W, v * H, the texel (px, py), `inside` (the texel is in the image) and `taken`
+    (inside and within the depth threshold: the pixel takes history); left empty when frame_count is 0."""
     f = np.float32
     H, W = depth.shape
     m = np.asarray(delta_colmajor, dtype=f)
@@ -205,7 +206,10 @@ def temporal_reproject(delta_colmajor, frame_count, screen_u8, depth, fb1, fb2):
             px, py = to_int(u * f(W)), to_int(v * f(H))
             ok = (px >= 0) & (px < W) & (py >= 0) & (py < H)               # T:59
             pxc, pyc = np.clip(px, 0, W - 1), np.clip(py, 0, H - 1)
+            inside = ok.copy()
             ok &= np.abs(depth[pyc, pxc] - cz) < f(0.1)
+            if detail is not None:   # the pass's own intermediates, for tests that assert what a case exercises
+                detail.update(uw=u * f(W), vh=v * f(H), px=px, py=py, inside=inside, taken=ok, cz=cz)
             rep[ok] = prev[pyc, pxc][..., :3][ok]                          # T:60
     blended = cur * (f(1.0) - f(0.75)) + rep * f(0.75)                     # T:64 mix()
     hist = np.concatenate([blended, np.ones((H, W, 1), f)], axis=-1)       # T:66
