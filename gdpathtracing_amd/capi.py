@@ -50,15 +50,16 @@ SYMBOLS = [
     "jpt_abi_version", "jpt_create", "jpt_destroy", "jpt_last_error", "jpt_set_stream", "jpt_get_stream", "jpt_set_stream_priority", "jpt_renders_in_flight", "jpt_set_memory_policy", "jpt_get_workspace_bytes",
     "jpt_scene_upload_reference_layout", "jpt_set_upload_mode", "jpt_scene_tree_kind", "jpt_scene_upload_note", "jpt_scene_ties_exact", "jpt_scene_begin", "jpt_scene_add_mesh", "jpt_scene_add_instance",
     "jpt_scene_set_materials", "jpt_scene_set_textures", "jpt_scene_commit", "jpt_scene_get_reference_buffer",
-    "jpt_scene_set_instance_transform", "jpt_scene_update_tlas", "jpt_scene_refit_tlas", "jpt_scene_update_reference_tlas", "jpt_scene_update_mesh",
+    "jpt_scene_set_instance_transform", "jpt_scene_update_tlas", "jpt_scene_refit_tlas", "jpt_scene_rebuild_tlas", "jpt_scene_update_reference_tlas", "jpt_scene_update_mesh",
     "jpt_set_params", "jpt_set_kernel", "jpt_set_debug_steps", "jpt_set_kernel_timing", "jpt_set_partition", "jpt_set_camera", "jpt_render", "jpt_render_counted", "jpt_render_async",
     "jpt_sync", "jpt_accum_reset", "jpt_set_progressive_frame_count", "jpt_set_denoising_mode", "jpt_set_temporal_params", "jpt_set_outputs", "jpt_read_ldr_rgba8", "jpt_readback_ldr_begin", "jpt_readback_ldr_end", "jpt_read_accum_f32", "jpt_read_depth_f32",
     "jpt_device_accum", "jpt_assemble_from_ranks", "jpt_device_ldr", "jpt_assemble_ldr_from_ranks", "jpt_local_rows", "jpt_get_stats",
     "jpt_scene_share", "jpt_multi_create", "jpt_multi_destroy", "jpt_multi_last_error", "jpt_multi_world", "jpt_multi_ctx",
-    "jpt_multi_share_scene", "jpt_multi_set_instance_transform", "jpt_multi_update_tlas", "jpt_multi_refit_tlas",
+    "jpt_multi_share_scene", "jpt_multi_set_instance_transform", "jpt_multi_update_tlas", "jpt_multi_refit_tlas", "jpt_multi_rebuild_tlas",
     "jpt_multi_update_reference_tlas", "jpt_multi_update_mesh", "jpt_multi_set_params", "jpt_multi_set_camera", "jpt_multi_accum_reset", "jpt_multi_set_gather",
     "jpt_multi_render", "jpt_multi_sync", "jpt_multi_gather_plan", "jpt_multi_read_ldr_rgba8", "jpt_multi_read_accum_f32",
     "jpt_debug_quantize_nodes4", "jpt_debug_node_step4", "jpt_debug_last_error", "jpt_debug_mesh_records",
+    "jpt_debug_tlas_order", "jpt_debug_tlas_template", "jpt_debug_tlas_records",
     "jpt_set_environment", "jpt_set_environment_params", "jpt_multi_set_environment", "jpt_multi_set_environment_params",
     "jpt_debug_env_lookup",
     "jpt_set_environment_sampling", "jpt_multi_set_environment_sampling", "jpt_debug_env_tables", "jpt_debug_env_sample", "jpt_debug_env_pdf",
@@ -343,6 +344,7 @@ def lib():
     L.jpt_scene_set_instance_transform.argtypes = [vp, u32, vp]
     L.jpt_scene_update_tlas.argtypes = [vp]
     L.jpt_scene_refit_tlas.argtypes = [vp, vp, u32]
+    L.jpt_scene_rebuild_tlas.argtypes = [vp, vp, u32]
     L.jpt_scene_update_reference_tlas.argtypes = [vp, vp, u32, vp, u32]
     L.jpt_scene_update_mesh.argtypes = [vp, u32, C.POINTER(Surface), i32]
     L.jpt_set_params.argtypes = [vp, i32, i32, i32, i32, i32]
@@ -390,6 +392,7 @@ def lib():
     L.jpt_multi_set_instance_transform.argtypes = [vp, u32, vp]
     L.jpt_multi_update_tlas.argtypes = [vp]
     L.jpt_multi_refit_tlas.argtypes = [vp, vp, u32]
+    L.jpt_multi_rebuild_tlas.argtypes = [vp, vp, u32]
     L.jpt_multi_update_reference_tlas.argtypes = [vp, vp, u32, vp, u32]
     L.jpt_multi_update_mesh.argtypes = [vp, u32, C.POINTER(Surface), i32]
     L.jpt_multi_set_params.argtypes = [vp, i32, i32, i32, i32, i32]
@@ -405,6 +408,9 @@ def lib():
     L.jpt_debug_node_step4.argtypes = [C.c_int, vp, u32, vp, u32, i32, vp]
     L.jpt_debug_last_error.restype = C.c_char_p
     L.jpt_debug_mesh_records.argtypes = [vp, u32, vp, vp, u32, vp, vp, u32, C.POINTER(i32)]
+    L.jpt_debug_tlas_order.argtypes = [C.c_int, vp, vp, u32, vp, vp]
+    L.jpt_debug_tlas_template.argtypes = [u32, vp, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.jpt_debug_tlas_records.argtypes = [vp, vp, vp, u32, C.POINTER(u32), C.POINTER(i32), vp, vp]
     L.jpt_set_environment.argtypes = [vp, vp, i32, i32]
     L.jpt_set_environment_params.argtypes = [vp, vp, C.c_float]
     L.jpt_multi_set_environment.argtypes = [vp, vp, i32, i32]

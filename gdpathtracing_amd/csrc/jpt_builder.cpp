@@ -1938,6 +1938,12 @@ void refit4_schedule(const std::vector<WideNode4>& nodes, int32_t root, std::vec
     }
 }
 
+uint32_t stack_need4_under(const std::vector<WideNode4>& nodes, int32_t root)
+{
+    std::vector<int32_t> memo(nodes.size(), -1);
+    return need4(nodes, root, memo);
+}
+
 void compute_stack_need(WideScene& out)
 {
     {

@@ -177,6 +177,9 @@ void tlas4_refit_schedule(const WideScene& w, std::vector<uint32_t>& order, std:
 // The same for the records under `root` of any four-child array (a mesh's BLAS for jpt_scene_update_mesh): APPENDS the levels to
 // `order` and their ends to `level_start` (whose last entry is where they start)
 void refit4_schedule(const std::vector<WideNode4>& nodes, int32_t root, std::vector<uint32_t>& order, std::vector<uint32_t>& level_start);
+// The pending entries a near-first walk of the four-child records under `root` can need (compute_stack_need's figure for one tree:
+// WideScene::stack_need4 is this for the TLAS, + 1, + the largest of the instances' BLASes)
+uint32_t stack_need4_under(const std::vector<WideNode4>& nodes, int32_t root);
 
 // Reference layout -> flattened layout.  Keeps topology, boxes and child order, so traversal visits the
 // same nodes in the same order as main.glsl:270-350 does on the reference arrays.

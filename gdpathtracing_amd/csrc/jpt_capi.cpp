@@ -144,6 +144,10 @@ int upload_nodes4(jpt_ctx* c, bool tlas_only)
     c->cur_set = 0;
     c->set_b_ready = false;  // the instance arrays of the other copies are made (again) by the next refit
     for (bool& v : c->set_retired_valid) v = false;
+    // every tail gets the host's topology again: the refits run over its schedule until the next jpt_scene_rebuild_tlas
+    c->topo_rebuilt = false;
+    c->topo_gen = 0;
+    for (uint32_t& g : c->set_topo_gen) g = 0;
     if (w.instances4.empty() && nb == 0) return JPT_OK;
     auto quantised = [](const std::vector<WideNode4>& in) {
         std::vector<WideNodeQ> out(in.size());
@@ -1478,10 +1482,43 @@ int ensure_refit_stream(jpt_ctx* c)
     return JPT_OK;
 }
 
+// The template of jpt_scene_rebuild_tlas for `n` instances (jpt_tlas_rebuild.h) with its refit schedule and stack need, on the host
+// and on the device, and the sort's buffers: made at the first rebuild of this instance count (the host waits for the copies, once)
+// and kept.  A count that changes comes with a new scene, whose upload the refit stream has long finished for; it is drained all the same.
+int ensure_tlas_template(jpt_ctx* c, uint32_t n)
+{
+    if (c->tlas_tmpl.n != n) {
+        make_tlas_template(n, c->tlas_tmpl);
+        std::vector<uint32_t> identity(n);
+        for (uint32_t i = 0; i < n; i++) identity[i] = i;
+        std::vector<WideNode4> records;
+        tlas_template_records(c->tlas_tmpl, identity.data(), records);
+        c->tmpl_order_h.clear();
+        c->tmpl_levels_h.assign(1, 0u);
+        refit4_schedule(records, 0, c->tmpl_order_h, c->tmpl_levels_h);
+        c->tmpl_stack_need = stack_need4_under(records, 0);
+        HIP_TRY(c, hipStreamSynchronize(c->refit_stream));
+        c->d_tmpl_child.release();   // (made again below)
+    }
+    if (c->d_tmpl_child.p) return JPT_OK;
+    hipStream_t rs = c->refit_stream;
+    HIP_TRY(c, c->d_tmpl_child.upload(c->tlas_tmpl.child, rs));
+    HIP_TRY(c, c->d_tmpl_order.upload(c->tmpl_order_h, rs));
+    HIP_TRY(c, c->d_tmpl_levels.upload(c->tmpl_levels_h, rs));
+    HIP_TRY(c, c->d_tlas_sorted.resize(n));
+    HIP_TRY(c, c->d_tlas_sort_keys.resize(n > kTlasLdsKeys ? 2 * (size_t)n : 0));
+    HIP_TRY(c, hipStreamSynchronize(rs));   // pageable host vectors
+    return JPT_OK;
+}
+
 // Instance records and TLAS boxes from the transforms at `dev_view` (n_instances x 12 floats the device can read), written into the
 // copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
 // from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
-int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances)
+// `rebuild_sorted` (jpt_scene_rebuild_tlas; ensure_tlas_template has run): the copy also gets a new topology, the template's over the
+// instances sorted on the device, and the host's mirror of the records (c->wide, the schedule) becomes the template over
+// rebuild_sorted, boxes not yet refitted.  Every later refit then runs over the template's schedule, and one into a copy whose tail
+// still holds an older topology first copies the current copy's tail.
+int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances, const uint32_t* rebuild_sorted = nullptr)
 {
     lights_stale(c, false);
     hipStream_t s = c->stream;
@@ -1526,9 +1563,28 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
     a.nodes4 = b.nodes4.p;
     a.nodesq = b.nodesq.p;
     a.n_blas_records = (uint32_t)(c->wide.blas_nodes4.size() + (size_t)next * c->tlas4_cap);
+    if (rebuild_sorted) {
+        WideScene& w = c->wide;
+        const uint32_t blas_need = w.stack_need4 - 1u - stack_need4_under(w.tlas_nodes4, w.tlas_root4);
+        tlas_template_records(c->tlas_tmpl, rebuild_sorted, w.tlas_nodes4);
+        w.tlas_root4 = 0;
+        w.stack_need4 = c->tmpl_stack_need + 1u + blas_need;
+        c->tlas4_order_h = c->tmpl_order_h;
+        c->tlas4_levels_h = c->tmpl_levels_h;
+        c->n_tlas4_levels = (uint32_t)c->tmpl_levels_h.size() - 1u;
+        c->topo_rebuilt = true;
+        c->set_topo_gen[next] = ++c->topo_gen;
+        a.rebuild_child = c->d_tmpl_child.p;
+        a.sorted = c->d_tlas_sorted.p;
+        a.sort_scratch = c->d_tlas_sort_keys.p;
+    } else if (c->set_topo_gen[next] != c->topo_gen) {
+        a.copy_tail = true;
+        a.copy_from = (uint32_t)(c->wide.blas_nodes4.size() + (size_t)c->cur_set * c->tlas4_cap);
+        c->set_topo_gen[next] = c->topo_gen;
+    }
     a.n_tlas_records = (uint32_t)c->wide.tlas_nodes4.size();
-    a.order = c->d_tlas4_order.p;
-    a.level_start = c->d_tlas4_levels.p;
+    a.order = c->topo_rebuilt ? c->d_tmpl_order.p : c->d_tlas4_order.p;
+    a.level_start = c->topo_rebuilt ? c->d_tmpl_levels.p : c->d_tlas4_levels.p;
     a.n_levels = c->n_tlas4_levels;
     launch_tlas4_refit(rs, a);
     HIP_TRY(c, hipGetLastError());
@@ -1575,11 +1631,15 @@ int jpt_scene_update_tlas(jpt_ctx* c)
     return rc;
 }
 
-int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
+namespace {
+
+// jpt_scene_refit_tlas and jpt_scene_rebuild_tlas (`rebuild`; `call`: the name for the state message): the same checks, staging and
+// side effects; the rebuild also gives the copy it writes a new topology
+int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, bool rebuild, const char* call)
 {
     if (!c) return JPT_E_INVALID;
     if (!c->host_scene_ready || c->building || !walks_nodes4(c) || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas needs a scene made by jpt_scene_commit with the native builder");
+        return fail(c, JPT_E_STATE, std::string(call) + " needs a scene made by jpt_scene_commit with the native builder");
     if (!transforms12 && n_instances) return fail(c, JPT_E_INVALID, "null transforms");
     if (n_instances != c->ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the refit runs on the device (jpt_scene_update_tlas is the host route)");
@@ -1588,8 +1648,40 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     c->tlas_dirty = true;
     if (!c->ds.use4 || !c->scene_ready) return jpt_scene_update_tlas(c);  // no four-child records to refit
     if (n_instances == 0) return JPT_OK;
+    if (n_instances <= 1) rebuild = false;   // one instance is its own order
+    if (rebuild && n_instances > kTlasRebuildMaxInstances)
+        return fail(c, JPT_E_LIMIT, "jpt_scene_rebuild_tlas sorts at most " + std::to_string(kTlasRebuildMaxInstances) + " instances");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_refit_stream(c);
+    if (rc != JPT_OK) return rc;
+    // The host's side of a rebuild, before anything is written.  For a modest number of instances the host repeats the sort on its
+    // own root-rule boxes (the mirror below): its order may differ from the device's, whose boxes are tightened by the cuts, but
+    // every instance is under the mirror's root, which is all the sky cull asks.  Beyond that the mirror's leaves are in index order
+    // and the cull is off.
+    const bool mirror = n_instances <= 4096u && !c->mesh_deformed;
+    std::vector<RefInstance> boxes;
+    if (mirror) {
+        boxes.resize(n_instances);
+        for (uint32_t i = 0; i < n_instances; i++) {
+            const RefBvhNode& root = c->ref.bvh_nodes[c->ref.instances[i].blas_index];
+            instance_record(transforms12 + (size_t)i * 12, root.aabbMin, root.aabbMax, true, boxes[i]);
+        }
+    }
+    std::vector<uint32_t> sorted;
+    if (rebuild) {
+        rc = ensure_tlas_template(c, n_instances);
+        if (rc != JPT_OK) return rc;
+        const WideScene& w = c->wide;
+        const uint32_t need = w.stack_need4 - stack_need4_under(w.tlas_nodes4, w.tlas_root4) + c->tmpl_stack_need;
+        if (need > trace_stack_capacity())
+            return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the TLAS rebuild: a traversal could need " + std::to_string(need) +
+                                            " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
+        sorted.resize(n_instances);
+        if (mirror) tlas_order_host(&boxes[0].aabbMin.x, &boxes[0].aabbMax.x, sizeof(RefInstance) / sizeof(float), n_instances, nullptr, sorted.data());
+        else
+            for (uint32_t i = 0; i < n_instances; i++) sorted[i] = i;
+    }
     const size_t bytes = (size_t)n_instances * 12 * sizeof(float);
     int st = 0;
     HIP_TRY(c, c->refit_stage.next(bytes, st));
@@ -1597,8 +1689,7 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     // the kernel reads the transforms straight from the pinned buffer (48 B per instance over the host link)
     float* dev_view = nullptr;
     HIP_TRY(c, hipHostGetDevicePointer((void**)&dev_view, c->refit_stage.buf[st].p, 0));
-    int rc = ensure_refit_stream(c);
-    if (rc == JPT_OK) rc = queue_instance_refit(c, dev_view, n_instances);
+    rc = queue_instance_refit(c, dev_view, n_instances, rebuild ? sorted.data() : nullptr);
     if (rc != JPT_OK) return rc;
     HIP_TRY(c, hipEventRecord(c->refit_stage.copied[st], c->refit_stream));
     // The sky cull (compute_sky_cull) projects the boxes the TLAS root offers, on the host.  For a modest number of
@@ -1607,13 +1698,8 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     // boxes contain the device's (safe for the cull) but are looser.  Beyond that the cull is off until the next
     // jpt_scene_update_tlas.  After jpt_scene_update_mesh the host's root boxes are the committed vertices': off until the next
     // jpt_scene_commit.
-    if (n_instances <= 4096u && !c->tlas4_levels_h.empty() && !c->mesh_deformed) {
+    if (mirror && !c->tlas4_levels_h.empty()) {
         WideScene& w = c->wide;
-        std::vector<RefInstance> boxes(n_instances);
-        for (uint32_t i = 0; i < n_instances; i++) {
-            const RefBvhNode& root = c->ref.bvh_nodes[c->ref.instances[i].blas_index];
-            instance_record(transforms12 + (size_t)i * 12, root.aabbMin, root.aabbMax, true, boxes[i]);
-        }
         for (size_t l = 0; l + 1 < c->tlas4_levels_h.size(); l++)
             for (uint32_t k = c->tlas4_levels_h[l]; k < c->tlas4_levels_h[l + 1]; k++)
                 refit_slots(w.tlas_nodes4[c->tlas4_order_h[k]], w.tlas_nodes4.data(), [&](int32_t ref, float* lo, float* hi) {
@@ -1629,6 +1715,18 @@ int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_insta
     c->ds.x.tlas_current = false;   // the copy of the reference's instance level is the last HOST update's: until the next one exact ties are decided inside one instance only (jpt_tie_walk.h)
     c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return JPT_OK;
+}
+
+}  // namespace
+
+int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
+{
+    return move_instances(c, transforms12, n_instances, false, "jpt_scene_refit_tlas");
+}
+
+int jpt_scene_rebuild_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
+{
+    return move_instances(c, transforms12, n_instances, true, "jpt_scene_rebuild_tlas");
 }
 
 namespace {
@@ -1990,6 +2088,46 @@ int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void*
         HIP_TRY(c, hipMemcpy(nodesq_out, c->dev.nodesq.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
     if (tris_out) HIP_TRY(c, hipMemcpy(tris_out, c->dev.wtris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(WideTri), hipMemcpyDeviceToHost));
     if (shade_out) HIP_TRY(c, hipMemcpy(shade_out, c->dev.shade_tris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(ShadeTri), hipMemcpyDeviceToHost));
+    return JPT_OK;
+}
+
+int jpt_debug_tlas_records(jpt_ctx* c, void* nodes4_out, void* nodesq_out, uint32_t capacity, uint32_t* n_records, int32_t* root_out, float* inst_lo3,
+                           float* inst_hi3)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!c->host_scene_ready || c->building || !walks_nodes4(c) || !c->from_commit)
+        return fail(c, JPT_E_STATE, "jpt_debug_tlas_records needs a scene made by jpt_scene_commit with the native builder");
+    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the records are on the device");
+    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
+    const size_t nt = c->wide.tlas_nodes4.size(), ni = c->ref.instances.size();
+    const int32_t base = (int32_t)(c->wide.blas_nodes4.size() + (size_t)c->cur_set * c->tlas4_cap);
+    if (n_records) *n_records = (uint32_t)nt;
+    if (root_out) *root_out = c->ds.tlas_root4 >= 0 ? c->ds.tlas_root4 - base : c->ds.tlas_root4;
+    if ((nodes4_out || nodesq_out) && capacity < nt) return fail(c, JPT_E_INVALID, "record buffers too small");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the context's stream follows every refit)
+    if (nodes4_out && nt) {
+        HIP_TRY(c, hipMemcpy(nodes4_out, c->dev.nodes4.p + base, nt * sizeof(WideNode4), hipMemcpyDeviceToHost));
+        WideNode4* r = static_cast<WideNode4*>(nodes4_out);
+        for (size_t i = 0; i < nt; i++)
+            for (int k = 0; k < 4; k++)
+                if (r[i].child[k] >= 0) r[i].child[k] -= base;
+    }
+    if (nodesq_out && nt) {
+        HIP_TRY(c, hipMemcpy(nodesq_out, c->dev.nodesq.p + base, nt * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
+        WideNodeQ* r = static_cast<WideNodeQ*>(nodesq_out);
+        for (size_t i = 0; i < nt; i++)
+            for (int k = 0; k < 4; k++)
+                if (r[i].child[k] >= 0) r[i].child[k] -= base;
+    }
+    if ((inst_lo3 || inst_hi3) && ni) {
+        std::vector<RefInstance> inst(ni);
+        HIP_TRY(c, hipMemcpy(inst.data(), c->dev.set[c->cur_set].inst.p, ni * sizeof(RefInstance), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < ni; i++) {
+            if (inst_lo3) inst_lo3[3 * i] = inst[i].aabbMin.x, inst_lo3[3 * i + 1] = inst[i].aabbMin.y, inst_lo3[3 * i + 2] = inst[i].aabbMin.z;
+            if (inst_hi3) inst_hi3[3 * i] = inst[i].aabbMax.x, inst_hi3[3 * i + 1] = inst[i].aabbMax.y, inst_hi3[3 * i + 2] = inst[i].aabbMax.z;
+        }
+    }
     return JPT_OK;
 }
 

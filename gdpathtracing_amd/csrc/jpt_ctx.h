@@ -12,6 +12,7 @@
 #include "jpt_display.h"
 #include "jpt_lightmap.h"
 #include "jpt_meter.h"
+#include "jpt_tlas_rebuild.h"
 #include "jpt_variance.h"
 #include "jpt_kernels.h"
 
@@ -432,6 +433,19 @@ struct jpt_ctx {
     bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
     bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
     std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
+    // a new topology made on the device (jpt_scene_rebuild_tlas): the template of the scene's instance count with its schedule and the
+    // sort's buffers, made at the first rebuild of that count and kept.  After a rebuild c->wide.tlas_nodes4 / tlas_root4 / stack_need4
+    // and the schedule's host copy above are the template's, and the refits run over tmpl_order / tmpl_levels (topo_rebuilt), until
+    // the next upload.  topo_gen counts the rebuilds since the last upload; set_topo_gen[k]: the one whose topology the TLAS tail of
+    // copy k holds (a refit into a copy that is behind first copies the current copy's tail: queue_instance_refit).
+    TlasTemplate tlas_tmpl;
+    std::vector<uint32_t> tmpl_order_h, tmpl_levels_h;
+    uint32_t tmpl_stack_need = 0;
+    DevBuf<int32_t> d_tmpl_child;
+    DevBuf<uint32_t> d_tmpl_order, d_tmpl_levels, d_tlas_sorted;
+    DevBuf<uint64_t> d_tlas_sort_keys;
+    bool topo_rebuilt = false;
+    uint32_t topo_gen = 0, set_topo_gen[kInstanceSets] = {};
     // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in dev.nodes4 and its schedule
     // (refit4_schedule), made at the first update after an upload
     struct MeshRefit {

@@ -19,11 +19,13 @@
 
 #include "jpt_encode.h"
 #include "jpt_atrous_pass.h"
+#include "jpt_builder.h"
 #include "jpt_instance_math.h"
 #include "jpt_kernels.h"
 #include "jpt_lightmap.h"
 #include "jpt_nodeq.h"
 #include "jpt_primary_ray.h"
+#include "jpt_tlas_rebuild.h"
 #include "jpt_trace_core.h"
 
 using namespace jpt;
@@ -1098,6 +1100,75 @@ int jpt_debug_env_pdf(int device_id, const float* rgb, int32_t width, int32_t he
                       float* pdf_out)
 {
     return env_sampling_debug(device_id, rgb, width, height, rotation9, 2, dirs3, n, nullptr, pdf_out, nullptr, nullptr, nullptr);
+}
+
+int jpt_debug_tlas_order(int device_id, const float* lo3, const float* hi3, uint32_t n, uint64_t* keys_out, uint32_t* sorted_instances_out)
+{
+    if (n == 0) return JPT_OK;
+    if (!lo3 || !hi3 || !sorted_instances_out) {
+        g_debug_error = "jpt_debug_tlas_order: null argument";
+        return JPT_E_INVALID;
+    }
+    if (n > kTlasRebuildMaxInstances) {
+        g_debug_error = "jpt_debug_tlas_order: more than 32767 instances";
+        return JPT_E_LIMIT;
+    }
+    if (device_id < 0) {
+        tlas_order_host(lo3, hi3, 3, n, keys_out, sorted_instances_out);
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the keys (n), the sort's two buffers (2 n), the boxes (6 n floats), the order (n words)
+    const size_t b_keys = (size_t)n * 8, b_box = (size_t)n * 12;
+    char* d_all = nullptr;
+    if ((e = hipMalloc((void**)&d_all, 3 * b_keys + 2 * b_box + (size_t)n * 4)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    uint64_t* d_keys = reinterpret_cast<uint64_t*>(d_all);
+    float* d_lo = reinterpret_cast<float*>(d_all + 3 * b_keys);
+    float* d_hi = reinterpret_cast<float*>(d_all + 3 * b_keys + b_box);
+    uint32_t* d_sorted = reinterpret_cast<uint32_t*>(d_all + 3 * b_keys + 2 * b_box);
+    int rc = JPT_OK;
+    if ((e = hipMemcpy(d_lo, lo3, b_box, hipMemcpyHostToDevice)) != hipSuccess || (e = hipMemcpy(d_hi, hi3, b_box, hipMemcpyHostToDevice)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        launch_tlas_order(nullptr, d_lo, d_hi, 3, n, d_keys, d_keys + n, d_sorted);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "tlas_order_kernel");
+    }
+    if (rc == JPT_OK && keys_out && (e = hipMemcpy(keys_out, d_keys, b_keys, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK && (e = hipMemcpy(sorted_instances_out, d_sorted, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_tlas_template(uint32_t n, int32_t* child_out, uint32_t capacity, uint32_t* n_records, uint32_t* n_levels, uint32_t* stack_need)
+{
+    if (n < 2 || n > kTlasRebuildMaxInstances) {
+        g_debug_error = "jpt_debug_tlas_template: 2 .. 32767 instances";
+        return JPT_E_INVALID;
+    }
+    TlasTemplate t;
+    make_tlas_template(n, t);
+    if (n_records) *n_records = t.n_records;
+    if (n_levels) *n_levels = t.n_levels;
+    if (stack_need) {
+        std::vector<uint32_t> identity(n);
+        for (uint32_t i = 0; i < n; i++) identity[i] = i;
+        std::vector<WideNode4> records;
+        tlas_template_records(t, identity.data(), records);
+        *stack_need = stack_need4_under(records, 0);
+    }
+    if (child_out) {
+        if (capacity < t.n_records) {
+            g_debug_error = "jpt_debug_tlas_template: record buffer too small";
+            return JPT_E_INVALID;
+        }
+        std::memcpy(child_out, t.child.data(), t.child.size() * sizeof(int32_t));
+    }
+    return JPT_OK;
 }
 
 }  // extern "C"

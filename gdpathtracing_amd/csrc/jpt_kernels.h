@@ -413,8 +413,24 @@ struct Tlas4RefitArgs {
     const uint32_t* order = nullptr;         // tlas4_refit_schedule
     const uint32_t* level_start = nullptr;
     uint32_t n_levels = 0;
+    // before the boxes, the tail's topology (jpt_scene_rebuild_tlas, jpt_kernels_tlas.hip) -- made anew from the template's child words
+    // (rebuild_child non-null: n_tlas_records x 4; sorted: n_instances words; sort_scratch: 2 n_instances keys, read beyond
+    // kTlasLdsKeys instances only) -- or copied from the tail at copy_from (copy_tail: the copy written holds an older topology)
+    const int32_t* rebuild_child = nullptr;
+    uint32_t* sorted = nullptr;
+    uint64_t* sort_scratch = nullptr;
+    bool copy_tail = false;
+    uint32_t copy_from = 0;
 };
 void launch_tlas4_refit(hipStream_t stream, const Tlas4RefitArgs& args);
+// The steps of a rebuild alone (jpt_kernels_tlas.hip; every pointer a device pointer).  launch_tlas_order: boxes at lo / hi (`stride`
+// floats between instances, n <= kTlasRebuildMaxInstances) -> the key of every instance (keys_out, may be null) and the instance at
+// every position of the sorted order; one block.  launch_tlas_template: the template's child words into the records at `base`.
+// launch_tlas_tail_copy: n_records records from one tail to another, internal references rebased.
+void launch_tlas_order(hipStream_t stream, const float* lo, const float* hi, uint32_t stride, uint32_t n, uint64_t* keys_out, uint64_t* scratch,
+                       uint32_t* sorted_out);
+void launch_tlas_template(hipStream_t stream, const int32_t* tmpl, uint32_t n_records, const uint32_t* sorted, WideNode4* nodes4, uint32_t base);
+void launch_tlas_tail_copy(hipStream_t stream, WideNode4* nodes4, uint32_t from_base, uint32_t to_base, uint32_t n_records);
 
 // Deforming a committed mesh without the host (jpt_scene_update_mesh, jpt_kernels_mesh.hip): the mesh's triangle records from new
 // vertices, its four-child BLAS records refitted bottom-up (order / level_start: refit4_schedule of the mesh, on the device;

@@ -169,6 +169,14 @@ void launch_tlas4_refit(hipStream_t stream, const Tlas4RefitArgs& a)
     if (a.n_instances == 0) return;
     hipLaunchKernelGGL(instance_refit_kernel, dim3((a.n_instances + 255) / 256), dim3(256), 0, stream, a.transforms12, a.n_instances, a.bvh,
                        a.instances, a.wide_instances4, a.reach, a.cut_boxes, a.cut_range);
+    if (a.rebuild_child) {
+        // the keys come from the world boxes the records just got, cut tightening included
+        launch_tlas_order(stream, &a.instances->aabbMin.x, &a.instances->aabbMax.x, (uint32_t)(sizeof(RefInstance) / sizeof(float)), a.n_instances,
+                          nullptr, a.sort_scratch, a.sorted);
+        launch_tlas_template(stream, a.rebuild_child, a.n_tlas_records, a.sorted, a.nodes4, a.n_blas_records);
+    } else if (a.copy_tail) {
+        launch_tlas_tail_copy(stream, a.nodes4, a.copy_from, a.n_blas_records, a.n_tlas_records);
+    }
     if (a.n_levels) {
         hipLaunchKernelGGL(tlas4_refit_kernel, dim3(1), dim3(1024), 0, stream, a.nodes4, a.n_blas_records, a.order, a.level_start, a.n_levels,
                            a.instances);

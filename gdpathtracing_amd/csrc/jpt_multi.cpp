@@ -218,6 +218,17 @@ int jpt_multi_refit_tlas(jpt_multi* m, const float* transforms12, uint32_t n_ins
     return JPT_OK;
 }
 
+int jpt_multi_rebuild_tlas(jpt_multi* m, const float* transforms12, uint32_t n_instances)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        (void)hipSetDevice(m->devices[r]);
+        const int rc = jpt_scene_rebuild_tlas(m->ctx[r], transforms12, n_instances);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_update_mesh(jpt_multi* m, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
 {
     if (!m) return JPT_E_INVALID;

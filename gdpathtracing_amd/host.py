@@ -81,6 +81,35 @@ def debug_skin(device_id, bind_positions, bind_normals, rig: "SurfaceRig", influ
     return out_p, out_n
 
 
+def _debug_check(L, rc, what):
+    if rc != capi.OK:
+        msg = L.jpt_debug_last_error()
+        raise capi.JptError("%s failed (%d): %s" % (what, rc, msg.decode() if msg else ""), rc)
+
+
+def debug_tlas_order(device_id, lo, hi, with_keys=True):
+    """jpt_debug_tlas_order: the sort of jpt_scene_rebuild_tlas alone over caller-made world boxes (float32 [n, 3] each) -- (keys uint64
+    [n] per instance, or None; the instance at every sorted position, uint32 [n]).  device_id -1: the host's copy of the functions."""
+    L = capi.lib()
+    lo = np.ascontiguousarray(lo, dtype=np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, dtype=np.float32).reshape(-1, 3)
+    keys = np.zeros(len(lo), np.uint64) if with_keys else None
+    order = np.zeros(len(lo), np.uint32)
+    _debug_check(L, L.jpt_debug_tlas_order(device_id, _ptr(lo), _ptr(hi), len(lo), _ptr(keys), _ptr(order)), "jpt_debug_tlas_order")
+    return keys, order
+
+
+def debug_tlas_template(n):
+    """jpt_debug_tlas_template: the tree jpt_scene_rebuild_tlas puts over n sorted positions -- dict with `child` (int32 [n_records, 4]:
+    >= 0 a record, ~position a leaf, INT32_MIN empty), `n_levels` and `stack_need`."""
+    L = capi.lib()
+    nr, nl, sn = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _debug_check(L, L.jpt_debug_tlas_template(n, None, 0, C.byref(nr), C.byref(nl), C.byref(sn)), "jpt_debug_tlas_template")
+    child = np.zeros((nr.value, 4), np.int32)
+    _debug_check(L, L.jpt_debug_tlas_template(n, _ptr(child), nr.value, C.byref(nr), C.byref(nl), C.byref(sn)), "jpt_debug_tlas_template")
+    return dict(child=child, n_levels=int(nl.value), stack_need=int(sn.value))
+
+
 @atexit.register
 def _close_live_contexts():
     # contexts the caller forgot to close are destroyed while the HIP runtime is still up (this handler is registered
@@ -632,6 +661,28 @@ class Context:
         no synchronisation); transforms12: [n_instances, 12] float32."""
         t = np.ascontiguousarray(transforms12, dtype=np.float32).reshape(-1, 12)
         self._ck(self._lib.jpt_scene_refit_tlas(self.h, _ptr(t), t.shape[0]), "jpt_scene_refit_tlas")
+
+    def rebuild_tlas(self, transforms12):
+        """refit_tlas with a new topology (jpt_scene_rebuild_tlas): the instances are sorted along a Morton curve on the device and a
+        fixed four-way tree over that order replaces the TLAS records; no host rebuild, no synchronisation."""
+        t = np.ascontiguousarray(transforms12, dtype=np.float32).reshape(-1, 12)
+        self._ck(self._lib.jpt_scene_rebuild_tlas(self.h, _ptr(t), t.shape[0]), "jpt_scene_rebuild_tlas")
+
+    debug_tlas_order = staticmethod(debug_tlas_order)
+    debug_tlas_template = staticmethod(debug_tlas_template)
+
+    def debug_tlas_records(self, n_instances: int):
+        """The TLAS records new renders read (jpt_debug_tlas_records): dict with `root`, `nodes4` (uint8 [n, 128]), `nodesq` (uint8
+        [n, 64]), child references counted from the first record, and the world boxes `lo`, `hi` (float32 [n_instances, 3]) of the scene's n_instances
+        instance records."""
+        L = self._lib
+        n, root = C.c_uint32(), C.c_int32()
+        self._ck(L.jpt_debug_tlas_records(self.h, None, None, 0, C.byref(n), C.byref(root), None, None), "jpt_debug_tlas_records")
+        nodes4, nodesq = np.zeros((n.value, 128), np.uint8), np.zeros((n.value, 64), np.uint8)
+        lo, hi = np.zeros((n_instances, 3), np.float32), np.zeros((n_instances, 3), np.float32)
+        self._ck(L.jpt_debug_tlas_records(self.h, _ptr(nodes4), _ptr(nodesq), n.value, C.byref(n), C.byref(root), _ptr(lo), _ptr(hi)),
+                 "jpt_debug_tlas_records")
+        return dict(root=int(root.value), nodes4=nodes4, nodesq=nodesq, lo=lo, hi=hi)
 
     def update_reference_tlas(self, instances, tlas_nodes):
         a, b = np.ascontiguousarray(instances), np.ascontiguousarray(tlas_nodes)
@@ -1326,10 +1377,11 @@ class GeometryGroup3D:
         ctx.build_scene(self.scene, self.builder)
         self._built = [np.array(i.transform, dtype=np.float32) for i in self.scene.instances]
 
-    def update_transforms(self, refit: bool = False) -> int:
+    def update_transforms(self, refit: bool = False, rebuild: bool = False) -> int:
         """Moving nodes without build() again (the reference has no such call; README.md:39-40 wants one): hands
         the changed instance transforms to the library, which redoes BLASInstance records + TLAS only -- on the host
-        (rebuild, the default) or, with refit=True, on the device over the topology of the last build."""
+        (rebuild, the default) or, with refit=True, on the device over the topology of the last build; rebuild=True (with refit): with a
+        new topology made on the device (jpt_scene_rebuild_tlas), for nodes that swap places."""
         moved = 0
         for i, inst in enumerate(self.scene.instances):
             now = np.asarray(inst.transform, dtype=np.float32)
@@ -1338,7 +1390,9 @@ class GeometryGroup3D:
                 self._built[i] = now.copy()
                 moved += 1
         if moved:
-            if refit:
+            if refit and rebuild:
+                self.ctx.rebuild_tlas(np.stack(self._built))
+            elif refit:
                 self.ctx.refit_tlas(np.stack(self._built))
             else:
                 self.ctx.update_tlas()
@@ -1524,6 +1578,10 @@ class MultiContext:
     def refit_tlas(self, transforms12):
         t = np.ascontiguousarray(transforms12, dtype=np.float32).reshape(-1, 12)
         self._ck(self._lib.jpt_multi_refit_tlas(self.h, _ptr(t), t.shape[0]), "jpt_multi_refit_tlas")
+
+    def rebuild_tlas(self, transforms12):
+        t = np.ascontiguousarray(transforms12, dtype=np.float32).reshape(-1, 12)
+        self._ck(self._lib.jpt_multi_rebuild_tlas(self.h, _ptr(t), t.shape[0]), "jpt_multi_rebuild_tlas")
 
     def update_reference_tlas(self, instances, tlas_nodes):
         a, b = np.ascontiguousarray(instances), np.ascontiguousarray(tlas_nodes)

@@ -303,6 +303,20 @@ int jpt_scene_update_tlas(jpt_ctx *ctx);
  *   re-optimises the topology: call it now and then when instances travel far).  The closest hit does not depend on
  *   the topology, so the image equals a fresh commit of the moved scene except at exact distance ties. */
 int jpt_scene_refit_tlas(jpt_ctx *ctx, const float *transforms12, uint32_t n_instances);
+/*   route (ii), on the device, with a NEW TOPOLOGY: jpt_scene_refit_tlas's arguments, state rules, error codes, fall-back and
+ *   pipelining (the copy of the instance level no render reads, on the refit stream; the host waits for nothing but the one-time
+ *   seeding of the copies and the reuse of a staging slot; renders queued before the call show the old scene, renders queued after
+ *   it the new one) -- but the TLAS records are made anew: the instances are sorted on the device along a Morton curve through the
+ *   centres of the world boxes their records just got (30 bits, the instance's index below them), and a fixed four-way tree over
+ *   the sorted order -- a function of the instance count alone, so its root, refit schedule and stack need are known without asking
+ *   the device -- takes them as its leaves.  Use it where a refit degrades: instances that swap places (debris, crowds, a shuffled
+ *   grid) grow the boxes of the last commit's tree until every record near the root covers the scene.  The tree is a Morton tree,
+ *   not jpt_scene_update_tlas's SAH tree (README: the measured difference); later refits, mesh updates and poses keep its topology,
+ *   and jpt_scene_update_tlas afterwards rebuilds on the host from the kept transforms as ever.  At most 32 767 instances
+ *   (JPT_E_LIMIT beyond; a tree deeper than the kernels' stack: JPT_E_LIMIT before anything is written); with one instance the call
+ *   is the refit.  The first rebuild of an instance count uploads the tree's template (the host waits for it, once).  The image
+ *   equals a fresh commit of the moved scene except at exact distance ties. */
+int jpt_scene_rebuild_tlas(jpt_ctx *ctx, const float *transforms12, uint32_t n_instances);
 /*   route (ii), on the device: new vertex positions (and normals) for mesh `mesh_id` (jpt_scene_add_mesh's id) of the
  *   committed scene; same surfaces, vertex counts and index arrays as at jpt_scene_add_mesh (otherwise: JPT_E_INVALID,
  *   "topology changed: commit the scene again").  Replaces GeometryGroup3D::build() of the whole scene, which is what a
@@ -1429,6 +1443,7 @@ int jpt_multi_share_scene(jpt_multi *m);                   /* jpt_scene_share(ra
 int jpt_multi_set_instance_transform(jpt_multi *m, uint32_t instance, const float *transform12);
 int jpt_multi_update_tlas(jpt_multi *m);
 int jpt_multi_refit_tlas(jpt_multi *m, const float *transforms12, uint32_t n_instances);
+int jpt_multi_rebuild_tlas(jpt_multi *m, const float *transforms12, uint32_t n_instances);
 int jpt_multi_update_reference_tlas(jpt_multi *m, const void *blas_instances, uint32_t n_instances,
                                     const void *tlas_nodes, uint32_t n_tlas_nodes);
 /* jpt_scene_update_mesh on every rank's replica */
@@ -1680,6 +1695,25 @@ int jpt_debug_denoise_history(int device_id, int32_t width, int32_t height, cons
  * Waits for the context's stream. */
 int jpt_debug_mesh_records(jpt_ctx *ctx, uint32_t mesh_id, void *nodes4_out, void *nodesq_out, uint32_t node_capacity,
                            void *tris_out, void *shade_out, uint32_t tri_capacity, int32_t *info_out);
+/* jpt_scene_rebuild_tlas's steps alone (its tests).
+ * jpt_debug_tlas_order: n <= 32 767 world boxes (lo3 / hi3: 3 floats per instance) -> the 45-bit key of every instance (keys_out, may
+ *   be NULL: Morton code << 15 | index) and the instance at every position of the ascending order.  Per axis: c = (lo + hi) * 0.5f;
+ *   bmin / bmax the least and greatest FINITE c; inv = bmax - bmin > 0 ? 1024.0f / (bmax - bmin) : 0; f = floor((c - bmin) * inv);
+ *   cell = f >= 1024 ? 1023 : f >= 0 ? (uint32) f : 0, and 0 for a non-finite c; every step one binary32 operation.  device_id >= 0:
+ *   the kernel the rebuild launches, on that device; device_id < 0: the same functions compiled for the host, sorted by std::sort.
+ * jpt_debug_tlas_template: the tree over n sorted positions (2 <= n <= 32 767), 4 child words per record: >= 0 a record, ~position
+ *   a leaf, or 0x80000000 an empty slot.  Records are numbered breadth first, record 0 the root over [0, n); a record over m <= 4
+ *   positions holds them as its first slots; a record over more cuts its range into four parts of floor(m / 4), one more for the first
+ *   m mod 4, a part of one position being a leaf slot.  n_records, n_levels, stack_need (the pending entries a walk of it can need):
+ *   any may be NULL; child_out may be NULL, capacity in records.
+ * jpt_debug_tlas_records: the TLAS records of the copy of the instance level new renders read, float (128 B) and quantised (64 B),
+ *   internal child references counted from the first of them (root_out: the root's, 0 after a rebuild; negative: the root is an
+ *   instance), and the world boxes of that copy's instance records (3 floats per instance each).  Any output may be NULL; capacity
+ *   in records.  Waits for the context's stream. */
+int jpt_debug_tlas_order(int device_id, const float *lo3, const float *hi3, uint32_t n, uint64_t *keys_out, uint32_t *sorted_instances_out);
+int jpt_debug_tlas_template(uint32_t n, int32_t *child_out, uint32_t capacity, uint32_t *n_records, uint32_t *n_levels, uint32_t *stack_need);
+int jpt_debug_tlas_records(jpt_ctx *ctx, void *nodes4_out, void *nodesq_out, uint32_t capacity, uint32_t *n_records, int32_t *root_out,
+                           float *inst_lo3, float *inst_hi3);
 
 /* jpt_scene_pose_mesh's arithmetic alone, on one caller-made rig of n_vertices vertices (one surface's arrays, as jpt_surface_rig's;
  * bind_normals3 may be NULL: no normals, normals3_out is not written and normal_deltas must be NULL) and one pose.  The arguments are

@@ -629,8 +629,10 @@ class GeometryGroup3D {
     MeshInstance3D& get_child(size_t i) { return children.at(i); }
     size_t get_child_count() const { return children.size(); }
     // refit_on_device: instance records + TLAS boxes recomputed by two kernels over the topology of the last build
-    // (jpt_scene_refit_tlas: no host rebuild, no stall); default: host rebuild (jpt_scene_update_tlas)
-    int update_transforms(bool refit_on_device = false)
+    // (jpt_scene_refit_tlas: no host rebuild, no stall); default: host rebuild (jpt_scene_update_tlas).  rebuild_topology (with
+    // refit_on_device): the TLAS is also made anew on the device from the instances' new places (jpt_scene_rebuild_tlas) -- for nodes
+    // that swap places, where a refit's boxes grow over the scene
+    int update_transforms(bool refit_on_device = false, bool rebuild_topology = false)
     {
         if (!ctx_) throw std::runtime_error("GeometryGroup3D::update_transforms before build");
         int moved = 0;
@@ -653,8 +655,14 @@ class GeometryGroup3D {
                 std::vector<float> all;
                 all.reserve(built_transforms_.size() * 12);
                 for (const auto& t : built_transforms_) all.insert(all.end(), t.begin(), t.end());
-                if (multi_) mcheck(jpt_multi_refit_tlas(multi_, all.data(), (uint32_t)built_transforms_.size()), "jpt_multi_refit_tlas");
-                else check(ctx_, jpt_scene_refit_tlas(ctx_, all.data(), (uint32_t)built_transforms_.size()), "jpt_scene_refit_tlas");
+                const uint32_t n = (uint32_t)built_transforms_.size();
+                if (rebuild_topology) {
+                    if (multi_) mcheck(jpt_multi_rebuild_tlas(multi_, all.data(), n), "jpt_multi_rebuild_tlas");
+                    else check(ctx_, jpt_scene_rebuild_tlas(ctx_, all.data(), n), "jpt_scene_rebuild_tlas");
+                } else {
+                    if (multi_) mcheck(jpt_multi_refit_tlas(multi_, all.data(), n), "jpt_multi_refit_tlas");
+                    else check(ctx_, jpt_scene_refit_tlas(ctx_, all.data(), n), "jpt_scene_refit_tlas");
+                }
             } else {
                 if (multi_) mcheck(jpt_multi_update_tlas(multi_), "jpt_multi_update_tlas");
                 else check(ctx_, jpt_scene_update_tlas(ctx_), "jpt_scene_update_tlas");
