@@ -2,7 +2,6 @@
 #include "jpt_ctx.h"
 
 #include <algorithm>
-#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -10,9 +9,62 @@
 #include <string>
 #include <vector>
 
-#include "jpt_instance_math.h"
-#include "jpt_mesh_math.h"
 #include "jpt_tuning.h"
+
+// The view the kernels take (c->ds) of the scene's device arrays (c->dev): the counts from c->ref / c->wide, the instance level the
+// copy new renders read (cur_set).  Whether the tie shadow is usable and current (ds.x.ok, ds.x.tlas_current) is upload_shadow's.
+void jpt::set_scene_view(jpt_ctx* c)
+{
+    const SceneBufs& b = c->dev;
+    const SceneBufs::InstanceSet& is = b.set[c->upd.cur_set];
+    const RefScene& r = c->ref;
+    const WideScene& w = c->wide;
+    DeviceScene& d = c->ds;
+    const bool reach = !r.reach_tri.empty() && r.reach_tri.size() == r.tri_geom.size() && r.reach_inst.size() == r.instances.size();
+    d.reach_tri = reach ? b.reach_tri.p : nullptr;
+    d.reach_inst = reach ? is.reach.p : nullptr;
+    d.ref_tri_geom = b.tri_geom.p;
+    d.shade_tris = b.shade_tris.p;
+    d.ref_materials = b.materials.p;
+    d.ref_bvh = b.bvh.p;
+    d.ref_instances = is.inst.p;
+    d.ref_tlas = b.tlas.p;
+    d.tex = b.tex.p;
+    d.n_tris = (uint32_t)r.tri_geom.size();
+    d.n_materials = (uint32_t)r.materials.size();
+    d.n_ref_bvh = (uint32_t)r.bvh_nodes.size();
+    d.n_instances = (uint32_t)r.instances.size();
+    d.n_ref_tlas = (uint32_t)r.tlas_nodes.size();
+    d.tex_res = r.tex_res;
+    d.n_layers = r.n_layers;
+    d.blas_nodes = b.wblas.p;
+    d.wide_tris = b.wtris.p;
+    d.tlas_nodes = b.wtlas.p;
+    d.wide_instances = b.winst.p;
+    d.tlas_root = w.tlas_root;
+    d.n_blas_nodes = (uint32_t)w.blas_nodes.size();
+    d.n_tlas_nodes = (uint32_t)w.tlas_nodes.size();
+    d.use4 = walks_nodes4(c);
+    d.stack_need4 = w.stack_need4;
+    d.wide_instances4 = is.winst4.p;
+    // upload_nodes4: the BLAS records, then the TLAS tail of each copy
+    const bool any4 = !w.instances4.empty() || !w.blas_nodes4.empty();
+    const size_t tail_base = c->upd.tail_first(w, c->upd.cur_set);
+    d.nodes4 = any4 ? b.nodes4.p : nullptr;
+    d.nodesq = any4 ? b.nodesq.p : nullptr;
+    d.tlas_root4 = !any4 ? 0 : w.tlas_root4 >= 0 ? w.tlas_root4 + (int32_t)tail_base : w.tlas_root4;
+    TieShadowDev& x = d.x;
+    x.bvh = b.x_bvh.p;
+    x.tri_geom = b.x_tri_geom.p;
+    x.instances = b.x_inst.p;
+    x.tlas = b.x_tlas.p;
+    x.tri_native = b.x_tri_native.p;
+    x.native_ref = b.x_native_ref.p;
+    x.tri_leaf = b.x_tri_leaf.p;
+    x.subtree_end = b.x_subtree_end.p;
+    x.tlas_parent = b.x_tlas_parent.p;
+    x.inst_tlas_leaf = b.x_inst_leaf.p;
+}
 
 namespace {
 
@@ -63,72 +115,12 @@ int alloc_framebuffers(jpt_ctx* c)
     return JPT_OK;
 }
 
-// the kernels walk the four-child records of the native tree (the native builder's trees and native uploads); reference-exact and
-// as-given trees keep the two-child records so the kernels visit them node for node like main.glsl (event counters equal the
-// oracle's)
-bool walks_nodes4(const jpt_ctx* c) { return c->tree == JPT_TREE_NATIVE_REACH || c->tree == JPT_TREE_NATIVE_WATERTIGHT; }
-
 // the builder's mode for the scene's tree (an as-given upload: ReferenceExact; rebuild_instances only sees committed scenes)
 BuildMode build_mode(const jpt_ctx* c)
 {
     if (c->tree == JPT_TREE_NATIVE_REACH) return BuildMode::Sah;
     if (c->tree == JPT_TREE_NATIVE_WATERTIGHT) return BuildMode::SahWatertight;
     return BuildMode::ReferenceExact;
-}
-
-// The view the kernels take (c->ds) of the scene's device arrays (c->dev): the counts from c->ref / c->wide, the instance level the
-// copy new renders read (cur_set).  Whether the tie shadow is usable and current (ds.x.ok, ds.x.tlas_current) is upload_shadow's.
-void set_scene_view(jpt_ctx* c)
-{
-    const SceneBufs& b = c->dev;
-    const SceneBufs::InstanceSet& is = b.set[c->cur_set];
-    const RefScene& r = c->ref;
-    const WideScene& w = c->wide;
-    DeviceScene& d = c->ds;
-    const bool reach = !r.reach_tri.empty() && r.reach_tri.size() == r.tri_geom.size() && r.reach_inst.size() == r.instances.size();
-    d.reach_tri = reach ? b.reach_tri.p : nullptr;
-    d.reach_inst = reach ? is.reach.p : nullptr;
-    d.ref_tri_geom = b.tri_geom.p;
-    d.shade_tris = b.shade_tris.p;
-    d.ref_materials = b.materials.p;
-    d.ref_bvh = b.bvh.p;
-    d.ref_instances = is.inst.p;
-    d.ref_tlas = b.tlas.p;
-    d.tex = b.tex.p;
-    d.n_tris = (uint32_t)r.tri_geom.size();
-    d.n_materials = (uint32_t)r.materials.size();
-    d.n_ref_bvh = (uint32_t)r.bvh_nodes.size();
-    d.n_instances = (uint32_t)r.instances.size();
-    d.n_ref_tlas = (uint32_t)r.tlas_nodes.size();
-    d.tex_res = r.tex_res;
-    d.n_layers = r.n_layers;
-    d.blas_nodes = b.wblas.p;
-    d.wide_tris = b.wtris.p;
-    d.tlas_nodes = b.wtlas.p;
-    d.wide_instances = b.winst.p;
-    d.tlas_root = w.tlas_root;
-    d.n_blas_nodes = (uint32_t)w.blas_nodes.size();
-    d.n_tlas_nodes = (uint32_t)w.tlas_nodes.size();
-    d.use4 = walks_nodes4(c);
-    d.stack_need4 = w.stack_need4;
-    d.wide_instances4 = is.winst4.p;
-    // upload_nodes4: the BLAS records, then the TLAS tail of each copy
-    const bool any4 = !w.instances4.empty() || !w.blas_nodes4.empty();
-    const size_t tail_base = w.blas_nodes4.size() + (size_t)c->cur_set * c->tlas4_cap;
-    d.nodes4 = any4 ? b.nodes4.p : nullptr;
-    d.nodesq = any4 ? b.nodesq.p : nullptr;
-    d.tlas_root4 = !any4 ? 0 : w.tlas_root4 >= 0 ? w.tlas_root4 + (int32_t)tail_base : w.tlas_root4;
-    TieShadowDev& x = d.x;
-    x.bvh = b.x_bvh.p;
-    x.tri_geom = b.x_tri_geom.p;
-    x.instances = b.x_inst.p;
-    x.tlas = b.x_tlas.p;
-    x.tri_native = b.x_tri_native.p;
-    x.native_ref = b.x_native_ref.p;
-    x.tri_leaf = b.x_tri_leaf.p;
-    x.subtree_end = b.x_subtree_end.p;
-    x.tlas_parent = b.x_tlas_parent.p;
-    x.inst_tlas_leaf = b.x_inst_leaf.p;
 }
 
 // Four-child records on the device: [ BLAS records | TLAS records ], internal child references of the TLAS part and
@@ -141,13 +133,6 @@ int upload_nodes4(jpt_ctx* c, bool tlas_only)
     const size_t cap_t = std::max<size_t>(w.instances4.size(), std::max<size_t>(nt, 1));
     const size_t cap = nb + (size_t)kInstanceSets * cap_t;  // one TLAS tail per copy of the instance level (jpt_scene_refit_tlas)
     hipStream_t s = c->stream;
-    c->cur_set = 0;
-    c->set_b_ready = false;  // the instance arrays of the other copies are made (again) by the next refit
-    for (bool& v : c->set_retired_valid) v = false;
-    // every tail gets the host's topology again: the refits run over its schedule until the next jpt_scene_rebuild_tlas
-    c->topo_rebuilt = false;
-    c->topo_gen = 0;
-    for (uint32_t& g : c->set_topo_gen) g = 0;
     if (w.instances4.empty() && nb == 0) return JPT_OK;
     auto quantised = [](const std::vector<WideNode4>& in) {
         std::vector<WideNodeQ> out(in.size());
@@ -176,17 +161,12 @@ int upload_nodes4(jpt_ctx* c, bool tlas_only)
         if (nt) HIP_TRY(c, hipMemcpyAsync(b.nodesq.p + base, qtail.data(), nt * sizeof(WideNodeQ), hipMemcpyHostToDevice, s));
         HIP_TRY(c, hipStreamSynchronize(s));  // `tail`, `qtail` are pageable host memory
     }
-    c->tlas4_cap = cap_t;
-    {
-        // bottom-up schedule of the TLAS records, for refits on the device
-        std::vector<uint32_t>&order = c->tlas4_order_h, &levels = c->tlas4_levels_h;
-        tlas4_refit_schedule(w, order, levels);
-        HIP_TRY(c, c->d_tlas4_order.upload(order, s));
-        HIP_TRY(c, c->d_tlas4_levels.upload(levels, s));
-        HIP_TRY(c, hipStreamSynchronize(s));  // pageable host vectors
-        c->n_tlas4_levels = (uint32_t)levels.size() - 1u;
-        c->cull_boxes_current = true;
-    }
+    c->upd.tlas4_cap = cap_t;
+    // bottom-up schedule of the TLAS records, for refits on the device
+    tlas4_refit_schedule(w, c->upd.tlas4_order_h, c->upd.tlas4_levels_h);
+    HIP_TRY(c, c->upd.d_tlas4_order.upload(c->upd.tlas4_order_h, s));
+    HIP_TRY(c, c->upd.d_tlas4_levels.upload(c->upd.tlas4_levels_h, s));
+    HIP_TRY(c, hipStreamSynchronize(s));  // pageable host vectors
     return JPT_OK;
 }
 
@@ -238,15 +218,16 @@ int upload_shadow(jpt_ctx* c, bool instances_only)
     return JPT_OK;
 }
 
-// The rigs of jpt_scene_set_mesh_rig leave with the scene they were set for (a queued pose may still read them: the refit stream first)
-void drop_mesh_rigs(jpt_ctx* c)
+// What both uploads end with on the device, of the `whole` scene or of its instance level: the one place that says a host upload
+// happened (SceneUpdates::host_uploaded; a host-only context never leaves that state), then the four-child records, the shadow and the view
+int finish_upload(jpt_ctx* c, bool whole)
 {
-    if (c->mesh_rigs.empty()) return;
-    if (c->device >= 0 && c->refit_stream) {
-        (void)hipSetDevice(c->device);
-        (void)hipStreamSynchronize(c->refit_stream);
-    }
-    c->mesh_rigs.clear();
+    c->upd.host_uploaded(whole, c->wide);
+    int rc = upload_nodes4(c, !whole);
+    if (rc != JPT_OK) return rc;
+    rc = upload_shadow(c, !whole);
+    set_scene_view(c);
+    return rc;
 }
 
 // host RefScene (+ flatten) -> device
@@ -274,9 +255,6 @@ int upload_scene(jpt_ctx* c)
     }
     c->host_scene_ready = true;
     c->tlas_dirty = false;
-    c->refit_active = false;
-    c->mesh_deformed = false;
-    c->mesh_refit_ready = false;
     note_ties(c);
     if (c->device < 0) return JPT_OK;  // host-only context: arrays stay on the host, nothing can be rendered
     HIP_TRY(c, hipSetDevice(c->device));
@@ -312,17 +290,40 @@ int upload_scene(jpt_ctx* c)
     HIP_TRY(c, b.cut_boxes.upload(c->ref.inst_cut_boxes, s));
     HIP_TRY(c, b.cut_range.upload(c->ref.inst_cut_range, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    {
-        const int rc4 = upload_nodes4(c, false);
-        if (rc4 != JPT_OK) return rc4;
+    const int rc = finish_upload(c, true);
+    if (rc == JPT_OK) c->scene_ready = true;
+    return rc;
+}
+
+// instances / TLAS of c->ref changed (BLASes did not): re-flatten that part and upload it
+int upload_tlas_update(jpt_ctx* c)
+{
+    lights_stale(c, true);
+    std::string err;
+    const bool use4 = walks_nodes4(c);
+    if (!reflatten_tlas(c->ref, c->wide, use4, err)) return fail(c, JPT_E_INVALID, "tlas update: " + err);
+    const uint32_t need = use4 ? c->wide.stack_need4 : c->wide.stack_need2;
+    if (need > trace_stack_capacity()) {
+        c->scene_ready = c->host_scene_ready = false;
+        return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the TLAS update: a traversal could need " +
+                                        std::to_string(need) + " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
     }
-    {
-        const int rcx = upload_shadow(c, false);
-        set_scene_view(c);
-        if (rcx != JPT_OK) return rcx;
-    }
-    c->scene_ready = true;
-    return JPT_OK;
+    if (c->device < 0) return JPT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    SceneBufs& b = c->dev;
+    // renders already queued on the stream still read the old records: let them finish before the buffers move
+    HIP_TRY(c, hipStreamSynchronize(s));
+    HIP_TRY(c, b.set[0].inst.upload(c->ref.instances, s));
+    HIP_TRY(c, b.tlas.upload(c->ref.tlas_nodes, s));
+    HIP_TRY(c, b.wtlas.upload(c->wide.tlas_nodes, s));
+    HIP_TRY(c, b.winst.upload(c->wide.instances, s));
+    HIP_TRY(c, b.set[0].winst4.upload(c->wide.instances4, s));
+    HIP_TRY(c, b.set[0].reach.upload(c->ref.reach_inst, s));
+    HIP_TRY(c, b.cut_boxes.upload(c->ref.inst_cut_boxes, s));
+    HIP_TRY(c, b.cut_range.upload(c->ref.inst_cut_range, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    return finish_upload(c, false);
 }
 
 int validate_ref_scene(jpt_ctx* c, const RefScene& r)
@@ -352,7 +353,7 @@ void compute_sky_cull(const jpt_ctx* c, SkyCull& out)
 {
     out.n = -1;
     if (!tuning().sky_cull || c->width <= 0 || c->height <= 0) return;
-    if (!c->cull_boxes_current) return;  // the root's boxes were last refitted on the device only: the host copy is stale
+    if (!c->upd.cull_boxes_current) return;  // the root's boxes were last refitted on the device only: the host copy is stale
     // the boxes: children of the TLAS root record in the layout the kernels walk
     double lo[4][3], hi[4][3];
     int n = 0;
@@ -750,9 +751,9 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
     if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
     if (!c->camera_set) return fail(c, JPT_E_STATE, "jpt_set_camera not called");
     if (n_frames < 0) return fail(c, JPT_E_INVALID, "n_frames < 0");
-    if (c->mesh_deformed && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
+    if (c->upd.mesh_deformed && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
         return fail(c, JPT_E_STATE, "jpt_scene_update_mesh refits the default kernel's records only: call jpt_scene_commit before rendering with another kernel");
-    if (c->refit_active && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
+    if (c->upd.refit_active && (c->kernel_variant != JPT_KERNEL_WAVEFRONT || c->debug_steps))
         return fail(c, JPT_E_STATE, "jpt_scene_refit_tlas refits the default kernel's records only: call jpt_scene_update_tlas before rendering with another kernel");
     return JPT_OK;
 }
@@ -875,10 +876,10 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
     // (first use of the slot, or renders that went through `s` itself since), wait for whatever `s` holds now
     if (!ps.acc_done_valid) HIP_TRY(c, hipEventRecord(ps.ev_acc_done, s));
     HIP_TRY(c, hipStreamWaitEvent(ps.stream, ps.ev_acc_done, 0));
-    if (ps.refit_seen != c->refit_wait_seq) {
+    if (ps.refit_seen != c->upd.refit_wait_seq) {
         // the instance level this render reads was refitted on the refit stream (jpt_scene_refit_tlas)
-        HIP_TRY(c, hipStreamWaitEvent(ps.stream, c->ev_refit_done, 0));
-        ps.refit_seen = c->refit_wait_seq;
+        HIP_TRY(c, hipStreamWaitEvent(ps.stream, c->upd.ev_refit_done, 0));
+        ps.refit_seen = c->upd.refit_wait_seq;
     }
     // The accumulation runs on the slot's stream too, after whatever `s` holds now (the previous render's accumulation, an
     // upload, a read-back), and `s` then waits for it: the results are those of serial execution, and `s` itself carries no
@@ -1135,10 +1136,7 @@ void jpt_destroy(jpt_ctx* c)
     for (hipEvent_t e : c->primary.refl_ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->enc_ev) if (e) (void)hipEventDestroy(e);
     if (c->ev_enc_readback) (void)hipEventDestroy(c->ev_enc_readback);
-    if (c->refit_stream) { (void)hipStreamSynchronize(c->refit_stream); (void)hipStreamDestroy(c->refit_stream); }
-    for (hipEvent_t e : c->ev_set_retired) if (e) (void)hipEventDestroy(e);
-    if (c->ev_refit_done) (void)hipEventDestroy(c->ev_refit_done);
-    if (c->ev_mesh_drain) (void)hipEventDestroy(c->ev_mesh_drain);
+    c->upd.destroy_stream();
     release_streams(c);
     for (hipEvent_t e : c->group_streams.join) if (e) (void)hipEventDestroy(e);
     if (c->group_streams.fork) (void)hipEventDestroy(c->group_streams.fork);
@@ -1411,9 +1409,9 @@ int jpt_scene_share(jpt_ctx* dst, jpt_ctx* src)
     if (!dst || !src) return JPT_E_INVALID;
     if (dst == src) return JPT_OK;
     if (!src->host_scene_ready || src->building) return fail(dst, JPT_E_STATE, "the source context holds no committed scene");
-    if (src->mesh_deformed)
+    if (src->upd.mesh_deformed)
         return fail(dst, JPT_E_STATE, "the source context's meshes were deformed on the device (jpt_scene_update_mesh): its host copy of the scene is stale until the next jpt_scene_commit");
-    if (src->from_commit && (src->tlas_dirty || src->refit_active)) {  // bring the source's host arrays up to date with its last transforms
+    if (src->from_commit && (src->tlas_dirty || src->upd.refit_active)) {  // bring the source's host arrays up to date with its last transforms
         const int rc = jpt_scene_update_tlas(src);
         if (rc != JPT_OK) return fail(dst, rc, std::string("source context: ") + src->error);
     }
@@ -1432,179 +1430,9 @@ int jpt_scene_share(jpt_ctx* dst, jpt_ctx* src)
     return rc;
 }
 
-namespace {
-
-// instances / TLAS of c->ref changed (BLASes did not): re-flatten that part and upload it
-int upload_tlas_update(jpt_ctx* c)
-{
-    lights_stale(c, true);
-    std::string err;
-    const bool use4 = walks_nodes4(c);
-    if (!reflatten_tlas(c->ref, c->wide, use4, err)) return fail(c, JPT_E_INVALID, "tlas update: " + err);
-    const uint32_t need = use4 ? c->wide.stack_need4 : c->wide.stack_need2;
-    if (need > trace_stack_capacity()) {
-        c->scene_ready = c->host_scene_ready = false;
-        return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the TLAS update: a traversal could need " +
-                                        std::to_string(need) + " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
-    }
-    if (c->device < 0) return JPT_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    hipStream_t s = c->stream;
-    SceneBufs& b = c->dev;
-    // renders already queued on the stream still read the old records: let them finish before the buffers move
-    HIP_TRY(c, hipStreamSynchronize(s));
-    HIP_TRY(c, b.set[0].inst.upload(c->ref.instances, s));
-    HIP_TRY(c, b.tlas.upload(c->ref.tlas_nodes, s));
-    HIP_TRY(c, b.wtlas.upload(c->wide.tlas_nodes, s));
-    HIP_TRY(c, b.winst.upload(c->wide.instances, s));
-    HIP_TRY(c, b.set[0].winst4.upload(c->wide.instances4, s));
-    HIP_TRY(c, b.set[0].reach.upload(c->ref.reach_inst, s));
-    HIP_TRY(c, b.cut_boxes.upload(c->ref.inst_cut_boxes, s));
-    HIP_TRY(c, b.cut_range.upload(c->ref.inst_cut_range, s));
-    HIP_TRY(c, hipStreamSynchronize(s));
-    {
-        const int rc4 = upload_nodes4(c, true);
-        if (rc4 != JPT_OK) return rc4;
-    }
-    c->refit_active = false;
-    const int rc = upload_shadow(c, true);
-    set_scene_view(c);
-    return rc;
-}
-
-// The refit stream and the events that order device refits against renders (jpt_scene_refit_tlas, jpt_scene_update_mesh)
-int ensure_refit_stream(jpt_ctx* c)
-{
-    if (!c->refit_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->refit_stream, hipStreamNonBlocking));
-    for (int k = 0; k < kInstanceSets; k++)
-        if (!c->ev_set_retired[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_set_retired[k], hipEventDisableTiming));
-    if (!c->ev_refit_done) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_refit_done, hipEventDisableTiming));
-    return JPT_OK;
-}
-
-// The template of jpt_scene_rebuild_tlas for `n` instances (jpt_tlas_rebuild.h) with its refit schedule and stack need, on the host
-// and on the device, and the sort's buffers: made at the first rebuild of this instance count (the host waits for the copies, once)
-// and kept.  A count that changes comes with a new scene, whose upload the refit stream has long finished for; it is drained all the same.
-int ensure_tlas_template(jpt_ctx* c, uint32_t n)
-{
-    if (c->tlas_tmpl.n != n) {
-        make_tlas_template(n, c->tlas_tmpl);
-        std::vector<uint32_t> identity(n);
-        for (uint32_t i = 0; i < n; i++) identity[i] = i;
-        std::vector<WideNode4> records;
-        tlas_template_records(c->tlas_tmpl, identity.data(), records);
-        c->tmpl_order_h.clear();
-        c->tmpl_levels_h.assign(1, 0u);
-        refit4_schedule(records, 0, c->tmpl_order_h, c->tmpl_levels_h);
-        c->tmpl_stack_need = stack_need4_under(records, 0);
-        HIP_TRY(c, hipStreamSynchronize(c->refit_stream));
-        c->d_tmpl_child.release();   // (made again below)
-    }
-    if (c->d_tmpl_child.p) return JPT_OK;
-    hipStream_t rs = c->refit_stream;
-    HIP_TRY(c, c->d_tmpl_child.upload(c->tlas_tmpl.child, rs));
-    HIP_TRY(c, c->d_tmpl_order.upload(c->tmpl_order_h, rs));
-    HIP_TRY(c, c->d_tmpl_levels.upload(c->tmpl_levels_h, rs));
-    HIP_TRY(c, c->d_tlas_sorted.resize(n));
-    HIP_TRY(c, c->d_tlas_sort_keys.resize(n > kTlasLdsKeys ? 2 * (size_t)n : 0));
-    HIP_TRY(c, hipStreamSynchronize(rs));   // pageable host vectors
-    return JPT_OK;
-}
-
-// Instance records and TLAS boxes from the transforms at `dev_view` (n_instances x 12 floats the device can read), written into the
-// copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
-// from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
-// `rebuild_sorted` (jpt_scene_rebuild_tlas; ensure_tlas_template has run): the copy also gets a new topology, the template's over the
-// instances sorted on the device, and the host's mirror of the records (c->wide, the schedule) becomes the template over
-// rebuild_sorted, boxes not yet refitted.  Every later refit then runs over the template's schedule, and one into a copy whose tail
-// still holds an older topology first copies the current copy's tail.
-int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances, const uint32_t* rebuild_sorted = nullptr)
-{
-    lights_stale(c, false);
-    hipStream_t s = c->stream;
-    SceneBufs& b = c->dev;
-    if (!c->set_b_ready) {
-        // first refit since the last host upload: the other copies of the instance arrays start as copies of copy 0
-        // (the TLAS tails were all uploaded).  Once per upload, so the drain does not matter.
-        HIP_TRY(c, hipStreamSynchronize(s));
-        const SceneBufs::InstanceSet& first = b.set[0];
-        for (int k = 1; k < kInstanceSets; k++) {
-            SceneBufs::InstanceSet& to = b.set[k];
-            HIP_TRY(c, to.inst.resize(first.inst.n));
-            HIP_TRY(c, to.winst4.resize(first.winst4.n));
-            HIP_TRY(c, hipMemcpyAsync(to.inst.p, first.inst.p, first.inst.n * sizeof(RefInstance), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(c, hipMemcpyAsync(to.winst4.p, first.winst4.p, first.winst4.n * sizeof(WideInstance), hipMemcpyDeviceToDevice, s));
-            HIP_TRY(c, to.reach.resize(first.reach.n));
-            if (first.reach.n)
-                HIP_TRY(c, hipMemcpyAsync(to.reach.p, first.reach.p, first.reach.n * sizeof(ReachInst), hipMemcpyDeviceToDevice, s));
-        }
-        HIP_TRY(c, hipStreamSynchronize(s));
-        c->set_b_ready = true;
-        for (bool& v : c->set_retired_valid) v = false;
-    }
-    // The refit writes the copy that new renders do not read yet (`next`); its last readers are the renders queued
-    // before the refit that retired it, i.e. before ev_set_retired[next] was recorded on the context's stream (which
-    // waits for every render).  The renders queued since read the current copy and keep running meanwhile.
-    const int next = (c->cur_set + 1) % kInstanceSets;
-    HIP_TRY(c, hipEventRecord(c->ev_set_retired[c->cur_set], s));
-    c->set_retired_valid[c->cur_set] = true;
-    hipStream_t rs = c->refit_stream;
-    if (c->set_retired_valid[next]) HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_set_retired[next], 0));
-    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty();
-    Tlas4RefitArgs a;
-    a.transforms12 = dev_view;
-    a.n_instances = n_instances;
-    a.bvh = b.bvh.p;
-    a.instances = b.set[next].inst.p;
-    a.wide_instances4 = b.set[next].winst4.p;
-    a.reach = c->ds.reach_tri ? b.set[next].reach.p : nullptr;
-    a.cut_boxes = cuts ? b.cut_boxes.p : nullptr;
-    a.cut_range = cuts ? b.cut_range.p : nullptr;
-    a.nodes4 = b.nodes4.p;
-    a.nodesq = b.nodesq.p;
-    a.n_blas_records = (uint32_t)(c->wide.blas_nodes4.size() + (size_t)next * c->tlas4_cap);
-    if (rebuild_sorted) {
-        WideScene& w = c->wide;
-        const uint32_t blas_need = w.stack_need4 - 1u - stack_need4_under(w.tlas_nodes4, w.tlas_root4);
-        tlas_template_records(c->tlas_tmpl, rebuild_sorted, w.tlas_nodes4);
-        w.tlas_root4 = 0;
-        w.stack_need4 = c->tmpl_stack_need + 1u + blas_need;
-        c->tlas4_order_h = c->tmpl_order_h;
-        c->tlas4_levels_h = c->tmpl_levels_h;
-        c->n_tlas4_levels = (uint32_t)c->tmpl_levels_h.size() - 1u;
-        c->topo_rebuilt = true;
-        c->set_topo_gen[next] = ++c->topo_gen;
-        a.rebuild_child = c->d_tmpl_child.p;
-        a.sorted = c->d_tlas_sorted.p;
-        a.sort_scratch = c->d_tlas_sort_keys.p;
-    } else if (c->set_topo_gen[next] != c->topo_gen) {
-        a.copy_tail = true;
-        a.copy_from = (uint32_t)(c->wide.blas_nodes4.size() + (size_t)c->cur_set * c->tlas4_cap);
-        c->set_topo_gen[next] = c->topo_gen;
-    }
-    a.n_tlas_records = (uint32_t)c->wide.tlas_nodes4.size();
-    a.order = c->topo_rebuilt ? c->d_tmpl_order.p : c->d_tlas4_order.p;
-    a.level_start = c->topo_rebuilt ? c->d_tmpl_levels.p : c->d_tlas4_levels.p;
-    a.n_levels = c->n_tlas4_levels;
-    launch_tlas4_refit(rs, a);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipEventRecord(c->ev_refit_done, rs));
-    // the context's stream (blocking renders, read-backs, uploads, foreign work) is ordered after the refit; queued
-    // renders wait for it on their own streams (do_render_batch), not through the context's stream
-    HIP_TRY(c, hipStreamWaitEvent(s, c->ev_refit_done, 0));
-    c->refit_wait_seq++;
-    c->cur_set = next;
-    set_scene_view(c);
-    return JPT_OK;
-}
-
-}  // namespace
-
 int jpt_scene_set_instance_transform(jpt_ctx* c, uint32_t instance, const float* transform12)
 {
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_set_instance_transform needs a scene made by jpt_scene_commit");
+    if (const int rc = needs_scene(c, kFromCommit, "jpt_scene_set_instance_transform", " needs a scene made by jpt_scene_commit"); rc != JPT_OK) return rc;
     if (!transform12) return fail(c, JPT_E_INVALID, "null transform");
     if (!c->builder.set_instance_transform(instance, transform12)) return fail(c, JPT_E_INVALID, "no such instance");
     c->tlas_dirty = true;
@@ -1613,10 +1441,8 @@ int jpt_scene_set_instance_transform(jpt_ctx* c, uint32_t instance, const float*
 
 int jpt_scene_update_tlas(jpt_ctx* c)
 {
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_scene_update_tlas needs a scene made by jpt_scene_commit");
-    if (c->mesh_deformed)
+    if (const int rc = needs_scene(c, kFromCommit, "jpt_scene_update_tlas", " needs a scene made by jpt_scene_commit"); rc != JPT_OK) return rc;
+    if (c->upd.mesh_deformed)
         return fail(c, JPT_E_STATE, "a mesh was deformed on the device (jpt_scene_update_mesh): the host's copy of the scene is stale until the next jpt_scene_commit");
     if (!c->tlas_dirty) return JPT_OK;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1629,506 +1455,6 @@ int jpt_scene_update_tlas(jpt_ctx* c)
     if (rc == JPT_OK) c->tlas_dirty = false;
     c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return rc;
-}
-
-namespace {
-
-// jpt_scene_refit_tlas and jpt_scene_rebuild_tlas (`rebuild`; `call`: the name for the state message): the same checks, staging and
-// side effects; the rebuild also gives the copy it writes a new topology
-int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, bool rebuild, const char* call)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !walks_nodes4(c) || !c->from_commit)
-        return fail(c, JPT_E_STATE, std::string(call) + " needs a scene made by jpt_scene_commit with the native builder");
-    if (!transforms12 && n_instances) return fail(c, JPT_E_INVALID, "null transforms");
-    if (n_instances != c->ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the refit runs on the device (jpt_scene_update_tlas is the host route)");
-    // the host keeps the transforms (a later jpt_scene_update_tlas rebuilds from them); its arrays are stale from here on
-    for (uint32_t i = 0; i < n_instances; i++) (void)c->builder.set_instance_transform(i, transforms12 + (size_t)i * 12);
-    c->tlas_dirty = true;
-    if (!c->ds.use4 || !c->scene_ready) return jpt_scene_update_tlas(c);  // no four-child records to refit
-    if (n_instances == 0) return JPT_OK;
-    if (n_instances <= 1) rebuild = false;   // one instance is its own order
-    if (rebuild && n_instances > kTlasRebuildMaxInstances)
-        return fail(c, JPT_E_LIMIT, "jpt_scene_rebuild_tlas sorts at most " + std::to_string(kTlasRebuildMaxInstances) + " instances");
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_refit_stream(c);
-    if (rc != JPT_OK) return rc;
-    // The host's side of a rebuild, before anything is written.  For a modest number of instances the host repeats the sort on its
-    // own root-rule boxes (the mirror below): its order may differ from the device's, whose boxes are tightened by the cuts, but
-    // every instance is under the mirror's root, which is all the sky cull asks.  Beyond that the mirror's leaves are in index order
-    // and the cull is off.
-    const bool mirror = n_instances <= 4096u && !c->mesh_deformed;
-    std::vector<RefInstance> boxes;
-    if (mirror) {
-        boxes.resize(n_instances);
-        for (uint32_t i = 0; i < n_instances; i++) {
-            const RefBvhNode& root = c->ref.bvh_nodes[c->ref.instances[i].blas_index];
-            instance_record(transforms12 + (size_t)i * 12, root.aabbMin, root.aabbMax, true, boxes[i]);
-        }
-    }
-    std::vector<uint32_t> sorted;
-    if (rebuild) {
-        rc = ensure_tlas_template(c, n_instances);
-        if (rc != JPT_OK) return rc;
-        const WideScene& w = c->wide;
-        const uint32_t need = w.stack_need4 - stack_need4_under(w.tlas_nodes4, w.tlas_root4) + c->tmpl_stack_need;
-        if (need > trace_stack_capacity())
-            return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the TLAS rebuild: a traversal could need " + std::to_string(need) +
-                                            " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
-        sorted.resize(n_instances);
-        if (mirror) tlas_order_host(&boxes[0].aabbMin.x, &boxes[0].aabbMax.x, sizeof(RefInstance) / sizeof(float), n_instances, nullptr, sorted.data());
-        else
-            for (uint32_t i = 0; i < n_instances; i++) sorted[i] = i;
-    }
-    const size_t bytes = (size_t)n_instances * 12 * sizeof(float);
-    int st = 0;
-    HIP_TRY(c, c->refit_stage.next(bytes, st));
-    std::memcpy(c->refit_stage.buf[st].p, transforms12, bytes);
-    // the kernel reads the transforms straight from the pinned buffer (48 B per instance over the host link)
-    float* dev_view = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&dev_view, c->refit_stage.buf[st].p, 0));
-    rc = queue_instance_refit(c, dev_view, n_instances, rebuild ? sorted.data() : nullptr);
-    if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->refit_stage.copied[st], c->refit_stream));
-    // The sky cull (compute_sky_cull) projects the boxes the TLAS root offers, on the host.  For a modest number of
-    // instances the host repeats the TLAS refit on its own copy of the four-child TLAS records (refit_slots, same schedule:
-    // ~0.1 us per instance), over instance boxes by the root rule alone: without the cut tightening the device applies, so its
-    // boxes contain the device's (safe for the cull) but are looser.  Beyond that the cull is off until the next
-    // jpt_scene_update_tlas.  After jpt_scene_update_mesh the host's root boxes are the committed vertices': off until the next
-    // jpt_scene_commit.
-    if (mirror && !c->tlas4_levels_h.empty()) {
-        WideScene& w = c->wide;
-        for (size_t l = 0; l + 1 < c->tlas4_levels_h.size(); l++)
-            for (uint32_t k = c->tlas4_levels_h[l]; k < c->tlas4_levels_h[l + 1]; k++)
-                refit_slots(w.tlas_nodes4[c->tlas4_order_h[k]], w.tlas_nodes4.data(), [&](int32_t ref, float* lo, float* hi) {
-                    const RefInstance& in = boxes[(uint32_t)~ref];
-                    lo[0] = in.aabbMin.x; lo[1] = in.aabbMin.y; lo[2] = in.aabbMin.z;
-                    hi[0] = in.aabbMax.x; hi[1] = in.aabbMax.y; hi[2] = in.aabbMax.z;
-                });
-        c->cull_boxes_current = true;
-    } else {
-        c->cull_boxes_current = false;
-    }
-    c->refit_active = true;
-    c->ds.x.tlas_current = false;   // the copy of the reference's instance level is the last HOST update's: until the next one exact ties are decided inside one instance only (jpt_tie_walk.h)
-    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return JPT_OK;
-}
-
-}  // namespace
-
-int jpt_scene_refit_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
-{
-    return move_instances(c, transforms12, n_instances, false, "jpt_scene_refit_tlas");
-}
-
-int jpt_scene_rebuild_tlas(jpt_ctx* c, const float* transforms12, uint32_t n_instances)
-{
-    return move_instances(c, transforms12, n_instances, true, "jpt_scene_rebuild_tlas");
-}
-
-namespace {
-
-// Per mesh: where its records and triangles are on the device and the bottom-up schedule of its records (refit4_schedule), with
-// the triangles' vertex indices; made and uploaded at the first jpt_scene_update_mesh after an upload (once per upload: the
-// host waits for the copies).
-int ensure_mesh_refit(jpt_ctx* c)
-{
-    if (c->mesh_refit_ready) return JPT_OK;
-    const RefScene& r = c->ref;
-    const WideScene& w = c->wide;
-    const size_t n_meshes = r.mesh_roots.size();
-    if (r.mesh_tri_range.size() != 2 * n_meshes || r.tri_vidx.size() != 3 * r.tri_geom.size() || w.instances4.size() != r.instances.size())
-        return fail(c, JPT_E_STATE, "the scene holds no vertex map for device updates: commit it again with JPT_BUILD_SAH_WATERTIGHT");
-    c->mesh_refit.assign(n_meshes, jpt_ctx::MeshRefit{});
-    c->mesh_order_h.clear();
-    c->mesh_levels_h.clear();
-    for (size_t m = 0; m < n_meshes; m++) {
-        jpt_ctx::MeshRefit& mr = c->mesh_refit[m];
-        mr.bvh_root = r.mesh_roots[m];
-        mr.tri_first = r.mesh_tri_range[2 * m];
-        mr.n_tris = r.mesh_tri_range[2 * m + 1];
-        if (mr.n_tris == 0) continue;   // (an empty mesh stands for another mesh's tree: nothing of its own on the device)
-        size_t inst = r.instances.size();
-        for (size_t i = 0; i < r.instances.size(); i++)
-            if (r.instances[i].blas_index == mr.bvh_root) {
-                inst = i;
-                break;
-            }
-        if (inst == r.instances.size()) continue;   // no instance names it: flatten made no tree for it
-        mr.has_tree = true;
-        mr.root4 = w.instances4[inst].root;
-        mr.level_first = (uint32_t)c->mesh_levels_h.size();
-        const size_t order_first = c->mesh_order_h.size();
-        c->mesh_levels_h.push_back((uint32_t)order_first);
-        refit4_schedule(w.blas_nodes4, mr.root4, c->mesh_order_h, c->mesh_levels_h);
-        mr.n_levels = (uint32_t)(c->mesh_levels_h.size() - mr.level_first - 1);
-        if (mr.root4 >= 0) {
-            uint32_t lo = (uint32_t)mr.root4, hi = (uint32_t)mr.root4;
-            for (size_t k = order_first; k < c->mesh_order_h.size(); k++) {
-                lo = std::min(lo, c->mesh_order_h[k]);
-                hi = std::max(hi, c->mesh_order_h[k]);
-            }
-            mr.rec_first = lo;
-            mr.n_recs = hi - lo + 1;
-        }
-    }
-    {
-        const int rc = ensure_refit_stream(c);
-        if (rc != JPT_OK) return rc;
-    }
-    hipStream_t rs = c->refit_stream;
-    HIP_TRY(c, c->d_tri_vidx.upload(r.tri_vidx, rs));
-    HIP_TRY(c, c->d_mesh_order.upload(c->mesh_order_h, rs));
-    HIP_TRY(c, c->d_mesh_levels.upload(c->mesh_levels_h, rs));
-    HIP_TRY(c, hipStreamSynchronize(rs));   // pageable host vectors
-    c->mesh_refit_ready = true;
-    return JPT_OK;
-}
-
-// The state and argument checks of a call that gives new arrays for a committed mesh (`call`: jpt_scene_update_mesh,
-// jpt_scene_set_mesh_rig): a JPT_BUILD_SAH_WATERTIGHT commit, the mesh's own topology, normals for every surface or for none
-// (with_normals: whether they came).  sv: the surfaces as the builder views them.
-int check_mesh_arrays(jpt_ctx* c, const char* call, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces, std::vector<SurfaceView>& sv,
-                      int& with_normals)
-{
-    if (!c->host_scene_ready || c->building || !c->from_commit)
-        return fail(c, JPT_E_STATE, std::string(call) + " needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
-    if (!walks_nodes4(c))
-        return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_REFERENCE_EXACT: its trees are the reference's own, which a refit "
-                                    "would not keep (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
-    if (c->tree != JPT_TREE_NATIVE_WATERTIGHT)
-        return fail(c, JPT_E_STATE, "the scene was committed with JPT_BUILD_SAH: its reach records and tie shadow are the reference builder's "
-                                    "tree of the committed vertices (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
-    if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
-    if (n_surfaces < 0 || (n_surfaces && !surfaces)) return fail(c, JPT_E_INVALID, "bad surface array");
-    sv.assign((size_t)n_surfaces, SurfaceView{});
-    int with_vertices = 0;
-    with_normals = 0;
-    for (int32_t i = 0; i < n_surfaces; i++) {
-        const jpt_surface& x = surfaces[i];
-        if (x.n_vertices > 0) {
-            if (!x.vertices) return fail(c, JPT_E_INVALID, "surface needs a vertex array");
-            with_vertices++;
-            with_normals += x.normals ? 1 : 0;
-        }
-        sv[(size_t)i] = SurfaceView{x.vertices, x.normals, nullptr, x.indices, x.n_vertices, x.n_indices};
-    }
-    if (!c->builder.same_topology(mesh_id, sv.data(), n_surfaces)) return fail(c, JPT_E_INVALID, "topology changed: commit the scene again");
-    if (with_normals != 0 && with_normals != with_vertices) return fail(c, JPT_E_INVALID, "give normals for every surface of the mesh or for none");
-    return JPT_OK;
-}
-
-// What jpt_scene_update_mesh and jpt_scene_pose_mesh do once the mesh's new vertices (and normals, or null: they stay) are on their way
-// into d_mesh_in behind its bounds head, on the refit stream and behind the pipeline drain: the mesh's records refitted from them,
-// then the instance level over the new root boxes with the current transforms (`dev_transforms`: the stage's copy, as the device sees
-// it), as jpt_scene_refit_tlas does; the stage `st` of mesh_stage is free again once all of it has run.
-int queue_mesh_refit(jpt_ctx* c, const jpt_ctx::MeshRefit& mr, const float* verts, const float* normals, const float* dev_transforms, int st,
-                     std::chrono::steady_clock::time_point t0)
-{
-    hipStream_t rs = c->refit_stream;
-    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
-    MeshRefitArgs a;
-    a.bounds = reinterpret_cast<int32_t*>(c->d_mesh_in.p);
-    a.verts = verts;
-    a.normals = normals;
-    a.vidx = c->d_tri_vidx.p;
-    a.tri_first = mr.tri_first;
-    a.n_tris = mr.n_tris;
-    const SceneBufs& b = c->dev;
-    a.wtris = b.wtris.p;
-    a.shade = b.shade_tris.p;
-    a.nodes4 = b.nodes4.p;
-    a.nodesq = b.nodesq.p;
-    a.order = c->d_mesh_order.p;
-    a.level_start = c->d_mesh_levels.p + mr.level_first;
-    a.root4 = mr.root4;
-    a.bvh = b.bvh.p;
-    a.bvh_root = mr.bvh_root;
-    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->ref.inst_cut_boxes.empty();
-    a.cut_range = cuts ? b.cut_range.p : nullptr;
-    a.instances = b.set[0].inst.p;   // (blas_index is the same in every copy of the instance level)
-    a.n_instances = n_inst;
-    launch_mesh_refit(rs, a, c->mesh_levels_h.data() + mr.level_first, mr.n_levels);
-    HIP_TRY(c, hipGetLastError());
-    // the instance level over the new root boxes, with the current transforms, as jpt_scene_refit_tlas does
-    const int rc = queue_instance_refit(c, dev_transforms, n_inst);
-    if (rc != JPT_OK) return rc;
-    HIP_TRY(c, hipEventRecord(c->mesh_stage.copied[st], rs));
-    c->cull_boxes_current = false;   // the host's TLAS boxes are stale: no sky cull until the next upload
-    c->refit_active = true;
-    c->ds.x.tlas_current = false;
-    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return JPT_OK;
-}
-
-}  // namespace
-
-int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
-{
-    if (!c) return JPT_E_INVALID;
-    std::vector<SurfaceView> sv;
-    int with_normals = 0;
-    int rc = check_mesh_arrays(c, "jpt_scene_update_mesh", mesh_id, surfaces, n_surfaces, sv, with_normals);
-    if (rc != JPT_OK) return rc;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the update runs on the device");
-    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_mesh_refit(c);
-    if (rc != JPT_OK) return rc;
-    c->mesh_deformed = true;   // (the host's arrays describe the committed vertices from here on)
-    const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
-    if (!mr.has_tree) return JPT_OK;   // no instance names the mesh: the device holds nothing of it
-    hipStream_t s = c->stream, rs = c->refit_stream;
-    // staging: [6 ordered keys + pad: 32 B][vertices][normals][transforms]; the first three parts are copied to the device, the
-    // instance refit reads the transforms from the pinned buffer
-    const size_t nv = c->builder.mesh_vertex_count(mesh_id);
-    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
-    const size_t head = 32, vbytes = nv * 3 * sizeof(float), nbytes = with_normals ? vbytes : 0, tbytes = (size_t)n_inst * 12 * sizeof(float);
-    const size_t dev_bytes = head + vbytes + nbytes, bytes = dev_bytes + tbytes;
-    int st = 0;
-    HIP_TRY(c, c->mesh_stage.next(bytes, st));
-    if (!c->ev_mesh_drain) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_drain, hipEventDisableTiming));
-    char* h = c->mesh_stage.buf[st].as<char>();
-    {
-        int32_t keys[8] = {ordered_key(FLT_MAX), ordered_key(FLT_MAX), ordered_key(FLT_MAX),
-                           ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), 0, 0};
-        std::memcpy(h, keys, sizeof keys);
-        size_t off = head;
-        for (const SurfaceView& x : sv) {
-            const size_t b = (size_t)x.n_vertices * 3 * sizeof(float);
-            if (b) std::memcpy(h + off, x.vertices, b);
-            if (b && with_normals) std::memcpy(h + off + vbytes, x.normals, b);
-            off += b;
-        }
-        for (uint32_t i = 0; i < n_inst; i++) std::memcpy(h + dev_bytes + (size_t)i * 48, c->builder.instance_transform(i), 48);
-    }
-    if (c->d_mesh_in.n < dev_bytes) {
-        HIP_TRY(c, hipStreamSynchronize(rs));   // (an earlier update may still read the old buffer)
-        HIP_TRY(c, c->d_mesh_in.resize(dev_bytes));
-    }
-    char* hdev = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&hdev, h, 0));
-    // The BLAS records, triangle records and root boxes are shared by every copy of the instance level: the update waits on the
-    // device for every render queued before it (the context's stream follows them all) -- one pipeline drain.
-    HIP_TRY(c, hipEventRecord(c->ev_mesh_drain, s));
-    HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_mesh_drain, 0));
-    HIP_TRY(c, hipMemcpyAsync(c->d_mesh_in.p, h, dev_bytes, hipMemcpyHostToDevice, rs));
-    return queue_mesh_refit(c, mr, reinterpret_cast<const float*>(c->d_mesh_in.p + head),
-                            with_normals ? reinterpret_cast<const float*>(c->d_mesh_in.p + head + vbytes) : nullptr,
-                            reinterpret_cast<const float*>(hdev + dev_bytes), st, t0);
-}
-
-int jpt_scene_set_mesh_rig(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* bind, const jpt_surface_rig* rigs, int32_t n_surfaces, int32_t influences,
-                           int32_t n_blend_shapes)
-{
-    if (!c) return JPT_E_INVALID;
-    std::vector<SurfaceView> sv;
-    int with_normals = 0;
-    int rc = check_mesh_arrays(c, "jpt_scene_set_mesh_rig", mesh_id, bind, n_surfaces, sv, with_normals);
-    if (rc != JPT_OK) return rc;
-    if (n_surfaces && !rigs) return fail(c, JPT_E_INVALID, "jpt_scene_set_mesh_rig: bad rig array");
-    std::vector<SkinPiece> pieces((size_t)n_surfaces);
-    for (int32_t i = 0; i < n_surfaces; i++) {
-        SkinPiece& x = pieces[(size_t)i];
-        x.n_vertices = bind[i].n_vertices;
-        x.positions = bind[i].vertices;
-        x.normals = bind[i].normals;
-        x.bones = rigs[i].bones;
-        x.weights = rigs[i].weights;
-        x.dpos = rigs[i].position_deltas;
-        x.dnrm = rigs[i].normal_deltas;
-    }
-    SkinRigInfo info;
-    std::string why;
-    rc = check_skin_rig("jpt_scene_set_mesh_rig", pieces.data(), n_surfaces, influences, n_blend_shapes, with_normals != 0, info, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the rig is kept on the device");
-    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
-    HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_mesh_refit(c);
-    if (rc != JPT_OK) return rc;
-    {
-        auto old = c->mesh_rigs.find(mesh_id);
-        if (old != c->mesh_rigs.end()) {
-            if (old->second.d_rig.p) HIP_TRY(c, hipStreamSynchronize(c->refit_stream));   // (a queued pose may still read the rig this one replaces)
-            c->mesh_rigs.erase(old);
-        }
-    }
-    jpt_ctx::MeshRig& rig = c->mesh_rigs[mesh_id];
-    rig.info = info;
-    if (!c->mesh_refit[mesh_id].has_tree || info.bytes == 0) return JPT_OK;   // no instance names the mesh: nothing of it on the device
-    std::vector<char> block(info.bytes);
-    pack_skin_rig(info, pieces.data(), n_surfaces, block.data());
-    hipError_t e = rig.d_rig.resize(info.bytes);
-    if (e == hipSuccess) e = hipMemcpyAsync(rig.d_rig.p, block.data(), info.bytes, hipMemcpyHostToDevice, c->refit_stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->refit_stream);   // pageable host memory
-    if (e != hipSuccess) {
-        c->mesh_rigs.erase(mesh_id);
-        return hip_fail(c, e, "jpt_scene_set_mesh_rig: the rig's copy");
-    }
-    return JPT_OK;
-}
-
-int jpt_scene_clear_mesh_rig(jpt_ctx* c, uint32_t mesh_id)
-{
-    if (!c) return JPT_E_INVALID;
-    auto it = c->mesh_rigs.find(mesh_id);
-    if (it == c->mesh_rigs.end()) return JPT_OK;
-    if (it->second.d_rig.p) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        if (c->refit_stream) HIP_TRY(c, hipStreamSynchronize(c->refit_stream));   // (a queued pose may still read it)
-    }
-    c->mesh_rigs.erase(it);
-    return JPT_OK;
-}
-
-int jpt_scene_pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
-{
-    if (!c) return JPT_E_INVALID;
-    // jpt_scene_update_mesh's state rules, on their own account: a rig is dropped with its scene, but a pose does not rely on that
-    if (!c->host_scene_ready || c->building || !c->from_commit || !walks_nodes4(c) || c->tree != JPT_TREE_NATIVE_WATERTIGHT)
-        return fail(c, JPT_E_STATE, "jpt_scene_pose_mesh needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT");
-    auto it = c->mesh_rigs.find(mesh_id);
-    if (it == c->mesh_rigs.end()) return fail(c, JPT_E_STATE, "jpt_scene_pose_mesh: the mesh has no rig (jpt_scene_set_mesh_rig; a commit or an upload drops it)");
-    const jpt_ctx::MeshRig& rig = it->second;
-    const SkinRigInfo& info = rig.info;
-    std::vector<SkinShape> active;
-    std::string why;
-    int rc = check_skin_pose("jpt_scene_pose_mesh", info, bone_transforms12, n_bones, blend_weights, n_blend_weights, active, why);
-    if (rc != JPT_OK) return fail(c, rc, why);
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the pose runs on the device");
-    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(c, hipSetDevice(c->device));
-    rc = ensure_mesh_refit(c);
-    if (rc != JPT_OK) return rc;
-    const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
-    // no instance names the mesh: the device holds nothing of it, nothing changes anywhere and the host's copy of the scene stays current
-    if (!mr.has_tree || !rig.d_rig.p) return JPT_OK;
-    c->mesh_deformed = true;   // (as jpt_scene_update_mesh: the host's arrays describe the committed vertices from here on)
-    hipStream_t s = c->stream, rs = c->refit_stream;
-    // staging: [6 ordered keys + pad: 32 B][palette: the bones the rig can name][active shapes, padded to 16 B][transforms]; the first
-    // three parts are copied to the head of d_mesh_in, where the vertices and normals the skin kernel writes follow them
-    const size_t nv = info.n_vertices;
-    const uint32_t n_pal = info.influences ? (uint32_t)(info.max_bone + 1) : 0u;
-    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
-    const size_t head = 32, pbytes = (size_t)n_pal * 48, abytes = (active.size() * sizeof(SkinShape) + 15u) & ~(size_t)15u;
-    const size_t in_bytes = head + pbytes + abytes, vbytes = (nv * 3 * sizeof(float) + 15u) & ~(size_t)15u, nbytes = info.with_normals ? vbytes : 0;
-    const size_t dev_bytes = in_bytes + vbytes + nbytes, tbytes = (size_t)n_inst * 12 * sizeof(float);
-    int st = 0;
-    HIP_TRY(c, c->mesh_stage.next(in_bytes + tbytes, st));
-    if (!c->ev_mesh_drain) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_mesh_drain, hipEventDisableTiming));
-    char* h = c->mesh_stage.buf[st].as<char>();
-    {
-        int32_t keys[8] = {ordered_key(FLT_MAX), ordered_key(FLT_MAX), ordered_key(FLT_MAX),
-                           ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), 0, 0};
-        std::memcpy(h, keys, sizeof keys);
-        if (pbytes) std::memcpy(h + head, bone_transforms12, pbytes);
-        std::memset(h + head + pbytes, 0, abytes);
-        if (!active.empty()) std::memcpy(h + head + pbytes, active.data(), active.size() * sizeof(SkinShape));
-        for (uint32_t i = 0; i < n_inst; i++) std::memcpy(h + in_bytes + (size_t)i * 48, c->builder.instance_transform(i), 48);
-    }
-    if (c->d_mesh_in.n < dev_bytes) {
-        HIP_TRY(c, hipStreamSynchronize(rs));   // (an earlier update may still read the old buffer)
-        HIP_TRY(c, c->d_mesh_in.resize(dev_bytes));
-    }
-    char* hdev = nullptr;
-    HIP_TRY(c, hipHostGetDevicePointer((void**)&hdev, h, 0));
-    // d_mesh_in is read and written by work on the refit stream alone (the copies and kernels of the updates and poses; no render, read-back or
-    // instance refit touches it), and that stream runs in order: the pose's copy and the skin kernel are queued AHEAD of the drain wait,
-    // so they run beside the renders still in flight; only the refit of the shared records waits for them.
-    HIP_TRY(c, hipMemcpyAsync(c->d_mesh_in.p, h, in_bytes, hipMemcpyHostToDevice, rs));
-    SkinArgs a;
-    a.rig = skin_rig_view(info, rig.d_rig.p);
-    a.influences = info.influences;
-    a.palette = reinterpret_cast<const float*>(c->d_mesh_in.p + head);
-    a.n_bones = n_pal;
-    a.active = reinterpret_cast<const SkinShape*>(c->d_mesh_in.p + head + pbytes);
-    a.n_active = (uint32_t)active.size();
-    a.verts_out = reinterpret_cast<float*>(c->d_mesh_in.p + in_bytes);
-    a.normals_out = info.with_normals ? reinterpret_cast<float*>(c->d_mesh_in.p + in_bytes + vbytes) : nullptr;
-    launch_mesh_skin(rs, a);
-    HIP_TRY(c, hipGetLastError());
-    // The BLAS records, triangle records and root boxes are shared by every copy of the instance level: one pipeline drain on the
-    // device, as jpt_scene_update_mesh
-    HIP_TRY(c, hipEventRecord(c->ev_mesh_drain, s));
-    HIP_TRY(c, hipStreamWaitEvent(rs, c->ev_mesh_drain, 0));
-    return queue_mesh_refit(c, mr, a.verts_out, a.normals_out, reinterpret_cast<const float*>(hdev + in_bytes), st, t0);
-}
-
-int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void* nodesq_out, uint32_t node_capacity, void* tris_out,
-                           void* shade_out, uint32_t tri_capacity, int32_t* info_out)
-{
-    if (!c || !info_out) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !c->from_commit || c->tree != JPT_TREE_NATIVE_WATERTIGHT)
-        return fail(c, JPT_E_STATE, "jpt_debug_mesh_records needs a scene committed with JPT_BUILD_SAH_WATERTIGHT");
-    if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the records are on the device");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int rc = ensure_mesh_refit(c);
-    if (rc != JPT_OK) return rc;
-    const jpt_ctx::MeshRefit& mr = c->mesh_refit[mesh_id];
-    info_out[0] = mr.has_tree ? 1 : 0;
-    info_out[1] = mr.root4;
-    info_out[2] = (int32_t)mr.rec_first;
-    info_out[3] = (int32_t)mr.n_recs;
-    info_out[4] = (int32_t)mr.tri_first;
-    info_out[5] = (int32_t)mr.n_tris;
-    if (!mr.has_tree) return JPT_OK;
-    if ((nodes4_out || nodesq_out) && node_capacity < mr.n_recs) return fail(c, JPT_E_INVALID, "record buffers too small");
-    if ((tris_out || shade_out) && tri_capacity < mr.n_tris) return fail(c, JPT_E_INVALID, "triangle buffers too small");
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the context's stream follows every update)
-    if (nodes4_out && mr.n_recs)
-        HIP_TRY(c, hipMemcpy(nodes4_out, c->dev.nodes4.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNode4), hipMemcpyDeviceToHost));
-    if (nodesq_out && mr.n_recs)
-        HIP_TRY(c, hipMemcpy(nodesq_out, c->dev.nodesq.p + mr.rec_first, (size_t)mr.n_recs * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
-    if (tris_out) HIP_TRY(c, hipMemcpy(tris_out, c->dev.wtris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(WideTri), hipMemcpyDeviceToHost));
-    if (shade_out) HIP_TRY(c, hipMemcpy(shade_out, c->dev.shade_tris.p + mr.tri_first, (size_t)mr.n_tris * sizeof(ShadeTri), hipMemcpyDeviceToHost));
-    return JPT_OK;
-}
-
-int jpt_debug_tlas_records(jpt_ctx* c, void* nodes4_out, void* nodesq_out, uint32_t capacity, uint32_t* n_records, int32_t* root_out, float* inst_lo3,
-                           float* inst_hi3)
-{
-    if (!c) return JPT_E_INVALID;
-    if (!c->host_scene_ready || c->building || !walks_nodes4(c) || !c->from_commit)
-        return fail(c, JPT_E_STATE, "jpt_debug_tlas_records needs a scene made by jpt_scene_commit with the native builder");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the records are on the device");
-    if (!c->scene_ready || !c->ds.use4) return fail(c, JPT_E_STATE, "no scene on the device");
-    const size_t nt = c->wide.tlas_nodes4.size(), ni = c->ref.instances.size();
-    const int32_t base = (int32_t)(c->wide.blas_nodes4.size() + (size_t)c->cur_set * c->tlas4_cap);
-    if (n_records) *n_records = (uint32_t)nt;
-    if (root_out) *root_out = c->ds.tlas_root4 >= 0 ? c->ds.tlas_root4 - base : c->ds.tlas_root4;
-    if ((nodes4_out || nodesq_out) && capacity < nt) return fail(c, JPT_E_INVALID, "record buffers too small");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the context's stream follows every refit)
-    if (nodes4_out && nt) {
-        HIP_TRY(c, hipMemcpy(nodes4_out, c->dev.nodes4.p + base, nt * sizeof(WideNode4), hipMemcpyDeviceToHost));
-        WideNode4* r = static_cast<WideNode4*>(nodes4_out);
-        for (size_t i = 0; i < nt; i++)
-            for (int k = 0; k < 4; k++)
-                if (r[i].child[k] >= 0) r[i].child[k] -= base;
-    }
-    if (nodesq_out && nt) {
-        HIP_TRY(c, hipMemcpy(nodesq_out, c->dev.nodesq.p + base, nt * sizeof(WideNodeQ), hipMemcpyDeviceToHost));
-        WideNodeQ* r = static_cast<WideNodeQ*>(nodesq_out);
-        for (size_t i = 0; i < nt; i++)
-            for (int k = 0; k < 4; k++)
-                if (r[i].child[k] >= 0) r[i].child[k] -= base;
-    }
-    if ((inst_lo3 || inst_hi3) && ni) {
-        std::vector<RefInstance> inst(ni);
-        HIP_TRY(c, hipMemcpy(inst.data(), c->dev.set[c->cur_set].inst.p, ni * sizeof(RefInstance), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < ni; i++) {
-            if (inst_lo3) inst_lo3[3 * i] = inst[i].aabbMin.x, inst_lo3[3 * i + 1] = inst[i].aabbMin.y, inst_lo3[3 * i + 2] = inst[i].aabbMin.z;
-            if (inst_hi3) inst_hi3[3 * i] = inst[i].aabbMax.x, inst_hi3[3 * i + 1] = inst[i].aabbMax.y, inst_hi3[3 * i + 2] = inst[i].aabbMax.z;
-        }
-    }
-    return JPT_OK;
 }
 
 int jpt_scene_update_reference_tlas(jpt_ctx* c, const void* blas_instances, uint32_t n_instances, const void* tlas_nodes,
@@ -2202,9 +1528,9 @@ int jpt_scene_update_reference_tlas(jpt_ctx* c, const void* blas_instances, uint
 int jpt_scene_get_reference_buffer(jpt_ctx* c, int32_t which, void* out, size_t capacity, size_t* size_out)
 {
     if (!c) return JPT_E_INVALID;
-    if (c->mesh_deformed)
+    if (c->upd.mesh_deformed)
         return fail(c, JPT_E_STATE, "a mesh was deformed on the device (jpt_scene_update_mesh): the host's copy of the scene is stale until the next jpt_scene_commit");
-    if (c->refit_active && (which == JPT_BUF_INSTANCES || which == JPT_BUF_TLAS_NODES || which == JPT_BUF_REACH_INSTANCES)) {
+    if (c->upd.refit_active && (which == JPT_BUF_INSTANCES || which == JPT_BUF_TLAS_NODES || which == JPT_BUF_REACH_INSTANCES)) {
         // the instance level was last refitted on the device: bring the host mirrors (and the device) to a fresh build
         const int rc = jpt_scene_update_tlas(c);
         if (rc != JPT_OK) return rc;

@@ -1,5 +1,5 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
+// (jpt_capi.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
 #pragma once
 #include "../../include/jpt.h"
 
@@ -132,7 +132,7 @@ struct PipeSlot {
     hipStream_t stream = nullptr;
     hipEvent_t ev_paths_done = nullptr, ev_acc_done = nullptr;
     bool acc_done_valid = false;   // ev_acc_done follows the last accumulation that read `workspace`
-    uint64_t refit_seen = 0;       // the refit (jpt_ctx::refit_wait_seq) the slot's stream has last waited for
+    uint64_t refit_seen = 0;       // the refit (SceneUpdates::refit_wait_seq) the slot's stream has last waited for
     DevBuf<char> workspace;
 };
 
@@ -336,6 +336,99 @@ int ensure_variance(jpt_ctx* c);
 int reads_sum(jpt_ctx* c, const char* call, const char* what, const char* host_only, const char* whole = "", const char* steps = nullptr);
 int sum_ready(jpt_ctx* c, const char* call);
 
+// What the context holds of the calls that change a committed scene on the device without a new commit (the refits, rebuilds, mesh updates,
+// rigs and poses of jpt_scene_update.cpp, and its two debug readers).  The uploads (jpt_capi.cpp) put it back through host_uploaded; the
+// renders read cur_set through the view, wait for ev_refit_done and refuse on refit_active / mesh_deformed.
+struct SceneUpdates {
+    // device refit of the instance level (jpt_scene_refit_tlas)
+    StagingRing refit_stage;           // pinned staging for the transforms
+    size_t tlas4_cap = 0;              // records reserved per TLAS tail
+    int cur_set = 0;                   // which copy new renders read
+    bool set_b_ready = false;          // copies 1.. exist and mirror the last host upload
+    hipStream_t refit_stream = nullptr;
+    hipEvent_t ev_set_retired[kInstanceSets] = {}, ev_refit_done = nullptr;
+    bool set_retired_valid[kInstanceSets] = {};
+    uint64_t refit_wait_seq = 0;
+    DevBuf<uint32_t> d_tlas4_order, d_tlas4_levels;
+    bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
+    bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
+    std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
+    // a new topology made on the device (jpt_scene_rebuild_tlas): the template of the scene's instance count with its schedule and the
+    // sort's buffers, made at the first rebuild of that count and kept.  After a rebuild c->wide.tlas_nodes4 / tlas_root4 / stack_need4
+    // and the schedule's host copy above are the template's, and the refits run over tmpl_order / tmpl_levels (topo_rebuilt), until
+    // the next upload.  topo_gen counts the rebuilds since the last upload; set_topo_gen[k]: the one whose topology the TLAS tail of
+    // copy k holds (a refit into a copy that is behind first copies the current copy's tail: queue_instance_refit).
+    TlasTemplate tlas_tmpl;
+    std::vector<uint32_t> tmpl_order_h, tmpl_levels_h;
+    uint32_t tmpl_stack_need = 0;
+    DevBuf<int32_t> d_tmpl_child;
+    DevBuf<uint32_t> d_tmpl_order, d_tmpl_levels, d_tlas_sorted;
+    DevBuf<uint64_t> d_tlas_sort_keys;
+    bool topo_rebuilt = false;
+    uint32_t topo_gen = 0, set_topo_gen[kInstanceSets] = {};
+    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in dev.nodes4 and its schedule
+    // (refit4_schedule), made at the first update after an upload
+    struct MeshRefit {
+        bool has_tree = false;              // an instance names the mesh and it has triangles: the device holds its tree
+        int32_t root4 = 0;                  // its root reference in dev.nodes4
+        uint32_t bvh_root = 0;              // its root in dev.bvh (RefScene::mesh_roots)
+        uint32_t tri_first = 0, n_tris = 0;
+        uint32_t rec_first = 0, n_recs = 0;  // the span of dev.nodes4 its records occupy
+        uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
+    };
+    std::vector<MeshRefit> mesh_refit;
+    bool mesh_refit_ready = false;
+    std::vector<uint32_t> mesh_order_h, mesh_levels_h;
+    DevBuf<uint32_t> d_mesh_order, d_mesh_levels, d_tri_vidx;
+    DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
+    StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
+    hipEvent_t ev_mesh_drain = nullptr;
+    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
+    // posing committed meshes on the device (jpt_scene_set_mesh_rig / jpt_scene_pose_mesh): per rigged mesh the rig's layout and, when
+    // an instance names the mesh, its block on the device (jpt_kernels_skin.hip); dropped by jpt_scene_begin and every upload
+    struct MeshRig {
+        SkinRigInfo info;
+        DevBuf<char> d_rig;   // empty for a mesh no instance names
+    };
+    std::map<uint32_t, MeshRig> mesh_rigs;
+    // The one place that says which state a host upload puts back (finish_upload, jpt_capi.cpp): of the whole scene `w` (`whole`) or of
+    // its instance level only, which leaves what is known of the meshes.  A scene without four-child records uploads no tails:
+    // tlas4_cap and cull_boxes_current then stay what the scene before it left.
+    void host_uploaded(bool whole, const WideScene& w)
+    {
+        cur_set = 0;
+        set_b_ready = false;  // the instance arrays of the other copies are made (again) by the next refit
+        for (bool& v : set_retired_valid) v = false;
+        // every tail gets the host's topology again: the refits run over its schedule until the next jpt_scene_rebuild_tlas
+        topo_rebuilt = false;
+        topo_gen = 0;
+        for (uint32_t& g : set_topo_gen) g = 0;
+        refit_active = false;
+        if (whole) mesh_deformed = mesh_refit_ready = false;
+        if (!w.instances4.empty() || !w.blas_nodes4.empty()) cull_boxes_current = true;
+    }
+    // the first record of copy k's TLAS tail in dev.nodes4 (upload_nodes4: the BLAS records, then one tail per copy)
+    size_t tail_first(const WideScene& w, int k) const { return w.blas_nodes4.size() + (size_t)k * tlas4_cap; }
+    // The refit stream and the events ensure_refit_stream and the mesh calls make, given back once the stream has run dry (jpt_destroy)
+    void destroy_stream()
+    {
+        if (refit_stream) { (void)hipStreamSynchronize(refit_stream); (void)hipStreamDestroy(refit_stream); }
+        for (hipEvent_t e : ev_set_retired) if (e) (void)hipEventDestroy(e);
+        if (ev_refit_done) (void)hipEventDestroy(ev_refit_done);
+        if (ev_mesh_drain) (void)hipEventDestroy(ev_mesh_drain);
+    }
+};
+// the view the kernels take (c->ds) of the scene's device arrays, with the instance level of the copy new renders read (jpt_capi.cpp)
+void set_scene_view(jpt_ctx* c);
+// the rigs of jpt_scene_set_mesh_rig leave with the scene they were set for, behind the refit stream (jpt_scene_update.cpp)
+void drop_mesh_rigs(jpt_ctx* c);
+// The refusals these calls open with: no context (JPT_E_INVALID), no scene from jpt_scene_commit ("<call><what>"); for the two trees a
+// JPT_BUILD_REFERENCE_EXACT commit (`exact`: the call's sentence, null: "<call><what>" again); for kWatertightTree a JPT_BUILD_SAH commit (`sah`,
+// likewise).  on_device, after the argument checks: a host-only context, in the call's words, and with `scene` "no scene on the device"
+enum SceneNeed { kFromCommit, kNativeTree, kWatertightTree };
+int needs_scene(jpt_ctx* c, SceneNeed need, const char* call, const char* what, const char* exact = nullptr, const char* sah = nullptr);
+int on_device(jpt_ctx* c, const char* host_only, bool scene);
+
 }  // namespace jpt
 
 using namespace jpt;   // (jpt_ctx is the name include/jpt.h gives it: global)
@@ -389,6 +482,7 @@ struct jpt_ctx {
     int last_pipe_slots = 0;               // jpt_renders_in_flight
     bool aux_borrowed[kMaxGroups - 1] = {};   // group_streams.aux_stream[k] is slot[k].stream (ensure_group_streams): not destroyed on its own
     uint64_t async_seq = 0;
+    int idle_streak = 0;   // queued renders in a row that found nothing in flight (plan_launch)
     std::vector<uint32_t> h_qcount;  // per-bounce queue sizes of the last wavefront render
     std::vector<hipEvent_t> trace_events;  // pairs around each wf_trace launch of the last render
     int32_t trace_events_used = 0;
@@ -418,59 +512,6 @@ struct jpt_ctx {
     DevBuf<float4> d_hist1, d_hist2;   // frameBuffer1 / frameBuffer2 of temporal_reprojection.glsl:16-17
     float4* hist_written = nullptr;    // the one the last temporal pass wrote
 
-    // device refit of the instance level (jpt_scene_refit_tlas)
-    StagingRing refit_stage;           // pinned staging for the transforms
-    size_t tlas4_cap = 0;              // records reserved per TLAS tail
-    int cur_set = 0;                   // which copy new renders read
-    bool set_b_ready = false;          // copies 1.. exist and mirror the last host upload
-    hipStream_t refit_stream = nullptr;
-    hipEvent_t ev_set_retired[kInstanceSets] = {}, ev_refit_done = nullptr;
-    bool set_retired_valid[kInstanceSets] = {};
-    uint64_t refit_wait_seq = 0;
-    int idle_streak = 0;   // queued renders in a row that found nothing in flight (plan_launch)
-    DevBuf<uint32_t> d_tlas4_order, d_tlas4_levels;
-    uint32_t n_tlas4_levels = 0;
-    bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
-    bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
-    std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
-    // a new topology made on the device (jpt_scene_rebuild_tlas): the template of the scene's instance count with its schedule and the
-    // sort's buffers, made at the first rebuild of that count and kept.  After a rebuild c->wide.tlas_nodes4 / tlas_root4 / stack_need4
-    // and the schedule's host copy above are the template's, and the refits run over tmpl_order / tmpl_levels (topo_rebuilt), until
-    // the next upload.  topo_gen counts the rebuilds since the last upload; set_topo_gen[k]: the one whose topology the TLAS tail of
-    // copy k holds (a refit into a copy that is behind first copies the current copy's tail: queue_instance_refit).
-    TlasTemplate tlas_tmpl;
-    std::vector<uint32_t> tmpl_order_h, tmpl_levels_h;
-    uint32_t tmpl_stack_need = 0;
-    DevBuf<int32_t> d_tmpl_child;
-    DevBuf<uint32_t> d_tmpl_order, d_tmpl_levels, d_tlas_sorted;
-    DevBuf<uint64_t> d_tlas_sort_keys;
-    bool topo_rebuilt = false;
-    uint32_t topo_gen = 0, set_topo_gen[kInstanceSets] = {};
-    // deforming committed meshes on the device (jpt_scene_update_mesh).  Per mesh: its records in dev.nodes4 and its schedule
-    // (refit4_schedule), made at the first update after an upload
-    struct MeshRefit {
-        bool has_tree = false;              // an instance names the mesh and it has triangles: the device holds its tree
-        int32_t root4 = 0;                  // its root reference in dev.nodes4
-        uint32_t bvh_root = 0;              // its root in dev.bvh (RefScene::mesh_roots)
-        uint32_t tri_first = 0, n_tris = 0;
-        uint32_t rec_first = 0, n_recs = 0;  // the span of dev.nodes4 its records occupy
-        uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
-    };
-    std::vector<MeshRefit> mesh_refit;
-    bool mesh_refit_ready = false;
-    std::vector<uint32_t> mesh_order_h, mesh_levels_h;
-    DevBuf<uint32_t> d_mesh_order, d_mesh_levels, d_tri_vidx;
-    DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
-    StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
-    hipEvent_t ev_mesh_drain = nullptr;
-    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
-    // posing committed meshes on the device (jpt_scene_set_mesh_rig / jpt_scene_pose_mesh): per rigged mesh the rig's layout and, when
-    // an instance names the mesh, its block on the device (jpt_kernels_skin.hip); dropped by jpt_scene_begin and every upload
-    struct MeshRig {
-        SkinRigInfo info;
-        DevBuf<char> d_rig;   // empty for a mesh no instance names
-    };
-    std::map<uint32_t, MeshRig> mesh_rigs;
     PinnedBuf h_ldr_pinned;    // the split read-back of the display image
     PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
     hipEvent_t ev_readback = nullptr;
@@ -480,6 +521,7 @@ struct jpt_ctx {
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
     PrimaryState primary;     // the lens, the camera model, the bake images, the probes and the reflection probes (jpt_primary.cpp)
     PostState post;           // the parameters, buffers and validity flags of the calls that read the progressive sum (jpt_post.cpp)
+    SceneUpdates upd;         // the copies, streams, schedules and flags of the calls that change a committed scene on the device (jpt_scene_update.cpp)
 
     // jpt_encode (jpt_encode.cpp): its own buffer, grow-only and kept until jpt_destroy -- a snapshot that no other call writes;
     // enc_valid: it holds the texels enc_info describes.  enc_ev: two events around the last jpt_encode's kernel under
@@ -500,6 +542,11 @@ struct jpt_ctx {
 
     jpt_stats stats;
 };
+
+// the kernels walk the four-child records of the native tree (the native builder's trees and native uploads); reference-exact and
+// as-given trees keep the two-child records so the kernels visit them node for node like main.glsl (event counters equal the
+// oracle's)
+static inline bool walks_nodes4(const jpt_ctx* c) { return c->tree == JPT_TREE_NATIVE_REACH || c->tree == JPT_TREE_NATIVE_WATERTIGHT; }
 
 static inline int fail(jpt_ctx* c, int code, const std::string& msg)
 {

@@ -1,4 +1,4 @@
-// jpt_kernels.h -- what the host layer (jpt_capi.cpp, jpt_lighting.cpp, jpt_primary.cpp) sees of the device code, and the two values a
+// jpt_kernels.h -- what the host layer (jpt_capi.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp) sees of the device code, and the two values a
 // render's launches read: its Lighting and its PrimaryRays.
 #pragma once
 

@@ -1,7 +1,7 @@
 // jpt_mesh_math.h -- the per-triangle arithmetic of the native BLAS, written once for the host builder (jpt_builder.cpp: flatten,
 // SahBlasBuilder) and for the device refit of a deformed mesh (jpt_kernels_mesh.hip, jpt_scene_update_mesh), and the refit
 // arithmetic of the four-child records and of the instances' cut boxes, written once for the device refits (jpt_kernels_mesh.hip,
-// jpt_kernels_post.hip), the host's mirror of the TLAS refit (jpt_capi.cpp) and the host builder (InstanceCuts): plain float
+// jpt_kernels_post.hip), the host's mirror of the TLAS refit (jpt_scene_update.cpp) and the host builder (InstanceCuts): plain float
 // arithmetic only, compiled without contraction on both sides, so the two give the same bits.
 #pragma once
 

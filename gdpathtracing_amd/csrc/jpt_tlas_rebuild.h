@@ -1,5 +1,5 @@
 // jpt_tlas_rebuild.h -- the arithmetic of jpt_scene_rebuild_tlas, written once for the device (jpt_kernels_tlas.hip), for the host's
-// mirror of it (the sky cull's boxes, jpt_capi.cpp) and for jpt_debug_tlas_order's host form: the sort key of an instance from its
+// mirror of it (the sky cull's boxes, jpt_scene_update.cpp) and for jpt_debug_tlas_order's host form: the sort key of an instance from its
 // world box, and the fixed four-way topology over the sorted instances.  Every float step is one binary32 operation, a
 // compare-and-select or a floor, in source order, compiled without contraction on both sides, so the two give the same bits.
 #pragma once

@@ -16,7 +16,7 @@ import np_skin
 import np_tlas_rebuild as ref
 from test_gpu_mesh_update import deform
 from test_gpu_parity import _moved, _moves_for, _render_hip, rel_l2
-from test_gpu_skin import TUBE, host_rigs, pose as skin_pose, small_scene, tube_rigs, with_mesh
+from test_gpu_skin import SPARE, TUBE, host_rigs, pose as skin_pose, small_scene, tube_rigs, with_mesh
 from test_tlas_rebuild_host import ORDER_CASES
 
 pytestmark = pytest.mark.gpu
@@ -294,6 +294,107 @@ def _fresh_watertight(scene):
         return _watertight_frame(ctx)
     finally:
         ctx.close()
+
+
+STALE_HOST_COPY = "a mesh was deformed on the device (jpt_scene_update_mesh): the host's copy of the scene is stale until the next jpt_scene_commit"
+
+
+def _five_instances():
+    """small_scene with its spare box named by two more instances: three meshes, five instances"""
+    sc = small_scene()
+    sc.instances = sc.instances + [scenes.Instance(SPARE, scenes.transform12(scenes.rot_y(25.0), (-1.1, 0.5, 0.4)), [1]),
+                                   scenes.Instance(SPARE, scenes.transform12(np.eye(3) * 0.6, (1.2, 0.3, 0.9)), [4])]
+    return sc
+
+
+def _small_ctx(scene):
+    ctx = host.Context(0)
+    ctx.build_scene(scene, capi.BUILD_SAH_WATERTIGHT)
+    ctx.set_params(64, 48, 2)
+    ctx.set_camera(scenes.camera_block(scene.camera, 64, 48))
+    return ctx
+
+
+def _small_frame(ctx, asynchronous):
+    """2 frames; (accum, depth, rays) as _watertight_frame gives them -- a queued render is not counted: its ray count is what the statistics hold"""
+    ctx.accum_reset()
+    ctx.render(2, 1, counted=not asynchronous, asynchronous=asynchronous)
+    return ctx.read_accum(), ctx.read_depth(), ctx.stats()["rays"]
+
+
+def test_every_scene_update_in_one_context_queued_equals_synced_and_fresh_commits(hiplib):
+    """Every way the device's scene moves ahead of the host and is put back, in one context: refit, render, rebuild, render, jpt_scene_update_mesh,
+    pose, a refit into a copy whose tail is a topology behind, render, the host route refused for the deformed mesh, a whole commit, a refit
+    that makes the copies again, render.  Queued without a wait up to the third image, every image equals, bit for bit, the one of the same
+    calls with jpt_sync after each; the third and the fourth equal a fresh commit of the same vertices and transforms."""
+    import torch
+    sc = _five_instances()
+    bind, rigs = sc.meshes[TUBE], tube_rigs(sc.meshes[TUBE])
+    pal, bw = skin_pose(1)
+    posed, bent = np_skin.skin_mesh(bind, rigs, 4, pal, bw), deform(sc.meshes[SPARE], 1)
+    m1 = _jitter_all(sc, 3)
+    m2 = _jitter_all(m1, 4)
+    m3 = _jitter_all(m2, 5)
+    m4 = _jitter_all(m3, 6)
+    at8, at12 = (with_mesh(with_mesh(m, SPARE, bent), TUBE, posed) for m in (m3, m4))
+
+    def run(synced):
+        ctx = _small_ctx(sc)
+        after = ctx.sync if synced else (lambda: None)
+        try:
+            ctx.set_mesh_rig(TUBE, bind, host_rigs(rigs), 4, 2)
+            stream = torch.cuda.ExternalStream(ctx.get_stream(), device=torch.device("cuda", 0))
+            ptr, nbytes = ctx.device_accum()
+
+            class _View:
+                __cuda_array_interface__ = {"shape": (nbytes // 4,), "typestr": "<f4", "data": (ptr, False), "version": 2}
+
+            accum, snaps = torch.as_tensor(_View(), device=torch.device("cuda", 0)), []
+
+            def queued_frame():
+                ctx.accum_reset()
+                ctx.render(2, 1, asynchronous=True)
+                after()
+                snaps.append(accum.clone())
+
+            with torch.cuda.stream(stream):
+                ctx.refit_tlas(all_t12(m1))                    # 1
+                after()
+                queued_frame()                                 # 2
+                ctx.rebuild_tlas(all_t12(m2))                  # 3
+                after()
+                queued_frame()                                 # 4
+                ctx.update_mesh(SPARE, bent)                   # 5
+                after()
+                ctx.pose_mesh(TUBE, pal, bw)                   # 6
+                after()
+                ctx.refit_tlas(all_t12(m3))                    # 7: copy 5's tail still holds the committed topology
+                after()
+                third = _small_frame(ctx, True)                # 8
+            first, second = (s.cpu().numpy().reshape(48, 64, 4) for s in snaps)
+            assert ctx._lib.jpt_scene_update_tlas(ctx.h) == -4 and ctx.last_error() == STALE_HOST_COPY   # 9
+            ctx.build_scene(at8, capi.BUILD_SAH_WATERTIGHT)    # 10
+            after()
+            ctx.refit_tlas(all_t12(m4))                        # 11
+            after()
+            return first, second, third, _small_frame(ctx, False)   # 12
+        finally:
+            ctx.close()
+
+    def fresh(scene, asynchronous):
+        ctx = _small_ctx(scene)
+        try:
+            return _small_frame(ctx, asynchronous)
+        finally:
+            ctx.close()
+
+    queued, synced = run(False), run(True)
+    for k in (0, 1):
+        assert np.array_equal(queued[k].view(np.uint32), synced[k].view(np.uint32)), "image %d" % (k + 1)
+    _assert_frames_equal(queued[2], synced[2], "image 3, queued against synced")
+    _assert_frames_equal(queued[3], synced[3], "image 4, queued against synced")
+    _assert_frames_equal(queued[2], fresh(at8, True), "image 3 against a fresh commit")
+    _assert_frames_equal(queued[3], fresh(at12, False), "image 4 against a fresh commit")
 
 
 def test_queries_and_guides_follow_a_rebuild(hiplib):
