@@ -89,6 +89,7 @@ SYMBOLS = [
     "jpt_debug_skin",
     "jpt_encode", "jpt_get_encoded_info", "jpt_read_encoded", "jpt_readback_encoded_begin", "jpt_readback_encoded_end", "jpt_device_encoded",
     "jpt_get_encode_timing", "jpt_debug_encode",
+    "jpt_scene_rebuild_mesh", "jpt_scene_pose_mesh_rebuild", "jpt_multi_rebuild_mesh", "jpt_multi_pose_mesh_rebuild", "jpt_debug_mesh_order",
     "jpt_sky_defaults", "jpt_set_sky", "jpt_read_environment_f32", "jpt_multi_set_sky", "jpt_debug_sky", "jpt_debug_sky_radiance", "jpt_debug_pow01",
 ]
 
@@ -540,6 +541,12 @@ def lib():
         L.jpt_scene_clear_mesh_rig.argtypes = [vp, u32]
         L.jpt_multi_clear_mesh_rig.argtypes = [vp, u32]
         L.jpt_debug_skin.argtypes = [C.c_int, vp, vp, u32, vp, vp, i32, vp, vp, i32, vp, u32, vp, vp, vp]
+    if hasattr(L, "jpt_scene_rebuild_mesh") or "JPT_LIB" not in os.environ:
+        for n in ("jpt_scene_rebuild_mesh", "jpt_multi_rebuild_mesh"):
+            getattr(L, n).argtypes = [vp, u32, C.POINTER(Surface), i32]
+        for n in ("jpt_scene_pose_mesh_rebuild", "jpt_multi_pose_mesh_rebuild"):
+            getattr(L, n).argtypes = [vp, u32, vp, u32, vp, u32]
+        L.jpt_debug_mesh_order.argtypes = [C.c_int, vp, u32, vp, u32, vp, vp]
     if hasattr(L, "jpt_encode") or "JPT_LIB" not in os.environ:
         L.jpt_encode.argtypes = [vp, i32, i32, i32]
         L.jpt_get_encoded_info.argtypes = [vp, C.POINTER(EncodedInfo)]

@@ -1944,6 +1944,13 @@ uint32_t stack_need4_under(const std::vector<WideNode4>& nodes, int32_t root)
     return need4(nodes, root, memo);
 }
 
+void stack_need4_each(const std::vector<WideNode4>& nodes, const std::vector<int32_t>& roots, std::vector<uint32_t>& out)
+{
+    std::vector<int32_t> memo(nodes.size(), -1);
+    out.resize(roots.size());
+    for (size_t i = 0; i < roots.size(); i++) out[i] = need4(nodes, roots[i], memo);
+}
+
 void compute_stack_need(WideScene& out)
 {
     {

@@ -180,6 +180,8 @@ void refit4_schedule(const std::vector<WideNode4>& nodes, int32_t root, std::vec
 // The pending entries a near-first walk of the four-child records under `root` can need (compute_stack_need's figure for one tree:
 // WideScene::stack_need4 is this for the TLAS, + 1, + the largest of the instances' BLASes)
 uint32_t stack_need4_under(const std::vector<WideNode4>& nodes, int32_t root);
+// ... under each of `roots`, in one pass over the records
+void stack_need4_each(const std::vector<WideNode4>& nodes, const std::vector<int32_t>& roots, std::vector<uint32_t>& out);
 
 // Reference layout -> flattened layout.  Keeps topology, boxes and child order, so traversal visits the
 // same nodes in the same order as main.glsl:270-350 does on the reference arrays.

@@ -375,7 +375,22 @@ struct SceneUpdates {
         uint32_t tri_first = 0, n_tris = 0;
         uint32_t rec_first = 0, n_recs = 0;  // the span of dev.nodes4 its records occupy
         uint32_t level_first = 0, n_levels = 0;   // its level starts: mesh_levels_h[level_first .. level_first + n_levels]
+        bool rebuilt = false;               // jpt_scene_rebuild_mesh gave it a region: root4 / rec_first / n_recs name the region, the levels are mesh_regions[mesh]'s (level_first 0)
     };
+    // A new topology made on the device (jpt_scene_rebuild_mesh).  Per rebuilt mesh a region of dev.nodes4 / nodesq BEHIND the TLAS tails
+    // (the template of its triangle count needs more records than the commit's tree has), reserved at the mesh's first rebuild and kept
+    // until the next whole upload, with the template's child words, its schedule (absolute record indices) and level starts; the old range
+    // is no longer referenced.  mesh_need: the stack need of every mesh's tree
+    // as it is now (made at the first rebuild: c->wide.stack_need4 is the TLAS need + 1 + the largest of them).  d_mesh_sort: the sort's
+    // working set, of the largest mesh rebuilt so far (jpt_mesh_rebuild.h: mesh_sort_words).
+    struct MeshRegion {
+        DevBuf<int32_t> d_child;
+        DevBuf<uint32_t> d_order, d_levels;
+        std::vector<uint32_t> levels_h;
+    };
+    std::map<uint32_t, MeshRegion> mesh_regions;
+    std::vector<uint32_t> mesh_need;
+    DevBuf<uint32_t> d_mesh_sort;
     std::vector<MeshRefit> mesh_refit;
     bool mesh_refit_ready = false;
     std::vector<uint32_t> mesh_order_h, mesh_levels_h;
@@ -405,6 +420,7 @@ struct SceneUpdates {
         for (uint32_t& g : set_topo_gen) g = 0;
         refit_active = false;
         if (whole) mesh_deformed = mesh_refit_ready = false;
+        if (whole) mesh_need.clear();   // (upload_nodes4 makes the record arrays anew: the regions behind the tails are gone; drop_mesh_rigs freed their schedules)
         if (!w.instances4.empty() || !w.blas_nodes4.empty()) cull_boxes_current = true;
     }
     // the first record of copy k's TLAS tail in dev.nodes4 (upload_nodes4: the BLAS records, then one tail per copy)
@@ -420,7 +436,7 @@ struct SceneUpdates {
 };
 // the view the kernels take (c->ds) of the scene's device arrays, with the instance level of the copy new renders read (jpt_capi.cpp)
 void set_scene_view(jpt_ctx* c);
-// the rigs of jpt_scene_set_mesh_rig leave with the scene they were set for, behind the refit stream (jpt_scene_update.cpp)
+// the rigs of jpt_scene_set_mesh_rig, and the regions of jpt_scene_rebuild_mesh, leave with the scene they were set for, behind the refit stream (jpt_scene_update.cpp)
 void drop_mesh_rigs(jpt_ctx* c);
 // The refusals these calls open with: no context (JPT_E_INVALID), no scene from jpt_scene_commit ("<call><what>"); for the two trees a
 // JPT_BUILD_REFERENCE_EXACT commit (`exact`: the call's sentence, null: "<call><what>" again); for kWatertightTree a JPT_BUILD_SAH commit (`sah`,

@@ -23,6 +23,7 @@
 #include "jpt_instance_math.h"
 #include "jpt_kernels.h"
 #include "jpt_lightmap.h"
+#include "jpt_mesh_rebuild.h"
 #include "jpt_nodeq.h"
 #include "jpt_primary_ray.h"
 #include "jpt_tlas_rebuild.h"
@@ -1140,6 +1141,61 @@ int jpt_debug_tlas_order(int device_id, const float* lo3, const float* hi3, uint
     }
     if (rc == JPT_OK && keys_out && (e = hipMemcpy(keys_out, d_keys, b_keys, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     if (rc == JPT_OK && (e = hipMemcpy(sorted_instances_out, d_sorted, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d_all);
+    return rc;
+}
+
+int jpt_debug_mesh_order(int device_id, const float* vertices3, uint32_t n_vertices, const uint32_t* indices, uint32_t n_tris, uint32_t* codes_out,
+                         uint32_t* sorted_tris_out)
+{
+    if (n_tris == 0) return JPT_OK;
+    if (!vertices3 || !indices || !sorted_tris_out) {
+        g_debug_error = "jpt_debug_mesh_order: null argument";
+        return JPT_E_INVALID;
+    }
+    if (n_tris > kMeshRebuildMaxTris) {
+        g_debug_error = "jpt_debug_mesh_order: more than 2^25 triangles";
+        return JPT_E_LIMIT;
+    }
+    for (size_t k = 0; k < (size_t)n_tris * 3; k++)
+        if (indices[k] >= n_vertices) {
+            g_debug_error = "jpt_debug_mesh_order: a triangle names a vertex beyond n_vertices";
+            return JPT_E_INVALID;
+        }
+    if (device_id < 0) {
+        mesh_order_host(vertices3, indices, n_tris, codes_out, sorted_tris_out);
+        return JPT_OK;
+    }
+    auto hip_fail = [](hipError_t e, const char* what) {
+        g_debug_error = std::string(what) + ": " + hipGetErrorString(e);
+        return JPT_E_DEVICE;
+    };
+    hipError_t e;
+    if ((e = hipSetDevice(device_id)) != hipSuccess) return hip_fail(e, "hipSetDevice");
+    // the vertices, the indices, the sort's working set
+    const size_t b_verts = (size_t)n_vertices * 12, b_idx = (size_t)n_tris * 12, b_work = mesh_sort_words(n_tris) * 4;
+    char* d_all = nullptr;
+    if ((e = hipMalloc((void**)&d_all, b_verts + b_idx + b_work)) != hipSuccess) return hip_fail(e, "hipMalloc");
+    MeshOrderArgs a;
+    a.verts = reinterpret_cast<const float*>(d_all);
+    a.vidx = reinterpret_cast<const uint32_t*>(d_all + b_verts);
+    a.n_tris = n_tris;
+    a.work = reinterpret_cast<uint32_t*>(d_all + b_verts + b_idx);
+    int rc = JPT_OK;
+    if ((e = hipMemcpy(d_all, vertices3, b_verts, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(d_all + b_verts, indices, b_idx, hipMemcpyHostToDevice)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        launch_mesh_order_codes(nullptr, a);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "mesh_codes_kernel");
+    }
+    if (rc == JPT_OK && codes_out && (e = hipMemcpy(codes_out, mesh_order_codes(a), (size_t)n_tris * 4, hipMemcpyDeviceToHost)) != hipSuccess)
+        rc = hip_fail(e, "hipMemcpy");
+    if (rc == JPT_OK) {
+        launch_mesh_order_sort(nullptr, a);
+        if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess) rc = hip_fail(e, "mesh_sort_scatter_kernel");
+    }
+    if (rc == JPT_OK && (e = hipMemcpy(sorted_tris_out, mesh_order_sorted(a), (size_t)n_tris * 4, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d_all);
     return rc;
 }

@@ -456,6 +456,34 @@ struct MeshRefitArgs {
     uint32_t n_instances = 0;
 };
 void launch_mesh_refit(hipStream_t stream, const MeshRefitArgs& args, const uint32_t* h_level_start, uint32_t n_levels);
+// its two halves, for a caller that puts a new topology between them (jpt_scene_rebuild_mesh): the triangle records and the mesh's
+// bounds; the records level by level, then the root box
+void launch_mesh_tris(hipStream_t stream, const MeshRefitArgs& args);
+void launch_mesh_records(hipStream_t stream, const MeshRefitArgs& args, const uint32_t* h_level_start, uint32_t n_levels);
+
+// A new topology for a committed mesh (jpt_scene_rebuild_mesh, jpt_kernels_mesh_rebuild.hip; the arithmetic: jpt_mesh_rebuild.h): the
+// mesh's triangles in ascending (Morton code of the vertex box's centre, triangle) order.  `work`: mesh_sort_words(n_tris) words of
+// device memory, written and read by these launches only.  launch_mesh_order_codes: the bounds of the centres, then at mesh_order_codes
+// the code of every triangle and at mesh_order_sorted tri_first + its index in the mesh, both in triangle order (jpt_debug_mesh_order
+// copies the codes out here); launch_mesh_order_sort: both arrays sorted in place (through the second pair of buffers and back), so
+// mesh_order_sorted holds the triangle at every sorted position; launch_mesh_order: all of it.
+struct MeshOrderArgs {
+    const float* verts = nullptr;      // as MeshRefitArgs
+    const uint32_t* vidx = nullptr;
+    uint32_t tri_first = 0, n_tris = 0;
+    uint32_t* work = nullptr;
+};
+inline uint32_t* mesh_order_codes(const MeshOrderArgs& a) { return a.work + 8; }
+inline uint32_t* mesh_order_sorted(const MeshOrderArgs& a) { return a.work + 8 + a.n_tris; }
+void launch_mesh_order_codes(hipStream_t stream, const MeshOrderArgs& args);
+void launch_mesh_order_sort(hipStream_t stream, const MeshOrderArgs& args);
+inline void launch_mesh_order(hipStream_t stream, const MeshOrderArgs& args)
+{
+    launch_mesh_order_codes(stream, args);
+    launch_mesh_order_sort(stream, args);
+}
+// the root word of every instance of the mesh at `bvh_root` in one copy of the instance level (instance_refit_kernel never writes it)
+void launch_mesh_root_words(hipStream_t stream, WideInstance* winst4, const RefInstance* instances, uint32_t n_instances, uint32_t bvh_root, int32_t root);
 
 // Posing a committed mesh on the device (jpt_scene_pose_mesh, jpt_kernels_skin.hip; the arithmetic: jpt_skin.h): one thread per vertex
 // of the mesh writes packed float3 positions -- and normals, when the rig has them -- where the mesh refit reads them

@@ -162,8 +162,19 @@ __global__ __launch_bounds__(256) void mesh_root_kernel(MeshRefitArgs a)
 
 void launch_mesh_refit(hipStream_t stream, const MeshRefitArgs& a, const uint32_t* h_level_start, uint32_t n_levels)
 {
+    launch_mesh_tris(stream, a);
+    launch_mesh_records(stream, a, h_level_start, n_levels);
+}
+
+void launch_mesh_tris(hipStream_t stream, const MeshRefitArgs& a)
+{
     if (a.n_tris == 0) return;
     hipLaunchKernelGGL(mesh_tri_kernel, dim3((a.n_tris + 255u) / 256u), dim3(256), 0, stream, a);
+}
+
+void launch_mesh_records(hipStream_t stream, const MeshRefitArgs& a, const uint32_t* h_level_start, uint32_t n_levels)
+{
+    if (a.n_tris == 0) return;
     // a grid per level up to the last level that holds more records than one block has threads, then one block for the levels
     // above it (a small mesh: one launch)
     uint32_t split = n_levels;

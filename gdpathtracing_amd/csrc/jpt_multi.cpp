@@ -263,6 +263,28 @@ int jpt_multi_pose_mesh(jpt_multi* m, uint32_t mesh_id, const float* bone_transf
     return JPT_OK;
 }
 
+int jpt_multi_rebuild_mesh(jpt_multi* m, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        (void)hipSetDevice(m->devices[r]);
+        const int rc = jpt_scene_rebuild_mesh(m->ctx[r], mesh_id, surfaces, n_surfaces);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
+int jpt_multi_pose_mesh_rebuild(jpt_multi* m, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
+{
+    if (!m) return JPT_E_INVALID;
+    for (size_t r = 0; r < m->ctx.size(); r++) {
+        (void)hipSetDevice(m->devices[r]);
+        const int rc = jpt_scene_pose_mesh_rebuild(m->ctx[r], mesh_id, bone_transforms12, n_bones, blend_weights, n_blend_weights);
+        if (rc != JPT_OK) return mfail_ctx(m, (int)r, rc);
+    }
+    return JPT_OK;
+}
+
 int jpt_multi_clear_mesh_rig(jpt_multi* m, uint32_t mesh_id)
 {
     if (!m) return JPT_E_INVALID;

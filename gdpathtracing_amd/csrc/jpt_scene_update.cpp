@@ -1,5 +1,5 @@
 // jpt_scene_update.cpp -- the calls that change a committed scene on the device without a new commit (jpt_scene_refit_tlas, jpt_scene_rebuild_tlas,
-// jpt_scene_update_mesh, jpt_scene_set_mesh_rig, jpt_scene_clear_mesh_rig, jpt_scene_pose_mesh) and the two that read their results (jpt_debug_mesh_records,
+// jpt_scene_update_mesh, jpt_scene_rebuild_mesh, jpt_scene_set_mesh_rig, jpt_scene_clear_mesh_rig, jpt_scene_pose_mesh, jpt_scene_pose_mesh_rebuild) and the two that read their results (jpt_debug_mesh_records,
 // jpt_debug_tlas_records), over SceneUpdates (jpt_ctx.h).  The host route (jpt_scene_update_tlas) is jpt_capi.cpp's, with the uploads it is made of.
 #include "jpt_ctx.h"
 
@@ -9,6 +9,7 @@
 
 #include "jpt_instance_math.h"
 #include "jpt_mesh_math.h"
+#include "jpt_mesh_rebuild.h"
 
 int jpt::needs_scene(jpt_ctx* c, SceneNeed need, const char* call, const char* what, const char* exact, const char* sah)
 {
@@ -68,20 +69,13 @@ int ensure_tlas_template(jpt_ctx* c, uint32_t n)
     return JPT_OK;
 }
 
-// Instance records and TLAS boxes from the transforms at `dev_view` (n_instances x 12 floats the device can read), written into the
-// copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
-// from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
-// `rebuild_sorted` (jpt_scene_rebuild_tlas; ensure_tlas_template has run): the copy also gets a new topology, the template's over the
-// instances sorted on the device, and the host's mirror of the records (c->wide, the schedule) becomes the template over
-// rebuild_sorted, boxes not yet refitted.  Every later refit then runs over the template's schedule, and one into a copy whose tail
-// still holds an older topology first copies the current copy's tail.
-int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances, const uint32_t* rebuild_sorted = nullptr)
+// The other copies of the instance level, made at the first refit (or mesh rebuild) since the last host upload
+int ensure_instance_copies(jpt_ctx* c)
 {
-    lights_stale(c, false);
     hipStream_t s = c->stream;
     SceneBufs& b = c->dev;
     if (!c->upd.set_b_ready) {
-        // first refit since the last host upload: the other copies of the instance arrays start as copies of copy 0
+        // the other copies of the instance arrays start as copies of copy 0
         // (the TLAS tails were all uploaded).  Once per upload, so the drain does not matter.
         HIP_TRY(c, hipStreamSynchronize(s));
         const SceneBufs::InstanceSet& first = b.set[0];
@@ -99,6 +93,22 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
         c->upd.set_b_ready = true;
         for (bool& v : c->upd.set_retired_valid) v = false;
     }
+    return JPT_OK;
+}
+
+// Instance records and TLAS boxes from the transforms at `dev_view` (n_instances x 12 floats the device can read), written into the
+// copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
+// from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
+// `rebuild_sorted` (jpt_scene_rebuild_tlas; ensure_tlas_template has run): the copy also gets a new topology, the template's over the
+// instances sorted on the device, and the host's mirror of the records (c->wide, the schedule) becomes the template over
+// rebuild_sorted, boxes not yet refitted.  Every later refit then runs over the template's schedule, and one into a copy whose tail
+// still holds an older topology first copies the current copy's tail.
+int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances, const uint32_t* rebuild_sorted = nullptr)
+{
+    lights_stale(c, false);
+    if (const int rc = ensure_instance_copies(c); rc != JPT_OK) return rc;
+    hipStream_t s = c->stream;
+    SceneBufs& b = c->dev;
     // The refit writes the copy that new renders do not read yet (`next`); its last readers are the renders queued
     // before the refit that retired it, i.e. before ev_set_retired[next] was recorded on the context's stream (which
     // waits for every render).  The renders queued since read the current copy and keep running meanwhile.
@@ -298,6 +308,95 @@ int ensure_mesh_refit(jpt_ctx* c)
     return JPT_OK;
 }
 
+// The region of jpt_scene_rebuild_mesh for mesh `mesh_id` (ensure_mesh_refit has run; the mesh has a tree of two triangles or more).  At
+// the mesh's first rebuild since the last upload: the template of its triangle count (make_tlas_template) with its schedule and
+// stack need; JPT_E_LIMIT, before anything is written or reserved, when a traversal could then need more entries than the kernels
+// hold; then -- the host waits for the queued renders and refits, once per mesh -- the record arrays grown by the template's records
+// BEHIND the TLAS tails (every existing offset stays), the root word of the mesh's instances pointed at the region's record 0 in every
+// copy of the instance level and in c->wide.instances4, the template's child words, schedule and level starts uploaded, the sort's
+// working set sized, and mesh_refit[mesh_id] naming the region.  Later calls find all of it in place.
+int ensure_mesh_region(jpt_ctx* c, uint32_t mesh_id, const char* call)
+{
+    SceneUpdates& u = c->upd;
+    SceneUpdates::MeshRefit& mr = u.mesh_refit[mesh_id];
+    if (mr.rebuilt) return u.mesh_regions.count(mesh_id) ? JPT_OK : fail(c, JPT_E_STATE, std::string(call) + ": the mesh's region left with its scene");
+    WideScene& w = c->wide;
+    if (u.mesh_need.empty()) {
+        std::vector<int32_t> roots(u.mesh_refit.size(), -1);   // (a leaf root, and a mesh without a tree: need 0)
+        for (size_t m = 0; m < roots.size(); m++)
+            if (u.mesh_refit[m].has_tree) roots[m] = u.mesh_refit[m].root4;
+        stack_need4_each(w.blas_nodes4, roots, u.mesh_need);
+    }
+    TlasTemplate t;
+    make_tlas_template(mr.n_tris, t);
+    std::vector<uint32_t> order, levels(1, 0u);
+    uint32_t need_own = 0;
+    {
+        std::vector<uint32_t> identity(mr.n_tris);
+        for (uint32_t i = 0; i < mr.n_tris; i++) identity[i] = i;
+        std::vector<WideNode4> records;
+        tlas_template_records(t, identity.data(), records);
+        refit4_schedule(records, 0, order, levels);
+        need_own = stack_need4_under(records, 0);
+    }
+    uint32_t blas_old = 0, blas_new = need_own;
+    for (size_t m = 0; m < u.mesh_need.size(); m++) {
+        blas_old = std::max(blas_old, u.mesh_need[m]);
+        if (m != mesh_id) blas_new = std::max(blas_new, u.mesh_need[m]);
+    }
+    const uint32_t need = w.stack_need4 - blas_old + blas_new;   // (stack_need4: the TLAS need + 1 + the largest mesh need)
+    if (need > trace_stack_capacity())
+        return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the mesh rebuild: a traversal could need " + std::to_string(need) +
+                                        " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
+    SceneBufs& b = c->dev;
+    const size_t first = b.nodes4.n, total = first + t.n_records;
+    if (b.nodesq.n != first || total > (size_t)0x7fffffff) return fail(c, JPT_E_LIMIT, std::string(call) + ": more records than a child word can name");
+    int rc = ensure_refit_stream(c);
+    if (rc != JPT_OK) return rc;
+    hipStream_t s = c->stream, rs = u.refit_stream;
+    // every render, read-back and refit queued so far holds the arrays' addresses (the context's stream follows them all)
+    HIP_TRY(c, hipStreamSynchronize(rs));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    {
+        DevBuf<WideNode4> n4;
+        DevBuf<WideNodeQ> nq;
+        HIP_TRY(c, n4.resize(total));
+        HIP_TRY(c, nq.resize(total));
+        HIP_TRY(c, hipMemcpyAsync(n4.p, b.nodes4.p, first * sizeof(WideNode4), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipMemcpyAsync(nq.p, b.nodesq.p, first * sizeof(WideNodeQ), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(c, hipStreamSynchronize(s));
+        std::swap(n4.p, b.nodes4.p);
+        std::swap(n4.n, b.nodes4.n);
+        std::swap(nq.p, b.nodesq.p);
+        std::swap(nq.n, b.nodesq.n);
+    }
+    rc = ensure_instance_copies(c);
+    if (rc != JPT_OK) return rc;
+    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    for (int k = 0; k < kInstanceSets; k++) launch_mesh_root_words(s, b.set[k].winst4.p, b.set[0].inst.p, n_inst, mr.bvh_root, (int32_t)first);
+    HIP_TRY(c, hipGetLastError());
+    for (uint32_t i = 0; i < n_inst; i++)
+        if (c->ref.instances[i].blas_index == mr.bvh_root) w.instances4[i].root = (int32_t)first;
+    for (uint32_t& r : order) r += (uint32_t)first;
+    SceneUpdates::MeshRegion& rg = u.mesh_regions[mesh_id];
+    HIP_TRY(c, rg.d_child.upload(t.child, s));
+    HIP_TRY(c, rg.d_order.upload(order, s));
+    HIP_TRY(c, rg.d_levels.upload(levels, s));
+    if (u.d_mesh_sort.n < mesh_sort_words(mr.n_tris)) HIP_TRY(c, u.d_mesh_sort.resize(mesh_sort_words(mr.n_tris)));
+    HIP_TRY(c, hipStreamSynchronize(s));   // pageable host vectors
+    rg.levels_h = levels;
+    mr.root4 = (int32_t)first;
+    mr.rec_first = (uint32_t)first;
+    mr.n_recs = t.n_records;
+    mr.level_first = 0;
+    mr.n_levels = (uint32_t)levels.size() - 1u;
+    mr.rebuilt = true;
+    u.mesh_need[mesh_id] = need_own;
+    w.stack_need4 = need;
+    set_scene_view(c);
+    return JPT_OK;
+}
+
 // The state and argument checks of a call that gives new arrays for a committed mesh (`call`: jpt_scene_update_mesh,
 // jpt_scene_set_mesh_rig): a JPT_BUILD_SAH_WATERTIGHT commit, the mesh's own topology, normals for every surface or for none
 // (with_normals: whether they came).  sv: the surfaces as the builder views them.
@@ -368,9 +467,18 @@ hipError_t drain_pipeline(jpt_ctx* c)
 // into d_mesh_in behind its bounds head, on the refit stream and behind the pipeline drain: the mesh's records refitted from them,
 // then the instance level over the new root boxes with the current transforms (`dev_transforms`: the stage's copy, as the device sees
 // it), as jpt_scene_refit_tlas does; the stage `st` of mesh_stage is free again once all of it has run.
-int queue_mesh_refit(jpt_ctx* c, const SceneUpdates::MeshRefit& mr, const float* verts, const float* normals, const float* dev_transforms,
+// `rebuild` (ensure_mesh_region has run for `mesh_id`): between the triangle records and the refit the region's records get a new
+// topology, the template's over the mesh's triangles sorted on the device (jpt_kernels_mesh_rebuild.hip).
+int queue_mesh_refit(jpt_ctx* c, uint32_t mesh_id, bool rebuild, const float* verts, const float* normals, const float* dev_transforms,
                      const MeshStage& st, std::chrono::steady_clock::time_point t0)
 {
+    const SceneUpdates::MeshRefit& mr = c->upd.mesh_refit[mesh_id];
+    const SceneUpdates::MeshRegion* rg = nullptr;
+    if (mr.rebuilt) {
+        const auto it = c->upd.mesh_regions.find(mesh_id);
+        if (it == c->upd.mesh_regions.end()) return fail(c, JPT_E_STATE, "the mesh's region left with its scene");
+        rg = &it->second;
+    }
     const uint32_t n_inst = (uint32_t)c->ref.instances.size();
     MeshRefitArgs a;
     a.bounds = reinterpret_cast<int32_t*>(c->upd.d_mesh_in.p);
@@ -384,8 +492,8 @@ int queue_mesh_refit(jpt_ctx* c, const SceneUpdates::MeshRefit& mr, const float*
     a.shade = b.shade_tris.p;
     a.nodes4 = b.nodes4.p;
     a.nodesq = b.nodesq.p;
-    a.order = c->upd.d_mesh_order.p;
-    a.level_start = c->upd.d_mesh_levels.p + mr.level_first;
+    a.order = rg ? rg->d_order.p : c->upd.d_mesh_order.p;
+    a.level_start = rg ? rg->d_levels.p : c->upd.d_mesh_levels.p + mr.level_first;
     a.root4 = mr.root4;
     a.bvh = b.bvh.p;
     a.bvh_root = mr.bvh_root;
@@ -393,7 +501,22 @@ int queue_mesh_refit(jpt_ctx* c, const SceneUpdates::MeshRefit& mr, const float*
     a.cut_range = cuts ? b.cut_range.p : nullptr;
     a.instances = b.set[0].inst.p;   // (blas_index is the same in every copy of the instance level)
     a.n_instances = n_inst;
-    launch_mesh_refit(c->upd.refit_stream, a, c->upd.mesh_levels_h.data() + mr.level_first, mr.n_levels);
+    const uint32_t* h_levels = rg ? rg->levels_h.data() : c->upd.mesh_levels_h.data() + mr.level_first;
+    if (rebuild && rg) {
+        hipStream_t rs = c->upd.refit_stream;
+        launch_mesh_tris(rs, a);
+        MeshOrderArgs o;
+        o.verts = verts;
+        o.vidx = a.vidx;
+        o.tri_first = mr.tri_first;
+        o.n_tris = mr.n_tris;
+        o.work = c->upd.d_mesh_sort.p;
+        launch_mesh_order(rs, o);
+        launch_tlas_template(rs, rg->d_child.p, mr.n_recs, mesh_order_sorted(o), a.nodes4, mr.rec_first);
+        launch_mesh_records(rs, a, h_levels, mr.n_levels);
+    } else {
+        launch_mesh_refit(c->upd.refit_stream, a, h_levels, mr.n_levels);
+    }
     HIP_TRY(c, hipGetLastError());
     // the instance level over the new root boxes, with the current transforms, as jpt_scene_refit_tlas does
     const int rc = queue_instance_refit(c, dev_transforms, n_inst);
@@ -409,29 +532,37 @@ int queue_mesh_refit(jpt_ctx* c, const SceneUpdates::MeshRefit& mr, const float*
 // The rigs of jpt_scene_set_mesh_rig leave with the scene they were set for (a queued pose may still read them: the refit stream first)
 void jpt::drop_mesh_rigs(jpt_ctx* c)
 {
-    if (c->upd.mesh_rigs.empty()) return;
+    if (c->upd.mesh_rigs.empty() && c->upd.mesh_regions.empty()) return;
     if (c->device >= 0 && c->upd.refit_stream) {
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->upd.refit_stream);
     }
     c->upd.mesh_rigs.clear();
+    c->upd.mesh_regions.clear();   // (the regions' records go with the record arrays, at the upload that follows: host_uploaded)
 }
 
 int jpt_scene_refit_tlas(jpt_ctx* c, const float* t12, uint32_t n) { return move_instances(c, t12, n, false, "jpt_scene_refit_tlas"); }
 int jpt_scene_rebuild_tlas(jpt_ctx* c, const float* t12, uint32_t n) { return move_instances(c, t12, n, true, "jpt_scene_rebuild_tlas"); }
 
-int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+namespace {
+
+// jpt_scene_update_mesh and jpt_scene_rebuild_mesh (`rebuild`; `call`: the name for the messages): the same checks, staging and side effects;
+// the rebuild also gives the mesh's records a new topology (a mesh of fewer than two triangles is its own order: the refit)
+int deform_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces, bool rebuild, const char* call)
 {
     std::vector<SurfaceView> sv;
     int with_normals = 0;
-    int rc = check_mesh_arrays(c, "jpt_scene_update_mesh", mesh_id, surfaces, n_surfaces, sv, with_normals);
+    int rc = check_mesh_arrays(c, call, mesh_id, surfaces, n_surfaces, sv, with_normals);
     if (rc == JPT_OK) rc = on_device(c, "host-only context: the update runs on the device", true);
     if (rc != JPT_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     rc = ensure_mesh_refit(c);
     if (rc != JPT_OK) return rc;
-    c->upd.mesh_deformed = true;   // (the host's arrays describe the committed vertices from here on)
     const SceneUpdates::MeshRefit& mr = c->upd.mesh_refit[mesh_id];
+    rebuild = rebuild && mr.has_tree && mr.n_tris >= 2;
+    if (rebuild) rc = ensure_mesh_region(c, mesh_id, call);
+    if (rc != JPT_OK) return rc;
+    c->upd.mesh_deformed = true;   // (the host's arrays describe the committed vertices from here on)
     if (!mr.has_tree) return JPT_OK;   // no instance names the mesh: the device holds nothing of it
     // staging: [6 ordered keys + pad: 32 B][vertices][normals][transforms]; the first three parts are copied to the device, the
     // instance refit reads the transforms from the pinned buffer
@@ -451,8 +582,19 @@ int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfa
     HIP_TRY(c, drain_pipeline(c));
     const char* in = c->upd.d_mesh_in.p;
     HIP_TRY(c, hipMemcpyAsync(c->upd.d_mesh_in.p, st.h, dev_bytes, hipMemcpyHostToDevice, c->upd.refit_stream));
-    return queue_mesh_refit(c, mr, reinterpret_cast<const float*>(in + head), with_normals ? reinterpret_cast<const float*>(in + head + vbytes) : nullptr,
+    return queue_mesh_refit(c, mesh_id, rebuild, reinterpret_cast<const float*>(in + head), with_normals ? reinterpret_cast<const float*>(in + head + vbytes) : nullptr,
                             reinterpret_cast<const float*>(st.dev + dev_bytes), st, t0);
+}
+
+}  // namespace
+
+int jpt_scene_update_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+{
+    return deform_mesh(c, mesh_id, surfaces, n_surfaces, false, "jpt_scene_update_mesh");
+}
+int jpt_scene_rebuild_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32_t n_surfaces)
+{
+    return deform_mesh(c, mesh_id, surfaces, n_surfaces, true, "jpt_scene_rebuild_mesh");
 }
 
 int jpt_scene_set_mesh_rig(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* bind, const jpt_surface_rig* rigs, int32_t n_surfaces, int32_t influences,
@@ -510,17 +652,21 @@ int jpt_scene_clear_mesh_rig(jpt_ctx* c, uint32_t mesh_id)
     return JPT_OK;
 }
 
-int jpt_scene_pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
+namespace {
+
+// jpt_scene_pose_mesh and jpt_scene_pose_mesh_rebuild (`rebuild`; `call`: the name for the messages), as deform_mesh
+int pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights,
+              bool rebuild, const char* call)
 {
     // jpt_scene_update_mesh's state rules, on their own account: a rig is dropped with its scene, but a pose does not rely on that
-    if (const int rc = needs_scene(c, kWatertightTree, "jpt_scene_pose_mesh", " needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT"); rc != JPT_OK) return rc;
+    if (const int rc = needs_scene(c, kWatertightTree, call, " needs a scene made by jpt_scene_commit with JPT_BUILD_SAH_WATERTIGHT"); rc != JPT_OK) return rc;
     auto it = c->upd.mesh_rigs.find(mesh_id);
-    if (it == c->upd.mesh_rigs.end()) return fail(c, JPT_E_STATE, "jpt_scene_pose_mesh: the mesh has no rig (jpt_scene_set_mesh_rig; a commit or an upload drops it)");
+    if (it == c->upd.mesh_rigs.end()) return fail(c, JPT_E_STATE, std::string(call) + ": the mesh has no rig (jpt_scene_set_mesh_rig; a commit or an upload drops it)");
     const SceneUpdates::MeshRig& rig = it->second;
     const SkinRigInfo& info = rig.info;
     std::vector<SkinShape> active;
     std::string why;
-    int rc = check_skin_pose("jpt_scene_pose_mesh", info, bone_transforms12, n_bones, blend_weights, n_blend_weights, active, why);
+    int rc = check_skin_pose(call, info, bone_transforms12, n_bones, blend_weights, n_blend_weights, active, why);
     if (rc != JPT_OK) return fail(c, rc, why);
     rc = on_device(c, "host-only context: the pose runs on the device", true);
     if (rc != JPT_OK) return rc;
@@ -530,6 +676,9 @@ int jpt_scene_pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transfor
     const SceneUpdates::MeshRefit& mr = c->upd.mesh_refit[mesh_id];
     // no instance names the mesh: the device holds nothing of it, nothing changes anywhere and the host's copy of the scene stays current
     if (!mr.has_tree || !rig.d_rig.p) return JPT_OK;
+    rebuild = rebuild && mr.n_tris >= 2;
+    if (rebuild) rc = ensure_mesh_region(c, mesh_id, call);
+    if (rc != JPT_OK) return rc;
     c->upd.mesh_deformed = true;   // (as jpt_scene_update_mesh: the host's arrays describe the committed vertices from here on)
     // staging: [6 ordered keys + pad: 32 B][palette: the bones the rig can name][active shapes, padded to 16 B][transforms]; the first
     // three parts are copied to the head of d_mesh_in, where the vertices and normals the skin kernel writes follow them
@@ -561,7 +710,18 @@ int jpt_scene_pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transfor
     // The BLAS records, triangle records and root boxes are shared by every copy of the instance level: one pipeline drain on the
     // device, as jpt_scene_update_mesh
     HIP_TRY(c, drain_pipeline(c));
-    return queue_mesh_refit(c, mr, a.verts_out, a.normals_out, reinterpret_cast<const float*>(st.dev + in_bytes), st, t0);
+    return queue_mesh_refit(c, mesh_id, rebuild, a.verts_out, a.normals_out, reinterpret_cast<const float*>(st.dev + in_bytes), st, t0);
+}
+
+}  // namespace
+
+int jpt_scene_pose_mesh(jpt_ctx* c, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
+{
+    return pose_mesh(c, mesh_id, bone_transforms12, n_bones, blend_weights, n_blend_weights, false, "jpt_scene_pose_mesh");
+}
+int jpt_scene_pose_mesh_rebuild(jpt_ctx* c, uint32_t mesh_id, const float* bone_transforms12, uint32_t n_bones, const float* blend_weights, uint32_t n_blend_weights)
+{
+    return pose_mesh(c, mesh_id, bone_transforms12, n_bones, blend_weights, n_blend_weights, true, "jpt_scene_pose_mesh_rebuild");
 }
 
 int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void* nodesq_out, uint32_t node_capacity, void* tris_out,

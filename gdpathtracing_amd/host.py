@@ -99,6 +99,19 @@ def debug_tlas_order(device_id, lo, hi, with_keys=True):
     return keys, order
 
 
+def debug_mesh_order(device_id, vertices, indices, with_codes=True):
+    """jpt_debug_mesh_order: the order of jpt_scene_rebuild_mesh alone over a caller-made mesh (vertices float32 [v, 3], indices uint32
+    [t, 3]) -- (codes uint32 [t] per triangle, or None; the triangle at every sorted position, uint32 [t]).  device_id -1: the host's
+    copy of the functions."""
+    L = capi.lib()
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    ix = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+    codes = np.zeros(len(ix), np.uint32) if with_codes else None
+    order = np.zeros(len(ix), np.uint32)
+    _debug_check(L, L.jpt_debug_mesh_order(device_id, _ptr(v), len(v), _ptr(ix), len(ix), _ptr(codes), _ptr(order)), "jpt_debug_mesh_order")
+    return codes, order
+
+
 def debug_tlas_template(n):
     """jpt_debug_tlas_template: the tree jpt_scene_rebuild_tlas puts over n sorted positions -- dict with `child` (int32 [n_records, 4]:
     >= 0 a record, ~position a leaf, INT32_MIN empty), `n_levels` and `stack_need`."""
@@ -695,17 +708,28 @@ class Context:
         arr = _update_surfaces(mesh, with_normals)
         self._ck(self._lib.jpt_scene_update_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_scene_update_mesh")
 
+    def rebuild_mesh(self, mesh_id: int, mesh: scenes.Mesh, with_normals: bool = True):
+        """update_mesh with a new BLAS topology (jpt_scene_rebuild_mesh): the mesh's triangles are sorted along a Morton curve on the
+        device and a fixed four-way tree over that order, in a region of its own, replaces the mesh's records; later update_mesh /
+        pose_mesh calls refit over it.  The mesh's first rebuild may wait for the queued renders; no later one does."""
+        arr = _update_surfaces(mesh, with_normals)
+        self._ck(self._lib.jpt_scene_rebuild_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_scene_rebuild_mesh")
+
+    debug_mesh_order = staticmethod(debug_mesh_order)
+
     def set_mesh_rig(self, mesh_id: int, bind: scenes.Mesh, rigs, influences: int, n_blend_shapes: int, with_normals: bool = True):
         """The rig of a committed mesh, kept on the device (jpt_scene_set_mesh_rig): `bind` is the bind-pose mesh (same surfaces, vertex
         counts and index arrays as committed; with_normals False: the committed normals stay), `rigs` one SurfaceRig per surface."""
         arr, rarr = _update_surfaces(bind, with_normals), _rig_surfaces(rigs)
         self._ck(self._lib.jpt_scene_set_mesh_rig(self.h, mesh_id, arr, rarr, len(bind.surfaces), influences, n_blend_shapes), "jpt_scene_set_mesh_rig")
 
-    def pose_mesh(self, mesh_id: int, bone_transforms12=None, blend_weights=None):
+    def pose_mesh(self, mesh_id: int, bone_transforms12=None, blend_weights=None, rebuild: bool = False):
         """One pose of a rigged mesh (jpt_scene_pose_mesh): float32 [n_bones, 12] bone transforms (bone pose x inverse bind, transform12
-        layout) and one weight per blend shape; the vertices are computed and the mesh refitted on the device, no synchronisation."""
+        layout) and one weight per blend shape; the vertices are computed and the mesh refitted on the device, no synchronisation.
+        rebuild: with a new BLAS topology over the posed vertices (jpt_scene_pose_mesh_rebuild), as rebuild_mesh."""
         b, nb, w, nw = _pose_arrays(bone_transforms12, blend_weights)
-        self._ck(self._lib.jpt_scene_pose_mesh(self.h, mesh_id, _ptr(b), nb, _ptr(w), nw), "jpt_scene_pose_mesh")
+        name = "jpt_scene_pose_mesh_rebuild" if rebuild else "jpt_scene_pose_mesh"
+        self._ck(getattr(self._lib, name)(self.h, mesh_id, _ptr(b), nb, _ptr(w), nw), name)
 
     def clear_mesh_rig(self, mesh_id: int):
         self._ck(self._lib.jpt_scene_clear_mesh_rig(self.h, mesh_id), "jpt_scene_clear_mesh_rig")
@@ -1408,13 +1432,23 @@ class GeometryGroup3D:
             self.scene.meshes[mesh_index] = mesh
         self.ctx.update_mesh(mesh_index, mesh)
 
+    def rebuild_mesh(self, mesh_index: int, mesh: Optional[scenes.Mesh] = None):
+        """update_mesh with a new BLAS topology made on the device (jpt_scene_rebuild_mesh): for a mesh that deformed far from its
+        shape at build()"""
+        if mesh is None:
+            mesh = self.scene.meshes[mesh_index]
+        else:
+            self.scene.meshes[mesh_index] = mesh
+        self.ctx.rebuild_mesh(mesh_index, mesh)
+
     def set_mesh_rig(self, mesh_index: int, rigs, influences: int, n_blend_shapes: int, bind: Optional[scenes.Mesh] = None, with_normals: bool = True):
         """The rig of one of the group's meshes (Skeleton3D / Skin and blend shapes): `bind` (default: the scene's own mesh) is its bind pose"""
         self.ctx.set_mesh_rig(mesh_index, self.scene.meshes[mesh_index] if bind is None else bind, rigs, influences, n_blend_shapes, with_normals)
 
-    def pose_mesh(self, mesh_index: int, bone_transforms12=None, blend_weights=None):
-        """A rigged mesh posed on the device, without build() again; the scene's own mesh object keeps its bind pose"""
-        self.ctx.pose_mesh(mesh_index, bone_transforms12, blend_weights)
+    def pose_mesh(self, mesh_index: int, bone_transforms12=None, blend_weights=None, rebuild: bool = False):
+        """A rigged mesh posed on the device, without build() again; the scene's own mesh object keeps its bind pose.  rebuild: with a
+        new BLAS topology over the posed vertices"""
+        self.ctx.pose_mesh(mesh_index, bone_transforms12, blend_weights, rebuild)
 
     def clear_mesh_rig(self, mesh_index: int):
         self.ctx.clear_mesh_rig(mesh_index)
@@ -1591,17 +1625,24 @@ class MultiContext:
         arr = _update_surfaces(mesh, with_normals)
         self._ck(self._lib.jpt_multi_update_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_multi_update_mesh")
 
+    def rebuild_mesh(self, mesh_id: int, mesh: scenes.Mesh, with_normals: bool = True):
+        """update_mesh with a new BLAS topology (jpt_multi_rebuild_mesh: every rank's replica)"""
+        arr = _update_surfaces(mesh, with_normals)
+        self._ck(self._lib.jpt_multi_rebuild_mesh(self.h, mesh_id, arr, len(mesh.surfaces)), "jpt_multi_rebuild_mesh")
+
     def set_mesh_rig(self, mesh_id: int, bind: scenes.Mesh, rigs, influences: int, n_blend_shapes: int, with_normals: bool = True):
         """The rig of a committed mesh, kept on the device (jpt_multi_set_mesh_rig: every rank's replica): `bind` is the bind-pose mesh (same surfaces, vertex
         counts and index arrays as committed; with_normals False: the committed normals stay), `rigs` one SurfaceRig per surface."""
         arr, rarr = _update_surfaces(bind, with_normals), _rig_surfaces(rigs)
         self._ck(self._lib.jpt_multi_set_mesh_rig(self.h, mesh_id, arr, rarr, len(bind.surfaces), influences, n_blend_shapes), "jpt_multi_set_mesh_rig")
 
-    def pose_mesh(self, mesh_id: int, bone_transforms12=None, blend_weights=None):
+    def pose_mesh(self, mesh_id: int, bone_transforms12=None, blend_weights=None, rebuild: bool = False):
         """One pose of a rigged mesh (jpt_multi_pose_mesh: every rank's replica): float32 [n_bones, 12] bone transforms (bone pose x inverse bind, transform12
-        layout) and one weight per blend shape; the vertices are computed and the mesh refitted on the device, no synchronisation."""
+        layout) and one weight per blend shape; the vertices are computed and the mesh refitted on the device, no synchronisation.
+        rebuild: with a new BLAS topology (jpt_multi_pose_mesh_rebuild)."""
         b, nb, w, nw = _pose_arrays(bone_transforms12, blend_weights)
-        self._ck(self._lib.jpt_multi_pose_mesh(self.h, mesh_id, _ptr(b), nb, _ptr(w), nw), "jpt_multi_pose_mesh")
+        name = "jpt_multi_pose_mesh_rebuild" if rebuild else "jpt_multi_pose_mesh"
+        self._ck(getattr(self._lib, name)(self.h, mesh_id, _ptr(b), nb, _ptr(w), nw), name)
 
     def clear_mesh_rig(self, mesh_id: int):
         self._ck(self._lib.jpt_multi_clear_mesh_rig(self.h, mesh_id), "jpt_multi_clear_mesh_rig")

@@ -328,8 +328,8 @@ int jpt_scene_rebuild_tlas(jpt_ctx *ctx, const float *transforms12, uint32_t n_i
  *   not wait (except when a staging slot is reused).  The BLAS records are shared by every render, so the update waits on the
  *   device for every render queued before it: ONE PIPELINE DRAIN on the device per update; the renders queued after it wait
  *   for it.  The image of every later render equals a fresh JPT_BUILD_SAH_WATERTIGHT commit of the deformed scene except at
- *   exact distance ties; the topology stays the last commit's, so the boxes grow with the deformation -- a new commit
- *   re-optimises the tree: call it now and then when a mesh deforms far.  JPT_BUILD_SAH_WATERTIGHT scenes only (JPT_E_STATE
+ *   exact distance ties; the topology stays the last commit's, so the boxes grow with the deformation -- jpt_scene_rebuild_mesh
+ *   gives the mesh a new topology on the device, a new commit re-optimises the tree: call one now and then when a mesh deforms far.  JPT_BUILD_SAH_WATERTIGHT scenes only (JPT_E_STATE
  *   otherwise: JPT_BUILD_SAH's reach records and tie shadow are the reference builder's tree of the old vertices, and
  *   reference-exact trees are the reference's own).  Until the next jpt_scene_commit the host's copy of the scene is stale:
  *   jpt_scene_update_tlas, jpt_scene_share, jpt_scene_get_reference_buffer and renders with JPT_KERNEL_REFERENCE_LAYOUT or
@@ -337,6 +337,40 @@ int jpt_scene_rebuild_tlas(jpt_ctx *ctx, const float *transforms12, uint32_t n_i
  *   names has nothing on the device: its update succeeds and changes nothing there.  Host-only contexts: JPT_E_DEVICE after
  *   the argument checks. */
 int jpt_scene_update_mesh(jpt_ctx *ctx, uint32_t mesh_id, const jpt_surface *surfaces, int32_t n_surfaces);
+/*   route (ii), on the device, with a NEW BLAS TOPOLOGY: jpt_scene_update_mesh's arguments, state rules, error codes and messages
+ *   (with this call's name where a message names the call), its staging ring, its one pipeline drain on the device, the instance
+ *   refit behind it and every restriction of a deformed scene (a JPT_BUILD_SAH_WATERTIGHT commit, the mesh's own topology of
+ *   surfaces and indices, a stale host copy, the default kernel only, no sky cull) -- but the mesh's four-child records are made
+ *   anew from the new vertices.  Use it where a refit degrades: cloth, a ragdoll, a morph between distant shapes, debris that lives
+ *   in one mesh grow the leaf boxes of the last commit's tree until every record near the root covers the mesh.
+ *
+ *   The tree.  Triangle boxes: a triangle's box is the min and max of its three vertices taken one after the other from +-FLT_MAX
+ *   ((b < a) ? b : a and (a < b) ? b : a, so a NaN coordinate is skipped).  Centres: per axis (lo + hi) * 0.5.  Bounds: per axis the
+ *   min and max of the mesh's finite centres (an axis without one: +FLT_MAX .. -FLT_MAX).  Code: the 30-bit Morton code of
+ *   jpt_scene_rebuild_tlas over the triangle's vertex box -- cell = min(1023, floor((centre - bmin) * inv)), inv = 1024 / (bmax -
+ *   bmin) or 0 for an axis of no extent, a non-finite centre or product in cell 0, x in the highest bit of each triple; no float
+ *   step of its own.  Order: ascending by (code, triangle index within the mesh) -- a stable sort by code; the order is unique, so
+ *   any correct sort gives the same permutation.  Topology: jpt_debug_tlas_template's tree of n_tris sorted positions; a leaf slot
+ *   over position p is the ONE triangle tri_first + sorted[p], its reference ~(int32_t)(tri_first + sorted[p]) (count 1).  The
+ *   shading arrays are indexed by device triangle order: triangles are NOT reordered.  Boxes and quantised records: the refit's,
+ *   bit for bit -- a leaf slot its triangle's vertex box widened by the mesh's padding, an internal slot the union of the record
+ *   below, then jpt_debug_quantize_nodes4's form, then the mesh's root box.  A mesh of fewer than two triangles: the call is the
+ *   refit.
+ *
+ *   Storage.  The tree has about n_tris / 3 records, more than the commit's SAH tree: the mesh's first rebuild reserves a region of
+ *   that many records BEHIND the TLAS tails (every existing record keeps its index), points the root word of the mesh's instances
+ *   at it, uploads the tree's template and sizes the sort's buffers; that first call may WAIT on the host for the renders queued
+ *   before it.  After it no call waits for anything but the reuse of a staging slot.  The region is kept: later
+ *   jpt_scene_update_mesh / jpt_scene_pose_mesh calls refit over the rebuilt topology, later rebuilds reuse it,
+ *   jpt_debug_mesh_records reports it; the commit's range is no longer referenced.  jpt_scene_commit, an upload and jpt_scene_share
+ *   INTO the context drop every region.  A tree deeper than the kernels' stack: JPT_E_LIMIT before anything is written or reserved.
+ *
+ *   The image of every later render equals a fresh JPT_BUILD_SAH_WATERTIGHT commit of the deformed scene except at exact distance
+ *   ties.  The tree is a Morton tree with one-triangle leaves, not the commit's SAH tree (README, DESIGN.md section 5: the measured
+ *   difference, which says when to refit, rebuild or commit).  Not covered: SAH or any treelet optimisation; leaves of more than one
+ *   triangle; 63-bit codes; a host mirror of the rebuilt tree; JPT_BUILD_SAH and reference-exact scenes; returning the regions'
+ *   memory before the next commit. */
+int jpt_scene_rebuild_mesh(jpt_ctx *ctx, uint32_t mesh_id, const jpt_surface *surfaces, int32_t n_surfaces);
 /*   route (ii), on the device, from a bone palette: what Godot computes for a MeshInstance3D with a Skeleton3D / Skin and an ArrayMesh's
  *   blend shapes (relative mode), done where the mesh refit reads its result.  jpt_scene_set_mesh_rig stores, once per mesh, what stays
  *   constant after the commit; jpt_scene_pose_mesh then takes the few numbers that change per frame and does jpt_scene_update_mesh's
@@ -353,7 +387,7 @@ int jpt_scene_update_mesh(jpt_ctx *ctx, uint32_t mesh_id, const jpt_surface *sur
  *   caller: it maps a mesh-space bind position to a mesh-space posed position; instance transforms are not involved.
  *
  *   Not covered: dual-quaternion skinning, absolute (normalised-mode) blend shapes, tangents, per-instance poses (a mesh has ONE pose:
- *   its instances share the BLAS), and any re-optimisation of the tree (commit again when a mesh deforms far). */
+ *   its instances share the BLAS), and any SAH re-optimisation of the tree (jpt_scene_pose_mesh_rebuild gives it a new Morton topology; commit again for a SAH tree). */
 typedef struct {
     const int32_t *bones;            /* n_vertices * influences   Mesh::ARRAY_BONES   (NULL when influences == 0) */
     const float   *weights;          /* n_vertices * influences   Mesh::ARRAY_WEIGHTS (NULL when influences == 0) */
@@ -384,6 +418,10 @@ int jpt_scene_set_mesh_rig(jpt_ctx *ctx, uint32_t mesh_id, const jpt_surface *bi
  *   current. */
 int jpt_scene_pose_mesh(jpt_ctx *ctx, uint32_t mesh_id, const float *bone_transforms12, uint32_t n_bones,
                         const float *blend_weights, uint32_t n_blend_weights);
+/*   jpt_scene_pose_mesh with a NEW BLAS TOPOLOGY: its arguments, checks and messages (under this call's name), and behind the skin
+ *   kernel the call IS jpt_scene_rebuild_mesh over the posed vertices -- the tree, the region and the first call's wait as there. */
+int jpt_scene_pose_mesh_rebuild(jpt_ctx *ctx, uint32_t mesh_id, const float *bone_transforms12, uint32_t n_bones,
+                                const float *blend_weights, uint32_t n_blend_weights);
 /*   Drops the rig of `mesh_id` (no rig: nothing happens); the mesh keeps its last pose. */
 int jpt_scene_clear_mesh_rig(jpt_ctx *ctx, uint32_t mesh_id);
 /*   route (i): the caller re-ran BLASInstance::set_transform / TLAS::build itself; same instance count and
@@ -1454,6 +1492,10 @@ int jpt_multi_set_mesh_rig(jpt_multi *m, uint32_t mesh_id, const jpt_surface *bi
 int jpt_multi_pose_mesh(jpt_multi *m, uint32_t mesh_id, const float *bone_transforms12, uint32_t n_bones,
                         const float *blend_weights, uint32_t n_blend_weights);
 int jpt_multi_clear_mesh_rig(jpt_multi *m, uint32_t mesh_id);
+/* jpt_scene_rebuild_mesh / jpt_scene_pose_mesh_rebuild on every rank's replica */
+int jpt_multi_rebuild_mesh(jpt_multi *m, uint32_t mesh_id, const jpt_surface *surfaces, int32_t n_surfaces);
+int jpt_multi_pose_mesh_rebuild(jpt_multi *m, uint32_t mesh_id, const float *bone_transforms12, uint32_t n_bones,
+                                const float *blend_weights, uint32_t n_blend_weights);
 int jpt_multi_set_params(jpt_multi *m, int32_t width, int32_t height, int32_t max_bounces, int32_t accum_mode, int32_t sampler_mode);
 /* jpt_set_environment / jpt_set_environment_params on every rank */
 int jpt_multi_set_environment(jpt_multi *m, const float *rgb, int32_t width, int32_t height);
@@ -1714,6 +1756,13 @@ int jpt_debug_tlas_order(int device_id, const float *lo3, const float *hi3, uint
 int jpt_debug_tlas_template(uint32_t n, int32_t *child_out, uint32_t capacity, uint32_t *n_records, uint32_t *n_levels, uint32_t *stack_need);
 int jpt_debug_tlas_records(jpt_ctx *ctx, void *nodes4_out, void *nodesq_out, uint32_t capacity, uint32_t *n_records, int32_t *root_out,
                            float *inst_lo3, float *inst_hi3);
+/* jpt_scene_rebuild_mesh's order alone (its tests): n_tris triangles of three indices each into n_vertices vertices (3 floats each) ->
+ * the 30-bit code of every triangle (codes_out, may be NULL) and the triangle (0 .. n_tris - 1) at every position of the order
+ * ascending by (code, triangle), as jpt_scene_rebuild_mesh words it.  JPT_E_INVALID: a NULL array (n_tris > 0), an index >=
+ * n_vertices; JPT_E_LIMIT: more than 2^25 triangles.  device_id >= 0: the kernels the rebuild launches, on that device; device_id < 0:
+ * the same functions compiled for the host, sorted by std::sort. */
+int jpt_debug_mesh_order(int device_id, const float *vertices3, uint32_t n_vertices, const uint32_t *indices, uint32_t n_tris,
+                         uint32_t *codes_out /* may be NULL */, uint32_t *sorted_tris_out);
 
 /* jpt_scene_pose_mesh's arithmetic alone, on one caller-made rig of n_vertices vertices (one surface's arrays, as jpt_surface_rig's;
  * bind_normals3 may be NULL: no normals, normals3_out is not written and normal_deltas must be NULL) and one pose.  The arguments are

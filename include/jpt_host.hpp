@@ -687,6 +687,18 @@ class GeometryGroup3D {
         if (multi_) mcheck(jpt_multi_update_mesh(multi_, (uint32_t)id, sv.data(), (int32_t)sv.size()), "jpt_multi_update_mesh");
         else check(ctx_, jpt_scene_update_mesh(ctx_, (uint32_t)id, sv.data(), (int32_t)sv.size()), "jpt_scene_update_mesh");
     }
+    // update_mesh with a new BLAS topology made on the device (jpt_scene_rebuild_mesh): for a mesh that deformed far from its shape at
+    // build(); later update_mesh / pose_mesh calls refit over the new topology.  The mesh's first rebuild may wait for the queued renders.
+    void rebuild_mesh(const ArrayMesh* mesh)
+    {
+        const uint32_t id = built_mesh_id(mesh, "rebuild_mesh");
+        std::vector<jpt_surface> sv;
+        for (const Surface& x : mesh->surfaces)
+            sv.push_back(jpt_surface{x.vertices.data(), x.normals.empty() ? nullptr : x.normals.data(), nullptr, x.indices.data(),
+                                     (int32_t)(x.vertices.size() / 3), (int32_t)x.indices.size()});
+        if (multi_) mcheck(jpt_multi_rebuild_mesh(multi_, id, sv.data(), (int32_t)sv.size()), "jpt_multi_rebuild_mesh");
+        else check(ctx_, jpt_scene_rebuild_mesh(ctx_, id, sv.data(), (int32_t)sv.size()), "jpt_scene_rebuild_mesh");
+    }
 
     // A skinned or morphed mesh (Skeleton3D with Skin, ArrayMesh blend shapes), posed on the device.  set_mesh_rig: `mesh` is one of the
     // ArrayMesh objects the last build() collected, in its bind pose, `rigs` one SurfaceRig per surface (jpt_scene_set_mesh_rig).
@@ -710,12 +722,18 @@ class GeometryGroup3D {
         if (multi_) mcheck(jpt_multi_set_mesh_rig(multi_, id, sv.data(), rv.data(), (int32_t)sv.size(), influences, n_blend_shapes), "jpt_multi_set_mesh_rig");
         else check(ctx_, jpt_scene_set_mesh_rig(ctx_, id, sv.data(), rv.data(), (int32_t)sv.size(), influences, n_blend_shapes), "jpt_scene_set_mesh_rig");
     }
-    void pose_mesh(const ArrayMesh* mesh, const std::vector<float>& bone_transforms12, const std::vector<float>& blend_weights)
+    // rebuild: with a new BLAS topology over the posed vertices (jpt_scene_pose_mesh_rebuild), as rebuild_mesh
+    void pose_mesh(const ArrayMesh* mesh, const std::vector<float>& bone_transforms12, const std::vector<float>& blend_weights, bool rebuild = false)
     {
         const uint32_t id = built_mesh_id(mesh, "pose_mesh");
         const float* b = bone_transforms12.empty() ? nullptr : bone_transforms12.data();
         const float* w = blend_weights.empty() ? nullptr : blend_weights.data();
         const uint32_t nb = (uint32_t)(bone_transforms12.size() / 12), nw = (uint32_t)blend_weights.size();
+        if (rebuild) {
+            if (multi_) mcheck(jpt_multi_pose_mesh_rebuild(multi_, id, b, nb, w, nw), "jpt_multi_pose_mesh_rebuild");
+            else check(ctx_, jpt_scene_pose_mesh_rebuild(ctx_, id, b, nb, w, nw), "jpt_scene_pose_mesh_rebuild");
+            return;
+        }
         if (multi_) mcheck(jpt_multi_pose_mesh(multi_, id, b, nb, w, nw), "jpt_multi_pose_mesh");
         else check(ctx_, jpt_scene_pose_mesh(ctx_, id, b, nb, w, nw), "jpt_scene_pose_mesh");
     }
