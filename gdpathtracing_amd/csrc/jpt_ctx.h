@@ -1,5 +1,5 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
+// (jpt_capi.cpp, jpt_render.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
 #pragma once
 #include "../../include/jpt.h"
 
@@ -136,6 +136,79 @@ struct PipeSlot {
     DevBuf<char> workspace;
 };
 
+// What the context holds of how its renders are planned, launched, pipelined and timed: written and read by the render entry points, the
+// plan and the policy calls (jpt_render.cpp).  The rest of the host layer only tells it that a workspace was touched behind the
+// pipeline's back (workspaces_touched: jpt_set_stream, the lighting's table kernels) and makes and gives back its events (jpt_create,
+// jpt_destroy).  Render pipelining (jpt_render_async): consecutive asynchronous renders run their path kernels on the slots' streams with
+// their own workspaces, so one render's launch tails overlap the next render's kernels; the accumulation kernels are ordered on the
+// context's stream.
+struct RenderPipe {
+    // the render's event pair, around its launches on the context's stream: their distance is last_render_ms, and ev1 is also what
+    // pipeline_idle asks (completed: nothing of this context is in flight)
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // the pipeline slots and the frame groups' helper streams, all made on first use
+    static constexpr int kPipeSlots = 8;   // the most; the rule is 4, or 6 where six of the slots' streams run side by side (six_queues_probe)
+    PipeSlot slot[kPipeSlots];
+    Wf2Streams group_streams;                 // helper streams / events of the frame groups (launch_wf2_render)
+    bool aux_borrowed[kMaxGroups - 1] = {};   // group_streams.aux_stream[k] is slot[k].stream (ensure_group_streams): not destroyed on its own
+    // the plan's memory (plan_launch)
+    int six_queues = -1;       // -1: not probed yet; 0 / 1
+    int last_pipe_slots = 0;   // jpt_renders_in_flight
+    uint64_t async_seq = 0;    // counts the queued renders (jpt_set_memory_policy starts it over): the next one's slot is async_seq % slots
+    int idle_streak = 0;       // queued renders in a row that found nothing in flight
+    // the host's policy
+    int32_t slot_priority = JPT_STREAM_PRIORITY_DEFAULT;   // jpt_set_stream_priority
+    int32_t max_slots = 0;                                 // jpt_set_memory_policy: renders in flight (0: the library's rule)
+    uint64_t workspace_budget = 0;                         // ... and bytes per workspace (0: tuning().workspace_budget_mb)
+    // what the last render left for the statistics
+    std::vector<uint32_t> h_qcount;         // per-bounce queue sizes of the last wavefront render
+    std::vector<hipEvent_t> trace_events;   // pairs around each wf_trace launch of the last render (jpt_ctx::kernel_timing)
+    int32_t trace_events_used = 0;
+    // the tiles' sky cells (launch_sky_tiles): a function of the camera, the image size and the partition -- made when one of them
+    // changes, read by every accumulation until then
+    DevBuf<uint32_t> d_sky_tiles;
+    RefCamera sky_tiles_camera;
+    int32_t sky_tiles_key[5] = {0, 0, 0, 0, 0};   // width, height, local_rows, rank, world
+    bool sky_tiles_valid = false;
+
+    // a slot's workspace (every slot's) was written or read outside the pipeline's own order: its ev_acc_done says nothing any more
+    void workspace_touched(int k) { slot[k].acc_done_valid = false; }
+    void workspaces_touched() { for (PipeSlot& ps : slot) ps.acc_done_valid = false; }
+    hipError_t drain_slots();      // waits for every slot stream that exists; the first error
+    void release_streams();        // drains and destroys the slots' streams and the helper streams; the next render that needs them makes new ones
+    hipError_t create_events();    // ev0 and ev1 (jpt_create)
+    void destroy();                // every event and stream above, once the context's stream has run dry (jpt_destroy)
+};
+
+// The launch shape of one render: where it runs, in how many frame groups, with how many segments per tracing block.
+struct LaunchPlan {
+    enum Route { kReference, kStream, kSlot } route = kReference;   // the reference-layout kernel / the context's stream / a pipeline slot
+    int slot = 0, slots = 0;    // kSlot: the slot, and how many there are
+    int groups = 1;             // frame groups (launch_wf2_render)
+    int chain = 1;              // wf2_trace: consecutive segments per block
+};
+// What plan_launch asks of the device, each only where a rule reaches it (their side effects are part of the rules).
+struct PlanDevice {
+    bool (*six_queues)(jpt_ctx*);                // six of the slots' streams run side by side (six_queues_probe)
+    bool (*idle)(jpt_ctx*);                      // nothing of this context is in flight (pipeline_idle)
+    bool (*slot_stream)(jpt_ctx*, int slot);     // the slot's stream and events exist, made if need be (ensure_pipe_slot)
+    int (*group_streams)(jpt_ctx*, int groups);  // helper streams there are for `groups` frame groups (ensure_group_streams)
+};
+// Every rule of a render's launch shape, in one place (jpt_render.cpp; declared here for tests/cpp/plan_launch_test.cpp, which passes a
+// PlanDevice of its own).  fp: the render's frame_params; r: its sky cull and lighting.
+LaunchPlan plan_launch(jpt_ctx* c, const FrameParams& fp, const Wf2Render& r, bool counted, bool blocking, const PlanDevice& dev);
+
+// The temporal pass's state (JPT_DENOISE_TEMPORAL): written by jpt_set_temporal_params and the render that runs the pass (jpt_render.cpp),
+// dropped by everything that starts its history over (restart), read by jpt_read_accum_f32.
+struct TemporalState {
+    RefTemporalParams temporal;
+    bool temporal_set = false, hist_valid = false;
+    DevBuf<float4> d_hist1, d_hist2;   // frameBuffer1 / frameBuffer2 of temporal_reprojection.glsl:16-17
+    float4* hist_written = nullptr;    // the one the last temporal pass wrote
+    // the history images start from zero at the next pass (a new TemporalReprojection object), and there is nothing to read until then
+    void restart() { hist_valid = false; hist_written = nullptr; }
+};
+
 // What the context holds of its renders' lighting: written by the setters, read by lighting_bound and resolve_lighting (all in
 // jpt_lighting.cpp), which turn it into the one value the renders take (Lighting, jpt_kernels.h)
 struct LightingState {
@@ -237,6 +310,8 @@ int read_out(jpt_ctx* c, const void* src, size_t bytes, void* out);
 // ... of an image of `comps` elements of `elem` bytes per pixel: `src` holds the whole image (`whole`), or the context's rows, which are
 // scattered to their image rows of a zeroed `out` when the context is a partition (world > 1)
 int read_rows_out(jpt_ctx* c, const void* src, size_t elem, int comps, bool whole, void* out);
+// ... whose pinned buffer is given back whenever the framebuffers are re-made, and by jpt_set_memory_policy (jpt_render.cpp)
+void release_read_staging(jpt_ctx* c);
 
 // What the context holds of its post stages, the calls that read the progressive sum on the context's stream and keep what they make in
 // buffers of their own: written and read by those calls and their read-backs (jpt_post.cpp; jpt_encode.cpp reads three of the images)
@@ -452,8 +527,6 @@ using namespace jpt;   // (jpt_ctx is the name include/jpt.h gives it: global)
 struct jpt_ctx {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    Wf2Streams group_streams;  // helper streams / events of the frame groups (launch_wf2_render)
     std::string error;
 
     // host scene
@@ -465,9 +538,6 @@ struct jpt_ctx {
     bool host_scene_ready = false;  // c->ref / c->wide hold a complete scene (also true on host-only contexts)
     bool from_commit = false;       // the scene came from jpt_scene_commit: c->builder holds its meshes and transforms
     int32_t upload_mode = JPT_UPLOAD_NATIVE_TREE;  // jpt_set_upload_mode
-    int32_t slot_priority = JPT_STREAM_PRIORITY_DEFAULT;  // jpt_set_stream_priority
-    int32_t max_slots = 0;              // jpt_set_memory_policy: renders in flight (0: the library's rule)
-    uint64_t workspace_budget = 0;      // ... and bytes per workspace (0: tuning().workspace_budget_mb)
     std::string upload_note;        // why the last reference-layout upload is walked as given (empty: it is not)
     std::string ties_note;          // why exact distance ties fall to the native tree's order (empty: they are decided exactly)
     std::vector<RefMaterial> pending_materials;
@@ -489,44 +559,21 @@ struct jpt_ctx {
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
     bool depth_valid = false;              // d_depth holds the last render's depth image
-    // render pipelining (jpt_render_async): consecutive asynchronous renders run their path kernels on the slots' streams
-    // with their own workspaces, so one render's launch tails overlap the next render's kernels; the accumulation
-    // kernels are ordered on the context's stream
-    static constexpr int kPipeSlots = 8;   // the most; the rule is 4, or 6 where six of the slots' streams run side by side (six_queues_probe)
-    PipeSlot slot[kPipeSlots];
-    int six_queues = -1;                   // -1: not probed yet; 0 / 1
-    int last_pipe_slots = 0;               // jpt_renders_in_flight
-    bool aux_borrowed[kMaxGroups - 1] = {};   // group_streams.aux_stream[k] is slot[k].stream (ensure_group_streams): not destroyed on its own
-    uint64_t async_seq = 0;
-    int idle_streak = 0;   // queued renders in a row that found nothing in flight (plan_launch)
-    std::vector<uint32_t> h_qcount;  // per-bounce queue sizes of the last wavefront render
-    std::vector<hipEvent_t> trace_events;  // pairs around each wf_trace launch of the last render
-    int32_t trace_events_used = 0;
-    bool kernel_timing = false;
+    bool kernel_timing = false;   // jpt_set_kernel_timing: event pairs around the launches (pipe.trace_events, primary.refl_ev, enc_ev)
 
     // framebuffers (local rows of this partition)
     DevBuf<float4> d_accum;
     DevBuf<uint32_t> d_ldr;
     DevBuf<float> d_depth;
     DevBuf<DevCounters> d_counters;
-    // the tiles' sky cells (launch_sky_tiles): a function of the camera, the image size and the partition -- made when one of them
-    // changes, read by every accumulation until then
-    DevBuf<uint32_t> d_sky_tiles;
-    RefCamera sky_tiles_camera;
-    int32_t sky_tiles_key[5] = {0, 0, 0, 0, 0};   // width, height, local_rows, rank, world
-    bool sky_tiles_valid = false;
     // assembled full image on the gathering rank
     DevBuf<float4> d_full_accum;
     DevBuf<uint32_t> d_full_ldr;
     bool assembled = false;      // d_full_accum + d_full_ldr hold the whole image (jpt_assemble_from_ranks)
     bool assembled_ldr = false;  // d_full_ldr only (jpt_assemble_ldr_from_ranks)
 
-    // post-processing mode (PathTracingCamera::Denoising) and the temporal pass's state
+    // post-processing mode (PathTracingCamera::Denoising)
     int32_t denoise = JPT_DENOISE_PROGRESSIVE;
-    RefTemporalParams temporal;
-    bool temporal_set = false, hist_valid = false;
-    DevBuf<float4> d_hist1, d_hist2;   // frameBuffer1 / frameBuffer2 of temporal_reprojection.glsl:16-17
-    float4* hist_written = nullptr;    // the one the last temporal pass wrote
 
     PinnedBuf h_ldr_pinned;    // the split read-back of the display image
     PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
@@ -534,6 +581,8 @@ struct jpt_ctx {
     bool readback_pending = false;
     bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
 
+    RenderPipe pipe;          // the events, slots, streams, plan memory and policy of the renders (jpt_render.cpp)
+    TemporalState reproj;     // the temporal pass's parameters and history images (jpt_render.cpp)
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
     PrimaryState primary;     // the lens, the camera model, the bake images, the probes and the reflection probes (jpt_primary.cpp)
     PostState post;           // the parameters, buffers and validity flags of the calls that read the progressive sum (jpt_post.cpp)

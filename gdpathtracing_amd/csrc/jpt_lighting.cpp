@@ -100,7 +100,7 @@ int ensure_light_tables(jpt_ctx* c)
     a.marg = l.d_light_marg.p;
     launch_light_tables(s, a);
     HIP_TRY(c, hipGetLastError());
-    for (PipeSlot& ps : c->slot) ps.acc_done_valid = false;
+    c->pipe.workspaces_touched();
     l.light_table_stale = false;
     return JPT_OK;
 }
@@ -501,7 +501,7 @@ int jpt_set_sky(jpt_ctx* c, const jpt_sky_params* params, int32_t width, int32_t
     l.env_tables = false;   // (the tables' buffers stay: a rebuild of the same size reuses them, on this stream)
     launch_sky(c->stream, P, width, height, samples, l.d_env.p);
     HIP_TRY(c, hipGetLastError());
-    for (PipeSlot& ps : c->slot) ps.acc_done_valid = false;
+    c->pipe.workspaces_touched();
     l.env_set = true;
     if (l.env_sampling == JPT_ENV_SAMPLING_MIS) return build_env_tables(c);
     return JPT_OK;

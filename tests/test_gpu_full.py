@@ -738,7 +738,7 @@ def test_asynchronous_renders_pipeline_in_order(oracle, hiplib):
 
 def test_one_render_in_flight_at_a_time_then_a_burst(oracle, hiplib):
     """A host that queues one render, waits, queues the next: from the third such render on the library launches them like
-    blocking renders (frame groups, full-width launches: jpt_capi.cpp, `lone_async`), and goes back to the pipelined form as soon
+    blocking renders (frame groups, full-width launches: jpt_render.cpp, plan_launch's `lone`), and goes back to the pipelined form as soon
     as a render finds work in flight.  Eight renders continuing one accumulation -- five one at a time (sync, read-back or the
     split read-back in between), then a burst of three -- leave what the same frames leave through jpt_render, and that is the
     oracle's image."""
@@ -1152,7 +1152,7 @@ def test_zero_throughput_vertices_are_counted(hiplib):
 def test_renders_in_flight_follow_the_hardware_queues(hiplib, queues, slots):
     """Six renders in flight where six of the library's streams get a hardware queue each, four where they have to share a smaller
     pool (here: one or two queues per priority level at the process's first HIP call) -- measured by the library before its first
-    queued render (jpt_capi.cpp, six_queues_probe), reported by jpt_renders_in_flight.  Either way a queue of renders leaves the image
+    queued render (jpt_render.cpp, six_queues_probe), reported by jpt_renders_in_flight.  Either way a queue of renders leaves the image
     of the same renders made one at a time.  The variable is read once per process: a child process per setting."""
     import subprocess
     import sys

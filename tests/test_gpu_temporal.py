@@ -1,4 +1,4 @@
-"""TEMPORAL_REPROJECTION on the device -- temporal_kernel (jpt_kernels_post.hip) and the state around it in jpt_capi.cpp (the two
+"""TEMPORAL_REPROJECTION on the device -- temporal_kernel (jpt_kernels_post.hip) and the state around it in jpt_render.cpp and jpt_capi.cpp (the two
 history images, hist_valid, hist_written, the image picked by frame_count % 2) -- at the edges tests/test_oracle_temporal.py pins
 for the oracle on the CPU.  Every comparison is bit for bit.  Two yardsticks:
 
