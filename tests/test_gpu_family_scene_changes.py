@@ -435,6 +435,63 @@ def test_pose_mesh_equals_a_fresh_commit_and_outlives_its_rig(hiplib, family, li
         ctx.close()
 
 
+# ---- 4a. jpt_scene_rebuild_tlas: a new instance-level topology -------------------------------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_rebuild_tlas_equals_a_fresh_commit_and_refuses_the_audit_kernel(hiplib, family, lighting):
+    """change 2 with jpt_scene_rebuild_tlas: the balanced four-way tree over the Morton order in place of the commit's"""
+    st = stage(family)
+    sc2 = box_moved(st, 2)
+    ctx = ctx_for(st.scene, family, lighting, WATERTIGHT)
+    try:
+        before = state(ctx, family)
+        ctx.rebuild_tlas(all_transforms(sc2))
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting, WATERTIGHT), "rebuild_tlas")
+        assert_moved(after, before, family, "rebuild_tlas")
+        assert_post(ctx, after, family, "rebuild_tlas")
+        assert_audit_refused(ctx, family, b"jpt_scene_refit_tlas")
+        assert_state(state(ctx, family), after, "rebuild_tlas, after the refused renders")
+        ctx.update_tlas()   # brings the other kernel's records up to date
+        assert_state(state(ctx, family, AUDIT), fresh_state(sc2, family, lighting, WATERTIGHT, AUDIT), "rebuild_tlas + update_tlas, audit kernel")
+        assert_state(state(ctx, family), after, "rebuild_tlas + update_tlas")
+    finally:
+        ctx.close()
+
+
+# ---- 4b. jpt_scene_rebuild_mesh, then jpt_scene_pose_mesh_rebuild: new BLAS topologies --------------------------------------------------
+
+@pytest.mark.parametrize("family,lighting", CASES)
+def test_rebuild_mesh_equals_a_fresh_commit_and_refuses_the_audit_kernel(hiplib, family, lighting):
+    """change 3 with jpt_scene_rebuild_mesh on the box, then a pose of the tube that rebuilds its tree as well: two meshes' records
+    in regions of their own"""
+    st = stage(family)
+    new, sc2 = box_deformed(st, 2)
+    bind = st.scene.meshes[st.tube_mesh]
+    rigs = tube_rigs(bind)
+    pal, bw = skin_pose(1)
+    sc3 = with_mesh(sc2, st.tube_mesh, np_skin.skin_mesh(bind, rigs, 4, pal, bw))
+    ctx = ctx_for(st.scene, family, lighting, WATERTIGHT)
+    try:
+        before = state(ctx, family)
+        ctx.rebuild_mesh(st.box_mesh, new, with_normals=True)
+        after = state(ctx, family)
+        assert_state(after, fresh_state(sc2, family, lighting, WATERTIGHT), "rebuild_mesh")
+        assert_moved(after, before, family, "rebuild_mesh")
+        assert_post(ctx, after, family, "rebuild_mesh")
+        assert_audit_refused(ctx, family, b"jpt_scene_update_mesh")
+        assert_state(state(ctx, family), after, "rebuild_mesh, after the refused renders")
+        ctx.set_mesh_rig(st.tube_mesh, bind, host_rigs(rigs), 4, 2)
+        ctx.pose_mesh(st.tube_mesh, pal, bw, rebuild=True)
+        posed = state(ctx, family)
+        assert_state(posed, fresh_state(sc3, family, lighting, WATERTIGHT), "rebuild_mesh, then pose_mesh with a rebuild")
+        assert_moved(posed, after, family, "pose_mesh with a rebuild")
+        assert_post(ctx, posed, family, "pose_mesh with a rebuild")
+        assert_audit_refused(ctx, family, b"jpt_scene_update_mesh")
+    finally:
+        ctx.close()
+
+
 # ---- 5. a second jpt_scene_commit -----------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("family,lighting", CASES)
