@@ -1,4 +1,5 @@
-// jpt_capi.cpp -- the C ABI of include/jpt.h over the HIP kernels and the host builder.
+// jpt_capi.cpp -- the C ABI of include/jpt.h over the HIP kernels and the host builder: the context's life cycle and stream, the host
+// scene and its uploads, the ray queries and the one-line setters (the rest of the ABI: the other host files named in jpt_ctx.h).
 #include "jpt_ctx.h"
 
 #include <algorithm>
@@ -66,54 +67,9 @@ void jpt::set_scene_view(jpt_ctx* c)
     x.inst_tlas_leaf = b.x_inst_leaf.p;
 }
 
-// The blocking read-backs' pinned staging buffer grows to the largest read-back ever made (133 MB after one jpt_read_accum_f32 of a
-// 3840 x 2160 image) and would otherwise be held until jpt_destroy: given back whenever the framebuffers are re-made (another
-// resolution or partition) and by jpt_set_memory_policy; the next read-back allocates what it needs.
-void jpt::release_read_staging(jpt_ctx* c) { c->h_read_pinned.release(); }
-
 namespace {
 
 thread_local std::string g_create_error;
-
-int32_t rows_of_rank(int32_t height, int32_t rank, int32_t world)
-{
-    const int32_t n_strips = (height + kStripRows - 1) / kStripRows;
-    int32_t rows = 0;
-    for (int32_t s = rank; s < n_strips; s += world) {
-        const int32_t y0 = s * kStripRows;
-        rows += (y0 + kStripRows <= height) ? kStripRows : (height - y0);
-    }
-    return rows;
-}
-
-int32_t max_rows_of_any_rank(int32_t height, int32_t world)
-{
-    int32_t m = 0;
-    for (int32_t r = 0; r < world; r++) m = std::max(m, rows_of_rank(height, r, world));
-    return m;
-}
-
-int alloc_framebuffers(jpt_ctx* c)
-{
-    if ((size_t)max_rows_of_any_rank(c->height, c->world) * c->width != c->d_accum.n) release_read_staging(c);
-    c->local_rows = rows_of_rank(c->height, c->rank, c->world);
-    // every rank allocates the same (maximum) size so a gather sees equal-sized pieces
-    const size_t npx = (size_t)max_rows_of_any_rank(c->height, c->world) * c->width;
-    HIP_TRY(c, c->d_accum.resize(npx));
-    HIP_TRY(c, c->d_ldr.resize(npx));
-    HIP_TRY(c, c->d_depth.resize(npx));
-    HIP_TRY(c, c->d_counters.resize(1));
-    if (npx) {
-        HIP_TRY(c, hipMemsetAsync(c->d_accum.p, 0, npx * sizeof(float4), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_ldr.p, 0, npx * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(c->d_depth.p, 0, npx * sizeof(float), c->stream));
-    }
-    c->frame_count = 0;
-    c->accum_restarts++;
-    c->assembled = c->assembled_ldr = false;
-    c->post.framebuffers_remade(false);
-    return JPT_OK;
-}
 
 // the builder's mode for the scene's tree (an as-given upload: ReferenceExact; rebuild_instances only sees committed scenes)
 BuildMode build_mode(const jpt_ctx* c)
@@ -343,67 +299,7 @@ int validate_ref_scene(jpt_ctx* c, const RefScene& r)
     return JPT_OK;
 }
 
-// local strip-major rows -> full image rows, on the host
-template <typename T>
-void scatter_rows(const T* local, T* out, int32_t width, int32_t height, int32_t rank, int32_t world, int comps)
-{
-    const int32_t n_strips = (height + kStripRows - 1) / kStripRows;
-    int32_t ly = 0;
-    for (int32_t s = rank; s < n_strips; s += world) {
-        for (int32_t r = 0; r < kStripRows; r++) {
-            const int32_t y = s * kStripRows + r;
-            if (y >= height) break;
-            std::memcpy(out + (size_t)y * width * comps, local + (size_t)ly * width * comps, (size_t)width * comps * sizeof(T));
-            ly++;
-        }
-    }
-}
-template <typename T>
-void scatter_rows(const std::vector<T>& local, T* out, int32_t width, int32_t height, int32_t rank, int32_t world, int comps)
-{
-    scatter_rows(local.data(), out, width, height, rank, world, comps);
-}
-
-// the pinned staging buffer of the display image's split read-backs (one full image)
-int ensure_ldr_pinned(jpt_ctx* c)
-{
-    HIP_TRY(c, c->h_ldr_pinned.reserve((size_t)c->width * c->height * sizeof(uint32_t)));
-    return JPT_OK;
-}
-
 }  // namespace
-
-// Blocking read-backs (jpt_read_ldr_rgba8 / accum_f32 / depth_f32): device -> the context's pinned read buffer -> the caller's
-// memory.  A device-to-host copy straight into pageable memory runs at ~3 GB/s (8 MB of display image: 2.7 ms; 33 MB of float4
-// sums: 11 ms); through pinned memory the copy runs at the link's rate and the host copy at memory speed.  (A buffer of its
-// own: the split read-back's staging buffer may hold an image in flight.)
-int jpt::staged_read(jpt_ctx* c, const void* src, size_t bytes)
-{
-    HIP_TRY(c, c->h_read_pinned.reserve(bytes));
-    if (bytes) {
-        HIP_TRY(c, hipMemcpyAsync(c->h_read_pinned.p, src, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return JPT_OK;
-}
-
-int jpt::read_out(jpt_ctx* c, const void* src, size_t bytes, void* out)
-{
-    const int rc = staged_read(c, src, bytes);
-    if (rc == JPT_OK && bytes) std::memcpy(out, c->h_read_pinned.p, bytes);
-    return rc;
-}
-
-int jpt::read_rows_out(jpt_ctx* c, const void* src, size_t elem, int comps, bool whole, void* out)
-{
-    const size_t px_bytes = elem * (size_t)comps, full = (size_t)c->width * c->height * px_bytes;
-    if (whole || c->world == 1) return read_out(c, src, whole ? full : (size_t)c->local_rows * c->width * px_bytes, out);
-    const int rc = staged_read(c, src, (size_t)c->local_rows * c->width * px_bytes);
-    if (rc != JPT_OK) return rc;
-    std::memset(out, 0, full);
-    scatter_rows(c->h_read_pinned.as<const char>(), static_cast<char*>(out), c->width, c->height, c->rank, c->world, (int)px_bytes);
-    return JPT_OK;
-}
 
 extern "C" {
 
@@ -461,10 +357,9 @@ void jpt_destroy(jpt_ctx* c)
     }
     (void)hipSetDevice(c->device);
     if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-    if (c->ev_readback) (void)hipEventDestroy(c->ev_readback);
-    for (hipEvent_t e : c->primary.refl_ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->enc_ev) if (e) (void)hipEventDestroy(e);
-    if (c->ev_enc_readback) (void)hipEventDestroy(c->ev_enc_readback);
+    c->image.destroy();
+    c->primary.destroy();
+    c->enc.destroy();
     c->upd.destroy_stream();
     c->pipe.destroy();
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -829,48 +724,6 @@ int jpt_scene_get_reference_buffer(jpt_ctx* c, int32_t which, void* out, size_t 
     return JPT_OK;
 }
 
-int jpt_set_params(jpt_ctx* c, int32_t width, int32_t height, int32_t max_bounces, int32_t accum_mode, int32_t sampler_mode)
-{
-    if (!c) return JPT_E_INVALID;
-    if (width < 0 || height < 0 || width > 65536 || height > 65536) return fail(c, JPT_E_INVALID, "bad resolution");
-    if (max_bounces < 0 || max_bounces > kMaxBounces) return fail(c, JPT_E_INVALID, "max_bounces must be in [0,64]");
-    if (accum_mode != JPT_ACCUM_REF_LDR8 && accum_mode != JPT_ACCUM_HDR_F32) return fail(c, JPT_E_INVALID, "unknown accum_mode");
-    if (sampler_mode < JPT_SAMPLER_NEAREST_CLAMP || sampler_mode > JPT_SAMPLER_LINEAR_REPEAT) return fail(c, JPT_E_INVALID, "unknown sampler_mode");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context has no framebuffers");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (width != c->width || height != c->height) {
-        // the post stages' images are of the old size: given back once the work that uses them has run
-        if (c->post.sized_buffers()) HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->post.framebuffers_remade(true);
-        c->primary.sh_valid = c->primary.refl_valid = false;   // (jpt_probe_project's coefficients and jpt_reflection_prefilter's chain likewise)
-        // the temporal history is of the old size too (a new TemporalReprojection object): zeros at the next pass, and nothing to
-        // read until then -- the pixel count alone does not tell (32 x 32 -> 16 x 64), and hist_written is sized by the old one
-        c->reproj.restart();
-    }
-    c->width = width;
-    c->height = height;
-    c->max_bounces = max_bounces;
-    c->accum_mode = accum_mode;
-    c->sampler_mode = sampler_mode;
-    c->ds.sampler_mode = sampler_mode;
-    c->params_set = true;
-    c->depth_valid = false;
-    return alloc_framebuffers(c);
-}
-
-int jpt_set_partition(jpt_ctx* c, int32_t rank, int32_t world)
-{
-    if (!c) return JPT_E_INVALID;
-    if (world < 1 || rank < 0 || rank >= world) return fail(c, JPT_E_INVALID, "need 0 <= rank < world");
-    c->rank = rank;
-    c->world = world;
-    if (c->params_set && c->device >= 0) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        return alloc_framebuffers(c);
-    }
-    return JPT_OK;
-}
-
 int jpt_set_camera(jpt_ctx* c, const void* camera160)
 {
     if (!c || !camera160) return fail(c, JPT_E_INVALID, "null camera");
@@ -894,53 +747,6 @@ int jpt_set_debug_steps(jpt_ctx* c, int32_t enable)
     return JPT_OK;
 }
 
-int jpt_accum_reset(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    c->frame_count = 0;  // frame_count == 1 on the next frame overwrites the sum (progressive_rendering.glsl:34)
-    c->accum_restarts++;
-    c->stats.frames = 0;
-    c->assembled = c->assembled_ldr = false;
-    c->reproj.restart();  // temporal mode: history images start from zero again, and jpt_read_accum_f32 has nothing to show until a pass has run
-    return JPT_OK;
-}
-
-int jpt_set_progressive_frame_count(jpt_ctx* c, uint32_t next_frame_count)
-{
-    if (!c) return JPT_E_INVALID;
-    if (next_frame_count == 0) return fail(c, JPT_E_INVALID, "frame_count starts at 1 (progressive_rendering.cpp:20)");
-    c->frame_count = next_frame_count - 1u;
-    c->accum_restarts++;
-    c->stats.frames = c->frame_count;
-    c->assembled = c->assembled_ldr = false;
-    return JPT_OK;
-}
-
-int jpt_set_denoising_mode(jpt_ctx* c, int32_t mode)
-{
-    if (!c) return JPT_E_INVALID;
-    if (mode != JPT_DENOISE_PROGRESSIVE && mode != JPT_DENOISE_TEMPORAL && mode != JPT_DENOISE_NONE)
-        return fail(c, JPT_E_INVALID, "unknown denoising mode");
-    if (mode != c->denoise) {
-        // the modes do not share state: the progressive sum and the temporal history both start over
-        c->frame_count = 0;
-        c->accum_restarts++;
-        c->stats.frames = 0;
-        c->reproj.restart();
-        c->assembled = c->assembled_ldr = false;
-    }
-    c->denoise = mode;
-    return JPT_OK;
-}
-
-int jpt_set_outputs(jpt_ctx* c, uint32_t outputs)
-{
-    if (!c) return JPT_E_INVALID;
-    if (outputs & ~(uint32_t)JPT_OUTPUT_DEPTH) return fail(c, JPT_E_INVALID, "jpt_set_outputs: unknown output bit");
-    c->outputs = outputs;   // (takes effect with the next render; a depth image already written stays readable until then)
-    return JPT_OK;
-}
-
 int jpt_set_temporal_params(jpt_ctx* c, const void* render_parameters)
 {
     if (!c) return JPT_E_INVALID;
@@ -948,75 +754,6 @@ int jpt_set_temporal_params(jpt_ctx* c, const void* render_parameters)
     std::memcpy(&c->reproj.temporal, render_parameters, sizeof(RefTemporalParams));
     c->reproj.temporal_set = true;
     return JPT_OK;
-}
-
-static int read_common(jpt_ctx* c, void* out)
-{
-    if (!c || !out) return fail(c, JPT_E_INVALID, "null output");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return JPT_OK;
-}
-
-int jpt_read_ldr_rgba8(jpt_ctx* c, uint8_t* out)
-{
-    const int rc = read_common(c, out);
-    if (rc) return rc;
-    // What the reference does every frame (get_image_uniform_buffer, path_tracing_camera.cpp:228-229): through staged_read.
-    const bool whole = c->assembled || c->assembled_ldr;
-    return read_rows_out(c, whole ? c->d_full_ldr.p : c->d_ldr.p, sizeof(uint32_t), 1, whole, out);
-}
-
-int jpt_readback_ldr_begin(jpt_ctx* c)
-{
-    if (!c) return JPT_E_INVALID;
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
-    if (c->readback_pending) return fail(c, JPT_E_STATE, "a read-back is already in flight (call jpt_readback_ldr_end)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->readback_full = c->assembled || c->assembled_ldr;
-    const size_t px = c->readback_full ? (size_t)c->width * c->height : (size_t)c->local_rows * c->width;
-    {
-        const int rc = ensure_ldr_pinned(c);
-        if (rc) return rc;
-    }
-    if (!c->ev_readback) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_readback, hipEventDisableTiming));
-    if (px)
-        HIP_TRY(c, hipMemcpyAsync(c->h_ldr_pinned.p, c->readback_full ? c->d_full_ldr.p : c->d_ldr.p, px * sizeof(uint32_t),
-                                  hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->ev_readback, c->stream));
-    c->readback_pending = true;
-    return JPT_OK;
-}
-
-int jpt_readback_ldr_end(jpt_ctx* c, uint8_t* out)
-{
-    if (!c || !out) return fail(c, JPT_E_INVALID, "null output");
-    if (!c->readback_pending) return fail(c, JPT_E_STATE, "no read-back in flight (call jpt_readback_ldr_begin)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->ev_readback));
-    c->readback_pending = false;
-    const size_t full = (size_t)c->width * c->height;
-    if (c->readback_full || c->world == 1) {
-        std::memcpy(out, c->h_ldr_pinned.p, full * 4);
-    } else {
-        std::memset(out, 0, full * 4);
-        scatter_rows(c->h_ldr_pinned.as<const uint32_t>(), reinterpret_cast<uint32_t*>(out), c->width, c->height, c->rank, c->world, 1);
-    }
-    return JPT_OK;
-}
-
-int jpt_read_accum_f32(jpt_ctx* c, float* out)
-{
-    const int rc = read_common(c, out);
-    if (rc) return rc;
-    if (c->denoise == JPT_DENOISE_TEMPORAL) {
-        // the rgba32f image of this mode is the history image the last pass wrote
-        if (!c->reproj.hist_written) return fail(c, JPT_E_STATE, "no temporal pass has run since the last reset");
-        return read_out(c, c->reproj.hist_written, (size_t)c->width * c->height * sizeof(float4), out);
-    }
-    return read_rows_out(c, c->assembled ? c->d_full_accum.p : c->d_accum.p, sizeof(float), 4, c->assembled, out);
 }
 
 // ---- jpt_query_rays / jpt_query_pixels -----------------------------------------------------------------------------------------
@@ -1058,7 +795,7 @@ static int query_chunk(jpt_ctx* c, bool any, const CamModelDev* pixels, const vo
     char* d_rays = c->d_query.p;
     char* d_hits = d_rays + cap * sizeof(jpt_ray);
     char* d_occ = d_hits + cap * sizeof(jpt_ray_hit);
-    char* h = c->h_read_pinned.as<char>();
+    char* h = c->image.h_read_pinned.as<char>();
     hipStream_t s = c->stream;
     if (pixels) {   // 8 B per ray go up, into the hits' part; the rays are made from them in place on the device
         std::memcpy(h, in, (size_t)m * 2 * sizeof(float));
@@ -1083,7 +820,7 @@ static int query_host(jpt_ctx* c, bool any, const CamModelDev* pixels, const voi
 {
     const size_t cap = ((size_t)(n < kQueryChunk ? n : kQueryChunk) + 15) & ~(size_t)15;
     if (c->d_query.n < cap * 97) HIP_TRY(c, c->d_query.resize(cap * 97));
-    HIP_TRY(c, c->h_read_pinned.reserve(cap * (sizeof(jpt_ray_hit) + 1)));
+    HIP_TRY(c, c->image.h_read_pinned.reserve(cap * (sizeof(jpt_ray_hit) + 1)));
     const size_t in_stride = pixels ? 2 * sizeof(float) : sizeof(jpt_ray);
     for (size_t first = 0; first < n; first += kQueryChunk) {
         const uint32_t m = (uint32_t)(n - first < kQueryChunk ? n - first : kQueryChunk);
@@ -1135,66 +872,6 @@ int jpt_query_pixels(jpt_ctx* c, const float* xy, uint32_t n, jpt_ray_hit* hits_
     CamModelDev cm;   // (jpt_set_camera_model: picking follows the model)
     if ((rc = view_now(c, "jpt_query_pixels", "picking rays", cm)) != JPT_OK) return rc;
     return query_host(c, false, &cm, xy, n, hits_out, nullptr);
-}
-
-int jpt_read_depth_f32(jpt_ctx* c, float* out)
-{
-    int rc = read_common(c, out);
-    if (rc) return rc;
-    if (!c->depth_valid)
-        return fail(c, JPT_E_STATE, (c->outputs & JPT_OUTPUT_DEPTH) ? "no render has written the depth image yet"
-                                                                     : "the depth image is switched off (jpt_set_outputs): no render writes it");
-    return read_rows_out(c, c->d_depth.p, sizeof(float), 1, false, out);
-}
-
-void* jpt_device_accum(jpt_ctx* c, size_t* bytes_out)
-{
-    if (!c) return nullptr;
-    if (bytes_out) *bytes_out = c->d_accum.n * sizeof(float4);
-    return c->d_accum.p;
-}
-
-void* jpt_device_ldr(jpt_ctx* c, size_t* bytes_out)
-{
-    if (!c) return nullptr;
-    if (bytes_out) *bytes_out = c->d_ldr.n * sizeof(uint32_t);
-    return c->d_ldr.p;
-}
-
-int32_t jpt_local_rows(jpt_ctx* c) { return c ? c->local_rows : 0; }
-
-int jpt_assemble_from_ranks(jpt_ctx* c, const void* device_gathered, int32_t world)
-{
-    if (!c || !device_gathered) return fail(c, JPT_E_INVALID, "null gathered buffer");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
-    if (world != c->world) return fail(c, JPT_E_INVALID, "world differs from jpt_set_partition");
-    if (c->denoise != JPT_DENOISE_PROGRESSIVE)
-        return fail(c, JPT_E_STATE, "assembling re-derives the progressive display image; the other denoising modes run on one context");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const size_t full = (size_t)c->width * c->height;
-    HIP_TRY(c, c->d_full_accum.resize(full));
-    HIP_TRY(c, c->d_full_ldr.resize(full));
-    launch_assemble(c->stream, (const float4*)device_gathered, c->d_accum.p, c->rank, world, c->width, c->height,
-                    max_rows_of_any_rank(c->height, world), c->d_full_accum.p, c->d_full_ldr.p, c->frame_count);
-    HIP_TRY(c, hipGetLastError());
-    c->assembled = true;  // asynchronous on the context's stream; jpt_read_* / jpt_sync wait for it
-    return JPT_OK;
-}
-
-int jpt_assemble_ldr_from_ranks(jpt_ctx* c, const void* device_gathered, int32_t world)
-{
-    if (!c || !device_gathered) return fail(c, JPT_E_INVALID, "null gathered buffer");
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context");
-    if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
-    if (world != c->world) return fail(c, JPT_E_INVALID, "world differs from jpt_set_partition");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, c->d_full_ldr.resize((size_t)c->width * c->height));
-    launch_assemble_ldr(c->stream, (const uint32_t*)device_gathered, c->d_ldr.p, c->rank, world, c->width, c->height,
-                        max_rows_of_any_rank(c->height, world), c->d_full_ldr.p);
-    HIP_TRY(c, hipGetLastError());
-    c->assembled_ldr = true;  // asynchronous on the context's stream; jpt_read_ldr_rgba8 / jpt_sync wait for it
-    return JPT_OK;
 }
 
 int jpt_get_stats(jpt_ctx* c, jpt_stats* out)

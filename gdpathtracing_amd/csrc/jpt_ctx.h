@@ -1,5 +1,5 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_render.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
+// (jpt_capi.cpp, jpt_image.cpp, jpt_render.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
 #pragma once
 #include "../../include/jpt.h"
 
@@ -87,6 +87,38 @@ struct StagingRing {
         st = (int)(seq++ % (uint64_t)kRefitStages);
         hipError_t e = copied[st] ? hipEventSynchronize(copied[st]) : hipEventCreateWithFlags(&copied[st], hipEventDisableTiming);
         return e == hipSuccess ? buf[st].reserve(bytes) : e;
+    }
+};
+
+// A read-back in two halves, so that the host does other work while the copy runs: begin queues the copy into a pinned buffer of its
+// own on the caller's stream, wait blocks until it has landed.  One copy in flight at a time (`pending`; the owner refuses a second).
+struct SplitReadback {
+    PinnedBuf buf;
+    hipEvent_t ev = nullptr;   // made at the first begin; follows the copy in flight
+    bool pending = false;      // a begin has not been waited for yet
+    size_t bytes = 0;          // what the copy in flight copies
+    // `n` bytes at `src` -> buf behind everything queued on `s` so far (nothing is copied when n == 0)
+    hipError_t begin(const void* src, size_t n, hipStream_t s)
+    {
+        hipError_t e = buf.reserve(n);
+        if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e == hipSuccess && n) e = hipMemcpyAsync(buf.p, src, n, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev, s);
+        if (e != hipSuccess) return e;
+        bytes = n;
+        pending = true;
+        return hipSuccess;
+    }
+    hipError_t wait()
+    {
+        const hipError_t e = hipEventSynchronize(ev);
+        if (e == hipSuccess) pending = false;
+        return e;
+    }
+    void destroy()   // the event (the buffer is its destructor's)
+    {
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
     }
 };
 
@@ -292,6 +324,13 @@ struct PrimaryState {
     CubeDev cube_dev() const { return make_cube_dev(d_cube_pos.p, cube_n, cube_face, cube_per_row); }
     // the levels a jpt_reflection_prefilter of the probes makes now
     int32_t refl_levels_now() const { return refl_levels ? refl_levels : cube_log2(cube_face) + 1; }
+    void destroy()   // refl_ev (jpt_destroy)
+    {
+        for (hipEvent_t& e : refl_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
 };
 // Where the paths of one render of `c` start, once it is validated: the one of the six sources the context's state names, with the
 // others zeroed; kPinhole with DEBUG_STEPS, which ignores the lens, the model, the images and the probes as it ignores lighting.  In
@@ -303,7 +342,66 @@ int resolve_primary(jpt_ctx* c, PrimaryRays& out);
 // context's model seen through its camera as both are now -- no render's refusals apply.  JPT_E_STATE while the context holds bake
 // images, probes or reflection probes (`rays`: what the call's rays are, for the message).
 int view_now(jpt_ctx* c, const char* call, const char* rays, CamModelDev& out);
-// Blocking read-backs: device -> the context's pinned read buffer (h_read_pinned), on the context's stream (jpt_capi.cpp) ...
+// What the context holds of the image itself: the framebuffers of its rows and their sizes, how often the progressive sum started over, the
+// image assembled from every rank's piece, and the read-backs' staging (jpt_image.cpp).  Written by jpt_set_params / jpt_set_partition
+// (alloc_framebuffers), the renders (jpt_render.cpp: the buffers, depth_valid), the two jpt_assemble_* calls and restart_sum; read by
+// every post stage (jpt_post.cpp, jpt_primary.cpp, jpt_encode.cpp: d_accum) and every read-back.  The partition itself and the
+// progressive count stay in jpt_ctx beside width and height (rank, world, local_rows, frame_count): a render's FrameParams are made
+// of them, and tests/cpp/plan_launch_test.cpp sets them there.
+struct ImageSource {
+    const void* p;
+    bool whole;   // p holds the whole image (else: the context's rows)
+};
+struct ImageState {
+    // the partition's sizes (jpt_ctx::rank / world / local_rows are the renders' parameters, beside width and height: the context
+    // renders the strips rank, rank + world, ... into local_rows rows, rows_of_rank).  Every rank's buffers have the size of the largest
+    // rank's share, so that a gather sees equal pieces: piece_rows rows, piece_px pixels.  local_rows and these two are
+    // alloc_framebuffers', which runs whenever the resolution or the partition changes.
+    int32_t piece_rows = 0;
+    size_t piece_px = 0;
+    // framebuffers (piece_px each; the first local_rows rows are the context's)
+    DevBuf<float4> d_accum;
+    DevBuf<uint32_t> d_ldr;
+    DevBuf<float> d_depth;
+    bool depth_valid = false;      // d_depth holds the last render's depth image
+    // the progressive count is jpt_ctx::frame_count (every render's FrameParams start from it); only restart_sum and the renders write it
+    uint64_t accum_restarts = 0;  // how often the accumulation started over or was re-positioned (what a history call of jpt_denoise remembers)
+    // assembled full image on the gathering rank
+    DevBuf<float4> d_full_accum;
+    DevBuf<uint32_t> d_full_ldr;
+    bool assembled = false;        // d_full_accum + d_full_ldr hold the whole image (jpt_assemble_from_ranks)
+    bool assembled_ldr = false;    // d_full_ldr only (jpt_assemble_ldr_from_ranks)
+    // the read-backs' staging
+    PinnedBuf h_read_pinned;       // blocking read-backs (staged_read; the ray queries and jpt_read_denoise_history_f32 borrow it)
+    SplitReadback ldr_read;        // the split read-back of the display image (jpt_readback_ldr_begin / _end)
+    bool readback_full = false;    // the read-back in flight copies the assembled image (else: this context's rows)
+
+    // the display image (the sum) a read-back reads now: the assembled one while there is one
+    ImageSource display_now() const
+    {
+        const bool whole = assembled || assembled_ldr;
+        return {whole ? (const void*)d_full_ldr.p : d_ldr.p, whole};
+    }
+    ImageSource sum_now() const { return {assembled ? d_full_accum.p : d_accum.p, assembled}; }
+    void destroy() { ldr_read.destroy(); }   // the split read-back's event (jpt_destroy)
+};
+// The one place that says what starts over when the progressive sum does, and for whom.  Every row drops the assembled image
+// (assembled = assembled_ldr = false): it is of frames that are no longer the sum's.
+//   how               caller                                      frame_count   accum_restarts   stats.frames   temporal history   post stages
+//   kSumReset         jpt_accum_reset                             0             ++               0              restarted          --
+//                     jpt_set_denoising_mode, on a change only
+//   kSumPositioned    jpt_set_progressive_frame_count(n)          n - 1         ++               n - 1          kept               --
+//   kSumFramebuffers  alloc_framebuffers                          0             ++               kept           kept (*)           framebuffers_remade(false)
+//   kSumRendered      do_render_batch (adds its frames itself)    kept          kept             kept           kept               --
+// (*) jpt_set_params restarts the temporal history itself, on another size only.  `count`: kSumPositioned's n - 1.
+enum SumRestart { kSumReset, kSumPositioned, kSumFramebuffers, kSumRendered };
+void restart_sum(jpt_ctx* c, SumRestart how, uint32_t count = 0);
+// The partition's arithmetic (declared here for tests/cpp/image_rows_test.cpp): the rows of `rank`'s strips; the largest rank's share;
+// a rank's rows, in the order of its buffers, to their image rows of `out` (px_bytes per pixel), on the host
+int32_t rows_of_rank(int32_t height, int32_t rank, int32_t world);
+int32_t max_rows_of_any_rank(int32_t height, int32_t world);
+void scatter_rows(const char* local, char* out, int32_t width, int32_t height, int32_t rank, int32_t world, size_t px_bytes);
+// Blocking read-backs: device -> the context's pinned read buffer (image.h_read_pinned), on the context's stream (jpt_image.cpp) ...
 int staged_read(jpt_ctx* c, const void* src, size_t bytes);
 // ... and on to the caller's memory: `bytes` at `out` (nothing is copied when bytes == 0)
 int read_out(jpt_ctx* c, const void* src, size_t bytes, void* out);
@@ -333,7 +431,7 @@ struct PostState {
     // without history in between does not touch them) and the (m, v_0) image the filter reads, 112 B per pixel, made at the first
     // history call at a resolution; dh_cur: the set the last history call wrote, dh_have: it holds one (dropped by
     // jpt_denoise_history_reset, another size, switching enable), seen from dh_camera; dh_called / dh_restarts: a history call has
-    // consumed the frames of accumulation restart dh_restarts (jpt_ctx::accum_restarts); dh_read: d_dh_iv and set dh_cur hold a
+    // consumed the frames of accumulation restart dh_restarts (ImageState::accum_restarts); dh_read: d_dh_iv and set dh_cur hold a
     // history call's result at the current resolution (jpt_read_denoise_history_f32)
     HistoryParams dn_hist;
     DevBuf<float4> d_dh_set[2][3], d_dh_iv;
@@ -410,6 +508,27 @@ int ensure_variance(jpt_ctx* c);
 // and, unless `host_only` is null, a host-only context, in the call's own words.  sum_ready: no jpt_set_params, no frame since the reset.
 int reads_sum(jpt_ctx* c, const char* call, const char* what, const char* host_only, const char* whole = "", const char* steps = nullptr);
 int sum_ready(jpt_ctx* c, const char* call);
+
+// What the context holds of jpt_encode: written and read by that call, its read-backs and its timing (jpt_encode.cpp).  The buffer is its
+// own, grow-only and kept until jpt_destroy -- a snapshot that no other call writes; valid: it holds the texels `info` describes.
+// ev: two events around the last jpt_encode's kernel under jpt_set_kernel_timing (timed), made at the first such call.  read: the split
+// read-back of the buffer (jpt_readback_encoded_begin / _end), with staging of its own beside the display image's.
+struct EncodeState {
+    DevBuf<char> d_encoded;
+    jpt_encoded_info info = {};
+    bool valid = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+    SplitReadback read;
+    void destroy()   // the events (jpt_destroy)
+    {
+        for (hipEvent_t& e : ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        read.destroy();
+    }
+};
 
 // What the context holds of the calls that change a committed scene on the device without a new commit (the refits, rebuilds, mesh updates,
 // rigs and poses of jpt_scene_update.cpp, and its two debug readers).  The uploads (jpt_capi.cpp) put it back through host_uploaded; the
@@ -551,56 +670,26 @@ struct jpt_ctx {
     // per-render state
     bool params_set = false, camera_set = false;
     int32_t width = 0, height = 0, max_bounces = 4, accum_mode = 0, sampler_mode = 0;
-    int32_t rank = 0, world = 1, local_rows = 0;
+    int32_t rank = 0, world = 1, local_rows = 0;   // jpt_set_partition; local_rows: alloc_framebuffers' (jpt_image.cpp)
     RefCamera camera;
-    uint32_t frame_count = 0;  // frames accumulated since reset
-    uint64_t accum_restarts = 0;   // how often the accumulation started over or was re-positioned (what a history call of jpt_denoise remembers)
+    uint32_t frame_count = 0;  // frames accumulated since reset (restart_sum, jpt_image.cpp)
     int32_t kernel_variant = JPT_KERNEL_WAVEFRONT;
     bool debug_steps = false;  // jpt_set_debug_steps: the shader's DEBUG_STEPS build, on the audit kernel
     uint32_t outputs = JPT_OUTPUT_DEPTH;   // jpt_set_outputs: which of main.glsl's images the renders produce beside the colour
-    bool depth_valid = false;              // d_depth holds the last render's depth image
-    bool kernel_timing = false;   // jpt_set_kernel_timing: event pairs around the launches (pipe.trace_events, primary.refl_ev, enc_ev)
-
-    // framebuffers (local rows of this partition)
-    DevBuf<float4> d_accum;
-    DevBuf<uint32_t> d_ldr;
-    DevBuf<float> d_depth;
-    DevBuf<DevCounters> d_counters;
-    // assembled full image on the gathering rank
-    DevBuf<float4> d_full_accum;
-    DevBuf<uint32_t> d_full_ldr;
-    bool assembled = false;      // d_full_accum + d_full_ldr hold the whole image (jpt_assemble_from_ranks)
-    bool assembled_ldr = false;  // d_full_ldr only (jpt_assemble_ldr_from_ranks)
+    bool kernel_timing = false;   // jpt_set_kernel_timing: event pairs around the launches (pipe.trace_events, primary.refl_ev, enc.ev)
+    DevBuf<DevCounters> d_counters;   // a counted render's event counters (made with the framebuffers, read into stats)
 
     // post-processing mode (PathTracingCamera::Denoising)
     int32_t denoise = JPT_DENOISE_PROGRESSIVE;
 
-    PinnedBuf h_ldr_pinned;    // the split read-back of the display image
-    PinnedBuf h_read_pinned;   // blocking read-backs (staged_read)
-    hipEvent_t ev_readback = nullptr;
-    bool readback_pending = false;
-    bool readback_full = false;  // the read-back in flight copies the assembled image (else: this context's rows)
-
-    RenderPipe pipe;          // the events, slots, streams, plan memory and policy of the renders (jpt_render.cpp)
+    ImageState image;         // the framebuffers and their sizes, the restart count, the assembled image and the read-backs' staging (jpt_image.cpp)
+    RenderPipe pipe;         // the events, slots, streams, plan memory and policy of the renders (jpt_render.cpp)
     TemporalState reproj;     // the temporal pass's parameters and history images (jpt_render.cpp)
     LightingState lighting;   // the environment map, the emitters and their sampling modes (jpt_lighting.cpp)
     PrimaryState primary;     // the lens, the camera model, the bake images, the probes and the reflection probes (jpt_primary.cpp)
     PostState post;           // the parameters, buffers and validity flags of the calls that read the progressive sum (jpt_post.cpp)
     SceneUpdates upd;         // the copies, streams, schedules and flags of the calls that change a committed scene on the device (jpt_scene_update.cpp)
-
-    // jpt_encode (jpt_encode.cpp): its own buffer, grow-only and kept until jpt_destroy -- a snapshot that no other call writes;
-    // enc_valid: it holds the texels enc_info describes.  enc_ev: two events around the last jpt_encode's kernel under
-    // jpt_set_kernel_timing (enc_timed), made at the first such call.  The split read-back of it has a pinned buffer, an event and a
-    // pending flag of its own (the display image's: h_ldr_pinned, ev_readback); enc_read_bytes: what the read-back in flight copies.
-    DevBuf<char> d_encoded;
-    jpt_encoded_info enc_info = {};
-    bool enc_valid = false;
-    hipEvent_t enc_ev[2] = {nullptr, nullptr};
-    bool enc_timed = false;
-    PinnedBuf h_enc_pinned;
-    hipEvent_t ev_enc_readback = nullptr;
-    bool enc_readback_pending = false;
-    size_t enc_read_bytes = 0;
+    EncodeState enc;          // jpt_encode's buffer, what it holds, its timing and its split read-back (jpt_encode.cpp)
 
     // jpt_query_rays / jpt_query_pixels (host forms): one chunk's rays, hits and occlusion bytes on the device, grow-only
     DevBuf<char> d_query;

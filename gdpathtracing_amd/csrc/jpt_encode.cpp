@@ -31,7 +31,7 @@ int resolve_source(jpt_ctx* c, int32_t source, int32_t level, EncodeSource& s)
         int rc = reads_sum(c, "jpt_encode", ": the mean is of the progressive accumulation", nullptr);   // (the device: jpt_encode has asked)
         if (rc == JPT_OK) rc = sum_ready(c, "jpt_encode");
         if (rc != JPT_OK) return rc;
-        s.src = c->d_accum.p;
+        s.src = c->image.d_accum.p;
         s.divisor = (float)c->frame_count;
         s.alpha_one = true;
         return JPT_OK;
@@ -94,31 +94,31 @@ int jpt_encode(jpt_ctx* c, int32_t source, int32_t level, int32_t format)
     if (rc != JPT_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)s.n * encode_texel_bytes(format);
-    if (c->d_encoded.n < bytes) {
+    if (c->enc.d_encoded.n < bytes) {
         // (a split read-back in flight may still copy from the old buffer)
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        c->enc_valid = false;
-        HIP_TRY(c, c->d_encoded.resize(bytes));
+        c->enc.valid = false;
+        HIP_TRY(c, c->enc.d_encoded.resize(bytes));
     }
     const bool timed = c->kernel_timing;
     if (timed)
-        for (hipEvent_t& e : c->enc_ev)
+        for (hipEvent_t& e : c->enc.ev)
             if (!e) HIP_TRY(c, hipEventCreate(&e));
     // On the context's stream, as jpt_display: behind the accumulation of every render queued so far and behind the post calls queued
     // before it (also behind the copy of a split read-back in flight, which was queued first); whatever is queued later runs after it.
-    if (timed) HIP_TRY(c, hipEventRecord(c->enc_ev[0], c->stream));
-    launch_encode(c->stream, format, s.src, s.n, s.divisor, s.alpha_one, c->d_encoded.p);
-    if (timed) HIP_TRY(c, hipEventRecord(c->enc_ev[1], c->stream));
+    if (timed) HIP_TRY(c, hipEventRecord(c->enc.ev[0], c->stream));
+    launch_encode(c->stream, format, s.src, s.n, s.divisor, s.alpha_one, c->enc.d_encoded.p);
+    if (timed) HIP_TRY(c, hipEventRecord(c->enc.ev[1], c->stream));
     HIP_TRY(c, hipGetLastError());
-    c->enc_timed = timed;
-    c->enc_info.source = source;
-    c->enc_info.format = format;
-    c->enc_info.level = level;
-    c->enc_info.width = s.width;
-    c->enc_info.height = s.height;
-    c->enc_info.n_texels = s.n;
-    c->enc_info.bytes = bytes;
-    c->enc_valid = true;
+    c->enc.timed = timed;
+    c->enc.info.source = source;
+    c->enc.info.format = format;
+    c->enc.info.level = level;
+    c->enc.info.width = s.width;
+    c->enc.info.height = s.height;
+    c->enc.info.n_texels = s.n;
+    c->enc.info.bytes = bytes;
+    c->enc.valid = true;
     return JPT_OK;
 }
 
@@ -127,7 +127,7 @@ static int encoded_common(jpt_ctx* c, const char* call, bool have_out)
     if (!c) return JPT_E_INVALID;
     if (!have_out) return fail(c, JPT_E_INVALID, std::string(call) + ": null output");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, std::string(call) + ": host-only context: jpt_encode runs on the device");
-    if (!c->enc_valid) return fail(c, JPT_E_STATE, std::string(call) + ": no jpt_encode yet");
+    if (!c->enc.valid) return fail(c, JPT_E_STATE, std::string(call) + ": no jpt_encode yet");
     return JPT_OK;
 }
 
@@ -135,7 +135,7 @@ int jpt_get_encoded_info(jpt_ctx* c, jpt_encoded_info* out)
 {
     const int rc = encoded_common(c, "jpt_get_encoded_info", out != nullptr);
     if (rc) return rc;
-    *out = c->enc_info;
+    *out = c->enc.info;
     return JPT_OK;
 }
 
@@ -143,25 +143,19 @@ int jpt_read_encoded(jpt_ctx* c, void* out, size_t capacity)
 {
     int rc = encoded_common(c, "jpt_read_encoded", out != nullptr);
     if (rc) return rc;
-    const size_t bytes = (size_t)c->enc_info.bytes;
+    const size_t bytes = (size_t)c->enc.info.bytes;
     if (capacity < bytes) return fail(c, JPT_E_INVALID, "jpt_read_encoded: capacity is " + std::to_string(capacity) + " bytes and the encoded image has " + std::to_string(bytes));
     HIP_TRY(c, hipSetDevice(c->device));
-    return read_out(c, c->d_encoded.p, bytes, out);
+    return read_out(c, c->enc.d_encoded.p, bytes, out);
 }
 
 int jpt_readback_encoded_begin(jpt_ctx* c)
 {
     const int rc = encoded_common(c, "jpt_readback_encoded_begin", true);
     if (rc) return rc;
-    if (c->enc_readback_pending) return fail(c, JPT_E_STATE, "jpt_readback_encoded_begin: a read-back is already in flight (call jpt_readback_encoded_end)");
+    if (c->enc.read.pending) return fail(c, JPT_E_STATE, "jpt_readback_encoded_begin: a read-back is already in flight (call jpt_readback_encoded_end)");
     HIP_TRY(c, hipSetDevice(c->device));
-    const size_t bytes = (size_t)c->enc_info.bytes;
-    HIP_TRY(c, c->h_enc_pinned.reserve(bytes));
-    if (!c->ev_enc_readback) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_enc_readback, hipEventDisableTiming));
-    if (bytes) HIP_TRY(c, hipMemcpyAsync(c->h_enc_pinned.p, c->d_encoded.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipEventRecord(c->ev_enc_readback, c->stream));
-    c->enc_read_bytes = bytes;
-    c->enc_readback_pending = true;
+    HIP_TRY(c, c->enc.read.begin(c->enc.d_encoded.p, (size_t)c->enc.info.bytes, c->stream));
     return JPT_OK;
 }
 
@@ -169,22 +163,22 @@ int jpt_readback_encoded_end(jpt_ctx* c, void* out, size_t capacity)
 {
     if (!c) return JPT_E_INVALID;
     if (!out) return fail(c, JPT_E_INVALID, "jpt_readback_encoded_end: null output");
-    if (!c->enc_readback_pending) return fail(c, JPT_E_STATE, "jpt_readback_encoded_end: no read-back in flight (call jpt_readback_encoded_begin)");
-    if (capacity < c->enc_read_bytes)   // (the read-back stays in flight: the call may be repeated with room)
+    SplitReadback& rb = c->enc.read;
+    if (!rb.pending) return fail(c, JPT_E_STATE, "jpt_readback_encoded_end: no read-back in flight (call jpt_readback_encoded_begin)");
+    if (capacity < rb.bytes)   // (the read-back stays in flight: the call may be repeated with room)
         return fail(c, JPT_E_INVALID, "jpt_readback_encoded_end: capacity is " + std::to_string(capacity) + " bytes and the read-back in flight has " +
-                                          std::to_string(c->enc_read_bytes));
+                                          std::to_string(rb.bytes));
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->ev_enc_readback));
-    c->enc_readback_pending = false;
-    if (c->enc_read_bytes) std::memcpy(out, c->h_enc_pinned.p, c->enc_read_bytes);
+    HIP_TRY(c, rb.wait());
+    if (rb.bytes) std::memcpy(out, rb.buf.p, rb.bytes);
     return JPT_OK;
 }
 
 void* jpt_device_encoded(jpt_ctx* c, size_t* bytes_out)
 {
-    const bool have = c && c->device >= 0 && c->enc_valid;
-    if (bytes_out) *bytes_out = have ? (size_t)c->enc_info.bytes : 0;
-    return have ? c->d_encoded.p : nullptr;
+    const bool have = c && c->device >= 0 && c->enc.valid;
+    if (bytes_out) *bytes_out = have ? (size_t)c->enc.info.bytes : 0;
+    return have ? c->enc.d_encoded.p : nullptr;
 }
 
 int jpt_get_encode_timing(jpt_ctx* c, float* ms)
@@ -192,10 +186,10 @@ int jpt_get_encode_timing(jpt_ctx* c, float* ms)
     if (!c) return JPT_E_INVALID;
     if (!ms) return fail(c, JPT_E_INVALID, "jpt_get_encode_timing: null output");
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "jpt_get_encode_timing: host-only context: jpt_encode runs on the device");
-    if (!c->enc_valid || !c->enc_timed) return fail(c, JPT_E_STATE, "jpt_get_encode_timing: the last jpt_encode did not run under jpt_set_kernel_timing");
+    if (!c->enc.valid || !c->enc.timed) return fail(c, JPT_E_STATE, "jpt_get_encode_timing: the last jpt_encode did not run under jpt_set_kernel_timing");
     HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipEventSynchronize(c->enc_ev[1]));
-    HIP_TRY(c, hipEventElapsedTime(ms, c->enc_ev[0], c->enc_ev[1]));
+    HIP_TRY(c, hipEventSynchronize(c->enc.ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(ms, c->enc.ev[0], c->enc.ev[1]));
     return JPT_OK;
 }
 

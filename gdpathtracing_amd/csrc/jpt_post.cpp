@@ -232,7 +232,7 @@ int jpt_denoise(jpt_ctx* c)
             return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_history on: the lens radius is > 0 (jpt_set_lens): the history is reprojected through a pinhole");
         if (c->primary.camera_model != JPT_CAMERA_PINHOLE)
             return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_history on: the camera model must be JPT_CAMERA_PINHOLE (jpt_set_camera_model)");
-        if (q.dh_called && q.dh_restarts == c->accum_restarts)
+        if (q.dh_called && q.dh_restarts == c->image.accum_restarts)
             return fail(c, JPT_E_STATE, "jpt_denoise with jpt_set_denoise_history on: the history already holds the frames accumulated since the last reset, and a "
                                         "second call would count them twice (jpt_accum_reset or jpt_denoise_history_reset first)");
     }
@@ -269,23 +269,23 @@ int jpt_denoise(jpt_ctx* c)
                                    std::memcmp(&q.dh_camera.position, &c->camera.position, sizeof c->camera.position) == 0;
             HistoryView view;
             std::memcpy(view.vp, q.dh_camera.vp, sizeof view.vp);
-            launch_denoise_history(s, q.dn_hist, q.dn_params.normal_power_log2, c->width, c->height, c->d_accum.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
+            launch_denoise_history(s, q.dn_hist, q.dn_params.normal_power_log2, c->width, c->height, c->image.d_accum.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
                                    q.d_dn_alb.p, view, same_view, q.dh_have ? prev[0].p : nullptr, q.dh_have ? prev[1].p : nullptr,
                                    q.dh_have ? prev[2].p : nullptr, next[0].p, next[1].p, next[2].p, q.d_dh_iv.p);
             launch_atrous_history(s, q.dn_params, q.dn_var, c->width, c->height, q.d_dh_iv.p, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
                                   q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
         } else if (guided)
-            launch_atrous_variance(s, q.dn_params, q.dn_var, c->width, c->height, 0, c->d_accum.p, q.d_variance.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
+            launch_atrous_variance(s, q.dn_params, q.dn_var, c->width, c->height, 0, c->image.d_accum.p, q.d_variance.p, c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p,
                                    q.d_dn_alb.p, q.d_dn_ping.p, q.d_dn_pong.p, q.d_dn_ldr.p, q.d_dn_var.p);
         else
-            launch_atrous(s, q.dn_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
+            launch_atrous(s, q.dn_params, c->width, c->height, c->image.d_accum.p, (float)c->frame_count, q.d_dn_pos.p, q.d_dn_nrm.p, q.d_dn_alb.p, q.d_dn_ping.p,
                           q.d_dn_pong.p, q.d_dn_ldr.p);
         HIP_TRY(c, hipGetLastError());
     }
     if (history) {
         q.dh_cur ^= 1;
         q.dh_have = q.dh_called = q.dh_read = true;
-        q.dh_restarts = c->accum_restarts;
+        q.dh_restarts = c->image.accum_restarts;
         q.dh_camera = c->camera;
     }
     q.dn_valid = true;
@@ -336,7 +336,7 @@ int jpt_read_denoise_history_f32(jpt_ctx* c, float* integrated4, float* length)
     if (integrated4 && (rc = read_out(c, q.d_dh_iv.p, npx * sizeof(float4), integrated4)) != JPT_OK) return rc;
     if (length) {   // the .w of the (m, N) plane
         if ((rc = staged_read(c, q.d_dh_set[q.dh_cur][0].p, npx * sizeof(float4))) != JPT_OK) return rc;
-        const float4* mn = c->h_read_pinned.as<float4>();
+        const float4* mn = c->image.h_read_pinned.as<float4>();
         for (size_t i = 0; i < npx; i++) length[i] = mn[i].w;
     }
     return JPT_OK;
@@ -425,7 +425,7 @@ int jpt_bake_finish(jpt_ctx* c)
     }
     // On the context's stream, as jpt_denoise: behind the accumulation of every render queued so far, and the accumulation of every
     // later render waits for what it holds.
-    q.lm_result = launch_lightmap_finish(c->stream, q.lm_params, c->width, c->height, c->d_accum.p, (float)c->frame_count, p.d_bake_pos.p, p.d_bake_nrm.p,
+    q.lm_result = launch_lightmap_finish(c->stream, q.lm_params, c->width, c->height, c->image.d_accum.p, (float)c->frame_count, p.d_bake_pos.p, p.d_bake_nrm.p,
                                          q.d_lm_xg.p, q.d_lm_ng.p, q.d_lm_ping.p, q.d_lm_pong.p);
     HIP_TRY(c, hipGetLastError());
     return JPT_OK;
@@ -566,7 +566,7 @@ int jpt_display(jpt_ctx* c)
     // On the context's stream, as jpt_denoise: behind the accumulation of every render queued so far and behind a jpt_denoise queued
     // before it; the accumulation of every later render (and a later jpt_denoise) waits for what it holds.
     if (npx) {
-        launch_display(c->stream, prm, c->width, c->height, denoised ? q.d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count,
+        launch_display(c->stream, prm, c->width, c->height, denoised ? q.d_dn_ping.p : c->image.d_accum.p, denoised ? 1.0f : (float)c->frame_count,
                        q.d_disp_pyramid.p, q.d_disp_f32.p, q.d_disp_ldr.p, q.auto_exposure ? &q.d_meter_state.p->exposure : nullptr);
         HIP_TRY(c, hipGetLastError());
     }
@@ -645,7 +645,7 @@ int jpt_meter(jpt_ctx* c)
     // On the context's stream, as jpt_display: behind the accumulation of every render, a jpt_denoise and a jpt_display queued before
     // it; a later jpt_display with auto-exposure reads the state record behind the resolve.
     const bool first = !q.meter_valid;
-    launch_meter(c->stream, prm, c->width, c->height, denoised ? q.d_dn_ping.p : c->d_accum.p, denoised ? 1.0f : (float)c->frame_count, first, q.d_meter_bins.p,
+    launch_meter(c->stream, prm, c->width, c->height, denoised ? q.d_dn_ping.p : c->image.d_accum.p, denoised ? 1.0f : (float)c->frame_count, first, q.d_meter_bins.p,
                  q.d_meter_state.p);
     HIP_TRY(c, hipGetLastError());
     q.meter_valid = true;
@@ -742,7 +742,7 @@ int jpt_noise_estimate(jpt_ctx* c)
     // without a surface is not counted.
     const PrimaryState& p = c->primary;
     const float4* normal = p.has_bake() && !p.has_cubes() && p.bake_w == c->width && p.bake_h == c->height ? p.d_bake_nrm.p : nullptr;   // (resolve_primary's bake render)
-    launch_noise_estimate(c->stream, q.noise_params, c->width, c->height, c->d_accum.p, q.d_variance.p, c->frame_count, normal, q.d_noise_bins.p, q.d_noise_tiles.p,
+    launch_noise_estimate(c->stream, q.noise_params, c->width, c->height, c->image.d_accum.p, q.d_variance.p, c->frame_count, normal, q.d_noise_bins.p, q.d_noise_tiles.p,
                           q.d_noise_result.p);
     HIP_TRY(c, hipGetLastError());
     q.noise_valid = true;

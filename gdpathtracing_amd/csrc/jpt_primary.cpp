@@ -650,7 +650,7 @@ int jpt_probe_project(jpt_ctx* c, int32_t flags)
     }
     // On the context's stream, as jpt_bake_finish: behind the accumulation of every render queued so far, and the accumulation of every
     // later render waits for what it reads.
-    launch_probe_project(c->stream, p.probe_dev(), c->d_accum.p, (float)c->frame_count, p.d_probe_table.p, p.d_probe_sh.p);
+    launch_probe_project(c->stream, p.probe_dev(), c->image.d_accum.p, (float)c->frame_count, p.d_probe_table.p, p.d_probe_sh.p);
     HIP_TRY(c, hipGetLastError());
     p.sh_valid = true;
     return JPT_OK;
@@ -819,7 +819,7 @@ int jpt_reflection_prefilter(jpt_ctx* c)
     // On the context's stream, as jpt_probe_project: behind the accumulation of every render queued so far, and the accumulation of
     // every later render waits for what it reads.
     if (timed) HIP_TRY(c, hipEventRecord(p.refl_ev[0], c->stream));
-    launch_reflection_chain(c->stream, rd, c->d_accum.p, (float)c->frame_count, p.d_refl_chain.p);
+    launch_reflection_chain(c->stream, rd, c->image.d_accum.p, (float)c->frame_count, p.d_refl_chain.p);
     if (timed) HIP_TRY(c, hipEventRecord(p.refl_ev[1], c->stream));
     launch_reflection_prefilter(c->stream, rd, p.d_refl_chain.p, p.d_refl_table.p, p.d_refl_lvl.p, p.d_refl_out.p);
     if (timed) HIP_TRY(c, hipEventRecord(p.refl_ev[2], c->stream));

@@ -534,12 +534,12 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
             one.frame_count = c->frame_count + (uint32_t)f + 1;
             one.n_frames = 1;
             one.depth_frame = 0;
-            launch_ref_frame(s, c->ds, one, c->camera, c->d_accum.p, c->d_ldr.p, depth_img, cnt, r.lighting, r.primary);
+            launch_ref_frame(s, c->ds, one, c->camera, c->image.d_accum.p, c->image.d_ldr.p, depth_img, cnt, r.lighting, r.primary);
         }
         return JPT_OK;
     }
     if (p.route == LaunchPlan::kStream) {
-        launch_wf2_render(s, c->ds, fp, c->camera, c->pipe.slot[0].workspace.p, c->d_accum.p, c->d_ldr.p, depth_img, cnt,
+        launch_wf2_render(s, c->ds, fp, c->camera, c->pipe.slot[0].workspace.p, c->image.d_accum.p, c->image.d_ldr.p, depth_img, cnt,
                           c->kernel_timing ? c->pipe.trace_events.data() : nullptr, r, p.groups, p.chain, c->pipe.group_streams);
         return JPT_OK;
     }
@@ -577,7 +577,7 @@ int launch_render(jpt_ctx* c, const LaunchPlan& p, const FrameParams& fp, Wf2Ren
     // kernels of a render (the hardware runs a handful of queues side by side; a busy `s` would be one more)
     HIP_TRY(c, hipEventRecord(ps.ev_paths_done, s));
     r.before_acc = ps.ev_paths_done;
-    launch_wf2_render(ps.stream, c->ds, fp, c->camera, ps.workspace.p, c->d_accum.p, c->d_ldr.p, depth_img, nullptr, nullptr, r,
+    launch_wf2_render(ps.stream, c->ds, fp, c->camera, ps.workspace.p, c->image.d_accum.p, c->image.d_ldr.p, depth_img, nullptr, nullptr, r,
                       p.groups, p.chain, c->pipe.group_streams);
     HIP_TRY(c, hipEventRecord(ps.ev_acc_done, ps.stream));
     HIP_TRY(c, hipStreamWaitEvent(s, ps.ev_acc_done, 0));
@@ -663,7 +663,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     int rc = validate_render(c, n_frames);
     if (rc != JPT_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    c->assembled = c->assembled_ldr = false;
+    restart_sum(c, kSumRendered);   // (an assembled image is of the frames before this render)
     const bool wavefront = c->kernel_variant == JPT_KERNEL_WAVEFRONT && !c->debug_steps;   // (DEBUG_STEPS exists in the audit kernel only)
     // the depth image (main.glsl:432,435) has one reader, the temporal pass: off when the host said so (jpt_set_outputs)
     const bool want_depth = (c->outputs & JPT_OUTPUT_DEPTH) != 0u || c->denoise == JPT_DENOISE_TEMPORAL;
@@ -685,9 +685,9 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
     if ((rc = prepare_render(c, fp, counted, wavefront, r)) != JPT_OK) return rc;
     bool pipelined = false;
     if (c->local_rows > 0 && c->width > 0 && n_frames > 0) {
-        c->depth_valid = want_depth;
+        c->image.depth_valid = want_depth;
         const LaunchPlan p = plan_launch(c, fp, r, counted, blocking, kPlanDevice);
-        rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->d_depth.p : nullptr);
+        rc = launch_render(c, p, fp, r, counted ? c->d_counters.p : nullptr, want_depth ? c->image.d_depth.p : nullptr);
         if (rc != JPT_OK) return rc;
         if (r.bake_dir) c->post.bake_dir_valid = true;
         if (r.variance) c->post.variance_valid = true;
@@ -695,7 +695,7 @@ int do_render_batch(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bo
         if (c->denoise == JPT_DENOISE_TEMPORAL) {
             // TemporalReprojection::render's dispatch (temporal_reprojection.cpp:71): screen + depth of this frame in,
             // blended history and the displayed screen out
-            launch_temporal(c->stream, c->reproj.temporal, c->d_ldr.p, c->d_depth.p, c->reproj.d_hist1.p, c->reproj.d_hist2.p);
+            launch_temporal(c->stream, c->reproj.temporal, c->image.d_ldr.p, c->image.d_depth.p, c->reproj.d_hist1.p, c->reproj.d_hist2.p);
             c->reproj.hist_written = (c->reproj.temporal.frame_count % 2u) == 0u ? c->reproj.d_hist2.p : c->reproj.d_hist1.p;
         }
         HIP_TRY(c, hipGetLastError());
