@@ -1361,7 +1361,7 @@ struct Flattener {
     // its size, not 2^depth), a node met again while its own subtree is still open is a cycle (kOpen: an error --
     // main.glsl:270-350 would never leave it), and no chain is followed deeper than kMaxDepth frames of the host
     // stack.  That loses nothing: the kernels' traversal stack holds fewer than 100 entries and a tree that could need
-    // more is refused after the flatten (compute_stack_need, jpt_capi.cpp upload_scene), so a tree this deep was never
+    // more is refused after the flatten (compute_stack_need, jpt_scene.cpp upload_scene), so a tree this deep was never
     // going to be accepted; the bound only keeps collapse4 / need2 / need4, which recurse over what is made here, shallow.
     enum : uint8_t { kUnseen = 0, kOpen = 1, kDone = 2 };
     static constexpr uint32_t kMaxDepth = 512u;

@@ -1,8 +1,10 @@
 // jpt_ctx.h -- the context behind the C ABI of include/jpt.h, with the helpers it is made of: private to the host layer
-// (jpt_capi.cpp, jpt_image.cpp, jpt_render.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp, jpt_encode.cpp).
+// (jpt_capi.cpp, jpt_scene.cpp, jpt_query.cpp, jpt_image.cpp, jpt_render.cpp, jpt_scene_update.cpp, jpt_lighting.cpp, jpt_primary.cpp, jpt_post.cpp,
+// jpt_encode.cpp).
 #pragma once
 #include "../../include/jpt.h"
 
+#include <chrono>
 #include <map>
 
 #include "jpt_builder.h"
@@ -257,7 +259,7 @@ struct LightingState {
     bool env_tables = false;
     float env_total = 0.0f;
     // importance sampling of the emissive triangles (jpt_set_light_sampling): the mode, the context's like the map's; the emitters
-    // (instance, triangle pairs from c->ref, host) and their device tables -- both made at the first render that needs them after
+    // (instance, triangle pairs from c->scene.ref, host) and their device tables -- both made at the first render that needs them after
     // the scene changed (light_cand_stale: its instances or materials; light_table_stale: also its geometry, refits included)
     int32_t light_sampling = JPT_LIGHT_SAMPLING_BRDF;
     std::vector<uint32_t> light_cand_h;
@@ -266,7 +268,7 @@ struct LightingState {
     DevBuf<float4> d_light_tri;
     DevBuf<float> d_light_cdf, d_light_marg;   // per emitter; the marginal CDF's n_blocks entries, then the total power
     // material extensions (jpt_set_material_extensions): the flags, the context's like the modes; and whether some material of the
-    // host's mirror (c->ref.materials) has a sanitised transmission > 0, scanned whenever the materials may have changed
+    // host's mirror (c->scene.ref.materials) has a sanitised transmission > 0, scanned whenever the materials may have changed
     uint32_t material_ext = JPT_MATERIAL_EXT_NONE;
     bool transmissive_materials = false;
 };
@@ -531,7 +533,7 @@ struct EncodeState {
 };
 
 // What the context holds of the calls that change a committed scene on the device without a new commit (the refits, rebuilds, mesh updates,
-// rigs and poses of jpt_scene_update.cpp, and its two debug readers).  The uploads (jpt_capi.cpp) put it back through host_uploaded; the
+// rigs and poses of jpt_scene_update.cpp, and its two debug readers).  The uploads (jpt_scene.cpp) put it back through host_uploaded; the
 // renders read cur_set through the view, wait for ev_refit_done and refuse on refit_active / mesh_deformed.
 struct SceneUpdates {
     // device refit of the instance level (jpt_scene_refit_tlas)
@@ -545,10 +547,10 @@ struct SceneUpdates {
     uint64_t refit_wait_seq = 0;
     DevBuf<uint32_t> d_tlas4_order, d_tlas4_levels;
     bool refit_active = false;         // the device's instance level is ahead of the host mirrors (and of the other kernels' arrays)
-    bool cull_boxes_current = true;    // c->wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
+    bool cull_boxes_current = true;    // c->scene.wide.tlas_nodes4 holds the boxes of the copy new renders read (sky cull)
     std::vector<uint32_t> tlas4_order_h, tlas4_levels_h;   // the refit schedule, host copy
     // a new topology made on the device (jpt_scene_rebuild_tlas): the template of the scene's instance count with its schedule and the
-    // sort's buffers, made at the first rebuild of that count and kept.  After a rebuild c->wide.tlas_nodes4 / tlas_root4 / stack_need4
+    // sort's buffers, made at the first rebuild of that count and kept.  After a rebuild c->scene.wide.tlas_nodes4 / tlas_root4 / stack_need4
     // and the schedule's host copy above are the template's, and the refits run over tmpl_order / tmpl_levels (topo_rebuilt), until
     // the next upload.  topo_gen counts the rebuilds since the last upload; set_topo_gen[k]: the one whose topology the TLAS tail of
     // copy k holds (a refit into a copy that is behind first copies the current copy's tail: queue_instance_refit).
@@ -575,7 +577,7 @@ struct SceneUpdates {
     // (the template of its triangle count needs more records than the commit's tree has), reserved at the mesh's first rebuild and kept
     // until the next whole upload, with the template's child words, its schedule (absolute record indices) and level starts; the old range
     // is no longer referenced.  mesh_need: the stack need of every mesh's tree
-    // as it is now (made at the first rebuild: c->wide.stack_need4 is the TLAS need + 1 + the largest of them).  d_mesh_sort: the sort's
+    // as it is now (made at the first rebuild: c->scene.wide.stack_need4 is the TLAS need + 1 + the largest of them).  d_mesh_sort: the sort's
     // working set, of the largest mesh rebuilt so far (jpt_mesh_rebuild.h: mesh_sort_words).
     struct MeshRegion {
         DevBuf<int32_t> d_child;
@@ -592,7 +594,7 @@ struct SceneUpdates {
     DevBuf<char> d_mesh_in;                  // the staged update: bounds header, vertices, normals
     StagingRing mesh_stage;            // pinned staging for the updates (header, vertices, normals, transforms)
     hipEvent_t ev_mesh_drain = nullptr;
-    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->ref, c->wide) are stale until the next upload
+    bool mesh_deformed = false;   // a mesh was deformed on the device: the host mirrors (c->scene.ref, c->scene.wide) are stale until the next upload
     // posing committed meshes on the device (jpt_scene_set_mesh_rig / jpt_scene_pose_mesh): per rigged mesh the rig's layout and, when
     // an instance names the mesh, its block on the device (jpt_kernels_skin.hip); dropped by jpt_scene_begin and every upload
     struct MeshRig {
@@ -600,7 +602,7 @@ struct SceneUpdates {
         DevBuf<char> d_rig;   // empty for a mesh no instance names
     };
     std::map<uint32_t, MeshRig> mesh_rigs;
-    // The one place that says which state a host upload puts back (finish_upload, jpt_capi.cpp): of the whole scene `w` (`whole`) or of
+    // The one place that says which state a host upload puts back (finish_upload, jpt_scene.cpp): of the whole scene `w` (`whole`) or of
     // its instance level only, which leaves what is known of the meshes.  A scene without four-child records uploads no tails:
     // tlas4_cap and cull_boxes_current then stay what the scene before it left.
     void host_uploaded(bool whole, const WideScene& w)
@@ -628,16 +630,96 @@ struct SceneUpdates {
         if (ev_mesh_drain) (void)hipEventDestroy(ev_mesh_drain);
     }
 };
-// the view the kernels take (c->ds) of the scene's device arrays, with the instance level of the copy new renders read (jpt_capi.cpp)
+// The scene on the host: the builder of the last jpt_scene_begin, the scene in the reference's layout (ref) and flattened (wide), and what
+// says which calls it admits.  Written by the entry points of jpt_scene.cpp and by move_instances (jpt_scene_update.cpp: the builder's
+// transforms, tlas_dirty); read by every file of the host layer -- the renders and post stages ask device_ready, the lighting reads ref.
+// The state, row by row as the code has it ("." stays; rigs: drop_mesh_rigs, the rigs and regions of SceneUpdates; ms: stats.last_build_ms;
+// refit / deformed: upd.refit_active / upd.mesh_deformed, put back by host_uploaded, which a host-only context never reaches -- there both stay false):
+//   call                                     building  host_ready  device_ready  from_commit  tlas_dirty  tree       upload_note   rigs     refit  deformed  ms
+//   jpt_scene_begin                          true      .           .             .            .           .          .             dropped  .      .         .
+//   jpt_scene_commit, accepted               false     true        true (1)      true         false       builder's  ""            dropped  false  false     written
+//     refused by the builder                 . (true)  false       false         .            .           .          .             dropped  .      .         .
+//     refused by validate_ref_scene          . (true)  false       false         .            .           builder's  .             dropped  .      .         .
+//     refused as too deep (or by flatten)    false     false       false         true         .           builder's  ""            dropped  .      .         written
+//   jpt_scene_upload_reference_layout
+//     native                                 .         true        true (1)      false        false       REACH      "" (2)        dropped  false  false     written
+//     as given                               .         true        true (1)      false        false       AS_GIVEN   why           dropped  false  false     written
+//     refused before the arrays are taken    .         .           .             .            .           .          .             .        .      .         .
+//     refused after, by validate_ref_scene   .         false       false         false        .           .          ""            dropped  .      .         .
+//     refused after, as too deep / flatten   .         false       false         false        .           as above   as above      dropped  .      .         written
+//   jpt_scene_share (the destination)        false     true        true (1)      source's     false       source's   source's      dropped  false  false     written
+//     (the source, when from_commit and tlas_dirty or refit: jpt_scene_update_tlas below; refused: the destination is not touched)
+//   jpt_scene_set_instance_transform         .         .           .             .            true        .          .             .        .      .         .
+//   jpt_scene_update_tlas, nothing dirty     .         .           .             .            .           .          .             .        .      .         .
+//     accepted                               .         .           .             .            false       .          .             .        false  .         written
+//     refused by the builder                 .         false       false         .            .           .          .             kept     .      .         .
+//     refused as too deep                    .         false       false         .            .           .          .             kept     .      .         written
+//     refused by reflatten_tlas              .         .           .             .            .           .          .             .        .      .         written
+//   jpt_scene_update_reference_tlas
+//     accepted                               .         .           .             .            .           .          .             .        false  .         written
+//     refused before the arrays are taken    .         .           .             .            .           .          .             .        .      .         . (3)
+//     rejected and rolled back               .         true        true (1)      .            .           .          .             .        false  .         written
+//     rolled back, the way back failed       .         false       false         .            .           .          .             kept     (4)    .         written
+//   jpt_scene_refit_tlas, _rebuild_tlas      .         .           .             .            true        .          .             .        true   .         written
+//     (without four-child records on the device: jpt_scene_update_tlas; a refusal after the device check -- the rebuild's limits, a device
+//     error -- leaves tlas_dirty true and the builder's transforms set, and writes no ms)
+//   jpt_scene_update_mesh, _rebuild_mesh,    .         .           .             .            .           .          .             . (5)    true   true      written
+//   jpt_scene_pose_mesh, _pose_mesh_rebuild
+// (1) false on a host-only context.  (2) or why the arrays are walked as given after all, with tree AS_GIVEN.  (3) the native route's
+// refusal by native_instances_from_uploaded comes after t0 was taken and still writes nothing.  (4) whatever the failed upload left.
+// (5) jpt_scene_rebuild_mesh adds the mesh's region.  A device error (JPT_E_DEVICE) leaves the flags of the step it
+// stopped at: in an upload of the whole scene host_ready true and device_ready false, in one of the instance level both as they were.
+struct HostScene {
+    SceneBuilder builder;
+    RefScene ref;
+    WideScene wide;
+    bool building = false;       // between jpt_scene_begin and the commit that is accepted (or refused too deep)
+    bool host_ready = false;     // ref / wide hold a complete scene (also true on host-only contexts)
+    bool device_ready = false;   // ... and jpt_ctx::dev holds it: what a render, a post stage and a query ask
+    bool from_commit = false;    // the scene came from jpt_scene_commit: builder holds its meshes and transforms
+    bool tlas_dirty = false;     // builder's transforms are ahead of ref's instance level
+    int32_t tree = JPT_TREE_NONE;   // the JPT_TREE_* of the scene in ref (jpt_scene_tree_kind answers it once host_ready)
+    int32_t upload_mode = JPT_UPLOAD_NATIVE_TREE;  // jpt_set_upload_mode
+    // jpt_scene_upload_note and jpt_scene_ties_exact hand out their c_str(): they live as long as the context
+    std::string upload_note;     // why the last reference-layout upload is walked as given (empty: it is not)
+    std::string ties_note;       // why exact distance ties fall to the native tree's order (empty: they are decided exactly)
+    // jpt_scene_set_materials / _set_textures, until the commit copies them into ref
+    std::vector<RefMaterial> pending_materials;
+    std::vector<uint8_t> pending_tex;
+    int32_t pending_tex_res = 0, pending_layers = 0;
+
+    // the kernels walk the four-child records of the native tree (the native builder's trees and native uploads); reference-exact and
+    // as-given trees keep the two-child records so the kernels visit them node for node like main.glsl (event counters equal the oracle's)
+    bool walks_nodes4() const { return tree == JPT_TREE_NATIVE_REACH || tree == JPT_TREE_NATIVE_WATERTIGHT; }
+    // what a traversal of the scene in `wide` could need of the kernels' stack
+    uint32_t stack_need() const { return walks_nodes4() ? wide.stack_need4 : wide.stack_need2; }
+    void not_ready() { host_ready = device_ready = false; }   // (the rigs stay: scene_left, jpt_scene.cpp, is the whole transition)
+};
+// A tree deeper than the kernels' stack, refused where it is made (`after`: "", " after the TLAS update", " after the TLAS rebuild",
+// " after the mesh rebuild"; jpt_scene.cpp, with the other transitions and refusals the scene's calls share)
+int too_deep(jpt_ctx* c, uint32_t need, const char* after);
+// host time since t0, for stats.last_build_ms (no scope guard: the early returns of the calls that time themselves write nothing)
+inline double ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+// the view the kernels take (c->ds) of the scene's device arrays, with the instance level of the copy new renders read (jpt_scene.cpp)
 void set_scene_view(jpt_ctx* c);
 // the rigs of jpt_scene_set_mesh_rig, and the regions of jpt_scene_rebuild_mesh, leave with the scene they were set for, behind the refit stream (jpt_scene_update.cpp)
 void drop_mesh_rigs(jpt_ctx* c);
 // The refusals these calls open with: no context (JPT_E_INVALID), no scene from jpt_scene_commit ("<call><what>"); for the two trees a
 // JPT_BUILD_REFERENCE_EXACT commit (`exact`: the call's sentence, null: "<call><what>" again); for kWatertightTree a JPT_BUILD_SAH commit (`sah`,
 // likewise).  on_device, after the argument checks: a host-only context, in the call's words, and with `scene` "no scene on the device"
+// (jpt_scene.cpp)
 enum SceneNeed { kFromCommit, kNativeTree, kWatertightTree };
 int needs_scene(jpt_ctx* c, SceneNeed need, const char* call, const char* what, const char* exact = nullptr, const char* sah = nullptr);
 int on_device(jpt_ctx* c, const char* host_only, bool scene);
+
+// jpt_query_rays / jpt_query_pixels (host forms, jpt_query.cpp): one chunk's rays, hits and occlusion bytes on the device, grow-only.  The
+// host side of a chunk borrows the image's pinned read buffer (image.h_read_pinned): a query and a blocking read-back never overlap.
+struct QueryState {
+    DevBuf<char> d_query;
+};
 
 }  // namespace jpt
 
@@ -648,20 +730,7 @@ struct jpt_ctx {
     hipStream_t own_stream = nullptr, stream = nullptr;
     std::string error;
 
-    // host scene
-    SceneBuilder builder;
-    RefScene ref;
-    WideScene wide;
-    bool building = false, scene_ready = false, tlas_dirty = false;
-    int32_t tree = JPT_TREE_NONE;   // the JPT_TREE_* of the scene in c->ref (jpt_scene_tree_kind answers it once host_scene_ready)
-    bool host_scene_ready = false;  // c->ref / c->wide hold a complete scene (also true on host-only contexts)
-    bool from_commit = false;       // the scene came from jpt_scene_commit: c->builder holds its meshes and transforms
-    int32_t upload_mode = JPT_UPLOAD_NATIVE_TREE;  // jpt_set_upload_mode
-    std::string upload_note;        // why the last reference-layout upload is walked as given (empty: it is not)
-    std::string ties_note;          // why exact distance ties fall to the native tree's order (empty: they are decided exactly)
-    std::vector<RefMaterial> pending_materials;
-    std::vector<uint8_t> pending_tex;
-    int32_t pending_tex_res = 0, pending_layers = 0;
+    HostScene scene;          // the builder, the scene on the host, its flags and notes (jpt_scene.cpp; the table: HostScene)
 
     // device scene
     SceneBufs dev;
@@ -691,16 +760,10 @@ struct jpt_ctx {
     SceneUpdates upd;         // the copies, streams, schedules and flags of the calls that change a committed scene on the device (jpt_scene_update.cpp)
     EncodeState enc;          // jpt_encode's buffer, what it holds, its timing and its split read-back (jpt_encode.cpp)
 
-    // jpt_query_rays / jpt_query_pixels (host forms): one chunk's rays, hits and occlusion bytes on the device, grow-only
-    DevBuf<char> d_query;
+    QueryState query;         // the host forms' staging on the device (jpt_query.cpp)
 
     jpt_stats stats;
 };
-
-// the kernels walk the four-child records of the native tree (the native builder's trees and native uploads); reference-exact and
-// as-given trees keep the two-child records so the kernels visit them node for node like main.glsl (event counters equal the
-// oracle's)
-static inline bool walks_nodes4(const jpt_ctx* c) { return c->tree == JPT_TREE_NATIVE_REACH || c->tree == JPT_TREE_NATIVE_WATERTIGHT; }
 
 static inline int fail(jpt_ctx* c, int code, const std::string& msg)
 {

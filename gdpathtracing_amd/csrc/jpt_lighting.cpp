@@ -10,13 +10,13 @@
 
 namespace {
 
-// The emitters of c->ref, instance-major, each instance's triangles (the leaves under its BLAS root, each triangle once) in
+// The emitters of c->scene.ref, instance-major, each instance's triangles (the leaves under its BLAS root, each triangle once) in
 // ascending index: those whose Le (light_emission) has lum(Le) > 0.  True when there is one.
 bool light_candidates(jpt_ctx* c)
 {
     LightingState& l = c->lighting;
     if (!l.light_cand_stale) return !l.light_cand_h.empty();
-    const RefScene& r = c->ref;
+    const RefScene& r = c->scene.ref;
     l.light_cand_h.clear();
     l.light_cand_stale = false;
     l.light_cand_uploaded = false;
@@ -123,7 +123,7 @@ void lights_stale(jpt_ctx* c, bool listed)
     if (!listed) return;
     c->lighting.light_cand_stale = true;
     bool any = false;
-    for (const RefMaterial& m : c->ref.materials) any = any || material_transmission(m.padding[0]) > 0.0f;
+    for (const RefMaterial& m : c->scene.ref.materials) any = any || material_transmission(m.padding[0]) > 0.0f;
     c->lighting.transmissive_materials = any;
 }
 
@@ -134,11 +134,11 @@ Lighting lighting_bound(const jpt_ctx* c)
     if (c->debug_steps) return lg;   // (DEBUG_STEPS counts the audit kernel's steps: its render sees no light)
     // (a black map's MIS render is the BRDF-mode render -- no map samples, every weight 1: the *_env kernels)
     const bool mis = l.env_set && l.env_sampling == JPT_ENV_SAMPLING_MIS && l.env_tables && l.env_total > 0.0f;
-    const bool emitters = l.light_sampling == JPT_LIGHT_SAMPLING_MIS && c->device >= 0 && c->scene_ready && (l.light_cand_stale || !l.light_cand_h.empty());
+    const bool emitters = l.light_sampling == JPT_LIGHT_SAMPLING_MIS && c->device >= 0 && c->scene.device_ready && (l.light_cand_stale || !l.light_cand_h.empty());
     lg.env_mode = mis ? 2 : (l.env_set ? 1 : 0);
     lg.kind = emitters ? Lighting::kEmitters : (mis ? Lighting::kMapMis : (l.env_set ? Lighting::kMap : Lighting::kSky));
     // (the extension words are read only when the flag says so AND some material then transmits: otherwise today's kernels)
-    lg.transmissive = (l.material_ext & JPT_MATERIAL_EXT_TRANSMISSION) != 0u && l.transmissive_materials && c->device >= 0 && c->scene_ready;
+    lg.transmissive = (l.material_ext & JPT_MATERIAL_EXT_TRANSMISSION) != 0u && l.transmissive_materials && c->device >= 0 && c->scene.device_ready;
     return lg;
 }
 
@@ -328,7 +328,7 @@ static int debug_lights(jpt_ctx* c, LightDev& out)
 {
     out = LightDev{};
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context: the emitter tables are on the device");
-    if (!c->scene_ready) return fail(c, JPT_E_STATE, "no scene");
+    if (!c->scene.device_ready) return fail(c, JPT_E_STATE, "no scene");
     HIP_TRY(c, hipSetDevice(c->device));
     if (!light_candidates(c)) return JPT_OK;
     const int rc = ensure_light_tables(c);

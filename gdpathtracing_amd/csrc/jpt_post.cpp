@@ -219,7 +219,7 @@ int jpt_denoise(jpt_ctx* c)
     if (!c) return JPT_E_INVALID;
     const int rc = reads_sum(c, "jpt_denoise", " filters the progressive accumulation", "host-only context: jpt_denoise runs on the device");
     if (rc != JPT_OK) return rc;
-    if (!c->scene_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
+    if (!c->scene.device_ready) return fail(c, JPT_E_STATE, "jpt_denoise: no scene");
     if (!c->params_set || !c->camera_set) return fail(c, JPT_E_STATE, "jpt_denoise: jpt_set_params / jpt_set_camera not called");
     if (c->frame_count == 0) return fail(c, JPT_E_STATE, "jpt_denoise: no frame accumulated since the last reset");
     CamModelDev cm;   // (the guides are the first hits of the view the renders took: jpt_set_camera_model)

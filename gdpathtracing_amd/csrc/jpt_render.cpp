@@ -1,7 +1,7 @@
 // jpt_render.cpp -- how a render is planned, launched, pipelined and timed (RenderPipe, jpt_ctx.h): the three render entry points and what
 // they are made of -- validate, prepare, plan (plan_launch: every measured scheduling rule, with the measurements), launch, read back -- the
 // pipeline slots and the frame groups' helper streams, the policy calls that shape them (jpt_set_stream_priority, jpt_set_memory_policy,
-// jpt_get_workspace_bytes, jpt_renders_in_flight, jpt_set_kernel_timing), jpt_sync, and the temporal pass's part of a render (TemporalState).
+// jpt_get_workspace_bytes, jpt_renders_in_flight, jpt_set_kernel_timing), jpt_sync, and the temporal pass's parameters (jpt_set_temporal_params) and part of a render (TemporalState).
 #include "jpt_ctx.h"
 
 #include <algorithm>
@@ -80,8 +80,8 @@ void compute_sky_cull(const jpt_ctx* c, SkyCull& out)
     // the boxes: children of the TLAS root record in the layout the kernels walk
     double lo[4][3], hi[4][3];
     int n = 0;
-    const WideScene& w = c->wide;
-    const bool use4 = walks_nodes4(c);
+    const WideScene& w = c->scene.wide;
+    const bool use4 = c->scene.walks_nodes4();
     if (w.instances.empty()) return;
     if (use4) {
         if (w.tlas_root4 < 0 || (size_t)w.tlas_root4 >= w.tlas_nodes4.size()) return;  // the root is a single instance
@@ -197,7 +197,7 @@ void summed_stats(jpt_stats& a, const jpt_stats& b, F f)
 int do_render(jpt_ctx* c, int32_t n_frames, uint32_t first_frame_index, bool counted, bool blocking)
 {
     if (!c) return JPT_E_INVALID;
-    if (c->device < 0 || !c->scene_ready || !c->params_set || !c->camera_set || n_frames <= 0)
+    if (c->device < 0 || !c->scene.device_ready || !c->params_set || !c->camera_set || n_frames <= 0)
         return do_render_batch(c, n_frames, first_frame_index, counted, blocking);  // reports the error / no-op
     // a budget the caller set is a cap, not a hint: one frame is the smallest batch there is
     if (c->pipe.workspace_budget && c->kernel_variant != JPT_KERNEL_REFERENCE_LAYOUT && !c->debug_steps) {
@@ -336,7 +336,7 @@ bool six_queues_probe(jpt_ctx* c)
         for (int k = 0; k < kProbe; k++) launch_queue_spin(c->pipe.slot[k].stream, ticks);
         for (int k = 0; k < kProbe; k++)
             if (hipStreamSynchronize(c->pipe.slot[k].stream) != hipSuccess) return false;
-        best = std::min(best, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+        best = std::min(best, ms_since(t0));
     }
     if (hipGetLastError() != hipSuccess) return false;
     c->pipe.six_queues = best < 0.4 * 1.6 ? 1 : 0;
@@ -425,9 +425,9 @@ LaunchPlan jpt::plan_launch(jpt_ctx* c, const FrameParams& fp, const Wf2Render& 
     // past the caches, which are bound by the latency of their fetches and want every wave they can get (1 M
     // triangles, 2 spp: 9.49 -> 9.93 ms): one segment per block (profiles/r03/r03ao_lone_chain.txt).
     const uint64_t window_paths = ((uint64_t)c->width * (uint64_t)c->local_rows - wf2_pixels_outside_window(r.cull, fp)) * (uint64_t)fp.n_frames;
-    const size_t walked_bytes = c->wide.blas_nodes4.size() * sizeof(WideNodeQ) + c->wide.tris.size() * sizeof(WideTri);
+    const size_t walked_bytes = c->scene.wide.blas_nodes4.size() * sizeof(WideNodeQ) + c->scene.wide.tris.size() * sizeof(WideTri);
     const bool small = window_paths <= 1500000u && walked_bytes <= ((size_t)32 << 20);
-    p.chain = (p.groups == 2 || (walks_nodes4(c) && small)) ? 2 : 1;
+    p.chain = (p.groups == 2 || (c->scene.walks_nodes4() && small)) ? 2 : 1;
     return p;
 }
 
@@ -460,7 +460,7 @@ int validate_render(jpt_ctx* c, int32_t n_frames)
 {
     if (!c) return JPT_E_INVALID;
     if (c->device < 0) return fail(c, JPT_E_DEVICE, "host-only context (JPT_DEVICE_HOST_ONLY) cannot render: there is no CPU fallback");
-    if (!c->scene_ready) return fail(c, JPT_E_STATE, "no scene: call jpt_scene_upload_reference_layout or jpt_scene_commit first");
+    if (!c->scene.device_ready) return fail(c, JPT_E_STATE, "no scene: call jpt_scene_upload_reference_layout or jpt_scene_commit first");
     if (!c->params_set) return fail(c, JPT_E_STATE, "jpt_set_params not called");
     if (!c->camera_set) return fail(c, JPT_E_STATE, "jpt_set_camera not called");
     if (n_frames < 0) return fail(c, JPT_E_INVALID, "n_frames < 0");
@@ -783,6 +783,15 @@ int jpt_set_kernel_timing(jpt_ctx* c, int32_t enable)
     if (!c) return JPT_E_INVALID;
     c->kernel_timing = enable != 0;
     if (!c->kernel_timing) c->pipe.trace_events_used = 0;
+    return JPT_OK;
+}
+
+int jpt_set_temporal_params(jpt_ctx* c, const void* render_parameters)
+{
+    if (!c) return JPT_E_INVALID;
+    if (!render_parameters) return fail(c, JPT_E_INVALID, "null RenderParameters");
+    std::memcpy(&c->reproj.temporal, render_parameters, sizeof(RefTemporalParams));
+    c->reproj.temporal_set = true;
     return JPT_OK;
 }
 

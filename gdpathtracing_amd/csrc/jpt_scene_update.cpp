@@ -1,6 +1,7 @@
 // jpt_scene_update.cpp -- the calls that change a committed scene on the device without a new commit (jpt_scene_refit_tlas, jpt_scene_rebuild_tlas,
 // jpt_scene_update_mesh, jpt_scene_rebuild_mesh, jpt_scene_set_mesh_rig, jpt_scene_clear_mesh_rig, jpt_scene_pose_mesh, jpt_scene_pose_mesh_rebuild) and the two that read their results (jpt_debug_mesh_records,
-// jpt_debug_tlas_records), over SceneUpdates (jpt_ctx.h).  The host route (jpt_scene_update_tlas) is jpt_capi.cpp's, with the uploads it is made of.
+// jpt_debug_tlas_records), over SceneUpdates (jpt_ctx.h).  The host route (jpt_scene_update_tlas) is jpt_scene.cpp's, with the uploads it is made of
+// and the refusals these calls open with (needs_scene, on_device).
 #include "jpt_ctx.h"
 
 #include <cfloat>
@@ -10,23 +11,6 @@
 #include "jpt_instance_math.h"
 #include "jpt_mesh_math.h"
 #include "jpt_mesh_rebuild.h"
-
-int jpt::needs_scene(jpt_ctx* c, SceneNeed need, const char* call, const char* what, const char* exact, const char* sah)
-{
-    if (!c) return JPT_E_INVALID;
-    const std::string own = std::string(call) + what;
-    if (!c->host_scene_ready || c->building || !c->from_commit) return fail(c, JPT_E_STATE, own);
-    if (need != kFromCommit && !walks_nodes4(c)) return fail(c, JPT_E_STATE, exact ? exact : own);
-    if (need == kWatertightTree && c->tree != JPT_TREE_NATIVE_WATERTIGHT) return fail(c, JPT_E_STATE, sah ? sah : own);
-    return JPT_OK;
-}
-
-int jpt::on_device(jpt_ctx* c, const char* host_only, bool scene)
-{
-    if (c->device < 0) return fail(c, JPT_E_DEVICE, host_only);
-    if (scene && (!c->scene_ready || !c->ds.use4)) return fail(c, JPT_E_STATE, "no scene on the device");
-    return JPT_OK;
-}
 
 namespace {
 
@@ -100,7 +84,7 @@ int ensure_instance_copies(jpt_ctx* c)
 // copy of the instance level that new renders do not read yet, on the refit stream; the context's stream and every render queued
 // from now on wait for it (refit_wait_seq).  The BLAS root boxes are read from the reference-layout nodes.
 // `rebuild_sorted` (jpt_scene_rebuild_tlas; ensure_tlas_template has run): the copy also gets a new topology, the template's over the
-// instances sorted on the device, and the host's mirror of the records (c->wide, the schedule) becomes the template over
+// instances sorted on the device, and the host's mirror of the records (c->scene.wide, the schedule) becomes the template over
 // rebuild_sorted, boxes not yet refitted.  Every later refit then runs over the template's schedule, and one into a copy whose tail
 // still holds an older topology first copies the current copy's tail.
 int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances, const uint32_t* rebuild_sorted = nullptr)
@@ -117,7 +101,7 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
     c->upd.set_retired_valid[c->upd.cur_set] = true;
     hipStream_t rs = c->upd.refit_stream;
     if (c->upd.set_retired_valid[next]) HIP_TRY(c, hipStreamWaitEvent(rs, c->upd.ev_set_retired[next], 0));
-    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->ref.inst_cut_boxes.empty();
+    const bool cuts = c->scene.ref.inst_cut_range.size() == 2 * (size_t)n_instances && !c->scene.ref.inst_cut_boxes.empty();
     Tlas4RefitArgs a;
     a.transforms12 = dev_view;
     a.n_instances = n_instances;
@@ -129,9 +113,9 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
     a.cut_range = cuts ? b.cut_range.p : nullptr;
     a.nodes4 = b.nodes4.p;
     a.nodesq = b.nodesq.p;
-    a.n_blas_records = (uint32_t)c->upd.tail_first(c->wide, next);
+    a.n_blas_records = (uint32_t)c->upd.tail_first(c->scene.wide, next);
     if (rebuild_sorted) {
-        WideScene& w = c->wide;
+        WideScene& w = c->scene.wide;
         const uint32_t blas_need = w.stack_need4 - 1u - stack_need4_under(w.tlas_nodes4, w.tlas_root4);
         tlas_template_records(c->upd.tlas_tmpl, rebuild_sorted, w.tlas_nodes4);
         w.tlas_root4 = 0;
@@ -145,10 +129,10 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
         a.sort_scratch = c->upd.d_tlas_sort_keys.p;
     } else if (c->upd.set_topo_gen[next] != c->upd.topo_gen) {
         a.copy_tail = true;
-        a.copy_from = (uint32_t)c->upd.tail_first(c->wide, c->upd.cur_set);
+        a.copy_from = (uint32_t)c->upd.tail_first(c->scene.wide, c->upd.cur_set);
         c->upd.set_topo_gen[next] = c->upd.topo_gen;
     }
-    a.n_tlas_records = (uint32_t)c->wide.tlas_nodes4.size();
+    a.n_tlas_records = (uint32_t)c->scene.wide.tlas_nodes4.size();
     a.order = c->upd.topo_rebuilt ? c->upd.d_tmpl_order.p : c->upd.d_tlas4_order.p;
     a.level_start = c->upd.topo_rebuilt ? c->upd.d_tmpl_levels.p : c->upd.d_tlas4_levels.p;
     a.n_levels = (uint32_t)c->upd.tlas4_levels_h.size() - 1u;
@@ -164,7 +148,7 @@ int queue_instance_refit(jpt_ctx* c, const float* dev_view, uint32_t n_instances
     return JPT_OK;
 }
 
-// The device moved ahead of the host's mirrors (c->ref, c->wide) and of the other kernels' arrays, until the next upload.  `boxes_mirrored`:
+// The device moved ahead of the host's mirrors (c->scene.ref, c->scene.wide) and of the other kernels' arrays, until the next upload.  `boxes_mirrored`:
 // the host's TLAS boxes were refitted along, so the sky cull (compute_sky_cull) may go on reading them.
 void device_ahead(jpt_ctx* c, bool boxes_mirrored)
 {
@@ -179,12 +163,12 @@ int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, 
 {
     if (const int rc = needs_scene(c, kNativeTree, call, " needs a scene made by jpt_scene_commit with the native builder"); rc != JPT_OK) return rc;
     if (!transforms12 && n_instances) return fail(c, JPT_E_INVALID, "null transforms");
-    if (n_instances != c->ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
+    if (n_instances != c->scene.ref.instances.size()) return fail(c, JPT_E_INVALID, "one transform per instance of the committed scene");
     if (const int rc = on_device(c, "host-only context: the refit runs on the device (jpt_scene_update_tlas is the host route)", false); rc != JPT_OK) return rc;
     // the host keeps the transforms (a later jpt_scene_update_tlas rebuilds from them); its arrays are stale from here on
-    for (uint32_t i = 0; i < n_instances; i++) (void)c->builder.set_instance_transform(i, transforms12 + (size_t)i * 12);
-    c->tlas_dirty = true;
-    if (!c->ds.use4 || !c->scene_ready) return jpt_scene_update_tlas(c);  // no four-child records to refit
+    for (uint32_t i = 0; i < n_instances; i++) (void)c->scene.builder.set_instance_transform(i, transforms12 + (size_t)i * 12);
+    c->scene.tlas_dirty = true;
+    if (!c->ds.use4 || !c->scene.device_ready) return jpt_scene_update_tlas(c);  // no four-child records to refit
     if (n_instances == 0) return JPT_OK;
     if (n_instances <= 1) rebuild = false;   // one instance is its own order
     if (rebuild && n_instances > kTlasRebuildMaxInstances)
@@ -202,7 +186,7 @@ int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, 
     if (mirror) {
         boxes.resize(n_instances);
         for (uint32_t i = 0; i < n_instances; i++) {
-            const RefBvhNode& root = c->ref.bvh_nodes[c->ref.instances[i].blas_index];
+            const RefBvhNode& root = c->scene.ref.bvh_nodes[c->scene.ref.instances[i].blas_index];
             instance_record(transforms12 + (size_t)i * 12, root.aabbMin, root.aabbMax, true, boxes[i]);
         }
     }
@@ -210,11 +194,9 @@ int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, 
     if (rebuild) {
         rc = ensure_tlas_template(c, n_instances);
         if (rc != JPT_OK) return rc;
-        const WideScene& w = c->wide;
+        const WideScene& w = c->scene.wide;
         const uint32_t need = w.stack_need4 - stack_need4_under(w.tlas_nodes4, w.tlas_root4) + c->upd.tmpl_stack_need;
-        if (need > trace_stack_capacity())
-            return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the TLAS rebuild: a traversal could need " + std::to_string(need) +
-                                            " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
+        if (need > trace_stack_capacity()) return too_deep(c, need, " after the TLAS rebuild");
         sorted.resize(n_instances);
         if (mirror) tlas_order_host(&boxes[0].aabbMin.x, &boxes[0].aabbMax.x, sizeof(RefInstance) / sizeof(float), n_instances, nullptr, sorted.data());
         else
@@ -238,7 +220,7 @@ int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, 
     // jpt_scene_commit.
     const bool mirrored = mirror && !c->upd.tlas4_levels_h.empty();
     if (mirrored) {
-        WideScene& w = c->wide;
+        WideScene& w = c->scene.wide;
         for (size_t l = 0; l + 1 < c->upd.tlas4_levels_h.size(); l++)
             for (uint32_t k = c->upd.tlas4_levels_h[l]; k < c->upd.tlas4_levels_h[l + 1]; k++)
                 refit_slots(w.tlas_nodes4[c->upd.tlas4_order_h[k]], w.tlas_nodes4.data(), [&](int32_t ref, float* lo, float* hi) {
@@ -248,7 +230,7 @@ int move_instances(jpt_ctx* c, const float* transforms12, uint32_t n_instances, 
                 });
     }
     device_ahead(c, mirrored);
-    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->stats.last_build_ms = ms_since(t0);
     return JPT_OK;
 }
 
@@ -259,8 +241,8 @@ int ensure_mesh_refit(jpt_ctx* c)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->upd.mesh_refit_ready) return JPT_OK;
-    const RefScene& r = c->ref;
-    const WideScene& w = c->wide;
+    const RefScene& r = c->scene.ref;
+    const WideScene& w = c->scene.wide;
     const size_t n_meshes = r.mesh_roots.size();
     if (r.mesh_tri_range.size() != 2 * n_meshes || r.tri_vidx.size() != 3 * r.tri_geom.size() || w.instances4.size() != r.instances.size())
         return fail(c, JPT_E_STATE, "the scene holds no vertex map for device updates: commit it again with JPT_BUILD_SAH_WATERTIGHT");
@@ -313,14 +295,14 @@ int ensure_mesh_refit(jpt_ctx* c)
 // stack need; JPT_E_LIMIT, before anything is written or reserved, when a traversal could then need more entries than the kernels
 // hold; then -- the host waits for the queued renders and refits, once per mesh -- the record arrays grown by the template's records
 // BEHIND the TLAS tails (every existing offset stays), the root word of the mesh's instances pointed at the region's record 0 in every
-// copy of the instance level and in c->wide.instances4, the template's child words, schedule and level starts uploaded, the sort's
+// copy of the instance level and in c->scene.wide.instances4, the template's child words, schedule and level starts uploaded, the sort's
 // working set sized, and mesh_refit[mesh_id] naming the region.  Later calls find all of it in place.
 int ensure_mesh_region(jpt_ctx* c, uint32_t mesh_id, const char* call)
 {
     SceneUpdates& u = c->upd;
     SceneUpdates::MeshRefit& mr = u.mesh_refit[mesh_id];
     if (mr.rebuilt) return u.mesh_regions.count(mesh_id) ? JPT_OK : fail(c, JPT_E_STATE, std::string(call) + ": the mesh's region left with its scene");
-    WideScene& w = c->wide;
+    WideScene& w = c->scene.wide;
     if (u.mesh_need.empty()) {
         std::vector<int32_t> roots(u.mesh_refit.size(), -1);   // (a leaf root, and a mesh without a tree: need 0)
         for (size_t m = 0; m < roots.size(); m++)
@@ -345,9 +327,7 @@ int ensure_mesh_region(jpt_ctx* c, uint32_t mesh_id, const char* call)
         if (m != mesh_id) blas_new = std::max(blas_new, u.mesh_need[m]);
     }
     const uint32_t need = w.stack_need4 - blas_old + blas_new;   // (stack_need4: the TLAS need + 1 + the largest mesh need)
-    if (need > trace_stack_capacity())
-        return fail(c, JPT_E_LIMIT, "acceleration structure too deep after the mesh rebuild: a traversal could need " + std::to_string(need) +
-                                        " stack entries, the kernels hold " + std::to_string(trace_stack_capacity()));
+    if (need > trace_stack_capacity()) return too_deep(c, need, " after the mesh rebuild");
     SceneBufs& b = c->dev;
     const size_t first = b.nodes4.n, total = first + t.n_records;
     if (b.nodesq.n != first || total > (size_t)0x7fffffff) return fail(c, JPT_E_LIMIT, std::string(call) + ": more records than a child word can name");
@@ -372,11 +352,11 @@ int ensure_mesh_region(jpt_ctx* c, uint32_t mesh_id, const char* call)
     }
     rc = ensure_instance_copies(c);
     if (rc != JPT_OK) return rc;
-    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    const uint32_t n_inst = (uint32_t)c->scene.ref.instances.size();
     for (int k = 0; k < kInstanceSets; k++) launch_mesh_root_words(s, b.set[k].winst4.p, b.set[0].inst.p, n_inst, mr.bvh_root, (int32_t)first);
     HIP_TRY(c, hipGetLastError());
     for (uint32_t i = 0; i < n_inst; i++)
-        if (c->ref.instances[i].blas_index == mr.bvh_root) w.instances4[i].root = (int32_t)first;
+        if (c->scene.ref.instances[i].blas_index == mr.bvh_root) w.instances4[i].root = (int32_t)first;
     for (uint32_t& r : order) r += (uint32_t)first;
     SceneUpdates::MeshRegion& rg = u.mesh_regions[mesh_id];
     HIP_TRY(c, rg.d_child.upload(t.child, s));
@@ -409,7 +389,7 @@ int check_mesh_arrays(jpt_ctx* c, const char* call, uint32_t mesh_id, const jpt_
                                "the scene was committed with JPT_BUILD_SAH: its reach records and tie shadow are the reference builder's "
                                "tree of the committed vertices (commit with JPT_BUILD_SAH_WATERTIGHT to deform meshes on the device)");
     if (rc != JPT_OK) return rc;
-    if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
+    if (mesh_id >= c->scene.builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
     if (n_surfaces < 0 || (n_surfaces && !surfaces)) return fail(c, JPT_E_INVALID, "bad surface array");
     sv.assign((size_t)n_surfaces, SurfaceView{});
     int with_vertices = 0;
@@ -423,7 +403,7 @@ int check_mesh_arrays(jpt_ctx* c, const char* call, uint32_t mesh_id, const jpt_
         }
         sv[(size_t)i] = SurfaceView{x.vertices, x.normals, nullptr, x.indices, x.n_vertices, x.n_indices};
     }
-    if (!c->builder.same_topology(mesh_id, sv.data(), n_surfaces)) return fail(c, JPT_E_INVALID, "topology changed: commit the scene again");
+    if (!c->scene.builder.same_topology(mesh_id, sv.data(), n_surfaces)) return fail(c, JPT_E_INVALID, "topology changed: commit the scene again");
     if (with_normals != 0 && with_normals != with_vertices) return fail(c, JPT_E_INVALID, "give normals for every surface of the mesh or for none");
     return JPT_OK;
 }
@@ -440,14 +420,14 @@ struct MeshStage {
 int stage_mesh_update(jpt_ctx* c, size_t t_off, size_t dev_bytes, MeshStage& st)
 {
     SceneUpdates& u = c->upd;
-    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    const uint32_t n_inst = (uint32_t)c->scene.ref.instances.size();
     HIP_TRY(c, u.mesh_stage.next(t_off + (size_t)n_inst * 12 * sizeof(float), st.index));
     if (!u.ev_mesh_drain) HIP_TRY(c, hipEventCreateWithFlags(&u.ev_mesh_drain, hipEventDisableTiming));
     st.h = u.mesh_stage.buf[st.index].as<char>();
     const int32_t keys[8] = {ordered_key(FLT_MAX), ordered_key(FLT_MAX), ordered_key(FLT_MAX),
                              ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), ordered_key(-FLT_MAX), 0, 0};
     std::memcpy(st.h, keys, sizeof keys);
-    for (uint32_t i = 0; i < n_inst; i++) std::memcpy(st.h + t_off + (size_t)i * 48, c->builder.instance_transform(i), 48);
+    for (uint32_t i = 0; i < n_inst; i++) std::memcpy(st.h + t_off + (size_t)i * 48, c->scene.builder.instance_transform(i), 48);
     if (u.d_mesh_in.n < dev_bytes) {
         HIP_TRY(c, hipStreamSynchronize(u.refit_stream));   // (an earlier update may still read the old buffer)
         HIP_TRY(c, u.d_mesh_in.resize(dev_bytes));
@@ -479,7 +459,7 @@ int queue_mesh_refit(jpt_ctx* c, uint32_t mesh_id, bool rebuild, const float* ve
         if (it == c->upd.mesh_regions.end()) return fail(c, JPT_E_STATE, "the mesh's region left with its scene");
         rg = &it->second;
     }
-    const uint32_t n_inst = (uint32_t)c->ref.instances.size();
+    const uint32_t n_inst = (uint32_t)c->scene.ref.instances.size();
     MeshRefitArgs a;
     a.bounds = reinterpret_cast<int32_t*>(c->upd.d_mesh_in.p);
     a.verts = verts;
@@ -497,7 +477,7 @@ int queue_mesh_refit(jpt_ctx* c, uint32_t mesh_id, bool rebuild, const float* ve
     a.root4 = mr.root4;
     a.bvh = b.bvh.p;
     a.bvh_root = mr.bvh_root;
-    const bool cuts = c->ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->ref.inst_cut_boxes.empty();
+    const bool cuts = c->scene.ref.inst_cut_range.size() == 2 * (size_t)n_inst && !c->scene.ref.inst_cut_boxes.empty();
     a.cut_range = cuts ? b.cut_range.p : nullptr;
     a.instances = b.set[0].inst.p;   // (blas_index is the same in every copy of the instance level)
     a.n_instances = n_inst;
@@ -523,7 +503,7 @@ int queue_mesh_refit(jpt_ctx* c, uint32_t mesh_id, bool rebuild, const float* ve
     if (rc != JPT_OK) return rc;
     HIP_TRY(c, hipEventRecord(c->upd.mesh_stage.copied[st.index], c->upd.refit_stream));
     device_ahead(c, false);   // the host's TLAS boxes are stale: no sky cull until the next upload
-    c->stats.last_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->stats.last_build_ms = ms_since(t0);
     return JPT_OK;
 }
 
@@ -566,7 +546,7 @@ int deform_mesh(jpt_ctx* c, uint32_t mesh_id, const jpt_surface* surfaces, int32
     if (!mr.has_tree) return JPT_OK;   // no instance names the mesh: the device holds nothing of it
     // staging: [6 ordered keys + pad: 32 B][vertices][normals][transforms]; the first three parts are copied to the device, the
     // instance refit reads the transforms from the pinned buffer
-    const size_t head = 32, vbytes = c->builder.mesh_vertex_count(mesh_id) * 3 * sizeof(float), nbytes = with_normals ? vbytes : 0, dev_bytes = head + vbytes + nbytes;
+    const size_t head = 32, vbytes = c->scene.builder.mesh_vertex_count(mesh_id) * 3 * sizeof(float), nbytes = with_normals ? vbytes : 0, dev_bytes = head + vbytes + nbytes;
     MeshStage st;
     rc = stage_mesh_update(c, dev_bytes, dev_bytes, st);
     if (rc != JPT_OK) return rc;
@@ -729,7 +709,7 @@ int jpt_debug_mesh_records(jpt_ctx* c, uint32_t mesh_id, void* nodes4_out, void*
 {
     if (!c || !info_out) return JPT_E_INVALID;
     if (const int rc = needs_scene(c, kWatertightTree, "jpt_debug_mesh_records", " needs a scene committed with JPT_BUILD_SAH_WATERTIGHT"); rc != JPT_OK) return rc;
-    if (mesh_id >= c->builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
+    if (mesh_id >= c->scene.builder.mesh_count()) return fail(c, JPT_E_INVALID, "no such mesh");
     int rc = on_device(c, "host-only context: the records are on the device", false);
     if (rc == JPT_OK) rc = ensure_mesh_refit(c);
     if (rc != JPT_OK) return rc;
@@ -754,8 +734,8 @@ int jpt_debug_tlas_records(jpt_ctx* c, void* nodes4_out, void* nodesq_out, uint3
 {
     if (const int rc = needs_scene(c, kNativeTree, "jpt_debug_tlas_records", " needs a scene made by jpt_scene_commit with the native builder"); rc != JPT_OK) return rc;
     if (const int rc = on_device(c, "host-only context: the records are on the device", true); rc != JPT_OK) return rc;
-    const size_t nt = c->wide.tlas_nodes4.size(), ni = c->ref.instances.size();
-    const int32_t base = (int32_t)c->upd.tail_first(c->wide, c->upd.cur_set);
+    const size_t nt = c->scene.wide.tlas_nodes4.size(), ni = c->scene.ref.instances.size();
+    const int32_t base = (int32_t)c->upd.tail_first(c->scene.wide, c->upd.cur_set);
     if (n_records) *n_records = (uint32_t)nt;
     if (root_out) *root_out = c->ds.tlas_root4 >= 0 ? c->ds.tlas_root4 - base : c->ds.tlas_root4;
     if ((nodes4_out || nodesq_out) && capacity < nt) return fail(c, JPT_E_INVALID, "record buffers too small");

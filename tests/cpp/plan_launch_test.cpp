@@ -29,7 +29,7 @@ jpt_ctx* context(int32_t w, int32_t rows, int32_t tree = JPT_TREE_NATIVE_REACH)
         std::fprintf(stderr, "jpt_create failed\n");
         std::exit(2);
     }
-    c->tree = tree;
+    c->scene.tree = tree;
     c->width = w;
     c->height = c->local_rows = rows;
     c->max_bounces = 4;
